@@ -3,6 +3,7 @@
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: starts its own N rank processes, see self_launch)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+  python bench.py --full ...                           (the headline line plus roofline and cpu_baseline, below)
 
 A "step" is one full render of the workload through the C ABI (HIP persistent path-trace
 kernel + chunk combine, output left in HBM) plus, for N > 1, the single RCCL gather of the
@@ -10,7 +11,16 @@ framebuffer to rank 0.  Workload = the configuration the metric is quoted on: th
 bunny.ply (69 451 triangles) in a closed room, 1920x1080, 1024 spp, rr 0.8 -- one frame,
 sharded by 8x8-pixel blocks over the N GPUs (total work fixed => "strong" scaling).
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+Prints ONE JSON line on rank 0 with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step =
+wall milliseconds of one timed step, the mean over --steps) and the workload's config.  A plain run does nothing else:
+set up, warm up, time the steps, dump the outputs if asked, print.
+
+  --dump-outputs DIR : after the timed steps, writes the frame the last timed step left on rank 0 (what a caller of the
+                       render call receives) as DIR/image.npy, float32 [H, W, 3].  Inputs are fixed by the arguments
+                       (scene, size, spp, seed, policy), so two builds can be compared output for output.  A frame over
+                       64 MB is written as a fixed sample instead: DIR/image_sample.npy (float32 [n, 3]) and the flat
+                       pixel indices it was taken at, DIR/image_sample_pixel.npy (float64 [n]).
+  --full             : also the figures that take runs or processes of their own, added to the same line:
   roofline     : what bounds the kernel is VALU issue at partial lane utilisation (and the memory
                  latency behind it), not HBM bandwidth, so the headline figure is
                    bound "valu": achieved = useful vector lane-operations per second
@@ -49,8 +59,12 @@ VALU_PEAK_TLANEOPS = 78.65  # same guide: 157.3 TFLOP/s f32 vector = 256 CUs x 1
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline (an untimed counters render) and, on one GPU, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/image.npy (float32; a fixed sample above 64 MB)")
     ap.add_argument("--scene", default="c3_bunny_room")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -66,7 +80,10 @@ def parse_args():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, meet over the process group (gloo on a machine without a GPU), print one line, exit: "
                          "exercises the launch path without rendering")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(args):
@@ -209,6 +226,93 @@ def pmc_stamp(workload_key):
     return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the assembled frame of the last timed step as float32 .npy; above DUMP_LIMIT_BYTES a fixed,
+    seeded sample of its pixels and the flat pixel indices of that sample."""
+    import numpy as np
+    img = np.ascontiguousarray(frame.cpu().numpy() if hasattr(frame, "cpu") else np.asarray(frame), dtype=np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+        return
+    pixels = img.reshape(-1, img.shape[-1])
+    n = DUMP_LIMIT_BYTES // 2 // pixels[0].nbytes
+    idx = np.sort(np.random.default_rng(20241016).choice(len(pixels), size=n, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), pixels[idx])
+    np.save(os.path.join(out_dir, "image_sample_pixel.npy"), idx.astype(np.float64))
+
+
+def roofline_figures(args, api, scene, torch, dev, stream, chunk, rank, world, paths_per_step, kernel_ms):
+    """--full: what bounds the timed kernel (the `roofline` entry; a dict on rank 0, None elsewhere).  Takes a render
+    of its own on every rank (the counters build), untimed."""
+    W, H = args.width, args.height
+    # algorithmic bytes per path from exact device counters (untimed counters build of the same
+    # kernel, same scene/seed/policy at reduced spp: the per-path averages are spp-independent)
+    cspp = args.chunk if args.policy == "chunk" else min(args.spp, 4)
+    cparams = api.Scene.params(W, H, cspp, args.seed, args.policy, chunk=chunk, counters=True, shard=(rank, world))
+    cfb = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+    cst = scene.render_device(cfb.data_ptr(), cparams, stream=stream, want_stats=True)
+    R = cst["rays"] / max(1, cst["paths"])
+    Vn = cst["node_tests"] / max(1, cst["rays"])
+    Vt = cst["tri_tests"] / max(1, cst["rays"])
+    Vp = cst["analytic_tests"] / max(1, cst["rays"])
+    bytes_per_path = R * (Vn * 32.0 + Vt * 36.0 + Vp * 32.0) + 12.0 / args.spp
+    # the analytic prologue's shape records are read once per workgroup into LDS and broadcast: they are not memory
+    # traffic in any physical sense.  Counting only divergent reads (tree nodes, triangles, analytic shapes IN the tree):
+    pro = scene.tree_info().get("prologue_prims", 0)
+    bytes_per_path_divergent = R * (Vn * 32.0 + Vt * 36.0 + max(0.0, Vp - pro) * 32.0) + 12.0 / args.spp
+    my_paths = paths_per_step / world  # per launch on this rank (blocks are dealt round-robin)
+    k_ms = sum(kernel_ms) / len(kernel_ms)
+    achieved = bytes_per_path * my_paths / (k_ms * 1e-3) / 1e9
+    # measured figures come from a separate rocprofv3 --pmc run of THIS step (the profiler cannot be attached from
+    # inside); they are quoted only while the stamp matches the kernel sources in the tree and the workload
+    workload_key = "%s %dx%d %dspp %s%d x%d" % (args.scene, W, H, args.spp, args.policy, args.chunk if args.policy == "chunk" else 0, world)
+    stamp = pmc_stamp(workload_key)
+    traffic = stamp.get("hbm_bytes_per_launch") if stamp else None
+    achieved_divergent = bytes_per_path_divergent * my_paths / (k_ms * 1e-3) / 1e9
+
+    if rank != 0:
+        return None
+    k_s = k_ms * 1e-3
+    hbm = {"achieved": achieved_divergent, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved_divergent / HBM_PEAK_GBS,
+           "bytes_per_path": bytes_per_path_divergent,
+           "what": "SURVEY 8d's algorithmic bytes from exact device counters, without the analytic prologue's records (wave-uniform reads "
+                   "served from the LDS tables), per launch / kernel time",
+           "measured_gbs": (traffic / k_s / 1e9) if traffic else None,
+           "measured_frac": (traffic / k_s / 1e9 / HBM_PEAK_GBS) if traffic else None,
+           "l2_hit_rate": stamp.get("l2_hit_rate") if stamp else None,
+           "contract_bytes_per_path": bytes_per_path, "contract_achieved": achieved, "contract_frac": achieved / HBM_PEAK_GBS,
+           "contract_note": "8d's formula as written prices the prologue's LDS-served records as HBM bytes: saturated, kept for continuity only"}
+    if stamp and stamp.get("counters", {}).get("SQ_INSTS_VALU"):
+        # useful vector lane-operations per second: wave-level VALU instructions of one launch (PMC) x 64 lanes x the
+        # fraction of lanes that were active in them, over the kernel time measured live
+        valu_insts = float(stamp["counters"]["SQ_INSTS_VALU"])
+        useful = valu_insts * 64.0 * float(stamp["lanes_active"]) / k_s / 1e12
+        roofline = {"bound": "valu", "achieved": useful, "peak": VALU_PEAK_TLANEOPS, "unit": "Tlane-op/s", "frac": useful / VALU_PEAK_TLANEOPS,
+                    "traffic": traffic, "valu_insts_per_launch": valu_insts, "lanes_active": stamp.get("lanes_active"),
+                    "valu_issue_frac": valu_insts / k_s / (VALU_PEAK_TLANEOPS * 1e12 / 64.0),
+                    "valu_issue_frac_at_stamp": stamp.get("valu_issue_frac"),
+                    "wave_cycles_waiting_on_memory": stamp.get("wave_cycles_waiting_on_memory"),
+                    "limiter": "VALU issue at partial lane utilisation (divergence) with memory latency behind it; not HBM bandwidth"}
+    else:
+        roofline = {"bound": "hbm", "achieved": achieved_divergent, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved_divergent / HBM_PEAK_GBS, "traffic": None, "lanes_active": None, "valu_issue_frac": None,
+                    "limiter": "no PMC stamp matches these kernel sources and this workload (profiles/*pmc_stamp*.json): "
+                               "falling back to the divergent algorithmic bytes against the HBM peak"}
+    roofline.update({
+        "hbm": hbm, "frac_divergent": achieved_divergent / HBM_PEAK_GBS,
+        "pmc_stamp": ({"file": stamp.get("file"), "kernel_hash": stamp["kernel_hash"], "git_commit": stamp.get("git_commit"),
+                       "source": stamp.get("source"), "workload_key": stamp.get("workload_key")} if stamp else None),
+        "kernel_hash": kernel_source_hash(), "workload_key": workload_key,
+        "kernel": "pt_persistent", "kernel_ms": k_ms,
+        "rays_per_path": R, "node_tests_per_ray": Vn, "tri_tests_per_ray": Vt,
+        "analytic_tests_per_ray": Vp, "prologue_tests_per_ray": pro, "fallback_rays": cst["fallback_rays"]})
+    return roofline
+
+
 def main():
     args = parse_args()
     rank = int(os.environ.get("RANK", "0"))
@@ -333,6 +437,8 @@ def main():
             fb = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
             params = api.Scene.params(W, H, args.spp, args.seed, args.policy, chunk=chunk, shard=(rank, world))
 
+    frame = [fb]  # what the last step handed rank 0: the assembled frame (--dump-outputs)
+
     def step(want_stats=False):
         if sharded is not None:
             st = sharded.render(params, stream=stream, want_stats=want_stats)
@@ -342,9 +448,9 @@ def main():
         if world > 1:
             if share_gpu:
                 torch.cuda.synchronize()
-                odist.gather_framebuffer(fb.cpu(), W, H, rank, world)
+                frame[0] = odist.gather_framebuffer(fb.cpu(), W, H, rank, world)
             else:
-                odist.gather_framebuffer(fb, W, H, rank, world)
+                frame[0] = odist.gather_framebuffer(fb, W, H, rank, world)
         return st
 
     def fence():
@@ -371,66 +477,11 @@ def main():
     paths_per_step = float(W) * H * args.spp
     value = paths_per_step / (ms_per_step * 1e-3) / 1e6
 
-    # algorithmic bytes per path from exact device counters (untimed counters build of the same
-    # kernel, same scene/seed/policy at reduced spp: the per-path averages are spp-independent)
-    cspp = args.chunk if args.policy == "chunk" else min(args.spp, 4)
-    cparams = api.Scene.params(W, H, cspp, args.seed, args.policy, chunk=chunk, counters=True, shard=(rank, world))
-    cfb = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
-    cst = scene.render_device(cfb.data_ptr(), cparams, stream=stream, want_stats=True)
-    R = cst["rays"] / max(1, cst["paths"])
-    Vn = cst["node_tests"] / max(1, cst["rays"])
-    Vt = cst["tri_tests"] / max(1, cst["rays"])
-    Vp = cst["analytic_tests"] / max(1, cst["rays"])
-    bytes_per_path = R * (Vn * 32.0 + Vt * 36.0 + Vp * 32.0) + 12.0 / args.spp
-    # the analytic prologue's shape records are read once per workgroup into LDS and broadcast: they are not memory
-    # traffic in any physical sense.  Counting only divergent reads (tree nodes, triangles, analytic shapes IN the tree):
-    pro = scene.tree_info().get("prologue_prims", 0)
-    bytes_per_path_divergent = R * (Vn * 32.0 + Vt * 36.0 + max(0.0, Vp - pro) * 32.0) + 12.0 / args.spp
-    my_paths = paths_per_step / world  # per launch on this rank (blocks are dealt round-robin)
-    k_ms = sum(kernel_ms) / len(kernel_ms)
-    achieved = bytes_per_path * my_paths / (k_ms * 1e-3) / 1e9
-    # measured figures come from a separate rocprofv3 --pmc run of THIS step (the profiler cannot be attached from
-    # inside); they are quoted only while the stamp matches the kernel sources in the tree and the workload
-    workload_key = "%s %dx%d %dspp %s%d x%d" % (args.scene, W, H, args.spp, args.policy, args.chunk if args.policy == "chunk" else 0, world)
-    stamp = pmc_stamp(workload_key)
-    traffic = stamp.get("hbm_bytes_per_launch") if stamp else None
-    achieved_divergent = bytes_per_path_divergent * my_paths / (k_ms * 1e-3) / 1e9
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame[0])
+    roofline = roofline_figures(args, api, scene, torch, dev, stream, chunk, rank, world, paths_per_step, kernel_ms) if args.full else None
 
     if rank == 0:
-        k_s = k_ms * 1e-3
-        hbm = {"achieved": achieved_divergent, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved_divergent / HBM_PEAK_GBS,
-               "bytes_per_path": bytes_per_path_divergent,
-               "what": "SURVEY 8d's algorithmic bytes from exact device counters, without the analytic prologue's records (wave-uniform reads "
-                       "served from the LDS tables), per launch / kernel time",
-               "measured_gbs": (traffic / k_s / 1e9) if traffic else None,
-               "measured_frac": (traffic / k_s / 1e9 / HBM_PEAK_GBS) if traffic else None,
-               "l2_hit_rate": stamp.get("l2_hit_rate") if stamp else None,
-               "contract_bytes_per_path": bytes_per_path, "contract_achieved": achieved, "contract_frac": achieved / HBM_PEAK_GBS,
-               "contract_note": "8d's formula as written prices the prologue's LDS-served records as HBM bytes: saturated, kept for continuity only"}
-        if stamp and stamp.get("counters", {}).get("SQ_INSTS_VALU"):
-            # useful vector lane-operations per second: wave-level VALU instructions of one launch (PMC) x 64 lanes x the
-            # fraction of lanes that were active in them, over the kernel time measured live
-            valu_insts = float(stamp["counters"]["SQ_INSTS_VALU"])
-            useful = valu_insts * 64.0 * float(stamp["lanes_active"]) / k_s / 1e12
-            roofline = {"bound": "valu", "achieved": useful, "peak": VALU_PEAK_TLANEOPS, "unit": "Tlane-op/s", "frac": useful / VALU_PEAK_TLANEOPS,
-                        "traffic": traffic, "valu_insts_per_launch": valu_insts, "lanes_active": stamp.get("lanes_active"),
-                        "valu_issue_frac": valu_insts / k_s / (VALU_PEAK_TLANEOPS * 1e12 / 64.0),
-                        "valu_issue_frac_at_stamp": stamp.get("valu_issue_frac"),
-                        "wave_cycles_waiting_on_memory": stamp.get("wave_cycles_waiting_on_memory"),
-                        "limiter": "VALU issue at partial lane utilisation (divergence) with memory latency behind it; not HBM bandwidth"}
-        else:
-            roofline = {"bound": "hbm", "achieved": achieved_divergent, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": achieved_divergent / HBM_PEAK_GBS, "traffic": None, "lanes_active": None, "valu_issue_frac": None,
-                        "limiter": "no PMC stamp matches these kernel sources and this workload (profiles/*pmc_stamp*.json): "
-                                   "falling back to the divergent algorithmic bytes against the HBM peak"}
-        roofline.update({
-            "hbm": hbm, "frac_divergent": achieved_divergent / HBM_PEAK_GBS,
-            "pmc_stamp": ({"file": stamp.get("file"), "kernel_hash": stamp["kernel_hash"], "git_commit": stamp.get("git_commit"),
-                           "source": stamp.get("source"), "workload_key": stamp.get("workload_key")} if stamp else None),
-            "kernel_hash": kernel_source_hash(), "workload_key": workload_key,
-            "kernel": "pt_persistent", "kernel_ms": k_ms,
-            "rays_per_path": R, "node_tests_per_ray": Vn, "tri_tests_per_ray": Vt,
-            "analytic_tests_per_ray": Vp, "prologue_tests_per_ray": pro, "fallback_rays": cst["fallback_rays"]})
         line = {
             "metric": "Mpaths/s", "value": value, "unit": "Mpaths/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
@@ -444,9 +495,10 @@ def main():
                        "width": W, "height": H, "spp": args.spp, "paths_per_step": paths_per_step, "gather": gather_impl,
                        "gather_fallback": bool(world > 1 and sharded is None),
                        "launch": launch_mode, "workspace_bytes_per_rank": api.workspace_bytes(params)},
-            "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line["roofline"] = roofline
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, scene_path)
         print(json.dumps(line), flush=True)
     if world > 1:

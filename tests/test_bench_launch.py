@@ -8,7 +8,10 @@ import subprocess
 import sys
 import time
 
-from conftest import ROOT
+import numpy as np
+import pytest
+
+from conftest import ROOT, assert_bits_equal
 
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -57,3 +60,49 @@ def test_torchrun_form_still_works():
     assert r.returncode == 0, r.stderr[-2000:]
     js = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(js) == 1 and js[0]["world"] == 2
+
+
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0"], timeout=60)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_dump_of_a_large_frame_is_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs above the size limit: the same seeded pixels every time, stored with their flat indices"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 12 * 100)
+    img = np.arange(30 * 20 * 3, dtype=np.float32).reshape(30, 20, 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), img)
+    assert sorted(os.listdir(tmp_path / "a")) == ["image_sample.npy", "image_sample_pixel.npy"]
+    sample = np.load(tmp_path / "a" / "image_sample.npy")
+    pixel = np.load(tmp_path / "a" / "image_sample_pixel.npy")
+    assert sample.dtype == np.float32 and pixel.dtype == np.float64 and len(sample) == len(pixel) == 50
+    np.testing.assert_array_equal(sample, img.reshape(-1, 3)[pixel.astype(np.int64)])
+    np.testing.assert_array_equal(pixel, np.load(tmp_path / "b" / "image_sample_pixel.npy"))
+    bench.dump_outputs(str(tmp_path / "c"), img[:2])  # within the limit: the whole frame
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "image.npy"), img[:2])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_rendered_frame(api, oracle, tmp_path):
+    """a plain run times the steps and writes the last step's frame, which is the render call's image bit for bit; the
+    roofline and the CPU baseline appear only with --full"""
+    w, h, spp, seed = 64, 40, 8, 7
+    size = ["--width", str(w), "--height", str(h), "--spp", str(spp), "--chunk", "4", "--seed", str(seed)]
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")] + size, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    js = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert js["steps"] == 2 and js["ms_per_step"] > 0 and js["metric"] == js["unit"] == "Mpaths/s"
+    assert "roofline" not in js and "cpu_baseline" not in js
+    got = np.load(tmp_path / "out" / "image.npy")
+    assert got.dtype == np.float32 and got.shape == (h, w, 3)
+    scene = api.Scene.load_scn(os.path.join(ROOT, "data", "c3_bunny_room.scn")).commit()
+    ref, _ = oracle.OracleScene(scene.flatten(w, h)).render(w, h, spp, seed, "chunk", chunk=4, threads=8)
+    assert_bits_equal(got, ref, "bench.py --dump-outputs vs the oracle")
+    r = _run(["--gpus", "1", "--steps", "1", "--warmup", "1", "--full", "--cpu-sample-spp", "4"] + size, env={"ORT_CPU_BASELINE_CORES": "1"},
+             timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    js = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert js["roofline"]["kernel_ms"] > 0 and js["cpu_baseline"]["value"] > 0

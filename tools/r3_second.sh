@@ -13,7 +13,7 @@ ORT_EXCHANGE=0 PROXY_WORLDS=1,8 timeout -k 10 300 python3 tools/scaling_proxy.py
 PROXY_WORLDS=1,8 timeout -k 10 300 python3 tools/scaling_proxy.py c4_dwarf_room 3840 2160 512 64 $O/proxy_c4.json > $O/proxy_c4.log 2>&1
 ORT_LPT=0 PROXY_WORLDS=1,8 timeout -k 10 300 python3 tools/scaling_proxy.py c4_dwarf_room 3840 2160 512 64 $O/proxy_c4_nolpt.json > $O/proxy_c4_nolpt.log 2>&1
 echo "proxies done" >> $O/progress.txt
-timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc $?" >> $O/progress.txt
+timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc $?" >> $O/progress.txt
 timeout -k 10 300 python3 tools/util_run.py c2_analytic 1920 1080 256 64 > $O/util_c2.log 2>&1
 timeout -k 10 300 python3 tools/util_run.py c5:708 3840 2160 64 64 > $O/util_c5.log 2>&1
 timeout -k 10 300 python3 tools/util_run.py c3_bunny_room 1920 1080 256 64 > $O/util_c3_plain.log 2>&1

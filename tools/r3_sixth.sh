@@ -11,11 +11,11 @@ ORT_DEBUG_DRAIN=1 ORT_DEBUG_FALLBACK=1 PROXY_REPS=1 PROXY_WORLDS=1,8 $P $O/p_dra
 ORT_LPT=0 ORT_DEBUG_DRAIN=1 ORT_DEBUG_FALLBACK=1 PROXY_REPS=1 PROXY_WORLDS=1,8 $P $O/p_drain_nolpt.json > $O/p_drain_nolpt.log 2>&1
 PROXY_WORLDS=1,2,4,8 $P $O/p_default.json > $O/p_default.log 2>&1
 echo "drain done" >> $O/progress.txt
-timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc $?" >> $O/progress.txt
-timeout -k 10 300 python3 bench.py --scene c2_analytic --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err
-ORT_LPT=0 timeout -k 10 300 python3 bench.py --scene c2_analytic --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c2_nolpt.json 2> $O/bench_c2_nolpt.err
-timeout -k 10 300 python3 bench.py --scene c4_dwarf_room --width 3840 --height 2160 --spp 512 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c4.json 2> $O/bench_c4.err
-timeout -k 10 300 python3 bench.py --scene c5_heightfield_708 --width 3840 --height 2160 --spp 256 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err
+timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc $?" >> $O/progress.txt
+timeout -k 10 300 python3 bench.py --full --scene c2_analytic --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err
+ORT_LPT=0 timeout -k 10 300 python3 bench.py --full --scene c2_analytic --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c2_nolpt.json 2> $O/bench_c2_nolpt.err
+timeout -k 10 300 python3 bench.py --full --scene c4_dwarf_room --width 3840 --height 2160 --spp 512 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c4.json 2> $O/bench_c4.err
+timeout -k 10 300 python3 bench.py --full --scene c5_heightfield_708 --width 3840 --height 2160 --spp 256 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err
 echo "benches done" >> $O/progress.txt
 timeout -k 10 300 python3 tools/util_run.py c3_bunny_room 1920 1080 1024 64 > $O/util_c3.log 2>&1
 ORT_EXCHANGE=0 timeout -k 10 300 python3 tools/util_run.py c3_bunny_room 1920 1080 256 64 > $O/util_c3_plain.log 2>&1
