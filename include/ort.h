@@ -233,6 +233,32 @@ int ort_render_image_device(ort_scene *scene, const ort_render_params *params, v
    block layout: a shard keeps 1/shard_count of a frame per chunk) */
 int ort_render_workspace_bytes(const ort_render_params *params, uint64_t *bytes);
 
+/* ---- closest-hit ray queries ----------------------------------------------------------
+ * Replaces raycast_top_most_node (reference code/ray.cpp:1165-1176): the closest hit of each of the caller's rays,
+ * bit for bit the reference's hit_t, hit_normal and hit_mat_index (ties in the reference's test order, phantom
+ * sphere hits and visibility chains included).  A miss is t = FLT_MAX, n = 0, mat = 0, prim = ORT_NO_PRIM.
+ * Rays: count x {o.xyz, d.xyz} f32, 24 B each; d need not be of unit length (the reference does not normalise it),
+ * zero components are allowed; non-finite origins or directions are outside the contract.  hits[i] answers rays[i];
+ * results do not depend on count, order or how the batch is sliced.
+ * prim = kind << 28 | index: index is the shape's position in the scene's own arrays (the get_spheres / get_boxes /
+ * get_cylinders order), for triangles the mesh-major triangle id (triangles of the earlier meshes, then the
+ * triangle within its mesh, index_count / 3 per mesh).
+ * flags: ORT_RENDER_COUNTERS fills the work counters of stats (rays, node / triangle / analytic tests); stats (may be
+ * NULL) always gets fallback_rays and kernel_ms, paths = 0.
+ * Both pointers must be 8-byte aligned.  Errors are reported before any device work: ORT_ERR_INVALID (null or
+ * misaligned pointer with count > 0), ORT_ERR_STATE (scene not committed), ORT_ERR_NO_DEVICE (not uploaded);
+ * count == 0 returns ORT_OK without a launch. */
+typedef struct { float t; ort_v3 n; uint32_t mat; uint32_t prim; } ort_hit; /* 24 B */
+enum { ORT_HIT_TRIANGLE = 0, ORT_HIT_BOX = 2, ORT_HIT_CYLINDER = 3, ORT_HIT_SPHERE = 4 };
+#define ORT_NO_PRIM 0xffffffffu
+
+/* host rays in, host hits out; synchronous (staged through device buffers kept per scene, in bounded slices) */
+int ort_raycast(ort_scene *scene, const float *rays, uint64_t count, ort_hit *hits, uint32_t flags, ort_stats *stats);
+/* DEVICE rays and hits on the scene's device (e.g. torch tensors' data_ptr); enqueued on hip_stream (NULL = the
+   default stream), returns without waiting unless stats != NULL -- as the device form of the render call */
+int ort_raycast_device(ort_scene *scene, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags,
+                       void *hip_stream, ort_stats *stats);
+
 /* ---- multi-GPU: block sharding and the one collective -------------------------------------
  * Replaces main()'s shared-memory tile pool (macos_main.mm:565-671: eight pthreads, one queue, one framebuffer)
  * across the GPUs of a node: scene replicated, 8x8 blocks dealt round-robin, every rank renders its blocks into a

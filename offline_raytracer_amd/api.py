@@ -21,6 +21,8 @@ POLICIES = {"tile32": POLICY_TILE32, "whole": POLICY_WHOLE, "pixel": POLICY_PIXE
 RENDER_COUNTERS = 1
 RENDER_PACKED = 2
 COMM_ID_BYTES = 128
+HIT_TRIANGLE, HIT_BOX, HIT_CYLINDER, HIT_SPHERE = 0, 2, 3, 4
+NO_PRIM = 0xFFFFFFFF
 
 
 class OrtError(RuntimeError):
@@ -95,6 +97,15 @@ class Camera(C.Structure):
     _fields_ = [("p", V3), ("x_axis", V3), ("y_axis", V3), ("z_axis", V3)]
 
 
+class Hit(C.Structure):
+    """ort_hit: the closest hit of one ray (raycast_top_most_node's hit_t, hit_normal, hit_mat_index) and its shape."""
+    _fields_ = [("t", C.c_float), ("n", V3), ("mat", C.c_uint32), ("prim", C.c_uint32)]
+
+
+HIT_DTYPE = np.dtype([("t", "<f4"), ("n", "<f4", 3), ("mat", "<u4"), ("prim", "<u4")])
+assert HIT_DTYPE.itemsize == C.sizeof(Hit) == 24
+
+
 # every symbol include/ort.h declares
 EXPORTS = [
     "ort_last_error", "ort_abi_version", "ort_scene_load_scn", "ort_scene_parse_scn", "ort_scene_create",
@@ -105,7 +116,7 @@ EXPORTS = [
     "ort_render_workspace_bytes", "ort_unit_eval_device", "ort_rgbe", "ort_write_hdr",
     "ort_shard_block_count", "ort_pack_blocks_host", "ort_unpack_blocks_host", "ort_unpack_blocks_device",
     "ort_comm_unique_id", "ort_comm_create", "ort_comm_create_local", "ort_comm_destroy", "ort_gather_framebuffer",
-    "ort_gather_framebuffer_local"]
+    "ort_gather_framebuffer_local", "ort_raycast", "ort_raycast_device"]
 
 _lib = None
 
@@ -168,6 +179,9 @@ def lib():
                                               C.POINTER(Stats)]
         L.ort_render_workspace_bytes.argtypes = [C.POINTER(RenderParams), C.POINTER(C.c_uint64)]
         L.ort_unit_eval_device.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.ort_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
+        L.ort_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                         C.POINTER(Stats)]
         L.ort_rgbe.restype = C.c_uint32
         L.ort_rgbe.argtypes = [C.c_float, C.c_float, C.c_float]
         L.ort_write_hdr.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]
@@ -349,6 +363,47 @@ class Scene:
                                              C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
+    # -- closest-hit ray queries -----------------------------------------------------------
+    def raycast(self, rays, counters=False):
+        """Closest hit of each ray (raycast_top_most_node, ray.cpp:1165).  rays: (N, 6) float32 o.xyz d.xyz (d need
+        not be unit length).  Returns (hits: HIT_DTYPE[N], stats dict); synchronous."""
+        rays = np.ascontiguousarray(rays, dtype="<f4")
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must be an (N, 6) array of o.xyz d.xyz, got shape %s" % (rays.shape,))
+        hits = np.zeros(len(rays), HIT_DTYPE)
+        st = Stats()
+        _check(lib().ort_raycast(self.handle, rays.ctypes.data, len(rays), hits.ctypes.data,
+                                 RENDER_COUNTERS if counters else 0, C.byref(st)))
+        return hits, st.as_dict()
+
+    def raycast_device(self, d_rays_ptr, count, d_hits_ptr, stream=None, counters=False, want_stats=False):
+        """Device rays (count x 6 float32) -> device hits (count x 24 B, HIT_DTYPE), raw pointers on the scene's device,
+        e.g. torch tensors' data_ptr().  Enqueued on stream; waits only when want_stats (returns the stats dict)."""
+        st = Stats() if want_stats else None
+        _check(lib().ort_raycast_device(self.handle, C.c_void_p(d_rays_ptr), count, C.c_void_p(d_hits_ptr),
+                                        RENDER_COUNTERS if counters else 0, C.c_void_p(stream) if stream else None,
+                                        C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def triangle_of(self, index):
+        """mesh-major triangle id (decode_prim of a triangle hit) -> (mesh, triangle within that mesh).  Accepts arrays."""
+        first = getattr(self, "_tri_first", None)
+        if first is None:
+            counts = []
+            for i in range(self.info().mesh_count):
+                m = Mesh()
+                _check(lib().ort_scene_get_mesh(self.handle, i, C.byref(m)))
+                counts.append(m.index_count // 3)
+            first = self._tri_first = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        idx = np.asarray(index, dtype=np.int64)
+        if (idx < 0).any() or (idx >= first[-1]).any():
+            raise IndexError("triangle id out of range (the scene has %d triangles)" % first[-1])
+        mesh = np.searchsorted(first, idx, side="right") - 1
+        local = idx - first[mesh]
+        if np.ndim(index) == 0:
+            return int(mesh), int(local)
+        return mesh, local
+
     def tiled_raytrace(self, out, x0, y0, x1, y1, rng_state, spp, rr=0.8):
         """Exact analogue of one reference call (ray.cpp:1178); returns (shape_tests, new_rng_state)."""
         height, width = out.shape[:2]
@@ -366,6 +421,18 @@ class Scene:
         _check(lib().ort_tiled_raytrace_batch(self.handle, out.ctypes.data, width, height, jobs.ctypes.data, len(jobs),
                                               rr, finals.ctypes.data, C.byref(st)))
         return finals, st.as_dict()
+
+
+def decode_prim(prim):
+    """ort_hit.prim -> (kind, index): kind is HIT_TRIANGLE / HIT_BOX / HIT_CYLINDER / HIT_SPHERE, index the shape's
+    position in the scene's own arrays (triangles: mesh-major id, see Scene.triangle_of).  A miss (NO_PRIM) gives
+    (None, None); arrays give int64 arrays, -1 for misses."""
+    if np.ndim(prim) == 0:
+        p = int(prim)
+        return (None, None) if p == NO_PRIM else (p >> 28, p & 0x0FFFFFFF)
+    p = np.asarray(prim, dtype=np.uint32).astype(np.int64)
+    miss = p == NO_PRIM
+    return np.where(miss, -1, p >> 28), np.where(miss, -1, p & 0x0FFFFFFF)
 
 
 def unit_eval_device(records, device=0):

@@ -362,6 +362,40 @@ static int ort_unit_eval_device_impl(int device, const void *records, uint32_t c
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
+/* ray queries: argument and state errors first, so that they are the same on a machine without a device */
+static int check_raycast(const ort_scene *s, const void *rays, uint64_t count, const void *hits) {
+    if (!s) return fail(ORT_ERR_INVALID, "null scene");
+    if (count && (!rays || !hits)) return fail(ORT_ERR_INVALID, "null rays or hits");
+    if (count && (((uintptr_t)rays | (uintptr_t)hits) & 7u)) return fail(ORT_ERR_INVALID, "rays and hits must be 8-byte aligned");
+    if (!s->tree.built) return fail(ORT_ERR_STATE, "ort_scene_commit has not been called");
+    if (!s->dev) return fail(ORT_ERR_NO_DEVICE, "scene is not resident on a HIP device: call ort_scene_upload (no CPU fallback)");
+    return ORT_OK;
+}
+
+static int ort_raycast_impl(ort_scene *s, const float *rays, uint64_t count, ort_hit *hits, uint32_t flags, ort_stats *stats) {
+    int rc = check_raycast(s, rays, count, hits);
+    if (rc != ORT_OK) return rc;
+    if (count == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return ORT_OK;
+    }
+    std::string err;
+    rc = ort::device_raycast(s, rays, nullptr, count, hits, nullptr, flags, nullptr, stats, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
+static int ort_raycast_device_impl(ort_scene *s, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags, void *hip_stream, ort_stats *stats) {
+    int rc = check_raycast(s, d_rays, count, d_hits);
+    if (rc != ORT_OK) return rc;
+    if (count == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return ORT_OK;
+    }
+    std::string err;
+    rc = ort::device_raycast(s, nullptr, d_rays, count, nullptr, d_hits, flags, hip_stream, stats, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
 static int ort_render_workspace_bytes_impl(const ort_render_params *p, uint64_t *bytes) {
     if (!p || !bytes) return fail(ORT_ERR_INVALID, "null argument");
     *bytes = ort::render_workspace_bytes(p);
@@ -453,6 +487,8 @@ int ort_tiled_raytrace(ort_scene *s, float *out_rgb, int32_t width, int32_t heig
 int ort_render_image(ort_scene *s, const ort_render_params *p, float *out_rgb, ort_stats *stats) { return guarded([&]() { return ort_render_image_impl(s, p, out_rgb, stats); }); }
 int ort_render_image_device(ort_scene *s, const ort_render_params *p, void *d_out_rgb, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_render_image_device_impl(s, p, d_out_rgb, hip_stream, stats); }); }
 int ort_unit_eval_device(int device, const void *records, uint32_t count, float *out) { return guarded([&]() { return ort_unit_eval_device_impl(device, records, count, out); }); }
+int ort_raycast(ort_scene *s, const float *rays, uint64_t count, ort_hit *hits, uint32_t flags, ort_stats *stats) { return guarded([&]() { return ort_raycast_impl(s, rays, count, hits, flags, stats); }); }
+int ort_raycast_device(ort_scene *s, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_raycast_device_impl(s, d_rays, count, d_hits, flags, hip_stream, stats); }); }
 int ort_render_workspace_bytes(const ort_render_params *p, uint64_t *bytes) { return guarded([&]() { return ort_render_workspace_bytes_impl(p, bytes); }); }
 int ort_shard_block_count(int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, uint64_t *blocks) { return guarded([&]() { return ort_shard_block_count_impl(width, height, shard_index, shard_count, blocks); }); }
 int ort_pack_blocks_host(const float *full_rgb, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, float *packed) { return guarded([&]() { return ort_pack_blocks_host_impl(full_rgb, width, height, shard_index, shard_count, packed); }); }

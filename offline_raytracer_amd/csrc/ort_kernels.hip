@@ -107,6 +107,11 @@ struct DeviceScene {
     void *wf_mem = nullptr; /* wavefront state, carved into the WfView arrays */
     size_t wf_bytes = 0;
     unsigned long long *h_active = nullptr; /* pinned */
+    /* ray queries (device_raycast): the shape table, built at the first query on this upload, and the host path's staging */
+    void *prim_src = nullptr;
+    float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0}; /* shapes and camera (raycast_needs_exact) */
+    void *ray_in = nullptr, *hit_out = nullptr;
+    size_t ray_in_bytes = 0, hit_out_bytes = 0;
 };
 
 /* ---- host side --------------------------------------------------------------------------- */
@@ -140,7 +145,8 @@ void device_release(Scene *scene) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     void *ptrs[] = {d->nodes, d->nodes4, d->tris, d->spheres, d->boxes, d->cyls, d->prim_info,
-                    d->materials, d->light_is_sphere, d->tab, d->cold, d->rv_dev, d->ref_nodes, d->ref_recs, d->chain_boxes, d->tri_order, d->sphere_order, d->box_order, d->cyl_order, d->bfs_pool, d->bfs_locks, d->ctrl, d->partial, d->staging, d->jobs, d->states};
+                    d->materials, d->light_is_sphere, d->tab, d->cold, d->rv_dev, d->ref_nodes, d->ref_recs, d->chain_boxes, d->tri_order, d->sphere_order, d->box_order, d->cyl_order, d->bfs_pool, d->bfs_locks, d->ctrl, d->partial, d->staging, d->jobs, d->states,
+                    d->prim_src, d->ray_in, d->hit_out};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (d->wf_mem) (void)hipFree(d->wf_mem);
@@ -371,32 +377,20 @@ static int launch_wavefront(DeviceScene *d, const SceneView &sv, const RenderVie
     return ORT_OK;
 }
 
-int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *jobs, uint32_t job_count, void *d_out,
-                  float *h_out, void *stream_v, uint32_t *final_states, ort_stats *stats, std::string *err) {
-    DeviceScene *d = scene->dev;
-    if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
-    ORT_HIP(hipSetDevice(d->device));
-    hipStream_t stream = (hipStream_t)stream_v;
-    const bool packed_out = (p->flags & ORT_RENDER_PACKED) != 0 && !jobs;
-    const size_t image_bytes = packed_out ? (size_t)block_grid_for(p).my_blocks * 768u : (size_t)p->width * (size_t)p->height * 12u;
-    int rc;
-    /* One render at a time per scene: the job counter, the work counters, the partial planes and the stashes belong
-       to the scene.  A render that was returned from without waiting is waited for here, and its tripwire checked. */
-    if (d->inflight) {
-        ORT_HIP(hipEventSynchronize(d->ev_done));
-        d->inflight = false;
-        unsigned long long ovf = 0;
-        ORT_HIP(hipMemcpy(&ovf, d->ctrl + 7, sizeof(ovf), hipMemcpyDeviceToHost));
-        if (ovf) { *err = "the previous render on this scene overflowed a reference-order fallback queue"; return ORT_ERR_UNSUPPORTED; }
-    }
+/* a render or ray query that was returned from without waiting: waited for, and its tripwire checked (one call at a time
+   per scene: the job counter and the work counters in ctrl, and the RenderView in rv_dev, belong to the scene) */
+static int settle_inflight(DeviceScene *d, std::string *err) {
+    if (!d->inflight) return ORT_OK;
+    ORT_HIP(hipEventSynchronize(d->ev_done));
+    d->inflight = false;
+    unsigned long long ovf = 0;
+    ORT_HIP(hipMemcpy(&ovf, d->ctrl + 7, sizeof(ovf), hipMemcpyDeviceToHost));
+    if (ovf) { *err = "the previous render on this scene overflowed a reference-order fallback queue"; return ORT_ERR_UNSUPPORTED; }
+    return ORT_OK;
+}
 
-    float *out = (float *)d_out;
-    if (!out) {
-        if ((rc = ensure((void **)&d->staging, &d->staging_bytes, image_bytes, err))) return rc;
-        out = d->staging;
-        if (h_out) ORT_HIP(hipMemcpyAsync(out, h_out, image_bytes, hipMemcpyHostToDevice, stream));
-    }
-
+/* the scene as every kernel sees it (camera and diagnostics are the render's to add); re-reads the knobs under ORT_KNOBS_LIVE */
+static SceneView scene_view(Scene *scene, DeviceScene *d) {
     SceneView sv{};
     sv.nodes = (const float4 *)d->nodes; sv.tris = (const float4 *)d->tris;
     sv.spheres = (const float4 *)d->spheres; sv.boxes = (const float4 *)d->boxes; sv.cyls = (const float4 *)d->cyls;
@@ -412,9 +406,33 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
     sv.pro_cyls = scene->tree.pro_cyls;
     sv.chain_boxes = (const float4 *)d->chain_boxes;
     if (getenv("ORT_KNOBS_LIVE")) { const int keep = d->knobs.blocks_per_cu; d->knobs = read_knobs(); d->knobs.blocks_per_cu = keep; }
-    const Knobs &kn = d->knobs;
-    sv.force_fallback_mask = kn.force_fallback_mask;
+    sv.force_fallback_mask = d->knobs.force_fallback_mask;
     sv.cold = (const ORT_CONSTANT_AS SceneCold *)d->cold;
+    return sv;
+}
+
+int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *jobs, uint32_t job_count, void *d_out,
+                  float *h_out, void *stream_v, uint32_t *final_states, ort_stats *stats, std::string *err) {
+    DeviceScene *d = scene->dev;
+    if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
+    ORT_HIP(hipSetDevice(d->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    const bool packed_out = (p->flags & ORT_RENDER_PACKED) != 0 && !jobs;
+    const size_t image_bytes = packed_out ? (size_t)block_grid_for(p).my_blocks * 768u : (size_t)p->width * (size_t)p->height * 12u;
+    int rc;
+    /* One render at a time per scene: the job counter, the work counters, the partial planes and the stashes belong
+       to the scene.  A render that was returned from without waiting is waited for here, and its tripwire checked. */
+    if ((rc = settle_inflight(d, err))) return rc;
+
+    float *out = (float *)d_out;
+    if (!out) {
+        if ((rc = ensure((void **)&d->staging, &d->staging_bytes, image_bytes, err))) return rc;
+        out = d->staging;
+        if (h_out) ORT_HIP(hipMemcpyAsync(out, h_out, image_bytes, hipMemcpyHostToDevice, stream));
+    }
+
+    SceneView sv = scene_view(scene, d);
+    const Knobs &kn = d->knobs;
     const bool want_util = kn.debug_util; /* developer diagnostics, counters build only */
     sv.util = want_util ? d->ctrl + 8 : nullptr;
     ort_camera cam;
@@ -696,6 +714,144 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
     return ORT_OK;
 }
 
+/* ---- closest-hit ray queries (ort_raycast*) ------------------------------------------------------------------------ */
+/* Fixed by a measured sweep (profiles/r04_raycast_tuning.md); the -D forms exist for such sweeps (tools/build_variant.sh) */
+#ifndef ORT_RAYCAST_REFILL
+#define ORT_RAYCAST_REFILL 32 /* leave the traversal loop, and start new rays, when fewer lanes than this are still tracing */
+#endif
+#ifndef ORT_RAYCAST_BATCH
+#define ORT_RAYCAST_BATCH 1024 /* ray indices a wave draws per atomic */
+#endif
+#ifndef ORT_RAYCAST_TAIL
+#define ORT_RAYCAST_TAIL 4 /* ... until this many rays per lane are left: then exactly as many as it needs */
+#endif
+constexpr uint64_t kRaycastSlice = 1ull << 22; /* rays per launch of the host form (2 x 96 MB of staging) */
+
+/* the inverse of the tree's slot maps, in PrimInfo order (triangles | boxes | cylinders | spheres): slot -> kind << 28 |
+   the shape's index in the scene's own arrays.  Built and uploaded at the first query, so that render-only users pay nothing */
+static int ensure_prim_src(Scene *scene, DeviceScene *d, std::string *err) {
+    if (d->prim_src) return ORT_OK;
+    const Tree &t = scene->tree;
+    std::vector<uint32_t> src((size_t)d->info_sphere + t.spheres.size(), kNoPrim);
+    bool bijective = src.size() == t.tri_slot.size() + t.box_slot.size() + t.cyl_slot.size() + t.sphere_slot.size();
+    auto invert = [&](uint32_t kind, uint32_t base, const std::vector<uint32_t> &slot, size_t slots) {
+        bijective = bijective && slot.size() == slots;
+        for (size_t i = 0; i < slot.size() && bijective; ++i) {
+            bijective = slot[i] < slots && src[base + slot[i]] == kNoPrim && i < 0x10000000u;
+            if (bijective) src[base + slot[i]] = (kind << 28) | (uint32_t)i;
+        }
+    };
+    invert(PRIM_TRI, 0u, t.tri_slot, t.tris.size());
+    invert(PRIM_BOX, d->info_box, t.box_slot, t.boxes.size());
+    invert(PRIM_CYL, d->info_cyl, t.cyl_slot, t.cyls.size());
+    invert(PRIM_SPHERE, d->info_sphere, t.sphere_slot, t.spheres.size());
+    for (uint32_t v : src) bijective = bijective && v != kNoPrim;
+    if (!bijective) { *err = "internal: the tree's slot maps are not a bijection onto its shape arrays"; return ORT_ERR_INTERNAL; }
+    /* the box of everything ort_tree.cpp sized the quadric boxes for: shapes and camera */
+    float lo[3] = {scene->camera_p.x, scene->camera_p.y, scene->camera_p.z}, hi[3] = {lo[0], lo[1], lo[2]};
+    auto grow = [&](float x, float y, float z, float r) {
+        const float p[3] = {x, y, z};
+        for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], p[k] - r); hi[k] = std::max(hi[k], p[k] + r); }
+    };
+    for (const ort_sphere &q : scene->spheres) grow(q.center.x, q.center.y, q.center.z, fabsf(q.r));
+    for (const ort_box &q : scene->boxes) { grow(q.min.x, q.min.y, q.min.z, 0.0f); grow(q.max.x, q.max.y, q.max.z, 0.0f); }
+    for (const ort_cylinder &q : scene->cylinders) {
+        grow(q.base.x, q.base.y, q.base.z, fabsf(q.r));
+        grow(q.base.x + q.axis.x, q.base.y + q.axis.y, q.base.z + q.axis.z, fabsf(q.r));
+    }
+    for (const HostMesh &m : scene->meshes)
+        for (size_t i = 0; i + 2 < m.vertices.size(); i += 3) grow(m.vertices[i], m.vertices[i + 1], m.vertices[i + 2], 0.0f);
+    memcpy(d->scene_lo, lo, sizeof(lo));
+    memcpy(d->scene_hi, hi, sizeof(hi));
+    return upload_vec(src, &d->prim_src, err);
+}
+
+/* one launch over count rays at d_rays -> d_hits (device pointers); stats (may be NULL): synchronous, counters added */
+static int launch_raycast(Scene *scene, DeviceScene *d, const void *d_rays, uint64_t count, void *d_hits, bool counters, hipStream_t stream,
+                          ort_stats *stats, std::string *err) {
+    int rc;
+    if ((rc = settle_inflight(d, err))) return rc;
+    const SceneView sv = scene_view(scene, d);
+    RaycastIO io;
+    io.rays = (const float2 *)d_rays;
+    io.hits = (uint2 *)d_hits;
+    io.prim_src = (const uint32_t *)d->prim_src;
+    io.tree_spheres = scene->tree.spheres.size() > scene->tree.pro_spheres;
+    io.tree_quadrics = io.tree_spheres || scene->tree.cyls.size() > scene->tree.pro_cyls;
+    memcpy(io.lo, d->scene_lo, sizeof(io.lo));
+    memcpy(io.hi, d->scene_hi, sizeof(io.hi));
+    unsigned int grid = (unsigned int)((count + kBlock - 1) / kBlock);
+    if (grid > d->max_blocks) grid = d->max_blocks;
+    const unsigned long long lanes = (unsigned long long)grid * kBlock;
+    RenderView rv{};
+    rv.job_count = count;
+    rv.next_job = d->ctrl;
+    rv.counters = d->ctrl + 1;
+    rv.job_batch = ORT_RAYCAST_BATCH;
+    rv.batch_until = count > ORT_RAYCAST_TAIL * lanes ? count - ORT_RAYCAST_TAIL * lanes : 0ull;
+    const size_t fast_tree_bytes = scene->tree.nodes.size() * sizeof(DevNode) + scene->tree.tris.size() * sizeof(DevTri);
+    rv.refill_below = ORT_RAYCAST_REFILL;
+    rv.descend_below = fast_tree_bytes <= (size_t)(16u << 20) ? 8 : 16; /* as the renders (device_render) */
+    ORT_HIP(hipMemsetAsync(d->ctrl, 0, 128 * sizeof(unsigned long long), stream));
+    ORT_HIP(hipMemcpyAsync(d->rv_dev, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
+    RenderHot hot{};
+    hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
+    hot.c = (const ORT_CONSTANT_AS RenderView *)d->rv_dev;
+    const bool tabs = (d->tab_flags & TAB_PRO) != 0;
+    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
+    if (counters) {
+        if (tabs) hipLaunchKernelGGL((raycast_rays<true, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+        else hipLaunchKernelGGL((raycast_rays<true, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+    } else {
+        if (tabs) hipLaunchKernelGGL((raycast_rays<false, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+        else hipLaunchKernelGGL((raycast_rays<false, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+    }
+    ORT_HIP(hipGetLastError());
+    if (stats) ORT_HIP(hipEventRecord(d->ev1, stream));
+    ORT_HIP(hipEventRecord(d->ev_done, stream));
+    d->inflight = true;
+    if (stats) {
+        if ((rc = settle_inflight(d, err))) return rc;
+        float ms = 0;
+        ORT_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+        unsigned long long c[6];
+        ORT_HIP(hipMemcpy(c, d->ctrl + 1, sizeof(c), hipMemcpyDeviceToHost));
+        stats->kernel_ms += ms;
+        stats->fallback_rays += c[5];
+        if (counters) { stats->rays += c[1]; stats->node_tests += c[2]; stats->tri_tests += c[3]; stats->analytic_tests += c[4]; }
+    }
+    return ORT_OK;
+}
+
+int device_raycast(Scene *scene, const float *h_rays, const void *d_rays, uint64_t count, ort_hit *h_hits, void *d_hits, uint32_t flags,
+                   void *stream_v, ort_stats *stats, std::string *err) {
+    static_assert(sizeof(ort_hit) == 24, "ort_hit is three 8-byte words");
+    DeviceScene *d = scene->dev;
+    if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
+    ORT_HIP(hipSetDevice(d->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    int rc;
+    if ((rc = ensure_prim_src(scene, d, err))) return rc;
+    const bool counters = (flags & ORT_RENDER_COUNTERS) != 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!h_rays) return launch_raycast(scene, d, d_rays, count, d_hits, counters, stream, stats, err);
+    /* host form: bounded slices through the scene's staging buffers; every ray is answered on its own, so the slicing
+       cannot change a result */
+    const uint64_t slice = count < kRaycastSlice ? count : kRaycastSlice;
+    if ((rc = ensure(&d->ray_in, &d->ray_in_bytes, (size_t)slice * 24u, err))) return rc;
+    if ((rc = ensure(&d->hit_out, &d->hit_out_bytes, (size_t)slice * sizeof(ort_hit), err))) return rc;
+    for (uint64_t at = 0; at < count; at += slice) {
+        const uint64_t n = count - at < slice ? count - at : slice;
+        if ((rc = settle_inflight(d, err))) return rc; /* the staging buffers are the previous slice's until it is done */
+        ORT_HIP(hipMemcpyAsync(d->ray_in, h_rays + 6u * at, (size_t)n * 24u, hipMemcpyHostToDevice, stream));
+        if ((rc = launch_raycast(scene, d, d->ray_in, n, d->hit_out, counters, stream, stats, err))) return rc;
+        ORT_HIP(hipMemcpyAsync(h_hits + at, d->hit_out, (size_t)n * sizeof(ort_hit), hipMemcpyDeviceToHost, stream));
+        ORT_HIP(hipStreamSynchronize(stream));
+    }
+    return settle_inflight(d, err);
+}
+
 } // namespace ort
+
 
 #endif /* !ORT_HOST_SIM */

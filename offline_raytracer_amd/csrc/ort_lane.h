@@ -1952,6 +1952,95 @@ __global__ void combine_chunks(RenderHot rv) {
     combine_pixel(rv, idx);
 }
 
+/* ---- closest-hit ray queries (ort_raycast): raycast_top_most_node, ray.cpp:1165-1176 --------------------------------
+ * The path-trace loop without shading: a lane without a ray takes the next ray index from its wave's batch (draw_job:
+ * the job space is the ray array, job_count rays), starts it (begin_ray: analytic prologue from the LDS tables),
+ * traverses with refill_below -- so the finished lanes of a wave fetch new rays while the rest are still in the tree --
+ * and, once the ray is finished, resolves its hit to the reference's answer (resolve_hit: chains, ties, phantoms, the
+ * exact fallback) and writes the record, the normal normalised as raycast_bvh returns it.  A wave's ray indices are contiguous, so its 24-byte loads and stores
+ * coalesce; both are done as three 8-byte accesses (the host checks the alignment). */
+struct RaycastIO {
+    const float2 *rays;        /* count x 3: o.x o.y | o.z d.x | d.y d.z */
+    uint2 *hits;               /* count x 3: t n.x | n.y n.z | mat prim (ort_hit) */
+    const uint32_t *prim_src;  /* info_index order -> kind << 28 | the shape's index in the scene's own arrays */
+    /* The fast tree's quadric boxes hold every hit the reference's intersectors can report for the rays a render casts
+       (ort_tree.cpp): unit directions, origins within the scene's box (shapes and camera).  A caller's ray need not be
+       either.  A sphere's tangent branch (|b^2 - a c| < 1e-5, ray.cpp:174) widens as 1e-5 / |d|^2 when |d| < 1 -- a
+       "hit" far outside the sphere's box -- and the f32 cancellation of both quadrics grows with the origin's distance.
+       Such rays take the exact walk of the reference octree instead (resolve_hit: a phantom that could win). */
+    uint32_t tree_spheres;     /* the fast tree holds spheres (those of the analytic prologue are tested outright) */
+    uint32_t tree_quadrics;    /* ... spheres or cylinders */
+    float lo[3], hi[3];        /* the scene's box as ort_tree.cpp sized the quadric boxes for */
+};
+
+ORT_D bool raycast_needs_exact(const RaycastIO &io, V3 org, V3 dir) {
+    const bool short_dir = io.tree_spheres && !(len2(dir) >= 0.999f);
+    const bool far = io.tree_quadrics && !(org.x >= io.lo[0] && org.x <= io.hi[0] && org.y >= io.lo[1] && org.y <= io.hi[1] &&
+                                          org.z >= io.lo[2] && org.z <= io.hi[2]);
+    return short_dir || far;
+}
+
+template <bool COUNTERS, bool TABS>
+ORT_D void raycast_lane(const SceneView &sv, const RenderHot &rv, const RaycastIO &io, const float4 *tab, uint32_t *lds_stack, const int tid,
+                        const uint32_t lane_id, unsigned long long *pool) {
+    uint32_t spill[kSpillStack];
+    PathState P;
+    HitState h;
+    Trav T;
+    Counters c;
+    Prof pr;
+    unsigned long long ray = 0;
+    bool tracing = false, held = false, more = true; /* held: this lane's ray is finished but its hit is not written yet */
+    for (;;) {
+        if (!tracing) {
+            if (held) {
+                resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+                const uint32_t src = h.hit_prim != kNoPrim ? io.prim_src[info_index(sv, h.hit_prim)] : kNoPrim;
+                const V3 n = normalize(h.hit_n); /* ray.cpp:817: the normal leaves raycast_bvh normalised (a miss's stays 0) */
+                uint2 *o = io.hits + 3ull * ray;
+                o[0] = make_uint2(om_f32_bits(h.best_t), om_f32_bits(n.x));
+                o[1] = make_uint2(om_f32_bits(n.y), om_f32_bits(n.z));
+                o[2] = make_uint2(h.hit_mat, src);
+                held = false;
+            }
+            if (more) {
+                const unsigned long long j = pool ? draw_job(rv, pool) : ORT_NEXT_JOB(rv.c->next_job);
+                if (j < rv.c->job_count) {
+                    const float2 *r = io.rays + 3ull * j;
+                    const float2 a = r[0], b = r[1], e = r[2];
+                    P.org = mk(a.x, a.y, b.x);
+                    P.dir = mk(b.y, e.x, e.y);
+                    ray = j;
+                    begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
+                    if (ORT_RARE(raycast_needs_exact(io, P.org, P.dir))) {
+                        T.cur = kTraversalDone; /* no fast traversal: resolve_hit re-casts it exactly (a phantom that could win) */
+                        h.phantom_t = 0.0f;
+                    }
+                    if (COUNTERS) c.rays++;
+                    tracing = held = true;
+                } else {
+                    more = false;
+                }
+            }
+        }
+        /* a lane that is not tracing now has no ray and will get none */
+        if (ORT_BALLOT(tracing) == 0ull) break;
+        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS, true>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+    }
+    flush_counters(rv, c, COUNTERS);
+}
+
+/* TABS: the prologue shapes fit their LDS slot (every scene of this repository); otherwise they are read from HBM */
+template <bool COUNTERS, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+raycast_rays(SceneView sv, RenderHot rv, RaycastIO io) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* per wave: the unissued part of its last batch of ray indices (draw_job) */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    if (TABS) fill_tab(sv, lds_tab);
+    raycast_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+}
+
 #endif /* !ORT_W5_TU */
 #endif /* !ORT_HOST_SIM */
 

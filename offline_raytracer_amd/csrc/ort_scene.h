@@ -193,6 +193,9 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
 uint64_t render_workspace_bytes(const ort_render_params *p);
 int device_unit_eval(int device, const void *records, uint32_t n, float *out, std::string *err);
 uint64_t shard_block_count(const ort_render_params *p);
+/* closest-hit queries: host rays / hits (h_*, synchronous) or device ones (d_*, enqueued on stream) */
+int device_raycast(Scene *scene, const float *h_rays, const void *d_rays, uint64_t count, ort_hit *h_hits, void *d_hits, uint32_t flags,
+                   void *stream, ort_stats *stats, std::string *err);
 /* ort_comm.cpp */
 struct Comm;
 uint64_t comm_shard_blocks(int32_t w, int32_t h, uint32_t index, uint32_t count);

@@ -1,0 +1,62 @@
+"""Developer script: compare the machine code of the kernels of two device-assembly files, kernel by kernel.
+
+Make the two files from two trees (same flags as the Makefile, device side only), e.g. for the four-waves unit:
+  hipcc -std=c++17 -O3 -fPIC -ffp-contract=off -fno-math-errno --offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt \
+        --cuda-device-only -S -x hip offline_raytracer_amd/csrc/ort_kernels.hip -o before.s
+(the five-waves unit ort_kernels_w5.hip with -mllvm -disable-machine-licm as well).  Then
+  python3 tools/isa_diff.py before.s after.s [name filter regex]
+prints, per kernel symbol present in both, whether its instructions are identical.  Local labels are renumbered by
+their order inside the function (a kernel added before another shifts the function numbers in .LBB<f>_<n>);
+comments and assembler directives are ignored.  Exit status 1 if any common kernel differs."""
+import re
+import sys
+
+DEFAULT = r"pt_persistent|wf_|combine_chunks|unit_eval"
+
+
+def functions(path):
+    out, cur, body = {}, None, []
+    for line in open(path):
+        m = re.match(r"^([A-Za-z_.$][\w.$]*):\s*(;.*)?$", line)
+        if m and not m.group(1).startswith(".L"):
+            cur, body = m.group(1), []
+            continue
+        if cur is None:
+            continue
+        if line.startswith(".Lfunc_end"):
+            out[cur] = body
+            cur = None
+            continue
+        s = line.split(";")[0].strip()
+        if not s or (s.startswith(".") and not s.startswith(".LBB") and ":" not in s):
+            continue  # directives (.p2align, .loc, ...) and comments
+        body.append(s)
+    return out
+
+
+def normalised(body):
+    names = {}
+
+    def ren(m):
+        return names.setdefault(m.group(0), ".L%d" % len(names))
+    return [re.sub(r"\.LBB\d+_\d+|\.Ltmp\d+", ren, s) for s in body]
+
+
+def main():
+    a, b = functions(sys.argv[1]), functions(sys.argv[2])
+    pat = re.compile(sys.argv[3] if len(sys.argv) > 3 else DEFAULT)
+    common = sorted(k for k in a if k in b and pat.search(k))
+    differ = 0
+    for k in common:
+        same = normalised(a[k]) == normalised(b[k])
+        differ += not same
+        print("%-9s %6d instr  %s" % ("identical" if same else "DIFFERS", len(a[k]), k))
+    only = sorted(k for k in set(a) ^ set(b) if pat.search(k))
+    for k in only:
+        print("only in %s: %s" % ("before" if k in a else "after", k))
+    print("%d kernels compared, %d differ" % (len(common), differ))
+    sys.exit(1 if differ else 0)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Developer script: registers / spills / scratch of every path-trace kernel variant (hipcc -Rpass-analysis=kernel-resource-usage).
+# Developer script: registers / spills / scratch of every path-trace and ray-query kernel variant (hipcc -Rpass-analysis=kernel-resource-usage).
 # usage: tools/kernel_resources.sh [extra hipcc flags]
 cd "$(dirname "$0")/../offline_raytracer_amd/csrc"
 /opt/rocm/bin/hipcc -std=c++17 -O3 -fPIC -ffp-contract=off -fno-math-errno --offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt \
@@ -13,7 +13,7 @@ for line in sys.stdin:
     m = re.search(r"remark: +(\w[^:]*): (\S+)", line)
     if m and cur: rows[cur][m.group(1).strip()] = m.group(2)
 for k, v in rows.items():
-    if "pt_persistent" not in k and "wf_" not in k: continue
-    name = k.replace("_ZN3ort", "").replace("EvNS_9SceneViewENS_9RenderHotE", "")
+    if "pt_persistent" not in k and "wf_" not in k and "raycast_rays" not in k: continue
+    name = k.replace("_ZN3ort", "").replace("EvNS_9SceneViewENS_9RenderHotE", "").replace("NS_9RaycastIOE", "")
     print(name, " ".join("%s=%s" % (a, b) for a, b in v.items()))
 '
