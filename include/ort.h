@@ -304,7 +304,18 @@ int ort_gather_framebuffer_local(ort_comm **comms, int world, const void *const 
  * 10 normalize math.h:298-310   in v                         out v.xyz
  * 11 fresnel/ggx/geometry ray.cpp:825-897 in Ks l_dot_h N H rough w     out F.xyz D G
  * 12 rng       random.h:5-53    in seed(bits) job(bits)      out step(bits) rng_01 rng_between(0,2pi) state(bits) job_seed(bits)
- * 13 IEEE ops                   in a b c                     out a/b sqrt(a) a*b a+b a-b (f32)bits(a) a*b+c */
+ * 13 IEEE ops                   in a b c                     out a/b sqrt(a) a*b a+b a-b (f32)bits(a) a*b+c
+ * Ops 14-19 run the specialised forms the render and raycast kernels call in place of the functions above, composed
+ * as those kernels compose them; each must give its generic function's answer (diagnostics for the parity tests):
+ * 14 aab forms  (op 3's inputs, 1/d as op 3)                 out hit_aab_finite t n.xyz, hit_aab_t_finite t, hit_aab_t t
+ *               (the _finite forms only for finite o and 1/d: all_finite6)
+ * 15 pdf_eval_scattering in N wi wo Kd Ks Kt ior rough dist rr      out p f.xyz (f = 0 unless p > 1e-6)
+ * 16 diffuse pdf/eval    (op 15's inputs)                    out pdf_brdf<true> * rr, eval_scattering<true> f.xyz
+ *               (only for materials with |Ks|^2, |Kt|^2, ps_c, pt_c all 0)
+ * 17 BSDF sample as the all-lobes kernels draw it (op 5's inputs and outputs): sample_brdf_draw, ort_sincosf of phi,
+ *               sample_brdf_finish<NORMALIZED = false>, normalize
+ * 18 the same as the diffuse kernels draw it (sample_brdf_draw<true>, sample_brdf_finish<false, true>; diffuse materials)
+ * 19 sincos     in x                                         out ort_sincosf of x: sin cos */
 int ort_unit_eval_device(int device, const void *records, uint32_t count, float *out);
 
 /* ---- output ------------------------------------------------------------------------

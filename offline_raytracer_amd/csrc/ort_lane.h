@@ -1782,6 +1782,111 @@ ORT_D void combine_pixel(const RenderHot &rv, unsigned long long idx) {
     o[0] = acc.x; o[1] = acc.y; o[2] = acc.z;
 }
 
+/* one record of the parity tests' per-function evaluation (unit_eval on the device, tools/host_sim --unit on the host):
+   op and in[24] -> out[8], op codes and layouts as documented in include/ort.h (ort_unit_eval_device).  Ops 1-13 call
+   the reference-shaped functions; ops 14 and up call the specialised forms the render and raycast kernels run instead,
+   composed as those kernels compose them, so that each can be held against the generic function's answer. */
+ORT_D void unit_eval_op(uint32_t op, const float *a, float *o) {
+    for (int k = 0; k < 8; ++k) o[k] = 0.0f;
+    auto in3 = [&](int k) { return mk(a[k], a[k + 1], a[k + 2]); };
+    V3 n3 = mk(0, 0, 0);
+    switch (op) {
+    case 1: {
+        V3 v0 = in3(0), e1 = sub(in3(3), v0), e2 = sub(in3(6), v0);
+        float t = hit_triangle(v0, e1, e2, in3(9), in3(12));
+        o[0] = t;
+        if (t >= 0.0f) { V3 c = cross(e1, e2); o[1] = c.x; o[2] = c.y; o[3] = c.z; }
+    } break;
+    case 2: { bool tg; float t = hit_sphere(in3(0), a[3], in3(4), in3(7), n3, tg); o[0] = t; o[1] = n3.x; o[2] = n3.y; o[3] = n3.z; } break;
+    case 3: { V3 dd = in3(9); float t = hit_aab(in3(0), in3(3), in3(6), mk(1.0f / dd.x, 1.0f / dd.y, 1.0f / dd.z), n3); o[0] = t; o[1] = n3.x; o[2] = n3.y; o[3] = n3.z; } break;
+    case 4: {
+        /* host-precomputed frame arrives in a[13..22]: rot rows (9) + |axis| */
+        float t = hit_cylinder(in3(0), a[6], in3(13), in3(16), in3(19), a[22], in3(7), in3(10), n3);
+        o[0] = t; o[1] = n3.x; o[2] = n3.y; o[3] = n3.z;
+    } break;
+    case 5: {
+        uint32_t seed = om_f32_bits(a[0]);
+        Mat m = make_mat(in3(8), in3(11), in3(14), a[17]);
+        bool tr;
+        V3 wi = sample_brdf(seed, in3(1), in3(4), a[7], m, tr);
+        o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = tr ? 1.0f : 0.0f; o[4] = om_bits_f32(seed);
+    } break;
+    case 6: {
+        Mat m = make_mat(in3(10), in3(13), in3(16), a[19]);
+        o[0] = pdf_brdf(in3(0), in3(3), in3(6), a[9], m);
+    } break;
+    case 7: {
+        Mat m = make_mat(in3(9), in3(12), in3(15), a[18]);
+        V3 f = eval_scattering(in3(0), in3(3), in3(6), m, a[19], a[20]);
+        o[0] = f.x; o[1] = f.y; o[2] = f.z;
+    } break;
+    case 8: { V3 r = sample_lobe(in3(0), a[3], a[4]); o[0] = r.x; o[1] = r.y; o[2] = r.z; } break;
+    case 9:
+        o[0] = ort_sinf(a[0]); o[1] = ort_cosf(a[0]); o[2] = ort_atan2f(a[1], a[0]); o[3] = ort_powf(a[0], a[1]); o[4] = ort_logf(a[0]);
+        break;
+    case 10: { V3 r = normalize(in3(0)); o[0] = r.x; o[1] = r.y; o[2] = r.z; } break;
+    case 11: {
+        V3 F = fresnel(in3(0), a[3]);
+        o[0] = F.x; o[1] = F.y; o[2] = F.z;
+        o[3] = ggx_d(in3(4), in3(7), a[10]);
+        o[4] = geom(in3(11), in3(4), in3(7), a[10]);
+    } break;
+    case 12: { /* RNG: seed -> state after one step, rng_01, rng_between(0, 2pi) from the same seed */
+        uint32_t s0 = om_f32_bits(a[0]), s1 = s0, s2 = s0;
+        rng_step(s0);
+        o[0] = om_bits_f32(s0);
+        o[1] = rng_01(s1);
+        o[2] = rng_between(s2, 0.0f, 2 * kPi);
+        o[3] = om_bits_f32(s2);
+        o[4] = om_bits_f32(job_seed(om_f32_bits(a[0]), om_f32_bits(a[1])));
+    } break;
+    case 13: { /* raw IEEE f32 arithmetic: the bit-exactness premise (div, sqrt, mul, add, sub, u32->f32) */
+        o[0] = a[0] / a[1]; o[1] = __builtin_sqrtf(a[0]); o[2] = a[0] * a[1]; o[3] = a[0] + a[1]; o[4] = a[0] - a[1];
+        o[5] = (float)om_f32_bits(a[0]); o[6] = a[0] * a[1] + a[2];
+    } break;
+    case 14: { /* the box forms of the fast paths (op 3's inputs): test_prim<FINITE_RAY> and the analytic prologue; node admission */
+        V3 dd = in3(9), inv = mk(1.0f / dd.x, 1.0f / dd.y, 1.0f / dd.z);
+        float t = hit_aab_finite(in3(0), in3(3), in3(6), inv, n3);
+        o[0] = t; o[1] = n3.x; o[2] = n3.y; o[3] = n3.z;
+        o[4] = hit_aab_t_finite(in3(0), in3(3), in3(6), inv);
+        o[5] = hit_aab_t(in3(0), in3(3), in3(6), inv);
+    } break;
+    case 15: { /* pdf_eval_scattering, as produce_ray's all-lobes flavour calls it: f stays 0 unless p > 1e-6 */
+        Mat m = make_mat(in3(9), in3(12), in3(15), a[18]);
+        V3 f = mk(0, 0, 0);
+        o[0] = pdf_eval_scattering(in3(0), in3(3), in3(6), m, a[19], a[20], a[21], f);
+        o[1] = f.x; o[2] = f.y; o[3] = f.z;
+    } break;
+    case 16: { /* the diffuse flavour's pdf and BSDF (op 15's inputs; only for materials the upload guard calls diffuse) */
+        Mat m = make_mat(in3(9), in3(12), in3(15), a[18]);
+        o[0] = pdf_brdf<true>(in3(0), in3(3), in3(6), a[19], m) * a[21];
+        V3 f = eval_scattering<true>(in3(0), in3(3), in3(6), m, a[19], a[20]);
+        o[1] = f.x; o[2] = f.y; o[3] = f.z;
+    } break;
+    case 17: case 18: { /* produce_ray's BSDF sample (op 5's inputs): 17 the all-lobes flavour, 18 the diffuse one */
+        uint32_t seed = om_f32_bits(a[0]);
+        Mat m = make_mat(in3(8), in3(11), in3(14), a[17]);
+        const V3 n = in3(1), wo = in3(4);
+        bool tr = false;
+        float sn, cs;
+        V3 wi;
+        if (op == 17) {
+            BrdfDraw draw = sample_brdf_draw<false>(seed, a[7], m);
+            ort_sincosf(draw.phi, &sn, &cs);
+            wi = normalize(sample_brdf_finish<false>(n, normalize(n), wo, m, draw, cs, sn, tr));
+        } else {
+            BrdfDraw draw = sample_brdf_draw<true>(seed, a[7], m);
+            ort_sincosf(draw.phi, &sn, &cs);
+            const V3 unit1 = normalize(n);
+            wi = normalize(sample_brdf_finish<false, true>(n, unit1, wo, m, draw, cs, sn, tr));
+        }
+        o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = tr ? 1.0f : 0.0f; o[4] = om_bits_f32(seed);
+    } break;
+    case 19: { float sn, cs; ort_sincosf(a[0], &sn, &cs); o[0] = sn; o[1] = cs; } break;
+    default: break;
+    }
+}
+
 #ifndef ORT_HOST_SIM
 #ifndef ORT_WAVES_PER_EU
 #define ORT_WAVES_PER_EU 4 /* VGPR budget: 4 waves/SIMD = 128 registers, 7 (diffuse flavour) / 26 (general) spilled; tuned on MI355X: profiles/r01_tuning.md */
@@ -1881,68 +1986,10 @@ __global__ void unit_eval(const uint32_t *records, uint32_t n, float *out) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t *rec = records + 25u * i;
-    uint32_t op = rec[0];
     float a[24];
     for (int k = 0; k < 24; ++k) a[k] = om_bits_f32(rec[1 + k]);
-    float o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto in3 = [&](int k) { return mk(a[k], a[k + 1], a[k + 2]); };
-    V3 n3 = mk(0, 0, 0);
-    switch (op) {
-    case 1: {
-        V3 v0 = in3(0), e1 = sub(in3(3), v0), e2 = sub(in3(6), v0);
-        float t = hit_triangle(v0, e1, e2, in3(9), in3(12));
-        o[0] = t;
-        if (t >= 0.0f) { V3 c = cross(e1, e2); o[1] = c.x; o[2] = c.y; o[3] = c.z; }
-    } break;
-    case 2: { bool tg; float t = hit_sphere(in3(0), a[3], in3(4), in3(7), n3, tg); o[0] = t; o[1] = n3.x; o[2] = n3.y; o[3] = n3.z; } break;
-    case 3: { V3 dd = in3(9); float t = hit_aab(in3(0), in3(3), in3(6), mk(1.0f / dd.x, 1.0f / dd.y, 1.0f / dd.z), n3); o[0] = t; o[1] = n3.x; o[2] = n3.y; o[3] = n3.z; } break;
-    case 4: {
-        /* host-precomputed frame arrives in a[13..22]: rot rows (9) + |axis| */
-        float t = hit_cylinder(in3(0), a[6], in3(13), in3(16), in3(19), a[22], in3(7), in3(10), n3);
-        o[0] = t; o[1] = n3.x; o[2] = n3.y; o[3] = n3.z;
-    } break;
-    case 5: {
-        uint32_t seed = om_f32_bits(a[0]);
-        Mat m = make_mat(in3(8), in3(11), in3(14), a[17]);
-        bool tr;
-        V3 wi = sample_brdf(seed, in3(1), in3(4), a[7], m, tr);
-        o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = tr ? 1.0f : 0.0f; o[4] = om_bits_f32(seed);
-    } break;
-    case 6: {
-        Mat m = make_mat(in3(10), in3(13), in3(16), a[19]);
-        o[0] = pdf_brdf(in3(0), in3(3), in3(6), a[9], m);
-    } break;
-    case 7: {
-        Mat m = make_mat(in3(9), in3(12), in3(15), a[18]);
-        V3 f = eval_scattering(in3(0), in3(3), in3(6), m, a[19], a[20]);
-        o[0] = f.x; o[1] = f.y; o[2] = f.z;
-    } break;
-    case 8: { V3 r = sample_lobe(in3(0), a[3], a[4]); o[0] = r.x; o[1] = r.y; o[2] = r.z; } break;
-    case 9:
-        o[0] = ort_sinf(a[0]); o[1] = ort_cosf(a[0]); o[2] = ort_atan2f(a[1], a[0]); o[3] = ort_powf(a[0], a[1]); o[4] = ort_logf(a[0]);
-        break;
-    case 10: { V3 r = normalize(in3(0)); o[0] = r.x; o[1] = r.y; o[2] = r.z; } break;
-    case 11: {
-        V3 F = fresnel(in3(0), a[3]);
-        o[0] = F.x; o[1] = F.y; o[2] = F.z;
-        o[3] = ggx_d(in3(4), in3(7), a[10]);
-        o[4] = geom(in3(11), in3(4), in3(7), a[10]);
-    } break;
-    case 12: { /* RNG: seed -> state after one step, rng_01, rng_between(0, 2pi) from the same seed */
-        uint32_t s0 = om_f32_bits(a[0]), s1 = s0, s2 = s0;
-        rng_step(s0);
-        o[0] = om_bits_f32(s0);
-        o[1] = rng_01(s1);
-        o[2] = rng_between(s2, 0.0f, 2 * kPi);
-        o[3] = om_bits_f32(s2);
-        o[4] = om_bits_f32(job_seed(om_f32_bits(a[0]), om_f32_bits(a[1])));
-    } break;
-    case 13: { /* raw IEEE f32 arithmetic: the bit-exactness premise (div, sqrt, mul, add, sub, u32->f32) */
-        o[0] = a[0] / a[1]; o[1] = __builtin_sqrtf(a[0]); o[2] = a[0] * a[1]; o[3] = a[0] + a[1]; o[4] = a[0] - a[1];
-        o[5] = (float)om_f32_bits(a[0]); o[6] = a[0] * a[1] + a[2];
-    } break;
-    default: break;
-    }
+    float o[8];
+    unit_eval_op(rec[0], a, o);
     for (int k = 0; k < 8; ++k) out[8u * i + k] = o[k];
 }
 

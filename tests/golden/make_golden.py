@@ -9,7 +9,7 @@ What is committed is data only: inputs and the reference's outputs.
   ref_det   = reference + deterministic libm (oracle/det_math.h)  -> bit-exact anchor
   ref_glibc = reference + glibc libm, "as shipped" on this box     -> distance report
 
-usage: python tests/golden/make_golden.py
+usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges]
 """
 import json
 import os
@@ -211,7 +211,20 @@ def golden_showcase():
                         rows=np.array([300, 332]), cols=np.array([560, 624]), rgbe=np.ascontiguousarray(px[300:332, 560:624]))
 
 
+def golden_unit_edges():
+    """the corner sets of tests/unit_cases.py for ops 1-11 through the reference (ref_det) -> unit_edges.npz"""
+    import unit_cases  # noqa: E402  (tests/ is on the path)
+    recs = np.concatenate([unit_cases.records(op, unit_cases.corners(op)) for op in range(1, 12)])
+    recs.tofile(os.path.join(TMP, "edges_in.bin"))
+    run(REF_DET, "unit", os.path.join(TMP, "edges_in.bin"), os.path.join(TMP, "edges_det.bin"))
+    np.savez_compressed(os.path.join(HERE, "unit_edges.npz"), records=recs,
+                        ref_det=ref_io.read_unit_output(os.path.join(TMP, "edges_det.bin")))
+
+
 def main():
+    if "--only-unit-edges" in sys.argv:  # add / refresh unit_edges.npz without touching the others
+        golden_unit_edges()
+        return
     if "--only-showcase" in sys.argv:
         golden_showcase()
         return
@@ -331,6 +344,7 @@ def main():
 
     golden_c5(manifest)
     golden_showcase()
+    golden_unit_edges()
 
     # cross-check values recorded by the survey, re-measured here on ref_glibc
     js = run(REF_GLIBC, "render", DATA + "testscene.scn", DATA, 64, 64, 4, 12345, "whole", os.path.join(TMP, "x.f32"))

@@ -236,3 +236,184 @@ def test_renders_unchanged_by_raycasts(api, oracle):
     ref, _ = oracle.OracleScene(scene.flatten(W, H)).render(W, H, 8, 99, "chunk", chunk=4, threads=4)
     assert_bits_equal(after, ref, "render after raycasts vs oracle")
     scene.close()
+
+
+# ---- rays at the exact walk's thresholds (raycast_needs_exact, ort_lane.h) -------------------------------------------
+# raycast_needs_exact sends a ray to the exact octree walk when |d|^2 < 0.999 with spheres in the fast tree, or when its
+# origin lies outside the scene box with quadrics in it.  Rays with |d|^2 in [0.999, 1) stay in the fast tree, whose
+# sphere boxes (ort_tree.cpp) must then hold every tangent-band "hit" (|b^2 - a c| < 1e-5: a band that widens as
+# 1e-5 / |d|^2), and rays from exactly the scene box's faces count as inside.
+LEN2 = [np.float32(0.998), np.nextafter(np.float32(0.999), np.float32(0)), np.float32(0.999),
+        np.nextafter(np.float32(0.999), np.float32(2)), np.float32(0.9995), np.float32(1 - 2.0 ** -24), np.float32(1),
+        np.float32(1.01)]
+
+
+def _threshold_scene(api, small):
+    """small = False: a room (six slabs), 30 spheres (r 0, 1e-3, 2e-3 and 0.05 among them) and four cylinders;
+    small = True: a handful of the same shapes within a box of diagonal < 1, so that the boxes' scene-size slack is
+    at its least"""
+    rng = np.random.default_rng(424242 + small)
+    mats = np.zeros(4, api.MATERIAL_DTYPE)
+    mats["diffuse"][1] = (0.7, 0.7, 0.7)
+    mats["specular"][2, :3] = 1
+    mats["transmission"][3] = 1; mats["ior"][1:] = (1.0, 1.0, 1.4)
+    tiny = [0.0, 1e-3, 2e-3, 0.05]
+    if small:
+        sph = np.zeros(8, api.SPHERE_DTYPE)
+        for i in range(8):
+            sph[i] = (rng.uniform(0.1, 0.4, 3), tiny[i % 4] if i < 6 else 0.03, 1 + i % 3)
+        cyl = np.zeros(2, api.CYLINDER_DTYPE)
+        cyl[0] = ((0.05, 0.05, 0.05), (0, 0, 0.3), 0.02, 1)
+        cyl[1] = ((0.45, 0.1, 0.2), (-0.1, 0.2, 0.05), 1e-3, 2)
+        box = np.zeros(1, api.BOX_DTYPE)
+        box[0] = ((0.2, 0.3, 0.0), (0.3, 0.35, 0.08), 1)
+        cam = (0.25, 0.0, 0.25)
+    else:
+        sph = np.zeros(30, api.SPHERE_DTYPE)
+        for i in range(30):
+            r = tiny[i % 4] if i < 16 else rng.uniform(0.1, 0.8)
+            sph[i] = (rng.uniform(-3, 3, 3) * (1, 1, 0) + (0, 0, rng.uniform(0.3, 4)), r, 1 + i % 3)
+        cyl = np.zeros(4, api.CYLINDER_DTYPE)
+        for i in range(4):
+            cyl[i] = (rng.uniform(-2.5, 2.5, 3) * (1, 1, 0) + (0, 0, 0.5), (0, 0, 1.5) if i == 0 else rng.normal(size=3),
+                      (0.2, 1e-3, 0.05, 0.3)[i], 1 + i % 3)
+        box = np.zeros(6, api.BOX_DTYPE)
+        room = [((-4, -4, -0.2), (4, 4, 0)), ((-4, -4, 5), (4, 4, 5.2)), ((-4.2, -4, -0.2), (-4, 4, 5.2)),
+                ((4, -4, -0.2), (4.2, 4, 5.2)), ((-4, -4.2, -0.2), (4, -4, 5.2)), ((-4, 4, -0.2), (4, 4.2, 5.2))]
+        for i, (lo, hi) in enumerate(room):
+            box[i] = (lo, hi, 1)
+        cam = (3.3, 2.0, 2.6)
+    return api.Scene.from_arrays(mats, sph, box, cyl, None, camera_p=cam, camera_height_ratio=0.3, screen=(64, 48))
+
+
+def _scene_box(flat, cam):
+    """the box ort_kernels.hip (the query tables, "the box of everything ort_tree.cpp sized the quadric boxes for")
+    computes, in f32: the camera, spheres and cylinder ends +- |r|, box corners"""
+    lo = np.array(cam, "<f4").copy()
+    hi = lo.copy()
+
+    def grow(p, r):
+        p = np.asarray(p, "<f4")
+        r = np.float32(abs(r))
+        np.minimum(lo, p - r, out=lo)
+        np.maximum(hi, p + r, out=hi)
+    for s in flat.spheres:
+        grow(s["center"], s["r"])
+    for b in flat.boxes:
+        grow(b["min"], 0)
+        grow(b["max"], 0)
+    for c in flat.cylinders:
+        grow(c["base"], c["r"])
+        grow(np.asarray(c["base"], "<f4") + np.asarray(c["axis"], "<f4"), c["r"])
+    return lo, hi
+
+
+def _dir_of_len2(u, target):
+    """a multiple of the unit vector u whose |d|^2, summed in f32 as the kernel does, is target (or the nearest)"""
+    s = np.float32(np.sqrt(np.float64(target)))
+    best = None
+    for k in range(-6, 7):
+        sk = s
+        for _ in range(abs(k)):
+            sk = np.nextafter(sk, np.float32(np.inf if k > 0 else 0))
+        d = (u * sk).astype("<f4")
+        l2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+        err = abs(float(l2) - float(target))
+        if best is None or err < best[0]:
+            best = (err, d)
+        if err == 0:
+            break
+    return best[1]
+
+
+def _threshold_rays(flat, cam, rng, dists):
+    rays = []
+    axes = np.eye(3, dtype="<f4")
+    for s in flat.spheres:
+        c, r = np.asarray(s["center"], "<f4"), float(s["r"])
+        for l2 in LEN2:
+            for j in range(3):
+                u = [axes[j], -axes[j], (axes[j] + axes[(j + 1) % 3] * 0.37) / np.float32(np.linalg.norm([1, 0.37]))][j].astype("<f4")
+                w = np.cross(u, axes[(j + 2) % 3]).astype("<f4")
+                w /= np.float32(np.linalg.norm(w))
+                d = _dir_of_len2(u, l2)
+                # perpendicular offsets across both edges of the tangent band: D^2 = r^2 +- 1e-5 / |d|^2
+                offs = []
+                for sign in (1, -1):
+                    e2 = r * r + sign * 1e-5 / float(l2)
+                    if e2 > 0:
+                        D = np.sqrt(e2)
+                        offs += [D * (1 + k * 2e-7) for k in range(-6, 7)] + [D * (1 + k * 1e-5) for k in (-3, -1, 1, 3)]
+                offs += [r, 0.5 * r]
+                for D in offs:
+                    for L in dists:
+                        o = (c - np.float32(L) * u + np.float32(D) * w).astype("<f4")
+                        rays.append(np.concatenate([o, d]))
+    # origins exactly on the faces of the scene box, one ulp inside and outside, pointed at the shapes
+    lo, hi = _scene_box(flat, cam)
+    targets = np.concatenate([np.asarray(flat.spheres["center"], "<f4"), np.asarray(flat.cylinders["base"], "<f4")])
+    for k in range(3):
+        for face in (lo[k], hi[k]):
+            for step in (None, 0, np.inf):
+                for _ in range(24):
+                    o = (lo + (hi - lo) * rng.uniform(0, 1, 3).astype("<f4")).astype("<f4")
+                    o[k] = face if step is None else np.nextafter(face, np.float32(step) if step else np.float32(-np.inf))
+                    t = targets[rng.integers(0, len(targets))]
+                    u = (t - o).astype(np.float64)
+                    n = np.linalg.norm(u)
+                    u = (u / n if n > 0 else np.array([1.0, 0, 0])).astype("<f4")
+                    rays.append(np.concatenate([o, _dir_of_len2(u, LEN2[rng.integers(0, len(LEN2))])]))
+        # on an edge and a corner of the box
+        rays.append(np.concatenate([lo, _dir_of_len2(np.full(3, 1 / np.sqrt(3), "<f4"), 1)]))
+        rays.append(np.concatenate([hi, _dir_of_len2(np.full(3, -1 / np.sqrt(3), "<f4"), 0.999)]))
+    return np.array(rays, "<f4")
+
+
+def _needs_exact(rays, lo, hi, tree_spheres, tree_quadrics):
+    """raycast_needs_exact (ort_lane.h) restated in f32"""
+    d = rays[:, 3:6]
+    l2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    o = rays[:, 0:3]
+    inside = ((o >= lo) & (o <= hi)).all(axis=1)
+    return (tree_spheres & ~(l2 >= np.float32(0.999))) | (tree_quadrics & ~inside)
+
+
+@pytest.mark.parametrize("small", [False, True], ids=["room", "small"])
+def test_exact_walk_thresholds(api, oracle, monkeypatch, small):
+    """tangent rays across the sphere band at |d|^2 around 0.999 and 1, origins on the scene box's faces and one ulp
+    either side, every quadric in the fast tree (no analytic prologue): t, normal and material bit-equal to the
+    oracle, the reported shape consistent, at least the rays raycast_needs_exact selects counted as exact walks, and
+    the same answers with every ray forced to the exact walk"""
+    monkeypatch.setenv("ORT_ANALYTIC_PROLOGUE", "0")
+    scene = _threshold_scene(api, small).commit()
+    monkeypatch.delenv("ORT_ANALYTIC_PROLOGUE")
+    scene.upload(0)
+    flat = scene.flatten(64, 48)
+    cam = np.array([scene.info().camera_p.x, scene.info().camera_p.y, scene.info().camera_p.z], "<f4")
+    lo, hi = _scene_box(flat, cam)
+    if small:
+        assert float(np.linalg.norm((hi - lo).astype(np.float64))) < 1.0
+    rays = _threshold_rays(flat, cam, np.random.default_rng(99 + small), (0.03, 0.08) if small else (0.4, 2.5))
+    hits, st = scene.raycast(rays)
+    t, nrm, mat = oracle.OracleScene(flat, with_reference_csg=False).raycast(rays[:, 0:3], rays[:, 3:6])
+    assert_same_hits(hits, t, nrm, mat, "thresholds (%s)" % ("small" if small else "room"))
+    # the reported shape: none exactly for the misses, else one whose material is the hit's
+    missed = hits["t"] == FLT_MAX
+    assert ((hits["prim"] == api.NO_PRIM) == missed).all()
+    kind, index = api.decode_prim(hits["prim"][~missed])
+    table = {api.HIT_SPHERE: flat.spheres, api.HIT_BOX: flat.boxes, api.HIT_CYLINDER: flat.cylinders}
+    for k, arr in table.items():
+        sel = kind == k
+        assert (arr["mat"][index[sel]] == hits["mat"][~missed][sel]).all()
+    assert (kind != api.HIT_TRIANGLE).all()
+    need = _needs_exact(rays, lo, hi, len(flat.spheres) > 0, len(flat.spheres) + len(flat.cylinders) > 0)
+    assert 0 < need.sum() < len(rays)
+    assert st["fallback_rays"] >= need.sum(), (st["fallback_rays"], int(need.sum()))
+    # the fast tree really answers the rays at |d|^2 >= 0.999 from inside the box
+    assert (~need).sum() > len(rays) // 3
+    monkeypatch.setenv("ORT_DEBUG_FORCE_FALLBACK", "0")
+    exact, st_x = scene.raycast(rays)
+    monkeypatch.delenv("ORT_DEBUG_FORCE_FALLBACK")
+    assert st_x["fallback_rays"] == len(rays)
+    assert exact.tobytes() == hits.tobytes()
+    scene.close()

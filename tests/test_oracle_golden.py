@@ -38,6 +38,30 @@ def test_unit_tables(oracle):
         assert_bits_equal(got[sel], want[sel], "unit op %d" % op)
 
 
+def test_unit_edges(oracle):
+    """the corner sets of tests/unit_cases.py (+-0 and NaN slab products, tangent bands, radicands of exactly 0, normals
+    in the 1e-4 band around +-z, quadrant boundaries, ...) for ops 1-11, against the reference build (unit_edges.npz).
+    Bit for bit; a NaN matches any NaN."""
+    import unit_cases
+    z = np.load(os.path.join(GOLDEN, "unit_edges.npz"))
+    recs = z["records"].view(ref_io.UNIT_REC_DTYPE).reshape(-1)
+    assert sorted(np.unique(recs["op"])) == list(range(1, 12))
+    got = oracle.unit_batch(recs)
+    for op in range(1, 12):
+        sel = recs["op"] == op
+        unit_cases.assert_match(got[sel], z["ref_det"][sel], recs["a"][sel], "oracle op %d vs the reference" % op)
+
+
+def test_unit_edges_are_the_generators_corner_sets():
+    """unit_edges.npz holds exactly what tests/unit_cases.py makes today (a changed generator needs new fixtures:
+    make_golden.py --only-unit-edges)"""
+    import unit_cases
+    z = np.load(os.path.join(GOLDEN, "unit_edges.npz"))
+    recs = z["records"].view(ref_io.UNIT_REC_DTYPE).reshape(-1)
+    want = np.concatenate([unit_cases.records(op, unit_cases.corners(op)) for op in range(1, 12)])
+    assert recs.tobytes() == want.tobytes()
+
+
 def test_libm_is_close_to_glibc():
     """the deterministic libm is within 1 ulp of glibc on the path's argument ranges (documents
     the distance between the bit-exact anchor and the as-shipped build)."""

@@ -12,6 +12,7 @@
  * (tests/test_host.py holds its image against the oracle; nothing else uses it).
  *
  * build: see tools/Makefile     run: [SIM_THREADS=n] host_sim <scn> <base> W H spp seed policy chunk out.f32
+ *                                  or: host_sim --unit records.bin out.f32   (ort_unit_eval_device on the host)
  */
 #define ORT_HOST_SIM 1
 #include <stdint.h>
@@ -34,7 +35,38 @@ static void cs_dump() { static const char *nm[4] = {"chain len:", "first-outside
     for (int k = 0; k < 4; ++k) { fprintf(stderr, "%s", nm[k]); for (int i = 0; i < 16; ++i) fprintf(stderr, " %llu", g_cs[k][i]); fprintf(stderr, "\n"); } }
 #endif
 
+/* --unit IN OUT: the per-function records of ort_unit_eval_device ({u32 op; f32 in[24]} -> f32 out[8]) through the lane
+   code's own dispatch (unit_eval_op), compiled for the host; op 4's frame is filled in as ort_unit_eval_device does */
+static int unit_mode(const char *in_path, const char *out_path) {
+    FILE *f = fopen(in_path, "rb");
+    if (!f) { fprintf(stderr, "cannot read %s\n", in_path); return 1; }
+    std::vector<unsigned char> rec;
+    unsigned char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof(buf), f)) > 0) rec.insert(rec.end(), buf, buf + got);
+    fclose(f);
+    if (rec.size() % 100u) { fprintf(stderr, "%s: not a whole number of 100-byte records\n", in_path); return 1; }
+    const size_t n = rec.size() / 100u;
+    std::vector<float> out(8 * n);
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t op;
+        float a[24];
+        memcpy(&op, &rec[100 * i], 4);
+        memcpy(a, &rec[100 * i + 4], 96);
+        if (op == 4u) {
+            ort_cylinder c{{a[0], a[1], a[2]}, {a[3], a[4], a[5]}, a[6], 0};
+            cylinder_frame_for(c, a + 13, a + 22);
+        }
+        unit_eval_op(op, a, &out[8 * i]);
+    }
+    FILE *g = fopen(out_path, "wb");
+    if (!g || fwrite(out.data(), 4, out.size(), g) != out.size()) { fprintf(stderr, "cannot write %s\n", out_path); return 1; }
+    fclose(g);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc == 4 && std::string(argv[1]) == "--unit") return unit_mode(argv[2], argv[3]);
     if (argc < 10) { fprintf(stderr, "usage: host_sim scn base W H spp seed policy chunk out.f32 [shard_index shard_count]\n"); return 2; }
     int W = atoi(argv[3]), H = atoi(argv[4]);
     uint32_t spp = (uint32_t)strtoul(argv[5], 0, 10), seed = (uint32_t)strtoul(argv[6], 0, 10);
