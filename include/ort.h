@@ -238,7 +238,12 @@ int ort_render_workspace_bytes(const ort_render_params *params, uint64_t *bytes)
  * bit for bit the reference's hit_t, hit_normal and hit_mat_index (ties in the reference's test order, phantom
  * sphere hits and visibility chains included).  A miss is t = FLT_MAX, n = 0, mat = 0, prim = ORT_NO_PRIM.
  * Rays: count x {o.xyz, d.xyz} f32, 24 B each; d need not be of unit length (the reference does not normalise it),
- * zero components are allowed; non-finite origins or directions are outside the contract.  hits[i] answers rays[i];
+ * zero components are allowed.  Every IEEE-754 ray gets the reference's answer, NaN, infinite, zero, subnormal and
+ * overflowing components included: every non-NaN output bit for bit, a NaN output NaN in the same field and component
+ * (its sign and payload are not part of the contract: x86 and gfx950 make different default NaNs).  Rays the fast tree
+ * cannot answer exactly take the exact octree walk, roughly 1 000x slower per ray: |d|^2 < 0.999 with spheres in the
+ * tree, an origin outside the scene's box with quadrics in it, and a +-0 or NaN direction component (axis-aligned
+ * rays) when boxes are in it (raycast_rays).  hits[i] answers rays[i];
  * results do not depend on count, order or how the batch is sliced.
  * prim = kind << 28 | index: index is the shape's position in the scene's own arrays (the get_spheres / get_boxes /
  * get_cylinders order), for triangles the mesh-major triangle id (triangles of the earlier meshes, then the

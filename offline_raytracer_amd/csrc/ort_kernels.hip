@@ -778,6 +778,7 @@ static int launch_raycast(Scene *scene, DeviceScene *d, const void *d_rays, uint
     io.prim_src = (const uint32_t *)d->prim_src;
     io.tree_spheres = scene->tree.spheres.size() > scene->tree.pro_spheres;
     io.tree_quadrics = io.tree_spheres || scene->tree.cyls.size() > scene->tree.pro_cyls;
+    io.tree_boxes = scene->tree.boxes.size() > scene->tree.pro_boxes;
     memcpy(io.lo, d->scene_lo, sizeof(io.lo));
     memcpy(io.hi, d->scene_hi, sizeof(io.hi));
     unsigned int grid = (unsigned int)((count + kBlock - 1) / kBlock);

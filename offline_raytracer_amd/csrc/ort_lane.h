@@ -2014,17 +2014,22 @@ struct RaycastIO {
        (ort_tree.cpp): unit directions, origins within the scene's box (shapes and camera).  A caller's ray need not be
        either.  A sphere's tangent branch (|b^2 - a c| < 1e-5, ray.cpp:174) widens as 1e-5 / |d|^2 when |d| < 1 -- a
        "hit" far outside the sphere's box -- and the f32 cancellation of both quadrics grows with the origin's distance.
+       A cylinder's quadric degrades once |d|^2 nears the subnormal range (a = dx^2 + dy^2 is 0 below |d| ~ 1e-19).
+       A direction component of +-0 (or NaN, or one whose reciprocal overflows) makes 1/d non-finite: box shapes in the
+       fast tree then part from the reference for rays from exactly a box's face plane (grazing a room's wall).
        Such rays take the exact walk of the reference octree instead (resolve_hit: a phantom that could win). */
     uint32_t tree_spheres;     /* the fast tree holds spheres (those of the analytic prologue are tested outright) */
     uint32_t tree_quadrics;    /* ... spheres or cylinders */
+    uint32_t tree_boxes;       /* ... boxes */
     float lo[3], hi[3];        /* the scene's box as ort_tree.cpp sized the quadric boxes for */
 };
 
-ORT_D bool raycast_needs_exact(const RaycastIO &io, V3 org, V3 dir) {
-    const bool short_dir = io.tree_spheres && !(len2(dir) >= 0.999f);
+ORT_D bool raycast_needs_exact(const RaycastIO &io, V3 org, V3 dir, V3 inv_d) {
+    const bool short_dir = io.tree_quadrics && !(len2(dir) >= (io.tree_spheres ? 0.999f : 1e-30f));
+    const bool inv_nonfinite = io.tree_boxes && !(((inv_d.x - inv_d.x) + (inv_d.y - inv_d.y)) + (inv_d.z - inv_d.z) == 0.0f);
     const bool far = io.tree_quadrics && !(org.x >= io.lo[0] && org.x <= io.hi[0] && org.y >= io.lo[1] && org.y <= io.hi[1] &&
                                           org.z >= io.lo[2] && org.z <= io.hi[2]);
-    return short_dir || far;
+    return short_dir || far || inv_nonfinite;
 }
 
 template <bool COUNTERS, bool TABS>
@@ -2059,7 +2064,7 @@ ORT_D void raycast_lane(const SceneView &sv, const RenderHot &rv, const RaycastI
                     P.dir = mk(b.y, e.x, e.y);
                     ray = j;
                     begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
-                    if (ORT_RARE(raycast_needs_exact(io, P.org, P.dir))) {
+                    if (ORT_RARE(raycast_needs_exact(io, P.org, P.dir, T.inv_d))) {
                         T.cur = kTraversalDone; /* no fast traversal: resolve_hit re-casts it exactly (a phantom that could win) */
                         h.phantom_t = 0.0f;
                     }

@@ -9,7 +9,7 @@ What is committed is data only: inputs and the reference's outputs.
   ref_det   = reference + deterministic libm (oracle/det_math.h)  -> bit-exact anchor
   ref_glibc = reference + glibc libm, "as shipped" on this box     -> distance report
 
-usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges]
+usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges]
 """
 import json
 import os
@@ -221,7 +221,32 @@ def golden_unit_edges():
                         ref_det=ref_io.read_unit_output(os.path.join(TMP, "edges_det.bin")))
 
 
+def ref_raycast(scn, rays):
+    """raycast_top_most_node of the reference (ref_det) for rays (n, 6) -> (t, n, mat)"""
+    np.ascontiguousarray(rays, "<f4").tofile(os.path.join(TMP, "rays.bin"))
+    run(REF_DET, "raycast", scn, DATA, os.path.join(TMP, "rays.bin"), os.path.join(TMP, "hits.bin"))
+    hits = np.fromfile(os.path.join(TMP, "hits.bin"), dtype=np.dtype([("t", "<f4"), ("n", "<f4", 3), ("mat", "<u4")]))
+    return hits["t"], hits["n"], hits["mat"]
+
+
+def golden_raycast_edges():
+    """the hostile rays of tests/raycast_cases.py (non-finite, zero, extreme and grazing) through the reference
+    (ref_det) -> raycast_edges_<scene>.npz; the surface points of the generator come from the reference's own casts"""
+    import raycast_cases  # noqa: E402  (tests/ is on the path)
+    for name in SCENES:
+        scn = DATA + name + ".scn"
+        dump = os.path.join(TMP, name + ".dump")
+        run(REF_DET, "scene-dump", scn, DATA, 64, 64, dump)
+        flat = ref_io.read_scene_dump(dump)
+        rays, cat = raycast_cases.cases(flat, lambda r: ref_raycast(scn, r)[0])
+        t, n, mat = ref_raycast(scn, rays)
+        np.savez_compressed(os.path.join(HERE, "raycast_edges_%s.npz" % name), rays=rays, category=cat, t=t, n=n, mat=mat)
+
+
 def main():
+    if "--only-raycast-edges" in sys.argv:  # add / refresh raycast_edges_<scene>.npz without touching the others
+        golden_raycast_edges()
+        return
     if "--only-unit-edges" in sys.argv:  # add / refresh unit_edges.npz without touching the others
         golden_unit_edges()
         return
@@ -345,6 +370,7 @@ def main():
     golden_c5(manifest)
     golden_showcase()
     golden_unit_edges()
+    golden_raycast_edges()
 
     # cross-check values recorded by the survey, re-measured here on ref_glibc
     js = run(REF_GLIBC, "render", DATA + "testscene.scn", DATA, 64, 64, 4, 12345, "whole", os.path.join(TMP, "x.f32"))

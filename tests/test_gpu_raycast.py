@@ -239,10 +239,10 @@ def test_renders_unchanged_by_raycasts(api, oracle):
 
 
 # ---- rays at the exact walk's thresholds (raycast_needs_exact, ort_lane.h) -------------------------------------------
-# raycast_needs_exact sends a ray to the exact octree walk when |d|^2 < 0.999 with spheres in the fast tree, or when its
-# origin lies outside the scene box with quadrics in it.  Rays with |d|^2 in [0.999, 1) stay in the fast tree, whose
-# sphere boxes (ort_tree.cpp) must then hold every tangent-band "hit" (|b^2 - a c| < 1e-5: a band that widens as
-# 1e-5 / |d|^2), and rays from exactly the scene box's faces count as inside.
+# raycast_needs_exact sends a ray to the exact octree walk when |d|^2 < 0.999 with spheres in the fast tree (< 1e-30
+# with cylinders alone), or when its origin lies outside the scene box with quadrics in it.  Rays with |d|^2 in
+# [0.999, 1) stay in the fast tree, whose sphere boxes (ort_tree.cpp) must then hold every tangent-band "hit"
+# (|b^2 - a c| < 1e-5: a band that widens as 1e-5 / |d|^2), and rays from exactly the scene box's faces count as inside.
 LEN2 = [np.float32(0.998), np.nextafter(np.float32(0.999), np.float32(0)), np.float32(0.999),
         np.nextafter(np.float32(0.999), np.float32(2)), np.float32(0.9995), np.float32(1 - 2.0 ** -24), np.float32(1),
         np.float32(1.01)]
@@ -375,7 +375,8 @@ def _needs_exact(rays, lo, hi, tree_spheres, tree_quadrics):
     l2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
     o = rays[:, 0:3]
     inside = ((o >= lo) & (o <= hi)).all(axis=1)
-    return (tree_spheres & ~(l2 >= np.float32(0.999))) | (tree_quadrics & ~inside)
+    short = ~(l2 >= np.float32(0.999 if tree_spheres else 1e-30))
+    return (tree_quadrics & short) | (tree_quadrics & ~inside)
 
 
 @pytest.mark.parametrize("small", [False, True], ids=["room", "small"])

@@ -126,6 +126,56 @@ def test_raycast_matches_reference(oracle, name, load_scene):
     assert (mat == z["mat"]).all()
 
 
+@pytest.mark.parametrize("name", SCENES)
+def test_raycast_edges_match_reference(oracle, name, load_scene):
+    """the hostile rays of tests/raycast_cases.py (non-finite, zero, extreme and grazing; raycast_edges_<scene>.npz):
+    t, normal, material bit for bit, a NaN where the reference has one"""
+    import raycast_cases
+    z = np.load(os.path.join(GOLDEN, "raycast_edges_%s.npz" % name))
+    osc = oracle.OracleScene(load_scene(name).flatten(64, 64))
+    t, n, mat = osc.raycast(z["rays"][:, 0:3], z["rays"][:, 3:6])
+    raycast_cases.assert_same_answers(t, n, mat, z["t"], z["n"], z["mat"], name + " oracle vs the reference")
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_raycast_edges_are_the_generators_rays(oracle, name, load_scene):
+    """raycast_edges_<scene>.npz holds exactly what tests/raycast_cases.py makes today (a changed generator needs new
+    fixtures: make_golden.py --only-raycast-edges)"""
+    import raycast_cases
+    z = np.load(os.path.join(GOLDEN, "raycast_edges_%s.npz" % name))
+    flat = load_scene(name).flatten(64, 64)
+    osc = oracle.OracleScene(flat)
+    rays, cat = raycast_cases.cases(flat, lambda r: osc.raycast(r[:, 0:3], r[:, 3:6])[0])
+    assert rays.tobytes() == z["rays"].tobytes()
+    assert (cat == z["category"]).all()
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_raycast_edges_are_not_all_misses(name):
+    """every category is there, and the reference hits something with non-finite, extreme, grazing and far rays: a
+    fixture of misses alone would pin nothing but the miss record"""
+    import raycast_cases
+    z = np.load(os.path.join(GOLDEN, "raycast_edges_%s.npz" % name))
+    assert len(z["rays"]) <= 2000 and len(z["t"]) == len(z["rays"])
+    bits = z["rays"].view("<u4")
+    hit = z["t"] < raycast_cases.FLT_MAX
+    for c, what in enumerate(raycast_cases.CATEGORIES):
+        sel = z["category"] == c
+        assert sel.sum() >= 100, what
+        if what != "zero":
+            assert hit[sel].sum() >= 20, what
+    nonfinite = z["category"] == raycast_cases.CATEGORIES.index("nonfinite")
+    # qNaN, the negative NaN and both infinities in every component, hit or not
+    for comp in range(6):
+        for v in (raycast_cases.QNAN, raycast_cases.NEG_NAN, np.float32(np.inf), np.float32(-np.inf)):
+            assert (bits[nonfinite, comp] == np.float32(v).view("<u4")).sum() >= 6, (comp, v)
+    assert hit[nonfinite & np.isnan(z["rays"][:, 0:6]).any(axis=1)].any()
+    # the zero rays: all eight sign patterns of (+-0, +-0, +-0)
+    zero = z["rays"][z["category"] == raycast_cases.CATEGORIES.index("zero")]
+    patterns = {tuple(r) for r in zero[:, 3:6].view("<u4") if not (r & 0x7FFFFFFF).any()}
+    assert len(patterns) == 8
+
+
 def test_glibc_distance_is_recorded_and_small(manifest):
     """reference + glibc libm vs reference + deterministic libm on the same seeds: almost all
     pixels bit-equal; the rest are single decorrelated paths (1/spp-sized) -- see DESIGN.md."""

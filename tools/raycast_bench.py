@@ -4,7 +4,10 @@ Per scene: 2^24 rays per call (the golden tables' distribution -- origins in and
 directions -- drawn on the device from a fixed seed), warm-up calls, then calls until at least --seconds of timed work;
 the rate comes from HIP events around the calls.  One more call with ORT_RENDER_COUNTERS gives the work per ray.
 Prints one JSON line per scene.  For the kernel time alone run it under rocprofv3 --kernel-trace --stats.
-usage: python3 tools/raycast_bench.py [--scenes c2_analytic,c3_bunny_room,...] [--rays-log2 24] [--warmup 5] [--seconds 1]"""
+--dirs axis casts the same origins along the six axis directions (+-x, +-y, +-z with +-0 in the other components,
+e.g. height probes): the directions whose 1/d has infinite components.
+usage: python3 tools/raycast_bench.py [--scenes c2_analytic,c3_bunny_room,...] [--rays-log2 24] [--warmup 5] [--seconds 1]
+                                      [--dirs uniform|axis]"""
 import argparse
 import json
 import os
@@ -27,7 +30,7 @@ def scene_path(name):
     return os.path.join(ROOT, "data", name + ".scn")
 
 
-def make_rays(torch, n, seed, dev):
+def make_rays(torch, n, seed, dev, dirs="uniform"):
     """tests/golden/make_golden.py's distribution: half the origins near the middle of the room, half anywhere in it"""
     g = torch.Generator(device=dev)
     g.manual_seed(seed)
@@ -41,6 +44,9 @@ def make_rays(torch, n, seed, dev):
     o[:h] = lo2 + u[:h] * (hi2 - lo2)
     d = torch.randn((n, 3), generator=g, device=dev)
     d = d / d.norm(dim=1, keepdim=True)
+    if dirs == "axis":  # the largest component's axis and sign, the other two +0 or -0 (their signs kept)
+        k = d.abs().argmax(dim=1, keepdim=True)
+        d = torch.where(torch.arange(3, device=dev)[None, :] == k, torch.sign(d), d * 0)
     return torch.cat([o, d], dim=1).float().contiguous()
 
 
@@ -51,6 +57,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=20261016)
+    ap.add_argument("--dirs", choices=["uniform", "axis"], default="uniform")
     args = ap.parse_args()
     import torch
     from offline_raytracer_amd import api
@@ -61,7 +68,7 @@ def main():
         t0 = time.time()
         scene = api.Scene.load_scn(scene_path(name)).commit().upload(0)
         load_s = time.time() - t0
-        rays = make_rays(torch, n, args.seed, dev)
+        rays = make_rays(torch, n, args.seed, dev, args.dirs)
         hits = torch.empty(n * 24, dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
         call = lambda **kw: scene.raycast_device(rays.data_ptr(), n, hits.data_ptr(), stream=stream.cuda_stream, **kw)  # noqa: E731
@@ -84,7 +91,7 @@ def main():
         sc = call(counters=True, want_stats=True)
         h = hits.view(torch.float32).view(-1, 6)[:, 0]
         hit_fraction = float((h < 3.4e38).float().mean().item())
-        out = {"tool": "raycast_bench", "scene": name, "rays_per_call": n, "calls": calls, "timed_ms": round(total_ms, 3),
+        out = {"tool": "raycast_bench", "scene": name, "dirs": args.dirs, "rays_per_call": n, "calls": calls, "timed_ms": round(total_ms, 3),
                "grays_per_s": n * calls / (total_ms * 1e-3) / 1e9,
                "ms_per_call_median": sorted(ev)[len(ev) // 2], "kernel_ms": st["kernel_ms"],
                "grays_per_s_kernel_ms": n / (st["kernel_ms"] * 1e-3) / 1e9,
