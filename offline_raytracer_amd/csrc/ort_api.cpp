@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "ort_plan.h" /* shard_block_count, render_workspace_bytes */
 #include "ort_scene.h"
 
 namespace {

@@ -1,0 +1,299 @@
+/*
+ * ort_plan.h -- the launch policy of the render call, as arithmetic: what device_render (ort_kernels.hip) launches, with which
+ * grid and which thresholds, decided from a few facts about the uploaded scene (SceneTraits), the render parameters and the
+ * developer knobs.  Host-only and free of HIP, so that tools/launch_plan.cpp and tests/test_launch_plan.py can hold the
+ * measured crossovers without a device.  ort_kernels.hip turns a LaunchPlan into launches and decides nothing.
+ */
+#ifndef ORT_PLAN_H
+#define ORT_PLAN_H
+
+#include <stddef.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../../include/ort.h"
+
+namespace ort {
+
+/* Developer knobs (none changes a result).  The environment is read ONCE, when the scene is uploaded
+   (ort_scene_upload); ORT_KNOBS_LIVE=1 -- tests and tuning sweeps that flip a knob between two renders of one uploaded
+   scene -- reads it again at every render.  -1 = not set: the launch policy decides. */
+struct Knobs {
+    uint32_t force_fallback_mask = 0xffffffffu; /* ORT_DEBUG_FORCE_FALLBACK */
+    bool debug_util = false, debug_fallback = false, debug_drain = false; /* ORT_DEBUG_UTIL, ORT_DEBUG_FALLBACK, ORT_DEBUG_DRAIN */
+    int cache_resident = -1;   /* ORT_CACHE_RESIDENT */
+    int refill_below = -1, descend_below = -1; /* ORT_REFILL_BELOW, ORT_DESCEND_BELOW */
+    bool wavefront = false;    /* ORT_MODE=wavefront */
+    bool general_kernel = false; /* ORT_KERNEL=general */
+    int lds_tables = -1;       /* ORT_LDS_TABLES */
+    int exchange = -1;         /* ORT_EXCHANGE */
+    int long_min = -1, long_refill = -1, inflight_cap = -1, park_min = -1; /* ORT_LONG_MIN, ORT_LONG_REFILL, ORT_INFLIGHT_CAP, ORT_PARK_MIN */
+    int lpt = -1;              /* ORT_LPT=0: CHUNK jobs issued chunk-major (rounds 1-2) instead of block-major */
+    int wide = -1;             /* ORT_WIDE=1: traverse the 4-wide form of the tree (default: never) */
+    int waves5 = -1;           /* ORT_WAVES5=0 / 1: the plain loop's five-waves-per-SIMD build (default: all-lobes flavour, trees that leave the L2) */
+    int endgame_jobs = -1;     /* ORT_ENDGAME_JOBS: the ray exchange drains its stashes over the last n/4 jobs per lane (default 16 = four jobs) */
+    int blocks_per_cu = -1;    /* ORT_BLOCKS_PER_CU (takes effect at upload) */
+    int job_batch = -1, batch_tail = -1; /* ORT_JOB_BATCH: job indices a wave draws at a time (0: one draw per job); ORT_BATCH_TAIL: ... until this many jobs per lane are left */
+};
+inline int env_int(const char *name, int unset = -1) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : unset;
+}
+inline Knobs read_knobs() {
+    Knobs k;
+    const char *e;
+    if ((e = getenv("ORT_DEBUG_FORCE_FALLBACK"))) k.force_fallback_mask = (uint32_t)strtoul(e, nullptr, 0);
+    k.debug_util = getenv("ORT_DEBUG_UTIL") != nullptr;
+    k.debug_fallback = getenv("ORT_DEBUG_FALLBACK") != nullptr;
+    k.debug_drain = getenv("ORT_DEBUG_DRAIN") != nullptr;
+    k.cache_resident = env_int("ORT_CACHE_RESIDENT");
+    k.refill_below = env_int("ORT_REFILL_BELOW");
+    k.descend_below = env_int("ORT_DESCEND_BELOW");
+    k.wavefront = (e = getenv("ORT_MODE")) && strcmp(e, "wavefront") == 0;
+    k.general_kernel = (e = getenv("ORT_KERNEL")) && strcmp(e, "general") == 0;
+    k.lds_tables = env_int("ORT_LDS_TABLES");
+    k.exchange = env_int("ORT_EXCHANGE");
+    k.long_min = env_int("ORT_LONG_MIN");
+    k.long_refill = env_int("ORT_LONG_REFILL");
+    k.inflight_cap = env_int("ORT_INFLIGHT_CAP");
+    k.park_min = env_int("ORT_PARK_MIN");
+    k.lpt = env_int("ORT_LPT");
+    k.wide = env_int("ORT_WIDE");
+    k.waves5 = env_int("ORT_WAVES5");
+    k.endgame_jobs = env_int("ORT_ENDGAME_JOBS");
+    k.blocks_per_cu = env_int("ORT_BLOCKS_PER_CU");
+    k.job_batch = env_int("ORT_JOB_BATCH");
+    k.batch_tail = env_int("ORT_BATCH_TAIL");
+    return k;
+}
+
+/* The lane code's limits the policy counts with (ort_lane.h, which only a HIP unit can include: ort_kernels.hip asserts every
+   one of them equal to its original) */
+constexpr uint32_t kPlanBlock = 256;     /* kBlock: lanes per workgroup */
+constexpr uint32_t kPlanLdsStack = 24;   /* kLdsStack of the four-waves unit, the one with the ray exchange */
+constexpr uint32_t kPlanStashVecs = 9, kPlanCapL = 128, kPlanCapR = 192; /* kStashVecs, kCapL, kCapR */
+constexpr uint32_t kPlanAllTabs = 1u | 2u | 8u; /* TAB_PRO | TAB_LIGHTS | TAB_MATS */
+enum : int { PLAN_JOBS_EXPLICIT = 0, PLAN_JOBS_PIXEL = 1, PLAN_JOBS_CHUNK = 2 }; /* JOBS_* */
+
+/* the resident workgroups of a persistent launch: per_cu for each compute unit (256 units where the device reports none) */
+inline unsigned int persistent_blocks(int cu_count, unsigned int per_cu) { return (unsigned int)(cu_count > 0 ? cu_count : 256) * per_cu; }
+/* ... as fixed at upload: 4 workgroups of 256 lanes per CU (4 = one wave per SIMD each), or ORT_BLOCKS_PER_CU */
+inline unsigned int upload_max_blocks(int cu_count, const Knobs &kn) {
+    unsigned int per_cu = kn.blocks_per_cu > 0 ? (unsigned int)kn.blocks_per_cu : 4u;
+    if (per_cu < 1u || per_cu > 8u) per_cu = 4u;
+    return persistent_blocks(cu_count, per_cu);
+}
+
+/* the one cache-residency line: trees up to 16 MB stay in the 8 x 4 MB of L2.  knob = ORT_CACHE_RESIDENT (A/B runs: treat
+   the tree as (not) cache-resident), -1: not set */
+inline bool tree_is_cache_resident(size_t fast_tree_bytes, int knob) {
+    return knob >= 0 ? knob != 0 : fast_tree_bytes <= (size_t)(16u << 20);
+}
+
+/* the 8x8 blocks a PIXEL / CHUNK render enumerates: the whole grid in its global numbering when sharded (that is
+   what block_id % world == rank refers to), only the blocks under the rect on one GPU */
+struct BlockGrid { uint32_t blocks_w, block_x0, block_y0, my_blocks, shard_index, shard_count; };
+inline BlockGrid block_grid_for(const ort_render_params *p) {
+    BlockGrid g;
+    g.shard_count = p->shard_count > 1 ? p->shard_count : 1;
+    g.shard_index = p->shard_count > 1 ? p->shard_index : 0;
+    g.blocks_w = (uint32_t)((p->width + 7) / 8);
+    uint32_t total = g.blocks_w * (uint32_t)((p->height + 7) / 8);
+    g.block_x0 = g.block_y0 = 0;
+    if (g.shard_count == 1 && p->x1 > p->x0 && p->y1 > p->y0) {
+        g.block_x0 = (uint32_t)(p->x0 / 8);
+        g.block_y0 = (uint32_t)(p->y0 / 8);
+        g.blocks_w = (uint32_t)((p->x1 + 7) / 8) - g.block_x0;
+        total = g.blocks_w * ((uint32_t)((p->y1 + 7) / 8) - g.block_y0);
+    }
+    g.my_blocks = (total > g.shard_index) ? (total - g.shard_index + g.shard_count - 1) / g.shard_count : 0;
+    return g;
+}
+
+inline uint64_t shard_block_count(const ort_render_params *p) { return block_grid_for(p).my_blocks; }
+
+inline uint64_t render_workspace_bytes(const ort_render_params *p) {
+    if (p->policy != ORT_POLICY_CHUNK || p->chunk == 0) return 0;
+    uint64_t nch = p->spp / p->chunk;
+    return nch * (uint64_t)block_grid_for(p).my_blocks * 64ull * 12ull; /* partial planes hold this shard's blocks only */
+}
+
+/* what the policy reads from an uploaded scene, and nothing else */
+struct SceneTraits {
+    bool diffuse_only = false;   /* no surface material can enter the specular / transmission blocks */
+    uint32_t tab_flags = 0;      /* which small tables fit their LDS slots (TAB_*) */
+    size_t fast_tree_bytes = 0;  /* nodes and triangles of the fast tree */
+    float sah_cost = 0;          /* expected node visits of a random ray through the scene box (ort_tree.cpp) */
+    bool has_wide = false;       /* the 4-wide form of the tree is uploaded */
+    int cu_count = 0;
+    unsigned int max_blocks = 0; /* resident workgroups of a persistent launch, fixed at upload */
+};
+
+/* everything device_render decides before it touches the device */
+struct LaunchPlan {
+    /* the kernel: wavefront <counters> | five waves <diffuse> | exchange <counters, diffuse> | plain loop <counters, diffuse, tabs,
+       implicit, wide>.  diffuse / tabs / implicit are the kernel's template arguments: under counters the diffuse flavour only
+       exists with the ORT_DEBUG_UTIL probes, and the exchange kernels know no other job space than the implicit ones */
+    bool wavefront = false, exchange = false, five = false, wide = false, counters = false, diffuse = false, tabs = false, implicit = false;
+    bool util = false; /* ORT_DEBUG_UTIL probes (counters builds) */
+    unsigned int grid = 1;
+    /* the job space */
+    int mode = PLAN_JOBS_EXPLICIT;
+    uint32_t nchunks = 0;
+    unsigned long long job_count = 0;
+    BlockGrid blocks{};
+    /* the RenderView fields that are policy */
+    int refill_below = 0, descend_below = 0;
+    uint32_t capL = 0, capR = 0, long_min = 0, long_refill = 0, inflight_cap = 0, park_min = 0;
+    unsigned long long endgame_from = 0;
+    uint32_t stash_wave_f4 = 0;
+    uint32_t block_major = 0;
+    uint32_t job_batch = 0;
+    unsigned long long batch_until = 0;
+    /* the buffers that follow: CHUNK partial planes (= render_workspace_bytes), the waves' stashes, ORT_DEBUG_DRAIN end times
+       (allocated only by calls that read stats back) */
+    size_t partial_bytes = 0, stash_bytes = 0, drain_bytes = 0;
+};
+
+/* job_count: the number of explicit jobs (explicit_jobs; ignored otherwise: PIXEL / CHUNK job spaces follow from p).
+   w5_layout_ok: the five-waves unit's argument structs have this unit's layout (ort_launch_w5 takes them as bytes). */
+inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, bool explicit_jobs, uint64_t job_count, bool w5_layout_ok,
+                              const Knobs &kn) {
+    LaunchPlan pl;
+    const bool want_util = kn.debug_util; /* developer diagnostics, counters build only */
+    /* tuning knobs; results do not depend on them.  Defaults tuned on MI355X (profiles/r01_tuning.md)
+       separately for trees that stay in L2 and trees that do not */
+    const bool cache_resident_tree = tree_is_cache_resident(t.fast_tree_bytes, kn.cache_resident);
+    pl.refill_below = kn.refill_below >= 0 ? kn.refill_below : (cache_resident_tree ? 16 : 32); /* 12 until the block-major issue (round 3: 8-way shard 64.4 -> 63.8 ms) */
+    if (pl.refill_below < 1) pl.refill_below = 1;
+    if (pl.refill_below > 64) pl.refill_below = 64;
+    /* cache-resident trees (bunny room: 6 MB): 8, worth +10 %.  Trees that leave the 8 x 4 MB of L2 (the 1M-triangle
+       scene, 86 MB): 16 and a later refill (32): the waits are longer there, so leaving the loops costs more
+       (3840x2160, 256 spp: 1 272 Mpaths/s; with the small-tree values 1 100; profiles/r02_tuning.md) */
+    pl.descend_below = kn.descend_below >= 0 ? kn.descend_below : (cache_resident_tree ? 8 : 16);
+    if (pl.descend_below < 0) pl.descend_below = 0;
+    if (pl.descend_below > 64) pl.descend_below = 64;
+
+    pl.blocks = block_grid_for(&p);
+    if (explicit_jobs) {
+        pl.mode = PLAN_JOBS_EXPLICIT;
+        pl.job_count = job_count;
+    } else if (p.policy == ORT_POLICY_PIXEL) {
+        pl.mode = PLAN_JOBS_PIXEL;
+        pl.nchunks = 1;
+        pl.job_count = (unsigned long long)pl.blocks.my_blocks * 64ull;
+    } else {
+        pl.mode = PLAN_JOBS_CHUNK;
+        pl.nchunks = p.spp / p.chunk;
+        pl.job_count = (unsigned long long)pl.blocks.my_blocks * 64ull * pl.nchunks;
+        pl.partial_bytes = (size_t)pl.nchunks * (size_t)pl.blocks.my_blocks * 64u * 12u; /* = render_workspace_bytes(p) */
+    }
+
+    const bool counters = (p.flags & ORT_RENDER_COUNTERS) != 0;
+    const bool wavefront = kn.wavefront; /* ORT_MODE=wavefront; results are identical */
+    const bool diffuse = t.diffuse_only && !kn.general_kernel; /* ORT_KERNEL=general forces the all-lobes kernel (A/B runs; same results) */
+    /* TABS: the scene's small tables all fit their LDS slots (every scene of this repository); otherwise HBM */
+    const bool tabs = (t.tab_flags & kPlanAllTabs) == kPlanAllTabs && kn.lds_tables != 0; /* ORT_LDS_TABLES=0: read them from HBM anyway (A/B runs; same results) */
+    /* the plain loop of implicit job spaces exists at FIVE waves per SIMD as well (ort_kernels_w5.hip: 96 registers, 20 LDS stack
+       entries, machine LICM off).  Same call, four / five waves: analytic scene 3 302 / 3 514 Mpaths/s, glass room 3 625 / 3 848,
+       testscene 2 790 / 2 885, 1M-triangle scene 1 401 / 1 500 -- the all-lobes flavour and trees that leave the L2 take it.  The
+       diffuse flavour on a cache-resident tree does not: bunny room whole frame 4 729 / 4 712, its 4- / 8-way shards 117.0 / 119.2 and
+       63.5 / 65.9 ms (a quarter more lanes, a quarter fewer jobs per lane: the tail weighs more); nor the ray exchange (5 053 / 4 949).
+       ORT_WAVES5=0 / 1 forces. */
+    const bool can_five = !wavefront && !counters && tabs && pl.mode != PLAN_JOBS_EXPLICIT && kn.wide <= 0 && kn.exchange <= 0 && w5_layout_ok;
+    /* persistent grid: 4 blocks of 256 lanes per CU (5 for the five-waves kernels, decided below), never more lanes than jobs */
+    unsigned long long lanes_wanted = pl.job_count;
+    unsigned int max_blocks = t.max_blocks;
+    unsigned int grid = (unsigned int)((lanes_wanted + kPlanBlock - 1) / kPlanBlock);
+    if (grid > max_blocks) grid = max_blocks;
+    if (grid == 0) grid = 1;
+    bool exch = false;
+    if (!wavefront) {
+        /* ray exchange (pt_lane_x): bit-identical; 60 of 64 lanes in the shading pass instead of 53 and leaf
+           visits four times better filled, against the parking traffic.  On by itself where it is a gain
+           (profiles/r02_tuning.md): the diffuse flavour (the all-lobes one spills too much around the exchange) on
+           launches of at least 24 jobs per lane -- every parked path is a job in progress, so a wave's tail grows with
+           what it has parked, which short launches cannot amortise (round 3, stashes drained over the last four jobs per
+           lane: 2- / 4- / 8-way shard of the headline frame, 63 / 32 / 16 jobs per lane: 216.2 / 115.5 / 65.2 ms with the exchange,
+           228.6 / 117.0 / 63.5 plain).  ORT_EXCHANGE=0 / 1 forces it. */
+        /* ... and not for trees that leave the L2: the 1M-triangle scene runs 1 392 Mpaths/s with it and 1 393 without (round 2:
+           1 268 / 1 272), and its stashes would move 3 TB/s through the fabric for that */
+        /* ... and only where rays spend their time in the tree: since a wave draws its jobs in batches of like jobs (draw_job) the
+           plain loop keeps its lanes together by itself, and the exchange pays from an SAH cost of the tree (expected node visits of a
+           random ray through the scene box, ort_tree.cpp) of about 0.09 -- 1080p / 512 spp, exchange / plain loop, Mpaths/s: bunny at
+           scale 3 / 5 / 8 / 12 (SAH cost 0.027 / 0.076 / 0.19 / 0.44) 5 428 / 5 844, 5 143 / 5 151, 3 904 / 3 728, 3 173 / 2 946; dwarf at
+           scale 0.008 / 0.012 / 0.02 / 0.03 (0.018 / 0.040 / 0.11 / 0.25) 5 335 / 5 666, 4 921 / 5 143, 4 454 / 4 276, 3 626 / 3 483 */
+        const bool worth_it = diffuse && cache_resident_tree && t.sah_cost >= 0.09f && pl.job_count >= 24ull * (unsigned long long)grid * kPlanBlock;
+        exch = tabs && pl.mode != PLAN_JOBS_EXPLICIT && (kn.exchange >= 0 ? kn.exchange != 0 : worth_it) && (!counters || (want_util && diffuse));
+        if (exch && kn.refill_below < 0) pl.refill_below = 24; /* stragglers park instead of idling: leave the loop a little earlier (dwarf room 4K, 16 / 24 / 48: 4 466 / 4 536 / 4 536 Mpaths/s) */
+        if (exch) {
+            pl.capL = kPlanCapL; pl.capR = kPlanCapR;
+            pl.long_min = kn.long_min >= 0 ? (uint32_t)kn.long_min : 64u;
+            pl.long_refill = kn.long_refill >= 0 ? (uint32_t)kn.long_refill : 32u;
+            pl.inflight_cap = kn.inflight_cap >= 0 ? (uint32_t)kn.inflight_cap : 64u;
+            pl.park_min = kn.park_min >= 0 ? (uint32_t)kn.park_min : 1u;
+            if (pl.long_min < 1u) pl.long_min = 1u;
+            if (pl.long_min > pl.capL) pl.long_min = pl.capL;
+            if (pl.long_refill > 64u) pl.long_refill = 64u;
+            /* a wave whose lanes all hold off new jobs (parked paths >= inflight_cap) must be able to start a traversal phase
+               on what it has parked (parked + tracing >= long_min), or nothing in it could ever move again */
+            if (pl.inflight_cap < pl.long_min) pl.inflight_cap = pl.long_min;
+            if (pl.inflight_cap < 1u) pl.inflight_cap = 1u;
+            {
+                /* the last FOUR jobs per lane (round 3, whole frame / 2- / 4- / 8-way shard: 0 jobs 431.5 / 224.4 / 122.3 / 71.6 ms, two
+                   426.3 / 219.8 / 117.5 / 66.1, four 426.4 / 218.8 / 116.6 / 64.6) */
+                const unsigned long long quarter_jobs = kn.endgame_jobs >= 0 ? (unsigned long long)kn.endgame_jobs : 16ull;
+                const unsigned long long tail_jobs = quarter_jobs * (unsigned long long)grid * kPlanBlock / 4ull;
+                pl.endgame_from = pl.job_count > tail_jobs ? pl.job_count - tail_jobs : 0ull;
+            }
+            pl.stash_wave_f4 = (kPlanStashVecs + kPlanLdsStack / 4u) * pl.capL + kPlanStashVecs * pl.capR;
+            pl.stash_bytes = (size_t)t.max_blocks * (kPlanBlock / 64) * pl.stash_wave_f4 * 16u; /* float4 units */
+        }
+    }
+    const bool five = can_five && !exch && (kn.waves5 >= 0 ? kn.waves5 != 0 : (!diffuse || !cache_resident_tree));
+    if (five && kn.blocks_per_cu <= 0) {
+        max_blocks = persistent_blocks(t.cu_count, 5u);
+        grid = (unsigned int)((lanes_wanted + kPlanBlock - 1) / kPlanBlock);
+        if (grid > max_blocks) grid = max_blocks;
+        if (grid == 0) grid = 1;
+    }
+    /* CHUNK renders issue their jobs block-major (see "the order in which a CHUNK render issues its jobs"); ORT_LPT=0:
+       chunk-major as in rounds 1-2 (A/B runs; same image either way) */
+    if (pl.mode == PLAN_JOBS_CHUNK && pl.nchunks >= 2u && kn.lpt != 0) pl.block_major = 1u;
+    /* a wave draws its job indices in batches (ort_lane.h: draw_job) until ORT_BATCH_TAIL jobs per lane are left in the job
+       space, then one by one: the end of a launch is dealt as finely as before */
+    if (!wavefront) {
+        /* 64 indices at a time, 128 on launches of 96 jobs per lane and more; what a wave holds back is at most two jobs per lane of
+           its own, of up to eight average job lengths each in the expensive blocks: batches stop 8 (16) jobs per lane before the
+           end.  Whole headline frame / its 8-way shard, ms: no batches 422.5 / 63.7, 32: 418.9 / 63.1, 64: 414.3 / 62.0, 128: 411.3 /
+           74.4 (with the tail of 64), 256: 419.9 / 113 (profiles/r03_tuning.md) */
+        const unsigned long long lanes = (unsigned long long)grid * kPlanBlock;
+        pl.job_batch = kn.job_batch >= 0 ? (uint32_t)kn.job_batch : (pl.job_count >= 96ull * lanes ? 128u : 64u);
+        const unsigned long long per_lane = kn.batch_tail >= 0 ? (unsigned long long)kn.batch_tail : 8ull * ((pl.job_batch + 63u) / 64u);
+        const unsigned long long tail = per_lane * lanes;
+        pl.batch_until = pl.job_count > tail ? pl.job_count - tail : 0ull;
+    }
+    if (kn.debug_drain && !wavefront) pl.drain_bytes = (size_t)max_blocks * (kPlanBlock / 64) * sizeof(unsigned long long);
+    /* 4-wide tree (DevNode4): half the dependent node fetches per ray -- and twice the vector instructions per visit, in a
+       kernel that is issue-bound at a third of its lanes on the trees it was meant for: 1 218 against 1 368 Mpaths/s on the
+       1M-triangle scene (profiles/r03_tuning.md).  Off unless ORT_WIDE=1 asks for it (same image either way). */
+    const bool wide = t.has_wide && !exch && tabs && (counters || pl.mode != PLAN_JOBS_EXPLICIT) && !(counters && diffuse && want_util) && kn.wide > 0;
+
+    pl.wavefront = wavefront;
+    pl.counters = counters;
+    pl.util = want_util;
+    pl.exchange = exch;
+    pl.five = five;
+    pl.wide = wide && !wavefront;
+    pl.diffuse = diffuse && (!counters || want_util);
+    pl.tabs = tabs;
+    /* IMPLICIT job spaces (PIXEL / CHUNK policies): the variant whose lanes carry no job rect / count / index */
+    pl.implicit = !wavefront && !counters && tabs && pl.mode != PLAN_JOBS_EXPLICIT;
+    pl.grid = grid;
+    return pl;
+}
+
+} // namespace ort
+
+#endif

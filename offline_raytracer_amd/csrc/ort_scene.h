@@ -190,9 +190,7 @@ int device_upload(Scene *scene, int device, std::string *err);
 void device_release(Scene *scene);
 int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *jobs, uint32_t job_count,
                   void *d_out, float *h_out, void *stream, uint32_t *final_states, ort_stats *stats, std::string *err);
-uint64_t render_workspace_bytes(const ort_render_params *p);
 int device_unit_eval(int device, const void *records, uint32_t n, float *out, std::string *err);
-uint64_t shard_block_count(const ort_render_params *p);
 /* closest-hit queries: host rays / hits (h_*, synchronous) or device ones (d_*, enqueued on stream) */
 int device_raycast(Scene *scene, const float *h_rays, const void *d_rays, uint64_t count, ort_hit *h_hits, void *d_hits, uint32_t flags,
                    void *stream, ort_stats *stats, std::string *err);

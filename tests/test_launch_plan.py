@@ -1,0 +1,261 @@
+"""The launch policy of the render call (csrc/ort_plan.h: plan_render) without a device, through tools/launch_plan: which kernel,
+which grid, which thresholds.  Expected values are the defaults and crossovers of DESIGN.md sections 5-6 as the code states
+them: SAH cost 0.09, 24 and 96 jobs per lane, 16 MB of fast tree, five waves for the all-lobes flavour and trees that leave the
+L2.  The GPU tests compare images of forced variants (ORT_WAVES5, ORT_EXCHANGE, ORT_WIDE, ...); the tests here are what says
+that each forcing really selects the kernel its test names, and which requests fall back silently."""
+import json
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+TOOL = os.path.join(ROOT, "tools", "launch_plan")
+CU = 256
+LANES = CU * 4 * 256  # four workgroups of 256 lanes per compute unit
+KNOBS = ("ORT_DEBUG_FORCE_FALLBACK ORT_DEBUG_UTIL ORT_DEBUG_FALLBACK ORT_DEBUG_DRAIN ORT_CACHE_RESIDENT ORT_REFILL_BELOW ORT_DESCEND_BELOW "
+         "ORT_MODE ORT_KERNEL ORT_LDS_TABLES ORT_EXCHANGE ORT_LONG_MIN ORT_LONG_REFILL ORT_INFLIGHT_CAP ORT_PARK_MIN ORT_LPT ORT_WIDE ORT_WAVES5 "
+         "ORT_ENDGAME_JOBS ORT_BLOCKS_PER_CU ORT_JOB_BATCH ORT_BATCH_TAIL").split()
+
+
+@pytest.fixture(scope="module")
+def tool():
+    src = [os.path.join(ROOT, "tools", "launch_plan.cpp"), os.path.join(ROOT, "offline_raytracer_amd", "csrc", "ort_plan.h"),
+           os.path.join(ROOT, "include", "ort.h")]
+    if not os.path.exists(TOOL) or any(os.path.getmtime(s) > os.path.getmtime(TOOL) for s in src):
+        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+        cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or (hipcc if os.path.exists(hipcc) else None)
+        if cxx is None:
+            pytest.skip("tools/launch_plan is not built and there is no C++ compiler to build it with")
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tools"), "launch_plan", "CXX=" + cxx])
+    return TOOL
+
+
+def plan(tool, env=None, **kw):
+    """the plan for a 256-unit device; by default a diffuse scene with all tables, a 6 MB tree and a cheap one (SAH cost 0.05)"""
+    args = dict(cu_count=CU, diffuse_only=1, fast_tree_bytes=6 << 20, sah_cost=0.05)
+    args.update(kw)
+    e = {k: v for k, v in os.environ.items() if k not in KNOBS}
+    e.update(env or {})
+    r = subprocess.run([tool] + ["%s=%s" % kv for kv in args.items()], env=e, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    return json.loads(r.stdout)
+
+
+def kernel(p):
+    """the plan's kernel in words"""
+    if p["wavefront"]:
+        return "wavefront"
+    name = "five" if p["five"] else "exchange" if p["exchange"] else "wide" if p["wide"] else "plain"
+    return name + "".join("+" + f for f in ("counters", "diffuse", "tabs", "implicit") if p[f])
+
+
+HD = dict(width=1920, height=1080, chunk=64)   # 32 400 blocks of 8x8
+UHD = dict(width=3840, height=2160, chunk=64)  # 129 600
+SMALL = dict(width=256, height=256, spp=16, chunk=4)  # what the GPU parity tests render
+
+
+# ---- the five BASELINE configurations ---------------------------------------------------------------------------------
+def test_c3_headline_frame_runs_the_plain_loop_at_four_waves(tool):
+    p = plan(tool, sah_cost=0.076, spp=1024, **HD)
+    jobs = 32400 * 64 * 16
+    assert kernel(p) == "plain+diffuse+tabs+implicit"
+    assert (p["grid"], p["refill_below"], p["descend_below"], p["block_major"], p["job_batch"]) == (1024, 16, 8, 1, 128)
+    assert p["job_count"] == jobs and jobs >= 96 * LANES
+    assert p["batch_until"] == jobs - 16 * LANES  # batches of 128 stop 16 jobs per lane before the end
+    assert p["partial_bytes"] == jobs * 12 and p["stash_bytes"] == 0 and p["drain_bytes"] == 0
+
+
+def test_c3_eight_way_shard_draws_batches_of_64(tool):
+    p = plan(tool, sah_cost=0.076, spp=1024, shard_index=0, shard_count=8, **HD)
+    jobs = 4050 * 64 * 16  # 15.8 jobs per lane
+    assert kernel(p) == "plain+diffuse+tabs+implicit" and p["grid"] == 1024
+    assert (p["job_count"], p["job_batch"], p["batch_until"]) == (jobs, 64, jobs - 8 * LANES)
+
+
+def test_c4_dwarf_room_takes_the_ray_exchange(tool):
+    p = plan(tool, sah_cost=0.11, spp=512, **UHD)
+    jobs = 129600 * 64 * 8
+    assert kernel(p).startswith("exchange+diffuse") and p["grid"] == 1024
+    assert (p["refill_below"], p["descend_below"], p["job_batch"]) == (24, 8, 128)
+    assert p["endgame_from"] == jobs - 4 * LANES  # the stashes drain over the last four jobs per lane
+    assert (p["capL"], p["capR"], p["long_min"], p["long_refill"], p["inflight_cap"], p["park_min"]) == (128, 192, 64, 32, 64, 1)
+    # per wave: L records of 9 float4 and L stacks of 24 / 4 float4 for 128 paths, R records of 9 float4 for 192
+    assert p["stash_wave_f4"] == (9 + 24 // 4) * 128 + 9 * 192
+    assert p["stash_bytes"] == 1024 * 4 * p["stash_wave_f4"] * 16
+
+
+def test_c2_all_lobes_scene_runs_five_waves(tool):
+    p = plan(tool, diffuse_only=0, spp=1024, **HD)
+    assert kernel(p) == "five+tabs+implicit" and p["grid"] == 5 * CU
+    assert (p["refill_below"], p["descend_below"]) == (16, 8)
+
+
+def test_c5_tree_out_of_the_l2_runs_five_waves_with_later_exits(tool):
+    p = plan(tool, fast_tree_bytes=86 << 20, sah_cost=0.5, spp=4096, **UHD)  # SAH cost and launch length would earn the exchange
+    assert kernel(p) == "five+diffuse+tabs+implicit" and p["grid"] == 5 * CU
+    assert (p["refill_below"], p["descend_below"]) == (32, 16)
+
+
+# ---- the crossovers, one step either side ----------------------------------------------------------------------------
+def test_exchange_from_an_sah_cost_of_0_09(tool):
+    assert plan(tool, sah_cost=0.09, spp=512, **UHD)["exchange"] == 1
+    assert kernel(plan(tool, sah_cost=0.0899, spp=512, **UHD)) == "plain+diffuse+tabs+implicit"
+
+
+def test_exchange_from_24_jobs_per_lane(tool):
+    at = plan(tool, sah_cost=0.2, policy="pixel", width=3072, height=2048, spp=4)
+    below = plan(tool, sah_cost=0.2, policy="pixel", width=3072, height=2040, spp=4)
+    assert at["job_count"] == 24 * LANES and at["exchange"] == 1
+    assert below["job_count"] == 24 * LANES - 384 * 64 and below["exchange"] == 0
+
+
+def test_batches_of_128_from_96_jobs_per_lane(tool):
+    at = plan(tool, width=3072, height=2048, spp=4, chunk=1)
+    below = plan(tool, width=3072, height=2040, spp=4, chunk=1)
+    assert at["job_count"] == 96 * LANES and (at["job_batch"], at["batch_until"]) == (128, 80 * LANES)
+    assert (below["job_batch"], below["batch_until"]) == (64, below["job_count"] - 8 * LANES)
+
+
+def test_cache_residency_ends_at_16_mb(tool):
+    at = plan(tool, fast_tree_bytes=16 << 20, spp=1024, **HD)
+    over = plan(tool, fast_tree_bytes=(16 << 20) + 1, spp=1024, **HD)
+    assert (kernel(at), at["refill_below"], at["descend_below"]) == ("plain+diffuse+tabs+implicit", 16, 8)
+    assert (kernel(over), over["refill_below"], over["descend_below"]) == ("five+diffuse+tabs+implicit", 32, 16)
+    forced = plan(tool, {"ORT_CACHE_RESIDENT": "0"}, spp=1024, **HD)  # A/B runs
+    assert (kernel(forced), forced["refill_below"], forced["descend_below"]) == ("five+diffuse+tabs+implicit", 32, 16)
+    assert kernel(plan(tool, {"ORT_CACHE_RESIDENT": "1"}, fast_tree_bytes=86 << 20, spp=1024, **HD)) == "plain+diffuse+tabs+implicit"
+
+
+# ---- what the GPU tests force is what they get ---------------------------------------------------------------------------
+@pytest.mark.parametrize("policy", ["chunk", "pixel"])
+def test_waves5_forces_the_five_waves_build(tool, policy):
+    a = plan(tool, {"ORT_EXCHANGE": "0", "ORT_WAVES5": "0"}, policy=policy, **SMALL)
+    b = plan(tool, {"ORT_EXCHANGE": "0", "ORT_WAVES5": "1"}, policy=policy, **SMALL)
+    assert kernel(a) == "plain+diffuse+tabs+implicit" and kernel(b) == "five+diffuse+tabs+implicit"
+    assert a["grid"] == b["grid"] == 1024 * (4 if policy == "chunk" else 1) * 64 // 256  # fewer jobs than resident lanes
+
+
+def test_wide_needs_the_wide_tree(tool):
+    assert kernel(plan(tool, {"ORT_WIDE": "1"}, has_wide=1, **SMALL)) == "wide+diffuse+tabs+implicit"
+    assert kernel(plan(tool, {"ORT_WIDE": "1"}, has_wide=1, diffuse_only=0, **SMALL)) == "wide+tabs+implicit"
+    assert kernel(plan(tool, {"ORT_WIDE": "1"}, has_wide=1, counters=1, **SMALL)) == "wide+counters+tabs"
+    assert kernel(plan(tool, {"ORT_WIDE": "1"}, has_wide=0, **SMALL)) == "plain+diffuse+tabs+implicit"
+    assert kernel(plan(tool, {"ORT_WIDE": "0"}, has_wide=1, **SMALL)) == "plain+diffuse+tabs+implicit"
+    assert kernel(plan(tool, has_wide=1, **SMALL)) == "plain+diffuse+tabs+implicit"  # never by itself
+
+
+def test_exchange_forced_needs_all_tables_and_an_implicit_job_space(tool):
+    assert kernel(plan(tool, {"ORT_EXCHANGE": "1"}, **SMALL)).startswith("exchange+diffuse")
+    assert kernel(plan(tool, {"ORT_EXCHANGE": "1"}, policy="pixel", **SMALL)).startswith("exchange+diffuse")
+    assert kernel(plan(tool, {"ORT_EXCHANGE": "1"}, diffuse_only=0, **SMALL)).startswith("exchange+tabs")  # all lobes, when asked
+    assert plan(tool, {"ORT_EXCHANGE": "1"}, **SMALL)["refill_below"] == 24
+    assert plan(tool, {"ORT_EXCHANGE": "1", "ORT_REFILL_BELOW": "16"}, **SMALL)["refill_below"] == 16
+    for missing in (1, 2, 8):  # TAB_PRO, TAB_LIGHTS, TAB_MATS
+        assert kernel(plan(tool, {"ORT_EXCHANGE": "1"}, tab_flags=11 & ~missing, **SMALL)) == "plain+diffuse"
+    assert kernel(plan(tool, {"ORT_EXCHANGE": "1", "ORT_LDS_TABLES": "0"}, **SMALL)) == "plain+diffuse"
+    assert kernel(plan(tool, {"ORT_EXCHANGE": "1"}, explicit_jobs=1, job_count=1024)) == "plain+diffuse+tabs"
+    assert kernel(plan(tool, {"ORT_EXCHANGE": "0"}, sah_cost=0.11, spp=512, **UHD)) == "plain+diffuse+tabs+implicit"
+    # counters: only the diffuse flavour with the ORT_DEBUG_UTIL probes has an exchange build
+    assert kernel(plan(tool, {"ORT_EXCHANGE": "1"}, counters=1, **SMALL)) == "plain+counters+tabs"
+    assert kernel(plan(tool, {"ORT_EXCHANGE": "1", "ORT_DEBUG_UTIL": "1"}, counters=1, **SMALL)) == "exchange+counters+diffuse+tabs"
+
+
+def test_the_other_forcings(tool):
+    assert kernel(plan(tool, {"ORT_KERNEL": "general"}, **SMALL)) == "five+tabs+implicit"  # all lobes: five waves by itself
+    assert kernel(plan(tool, {"ORT_KERNEL": "general", "ORT_WAVES5": "0"}, **SMALL)) == "plain+tabs+implicit"
+    assert kernel(plan(tool, {"ORT_LDS_TABLES": "0"}, **SMALL)) == "plain+diffuse"
+    assert kernel(plan(tool, {"ORT_LDS_TABLES": "0"}, diffuse_only=0, **SMALL)) == "plain"
+    assert kernel(plan(tool, {"ORT_MODE": "wavefront"}, **SMALL)) == "wavefront"
+    assert kernel(plan(tool, {"ORT_MODE": "persistent"}, **SMALL)) == "plain+diffuse+tabs+implicit"
+    assert plan(tool, **SMALL)["block_major"] == 1 and plan(tool, {"ORT_LPT": "0"}, **SMALL)["block_major"] == 0
+    assert plan(tool, policy="pixel", **SMALL)["block_major"] == 0 and plan(tool, width=256, height=256, spp=4, chunk=4)["block_major"] == 0
+    p = plan(tool, {"ORT_JOB_BATCH": "0"}, **SMALL)
+    assert (p["job_batch"], p["batch_until"]) == (0, p["job_count"])  # no tail to hold back: every draw goes to the counter anyway
+    p = plan(tool, {"ORT_JOB_BATCH": "7", "ORT_BATCH_TAIL": "1"}, spp=1024, **HD)
+    assert (p["job_batch"], p["batch_until"]) == (7, p["job_count"] - LANES)
+    assert plan(tool, {"ORT_ENDGAME_JOBS": "0", "ORT_EXCHANGE": "1"}, **SMALL)["endgame_from"] == 1024 * 64 * 4
+
+
+# ---- the silent fall-backs, stated as such -------------------------------------------------------------------------------
+def test_no_five_waves_when_the_two_units_disagree_on_the_argument_layout(tool):
+    for env in ({"ORT_EXCHANGE": "0", "ORT_WAVES5": "1"}, {}):
+        assert kernel(plan(tool, env, diffuse_only=0, w5_layout_ok=0, **SMALL)) == "plain+tabs+implicit"
+    assert plan(tool, fast_tree_bytes=86 << 20, w5_layout_ok=0, **SMALL)["five"] == 0
+
+
+def test_no_five_waves_next_to_a_wide_or_exchange_request_or_without_tables(tool):
+    for env in ({"ORT_WIDE": "1"}, {"ORT_EXCHANGE": "1"}, {"ORT_LDS_TABLES": "0"}, {"ORT_MODE": "wavefront"}):
+        assert plan(tool, dict(env, ORT_WAVES5="1"), **SMALL)["five"] == 0, env
+    assert plan(tool, {"ORT_WAVES5": "1"}, tab_flags=3, **SMALL)["five"] == 0
+
+
+def test_counters_never_run_five_waves_or_the_implicit_variant(tool):
+    for env in ({}, {"ORT_WAVES5": "1", "ORT_EXCHANGE": "0"}, {"ORT_DEBUG_UTIL": "1"}, {"ORT_KERNEL": "general"}):
+        for diffuse_only in (0, 1):
+            p = plan(tool, env, counters=1, diffuse_only=diffuse_only, **SMALL)
+            assert (p["five"], p["implicit"], p["counters"]) == (0, 0, 1), env
+    # the diffuse flavour with counters is the one with the probes
+    assert kernel(plan(tool, counters=1, **SMALL)) == "plain+counters+tabs"
+    assert kernel(plan(tool, {"ORT_DEBUG_UTIL": "1"}, counters=1, **SMALL)) == "plain+counters+diffuse+tabs"
+    assert kernel(plan(tool, {"ORT_LDS_TABLES": "0"}, counters=1, **SMALL)) == "plain+counters"
+
+
+def test_explicit_jobs_run_neither_exchange_nor_five_waves_nor_the_implicit_variant(tool):
+    for env in ({}, {"ORT_EXCHANGE": "1"}, {"ORT_WAVES5": "1", "ORT_EXCHANGE": "0"}, {"ORT_WIDE": "1"}):
+        for diffuse_only in (0, 1):
+            p = plan(tool, env, explicit_jobs=1, job_count=100 * LANES, diffuse_only=diffuse_only, sah_cost=0.5, has_wide=1)
+            assert kernel(p) == ("plain+diffuse+tabs" if diffuse_only else "plain+tabs"), env
+            assert p["block_major"] == 0 and p["partial_bytes"] == 0
+    assert kernel(plan(tool, {"ORT_WIDE": "1"}, explicit_jobs=1, job_count=1024, has_wide=1, counters=1)) == "wide+counters+tabs"
+
+
+# ---- clamps ---------------------------------------------------------------------------------------------------------
+VALUES = ["0", "1", "5", "63", "64", "65", "128", "129", "1000", "100000"]
+
+
+@pytest.mark.parametrize("long_min", VALUES)
+def test_exchange_knobs_cannot_stall_a_wave(tool, long_min):
+    for cap in VALUES:
+        for refill in ("0", "64", "1000"):
+            p = plan(tool, {"ORT_EXCHANGE": "1", "ORT_LONG_MIN": long_min, "ORT_INFLIGHT_CAP": cap, "ORT_LONG_REFILL": refill}, **SMALL)
+            assert p["exchange"] == 1
+            assert p["inflight_cap"] >= p["long_min"] >= 1 and p["long_min"] <= p["capL"] == 128
+            assert p["long_min"] == min(max(int(long_min), 1), 128) and p["inflight_cap"] == max(int(cap), p["long_min"])
+            assert p["long_refill"] == min(int(refill), 64)
+
+
+@pytest.mark.parametrize("exchange", ["0", "1"])
+def test_loop_exit_thresholds_stay_in_range(tool, exchange):
+    for v in VALUES:
+        p = plan(tool, {"ORT_EXCHANGE": exchange, "ORT_REFILL_BELOW": v, "ORT_DESCEND_BELOW": v}, **SMALL)
+        assert p["refill_below"] == min(max(int(v), 1), 64) and p["descend_below"] == min(int(v), 64)
+
+
+# ---- the grid -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("jobs", [0, 1, 255, 256, 257, 1000, 256 * 1024 - 1, 256 * 1024, 256 * 1280 + 1, 10**9])
+def test_at_least_one_workgroup_and_never_more_lanes_than_jobs(tool, jobs):
+    for env, kw in (({}, {}), ({"ORT_MODE": "wavefront"}, {}), ({}, {"counters": 1}), ({"ORT_BLOCKS_PER_CU": "8"}, {}), ({"ORT_BLOCKS_PER_CU": "9"}, {})):
+        p = plan(tool, env, explicit_jobs=1, job_count=jobs, **kw)
+        per_cu = 8 if env.get("ORT_BLOCKS_PER_CU") == "8" else 4  # 1..8, anything else: 4
+        assert p["max_blocks"] == CU * per_cu
+        assert p["grid"] == min(max((jobs + 255) // 256, 1), CU * per_cu)
+        assert p["batch_until"] <= p["job_count"] == jobs
+
+
+@pytest.mark.parametrize("w,h", [(1, 1), (8, 8), (9, 8), (64, 64), (1920, 1080)])
+def test_implicit_job_spaces_fill_the_grid_they_need(tool, w, h):
+    blocks = ((w + 7) // 8) * ((h + 7) // 8)
+    for env, per_cu in (({"ORT_WAVES5": "0"}, 4), ({"ORT_WAVES5": "1"}, 5), ({"ORT_EXCHANGE": "1"}, 4)):
+        for policy, per_block in (("pixel", 64), ("chunk", 128)):
+            p = plan(tool, env, policy=policy, width=w, height=h, spp=8, chunk=4)
+            assert p["job_count"] == blocks * per_block and p["five"] == (per_cu == 5)
+            assert p["grid"] == min((p["job_count"] + 255) // 256, CU * per_cu) >= 1
+            assert p["endgame_from"] <= p["job_count"] and p["batch_until"] <= p["job_count"]
+    # a shard that owns no block at all
+    p = plan(tool, width=8, height=8, spp=8, chunk=4, shard_index=3, shard_count=8)
+    assert (p["job_count"], p["grid"]) == (0, 1)
+    # five waves under ORT_BLOCKS_PER_CU keep the grid the upload fixed
+    assert plan(tool, {"ORT_WAVES5": "1", "ORT_BLOCKS_PER_CU": "6"}, spp=1024, **HD)["grid"] == CU * 6

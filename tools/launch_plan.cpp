@@ -1,0 +1,64 @@
+/* Developer tool: what device_render would launch.  The launch policy (csrc/ort_plan.h) is arithmetic on a few facts about the
+   uploaded scene, the render parameters and the knobs, so it runs without a device:
+     [ORT_... knobs] tools/launch_plan key=value ...   ->   the plan, one JSON line
+   keys: the SceneTraits and ort_render_params fields by name, policy=pixel|chunk, counters=1, explicit_jobs=1 job_count=N,
+   w5_layout_ok=0; max_blocks defaults to what an upload on cu_count units fixes.  tests/test_launch_plan.py holds the measured
+   crossovers and the knobs the GPU tests force kernels with against it. */
+#include <stdio.h>
+
+#include "../include/ort.h"
+#include "../offline_raytracer_amd/csrc/ort_plan.h"
+
+int main(int argc, char **argv) {
+    const ort::Knobs kn = ort::read_knobs();
+    ort::SceneTraits t;
+    t.tab_flags = ort::kPlanAllTabs;
+    t.cu_count = 256;
+    ort_render_params p{};
+    p.policy = ORT_POLICY_CHUNK;
+    p.chunk = 1;
+    p.rr = 0.8f;
+    bool explicit_jobs = false, w5_layout_ok = true;
+    unsigned long long job_count = 0;
+    for (int i = 1; i < argc; ++i) {
+        const char *eq = strchr(argv[i], '=');
+        const size_t n = eq ? (size_t)(eq - argv[i]) : 0;
+        const char *v = eq ? eq + 1 : "";
+        auto is = [&](const char *key) { return strlen(key) == n && strncmp(argv[i], key, n) == 0; };
+        if (is("diffuse_only")) t.diffuse_only = atoi(v) != 0;
+        else if (is("tab_flags")) t.tab_flags = (uint32_t)strtoul(v, nullptr, 0);
+        else if (is("fast_tree_bytes")) t.fast_tree_bytes = (size_t)strtoull(v, nullptr, 0);
+        else if (is("sah_cost")) t.sah_cost = strtof(v, nullptr);
+        else if (is("has_wide")) t.has_wide = atoi(v) != 0;
+        else if (is("cu_count")) t.cu_count = atoi(v);
+        else if (is("max_blocks")) t.max_blocks = (unsigned int)strtoul(v, nullptr, 0);
+        else if (is("width")) p.width = atoi(v);
+        else if (is("height")) p.height = atoi(v);
+        else if (is("x0")) p.x0 = atoi(v);
+        else if (is("y0")) p.y0 = atoi(v);
+        else if (is("x1")) p.x1 = atoi(v);
+        else if (is("y1")) p.y1 = atoi(v);
+        else if (is("policy")) p.policy = strcmp(v, "pixel") == 0 ? ORT_POLICY_PIXEL : ORT_POLICY_CHUNK;
+        else if (is("spp")) p.spp = (uint32_t)strtoul(v, nullptr, 0);
+        else if (is("chunk")) p.chunk = (uint32_t)strtoul(v, nullptr, 0);
+        else if (is("counters")) p.flags |= atoi(v) ? ORT_RENDER_COUNTERS : 0;
+        else if (is("shard_index")) p.shard_index = (uint32_t)strtoul(v, nullptr, 0);
+        else if (is("shard_count")) p.shard_count = (uint32_t)strtoul(v, nullptr, 0);
+        else if (is("explicit_jobs")) explicit_jobs = atoi(v) != 0;
+        else if (is("job_count")) job_count = strtoull(v, nullptr, 0);
+        else if (is("w5_layout_ok")) w5_layout_ok = atoi(v) != 0;
+        else { fprintf(stderr, "launch_plan: unknown argument %s\n", argv[i]); return 2; }
+    }
+    if (!t.max_blocks) t.max_blocks = ort::upload_max_blocks(t.cu_count, kn);
+    if (!explicit_jobs && p.policy == ORT_POLICY_CHUNK && p.chunk == 0) { fprintf(stderr, "launch_plan: chunk=0\n"); return 2; }
+    const ort::LaunchPlan l = ort::plan_render(t, p, explicit_jobs, job_count, w5_layout_ok, kn);
+    printf("{\"wavefront\": %d, \"exchange\": %d, \"five\": %d, \"wide\": %d, \"counters\": %d, \"diffuse\": %d, \"tabs\": %d, \"implicit\": %d, \"util\": %d, "
+           "\"grid\": %u, \"mode\": %d, \"nchunks\": %u, \"job_count\": %llu, \"my_blocks\": %u, \"refill_below\": %d, \"descend_below\": %d, "
+           "\"capL\": %u, \"capR\": %u, \"long_min\": %u, \"long_refill\": %u, \"inflight_cap\": %u, \"park_min\": %u, \"endgame_from\": %llu, "
+           "\"stash_wave_f4\": %u, \"block_major\": %u, \"job_batch\": %u, \"batch_until\": %llu, \"partial_bytes\": %zu, \"stash_bytes\": %zu, "
+           "\"drain_bytes\": %zu, \"max_blocks\": %u}\n",
+           l.wavefront, l.exchange, l.five, l.wide, l.counters, l.diffuse, l.tabs, l.implicit, l.util, l.grid, l.mode, l.nchunks, l.job_count,
+           l.blocks.my_blocks, l.refill_below, l.descend_below, l.capL, l.capR, l.long_min, l.long_refill, l.inflight_cap, l.park_min,
+           l.endgame_from, l.stash_wave_f4, l.block_major, l.job_batch, l.batch_until, l.partial_bytes, l.stash_bytes, l.drain_bytes, t.max_blocks);
+    return 0;
+}
