@@ -159,7 +159,12 @@ int ort_scene_get_tree_info(const ort_scene *scene, ort_tree_info *out);
 
 /* ---- device ---------------------------------------------------------------------- */
 int ort_device_count(int *count);
-/* copies the committed scene into the HBM of HIP device <device> (hipSetDevice) */
+/* copies the committed scene into the HBM of HIP device <device> (hipSetDevice).  Also decided here, once per upload: which of
+ * the scene's small read-only tables fit the slots the kernels keep in LDS -- up to 48 materials (material 0, "no hit",
+ * included), up to 64 lights, up to 40 float4 of the commit's prologue shapes (a box takes 2, a sphere 1, a cylinder 4).  A
+ * scene past any of the three (48 surface materials, 65 lights) renders the same image through the kernels that read all of
+ * these tables from HBM, and without the ray exchange, the five-waves build, the implicit job spaces and the wide tree; ray
+ * queries depend on the prologue's size alone.  The speed of that form has not been measured. */
 int ort_scene_upload(ort_scene *scene, int device);
 
 /* ---- the render call ---------------------------------------------------------------

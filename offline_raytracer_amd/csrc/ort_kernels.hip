@@ -19,7 +19,9 @@ namespace ort {
 using namespace ortd;
 
 static_assert(kPlanBlock == (uint32_t)kBlock && kPlanLdsStack == (uint32_t)kLdsStack && kPlanStashVecs == kStashVecs && kPlanCapL == kCapL &&
-              kPlanCapR == kCapR && kPlanAllTabs == (TAB_PRO | TAB_LIGHTS | TAB_MATS) && (int)PLAN_JOBS_EXPLICIT == (int)JOBS_EXPLICIT &&
+              kPlanCapR == kCapR && kPlanAllTabs == (TAB_PRO | TAB_LIGHTS | TAB_MATS) && kPlanTabPro == TAB_PRO && kPlanTabLights == TAB_LIGHTS &&
+              kPlanTabMats == TAB_MATS && kPlanTabMatCap == (uint32_t)kTabMatCap && kPlanTabLightCap == (uint32_t)kTabLightCap &&
+              kPlanTabProCap == (uint32_t)kTabProCap && (int)PLAN_JOBS_EXPLICIT == (int)JOBS_EXPLICIT &&
               (int)PLAN_JOBS_PIXEL == (int)JOBS_PIXEL && (int)PLAN_JOBS_CHUNK == (int)JOBS_CHUNK,
               "ort_plan.h counts with the lane code's limits");
 
@@ -163,30 +165,23 @@ int device_upload(Scene *scene, int device, std::string *err) {
         /* the image of the LDS tables: root node, prologue shapes, light flags, materials */
         std::vector<float4> tab((size_t)kTabF4, make_float4(0, 0, 0, 0));
         uint32_t *tw = (uint32_t *)tab.data();
-        d->tab_flags = 0;
+        d->tab_flags = table_fit_flags(mats.size(), lis.size(), t.pro_boxes, t.pro_spheres, t.pro_cyls);
         if (!t.nodes.empty()) memcpy(&tab[kTabRoot], &t.nodes[0], sizeof(DevNode));
         {
             /* the top of the fast tree; slots beyond the tree's size are never addressed */
             const size_t nt = t.nodes.size() < (size_t)kTreeletNodes ? t.nodes.size() : (size_t)kTreeletNodes;
             if (nt) memcpy(&tab[kTabTreelet], t.nodes.data(), nt * sizeof(DevNode));
         }
-        if (2u * t.pro_boxes + t.pro_spheres + 4u * t.pro_cyls <= (uint32_t)kTabProCap) {
+        if (d->tab_flags & TAB_PRO) {
             float4 *q = &tab[kTabPro];
             if (t.pro_boxes) memcpy(q, t.boxes.data(), (size_t)t.pro_boxes * sizeof(DevBox));
             q += 2u * t.pro_boxes;
             if (t.pro_spheres) memcpy(q, t.spheres.data(), (size_t)t.pro_spheres * sizeof(DevSphere));
             q += t.pro_spheres;
             if (t.pro_cyls) memcpy(q, t.cyls.data(), (size_t)t.pro_cyls * sizeof(DevCyl));
-            d->tab_flags |= TAB_PRO;
         }
-        if (lis.size() <= (size_t)kTabLightCap) {
-            if (!lis.empty()) memcpy(tw + 4 * kTabLights, lis.data(), lis.size() * 4u);
-            d->tab_flags |= TAB_LIGHTS;
-        }
-        if (mats.size() <= (size_t)kTabMatCap) {
-            memcpy(&tab[kTabMats], mats.data(), mats.size() * sizeof(DevMaterial));
-            d->tab_flags |= TAB_MATS;
-        }
+        if ((d->tab_flags & TAB_LIGHTS) && !lis.empty()) memcpy(tw + 4 * kTabLights, lis.data(), lis.size() * 4u);
+        if (d->tab_flags & TAB_MATS) memcpy(&tab[kTabMats], mats.data(), mats.size() * sizeof(DevMaterial));
         if ((rc = upload_vec(tab, &d->tab, err))) return rc;
     }
     const RefTree &rt = scene->ref;

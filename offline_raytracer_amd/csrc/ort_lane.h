@@ -2082,7 +2082,8 @@ ORT_D void raycast_lane(const SceneView &sv, const RenderHot &rv, const RaycastI
     flush_counters(rv, c, COUNTERS);
 }
 
-/* TABS: the prologue shapes fit their LDS slot (every scene of this repository); otherwise they are read from HBM */
+/* TABS: the prologue shapes fit their LDS slot (TAB_PRO: at most kTabProCap float4, ort_plan.h table_fit_flags); otherwise they
+   are read from HBM */
 template <bool COUNTERS, bool TABS>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
 raycast_rays(SceneView sv, RenderHot rv, RaycastIO io) {

@@ -73,7 +73,9 @@ inline Knobs read_knobs() {
 constexpr uint32_t kPlanBlock = 256;     /* kBlock: lanes per workgroup */
 constexpr uint32_t kPlanLdsStack = 24;   /* kLdsStack of the four-waves unit, the one with the ray exchange */
 constexpr uint32_t kPlanStashVecs = 9, kPlanCapL = 128, kPlanCapR = 192; /* kStashVecs, kCapL, kCapR */
-constexpr uint32_t kPlanAllTabs = 1u | 2u | 8u; /* TAB_PRO | TAB_LIGHTS | TAB_MATS */
+constexpr uint32_t kPlanTabPro = 1u, kPlanTabLights = 2u, kPlanTabMats = 8u; /* TAB_PRO, TAB_LIGHTS, TAB_MATS */
+constexpr uint32_t kPlanAllTabs = kPlanTabPro | kPlanTabLights | kPlanTabMats;
+constexpr uint32_t kPlanTabMatCap = 48, kPlanTabLightCap = 64, kPlanTabProCap = 40; /* kTabMatCap, kTabLightCap, kTabProCap */
 enum : int { PLAN_JOBS_EXPLICIT = 0, PLAN_JOBS_PIXEL = 1, PLAN_JOBS_CHUNK = 2 }; /* JOBS_* */
 
 /* the resident workgroups of a persistent launch: per_cu for each compute unit (256 units where the device reports none) */
@@ -117,6 +119,20 @@ inline uint64_t render_workspace_bytes(const ort_render_params *p) {
     if (p->policy != ORT_POLICY_CHUNK || p->chunk == 0) return 0;
     uint64_t nch = p->spp / p->chunk;
     return nch * (uint64_t)block_grid_for(p).my_blocks * 64ull * 12ull; /* partial planes hold this shard's blocks only */
+}
+
+/* Which of the scene's small read-only tables fit their LDS slots (TAB_* bits), decided once at upload: the materials, index 0
+   included, up to 48 records; the light types up to 64 lights; the analytic prologue's shapes up to 40 float4 (a box takes two, a
+   sphere one, a cylinder four).  A table at its cap uses the last float4 of its slot.  The render kernels keep the tables in LDS
+   only if all three fit, the ray queries look at the prologue alone; a scene past a cap -- 48 surface materials, 65 lights --
+   is read from HBM by the TABS = false kernels and runs neither the ray exchange, the five-waves build, the implicit job
+   spaces nor the wide tree (plan_render below). */
+inline uint32_t table_fit_flags(size_t material_count, size_t light_count, uint32_t pro_boxes, uint32_t pro_spheres, uint32_t pro_cyls) {
+    uint32_t flags = 0;
+    if (2ull * pro_boxes + pro_spheres + 4ull * pro_cyls <= kPlanTabProCap) flags |= kPlanTabPro;
+    if (light_count <= kPlanTabLightCap) flags |= kPlanTabLights;
+    if (material_count <= kPlanTabMatCap) flags |= kPlanTabMats;
+    return flags;
 }
 
 /* what the policy reads from an uploaded scene, and nothing else */
@@ -193,7 +209,7 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
     const bool counters = (p.flags & ORT_RENDER_COUNTERS) != 0;
     const bool wavefront = kn.wavefront; /* ORT_MODE=wavefront; results are identical */
     const bool diffuse = t.diffuse_only && !kn.general_kernel; /* ORT_KERNEL=general forces the all-lobes kernel (A/B runs; same results) */
-    /* TABS: the scene's small tables all fit their LDS slots (every scene of this repository); otherwise HBM */
+    /* TABS: the scene's small tables all fit their LDS slots (table_fit_flags); otherwise every one of them is read from HBM */
     const bool tabs = (t.tab_flags & kPlanAllTabs) == kPlanAllTabs && kn.lds_tables != 0; /* ORT_LDS_TABLES=0: read them from HBM anyway (A/B runs; same results) */
     /* the plain loop of implicit job spaces exists at FIVE waves per SIMD as well (ort_kernels_w5.hip: 96 registers, 20 LDS stack
        entries, machine LICM off).  Same call, four / five waves: analytic scene 3 302 / 3 514 Mpaths/s, glass room 3 625 / 3 848,

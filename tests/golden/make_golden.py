@@ -9,7 +9,7 @@ What is committed is data only: inputs and the reference's outputs.
   ref_det   = reference + deterministic libm (oracle/det_math.h)  -> bit-exact anchor
   ref_glibc = reference + glibc libm, "as shipped" on this box     -> distance report
 
-usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges]
+usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges | --only-tables]
 """
 import json
 import os
@@ -201,6 +201,52 @@ def golden_c5(manifest):
     np.savez_compressed(os.path.join(HERE, "renders_%s.npz" % name), **arrays)
 
 
+TABLE_VARIANTS = ["at_caps", "mats_over", "lights_over", "ref_limits"]
+TABLE_RENDERS = [("pixel", 64, 48, 8, 1, 7), ("chunk", 64, 48, 16, 4, 7), ("tile32", 64, 64, 2, 1, 12345), ("whole", 24, 16, 4, 1, 999)]
+
+
+def golden_tablescenes(manifest):
+    """the scenes at and past the caps of the kernels' LDS tables (tools/make_tablescene.py; 48 materials, 64 lights) that the
+    reference can load: its loader's counts, its renders -> renders_tables_<variant>.npz, and its closest hits for the 400 rays
+    of the other raycast fixtures -> raycast_tables_<variant>.npz.  The .scn files are regenerated by the tests."""
+    import hashlib
+    import zlib
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import make_tablescene
+    manifest["tablescenes"] = {}
+    for variant in TABLE_VARIANTS:
+        d = tempfile.mkdtemp(prefix="tables_", dir=TMP) + "/"
+        scn, counts = make_tablescene.write_scene(d, stem=variant, **make_tablescene.variants()[variant])
+        dump = os.path.join(d, variant + ".dump")
+        info = run(REF_DET, "scene-dump", scn, d, 64, 48, dump)
+        dg = ref_io.scene_digest(ref_io.read_scene_dump(dump))
+        dg["octree"] = info
+        dg["scn_sha256"] = hashlib.sha256(open(scn, "rb").read()).hexdigest()
+        dg["counts"] = {k: v for k, v in counts.items() if k != "light_types"}
+        dg["renders"] = []
+        arrays = {}
+        for policy, W, H, spp, chunk, seed in TABLE_RENDERS:
+            out = os.path.join(d, "r.f32")
+            js = run(REF_DET, "render", scn, d, W, H, spp, seed, policy, out, chunk)
+            key = "%s_%dx%d_%dspp_c%d_s%d" % (policy, W, H, spp, chunk, seed)
+            arrays[key] = np.fromfile(out, "<f4").reshape(H, W, 3)
+            dg["renders"].append(dict(key=key, policy=policy, width=W, height=H, spp=spp, chunk=chunk, seed=seed,
+                                      shapes_tested=js["shapes_tested"], final_rng=js["final_rng"]))
+        np.savez_compressed(os.path.join(HERE, "renders_tables_%s.npz" % variant), **arrays)
+        rng = np.random.default_rng(zlib.crc32(("tables " + variant).encode()))
+        n = 400
+        o = np.stack([rng.uniform(-2.5, 14.5, n), rng.uniform(-2.5, 14.5, n), rng.uniform(0.05, 8.8, n)], axis=1).astype("<f4")
+        o[: n // 2] = np.stack([rng.uniform(-1.5, 1.5, n // 2), rng.uniform(-1.8, 1.5, n // 2), rng.uniform(0.05, 2.5, n // 2)], axis=1)
+        rays = np.concatenate([o, unit_vectors(rng, n)], axis=1).astype("<f4")
+        rays[n // 2:n // 2 + 100, 0:3] = (5.553228, 2.942755, 2.900874)   # from the camera towards the grid of shapes
+        rays[n // 2:n // 2 + 100, 3:6] = (np.array([-0.84, -0.44, -0.27]) + rng.uniform(-0.2, 0.2, (100, 3))).astype("<f4")
+        rays.tofile(os.path.join(d, "rays.bin"))
+        run(REF_DET, "raycast", scn, d, os.path.join(d, "rays.bin"), os.path.join(d, "hits.bin"))
+        hits = np.fromfile(os.path.join(d, "hits.bin"), dtype=np.dtype([("t", "<f4"), ("n", "<f4", 3), ("mat", "<u4")]))
+        np.savez_compressed(os.path.join(HERE, "raycast_tables_%s.npz" % variant), rays=rays, t=hits["t"], n=hits["n"], mat=hits["mat"])
+        manifest["tablescenes"][variant] = dg
+
+
 def golden_showcase():
     """a crop of an image the reference itself wrote (showcase/1.hdr): header, file size, 32x64 RGBE pixels"""
     raw = open("/root/reference/showcase/1.hdr", "rb").read()
@@ -252,6 +298,11 @@ def main():
         return
     if "--only-showcase" in sys.argv:
         golden_showcase()
+        return
+    if "--only-tables" in sys.argv:  # add / refresh the table-cap scenes' fixtures without touching the others
+        manifest = json.load(open(os.path.join(HERE, "manifest.json")))
+        golden_tablescenes(manifest)
+        json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
         return
     if "--only-c5" in sys.argv:  # add / refresh the C5 fixtures without touching the others
         manifest = json.load(open(os.path.join(HERE, "manifest.json")))
@@ -368,6 +419,7 @@ def main():
         np.savez_compressed(os.path.join(HERE, "raycast_%s.npz" % name), rays=rays, t=hits["t"], n=hits["n"], mat=hits["mat"])
 
     golden_c5(manifest)
+    golden_tablescenes(manifest)
     golden_showcase()
     golden_unit_edges()
     golden_raycast_edges()

@@ -24,10 +24,12 @@ def host_sim():
     return TOOL
 
 
-def _run(tool, scene, w, h, spp, seed, policy, chunk, out, threads, extra=None):
+def _run(tool, scene, w, h, spp, seed, policy, chunk, out, threads, extra=None, base=None):
+    """scene: the name of a scene under data/, or with base (its directory) the path of a .scn"""
     env = dict(os.environ, SIM_THREADS=str(threads))
     env.update(extra or {})
-    r = subprocess.run([tool, os.path.join(DATA, scene + ".scn"), DATA + "/", str(w), str(h), str(spp), str(seed), policy, str(chunk), out],
+    scn, base = (scene, base) if base else (os.path.join(DATA, scene + ".scn"), DATA + "/")
+    r = subprocess.run([tool, scn, base, str(w), str(h), str(spp), str(seed), policy, str(chunk), out],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-1500:]
     return np.fromfile(out, "<f4").reshape(h, w, 3)
@@ -54,3 +56,27 @@ def test_worker_pool_matches_the_oracle(host_sim, api, oracle, tmp_path, scene, 
     sc = api.Scene.load_scn(os.path.join(DATA, scene + ".scn")).commit()
     ref, _ = oracle.OracleScene(sc.flatten(w, h)).render(w, h, spp, 77, policy, chunk=max(chunk, 1), threads=8)
     assert_bits_equal(got, ref, "%s %s on 8 workers vs the oracle" % (scene, policy))
+
+
+@pytest.mark.parametrize("variant", ["mats_over", "lights_over", "ref_limits"])
+def test_lane_code_reads_the_tables_from_their_arrays_past_the_caps(host_sim, api, oracle, manifest, tmp_path, variant):
+    """host_sim runs the TABS = false lane code: materials through load_mat(sv.materials, m), light types through
+    sv.light_is_sphere[li].  The scenes of tools/make_tablescene.py with 49 materials, 65 lights and 100 of each put most of
+    what a path reads past index 48 / 64: the pixels are the compiled reference's (renders_tables_<variant>.npz) and, at a
+    size with ragged 8x8 edge blocks, the oracle's.  (Shown to fail on a scratch copy of ort_lane.h: with the light lookup
+    reading sv.light_is_sphere[li & 63] lights_over and ref_limits go red and every older test of this file and of
+    test_host.py stays green; with load_mat reading material hit_mat & 47 all three variants go red.)"""
+    import table_scenes
+    scene, _, csg = table_scenes.build(api, variant, tmp_path)
+    scn, base = str(tmp_path / (variant + ".scn")), str(tmp_path) + "/"
+    z = np.load(os.path.join(GOLDEN, "renders_tables_%s.npz" % variant))
+    for e in manifest["tablescenes"][variant]["renders"]:
+        threads = 8 if e["policy"] in ("pixel", "chunk", "tile32") else 1
+        got = _run(host_sim, scn, e["width"], e["height"], e["spp"], e["seed"], e["policy"], e["chunk"] if e["policy"] == "chunk" else 0,
+                   str(tmp_path / "g.f32"), threads, base=base)
+        assert_bits_equal(got, z[e["key"]], "%s %s vs the reference" % (variant, e["key"]))
+    scene.commit()
+    for w, h, spp, policy, chunk, extra in ((93, 61, 6, "chunk", 2, {}), (45, 35, 5, "pixel", 0, {"SIM_FORCE_FALLBACK": "0xf"})):
+        got = _run(host_sim, scn, w, h, spp, 77, policy, chunk, str(tmp_path / "o.f32"), 8, extra, base=base)
+        ref, _ = oracle.OracleScene(scene.flatten(w, h), with_reference_csg=csg).render(w, h, spp, 77, policy, chunk=max(chunk, 1), threads=8)
+        assert_bits_equal(got, ref, "%s %s on 8 workers vs the oracle" % (variant, policy))

@@ -212,6 +212,83 @@ def test_explicit_jobs_run_neither_exchange_nor_five_waves_nor_the_implicit_vari
     assert kernel(plan(tool, {"ORT_WIDE": "1"}, explicit_jobs=1, job_count=1024, has_wide=1, counters=1)) == "wide+counters+tabs"
 
 
+# ---- the caps of the LDS tables (table_fit_flags): what fits, and what a scene past a cap runs ---------------------------
+FORCE_ALL = {"ORT_EXCHANGE": "1", "ORT_WAVES5": "1", "ORT_WIDE": "1"}
+PLAIN_HBM = {(0, 1): "plain+diffuse", (0, 0): "plain", (1, 0): "plain+counters", (1, 1): "plain+counters"}  # (counters, diffuse_only)
+
+
+def _at_and_over(tool, at, over, missing):
+    """`at` fits its table and runs the table kernels; `over` loses the one table `missing` and with it the whole family:
+    pt_persistent<false, true, false> / <false, false, false> / <true, false, false>, whatever is asked for"""
+    for policy in ("chunk", "pixel"):
+        a = plan(tool, policy=policy, has_wide=1, **at, **SMALL)
+        assert a["tab_flags"] == 11 and kernel(a) == "plain+diffuse+tabs+implicit", at
+        assert kernel(plan(tool, policy=policy, diffuse_only=0, **at, **SMALL)) == "five+tabs+implicit"
+        assert kernel(plan(tool, {"ORT_EXCHANGE": "1"}, policy=policy, **at, **SMALL)).startswith("exchange+diffuse")
+        assert plan(tool, {"ORT_WAVES5": "1", "ORT_EXCHANGE": "0"}, policy=policy, **at, **SMALL)["five"] == 1
+        for env in ({}, FORCE_ALL):
+            for (counters, diffuse_only), name in PLAIN_HBM.items():
+                p = plan(tool, env, policy=policy, has_wide=1, counters=counters, diffuse_only=diffuse_only, **over, **SMALL)
+                assert p["tab_flags"] == 11 & ~missing, over
+                assert kernel(p) == name, (over, env, counters, diffuse_only)
+                assert (p["exchange"], p["five"], p["wide"], p["implicit"], p["tabs"]) == (0, 0, 0, 0, 0)
+    p = plan(tool, FORCE_ALL, explicit_jobs=1, job_count=4096, has_wide=1, **over)
+    assert kernel(p) == "plain+diffuse" and kernel(plan(tool, explicit_jobs=1, job_count=4096, **at)) == "plain+diffuse+tabs"
+
+
+def test_table_caps_are_the_lane_codes(tool):
+    """the numbers the scenes of tests/table_scenes.py are built from (ort_kernels.hip asserts them equal to kTabMatCap, kTabLightCap, kTabProCap)"""
+    assert plan(tool, **SMALL)["tab_caps"] == {"materials": 48, "lights": 64, "pro_slots": 40}
+    assert plan(tool, **SMALL)["tab_flags"] == 11  # an empty scene fits everywhere
+
+
+def test_48_materials_fit_and_49_do_not(tool):
+    _at_and_over(tool, dict(materials=48), dict(materials=49), 8)
+
+
+def test_64_lights_fit_and_65_do_not(tool):
+    _at_and_over(tool, dict(lights=64), dict(lights=65), 2)
+
+
+def test_40_prologue_slots_fit_and_41_do_not(tool):
+    _at_and_over(tool, dict(pro_boxes=20), dict(pro_boxes=21), 1)            # boxes alone: two float4 each
+    _at_and_over(tool, dict(pro_boxes=10, pro_spheres=4, pro_cyls=4), dict(pro_boxes=10, pro_spheres=5, pro_cyls=4), 1)  # 40, and 41 with an odd sphere count
+    assert plan(tool, pro_boxes=10, pro_spheres=3, pro_cyls=4, **SMALL)["tab_flags"] == 11   # 39
+    assert plan(tool, pro_cyls=10, **SMALL)["tab_flags"] == 11 and plan(tool, pro_cyls=10, pro_spheres=1, **SMALL)["tab_flags"] == 10
+    assert plan(tool, pro_spheres=40, **SMALL)["tab_flags"] == 11 and plan(tool, pro_spheres=41, **SMALL)["tab_flags"] == 10
+
+
+def test_each_table_is_judged_alone_and_an_explicit_tab_flags_wins(tool):
+    assert plan(tool, materials=49, lights=65, pro_boxes=21, **SMALL)["tab_flags"] == 0
+    assert plan(tool, materials=48, lights=64, pro_boxes=20, **SMALL)["tab_flags"] == 11
+    assert plan(tool, materials=300, lights=200, **SMALL)["tab_flags"] == 1
+    assert plan(tool, materials=300, tab_flags=11, **SMALL)["tab_flags"] == 11
+
+
+def test_the_scenes_of_the_gpu_table_tests_select_what_their_docstrings_name(tool):
+    """tests/test_gpu_tables.py: the variants of tools/make_tablescene.py (counts relative to the caps the tool prints) and the
+    kernels they take by themselves; ORT_LDS_TABLES=0 on the repository's own scenes.  The ray queries read TAB_PRO alone
+    (device_raycast): raycast_rays<*, false> where bit 1 of tab_flags is missing."""
+    import table_scenes
+    v = table_scenes.variants()
+    def names(kw, **more):
+        args = dict(materials=kw["materials"], lights=kw["lights"], **more)
+        return (kernel(plan(tool, FORCE_ALL, diffuse_only=0, **args, **SMALL)), kernel(plan(tool, FORCE_ALL, diffuse_only=1, **args, **SMALL)),
+                kernel(plan(tool, FORCE_ALL, diffuse_only=0, counters=1, **args, **SMALL)), plan(tool, **args, **SMALL)["tab_flags"])
+    assert names(v["at_caps"])[3] == 11 and names(v["at_caps"])[1].startswith("exchange+diffuse")
+    assert kernel(plan(tool, diffuse_only=0, materials=v["at_caps"]["materials"], lights=v["at_caps"]["lights"], **SMALL)) == "five+tabs+implicit"
+    assert names(v["mats_over"]) == ("plain", "plain+diffuse", "plain+counters", 3)          # pt_persistent<false, false, false>, <true, false, false>
+    assert names(v["mats_over_diffuse"]) == ("plain", "plain+diffuse", "plain+counters", 3)  # <false, true, false>: the scene is diffuse_only
+    assert names(v["lights_over"]) == ("plain", "plain+diffuse", "plain+counters", 9)
+    assert names(v["ref_limits"]) == names(v["beyond_ref"]) == ("plain", "plain+diffuse", "plain+counters", 1)
+    # pro_over: 40 boxes in the prologue under ORT_ANALYTIC_PROLOGUE=40, 21 under 21, 20 (the cap) under 20
+    assert names(v["pro_over"], pro_boxes=40) == names(v["pro_over"], pro_boxes=21) == ("plain", "plain+diffuse", "plain+counters", 10)
+    assert names(v["pro_over"], pro_boxes=20)[3] == 11
+    for counters in (0, 1):  # the knob, on scenes that fit
+        assert kernel(plan(tool, {"ORT_LDS_TABLES": "0"}, counters=counters, diffuse_only=0, **SMALL)) == ("plain+counters" if counters else "plain")
+    assert kernel(plan(tool, {"ORT_LDS_TABLES": "0"}, explicit_jobs=1, job_count=1024, diffuse_only=0)) == "plain"
+
+
 # ---- clamps ---------------------------------------------------------------------------------------------------------
 VALUES = ["0", "1", "5", "63", "64", "65", "128", "129", "1000", "100000"]
 

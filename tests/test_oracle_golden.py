@@ -251,3 +251,45 @@ def test_oracle_equals_the_reference_at_baseline_scale(api, oracle, manifest):
         rect = (x0, y0, x0 + 16, y0 + 8)
         img, _ = oracle.OracleScene(scene.flatten(1920, 1080)).render(1920, 1080, 1024, meta["seed"], "chunk", chunk=64, rect=rect, threads=8)
         assert_bits_equal(img[rect[1]:rect[3], rect[0]:rect[2]], z[name + "__det"][:8, :16], name)
+
+
+@pytest.mark.parametrize("variant", ["at_caps", "mats_over", "lights_over", "ref_limits"])
+def test_oracle_on_the_scenes_at_and_past_the_table_caps(api, oracle, manifest, tmp_path_factory, variant):
+    """tools/make_tablescene.py: 48 / 49 materials, 64 / 65 lights, and the most the reference's loader holds (100 materials,
+    100 lights).  The loader agrees with the reference's on every count and array, and the oracle equals the reference's own
+    pixels (renders_tables_<variant>.npz) and closest hits (raycast_tables_<variant>.npz), bit for bit; the conditions that
+    make the scene tell a wrong table index (table_scenes.assert_conditions) hold."""
+    import hashlib
+    import table_scenes
+    d = tmp_path_factory.mktemp("tables_" + variant)
+    scene, counts, csg = table_scenes.build(api, variant, d)
+    meta = manifest["tablescenes"][variant]
+    assert hashlib.sha256(open(os.path.join(str(d), variant + ".scn"), "rb").read()).hexdigest() == meta["scn_sha256"]
+    si = scene.info()
+    for kind, n in (("materials", si.material_count), ("spheres", si.sphere_count), ("boxes", si.box_count), ("cylinders", si.cylinder_count),
+                    ("lights", si.light_count), ("meshes", si.mesh_count)):
+        assert n == meta["octree"][kind] == counts[kind], kind
+    assert si.triangle_count == counts["triangles"]
+    scene.commit()
+    flat = scene.flatten(table_scenes.W, table_scenes.H)
+    dg = ref_io.scene_digest(flat)
+    for k in ("materials_sha256", "spheres_sha256", "boxes_sha256", "cylinders_sha256", "lights"):
+        assert dg[k] == meta[k], k
+    osc = oracle.OracleScene(flat, with_reference_csg=csg)
+    table_scenes.assert_conditions(variant, scene, osc, flat)
+    st = osc.tree_stats()
+    assert (st["nodes"], st["nonempty_leaves"], st["record_bytes"]) == (meta["octree"]["octree_nodes"], meta["octree"]["octree_leaves"], meta["octree"]["record_bytes"])
+    z = np.load(os.path.join(GOLDEN, "renders_tables_%s.npz" % variant))
+    assert len(meta["renders"]) == 4
+    for e in meta["renders"]:
+        o2 = oracle.OracleScene(scene.flatten(e["width"], e["height"]), with_reference_csg=csg)
+        img, rs = o2.render(e["width"], e["height"], e["spp"], e["seed"], e["policy"], chunk=e["chunk"], threads=1)
+        assert_bits_equal(img, z[e["key"]], "%s %s" % (variant, e["key"]))
+        assert rs["shapes_tested"] == e["shapes_tested"], e["key"]
+        if e["policy"] != "tile32":
+            assert rs["final_rng"] == e["final_rng"], e["key"]
+    r = np.load(os.path.join(GOLDEN, "raycast_tables_%s.npz" % variant))
+    t, n, mat = oracle.OracleScene(scene.flatten(64, 64), with_reference_csg=csg).raycast(r["rays"][:, 0:3], r["rays"][:, 3:6])
+    assert_bits_equal(t, r["t"], "t")
+    assert_bits_equal(n, r["n"], "normal")
+    assert (mat == r["mat"]).all() and (r["mat"] >= 7).sum() >= 40  # the fixture sees the grid's materials, not the walls alone

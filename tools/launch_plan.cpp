@@ -2,7 +2,8 @@
    uploaded scene, the render parameters and the knobs, so it runs without a device:
      [ORT_... knobs] tools/launch_plan key=value ...   ->   the plan, one JSON line
    keys: the SceneTraits and ort_render_params fields by name, policy=pixel|chunk, counters=1, explicit_jobs=1 job_count=N,
-   w5_layout_ok=0; max_blocks defaults to what an upload on cu_count units fixes.  tests/test_launch_plan.py holds the measured
+   w5_layout_ok=0; max_blocks defaults to what an upload on cu_count units fixes.  tab_flags, where not given, follows from
+   materials= (index 0 included), lights=, pro_boxes=, pro_spheres=, pro_cyls= as at upload (table_fit_flags; all 0 by default).  tests/test_launch_plan.py holds the measured
    crossovers and the knobs the GPU tests force kernels with against it. */
 #include <stdio.h>
 
@@ -18,7 +19,8 @@ int main(int argc, char **argv) {
     p.policy = ORT_POLICY_CHUNK;
     p.chunk = 1;
     p.rr = 0.8f;
-    bool explicit_jobs = false, w5_layout_ok = true;
+    bool explicit_jobs = false, w5_layout_ok = true, tab_flags_given = false;
+    unsigned long materials = 0, lights = 0, pro_boxes = 0, pro_spheres = 0, pro_cyls = 0;
     unsigned long long job_count = 0;
     for (int i = 1; i < argc; ++i) {
         const char *eq = strchr(argv[i], '=');
@@ -26,7 +28,12 @@ int main(int argc, char **argv) {
         const char *v = eq ? eq + 1 : "";
         auto is = [&](const char *key) { return strlen(key) == n && strncmp(argv[i], key, n) == 0; };
         if (is("diffuse_only")) t.diffuse_only = atoi(v) != 0;
-        else if (is("tab_flags")) t.tab_flags = (uint32_t)strtoul(v, nullptr, 0);
+        else if (is("tab_flags")) { t.tab_flags = (uint32_t)strtoul(v, nullptr, 0); tab_flags_given = true; }
+        else if (is("materials")) materials = strtoul(v, nullptr, 0);
+        else if (is("lights")) lights = strtoul(v, nullptr, 0);
+        else if (is("pro_boxes")) pro_boxes = strtoul(v, nullptr, 0);
+        else if (is("pro_spheres")) pro_spheres = strtoul(v, nullptr, 0);
+        else if (is("pro_cyls")) pro_cyls = strtoul(v, nullptr, 0);
         else if (is("fast_tree_bytes")) t.fast_tree_bytes = (size_t)strtoull(v, nullptr, 0);
         else if (is("sah_cost")) t.sah_cost = strtof(v, nullptr);
         else if (is("has_wide")) t.has_wide = atoi(v) != 0;
@@ -49,6 +56,7 @@ int main(int argc, char **argv) {
         else if (is("w5_layout_ok")) w5_layout_ok = atoi(v) != 0;
         else { fprintf(stderr, "launch_plan: unknown argument %s\n", argv[i]); return 2; }
     }
+    if (!tab_flags_given) t.tab_flags = ort::table_fit_flags(materials, lights, (uint32_t)pro_boxes, (uint32_t)pro_spheres, (uint32_t)pro_cyls);
     if (!t.max_blocks) t.max_blocks = ort::upload_max_blocks(t.cu_count, kn);
     if (!explicit_jobs && p.policy == ORT_POLICY_CHUNK && p.chunk == 0) { fprintf(stderr, "launch_plan: chunk=0\n"); return 2; }
     const ort::LaunchPlan l = ort::plan_render(t, p, explicit_jobs, job_count, w5_layout_ok, kn);
@@ -56,9 +64,10 @@ int main(int argc, char **argv) {
            "\"grid\": %u, \"mode\": %d, \"nchunks\": %u, \"job_count\": %llu, \"my_blocks\": %u, \"refill_below\": %d, \"descend_below\": %d, "
            "\"capL\": %u, \"capR\": %u, \"long_min\": %u, \"long_refill\": %u, \"inflight_cap\": %u, \"park_min\": %u, \"endgame_from\": %llu, "
            "\"stash_wave_f4\": %u, \"block_major\": %u, \"job_batch\": %u, \"batch_until\": %llu, \"partial_bytes\": %zu, \"stash_bytes\": %zu, "
-           "\"drain_bytes\": %zu, \"max_blocks\": %u}\n",
+           "\"drain_bytes\": %zu, \"max_blocks\": %u, \"tab_flags\": %u, \"tab_caps\": {\"materials\": %u, \"lights\": %u, \"pro_slots\": %u}}\n",
            l.wavefront, l.exchange, l.five, l.wide, l.counters, l.diffuse, l.tabs, l.implicit, l.util, l.grid, l.mode, l.nchunks, l.job_count,
            l.blocks.my_blocks, l.refill_below, l.descend_below, l.capL, l.capR, l.long_min, l.long_refill, l.inflight_cap, l.park_min,
-           l.endgame_from, l.stash_wave_f4, l.block_major, l.job_batch, l.batch_until, l.partial_bytes, l.stash_bytes, l.drain_bytes, t.max_blocks);
+           l.endgame_from, l.stash_wave_f4, l.block_major, l.job_batch, l.batch_until, l.partial_bytes, l.stash_bytes, l.drain_bytes, t.max_blocks,
+           t.tab_flags, ort::kPlanTabMatCap, ort::kPlanTabLightCap, ort::kPlanTabProCap);
     return 0;
 }
