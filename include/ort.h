@@ -269,6 +269,31 @@ int ort_raycast(ort_scene *scene, const float *rays, uint64_t count, ort_hit *hi
 int ort_raycast_device(ort_scene *scene, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags,
                        void *hip_stream, ort_stats *stats);
 
+/* ---- occlusion ray queries ------------------------------------------------------------
+ * "Is anything in the way before tmax?" -- shadow rays, ambient occlusion, line of sight.  With h the closest hit
+ * ort_raycast returns for rays[i] (the reference's raycast_top_most_node answer, bit for bit):
+ *     occluded[i] = (h.mat != 0 && h.t < tmax[i]) ? 1 : 0
+ * Rays as for ort_raycast (24 B each, d not normalised, any IEEE-754 bits); tmax[i] is in units of the ray parameter,
+ * the same t as ort_hit.t.  The comparison is the IEEE one: a NaN tmax or a NaN h.t gives 0; tmax <= 0, -0.0 and
+ * -inf give 0; a miss (t = FLT_MAX, mat = 0) gives 0 for every tmax, +inf included; tmax == h.t gives 0 (strict),
+ * the next float above h.t gives 1.  tmax == NULL means no limit: the answers of tmax[i] = +inf.  The output is one
+ * byte per ray, exactly 0 or 1 (the layout of a bool tensor).  occluded[i] answers rays[i]; results do not depend on
+ * count, order or how the batch is sliced.  There is no tmin: the intersectors' own threshold (1e-6) stands.
+ * The traversal never looks beyond tmax, writes one byte instead of 24 and needs no shape table; the rays that
+ * ort_raycast sends to the exact octree walk take it here too (occluded_rays).
+ * flags and stats as for ort_raycast.  rays must be 8-byte aligned, a non-NULL tmax 4-byte aligned.  count == 0 returns
+ * ORT_OK without a launch, whatever the other arguments.  Otherwise errors are reported before any device work, in
+ * this order: ORT_ERR_INVALID (null scene, rays or occluded; misaligned rays or tmax), ORT_ERR_STATE (scene not
+ * committed), ORT_ERR_NO_DEVICE (not uploaded). */
+
+/* host rays (and limits) in, host bytes out; synchronous (staged through device buffers kept per scene, in bounded slices) */
+int ort_occluded(ort_scene *scene, const float *rays, const float *tmax, uint64_t count, uint8_t *occluded, uint32_t flags,
+                 ort_stats *stats);
+/* DEVICE rays, limits (may be NULL) and bytes on the scene's device; enqueued on hip_stream (NULL = the default
+   stream), returns without waiting unless stats != NULL -- as ort_raycast_device */
+int ort_occluded_device(ort_scene *scene, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded,
+                        uint32_t flags, void *hip_stream, ort_stats *stats);
+
 /* ---- multi-GPU: block sharding and the one collective -------------------------------------
  * Replaces main()'s shared-memory tile pool (macos_main.mm:565-671: eight pthreads, one queue, one framebuffer)
  * across the GPUs of a node: scene replicated, 8x8 blocks dealt round-robin, every rank renders its blocks into a

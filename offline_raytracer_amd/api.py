@@ -116,7 +116,8 @@ EXPORTS = [
     "ort_render_workspace_bytes", "ort_unit_eval_device", "ort_rgbe", "ort_write_hdr",
     "ort_shard_block_count", "ort_pack_blocks_host", "ort_unpack_blocks_host", "ort_unpack_blocks_device",
     "ort_comm_unique_id", "ort_comm_create", "ort_comm_create_local", "ort_comm_destroy", "ort_gather_framebuffer",
-    "ort_gather_framebuffer_local", "ort_raycast", "ort_raycast_device"]
+    "ort_gather_framebuffer_local", "ort_raycast", "ort_raycast_device",
+    "ort_occluded", "ort_occluded_device"]
 
 _lib = None
 
@@ -182,6 +183,9 @@ def lib():
         L.ort_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
         L.ort_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
                                          C.POINTER(Stats)]
+        L.ort_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
+        L.ort_occluded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                          C.POINTER(Stats)]
         L.ort_rgbe.restype = C.c_uint32
         L.ort_rgbe.argtypes = [C.c_float, C.c_float, C.c_float]
         L.ort_write_hdr.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]
@@ -383,6 +387,37 @@ class Scene:
         _check(lib().ort_raycast_device(self.handle, C.c_void_p(d_rays_ptr), count, C.c_void_p(d_hits_ptr),
                                         RENDER_COUNTERS if counters else 0, C.c_void_p(stream) if stream else None,
                                         C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    # -- occlusion ray queries -------------------------------------------------------------
+    def occluded(self, rays, tmax=None, counters=False):
+        """Is anything in the way before tmax?  occluded[i] = (hit.mat != 0 and hit.t < tmax[i]) with hit the closest hit
+        raycast returns for rays[i]; the comparison is the IEEE one (NaN, zero and negative limits give False).  rays:
+        (N, 6) float32 o.xyz d.xyz; tmax: None (no limit), a scalar (broadcast) or an (N,) array, in units of the ray
+        parameter.  Returns (occluded: bool[N], stats dict); synchronous."""
+        rays = np.ascontiguousarray(rays, dtype="<f4")
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must be an (N, 6) array of o.xyz d.xyz, got shape %s" % (rays.shape,))
+        if tmax is not None:
+            tmax = np.asarray(tmax, dtype="<f4")
+            if tmax.ndim == 0:
+                tmax = np.full(len(rays), tmax, dtype="<f4")
+            if tmax.shape != (len(rays),):
+                raise ValueError("tmax must be a scalar or an (N,) array with N = %d, got shape %s" % (len(rays), tmax.shape))
+            tmax = np.ascontiguousarray(tmax)
+        out = np.zeros(len(rays), np.bool_)
+        st = Stats()
+        _check(lib().ort_occluded(self.handle, rays.ctypes.data, tmax.ctypes.data if tmax is not None else None, len(rays),
+                                  out.ctypes.data, RENDER_COUNTERS if counters else 0, C.byref(st)))
+        return out, st.as_dict()
+
+    def occluded_device(self, d_rays_ptr, d_tmax_ptr, count, d_out_ptr, stream=None, counters=False, want_stats=False):
+        """Device rays (count x 6 float32) and limits (count float32, or None: no limit) -> device bytes (count, each 0 or
+        1: a torch.bool tensor), raw pointers on the scene's device.  Enqueued on stream; waits only when want_stats."""
+        st = Stats() if want_stats else None
+        _check(lib().ort_occluded_device(self.handle, C.c_void_p(d_rays_ptr), C.c_void_p(d_tmax_ptr) if d_tmax_ptr else None,
+                                         count, C.c_void_p(d_out_ptr), RENDER_COUNTERS if counters else 0,
+                                         C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
     def triangle_of(self, index):

@@ -397,6 +397,42 @@ static int ort_raycast_device_impl(ort_scene *s, const void *d_rays, uint64_t co
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
+/* occlusion queries: count == 0 is OK whatever else is passed; then argument errors, then state errors */
+static int check_occluded(const ort_scene *s, const void *rays, const void *tmax, const void *occluded) {
+    if (!s) return fail(ORT_ERR_INVALID, "null scene");
+    if (!rays || !occluded) return fail(ORT_ERR_INVALID, "null rays or occluded");
+    if ((uintptr_t)rays & 7u) return fail(ORT_ERR_INVALID, "rays must be 8-byte aligned");
+    if ((uintptr_t)tmax & 3u) return fail(ORT_ERR_INVALID, "tmax must be 4-byte aligned");
+    if (!s->tree.built) return fail(ORT_ERR_STATE, "ort_scene_commit has not been called");
+    if (!s->dev) return fail(ORT_ERR_NO_DEVICE, "scene is not resident on a HIP device: call ort_scene_upload (no CPU fallback)");
+    return ORT_OK;
+}
+
+static int ort_occluded_impl(ort_scene *s, const float *rays, const float *tmax, uint64_t count, uint8_t *occluded, uint32_t flags, ort_stats *stats) {
+    if (count == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return ORT_OK;
+    }
+    int rc = check_occluded(s, rays, tmax, occluded);
+    if (rc != ORT_OK) return rc;
+    std::string err;
+    rc = ort::device_occluded(s, rays, nullptr, tmax, count, occluded, nullptr, flags, nullptr, stats, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
+static int ort_occluded_device_impl(ort_scene *s, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded, uint32_t flags, void *hip_stream,
+                                    ort_stats *stats) {
+    if (count == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return ORT_OK;
+    }
+    int rc = check_occluded(s, d_rays, d_tmax, d_occluded);
+    if (rc != ORT_OK) return rc;
+    std::string err;
+    rc = ort::device_occluded(s, nullptr, d_rays, d_tmax, count, nullptr, d_occluded, flags, hip_stream, stats, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
 static int ort_render_workspace_bytes_impl(const ort_render_params *p, uint64_t *bytes) {
     if (!p || !bytes) return fail(ORT_ERR_INVALID, "null argument");
     *bytes = ort::render_workspace_bytes(p);
@@ -490,6 +526,8 @@ int ort_render_image_device(ort_scene *s, const ort_render_params *p, void *d_ou
 int ort_unit_eval_device(int device, const void *records, uint32_t count, float *out) { return guarded([&]() { return ort_unit_eval_device_impl(device, records, count, out); }); }
 int ort_raycast(ort_scene *s, const float *rays, uint64_t count, ort_hit *hits, uint32_t flags, ort_stats *stats) { return guarded([&]() { return ort_raycast_impl(s, rays, count, hits, flags, stats); }); }
 int ort_raycast_device(ort_scene *s, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_raycast_device_impl(s, d_rays, count, d_hits, flags, hip_stream, stats); }); }
+int ort_occluded(ort_scene *s, const float *rays, const float *tmax, uint64_t count, uint8_t *occluded, uint32_t flags, ort_stats *stats) { return guarded([&]() { return ort_occluded_impl(s, rays, tmax, count, occluded, flags, stats); }); }
+int ort_occluded_device(ort_scene *s, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_occluded_device_impl(s, d_rays, d_tmax, count, d_occluded, flags, hip_stream, stats); }); }
 int ort_render_workspace_bytes(const ort_render_params *p, uint64_t *bytes) { return guarded([&]() { return ort_render_workspace_bytes_impl(p, bytes); }); }
 int ort_shard_block_count(int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, uint64_t *blocks) { return guarded([&]() { return ort_shard_block_count_impl(width, height, shard_index, shard_count, blocks); }); }
 int ort_pack_blocks_host(const float *full_rgb, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, float *packed) { return guarded([&]() { return ort_pack_blocks_host_impl(full_rgb, width, height, shard_index, shard_count, packed); }); }

@@ -89,7 +89,9 @@ struct DeviceScene {
     /* ray queries (device_raycast): the shape table, built at the first query on this upload, and the host path's staging */
     DevBuf prim_src;
     float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0}; /* shapes and camera (raycast_needs_exact) */
+    bool scene_box_known = false;
     DevBuf ray_in, hit_out;
+    DevBuf tmax_in, occ_out; /* occlusion queries (device_occluded): the host path's limits and bytes */
 };
 
 int device_count(int *n, std::string *err) {
@@ -557,6 +559,28 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
 #endif
 constexpr uint64_t kRaycastSlice = 1ull << 22; /* rays per launch of the host form (2 x 96 MB of staging) */
 
+/* the box of everything ort_tree.cpp sized the quadric boxes for (raycast_needs_exact), worked out at the first query of either kind */
+static void ensure_scene_box(Scene *scene, DeviceScene *d) {
+    if (d->scene_box_known) return;
+    /* shapes and camera */
+    float lo[3] = {scene->camera_p.x, scene->camera_p.y, scene->camera_p.z}, hi[3] = {lo[0], lo[1], lo[2]};
+    auto grow = [&](float x, float y, float z, float r) {
+        const float p[3] = {x, y, z};
+        for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], p[k] - r); hi[k] = std::max(hi[k], p[k] + r); }
+    };
+    for (const ort_sphere &q : scene->spheres) grow(q.center.x, q.center.y, q.center.z, fabsf(q.r));
+    for (const ort_box &q : scene->boxes) { grow(q.min.x, q.min.y, q.min.z, 0.0f); grow(q.max.x, q.max.y, q.max.z, 0.0f); }
+    for (const ort_cylinder &q : scene->cylinders) {
+        grow(q.base.x, q.base.y, q.base.z, fabsf(q.r));
+        grow(q.base.x + q.axis.x, q.base.y + q.axis.y, q.base.z + q.axis.z, fabsf(q.r));
+    }
+    for (const HostMesh &m : scene->meshes)
+        for (size_t i = 0; i + 2 < m.vertices.size(); i += 3) grow(m.vertices[i], m.vertices[i + 1], m.vertices[i + 2], 0.0f);
+    memcpy(d->scene_lo, lo, sizeof(lo));
+    memcpy(d->scene_hi, hi, sizeof(hi));
+    d->scene_box_known = true;
+}
+
 /* the inverse of the tree's slot maps, in PrimInfo order (triangles | boxes | cylinders | spheres): slot -> kind << 28 |
    the shape's index in the scene's own arrays.  Built and uploaded at the first query, so that render-only users pay nothing */
 static int ensure_prim_src(Scene *scene, DeviceScene *d, std::string *err) {
@@ -577,40 +601,24 @@ static int ensure_prim_src(Scene *scene, DeviceScene *d, std::string *err) {
     invert(PRIM_SPHERE, d->info_sphere, t.sphere_slot, t.spheres.size());
     for (uint32_t v : src) bijective = bijective && v != kNoPrim;
     if (!bijective) { *err = "internal: the tree's slot maps are not a bijection onto its shape arrays"; return ORT_ERR_INTERNAL; }
-    /* the box of everything ort_tree.cpp sized the quadric boxes for: shapes and camera */
-    float lo[3] = {scene->camera_p.x, scene->camera_p.y, scene->camera_p.z}, hi[3] = {lo[0], lo[1], lo[2]};
-    auto grow = [&](float x, float y, float z, float r) {
-        const float p[3] = {x, y, z};
-        for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], p[k] - r); hi[k] = std::max(hi[k], p[k] + r); }
-    };
-    for (const ort_sphere &q : scene->spheres) grow(q.center.x, q.center.y, q.center.z, fabsf(q.r));
-    for (const ort_box &q : scene->boxes) { grow(q.min.x, q.min.y, q.min.z, 0.0f); grow(q.max.x, q.max.y, q.max.z, 0.0f); }
-    for (const ort_cylinder &q : scene->cylinders) {
-        grow(q.base.x, q.base.y, q.base.z, fabsf(q.r));
-        grow(q.base.x + q.axis.x, q.base.y + q.axis.y, q.base.z + q.axis.z, fabsf(q.r));
-    }
-    for (const HostMesh &m : scene->meshes)
-        for (size_t i = 0; i + 2 < m.vertices.size(); i += 3) grow(m.vertices[i], m.vertices[i + 1], m.vertices[i + 2], 0.0f);
-    memcpy(d->scene_lo, lo, sizeof(lo));
-    memcpy(d->scene_hi, hi, sizeof(hi));
+    ensure_scene_box(scene, d);
     return upload_vec(src, &d->prim_src, err);
 }
 
-/* one launch over count rays at d_rays -> d_hits (device pointers); stats (may be NULL): synchronous, counters added */
-static int launch_raycast(Scene *scene, DeviceScene *d, const void *d_rays, uint64_t count, void *d_hits, bool counters, hipStream_t stream,
-                          ort_stats *stats, std::string *err) {
-    int rc;
-    if ((rc = settle_inflight(d, err))) return rc;
-    const SceneView sv = scene_view(scene, d);
-    RaycastIO io;
+/* what raycast_needs_exact reads, and the rays */
+static RaycastIO ray_query_io(Scene *scene, DeviceScene *d, const void *d_rays) {
+    RaycastIO io{};
     io.rays = (const float2 *)d_rays;
-    io.hits = (uint2 *)d_hits;
-    io.prim_src = d->prim_src.as<const uint32_t>();
     io.tree_spheres = scene->tree.spheres.size() > scene->tree.pro_spheres;
     io.tree_quadrics = io.tree_spheres || scene->tree.cyls.size() > scene->tree.pro_cyls;
     io.tree_boxes = scene->tree.boxes.size() > scene->tree.pro_boxes;
     memcpy(io.lo, d->scene_lo, sizeof(io.lo));
     memcpy(io.hi, d->scene_hi, sizeof(io.hi));
+    return io;
+}
+
+/* the launch policy of a ray query over count rays: the grid, and the job space (the ray array, drawn in batches) uploaded behind hot.c */
+static int ray_query_plan(Scene *scene, DeviceScene *d, uint64_t count, hipStream_t stream, unsigned int *grid_out, RenderHot *hot_out, std::string *err) {
     unsigned int grid = (unsigned int)((count + kBlock - 1) / kBlock);
     if (grid > d->max_blocks) grid = d->max_blocks;
     const unsigned long long lanes = (unsigned long long)grid * kBlock;
@@ -627,15 +635,14 @@ static int launch_raycast(Scene *scene, DeviceScene *d, const void *d_rays, uint
     RenderHot hot{};
     hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
     hot.c = (const ORT_CONSTANT_AS RenderView *)d->rv_dev.p;
-    const bool tabs = (d->tab_flags & TAB_PRO) != 0;
-    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
-    if (counters) {
-        if (tabs) hipLaunchKernelGGL((raycast_rays<true, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
-        else hipLaunchKernelGGL((raycast_rays<true, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
-    } else {
-        if (tabs) hipLaunchKernelGGL((raycast_rays<false, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
-        else hipLaunchKernelGGL((raycast_rays<false, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
-    }
+    *grid_out = grid;
+    *hot_out = hot;
+    return ORT_OK;
+}
+
+/* after the launch of a ray query: mark it in flight; with stats, wait for it and add its time and counters */
+static int ray_query_finish(DeviceScene *d, bool counters, hipStream_t stream, ort_stats *stats, std::string *err) {
+    int rc;
     ORT_HIP(hipGetLastError());
     if (stats) ORT_HIP(hipEventRecord(d->ev1, stream));
     ORT_HIP(hipEventRecord(d->ev_done, stream));
@@ -651,6 +658,59 @@ static int launch_raycast(Scene *scene, DeviceScene *d, const void *d_rays, uint
         if (counters) { stats->rays += c[1]; stats->node_tests += c[2]; stats->tri_tests += c[3]; stats->analytic_tests += c[4]; }
     }
     return ORT_OK;
+}
+
+/* one launch over count rays at d_rays -> d_hits (device pointers); stats (may be NULL): synchronous, counters added */
+static int launch_raycast(Scene *scene, DeviceScene *d, const void *d_rays, uint64_t count, void *d_hits, bool counters, hipStream_t stream,
+                          ort_stats *stats, std::string *err) {
+    int rc;
+    if ((rc = settle_inflight(d, err))) return rc;
+    const SceneView sv = scene_view(scene, d);
+    RaycastIO io = ray_query_io(scene, d, d_rays);
+    io.hits = (uint2 *)d_hits;
+    io.prim_src = d->prim_src.as<const uint32_t>();
+    unsigned int grid = 0;
+    RenderHot hot{};
+    if ((rc = ray_query_plan(scene, d, count, stream, &grid, &hot, err))) return rc;
+    const bool tabs = (d->tab_flags & TAB_PRO) != 0;
+    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
+    if (counters) {
+        if (tabs) hipLaunchKernelGGL((raycast_rays<true, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+        else hipLaunchKernelGGL((raycast_rays<true, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+    } else {
+        if (tabs) hipLaunchKernelGGL((raycast_rays<false, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+        else hipLaunchKernelGGL((raycast_rays<false, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+    }
+    return ray_query_finish(d, counters, stream, stats, err);
+}
+
+/* the same launch for occlusion: count rays at d_rays, limits at d_tmax (may be null) -> count bytes at d_out */
+static int launch_occluded(Scene *scene, DeviceScene *d, const void *d_rays, const void *d_tmax, uint64_t count, void *d_out, bool counters,
+                           hipStream_t stream, ort_stats *stats, std::string *err) {
+    int rc;
+    if ((rc = settle_inflight(d, err))) return rc;
+    const SceneView sv = scene_view(scene, d);
+    OccludedIO io{};
+    io.q = ray_query_io(scene, d, d_rays);
+    io.tmax = (const float *)d_tmax;
+    io.out = (uint8_t *)d_out;
+    const Tree &t = scene->tree;
+    io.mats_nonzero = 1u;
+    for (const std::vector<uint32_t> *m : {&t.tri_mat, &t.box_mat, &t.cyl_mat, &t.sphere_mat})
+        for (uint32_t v : *m) if (v == 0u) io.mats_nonzero = 0u;
+    unsigned int grid = 0;
+    RenderHot hot{};
+    if ((rc = ray_query_plan(scene, d, count, stream, &grid, &hot, err))) return rc;
+    const bool tabs = (d->tab_flags & TAB_PRO) != 0;
+    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
+    if (counters) {
+        if (tabs) hipLaunchKernelGGL((occluded_rays<true, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+        else hipLaunchKernelGGL((occluded_rays<true, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+    } else {
+        if (tabs) hipLaunchKernelGGL((occluded_rays<false, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+        else hipLaunchKernelGGL((occluded_rays<false, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+    }
+    return ray_query_finish(d, counters, stream, stats, err);
 }
 
 int device_raycast(Scene *scene, const float *h_rays, const void *d_rays, uint64_t count, ort_hit *h_hits, void *d_hits, uint32_t flags,
@@ -676,6 +736,34 @@ int device_raycast(Scene *scene, const float *h_rays, const void *d_rays, uint64
         ORT_HIP(hipMemcpyAsync(d->ray_in.p, h_rays + 6u * at, (size_t)n * 24u, hipMemcpyHostToDevice, stream));
         if ((rc = launch_raycast(scene, d, d->ray_in.p, n, d->hit_out.p, counters, stream, stats, err))) return rc;
         ORT_HIP(hipMemcpyAsync(h_hits + at, d->hit_out.p, (size_t)n * sizeof(ort_hit), hipMemcpyDeviceToHost, stream));
+        ORT_HIP(hipStreamSynchronize(stream));
+    }
+    return settle_inflight(d, err);
+}
+
+int device_occluded(Scene *scene, const float *h_rays, const void *d_rays, const void *tmax, uint64_t count, uint8_t *h_out, void *d_out,
+                    uint32_t flags, void *stream_v, ort_stats *stats, std::string *err) {
+    DeviceScene *d = scene->dev;
+    if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
+    ORT_HIP(hipSetDevice(d->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    int rc;
+    ensure_scene_box(scene, d); /* no shape table: a byte names no shape */
+    const bool counters = (flags & ORT_RENDER_COUNTERS) != 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!h_rays) return launch_occluded(scene, d, d_rays, tmax, count, d_out, counters, stream, stats, err);
+    /* host form: bounded slices through the scene's staging buffers, as device_raycast */
+    const uint64_t slice = count < kRaycastSlice ? count : kRaycastSlice;
+    if ((rc = d->ray_in.ensure((size_t)slice * 24u, err))) return rc;
+    if (tmax && (rc = d->tmax_in.ensure((size_t)slice * sizeof(float), err))) return rc;
+    if ((rc = d->occ_out.ensure((size_t)slice, err))) return rc;
+    for (uint64_t at = 0; at < count; at += slice) {
+        const uint64_t n = count - at < slice ? count - at : slice;
+        if ((rc = settle_inflight(d, err))) return rc; /* the staging buffers are the previous slice's until it is done */
+        ORT_HIP(hipMemcpyAsync(d->ray_in.p, h_rays + 6u * at, (size_t)n * 24u, hipMemcpyHostToDevice, stream));
+        if (tmax) ORT_HIP(hipMemcpyAsync(d->tmax_in.p, (const float *)tmax + at, (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
+        if ((rc = launch_occluded(scene, d, d->ray_in.p, tmax ? d->tmax_in.p : nullptr, n, d->occ_out.p, counters, stream, stats, err))) return rc;
+        ORT_HIP(hipMemcpyAsync(h_out + at, d->occ_out.p, (size_t)n, hipMemcpyDeviceToHost, stream));
         ORT_HIP(hipStreamSynchronize(stream));
     }
     return settle_inflight(d, err);

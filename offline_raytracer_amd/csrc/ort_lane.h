@@ -2094,6 +2094,116 @@ raycast_rays(SceneView sv, RenderHot rv, RaycastIO io) {
     raycast_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 
+/* ---- occlusion ray queries (ort_occluded): is anything in the way before tmax? ---------------------------------------
+ * occluded = (h.mat != 0 && h.t < tmax), h the closest hit raycast_rays returns.  The loop of raycast_lane with three
+ * differences.
+ * THE BOUND.  A ray starts with best_t = B = min(tmax, FLT_MAX) instead of FLT_MAX, so the prologue and the tree walk accept
+ * and descend only below B, from the first node on.  What that traversal knows afterwards:
+ *   - no winner: no shape is hit below B.  The reference's answer is some shape's distance or a phantom's, so it is >= B unless
+ *     a phantom lies at or below B (phantoms are never culled by distance: phantom_t is complete) -- resolve_hit's own
+ *     "phantom_t <= best_t" test, with best_t still B, sends exactly those to the exact walk.  Otherwise the answer is 0.
+ *   - a winner W: it is the nearest of ALL shapes (every other one is at or beyond B > t_W), which is chain_verdict's premise.
+ *     Its other premise -- t_other is the nearest other hit, exact inside the 2e-4 window above t_W -- no longer holds as it
+ *     stands: the walk has not seen runners-up at or beyond B.  Everything it has not seen is at or beyond B, so
+ *     min(runner_t, B) bounds the nearest other hit from below, and a smaller t_other only turns CH_ADMIT into CH_UNKNOWN.
+ *     The bound is therefore handed to resolve_hit as a runner-up; the re-traversals of resolve_hit start afresh (bounded by
+ *     the leaf box's entry, or unbounded) and owe nothing to B.  After resolve_hit, h is the reference's closest hit whenever
+ *     that lies below B, and the byte is the contract's comparison.
+ * tmax <= 0 or NaN: 0 without a traversal (a hit has t >= 1e-6).  B is 0 for them, which matters only to the forced walk below.
+ * EARLY END.  The reference's best distance only ever decreases, and it tests every record of every node it visits.  So
+ * if a candidate C with t_C < tmax is in a node the reference is certain to visit, its answer is at most t_C: occluded,
+ * whatever else the scene holds -- provided no shape carries material 0 (mats_nonzero), since the contract also asks
+ * mat != 0 of the final winner.  "Certain to visit" is decidable without knowing the nearest hit (chain_verdict's other
+ * clauses are not: they compare entry distances with the best at that moment): C lies in the root (chain length 0), or
+ * the ray's origin is inside every box of C's chain -- inside the smallest of them when the chain is nested
+ * (kChainNested) -- because a child that contains the origin is admitted unconditionally (ray.cpp:788-803).  The test is made
+ * once, on the prologue's winner, where the wave is converged; a candidate met inside the tree is not tested (a chain
+ * fetch per leaf hit costs more than the rest of the bounded walk) and goes through resolve_hit like every other ray.
+ * EXACT WALK.  The rays raycast_needs_exact names, and those ORT_DEBUG_FORCE_FALLBACK selects, skip the fast traversal
+ * and the early end; resolve_hit re-casts them exactly and their closest hit is compared with tmax.
+ * One byte out per ray, a plain byte store: a wave's ray indices are contiguous, 64 adjacent bytes. */
+struct OccludedIO {
+    RaycastIO q;            /* the rays and what raycast_needs_exact reads; hits and prim_src are null */
+    const float *tmax;      /* count limits, or null: none */
+    uint8_t *out;           /* count bytes, each 0 or 1 */
+    uint32_t mats_nonzero;  /* no shape of the scene carries material 0 */
+};
+
+template <bool COUNTERS, bool TABS>
+ORT_D void occluded_lane(const SceneView &sv, const RenderHot &rv, const OccludedIO &io, const float4 *tab, uint32_t *lds_stack, const int tid,
+                         const uint32_t lane_id, unsigned long long *pool) {
+    uint32_t spill[kSpillStack];
+    PathState P;
+    HitState h;
+    Trav T;
+    Counters c;
+    Prof pr;
+    unsigned long long ray = 0;
+    float bound = 0.0f;
+    bool tracing = false, held = false, more = true; /* held: this lane's ray is finished but its byte is not written yet */
+    for (;;) {
+        if (!tracing) {
+            if (held) {
+                h.runner_t = fminf(h.runner_t, bound); /* the bound is a runner-up the walk may not have seen */
+                resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+                io.out[ray] = (h.hit_mat != 0u && h.best_t < bound) ? (uint8_t)1 : (uint8_t)0;
+                held = false;
+            }
+            if (more) {
+                const unsigned long long j = pool ? draw_job(rv, pool) : ORT_NEXT_JOB(rv.c->next_job);
+                if (j < rv.c->job_count) {
+                    const float2 *r = io.q.rays + 3ull * j;
+                    const float2 a = r[0], b = r[1], e = r[2];
+                    const float tm = io.tmax ? io.tmax[j] : __builtin_inff();
+                    P.org = mk(a.x, a.y, b.x);
+                    P.dir = mk(b.y, e.x, e.y);
+                    ray = j;
+                    if (COUNTERS) c.rays++;
+                    const bool forced = sv.force_fallback_mask != 0xffffffffu && (om_f32_bits(P.dir.x) & sv.force_fallback_mask) == 0u;
+                    bound = (tm > 0.0f) ? fminf(tm, 3.402823466e+38f) : 0.0f;
+                    if (!(tm > 0.0f) && !forced) {
+                        io.out[j] = (uint8_t)0; /* nothing is hit below 1e-6 */
+                    } else {
+                        T.cur = 0;
+                        T.sp = 0;
+                        T.inv_d = mk(1.0f / P.dir.x, 1.0f / P.dir.y, 1.0f / P.dir.z); /* as begin_ray, with the bound for Flt_Max */
+                        reset_hit(h, bound);
+                        prologue_tests<COUNTERS, TABS>(sv, tab, P.org, P.dir, T.inv_d, h, c);
+                        bool seen = false; /* the prologue's winner is one the reference is certain to test */
+                        if (ORT_RARE(forced || raycast_needs_exact(io.q, P.org, P.dir, T.inv_d))) {
+                            T.cur = kTraversalDone; /* no fast traversal: resolve_hit re-casts it exactly (a phantom that could win) */
+                            h.phantom_t = 0.0f;
+                        } else if (io.mats_nonzero && h.hit_prim != kNoPrim) {
+                            const uint32_t word = sv.prim_info[info_index(sv, h.hit_prim)].chain;
+                            const uint32_t first = word & 0x07ffffffu;
+                            seen = (word >> 28) == 0u;
+                            if (!seen && (word & kChainNested)) seen = in_rect_half_open(sv.chain_boxes[2u * first], sv.chain_boxes[2u * first + 1u], P.org);
+                        }
+                        if (seen) io.out[j] = (uint8_t)1;
+                        else tracing = held = true;
+                    }
+                } else {
+                    more = false;
+                }
+            }
+        }
+        /* a lane that is neither tracing nor entitled to another draw has no ray and will get none */
+        if (ORT_BALLOT(tracing || more) == 0ull) break;
+        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS, true>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+    }
+    flush_counters(rv, c, COUNTERS);
+}
+
+template <bool COUNTERS, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+occluded_rays(SceneView sv, RenderHot rv, OccludedIO io) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    if (TABS) fill_tab(sv, lds_tab);
+    occluded_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+}
+
 #endif /* !ORT_W5_TU */
 #endif /* !ORT_HOST_SIM */
 

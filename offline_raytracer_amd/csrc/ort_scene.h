@@ -194,6 +194,10 @@ int device_unit_eval(int device, const void *records, uint32_t n, float *out, st
 /* closest-hit queries: host rays / hits (h_*, synchronous) or device ones (d_*, enqueued on stream) */
 int device_raycast(Scene *scene, const float *h_rays, const void *d_rays, uint64_t count, ort_hit *h_hits, void *d_hits, uint32_t flags,
                    void *stream, ort_stats *stats, std::string *err);
+/* occlusion queries: host rays / limits / bytes (h_rays, tmax a host pointer, synchronous) or device ones (d_rays, tmax a device
+   pointer, enqueued on stream); tmax may be null (no limit) */
+int device_occluded(Scene *scene, const float *h_rays, const void *d_rays, const void *tmax, uint64_t count, uint8_t *h_out, void *d_out,
+                    uint32_t flags, void *stream, ort_stats *stats, std::string *err);
 /* ort_comm.cpp */
 struct Comm;
 uint64_t comm_shard_blocks(int32_t w, int32_t h, uint32_t index, uint32_t count);
