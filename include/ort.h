@@ -238,6 +238,51 @@ int ort_render_image_device(ort_scene *scene, const ort_render_params *params, v
    block layout: a shard keeps 1/shard_count of a frame per chunk) */
 int ort_render_workspace_bytes(const ort_render_params *params, uint64_t *bytes);
 
+/* ---- a batch of camera views in one launch ---------------------------------------------
+ * The render call with the camera moved from the scene to the caller: view_count frames of one committed, uploaded
+ * scene, each from a pose of its own, in ONE persistent launch over [view][block][chunk][pixel] -- a turntable, a camera
+ * path, a stereo pair, many small probe views -- without re-creating the scene (tree, octree, upload) per pose and
+ * without paying a launch's fixed cost per view.
+ *
+ * Frame identity: the output is view_count frames, view-major, each width*height*3 f32 with row 0 at the bottom.  Frame v
+ * is, bit for bit, what ort_render_image would write for the same params with params.seed = views[v].seed if the scene's
+ * camera basis (ort_scene_get_camera) were views[v].camera.  Seeds belong to jobs, so neither the order of the views nor
+ * how the batch is cut into calls can change a bit of a frame.
+ * Seed and rect: params->seed is ignored.  The rect applies to every view; pixels outside it are left untouched in every
+ * frame.
+ * views is a HOST array in both forms; it is copied before the call returns (as the explicit job list of
+ * ort_tiled_raytrace_batch).
+ * Policies: ORT_POLICY_PIXEL and ORT_POLICY_CHUNK only.  TILE32 and WHOLE, shard_count > 1 and ORT_RENDER_PACKED return
+ * ORT_ERR_UNSUPPORTED: a multi-GPU caller deals views to GPUs, not blocks.
+ * view_count == 0 returns ORT_OK without a launch, whatever the other arguments.  view_count above ORT_MAX_VIEWS is
+ * ORT_ERR_INVALID.
+ * Where a camera may stand: the fast tree's quadric boxes are sized for ray origins within the box of all shapes and the
+ * scene's own camera_p, with 0.25 of slack per side (ort_scene_commit; DESIGN.md, render_views).  A view is accepted only
+ * if its aperture's bounding box -- per component k, p_k - 0.1 z_k +- 0.1 |x_k| +- 0.1 |y_k| -- has finite components and
+ * lies inside that box grown by 0.25 per side; otherwise the call returns ORT_ERR_UNSUPPORTED and ort_last_error() names
+ * the first offending view.  Bounce rays start at hits and need no rule.  A caller who needs a camera further out creates
+ * the scene with a camera_p out there.
+ * Errors are reported before any device work, in this order: ORT_ERR_INVALID (nulls, empty or bad params exactly as
+ * ort_render_image judges them, view cap exceeded), ORT_ERR_UNSUPPORTED (policy, shard, packed, camera outside the box),
+ * ORT_ERR_STATE (scene not committed), ORT_ERR_NO_DEVICE (not uploaded).
+ * stats as for the render call; with ORT_RENDER_COUNTERS paths = view_count * pixels * spp. */
+typedef struct { ort_camera camera; uint32_t seed; } ort_view; /* 52 B */
+#define ORT_MAX_VIEWS 4096u
+
+/* macos_main.mm:550-556 for a caller's pose: what ort_scene_get_camera does for the scene's own */
+int ort_camera_from_pose(const float p[3], const float quat_xyzw[4], float height_ratio, int32_t width, int32_t height,
+                         ort_camera *out);
+
+/* host views in, host frames out (view_count * width*height*3 floats; device staging is internal); synchronous */
+int ort_render_views(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
+                     float *out_rgb, ort_stats *stats);
+/* d_out_rgb is a DEVICE pointer (view_count * width*height*3 floats) on the scene's device; enqueued on hip_stream,
+   returns without waiting unless stats != NULL -- as ort_render_image_device */
+int ort_render_views_device(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
+                            void *d_out_rgb, void *hip_stream, ort_stats *stats);
+/* view_count times ort_render_workspace_bytes: the CHUNK partial planes are per view */
+int ort_render_views_workspace_bytes(const ort_render_params *params, uint32_t view_count, uint64_t *bytes);
+
 /* ---- closest-hit ray queries ----------------------------------------------------------
  * Replaces raycast_top_most_node (reference code/ray.cpp:1165-1176): the closest hit of each of the caller's rays,
  * bit for bit the reference's hit_t, hit_normal and hit_mat_index (ties in the reference's test order, phantom

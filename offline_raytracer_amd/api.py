@@ -23,6 +23,7 @@ RENDER_PACKED = 2
 COMM_ID_BYTES = 128
 HIT_TRIANGLE, HIT_BOX, HIT_CYLINDER, HIT_SPHERE = 0, 2, 3, 4
 NO_PRIM = 0xFFFFFFFF
+MAX_VIEWS = 4096  # ORT_MAX_VIEWS
 
 
 class OrtError(RuntimeError):
@@ -97,6 +98,15 @@ class Camera(C.Structure):
     _fields_ = [("p", V3), ("x_axis", V3), ("y_axis", V3), ("z_axis", V3)]
 
 
+class View(C.Structure):
+    """ort_view: one frame of a batch (ort_render_views): its camera basis and its seed."""
+    _fields_ = [("camera", Camera), ("seed", C.c_uint32)]
+
+
+VIEW_DTYPE = np.dtype([("camera", "<f4", (4, 3)), ("seed", "<u4")])
+assert VIEW_DTYPE.itemsize == C.sizeof(View) == 52
+
+
 class Hit(C.Structure):
     """ort_hit: the closest hit of one ray (raycast_top_most_node's hit_t, hit_normal, hit_mat_index) and its shape."""
     _fields_ = [("t", C.c_float), ("n", V3), ("mat", C.c_uint32), ("prim", C.c_uint32)]
@@ -117,7 +127,8 @@ EXPORTS = [
     "ort_shard_block_count", "ort_pack_blocks_host", "ort_unpack_blocks_host", "ort_unpack_blocks_device",
     "ort_comm_unique_id", "ort_comm_create", "ort_comm_create_local", "ort_comm_destroy", "ort_gather_framebuffer",
     "ort_gather_framebuffer_local", "ort_raycast", "ort_raycast_device",
-    "ort_occluded", "ort_occluded_device"]
+    "ort_occluded", "ort_occluded_device",
+    "ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes"]
 
 _lib = None
 
@@ -186,6 +197,11 @@ def lib():
         L.ort_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
         L.ort_occluded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
                                           C.POINTER(Stats)]
+        L.ort_camera_from_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.POINTER(Camera)]
+        L.ort_render_views.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
+        L.ort_render_views_device.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                              C.POINTER(Stats)]
+        L.ort_render_views_workspace_bytes.argtypes = [C.POINTER(RenderParams), C.c_uint32, C.POINTER(C.c_uint64)]
         L.ort_rgbe.restype = C.c_uint32
         L.ort_rgbe.argtypes = [C.c_float, C.c_float, C.c_float]
         L.ort_write_hdr.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]
@@ -218,6 +234,34 @@ def device_count():
 
 def _v3(a):
     return V3(float(a[0]), float(a[1]), float(a[2]))
+
+
+def camera_from_pose(p, quat_xyzw, ratio, width, height):
+    """Camera basis of a pose for a width x height image (macos_main.mm:550-556): rows p, x_axis, y_axis, z_axis as
+    Scene.camera returns them for the scene's own pose.  -> (4, 3) float32."""
+    p = np.ascontiguousarray(p, dtype="<f4")
+    q = np.ascontiguousarray(quat_xyzw, dtype="<f4")
+    if p.shape != (3,) or q.shape != (4,):
+        raise ValueError("p must have 3 components and quat_xyzw 4, got shapes %s and %s" % (p.shape, q.shape))
+    cam = Camera()
+    _check(lib().ort_camera_from_pose(p.ctypes.data, q.ctypes.data, float(ratio), int(width), int(height), C.byref(cam)))
+    return np.array([[v.x, v.y, v.z] for v in (cam.p, cam.x_axis, cam.y_axis, cam.z_axis)], dtype="<f4")
+
+
+def _views(cameras, seeds):
+    """(V, 4, 3) camera bases and (V,) seeds -> the ort_view array of a batch; ValueError on any other shape."""
+    cameras = np.asarray(cameras, dtype="<f4")
+    seeds = np.asarray(seeds)
+    if cameras.ndim != 3 or cameras.shape[1:] != (4, 3):
+        raise ValueError("cameras must be a (V, 4, 3) array of p, x_axis, y_axis, z_axis rows, got shape %s" % (cameras.shape,))
+    if seeds.shape != (len(cameras),):
+        raise ValueError("seeds must be a (V,) array with V = %d, got shape %s" % (len(cameras), seeds.shape))
+    if len(cameras) > MAX_VIEWS:
+        raise ValueError("at most %d views in one call, got %d" % (MAX_VIEWS, len(cameras)))
+    views = np.zeros(len(cameras), VIEW_DTYPE)
+    views["camera"] = cameras
+    views["seed"] = seeds.astype(np.int64) & 0xFFFFFFFF
+    return views
 
 
 class Scene:
@@ -367,6 +411,31 @@ class Scene:
                                              C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
+    # -- a batch of camera views in one launch ----------------------------------------------
+    def render_views(self, cameras, seeds, width, height, spp, policy="chunk", chunk=0, rect=None, rr=0.8, counters=False,
+                     out=None):
+        """One frame per view, in one launch.  cameras: (V, 4, 3) float32 bases (camera_from_pose, Scene.camera); seeds:
+        (V,).  Frame v is what render() gives with seed seeds[v] if the scene's camera were cameras[v].  Host
+        framebuffers in/out: returns (frames[V,H,W,3] float32, stats dict); pixels outside rect keep what out held."""
+        views = _views(cameras, seeds)
+        if out is None:
+            out = np.zeros((len(views), height, width, 3), dtype="<f4")
+        if out.shape != (len(views), height, width, 3) or out.dtype != np.dtype("<f4") or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous float32 array of shape %s" % ((len(views), height, width, 3),))
+        p = self.params(width, height, spp, 0, policy, chunk, rect, rr, counters)
+        st = Stats()
+        _check(lib().ort_render_views(self.handle, C.byref(p), views.ctypes.data, len(views), out.ctypes.data, C.byref(st)))
+        return out, st.as_dict()
+
+    def render_views_device(self, d_out_ptr, params, cameras, seeds, stream=None, want_stats=False):
+        """The same into a device buffer of V frames (raw device pointer, e.g. a (V, H, W, 3) torch tensor's data_ptr()).
+        Enqueued on stream; waits only when want_stats (returns the stats dict).  params.seed is ignored."""
+        views = _views(cameras, seeds)
+        st = Stats() if want_stats else None
+        _check(lib().ort_render_views_device(self.handle, C.byref(params), views.ctypes.data, len(views), C.c_void_p(d_out_ptr),
+                                             C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
     # -- closest-hit ray queries -----------------------------------------------------------
     def raycast(self, rays, counters=False):
         """Closest hit of each ray (raycast_top_most_node, ray.cpp:1165).  rays: (N, 6) float32 o.xyz d.xyz (d need
@@ -492,6 +561,12 @@ def write_hdr(path, image):
 def workspace_bytes(params):
     n = C.c_uint64(0)
     _check(lib().ort_render_workspace_bytes(C.byref(params), C.byref(n)))
+    return n.value
+
+
+def views_workspace_bytes(params, view_count):
+    n = C.c_uint64(0)
+    _check(lib().ort_render_views_workspace_bytes(C.byref(params), view_count, C.byref(n)))
     return n.value
 
 

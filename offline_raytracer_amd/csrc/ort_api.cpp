@@ -35,7 +35,8 @@ uint32_t xorshift(uint32_t *s) {
     return x;
 }
 
-int check_params(const ort_scene *scene, const ort_render_params *p) {
+/* the render parameters by themselves (everything check_params says before it looks at the scene's state) */
+int check_param_values(const ort_scene *scene, const ort_render_params *p) {
     if (!scene || !p) return fail(ORT_ERR_INVALID, "null scene or params");
     if (p->width <= 0 || p->height <= 0) return fail(ORT_ERR_INVALID, "image size must be positive");
     if ((uint64_t)p->width * (uint64_t)p->height > 0x7fffffffull / 3) return fail(ORT_ERR_INVALID, "image too large");
@@ -57,6 +58,12 @@ int check_params(const ort_scene *scene, const ort_render_params *p) {
         if (p->x0 != 0 || p->y0 != 0 || p->x1 != p->width || p->y1 != p->height)
             return fail(ORT_ERR_INVALID, "a packed framebuffer covers the whole image: the rect must be the full frame");
     }
+    return ORT_OK;
+}
+
+int check_params(const ort_scene *scene, const ort_render_params *p) {
+    int rc = check_param_values(scene, p);
+    if (rc != ORT_OK) return rc;
     if (!scene->tree.built) return fail(ORT_ERR_STATE, "ort_scene_commit has not been called");
     if (!scene->dev) return fail(ORT_ERR_NO_DEVICE, "scene is not resident on a HIP device: call ort_scene_upload (no CPU fallback)");
     return ORT_OK;
@@ -433,6 +440,63 @@ static int ort_occluded_device_impl(ort_scene *s, const void *d_rays, const void
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
+/* ---- a batch of views ---- */
+static int ort_camera_from_pose_impl(const float *p, const float *quat_xyzw, float height_ratio, int32_t width, int32_t height, ort_camera *out) {
+    if (!p || !quat_xyzw || !out || width <= 0 || height <= 0) return fail(ORT_ERR_INVALID, "bad argument");
+    ort::camera_from_pose(ort_v3{p[0], p[1], p[2]}, quat_xyzw, height_ratio, width, height, out);
+    return ORT_OK;
+}
+
+/* Where a camera may stand: camera rays start on the aperture (ray.cpp:1233-1239: p + 0.1 cos(a) x + 0.1 sin(a) y - 0.1 z), and the
+   fast tree answers for origins within the scene's box grown by the 0.25 per side build_tree allows (scene_origin_box).  The
+   aperture's bounding box must lie inside it; a non-finite component fails every comparison. */
+static bool view_in_box(const ort_camera &c, const float lo[3], const float hi[3]) {
+    const float p[3] = {c.p.x, c.p.y, c.p.z}, x[3] = {c.x_axis.x, c.x_axis.y, c.x_axis.z}, y[3] = {c.y_axis.x, c.y_axis.y, c.y_axis.z},
+                z[3] = {c.z_axis.x, c.z_axis.y, c.z_axis.z};
+    for (int k = 0; k < 3; ++k) {
+        const float mid = p[k] - 0.1f * z[k], ext = 0.1f * fabsf(x[k]) + 0.1f * fabsf(y[k]);
+        const float a = mid - ext, b = mid + ext;
+        if (!(fabsf(a) <= 3.0e38f) || !(fabsf(b) <= 3.0e38f)) return false;
+        if (!(a >= lo[k] - 0.25f) || !(b <= hi[k] + 0.25f)) return false;
+    }
+    return true;
+}
+
+/* view_count == 0 is OK whatever else is passed; then argument errors, what the call does not do, and the scene's state */
+static int render_views_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, void *d_out, float *h_out,
+                               void *stream, ort_stats *stats) {
+    if (view_count == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return ORT_OK;
+    }
+    if (!views || (!d_out && !h_out)) return fail(ORT_ERR_INVALID, "null views or framebuffer");
+    static_assert(sizeof(ort_view) == 52, "ort_view is a camera and a seed");
+    if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
+    int rc = check_param_values(s, p);
+    if (rc != ORT_OK) return rc;
+    if (p->policy != ORT_POLICY_PIXEL && p->policy != ORT_POLICY_CHUNK)
+        return fail(ORT_ERR_UNSUPPORTED, "a batch of views needs a per-pixel seeding policy (PIXEL or CHUNK)");
+    if (p->shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, "a batch of views is not sharded: deal views to GPUs, not blocks");
+    if (p->flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "a batch of views has no packed framebuffer");
+    float lo[3], hi[3];
+    ort::scene_origin_box(*s, lo, hi);
+    for (uint32_t v = 0; v < view_count; ++v)
+        if (!view_in_box(views[v].camera, lo, hi))
+            return fail(ORT_ERR_UNSUPPORTED, "view " + std::to_string(v) + ": the camera's aperture is not finite or leaves the box of the scene's shapes and its own "
+                                             "camera_p (+ 0.25 per side) that the tree was built for; create the scene with a camera_p out there");
+    if (!s->tree.built) return fail(ORT_ERR_STATE, "ort_scene_commit has not been called");
+    if (!s->dev) return fail(ORT_ERR_NO_DEVICE, "scene is not resident on a HIP device: call ort_scene_upload (no CPU fallback)");
+    std::string err;
+    rc = ort::device_render(s, p, nullptr, 0, d_out, h_out, stream, nullptr, stats, &err, views, view_count);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
+static int ort_render_views_workspace_bytes_impl(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) {
+    if (!p || !bytes) return fail(ORT_ERR_INVALID, "null argument");
+    *bytes = ort::render_views_workspace_bytes(p, view_count);
+    return ORT_OK;
+}
+
 static int ort_render_workspace_bytes_impl(const ort_render_params *p, uint64_t *bytes) {
     if (!p || !bytes) return fail(ORT_ERR_INVALID, "null argument");
     *bytes = ort::render_workspace_bytes(p);
@@ -529,6 +593,10 @@ int ort_raycast_device(ort_scene *s, const void *d_rays, uint64_t count, void *d
 int ort_occluded(ort_scene *s, const float *rays, const float *tmax, uint64_t count, uint8_t *occluded, uint32_t flags, ort_stats *stats) { return guarded([&]() { return ort_occluded_impl(s, rays, tmax, count, occluded, flags, stats); }); }
 int ort_occluded_device(ort_scene *s, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_occluded_device_impl(s, d_rays, d_tmax, count, d_occluded, flags, hip_stream, stats); }); }
 int ort_render_workspace_bytes(const ort_render_params *p, uint64_t *bytes) { return guarded([&]() { return ort_render_workspace_bytes_impl(p, bytes); }); }
+int ort_camera_from_pose(const float p[3], const float quat_xyzw[4], float height_ratio, int32_t width, int32_t height, ort_camera *out) { return guarded([&]() { return ort_camera_from_pose_impl(p, quat_xyzw, height_ratio, width, height, out); }); }
+int ort_render_views(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, float *out_rgb, ort_stats *stats) { return guarded([&]() { return render_views_common(s, p, views, view_count, nullptr, out_rgb, nullptr, stats); }); }
+int ort_render_views_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, void *d_out_rgb, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_views_common(s, p, views, view_count, d_out_rgb, nullptr, hip_stream, stats); }); }
+int ort_render_views_workspace_bytes(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) { return guarded([&]() { return ort_render_views_workspace_bytes_impl(p, view_count, bytes); }); }
 int ort_shard_block_count(int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, uint64_t *blocks) { return guarded([&]() { return ort_shard_block_count_impl(width, height, shard_index, shard_count, blocks); }); }
 int ort_pack_blocks_host(const float *full_rgb, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, float *packed) { return guarded([&]() { return ort_pack_blocks_host_impl(full_rgb, width, height, shard_index, shard_count, packed); }); }
 int ort_unpack_blocks_host(const float *packed, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, float *full_rgb) { return guarded([&]() { return ort_unpack_blocks_host_impl(packed, width, height, shard_index, shard_count, full_rgb); }); }

@@ -67,6 +67,8 @@ struct DeviceScene {
     DevBuf tab; /* image of the LDS tables (kTabF4 float4) */
     DevBuf cold; /* SceneCold */
     DevBuf rv_dev; /* the RenderView of the render in flight (RenderHot::c) */
+    DevBuf view_tab; /* ... and, for a batch of views, its camera table (RenderView::views) */
+    std::vector<float> view_tab_host; /* the source of that upload: the scene's, so that it outlives a call that does not wait */
     uint32_t tab_flags = 0;
     uint32_t light_count = 0;
     bool diffuse_only = false; /* no surface material can enter the specular / transmission blocks */
@@ -287,9 +289,28 @@ static int launch_wavefront(DeviceScene *d, const SceneView &sv, const RenderVie
     return ORT_OK;
 }
 
-/* The path-trace kernel a plan names.  These sixteen variants and the two of ort_kernels_w5.hip are all that is built (each costs
-   its share of minutes of compile time); plan_render produces no other, and one that did would be an error, not a fallback. */
+/* The path-trace kernel a plan names.  These sixteen variants, the six of a batch of views and the two of ort_kernels_w5.hip are
+   all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
+   an error, not a fallback. */
 static int launch_path_tracer(const LaunchPlan &pl, hipStream_t stream, const SceneView &sv, const RenderHot &hot, std::string *err) {
+    if (pl.views) { /* the plain loop with the camera table: counters | diffuse, tabs (implicit follows from both) */
+        if (pl.exchange || pl.five || pl.wide || pl.wavefront || pl.implicit != (!pl.counters && pl.tabs) || (pl.counters && pl.diffuse)) {
+            *err = "internal: no views kernel is built for this launch plan";
+            return ORT_ERR_INTERNAL;
+        }
+#define ORT_PTV(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot); return ORT_OK
+        if (pl.counters) {
+            if (pl.tabs) { ORT_PTV(pt_persistent<true, false, true, false, false, true>); }
+            ORT_PTV(pt_persistent<true, false, false, false, false, true>);
+        }
+        if (pl.diffuse) {
+            if (pl.tabs) { ORT_PTV(pt_persistent<false, true, true, true, false, true>); }
+            ORT_PTV(pt_persistent<false, true, false, false, false, true>);
+        }
+        if (pl.tabs) { ORT_PTV(pt_persistent<false, false, true, true, false, true>); }
+        ORT_PTV(pt_persistent<false, false, false, false, false, true>);
+#undef ORT_PTV
+    }
     if (pl.five) {
         ort_launch_w5(pl.diffuse ? 1 : 0, pl.grid, (void *)stream, &sv, &hot);
         return ORT_OK;
@@ -437,13 +458,16 @@ static int read_render_stats(const DeviceScene *d, bool counters, ort_stats *sta
 /* The render call.  What runs, on which grid and with which thresholds is plan_render's decision (ort_plan.h); this is the
    plumbing around it: settle the previous call, staging, plan, views, buffers, launch, combine, finish. */
 int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *jobs, uint32_t job_count, void *d_out,
-                  float *h_out, void *stream_v, uint32_t *final_states, ort_stats *stats, std::string *err) {
+                  float *h_out, void *stream_v, uint32_t *final_states, ort_stats *stats, std::string *err, const ort_view *views,
+                  uint32_t view_count) {
     DeviceScene *d = scene->dev;
     if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
     ORT_HIP(hipSetDevice(d->device));
     hipStream_t stream = (hipStream_t)stream_v;
     const bool packed_out = (p->flags & ORT_RENDER_PACKED) != 0 && !jobs;
-    const size_t image_bytes = packed_out ? (size_t)block_grid_for(p).my_blocks * 768u : (size_t)p->width * (size_t)p->height * 12u;
+    if (!views) view_count = 1;
+    /* a batch of views: view_count frames, view-major */
+    const size_t image_bytes = packed_out ? (size_t)block_grid_for(p).my_blocks * 768u : (size_t)view_count * (size_t)p->width * (size_t)p->height * 12u;
     int rc;
     /* One render at a time per scene: the job counter, the work counters, the partial planes and the stashes belong
        to the scene.  A render that was returned from without waiting is waited for here, and its tripwire checked. */
@@ -458,18 +482,21 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
 
     SceneView sv = scene_view(scene, d);
     const bool w5_layout_ok = ort_w5_sizeof_scene_view() == sizeof(SceneView) && ort_w5_sizeof_render_hot() == sizeof(RenderHot);
-    const LaunchPlan pl = plan_render(scene_traits(scene, d), *p, jobs != nullptr, job_count, w5_layout_ok, d->knobs);
+    const LaunchPlan pl = plan_render(scene_traits(scene, d), *p, jobs != nullptr, job_count, w5_layout_ok, d->knobs, view_count);
 
     sv.util = pl.util ? d->ctrl() + 8 : nullptr;
     if (pl.wide) sv.nodes = d->nodes4.as<const float4>();
+    /* the camera: the scene's own; a batch of one view is the same call with that view's camera and seed; the lanes of a larger
+       batch read theirs from the table (the VIEWS kernels: sv.cam stays the scene's, unread) */
     ort_camera cam;
     camera_basis(*scene, p->width, p->height, &cam);
+    if (views && !pl.views) cam = views[0].camera;
     memcpy(sv.cam, &cam, sizeof(cam));
 
     RenderView rv{};
     rv.W = p->width; rv.H = p->height;
     rv.x0 = p->x0; rv.y0 = p->y0; rv.x1 = p->x1; rv.y1 = p->y1;
-    rv.seed = p->seed; rv.spp = p->spp; rv.chunk = p->chunk; rv.rr = p->rr;
+    rv.seed = views && !pl.views ? views[0].seed : p->seed; rv.spp = p->spp; rv.chunk = p->chunk; rv.rr = p->rr;
     rv.out = out;
     rv.packed_out = packed_out;
     rv.next_job = d->ctrl();
@@ -496,6 +523,24 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
             if ((rc = d->states.ensure((size_t)job_count * 4u, err))) return rc;
             rv.final_states = d->states.as<uint32_t>();
         }
+    }
+    if (pl.views) {
+        /* 4 float4 per view: p.xyz and the seed's bits, then the three axes.  Both copies of the table are the previous call's
+           until that has finished (settled above); the caller's array is read here and not again */
+        std::vector<float> &tab = d->view_tab_host;
+        tab.assign((size_t)view_count * 16u, 0.0f);
+        for (uint32_t v = 0; v < view_count; ++v) {
+            float *q = &tab[(size_t)v * 16u];
+            const ort_camera &c = views[v].camera;
+            const float rows[4][3] = {{c.p.x, c.p.y, c.p.z}, {c.x_axis.x, c.x_axis.y, c.x_axis.z}, {c.y_axis.x, c.y_axis.y, c.y_axis.z}, {c.z_axis.x, c.z_axis.y, c.z_axis.z}};
+            for (int r = 0; r < 4; ++r) memcpy(q + 4 * r, rows[r], sizeof(rows[r]));
+            memcpy(q + 3, &views[v].seed, sizeof(uint32_t));
+        }
+        if ((rc = d->view_tab.ensure(tab.size() * sizeof(float), err))) return rc;
+        ORT_HIP(hipMemcpyAsync(d->view_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        rv.views = d->view_tab.as<const float4>();
+        rv.view_jobs = pl.view_jobs;
+        rv.view_count = pl.view_count;
     }
     if (pl.mode == PLAN_JOBS_CHUNK) {
         if ((rc = d->partial.ensure(pl.partial_bytes, err))) return rc;
@@ -526,7 +571,10 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
     if (rv.mode == JOBS_CHUNK) {
         unsigned long long total = (unsigned long long)rv.my_blocks * 64ull;
         unsigned int cgrid = (unsigned int)((total + 255) / 256);
-        if (cgrid) hipLaunchKernelGGL(combine_chunks, dim3(cgrid), dim3(256), 0, stream, hot);
+        if (pl.views) {
+            cgrid = (unsigned int)((total * pl.view_count + 255) / 256);
+            if (cgrid) hipLaunchKernelGGL(combine_chunks_views, dim3(cgrid), dim3(256), 0, stream, hot);
+        } else if (cgrid) hipLaunchKernelGGL(combine_chunks, dim3(cgrid), dim3(256), 0, stream, hot);
         ORT_HIP(hipGetLastError());
     }
     if (stats) ORT_HIP(hipEventRecord(d->ev1, stream));
@@ -562,22 +610,7 @@ constexpr uint64_t kRaycastSlice = 1ull << 22; /* rays per launch of the host fo
 /* the box of everything ort_tree.cpp sized the quadric boxes for (raycast_needs_exact), worked out at the first query of either kind */
 static void ensure_scene_box(Scene *scene, DeviceScene *d) {
     if (d->scene_box_known) return;
-    /* shapes and camera */
-    float lo[3] = {scene->camera_p.x, scene->camera_p.y, scene->camera_p.z}, hi[3] = {lo[0], lo[1], lo[2]};
-    auto grow = [&](float x, float y, float z, float r) {
-        const float p[3] = {x, y, z};
-        for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], p[k] - r); hi[k] = std::max(hi[k], p[k] + r); }
-    };
-    for (const ort_sphere &q : scene->spheres) grow(q.center.x, q.center.y, q.center.z, fabsf(q.r));
-    for (const ort_box &q : scene->boxes) { grow(q.min.x, q.min.y, q.min.z, 0.0f); grow(q.max.x, q.max.y, q.max.z, 0.0f); }
-    for (const ort_cylinder &q : scene->cylinders) {
-        grow(q.base.x, q.base.y, q.base.z, fabsf(q.r));
-        grow(q.base.x + q.axis.x, q.base.y + q.axis.y, q.base.z + q.axis.z, fabsf(q.r));
-    }
-    for (const HostMesh &m : scene->meshes)
-        for (size_t i = 0; i + 2 < m.vertices.size(); i += 3) grow(m.vertices[i], m.vertices[i + 1], m.vertices[i + 2], 0.0f);
-    memcpy(d->scene_lo, lo, sizeof(lo));
-    memcpy(d->scene_hi, hi, sizeof(hi));
+    scene_origin_box(*scene, d->scene_lo, d->scene_hi); /* shapes and camera */
     d->scene_box_known = true;
 }
 

@@ -175,6 +175,11 @@ struct RenderView {
     uint32_t job_batch;  /* a wave draws this many job indices from next_job at a time and hands them to its lanes one by one (0 / 1: every draw goes to next_job) */
     unsigned long long batch_until; /* ... while the job counter, as the wave last saw it, is below this index; after it: exactly as many as it needs */
     unsigned long long *drain; /* diagnostics (ORT_DEBUG_DRAIN): when each wave ran out of work (s_memrealtime), [workgroup * 4 + wave] */
+    /* a batch of views (ort_render_views; the VIEWS kernels): the job space is [view][the single view's job space], out holds
+       view_count frames and partial view_count sets of planes, view-major */
+    const float4 *views;          /* 4 per view: p.xyz seed(bits) | x_axis | y_axis | z_axis */
+    unsigned long long view_jobs; /* jobs of one view */
+    uint32_t view_count;
 };
 
 /* ---- the order in which a CHUNK render issues its jobs ----------------------------------------------------------
@@ -614,7 +619,8 @@ struct Counters {
    few registers stay live across the traversal loop */
 struct PathState {
     int ps = PS_NEED_JOB;
-    uint32_t rng = 0, job_index = 0;
+    uint32_t rng = 0, job_index = 0; /* job_index: the explicit job; in a batch of views (the VIEWS kernels, implicit job spaces) the view:
+                                        whose camera, seed and frame the job belongs to */
     uint32_t pxy = 0;  /* px | py << 16: the pixel being rendered */
     uint32_t jxx = 0;  /* jx0 | jx1 << 16: the job rect's x range */
     uint32_t jyp = 0;  /* jy1 | plane << 16: the rect's end row; CHUNK policy: which partial plane */
@@ -644,6 +650,13 @@ ORT_D float *pixel_ptr(const RenderHot &rv, uint32_t plane, uint32_t x, uint32_t
     if (rv.mode == JOBS_CHUNK) return rv.c->partial + ((size_t)plane * rv.c->my_blocks * 64u + packed_index(rv, x, y)) * 3u;
     if (rv.c->packed_out) return rv.c->out + packed_index(rv, x, y) * 3u;
     return rv.c->out + 3u * ((size_t)y * (size_t)rv.W + (size_t)x);
+}
+
+/* the same in a batch of views (the VIEWS kernels): set `view` of the partial planes, frame `view` of the output; never packed,
+   never sharded */
+ORT_D float *view_pixel_ptr(const RenderHot &rv, uint32_t view, uint32_t plane, uint32_t x, uint32_t y) {
+    if (rv.mode == JOBS_CHUNK) return rv.c->partial + (((size_t)view * rv.c->nchunks + plane) * rv.c->my_blocks * 64u + packed_index(rv, x, y)) * 3u;
+    return rv.c->out + 3u * (((size_t)view * (size_t)rv.H + (size_t)y) * (size_t)rv.W + (size_t)x);
 }
 
 /* traversal state of one ray on the fast tree */
@@ -888,6 +901,29 @@ ORT_D V3 focal_point(const RenderHot &rv, uint32_t pxy, V3 cam_p, V3 cam_x, V3 c
     return add(cam_p, scale(focal_length, to_pixel));
 }
 
+/* VIEWS: the camera of view v as the table holds it (RenderView::views).  Read where it is needed -- once per pixel for the
+   focal point, once per camera sample for the aperture point -- instead of held in twelve registers through the traversal loop:
+   64 bytes that every lane of a wave almost always shares, from L1 / L2, per path of hundreds of node tests */
+struct ViewCamera { V3 p, x, y, z; };
+ORT_D ViewCamera load_view_camera(const RenderHot &rv, uint32_t v) {
+    const float4 *q = rv.c->views + 4u * (size_t)v;
+    const float4 a = q[0], b = q[1], c = q[2], d = q[3];
+    ViewCamera cam;
+    cam.p = mk(a.x, a.y, a.z);
+    cam.x = mk(b.x, b.y, b.z);
+    cam.y = mk(c.x, c.y, c.z);
+    cam.z = mk(d.x, d.y, d.z);
+    return cam;
+}
+/* ... and what produce_ray computes from sv.cam, from it: the pixel's focal point (ray.cpp:1198, :1215-1221) and the point on
+   the aperture (ray.cpp:1233-1239), the same expressions in the same order */
+ORT_D V3 view_focal_point(const RenderHot &rv, uint32_t pxy, const ViewCamera &cam) {
+    return focal_point(rv, pxy, cam.p, cam.x, cam.y, cam.z, len(sub(cam.p, mk(0, 0, 0.2f))));
+}
+ORT_D V3 view_aperture_point(const ViewCamera &cam, float aperture, float cs, float sn) {
+    return sub(add(add(cam.p, scale(aperture * cs, cam.x)), scale(aperture * sn, cam.y)), scale(0.1f, cam.z));
+}
+
 /* Advance the lane's path state machine until it has produced the next ray (returns true; the ray
    is P.org / P.dir) or has run out of work (returns false).  On entry with P.ps == PS_HIT, h holds
    the resolved closest hit of the ray produced by the previous call. */
@@ -934,10 +970,13 @@ ORT_D unsigned long long *wave_job_pool(const RenderHot &rv, unsigned long long 
 
 /* IMPLICIT: the caller vouches for an implicit job space (PIXEL / CHUNK policies: every job is one pixel, spp_u
    samples): the job's rect, its sample count and its index then need no registers of their own */
-template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false>
+/* VIEWS: a batch of views (ort_render_views): the job index names the view first, and the view's camera and seed come from
+   the table behind rv.c->views instead of sv.cam and rv.c->seed -- the same expressions on the same operands, so the same bits */
+template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool VIEWS = false>
 ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, Prof &pr,
                        float *focal_cache = nullptr, int focal_stride = 0, uint32_t spp_u = 0, uint32_t *late_flag = nullptr, bool no_new_job = false,
                        unsigned long long *pool = nullptr) {
+    /* VIEWS: unused; every lane reads its view's camera where it needs it (load_view_camera) */
     const V3 cam_p = mk(sv.cam[0], sv.cam[1], sv.cam[2]);
     const V3 cam_x = mk(sv.cam[3], sv.cam[4], sv.cam[5]);
     const V3 cam_y = mk(sv.cam[6], sv.cam[7], sv.cam[8]);
@@ -1022,7 +1061,9 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 /* ray.cpp:1428 */
                 V3 o = divs(P.color, (float)job_spp);
                 uint32_t px = P.pxy & 0xffffu, py = P.pxy >> 16;
-                float *p = pixel_ptr(rv, P.jyp >> 16, px, py);
+                float *p;
+                if constexpr (VIEWS) p = view_pixel_ptr(rv, P.job_index, P.jyp >> 16, px, py);
+                else p = pixel_ptr(rv, P.jyp >> 16, px, py);
                 p[0] = o.x; p[1] = o.y; p[2] = o.z;
                 if (IMPLICIT) {
                     P.ps = PS_NEED_JOB; /* a one-pixel job ends with its pixel */
@@ -1060,6 +1101,12 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                         continue;
                     }
                 } else {
+                    uint32_t seed;
+                    if constexpr (VIEWS) { /* [view][the view's job space]: the view's seed sits in the fourth word of its table entry */
+                        P.job_index = (uint32_t)(j / rv.c->view_jobs);
+                        j = j % rv.c->view_jobs;
+                        seed = om_f32_bits(rv.c->views[4u * (size_t)P.job_index].w);
+                    }
                     /* implicit job space: [chunk k][my 8x8 block b][pixel-in-block p] */
                     unsigned long long per_chunk = (unsigned long long)rv.c->my_blocks * 64ull;
                     uint32_t k, lb, pin; /* chunk, local block, pixel in block */
@@ -1083,11 +1130,13 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                     if (!IMPLICIT) P.jxx = (uint32_t)x | ((uint32_t)(x + 1) << 16);
                     P.pxy = (uint32_t)x | ((uint32_t)y << 16);
                     if (rv.mode == JOBS_PIXEL) {
-                        P.rng = job_seed(rv.c->seed, pix);
+                        if constexpr (VIEWS) P.rng = job_seed(seed, pix);
+                        else P.rng = job_seed(rv.c->seed, pix);
                         if (!IMPLICIT) P.spp = rv.c->spp;
                         P.jyp = (uint32_t)(y + 1);
                     } else {
-                        P.rng = job_seed(rv.c->seed, k * (uint32_t)(rv.W * rv.H) + pix);
+                        if constexpr (VIEWS) P.rng = job_seed(seed, k * (uint32_t)(rv.W * rv.H) + pix);
+                        else P.rng = job_seed(rv.c->seed, k * (uint32_t)(rv.W * rv.H) + pix);
                         if (!IMPLICIT) P.spp = rv.c->chunk;
                         P.jyp = (uint32_t)(y + 1) | (k << 16);
                     }
@@ -1100,13 +1149,19 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 P.sample = 0;
                 P.ps = PS_SAMPLE;
                 if (focal_cache) { /* the pixel's focal point, once per pixel (persistent kernel: three floats of LDS per lane) */
-                    V3 f = focal_point(rv, P.pxy, cam_p, cam_x, cam_y, cam_z, focal_length);
+                    V3 f;
+                    if constexpr (VIEWS) f = view_focal_point(rv, P.pxy, load_view_camera(rv, P.job_index));
+                    else f = focal_point(rv, P.pxy, cam_p, cam_x, cam_y, cam_z, focal_length);
                     focal_cache[0] = f.x; focal_cache[focal_stride] = f.y; focal_cache[2 * focal_stride] = f.z;
                 }
             }
             if (P.sample == job_spp) continue; /* spp == 0: the reference's sample loop runs zero times */
             /* ray.cpp:1215-1221: point on the focal plane through the pixel centre: a function of the pixel alone,
                read back from the per-lane cache or (wavefront mode) recomputed -- same expressions, same bits */
+            if constexpr (VIEWS)
+                focal = focal_cache ? mk(focal_cache[0], focal_cache[focal_stride], focal_cache[2 * focal_stride])
+                                    : view_focal_point(rv, P.pxy, load_view_camera(rv, P.job_index));
+            else
             focal = focal_cache ? mk(focal_cache[0], focal_cache[focal_stride], focal_cache[2 * focal_stride])
                                 : focal_point(rv, P.pxy, cam_p, cam_x, cam_y, cam_z, focal_length);
             angle = rng_between(P.rng, 0.0f, 2 * kPi); /* ray.cpp:1232 */
@@ -1123,8 +1178,11 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                :1158) and so do camera lanes (the ray direction, :1240, and -- sic -- the direction again for wo,
                :1241): two converged evaluations instead of four divergent ones */
             V3 ap = mk(0, 0, 0);
-            if (!bounce) /* ray.cpp:1233-1239 */
+            if (!bounce) { /* ray.cpp:1233-1239 */
+                if constexpr (VIEWS) ap = view_aperture_point(load_view_camera(rv, P.job_index), aperture, cs, sn);
+                else
                 ap = sub(add(add(cam_p, scale(aperture * cs, cam_x)), scale(aperture * sn, cam_y)), scale(0.1f, cam_z));
+            }
             const V3 unit1 = normalize(bounce ? n : sub(focal, ap));
             bool is_trans = false;
             V3 raw = unit1;
@@ -1149,6 +1207,8 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 raw = sample_brdf_finish<false>(n, normalize(n), P.wo, m, draw, cs, sn, is_trans);
             } else {
                 /* ray.cpp:1233-1246 */
+                if constexpr (VIEWS) ap = view_aperture_point(load_view_camera(rv, P.job_index), aperture, cs, sn);
+                else
                 ap = sub(add(add(cam_p, scale(aperture * cs, cam_x)), scale(aperture * sn, cam_y)), scale(0.1f, cam_z));
                 raw = sub(focal, ap);
             }
@@ -1457,7 +1517,7 @@ ORT_D void flush_counters(const RenderHot &rv, const Counters &c, bool all) {
 }
 
 /* persistent mode: one lane runs jobs until the job space is empty */
-template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool WIDE = false>
+template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool WIDE = false, bool VIEWS = false>
 ORT_D void pt_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, float *lds_focal, const int tid,
                    const uint32_t lane_id, bool prof_on = false, unsigned long long *pool = nullptr) {
     uint32_t spill[kSpillStack];
@@ -1479,7 +1539,7 @@ ORT_D void pt_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, 
             ORT_PHASE(pr, sv, 7, true);
             if (P.ps == PS_HIT) resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true, WIDE>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
             ORT_PHASE(pr, sv, 0, P.ps == PS_HIT);
-            tracing = produce_ray<COUNTERS, DIFFUSE, TABS, IMPLICIT>(sv, rv, tab, P, h, c, pr, lds_focal + tid, kBlock, spp_u, nullptr, false, pool);
+            tracing = produce_ray<COUNTERS, DIFFUSE, TABS, IMPLICIT, VIEWS>(sv, rv, tab, P, h, c, pr, lds_focal + tid, kBlock, spp_u, nullptr, false, pool);
             if (tracing) {
                 begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
                 if (COUNTERS) c.rays++;
@@ -1765,7 +1825,8 @@ ORT_D void wf_trace_slot(const SceneView &sv, const float4 *tab, const WfView &w
 }
 
 /* pixel = (sum over k of partial[k], in k order) / nchunks for one pixel (CHUNK policy) */
-ORT_D void combine_pixel(const RenderHot &rv, unsigned long long idx) {
+/* view: which frame of the output and which set of partial planes (ort_render_views; 0 otherwise) */
+ORT_D void combine_pixel(const RenderHot &rv, unsigned long long idx, uint32_t view = 0) {
     uint32_t blk = rv.c->shard_index + (uint32_t)(idx >> 6) * rv.c->shard_count;
     uint32_t pin = (uint32_t)(idx & 63ull);
     int x = (int)((rv.c->block_x0 + blk % rv.c->blocks_w) * 8u + (pin & 7u));
@@ -1774,11 +1835,11 @@ ORT_D void combine_pixel(const RenderHot &rv, unsigned long long idx) {
     const size_t plane = (size_t)rv.c->my_blocks * 64u * 3u; /* partial planes are packed: idx is the pixel's place in each */
     V3 acc = mk(0, 0, 0);
     for (uint32_t k = 0; k < rv.c->nchunks; ++k) {
-        const float *p = rv.c->partial + (size_t)k * plane + 3u * (size_t)idx;
+        const float *p = rv.c->partial + ((size_t)view * rv.c->nchunks + k) * plane + 3u * (size_t)idx;
         acc = add(acc, mk(p[0], p[1], p[2]));
     }
     acc = divs(acc, (float)rv.c->nchunks);
-    float *o = rv.c->packed_out ? rv.c->out + 3u * (size_t)idx : rv.c->out + 3u * ((size_t)y * (size_t)rv.W + (size_t)x);
+    float *o = rv.c->packed_out ? rv.c->out + 3u * (size_t)idx : rv.c->out + 3u * (((size_t)view * (size_t)rv.H + (size_t)y) * (size_t)rv.W + (size_t)x);
     o[0] = acc.x; o[1] = acc.y; o[2] = acc.z;
 }
 
@@ -1900,7 +1961,8 @@ __device__ __forceinline__ void fill_tab(const SceneView &sv, float4 *lds_tab) {
     __syncthreads();
 }
 
-template <bool COUNTERS, bool DIFFUSE, bool TABS, bool IMPLICIT = false, bool WIDE = false>
+/* VIEWS: the kernels of ort_render_views (the plain loop only; SceneView::cam is not read) */
+template <bool COUNTERS, bool DIFFUSE, bool TABS, bool IMPLICIT = false, bool WIDE = false, bool VIEWS = false>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
 pt_persistent(SceneView sv, RenderHot rv) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
@@ -1914,7 +1976,7 @@ pt_persistent(SceneView sv, RenderHot rv) {
         if (threadIdx.x < 4) g_lds_prof[96 + threadIdx.x] = __builtin_amdgcn_s_memtime();
         __syncthreads();
     }
-    pt_lane<COUNTERS, DIFFUSE, TABS, IMPLICIT, WIDE>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, prof,
+    pt_lane<COUNTERS, DIFFUSE, TABS, IMPLICIT, WIDE, VIEWS>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, prof,
                                                     wave_job_pool(rv, lds_pool));
     if ((threadIdx.x & 63u) == 0u && rv.c->drain) rv.c->drain[blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime();
     if (prof) {
@@ -1997,6 +2059,12 @@ __global__ void combine_chunks(RenderHot rv) {
     unsigned long long idx = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (unsigned long long)rv.c->my_blocks * 64ull) return;
     combine_pixel(rv, idx);
+}
+/* the same over the frames of a batch of views: [view][this view's pixels] */
+__global__ void combine_chunks_views(RenderHot rv) {
+    const unsigned long long idx = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, per_view = (unsigned long long)rv.c->my_blocks * 64ull;
+    if (idx >= per_view * rv.c->view_count) return;
+    combine_pixel(rv, idx % per_view, (uint32_t)(idx / per_view));
 }
 
 /* ---- closest-hit ray queries (ort_raycast): raycast_top_most_node, ray.cpp:1165-1176 --------------------------------

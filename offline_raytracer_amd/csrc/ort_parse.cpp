@@ -567,15 +567,19 @@ int parse_scn_text(const char *text, size_t size, const char *base_dir, Scene *s
     return p.failed ? ORT_ERR_PARSE : ORT_OK;
 }
 
-void camera_basis(const Scene &s, int32_t width, int32_t height, ort_camera *out) {
-    float rx = s.camera_height_ratio * ((float)width / height);
-    Rot3 r = quat_matrix(s.camera_quat[0], s.camera_quat[1], s.camera_quat[2], s.camera_quat[3]);
+void camera_from_pose(const ort_v3 &p, const float quat_xyzw[4], float height_ratio, int32_t width, int32_t height, ort_camera *out) {
+    float rx = height_ratio * ((float)width / height);
+    Rot3 r = quat_matrix(quat_xyzw[0], quat_xyzw[1], quat_xyzw[2], quat_xyzw[3]);
     float ex[3] = {1, 0, 0}, ey[3] = {0, 1, 0}, ez[3] = {0, 0, 1};
     rotate(r, ex); rotate(r, ey); rotate(r, ez);
-    out->p = s.camera_p;
+    out->p = p;
     out->x_axis = {rx * ex[0], rx * ex[1], rx * ex[2]};
-    out->y_axis = {s.camera_height_ratio * ey[0], s.camera_height_ratio * ey[1], s.camera_height_ratio * ey[2]};
+    out->y_axis = {height_ratio * ey[0], height_ratio * ey[1], height_ratio * ey[2]};
     out->z_axis = {ez[0], ez[1], ez[2]};
+}
+
+void camera_basis(const Scene &s, int32_t width, int32_t height, ort_camera *out) {
+    camera_from_pose(s.camera_p, s.camera_quat, s.camera_height_ratio, width, height, out);
 }
 
 } // namespace ort

@@ -120,6 +120,8 @@ inline uint64_t render_workspace_bytes(const ort_render_params *p) {
     uint64_t nch = p->spp / p->chunk;
     return nch * (uint64_t)block_grid_for(p).my_blocks * 64ull * 12ull; /* partial planes hold this shard's blocks only */
 }
+/* a batch of views (ort_render_views): every view has partial planes of its own */
+inline uint64_t render_views_workspace_bytes(const ort_render_params *p, uint32_t view_count) { return (uint64_t)view_count * render_workspace_bytes(p); }
 
 /* Which of the scene's small read-only tables fit their LDS slots (TAB_* bits), decided once at upload: the materials, index 0
    included, up to 48 records; the light types up to 64 lights; the analytic prologue's shapes up to 40 float4 (a box takes two, a
@@ -153,6 +155,11 @@ struct LaunchPlan {
        exists with the ORT_DEBUG_UTIL probes, and the exchange kernels know no other job space than the implicit ones */
     bool wavefront = false, exchange = false, five = false, wide = false, counters = false, diffuse = false, tabs = false, implicit = false;
     bool util = false; /* ORT_DEBUG_UTIL probes (counters builds) */
+    /* a batch of views (ort_render_views, view_count > 1): the plain loop's VIEWS kernels, whose lanes read their camera from a
+       per-view table; the job space is view_count times the single view's, the view outermost */
+    bool views = false;
+    uint32_t view_count = 1;
+    unsigned long long view_jobs = 0; /* jobs of one view (job_count / view_count) */
     unsigned int grid = 1;
     /* the job space */
     int mode = PLAN_JOBS_EXPLICIT;
@@ -173,11 +180,18 @@ struct LaunchPlan {
 };
 
 /* job_count: the number of explicit jobs (explicit_jobs; ignored otherwise: PIXEL / CHUNK job spaces follow from p).
-   w5_layout_ok: the five-waves unit's argument structs have this unit's layout (ort_launch_w5 takes them as bytes). */
+   w5_layout_ok: the five-waves unit's argument structs have this unit's layout (ort_launch_w5 takes them as bytes).
+   view_count: the views of an ort_render_views batch (PIXEL / CHUNK job spaces only).  1 is the render call as it always was: a
+   batch of one view is that call with the view's camera and seed.  More than one: the job space is [view][block][chunk][pixel]
+   -- the view outermost, so the lanes of a wave almost always share a camera and the launch ends on the last view's last blocks --
+   and the launch is always the plain persistent loop at four waves: no ray exchange, no five-waves unit, no wide tree, no
+   wavefront mode and no ORT_DEBUG_UTIL probes, whatever the knobs say (those variants are not built with a camera table).
+   diffuse and tabs are decided as ever; the batch and refill rules count with the enlarged job space. */
 inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, bool explicit_jobs, uint64_t job_count, bool w5_layout_ok,
-                              const Knobs &kn) {
+                              const Knobs &kn, uint32_t view_count = 1) {
     LaunchPlan pl;
-    const bool want_util = kn.debug_util; /* developer diagnostics, counters build only */
+    const bool views = view_count > 1u && !explicit_jobs;
+    const bool want_util = kn.debug_util && !views; /* developer diagnostics, counters build only */
     /* tuning knobs; results do not depend on them.  Defaults tuned on MI355X (profiles/r01_tuning.md)
        separately for trees that stay in L2 and trees that do not */
     const bool cache_resident_tree = tree_is_cache_resident(t.fast_tree_bytes, kn.cache_resident);
@@ -205,9 +219,16 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
         pl.job_count = (unsigned long long)pl.blocks.my_blocks * 64ull * pl.nchunks;
         pl.partial_bytes = (size_t)pl.nchunks * (size_t)pl.blocks.my_blocks * 64u * 12u; /* = render_workspace_bytes(p) */
     }
+    pl.view_jobs = pl.job_count;
+    if (views) {
+        pl.views = true;
+        pl.view_count = view_count;
+        pl.job_count *= view_count;
+        pl.partial_bytes *= view_count; /* = render_views_workspace_bytes(p, view_count) */
+    }
 
     const bool counters = (p.flags & ORT_RENDER_COUNTERS) != 0;
-    const bool wavefront = kn.wavefront; /* ORT_MODE=wavefront; results are identical */
+    const bool wavefront = kn.wavefront && !views; /* ORT_MODE=wavefront; results are identical */
     const bool diffuse = t.diffuse_only && !kn.general_kernel; /* ORT_KERNEL=general forces the all-lobes kernel (A/B runs; same results) */
     /* TABS: the scene's small tables all fit their LDS slots (table_fit_flags); otherwise every one of them is read from HBM */
     const bool tabs = (t.tab_flags & kPlanAllTabs) == kPlanAllTabs && kn.lds_tables != 0; /* ORT_LDS_TABLES=0: read them from HBM anyway (A/B runs; same results) */
@@ -217,7 +238,7 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
        diffuse flavour on a cache-resident tree does not: bunny room whole frame 4 729 / 4 712, its 4- / 8-way shards 117.0 / 119.2 and
        63.5 / 65.9 ms (a quarter more lanes, a quarter fewer jobs per lane: the tail weighs more); nor the ray exchange (5 053 / 4 949).
        ORT_WAVES5=0 / 1 forces. */
-    const bool can_five = !wavefront && !counters && tabs && pl.mode != PLAN_JOBS_EXPLICIT && kn.wide <= 0 && kn.exchange <= 0 && w5_layout_ok;
+    const bool can_five = !views && !wavefront && !counters && tabs && pl.mode != PLAN_JOBS_EXPLICIT && kn.wide <= 0 && kn.exchange <= 0 && w5_layout_ok;
     /* persistent grid: 4 blocks of 256 lanes per CU (5 for the five-waves kernels, decided below), never more lanes than jobs */
     unsigned long long lanes_wanted = pl.job_count;
     unsigned int max_blocks = t.max_blocks;
@@ -241,7 +262,7 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
            scale 3 / 5 / 8 / 12 (SAH cost 0.027 / 0.076 / 0.19 / 0.44) 5 428 / 5 844, 5 143 / 5 151, 3 904 / 3 728, 3 173 / 2 946; dwarf at
            scale 0.008 / 0.012 / 0.02 / 0.03 (0.018 / 0.040 / 0.11 / 0.25) 5 335 / 5 666, 4 921 / 5 143, 4 454 / 4 276, 3 626 / 3 483 */
         const bool worth_it = diffuse && cache_resident_tree && t.sah_cost >= 0.09f && pl.job_count >= 24ull * (unsigned long long)grid * kPlanBlock;
-        exch = tabs && pl.mode != PLAN_JOBS_EXPLICIT && (kn.exchange >= 0 ? kn.exchange != 0 : worth_it) && (!counters || (want_util && diffuse));
+        exch = !views && tabs && pl.mode != PLAN_JOBS_EXPLICIT && (kn.exchange >= 0 ? kn.exchange != 0 : worth_it) && (!counters || (want_util && diffuse));
         if (exch && kn.refill_below < 0) pl.refill_below = 24; /* stragglers park instead of idling: leave the loop a little earlier (dwarf room 4K, 16 / 24 / 48: 4 466 / 4 536 / 4 536 Mpaths/s) */
         if (exch) {
             pl.capL = kPlanCapL; pl.capR = kPlanCapR;
@@ -294,7 +315,7 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
     /* 4-wide tree (DevNode4): half the dependent node fetches per ray -- and twice the vector instructions per visit, in a
        kernel that is issue-bound at a third of its lanes on the trees it was meant for: 1 218 against 1 368 Mpaths/s on the
        1M-triangle scene (profiles/r03_tuning.md).  Off unless ORT_WIDE=1 asks for it (same image either way). */
-    const bool wide = t.has_wide && !exch && tabs && (counters || pl.mode != PLAN_JOBS_EXPLICIT) && !(counters && diffuse && want_util) && kn.wide > 0;
+    const bool wide = !views && t.has_wide && !exch && tabs && (counters || pl.mode != PLAN_JOBS_EXPLICIT) && !(counters && diffuse && want_util) && kn.wide > 0;
 
     pl.wavefront = wavefront;
     pl.counters = counters;

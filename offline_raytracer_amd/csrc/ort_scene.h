@@ -4,7 +4,9 @@
 #ifndef ORT_SCENE_H
 #define ORT_SCENE_H
 
+#include <math.h>
 #include <stdint.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -175,6 +177,27 @@ struct Scene {
 int parse_scn_text(const char *text, size_t size, const char *base_dir, Scene *scene, std::string *err);
 int read_file(const char *path, std::vector<char> *out);
 void camera_basis(const Scene &s, int32_t width, int32_t height, ort_camera *out);
+/* the same for any pose (macos_main.mm:550-556) */
+void camera_from_pose(const ort_v3 &p, const float quat_xyzw[4], float height_ratio, int32_t width, int32_t height, ort_camera *out);
+
+/* The box of everything ort_tree.cpp sized the quadric boxes for: all shapes and the scene's own camera_p.  Ray origins within
+   it, with the 0.25 of slack per side the tree allows (build_tree: e = hi - lo + 0.5), get the reference's answers from the fast
+   tree: what the ray queries test a caller's origin against (raycast_needs_exact) and ort_render_views a caller's camera. */
+inline void scene_origin_box(const Scene &s, float lo[3], float hi[3]) {
+    lo[0] = hi[0] = s.camera_p.x; lo[1] = hi[1] = s.camera_p.y; lo[2] = hi[2] = s.camera_p.z;
+    auto grow = [&](float x, float y, float z, float r) {
+        const float p[3] = {x, y, z};
+        for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], p[k] - r); hi[k] = std::max(hi[k], p[k] + r); }
+    };
+    for (const ort_sphere &q : s.spheres) grow(q.center.x, q.center.y, q.center.z, fabsf(q.r));
+    for (const ort_box &q : s.boxes) { grow(q.min.x, q.min.y, q.min.z, 0.0f); grow(q.max.x, q.max.y, q.max.z, 0.0f); }
+    for (const ort_cylinder &q : s.cylinders) {
+        grow(q.base.x, q.base.y, q.base.z, fabsf(q.r));
+        grow(q.base.x + q.axis.x, q.base.y + q.axis.y, q.base.z + q.axis.z, fabsf(q.r));
+    }
+    for (const HostMesh &m : s.meshes)
+        for (size_t i = 0; i + 2 < m.vertices.size(); i += 3) grow(m.vertices[i], m.vertices[i + 1], m.vertices[i + 2], 0.0f);
+}
 
 /* ort_tree.cpp */
 int build_tree(Scene *scene, std::string *err);
@@ -188,8 +211,11 @@ uint32_t rgbe_pack(float r, float g, float b);
 int device_count(int *n, std::string *err);
 int device_upload(Scene *scene, int device, std::string *err);
 void device_release(Scene *scene);
+/* views (may be null: the scene's own camera and p->seed): view_count frames, each from views[v].camera with views[v].seed
+   (ort_render_views; PIXEL / CHUNK job spaces, jobs == null) */
 int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *jobs, uint32_t job_count,
-                  void *d_out, float *h_out, void *stream, uint32_t *final_states, ort_stats *stats, std::string *err);
+                  void *d_out, float *h_out, void *stream, uint32_t *final_states, ort_stats *stats, std::string *err,
+                  const ort_view *views = nullptr, uint32_t view_count = 1);
 int device_unit_eval(int device, const void *records, uint32_t n, float *out, std::string *err);
 /* closest-hit queries: host rays / hits (h_*, synchronous) or device ones (d_*, enqueued on stream) */
 int device_raycast(Scene *scene, const float *h_rays, const void *d_rays, uint64_t count, ort_hit *h_hits, void *d_hits, uint32_t flags,
