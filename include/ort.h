@@ -339,6 +339,41 @@ int ort_occluded(ort_scene *scene, const float *rays, const float *tmax, uint64_
 int ort_occluded_device(ort_scene *scene, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded,
                         uint32_t flags, void *hip_stream, ort_stats *stats);
 
+/* ---- radiance queries -----------------------------------------------------------------
+ * The path-traced light that arrives along a caller's own ray: light probes, irradiance and lightmap baking, sparse or
+ * foveated pixel sets, "rays in, colours out" batches -- the path tracer without its camera.
+ * out_rgb[i] is the reference's pixel value for a pixel whose every sample starts at o_i in direction d_i: the sample body
+ * of tiled_raytrace_bvh (ray.cpp:1247-1426: closest hit, emission, roulette, BSDF sampling, bounces) with wo =
+ * -normalize(d_i), run spp times on ONE xorshift stream that starts at seeds[i], WITHOUT the aperture draw of a camera
+ * sample (ray.cpp:1232); the samples' colours are summed in sample order and divided by (float)spp, component by
+ * component.  Bit for bit.  final_states[i] (final_states may be NULL) is the stream's state afterwards.  A seed of 0 is
+ * taken as 1, as the per-pixel seeding policies never hand out 0: a zero xorshift state never leaves zero.
+ * Rays as for ort_raycast: count x {o.xyz, d.xyz} f32, 24 B each, 8-byte aligned.  out_rgb is count x 3 f32, seeds and
+ * final_states count x u32 (4-byte aligned).  out_rgb[i] answers rays[i] with seeds[i]; results do not depend on count,
+ * order, how the batch is sliced or how rays fall on the GPU's lanes.
+ * The per-ray domain: d must be what a primary direction is in the reference -- all six components of the ray finite and
+ * |d|^2 (f32: x*x + y*y + z*z) within [0.999, 1.001].  A ray outside this domain gets out_rgb[i] = NaN NaN NaN and
+ * final_states[i] = seeds[i] (as given, 0 included), and is not traced; the other rays of the call are unaffected.  Inside the domain
+ * every ray gets the exact answer, axis-aligned directions and origins far outside the scene included: the primary rays
+ * that ort_raycast sends to the exact octree walk (a +-0 direction component with boxes in the tree, an origin outside the
+ * scene's box with quadrics in it) take it here too, roughly 1 000x slower per primary ray (radiance_rays).
+ * Bounce rays start at hits and need no rule.
+ * rr is the roulette's survival probability, as ort_render_params.rr, here within [0, 1): at 1 no path in a closed room ends.
+ * flags: ORT_RENDER_COUNTERS fills the work counters of stats, paths = (rays inside the domain) * spp; stats (may be NULL)
+ * always gets fallback_rays and kernel_ms.
+ * count == 0 returns ORT_OK without a launch, whatever the other arguments.  Otherwise errors are reported before any
+ * device work, in this order: ORT_ERR_INVALID (null scene, rays, seeds or out_rgb; misaligned pointer; spp == 0; rr
+ * outside [0, 1) or NaN), ORT_ERR_STATE (scene not committed), ORT_ERR_NO_DEVICE (not uploaded). */
+
+/* host rays and seeds in, host colours (and states) out; synchronous (staged through device buffers kept per scene, in
+   bounded slices) */
+int ort_radiance(ort_scene *scene, const float *rays, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr,
+                 float *out_rgb, uint32_t *final_states /* may be NULL */, uint32_t flags, ort_stats *stats);
+/* DEVICE rays, seeds, colours and states (may be NULL) on the scene's device; enqueued on hip_stream (NULL = the default
+   stream), returns without waiting unless stats != NULL -- as ort_raycast_device */
+int ort_radiance_device(ort_scene *scene, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr,
+                        void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats);
+
 /* ---- multi-GPU: block sharding and the one collective -------------------------------------
  * Replaces main()'s shared-memory tile pool (macos_main.mm:565-671: eight pthreads, one queue, one framebuffer)
  * across the GPUs of a node: scene replicated, 8x8 blocks dealt round-robin, every rank renders its blocks into a

@@ -127,7 +127,7 @@ EXPORTS = [
     "ort_shard_block_count", "ort_pack_blocks_host", "ort_unpack_blocks_host", "ort_unpack_blocks_device",
     "ort_comm_unique_id", "ort_comm_create", "ort_comm_create_local", "ort_comm_destroy", "ort_gather_framebuffer",
     "ort_gather_framebuffer_local", "ort_raycast", "ort_raycast_device",
-    "ort_occluded", "ort_occluded_device",
+    "ort_occluded", "ort_occluded_device", "ort_radiance", "ort_radiance_device",
     "ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes"]
 
 _lib = None
@@ -197,6 +197,10 @@ def lib():
         L.ort_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
         L.ort_occluded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
                                           C.POINTER(Stats)]
+        L.ort_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_uint32, C.POINTER(Stats)]
+        L.ort_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p,
+                                          C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
         L.ort_camera_from_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.POINTER(Camera)]
         L.ort_render_views.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
         L.ort_render_views_device.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
@@ -489,6 +493,38 @@ class Scene:
                                          C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
+    # -- radiance queries -----------------------------------------------------------------
+    def radiance(self, rays, seeds, spp, rr=0.8, want_states=False, counters=False):
+        """Path-traced radiance along each ray: spp samples of the reference's sample body from rays[i] on the xorshift
+        stream that starts at seeds[i] (0 is taken as 1), no aperture.  rays: (N, 6) float32 o.xyz d.xyz, d of unit length
+        (|d|^2 within [0.999, 1.001], all components finite; any other ray gives NaN NaN NaN and its seed back); seeds: (N,)
+        uint32, e.g. job_seeds(master, N).  Returns (rgb: float32[N, 3], stats dict), with want_states (rgb, states:
+        uint32[N], stats dict); synchronous."""
+        rays = np.ascontiguousarray(rays, dtype="<f4")
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must be an (N, 6) array of o.xyz d.xyz, got shape %s" % (rays.shape,))
+        seeds = np.asarray(seeds)
+        if seeds.shape != (len(rays),):
+            raise ValueError("seeds must be an (N,) array with N = %d, got shape %s" % (len(rays), seeds.shape))
+        seeds = np.ascontiguousarray(seeds.astype(np.int64) & 0xFFFFFFFF, dtype="<u4")
+        out = np.zeros((len(rays), 3), "<f4")
+        states = np.zeros(len(rays), "<u4") if want_states else None
+        st = Stats()
+        _check(lib().ort_radiance(self.handle, rays.ctypes.data, seeds.ctypes.data, len(rays), int(spp), float(rr), out.ctypes.data,
+                                  states.ctypes.data if want_states else None, RENDER_COUNTERS if counters else 0, C.byref(st)))
+        return (out, states, st.as_dict()) if want_states else (out, st.as_dict())
+
+    def radiance_device(self, d_rays, d_seeds, n, spp, rr, d_out, d_states=0, stream=0, counters=False, want_stats=False):
+        """Device rays (n x 6 float32) and seeds (n uint32) -> device colours (n x 3 float32) and, if d_states, final states
+        (n uint32): raw pointers on the scene's device, e.g. torch tensors' data_ptr().  Enqueued on stream; waits only when
+        want_stats (returns the stats dict)."""
+        st = Stats() if want_stats else None
+        _check(lib().ort_radiance_device(self.handle, C.c_void_p(d_rays), C.c_void_p(d_seeds), n, int(spp), float(rr),
+                                         C.c_void_p(d_out), C.c_void_p(d_states) if d_states else None,
+                                         RENDER_COUNTERS if counters else 0, C.c_void_p(stream) if stream else None,
+                                         C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
     def triangle_of(self, index):
         """mesh-major triangle id (decode_prim of a triangle hit) -> (mesh, triangle within that mesh).  Accepts arrays."""
         first = getattr(self, "_tri_first", None)
@@ -537,6 +573,19 @@ def decode_prim(prim):
     p = np.asarray(prim, dtype=np.uint32).astype(np.int64)
     miss = p == NO_PRIM
     return np.where(miss, -1, p >> 28), np.where(miss, -1, p & 0x0FFFFFFF)
+
+
+def job_seeds(master, n):
+    """job_seed(master, i) for i in range(n): the per-pixel seeding policies' seeds (fmix32 of master ^ i * 2654435761, 0
+    replaced by 1), for ray i of a radiance query.  -> uint32[n]"""
+    h = (np.uint64(int(master) & 0xFFFFFFFF) ^ ((np.arange(n, dtype=np.uint64) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)))
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x85EBCA6B)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(13)
+    h = (h * np.uint64(0xC2B2AE35)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(16)
+    h[h == 0] = 1
+    return h.astype("<u4")
 
 
 def unit_eval_device(records, device=0):

@@ -440,6 +440,45 @@ static int ort_occluded_device_impl(ort_scene *s, const void *d_rays, const void
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
+/* radiance queries: count == 0 is OK whatever else is passed; then argument errors, then state errors */
+static int check_radiance(const ort_scene *s, const void *rays, const void *seeds, uint32_t spp, float rr, const void *out_rgb, const void *final_states) {
+    if (!s) return fail(ORT_ERR_INVALID, "null scene");
+    if (!rays || !seeds || !out_rgb) return fail(ORT_ERR_INVALID, "null rays, seeds or out_rgb");
+    if ((uintptr_t)rays & 7u) return fail(ORT_ERR_INVALID, "rays must be 8-byte aligned");
+    if (((uintptr_t)seeds | (uintptr_t)out_rgb | (uintptr_t)final_states) & 3u) return fail(ORT_ERR_INVALID, "seeds, out_rgb and final_states must be 4-byte aligned");
+    if (spp == 0) return fail(ORT_ERR_INVALID, "spp must be >= 1");
+    if (!(rr >= 0.0f && rr < 1.0f)) return fail(ORT_ERR_INVALID, "rr must be in [0, 1): at 1 a path in a closed room never ends");
+    if (!s->tree.built) return fail(ORT_ERR_STATE, "ort_scene_commit has not been called");
+    if (!s->dev) return fail(ORT_ERR_NO_DEVICE, "scene is not resident on a HIP device: call ort_scene_upload (no CPU fallback)");
+    return ORT_OK;
+}
+
+static int ort_radiance_impl(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr, float *out_rgb,
+                             uint32_t *final_states, uint32_t flags, ort_stats *stats) {
+    if (count == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return ORT_OK;
+    }
+    int rc = check_radiance(s, rays, seeds, spp, rr, out_rgb, final_states);
+    if (rc != ORT_OK) return rc;
+    std::string err;
+    rc = ort::device_radiance(s, rays, nullptr, seeds, count, spp, rr, out_rgb, nullptr, final_states, nullptr, flags, nullptr, stats, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
+static int ort_radiance_device_impl(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out_rgb,
+                                    void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) {
+    if (count == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return ORT_OK;
+    }
+    int rc = check_radiance(s, d_rays, d_seeds, spp, rr, d_out_rgb, d_final_states);
+    if (rc != ORT_OK) return rc;
+    std::string err;
+    rc = ort::device_radiance(s, nullptr, d_rays, d_seeds, count, spp, rr, nullptr, d_out_rgb, nullptr, d_final_states, flags, hip_stream, stats, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
 /* ---- a batch of views ---- */
 static int ort_camera_from_pose_impl(const float *p, const float *quat_xyzw, float height_ratio, int32_t width, int32_t height, ort_camera *out) {
     if (!p || !quat_xyzw || !out || width <= 0 || height <= 0) return fail(ORT_ERR_INVALID, "bad argument");
@@ -592,6 +631,8 @@ int ort_raycast(ort_scene *s, const float *rays, uint64_t count, ort_hit *hits, 
 int ort_raycast_device(ort_scene *s, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_raycast_device_impl(s, d_rays, count, d_hits, flags, hip_stream, stats); }); }
 int ort_occluded(ort_scene *s, const float *rays, const float *tmax, uint64_t count, uint8_t *occluded, uint32_t flags, ort_stats *stats) { return guarded([&]() { return ort_occluded_impl(s, rays, tmax, count, occluded, flags, stats); }); }
 int ort_occluded_device(ort_scene *s, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_occluded_device_impl(s, d_rays, d_tmax, count, d_occluded, flags, hip_stream, stats); }); }
+int ort_radiance(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr, float *out_rgb, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return ort_radiance_impl(s, rays, seeds, count, spp, rr, out_rgb, final_states, flags, stats); }); }
+int ort_radiance_device(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_radiance_device_impl(s, d_rays, d_seeds, count, spp, rr, d_out_rgb, d_final_states, flags, hip_stream, stats); }); }
 int ort_render_workspace_bytes(const ort_render_params *p, uint64_t *bytes) { return guarded([&]() { return ort_render_workspace_bytes_impl(p, bytes); }); }
 int ort_camera_from_pose(const float p[3], const float quat_xyzw[4], float height_ratio, int32_t width, int32_t height, ort_camera *out) { return guarded([&]() { return ort_camera_from_pose_impl(p, quat_xyzw, height_ratio, width, height, out); }); }
 int ort_render_views(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, float *out_rgb, ort_stats *stats) { return guarded([&]() { return render_views_common(s, p, views, view_count, nullptr, out_rgb, nullptr, stats); }); }

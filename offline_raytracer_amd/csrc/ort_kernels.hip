@@ -94,6 +94,7 @@ struct DeviceScene {
     bool scene_box_known = false;
     DevBuf ray_in, hit_out;
     DevBuf tmax_in, occ_out; /* occlusion queries (device_occluded): the host path's limits and bytes */
+    DevBuf seed_in, rad_out, rad_states; /* radiance queries (device_radiance): the host path's seeds, colours and final states */
 };
 
 int device_count(int *n, std::string *err) {
@@ -289,8 +290,8 @@ static int launch_wavefront(DeviceScene *d, const SceneView &sv, const RenderVie
     return ORT_OK;
 }
 
-/* The path-trace kernel a plan names.  These sixteen variants, the six of a batch of views and the two of ort_kernels_w5.hip are
-   all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
+/* The path-trace kernel a plan names.  These sixteen variants, the six of a batch of views, the eight of the radiance queries
+   (launch_radiance) and the two of ort_kernels_w5.hip are all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
    an error, not a fallback. */
 static int launch_path_tracer(const LaunchPlan &pl, hipStream_t stream, const SceneView &sv, const RenderHot &hot, std::string *err) {
     if (pl.views) { /* the plain loop with the camera table: counters | diffuse, tabs (implicit follows from both) */
@@ -674,7 +675,7 @@ static int ray_query_plan(Scene *scene, DeviceScene *d, uint64_t count, hipStrea
 }
 
 /* after the launch of a ray query: mark it in flight; with stats, wait for it and add its time and counters */
-static int ray_query_finish(DeviceScene *d, bool counters, hipStream_t stream, ort_stats *stats, std::string *err) {
+static int ray_query_finish(DeviceScene *d, bool counters, hipStream_t stream, ort_stats *stats, std::string *err, bool paths = false) {
     int rc;
     ORT_HIP(hipGetLastError());
     if (stats) ORT_HIP(hipEventRecord(d->ev1, stream));
@@ -689,6 +690,7 @@ static int ray_query_finish(DeviceScene *d, bool counters, hipStream_t stream, o
         stats->kernel_ms += ms;
         stats->fallback_rays += c[5];
         if (counters) { stats->rays += c[1]; stats->node_tests += c[2]; stats->tri_tests += c[3]; stats->analytic_tests += c[4]; }
+        if (counters && paths) stats->paths += c[0]; /* radiance queries: primary rays traced */
     }
     return ORT_OK;
 }
@@ -797,6 +799,87 @@ int device_occluded(Scene *scene, const float *h_rays, const void *d_rays, const
         if (tmax) ORT_HIP(hipMemcpyAsync(d->tmax_in.p, (const float *)tmax + at, (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
         if ((rc = launch_occluded(scene, d, d->ray_in.p, tmax ? d->tmax_in.p : nullptr, n, d->occ_out.p, counters, stream, stats, err))) return rc;
         ORT_HIP(hipMemcpyAsync(h_out + at, d->occ_out.p, (size_t)n, hipMemcpyDeviceToHost, stream));
+        ORT_HIP(hipStreamSynchronize(stream));
+    }
+    return settle_inflight(d, err);
+}
+
+/* ---- radiance queries (ort_radiance*) ------------------------------------------------------------------------------ */
+constexpr uint64_t kRadianceSlice = 1ull << 20; /* rays per launch of the host form: a ray is spp paths, and 44 MB of staging */
+
+/* one launch over count rays at d_rays with d_seeds -> d_out (3 floats each) and d_states (may be null), all device pointers.
+   Which kernel, on which grid, is plan_radiance's decision (ort_plan.h) */
+static int launch_radiance(Scene *scene, DeviceScene *d, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out,
+                           void *d_states, bool counters, hipStream_t stream, ort_stats *stats, std::string *err) {
+    int rc;
+    if ((rc = settle_inflight(d, err))) return rc;
+    const SceneView sv = scene_view(scene, d);
+    const RadiancePlan pl = plan_radiance(scene_traits(scene, d), count, counters, d->knobs);
+    const RaycastIO q = ray_query_io(scene, d, d_rays);
+    RenderView rv{};
+    rv.mode = JOBS_PIXEL;
+    rv.job_count = count;
+    rv.next_job = d->ctrl();
+    rv.counters = d->ctrl() + 1;
+    rv.job_batch = pl.job_batch; rv.batch_until = pl.batch_until;
+    rv.refill_below = pl.refill_below; rv.descend_below = pl.descend_below;
+    rv.spp = spp; rv.rr = rr;
+    rv.out = (float *)d_out;
+    rv.final_states = (uint32_t *)d_states;
+    rv.rays = q.rays;
+    rv.seeds = (const uint32_t *)d_seeds;
+    rv.ray_tree_spheres = q.tree_spheres; rv.ray_tree_quadrics = q.tree_quadrics; rv.ray_tree_boxes = q.tree_boxes;
+    memcpy(rv.ray_lo, q.lo, sizeof(rv.ray_lo));
+    memcpy(rv.ray_hi, q.hi, sizeof(rv.ray_hi));
+    ORT_HIP(hipMemsetAsync(d->ctrl(), 0, 128 * sizeof(unsigned long long), stream));
+    ORT_HIP(hipMemcpyAsync(d->rv_dev.p, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
+    RenderHot hot{};
+    hot.mode = rv.mode; hot.rr = rv.rr;
+    hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
+    hot.c = (const ORT_CONSTANT_AS RenderView *)d->rv_dev.p;
+    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
+    enum : unsigned { C = 4, D = 2, T = 1 }; /* the template arguments */
+#define ORT_RAD(KEY, ...) case KEY: hipLaunchKernelGGL((__VA_ARGS__), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot); break
+    switch ((pl.counters ? C : 0u) | (pl.diffuse ? D : 0u) | (pl.tabs ? T : 0u)) {
+        ORT_RAD(C | D | T, radiance_rays<true, true, true>);
+        ORT_RAD(C | D, radiance_rays<true, true, false>);
+        ORT_RAD(C | T, radiance_rays<true, false, true>);
+        ORT_RAD(C, radiance_rays<true, false, false>);
+        ORT_RAD(D | T, radiance_rays<false, true, true>);
+        ORT_RAD(D, radiance_rays<false, true, false>);
+        ORT_RAD(T, radiance_rays<false, false, true>);
+        ORT_RAD(0u, radiance_rays<false, false, false>);
+    }
+#undef ORT_RAD
+    return ray_query_finish(d, counters, stream, stats, err, true);
+}
+
+int device_radiance(Scene *scene, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, uint32_t spp, float rr, float *h_out,
+                    void *d_out, uint32_t *h_states, void *d_states, uint32_t flags, void *stream_v, ort_stats *stats, std::string *err) {
+    DeviceScene *d = scene->dev;
+    if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
+    ORT_HIP(hipSetDevice(d->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    int rc;
+    ensure_scene_box(scene, d); /* no shape table: a colour names no shape */
+    const bool counters = (flags & ORT_RENDER_COUNTERS) != 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!h_rays) return launch_radiance(scene, d, d_rays, seeds, count, spp, rr, d_out, d_states, counters, stream, stats, err);
+    /* host form: bounded slices through the scene's staging buffers, as device_raycast; every ray is answered on its own stream */
+    const uint64_t slice = count < kRadianceSlice ? count : kRadianceSlice;
+    if ((rc = d->ray_in.ensure((size_t)slice * 24u, err))) return rc;
+    if ((rc = d->seed_in.ensure((size_t)slice * 4u, err))) return rc;
+    if ((rc = d->rad_out.ensure((size_t)slice * 12u, err))) return rc;
+    if (h_states && (rc = d->rad_states.ensure((size_t)slice * 4u, err))) return rc;
+    for (uint64_t at = 0; at < count; at += slice) {
+        const uint64_t n = count - at < slice ? count - at : slice;
+        if ((rc = settle_inflight(d, err))) return rc; /* the staging buffers are the previous slice's until it is done */
+        ORT_HIP(hipMemcpyAsync(d->ray_in.p, h_rays + 6u * at, (size_t)n * 24u, hipMemcpyHostToDevice, stream));
+        ORT_HIP(hipMemcpyAsync(d->seed_in.p, (const uint32_t *)seeds + at, (size_t)n * 4u, hipMemcpyHostToDevice, stream));
+        if ((rc = launch_radiance(scene, d, d->ray_in.p, d->seed_in.p, n, spp, rr, d->rad_out.p, h_states ? d->rad_states.p : nullptr, counters, stream, stats, err)))
+            return rc;
+        ORT_HIP(hipMemcpyAsync(h_out + 3u * at, d->rad_out.p, (size_t)n * 12u, hipMemcpyDeviceToHost, stream));
+        if (h_states) ORT_HIP(hipMemcpyAsync(h_states + at, d->rad_states.p, (size_t)n * 4u, hipMemcpyDeviceToHost, stream));
         ORT_HIP(hipStreamSynchronize(stream));
     }
     return settle_inflight(d, err);

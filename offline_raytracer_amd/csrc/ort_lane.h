@@ -180,6 +180,12 @@ struct RenderView {
     const float4 *views;          /* 4 per view: p.xyz seed(bits) | x_axis | y_axis | z_axis */
     unsigned long long view_jobs; /* jobs of one view */
     uint32_t view_count;
+    /* radiance queries (ort_radiance; the radiance_rays kernels): the job space is the caller's ray array, job j is ray j with spp
+       samples on the stream that starts at seeds[j]; out holds job_count x 3 floats, final_states (may be null) job_count states */
+    const float2 *rays;           /* job_count x 3: o.x o.y | o.z d.x | d.y d.z */
+    const uint32_t *seeds;
+    uint32_t ray_tree_spheres, ray_tree_quadrics, ray_tree_boxes; /* what raycast_needs_exact reads (RaycastIO), for the primary rays */
+    float ray_lo[3], ray_hi[3];
 };
 
 /* ---- the order in which a CHUNK render issues its jobs ----------------------------------------------------------
@@ -972,7 +978,12 @@ ORT_D unsigned long long *wave_job_pool(const RenderHot &rv, unsigned long long 
    samples): the job's rect, its sample count and its index then need no registers of their own */
 /* VIEWS: a batch of views (ort_render_views): the job index names the view first, and the view's camera and seed come from
    the table behind rv.c->views instead of sv.cam and rv.c->seed -- the same expressions on the same operands, so the same bits */
-template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool VIEWS = false>
+/* RAYS: radiance queries (ort_radiance; with IMPLICIT): the job space is the caller's ray array (rv.c->rays), a job is ONE ray with
+   spp_u samples on the stream that starts at rv.c->seeds[j].  Every sample starts at the ray's origin in the ray's direction,
+   with wo = -normalize(d) (ray.cpp:1240-1246 for a camera without an aperture), and no aperture angle is drawn; the job ends
+   with 12 bytes at out + 3 j and its stream's state.  The ray is read again for every sample (24 bytes from L2 per path of
+   hundreds of node tests) instead of held in six registers through the traversal loop; P.job_index | P.pxy << 32 is the ray index */
+template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool VIEWS = false, bool RAYS = false>
 ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, Prof &pr,
                        float *focal_cache = nullptr, int focal_stride = 0, uint32_t spp_u = 0, uint32_t *late_flag = nullptr, bool no_new_job = false,
                        unsigned long long *pool = nullptr) {
@@ -992,6 +1003,7 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
         BrdfDraw draw;
         Mat m;
         V3 n, focal;
+        V3 ray_o = mk(0, 0, 0), ray_d = mk(0, 0, 0); /* RAYS: the sample's ray as the caller gave it */
         if (P.ps == PS_HIT) {
             /* a traversal has finished: ray.cpp:817 then :1251-1277 (primary) or :1355-1421 (bounce) */
             bool alive = true;
@@ -1060,6 +1072,13 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
             if (P.ps == PS_SAMPLE && P.sample == job_spp) {
                 /* ray.cpp:1428 */
                 V3 o = divs(P.color, (float)job_spp);
+                if constexpr (RAYS) {
+                    const size_t ray = ((size_t)P.pxy << 32) | P.job_index;
+                    float *p = rv.c->out + 3u * ray;
+                    p[0] = o.x; p[1] = o.y; p[2] = o.z;
+                    if (rv.c->final_states) rv.c->final_states[ray] = P.rng;
+                    P.ps = PS_NEED_JOB;
+                } else {
                 uint32_t px = P.pxy & 0xffffu, py = P.pxy >> 16;
                 float *p;
                 if constexpr (VIEWS) p = view_pixel_ptr(rv, P.job_index, P.jyp >> 16, px, py);
@@ -1078,6 +1097,7 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                     P.ps = PS_PIXEL;
                 }
                 }
+                }
             }
             if (P.ps == PS_NEED_JOB) {
                 if (no_new_job) return false; /* ray exchange, end of the launch: this lane takes a parked path first (pt_lane_x) */
@@ -1089,6 +1109,24 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 j = ORT_NEXT_JOB(rv.c->next_job);
                 if (j >= rv.c->job_count) { P.ps = PS_DONE; break; }
                 if (IMPLICIT && late_flag && j >= rv.c->endgame_from) *late_flag = 1u; /* ray exchange: the launch is near its end (pt_lane_x) */
+                if constexpr (RAYS) {
+                    /* the per-ray domain (include/ort.h): six finite components, |d|^2 within [0.999, 1.001]: what a primary
+                       direction is in the reference.  A ray outside it is answered here, NaN and its seed, without a traversal */
+                    const float2 *r = rv.c->rays + 3ull * j;
+                    const float2 a = r[0], b = r[1], e = r[2];
+                    const uint32_t seed = rv.c->seeds[j];
+                    const V3 d = mk(b.y, e.x, e.y);
+                    const float l2 = len2(d);
+                    if (!(all_finite6(mk(a.x, a.y, b.x), d) && l2 >= 0.999f && l2 <= 1.001f)) {
+                        float *p = rv.c->out + 3u * (size_t)j;
+                        p[0] = p[1] = p[2] = om_bits_f32(0x7fc00000u);
+                        if (rv.c->final_states) rv.c->final_states[j] = seed;
+                        continue;
+                    }
+                    P.job_index = (uint32_t)j;
+                    P.pxy = (uint32_t)(j >> 32);
+                    P.rng = seed ? seed : 1u; /* as job_seed: a zero xorshift state never leaves zero */
+                } else
                 if (!IMPLICIT && rv.mode == JOBS_EXPLICIT) {
                     ort_tile_job jb = rv.c->jobs[j];
                     P.job_index = (uint32_t)j;
@@ -1158,6 +1196,12 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
             if (P.sample == job_spp) continue; /* spp == 0: the reference's sample loop runs zero times */
             /* ray.cpp:1215-1221: point on the focal plane through the pixel centre: a function of the pixel alone,
                read back from the per-lane cache or (wavefront mode) recomputed -- same expressions, same bits */
+            if constexpr (RAYS) { /* the caller's ray; no aperture, so no angle is drawn */
+                const float2 *r = rv.c->rays + 3ull * (((unsigned long long)P.pxy << 32) | P.job_index);
+                const float2 a = r[0], b = r[1], e = r[2];
+                ray_o = mk(a.x, a.y, b.x);
+                ray_d = mk(b.y, e.x, e.y);
+            } else {
             if constexpr (VIEWS)
                 focal = focal_cache ? mk(focal_cache[0], focal_cache[focal_stride], focal_cache[2 * focal_stride])
                                     : view_focal_point(rv, P.pxy, load_view_camera(rv, P.job_index));
@@ -1165,6 +1209,7 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
             focal = focal_cache ? mk(focal_cache[0], focal_cache[focal_stride], focal_cache[2 * focal_stride])
                                 : focal_point(rv, P.pxy, cam_p, cam_x, cam_y, cam_z, focal_length);
             angle = rng_between(P.rng, 0.0f, 2 * kPi); /* ray.cpp:1232 */
+            }
             ORT_PHASE(pr, sv, 2, true);
         }
         /* lanes that bounce and lanes that start a new camera sample both need cos/sin of one angle
@@ -1179,11 +1224,13 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                :1241): two converged evaluations instead of four divergent ones */
             V3 ap = mk(0, 0, 0);
             if (!bounce) { /* ray.cpp:1233-1239 */
+                if constexpr (RAYS) ap = ray_o;
+                else
                 if constexpr (VIEWS) ap = view_aperture_point(load_view_camera(rv, P.job_index), aperture, cs, sn);
                 else
                 ap = sub(add(add(cam_p, scale(aperture * cs, cam_x)), scale(aperture * sn, cam_y)), scale(0.1f, cam_z));
             }
-            const V3 unit1 = normalize(bounce ? n : sub(focal, ap));
+            const V3 unit1 = normalize(bounce ? n : (RAYS ? ray_d : sub(focal, ap)));
             bool is_trans = false;
             V3 raw = unit1;
             if (bounce) raw = sample_brdf_finish<false, true>(n, unit1, P.wo, m, draw, cs, sn, is_trans);
@@ -1192,8 +1239,11 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 if (is_trans) P.org = add(P.org, scale(2.0f * kEps, P.dir)); /* ray.cpp:1345-1348: dir is still the arriving direction */
                 P.dir = unit2;
             } else {
+                if constexpr (RAYS) { P.dir = ray_d; P.wo = neg(unit1); } /* the direction as given; wo = -normalize(d) */
+                else {
                 P.dir = unit1;
                 P.wo = neg(unit2);
+                }
                 P.org = ap;
                 P.weight = mk(1, 1, 1);
                 P.primary = true;
@@ -1207,9 +1257,13 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 raw = sample_brdf_finish<false>(n, normalize(n), P.wo, m, draw, cs, sn, is_trans);
             } else {
                 /* ray.cpp:1233-1246 */
+                if constexpr (RAYS) ap = ray_o;
+                else
                 if constexpr (VIEWS) ap = view_aperture_point(load_view_camera(rv, P.job_index), aperture, cs, sn);
                 else
                 ap = sub(add(add(cam_p, scale(aperture * cs, cam_x)), scale(aperture * sn, cam_y)), scale(0.1f, cam_z));
+                if constexpr (RAYS) raw = ray_d;
+                else
                 raw = sub(focal, ap);
             }
             const V3 unit = normalize(raw);
@@ -1217,8 +1271,11 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 if (is_trans) P.org = add(P.org, scale(2.0f * kEps, P.dir)); /* ray.cpp:1345-1348: dir is still the arriving direction */
                 P.dir = unit;
             } else {
+                if constexpr (RAYS) { P.dir = raw; P.wo = neg(unit); } /* the direction as given; wo = -normalize(d) */
+                else {
                 P.dir = unit;
                 P.wo = neg(normalize(P.dir)); /* normalised again (sic) */
+                }
                 P.org = ap;
                 P.weight = mk(1, 1, 1);
                 P.primary = true;
@@ -2270,6 +2327,59 @@ occluded_rays(SceneView sv, RenderHot rv, OccludedIO io) {
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
     occluded_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+}
+
+/* ---- radiance queries (ort_radiance): the path-traced light that arrives along a caller's ray ---------------------------
+ * The plain path-trace loop (pt_lane) with the ray array for a job space (produce_ray's RAYS flag): a lane draws a ray index from
+ * its wave's batch, runs spp samples of the reference's sample body (ray.cpp:1247-1426) from that ray on one xorshift stream,
+ * and writes the mean and the stream's state.  Primary rays are a caller's, so they pass raycast_needs_exact as the rays of
+ * ort_raycast do (inside the per-ray domain: an axis-aligned direction with boxes in the tree, an origin outside the scene's
+ * box with quadrics in it) and then skip the fast traversal: resolve_hit re-casts them exactly.  Bounce rays start at hits and
+ * need no rule, as in the render.  No ray exchange, no five-waves build, no wide tree, no wavefront mode (ort_plan.h). */
+template <bool COUNTERS, bool DIFFUSE, bool TABS>
+ORT_D void radiance_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, const int tid, const uint32_t lane_id,
+                         unsigned long long *pool) {
+    uint32_t spill[kSpillStack];
+    const uint32_t spp_u = rv.c->spp;
+    Prof pr;
+    PathState P;
+    HitState h;
+    Trav T;
+    Counters c;
+    bool tracing = false;
+    for (;;) {
+        if (!tracing) {
+            if (P.ps == PS_HIT) resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+            tracing = produce_ray<COUNTERS, DIFFUSE, TABS, true, false, true>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool);
+            if (tracing) {
+                begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
+                if (P.primary) {
+                    RaycastIO q{};
+                    q.tree_spheres = rv.c->ray_tree_spheres; q.tree_quadrics = rv.c->ray_tree_quadrics; q.tree_boxes = rv.c->ray_tree_boxes;
+                    for (int k = 0; k < 3; ++k) { q.lo[k] = rv.c->ray_lo[k]; q.hi[k] = rv.c->ray_hi[k]; }
+                    if (ORT_RARE(raycast_needs_exact(q, P.org, P.dir, T.inv_d))) {
+                        T.cur = kTraversalDone; /* no fast traversal: resolve_hit re-casts it exactly (a phantom that could win) */
+                        h.phantom_t = 0.0f;
+                    }
+                }
+                if (COUNTERS) c.rays++;
+            }
+        }
+        if (ORT_BALLOT(P.ps != PS_DONE) == 0ull) break;
+        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS, true>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+    }
+    flush_counters(rv, c, COUNTERS);
+}
+
+/* DIFFUSE and TABS as pt_persistent's: the BSDF flavour, and all three small tables in LDS or all of them in HBM */
+template <bool COUNTERS, bool DIFFUSE, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+radiance_rays(SceneView sv, RenderHot rv) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    if (TABS) fill_tab(sv, lds_tab);
+    radiance_lane<COUNTERS, DIFFUSE, TABS>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 
 #endif /* !ORT_W5_TU */

@@ -331,6 +331,40 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
     return pl;
 }
 
+/* The launch of a radiance query over count rays (ort_radiance; the radiance_rays kernels): always the plain persistent loop at
+   four waves, its job space the ray array.  The ray exchange, the five-waves unit, the wide tree and wavefront mode are not
+   built with a ray job space and their knobs are not looked at; ORT_DEBUG_UTIL has no probes here.  diffuse, tabs, the
+   refill and descend thresholds and the batch rules are decided as plan_render decides them for the plain loop, with one
+   difference: both BSDF flavours exist with counters.  Nothing of this has been tuned for ray batches yet. */
+struct RadiancePlan {
+    bool counters = false, diffuse = false, tabs = false;
+    unsigned int grid = 1;
+    int refill_below = 0, descend_below = 0;
+    uint32_t job_batch = 0;
+    unsigned long long batch_until = 0;
+};
+inline RadiancePlan plan_radiance(const SceneTraits &t, uint64_t count, bool counters, const Knobs &kn) {
+    RadiancePlan pl;
+    const bool cache_resident_tree = tree_is_cache_resident(t.fast_tree_bytes, kn.cache_resident);
+    pl.refill_below = kn.refill_below >= 0 ? kn.refill_below : (cache_resident_tree ? 16 : 32);
+    if (pl.refill_below < 1) pl.refill_below = 1;
+    if (pl.refill_below > 64) pl.refill_below = 64;
+    pl.descend_below = kn.descend_below >= 0 ? kn.descend_below : (cache_resident_tree ? 8 : 16);
+    if (pl.descend_below < 0) pl.descend_below = 0;
+    if (pl.descend_below > 64) pl.descend_below = 64;
+    pl.counters = counters;
+    pl.diffuse = t.diffuse_only && !kn.general_kernel;
+    pl.tabs = (t.tab_flags & kPlanAllTabs) == kPlanAllTabs && kn.lds_tables != 0;
+    pl.grid = (unsigned int)((count + kPlanBlock - 1) / kPlanBlock < t.max_blocks ? (count + kPlanBlock - 1) / kPlanBlock : t.max_blocks);
+    if (pl.grid == 0) pl.grid = 1;
+    const unsigned long long lanes = (unsigned long long)pl.grid * kPlanBlock;
+    pl.job_batch = kn.job_batch >= 0 ? (uint32_t)kn.job_batch : (count >= 96ull * lanes ? 128u : 64u);
+    const unsigned long long per_lane = kn.batch_tail >= 0 ? (unsigned long long)kn.batch_tail : 8ull * ((pl.job_batch + 63u) / 64u);
+    const unsigned long long tail = per_lane * lanes;
+    pl.batch_until = count > tail ? count - tail : 0ull;
+    return pl;
+}
+
 } // namespace ort
 
 #endif

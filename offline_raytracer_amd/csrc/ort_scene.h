@@ -224,6 +224,10 @@ int device_raycast(Scene *scene, const float *h_rays, const void *d_rays, uint64
    pointer, enqueued on stream); tmax may be null (no limit) */
 int device_occluded(Scene *scene, const float *h_rays, const void *d_rays, const void *tmax, uint64_t count, uint8_t *h_out, void *d_out,
                     uint32_t flags, void *stream, ort_stats *stats, std::string *err);
+/* radiance queries: host rays / seeds / colours / states (h_rays, seeds a host pointer, synchronous) or device ones (d_rays,
+   seeds a device pointer, enqueued on stream); the states may be null */
+int device_radiance(Scene *scene, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, uint32_t spp, float rr, float *h_out,
+                    void *d_out, uint32_t *h_states, void *d_states, uint32_t flags, void *stream, ort_stats *stats, std::string *err);
 /* ort_comm.cpp */
 struct Comm;
 uint64_t comm_shard_blocks(int32_t w, int32_t h, uint32_t index, uint32_t count);
