@@ -7,6 +7,7 @@
 
 #include "ort_lane.h"
 #include "ort_plan.h"
+#include "ort_setup.h"
 
 #ifndef ORT_HOST_SIM /* tools/host_sim.cpp drives the lane code itself and has no device */
 /* the five-waves build of the plain loop (ort_kernels_w5.hip) */
@@ -19,9 +20,7 @@ namespace ort {
 using namespace ortd;
 
 static_assert(kPlanBlock == (uint32_t)kBlock && kPlanLdsStack == (uint32_t)kLdsStack && kPlanStashVecs == kStashVecs && kPlanCapL == kCapL &&
-              kPlanCapR == kCapR && kPlanAllTabs == (TAB_PRO | TAB_LIGHTS | TAB_MATS) && kPlanTabPro == TAB_PRO && kPlanTabLights == TAB_LIGHTS &&
-              kPlanTabMats == TAB_MATS && kPlanTabMatCap == (uint32_t)kTabMatCap && kPlanTabLightCap == (uint32_t)kTabLightCap &&
-              kPlanTabProCap == (uint32_t)kTabProCap && (int)PLAN_JOBS_EXPLICIT == (int)JOBS_EXPLICIT &&
+              kPlanCapR == kCapR && (int)PLAN_JOBS_EXPLICIT == (int)JOBS_EXPLICIT && /* the table caps: ort_setup.h */
               (int)PLAN_JOBS_PIXEL == (int)JOBS_PIXEL && (int)PLAN_JOBS_CHUNK == (int)JOBS_CHUNK,
               "ort_plan.h counts with the lane code's limits");
 
@@ -151,8 +150,7 @@ int device_upload(Scene *scene, int device, std::string *err) {
         build_prim_info(t, scene->ref, info, d->info_box, d->info_cyl, d->info_sphere);
         if ((rc = upload_vec(info, &d->prim_info, err))) return rc;
     }
-    std::vector<DevMaterial> mats(scene->materials.size());
-    for (size_t i = 0; i < mats.size(); ++i) mats[i] = make_dev_material(scene->materials[i]);
+    const std::vector<DevMaterial> mats = dev_materials(*scene);
     if ((rc = upload_vec(mats, &d->materials, err))) return rc;
     d->diffuse_only = true; /* the four guards of eval_scattering / pdf_brdf, for every material a path can scatter on */
     for (size_t i = 1; i < mats.size(); ++i) {
@@ -162,31 +160,12 @@ int device_upload(Scene *scene, int device, std::string *err) {
         const float kt2 = dm.transmission[0] * dm.transmission[0] + dm.transmission[1] * dm.transmission[1] + dm.transmission[2] * dm.transmission[2];
         if (ks2 > 0.0f || kt2 > 0.0f || dm.ps_c > 0.0f || dm.pt_c > 0.0f) d->diffuse_only = false;
     }
-    std::vector<uint32_t> lis(scene->lights.size());
-    for (size_t i = 0; i < lis.size(); ++i) lis[i] = (scene->lights[i].type == 1u) ? 1u : 0u;
+    const std::vector<uint32_t> lis = light_sphere_flags(*scene);
     d->light_count = (uint32_t)lis.size();
     if ((rc = upload_vec(lis, &d->light_is_sphere, err))) return rc;
     {
-        /* the image of the LDS tables: root node, prologue shapes, light flags, materials */
-        std::vector<float4> tab((size_t)kTabF4, make_float4(0, 0, 0, 0));
-        uint32_t *tw = (uint32_t *)tab.data();
-        d->tab_flags = table_fit_flags(mats.size(), lis.size(), t.pro_boxes, t.pro_spheres, t.pro_cyls);
-        if (!t.nodes.empty()) memcpy(&tab[kTabRoot], &t.nodes[0], sizeof(DevNode));
-        {
-            /* the top of the fast tree; slots beyond the tree's size are never addressed */
-            const size_t nt = t.nodes.size() < (size_t)kTreeletNodes ? t.nodes.size() : (size_t)kTreeletNodes;
-            if (nt) memcpy(&tab[kTabTreelet], t.nodes.data(), nt * sizeof(DevNode));
-        }
-        if (d->tab_flags & TAB_PRO) {
-            float4 *q = &tab[kTabPro];
-            if (t.pro_boxes) memcpy(q, t.boxes.data(), (size_t)t.pro_boxes * sizeof(DevBox));
-            q += 2u * t.pro_boxes;
-            if (t.pro_spheres) memcpy(q, t.spheres.data(), (size_t)t.pro_spheres * sizeof(DevSphere));
-            q += t.pro_spheres;
-            if (t.pro_cyls) memcpy(q, t.cyls.data(), (size_t)t.pro_cyls * sizeof(DevCyl));
-        }
-        if ((d->tab_flags & TAB_LIGHTS) && !lis.empty()) memcpy(tw + 4 * kTabLights, lis.data(), lis.size() * 4u);
-        if (d->tab_flags & TAB_MATS) memcpy(&tab[kTabMats], mats.data(), mats.size() * sizeof(DevMaterial));
+        std::vector<F4> tab; /* the image of the LDS tables (pack_lds_tables) */
+        d->tab_flags = pack_lds_tables(t, mats, lis, tab);
         if ((rc = upload_vec(tab, &d->tab, err))) return rc;
     }
     const RefTree &rt = scene->ref;
@@ -526,17 +505,10 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
         }
     }
     if (pl.views) {
-        /* 4 float4 per view: p.xyz and the seed's bits, then the three axes.  Both copies of the table are the previous call's
-           until that has finished (settled above); the caller's array is read here and not again */
+        /* the camera table (pack_view_table).  Both copies of it are the previous call's until that has finished (settled
+           above); the caller's array is read here and not again */
         std::vector<float> &tab = d->view_tab_host;
-        tab.assign((size_t)view_count * 16u, 0.0f);
-        for (uint32_t v = 0; v < view_count; ++v) {
-            float *q = &tab[(size_t)v * 16u];
-            const ort_camera &c = views[v].camera;
-            const float rows[4][3] = {{c.p.x, c.p.y, c.p.z}, {c.x_axis.x, c.x_axis.y, c.x_axis.z}, {c.y_axis.x, c.y_axis.y, c.y_axis.z}, {c.z_axis.x, c.z_axis.y, c.z_axis.z}};
-            for (int r = 0; r < 4; ++r) memcpy(q + 4 * r, rows[r], sizeof(rows[r]));
-            memcpy(q + 3, &views[v].seed, sizeof(uint32_t));
-        }
+        pack_view_table(views, view_count, tab);
         if ((rc = d->view_tab.ensure(tab.size() * sizeof(float), err))) return rc;
         ORT_HIP(hipMemcpyAsync(d->view_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, stream));
         rv.views = d->view_tab.as<const float4>();
@@ -619,21 +591,8 @@ static void ensure_scene_box(Scene *scene, DeviceScene *d) {
    the shape's index in the scene's own arrays.  Built and uploaded at the first query, so that render-only users pay nothing */
 static int ensure_prim_src(Scene *scene, DeviceScene *d, std::string *err) {
     if (d->prim_src.p) return ORT_OK;
-    const Tree &t = scene->tree;
-    std::vector<uint32_t> src((size_t)d->info_sphere + t.spheres.size(), kNoPrim);
-    bool bijective = src.size() == t.tri_slot.size() + t.box_slot.size() + t.cyl_slot.size() + t.sphere_slot.size();
-    auto invert = [&](uint32_t kind, uint32_t base, const std::vector<uint32_t> &slot, size_t slots) {
-        bijective = bijective && slot.size() == slots;
-        for (size_t i = 0; i < slot.size() && bijective; ++i) {
-            bijective = slot[i] < slots && src[base + slot[i]] == kNoPrim && i < 0x10000000u;
-            if (bijective) src[base + slot[i]] = (kind << 28) | (uint32_t)i;
-        }
-    };
-    invert(PRIM_TRI, 0u, t.tri_slot, t.tris.size());
-    invert(PRIM_BOX, d->info_box, t.box_slot, t.boxes.size());
-    invert(PRIM_CYL, d->info_cyl, t.cyl_slot, t.cyls.size());
-    invert(PRIM_SPHERE, d->info_sphere, t.sphere_slot, t.spheres.size());
-    for (uint32_t v : src) bijective = bijective && v != kNoPrim;
+    std::vector<uint32_t> src;
+    const bool bijective = invert_prim_slots(scene->tree, d->info_box, d->info_cyl, d->info_sphere, src);
     if (!bijective) { *err = "internal: the tree's slot maps are not a bijection onto its shape arrays"; return ORT_ERR_INTERNAL; }
     ensure_scene_box(scene, d);
     return upload_vec(src, &d->prim_src, err);
@@ -643,11 +602,7 @@ static int ensure_prim_src(Scene *scene, DeviceScene *d, std::string *err) {
 static RaycastIO ray_query_io(Scene *scene, DeviceScene *d, const void *d_rays) {
     RaycastIO io{};
     io.rays = (const float2 *)d_rays;
-    io.tree_spheres = scene->tree.spheres.size() > scene->tree.pro_spheres;
-    io.tree_quadrics = io.tree_spheres || scene->tree.cyls.size() > scene->tree.pro_cyls;
-    io.tree_boxes = scene->tree.boxes.size() > scene->tree.pro_boxes;
-    memcpy(io.lo, d->scene_lo, sizeof(io.lo));
-    memcpy(io.hi, d->scene_hi, sizeof(io.hi));
+    ort::ray_query_io(*scene, d->scene_lo, d->scene_hi, &io);
     return io;
 }
 
@@ -729,10 +684,7 @@ static int launch_occluded(Scene *scene, DeviceScene *d, const void *d_rays, con
     io.q = ray_query_io(scene, d, d_rays);
     io.tmax = (const float *)d_tmax;
     io.out = (uint8_t *)d_out;
-    const Tree &t = scene->tree;
-    io.mats_nonzero = 1u;
-    for (const std::vector<uint32_t> *m : {&t.tri_mat, &t.box_mat, &t.cyl_mat, &t.sphere_mat})
-        for (uint32_t v : *m) if (v == 0u) io.mats_nonzero = 0u;
+    io.mats_nonzero = all_mats_nonzero(scene->tree);
     unsigned int grid = 0;
     RenderHot hot{};
     if ((rc = ray_query_plan(scene, d, count, stream, &grid, &hot, err))) return rc;

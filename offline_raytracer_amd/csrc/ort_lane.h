@@ -33,6 +33,7 @@
 
 #include "ort_device.h"
 #include "ort_scene.h"
+#include "ort_setup.h"
 
 #ifdef ORT_W5_TU
 #define ORT_NS ort_w5
@@ -60,19 +61,7 @@ constexpr size_t kBfsPoolBytes = 1024u << 20; /* at most; a queue holds one entr
 constexpr int kDiagFallback = 106;            /* fallback_counters = ctrl + 6: the diagnostics sit at ctrl[112..114] */
 constexpr uint32_t kBfsLockStride = 32;       /* u32 units: every lock word has a 128-byte line to itself */
 
-/* Small read-only tables every ray touches live in LDS, copied there once per workgroup: ~100 cycles of latency
-   instead of a trip to L1 / L2 on the critical path of every ray (the kernel is latency-bound: DESIGN.md).
-   Layout in float4 units; a table that does not fit its slot stays in HBM (SceneView::tab_flags). */
-constexpr int kTabRoot = 0;                      /* node 0 of the fast tree (4) */
-constexpr int kTabPro = 4;                       /* the analytic prologue's shapes: boxes (2 each), spheres (1), cylinders (4) */
-constexpr int kTabProCap = 40;
-constexpr int kTabLights = kTabPro + kTabProCap; /* light_is_sphere[64] as u32 */
-constexpr int kTabLightCap = 64;
-constexpr int kTabMats = kTabLights + kTabLightCap / 4; /* DevMaterial records, 5 each */
-constexpr int kTabMatCap = 48;
-constexpr int kTabTreelet = kTabMats + 5 * kTabMatCap; /* nodes [0, kTreeletNodes) of the fast tree, breadth-first top (ort_tree.cpp) */
-constexpr int kTabF4 = kTabTreelet + 4 * (int)kTreeletNodes; /* 428 float4 = 6848 B */
-enum : uint32_t { TAB_PRO = 1u, TAB_LIGHTS = 2u, TAB_MATS = 8u };
+/* the layout of the small LDS tables (kTabRoot ... kTabF4, TAB_*): ort_setup.h, with the host code that fills them */
 
 #ifdef ORT_HOST_SIM
 #define ORT_CONSTANT_AS
@@ -686,7 +675,8 @@ ORT_D void reset_hit(HitState &h, float best_t) {
 template <bool COUNTERS, bool TABS, bool HAS_EXCL = false>
 ORT_D void prologue_tests(const SceneView &sv, const float4 *tab, V3 org, V3 dir, V3 inv_d, HitState &h, Counters &c, uint32_t excl = kNoPrim) {
     /* TABS: the shapes' records come from the LDS tables */
-    const float4 *pb = tab + kTabPro, *ps = pb + 2u * sv.pro_boxes, *pc = ps + sv.pro_spheres;
+    const float4 *pb = nullptr, *ps = nullptr, *pc = nullptr; /* formed under TABS only: tab is null without them */
+    if (TABS) { pb = tab + kTabPro; ps = pb + 2u * sv.pro_boxes; pc = ps + sv.pro_spheres; }
     /* boxes: when every lane's origin and 1/d are finite (all but a handful of rays), the slab test runs on the
        hardware's min / max (hit_aab_finite: same values); wave-uniform choice, so no lane waits for the other form */
 #ifndef ORT_PROLOGUE_DEFER
@@ -694,7 +684,7 @@ ORT_D void prologue_tests(const SceneView &sv, const float4 *tab, V3 org, V3 dir
 #endif
     if (!ORT_PROLOGUE_DEFER && ORT_BALLOT(!all_finite6(org, inv_d)) == 0ull) {
         for (uint32_t i = 0; i < sv.pro_boxes; ++i)
-            test_prim<COUNTERS, false, true, TABS>(sv, PRIM_BOX, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, pb + 2u * i);
+            test_prim<COUNTERS, false, true, TABS>(sv, PRIM_BOX, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? pb + 2u * i : nullptr);
     } else
     if (ORT_BALLOT(!all_finite6(org, inv_d)) == 0ull) {
         /* distances only while the boxes compete (test_prim's rule: accept 1e-6 <= t < best, equal distances by reference
@@ -722,12 +712,12 @@ ORT_D void prologue_tests(const SceneView &sv, const float4 *tab, V3 org, V3 dir
         }
     } else {
         for (uint32_t i = 0; i < sv.pro_boxes; ++i)
-            test_prim<COUNTERS, false, false, TABS>(sv, PRIM_BOX, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, pb + 2u * i);
+            test_prim<COUNTERS, false, false, TABS>(sv, PRIM_BOX, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? pb + 2u * i : nullptr);
     }
     for (uint32_t i = 0; i < sv.pro_spheres; ++i)
-        test_prim<COUNTERS, false, false, TABS>(sv, PRIM_SPHERE, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, ps + i);
+        test_prim<COUNTERS, false, false, TABS>(sv, PRIM_SPHERE, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? ps + i : nullptr);
     for (uint32_t i = 0; i < sv.pro_cyls; ++i)
-        test_prim<COUNTERS, false, false, TABS>(sv, PRIM_CYL, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, pc + 4u * i);
+        test_prim<COUNTERS, false, false, TABS>(sv, PRIM_CYL, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? pc + 4u * i : nullptr);
 }
 
 #ifndef ORT_HOST_SIM
@@ -972,6 +962,9 @@ ORT_D unsigned long long *wave_job_pool(const RenderHot &rv, unsigned long long 
     if ((threadIdx.x & 63u) == 0u) { ((volatile unsigned long long *)pool)[0] = 0ull; ((volatile unsigned long long *)pool)[1] = 0ull; }
     return rv.c->job_batch > 1u ? pool : nullptr;
 }
+#else
+/* one simulated lane draws one index at a time (tools/host_sim.cpp passes no pool) */
+ORT_D unsigned long long draw_job(const RenderHot &rv, unsigned long long *) { return ORT_NEXT_JOB(rv.c->next_job); }
 #endif
 
 /* IMPLICIT: the caller vouches for an implicit job space (PIXEL / CHUNK policies: every job is one pixel, spp_u
@@ -2124,6 +2117,10 @@ __global__ void combine_chunks_views(RenderHot rv) {
     combine_pixel(rv, idx % per_view, (uint32_t)(idx / per_view));
 }
 
+#endif /* !ORT_W5_TU */
+#endif /* !ORT_HOST_SIM */
+
+#ifndef ORT_W5_TU
 /* ---- closest-hit ray queries (ort_raycast): raycast_top_most_node, ray.cpp:1165-1176 --------------------------------
  * The path-trace loop without shading: a lane without a ray takes the next ray index from its wave's batch (draw_job:
  * the job space is the ray array, job_count rays), starts it (begin_ray: analytic prologue from the LDS tables),
@@ -2209,6 +2206,7 @@ ORT_D void raycast_lane(const SceneView &sv, const RenderHot &rv, const RaycastI
 
 /* TABS: the prologue shapes fit their LDS slot (TAB_PRO: at most kTabProCap float4, ort_plan.h table_fit_flags); otherwise they
    are read from HBM */
+#ifndef ORT_HOST_SIM
 template <bool COUNTERS, bool TABS>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
 raycast_rays(SceneView sv, RenderHot rv, RaycastIO io) {
@@ -2218,6 +2216,7 @@ raycast_rays(SceneView sv, RenderHot rv, RaycastIO io) {
     if (TABS) fill_tab(sv, lds_tab);
     raycast_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
+#endif
 
 /* ---- occlusion ray queries (ort_occluded): is anything in the way before tmax? ---------------------------------------
  * occluded = (h.mat != 0 && h.t < tmax), h the closest hit raycast_rays returns.  The loop of raycast_lane with three
@@ -2319,6 +2318,7 @@ ORT_D void occluded_lane(const SceneView &sv, const RenderHot &rv, const Occlude
     flush_counters(rv, c, COUNTERS);
 }
 
+#ifndef ORT_HOST_SIM
 template <bool COUNTERS, bool TABS>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
 occluded_rays(SceneView sv, RenderHot rv, OccludedIO io) {
@@ -2328,6 +2328,7 @@ occluded_rays(SceneView sv, RenderHot rv, OccludedIO io) {
     if (TABS) fill_tab(sv, lds_tab);
     occluded_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
+#endif
 
 /* ---- radiance queries (ort_radiance): the path-traced light that arrives along a caller's ray ---------------------------
  * The plain path-trace loop (pt_lane) with the ray array for a job space (produce_ray's RAYS flag): a lane draws a ray index from
@@ -2372,6 +2373,7 @@ ORT_D void radiance_lane(const SceneView &sv, const RenderHot &rv, const float4 
 }
 
 /* DIFFUSE and TABS as pt_persistent's: the BSDF flavour, and all three small tables in LDS or all of them in HBM */
+#ifndef ORT_HOST_SIM
 template <bool COUNTERS, bool DIFFUSE, bool TABS>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
 radiance_rays(SceneView sv, RenderHot rv) {
@@ -2381,9 +2383,9 @@ radiance_rays(SceneView sv, RenderHot rv) {
     if (TABS) fill_tab(sv, lds_tab);
     radiance_lane<COUNTERS, DIFFUSE, TABS>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
+#endif
 
 #endif /* !ORT_W5_TU */
-#endif /* !ORT_HOST_SIM */
 
 } // namespace ORT_NS
 

@@ -52,6 +52,9 @@ struct Number {
     union { int32_t i; float f; } v;
 };
 
+/* -v as two's complement wraps it: INT32_MIN (an oversized literal, or 2147483648 itself) stays INT32_MIN, defined */
+inline int32_t negate_i32(int32_t v) { return (int32_t)(0u - (uint32_t)v); }
+
 Number lex_number(Cursor *c) {
     Number n;
     n.v.i = 0;
@@ -75,7 +78,7 @@ Number lex_number(Cursor *c) {
         ++c->at;
     }
     if (n.is_float) n.v.f = (float)(digits * scale);
-    else n.v.i = (int32_t)digits;
+    else n.v.i = digits < 2147483648.0 ? (int32_t)digits : INT32_MIN; /* too many digits for an i32: what x86's conversion gives, defined */
     if (exponent) {
         ++c->at; /* 'e' */
         bool plus = (c->peek() == '+');
@@ -138,7 +141,7 @@ ScnToken next_scn_token(Cursor *c) {
         } else {
             t.type = Tok::I32;
             t.i = n.v.i;
-            if (neg) t.i *= -1;
+            if (neg) t.i = negate_i32(t.i);
         }
     }
     c->skip_word(); /* every token ends by running to the next whitespace */
@@ -182,7 +185,7 @@ PlyToken next_ply_token(Cursor *c) {
             if (neg) ++c->at;
             Number n = lex_number(c);
             if (n.is_float) { t.type = PlyTok::F32; t.f = n.v.f; if (neg) t.f *= -1.0f; }
-            else { t.type = PlyTok::I32; t.i = n.v.i; if (neg) t.i *= -1; }
+            else { t.type = PlyTok::I32; t.i = n.v.i; if (neg) t.i = negate_i32(t.i); }
         } else {
             c->skip_line(); /* unknown header line */
         }
@@ -250,6 +253,8 @@ int load_ply(const std::vector<char> &file, HostMesh *mesh, std::string *err) {
         for (int32_t extra = 1; extra < k.i - 2; ++extra) {
             uint32_t prev = mesh->indices.back();
             PlyToken nx = next_ply_token(&c);
+            /* a count the line (or the file) does not hold: malformed, not two billion triangles of whatever comes next */
+            if (nx.type != PlyTok::I32) { *err = "ply: face index is not an integer"; return ORT_ERR_PARSE; }
             mesh->indices.push_back((uint32_t)a.i);
             mesh->indices.push_back(prev);
             mesh->indices.push_back((uint32_t)nx.i);
@@ -283,7 +288,7 @@ ObjToken next_obj_token(Cursor *c, bool *stuck) {
     } else if (c->peek() >= '0' && c->peek() <= '9') {
         Number n = lex_number(c);
         if (n.is_float) { t.type = ObjTok::F32; t.f = n.v.f; if (neg) t.f *= -1.0f; }
-        else { t.type = ObjTok::I32; t.i = n.v.i; if (neg) t.i *= -1; }
+        else { t.type = ObjTok::I32; t.i = n.v.i; if (neg) t.i = negate_i32(t.i); }
     } else if (!c->done() && !neg) {
         *stuck = true;
     }
@@ -331,9 +336,10 @@ int load_obj(const std::vector<char> &file, HostMesh *mesh, std::string *err) {
                 int more = (per_corner == 1) ? 0 : (per_corner == 2 ? 3 : 4);
                 for (int k = 0; k < more; ++k) next_obj_token(&c, &stuck);
             }
-            mesh->indices.push_back((uint32_t)(first[0] - 1));
-            mesh->indices.push_back((uint32_t)(first[1] - 1));
-            mesh->indices.push_back((uint32_t)(first[2] - 1));
+            /* one-based to zero-based in unsigned: the same index for every i32, and defined for INT32_MIN (checked against the vertex count later) */
+            mesh->indices.push_back((uint32_t)first[0] - 1u);
+            mesh->indices.push_back((uint32_t)first[1] - 1u);
+            mesh->indices.push_back((uint32_t)first[2] - 1u);
             uint32_t numbers_seen = 0;
             for (;;) {
                 Cursor look = c;
@@ -342,9 +348,9 @@ int load_obj(const std::vector<char> &file, HostMesh *mesh, std::string *err) {
                 if (nx.type == ObjTok::I32) {
                     if (numbers_seen % (uint32_t)per_corner == 0) {
                         uint32_t prev = mesh->indices.back();
-                        mesh->indices.push_back((uint32_t)(first[0] - 1));
+                        mesh->indices.push_back((uint32_t)first[0] - 1u);
                         mesh->indices.push_back(prev);
-                        mesh->indices.push_back((uint32_t)(nx.i - 1));
+                        mesh->indices.push_back((uint32_t)nx.i - 1u);
                     }
                     ++numbers_seen;
                     next_obj_token(&c, &stuck);

@@ -1,0 +1,134 @@
+/*
+ * ort_setup.h -- what the host works out from a committed scene before a kernel can run, as plain functions of their
+ * inputs: the layout and the image of the small LDS tables, the shape table of the ray queries (the inverse of the tree's
+ * slot maps), what raycast_needs_exact reads, and the camera table of a batch of views.  No HIP in here: ort_kernels.hip
+ * calls these and keeps the uploads and launches; tools/host_sim.cpp calls the same functions to run the lane code on host
+ * threads, so the CPU tests exercise the product's own tables (tests/test_query_lanes_host.py).
+ */
+#ifndef ORT_SETUP_H
+#define ORT_SETUP_H
+
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "ort_plan.h"
+#include "ort_scene.h"
+
+namespace ort {
+
+/* Small read-only tables every ray touches live in LDS, copied there once per workgroup: ~100 cycles of latency
+   instead of a trip to L1 / L2 on the critical path of every ray (the kernel is latency-bound: DESIGN.md).
+   Layout in float4 units; a table that does not fit its slot stays in HBM (SceneView::tab_flags). */
+constexpr int kTabRoot = 0;                      /* node 0 of the fast tree (4) */
+constexpr int kTabPro = 4;                       /* the analytic prologue's shapes: boxes (2 each), spheres (1), cylinders (4) */
+constexpr int kTabProCap = 40;
+constexpr int kTabLights = kTabPro + kTabProCap; /* light_is_sphere[64] as u32 */
+constexpr int kTabLightCap = 64;
+constexpr int kTabMats = kTabLights + kTabLightCap / 4; /* DevMaterial records, 5 each */
+constexpr int kTabMatCap = 48;
+constexpr int kTabTreelet = kTabMats + 5 * kTabMatCap; /* nodes [0, kTreeletNodes) of the fast tree, breadth-first top (ort_tree.cpp) */
+constexpr int kTabF4 = kTabTreelet + 4 * (int)kTreeletNodes; /* 428 float4 = 6848 B */
+enum : uint32_t { TAB_PRO = 1u, TAB_LIGHTS = 2u, TAB_MATS = 8u };
+
+static_assert(kPlanAllTabs == (TAB_PRO | TAB_LIGHTS | TAB_MATS) && kPlanTabPro == TAB_PRO && kPlanTabLights == TAB_LIGHTS && kPlanTabMats == TAB_MATS &&
+              kPlanTabMatCap == (uint32_t)kTabMatCap && kPlanTabLightCap == (uint32_t)kTabLightCap && kPlanTabProCap == (uint32_t)kTabProCap,
+              "ort_plan.h counts with the table layout's caps");
+static_assert(sizeof(F4) == 16 && sizeof(DevNode) == 4 * sizeof(F4) && sizeof(DevBox) == 2 * sizeof(F4) && sizeof(DevSphere) == sizeof(F4) &&
+              sizeof(DevCyl) == 4 * sizeof(F4) && sizeof(DevMaterial) == 5 * sizeof(F4), "the table layout counts records in 16-byte units");
+
+/* the materials and the lights' kinds as the kernels read them */
+inline std::vector<DevMaterial> dev_materials(const Scene &scene) {
+    std::vector<DevMaterial> mats(scene.materials.size());
+    for (size_t i = 0; i < mats.size(); ++i) mats[i] = make_dev_material(scene.materials[i]);
+    return mats;
+}
+inline std::vector<uint32_t> light_sphere_flags(const Scene &scene) {
+    std::vector<uint32_t> lis(scene.lights.size());
+    for (size_t i = 0; i < lis.size(); ++i) lis[i] = (scene.lights[i].type == 1u) ? 1u : 0u;
+    return lis;
+}
+
+/* the image of the LDS tables (kTabF4 records of 16 bytes): root node, prologue shapes, light flags, materials, the tree's top.
+   Returns which tables fit their slot (table_fit_flags); one that does not is left zero and read from its own array */
+inline uint32_t pack_lds_tables(const Tree &t, const std::vector<DevMaterial> &mats, const std::vector<uint32_t> &lis, std::vector<F4> &tab) {
+    tab.assign((size_t)kTabF4, F4{0, 0, 0, 0});
+    const uint32_t flags = table_fit_flags(mats.size(), lis.size(), t.pro_boxes, t.pro_spheres, t.pro_cyls);
+    if (!t.nodes.empty()) memcpy(&tab[kTabRoot], &t.nodes[0], sizeof(DevNode));
+    {
+        /* the top of the fast tree; slots beyond the tree's size are never addressed */
+        const size_t nt = t.nodes.size() < (size_t)kTreeletNodes ? t.nodes.size() : (size_t)kTreeletNodes;
+        if (nt) memcpy(&tab[kTabTreelet], t.nodes.data(), nt * sizeof(DevNode));
+    }
+    if (flags & TAB_PRO) {
+        F4 *q = &tab[kTabPro];
+        if (t.pro_boxes) memcpy(q, t.boxes.data(), (size_t)t.pro_boxes * sizeof(DevBox));
+        q += 2u * t.pro_boxes;
+        if (t.pro_spheres) memcpy(q, t.spheres.data(), (size_t)t.pro_spheres * sizeof(DevSphere));
+        q += t.pro_spheres;
+        if (t.pro_cyls) memcpy(q, t.cyls.data(), (size_t)t.pro_cyls * sizeof(DevCyl));
+    }
+    if ((flags & TAB_LIGHTS) && !lis.empty()) memcpy(&tab[kTabLights], lis.data(), lis.size() * 4u);
+    if ((flags & TAB_MATS) && !mats.empty()) memcpy(&tab[kTabMats], mats.data(), mats.size() * sizeof(DevMaterial));
+    return flags;
+}
+
+/* ray queries: the inverse of the tree's slot maps, in PrimInfo order (triangles | boxes | cylinders | spheres; info_* are
+   build_prim_info's): slot -> kind << 28 | the shape's index in the scene's own arrays.  False when the maps are no bijection
+   onto the shape arrays */
+inline bool invert_prim_slots(const Tree &t, uint32_t info_box, uint32_t info_cyl, uint32_t info_sphere, std::vector<uint32_t> &src) {
+    const uint32_t none = 0xffffffffu; /* kNoPrim */
+    src.assign((size_t)info_sphere + t.spheres.size(), none);
+    bool bijective = src.size() == t.tri_slot.size() + t.box_slot.size() + t.cyl_slot.size() + t.sphere_slot.size();
+    auto invert = [&](uint32_t kind, uint32_t base, const std::vector<uint32_t> &slot, size_t slots) {
+        bijective = bijective && slot.size() == slots && (size_t)base + slots <= src.size();
+        for (size_t i = 0; i < slot.size() && bijective; ++i) {
+            bijective = slot[i] < slots && src[base + slot[i]] == none && i < 0x10000000u;
+            if (bijective) src[base + slot[i]] = (kind << 28) | (uint32_t)i;
+        }
+    };
+    invert(PRIM_TRI, 0u, t.tri_slot, t.tris.size());
+    invert(PRIM_BOX, info_box, t.box_slot, t.boxes.size());
+    invert(PRIM_CYL, info_cyl, t.cyl_slot, t.cyls.size());
+    invert(PRIM_SPHERE, info_sphere, t.sphere_slot, t.spheres.size());
+    for (uint32_t v : src) bijective = bijective && v != none;
+    return bijective;
+}
+
+/* what raycast_needs_exact reads (IO: RaycastIO of ort_lane.h): which kinds of shape the fast tree holds, and the scene's box
+   (scene_origin_box) */
+template <typename IO>
+inline void ray_query_io(const Scene &scene, const float lo[3], const float hi[3], IO *io) {
+    io->tree_spheres = scene.tree.spheres.size() > scene.tree.pro_spheres;
+    io->tree_quadrics = io->tree_spheres || scene.tree.cyls.size() > scene.tree.pro_cyls;
+    io->tree_boxes = scene.tree.boxes.size() > scene.tree.pro_boxes;
+    memcpy(io->lo, lo, 3 * sizeof(float));
+    memcpy(io->hi, hi, 3 * sizeof(float));
+}
+
+/* occlusion queries: no shape of the scene carries material 0 (the early end of occluded_lane) */
+inline uint32_t all_mats_nonzero(const Tree &t) {
+    for (const std::vector<uint32_t> *m : {&t.tri_mat, &t.box_mat, &t.cyl_mat, &t.sphere_mat})
+        for (uint32_t v : *m) if (v == 0u) return 0u;
+    return 1u;
+}
+
+/* a batch of views: the camera table load_view_camera reads, 4 records of 16 bytes per view: p.xyz and the seed's bits, then
+   the three axes */
+inline void pack_view_table(const ort_view *views, uint32_t view_count, std::vector<float> &tab) {
+    tab.assign((size_t)view_count * 16u, 0.0f);
+    for (uint32_t v = 0; v < view_count; ++v) {
+        float *q = &tab[(size_t)v * 16u];
+        const ort_camera &c = views[v].camera;
+        const float rows[4][3] = {{c.p.x, c.p.y, c.p.z}, {c.x_axis.x, c.x_axis.y, c.x_axis.z}, {c.y_axis.x, c.y_axis.y, c.y_axis.z}, {c.z_axis.x, c.z_axis.y, c.z_axis.z}};
+        for (int r = 0; r < 4; ++r) memcpy(q + 4 * r, rows[r], sizeof(rows[r]));
+        memcpy(q + 3, &views[v].seed, sizeof(uint32_t));
+    }
+}
+
+} // namespace ort
+
+#endif

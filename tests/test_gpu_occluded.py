@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import raycast_cases
+from occluded_cases import RUNGS, drawn_limits, expected, ladder, laddered  # noqa: F401
 import table_scenes
 from conftest import GOLDEN
 from test_gpu_raycast import SCENES, golden_like, mixed_rays, torch_raycast
@@ -21,36 +22,7 @@ pytestmark = pytest.mark.gpu
 F32 = np.float32
 FLT_MAX = F32(3.4028235e38)
 INF = F32(np.inf)
-RUNGS = ["-inf", "-1", "-0.0", "0", "t/2", "prev(t)", "t", "next(t)", "2t", "FLT_MAX", "+inf", "NaN"]
 KINDS = ["golden distribution", "start on a surface", "axis-aligned / non-unit", "outside, missing"]
-
-
-def ladder(t):
-    """(len(t), 12) limits: the rungs of RUNGS for every expected distance"""
-    t = np.asarray(t, "<f4")
-    with np.errstate(over="ignore", invalid="ignore"):
-        cols = [np.full_like(t, -INF), np.full_like(t, -1), np.full_like(t, -0.0), np.zeros_like(t), t * F32(0.5),
-                np.nextafter(t, -INF), t, np.nextafter(t, INF), t * F32(2), np.full_like(t, FLT_MAX), np.full_like(t, INF),
-                np.full_like(t, np.nan)]
-    out = np.stack(cols, axis=1).astype("<f4")
-    assert out.shape[1] == len(RUNGS)
-    return out
-
-
-def expected(t, mat, tmax):
-    """the contract, as it reads"""
-    with np.errstate(invalid="ignore"):
-        return (np.asarray(mat) != 0) & (np.asarray(t, "<f4") < np.asarray(tmax, "<f4"))
-
-
-def laddered(rays, t, mat):
-    """every ray once per rung, all rungs in one batch -> (rays, tmax, expected, rung index)"""
-    lad = ladder(t)
-    k = lad.shape[1]
-    rr = np.repeat(np.ascontiguousarray(rays, "<f4"), k, axis=0)
-    tm = lad.reshape(-1)
-    want = expected(np.repeat(t, k), np.repeat(mat, k), tm)
-    return rr, tm, want, np.tile(np.arange(k), len(t))
 
 
 def assert_bytes(got, want, what, groups=None, names=None):
@@ -122,15 +94,6 @@ def test_reference_fixtures_through_the_ladder(api, gpu_scene, prefix, name):
 
 
 # ---- 2. the oracle at scale --------------------------------------------------------------------------------------------
-def drawn_limits(rng, t):
-    """per ray one of prev(t), t, next(t), t * U(0, 2), +inf"""
-    t = np.asarray(t, "<f4")
-    with np.errstate(over="ignore", invalid="ignore"):
-        choice = np.stack([np.nextafter(t, -INF), t, np.nextafter(t, INF), (t * rng.uniform(0, 2, len(t)).astype("<f4")).astype("<f4"),
-                           np.full_like(t, INF)], axis=1)
-    return choice[np.arange(len(t)), rng.integers(0, 5, len(t))].astype("<f4")
-
-
 @pytest.mark.parametrize("name,n", [(s, 20000) for s in SCENES] + [("c5_heightfield_224", 4000)])
 def test_against_oracle_at_scale(api, oracle, gpu_scene, name, n):
     scene = gpu_scene(name)

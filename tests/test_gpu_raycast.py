@@ -2,31 +2,21 @@
 reference's raycast_top_most_node (ray.cpp:1165-1176) -- its own outputs (tests/golden/raycast_*.npz) and, at scale
 and on the hard cases (rays that start on a surface, axis-aligned and non-unit directions, misses), the oracle."""
 import os
-import zlib
 
 import numpy as np
 import pytest
 
+import raycast_cases
 import ref_io
 from conftest import DATA, GOLDEN, assert_bits_equal
+from raycast_cases import golden_like, unit_vectors  # noqa: F401  (other test files import them from here)
+from raycast_cases import needs_exact as _needs_exact, scene_box as _scene_box, threshold_rays as _threshold_rays  # noqa: F401
+from raycast_cases import threshold_scene as _threshold_scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SCENES = ["testscene", "c2_analytic", "c3_bunny_room", "c4_dwarf_room", "letters", "glass_room", "rand_a", "rand_b"]
 FLT_MAX = np.float32(3.4028235e38)
-
-
-def unit_vectors(rng, n):
-    v = rng.normal(size=(n, 3))
-    return (v / np.linalg.norm(v, axis=1, keepdims=True)).astype("<f4")
-
-
-def golden_like(rng, n):
-    """the goldens' distribution (tests/golden/make_golden.py): origins in and around the room, uniform directions"""
-    o = np.stack([rng.uniform(-2.5, 14.5, n), rng.uniform(-2.5, 14.5, n), rng.uniform(0.05, 8.8, n)], axis=1)
-    h = n // 2
-    o[:h] = np.stack([rng.uniform(-1.5, 1.5, h), rng.uniform(-1.8, 1.5, h), rng.uniform(0.05, 2.5, h)], axis=1)
-    return np.concatenate([o.astype("<f4"), unit_vectors(rng, n)], axis=1)
 
 
 def hits_of(hits):
@@ -70,30 +60,8 @@ def test_reference_goldens(api, gpu_scene, name):
 
 
 def mixed_rays(scene, name, n):
-    """the four kinds of ray, n in all: golden distribution, rays that start on a surface (a first cast's o + t d, new
-    directions), axis-aligned / zero-component / non-unit directions, rays from outside that miss"""
-    rng = np.random.default_rng(zlib.crc32(("mixed " + name).encode()))
-    q = n // 4
-    a = golden_like(rng, q)
-    first, _ = scene.raycast(golden_like(rng, 2 * q))
-    base = golden_like(rng, 2 * q)
-    hit = first["t"] < FLT_MAX
-    o = base[hit, 0:3] + first["t"][hit, None] * base[hit, 3:6]  # float32 arithmetic, rounded per operation
-    o = o[:q].astype("<f4")
-    b = np.concatenate([o, unit_vectors(rng, len(o))], axis=1)
-    # axis-aligned and zero-component directions, non-unit lengths
-    axes = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1],
-                     [1, 1, 0], [0, -1, 1], [1, 0, -1], [-1, 1, 1]], "<f4")
-    d = axes[rng.integers(0, len(axes), q)] * rng.choice(np.array([1e-3, 0.1, 0.5, 1, 2, 37.5], "<f4"), q)[:, None]
-    mix = rng.random(q) < 0.3  # some non-unit random directions too
-    d[mix] = unit_vectors(rng, int(mix.sum())) * rng.uniform(0.01, 50, int(mix.sum()))[:, None].astype("<f4")
-    c = np.concatenate([golden_like(rng, q)[:, 0:3], d.astype("<f4")], axis=1)
-    # from far outside, pointing away from the scene
-    u = unit_vectors(rng, n - 3 * q)
-    e = np.concatenate([(u * np.float32(1000.0) + np.float32(6.0)).astype("<f4"), u * rng.uniform(0.5, 2, len(u))[:, None].astype("<f4")], axis=1)
-    rays = np.concatenate([a, b, c, e]).astype("<f4")
-    kinds = np.repeat(np.arange(4), [len(a), len(b), len(c), len(e)])
-    return rays, kinds
+    """raycast_cases.mixed_rays with the device's own first cast placing the surface starts"""
+    return raycast_cases.mixed_rays(lambda rays: scene.raycast(rays)[0]["t"], name, n)
 
 
 @pytest.mark.parametrize("name,n", [(s, 20000) for s in SCENES] + [("c5_heightfield_224", 4000)])
@@ -243,142 +211,6 @@ def test_renders_unchanged_by_raycasts(api, oracle):
 # with cylinders alone), or when its origin lies outside the scene box with quadrics in it.  Rays with |d|^2 in
 # [0.999, 1) stay in the fast tree, whose sphere boxes (ort_tree.cpp) must then hold every tangent-band "hit"
 # (|b^2 - a c| < 1e-5: a band that widens as 1e-5 / |d|^2), and rays from exactly the scene box's faces count as inside.
-LEN2 = [np.float32(0.998), np.nextafter(np.float32(0.999), np.float32(0)), np.float32(0.999),
-        np.nextafter(np.float32(0.999), np.float32(2)), np.float32(0.9995), np.float32(1 - 2.0 ** -24), np.float32(1),
-        np.float32(1.01)]
-
-
-def _threshold_scene(api, small):
-    """small = False: a room (six slabs), 30 spheres (r 0, 1e-3, 2e-3 and 0.05 among them) and four cylinders;
-    small = True: a handful of the same shapes within a box of diagonal < 1, so that the boxes' scene-size slack is
-    at its least"""
-    rng = np.random.default_rng(424242 + small)
-    mats = np.zeros(4, api.MATERIAL_DTYPE)
-    mats["diffuse"][1] = (0.7, 0.7, 0.7)
-    mats["specular"][2, :3] = 1
-    mats["transmission"][3] = 1; mats["ior"][1:] = (1.0, 1.0, 1.4)
-    tiny = [0.0, 1e-3, 2e-3, 0.05]
-    if small:
-        sph = np.zeros(8, api.SPHERE_DTYPE)
-        for i in range(8):
-            sph[i] = (rng.uniform(0.1, 0.4, 3), tiny[i % 4] if i < 6 else 0.03, 1 + i % 3)
-        cyl = np.zeros(2, api.CYLINDER_DTYPE)
-        cyl[0] = ((0.05, 0.05, 0.05), (0, 0, 0.3), 0.02, 1)
-        cyl[1] = ((0.45, 0.1, 0.2), (-0.1, 0.2, 0.05), 1e-3, 2)
-        box = np.zeros(1, api.BOX_DTYPE)
-        box[0] = ((0.2, 0.3, 0.0), (0.3, 0.35, 0.08), 1)
-        cam = (0.25, 0.0, 0.25)
-    else:
-        sph = np.zeros(30, api.SPHERE_DTYPE)
-        for i in range(30):
-            r = tiny[i % 4] if i < 16 else rng.uniform(0.1, 0.8)
-            sph[i] = (rng.uniform(-3, 3, 3) * (1, 1, 0) + (0, 0, rng.uniform(0.3, 4)), r, 1 + i % 3)
-        cyl = np.zeros(4, api.CYLINDER_DTYPE)
-        for i in range(4):
-            cyl[i] = (rng.uniform(-2.5, 2.5, 3) * (1, 1, 0) + (0, 0, 0.5), (0, 0, 1.5) if i == 0 else rng.normal(size=3),
-                      (0.2, 1e-3, 0.05, 0.3)[i], 1 + i % 3)
-        box = np.zeros(6, api.BOX_DTYPE)
-        room = [((-4, -4, -0.2), (4, 4, 0)), ((-4, -4, 5), (4, 4, 5.2)), ((-4.2, -4, -0.2), (-4, 4, 5.2)),
-                ((4, -4, -0.2), (4.2, 4, 5.2)), ((-4, -4.2, -0.2), (4, -4, 5.2)), ((-4, 4, -0.2), (4, 4.2, 5.2))]
-        for i, (lo, hi) in enumerate(room):
-            box[i] = (lo, hi, 1)
-        cam = (3.3, 2.0, 2.6)
-    return api.Scene.from_arrays(mats, sph, box, cyl, None, camera_p=cam, camera_height_ratio=0.3, screen=(64, 48))
-
-
-def _scene_box(flat, cam):
-    """the box ort_kernels.hip (the query tables, "the box of everything ort_tree.cpp sized the quadric boxes for")
-    computes, in f32: the camera, spheres and cylinder ends +- |r|, box corners"""
-    lo = np.array(cam, "<f4").copy()
-    hi = lo.copy()
-
-    def grow(p, r):
-        p = np.asarray(p, "<f4")
-        r = np.float32(abs(r))
-        np.minimum(lo, p - r, out=lo)
-        np.maximum(hi, p + r, out=hi)
-    for s in flat.spheres:
-        grow(s["center"], s["r"])
-    for b in flat.boxes:
-        grow(b["min"], 0)
-        grow(b["max"], 0)
-    for c in flat.cylinders:
-        grow(c["base"], c["r"])
-        grow(np.asarray(c["base"], "<f4") + np.asarray(c["axis"], "<f4"), c["r"])
-    return lo, hi
-
-
-def _dir_of_len2(u, target):
-    """a multiple of the unit vector u whose |d|^2, summed in f32 as the kernel does, is target (or the nearest)"""
-    s = np.float32(np.sqrt(np.float64(target)))
-    best = None
-    for k in range(-6, 7):
-        sk = s
-        for _ in range(abs(k)):
-            sk = np.nextafter(sk, np.float32(np.inf if k > 0 else 0))
-        d = (u * sk).astype("<f4")
-        l2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
-        err = abs(float(l2) - float(target))
-        if best is None or err < best[0]:
-            best = (err, d)
-        if err == 0:
-            break
-    return best[1]
-
-
-def _threshold_rays(flat, cam, rng, dists):
-    rays = []
-    axes = np.eye(3, dtype="<f4")
-    for s in flat.spheres:
-        c, r = np.asarray(s["center"], "<f4"), float(s["r"])
-        for l2 in LEN2:
-            for j in range(3):
-                u = [axes[j], -axes[j], (axes[j] + axes[(j + 1) % 3] * 0.37) / np.float32(np.linalg.norm([1, 0.37]))][j].astype("<f4")
-                w = np.cross(u, axes[(j + 2) % 3]).astype("<f4")
-                w /= np.float32(np.linalg.norm(w))
-                d = _dir_of_len2(u, l2)
-                # perpendicular offsets across both edges of the tangent band: D^2 = r^2 +- 1e-5 / |d|^2
-                offs = []
-                for sign in (1, -1):
-                    e2 = r * r + sign * 1e-5 / float(l2)
-                    if e2 > 0:
-                        D = np.sqrt(e2)
-                        offs += [D * (1 + k * 2e-7) for k in range(-6, 7)] + [D * (1 + k * 1e-5) for k in (-3, -1, 1, 3)]
-                offs += [r, 0.5 * r]
-                for D in offs:
-                    for L in dists:
-                        o = (c - np.float32(L) * u + np.float32(D) * w).astype("<f4")
-                        rays.append(np.concatenate([o, d]))
-    # origins exactly on the faces of the scene box, one ulp inside and outside, pointed at the shapes
-    lo, hi = _scene_box(flat, cam)
-    targets = np.concatenate([np.asarray(flat.spheres["center"], "<f4"), np.asarray(flat.cylinders["base"], "<f4")])
-    for k in range(3):
-        for face in (lo[k], hi[k]):
-            for step in (None, 0, np.inf):
-                for _ in range(24):
-                    o = (lo + (hi - lo) * rng.uniform(0, 1, 3).astype("<f4")).astype("<f4")
-                    o[k] = face if step is None else np.nextafter(face, np.float32(step) if step else np.float32(-np.inf))
-                    t = targets[rng.integers(0, len(targets))]
-                    u = (t - o).astype(np.float64)
-                    n = np.linalg.norm(u)
-                    u = (u / n if n > 0 else np.array([1.0, 0, 0])).astype("<f4")
-                    rays.append(np.concatenate([o, _dir_of_len2(u, LEN2[rng.integers(0, len(LEN2))])]))
-        # on an edge and a corner of the box
-        rays.append(np.concatenate([lo, _dir_of_len2(np.full(3, 1 / np.sqrt(3), "<f4"), 1)]))
-        rays.append(np.concatenate([hi, _dir_of_len2(np.full(3, -1 / np.sqrt(3), "<f4"), 0.999)]))
-    return np.array(rays, "<f4")
-
-
-def _needs_exact(rays, lo, hi, tree_spheres, tree_quadrics):
-    """raycast_needs_exact (ort_lane.h) restated in f32"""
-    d = rays[:, 3:6]
-    l2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
-    o = rays[:, 0:3]
-    inside = ((o >= lo) & (o <= hi)).all(axis=1)
-    short = ~(l2 >= np.float32(0.999 if tree_spheres else 1e-30))
-    return (tree_quadrics & short) | (tree_quadrics & ~inside)
-
-
 @pytest.mark.parametrize("small", [False, True], ids=["room", "small"])
 def test_exact_walk_thresholds(api, oracle, monkeypatch, small):
     """tangent rays across the sphere band at |d|^2 around 0.999 and 1, origins on the scene box's faces and one ulp

@@ -11,8 +11,18 @@
  * kernel.  The library never loads, links or runs it: the render call has no CPU fallback
  * (tests/test_host.py holds its image against the oracle; nothing else uses it).
  *
+ * The ray-query lanes (raycast_lane, occluded_lane, radiance_lane) and the batch-of-views flavour of pt_lane run here too, on
+ * the tables the product's own host code packs (ort_setup.h): tests/test_query_lanes_host.py holds them against the
+ * reference's answers and the oracle, tests/test_host_sanitizers.py runs the same binary built with ASan + UBSan
+ * (make host_sim_san).
+ *
  * build: see tools/Makefile     run: [SIM_THREADS=n] host_sim <scn> <base> W H spp seed policy chunk out.f32
- *                                  or: host_sim --unit records.bin out.f32   (ort_unit_eval_device on the host)
+ *   or: host_sim --unit records.bin out.f32   (ort_unit_eval_device on the host)
+ *   or: host_sim --raycast scn base rays.f32 hits.bin                        (ort_hit records)
+ *   or: host_sim --occluded scn base rays.f32 tmax.f32|- out.u8
+ *   or: host_sim --radiance scn base rays.f32 seeds.u32 spp rr out.f32 states.u32
+ *   or: host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32   (cams: p, x, y, z axes, 12 floats a view)
+ * All files raw little-endian.  SIM_TABS=1: the TABS = true lane code, on a heap copy of the LDS tables' image.
  */
 #define ORT_HOST_SIM 1
 #include <stdint.h>
@@ -65,56 +75,338 @@ static int unit_mode(const char *in_path, const char *out_path) {
     return 0;
 }
 
+static bool read_bytes(const char *path, std::vector<unsigned char> &out) {
+    FILE *f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "cannot read %s\n", path); return false; }
+    unsigned char buf[1 << 16];
+    size_t got;
+    out.clear();
+    while ((got = fread(buf, 1, sizeof(buf), f)) > 0) out.insert(out.end(), buf, buf + got);
+    fclose(f);
+    return true;
+}
+static bool write_bytes(const char *path, const void *p, size_t bytes) {
+    FILE *f = fopen(path, "wb");
+    const bool ok = f && (bytes == 0 || fwrite(p, 1, bytes, f) == bytes);
+    if (f) fclose(f);
+    if (!ok) fprintf(stderr, "cannot write %s\n", path);
+    return ok;
+}
+
+/* a committed scene as the lanes see it: what device_upload builds, in host memory, through the same functions (ort_setup.h) */
+struct Sim {
+    ort_scene *scene = nullptr;
+    SceneView sv{};
+    SceneCold cold{};
+    std::vector<DevMaterial> mats;
+    std::vector<uint32_t> lis;
+    std::vector<PrimInfo> prim_info;
+    uint32_t tab_flags = 0;
+    float4 *tab = nullptr; /* SIM_TABS: exactly kTabF4 float4 on the heap, so that a read past a slot's end is a read past the block */
+    unsigned long long ctrl[128] = {0}; /* as DeviceScene::ctrl_buf: [0] next_job, [1..5] counters, [6..7] fallback, diagnostics up to [6 + kDiagFallback + 2] */
+    int n_threads = 1;
+    ~Sim() { delete[] tab; if (scene) ort_scene_destroy(scene); }
+};
+
+/* need: the tables the mode's TABS kernel keeps in LDS (all three for the path tracers, TAB_PRO for the ray queries) */
+static int sim_open(Sim &S, const char *scn, const char *base, uint32_t need) {
+    if (ort_scene_load_scn(scn, base, &S.scene) != ORT_OK || ort_scene_commit(S.scene) != ORT_OK) {
+        fprintf(stderr, "scene: %s\n", ort_last_error());
+        return 1;
+    }
+    const Tree &t = S.scene->tree;
+    const RefTree &rt = S.scene->ref;
+    ort_tree_info ti;
+    ort_scene_get_tree_info(S.scene, &ti);
+    fprintf(stderr, "tree: %u nodes, %u leaves, max leaf %u, depth %u, sah %.2f\n", ti.node_count, ti.leaf_count, ti.max_leaf_prims, ti.max_depth, ti.sah_cost);
+    S.mats = dev_materials(*S.scene);
+    S.lis = light_sphere_flags(*S.scene);
+    SceneView &sv = S.sv;
+    sv.nodes = (const float4 *)t.nodes.data(); sv.tris = (const float4 *)t.tris.data();
+    sv.spheres = (const float4 *)t.spheres.data(); sv.boxes = (const float4 *)t.boxes.data(); sv.cyls = (const float4 *)t.cyls.data();
+    build_prim_info(t, rt, S.prim_info, sv.info_box, sv.info_cyl, sv.info_sphere);
+    sv.prim_info = S.prim_info.data();
+    sv.materials = (const float4 *)S.mats.data();
+    sv.light_is_sphere = S.lis.data(); sv.light_count = (uint32_t)S.lis.size();
+    sv.pro_boxes = t.pro_boxes; sv.pro_spheres = t.pro_spheres; sv.pro_cyls = t.pro_cyls;
+    {
+        std::vector<F4> img;
+        S.tab_flags = pack_lds_tables(t, S.mats, S.lis, img);
+        sv.tab_flags = S.tab_flags;
+        if (getenv("SIM_TABS") && atoi(getenv("SIM_TABS"))) {
+            if ((S.tab_flags & need) != need) {
+                fprintf(stderr, "SIM_TABS: the scene's tables do not fit their LDS slots (fit flags %u, needed %u)\n", S.tab_flags, need);
+                return 1;
+            }
+            S.tab = new float4[kTabF4];
+            memcpy(S.tab, img.data(), (size_t)kTabF4 * sizeof(float4));
+            sv.tab_src = S.tab;
+        }
+    }
+    sv.cold = &S.cold;
+    S.cold.ref_nodes = (const float4 *)rt.nodes.data(); S.cold.ref_recs = rt.recs.data(); sv.chain_boxes = (const float4 *)rt.chain_boxes.data();
+    S.cold.tri_order = rt.tri_order.data(); S.cold.sphere_order = rt.sphere_order.data(); S.cold.box_order = rt.box_order.data(); S.cold.cyl_order = rt.cyl_order.data();
+    S.cold.fallback_counters = S.ctrl + 6;
+    fprintf(stderr, "ref octree: %zu nodes, %u leaves, max leaf %u, chain boxes %zu\n", rt.nodes.size(), rt.nonempty_leaves, rt.max_leaf_records, rt.chain_boxes.size() / 2);
+    sv.force_fallback_mask = getenv("SIM_FORCE_FALLBACK") ? (uint32_t)strtoul(getenv("SIM_FORCE_FALLBACK"), 0, 0) : 0xffffffffu;
+    S.n_threads = getenv("SIM_THREADS") ? std::max(1, atoi(getenv("SIM_THREADS"))) : 1;
+    return 0;
+}
+
+/* a pool of workers on one job counter: every worker owns what a GPU lane owns (traversal stack, focal-point cache, its
+   queue of the exact fallback), shares what the lanes share (scene, tables, job counter, work counters, outputs) */
+template <typename Fn>
+static void run_lanes(const Sim &S, Fn lane) {
+    auto worker = [&](int w) {
+        SceneView svw = S.sv;
+        SceneCold coldw = S.cold;
+        std::vector<uint32_t> q(S.scene->ref.nodes.size() + 8), lock(1, 0u), stack(kLdsStack * kBlock);
+        std::vector<float> focal(3 * kBlock);
+        coldw.bfs_pool = q.data(); coldw.bfs_locks = lock.data(); coldw.bfs_queue_cap = (uint32_t)q.size(); coldw.bfs_queue_count = 1;
+        svw.cold = &coldw;
+        lane(svw, stack.data(), focal.data(), (uint32_t)w);
+    };
+    if (S.n_threads <= 1) { worker(0); return; }
+    std::vector<std::thread> pool;
+    for (int w = 0; w < S.n_threads; ++w) pool.emplace_back(worker, w);
+    for (auto &th : pool) th.join();
+}
+
+static void print_counters(const Sim &S, double sec, const char *tail = "") {
+    const unsigned long long *c = S.ctrl;
+    fprintf(stderr, "sim: %.2fs paths %llu rays %llu node_tests %llu tri_tests %llu analytic %llu fallback %llu overflow %llu%s\n", sec, c[1], c[2], c[3], c[4], c[5], c[6], c[7], tail);
+}
+
+/* the rays of a query: count x 6 floats, as 8-byte words (the lanes read them as three float2) */
+static bool read_rays(const char *path, std::vector<float2> &rays, size_t *count) {
+    std::vector<unsigned char> b;
+    if (!read_bytes(path, b)) return false;
+    if (b.size() % 24u) { fprintf(stderr, "%s: not a whole number of 24-byte rays\n", path); return false; }
+    *count = b.size() / 24u;
+    rays.resize(3 * *count); /* exactly: a read of ray `count` is a read past the block */
+    if (!b.empty()) memcpy(rays.data(), b.data(), b.size());
+    return true;
+}
+template <typename T>
+static bool read_array(const char *path, std::vector<T> &v, size_t want, const char *what) {
+    std::vector<unsigned char> b;
+    if (!read_bytes(path, b)) return false;
+    if (b.size() != want * sizeof(T)) { fprintf(stderr, "%s: %zu bytes, expected %zu %s\n", path, b.size(), want, what); return false; }
+    v.resize(want);
+    if (!b.empty()) memcpy(v.data(), b.data(), b.size());
+    return true;
+}
+
+/* what ray_query_plan (ort_kernels.hip) puts behind hot.c, for one simulated lane per thread: no batches */
+static RenderHot query_hot(Sim &S, RenderView &rv, size_t count) {
+    rv.job_count = count;
+    rv.next_job = S.ctrl;
+    rv.counters = S.ctrl + 1;
+    rv.refill_below = 32;
+    rv.descend_below = getenv("SIM_DESCEND_BELOW") ? atoi(getenv("SIM_DESCEND_BELOW")) : 8;
+    RenderHot hot{};
+    hot.mode = rv.mode; hot.rr = rv.rr;
+    hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
+    hot.c = &rv;
+    return hot;
+}
+
+static int raycast_mode(char **a) { /* scn base rays.f32 hits.bin */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO)) return rc;
+    size_t n = 0;
+    std::vector<float2> rays;
+    if (!read_rays(a[2], rays, &n)) return 1;
+    std::vector<uint2> hits(3 * n);
+    std::vector<uint32_t> src;
+    if (!invert_prim_slots(S.scene->tree, S.sv.info_box, S.sv.info_cyl, S.sv.info_sphere, src)) { fprintf(stderr, "the tree's slot maps are not a bijection onto its shape arrays\n"); return 1; }
+    float lo[3], hi[3];
+    scene_origin_box(*S.scene, lo, hi);
+    RaycastIO io{};
+    ray_query_io(*S.scene, lo, hi, &io);
+    io.rays = rays.data(); io.hits = hits.data(); io.prim_src = src.data();
+    RenderView rv{};
+    const RenderHot hot = query_hot(S, rv, n);
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
+        if (S.tab) raycast_lane<true, true>(sv, hot, io, S.tab, stack, 0, w, nullptr);
+        else raycast_lane<true, false>(sv, hot, io, nullptr, stack, 0, w, nullptr);
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    static_assert(sizeof(ort_hit) == 3 * sizeof(uint2), "ort_hit is three 8-byte words");
+    return write_bytes(a[3], hits.data(), n * sizeof(ort_hit)) ? 0 : 1;
+}
+
+static int occluded_mode(char **a) { /* scn base rays.f32 tmax.f32|- out.u8 */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO)) return rc;
+    size_t n = 0;
+    std::vector<float2> rays;
+    if (!read_rays(a[2], rays, &n)) return 1;
+    std::vector<float> tmax;
+    const bool limits = std::string(a[3]) != "-";
+    if (limits && !read_array(a[3], tmax, n, "limits")) return 1;
+    std::vector<uint8_t> out(n, (uint8_t)0xee); /* every byte is written: one that is not stays neither 0 nor 1 */
+    float lo[3], hi[3];
+    scene_origin_box(*S.scene, lo, hi);
+    OccludedIO io{};
+    ray_query_io(*S.scene, lo, hi, &io.q);
+    io.q.rays = rays.data();
+    io.tmax = limits ? tmax.data() : nullptr;
+    io.out = out.data();
+    io.mats_nonzero = all_mats_nonzero(S.scene->tree);
+    RenderView rv{};
+    const RenderHot hot = query_hot(S, rv, n);
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
+        if (S.tab) occluded_lane<true, true>(sv, hot, io, S.tab, stack, 0, w, nullptr);
+        else occluded_lane<true, false>(sv, hot, io, nullptr, stack, 0, w, nullptr);
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return write_bytes(a[4], out.data(), n) ? 0 : 1;
+}
+
+static int radiance_mode(char **a) { /* scn base rays.f32 seeds.u32 spp rr out.f32 states.u32 */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
+    size_t n = 0;
+    std::vector<float2> rays;
+    std::vector<uint32_t> seeds;
+    if (!read_rays(a[2], rays, &n) || !read_array(a[3], seeds, n, "seeds")) return 1;
+    std::vector<float> out(3 * n, 0.0f);
+    std::vector<uint32_t> states(n, 0u);
+    float lo[3], hi[3];
+    scene_origin_box(*S.scene, lo, hi);
+    RaycastIO q{};
+    ray_query_io(*S.scene, lo, hi, &q);
+    RenderView rv{}; /* as launch_radiance (ort_kernels.hip) */
+    rv.mode = JOBS_PIXEL;
+    rv.spp = (uint32_t)strtoul(a[4], 0, 10); rv.rr = (float)atof(a[5]);
+    rv.out = out.data(); rv.final_states = states.data();
+    rv.rays = rays.data(); rv.seeds = seeds.data();
+    rv.ray_tree_spheres = q.tree_spheres; rv.ray_tree_quadrics = q.tree_quadrics; rv.ray_tree_boxes = q.tree_boxes;
+    memcpy(rv.ray_lo, q.lo, sizeof(rv.ray_lo));
+    memcpy(rv.ray_hi, q.hi, sizeof(rv.ray_hi));
+    const RenderHot hot = query_hot(S, rv, n);
+    const bool diffuse_only = getenv("SIM_DIFFUSE") != nullptr; /* caller vouches for Ks = Kt = 0 */
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
+        if (diffuse_only) {
+            if (S.tab) radiance_lane<true, true, true>(sv, hot, S.tab, stack, 0, w, nullptr);
+            else radiance_lane<true, true, false>(sv, hot, nullptr, stack, 0, w, nullptr);
+        } else {
+            if (S.tab) radiance_lane<true, false, true>(sv, hot, S.tab, stack, 0, w, nullptr);
+            else radiance_lane<true, false, false>(sv, hot, nullptr, stack, 0, w, nullptr);
+        }
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return write_bytes(a[6], out.data(), 12 * n) && write_bytes(a[7], states.data(), 4 * n) ? 0 : 1;
+}
+
+static int views_mode(char **a) { /* scn base cams.f32 seeds.u32 W H spp policy chunk out.f32 */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
+    std::vector<unsigned char> cb;
+    if (!read_bytes(a[2], cb)) return 1;
+    if (cb.empty() || cb.size() % 48u) { fprintf(stderr, "%s: not a whole, positive number of 48-byte cameras\n", a[2]); return 1; }
+    const uint32_t nv = (uint32_t)(cb.size() / 48u);
+    std::vector<uint32_t> seeds;
+    if (!read_array(a[3], seeds, nv, "seeds")) return 1;
+    std::vector<ort_view> views(nv);
+    for (uint32_t v = 0; v < nv; ++v) { memcpy(&views[v].camera, &cb[48u * v], 48); views[v].seed = seeds[v]; }
+    static_assert(sizeof(ort_camera) == 48, "a camera is twelve floats");
+    const int W = atoi(a[4]), H = atoi(a[5]);
+    const uint32_t spp = (uint32_t)strtoul(a[6], 0, 10), chunk = (uint32_t)strtoul(a[8], 0, 10);
+    const std::string policy = a[7];
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) { fprintf(stderr, "bad frame size\n"); return 1; }
+    std::vector<float> tab_host; /* the camera table, 16-byte aligned for the lanes' float4 reads */
+    pack_view_table(views.data(), nv, tab_host);
+    std::vector<float4> view_tab(4u * nv);
+    memcpy(view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
+    ort_camera cam; /* sv.cam stays the scene's: the VIEWS lanes do not read it */
+    camera_basis(*S.scene, W, H, &cam);
+    memcpy(S.sv.cam, &cam, sizeof(cam));
+    RenderView rv{};
+    rv.W = W; rv.H = H; rv.x0 = 0; rv.y0 = 0; rv.x1 = W; rv.y1 = H;
+    rv.spp = spp; rv.chunk = chunk; rv.rr = getenv("SIM_RR") ? (float)atof(getenv("SIM_RR")) : 0.8f;
+    rv.shard_count = 1; rv.shard_index = 0;
+    rv.blocks_w = (uint32_t)((W + 7) / 8);
+    rv.my_blocks = rv.blocks_w * (uint32_t)((H + 7) / 8);
+    std::vector<float> out((size_t)nv * W * H * 3, 0.0f), partial;
+    if (policy == "pixel") { rv.mode = JOBS_PIXEL; rv.nchunks = 1; }
+    else if (policy == "chunk") {
+        if (!chunk || spp % chunk) { fprintf(stderr, "chunk must divide spp\n"); return 1; }
+        rv.mode = JOBS_CHUNK; rv.nchunks = spp / chunk;
+        partial.assign((size_t)nv * rv.nchunks * rv.my_blocks * 64 * 3, 0.0f); rv.partial = partial.data();
+    } else { fprintf(stderr, "a batch of views renders under the pixel or the chunk policy\n"); return 1; }
+    rv.view_jobs = (unsigned long long)rv.my_blocks * 64 * rv.nchunks;
+    rv.view_count = nv;
+    rv.views = view_tab.data();
+    rv.job_count = rv.view_jobs * nv;
+    rv.out = out.data(); rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
+    rv.refill_below = 12;
+    rv.descend_below = getenv("SIM_DESCEND_BELOW") ? atoi(getenv("SIM_DESCEND_BELOW")) : 8;
+    RenderHot hot{};
+    hot.mode = rv.mode; hot.W = rv.W; hot.H = rv.H; hot.rr = rv.rr; hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
+    hot.c = &rv;
+    const bool diffuse_only = getenv("SIM_DIFFUSE") != nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
+        if (diffuse_only) {
+            if (S.tab) pt_lane<true, true, true, false, false, true>(sv, hot, S.tab, stack, focal, 0, w);
+            else pt_lane<true, true, false, false, false, true>(sv, hot, nullptr, stack, focal, 0, w);
+        } else {
+            if (S.tab) pt_lane<true, false, true, false, false, true>(sv, hot, S.tab, stack, focal, 0, w);
+            else pt_lane<true, false, false, false, false, true>(sv, hot, nullptr, stack, focal, 0, w);
+        }
+    });
+    if (rv.mode == JOBS_CHUNK)
+        for (uint32_t v = 0; v < nv; ++v)
+            for (unsigned long long i = 0; i < (unsigned long long)rv.my_blocks * 64; ++i) combine_pixel(hot, i, v);
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return write_bytes(a[9], out.data(), out.size() * sizeof(float)) ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
-    if (argc == 4 && std::string(argv[1]) == "--unit") return unit_mode(argv[2], argv[3]);
-    if (argc < 10) { fprintf(stderr, "usage: host_sim scn base W H spp seed policy chunk out.f32 [shard_index shard_count]\n"); return 2; }
+    const std::string mode = argc > 1 ? argv[1] : "";
+    if (argc == 4 && mode == "--unit") return unit_mode(argv[2], argv[3]);
+    if (argc == 6 && mode == "--raycast") return raycast_mode(argv + 2);
+    if (argc == 7 && mode == "--occluded") return occluded_mode(argv + 2);
+    if (argc == 10 && mode == "--radiance") return radiance_mode(argv + 2);
+    if (argc == 12 && mode == "--views") return views_mode(argv + 2);
+    if (argc < 10 || mode.rfind("--", 0) == 0) {
+        fprintf(stderr, "usage: host_sim scn base W H spp seed policy chunk out.f32 [shard_index shard_count]\n"
+                        "       host_sim --unit records.bin out.f32\n"
+                        "       host_sim --raycast scn base rays.f32 hits.bin\n"
+                        "       host_sim --occluded scn base rays.f32 tmax.f32|- out.u8\n"
+                        "       host_sim --radiance scn base rays.f32 seeds.u32 spp rr out.f32 states.u32\n"
+                        "       host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32\n");
+        return 2;
+    }
     int W = atoi(argv[3]), H = atoi(argv[4]);
     uint32_t spp = (uint32_t)strtoul(argv[5], 0, 10), seed = (uint32_t)strtoul(argv[6], 0, 10);
     std::string policy = argv[7];
     uint32_t chunk = (uint32_t)strtoul(argv[8], 0, 10);
-    ort_scene *scene = nullptr;
-    if (ort_scene_load_scn(argv[1], argv[2], &scene) != ORT_OK || ort_scene_commit(scene) != ORT_OK) {
-        fprintf(stderr, "scene: %s\n", ort_last_error());
-        return 1;
-    }
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) { fprintf(stderr, "bad frame size\n"); return 1; }
+    Sim S;
+    if (int rc = sim_open(S, argv[1], argv[2], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
+    ort_scene *scene = S.scene;
     const Tree &t = scene->tree;
-    ort_tree_info ti;
-    ort_scene_get_tree_info(scene, &ti);
-    fprintf(stderr, "tree: %u nodes, %u leaves, max leaf %u, depth %u, sah %.2f\n", ti.node_count, ti.leaf_count, ti.max_leaf_prims, ti.max_depth, ti.sah_cost);
-
-    std::vector<DevMaterial> mats(scene->materials.size());
-    for (size_t i = 0; i < mats.size(); ++i) mats[i] = make_dev_material(scene->materials[i]);
-    std::vector<uint32_t> lis(scene->lights.size());
-    for (size_t i = 0; i < lis.size(); ++i) lis[i] = scene->lights[i].type == 1u;
-
-    SceneView sv{};
-    sv.nodes = (const float4 *)t.nodes.data(); sv.tris = (const float4 *)t.tris.data();
-    sv.spheres = (const float4 *)t.spheres.data(); sv.boxes = (const float4 *)t.boxes.data(); sv.cyls = (const float4 *)t.cyls.data();
-    static std::vector<PrimInfo> prim_info;
-    build_prim_info(t, scene->ref, prim_info, sv.info_box, sv.info_cyl, sv.info_sphere);
-    sv.prim_info = prim_info.data();
-    sv.materials = (const float4 *)mats.data();
-    sv.light_is_sphere = lis.data(); sv.light_count = (uint32_t)lis.size();
-    sv.pro_boxes = t.pro_boxes; sv.pro_spheres = t.pro_spheres; sv.pro_cyls = t.pro_cyls;
-    const RefTree &rt = scene->ref;
-    static SceneCold cold; sv.cold = &cold;
-    cold.ref_nodes = (const float4 *)rt.nodes.data(); cold.ref_recs = rt.recs.data(); sv.chain_boxes = (const float4 *)rt.chain_boxes.data();
-    cold.tri_order = rt.tri_order.data(); cold.sphere_order = rt.sphere_order.data(); cold.box_order = rt.box_order.data(); cold.cyl_order = rt.cyl_order.data();
-    fprintf(stderr, "ref octree: %zu nodes, %u leaves, max leaf %u, chain boxes %zu\n", rt.nodes.size(), rt.nonempty_leaves, rt.max_leaf_records, rt.chain_boxes.size() / 2);
+    SceneView &sv = S.sv;
+    unsigned long long *ctrl = S.ctrl;
     ort_camera cam;
     camera_basis(*scene, W, H, &cam);
     memcpy(sv.cam, &cam, sizeof(cam));
 
     std::vector<float> out((size_t)W * H * 3, 0.0f), partial;
-    unsigned long long ctrl[8] = {0};
     RenderView rv{};
     rv.W = W; rv.H = H; rv.x0 = 0; rv.y0 = 0; rv.x1 = W; rv.y1 = H;
     rv.seed = seed; rv.spp = spp; rv.chunk = chunk; rv.rr = getenv("SIM_RR") ? (float)atof(getenv("SIM_RR")) : 0.8f;
     rv.refill_below = 12;
     rv.descend_below = getenv("SIM_DESCEND_BELOW") ? atoi(getenv("SIM_DESCEND_BELOW")) : 8;
     rv.out = out.data(); rv.next_job = ctrl; rv.counters = ctrl + 1;
-    cold.fallback_counters = ctrl + 6;
     rv.shard_count = argc > 11 ? (uint32_t)atoi(argv[11]) : 1; rv.shard_index = argc > 11 ? (uint32_t)atoi(argv[10]) : 0;
+    if (!rv.shard_count || rv.shard_index >= rv.shard_count) { fprintf(stderr, "bad shard\n"); return 1; }
     rv.block_x0 = rv.block_y0 = 0;
     rv.blocks_w = (uint32_t)((W + 7) / 8);
     uint32_t blocks_total = rv.blocks_w * (uint32_t)((H + 7) / 8);
@@ -123,6 +415,7 @@ int main(int argc, char **argv) {
     std::vector<uint32_t> finals;
     if (policy == "pixel") { rv.mode = JOBS_PIXEL; rv.nchunks = 1; rv.job_count = (unsigned long long)rv.my_blocks * 64; }
     else if (policy == "chunk") {
+        if (!chunk || spp % chunk) { fprintf(stderr, "chunk must divide spp\n"); return 1; }
         rv.mode = JOBS_CHUNK; rv.nchunks = spp / chunk; rv.job_count = (unsigned long long)rv.my_blocks * 64 * rv.nchunks;
         partial.assign((size_t)rv.nchunks * rv.my_blocks * 64 * 3, 0.0f); rv.partial = partial.data(); /* packed block layout: edge blocks are whole */
     } else {
@@ -145,80 +438,62 @@ int main(int argc, char **argv) {
     hot.c = &rv;
     if (getenv("SIM_RAY_LOG")) { g_ray_log = fopen(getenv("SIM_RAY_LOG"), "wb"); g_dbg_x = atoi(getenv("SIM_X")); g_dbg_y = atoi(getenv("SIM_Y")); }
     if (getenv("SIM_DUMP_RNG")) { g_pixel_rng = pix_rng.data(); g_W = W; }
-    std::vector<uint32_t> lds(kLdsStack * kBlock);
     auto t0 = std::chrono::steady_clock::now();
-    std::vector<float> lds_focal(3 * kBlock);
-    std::vector<uint32_t> bfsq(scene->ref.nodes.size() + 8), bfs_lock(1, 0u);
-    cold.bfs_pool = bfsq.data();
-    cold.bfs_locks = bfs_lock.data();
-    cold.bfs_queue_cap = (uint32_t)bfsq.size();
-    cold.bfs_queue_count = 1;
-    sv.force_fallback_mask = getenv("SIM_FORCE_FALLBACK") ? (uint32_t)strtoul(getenv("SIM_FORCE_FALLBACK"), 0, 0) : 0xffffffffu;
-    const int n_threads = getenv("SIM_THREADS") ? std::max(1, atoi(getenv("SIM_THREADS"))) : 1;
+    const bool wide = getenv("SIM_WIDE") != nullptr, diffuse_only = getenv("SIM_DIFFUSE") != nullptr;
     if (getenv("SIM_WAVEFRONT")) {
         /* the wavefront schedule with a small slot pool: shade all slots, trace all slots, repeat */
-        uint32_t S = (uint32_t)atoi(getenv("SIM_WAVEFRONT"));
-        if (S > rv.job_count) S = (uint32_t)rv.job_count;
-        std::vector<float4> od0(S), hit0(S), p0(S), p1(S), p2(S);
-        std::vector<float2> od1(S);
-        std::vector<uint4> p3(S);
-        std::vector<uint32_t> hitp(S), flags(S, (uint32_t)PS_NEED_JOB);
+        if (S.tab) { fprintf(stderr, "SIM_TABS: the wavefront kernels read the tables from their arrays\n"); return 1; }
+        std::vector<uint32_t> bfsq(scene->ref.nodes.size() + 8), bfs_lock(1, 0u);
+        S.cold.bfs_pool = bfsq.data(); S.cold.bfs_locks = bfs_lock.data(); S.cold.bfs_queue_cap = (uint32_t)bfsq.size(); S.cold.bfs_queue_count = 1;
+        uint32_t slots = (uint32_t)atoi(getenv("SIM_WAVEFRONT"));
+        if (slots > rv.job_count) slots = (uint32_t)rv.job_count;
+        std::vector<float4> od0(slots), hit0(slots), p0(slots), p1(slots), p2(slots);
+        std::vector<float2> od1(slots);
+        std::vector<uint4> p3(slots);
+        std::vector<uint32_t> hitp(slots), flags(slots, (uint32_t)PS_NEED_JOB);
         unsigned long long active = 0;
-        WfView wf{S, od0.data(), od1.data(), hit0.data(), hitp.data(), p0.data(), p1.data(), p2.data(), p3.data(), flags.data(), &active};
+        WfView wf{slots, od0.data(), od1.data(), hit0.data(), hitp.data(), p0.data(), p1.data(), p2.data(), p3.data(), flags.data(), &active};
         std::vector<uint32_t> wlds(kWfLdsStack * kBlock), wspill(kWfSpill);
         Counters c;
         for (;;) {
             unsigned long long produced = 0;
-            for (uint32_t i = 0; i < S; ++i) produced += wf_shade_slot<true>(sv, hot, nullptr, wf, i, c) ? 1 : 0;
+            for (uint32_t i = 0; i < slots; ++i) produced += wf_shade_slot<true>(sv, hot, nullptr, wf, i, c) ? 1 : 0;
             if (!produced) break;
-            for (uint32_t i = 0; i < S; ++i) wf_trace_slot<true>(sv, nullptr, wf, i, 0, wlds.data(), wspill.data(), 0, c);
+            for (uint32_t i = 0; i < slots; ++i) wf_trace_slot<true>(sv, nullptr, wf, i, 0, wlds.data(), wspill.data(), 0, c);
         }
         flush_counters(hot, c, true);
-    } else
-    if (n_threads > 1) {
-        /* a pool of workers on one job counter: every worker owns what a GPU lane owns (traversal stack, focal-point cache, its
-           queue of the exact fallback), shares what the lanes share (scene, job counter, work counters, framebuffer) */
-        const bool wide = getenv("SIM_WIDE") != nullptr, diffuse_only = getenv("SIM_DIFFUSE") != nullptr;
-        if (wide && t.nodes4.empty()) { fprintf(stderr, "no wide tree\n"); return 1; }
-        std::vector<std::thread> pool;
-        for (int w = 0; w < n_threads; ++w)
-            pool.emplace_back([&, w]() {
-                SceneView svw = sv;
-                SceneCold coldw = cold;
-                std::vector<uint32_t> q(scene->ref.nodes.size() + 8), lock(1, 0u), stack(kLdsStack * kBlock);
-                std::vector<float> focal(3 * kBlock);
-                coldw.bfs_pool = q.data(); coldw.bfs_locks = lock.data(); coldw.bfs_queue_cap = (uint32_t)q.size(); coldw.bfs_queue_count = 1;
-                svw.cold = &coldw;
-                if (wide) { svw.nodes = (const float4 *)t.nodes4.data(); pt_lane<true, false, false, false, true>(svw, hot, nullptr, stack.data(), focal.data(), 0, (uint32_t)w); }
-                else if (diffuse_only) pt_lane<true, true>(svw, hot, nullptr, stack.data(), focal.data(), 0, (uint32_t)w);
-                else pt_lane<true>(svw, hot, nullptr, stack.data(), focal.data(), 0, (uint32_t)w);
-            });
-        for (auto &th : pool) th.join();
-    } else
-    if (getenv("SIM_WIDE")) { /* the 4-wide form of the tree (DevNode4, visit_node4) */
-        if (t.nodes4.empty()) { fprintf(stderr, "no wide tree\n"); return 1; }
-        fprintf(stderr, "wide tree: %zu nodes, depth %u\n", t.nodes4.size(), t.max_depth4);
-        sv.nodes = (const float4 *)t.nodes4.data();
-        pt_lane<true, false, false, false, true>(sv, hot, nullptr, lds.data(), lds_focal.data(), 0, 0);
-    } else
-    if (getenv("SIM_DIFFUSE")) pt_lane<true, true>(sv, hot, nullptr, lds.data(), lds_focal.data(), 0, 0); /* caller vouches for Ks = Kt = 0 */
-    else pt_lane<true>(sv, hot, nullptr, lds.data(), lds_focal.data(), 0, 0); /* TABS = false: the small tables are read from their arrays */
+    } else {
+        if (wide) { /* the 4-wide form of the tree (DevNode4, visit_node4) */
+            if (t.nodes4.empty()) { fprintf(stderr, "no wide tree\n"); return 1; }
+            fprintf(stderr, "wide tree: %zu nodes, depth %u\n", t.nodes4.size(), t.max_depth4);
+            sv.nodes = (const float4 *)t.nodes4.data();
+        }
+        /* TABS = false: the small tables are read from their arrays; SIM_TABS: from the packed image */
+        run_lanes(S, [&](const SceneView &svw, uint32_t *stack, float *focal, uint32_t w) {
+            if (wide) {
+                if (S.tab) pt_lane<true, false, true, false, true>(svw, hot, S.tab, stack, focal, 0, w);
+                else pt_lane<true, false, false, false, true>(svw, hot, nullptr, stack, focal, 0, w);
+            } else if (diffuse_only) { /* caller vouches for Ks = Kt = 0 */
+                if (S.tab) pt_lane<true, true, true>(svw, hot, S.tab, stack, focal, 0, w);
+                else pt_lane<true, true>(svw, hot, nullptr, stack, focal, 0, w);
+            } else {
+                if (S.tab) pt_lane<true, false, true>(svw, hot, S.tab, stack, focal, 0, w);
+                else pt_lane<true>(svw, hot, nullptr, stack, focal, 0, w);
+            }
+        });
+    }
     if (rv.mode == JOBS_CHUNK)
         for (unsigned long long i = 0; i < (unsigned long long)rv.my_blocks * 64; ++i) combine_pixel(hot, i);
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    
+
 #ifdef ORT_CHAIN_STATS
     cs_dump();
 #endif
-    fprintf(stderr, "sim: %.2fs paths %llu rays %llu node_tests %llu tri_tests %llu analytic %llu fallback %llu overflow %llu%s\n", sec, ctrl[1], ctrl[2], ctrl[3], ctrl[4], ctrl[5], ctrl[6], ctrl[7],
-            finals.empty() ? "" : (" final_rng " + std::to_string(finals.back())).c_str());
+    print_counters(S, sec, finals.empty() ? "" : (" final_rng " + std::to_string(finals.back())).c_str());
 #ifdef ORT_CHAIN_CROSSCHECK
     fprintf(stderr, "chain shortcut == full walk on %llu rays; unnested chains %u\n", g_chain_crosschecks, scene->ref.unnested_chains);
 #endif
     if (g_ray_log) fclose(g_ray_log);
-    if (g_pixel_rng) { FILE *g = fopen(getenv("SIM_DUMP_RNG"), "wb"); fwrite(pix_rng.data(), 4, pix_rng.size(), g); fclose(g); }
-    FILE *f = fopen(argv[9], "wb");
-    fwrite(out.data(), 4, out.size(), f);
-    fclose(f);
-    return 0;
+    if (g_pixel_rng && !write_bytes(getenv("SIM_DUMP_RNG"), pix_rng.data(), pix_rng.size() * 4)) return 1;
+    return write_bytes(argv[9], out.data(), out.size() * sizeof(float)) ? 0 : 1;
 }
