@@ -61,11 +61,21 @@ int check_param_values(const ort_scene *scene, const ort_render_params *p) {
     return ORT_OK;
 }
 
-int check_params(const ort_scene *scene, const ort_render_params *p) {
-    int rc = check_param_values(scene, p);
-    if (rc != ORT_OK) return rc;
+/* the scene's state, which every call that launches looks at last: committed, and resident on a device */
+int check_resident(const ort_scene *scene) {
     if (!scene->tree.built) return fail(ORT_ERR_STATE, "ort_scene_commit has not been called");
     if (!scene->dev) return fail(ORT_ERR_NO_DEVICE, "scene is not resident on a HIP device: call ort_scene_upload (no CPU fallback)");
+    return ORT_OK;
+}
+
+int check_params(const ort_scene *scene, const ort_render_params *p) {
+    int rc = check_param_values(scene, p);
+    return rc != ORT_OK ? rc : check_resident(scene);
+}
+
+/* a call over nothing: OK, and no work was done */
+int nothing_to_do(ort_stats *stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
     return ORT_OK;
 }
 
@@ -370,112 +380,56 @@ static int ort_unit_eval_device_impl(int device, const void *records, uint32_t c
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
-/* ray queries: argument and state errors first, so that they are the same on a machine without a device */
-static int check_raycast(const ort_scene *s, const void *rays, uint64_t count, const void *hits) {
+/* The ray queries.  Each call has a host form (h_*: the caller's memory, staged in slices) and a device form (d_*: device
+   pointers, enqueued on the caller's stream); a form passes its own pointers and nulls for the other's.  The order of the
+   checks is each call's contract (include/ort.h). */
+/* closest hits: argument and state errors first, so that they are the same on a machine without a device; then count == 0 */
+static int raycast_common(ort_scene *s, const float *h_rays, const void *d_rays, uint64_t count, ort_hit *h_hits, void *d_hits, uint32_t flags, void *stream,
+                          ort_stats *stats) {
+    const void *rays = h_rays ? (const void *)h_rays : d_rays, *hits = h_hits ? (const void *)h_hits : d_hits;
     if (!s) return fail(ORT_ERR_INVALID, "null scene");
     if (count && (!rays || !hits)) return fail(ORT_ERR_INVALID, "null rays or hits");
     if (count && (((uintptr_t)rays | (uintptr_t)hits) & 7u)) return fail(ORT_ERR_INVALID, "rays and hits must be 8-byte aligned");
-    if (!s->tree.built) return fail(ORT_ERR_STATE, "ort_scene_commit has not been called");
-    if (!s->dev) return fail(ORT_ERR_NO_DEVICE, "scene is not resident on a HIP device: call ort_scene_upload (no CPU fallback)");
-    return ORT_OK;
-}
-
-static int ort_raycast_impl(ort_scene *s, const float *rays, uint64_t count, ort_hit *hits, uint32_t flags, ort_stats *stats) {
-    int rc = check_raycast(s, rays, count, hits);
+    int rc = check_resident(s);
     if (rc != ORT_OK) return rc;
-    if (count == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return ORT_OK;
-    }
+    if (count == 0) return nothing_to_do(stats);
     std::string err;
-    rc = ort::device_raycast(s, rays, nullptr, count, hits, nullptr, flags, nullptr, stats, &err);
-    return rc == ORT_OK ? ORT_OK : fail(rc, err);
-}
-
-static int ort_raycast_device_impl(ort_scene *s, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags, void *hip_stream, ort_stats *stats) {
-    int rc = check_raycast(s, d_rays, count, d_hits);
-    if (rc != ORT_OK) return rc;
-    if (count == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return ORT_OK;
-    }
-    std::string err;
-    rc = ort::device_raycast(s, nullptr, d_rays, count, nullptr, d_hits, flags, hip_stream, stats, &err);
+    rc = ort::device_raycast(s, h_rays, d_rays, count, h_hits, d_hits, flags, stream, stats, &err);
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
 /* occlusion queries: count == 0 is OK whatever else is passed; then argument errors, then state errors */
-static int check_occluded(const ort_scene *s, const void *rays, const void *tmax, const void *occluded) {
+static int occluded_common(ort_scene *s, const float *h_rays, const void *d_rays, const void *tmax, uint64_t count, uint8_t *h_out, void *d_out, uint32_t flags,
+                           void *stream, ort_stats *stats) {
+    if (count == 0) return nothing_to_do(stats);
+    const void *rays = h_rays ? (const void *)h_rays : d_rays;
     if (!s) return fail(ORT_ERR_INVALID, "null scene");
-    if (!rays || !occluded) return fail(ORT_ERR_INVALID, "null rays or occluded");
+    if (!rays || !(h_out || d_out)) return fail(ORT_ERR_INVALID, "null rays or occluded");
     if ((uintptr_t)rays & 7u) return fail(ORT_ERR_INVALID, "rays must be 8-byte aligned");
     if ((uintptr_t)tmax & 3u) return fail(ORT_ERR_INVALID, "tmax must be 4-byte aligned");
-    if (!s->tree.built) return fail(ORT_ERR_STATE, "ort_scene_commit has not been called");
-    if (!s->dev) return fail(ORT_ERR_NO_DEVICE, "scene is not resident on a HIP device: call ort_scene_upload (no CPU fallback)");
-    return ORT_OK;
-}
-
-static int ort_occluded_impl(ort_scene *s, const float *rays, const float *tmax, uint64_t count, uint8_t *occluded, uint32_t flags, ort_stats *stats) {
-    if (count == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return ORT_OK;
-    }
-    int rc = check_occluded(s, rays, tmax, occluded);
+    int rc = check_resident(s);
     if (rc != ORT_OK) return rc;
     std::string err;
-    rc = ort::device_occluded(s, rays, nullptr, tmax, count, occluded, nullptr, flags, nullptr, stats, &err);
-    return rc == ORT_OK ? ORT_OK : fail(rc, err);
-}
-
-static int ort_occluded_device_impl(ort_scene *s, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded, uint32_t flags, void *hip_stream,
-                                    ort_stats *stats) {
-    if (count == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return ORT_OK;
-    }
-    int rc = check_occluded(s, d_rays, d_tmax, d_occluded);
-    if (rc != ORT_OK) return rc;
-    std::string err;
-    rc = ort::device_occluded(s, nullptr, d_rays, d_tmax, count, nullptr, d_occluded, flags, hip_stream, stats, &err);
+    rc = ort::device_occluded(s, h_rays, d_rays, tmax, count, h_out, d_out, flags, stream, stats, &err);
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
 /* radiance queries: count == 0 is OK whatever else is passed; then argument errors, then state errors */
-static int check_radiance(const ort_scene *s, const void *rays, const void *seeds, uint32_t spp, float rr, const void *out_rgb, const void *final_states) {
+static int radiance_common(ort_scene *s, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, uint32_t spp, float rr, float *h_out,
+                           void *d_out, uint32_t *h_states, void *d_states, uint32_t flags, void *stream, ort_stats *stats) {
+    if (count == 0) return nothing_to_do(stats);
+    const void *rays = h_rays ? (const void *)h_rays : d_rays, *out_rgb = h_out ? (const void *)h_out : d_out,
+               *final_states = h_states ? (const void *)h_states : d_states;
     if (!s) return fail(ORT_ERR_INVALID, "null scene");
     if (!rays || !seeds || !out_rgb) return fail(ORT_ERR_INVALID, "null rays, seeds or out_rgb");
     if ((uintptr_t)rays & 7u) return fail(ORT_ERR_INVALID, "rays must be 8-byte aligned");
     if (((uintptr_t)seeds | (uintptr_t)out_rgb | (uintptr_t)final_states) & 3u) return fail(ORT_ERR_INVALID, "seeds, out_rgb and final_states must be 4-byte aligned");
     if (spp == 0) return fail(ORT_ERR_INVALID, "spp must be >= 1");
     if (!(rr >= 0.0f && rr < 1.0f)) return fail(ORT_ERR_INVALID, "rr must be in [0, 1): at 1 a path in a closed room never ends");
-    if (!s->tree.built) return fail(ORT_ERR_STATE, "ort_scene_commit has not been called");
-    if (!s->dev) return fail(ORT_ERR_NO_DEVICE, "scene is not resident on a HIP device: call ort_scene_upload (no CPU fallback)");
-    return ORT_OK;
-}
-
-static int ort_radiance_impl(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr, float *out_rgb,
-                             uint32_t *final_states, uint32_t flags, ort_stats *stats) {
-    if (count == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return ORT_OK;
-    }
-    int rc = check_radiance(s, rays, seeds, spp, rr, out_rgb, final_states);
+    int rc = check_resident(s);
     if (rc != ORT_OK) return rc;
     std::string err;
-    rc = ort::device_radiance(s, rays, nullptr, seeds, count, spp, rr, out_rgb, nullptr, final_states, nullptr, flags, nullptr, stats, &err);
-    return rc == ORT_OK ? ORT_OK : fail(rc, err);
-}
-
-static int ort_radiance_device_impl(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out_rgb,
-                                    void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) {
-    if (count == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return ORT_OK;
-    }
-    int rc = check_radiance(s, d_rays, d_seeds, spp, rr, d_out_rgb, d_final_states);
-    if (rc != ORT_OK) return rc;
-    std::string err;
-    rc = ort::device_radiance(s, nullptr, d_rays, d_seeds, count, spp, rr, nullptr, d_out_rgb, nullptr, d_final_states, flags, hip_stream, stats, &err);
+    rc = ort::device_radiance(s, h_rays, d_rays, seeds, count, spp, rr, h_out, d_out, h_states, d_states, flags, stream, stats, &err);
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
@@ -504,10 +458,7 @@ static bool view_in_box(const ort_camera &c, const float lo[3], const float hi[3
 /* view_count == 0 is OK whatever else is passed; then argument errors, what the call does not do, and the scene's state */
 static int render_views_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, void *d_out, float *h_out,
                                void *stream, ort_stats *stats) {
-    if (view_count == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return ORT_OK;
-    }
+    if (view_count == 0) return nothing_to_do(stats);
     if (!views || (!d_out && !h_out)) return fail(ORT_ERR_INVALID, "null views or framebuffer");
     static_assert(sizeof(ort_view) == 52, "ort_view is a camera and a seed");
     if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
@@ -523,8 +474,7 @@ static int render_views_common(ort_scene *s, const ort_render_params *p, const o
         if (!view_in_box(views[v].camera, lo, hi))
             return fail(ORT_ERR_UNSUPPORTED, "view " + std::to_string(v) + ": the camera's aperture is not finite or leaves the box of the scene's shapes and its own "
                                              "camera_p (+ 0.25 per side) that the tree was built for; create the scene with a camera_p out there");
-    if (!s->tree.built) return fail(ORT_ERR_STATE, "ort_scene_commit has not been called");
-    if (!s->dev) return fail(ORT_ERR_NO_DEVICE, "scene is not resident on a HIP device: call ort_scene_upload (no CPU fallback)");
+    if ((rc = check_resident(s)) != ORT_OK) return rc;
     std::string err;
     rc = ort::device_render(s, p, nullptr, 0, d_out, h_out, stream, nullptr, stats, &err, views, view_count);
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
@@ -627,12 +577,12 @@ int ort_tiled_raytrace(ort_scene *s, float *out_rgb, int32_t width, int32_t heig
 int ort_render_image(ort_scene *s, const ort_render_params *p, float *out_rgb, ort_stats *stats) { return guarded([&]() { return ort_render_image_impl(s, p, out_rgb, stats); }); }
 int ort_render_image_device(ort_scene *s, const ort_render_params *p, void *d_out_rgb, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_render_image_device_impl(s, p, d_out_rgb, hip_stream, stats); }); }
 int ort_unit_eval_device(int device, const void *records, uint32_t count, float *out) { return guarded([&]() { return ort_unit_eval_device_impl(device, records, count, out); }); }
-int ort_raycast(ort_scene *s, const float *rays, uint64_t count, ort_hit *hits, uint32_t flags, ort_stats *stats) { return guarded([&]() { return ort_raycast_impl(s, rays, count, hits, flags, stats); }); }
-int ort_raycast_device(ort_scene *s, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_raycast_device_impl(s, d_rays, count, d_hits, flags, hip_stream, stats); }); }
-int ort_occluded(ort_scene *s, const float *rays, const float *tmax, uint64_t count, uint8_t *occluded, uint32_t flags, ort_stats *stats) { return guarded([&]() { return ort_occluded_impl(s, rays, tmax, count, occluded, flags, stats); }); }
-int ort_occluded_device(ort_scene *s, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_occluded_device_impl(s, d_rays, d_tmax, count, d_occluded, flags, hip_stream, stats); }); }
-int ort_radiance(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr, float *out_rgb, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return ort_radiance_impl(s, rays, seeds, count, spp, rr, out_rgb, final_states, flags, stats); }); }
-int ort_radiance_device(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_radiance_device_impl(s, d_rays, d_seeds, count, spp, rr, d_out_rgb, d_final_states, flags, hip_stream, stats); }); }
+int ort_raycast(ort_scene *s, const float *rays, uint64_t count, ort_hit *hits, uint32_t flags, ort_stats *stats) { return guarded([&]() { return raycast_common(s, rays, nullptr, count, hits, nullptr, flags, nullptr, stats); }); }
+int ort_raycast_device(ort_scene *s, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return raycast_common(s, nullptr, d_rays, count, nullptr, d_hits, flags, hip_stream, stats); }); }
+int ort_occluded(ort_scene *s, const float *rays, const float *tmax, uint64_t count, uint8_t *occluded, uint32_t flags, ort_stats *stats) { return guarded([&]() { return occluded_common(s, rays, nullptr, tmax, count, occluded, nullptr, flags, nullptr, stats); }); }
+int ort_occluded_device(ort_scene *s, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return occluded_common(s, nullptr, d_rays, d_tmax, count, nullptr, d_occluded, flags, hip_stream, stats); }); }
+int ort_radiance(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr, float *out_rgb, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_common(s, rays, nullptr, seeds, count, spp, rr, out_rgb, nullptr, final_states, nullptr, flags, nullptr, stats); }); }
+int ort_radiance_device(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_common(s, nullptr, d_rays, d_seeds, count, spp, rr, nullptr, d_out_rgb, nullptr, d_final_states, flags, hip_stream, stats); }); }
 int ort_render_workspace_bytes(const ort_render_params *p, uint64_t *bytes) { return guarded([&]() { return ort_render_workspace_bytes_impl(p, bytes); }); }
 int ort_camera_from_pose(const float p[3], const float quat_xyzw[4], float height_ratio, int32_t width, int32_t height, ort_camera *out) { return guarded([&]() { return ort_camera_from_pose_impl(p, quat_xyzw, height_ratio, width, height, out); }); }
 int ort_render_views(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, float *out_rgb, ort_stats *stats) { return guarded([&]() { return render_views_common(s, p, views, view_count, nullptr, out_rgb, nullptr, stats); }); }

@@ -4,6 +4,7 @@
  * kernels' four-waves-per-SIMD build (instantiated by launch_path_tracer below; the lane code itself is ort_lane.h).
  */
 #include <algorithm>
+#include <type_traits>
 
 #include "ort_lane.h"
 #include "ort_plan.h"
@@ -270,7 +271,7 @@ static int launch_wavefront(DeviceScene *d, const SceneView &sv, const RenderVie
 }
 
 /* The path-trace kernel a plan names.  These sixteen variants, the six of a batch of views, the eight of the radiance queries
-   (launch_radiance) and the two of ort_kernels_w5.hip are all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
+   (device_radiance) and the two of ort_kernels_w5.hip are all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
    an error, not a fallback. */
 static int launch_path_tracer(const LaunchPlan &pl, hipStream_t stream, const SceneView &sv, const RenderHot &hot, std::string *err) {
     if (pl.views) { /* the plain loop with the camera table: counters | diffuse, tabs (implicit follows from both) */
@@ -532,10 +533,7 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
     /* the RenderView goes to HBM (pageable source: the copy is staged before the call returns); the kernels get the few
        fields every ray reads by value and a pointer to the rest */
     ORT_HIP(hipMemcpyAsync(d->rv_dev.p, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
-    RenderHot hot{};
-    hot.mode = rv.mode; hot.W = rv.W; hot.H = rv.H; hot.rr = rv.rr;
-    hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
-    hot.c = (const ORT_CONSTANT_AS RenderView *)d->rv_dev.p;
+    const RenderHot hot = render_hot<RenderHot>(rv, d->rv_dev.p);
     if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
     if (pl.wavefront) rc = pl.counters ? launch_wavefront<true>(d, sv, rv, hot, stream, err) : launch_wavefront<false>(d, sv, rv, hot, stream, err);
     else rc = launch_path_tracer(pl, stream, sv, hot, err);
@@ -567,25 +565,11 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
     return ORT_OK;
 }
 
-/* ---- closest-hit ray queries (ort_raycast*) ------------------------------------------------------------------------ */
-/* Fixed by a measured sweep (profiles/r04_raycast_tuning.md); the -D forms exist for such sweeps (tools/build_variant.sh) */
-#ifndef ORT_RAYCAST_REFILL
-#define ORT_RAYCAST_REFILL 32 /* leave the traversal loop, and start new rays, when fewer lanes than this are still tracing */
-#endif
-#ifndef ORT_RAYCAST_BATCH
-#define ORT_RAYCAST_BATCH 1024 /* ray indices a wave draws per atomic */
-#endif
-#ifndef ORT_RAYCAST_TAIL
-#define ORT_RAYCAST_TAIL 4 /* ... until this many rays per lane are left: then exactly as many as it needs */
-#endif
-constexpr uint64_t kRaycastSlice = 1ull << 22; /* rays per launch of the host form (2 x 96 MB of staging) */
-
-/* the box of everything ort_tree.cpp sized the quadric boxes for (raycast_needs_exact), worked out at the first query of either kind */
-static void ensure_scene_box(Scene *scene, DeviceScene *d) {
-    if (d->scene_box_known) return;
-    scene_origin_box(*scene, d->scene_lo, d->scene_hi); /* shapes and camera */
-    d->scene_box_known = true;
-}
+/* ---- the ray queries (ort_raycast*, ort_occluded*, ort_radiance*) -------------------------------------------------------- */
+/* What is launched, on which grid and with which thresholds is plan_ray_query's and plan_radiance's decision (ort_plan.h); this
+   is the plumbing around them: one launch path (launch_query) and one host-form loop (run_sliced) for the three */
+constexpr uint64_t kRaycastSlice = 1ull << 22;  /* rays per launch of the host form of ort_raycast and ort_occluded (2 x 96 MB of staging) */
+constexpr uint64_t kRadianceSlice = 1ull << 20; /* ... of ort_radiance: a ray is spp paths, and 44 MB of staging */
 
 /* the inverse of the tree's slot maps, in PrimInfo order (triangles | boxes | cylinders | spheres): slot -> kind << 28 |
    the shape's index in the scene's own arrays.  Built and uploaded at the first query, so that render-only users pay nothing */
@@ -594,7 +578,6 @@ static int ensure_prim_src(Scene *scene, DeviceScene *d, std::string *err) {
     std::vector<uint32_t> src;
     const bool bijective = invert_prim_slots(scene->tree, d->info_box, d->info_cyl, d->info_sphere, src);
     if (!bijective) { *err = "internal: the tree's slot maps are not a bijection onto its shape arrays"; return ORT_ERR_INTERNAL; }
-    ensure_scene_box(scene, d);
     return upload_vec(src, &d->prim_src, err);
 }
 
@@ -606,32 +589,36 @@ static RaycastIO ray_query_io(Scene *scene, DeviceScene *d, const void *d_rays) 
     return io;
 }
 
-/* the launch policy of a ray query over count rays: the grid, and the job space (the ray array, drawn in batches) uploaded behind hot.c */
-static int ray_query_plan(Scene *scene, DeviceScene *d, uint64_t count, hipStream_t stream, unsigned int *grid_out, RenderHot *hot_out, std::string *err) {
-    unsigned int grid = (unsigned int)((count + kBlock - 1) / kBlock);
-    if (grid > d->max_blocks) grid = d->max_blocks;
-    const unsigned long long lanes = (unsigned long long)grid * kBlock;
-    RenderView rv{};
-    rv.job_count = count;
-    rv.next_job = d->ctrl();
-    rv.counters = d->ctrl() + 1;
-    rv.job_batch = ORT_RAYCAST_BATCH;
-    rv.batch_until = count > ORT_RAYCAST_TAIL * lanes ? count - ORT_RAYCAST_TAIL * lanes : 0ull;
-    rv.refill_below = ORT_RAYCAST_REFILL;
-    rv.descend_below = tree_is_cache_resident(fast_tree_bytes(scene), -1) ? 8 : 16; /* as the renders (plan_render), whatever ORT_CACHE_RESIDENT says */
-    ORT_HIP(hipMemsetAsync(d->ctrl(), 0, 128 * sizeof(unsigned long long), stream));
-    ORT_HIP(hipMemcpyAsync(d->rv_dev.p, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
-    RenderHot hot{};
-    hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
-    hot.c = (const ORT_CONSTANT_AS RenderView *)d->rv_dev.p;
-    *grid_out = grid;
-    *hot_out = hot;
-    return ORT_OK;
+/* runtime bools to template arguments: f(std::bool_constant...) with one constant per bool, true first at every level */
+template <typename F>
+static void with_bools(F f) { f(); }
+template <typename F, typename... Rest>
+static void with_bools(F f, bool b, Rest... rest) {
+    if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
-/* after the launch of a ray query: mark it in flight; with stats, wait for it and add its time and counters */
-static int ray_query_finish(DeviceScene *d, bool counters, hipStream_t stream, ort_stats *stats, std::string *err, bool paths = false) {
+/* One launch of a ray query over count rays.  rv holds what the query's lanes read behind hot.c besides the policy (nothing for
+   raycast_rays and occluded_rays, radiance_view for radiance_rays); issue(sv, hot, plan) enqueues the kernel the plan names.
+   stats (may be NULL): synchronous, the launch's time and counters added (radiance: the primary rays traced as paths) */
+template <typename Issue>
+static int launch_query(Scene *scene, DeviceScene *d, RenderView rv, uint64_t count, bool radiance, bool counters, hipStream_t stream, ort_stats *stats,
+                        std::string *err, Issue issue) {
     int rc;
+    if ((rc = settle_inflight(d, err))) return rc;
+    const SceneView sv = scene_view(scene, d);
+    const QueryPlan pl = radiance ? plan_radiance(scene_traits(scene, d), count, counters, d->knobs) : plan_ray_query(scene_traits(scene, d), count, counters);
+    rv.job_count = count; /* the job space: the ray array, drawn in batches */
+    rv.next_job = d->ctrl();
+    rv.counters = d->ctrl() + 1;
+    rv.job_batch = pl.job_batch; rv.batch_until = pl.batch_until;
+    rv.refill_below = pl.refill_below; rv.descend_below = pl.descend_below;
+    ORT_HIP(hipMemsetAsync(d->ctrl(), 0, 128 * sizeof(unsigned long long), stream));
+    ORT_HIP(hipMemcpyAsync(d->rv_dev.p, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
+    const RenderHot hot = render_hot<RenderHot>(rv, d->rv_dev.p);
+    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
+    issue(sv, hot, pl);
+    /* mark it in flight; with stats, wait for it and add its time and counters */
     ORT_HIP(hipGetLastError());
     if (stats) ORT_HIP(hipEventRecord(d->ev1, stream));
     ORT_HIP(hipEventRecord(d->ev_done, stream));
@@ -645,196 +632,126 @@ static int ray_query_finish(DeviceScene *d, bool counters, hipStream_t stream, o
         stats->kernel_ms += ms;
         stats->fallback_rays += c[5];
         if (counters) { stats->rays += c[1]; stats->node_tests += c[2]; stats->tri_tests += c[3]; stats->analytic_tests += c[4]; }
-        if (counters && paths) stats->paths += c[0]; /* radiance queries: primary rays traced */
+        if (counters && radiance) stats->paths += c[0];
     }
     return ORT_OK;
 }
 
-/* one launch over count rays at d_rays -> d_hits (device pointers); stats (may be NULL): synchronous, counters added */
-static int launch_raycast(Scene *scene, DeviceScene *d, const void *d_rays, uint64_t count, void *d_hits, bool counters, hipStream_t stream,
-                          ort_stats *stats, std::string *err) {
+/* One array of the host form of a query: `bytes` per ray between the caller's memory and a staging buffer of the scene, towards
+   the device or (out) back.  host == NULL: an optional array the caller did not pass; it does not travel, and dev() is null */
+struct QueryStream {
+    void *host;
+    DevBuf *stage;
+    size_t bytes;
+    bool out;
+    void *dev() const { return host ? stage->p : nullptr; }
+};
+
+/* The host form: bounded slices through the scene's staging buffers, launch(n) over the first n rays staged.  Every ray is
+   answered on its own (and on its own random stream), so the slicing cannot change a result */
+template <size_t N, typename Launch>
+static int run_sliced(DeviceScene *d, uint64_t count, uint64_t slice_cap, const QueryStream (&streams)[N], hipStream_t stream, std::string *err, Launch launch) {
     int rc;
-    if ((rc = settle_inflight(d, err))) return rc;
-    const SceneView sv = scene_view(scene, d);
-    RaycastIO io = ray_query_io(scene, d, d_rays);
-    io.hits = (uint2 *)d_hits;
-    io.prim_src = d->prim_src.as<const uint32_t>();
-    unsigned int grid = 0;
-    RenderHot hot{};
-    if ((rc = ray_query_plan(scene, d, count, stream, &grid, &hot, err))) return rc;
-    const bool tabs = (d->tab_flags & TAB_PRO) != 0;
-    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
-    if (counters) {
-        if (tabs) hipLaunchKernelGGL((raycast_rays<true, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
-        else hipLaunchKernelGGL((raycast_rays<true, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
-    } else {
-        if (tabs) hipLaunchKernelGGL((raycast_rays<false, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
-        else hipLaunchKernelGGL((raycast_rays<false, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
+    const uint64_t slice = count < slice_cap ? count : slice_cap;
+    for (const QueryStream &s : streams)
+        if (s.host && (rc = s.stage->ensure((size_t)slice * s.bytes, err))) return rc;
+    for (uint64_t at = 0; at < count; at += slice) {
+        const uint64_t n = count - at < slice ? count - at : slice;
+        if ((rc = settle_inflight(d, err))) return rc; /* the staging buffers are the previous slice's until it is done */
+        for (const QueryStream &s : streams)
+            if (s.host && !s.out) ORT_HIP(hipMemcpyAsync(s.stage->p, (const char *)s.host + at * s.bytes, (size_t)n * s.bytes, hipMemcpyHostToDevice, stream));
+        if ((rc = launch(n))) return rc;
+        for (const QueryStream &s : streams)
+            if (s.host && s.out) ORT_HIP(hipMemcpyAsync((char *)s.host + at * s.bytes, s.stage->p, (size_t)n * s.bytes, hipMemcpyDeviceToHost, stream));
+        ORT_HIP(hipStreamSynchronize(stream));
     }
-    return ray_query_finish(d, counters, stream, stats, err);
+    return settle_inflight(d, err);
 }
 
-/* the same launch for occlusion: count rays at d_rays, limits at d_tmax (may be null) -> count bytes at d_out */
-static int launch_occluded(Scene *scene, DeviceScene *d, const void *d_rays, const void *d_tmax, uint64_t count, void *d_out, bool counters,
-                           hipStream_t stream, ort_stats *stats, std::string *err) {
-    int rc;
-    if ((rc = settle_inflight(d, err))) return rc;
-    const SceneView sv = scene_view(scene, d);
-    OccludedIO io{};
-    io.q = ray_query_io(scene, d, d_rays);
-    io.tmax = (const float *)d_tmax;
-    io.out = (uint8_t *)d_out;
-    io.mats_nonzero = all_mats_nonzero(scene->tree);
-    unsigned int grid = 0;
-    RenderHot hot{};
-    if ((rc = ray_query_plan(scene, d, count, stream, &grid, &hot, err))) return rc;
-    const bool tabs = (d->tab_flags & TAB_PRO) != 0;
-    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
-    if (counters) {
-        if (tabs) hipLaunchKernelGGL((occluded_rays<true, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
-        else hipLaunchKernelGGL((occluded_rays<true, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
-    } else {
-        if (tabs) hipLaunchKernelGGL((occluded_rays<false, true>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
-        else hipLaunchKernelGGL((occluded_rays<false, false>), dim3(grid), dim3(kBlock), 0, stream, sv, hot, io);
-    }
-    return ray_query_finish(d, counters, stream, stats, err);
+/* what every query call starts with: the scene's device made current, the stats zeroed, and, from the first query of any kind
+   on, the box of everything ort_tree.cpp sized the quadric boxes for (shapes and camera: raycast_needs_exact) */
+static int begin_query(Scene *scene, ort_stats *stats, DeviceScene **d_out, std::string *err) {
+    DeviceScene *d = *d_out = scene->dev;
+    if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
+    ORT_HIP(hipSetDevice(d->device));
+    if (!d->scene_box_known) scene_origin_box(*scene, d->scene_lo, d->scene_hi);
+    d->scene_box_known = true;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    return ORT_OK;
 }
 
+/* closest hits: count rays at h_rays -> h_hits (host form) or at d_rays -> d_hits (device pointers, one launch) */
 int device_raycast(Scene *scene, const float *h_rays, const void *d_rays, uint64_t count, ort_hit *h_hits, void *d_hits, uint32_t flags,
                    void *stream_v, ort_stats *stats, std::string *err) {
     static_assert(sizeof(ort_hit) == 24, "ort_hit is three 8-byte words");
-    DeviceScene *d = scene->dev;
-    if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
-    ORT_HIP(hipSetDevice(d->device));
-    hipStream_t stream = (hipStream_t)stream_v;
+    DeviceScene *d;
     int rc;
-    if ((rc = ensure_prim_src(scene, d, err))) return rc;
+    if ((rc = begin_query(scene, stats, &d, err)) || (rc = ensure_prim_src(scene, d, err))) return rc;
+    hipStream_t stream = (hipStream_t)stream_v;
     const bool counters = (flags & ORT_RENDER_COUNTERS) != 0;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!h_rays) return launch_raycast(scene, d, d_rays, count, d_hits, counters, stream, stats, err);
-    /* host form: bounded slices through the scene's staging buffers; every ray is answered on its own, so the slicing
-       cannot change a result */
-    const uint64_t slice = count < kRaycastSlice ? count : kRaycastSlice;
-    if ((rc = d->ray_in.ensure((size_t)slice * 24u, err))) return rc;
-    if ((rc = d->hit_out.ensure((size_t)slice * sizeof(ort_hit), err))) return rc;
-    for (uint64_t at = 0; at < count; at += slice) {
-        const uint64_t n = count - at < slice ? count - at : slice;
-        if ((rc = settle_inflight(d, err))) return rc; /* the staging buffers are the previous slice's until it is done */
-        ORT_HIP(hipMemcpyAsync(d->ray_in.p, h_rays + 6u * at, (size_t)n * 24u, hipMemcpyHostToDevice, stream));
-        if ((rc = launch_raycast(scene, d, d->ray_in.p, n, d->hit_out.p, counters, stream, stats, err))) return rc;
-        ORT_HIP(hipMemcpyAsync(h_hits + at, d->hit_out.p, (size_t)n * sizeof(ort_hit), hipMemcpyDeviceToHost, stream));
-        ORT_HIP(hipStreamSynchronize(stream));
-    }
-    return settle_inflight(d, err);
+    auto launch = [&](const void *rays, void *hits, uint64_t n) {
+        RaycastIO io = ray_query_io(scene, d, rays);
+        io.hits = (uint2 *)hits;
+        io.prim_src = d->prim_src.as<const uint32_t>();
+        return launch_query(scene, d, RenderView{}, n, false, counters, stream, stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
+            with_bools([&](auto C, auto T) {
+                hipLaunchKernelGGL((raycast_rays<decltype(C)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot, io);
+            }, pl.counters, pl.tabs);
+        });
+    };
+    if (!h_rays) return launch(d_rays, d_hits, count);
+    const QueryStream s[] = {{(void *)h_rays, &d->ray_in, 24u, false}, {h_hits, &d->hit_out, sizeof(ort_hit), true}};
+    return run_sliced(d, count, kRaycastSlice, s, stream, err, [&](uint64_t n) { return launch(s[0].dev(), s[1].dev(), n); });
 }
 
+/* occlusion: the same for count rays and their limits at tmax (may be null; a host or a device pointer as the rays are) -> count
+   bytes.  No shape table: a byte names no shape */
 int device_occluded(Scene *scene, const float *h_rays, const void *d_rays, const void *tmax, uint64_t count, uint8_t *h_out, void *d_out,
                     uint32_t flags, void *stream_v, ort_stats *stats, std::string *err) {
-    DeviceScene *d = scene->dev;
-    if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
-    ORT_HIP(hipSetDevice(d->device));
+    DeviceScene *d;
+    int rc;
+    if ((rc = begin_query(scene, stats, &d, err))) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
-    int rc;
-    ensure_scene_box(scene, d); /* no shape table: a byte names no shape */
     const bool counters = (flags & ORT_RENDER_COUNTERS) != 0;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!h_rays) return launch_occluded(scene, d, d_rays, tmax, count, d_out, counters, stream, stats, err);
-    /* host form: bounded slices through the scene's staging buffers, as device_raycast */
-    const uint64_t slice = count < kRaycastSlice ? count : kRaycastSlice;
-    if ((rc = d->ray_in.ensure((size_t)slice * 24u, err))) return rc;
-    if (tmax && (rc = d->tmax_in.ensure((size_t)slice * sizeof(float), err))) return rc;
-    if ((rc = d->occ_out.ensure((size_t)slice, err))) return rc;
-    for (uint64_t at = 0; at < count; at += slice) {
-        const uint64_t n = count - at < slice ? count - at : slice;
-        if ((rc = settle_inflight(d, err))) return rc; /* the staging buffers are the previous slice's until it is done */
-        ORT_HIP(hipMemcpyAsync(d->ray_in.p, h_rays + 6u * at, (size_t)n * 24u, hipMemcpyHostToDevice, stream));
-        if (tmax) ORT_HIP(hipMemcpyAsync(d->tmax_in.p, (const float *)tmax + at, (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
-        if ((rc = launch_occluded(scene, d, d->ray_in.p, tmax ? d->tmax_in.p : nullptr, n, d->occ_out.p, counters, stream, stats, err))) return rc;
-        ORT_HIP(hipMemcpyAsync(h_out + at, d->occ_out.p, (size_t)n, hipMemcpyDeviceToHost, stream));
-        ORT_HIP(hipStreamSynchronize(stream));
-    }
-    return settle_inflight(d, err);
+    auto launch = [&](const void *rays, const void *limits, void *out, uint64_t n) {
+        OccludedIO io{};
+        io.q = ray_query_io(scene, d, rays);
+        io.tmax = (const float *)limits;
+        io.out = (uint8_t *)out;
+        io.mats_nonzero = all_mats_nonzero(scene->tree);
+        return launch_query(scene, d, RenderView{}, n, false, counters, stream, stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
+            with_bools([&](auto C, auto T) {
+                hipLaunchKernelGGL((occluded_rays<decltype(C)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot, io);
+            }, pl.counters, pl.tabs);
+        });
+    };
+    if (!h_rays) return launch(d_rays, tmax, d_out, count);
+    const QueryStream s[] = {{(void *)h_rays, &d->ray_in, 24u, false}, {(void *)tmax, &d->tmax_in, sizeof(float), false}, {h_out, &d->occ_out, 1u, true}};
+    return run_sliced(d, count, kRaycastSlice, s, stream, err, [&](uint64_t n) { return launch(s[0].dev(), s[1].dev(), s[2].dev(), n); });
 }
 
-/* ---- radiance queries (ort_radiance*) ------------------------------------------------------------------------------ */
-constexpr uint64_t kRadianceSlice = 1ull << 20; /* rays per launch of the host form: a ray is spp paths, and 44 MB of staging */
-
-/* one launch over count rays at d_rays with d_seeds -> d_out (3 floats each) and d_states (may be null), all device pointers.
-   Which kernel, on which grid, is plan_radiance's decision (ort_plan.h) */
-static int launch_radiance(Scene *scene, DeviceScene *d, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out,
-                           void *d_states, bool counters, hipStream_t stream, ort_stats *stats, std::string *err) {
-    int rc;
-    if ((rc = settle_inflight(d, err))) return rc;
-    const SceneView sv = scene_view(scene, d);
-    const RadiancePlan pl = plan_radiance(scene_traits(scene, d), count, counters, d->knobs);
-    const RaycastIO q = ray_query_io(scene, d, d_rays);
-    RenderView rv{};
-    rv.mode = JOBS_PIXEL;
-    rv.job_count = count;
-    rv.next_job = d->ctrl();
-    rv.counters = d->ctrl() + 1;
-    rv.job_batch = pl.job_batch; rv.batch_until = pl.batch_until;
-    rv.refill_below = pl.refill_below; rv.descend_below = pl.descend_below;
-    rv.spp = spp; rv.rr = rr;
-    rv.out = (float *)d_out;
-    rv.final_states = (uint32_t *)d_states;
-    rv.rays = q.rays;
-    rv.seeds = (const uint32_t *)d_seeds;
-    rv.ray_tree_spheres = q.tree_spheres; rv.ray_tree_quadrics = q.tree_quadrics; rv.ray_tree_boxes = q.tree_boxes;
-    memcpy(rv.ray_lo, q.lo, sizeof(rv.ray_lo));
-    memcpy(rv.ray_hi, q.hi, sizeof(rv.ray_hi));
-    ORT_HIP(hipMemsetAsync(d->ctrl(), 0, 128 * sizeof(unsigned long long), stream));
-    ORT_HIP(hipMemcpyAsync(d->rv_dev.p, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
-    RenderHot hot{};
-    hot.mode = rv.mode; hot.rr = rv.rr;
-    hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
-    hot.c = (const ORT_CONSTANT_AS RenderView *)d->rv_dev.p;
-    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
-    enum : unsigned { C = 4, D = 2, T = 1 }; /* the template arguments */
-#define ORT_RAD(KEY, ...) case KEY: hipLaunchKernelGGL((__VA_ARGS__), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot); break
-    switch ((pl.counters ? C : 0u) | (pl.diffuse ? D : 0u) | (pl.tabs ? T : 0u)) {
-        ORT_RAD(C | D | T, radiance_rays<true, true, true>);
-        ORT_RAD(C | D, radiance_rays<true, true, false>);
-        ORT_RAD(C | T, radiance_rays<true, false, true>);
-        ORT_RAD(C, radiance_rays<true, false, false>);
-        ORT_RAD(D | T, radiance_rays<false, true, true>);
-        ORT_RAD(D, radiance_rays<false, true, false>);
-        ORT_RAD(T, radiance_rays<false, false, true>);
-        ORT_RAD(0u, radiance_rays<false, false, false>);
-    }
-#undef ORT_RAD
-    return ray_query_finish(d, counters, stream, stats, err, true);
-}
-
+/* radiance: count rays with their seeds -> 3 floats each and, where asked for (h_states / d_states may be null), the final
+   states.  No shape table: a colour names no shape */
 int device_radiance(Scene *scene, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, uint32_t spp, float rr, float *h_out,
                     void *d_out, uint32_t *h_states, void *d_states, uint32_t flags, void *stream_v, ort_stats *stats, std::string *err) {
-    DeviceScene *d = scene->dev;
-    if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
-    ORT_HIP(hipSetDevice(d->device));
-    hipStream_t stream = (hipStream_t)stream_v;
+    DeviceScene *d;
     int rc;
-    ensure_scene_box(scene, d); /* no shape table: a colour names no shape */
+    if ((rc = begin_query(scene, stats, &d, err))) return rc;
+    hipStream_t stream = (hipStream_t)stream_v;
     const bool counters = (flags & ORT_RENDER_COUNTERS) != 0;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!h_rays) return launch_radiance(scene, d, d_rays, seeds, count, spp, rr, d_out, d_states, counters, stream, stats, err);
-    /* host form: bounded slices through the scene's staging buffers, as device_raycast; every ray is answered on its own stream */
-    const uint64_t slice = count < kRadianceSlice ? count : kRadianceSlice;
-    if ((rc = d->ray_in.ensure((size_t)slice * 24u, err))) return rc;
-    if ((rc = d->seed_in.ensure((size_t)slice * 4u, err))) return rc;
-    if ((rc = d->rad_out.ensure((size_t)slice * 12u, err))) return rc;
-    if (h_states && (rc = d->rad_states.ensure((size_t)slice * 4u, err))) return rc;
-    for (uint64_t at = 0; at < count; at += slice) {
-        const uint64_t n = count - at < slice ? count - at : slice;
-        if ((rc = settle_inflight(d, err))) return rc; /* the staging buffers are the previous slice's until it is done */
-        ORT_HIP(hipMemcpyAsync(d->ray_in.p, h_rays + 6u * at, (size_t)n * 24u, hipMemcpyHostToDevice, stream));
-        ORT_HIP(hipMemcpyAsync(d->seed_in.p, (const uint32_t *)seeds + at, (size_t)n * 4u, hipMemcpyHostToDevice, stream));
-        if ((rc = launch_radiance(scene, d, d->ray_in.p, d->seed_in.p, n, spp, rr, d->rad_out.p, h_states ? d->rad_states.p : nullptr, counters, stream, stats, err)))
-            return rc;
-        ORT_HIP(hipMemcpyAsync(h_out + 3u * at, d->rad_out.p, (size_t)n * 12u, hipMemcpyDeviceToHost, stream));
-        if (h_states) ORT_HIP(hipMemcpyAsync(h_states + at, d->rad_states.p, (size_t)n * 4u, hipMemcpyDeviceToHost, stream));
-        ORT_HIP(hipStreamSynchronize(stream));
-    }
-    return settle_inflight(d, err);
+    auto launch = [&](const void *rays, const void *ray_seeds, void *out, void *states, uint64_t n) {
+        RenderView rv{};
+        radiance_view(ray_query_io(scene, d, rays), ray_seeds, spp, rr, out, states, &rv);
+        return launch_query(scene, d, rv, n, true, counters, stream, stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
+            with_bools([&](auto C, auto D, auto T) {
+                hipLaunchKernelGGL((radiance_rays<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot);
+            }, pl.counters, pl.diffuse, pl.tabs);
+        });
+    };
+    if (!h_rays) return launch(d_rays, seeds, d_out, d_states, count);
+    const QueryStream s[] = {{(void *)h_rays, &d->ray_in, 24u, false}, {(void *)seeds, &d->seed_in, 4u, false}, {h_out, &d->rad_out, 12u, true},
+                             {h_states, &d->rad_states, 4u, true}};
+    return run_sliced(d, count, kRadianceSlice, s, stream, err, [&](uint64_t n) { return launch(s[0].dev(), s[1].dev(), s[2].dev(), s[3].dev(), n); });
 }
 
 } // namespace ort

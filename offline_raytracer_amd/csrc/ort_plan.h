@@ -1,8 +1,10 @@
 /*
- * ort_plan.h -- the launch policy of the render call, as arithmetic: what device_render (ort_kernels.hip) launches, with which
- * grid and which thresholds, decided from a few facts about the uploaded scene (SceneTraits), the render parameters and the
- * developer knobs.  Host-only and free of HIP, so that tools/launch_plan.cpp and tests/test_launch_plan.py can hold the
- * measured crossovers without a device.  ort_kernels.hip turns a LaunchPlan into launches and decides nothing.
+ * ort_plan.h -- the launch policy of the render call, of a batch of views and of the three ray queries, as arithmetic: what
+ * ort_kernels.hip launches, with which grid and which thresholds, decided from a few facts about the uploaded scene
+ * (SceneTraits), the render parameters or the ray count, and the developer knobs: plan_render for ort_render_image and
+ * ort_render_views, plan_ray_query for ort_raycast and ort_occluded, plan_radiance for ort_radiance.  Host-only and free of HIP,
+ * so that tools/launch_plan.cpp and tests/test_launch_plan.py can hold the measured crossovers without a device.
+ * ort_kernels.hip turns a LaunchPlan or a QueryPlan into launches and decides nothing.
  */
 #ifndef ORT_PLAN_H
 #define ORT_PLAN_H
@@ -148,6 +150,34 @@ struct SceneTraits {
     unsigned int max_blocks = 0; /* resident workgroups of a persistent launch, fixed at upload */
 };
 
+/* when a wave leaves its loops: the traversal loop (to start new rays) when fewer lanes than refill_below are still tracing, the
+   descend loop when fewer than descend_below still walk interior nodes.  ORT_REFILL_BELOW / ORT_DESCEND_BELOW, clamped; by
+   default tuned on MI355X (profiles/r01_tuning.md) separately for trees that stay in L2 and trees that do not */
+inline void plan_loop_exits(bool cache_resident_tree, const Knobs &kn, int *refill_below, int *descend_below) {
+    *refill_below = kn.refill_below >= 0 ? kn.refill_below : (cache_resident_tree ? 16 : 32); /* 12 until the block-major issue (round 3: 8-way shard 64.4 -> 63.8 ms) */
+    if (*refill_below < 1) *refill_below = 1;
+    if (*refill_below > 64) *refill_below = 64;
+    /* cache-resident trees (bunny room: 6 MB): 8, worth +10 %.  Trees that leave the 8 x 4 MB of L2 (the 1M-triangle
+       scene, 86 MB): 16 and a later refill (32): the waits are longer there, so leaving the loops costs more
+       (3840x2160, 256 spp: 1 272 Mpaths/s; with the small-tree values 1 100; profiles/r02_tuning.md) */
+    *descend_below = kn.descend_below >= 0 ? kn.descend_below : (cache_resident_tree ? 8 : 16);
+    if (*descend_below < 0) *descend_below = 0;
+    if (*descend_below > 64) *descend_below = 64;
+}
+
+/* a wave draws its job indices in batches (ort_lane.h: draw_job) until ORT_BATCH_TAIL jobs per lane are left in the job
+   space, then one by one: the end of a launch is dealt as finely as before.
+   64 indices at a time, 128 on launches of 96 jobs per lane and more; what a wave holds back is at most two jobs per lane of
+   its own, of up to eight average job lengths each in the expensive blocks: batches stop 8 (16) jobs per lane before the
+   end.  Whole headline frame / its 8-way shard, ms: no batches 422.5 / 63.7, 32: 418.9 / 63.1, 64: 414.3 / 62.0, 128: 411.3 /
+   74.4 (with the tail of 64), 256: 419.9 / 113 (profiles/r03_tuning.md) */
+inline void plan_job_batches(unsigned long long job_count, unsigned long long lanes, const Knobs &kn, uint32_t *job_batch, unsigned long long *batch_until) {
+    *job_batch = kn.job_batch >= 0 ? (uint32_t)kn.job_batch : (job_count >= 96ull * lanes ? 128u : 64u);
+    const unsigned long long per_lane = kn.batch_tail >= 0 ? (unsigned long long)kn.batch_tail : 8ull * ((*job_batch + 63u) / 64u);
+    const unsigned long long tail = per_lane * lanes;
+    *batch_until = job_count > tail ? job_count - tail : 0ull;
+}
+
 /* everything device_render decides before it touches the device */
 struct LaunchPlan {
     /* the kernel: wavefront <counters> | five waves <diffuse> | exchange <counters, diffuse> | plain loop <counters, diffuse, tabs,
@@ -192,18 +222,9 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
     LaunchPlan pl;
     const bool views = view_count > 1u && !explicit_jobs;
     const bool want_util = kn.debug_util && !views; /* developer diagnostics, counters build only */
-    /* tuning knobs; results do not depend on them.  Defaults tuned on MI355X (profiles/r01_tuning.md)
-       separately for trees that stay in L2 and trees that do not */
+    /* tuning knobs; results do not depend on them */
     const bool cache_resident_tree = tree_is_cache_resident(t.fast_tree_bytes, kn.cache_resident);
-    pl.refill_below = kn.refill_below >= 0 ? kn.refill_below : (cache_resident_tree ? 16 : 32); /* 12 until the block-major issue (round 3: 8-way shard 64.4 -> 63.8 ms) */
-    if (pl.refill_below < 1) pl.refill_below = 1;
-    if (pl.refill_below > 64) pl.refill_below = 64;
-    /* cache-resident trees (bunny room: 6 MB): 8, worth +10 %.  Trees that leave the 8 x 4 MB of L2 (the 1M-triangle
-       scene, 86 MB): 16 and a later refill (32): the waits are longer there, so leaving the loops costs more
-       (3840x2160, 256 spp: 1 272 Mpaths/s; with the small-tree values 1 100; profiles/r02_tuning.md) */
-    pl.descend_below = kn.descend_below >= 0 ? kn.descend_below : (cache_resident_tree ? 8 : 16);
-    if (pl.descend_below < 0) pl.descend_below = 0;
-    if (pl.descend_below > 64) pl.descend_below = 64;
+    plan_loop_exits(cache_resident_tree, kn, &pl.refill_below, &pl.descend_below);
 
     pl.blocks = block_grid_for(&p);
     if (explicit_jobs) {
@@ -298,19 +319,7 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
     /* CHUNK renders issue their jobs block-major (see "the order in which a CHUNK render issues its jobs"); ORT_LPT=0:
        chunk-major as in rounds 1-2 (A/B runs; same image either way) */
     if (pl.mode == PLAN_JOBS_CHUNK && pl.nchunks >= 2u && kn.lpt != 0) pl.block_major = 1u;
-    /* a wave draws its job indices in batches (ort_lane.h: draw_job) until ORT_BATCH_TAIL jobs per lane are left in the job
-       space, then one by one: the end of a launch is dealt as finely as before */
-    if (!wavefront) {
-        /* 64 indices at a time, 128 on launches of 96 jobs per lane and more; what a wave holds back is at most two jobs per lane of
-           its own, of up to eight average job lengths each in the expensive blocks: batches stop 8 (16) jobs per lane before the
-           end.  Whole headline frame / its 8-way shard, ms: no batches 422.5 / 63.7, 32: 418.9 / 63.1, 64: 414.3 / 62.0, 128: 411.3 /
-           74.4 (with the tail of 64), 256: 419.9 / 113 (profiles/r03_tuning.md) */
-        const unsigned long long lanes = (unsigned long long)grid * kPlanBlock;
-        pl.job_batch = kn.job_batch >= 0 ? (uint32_t)kn.job_batch : (pl.job_count >= 96ull * lanes ? 128u : 64u);
-        const unsigned long long per_lane = kn.batch_tail >= 0 ? (unsigned long long)kn.batch_tail : 8ull * ((pl.job_batch + 63u) / 64u);
-        const unsigned long long tail = per_lane * lanes;
-        pl.batch_until = pl.job_count > tail ? pl.job_count - tail : 0ull;
-    }
+    if (!wavefront) plan_job_batches(pl.job_count, (unsigned long long)grid * kPlanBlock, kn, &pl.job_batch, &pl.batch_until);
     if (kn.debug_drain && !wavefront) pl.drain_bytes = (size_t)max_blocks * (kPlanBlock / 64) * sizeof(unsigned long long);
     /* 4-wide tree (DevNode4): half the dependent node fetches per ray -- and twice the vector instructions per visit, in a
        kernel that is issue-bound at a third of its lanes on the trees it was meant for: 1 218 against 1 368 Mpaths/s on the
@@ -331,37 +340,69 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
     return pl;
 }
 
-/* The launch of a radiance query over count rays (ort_radiance; the radiance_rays kernels): always the plain persistent loop at
-   four waves, its job space the ray array.  The ray exchange, the five-waves unit, the wide tree and wavefront mode are not
-   built with a ray job space and their knobs are not looked at; ORT_DEBUG_UTIL has no probes here.  diffuse, tabs, the
-   refill and descend thresholds and the batch rules are decided as plan_render decides them for the plain loop, with one
-   difference: both BSDF flavours exist with counters.  Nothing of this has been tuned for ray batches yet. */
-struct RadiancePlan {
+/* ---- the ray queries: the job space is the caller's ray array -------------------------------------------------------- */
+/* what ort_kernels.hip launches for a query over count rays: <counters, tabs> of raycast_rays / occluded_rays, <counters,
+   diffuse, tabs> of radiance_rays, and the RenderView fields that are policy */
+struct QueryPlan {
     bool counters = false, diffuse = false, tabs = false;
     unsigned int grid = 1;
     int refill_below = 0, descend_below = 0;
     uint32_t job_batch = 0;
     unsigned long long batch_until = 0;
 };
-inline RadiancePlan plan_radiance(const SceneTraits &t, uint64_t count, bool counters, const Knobs &kn) {
-    RadiancePlan pl;
-    const bool cache_resident_tree = tree_is_cache_resident(t.fast_tree_bytes, kn.cache_resident);
-    pl.refill_below = kn.refill_below >= 0 ? kn.refill_below : (cache_resident_tree ? 16 : 32);
-    if (pl.refill_below < 1) pl.refill_below = 1;
-    if (pl.refill_below > 64) pl.refill_below = 64;
-    pl.descend_below = kn.descend_below >= 0 ? kn.descend_below : (cache_resident_tree ? 8 : 16);
-    if (pl.descend_below < 0) pl.descend_below = 0;
-    if (pl.descend_below > 64) pl.descend_below = 64;
+
+/* the persistent grid of a query: a lane per ray up to the resident workgroups */
+inline unsigned int query_grid(const SceneTraits &t, uint64_t count) {
+    const uint64_t blocks = (count + kPlanBlock - 1) / kPlanBlock;
+    return (unsigned int)(blocks < t.max_blocks ? blocks : t.max_blocks);
+}
+
+/* Closest-hit and occlusion queries.  Fixed by a measured sweep (profiles/r04_raycast_tuning.md); the -D forms exist for such
+   sweeps (tools/build_variant.sh) */
+#ifndef ORT_RAYCAST_REFILL
+#define ORT_RAYCAST_REFILL 32 /* leave the traversal loop, and start new rays, when fewer lanes than this are still tracing */
+#endif
+#ifndef ORT_RAYCAST_BATCH
+#define ORT_RAYCAST_BATCH 1024 /* ray indices a wave draws per atomic */
+#endif
+#ifndef ORT_RAYCAST_TAIL
+#define ORT_RAYCAST_TAIL 4 /* ... until this many rays per lane are left: then exactly as many as it needs */
+#endif
+/* The launch of ort_raycast and ort_occluded over count rays (count >= 1; raycast_rays, occluded_rays).  It takes no knobs,
+   and that is where it parts from plan_radiance below, each difference as the kernels were measured and shipped:
+   - refill_below, the batch and its tail are the three constants above: ORT_REFILL_BELOW, ORT_JOB_BATCH and ORT_BATCH_TAIL are
+     not read, and there is no 64 / 128 rule;
+   - descend_below is 8 or 16 by the 16 MB line, as the renders': ORT_DESCEND_BELOW is not read, and neither is
+     ORT_CACHE_RESIDENT;
+   - tabs is the prologue's table alone (TAB_PRO: these lanes read neither materials nor lights), whatever ORT_LDS_TABLES says;
+   - there is one BSDF-free flavour: diffuse stays false. */
+inline QueryPlan plan_ray_query(const SceneTraits &t, uint64_t count, bool counters) {
+    QueryPlan pl;
+    pl.counters = counters;
+    pl.tabs = (t.tab_flags & kPlanTabPro) != 0;
+    pl.grid = query_grid(t, count);
+    const unsigned long long lanes = (unsigned long long)pl.grid * kPlanBlock;
+    pl.refill_below = ORT_RAYCAST_REFILL;
+    pl.descend_below = tree_is_cache_resident(t.fast_tree_bytes, -1) ? 8 : 16;
+    pl.job_batch = ORT_RAYCAST_BATCH;
+    pl.batch_until = count > ORT_RAYCAST_TAIL * lanes ? count - ORT_RAYCAST_TAIL * lanes : 0ull;
+    return pl;
+}
+
+/* The launch of a radiance query over count rays (ort_radiance; the radiance_rays kernels): always the plain persistent loop at
+   four waves.  The ray exchange, the five-waves unit, the wide tree and wavefront mode are not built with a ray job space and
+   their knobs are not looked at; ORT_DEBUG_UTIL has no probes here.  diffuse, tabs, the refill and descend thresholds and the
+   batch rules are decided as plan_render decides them for the plain loop, with one difference: both BSDF flavours exist with
+   counters.  Nothing of this has been tuned for ray batches yet. */
+inline QueryPlan plan_radiance(const SceneTraits &t, uint64_t count, bool counters, const Knobs &kn) {
+    QueryPlan pl;
+    plan_loop_exits(tree_is_cache_resident(t.fast_tree_bytes, kn.cache_resident), kn, &pl.refill_below, &pl.descend_below);
     pl.counters = counters;
     pl.diffuse = t.diffuse_only && !kn.general_kernel;
     pl.tabs = (t.tab_flags & kPlanAllTabs) == kPlanAllTabs && kn.lds_tables != 0;
-    pl.grid = (unsigned int)((count + kPlanBlock - 1) / kPlanBlock < t.max_blocks ? (count + kPlanBlock - 1) / kPlanBlock : t.max_blocks);
+    pl.grid = query_grid(t, count);
     if (pl.grid == 0) pl.grid = 1;
-    const unsigned long long lanes = (unsigned long long)pl.grid * kPlanBlock;
-    pl.job_batch = kn.job_batch >= 0 ? (uint32_t)kn.job_batch : (count >= 96ull * lanes ? 128u : 64u);
-    const unsigned long long per_lane = kn.batch_tail >= 0 ? (unsigned long long)kn.batch_tail : 8ull * ((pl.job_batch + 63u) / 64u);
-    const unsigned long long tail = per_lane * lanes;
-    pl.batch_until = count > tail ? count - tail : 0ull;
+    plan_job_batches(count, (unsigned long long)pl.grid * kPlanBlock, kn, &pl.job_batch, &pl.batch_until);
     return pl;
 }
 

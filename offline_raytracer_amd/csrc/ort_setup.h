@@ -109,6 +109,32 @@ inline void ray_query_io(const Scene &scene, const float lo[3], const float hi[3
     memcpy(io->hi, hi, 3 * sizeof(float));
 }
 
+/* radiance queries: what radiance_lane reads behind hot.c besides the launch policy (View: RenderView of ort_lane.h) -- the
+   job space is one PIXEL-style job per ray; q is the query's ray_query_io with its rays set.  All pointers are the lanes' */
+template <typename View, typename IO>
+inline void radiance_view(const IO &q, const void *seeds, uint32_t spp, float rr, void *out, void *final_states, View *rv) {
+    rv->mode = PLAN_JOBS_PIXEL;
+    rv->spp = spp; rv->rr = rr;
+    rv->out = (float *)out;
+    rv->final_states = (uint32_t *)final_states;
+    rv->rays = q.rays;
+    rv->seeds = (const uint32_t *)seeds;
+    rv->ray_tree_spheres = q.tree_spheres; rv->ray_tree_quadrics = q.tree_quadrics; rv->ray_tree_boxes = q.tree_boxes;
+    memcpy(rv->ray_lo, q.lo, sizeof(rv->ray_lo));
+    memcpy(rv->ray_hi, q.hi, sizeof(rv->ray_hi));
+}
+
+/* the kernels' by-value argument (Hot: RenderHot of ort_lane.h): the few fields of rv every ray reads, and where the lanes find
+   the rest -- rv itself on the host, its copy in HBM on the device */
+template <typename Hot, typename View>
+inline Hot render_hot(const View &rv, const void *where) {
+    Hot hot{};
+    hot.mode = rv.mode; hot.W = rv.W; hot.H = rv.H; hot.rr = rv.rr;
+    hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
+    hot.c = (decltype(hot.c))where;
+    return hot;
+}
+
 /* occlusion queries: no shape of the scene carries material 0 (the early end of occluded_lane) */
 inline uint32_t all_mats_nonzero(const Tree &t) {
     for (const std::vector<uint32_t> *m : {&t.tri_mat, &t.box_mat, &t.cyl_mat, &t.sphere_mat})

@@ -227,6 +227,29 @@ def test_independent_of_batch_order_and_slicing(api, gpu_scene):
     assert again.tobytes() == ref.tobytes()
 
 
+def test_host_form_across_its_slice_boundary(api, gpu_scene):
+    """2^22 + 65 rays with a limit each: the host form stages rays, limits and bytes through the scene's buffers in slices of
+    2^22 rays, so this is two launches, the second of 65 rays from an offset into all three arrays.  Every byte equals the
+    device form's for the same rays in one launch, and the host form's for the two halves given separately (one slice each)."""
+    scene = gpu_scene("c3_bunny_room")
+    rng = np.random.default_rng(zlib.crc32(b"occluded slices"))
+    n = (1 << 22) + 65
+    rays = golden_like(rng, n)
+    hits, _ = torch_raycast(scene, rays)
+    tm = drawn_limits(rng, hits["t"])
+    ref, st_dev = torch_occluded(scene, rays, tm, counters=True, want_stats=True)
+    assert_bytes(ref, expected(hits["t"], hits["mat"], tm), "device form, one launch")
+    assert 0.1 < ref.mean() < 0.9 and ref[-65:].any() and not ref[-65:].all()  # neither slice can be had from a constant
+    got, st = scene.occluded(rays, tm, counters=True)
+    assert_bytes(got, ref, "host form, two slices")
+    assert st["rays"] == n == st_dev["rays"] and st["paths"] == 0
+    half = n // 2
+    a, st_a = scene.occluded(rays[:half], tm[:half], counters=True)
+    b, st_b = scene.occluded(rays[half:], tm[half:], counters=True)
+    assert np.concatenate([a, b]).tobytes() == ref.tobytes()
+    assert (st_a["rays"], st_b["rays"]) == (half, n - half)
+
+
 # ---- 8. the bound is used ------------------------------------------------------------------------------------------------
 def test_the_bound_cuts_the_traversal(api, gpu_scene):
     scene = gpu_scene("c3_bunny_room")

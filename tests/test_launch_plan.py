@@ -1,5 +1,5 @@
-"""The launch policy of the render call (csrc/ort_plan.h: plan_render) without a device, through tools/launch_plan: which kernel,
-which grid, which thresholds.  Expected values are the defaults and crossovers of DESIGN.md sections 5-6 as the code states
+"""The launch policy of the render call and of the ray queries (csrc/ort_plan.h: plan_render, plan_ray_query, plan_radiance)
+without a device, through tools/launch_plan: which kernel, which grid, which thresholds.  Expected values are the defaults and crossovers of DESIGN.md sections 5-6 as the code states
 them: SAH cost 0.09, 24 and 96 jobs per lane, 16 MB of fast tree, five waves for the all-lobes flavour and trees that leave the
 L2.  The GPU tests compare images of forced variants (ORT_WAVES5, ORT_EXCHANGE, ORT_WIDE, ...); the tests here are what says
 that each forcing really selects the kernel its test names, and which requests fall back silently."""
@@ -42,6 +42,11 @@ def plan(tool, env=None, **kw):
     r = subprocess.run([tool] + ["%s=%s" % kv for kv in args.items()], env=e, capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr
     return json.loads(r.stdout)
+
+
+def qplan(tool, query, count, env=None, **kw):
+    """the QueryPlan of a ray query over count rays on the same device; by default the scene of plan()"""
+    return plan(tool, env, query=query, count=count, **kw)
 
 
 def kernel(p):
@@ -268,9 +273,16 @@ def test_each_table_is_judged_alone_and_an_explicit_tab_flags_wins(tool):
 def test_the_scenes_of_the_gpu_table_tests_select_what_their_docstrings_name(tool):
     """tests/test_gpu_tables.py: the variants of tools/make_tablescene.py (counts relative to the caps the tool prints) and the
     kernels they take by themselves; ORT_LDS_TABLES=0 on the repository's own scenes.  The ray queries read TAB_PRO alone
-    (device_raycast): raycast_rays<*, false> where bit 1 of tab_flags is missing."""
+    (plan_ray_query): raycast_rays<*, false> and occluded_rays<*, false> where bit 1 of tab_flags is missing."""
     import table_scenes
     v = table_scenes.variants()
+    for query in ("raycast", "occluded"):
+        for name in ("mats_over", "mats_over_diffuse", "lights_over", "ref_limits", "beyond_ref"):  # past a cap the queries do not read
+            q = qplan(tool, query, 4000, materials=v[name]["materials"], lights=v[name]["lights"])
+            assert q["tab_flags"] & 1 and q["tab_flags"] != 11 and q["tabs"] == 1, (query, name)
+        for pro_boxes, tabs in ((40, 0), (21, 0), (20, 1)):
+            q = qplan(tool, query, 4000, materials=v["pro_over"]["materials"], lights=v["pro_over"]["lights"], pro_boxes=pro_boxes)
+            assert (q["tab_flags"] & 1, q["tabs"]) == (tabs, tabs), (query, pro_boxes)
     def names(kw, **more):
         args = dict(materials=kw["materials"], lights=kw["lights"], **more)
         return (kernel(plan(tool, FORCE_ALL, diffuse_only=0, **args, **SMALL)), kernel(plan(tool, FORCE_ALL, diffuse_only=1, **args, **SMALL)),
@@ -336,3 +348,99 @@ def test_implicit_job_spaces_fill_the_grid_they_need(tool, w, h):
     assert (p["job_count"], p["grid"]) == (0, 1)
     # five waves under ORT_BLOCKS_PER_CU keep the grid the upload fixed
     assert plan(tool, {"ORT_WAVES5": "1", "ORT_BLOCKS_PER_CU": "6"}, spp=1024, **HD)["grid"] == CU * 6
+
+
+# ---- the ray queries (plan_ray_query, plan_radiance): the job space is the ray array ---------------------------------------
+QUERY_KNOBS = ({"ORT_CACHE_RESIDENT": "0"}, {"ORT_CACHE_RESIDENT": "1"}, {"ORT_DESCEND_BELOW": "3"}, {"ORT_REFILL_BELOW": "5"}, {"ORT_JOB_BATCH": "7"},
+               {"ORT_BATCH_TAIL": "1"})
+CLOSEST = ["raycast", "occluded"]
+
+
+@pytest.mark.parametrize("query", CLOSEST)
+def test_ray_query_grid_and_batches(tool, query):
+    a, b, c = qplan(tool, query, 1), qplan(tool, query, 1000), qplan(tool, query, 10_000_000)
+    assert (a["grid"], a["batch_until"]) == (1, 0)
+    assert (b["grid"], b["batch_until"]) == (4, 0)
+    assert (c["grid"], c["job_batch"], c["batch_until"], c["refill_below"]) == (1024, 1024, 10_000_000 - 4 * LANES, 32)
+    for p in (a, b, c):
+        assert (p["job_batch"], p["refill_below"], p["diffuse"], p["counters"]) == (1024, 32, 0, 0)
+    assert qplan(tool, query, 1000, counters=1)["counters"] == 1
+    assert qplan(tool, query, 4 * LANES)["batch_until"] == 0 and qplan(tool, query, 4 * LANES + 1)["batch_until"] == 1
+    assert qplan(tool, query, 256 * 1024 + 1)["grid"] == 1024 and qplan(tool, query, 256 * 1023 + 1)["grid"] == 1024
+    assert qplan(tool, query, 256 * 1023)["grid"] == 1023
+
+
+@pytest.mark.parametrize("query", CLOSEST)
+def test_ray_query_descends_by_the_16_mb_line_and_reads_no_knob(tool, query):
+    for count in (1000, 10_000_000):
+        small, large = qplan(tool, query, count), qplan(tool, query, count, fast_tree_bytes=86 << 20)
+        assert small["descend_below"] == 8 and large["descend_below"] == 16
+        assert qplan(tool, query, count, fast_tree_bytes=16 << 20)["descend_below"] == 8
+        assert qplan(tool, query, count, fast_tree_bytes=(16 << 20) + 1)["descend_below"] == 16
+        for env in QUERY_KNOBS:
+            assert qplan(tool, query, count, env) == small, env
+            assert qplan(tool, query, count, env, fast_tree_bytes=86 << 20) == large, env
+
+
+@pytest.mark.parametrize("query", CLOSEST)
+def test_ray_query_tabs_is_the_prologues_table_alone(tool, query):
+    assert qplan(tool, query, 1000)["tabs"] == 1
+    for over in (dict(materials=49), dict(lights=65), dict(materials=300, lights=200)):  # past a cap, the prologue fits
+        q = qplan(tool, query, 1000, **over)
+        assert q["tab_flags"] & 1 and q["tab_flags"] != 11 and q["tabs"] == 1, over
+    q = qplan(tool, query, 1000, pro_boxes=21)
+    assert (q["tab_flags"], q["tabs"]) == (10, 0)
+    for flags in range(12):
+        if flags & 4 == 0:
+            assert qplan(tool, query, 1000, tab_flags=flags)["tabs"] == (flags & 1), flags
+    assert qplan(tool, query, 1000, {"ORT_LDS_TABLES": "0"})["tabs"] == 1
+    assert qplan(tool, query, 1000, {"ORT_LDS_TABLES": "0"}, pro_boxes=21)["tabs"] == 0
+    assert qplan(tool, query, 1000, {"ORT_KERNEL": "general"}, diffuse_only=1)["diffuse"] == 0  # no BSDF in these lanes
+
+
+def test_radiance_loop_exits_follow_the_tree_and_both_knobs(tool):
+    small, large = qplan(tool, "radiance", 1000), qplan(tool, "radiance", 1000, fast_tree_bytes=86 << 20)
+    assert (small["refill_below"], small["descend_below"]) == (16, 8)
+    assert (large["refill_below"], large["descend_below"]) == (32, 16)
+    forced = qplan(tool, "radiance", 1000, {"ORT_CACHE_RESIDENT": "0"})
+    assert (forced["refill_below"], forced["descend_below"]) == (32, 16)
+    forced = qplan(tool, "radiance", 1000, {"ORT_CACHE_RESIDENT": "1"}, fast_tree_bytes=86 << 20)
+    assert (forced["refill_below"], forced["descend_below"]) == (16, 8)
+    for v in VALUES:
+        p = qplan(tool, "radiance", 1000, {"ORT_REFILL_BELOW": v, "ORT_DESCEND_BELOW": v})
+        assert p["refill_below"] == min(max(int(v), 1), 64) and p["descend_below"] == min(int(v), 64)
+
+
+def test_radiance_batches_of_128_from_96_rays_per_lane(tool):
+    at, below = qplan(tool, "radiance", 96 * LANES), qplan(tool, "radiance", 96 * LANES - 1)
+    assert (at["grid"], at["job_batch"], at["batch_until"]) == (1024, 128, 80 * LANES)
+    assert (below["job_batch"], below["batch_until"]) == (64, 96 * LANES - 1 - 8 * LANES)
+    few = qplan(tool, "radiance", 1000)  # four workgroups, one ray per lane: nothing to batch
+    assert (few["grid"], few["job_batch"], few["batch_until"]) == (4, 64, 0)
+    assert qplan(tool, "radiance", 1)["grid"] == 1
+    p = qplan(tool, "radiance", 10_000_000, {"ORT_JOB_BATCH": "7", "ORT_BATCH_TAIL": "1"})
+    assert (p["job_batch"], p["batch_until"]) == (7, 10_000_000 - LANES)
+    p = qplan(tool, "radiance", 10_000_000, {"ORT_JOB_BATCH": "0"})
+    assert (p["job_batch"], p["batch_until"]) == (0, 10_000_000)
+    p = qplan(tool, "radiance", 10_000_000, {"ORT_JOB_BATCH": "256"})
+    assert (p["job_batch"], p["batch_until"]) == (256, 10_000_000 - 32 * LANES)
+
+
+def test_radiance_flavours(tool):
+    for counters in (0, 1):  # both BSDF flavours exist with counters
+        assert (qplan(tool, "radiance", 1000, counters=counters, diffuse_only=1)["diffuse"], qplan(tool, "radiance", 1000, counters=counters, diffuse_only=0)["diffuse"]) == (1, 0)
+        assert qplan(tool, "radiance", 1000, {"ORT_KERNEL": "general"}, counters=counters, diffuse_only=1)["diffuse"] == 0
+        assert qplan(tool, "radiance", 1000, counters=counters)["counters"] == counters
+    assert qplan(tool, "radiance", 1000)["tabs"] == 1
+    for missing in (1, 2, 8):  # all three tables, or none
+        assert qplan(tool, "radiance", 1000, tab_flags=11 & ~missing)["tabs"] == 0
+    assert qplan(tool, "radiance", 1000, materials=49)["tabs"] == 0 and qplan(tool, "radiance", 1000, lights=65)["tabs"] == 0
+    assert qplan(tool, "radiance", 1000, pro_boxes=21)["tabs"] == 0
+    assert qplan(tool, "radiance", 1000, {"ORT_LDS_TABLES": "0"})["tabs"] == 0
+
+
+def test_radiance_has_no_other_kernel_to_force(tool):
+    for count in (1000, 100 * LANES):
+        base = qplan(tool, "radiance", count, has_wide=1, sah_cost=0.5)
+        for env in ({"ORT_EXCHANGE": "1"}, {"ORT_WAVES5": "1"}, {"ORT_WIDE": "1"}, {"ORT_MODE": "wavefront"}, FORCE_ALL):
+            assert qplan(tool, "radiance", count, env, has_wide=1, sah_cost=0.5) == base, env

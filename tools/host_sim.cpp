@@ -197,18 +197,15 @@ static bool read_array(const char *path, std::vector<T> &v, size_t want, const c
     return true;
 }
 
-/* what ray_query_plan (ort_kernels.hip) puts behind hot.c, for one simulated lane per thread: no batches */
+/* the job space and thresholds launch_query (ort_kernels.hip) takes from its plan, chosen here for one simulated lane per
+   thread: no batches */
 static RenderHot query_hot(Sim &S, RenderView &rv, size_t count) {
     rv.job_count = count;
     rv.next_job = S.ctrl;
     rv.counters = S.ctrl + 1;
     rv.refill_below = 32;
     rv.descend_below = getenv("SIM_DESCEND_BELOW") ? atoi(getenv("SIM_DESCEND_BELOW")) : 8;
-    RenderHot hot{};
-    hot.mode = rv.mode; hot.rr = rv.rr;
-    hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
-    hot.c = &rv;
-    return hot;
+    return render_hot<RenderHot>(rv, &rv);
 }
 
 static int raycast_mode(char **a) { /* scn base rays.f32 hits.bin */
@@ -279,14 +276,9 @@ static int radiance_mode(char **a) { /* scn base rays.f32 seeds.u32 spp rr out.f
     scene_origin_box(*S.scene, lo, hi);
     RaycastIO q{};
     ray_query_io(*S.scene, lo, hi, &q);
-    RenderView rv{}; /* as launch_radiance (ort_kernels.hip) */
-    rv.mode = JOBS_PIXEL;
-    rv.spp = (uint32_t)strtoul(a[4], 0, 10); rv.rr = (float)atof(a[5]);
-    rv.out = out.data(); rv.final_states = states.data();
-    rv.rays = rays.data(); rv.seeds = seeds.data();
-    rv.ray_tree_spheres = q.tree_spheres; rv.ray_tree_quadrics = q.tree_quadrics; rv.ray_tree_boxes = q.tree_boxes;
-    memcpy(rv.ray_lo, q.lo, sizeof(rv.ray_lo));
-    memcpy(rv.ray_hi, q.hi, sizeof(rv.ray_hi));
+    q.rays = rays.data();
+    RenderView rv{};
+    radiance_view(q, seeds.data(), (uint32_t)strtoul(a[4], 0, 10), (float)atof(a[5]), out.data(), states.data(), &rv);
     const RenderHot hot = query_hot(S, rv, n);
     const bool diffuse_only = getenv("SIM_DIFFUSE") != nullptr; /* caller vouches for Ks = Kt = 0 */
     auto t0 = std::chrono::steady_clock::now();
@@ -346,9 +338,7 @@ static int views_mode(char **a) { /* scn base cams.f32 seeds.u32 W H spp policy 
     rv.out = out.data(); rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
     rv.refill_below = 12;
     rv.descend_below = getenv("SIM_DESCEND_BELOW") ? atoi(getenv("SIM_DESCEND_BELOW")) : 8;
-    RenderHot hot{};
-    hot.mode = rv.mode; hot.W = rv.W; hot.H = rv.H; hot.rr = rv.rr; hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
-    hot.c = &rv;
+    const RenderHot hot = render_hot<RenderHot>(rv, &rv);
     const bool diffuse_only = getenv("SIM_DIFFUSE") != nullptr;
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
@@ -433,9 +423,7 @@ int main(int argc, char **argv) {
         rv.mode = JOBS_EXPLICIT; rv.jobs = jobs.data(); rv.job_count = jobs.size(); rv.final_states = finals.data();
     }
     std::vector<uint32_t> pix_rng((size_t)W * H, 0);
-    RenderHot hot{};
-    hot.mode = rv.mode; hot.W = rv.W; hot.H = rv.H; hot.rr = rv.rr; hot.refill_below = rv.refill_below; hot.descend_below = rv.descend_below;
-    hot.c = &rv;
+    const RenderHot hot = render_hot<RenderHot>(rv, &rv);
     if (getenv("SIM_RAY_LOG")) { g_ray_log = fopen(getenv("SIM_RAY_LOG"), "wb"); g_dbg_x = atoi(getenv("SIM_X")); g_dbg_y = atoi(getenv("SIM_Y")); }
     if (getenv("SIM_DUMP_RNG")) { g_pixel_rng = pix_rng.data(); g_W = W; }
     auto t0 = std::chrono::steady_clock::now();

@@ -1,6 +1,8 @@
-/* Developer tool: what device_render would launch.  The launch policy (csrc/ort_plan.h) is arithmetic on a few facts about the
-   uploaded scene, the render parameters and the knobs, so it runs without a device:
+/* Developer tool: what device_render or a ray query would launch.  The launch policy (csrc/ort_plan.h) is arithmetic on a few
+   facts about the uploaded scene, the render parameters or the ray count and the knobs, so it runs without a device:
      [ORT_... knobs] tools/launch_plan key=value ...   ->   the plan, one JSON line
+   query=raycast|occluded|radiance count=N [counters=1]: the QueryPlan of that ray query over N rays (plan_ray_query,
+   plan_radiance) instead of a render's LaunchPlan.  Otherwise
    keys: the SceneTraits and ort_render_params fields by name, policy=pixel|chunk, counters=1, explicit_jobs=1 job_count=N,
    w5_layout_ok=0, views=N (the plan of an ort_render_views batch of N views; its fields are appended to the line); max_blocks
    defaults to what an upload on cu_count units fixes.  tab_flags, where not given, follows from
@@ -25,6 +27,8 @@ int main(int argc, char **argv) {
     unsigned long long job_count = 0;
     unsigned long view_count = 1;
     bool views_given = false;
+    const char *query = nullptr;
+    unsigned long long count = 0;
     for (int i = 1; i < argc; ++i) {
         const char *eq = strchr(argv[i], '=');
         const size_t n = eq ? (size_t)(eq - argv[i]) : 0;
@@ -57,11 +61,22 @@ int main(int argc, char **argv) {
         else if (is("explicit_jobs")) explicit_jobs = atoi(v) != 0;
         else if (is("job_count")) job_count = strtoull(v, nullptr, 0);
         else if (is("w5_layout_ok")) w5_layout_ok = atoi(v) != 0;
+        else if (is("query")) query = v;
+        else if (is("count")) count = strtoull(v, nullptr, 0);
         else if (is("views")) { view_count = strtoul(v, nullptr, 0); views_given = true; }
         else { fprintf(stderr, "launch_plan: unknown argument %s\n", argv[i]); return 2; }
     }
     if (!tab_flags_given) t.tab_flags = ort::table_fit_flags(materials, lights, (uint32_t)pro_boxes, (uint32_t)pro_spheres, (uint32_t)pro_cyls);
     if (!t.max_blocks) t.max_blocks = ort::upload_max_blocks(t.cu_count, kn);
+    if (query) {
+        const bool radiance = strcmp(query, "radiance") == 0, counters = (p.flags & ORT_RENDER_COUNTERS) != 0;
+        if ((!radiance && strcmp(query, "raycast") && strcmp(query, "occluded")) || count < 1) { fprintf(stderr, "launch_plan: query=raycast|occluded|radiance count=1...\n"); return 2; }
+        const ort::QueryPlan q = radiance ? ort::plan_radiance(t, count, counters, kn) : ort::plan_ray_query(t, count, counters);
+        printf("{\"query\": \"%s\", \"count\": %llu, \"counters\": %d, \"diffuse\": %d, \"tabs\": %d, \"grid\": %u, \"refill_below\": %d, \"descend_below\": %d, "
+               "\"job_batch\": %u, \"batch_until\": %llu, \"max_blocks\": %u, \"tab_flags\": %u}\n",
+               query, count, q.counters, q.diffuse, q.tabs, q.grid, q.refill_below, q.descend_below, q.job_batch, q.batch_until, t.max_blocks, t.tab_flags);
+        return 0;
+    }
     if (!explicit_jobs && p.policy == ORT_POLICY_CHUNK && p.chunk == 0) { fprintf(stderr, "launch_plan: chunk=0\n"); return 2; }
     if (views_given && (view_count < 1 || view_count > ORT_MAX_VIEWS || explicit_jobs)) { fprintf(stderr, "launch_plan: views=1..%u, implicit job spaces only\n", ORT_MAX_VIEWS); return 2; }
     const ort::LaunchPlan l = ort::plan_render(t, p, explicit_jobs, job_count, w5_layout_ok, kn, (uint32_t)view_count);
