@@ -374,6 +374,61 @@ int ort_radiance(ort_scene *scene, const float *rays, const uint32_t *seeds, uin
 int ort_radiance_device(ort_scene *scene, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr,
                         void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats);
 
+/* ---- adaptive radiance queries ----------------------------------------------------------
+ * ort_radiance with a sample count per ray: every ray is sampled until the estimated standard error of its mean luminance is
+ * small against the mean, between min_spp and max_spp samples.  A ray that looks at a light or into the dark stops at min_spp,
+ * a ray that sees light only after bounces runs on -- decided in the lane that traces it, with no trip to the host.
+ * Rays, seeds, the per-ray domain, rr, alignment, final_states, independence of count, order and slicing, and the host and the
+ * device form are exactly as for ort_radiance.  Per ray, every operation a separately rounded f32 operation (no FMA):
+ *  - Samples.  Samples are ort_radiance's samples.  Each is the reference's sample body from the ray, on one xorshift stream
+ *    that starts at seeds[i] (0 is taken as 1).
+ *  - Colour sum.  C is the running colour sum.  It starts at 0, and a sample adds at most one vector e to it: the emission term
+ *    of ray.cpp:1254-1259 or :1358-1371.
+ *  - Second moment.  Q is the running sum of squared sample luminance.  Whenever a vector e is added to C, compute
+ *    y = (0.2126f*e.x + 0.7152f*e.y) + 0.0722f*e.z, then Q = Q + y*y.  A sample that adds nothing leaves Q unchanged.
+ *  - When checks happen.  A check runs after sample n when n >= min_spp, n < max_spp and (n - min_spp) % check_every == 0.
+ *  - The check.
+ *        fn  = (float)n
+ *        Y   = (0.2126f*C.x + 0.7152f*C.y) + 0.0722f*C.z
+ *        m   = Y / fn
+ *        v   = Q / fn - m*m;   if (v < 0) v = 0;          (NaN stays NaN)
+ *        vm  = v / (fn - 1.0f)
+ *        a   = m < 0 ? -m : m;   b = a > floor ? a : floor
+ *        thr = tolerance * b
+ *        stop iff vm <= thr*thr                            (false, NaN included: keep sampling)
+ *  - Stopping.  The ray stops at the first check that says stop.  Otherwise it stops at n = max_spp.
+ *  - Outputs.  out_rgb[i] = C / (float)n, component by component (ray.cpp:1428 with n in place of spp); out_spp[i] = n;
+ *    out_m2[i] = Q; final_states[i] is the stream's state after sample n.  out_spp, out_m2 and final_states may each be NULL.
+ * What the rule means: it compares the estimated standard error of the mean luminance, sqrt(vm), against tolerance times the
+ * mean's magnitude, with floor standing in for the magnitude in the dark.  A caller rebuilds the estimate from the three
+ * outputs: n = out_spp[i]; the mean luminance m = luminance(out_rgb[i]) (Y / n up to one rounding); the sample variance
+ * v = max(0, out_m2[i] / n - m*m); the standard error of the mean sqrt(v / (n - 1)).  The sums themselves are C = out_rgb[i] * n
+ * (up to one rounding) and Q = out_m2[i].
+ * The known weakness: a ray that has seen no light in its first min_spp samples has v == 0 and stops black, though light might
+ * have reached it later (a small or far light seen only after bounces).  Callers pick min_spp for their scene.
+ * A ray outside the per-ray domain gets out_rgb = NaN NaN NaN, out_spp = 0, out_m2 = 0 and final_states[i] = seeds[i]; its
+ * neighbours are unaffected.
+ * Two identities: with min_spp == max_spp == n no check runs, and colours and final states are ort_radiance's at spp = n, bit for
+ * bit; with a tolerance so large that thr*thr is +inf every ray with finite Q stops at min_spp with ort_radiance's results at
+ * spp = min_spp.
+ * flags and stats as for ort_radiance; with ORT_RENDER_COUNTERS, paths is the number of samples taken: the sum of out_spp.
+ * count == 0 returns ORT_OK without a launch, whatever the other arguments.  Otherwise errors are reported before any device
+ * work, in ort_radiance's order with ad in the place of spp: ORT_ERR_INVALID (null scene, rays, seeds or out_rgb; misaligned
+ * rays (8 bytes), seeds, out_rgb, out_spp, out_m2 or final_states (4 bytes); ad == NULL, min_spp < 2, max_spp < min_spp, max_spp >
+ * 1 << 24 -- (float)n must be exact --, check_every == 0, tolerance or floor NaN, infinite or negative; rr outside [0, 1) or
+ * NaN), ORT_ERR_STATE (scene not committed), ORT_ERR_NO_DEVICE (not uploaded). */
+typedef struct { uint32_t min_spp, max_spp, check_every; float tolerance, floor; } ort_adaptive; /* 20 B */
+
+/* host rays and seeds in, host colours (and counts, second moments, states) out; synchronous, staged as ort_radiance */
+int ort_radiance_adaptive(ort_scene *scene, const float *rays, const uint32_t *seeds, uint64_t count, const ort_adaptive *ad, float rr,
+                          float *out_rgb, uint32_t *out_spp /* may be NULL */, float *out_m2 /* may be NULL */,
+                          uint32_t *final_states /* may be NULL */, uint32_t flags, ort_stats *stats);
+/* DEVICE pointers on the scene's device; enqueued on hip_stream (NULL = the default stream), returns without waiting unless
+   stats != NULL -- as ort_radiance_device */
+int ort_radiance_adaptive_device(ort_scene *scene, const void *d_rays, const void *d_seeds, uint64_t count, const ort_adaptive *ad, float rr,
+                                 void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, uint32_t flags, void *hip_stream,
+                                 ort_stats *stats);
+
 /* ---- multi-GPU: block sharding and the one collective -------------------------------------
  * Replaces main()'s shared-memory tile pool (macos_main.mm:565-671: eight pthreads, one queue, one framebuffer)
  * across the GPUs of a node: scene replicated, 8x8 blocks dealt round-robin, every rank renders its blocks into a

@@ -87,6 +87,15 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Adaptive(C.Structure):
+    """ort_adaptive: the stopping rule of an adaptive radiance query."""
+    _fields_ = [("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("check_every", C.c_uint32), ("tolerance", C.c_float),
+                ("floor", C.c_float)]
+
+
+assert C.sizeof(Adaptive) == 20
+
+
 class RenderParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32),
                 ("x1", C.c_int32), ("y1", C.c_int32), ("policy", C.c_int32), ("seed", C.c_uint32),
@@ -128,6 +137,7 @@ EXPORTS = [
     "ort_comm_unique_id", "ort_comm_create", "ort_comm_create_local", "ort_comm_destroy", "ort_gather_framebuffer",
     "ort_gather_framebuffer_local", "ort_raycast", "ort_raycast_device",
     "ort_occluded", "ort_occluded_device", "ort_radiance", "ort_radiance_device",
+    "ort_radiance_adaptive", "ort_radiance_adaptive_device",
     "ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes"]
 
 _lib = None
@@ -135,7 +145,7 @@ _lib = None
 
 def build_library():
     """Compile the HIP extension in-tree (hipcc --offload-arch=gfx950)."""
-    subprocess.check_call(["make", "-s", "-C", CSRC_DIR])
+    subprocess.check_call(["make", "-s", "-j3", "-C", CSRC_DIR])   # three kernel units, one job each
 
 
 def _share_hip_runtime_with_torch():
@@ -201,6 +211,11 @@ def lib():
                                    C.c_uint32, C.POINTER(Stats)]
         L.ort_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p,
                                           C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
+        L.ort_radiance_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Adaptive), C.c_float, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
+        L.ort_radiance_adaptive_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Adaptive), C.c_float,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                   C.POINTER(Stats)]
         L.ort_camera_from_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.POINTER(Camera)]
         L.ort_render_views.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
         L.ort_render_views_device.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
@@ -525,6 +540,48 @@ class Scene:
                                          C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
+    # -- adaptive radiance queries ----------------------------------------------------------
+    def radiance_adaptive(self, rays, seeds, min_spp, max_spp, tolerance, floor=0.05, check_every=4, rr=0.8, want_states=False,
+                          counters=False):
+        """radiance() with a sample count per ray: each ray is sampled until the estimated standard error of its mean
+        luminance is at most tolerance times the mean's magnitude (floor standing in for the magnitude in the dark), checked
+        after min_spp samples and then every check_every, and at most max_spp times (include/ort.h gives the rule operation
+        by operation).  A ray that saw no light in its first min_spp samples stops black: pick min_spp for the scene.
+        Returns (rgb: float32[N, 3], spp: uint32[N] samples taken, m2: float32[N] sum of squared sample luminance, stats
+        dict), with want_states (rgb, spp, m2, states, stats); a ray outside the domain gives NaN, 0, 0 and its seed."""
+        rays = np.ascontiguousarray(rays, dtype="<f4")
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must be an (N, 6) array of o.xyz d.xyz, got shape %s" % (rays.shape,))
+        seeds = np.asarray(seeds)
+        if seeds.shape != (len(rays),):
+            raise ValueError("seeds must be an (N,) array with N = %d, got shape %s" % (len(rays), seeds.shape))
+        seeds = np.ascontiguousarray(seeds.astype(np.int64) & 0xFFFFFFFF, dtype="<u4")
+        ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
+        out = np.zeros((len(rays), 3), "<f4")
+        spp = np.zeros(len(rays), "<u4")
+        m2 = np.zeros(len(rays), "<f4")
+        states = np.zeros(len(rays), "<u4") if want_states else None
+        st = Stats()
+        _check(lib().ort_radiance_adaptive(self.handle, rays.ctypes.data, seeds.ctypes.data, len(rays), C.byref(ad), float(rr),
+                                           out.ctypes.data, spp.ctypes.data, m2.ctypes.data,
+                                           states.ctypes.data if want_states else None, RENDER_COUNTERS if counters else 0,
+                                           C.byref(st)))
+        return (out, spp, m2, states, st.as_dict()) if want_states else (out, spp, m2, st.as_dict())
+
+    def radiance_adaptive_device(self, d_rays, d_seeds, n, min_spp, max_spp, tolerance, floor, check_every, rr, d_out, d_spp=0,
+                                 d_m2=0, d_states=0, stream=0, counters=False, want_stats=False):
+        """Device rays (n x 6 float32) and seeds (n uint32) -> device colours (n x 3 float32) and, where a pointer is given,
+        samples taken (n uint32), sums of squared sample luminance (n float32) and final states (n uint32): raw pointers on
+        the scene's device.  Enqueued on stream; waits only when want_stats (returns the stats dict)."""
+        st = Stats() if want_stats else None
+        ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
+        _check(lib().ort_radiance_adaptive_device(self.handle, C.c_void_p(d_rays), C.c_void_p(d_seeds), n, C.byref(ad), float(rr),
+                                                  C.c_void_p(d_out), C.c_void_p(d_spp) if d_spp else None,
+                                                  C.c_void_p(d_m2) if d_m2 else None, C.c_void_p(d_states) if d_states else None,
+                                                  RENDER_COUNTERS if counters else 0, C.c_void_p(stream) if stream else None,
+                                                  C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
     def triangle_of(self, index):
         """mesh-major triangle id (decode_prim of a triangle hit) -> (mesh, triangle within that mesh).  Accepts arrays."""
         first = getattr(self, "_tri_first", None)
@@ -561,6 +618,14 @@ class Scene:
         _check(lib().ort_tiled_raytrace_batch(self.handle, out.ctypes.data, width, height, jobs.ctypes.data, len(jobs),
                                               rr, finals.ctypes.data, C.byref(st)))
         return finals, st.as_dict()
+
+
+def _adaptive(min_spp, max_spp, check_every, tolerance, floor):
+    """-> Adaptive; counts that do not fit 32 bits are a ValueError here, everything else is the library's to judge"""
+    for name, v in (("min_spp", min_spp), ("max_spp", max_spp), ("check_every", check_every)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("%s must fit an unsigned 32-bit word, got %r" % (name, v))
+    return Adaptive(int(min_spp), int(max_spp), int(check_every), float(tolerance), float(floor))
 
 
 def decode_prim(prim):

@@ -4,6 +4,7 @@
  * lists, and dispatch to the HIP path in ort_kernels.hip.  There is no CPU render path:
  * every render entry point fails unless the scene is resident on a HIP device.
  */
+#include <float.h>
 #include <math.h>
 #include <string.h>
 
@@ -433,6 +434,34 @@ static int radiance_common(ort_scene *s, const float *h_rays, const void *d_rays
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
+/* adaptive radiance queries: as radiance_common, the stopping rule's parameters where spp stands there */
+static int radiance_adaptive_common(ort_scene *s, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, const ort_adaptive *ad, float rr,
+                                    float *h_out, void *d_out, uint32_t *h_spp, void *d_spp, float *h_m2, void *d_m2, uint32_t *h_states, void *d_states,
+                                    uint32_t flags, void *stream, ort_stats *stats) {
+    if (count == 0) return nothing_to_do(stats);
+    const void *rays = h_rays ? (const void *)h_rays : d_rays, *out_rgb = h_out ? (const void *)h_out : d_out,
+               *out_spp = h_spp ? (const void *)h_spp : d_spp, *out_m2 = h_m2 ? (const void *)h_m2 : d_m2,
+               *final_states = h_states ? (const void *)h_states : d_states;
+    if (!s) return fail(ORT_ERR_INVALID, "null scene");
+    if (!rays || !seeds || !out_rgb) return fail(ORT_ERR_INVALID, "null rays, seeds or out_rgb");
+    if ((uintptr_t)rays & 7u) return fail(ORT_ERR_INVALID, "rays must be 8-byte aligned");
+    if (((uintptr_t)seeds | (uintptr_t)out_rgb | (uintptr_t)out_spp | (uintptr_t)out_m2 | (uintptr_t)final_states) & 3u)
+        return fail(ORT_ERR_INVALID, "seeds, out_rgb, out_spp, out_m2 and final_states must be 4-byte aligned");
+    if (!ad) return fail(ORT_ERR_INVALID, "null ad (the adaptive parameters)");
+    if (ad->min_spp < 2u) return fail(ORT_ERR_INVALID, "min_spp must be >= 2: a variance needs two samples");
+    if (ad->max_spp < ad->min_spp) return fail(ORT_ERR_INVALID, "max_spp must be >= min_spp");
+    if (ad->max_spp > (1u << 24)) return fail(ORT_ERR_INVALID, "max_spp must be <= 1 << 24: a sample count must be exact in float");
+    if (ad->check_every == 0u) return fail(ORT_ERR_INVALID, "check_every must be >= 1");
+    if (!(ad->tolerance >= 0.0f && ad->tolerance <= FLT_MAX)) return fail(ORT_ERR_INVALID, "tolerance must be finite and >= 0");
+    if (!(ad->floor >= 0.0f && ad->floor <= FLT_MAX)) return fail(ORT_ERR_INVALID, "floor must be finite and >= 0");
+    if (!(rr >= 0.0f && rr < 1.0f)) return fail(ORT_ERR_INVALID, "rr must be in [0, 1): at 1 a path in a closed room never ends");
+    int rc = check_resident(s);
+    if (rc != ORT_OK) return rc;
+    std::string err;
+    rc = ort::device_radiance_adaptive(s, h_rays, d_rays, seeds, count, ad, rr, h_out, d_out, h_spp, d_spp, h_m2, d_m2, h_states, d_states, flags, stream, stats, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
 /* ---- a batch of views ---- */
 static int ort_camera_from_pose_impl(const float *p, const float *quat_xyzw, float height_ratio, int32_t width, int32_t height, ort_camera *out) {
     if (!p || !quat_xyzw || !out || width <= 0 || height <= 0) return fail(ORT_ERR_INVALID, "bad argument");
@@ -583,6 +612,8 @@ int ort_occluded(ort_scene *s, const float *rays, const float *tmax, uint64_t co
 int ort_occluded_device(ort_scene *s, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return occluded_common(s, nullptr, d_rays, d_tmax, count, nullptr, d_occluded, flags, hip_stream, stats); }); }
 int ort_radiance(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr, float *out_rgb, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_common(s, rays, nullptr, seeds, count, spp, rr, out_rgb, nullptr, final_states, nullptr, flags, nullptr, stats); }); }
 int ort_radiance_device(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_common(s, nullptr, d_rays, d_seeds, count, spp, rr, nullptr, d_out_rgb, nullptr, d_final_states, flags, hip_stream, stats); }); }
+int ort_radiance_adaptive(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, const ort_adaptive *ad, float rr, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_adaptive_common(s, rays, nullptr, seeds, count, ad, rr, out_rgb, nullptr, out_spp, nullptr, out_m2, nullptr, final_states, nullptr, flags, nullptr, stats); }); }
+int ort_radiance_adaptive_device(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, const ort_adaptive *ad, float rr, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_adaptive_common(s, nullptr, d_rays, d_seeds, count, ad, rr, nullptr, d_out_rgb, nullptr, d_out_spp, nullptr, d_out_m2, nullptr, d_final_states, flags, hip_stream, stats); }); }
 int ort_render_workspace_bytes(const ort_render_params *p, uint64_t *bytes) { return guarded([&]() { return ort_render_workspace_bytes_impl(p, bytes); }); }
 int ort_camera_from_pose(const float p[3], const float quat_xyzw[4], float height_ratio, int32_t width, int32_t height, ort_camera *out) { return guarded([&]() { return ort_camera_from_pose_impl(p, quat_xyzw, height_ratio, width, height, out); }); }
 int ort_render_views(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, float *out_rgb, ort_stats *stats) { return guarded([&]() { return render_views_common(s, p, views, view_count, nullptr, out_rgb, nullptr, stats); }); }

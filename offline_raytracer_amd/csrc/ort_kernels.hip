@@ -15,6 +15,11 @@
 void ort_launch_w5(int diffuse, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes);
 size_t ort_w5_sizeof_scene_view();
 size_t ort_w5_sizeof_render_hot();
+/* the adaptive radiance queries' kernels (ort_kernels_adaptive.hip) */
+void ort_launch_radiance_adaptive(int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes);
+size_t ort_adaptive_sizeof_scene_view();
+size_t ort_adaptive_sizeof_render_hot();
+size_t ort_adaptive_sizeof_render_view();
 
 namespace ort {
 
@@ -95,6 +100,7 @@ struct DeviceScene {
     DevBuf ray_in, hit_out;
     DevBuf tmax_in, occ_out; /* occlusion queries (device_occluded): the host path's limits and bytes */
     DevBuf seed_in, rad_out, rad_states; /* radiance queries (device_radiance): the host path's seeds, colours and final states */
+    DevBuf rad_spp, rad_m2; /* ... and (device_radiance_adaptive) sample counts and sums of squared luminance */
 };
 
 int device_count(int *n, std::string *err) {
@@ -271,7 +277,7 @@ static int launch_wavefront(DeviceScene *d, const SceneView &sv, const RenderVie
 }
 
 /* The path-trace kernel a plan names.  These sixteen variants, the six of a batch of views, the eight of the radiance queries
-   (device_radiance) and the two of ort_kernels_w5.hip are all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
+   (device_radiance), the eight of the adaptive ones (ort_kernels_adaptive.hip) and the two of ort_kernels_w5.hip are all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
    an error, not a fallback. */
 static int launch_path_tracer(const LaunchPlan &pl, hipStream_t stream, const SceneView &sv, const RenderHot &hot, std::string *err) {
     if (pl.views) { /* the plain loop with the camera table: counters | diffuse, tabs (implicit follows from both) */
@@ -752,6 +758,36 @@ int device_radiance(Scene *scene, const float *h_rays, const void *d_rays, const
     const QueryStream s[] = {{(void *)h_rays, &d->ray_in, 24u, false}, {(void *)seeds, &d->seed_in, 4u, false}, {h_out, &d->rad_out, 12u, true},
                              {h_states, &d->rad_states, 4u, true}};
     return run_sliced(d, count, kRadianceSlice, s, stream, err, [&](uint64_t n) { return launch(s[0].dev(), s[1].dev(), s[2].dev(), s[3].dev(), n); });
+}
+
+/* adaptive radiance: the same with the stopping rule's parameters (ad: checked by the caller) -> besides the colours and the
+   states, where asked for (null otherwise), every ray's sample count and its sum of squared sample luminance.  plan_radiance's
+   plan as it is; the kernels are ort_kernels_adaptive.hip's */
+int device_radiance_adaptive(Scene *scene, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, const ort_adaptive *ad, float rr,
+                             float *h_out, void *d_out, uint32_t *h_spp, void *d_spp, float *h_m2, void *d_m2, uint32_t *h_states, void *d_states,
+                             uint32_t flags, void *stream_v, ort_stats *stats, std::string *err) {
+    DeviceScene *d;
+    int rc;
+    if ((rc = begin_query(scene, stats, &d, err))) return rc;
+    if (ort_adaptive_sizeof_scene_view() != sizeof(SceneView) || ort_adaptive_sizeof_render_hot() != sizeof(RenderHot) ||
+        ort_adaptive_sizeof_render_view() != sizeof(RenderView)) {
+        *err = "internal: the adaptive kernels were built with other argument layouts";
+        return ORT_ERR_INTERNAL;
+    }
+    hipStream_t stream = (hipStream_t)stream_v;
+    const bool counters = (flags & ORT_RENDER_COUNTERS) != 0;
+    auto launch = [&](const void *rays, const void *ray_seeds, void *out, void *spp, void *m2, void *states, uint64_t n) {
+        RenderView rv{};
+        radiance_adaptive_view(ray_query_io(scene, d, rays), ray_seeds, *ad, rr, out, spp, m2, states, &rv);
+        return launch_query(scene, d, rv, n, true, counters, stream, stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
+            ort_launch_radiance_adaptive(pl.counters, pl.diffuse, pl.tabs, pl.grid, (void *)stream, &sv, &hot);
+        });
+    };
+    if (!h_rays) return launch(d_rays, seeds, d_out, d_spp, d_m2, d_states, count);
+    const QueryStream s[] = {{(void *)h_rays, &d->ray_in, 24u, false}, {(void *)seeds, &d->seed_in, 4u, false}, {h_out, &d->rad_out, 12u, true},
+                             {h_spp, &d->rad_spp, 4u, true}, {h_m2, &d->rad_m2, 4u, true}, {h_states, &d->rad_states, 4u, true}};
+    return run_sliced(d, count, kRadianceSlice, s, stream, err,
+                      [&](uint64_t n) { return launch(s[0].dev(), s[1].dev(), s[2].dev(), s[3].dev(), s[4].dev(), s[5].dev(), n); });
 }
 
 } // namespace ort

@@ -11,10 +11,11 @@
  * 2-wide tree of ort_tree.cpp with a per-lane stack whose first entries live in LDS
  * (column-per-lane, conflict-free) and whose tail spills to scratch.
  *
- * Included by two translation units: ort_kernels.hip (the library's kernels at four waves per SIMD, and the host side) and
- * ort_kernels_w5.hip (the plain-loop kernels at FIVE: 96 registers, 20 LDS stack entries, built with machine LICM off).
- * Same lane code, other limits (ORT_WAVES_PER_EU, ORT_LDS_STACK, ORT_SPILL_STACK); each unit compiles it in a namespace of its
- * own (ORT_NS), so that the two builds of one template are two symbols.  tools/host_sim.cpp compiles it for the host
+ * Included by three translation units: ort_kernels.hip (the library's kernels at four waves per SIMD, and the host side),
+ * ort_kernels_w5.hip (the plain-loop kernels at FIVE: 96 registers, 20 LDS stack entries, built with machine LICM off) and
+ * ort_kernels_adaptive.hip (the adaptive radiance queries' kernels, at the first unit's limits: a unit of their own so that they
+ * compile beside it).  Same lane code, other limits (ORT_WAVES_PER_EU, ORT_LDS_STACK, ORT_SPILL_STACK); each unit compiles it in a
+ * namespace of its own (ORT_NS), so that two builds of one template are two symbols.  tools/host_sim.cpp compiles it for the host
  * (ORT_HOST_SIM: one simulated lane).
  */
 #ifndef ORT_LANE_H
@@ -37,6 +38,8 @@
 
 #ifdef ORT_W5_TU
 #define ORT_NS ort_w5
+#elif defined(ORT_ADAPTIVE_TU)
+#define ORT_NS ort_ad
 #else
 #define ORT_NS ort
 #endif
@@ -175,6 +178,12 @@ struct RenderView {
     const uint32_t *seeds;
     uint32_t ray_tree_spheres, ray_tree_quadrics, ray_tree_boxes; /* what raycast_needs_exact reads (RaycastIO), for the primary rays */
     float ray_lo[3], ray_hi[3];
+    /* adaptive radiance queries (ort_radiance_adaptive; the radiance_adaptive_rays kernels): spp above is max_spp; a ray's sample
+       count and its sum of squared sample luminance go to ad_spp and ad_m2 (either may be null), job_count words each */
+    uint32_t ad_min_spp, ad_check_every;
+    float ad_tolerance, ad_floor;
+    uint32_t *ad_spp;
+    float *ad_m2;
 };
 
 /* ---- the order in which a CHUNK render issues its jobs ----------------------------------------------------------
@@ -624,6 +633,12 @@ struct PathState {
     bool primary = true;
 };
 
+/* what a lane of an adaptive radiance query keeps besides its PathState (produce_ray's ADAPT flag): no other kernel has these */
+struct AdaptState {
+    float q = 0;       /* Q: the running sum of squared sample luminance */
+    uint32_t next = 0; /* the sample count after which the next check runs; 0: a check has said stop */
+};
+
 struct HitState {
     float best_t = 0;
     V3 hit_n;
@@ -967,6 +982,23 @@ ORT_D unsigned long long *wave_job_pool(const RenderHot &rv, unsigned long long 
 ORT_D unsigned long long draw_job(const RenderHot &rv, unsigned long long *) { return ORT_NEXT_JOB(rv.c->next_job); }
 #endif
 
+/* adaptive radiance queries: the luminance of a colour, and the stopping rule after n samples with colour sum C and sum of
+   squared sample luminance Q, operation by operation as include/ort.h defines them (every operation rounded on its own: the
+   build contracts nothing).  The estimated standard error of the mean luminance against tolerance times the mean's magnitude,
+   lum_floor standing in for the magnitude in the dark; a NaN anywhere says "keep sampling" */
+ORT_D float adaptive_luminance(V3 e) { return (0.2126f * e.x + 0.7152f * e.y) + 0.0722f * e.z; }
+ORT_D bool adaptive_stop(V3 C, float Q, uint32_t n, float tolerance, float lum_floor) {
+    const float fn = (float)n;
+    const float m = adaptive_luminance(C) / fn;
+    float v = Q / fn - m * m;
+    if (v < 0.0f) v = 0.0f;
+    const float vm = v / (fn - 1.0f);
+    const float a = m < 0.0f ? -m : m;
+    const float b = a > lum_floor ? a : lum_floor;
+    const float thr = tolerance * b;
+    return vm <= thr * thr;
+}
+
 /* IMPLICIT: the caller vouches for an implicit job space (PIXEL / CHUNK policies: every job is one pixel, spp_u
    samples): the job's rect, its sample count and its index then need no registers of their own */
 /* VIEWS: a batch of views (ort_render_views): the job index names the view first, and the view's camera and seed come from
@@ -976,10 +1008,15 @@ ORT_D unsigned long long draw_job(const RenderHot &rv, unsigned long long *) { r
    with wo = -normalize(d) (ray.cpp:1240-1246 for a camera without an aperture), and no aperture angle is drawn; the job ends
    with 12 bytes at out + 3 j and its stream's state.  The ray is read again for every sample (24 bytes from L2 per path of
    hundreds of node tests) instead of held in six registers through the traversal loop; P.job_index | P.pxy << 32 is the ray index */
-template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool VIEWS = false, bool RAYS = false>
+/* ADAPT: adaptive radiance queries (ort_radiance_adaptive; with RAYS): spp_u is max_spp, and the job also ends at the first
+   check of the stopping rule (adaptive_stop) that says so.  A (the lane's AdaptState) holds the sum of squared sample
+   luminance and the sample count of the next check; the job writes its sample count and that sum besides the mean, which
+   divides by the samples taken.  Everything of it sits under if constexpr (ADAPT): the other kernels compile as without it */
+template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool VIEWS = false, bool RAYS = false, bool ADAPT = false>
 ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, Prof &pr,
                        float *focal_cache = nullptr, int focal_stride = 0, uint32_t spp_u = 0, uint32_t *late_flag = nullptr, bool no_new_job = false,
-                       unsigned long long *pool = nullptr) {
+                       unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
+    static_assert(!ADAPT || (RAYS && IMPLICIT), "the adaptive rule is built for the radiance queries");
     /* VIEWS: unused; every lane reads its view's camera where it needs it (load_view_camera) */
     const V3 cam_p = mk(sv.cam[0], sv.cam[1], sv.cam[2]);
     const V3 cam_x = mk(sv.cam[3], sv.cam[4], sv.cam[5]);
@@ -1013,7 +1050,10 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
             } else if (m.is_light) {
                 /* ray.cpp:1254-1259 (primary: unweighted, unchecked) / :1358-1371 (bounce: dropped if not finite) */
                 V3 e = P.primary ? m.emit : had(P.weight, m.emit);
-                if (P.primary || (!isnan3(e) && !isinf3(e))) P.color = add(P.color, e);
+                if (P.primary || (!isnan3(e) && !isinf3(e))) {
+                    P.color = add(P.color, e);
+                    if constexpr (ADAPT) { const float y = adaptive_luminance(e); A->q = A->q + y * y; }
+                }
                 alive = false;
             } else {
                 if (P.primary) {
@@ -1054,6 +1094,15 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
             } else {
                 P.sample++;
                 P.ps = PS_SAMPLE;
+                if constexpr (ADAPT) {
+                    /* a check runs after sample n when n >= min_spp, n < max_spp and (n - min_spp) % check_every == 0: A->next
+                       counts up to it, so nothing is divided per sample */
+                    if (P.sample == A->next && P.sample < spp_u) {
+                        const uint32_t after = A->next + rv.c->ad_check_every;
+                        A->next = after < A->next ? 0xffffffffu : after; /* beyond 2^32: never again */
+                        if (adaptive_stop(P.color, A->q, P.sample, rv.c->ad_tolerance, rv.c->ad_floor)) A->next = 0u;
+                    }
+                }
             }
             ORT_PHASE(pr, sv, 1, true);
         }
@@ -1062,14 +1111,20 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                Pixel write-back, next pixel / next job and the new camera ray all happen in this same
                pass, so the rest of the wave does not wait through a second trip round the loop. */
             const uint32_t job_spp = IMPLICIT ? spp_u : P.spp;
-            if (P.ps == PS_SAMPLE && P.sample == job_spp) {
+            bool job_ends = P.ps == PS_SAMPLE && P.sample == job_spp;
+            if constexpr (ADAPT) job_ends = P.ps == PS_SAMPLE && (P.sample == job_spp || A->next == 0u); /* ... or the rule said stop */
+            if (job_ends) {
                 /* ray.cpp:1428 */
-                V3 o = divs(P.color, (float)job_spp);
+                V3 o = divs(P.color, (float)(ADAPT ? P.sample : job_spp));
                 if constexpr (RAYS) {
                     const size_t ray = ((size_t)P.pxy << 32) | P.job_index;
                     float *p = rv.c->out + 3u * ray;
                     p[0] = o.x; p[1] = o.y; p[2] = o.z;
                     if (rv.c->final_states) rv.c->final_states[ray] = P.rng;
+                    if constexpr (ADAPT) {
+                        if (rv.c->ad_spp) rv.c->ad_spp[ray] = P.sample;
+                        if (rv.c->ad_m2) rv.c->ad_m2[ray] = A->q;
+                    }
                     P.ps = PS_NEED_JOB;
                 } else {
                 uint32_t px = P.pxy & 0xffffu, py = P.pxy >> 16;
@@ -1114,6 +1169,10 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                         float *p = rv.c->out + 3u * (size_t)j;
                         p[0] = p[1] = p[2] = om_bits_f32(0x7fc00000u);
                         if (rv.c->final_states) rv.c->final_states[j] = seed;
+                        if constexpr (ADAPT) {
+                            if (rv.c->ad_spp) rv.c->ad_spp[j] = 0u;
+                            if (rv.c->ad_m2) rv.c->ad_m2[j] = 0.0f;
+                        }
                         continue;
                     }
                     P.job_index = (uint32_t)j;
@@ -1179,6 +1238,7 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 P.color = mk(0, 0, 0); /* ray.cpp:1211 */
                 P.sample = 0;
                 P.ps = PS_SAMPLE;
+                if constexpr (ADAPT) { A->q = 0.0f; A->next = rv.c->ad_min_spp; }
                 if (focal_cache) { /* the pixel's focal point, once per pixel (persistent kernel: three floats of LDS per lane) */
                     V3 f;
                     if constexpr (VIEWS) f = view_focal_point(rv, P.pxy, load_view_camera(rv, P.job_index));
@@ -2059,7 +2119,7 @@ pt_persistent_x(SceneView sv, RenderHot rv) {
     }
 }
 
-#ifndef ORT_W5_TU /* the five-waves unit only needs the path-trace kernels */
+#if !defined(ORT_W5_TU) && !defined(ORT_ADAPTIVE_TU) /* the five-waves unit only needs the path-trace kernels, the adaptive one its own */
 /* wavefront kernels: fixed-size grids, grid-stride over the slots */
 template <bool COUNTERS>
 __global__ void __launch_bounds__(kBlock) wf_shade(SceneView sv, RenderHot rv, WfView wf, int count_active) {
@@ -2117,7 +2177,7 @@ __global__ void combine_chunks_views(RenderHot rv) {
     combine_pixel(rv, idx % per_view, (uint32_t)(idx / per_view));
 }
 
-#endif /* !ORT_W5_TU */
+#endif /* !ORT_W5_TU && !ORT_ADAPTIVE_TU */
 #endif /* !ORT_HOST_SIM */
 
 #ifndef ORT_W5_TU
@@ -2337,13 +2397,15 @@ occluded_rays(SceneView sv, RenderHot rv, OccludedIO io) {
  * ort_raycast do (inside the per-ray domain: an axis-aligned direction with boxes in the tree, an origin outside the scene's
  * box with quadrics in it) and then skip the fast traversal: resolve_hit re-casts them exactly.  Bounce rays start at hits and
  * need no rule, as in the render.  No ray exchange, no five-waves build, no wide tree, no wavefront mode (ort_plan.h). */
-template <bool COUNTERS, bool DIFFUSE, bool TABS>
+/* ADAPT: the adaptive query (ort_radiance_adaptive): the same loop, the job ending where produce_ray's stopping rule says */
+template <bool COUNTERS, bool DIFFUSE, bool TABS, bool ADAPT = false>
 ORT_D void radiance_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, const int tid, const uint32_t lane_id,
                          unsigned long long *pool) {
     uint32_t spill[kSpillStack];
     const uint32_t spp_u = rv.c->spp;
     Prof pr;
     PathState P;
+    [[maybe_unused]] AdaptState A; /* ADAPT only */
     HitState h;
     Trav T;
     Counters c;
@@ -2351,6 +2413,8 @@ ORT_D void radiance_lane(const SceneView &sv, const RenderHot &rv, const float4 
     for (;;) {
         if (!tracing) {
             if (P.ps == PS_HIT) resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+            if constexpr (ADAPT) tracing = produce_ray<COUNTERS, DIFFUSE, TABS, true, false, true, true>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool, &A);
+            else
             tracing = produce_ray<COUNTERS, DIFFUSE, TABS, true, false, true>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool);
             if (tracing) {
                 begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
@@ -2382,6 +2446,17 @@ radiance_rays(SceneView sv, RenderHot rv) {
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
     radiance_lane<COUNTERS, DIFFUSE, TABS>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+}
+
+/* the adaptive query's eight, as radiance_rays */
+template <bool COUNTERS, bool DIFFUSE, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+radiance_adaptive_rays(SceneView sv, RenderHot rv) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    if (TABS) fill_tab(sv, lds_tab);
+    radiance_lane<COUNTERS, DIFFUSE, TABS, true>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 #endif
 

@@ -228,6 +228,11 @@ int device_occluded(Scene *scene, const float *h_rays, const void *d_rays, const
    seeds a device pointer, enqueued on stream); the states may be null */
 int device_radiance(Scene *scene, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, uint32_t spp, float rr, float *h_out,
                     void *d_out, uint32_t *h_states, void *d_states, uint32_t flags, void *stream, ort_stats *stats, std::string *err);
+/* adaptive radiance queries: the same, with the stopping rule's parameters and two more optional outputs (samples taken, sum of
+   squared sample luminance) */
+int device_radiance_adaptive(Scene *scene, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, const ort_adaptive *ad, float rr,
+                             float *h_out, void *d_out, uint32_t *h_spp, void *d_spp, float *h_m2, void *d_m2, uint32_t *h_states, void *d_states,
+                             uint32_t flags, void *stream, ort_stats *stats, std::string *err);
 /* ort_comm.cpp */
 struct Comm;
 uint64_t comm_shard_blocks(int32_t w, int32_t h, uint32_t index, uint32_t count);

@@ -124,6 +124,18 @@ inline void radiance_view(const IO &q, const void *seeds, uint32_t spp, float rr
     memcpy(rv->ray_hi, q.hi, sizeof(rv->ray_hi));
 }
 
+/* adaptive radiance queries: radiance_view with max_spp for spp, then what the stopping rule reads and where a ray's sample
+   count and sum of squared luminance go (either may be null) */
+template <typename View, typename IO>
+inline void radiance_adaptive_view(const IO &q, const void *seeds, const ort_adaptive &ad, float rr, void *out, void *out_spp, void *out_m2,
+                                   void *final_states, View *rv) {
+    radiance_view(q, seeds, ad.max_spp, rr, out, final_states, rv);
+    rv->ad_min_spp = ad.min_spp; rv->ad_check_every = ad.check_every;
+    rv->ad_tolerance = ad.tolerance; rv->ad_floor = ad.floor;
+    rv->ad_spp = (uint32_t *)out_spp;
+    rv->ad_m2 = (float *)out_m2;
+}
+
 /* the kernels' by-value argument (Hot: RenderHot of ort_lane.h): the few fields of rv every ray reads, and where the lanes find
    the rest -- rv itself on the host, its copy in HBM on the device */
 template <typename Hot, typename View>

@@ -11,7 +11,7 @@
  * kernel.  The library never loads, links or runs it: the render call has no CPU fallback
  * (tests/test_host.py holds its image against the oracle; nothing else uses it).
  *
- * The ray-query lanes (raycast_lane, occluded_lane, radiance_lane) and the batch-of-views flavour of pt_lane run here too, on
+ * The ray-query lanes (raycast_lane, occluded_lane, radiance_lane with and without its adaptive rule) and the batch-of-views flavour of pt_lane run here too, on
  * the tables the product's own host code packs (ort_setup.h): tests/test_query_lanes_host.py holds them against the
  * reference's answers and the oracle, tests/test_host_sanitizers.py runs the same binary built with ASan + UBSan
  * (make host_sim_san).
@@ -21,6 +21,7 @@
  *   or: host_sim --raycast scn base rays.f32 hits.bin                        (ort_hit records)
  *   or: host_sim --occluded scn base rays.f32 tmax.f32|- out.u8
  *   or: host_sim --radiance scn base rays.f32 seeds.u32 spp rr out.f32 states.u32
+ *   or: host_sim --radiance-adaptive scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
  *   or: host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32   (cams: p, x, y, z axes, 12 floats a view)
  * All files raw little-endian.  SIM_TABS=1: the TABS = true lane code, on a heap copy of the LDS tables' image.
  */
@@ -295,6 +296,47 @@ static int radiance_mode(char **a) { /* scn base rays.f32 seeds.u32 spp rr out.f
     return write_bytes(a[6], out.data(), 12 * n) && write_bytes(a[7], states.data(), 4 * n) ? 0 : 1;
 }
 
+/* the adaptive query: radiance_lane<..., ADAPT>; tolerance and floor are read as float bits when written 0x........ (a test can
+   pass any float exactly), as decimals otherwise */
+static float float_arg(const char *s) {
+    if (s[0] == '0' && (s[1] == 'x' || s[1] == 'X')) { const uint32_t b = (uint32_t)strtoul(s, 0, 16); float f; memcpy(&f, &b, 4); return f; }
+    return (float)atof(s);
+}
+static int radiance_adaptive_mode(char **a) { /* scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32 */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
+    size_t n = 0;
+    std::vector<float2> rays;
+    std::vector<uint32_t> seeds;
+    if (!read_rays(a[2], rays, &n) || !read_array(a[3], seeds, n, "seeds")) return 1;
+    ort_adaptive ad{(uint32_t)strtoul(a[4], 0, 10), (uint32_t)strtoul(a[5], 0, 10), (uint32_t)strtoul(a[6], 0, 10), float_arg(a[7]), float_arg(a[8])};
+    if (ad.min_spp < 2u || ad.max_spp < ad.min_spp || ad.max_spp > (1u << 24) || ad.check_every == 0u) { fprintf(stderr, "bad adaptive parameters\n"); return 1; }
+    std::vector<float> out(3 * n, 0.0f), m2(n, -1.0f);
+    std::vector<uint32_t> spp(n, 0xeeeeeeeeu), states(n, 0u); /* every word is written: one that is not keeps its filler */
+    float lo[3], hi[3];
+    scene_origin_box(*S.scene, lo, hi);
+    RaycastIO q{};
+    ray_query_io(*S.scene, lo, hi, &q);
+    q.rays = rays.data();
+    RenderView rv{};
+    radiance_adaptive_view(q, seeds.data(), ad, (float)atof(a[9]), out.data(), spp.data(), m2.data(), states.data(), &rv);
+    const RenderHot hot = query_hot(S, rv, n);
+    const bool diffuse_only = getenv("SIM_DIFFUSE") != nullptr; /* caller vouches for Ks = Kt = 0 */
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
+        if (diffuse_only) {
+            if (S.tab) radiance_lane<true, true, true, true>(sv, hot, S.tab, stack, 0, w, nullptr);
+            else radiance_lane<true, true, false, true>(sv, hot, nullptr, stack, 0, w, nullptr);
+        } else {
+            if (S.tab) radiance_lane<true, false, true, true>(sv, hot, S.tab, stack, 0, w, nullptr);
+            else radiance_lane<true, false, false, true>(sv, hot, nullptr, stack, 0, w, nullptr);
+        }
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return write_bytes(a[10], out.data(), 12 * n) && write_bytes(a[11], spp.data(), 4 * n) && write_bytes(a[12], m2.data(), 4 * n) &&
+           write_bytes(a[13], states.data(), 4 * n) ? 0 : 1;
+}
+
 static int views_mode(char **a) { /* scn base cams.f32 seeds.u32 W H spp policy chunk out.f32 */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
@@ -363,6 +405,7 @@ int main(int argc, char **argv) {
     if (argc == 6 && mode == "--raycast") return raycast_mode(argv + 2);
     if (argc == 7 && mode == "--occluded") return occluded_mode(argv + 2);
     if (argc == 10 && mode == "--radiance") return radiance_mode(argv + 2);
+    if (argc == 16 && mode == "--radiance-adaptive") return radiance_adaptive_mode(argv + 2);
     if (argc == 12 && mode == "--views") return views_mode(argv + 2);
     if (argc < 10 || mode.rfind("--", 0) == 0) {
         fprintf(stderr, "usage: host_sim scn base W H spp seed policy chunk out.f32 [shard_index shard_count]\n"
@@ -370,6 +413,7 @@ int main(int argc, char **argv) {
                         "       host_sim --raycast scn base rays.f32 hits.bin\n"
                         "       host_sim --occluded scn base rays.f32 tmax.f32|- out.u8\n"
                         "       host_sim --radiance scn base rays.f32 seeds.u32 spp rr out.f32 states.u32\n"
+                        "       host_sim --radiance-adaptive scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
                         "       host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32\n");
         return 2;
     }

@@ -9,6 +9,7 @@ int device_unit_eval(int, const void *, uint32_t, float *, std::string *err) { *
 int device_raycast(Scene *, const float *, const void *, uint64_t, ort_hit *, void *, uint32_t, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_occluded(Scene *, const float *, const void *, const void *, uint64_t, uint8_t *, void *, uint32_t, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_radiance(Scene *, const float *, const void *, const void *, uint64_t, uint32_t, float, float *, void *, uint32_t *, void *, uint32_t, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
+int device_radiance_adaptive(Scene *, const float *, const void *, const void *, uint64_t, const ort_adaptive *, float, float *, void *, uint32_t *, void *, float *, void *, uint32_t *, void *, uint32_t, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 }
 /* the multi-GPU entry points of ort_api.cpp (ort_comm.cpp is HIP code): never called by the harness */
 namespace ort {
