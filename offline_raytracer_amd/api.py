@@ -196,30 +196,20 @@ def lib():
                                          C.POINTER(C.c_uint64)]
         L.ort_tiled_raytrace_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32,
                                                C.c_float, C.c_void_p, C.POINTER(Stats)]
-        L.ort_render_image.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.POINTER(Stats)]
-        L.ort_render_image_device.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_void_p,
-                                              C.POINTER(Stats)]
         L.ort_render_workspace_bytes.argtypes = [C.POINTER(RenderParams), C.POINTER(C.c_uint64)]
         L.ort_unit_eval_device.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
-        L.ort_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
-        L.ort_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
-                                         C.POINTER(Stats)]
-        L.ort_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
-        L.ort_occluded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
-                                          C.POINTER(Stats)]
-        L.ort_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p,
-                                   C.c_uint32, C.POINTER(Stats)]
-        L.ort_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p,
-                                          C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
-        L.ort_radiance_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Adaptive), C.c_float, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
-        L.ort_radiance_adaptive_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Adaptive), C.c_float,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
-                                                   C.POINTER(Stats)]
+        # host form / device form pairs: the device form takes the same arguments and a stream before the stats
+        vp, stats = C.c_void_p, C.POINTER(Stats)
+        for name, argtypes in (
+                ("ort_render_image", [vp, C.POINTER(RenderParams), vp, stats]),
+                ("ort_render_views", [vp, C.POINTER(RenderParams), vp, C.c_uint32, vp, stats]),
+                ("ort_raycast", [vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
+                ("ort_occluded", [vp, vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
+                ("ort_radiance", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_float, vp, vp, C.c_uint32, stats]),
+                ("ort_radiance_adaptive", [vp, vp, vp, C.c_uint64, C.POINTER(Adaptive), C.c_float, vp, vp, vp, vp, C.c_uint32, stats])):
+            getattr(L, name).argtypes = argtypes
+            getattr(L, name + "_device").argtypes = argtypes[:-1] + [vp, stats]
         L.ort_camera_from_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.POINTER(Camera)]
-        L.ort_render_views.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
-        L.ort_render_views_device.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                              C.POINTER(Stats)]
         L.ort_render_views_workspace_bytes.argtypes = [C.POINTER(RenderParams), C.c_uint32, C.POINTER(C.c_uint64)]
         L.ort_rgbe.restype = C.c_uint32
         L.ort_rgbe.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -265,6 +255,37 @@ def camera_from_pose(p, quat_xyzw, ratio, width, height):
     cam = Camera()
     _check(lib().ort_camera_from_pose(p.ctypes.data, q.ctypes.data, float(ratio), int(width), int(height), C.byref(cam)))
     return np.array([[v.x, v.y, v.z] for v in (cam.p, cam.x_axis, cam.y_axis, cam.z_axis)], dtype="<f4")
+
+
+def _rays(rays):
+    """-> (N, 6) float32, C-contiguous; ValueError on any other shape"""
+    rays = np.ascontiguousarray(rays, dtype="<f4")
+    if rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError("rays must be an (N, 6) array of o.xyz d.xyz, got shape %s" % (rays.shape,))
+    return rays
+
+
+def _seeds(seeds, n):
+    """-> uint32[n] (any integers, taken modulo 2^32); ValueError on any other shape"""
+    seeds = np.asarray(seeds)
+    if seeds.shape != (n,):
+        raise ValueError("seeds must be an (N,) array with N = %d, got shape %s" % (n, seeds.shape))
+    return np.ascontiguousarray(seeds.astype(np.int64) & 0xFFFFFFFF, dtype="<u4")
+
+
+def _ptr(p):
+    """a raw device pointer or a stream -> the ctypes argument; 0 and None are NULL"""
+    return C.c_void_p(p) if p else None
+
+
+def _flags(counters):
+    return RENDER_COUNTERS if counters else 0
+
+
+def _stats(want=True):
+    """-> (the ort_stats * argument of a call, what to return after it): a fresh struct and its as_dict, or NULL and None"""
+    st = Stats() if want else None
+    return (C.byref(st), st.as_dict) if want else (None, lambda: None)
 
 
 def _views(cameras, seeds):
@@ -410,7 +431,7 @@ class Scene:
         if pol == POLICY_CHUNK and not chunk:
             chunk = spp
         return RenderParams(width, height, x0, y0, x1, y1, pol, seed & 0xFFFFFFFF, spp, chunk, rr,
-                            (RENDER_COUNTERS if counters else 0) | (RENDER_PACKED if packed else 0), shard[0], shard[1])
+                            _flags(counters) | (RENDER_PACKED if packed else 0), shard[0], shard[1])
 
     def render(self, width, height, spp, seed, policy="chunk", chunk=0, rect=None, rr=0.8, counters=False,
                shard=(0, 1), out=None):
@@ -418,17 +439,15 @@ class Scene:
         p = self.params(width, height, spp, seed, policy, chunk, rect, rr, counters, shard)
         if out is None:
             out = np.zeros((height, width, 3), dtype="<f4")
-        st = Stats()
-        _check(lib().ort_render_image(self.handle, C.byref(p), out.ctypes.data, C.byref(st)))
-        return out, st.as_dict()
+        st, stats = _stats()
+        _check(lib().ort_render_image(self.handle, C.byref(p), out.ctypes.data, st))
+        return out, stats()
 
     def render_device(self, d_out_ptr, params, stream=None, want_stats=False):
         """Device framebuffer (raw device pointer, e.g. torch_tensor.data_ptr())."""
-        st = Stats() if want_stats else None
-        _check(lib().ort_render_image_device(self.handle, C.byref(params), C.c_void_p(d_out_ptr),
-                                             C.c_void_p(stream) if stream else None,
-                                             C.byref(st) if want_stats else None))
-        return st.as_dict() if want_stats else None
+        st, stats = _stats(want_stats)
+        _check(lib().ort_render_image_device(self.handle, C.byref(params), _ptr(d_out_ptr), _ptr(stream), st))
+        return stats()
 
     # -- a batch of camera views in one launch ----------------------------------------------
     def render_views(self, cameras, seeds, width, height, spp, policy="chunk", chunk=0, rect=None, rr=0.8, counters=False,
@@ -442,40 +461,34 @@ class Scene:
         if out.shape != (len(views), height, width, 3) or out.dtype != np.dtype("<f4") or not out.flags.c_contiguous:
             raise ValueError("out must be a C-contiguous float32 array of shape %s" % ((len(views), height, width, 3),))
         p = self.params(width, height, spp, 0, policy, chunk, rect, rr, counters)
-        st = Stats()
-        _check(lib().ort_render_views(self.handle, C.byref(p), views.ctypes.data, len(views), out.ctypes.data, C.byref(st)))
-        return out, st.as_dict()
+        st, stats = _stats()
+        _check(lib().ort_render_views(self.handle, C.byref(p), views.ctypes.data, len(views), out.ctypes.data, st))
+        return out, stats()
 
     def render_views_device(self, d_out_ptr, params, cameras, seeds, stream=None, want_stats=False):
         """The same into a device buffer of V frames (raw device pointer, e.g. a (V, H, W, 3) torch tensor's data_ptr()).
         Enqueued on stream; waits only when want_stats (returns the stats dict).  params.seed is ignored."""
         views = _views(cameras, seeds)
-        st = Stats() if want_stats else None
-        _check(lib().ort_render_views_device(self.handle, C.byref(params), views.ctypes.data, len(views), C.c_void_p(d_out_ptr),
-                                             C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
-        return st.as_dict() if want_stats else None
+        st, stats = _stats(want_stats)
+        _check(lib().ort_render_views_device(self.handle, C.byref(params), views.ctypes.data, len(views), _ptr(d_out_ptr), _ptr(stream), st))
+        return stats()
 
     # -- closest-hit ray queries -----------------------------------------------------------
     def raycast(self, rays, counters=False):
         """Closest hit of each ray (raycast_top_most_node, ray.cpp:1165).  rays: (N, 6) float32 o.xyz d.xyz (d need
         not be unit length).  Returns (hits: HIT_DTYPE[N], stats dict); synchronous."""
-        rays = np.ascontiguousarray(rays, dtype="<f4")
-        if rays.ndim != 2 or rays.shape[1] != 6:
-            raise ValueError("rays must be an (N, 6) array of o.xyz d.xyz, got shape %s" % (rays.shape,))
+        rays = _rays(rays)
         hits = np.zeros(len(rays), HIT_DTYPE)
-        st = Stats()
-        _check(lib().ort_raycast(self.handle, rays.ctypes.data, len(rays), hits.ctypes.data,
-                                 RENDER_COUNTERS if counters else 0, C.byref(st)))
-        return hits, st.as_dict()
+        st, stats = _stats()
+        _check(lib().ort_raycast(self.handle, rays.ctypes.data, len(rays), hits.ctypes.data, _flags(counters), st))
+        return hits, stats()
 
     def raycast_device(self, d_rays_ptr, count, d_hits_ptr, stream=None, counters=False, want_stats=False):
         """Device rays (count x 6 float32) -> device hits (count x 24 B, HIT_DTYPE), raw pointers on the scene's device,
         e.g. torch tensors' data_ptr().  Enqueued on stream; waits only when want_stats (returns the stats dict)."""
-        st = Stats() if want_stats else None
-        _check(lib().ort_raycast_device(self.handle, C.c_void_p(d_rays_ptr), count, C.c_void_p(d_hits_ptr),
-                                        RENDER_COUNTERS if counters else 0, C.c_void_p(stream) if stream else None,
-                                        C.byref(st) if want_stats else None))
-        return st.as_dict() if want_stats else None
+        st, stats = _stats(want_stats)
+        _check(lib().ort_raycast_device(self.handle, _ptr(d_rays_ptr), count, _ptr(d_hits_ptr), _flags(counters), _ptr(stream), st))
+        return stats()
 
     # -- occlusion ray queries -------------------------------------------------------------
     def occluded(self, rays, tmax=None, counters=False):
@@ -483,9 +496,7 @@ class Scene:
         raycast returns for rays[i]; the comparison is the IEEE one (NaN, zero and negative limits give False).  rays:
         (N, 6) float32 o.xyz d.xyz; tmax: None (no limit), a scalar (broadcast) or an (N,) array, in units of the ray
         parameter.  Returns (occluded: bool[N], stats dict); synchronous."""
-        rays = np.ascontiguousarray(rays, dtype="<f4")
-        if rays.ndim != 2 or rays.shape[1] != 6:
-            raise ValueError("rays must be an (N, 6) array of o.xyz d.xyz, got shape %s" % (rays.shape,))
+        rays = _rays(rays)
         if tmax is not None:
             tmax = np.asarray(tmax, dtype="<f4")
             if tmax.ndim == 0:
@@ -494,19 +505,18 @@ class Scene:
                 raise ValueError("tmax must be a scalar or an (N,) array with N = %d, got shape %s" % (len(rays), tmax.shape))
             tmax = np.ascontiguousarray(tmax)
         out = np.zeros(len(rays), np.bool_)
-        st = Stats()
+        st, stats = _stats()
         _check(lib().ort_occluded(self.handle, rays.ctypes.data, tmax.ctypes.data if tmax is not None else None, len(rays),
-                                  out.ctypes.data, RENDER_COUNTERS if counters else 0, C.byref(st)))
-        return out, st.as_dict()
+                                  out.ctypes.data, _flags(counters), st))
+        return out, stats()
 
     def occluded_device(self, d_rays_ptr, d_tmax_ptr, count, d_out_ptr, stream=None, counters=False, want_stats=False):
         """Device rays (count x 6 float32) and limits (count float32, or None: no limit) -> device bytes (count, each 0 or
         1: a torch.bool tensor), raw pointers on the scene's device.  Enqueued on stream; waits only when want_stats."""
-        st = Stats() if want_stats else None
-        _check(lib().ort_occluded_device(self.handle, C.c_void_p(d_rays_ptr), C.c_void_p(d_tmax_ptr) if d_tmax_ptr else None,
-                                         count, C.c_void_p(d_out_ptr), RENDER_COUNTERS if counters else 0,
-                                         C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
-        return st.as_dict() if want_stats else None
+        st, stats = _stats(want_stats)
+        _check(lib().ort_occluded_device(self.handle, _ptr(d_rays_ptr), _ptr(d_tmax_ptr), count, _ptr(d_out_ptr), _flags(counters),
+                                         _ptr(stream), st))
+        return stats()
 
     # -- radiance queries -----------------------------------------------------------------
     def radiance(self, rays, seeds, spp, rr=0.8, want_states=False, counters=False):
@@ -515,30 +525,23 @@ class Scene:
         (|d|^2 within [0.999, 1.001], all components finite; any other ray gives NaN NaN NaN and its seed back); seeds: (N,)
         uint32, e.g. job_seeds(master, N).  Returns (rgb: float32[N, 3], stats dict), with want_states (rgb, states:
         uint32[N], stats dict); synchronous."""
-        rays = np.ascontiguousarray(rays, dtype="<f4")
-        if rays.ndim != 2 or rays.shape[1] != 6:
-            raise ValueError("rays must be an (N, 6) array of o.xyz d.xyz, got shape %s" % (rays.shape,))
-        seeds = np.asarray(seeds)
-        if seeds.shape != (len(rays),):
-            raise ValueError("seeds must be an (N,) array with N = %d, got shape %s" % (len(rays), seeds.shape))
-        seeds = np.ascontiguousarray(seeds.astype(np.int64) & 0xFFFFFFFF, dtype="<u4")
+        rays = _rays(rays)
+        seeds = _seeds(seeds, len(rays))
         out = np.zeros((len(rays), 3), "<f4")
         states = np.zeros(len(rays), "<u4") if want_states else None
-        st = Stats()
+        st, stats = _stats()
         _check(lib().ort_radiance(self.handle, rays.ctypes.data, seeds.ctypes.data, len(rays), int(spp), float(rr), out.ctypes.data,
-                                  states.ctypes.data if want_states else None, RENDER_COUNTERS if counters else 0, C.byref(st)))
-        return (out, states, st.as_dict()) if want_states else (out, st.as_dict())
+                                  states.ctypes.data if want_states else None, _flags(counters), st))
+        return (out, states, stats()) if want_states else (out, stats())
 
     def radiance_device(self, d_rays, d_seeds, n, spp, rr, d_out, d_states=0, stream=0, counters=False, want_stats=False):
         """Device rays (n x 6 float32) and seeds (n uint32) -> device colours (n x 3 float32) and, if d_states, final states
         (n uint32): raw pointers on the scene's device, e.g. torch tensors' data_ptr().  Enqueued on stream; waits only when
         want_stats (returns the stats dict)."""
-        st = Stats() if want_stats else None
-        _check(lib().ort_radiance_device(self.handle, C.c_void_p(d_rays), C.c_void_p(d_seeds), n, int(spp), float(rr),
-                                         C.c_void_p(d_out), C.c_void_p(d_states) if d_states else None,
-                                         RENDER_COUNTERS if counters else 0, C.c_void_p(stream) if stream else None,
-                                         C.byref(st) if want_stats else None))
-        return st.as_dict() if want_stats else None
+        st, stats = _stats(want_stats)
+        _check(lib().ort_radiance_device(self.handle, _ptr(d_rays), _ptr(d_seeds), n, int(spp), float(rr), _ptr(d_out), _ptr(d_states),
+                                         _flags(counters), _ptr(stream), st))
+        return stats()
 
     # -- adaptive radiance queries ----------------------------------------------------------
     def radiance_adaptive(self, rays, seeds, min_spp, max_spp, tolerance, floor=0.05, check_every=4, rr=0.8, want_states=False,
@@ -549,38 +552,29 @@ class Scene:
         by operation).  A ray that saw no light in its first min_spp samples stops black: pick min_spp for the scene.
         Returns (rgb: float32[N, 3], spp: uint32[N] samples taken, m2: float32[N] sum of squared sample luminance, stats
         dict), with want_states (rgb, spp, m2, states, stats); a ray outside the domain gives NaN, 0, 0 and its seed."""
-        rays = np.ascontiguousarray(rays, dtype="<f4")
-        if rays.ndim != 2 or rays.shape[1] != 6:
-            raise ValueError("rays must be an (N, 6) array of o.xyz d.xyz, got shape %s" % (rays.shape,))
-        seeds = np.asarray(seeds)
-        if seeds.shape != (len(rays),):
-            raise ValueError("seeds must be an (N,) array with N = %d, got shape %s" % (len(rays), seeds.shape))
-        seeds = np.ascontiguousarray(seeds.astype(np.int64) & 0xFFFFFFFF, dtype="<u4")
+        rays = _rays(rays)
+        seeds = _seeds(seeds, len(rays))
         ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
         out = np.zeros((len(rays), 3), "<f4")
         spp = np.zeros(len(rays), "<u4")
         m2 = np.zeros(len(rays), "<f4")
         states = np.zeros(len(rays), "<u4") if want_states else None
-        st = Stats()
+        st, stats = _stats()
         _check(lib().ort_radiance_adaptive(self.handle, rays.ctypes.data, seeds.ctypes.data, len(rays), C.byref(ad), float(rr),
                                            out.ctypes.data, spp.ctypes.data, m2.ctypes.data,
-                                           states.ctypes.data if want_states else None, RENDER_COUNTERS if counters else 0,
-                                           C.byref(st)))
-        return (out, spp, m2, states, st.as_dict()) if want_states else (out, spp, m2, st.as_dict())
+                                           states.ctypes.data if want_states else None, _flags(counters), st))
+        return (out, spp, m2, states, stats()) if want_states else (out, spp, m2, stats())
 
     def radiance_adaptive_device(self, d_rays, d_seeds, n, min_spp, max_spp, tolerance, floor, check_every, rr, d_out, d_spp=0,
                                  d_m2=0, d_states=0, stream=0, counters=False, want_stats=False):
         """Device rays (n x 6 float32) and seeds (n uint32) -> device colours (n x 3 float32) and, where a pointer is given,
         samples taken (n uint32), sums of squared sample luminance (n float32) and final states (n uint32): raw pointers on
         the scene's device.  Enqueued on stream; waits only when want_stats (returns the stats dict)."""
-        st = Stats() if want_stats else None
+        st, stats = _stats(want_stats)
         ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
-        _check(lib().ort_radiance_adaptive_device(self.handle, C.c_void_p(d_rays), C.c_void_p(d_seeds), n, C.byref(ad), float(rr),
-                                                  C.c_void_p(d_out), C.c_void_p(d_spp) if d_spp else None,
-                                                  C.c_void_p(d_m2) if d_m2 else None, C.c_void_p(d_states) if d_states else None,
-                                                  RENDER_COUNTERS if counters else 0, C.c_void_p(stream) if stream else None,
-                                                  C.byref(st) if want_stats else None))
-        return st.as_dict() if want_stats else None
+        _check(lib().ort_radiance_adaptive_device(self.handle, _ptr(d_rays), _ptr(d_seeds), n, C.byref(ad), float(rr), _ptr(d_out),
+                                                  _ptr(d_spp), _ptr(d_m2), _ptr(d_states), _flags(counters), _ptr(stream), st))
+        return stats()
 
     def triangle_of(self, index):
         """mesh-major triangle id (decode_prim of a triangle hit) -> (mesh, triangle within that mesh).  Accepts arrays."""
@@ -614,10 +608,10 @@ class Scene:
         height, width = out.shape[:2]
         jobs = np.ascontiguousarray(jobs, dtype=JOB_DTYPE)
         finals = np.zeros(len(jobs), "<u4")
-        st = Stats()
+        st, stats = _stats()
         _check(lib().ort_tiled_raytrace_batch(self.handle, out.ctypes.data, width, height, jobs.ctypes.data, len(jobs),
-                                              rr, finals.ctypes.data, C.byref(st)))
-        return finals, st.as_dict()
+                                              rr, finals.ctypes.data, st))
+        return finals, stats()
 
 
 def _adaptive(min_spp, max_spp, check_every, tolerance, floor):
@@ -709,8 +703,7 @@ def unpack_blocks_host(packed, width, height, index, count, out=None):
 
 
 def unpack_blocks_device(d_packed_ptr, width, height, index, count, d_full_ptr, stream=None):
-    _check(lib().ort_unpack_blocks_device(C.c_void_p(d_packed_ptr), width, height, index, count, C.c_void_p(d_full_ptr),
-                                          C.c_void_p(stream) if stream else None))
+    _check(lib().ort_unpack_blocks_device(_ptr(d_packed_ptr), width, height, index, count, _ptr(d_full_ptr), _ptr(stream)))
 
 
 class Comm:
@@ -733,8 +726,7 @@ class Comm:
         return cls(h.value)
 
     def gather(self, d_packed_ptr, d_full_ptr, width, height, stream=None):
-        _check(lib().ort_gather_framebuffer(self.handle, C.c_void_p(d_packed_ptr), C.c_void_p(d_full_ptr) if d_full_ptr else None,
-                                            width, height, C.c_void_p(stream) if stream else None))
+        _check(lib().ort_gather_framebuffer(self.handle, _ptr(d_packed_ptr), _ptr(d_full_ptr), width, height, _ptr(stream)))
 
     def close(self):
         if self.handle:

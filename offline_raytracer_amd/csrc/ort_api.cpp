@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <exception>
+#include <initializer_list>
 #include <new>
 #include <memory>
 #include <string>
@@ -99,7 +100,10 @@ void tile32_jobs(const ort_render_params *p, std::vector<ort_tile_job> *jobs) {
         }
 }
 
-int render_common(ort_scene *scene, const ort_render_params *p, void *d_out, float *h_out, void *stream, ort_stats *stats) {
+/* out: the caller's memory (host) or a device pointer; device_render takes them apart */
+int render_common(ort_scene *scene, const ort_render_params *p, bool host, void *out, void *stream, ort_stats *stats) {
+    void *d_out = host ? nullptr : out;
+    float *h_out = host ? (float *)out : nullptr;
     int rc = check_params(scene, p);
     if (rc != ORT_OK) return rc;
     std::string err;
@@ -354,12 +358,12 @@ static int ort_tiled_raytrace_impl(ort_scene *s, float *out_rgb, int32_t width, 
 
 static int ort_render_image_impl(ort_scene *s, const ort_render_params *p, float *out_rgb, ort_stats *stats) {
     if (!out_rgb) return fail(ORT_ERR_INVALID, "null framebuffer");
-    return render_common(s, p, nullptr, out_rgb, nullptr, stats);
+    return render_common(s, p, true, out_rgb, nullptr, stats);
 }
 
 static int ort_render_image_device_impl(ort_scene *s, const ort_render_params *p, void *d_out_rgb, void *hip_stream, ort_stats *stats) {
     if (!d_out_rgb) return fail(ORT_ERR_INVALID, "null device framebuffer");
-    return render_common(s, p, d_out_rgb, nullptr, hip_stream, stats);
+    return render_common(s, p, false, d_out_rgb, hip_stream, stats);
 }
 
 static int ort_unit_eval_device_impl(int device, const void *records, uint32_t count, float *out) {
@@ -381,72 +385,50 @@ static int ort_unit_eval_device_impl(int device, const void *records, uint32_t c
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
-/* The ray queries.  Each call has a host form (h_*: the caller's memory, staged in slices) and a device form (d_*: device
-   pointers, enqueued on the caller's stream); a form passes its own pointers and nulls for the other's.  The order of the
+/* The ray queries.  Each call has a host form (the caller's memory, staged in slices) and a device form (device pointers,
+   enqueued on the caller's stream); both pass each array once, and the QueryCall says which form it is.  The order of the
    checks is each call's contract (include/ort.h). */
+/* one pointer argument: whether the call needs it, and the alignment it must have (8, 4 or 1: none) */
+struct PtrArg {
+    const void *p;
+    bool required;
+    unsigned align;
+};
+
+/* a required pointer that is null, then a pointer that is not 8-byte aligned, then one that is not 4-byte aligned */
+static int check_ptrs(std::initializer_list<PtrArg> args, const char *null_msg, const char *align8_msg, const char *align4_msg) {
+    for (const PtrArg &a : args)
+        if (a.required && !a.p) return fail(ORT_ERR_INVALID, null_msg);
+    for (unsigned align : {8u, 4u})
+        for (const PtrArg &a : args)
+            if (a.align == align && ((uintptr_t)a.p & (align - 1u))) return fail(ORT_ERR_INVALID, align == 8u ? align8_msg : align4_msg);
+    return ORT_OK;
+}
+
 /* closest hits: argument and state errors first, so that they are the same on a machine without a device; then count == 0 */
-static int raycast_common(ort_scene *s, const float *h_rays, const void *d_rays, uint64_t count, ort_hit *h_hits, void *d_hits, uint32_t flags, void *stream,
-                          ort_stats *stats) {
-    const void *rays = h_rays ? (const void *)h_rays : d_rays, *hits = h_hits ? (const void *)h_hits : d_hits;
+static int raycast_common(ort_scene *s, const ort::QueryCall &q, const void *rays, void *hits) {
     if (!s) return fail(ORT_ERR_INVALID, "null scene");
-    if (count && (!rays || !hits)) return fail(ORT_ERR_INVALID, "null rays or hits");
-    if (count && (((uintptr_t)rays | (uintptr_t)hits) & 7u)) return fail(ORT_ERR_INVALID, "rays and hits must be 8-byte aligned");
-    int rc = check_resident(s);
-    if (rc != ORT_OK) return rc;
-    if (count == 0) return nothing_to_do(stats);
+    int rc = q.count ? check_ptrs({{rays, true, 8}, {hits, true, 8}}, "null rays or hits", "rays and hits must be 8-byte aligned", "") : ORT_OK;
+    if (rc != ORT_OK || (rc = check_resident(s)) != ORT_OK) return rc;
+    if (q.count == 0) return nothing_to_do(q.stats);
     std::string err;
-    rc = ort::device_raycast(s, h_rays, d_rays, count, h_hits, d_hits, flags, stream, stats, &err);
+    rc = ort::device_raycast(s, q, rays, hits, &err);
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
 /* occlusion queries: count == 0 is OK whatever else is passed; then argument errors, then state errors */
-static int occluded_common(ort_scene *s, const float *h_rays, const void *d_rays, const void *tmax, uint64_t count, uint8_t *h_out, void *d_out, uint32_t flags,
-                           void *stream, ort_stats *stats) {
-    if (count == 0) return nothing_to_do(stats);
-    const void *rays = h_rays ? (const void *)h_rays : d_rays;
+static int occluded_common(ort_scene *s, const ort::QueryCall &q, const void *rays, const void *tmax, void *out) {
+    if (q.count == 0) return nothing_to_do(q.stats);
     if (!s) return fail(ORT_ERR_INVALID, "null scene");
-    if (!rays || !(h_out || d_out)) return fail(ORT_ERR_INVALID, "null rays or occluded");
-    if ((uintptr_t)rays & 7u) return fail(ORT_ERR_INVALID, "rays must be 8-byte aligned");
-    if ((uintptr_t)tmax & 3u) return fail(ORT_ERR_INVALID, "tmax must be 4-byte aligned");
-    int rc = check_resident(s);
-    if (rc != ORT_OK) return rc;
+    int rc = check_ptrs({{rays, true, 8}, {tmax, false, 4}, {out, true, 1}}, "null rays or occluded", "rays must be 8-byte aligned", "tmax must be 4-byte aligned");
+    if (rc != ORT_OK || (rc = check_resident(s)) != ORT_OK) return rc;
     std::string err;
-    rc = ort::device_occluded(s, h_rays, d_rays, tmax, count, h_out, d_out, flags, stream, stats, &err);
+    rc = ort::device_occluded(s, q, rays, tmax, out, &err);
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
-/* radiance queries: count == 0 is OK whatever else is passed; then argument errors, then state errors */
-static int radiance_common(ort_scene *s, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, uint32_t spp, float rr, float *h_out,
-                           void *d_out, uint32_t *h_states, void *d_states, uint32_t flags, void *stream, ort_stats *stats) {
-    if (count == 0) return nothing_to_do(stats);
-    const void *rays = h_rays ? (const void *)h_rays : d_rays, *out_rgb = h_out ? (const void *)h_out : d_out,
-               *final_states = h_states ? (const void *)h_states : d_states;
-    if (!s) return fail(ORT_ERR_INVALID, "null scene");
-    if (!rays || !seeds || !out_rgb) return fail(ORT_ERR_INVALID, "null rays, seeds or out_rgb");
-    if ((uintptr_t)rays & 7u) return fail(ORT_ERR_INVALID, "rays must be 8-byte aligned");
-    if (((uintptr_t)seeds | (uintptr_t)out_rgb | (uintptr_t)final_states) & 3u) return fail(ORT_ERR_INVALID, "seeds, out_rgb and final_states must be 4-byte aligned");
-    if (spp == 0) return fail(ORT_ERR_INVALID, "spp must be >= 1");
-    if (!(rr >= 0.0f && rr < 1.0f)) return fail(ORT_ERR_INVALID, "rr must be in [0, 1): at 1 a path in a closed room never ends");
-    int rc = check_resident(s);
-    if (rc != ORT_OK) return rc;
-    std::string err;
-    rc = ort::device_radiance(s, h_rays, d_rays, seeds, count, spp, rr, h_out, d_out, h_states, d_states, flags, stream, stats, &err);
-    return rc == ORT_OK ? ORT_OK : fail(rc, err);
-}
-
-/* adaptive radiance queries: as radiance_common, the stopping rule's parameters where spp stands there */
-static int radiance_adaptive_common(ort_scene *s, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, const ort_adaptive *ad, float rr,
-                                    float *h_out, void *d_out, uint32_t *h_spp, void *d_spp, float *h_m2, void *d_m2, uint32_t *h_states, void *d_states,
-                                    uint32_t flags, void *stream, ort_stats *stats) {
-    if (count == 0) return nothing_to_do(stats);
-    const void *rays = h_rays ? (const void *)h_rays : d_rays, *out_rgb = h_out ? (const void *)h_out : d_out,
-               *out_spp = h_spp ? (const void *)h_spp : d_spp, *out_m2 = h_m2 ? (const void *)h_m2 : d_m2,
-               *final_states = h_states ? (const void *)h_states : d_states;
-    if (!s) return fail(ORT_ERR_INVALID, "null scene");
-    if (!rays || !seeds || !out_rgb) return fail(ORT_ERR_INVALID, "null rays, seeds or out_rgb");
-    if ((uintptr_t)rays & 7u) return fail(ORT_ERR_INVALID, "rays must be 8-byte aligned");
-    if (((uintptr_t)seeds | (uintptr_t)out_rgb | (uintptr_t)out_spp | (uintptr_t)out_m2 | (uintptr_t)final_states) & 3u)
-        return fail(ORT_ERR_INVALID, "seeds, out_rgb, out_spp, out_m2 and final_states must be 4-byte aligned");
+/* the stopping rule's parameters by themselves */
+static int check_adaptive(const ort_adaptive *ad) {
     if (!ad) return fail(ORT_ERR_INVALID, "null ad (the adaptive parameters)");
     if (ad->min_spp < 2u) return fail(ORT_ERR_INVALID, "min_spp must be >= 2: a variance needs two samples");
     if (ad->max_spp < ad->min_spp) return fail(ORT_ERR_INVALID, "max_spp must be >= min_spp");
@@ -454,11 +436,25 @@ static int radiance_adaptive_common(ort_scene *s, const float *h_rays, const voi
     if (ad->check_every == 0u) return fail(ORT_ERR_INVALID, "check_every must be >= 1");
     if (!(ad->tolerance >= 0.0f && ad->tolerance <= FLT_MAX)) return fail(ORT_ERR_INVALID, "tolerance must be finite and >= 0");
     if (!(ad->floor >= 0.0f && ad->floor <= FLT_MAX)) return fail(ORT_ERR_INVALID, "floor must be finite and >= 0");
-    if (!(rr >= 0.0f && rr < 1.0f)) return fail(ORT_ERR_INVALID, "rr must be in [0, 1): at 1 a path in a closed room never ends");
-    int rc = check_resident(s);
+    return ORT_OK;
+}
+
+/* radiance queries: count == 0 is OK whatever else is passed; then argument errors, then state errors.  adaptive: the same
+   call with the stopping rule's parameters (ad, checked after the pointers) where spp stands, and out_spp and out_m2 */
+static int radiance_common(ort_scene *s, const ort::QueryCall &q, const void *rays, const void *seeds, uint32_t spp, float rr, bool adaptive,
+                           const ort_adaptive *ad, void *out_rgb, void *out_spp, void *out_m2, void *final_states) {
+    if (q.count == 0) return nothing_to_do(q.stats);
+    if (!s) return fail(ORT_ERR_INVALID, "null scene");
+    int rc = check_ptrs({{rays, true, 8}, {seeds, true, 4}, {out_rgb, true, 4}, {out_spp, false, 4}, {out_m2, false, 4}, {final_states, false, 4}},
+                        "null rays, seeds or out_rgb", "rays must be 8-byte aligned",
+                        adaptive ? "seeds, out_rgb, out_spp, out_m2 and final_states must be 4-byte aligned" : "seeds, out_rgb and final_states must be 4-byte aligned");
     if (rc != ORT_OK) return rc;
+    if (adaptive && (rc = check_adaptive(ad)) != ORT_OK) return rc;
+    if (!adaptive && spp == 0) return fail(ORT_ERR_INVALID, "spp must be >= 1");
+    if (!(rr >= 0.0f && rr < 1.0f)) return fail(ORT_ERR_INVALID, "rr must be in [0, 1): at 1 a path in a closed room never ends");
+    if ((rc = check_resident(s)) != ORT_OK) return rc;
     std::string err;
-    rc = ort::device_radiance_adaptive(s, h_rays, d_rays, seeds, count, ad, rr, h_out, d_out, h_spp, d_spp, h_m2, d_m2, h_states, d_states, flags, stream, stats, &err);
+    rc = ort::device_radiance(s, q, rays, seeds, spp, rr, adaptive ? ad : nullptr, out_rgb, out_spp, out_m2, final_states, &err);
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
@@ -485,10 +481,10 @@ static bool view_in_box(const ort_camera &c, const float lo[3], const float hi[3
 }
 
 /* view_count == 0 is OK whatever else is passed; then argument errors, what the call does not do, and the scene's state */
-static int render_views_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, void *d_out, float *h_out,
+static int render_views_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool host, void *out,
                                void *stream, ort_stats *stats) {
     if (view_count == 0) return nothing_to_do(stats);
-    if (!views || (!d_out && !h_out)) return fail(ORT_ERR_INVALID, "null views or framebuffer");
+    if (!views || !out) return fail(ORT_ERR_INVALID, "null views or framebuffer");
     static_assert(sizeof(ort_view) == 52, "ort_view is a camera and a seed");
     if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
     int rc = check_param_values(s, p);
@@ -505,7 +501,7 @@ static int render_views_common(ort_scene *s, const ort_render_params *p, const o
                                              "camera_p (+ 0.25 per side) that the tree was built for; create the scene with a camera_p out there");
     if ((rc = check_resident(s)) != ORT_OK) return rc;
     std::string err;
-    rc = ort::device_render(s, p, nullptr, 0, d_out, h_out, stream, nullptr, stats, &err, views, view_count);
+    rc = ort::device_render(s, p, nullptr, 0, host ? nullptr : out, host ? (float *)out : nullptr, stream, nullptr, stats, &err, views, view_count);
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
@@ -606,18 +602,18 @@ int ort_tiled_raytrace(ort_scene *s, float *out_rgb, int32_t width, int32_t heig
 int ort_render_image(ort_scene *s, const ort_render_params *p, float *out_rgb, ort_stats *stats) { return guarded([&]() { return ort_render_image_impl(s, p, out_rgb, stats); }); }
 int ort_render_image_device(ort_scene *s, const ort_render_params *p, void *d_out_rgb, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ort_render_image_device_impl(s, p, d_out_rgb, hip_stream, stats); }); }
 int ort_unit_eval_device(int device, const void *records, uint32_t count, float *out) { return guarded([&]() { return ort_unit_eval_device_impl(device, records, count, out); }); }
-int ort_raycast(ort_scene *s, const float *rays, uint64_t count, ort_hit *hits, uint32_t flags, ort_stats *stats) { return guarded([&]() { return raycast_common(s, rays, nullptr, count, hits, nullptr, flags, nullptr, stats); }); }
-int ort_raycast_device(ort_scene *s, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return raycast_common(s, nullptr, d_rays, count, nullptr, d_hits, flags, hip_stream, stats); }); }
-int ort_occluded(ort_scene *s, const float *rays, const float *tmax, uint64_t count, uint8_t *occluded, uint32_t flags, ort_stats *stats) { return guarded([&]() { return occluded_common(s, rays, nullptr, tmax, count, occluded, nullptr, flags, nullptr, stats); }); }
-int ort_occluded_device(ort_scene *s, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return occluded_common(s, nullptr, d_rays, d_tmax, count, nullptr, d_occluded, flags, hip_stream, stats); }); }
-int ort_radiance(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr, float *out_rgb, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_common(s, rays, nullptr, seeds, count, spp, rr, out_rgb, nullptr, final_states, nullptr, flags, nullptr, stats); }); }
-int ort_radiance_device(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_common(s, nullptr, d_rays, d_seeds, count, spp, rr, nullptr, d_out_rgb, nullptr, d_final_states, flags, hip_stream, stats); }); }
-int ort_radiance_adaptive(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, const ort_adaptive *ad, float rr, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_adaptive_common(s, rays, nullptr, seeds, count, ad, rr, out_rgb, nullptr, out_spp, nullptr, out_m2, nullptr, final_states, nullptr, flags, nullptr, stats); }); }
-int ort_radiance_adaptive_device(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, const ort_adaptive *ad, float rr, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_adaptive_common(s, nullptr, d_rays, d_seeds, count, ad, rr, nullptr, d_out_rgb, nullptr, d_out_spp, nullptr, d_out_m2, nullptr, d_final_states, flags, hip_stream, stats); }); }
+int ort_raycast(ort_scene *s, const float *rays, uint64_t count, ort_hit *hits, uint32_t flags, ort_stats *stats) { return guarded([&]() { return raycast_common(s, {true, count, flags, nullptr, stats}, rays, hits); }); }
+int ort_raycast_device(ort_scene *s, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return raycast_common(s, {false, count, flags, hip_stream, stats}, d_rays, d_hits); }); }
+int ort_occluded(ort_scene *s, const float *rays, const float *tmax, uint64_t count, uint8_t *occluded, uint32_t flags, ort_stats *stats) { return guarded([&]() { return occluded_common(s, {true, count, flags, nullptr, stats}, rays, tmax, occluded); }); }
+int ort_occluded_device(ort_scene *s, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return occluded_common(s, {false, count, flags, hip_stream, stats}, d_rays, d_tmax, d_occluded); }); }
+int ort_radiance(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr, float *out_rgb, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {true, count, flags, nullptr, stats}, rays, seeds, spp, rr, false, nullptr, out_rgb, nullptr, nullptr, final_states); }); }
+int ort_radiance_device(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {false, count, flags, hip_stream, stats}, d_rays, d_seeds, spp, rr, false, nullptr, d_out_rgb, nullptr, nullptr, d_final_states); }); }
+int ort_radiance_adaptive(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, const ort_adaptive *ad, float rr, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {true, count, flags, nullptr, stats}, rays, seeds, 0, rr, true, ad, out_rgb, out_spp, out_m2, final_states); }); }
+int ort_radiance_adaptive_device(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, const ort_adaptive *ad, float rr, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {false, count, flags, hip_stream, stats}, d_rays, d_seeds, 0, rr, true, ad, d_out_rgb, d_out_spp, d_out_m2, d_final_states); }); }
 int ort_render_workspace_bytes(const ort_render_params *p, uint64_t *bytes) { return guarded([&]() { return ort_render_workspace_bytes_impl(p, bytes); }); }
 int ort_camera_from_pose(const float p[3], const float quat_xyzw[4], float height_ratio, int32_t width, int32_t height, ort_camera *out) { return guarded([&]() { return ort_camera_from_pose_impl(p, quat_xyzw, height_ratio, width, height, out); }); }
-int ort_render_views(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, float *out_rgb, ort_stats *stats) { return guarded([&]() { return render_views_common(s, p, views, view_count, nullptr, out_rgb, nullptr, stats); }); }
-int ort_render_views_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, void *d_out_rgb, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_views_common(s, p, views, view_count, d_out_rgb, nullptr, hip_stream, stats); }); }
+int ort_render_views(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, float *out_rgb, ort_stats *stats) { return guarded([&]() { return render_views_common(s, p, views, view_count, true, out_rgb, nullptr, stats); }); }
+int ort_render_views_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, void *d_out_rgb, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_views_common(s, p, views, view_count, false, d_out_rgb, hip_stream, stats); }); }
 int ort_render_views_workspace_bytes(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) { return guarded([&]() { return ort_render_views_workspace_bytes_impl(p, view_count, bytes); }); }
 int ort_shard_block_count(int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, uint64_t *blocks) { return guarded([&]() { return ort_shard_block_count_impl(width, height, shard_index, shard_count, blocks); }); }
 int ort_pack_blocks_host(const float *full_rgb, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, float *packed) { return guarded([&]() { return ort_pack_blocks_host_impl(full_rgb, width, height, shard_index, shard_count, packed); }); }

@@ -97,10 +97,7 @@ struct DeviceScene {
     DevBuf prim_src;
     float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0}; /* shapes and camera (raycast_needs_exact) */
     bool scene_box_known = false;
-    DevBuf ray_in, hit_out;
-    DevBuf tmax_in, occ_out; /* occlusion queries (device_occluded): the host path's limits and bytes */
-    DevBuf seed_in, rad_out, rad_states; /* radiance queries (device_radiance): the host path's seeds, colours and final states */
-    DevBuf rad_spp, rad_m2; /* ... and (device_radiance_adaptive) sample counts and sums of squared luminance */
+    DevBuf query_stage[6]; /* the i-th array of the host form in flight (run_query); six: the adaptive radiance query's */
 };
 
 int device_count(int *n, std::string *err) {
@@ -575,7 +572,8 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
 /* What is launched, on which grid and with which thresholds is plan_ray_query's and plan_radiance's decision (ort_plan.h); this
    is the plumbing around them: one launch path (launch_query) and one host-form loop (run_sliced) for the three */
 constexpr uint64_t kRaycastSlice = 1ull << 22;  /* rays per launch of the host form of ort_raycast and ort_occluded (2 x 96 MB of staging) */
-constexpr uint64_t kRadianceSlice = 1ull << 20; /* ... of ort_radiance: a ray is spp paths, and 44 MB of staging */
+constexpr uint64_t kRadianceSlice = 1ull << 20; /* ... of ort_radiance and ort_radiance_adaptive: a ray is spp paths; 44 and 52 MB of staging */
+/* tests/test_gpu_slice_boundary.py mirrors both: it runs every query over one slice and a ragged remainder */
 
 /* the inverse of the tree's slot maps, in PrimInfo order (triangles | boxes | cylinders | spheres): slot -> kind << 28 |
    the shape's index in the scene's own arrays.  Built and uploaded at the first query, so that render-only users pay nothing */
@@ -587,10 +585,10 @@ static int ensure_prim_src(Scene *scene, DeviceScene *d, std::string *err) {
     return upload_vec(src, &d->prim_src, err);
 }
 
-/* what raycast_needs_exact reads, and the rays */
-static RaycastIO ray_query_io(Scene *scene, DeviceScene *d, const void *d_rays) {
+/* what raycast_needs_exact reads, and the rays (a device pointer) */
+static RaycastIO ray_query_io(Scene *scene, DeviceScene *d, const void *rays) {
     RaycastIO io{};
-    io.rays = (const float2 *)d_rays;
+    io.rays = (const float2 *)rays;
     ort::ray_query_io(*scene, d->scene_lo, d->scene_hi, &io);
     return io;
 }
@@ -686,108 +684,104 @@ static int begin_query(Scene *scene, ort_stats *stats, DeviceScene **d_out, std:
     return ORT_OK;
 }
 
-/* closest hits: count rays at h_rays -> h_hits (host form) or at d_rays -> d_hits (device pointers, one launch) */
-int device_raycast(Scene *scene, const float *h_rays, const void *d_rays, uint64_t count, ort_hit *h_hits, void *d_hits, uint32_t flags,
-                   void *stream_v, ort_stats *stats, std::string *err) {
+/* One array of a query call: `bytes` per ray, read by the kernel or (out) written.  p == NULL: an optional array the caller did
+   not pass */
+struct QueryArray {
+    const void *p;
+    size_t bytes;
+    bool out;
+};
+
+/* A query over its arrays, launch(p, n) running the first n rays at the device pointers p[i].  The device form: the caller's
+   pointers, one launch.  The host form: run_sliced, array i staged through the scene's i-th staging buffer */
+template <size_t N, typename Launch>
+static int run_query(DeviceScene *d, const QueryCall &q, uint64_t slice_cap, const QueryArray (&arrays)[N], std::string *err, Launch launch) {
+    static_assert(N <= sizeof(d->query_stage) / sizeof(d->query_stage[0]), "one staging buffer per array");
+    void *p[N];
+    if (!q.host) {
+        for (size_t i = 0; i < N; ++i) p[i] = (void *)arrays[i].p;
+        return launch(p, q.count);
+    }
+    QueryStream s[N];
+    for (size_t i = 0; i < N; ++i) s[i] = QueryStream{(void *)arrays[i].p, &d->query_stage[i], arrays[i].bytes, arrays[i].out};
+    return run_sliced(d, q.count, slice_cap, s, (hipStream_t)q.stream, err, [&](uint64_t n) {
+        for (size_t i = 0; i < N; ++i) p[i] = s[i].dev();
+        return launch(p, n);
+    });
+}
+
+/* closest hits: count rays -> count hits */
+int device_raycast(Scene *scene, const QueryCall &q, const void *rays, void *hits, std::string *err) {
     static_assert(sizeof(ort_hit) == 24, "ort_hit is three 8-byte words");
     DeviceScene *d;
     int rc;
-    if ((rc = begin_query(scene, stats, &d, err)) || (rc = ensure_prim_src(scene, d, err))) return rc;
-    hipStream_t stream = (hipStream_t)stream_v;
-    const bool counters = (flags & ORT_RENDER_COUNTERS) != 0;
-    auto launch = [&](const void *rays, void *hits, uint64_t n) {
-        RaycastIO io = ray_query_io(scene, d, rays);
-        io.hits = (uint2 *)hits;
+    if ((rc = begin_query(scene, q.stats, &d, err)) || (rc = ensure_prim_src(scene, d, err))) return rc;
+    hipStream_t stream = (hipStream_t)q.stream;
+    const bool counters = (q.flags & ORT_RENDER_COUNTERS) != 0;
+    const QueryArray arrays[] = {{rays, 24u, false}, {hits, sizeof(ort_hit), true}};
+    return run_query(d, q, kRaycastSlice, arrays, err, [&](void *const *p, uint64_t n) {
+        RaycastIO io = ray_query_io(scene, d, p[0]);
+        io.hits = (uint2 *)p[1];
         io.prim_src = d->prim_src.as<const uint32_t>();
-        return launch_query(scene, d, RenderView{}, n, false, counters, stream, stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
+        return launch_query(scene, d, RenderView{}, n, false, counters, stream, q.stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
             with_bools([&](auto C, auto T) {
                 hipLaunchKernelGGL((raycast_rays<decltype(C)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot, io);
             }, pl.counters, pl.tabs);
         });
-    };
-    if (!h_rays) return launch(d_rays, d_hits, count);
-    const QueryStream s[] = {{(void *)h_rays, &d->ray_in, 24u, false}, {h_hits, &d->hit_out, sizeof(ort_hit), true}};
-    return run_sliced(d, count, kRaycastSlice, s, stream, err, [&](uint64_t n) { return launch(s[0].dev(), s[1].dev(), n); });
+    });
 }
 
-/* occlusion: the same for count rays and their limits at tmax (may be null; a host or a device pointer as the rays are) -> count
-   bytes.  No shape table: a byte names no shape */
-int device_occluded(Scene *scene, const float *h_rays, const void *d_rays, const void *tmax, uint64_t count, uint8_t *h_out, void *d_out,
-                    uint32_t flags, void *stream_v, ort_stats *stats, std::string *err) {
+/* occlusion: the same for count rays and their limits at tmax (may be null) -> count bytes.  No shape table: a byte names no
+   shape */
+int device_occluded(Scene *scene, const QueryCall &q, const void *rays, const void *tmax, void *out, std::string *err) {
     DeviceScene *d;
     int rc;
-    if ((rc = begin_query(scene, stats, &d, err))) return rc;
-    hipStream_t stream = (hipStream_t)stream_v;
-    const bool counters = (flags & ORT_RENDER_COUNTERS) != 0;
-    auto launch = [&](const void *rays, const void *limits, void *out, uint64_t n) {
+    if ((rc = begin_query(scene, q.stats, &d, err))) return rc;
+    hipStream_t stream = (hipStream_t)q.stream;
+    const bool counters = (q.flags & ORT_RENDER_COUNTERS) != 0;
+    const QueryArray arrays[] = {{rays, 24u, false}, {tmax, sizeof(float), false}, {out, 1u, true}};
+    return run_query(d, q, kRaycastSlice, arrays, err, [&](void *const *p, uint64_t n) {
         OccludedIO io{};
-        io.q = ray_query_io(scene, d, rays);
-        io.tmax = (const float *)limits;
-        io.out = (uint8_t *)out;
+        io.q = ray_query_io(scene, d, p[0]);
+        io.tmax = (const float *)p[1];
+        io.out = (uint8_t *)p[2];
         io.mats_nonzero = all_mats_nonzero(scene->tree);
-        return launch_query(scene, d, RenderView{}, n, false, counters, stream, stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
+        return launch_query(scene, d, RenderView{}, n, false, counters, stream, q.stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
             with_bools([&](auto C, auto T) {
                 hipLaunchKernelGGL((occluded_rays<decltype(C)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot, io);
             }, pl.counters, pl.tabs);
         });
-    };
-    if (!h_rays) return launch(d_rays, tmax, d_out, count);
-    const QueryStream s[] = {{(void *)h_rays, &d->ray_in, 24u, false}, {(void *)tmax, &d->tmax_in, sizeof(float), false}, {h_out, &d->occ_out, 1u, true}};
-    return run_sliced(d, count, kRaycastSlice, s, stream, err, [&](uint64_t n) { return launch(s[0].dev(), s[1].dev(), s[2].dev(), n); });
+    });
 }
 
-/* radiance: count rays with their seeds -> 3 floats each and, where asked for (h_states / d_states may be null), the final
-   states.  No shape table: a colour names no shape */
-int device_radiance(Scene *scene, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, uint32_t spp, float rr, float *h_out,
-                    void *d_out, uint32_t *h_states, void *d_states, uint32_t flags, void *stream_v, ort_stats *stats, std::string *err) {
+/* radiance: count rays with their seeds -> 3 floats each and, where asked for (states may be null), the final states.  No shape
+   table: a colour names no shape.  With ad (checked by the caller) the adaptive query: the stopping rule's parameters where spp
+   stands, and, where asked for, every ray's sample count and its sum of squared sample luminance; plan_radiance's plan as it
+   is, the kernels ort_kernels_adaptive.hip's */
+int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const void *seeds, uint32_t spp, float rr, const ort_adaptive *ad, void *out,
+                    void *out_spp, void *out_m2, void *states, std::string *err) {
     DeviceScene *d;
     int rc;
-    if ((rc = begin_query(scene, stats, &d, err))) return rc;
-    hipStream_t stream = (hipStream_t)stream_v;
-    const bool counters = (flags & ORT_RENDER_COUNTERS) != 0;
-    auto launch = [&](const void *rays, const void *ray_seeds, void *out, void *states, uint64_t n) {
-        RenderView rv{};
-        radiance_view(ray_query_io(scene, d, rays), ray_seeds, spp, rr, out, states, &rv);
-        return launch_query(scene, d, rv, n, true, counters, stream, stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
-            with_bools([&](auto C, auto D, auto T) {
-                hipLaunchKernelGGL((radiance_rays<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot);
-            }, pl.counters, pl.diffuse, pl.tabs);
-        });
-    };
-    if (!h_rays) return launch(d_rays, seeds, d_out, d_states, count);
-    const QueryStream s[] = {{(void *)h_rays, &d->ray_in, 24u, false}, {(void *)seeds, &d->seed_in, 4u, false}, {h_out, &d->rad_out, 12u, true},
-                             {h_states, &d->rad_states, 4u, true}};
-    return run_sliced(d, count, kRadianceSlice, s, stream, err, [&](uint64_t n) { return launch(s[0].dev(), s[1].dev(), s[2].dev(), s[3].dev(), n); });
-}
-
-/* adaptive radiance: the same with the stopping rule's parameters (ad: checked by the caller) -> besides the colours and the
-   states, where asked for (null otherwise), every ray's sample count and its sum of squared sample luminance.  plan_radiance's
-   plan as it is; the kernels are ort_kernels_adaptive.hip's */
-int device_radiance_adaptive(Scene *scene, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, const ort_adaptive *ad, float rr,
-                             float *h_out, void *d_out, uint32_t *h_spp, void *d_spp, float *h_m2, void *d_m2, uint32_t *h_states, void *d_states,
-                             uint32_t flags, void *stream_v, ort_stats *stats, std::string *err) {
-    DeviceScene *d;
-    int rc;
-    if ((rc = begin_query(scene, stats, &d, err))) return rc;
-    if (ort_adaptive_sizeof_scene_view() != sizeof(SceneView) || ort_adaptive_sizeof_render_hot() != sizeof(RenderHot) ||
-        ort_adaptive_sizeof_render_view() != sizeof(RenderView)) {
+    if ((rc = begin_query(scene, q.stats, &d, err))) return rc;
+    if (ad && (ort_adaptive_sizeof_scene_view() != sizeof(SceneView) || ort_adaptive_sizeof_render_hot() != sizeof(RenderHot) ||
+               ort_adaptive_sizeof_render_view() != sizeof(RenderView))) {
         *err = "internal: the adaptive kernels were built with other argument layouts";
         return ORT_ERR_INTERNAL;
     }
-    hipStream_t stream = (hipStream_t)stream_v;
-    const bool counters = (flags & ORT_RENDER_COUNTERS) != 0;
-    auto launch = [&](const void *rays, const void *ray_seeds, void *out, void *spp, void *m2, void *states, uint64_t n) {
+    hipStream_t stream = (hipStream_t)q.stream;
+    const bool counters = (q.flags & ORT_RENDER_COUNTERS) != 0;
+    const QueryArray arrays[] = {{rays, 24u, false}, {seeds, 4u, false}, {out, 12u, true}, {out_spp, 4u, true}, {out_m2, 4u, true}, {states, 4u, true}};
+    return run_query(d, q, kRadianceSlice, arrays, err, [&](void *const *p, uint64_t n) {
         RenderView rv{};
-        radiance_adaptive_view(ray_query_io(scene, d, rays), ray_seeds, *ad, rr, out, spp, m2, states, &rv);
-        return launch_query(scene, d, rv, n, true, counters, stream, stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
-            ort_launch_radiance_adaptive(pl.counters, pl.diffuse, pl.tabs, pl.grid, (void *)stream, &sv, &hot);
+        if (ad) radiance_adaptive_view(ray_query_io(scene, d, p[0]), p[1], *ad, rr, p[2], p[3], p[4], p[5], &rv);
+        else radiance_view(ray_query_io(scene, d, p[0]), p[1], spp, rr, p[2], p[5], &rv);
+        return launch_query(scene, d, rv, n, true, counters, stream, q.stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
+            if (ad) ort_launch_radiance_adaptive(pl.counters, pl.diffuse, pl.tabs, pl.grid, (void *)stream, &sv, &hot);
+            else with_bools([&](auto C, auto D, auto T) {
+                hipLaunchKernelGGL((radiance_rays<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot);
+            }, pl.counters, pl.diffuse, pl.tabs);
         });
-    };
-    if (!h_rays) return launch(d_rays, seeds, d_out, d_spp, d_m2, d_states, count);
-    const QueryStream s[] = {{(void *)h_rays, &d->ray_in, 24u, false}, {(void *)seeds, &d->seed_in, 4u, false}, {h_out, &d->rad_out, 12u, true},
-                             {h_spp, &d->rad_spp, 4u, true}, {h_m2, &d->rad_m2, 4u, true}, {h_states, &d->rad_states, 4u, true}};
-    return run_sliced(d, count, kRadianceSlice, s, stream, err,
-                      [&](uint64_t n) { return launch(s[0].dev(), s[1].dev(), s[2].dev(), s[3].dev(), s[4].dev(), s[5].dev(), n); });
+    });
 }
 
 } // namespace ort

@@ -217,22 +217,25 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
                   void *d_out, float *h_out, void *stream, uint32_t *final_states, ort_stats *stats, std::string *err,
                   const ort_view *views = nullptr, uint32_t view_count = 1);
 int device_unit_eval(int device, const void *records, uint32_t n, float *out, std::string *err);
-/* closest-hit queries: host rays / hits (h_*, synchronous) or device ones (d_*, enqueued on stream) */
-int device_raycast(Scene *scene, const float *h_rays, const void *d_rays, uint64_t count, ort_hit *h_hits, void *d_hits, uint32_t flags,
-                   void *stream, ort_stats *stats, std::string *err);
-/* occlusion queries: host rays / limits / bytes (h_rays, tmax a host pointer, synchronous) or device ones (d_rays, tmax a device
-   pointer, enqueued on stream); tmax may be null (no limit) */
-int device_occluded(Scene *scene, const float *h_rays, const void *d_rays, const void *tmax, uint64_t count, uint8_t *h_out, void *d_out,
-                    uint32_t flags, void *stream, ort_stats *stats, std::string *err);
-/* radiance queries: host rays / seeds / colours / states (h_rays, seeds a host pointer, synchronous) or device ones (d_rays,
-   seeds a device pointer, enqueued on stream); the states may be null */
-int device_radiance(Scene *scene, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, uint32_t spp, float rr, float *h_out,
-                    void *d_out, uint32_t *h_states, void *d_states, uint32_t flags, void *stream, ort_stats *stats, std::string *err);
-/* adaptive radiance queries: the same, with the stopping rule's parameters and two more optional outputs (samples taken, sum of
-   squared sample luminance) */
-int device_radiance_adaptive(Scene *scene, const float *h_rays, const void *d_rays, const void *seeds, uint64_t count, const ort_adaptive *ad, float rr,
-                             float *h_out, void *d_out, uint32_t *h_spp, void *d_spp, float *h_m2, void *d_m2, uint32_t *h_states, void *d_states,
-                             uint32_t flags, void *stream, ort_stats *stats, std::string *err);
+/* One ray query call.  host: the arrays are the caller's memory, staged to the device in bounded slices, and the call returns
+   when the answers are back; otherwise they are device pointers and the call is one launch enqueued on stream (it waits only
+   for stats).  Every array is passed once, whichever form it is */
+struct QueryCall {
+    bool host;
+    uint64_t count;
+    uint32_t flags;
+    void *stream;
+    ort_stats *stats; /* may be null */
+};
+/* closest hits: count rays -> count ort_hit */
+int device_raycast(Scene *scene, const QueryCall &q, const void *rays, void *hits, std::string *err);
+/* occlusion: count rays and their limits (tmax may be null: no limit) -> count bytes */
+int device_occluded(Scene *scene, const QueryCall &q, const void *rays, const void *tmax, void *out, std::string *err);
+/* radiance: count rays and seeds -> colours and, where asked for (null otherwise), final states.  ad == null: exactly spp samples
+   per ray; otherwise the adaptive query (spp unread): the stopping rule's parameters, and two more optional outputs (samples
+   taken, sum of squared sample luminance) */
+int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const void *seeds, uint32_t spp, float rr, const ort_adaptive *ad, void *out,
+                    void *out_spp, void *out_m2, void *states, std::string *err);
 /* ort_comm.cpp */
 struct Comm;
 uint64_t comm_shard_blocks(int32_t w, int32_t h, uint32_t index, uint32_t count);

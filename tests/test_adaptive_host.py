@@ -15,6 +15,7 @@ import radiance_cases as rc
 import table_scenes
 from adaptive_cases import Adaptive
 from conftest import DATA
+from host_cases import aligned as _aligned, scene as _scene
 
 NAMES = {"ort_radiance_adaptive", "ort_radiance_adaptive_device"}
 N_RAYS = 128
@@ -109,17 +110,6 @@ def test_adaptive_entry_points_have_c_linkage(api):
     assert all(n + "(" in hdr for n in NAMES)
     assert api.lib().ort_abi_version() == 3   # additive: the ABI version stands
     assert ctypes.sizeof(api.Adaptive) == 20
-
-
-def _scene(api, committed=True):
-    s = api.Scene.load_scn(os.path.join(DATA, "c2_analytic.scn"))
-    return s.commit() if committed else s
-
-
-def _aligned(nbytes):
-    buf = np.zeros(nbytes + 64, np.uint8)
-    off = (-buf.ctypes.data) % 16
-    return buf, buf.ctypes.data + off
 
 
 def _caller(api, device_form):

@@ -1,13 +1,12 @@
 """Occlusion ray queries (ort_occluded / ort_occluded_device), host side: the C ABI surface, and the argument and state
 errors in the order include/ort.h gives them -- all reported before any device work, so they are the same on a machine
 without a GPU -- and the shapes Scene.occluded accepts."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import DATA
+from host_cases import aligned as _aligned, scene as _scene
 
 NAMES = {"ort_occluded", "ort_occluded_device"}
 
@@ -18,17 +17,6 @@ def test_occluded_entry_points_have_c_linkage(api):
     assert NAMES <= names
     assert NAMES <= set(api.EXPORTS)
     assert api.lib().ort_abi_version() == 3   # additive: the ABI version stands
-
-
-def _scene(api, committed=True):
-    s = api.Scene.load_scn(os.path.join(DATA, "c2_analytic.scn"))
-    return s.commit() if committed else s
-
-
-def _aligned(nbytes):
-    buf = np.zeros(nbytes + 64, np.uint8)
-    off = (-buf.ctypes.data) % 16
-    return buf, buf.ctypes.data + off
 
 
 def _caller(api, device_form):

@@ -10,6 +10,7 @@ import pytest
 
 import radiance_cases as rc
 from conftest import DATA, assert_bits_equal
+from host_cases import aligned as _aligned, scene as _scene
 
 NAMES = {"ort_radiance", "ort_radiance_device"}
 
@@ -123,17 +124,6 @@ def test_job_seeds_are_the_oracles(api, oracle):
         assert got.dtype == np.dtype("<u4") and got.shape == (300,)
         assert got.tolist() == [oracle.job_seed(master, i) for i in range(300)]
     assert len(api.job_seeds(7, 0)) == 0
-
-
-def _scene(api, committed=True):
-    s = api.Scene.load_scn(os.path.join(DATA, "c2_analytic.scn"))
-    return s.commit() if committed else s
-
-
-def _aligned(nbytes):
-    buf = np.zeros(nbytes + 64, np.uint8)
-    off = (-buf.ctypes.data) % 16
-    return buf, buf.ctypes.data + off
 
 
 def _caller(api, device_form):

@@ -2,13 +2,12 @@
 argument and state errors (checked before any device work, so they are the same on a machine without a GPU), and
 the helpers that decode a hit's shape."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import DATA
+from host_cases import aligned as _aligned, scene as _scene
 
 
 def test_raycast_entry_points_have_c_linkage(api):
@@ -26,17 +25,6 @@ def test_hit_dtype_matches_ort_hit(api):
             api.HIT_DTYPE.fields["prim"][1]) == (0, 4, 16, 20)
     assert (api.HIT_TRIANGLE, api.HIT_BOX, api.HIT_CYLINDER, api.HIT_SPHERE) == (0, 2, 3, 4)
     assert api.NO_PRIM == 0xFFFFFFFF
-
-
-def _scene(api, committed=True):
-    s = api.Scene.load_scn(os.path.join(DATA, "c2_analytic.scn"))
-    return s.commit() if committed else s
-
-
-def _aligned(nbytes):
-    buf = np.zeros(nbytes + 64, np.uint8)
-    off = (-buf.ctypes.data) % 16
-    return buf, buf.ctypes.data + off
 
 
 @pytest.mark.parametrize("device_form", [False, True])

@@ -14,6 +14,7 @@ import pytest
 import oracle_lib
 import table_scenes
 from conftest import DATA, GOLDEN, assert_bits_equal
+from host_cases import scene as _scene
 from test_launch_plan import KNOBS
 
 NAMES = {"ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes"}
@@ -71,11 +72,6 @@ def test_camera_from_pose_argument_errors(api):
 
 
 # ---- errors, in order --------------------------------------------------------------------------------------------------
-def _scene(api, committed=True):
-    s = api.Scene.load_scn(os.path.join(DATA, "c2_analytic.scn"))
-    return s.commit() if committed else s
-
-
 def _caller(api, device_form):
     L = api.lib()
 

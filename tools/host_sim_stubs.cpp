@@ -6,10 +6,9 @@ int device_upload(Scene *, int, std::string *err) { *err = "host_sim: no device"
 void device_release(Scene *) {}
 int device_render(Scene *, const ort_render_params *, const ort_tile_job *, uint32_t, void *, float *, void *, uint32_t *, ort_stats *, std::string *err, const ort_view *, uint32_t) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_unit_eval(int, const void *, uint32_t, float *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
-int device_raycast(Scene *, const float *, const void *, uint64_t, ort_hit *, void *, uint32_t, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
-int device_occluded(Scene *, const float *, const void *, const void *, uint64_t, uint8_t *, void *, uint32_t, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
-int device_radiance(Scene *, const float *, const void *, const void *, uint64_t, uint32_t, float, float *, void *, uint32_t *, void *, uint32_t, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
-int device_radiance_adaptive(Scene *, const float *, const void *, const void *, uint64_t, const ort_adaptive *, float, float *, void *, uint32_t *, void *, float *, void *, uint32_t *, void *, uint32_t, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
+int device_raycast(Scene *, const QueryCall &, const void *, void *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
+int device_occluded(Scene *, const QueryCall &, const void *, const void *, void *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
+int device_radiance(Scene *, const QueryCall &, const void *, const void *, uint32_t, float, const ort_adaptive *, void *, void *, void *, void *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 }
 /* the multi-GPU entry points of ort_api.cpp (ort_comm.cpp is HIP code): never called by the harness */
 namespace ort {

@@ -11,6 +11,7 @@ Per scene (those of tools/raycast_bench.py), --spp samples per ray:
 Each gets --warmup calls, then --calls timed calls, one pair of HIP events per call, the three alternating call by call so
 that clocks and cache state drift alike.  One JSON line per scene: M paths/s of each from the median call, ratio_frame =
 radiance / render on the frame, s = (max - min) / median of the render's timings.  No ratio is required: the line records.
+host_us_per_call is raycast_bench.py's, for the frame family's call: at a small --size and --spp, the library's per-call overhead.
 usage: python3 tools/radiance_bench.py [--scenes ...] [--size 512] [--spp 64] [--warmup 3] [--calls 7]"""
 import argparse
 import json
@@ -60,6 +61,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--calls", type=int, default=7)
     ap.add_argument("--seed", type=int, default=20261017)
+    ap.add_argument("--host-calls", type=int, default=400)
     args = ap.parse_args()
     assert args.calls >= 5 and args.warmup >= 2
     import torch
@@ -114,6 +116,7 @@ def main():
                "rays_per_path": {k: v["rays"] / max(1, v["paths"]) for k, v in st.items()},
                "tests_per_path": {k: (v["node_tests"] + v["tri_tests"] + v["analytic_tests"]) / max(1, v["paths"]) for k, v in st.items()},
                "fallback_rays": {k: v["fallback_rays"] for k, v in st.items()},
+               "host_us_per_call": raycast_bench.host_us_per_call(calls[1][1], stream.synchronize, args.host_calls),
                "lib": os.path.relpath(api.LIB_PATH, ROOT)}
         print(json.dumps(out), flush=True)
         scene.close()

@@ -3,6 +3,8 @@
 Per scene: 2^24 rays per call (the golden tables' distribution -- origins in and around the room, uniform unit
 directions -- drawn on the device from a fixed seed), warm-up calls, then calls until at least --seconds of timed work;
 the rate comes from HIP events around the calls.  One more call with ORT_RENDER_COUNTERS gives the work per ray.
+host_us_per_call is the wall time of a call on the host, enqueued and with want_stats (quartiles of --host-calls calls each):
+at a small --rays-log2 it is the library's per-call overhead.
 Prints one JSON line per scene.  For the kernel time alone run it under rocprofv3 --kernel-trace --stats.
 --dirs axis casts the same origins along the six axis directions (+-x, +-y, +-z with +-0 in the other components,
 e.g. height probes): the directions whose 1/d has infinite components.
@@ -50,9 +52,26 @@ def make_rays(torch, n, seed, dev, dirs="uniform"):
     return torch.cat([o, d], dim=1).float().contiguous()
 
 
+def host_us_per_call(call, sync, calls):
+    """{"enqueue" | "want_stats": [first quartile, median, third quartile]} of the wall time of call(), in microseconds"""
+    out = {}
+    for key, kw in (("enqueue", {}), ("want_stats", {"want_stats": True})):
+        sync()
+        us = []
+        for _ in range(calls):
+            t0 = time.perf_counter()
+            call(**kw)
+            us.append((time.perf_counter() - t0) * 1e6)
+        us.sort()
+        out[key] = [round(us[len(us) * q // 4], 2) for q in (1, 2, 3)]
+    sync()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default=SCENES)
+    ap.add_argument("--host-calls", type=int, default=400)
     ap.add_argument("--rays-log2", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=1.0)
@@ -97,7 +116,7 @@ def main():
                "grays_per_s_kernel_ms": n / (st["kernel_ms"] * 1e-3) / 1e9,
                "node_tests_per_ray": sc["node_tests"] / n, "tri_tests_per_ray": sc["tri_tests"] / n,
                "analytic_tests_per_ray": sc["analytic_tests"] / n, "fallback_rays": sc["fallback_rays"],
-               "counted_rays": sc["rays"], "hit_fraction": hit_fraction, "tree": scene.tree_info(), "load_s": round(load_s, 2),
+               "host_us_per_call": host_us_per_call(call, stream.synchronize, args.host_calls), "counted_rays": sc["rays"], "hit_fraction": hit_fraction, "tree": scene.tree_info(), "load_s": round(load_s, 2),
                "lib": os.path.relpath(api.LIB_PATH, ROOT)}
         print(json.dumps(out), flush=True)
         scene.close()
