@@ -429,6 +429,62 @@ int ort_radiance_adaptive_device(ort_scene *scene, const void *d_rays, const voi
                                  void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, uint32_t flags, void *hip_stream,
                                  ort_stats *stats);
 
+/* ---- the adaptive camera render: one frame, or a batch of views ---------------------------------
+ * The camera render with a sample count per pixel: "this noise level, at most max_spp samples", and a sample-count map back.
+ * A pixel job under ORT_POLICY_PIXEL is all samples of pixel (x, y) on the stream job_seed(seed, y*W + x); the adaptive render is
+ * that job cut by the rule of ort_radiance_adaptive, unchanged.  Per pixel, every operation a separately rounded f32 operation:
+ *  - Samples.  A sample is a CAMERA sample of the reference (ray.cpp:1215-1426): the aperture draw of ray.cpp:1232 is part of it,
+ *    unlike in the radiance queries.  The pixel's samples run on one xorshift stream that starts at job_seed(seed, y*W + x).
+ *  - Colour sum and second moment.  C, Q, y and the luminance weights are as defined for ort_radiance_adaptive: a sample adds at
+ *    most one vector e to C, and then Q = Q + y*y with y = (0.2126f*e.x + 0.7152f*e.y) + 0.0722f*e.z.
+ *  - When checks happen.  A check runs after sample n when n >= min_spp, n < max_spp and (n - min_spp) % check_every == 0.
+ *  - The check.  As given for ort_radiance_adaptive, operation by operation (fn, Y, m, v, vm, a, b, thr; stop iff vm <= thr*thr).
+ *  - Stopping.  The pixel stops at the first check that says stop, otherwise at n = max_spp.
+ *  - Outputs.  pixel = C / (float)n, component by component (ray.cpp:1428 with n in place of spp).
+ * Per-pixel outputs, each a plane of width*height entries per frame with row 0 at the bottom:
+ *    out_rgb       3 f32 per pixel   the mean colour
+ *    out_spp       u32               n, the samples taken                         (may be NULL)
+ *    out_m2        f32               Q, the sum of squared sample luminance       (may be NULL)
+ *    final_states  u32               the stream's state after sample n            (may be NULL)
+ * Pixels outside the rect are left untouched in every plane.  A caller rebuilds the error estimate from the planes as described
+ * for ort_radiance_adaptive; the known weakness is the same: a pixel that has seen no light in its first min_spp samples stops
+ * black.
+ * Two identities.  (1) With min_spp == max_spp == n no check runs and out_rgb is ort_render_image's at ORT_POLICY_PIXEL and
+ * spp = n, bit for bit.  (2) With a tolerance so large that thr*thr is +inf, every pixel with finite Q stops at min_spp with that
+ * call's bits at spp = min_spp.
+ * Parameters.  params->policy must be ORT_POLICY_PIXEL; any other policy is ORT_ERR_UNSUPPORTED.  params->spp and params->chunk
+ * are ignored: ad->max_spp takes the place of spp before the parameter checks the render call shares.  shard_count > 1 and
+ * ORT_RENDER_PACKED return ORT_ERR_UNSUPPORTED.  ad is judged exactly as ort_radiance_adaptive judges it, rr as the render call
+ * judges it (rr >= 0).
+ * The views form follows ort_render_views: params->seed is ignored; the per-view seed and camera, the rule where a camera may
+ * stand, ORT_MAX_VIEWS and view_count == 0 (ORT_OK without a launch, whatever the other arguments) are as there; the planes hold
+ * view_count frames, view-major.  Frame v is, bit for bit and in every plane, what the single-frame call gives with params->seed
+ * = views[v].seed on a scene whose camera basis is views[v].camera.  The single-frame call is the one-view batch of the scene's own
+ * camera (ort_scene_get_camera) and params->seed.
+ * Errors are reported before any device work, in ort_render_views' order with the ad checks directly after the params checks:
+ * ORT_ERR_INVALID (null out_rgb or views, view cap exceeded, null scene or params, empty or bad params exactly as
+ * ort_render_image judges them with max_spp for spp; then ad == NULL, min_spp < 2, max_spp < min_spp, max_spp > 1 << 24,
+ * check_every == 0, tolerance or floor NaN, infinite or negative), ORT_ERR_UNSUPPORTED (policy, shard, packed, camera outside the
+ * box), ORT_ERR_STATE (scene not committed), ORT_ERR_NO_DEVICE (not uploaded).
+ * The device forms take DEVICE pointers on the scene's device, enqueue on hip_stream (NULL = the default stream) and wait only
+ * when stats != NULL; views is a HOST array in both forms, copied before the call returns.  stats as for the render call; with
+ * ORT_RENDER_COUNTERS, paths is the number of samples taken: the sum of out_spp over the rect of every frame.  No workspace is
+ * needed: PIXEL jobs have no partial planes. */
+
+/* host planes in, host planes out (device staging is internal); synchronous */
+int ort_render_adaptive(ort_scene *scene, const ort_render_params *params, const ort_adaptive *ad, float *out_rgb,
+                        uint32_t *out_spp /* may be NULL */, float *out_m2 /* may be NULL */, uint32_t *final_states /* may be NULL */,
+                        ort_stats *stats);
+int ort_render_adaptive_device(ort_scene *scene, const ort_render_params *params, const ort_adaptive *ad, void *d_out_rgb,
+                               void *d_out_spp, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats);
+/* view_count frames per plane, view-major */
+int ort_render_views_adaptive(ort_scene *scene, const ort_render_params *params, const ort_adaptive *ad, const ort_view *views,
+                              uint32_t view_count, float *out_rgb, uint32_t *out_spp /* may be NULL */, float *out_m2 /* may be NULL */,
+                              uint32_t *final_states /* may be NULL */, ort_stats *stats);
+int ort_render_views_adaptive_device(ort_scene *scene, const ort_render_params *params, const ort_adaptive *ad, const ort_view *views,
+                                     uint32_t view_count, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states,
+                                     void *hip_stream, ort_stats *stats);
+
 /* ---- multi-GPU: block sharding and the one collective -------------------------------------
  * Replaces main()'s shared-memory tile pool (macos_main.mm:565-671: eight pthreads, one queue, one framebuffer)
  * across the GPUs of a node: scene replicated, 8x8 blocks dealt round-robin, every rank renders its blocks into a

@@ -138,14 +138,15 @@ EXPORTS = [
     "ort_gather_framebuffer_local", "ort_raycast", "ort_raycast_device",
     "ort_occluded", "ort_occluded_device", "ort_radiance", "ort_radiance_device",
     "ort_radiance_adaptive", "ort_radiance_adaptive_device",
-    "ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes"]
+    "ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes",
+    "ort_render_adaptive", "ort_render_adaptive_device", "ort_render_views_adaptive", "ort_render_views_adaptive_device"]
 
 _lib = None
 
 
 def build_library():
     """Compile the HIP extension in-tree (hipcc --offload-arch=gfx950)."""
-    subprocess.check_call(["make", "-s", "-j3", "-C", CSRC_DIR])   # three kernel units, one job each
+    subprocess.check_call(["make", "-s", "-j4", "-C", CSRC_DIR])   # four kernel units, one job each
 
 
 def _share_hip_runtime_with_torch():
@@ -203,6 +204,8 @@ def lib():
         for name, argtypes in (
                 ("ort_render_image", [vp, C.POINTER(RenderParams), vp, stats]),
                 ("ort_render_views", [vp, C.POINTER(RenderParams), vp, C.c_uint32, vp, stats]),
+                ("ort_render_adaptive", [vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp, vp, stats]),
+                ("ort_render_views_adaptive", [vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, C.c_uint32, vp, vp, vp, vp, stats]),
                 ("ort_raycast", [vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
                 ("ort_occluded", [vp, vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
                 ("ort_radiance", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_float, vp, vp, C.c_uint32, stats]),
@@ -471,6 +474,72 @@ class Scene:
         views = _views(cameras, seeds)
         st, stats = _stats(want_stats)
         _check(lib().ort_render_views_device(self.handle, C.byref(params), views.ctypes.data, len(views), _ptr(d_out_ptr), _ptr(stream), st))
+        return stats()
+
+    # -- the adaptive camera render: one frame, or a batch of views ----------------------------
+    @staticmethod
+    def _planes(shape, out, want_states):
+        """the four host planes of an adaptive render: zeros, or the caller's (out: (rgb, spp, m2[, states]), checked)"""
+        specs = [(shape + (3,), "<f4"), (shape, "<u4"), (shape, "<f4")] + ([(shape, "<u4")] if want_states else [])
+        if out is None:
+            return [np.zeros(sh, dt) for sh, dt in specs]
+        if len(out) != len(specs):
+            raise ValueError("out must hold %d planes (rgb, spp, m2%s), got %d" % (len(specs), ", states" if want_states else "", len(out)))
+        for a, (sh, dt) in zip(out, specs):
+            if not isinstance(a, np.ndarray) or a.shape != sh or a.dtype != np.dtype(dt) or not a.flags.c_contiguous:
+                raise ValueError("out: every plane must be a C-contiguous array, expected shape %s dtype %s" % (sh, dt))
+        return list(out)
+
+    def render_adaptive(self, width, height, min_spp, max_spp, tolerance, floor=0.05, check_every=4, seed=0, rect=None, rr=0.8,
+                        want_states=False, counters=False, out=None):
+        """render(policy="pixel") with a sample count per pixel: each pixel is sampled until the estimated standard error of
+        its mean luminance is at most tolerance times the mean's magnitude (floor standing in for it in the dark), checked
+        after min_spp samples and then every check_every, at most max_spp times (include/ort.h gives the rule).  Returns (rgb
+        (H, W, 3) float32, spp (H, W) uint32 samples taken, m2 (H, W) float32 sum of squared sample luminance, stats dict),
+        with want_states (rgb, spp, m2, states (H, W) uint32, stats).  Pixels outside rect keep what out's planes held."""
+        ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
+        planes = self._planes((height, width), out, want_states)
+        p = self.params(width, height, 1, seed, "pixel", 0, rect, rr, counters)
+        st, stats = _stats()
+        _check(lib().ort_render_adaptive(self.handle, C.byref(p), C.byref(ad), planes[0].ctypes.data, planes[1].ctypes.data,
+                                         planes[2].ctypes.data, planes[3].ctypes.data if want_states else None, st))
+        return tuple(planes) + (stats(),)
+
+    def render_adaptive_device(self, params, min_spp, max_spp, tolerance, floor, check_every, d_out, d_spp=0, d_m2=0, d_states=0,
+                               stream=None, want_stats=False):
+        """The same into device planes (raw device pointers, e.g. torch tensors' data_ptr(): (H, W, 3) float32 and, where a
+        pointer is given, (H, W) uint32 / float32 / uint32).  params: Scene.params(..., policy="pixel"); its spp is ignored.
+        Enqueued on stream; waits only when want_stats (returns the stats dict)."""
+        ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
+        st, stats = _stats(want_stats)
+        _check(lib().ort_render_adaptive_device(self.handle, C.byref(params), C.byref(ad), _ptr(d_out), _ptr(d_spp), _ptr(d_m2),
+                                                _ptr(d_states), _ptr(stream), st))
+        return stats()
+
+    def render_views_adaptive(self, cameras, seeds, width, height, min_spp, max_spp, tolerance, floor=0.05, check_every=4, rect=None,
+                              rr=0.8, want_states=False, counters=False, out=None):
+        """render_adaptive for a batch of views in one launch (cameras, seeds as render_views): frame v is what
+        render_adaptive gives with seed seeds[v] if the scene's camera were cameras[v].  Returns (rgb (V, H, W, 3), spp (V, H,
+        W), m2 (V, H, W)[, states (V, H, W)], stats dict)."""
+        views = _views(cameras, seeds)
+        ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
+        planes = self._planes((len(views), height, width), out, want_states)
+        p = self.params(width, height, 1, 0, "pixel", 0, rect, rr, counters)
+        st, stats = _stats()
+        _check(lib().ort_render_views_adaptive(self.handle, C.byref(p), C.byref(ad), views.ctypes.data, len(views), planes[0].ctypes.data,
+                                               planes[1].ctypes.data, planes[2].ctypes.data,
+                                               planes[3].ctypes.data if want_states else None, st))
+        return tuple(planes) + (stats(),)
+
+    def render_views_adaptive_device(self, params, cameras, seeds, min_spp, max_spp, tolerance, floor, check_every, d_out, d_spp=0,
+                                     d_m2=0, d_states=0, stream=None, want_stats=False):
+        """The same into device planes of V frames each, view-major.  Enqueued on stream; waits only when want_stats (returns
+        the stats dict).  params.seed and params.spp are ignored."""
+        views = _views(cameras, seeds)
+        ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
+        st, stats = _stats(want_stats)
+        _check(lib().ort_render_views_adaptive_device(self.handle, C.byref(params), C.byref(ad), views.ctypes.data, len(views),
+                                                      _ptr(d_out), _ptr(d_spp), _ptr(d_m2), _ptr(d_states), _ptr(stream), st))
         return stats()
 
     # -- closest-hit ray queries -----------------------------------------------------------

@@ -505,6 +505,45 @@ static int render_views_common(ort_scene *s, const ort_render_params *p, const o
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
+/* The adaptive camera render, one frame or a batch of views.  view_count == 0 is OK whatever else is passed (the views form); then
+   render_views_common's order with the stopping rule's checks directly after the params': nulls and the view cap, the params with
+   ad->max_spp where spp stands (spp and chunk are not the caller's to set here), ad as ort_radiance_adaptive judges it, what the
+   call does not do (any policy but PIXEL, shards, a packed framebuffer, a camera outside the box), the scene's state.  !batch:
+   the single-frame form (views unread), the one-view batch of the scene's own camera and params->seed */
+static int render_adaptive_common(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, const ort_view *views, uint32_t view_count, bool batch,
+                                  bool host, void *out_rgb, void *out_spp, void *out_m2, void *states, void *stream, ort_stats *stats) {
+    if (batch && view_count == 0) return nothing_to_do(stats);
+    if (batch && (!views || !out_rgb)) return fail(ORT_ERR_INVALID, "null views or framebuffer");
+    if (!batch && !out_rgb) return fail(ORT_ERR_INVALID, host ? "null framebuffer" : "null device framebuffer");
+    if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
+    if (!s || !p) return fail(ORT_ERR_INVALID, "null scene or params");
+    ort_render_params q = *p;
+    q.spp = ad && ad->max_spp ? ad->max_spp : 1u; /* a null ad or a max_spp of 0 is check_adaptive's to name */
+    q.chunk = q.spp;
+    int rc = check_param_values(s, &q);
+    if (rc != ORT_OK || (rc = check_adaptive(ad)) != ORT_OK) return rc;
+    if (q.policy != ORT_POLICY_PIXEL) return fail(ORT_ERR_UNSUPPORTED, "the adaptive render cuts one-pixel jobs: it needs the PIXEL policy");
+    if (q.shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, "the adaptive render is not sharded");
+    if (q.flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "the adaptive render has no packed framebuffer");
+    ort_view own;
+    if (batch) {
+        float lo[3], hi[3];
+        ort::scene_origin_box(*s, lo, hi);
+        for (uint32_t v = 0; v < view_count; ++v)
+            if (!view_in_box(views[v].camera, lo, hi))
+                return fail(ORT_ERR_UNSUPPORTED, "view " + std::to_string(v) + ": the camera's aperture is not finite or leaves the box of the scene's shapes and its own "
+                                                 "camera_p (+ 0.25 per side) that the tree was built for; create the scene with a camera_p out there");
+    } else {
+        ort::camera_basis(*s, q.width, q.height, &own.camera);
+        own.seed = q.seed;
+        views = &own;
+    }
+    if ((rc = check_resident(s)) != ORT_OK) return rc;
+    std::string err;
+    rc = ort::device_render_adaptive(s, &q, *ad, views, view_count, host, out_rgb, out_spp, out_m2, states, stream, stats, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
 static int ort_render_views_workspace_bytes_impl(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) {
     if (!p || !bytes) return fail(ORT_ERR_INVALID, "null argument");
     *bytes = ort::render_views_workspace_bytes(p, view_count);
@@ -614,6 +653,10 @@ int ort_render_workspace_bytes(const ort_render_params *p, uint64_t *bytes) { re
 int ort_camera_from_pose(const float p[3], const float quat_xyzw[4], float height_ratio, int32_t width, int32_t height, ort_camera *out) { return guarded([&]() { return ort_camera_from_pose_impl(p, quat_xyzw, height_ratio, width, height, out); }); }
 int ort_render_views(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, float *out_rgb, ort_stats *stats) { return guarded([&]() { return render_views_common(s, p, views, view_count, true, out_rgb, nullptr, stats); }); }
 int ort_render_views_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, void *d_out_rgb, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_views_common(s, p, views, view_count, false, d_out_rgb, hip_stream, stats); }); }
+int ort_render_adaptive(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, nullptr, 1, false, true, out_rgb, out_spp, out_m2, final_states, nullptr, stats); }); }
+int ort_render_adaptive_device(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, nullptr, 1, false, false, d_out_rgb, d_out_spp, d_out_m2, d_final_states, hip_stream, stats); }); }
+int ort_render_views_adaptive(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, const ort_view *views, uint32_t view_count, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, views, view_count, true, true, out_rgb, out_spp, out_m2, final_states, nullptr, stats); }); }
+int ort_render_views_adaptive_device(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, const ort_view *views, uint32_t view_count, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, views, view_count, true, false, d_out_rgb, d_out_spp, d_out_m2, d_final_states, hip_stream, stats); }); }
 int ort_render_views_workspace_bytes(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) { return guarded([&]() { return ort_render_views_workspace_bytes_impl(p, view_count, bytes); }); }
 int ort_shard_block_count(int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, uint64_t *blocks) { return guarded([&]() { return ort_shard_block_count_impl(width, height, shard_index, shard_count, blocks); }); }
 int ort_pack_blocks_host(const float *full_rgb, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, float *packed) { return guarded([&]() { return ort_pack_blocks_host_impl(full_rgb, width, height, shard_index, shard_count, packed); }); }

@@ -20,6 +20,11 @@ void ort_launch_radiance_adaptive(int counters, int diffuse, int tabs, unsigned 
 size_t ort_adaptive_sizeof_scene_view();
 size_t ort_adaptive_sizeof_render_hot();
 size_t ort_adaptive_sizeof_render_view();
+/* the adaptive camera render's kernels (ort_kernels_render_adaptive.hip) */
+void ort_launch_render_adaptive(int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes);
+size_t ort_render_adaptive_sizeof_scene_view();
+size_t ort_render_adaptive_sizeof_render_hot();
+size_t ort_render_adaptive_sizeof_render_view();
 
 namespace ort {
 
@@ -274,9 +279,18 @@ static int launch_wavefront(DeviceScene *d, const SceneView &sv, const RenderVie
 }
 
 /* The path-trace kernel a plan names.  These sixteen variants, the six of a batch of views, the eight of the radiance queries
-   (device_radiance), the eight of the adaptive ones (ort_kernels_adaptive.hip) and the two of ort_kernels_w5.hip are all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
+   (device_radiance), the eight of the adaptive ones (ort_kernels_adaptive.hip), the eight of the adaptive camera render
+   (device_render_adaptive, ort_kernels_render_adaptive.hip) and the two of ort_kernels_w5.hip are all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
    an error, not a fallback. */
 static int launch_path_tracer(const LaunchPlan &pl, hipStream_t stream, const SceneView &sv, const RenderHot &hot, std::string *err) {
+    if (pl.adaptive) { /* pt_adaptive<counters, diffuse, tabs>: the plain loop over a batch of views, every pixel cut by the stopping rule */
+        if (!pl.views || !pl.implicit || pl.mode != PLAN_JOBS_PIXEL || pl.exchange || pl.five || pl.wide || pl.wavefront) {
+            *err = "internal: no adaptive kernel is built for this launch plan";
+            return ORT_ERR_INTERNAL;
+        }
+        ort_launch_render_adaptive(pl.counters, pl.diffuse, pl.tabs, pl.grid, (void *)stream, &sv, &hot);
+        return ORT_OK;
+    }
     if (pl.views) { /* the plain loop with the camera table: counters | diffuse, tabs (implicit follows from both) */
         if (pl.exchange || pl.five || pl.wide || pl.wavefront || pl.implicit != (!pl.counters && pl.tabs) || (pl.counters && pl.diffuse)) {
             *err = "internal: no views kernel is built for this launch plan";
@@ -565,6 +579,91 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
     if (stats && rv.drain && (rc = print_drain_diag(d, pl, err))) return rc;
     if (stats && (rc = read_render_stats(d, pl.counters, stats, err))) return rc;
     if (stats && pl.counters && pl.util && (rc = print_util_diag(d, err))) return rc;
+    return ORT_OK;
+}
+
+/* The adaptive camera render (ort_render_adaptive, ort_render_views_adaptive): view_count frames (the single-frame call passes
+   the scene's own camera and params->seed as its one view), every pixel sampled until the stopping rule ad (checked by the
+   caller) says stop.  What runs is plan_render_adaptive's decision; this is device_render's plumbing for it, with four planes
+   where that has one: rgb (12 bytes a pixel) and, each where asked for (null otherwise), the sample counts, the sums of squared
+   sample luminance and the final states (4 bytes a pixel), view-major.  host: the planes are the caller's memory, staged whole
+   both ways so that pixels outside the rect keep what they held, and the call returns when they are back; otherwise device
+   pointers, one launch enqueued on stream, waited for only with stats.  No workspace: PIXEL jobs have no partial planes */
+int device_render_adaptive(Scene *scene, const ort_render_params *p, const ort_adaptive &ad, const ort_view *views, uint32_t view_count, bool host,
+                           void *out_rgb, void *out_spp, void *out_m2, void *states, void *stream_v, ort_stats *stats, std::string *err) {
+    DeviceScene *d = scene->dev;
+    if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
+    ORT_HIP(hipSetDevice(d->device));
+    if (ort_render_adaptive_sizeof_scene_view() != sizeof(SceneView) || ort_render_adaptive_sizeof_render_hot() != sizeof(RenderHot) ||
+        ort_render_adaptive_sizeof_render_view() != sizeof(RenderView)) {
+        *err = "internal: the adaptive render kernels were built with other argument layouts";
+        return ORT_ERR_INTERNAL;
+    }
+    hipStream_t stream = (hipStream_t)stream_v;
+    int rc;
+    if ((rc = settle_inflight(d, err))) return rc;
+    const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
+    /* the planes as the lanes see them: the caller's device pointers, or the scene's staging buffers holding the caller's words */
+    struct Plane { void *caller; DevBuf *stage; size_t bytes; void *dev; };
+    Plane planes[4] = {{out_rgb, &d->staging, pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u, nullptr},
+                       {out_m2, &d->query_stage[4], pixels * 4u, nullptr}, {states, &d->query_stage[5], pixels * 4u, nullptr}};
+    for (Plane &pn : planes) {
+        pn.dev = pn.caller;
+        if (!host || !pn.caller) continue;
+        if ((rc = pn.stage->ensure(pn.bytes, err))) return rc;
+        pn.dev = pn.stage->p;
+        ORT_HIP(hipMemcpyAsync(pn.dev, pn.caller, pn.bytes, hipMemcpyHostToDevice, stream));
+    }
+
+    SceneView sv = scene_view(scene, d);
+    const LaunchPlan pl = plan_render_adaptive(scene_traits(scene, d), *p, d->knobs, view_count);
+    ort_camera cam; /* sv.cam stays the scene's: the VIEWS lanes do not read it */
+    camera_basis(*scene, p->width, p->height, &cam);
+    memcpy(sv.cam, &cam, sizeof(cam));
+
+    RenderView rv{};
+    rv.W = p->width; rv.H = p->height;
+    rv.x0 = p->x0; rv.y0 = p->y0; rv.x1 = p->x1; rv.y1 = p->y1;
+    rv.spp = ad.max_spp; rv.rr = p->rr;
+    rv.ad_min_spp = ad.min_spp; rv.ad_check_every = ad.check_every;
+    rv.ad_tolerance = ad.tolerance; rv.ad_floor = ad.floor;
+    rv.out = (float *)planes[0].dev;
+    rv.ad_spp = (uint32_t *)planes[1].dev;
+    rv.ad_m2 = (float *)planes[2].dev;
+    rv.final_states = (uint32_t *)planes[3].dev;
+    rv.next_job = d->ctrl();
+    rv.counters = d->ctrl() + 1;
+    rv.mode = pl.mode; rv.nchunks = pl.nchunks; rv.job_count = pl.job_count;
+    rv.shard_count = pl.blocks.shard_count; rv.shard_index = pl.blocks.shard_index;
+    rv.blocks_w = pl.blocks.blocks_w; rv.block_x0 = pl.blocks.block_x0; rv.block_y0 = pl.blocks.block_y0;
+    rv.my_blocks = pl.blocks.my_blocks;
+    rv.refill_below = pl.refill_below; rv.descend_below = pl.descend_below;
+    rv.job_batch = pl.job_batch; rv.batch_until = pl.batch_until;
+    {
+        /* the camera table, as device_render uploads it: the caller's array is read here and not again */
+        std::vector<float> &tab = d->view_tab_host;
+        pack_view_table(views, view_count, tab);
+        if ((rc = d->view_tab.ensure(tab.size() * sizeof(float), err))) return rc;
+        ORT_HIP(hipMemcpyAsync(d->view_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        rv.views = d->view_tab.as<const float4>();
+        rv.view_jobs = pl.view_jobs;
+        rv.view_count = pl.view_count;
+    }
+    ORT_HIP(hipMemsetAsync(d->ctrl(), 0, 128 * sizeof(unsigned long long), stream));
+    ORT_HIP(hipMemcpyAsync(d->rv_dev.p, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
+    const RenderHot hot = render_hot<RenderHot>(rv, d->rv_dev.p);
+    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
+    if ((rc = launch_path_tracer(pl, stream, sv, hot, err))) return rc;
+    ORT_HIP(hipGetLastError());
+    if (stats) ORT_HIP(hipEventRecord(d->ev1, stream));
+    if (host)
+        for (const Plane &pn : planes)
+            if (pn.caller) ORT_HIP(hipMemcpyAsync(pn.caller, pn.dev, pn.bytes, hipMemcpyDeviceToHost, stream));
+    ORT_HIP(hipEventRecord(d->ev_done, stream));
+    d->inflight = true;
+    if (stats || host)
+        if ((rc = settle_inflight(d, err, "reference-order fallback queue overflowed"))) return rc;
+    if (stats && (rc = read_render_stats(d, pl.counters, stats, err))) return rc;
     return ORT_OK;
 }
 

@@ -11,12 +11,12 @@
  * 2-wide tree of ort_tree.cpp with a per-lane stack whose first entries live in LDS
  * (column-per-lane, conflict-free) and whose tail spills to scratch.
  *
- * Included by three translation units: ort_kernels.hip (the library's kernels at four waves per SIMD, and the host side),
- * ort_kernels_w5.hip (the plain-loop kernels at FIVE: 96 registers, 20 LDS stack entries, built with machine LICM off) and
+ * Included by four translation units: ort_kernels.hip (the library's kernels at four waves per SIMD, and the host side),
+ * ort_kernels_w5.hip (the plain-loop kernels at FIVE: 96 registers, 20 LDS stack entries, built with machine LICM off),
  * ort_kernels_adaptive.hip (the adaptive radiance queries' kernels, at the first unit's limits: a unit of their own so that they
- * compile beside it).  Same lane code, other limits (ORT_WAVES_PER_EU, ORT_LDS_STACK, ORT_SPILL_STACK); each unit compiles it in a
- * namespace of its own (ORT_NS), so that two builds of one template are two symbols.  tools/host_sim.cpp compiles it for the host
- * (ORT_HOST_SIM: one simulated lane).
+ * compile beside it) and ort_kernels_render_adaptive.hip (the adaptive camera render's, likewise).  Same lane code, other limits
+ * (ORT_WAVES_PER_EU, ORT_LDS_STACK, ORT_SPILL_STACK); each unit compiles it in a namespace of its own (ORT_NS), so that two builds
+ * of one template are two symbols.  tools/host_sim.cpp compiles it for the host (ORT_HOST_SIM: one simulated lane).
  */
 #ifndef ORT_LANE_H
 #define ORT_LANE_H
@@ -40,6 +40,8 @@
 #define ORT_NS ort_w5
 #elif defined(ORT_ADAPTIVE_TU)
 #define ORT_NS ort_ad
+#elif defined(ORT_RENDER_ADAPTIVE_TU)
+#define ORT_NS ort_ra
 #else
 #define ORT_NS ort
 #endif
@@ -179,7 +181,9 @@ struct RenderView {
     uint32_t ray_tree_spheres, ray_tree_quadrics, ray_tree_boxes; /* what raycast_needs_exact reads (RaycastIO), for the primary rays */
     float ray_lo[3], ray_hi[3];
     /* adaptive radiance queries (ort_radiance_adaptive; the radiance_adaptive_rays kernels): spp above is max_spp; a ray's sample
-       count and its sum of squared sample luminance go to ad_spp and ad_m2 (either may be null), job_count words each */
+       count and its sum of squared sample luminance go to ad_spp and ad_m2 (either may be null), job_count words each.  The
+       adaptive camera render (pt_adaptive): the same fields; ad_spp, ad_m2 and final_states (each may be null) are planes of
+       view_count * W * H words, a pixel's word where its colour is in out */
     uint32_t ad_min_spp, ad_check_every;
     float ad_tolerance, ad_floor;
     uint32_t *ad_spp;
@@ -633,7 +637,8 @@ struct PathState {
     bool primary = true;
 };
 
-/* what a lane of an adaptive radiance query keeps besides its PathState (produce_ray's ADAPT flag): no other kernel has these */
+/* what a lane of an adaptive radiance query or an adaptive camera render keeps besides its PathState (produce_ray's ADAPT flag):
+   no other kernel has these.  radiance_adaptive_rays holds it in registers, pt_adaptive in LDS beside the focal cache */
 struct AdaptState {
     float q = 0;       /* Q: the running sum of squared sample luminance */
     uint32_t next = 0; /* the sample count after which the next check runs; 0: a check has said stop */
@@ -1008,15 +1013,17 @@ ORT_D bool adaptive_stop(V3 C, float Q, uint32_t n, float tolerance, float lum_f
    with wo = -normalize(d) (ray.cpp:1240-1246 for a camera without an aperture), and no aperture angle is drawn; the job ends
    with 12 bytes at out + 3 j and its stream's state.  The ray is read again for every sample (24 bytes from L2 per path of
    hundreds of node tests) instead of held in six registers through the traversal loop; P.job_index | P.pxy << 32 is the ray index */
-/* ADAPT: adaptive radiance queries (ort_radiance_adaptive; with RAYS): spp_u is max_spp, and the job also ends at the first
+/* ADAPT: adaptive radiance queries (ort_radiance_adaptive; with RAYS) and the adaptive camera render (ort_render_adaptive,
+   ort_render_views_adaptive; with VIEWS, one-pixel jobs in JOBS_PIXEL mode): spp_u is max_spp, and the job also ends at the first
    check of the stopping rule (adaptive_stop) that says so.  A (the lane's AdaptState) holds the sum of squared sample
    luminance and the sample count of the next check; the job writes its sample count and that sum besides the mean, which
-   divides by the samples taken.  Everything of it sits under if constexpr (ADAPT): the other kernels compile as without it */
+   divides by the samples taken -- per ray for a query, per pixel of its view's planes for a render, with the stream's state.
+   Everything of it sits under if constexpr (ADAPT): the other kernels compile as without it */
 template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool VIEWS = false, bool RAYS = false, bool ADAPT = false>
 ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, Prof &pr,
                        float *focal_cache = nullptr, int focal_stride = 0, uint32_t spp_u = 0, uint32_t *late_flag = nullptr, bool no_new_job = false,
                        unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
-    static_assert(!ADAPT || (RAYS && IMPLICIT), "the adaptive rule is built for the radiance queries");
+    static_assert(!ADAPT || (IMPLICIT && (RAYS || VIEWS)), "the adaptive rule is built for the radiance queries and for one-pixel jobs of a batch of views");
     /* VIEWS: unused; every lane reads its view's camera where it needs it (load_view_camera) */
     const V3 cam_p = mk(sv.cam[0], sv.cam[1], sv.cam[2]);
     const V3 cam_x = mk(sv.cam[3], sv.cam[4], sv.cam[5]);
@@ -1132,6 +1139,12 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 if constexpr (VIEWS) p = view_pixel_ptr(rv, P.job_index, P.jyp >> 16, px, py);
                 else p = pixel_ptr(rv, P.jyp >> 16, px, py);
                 p[0] = o.x; p[1] = o.y; p[2] = o.z;
+                if constexpr (ADAPT) { /* JOBS_PIXEL: the pixel's words of its view's planes, view_count frames of W * H each */
+                    const size_t at = ((size_t)P.job_index * (size_t)rv.H + (size_t)py) * (size_t)rv.W + (size_t)px;
+                    if (rv.c->ad_spp) rv.c->ad_spp[at] = P.sample;
+                    if (rv.c->ad_m2) rv.c->ad_m2[at] = A->q;
+                    if (rv.c->final_states) rv.c->final_states[at] = P.rng;
+                }
                 if (IMPLICIT) {
                     P.ps = PS_NEED_JOB; /* a one-pixel job ends with its pixel */
                 } else {
@@ -1627,9 +1640,11 @@ ORT_D void flush_counters(const RenderHot &rv, const Counters &c, bool all) {
 }
 
 /* persistent mode: one lane runs jobs until the job space is empty */
-template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool WIDE = false, bool VIEWS = false>
+/* ADAPT: the adaptive camera render (pt_adaptive): the same loop, a pixel ending where produce_ray's stopping rule says; A is the
+   lane's AdaptState, wherever the caller keeps it */
+template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool WIDE = false, bool VIEWS = false, bool ADAPT = false>
 ORT_D void pt_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, float *lds_focal, const int tid,
-                   const uint32_t lane_id, bool prof_on = false, unsigned long long *pool = nullptr) {
+                   const uint32_t lane_id, bool prof_on = false, unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
     uint32_t spill[kSpillStack];
     const uint32_t spp_u = IMPLICIT ? ((rv.mode == JOBS_PIXEL) ? rv.c->spp : rv.c->chunk) : 0u; /* samples per (one-pixel) job */
     Prof pr;
@@ -1649,6 +1664,8 @@ ORT_D void pt_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, 
             ORT_PHASE(pr, sv, 7, true);
             if (P.ps == PS_HIT) resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true, WIDE>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
             ORT_PHASE(pr, sv, 0, P.ps == PS_HIT);
+            if constexpr (ADAPT) tracing = produce_ray<COUNTERS, DIFFUSE, TABS, IMPLICIT, VIEWS, false, true>(sv, rv, tab, P, h, c, pr, lds_focal + tid, kBlock, spp_u, nullptr, false, pool, A);
+            else
             tracing = produce_ray<COUNTERS, DIFFUSE, TABS, IMPLICIT, VIEWS>(sv, rv, tab, P, h, c, pr, lds_focal + tid, kBlock, spp_u, nullptr, false, pool);
             if (tracing) {
                 begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
@@ -2095,6 +2112,31 @@ pt_persistent(SceneView sv, RenderHot rv) {
     }
 }
 
+/* The adaptive camera render (ort_render_adaptive, ort_render_views_adaptive): the plain loop over the implicit one-pixel jobs of a
+   batch of views (JOBS_PIXEL; the single frame is the one-view batch of the scene's own camera), every pixel cut by the stopping
+   rule.  Built in ort_kernels_render_adaptive.hip alone.  The lane's AdaptState (Q and the next check's sample count) lives in LDS
+   beside the focal cache, not in registers: it is touched once per SAMPLE -- hundreds of node tests -- while two more registers
+   would be live through the whole traversal loop of a kernel that sits at its 128-register cap and spills already; 2 KB of LDS
+   per workgroup leaves the four workgroups per CU their room.  No probes, no drain times */
+template <bool COUNTERS, bool DIFFUSE, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+pt_adaptive(SceneView sv, RenderHot rv) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ float lds_focal[3 * kBlock]; /* focal[component][lane] */
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as pt_persistent */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+#ifdef ORT_ADAPT_IN_REGISTERS /* A/B builds: the resource figures of the other choice (profiles/r12_render_adaptive.md) */
+    AdaptState adapt, *const A = &adapt;
+#else
+    static_assert(sizeof(AdaptState) == sizeof(uint2), "a lane's AdaptState is two words of LDS");
+    __shared__ uint2 lds_adapt[kBlock]; /* raw words: produce_ray sets both at every pixel's start, before it reads them */
+    AdaptState *const A = reinterpret_cast<AdaptState *>(lds_adapt) + threadIdx.x;
+#endif
+    if (TABS) fill_tab(sv, lds_tab);
+    pt_lane<COUNTERS, DIFFUSE, TABS, true, false, true, true>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
+                                                              wave_job_pool(rv, lds_pool), A);
+}
+
 /* the same with the ray exchange (pt_lane_x): implicit job spaces only, LDS tables required */
 template <bool COUNTERS, bool DIFFUSE>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
@@ -2119,7 +2161,7 @@ pt_persistent_x(SceneView sv, RenderHot rv) {
     }
 }
 
-#if !defined(ORT_W5_TU) && !defined(ORT_ADAPTIVE_TU) /* the five-waves unit only needs the path-trace kernels, the adaptive one its own */
+#if !defined(ORT_W5_TU) && !defined(ORT_ADAPTIVE_TU) && !defined(ORT_RENDER_ADAPTIVE_TU) /* the five-waves unit only needs the path-trace kernels, the adaptive ones their own */
 /* wavefront kernels: fixed-size grids, grid-stride over the slots */
 template <bool COUNTERS>
 __global__ void __launch_bounds__(kBlock) wf_shade(SceneView sv, RenderHot rv, WfView wf, int count_active) {
@@ -2177,7 +2219,7 @@ __global__ void combine_chunks_views(RenderHot rv) {
     combine_pixel(rv, idx % per_view, (uint32_t)(idx / per_view));
 }
 
-#endif /* !ORT_W5_TU && !ORT_ADAPTIVE_TU */
+#endif /* !ORT_W5_TU && !ORT_ADAPTIVE_TU && !ORT_RENDER_ADAPTIVE_TU */
 #endif /* !ORT_HOST_SIM */
 
 #ifndef ORT_W5_TU

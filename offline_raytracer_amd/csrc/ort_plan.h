@@ -2,7 +2,7 @@
  * ort_plan.h -- the launch policy of the render call, of a batch of views and of the three ray queries, as arithmetic: what
  * ort_kernels.hip launches, with which grid and which thresholds, decided from a few facts about the uploaded scene
  * (SceneTraits), the render parameters or the ray count, and the developer knobs: plan_render for ort_render_image and
- * ort_render_views, plan_ray_query for ort_raycast and ort_occluded, plan_radiance for ort_radiance.  Host-only and free of HIP,
+ * ort_render_views, plan_render_adaptive for ort_render_adaptive and ort_render_views_adaptive, plan_ray_query for ort_raycast and ort_occluded, plan_radiance for ort_radiance.  Host-only and free of HIP,
  * so that tools/launch_plan.cpp and tests/test_launch_plan.py can hold the measured crossovers without a device.
  * ort_kernels.hip turns a LaunchPlan or a QueryPlan into launches and decides nothing.
  */
@@ -188,6 +188,7 @@ struct LaunchPlan {
     /* a batch of views (ort_render_views, view_count > 1): the plain loop's VIEWS kernels, whose lanes read their camera from a
        per-view table; the job space is view_count times the single view's, the view outermost */
     bool views = false;
+    bool adaptive = false; /* the adaptive camera render (plan_render_adaptive): the pt_adaptive kernels <counters, diffuse, tabs> */
     uint32_t view_count = 1;
     unsigned long long view_jobs = 0; /* jobs of one view (job_count / view_count) */
     unsigned int grid = 1;
@@ -337,6 +338,36 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
     /* IMPLICIT job spaces (PIXEL / CHUNK policies): the variant whose lanes carry no job rect / count / index */
     pl.implicit = !wavefront && !counters && tabs && pl.mode != PLAN_JOBS_EXPLICIT;
     pl.grid = grid;
+    return pl;
+}
+
+/* The launch of the adaptive camera render (ort_render_adaptive, ort_render_views_adaptive; the pt_adaptive kernels) over
+   view_count >= 1 frames: always the plain persistent loop at four waves, over the implicit one-pixel jobs of the PIXEL policy,
+   with the camera read from the view table -- the single frame is the one-view batch of the scene's own camera.  The job space is
+   plan_render's for a batch of views, [view][block][pixel], and so are the grid, the refill and descend thresholds and the batch
+   rules; p.spp and p.chunk are not read (a job's length is the stopping rule's to decide, at most max_spp).  The ray exchange,
+   the five-waves unit, the wide tree and wavefront mode are not built with the rule and their knobs are not looked at;
+   ORT_DEBUG_UTIL and ORT_DEBUG_DRAIN have no probes here.  Both BSDF flavours exist with counters, as for the radiance queries;
+   every variant is IMPLICIT.  No partial planes, no stashes: no workspace. */
+inline LaunchPlan plan_render_adaptive(const SceneTraits &t, const ort_render_params &p, const Knobs &kn, uint32_t view_count = 1) {
+    LaunchPlan pl;
+    plan_loop_exits(tree_is_cache_resident(t.fast_tree_bytes, kn.cache_resident), kn, &pl.refill_below, &pl.descend_below);
+    pl.blocks = block_grid_for(&p); /* the caller has refused shards: the blocks under the rect */
+    pl.mode = PLAN_JOBS_PIXEL;
+    pl.nchunks = 1;
+    pl.view_jobs = (unsigned long long)pl.blocks.my_blocks * 64ull;
+    pl.views = true;
+    pl.view_count = view_count;
+    pl.job_count = pl.view_jobs * view_count;
+    pl.adaptive = true;
+    pl.counters = (p.flags & ORT_RENDER_COUNTERS) != 0;
+    pl.diffuse = t.diffuse_only && !kn.general_kernel;
+    pl.tabs = (t.tab_flags & kPlanAllTabs) == kPlanAllTabs && kn.lds_tables != 0;
+    pl.implicit = true;
+    unsigned long long blocks = (pl.job_count + kPlanBlock - 1) / kPlanBlock;
+    pl.grid = (unsigned int)(blocks < t.max_blocks ? blocks : t.max_blocks);
+    if (pl.grid == 0) pl.grid = 1;
+    plan_job_batches(pl.job_count, (unsigned long long)pl.grid * kPlanBlock, kn, &pl.job_batch, &pl.batch_until);
     return pl;
 }
 

@@ -217,6 +217,11 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
                   void *d_out, float *h_out, void *stream, uint32_t *final_states, ort_stats *stats, std::string *err,
                   const ort_view *views = nullptr, uint32_t view_count = 1);
 int device_unit_eval(int device, const void *records, uint32_t n, float *out, std::string *err);
+/* the adaptive camera render: view_count >= 1 frames, every pixel cut by the stopping rule ad.  The four planes (out_spp, out_m2
+   and states may each be null) are view-major, and either the caller's memory (host: staged, synchronous) or device pointers
+   (enqueued on stream, waited for only with stats) */
+int device_render_adaptive(Scene *scene, const ort_render_params *p, const ort_adaptive &ad, const ort_view *views, uint32_t view_count, bool host,
+                           void *out_rgb, void *out_spp, void *out_m2, void *states, void *stream, ort_stats *stats, std::string *err);
 /* One ray query call.  host: the arrays are the caller's memory, staged to the device in bounded slices, and the call returns
    when the answers are back; otherwise they are device pointers and the call is one launch enqueued on stream (it waits only
    for stats).  Every array is passed once, whichever form it is */

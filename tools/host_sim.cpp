@@ -11,7 +11,7 @@
  * kernel.  The library never loads, links or runs it: the render call has no CPU fallback
  * (tests/test_host.py holds its image against the oracle; nothing else uses it).
  *
- * The ray-query lanes (raycast_lane, occluded_lane, radiance_lane with and without its adaptive rule) and the batch-of-views flavour of pt_lane run here too, on
+ * The ray-query lanes (raycast_lane, occluded_lane, radiance_lane with and without its adaptive rule), the batch-of-views flavour of pt_lane and its adaptive one run here too, on
  * the tables the product's own host code packs (ort_setup.h): tests/test_query_lanes_host.py holds them against the
  * reference's answers and the oracle, tests/test_host_sanitizers.py runs the same binary built with ASan + UBSan
  * (make host_sim_san).
@@ -23,6 +23,9 @@
  *   or: host_sim --radiance scn base rays.f32 seeds.u32 spp rr out.f32 states.u32
  *   or: host_sim --radiance-adaptive scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
  *   or: host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32   (cams: p, x, y, z axes, 12 floats a view)
+ *   or: host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
+ *       (the adaptive camera render of the scene's own camera: pt_lane<..., VIEWS, ADAPT> over a one-view batch; the planes start
+ *       at the guard values -7.0f, 0xeeeeeeee, -1.0f, 0xdddddddd, which pixels outside the rect keep)
  * All files raw little-endian.  SIM_TABS=1: the TABS = true lane code, on a heap copy of the LDS tables' image.
  */
 #define ORT_HOST_SIM 1
@@ -399,6 +402,59 @@ static int views_mode(char **a) { /* scn base cams.f32 seeds.u32 W H spp policy 
     return write_bytes(a[9], out.data(), out.size() * sizeof(float)) ? 0 : 1;
 }
 
+/* the adaptive camera render (ort_render_adaptive): what device_render_adaptive sets up, for one simulated lane per thread */
+static int render_adaptive_mode(char **a) { /* scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32 */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
+    const int W = atoi(a[2]), H = atoi(a[3]), x0 = atoi(a[4]), y0 = atoi(a[5]), x1 = atoi(a[6]), y1 = atoi(a[7]);
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || x0 < 0 || y0 < 0 || x1 > W || y1 > H || x0 >= x1 || y0 >= y1) { fprintf(stderr, "bad frame size or rect\n"); return 1; }
+    ort_adaptive ad{(uint32_t)strtoul(a[9], 0, 10), (uint32_t)strtoul(a[10], 0, 10), (uint32_t)strtoul(a[11], 0, 10), float_arg(a[12]), float_arg(a[13])};
+    if (ad.min_spp < 2u || ad.max_spp < ad.min_spp || ad.max_spp > (1u << 24) || ad.check_every == 0u) { fprintf(stderr, "bad adaptive parameters\n"); return 1; }
+    ort_view view;
+    camera_basis(*S.scene, W, H, &view.camera);
+    view.seed = (uint32_t)strtoul(a[8], 0, 10);
+    memcpy(S.sv.cam, &view.camera, sizeof(view.camera)); /* unread by the VIEWS lanes */
+    std::vector<float> tab_host;
+    pack_view_table(&view, 1, tab_host);
+    std::vector<float4> view_tab(4u);
+    memcpy(view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
+    const size_t n = (size_t)W * H; /* exactly: a write past a plane's end is a write past the block */
+    std::vector<float> out(3 * n, -7.0f), m2(n, -1.0f);
+    std::vector<uint32_t> spp(n, 0xeeeeeeeeu), states(n, 0xddddddddu);
+    ort_render_params p{};
+    p.width = W; p.height = H; p.x0 = x0; p.y0 = y0; p.x1 = x1; p.y1 = y1;
+    const BlockGrid g = block_grid_for(&p); /* the blocks under the rect, as plan_render_adaptive counts them */
+    RenderView rv{};
+    rv.mode = JOBS_PIXEL; rv.nchunks = 1;
+    rv.W = W; rv.H = H; rv.x0 = x0; rv.y0 = y0; rv.x1 = x1; rv.y1 = y1;
+    rv.spp = ad.max_spp; rv.rr = (float)atof(a[14]);
+    rv.ad_min_spp = ad.min_spp; rv.ad_check_every = ad.check_every; rv.ad_tolerance = ad.tolerance; rv.ad_floor = ad.floor;
+    rv.out = out.data(); rv.ad_spp = spp.data(); rv.ad_m2 = m2.data(); rv.final_states = states.data();
+    rv.shard_count = g.shard_count; rv.shard_index = g.shard_index;
+    rv.blocks_w = g.blocks_w; rv.block_x0 = g.block_x0; rv.block_y0 = g.block_y0; rv.my_blocks = g.my_blocks;
+    rv.view_jobs = (unsigned long long)g.my_blocks * 64; rv.view_count = 1; rv.views = view_tab.data();
+    rv.job_count = rv.view_jobs;
+    rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
+    rv.refill_below = 12;
+    rv.descend_below = getenv("SIM_DESCEND_BELOW") ? atoi(getenv("SIM_DESCEND_BELOW")) : 8;
+    const RenderHot hot = render_hot<RenderHot>(rv, &rv);
+    const bool diffuse_only = getenv("SIM_DIFFUSE") != nullptr; /* caller vouches for Ks = Kt = 0 */
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
+        AdaptState A; /* the lane's own, as pt_adaptive's slot of LDS */
+        if (diffuse_only) {
+            if (S.tab) pt_lane<true, true, true, true, false, true, true>(sv, hot, S.tab, stack, focal, 0, w, false, nullptr, &A);
+            else pt_lane<true, true, false, true, false, true, true>(sv, hot, nullptr, stack, focal, 0, w, false, nullptr, &A);
+        } else {
+            if (S.tab) pt_lane<true, false, true, true, false, true, true>(sv, hot, S.tab, stack, focal, 0, w, false, nullptr, &A);
+            else pt_lane<true, false, false, true, false, true, true>(sv, hot, nullptr, stack, focal, 0, w, false, nullptr, &A);
+        }
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return write_bytes(a[15], out.data(), 12 * n) && write_bytes(a[16], spp.data(), 4 * n) && write_bytes(a[17], m2.data(), 4 * n) &&
+           write_bytes(a[18], states.data(), 4 * n) ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
     if (argc == 4 && mode == "--unit") return unit_mode(argv[2], argv[3]);
@@ -407,6 +463,7 @@ int main(int argc, char **argv) {
     if (argc == 10 && mode == "--radiance") return radiance_mode(argv + 2);
     if (argc == 16 && mode == "--radiance-adaptive") return radiance_adaptive_mode(argv + 2);
     if (argc == 12 && mode == "--views") return views_mode(argv + 2);
+    if (argc == 21 && mode == "--render-adaptive") return render_adaptive_mode(argv + 2);
     if (argc < 10 || mode.rfind("--", 0) == 0) {
         fprintf(stderr, "usage: host_sim scn base W H spp seed policy chunk out.f32 [shard_index shard_count]\n"
                         "       host_sim --unit records.bin out.f32\n"
@@ -414,7 +471,8 @@ int main(int argc, char **argv) {
                         "       host_sim --occluded scn base rays.f32 tmax.f32|- out.u8\n"
                         "       host_sim --radiance scn base rays.f32 seeds.u32 spp rr out.f32 states.u32\n"
                         "       host_sim --radiance-adaptive scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
-                        "       host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32\n");
+                        "       host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32\n"
+                        "       host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n");
         return 2;
     }
     int W = atoi(argv[3]), H = atoi(argv[4]);

@@ -4,7 +4,9 @@
    query=raycast|occluded|radiance count=N [counters=1]: the QueryPlan of that ray query over N rays (plan_ray_query,
    plan_radiance) instead of a render's LaunchPlan.  Otherwise
    keys: the SceneTraits and ort_render_params fields by name, policy=pixel|chunk, counters=1, explicit_jobs=1 job_count=N,
-   w5_layout_ok=0, views=N (the plan of an ort_render_views batch of N views; its fields are appended to the line); max_blocks
+   w5_layout_ok=0, views=N (the plan of an ort_render_views batch of N views; its fields are appended to the line), adaptive=1
+   (plan_render_adaptive: the plan of ort_render_adaptive, or with views=N of ort_render_views_adaptive; "adaptive" and the
+   views fields are appended); max_blocks
    defaults to what an upload on cu_count units fixes.  tab_flags, where not given, follows from
    materials= (index 0 included), lights=, pro_boxes=, pro_spheres=, pro_cyls= as at upload (table_fit_flags; all 0 by default).  tests/test_launch_plan.py holds the measured
    crossovers and the knobs the GPU tests force kernels with against it. */
@@ -26,7 +28,7 @@ int main(int argc, char **argv) {
     unsigned long materials = 0, lights = 0, pro_boxes = 0, pro_spheres = 0, pro_cyls = 0;
     unsigned long long job_count = 0;
     unsigned long view_count = 1;
-    bool views_given = false;
+    bool views_given = false, adaptive = false;
     const char *query = nullptr;
     unsigned long long count = 0;
     for (int i = 1; i < argc; ++i) {
@@ -64,6 +66,7 @@ int main(int argc, char **argv) {
         else if (is("query")) query = v;
         else if (is("count")) count = strtoull(v, nullptr, 0);
         else if (is("views")) { view_count = strtoul(v, nullptr, 0); views_given = true; }
+        else if (is("adaptive")) adaptive = atoi(v) != 0;
         else { fprintf(stderr, "launch_plan: unknown argument %s\n", argv[i]); return 2; }
     }
     if (!tab_flags_given) t.tab_flags = ort::table_fit_flags(materials, lights, (uint32_t)pro_boxes, (uint32_t)pro_spheres, (uint32_t)pro_cyls);
@@ -79,7 +82,9 @@ int main(int argc, char **argv) {
     }
     if (!explicit_jobs && p.policy == ORT_POLICY_CHUNK && p.chunk == 0) { fprintf(stderr, "launch_plan: chunk=0\n"); return 2; }
     if (views_given && (view_count < 1 || view_count > ORT_MAX_VIEWS || explicit_jobs)) { fprintf(stderr, "launch_plan: views=1..%u, implicit job spaces only\n", ORT_MAX_VIEWS); return 2; }
-    const ort::LaunchPlan l = ort::plan_render(t, p, explicit_jobs, job_count, w5_layout_ok, kn, (uint32_t)view_count);
+    if (adaptive && (explicit_jobs || p.policy != ORT_POLICY_PIXEL || p.shard_count > 1)) { fprintf(stderr, "launch_plan: adaptive=1 needs policy=pixel, implicit jobs and no shards\n"); return 2; }
+    const ort::LaunchPlan l = adaptive ? ort::plan_render_adaptive(t, p, kn, (uint32_t)view_count)
+                                       : ort::plan_render(t, p, explicit_jobs, job_count, w5_layout_ok, kn, (uint32_t)view_count);
     printf("{\"wavefront\": %d, \"exchange\": %d, \"five\": %d, \"wide\": %d, \"counters\": %d, \"diffuse\": %d, \"tabs\": %d, \"implicit\": %d, \"util\": %d, "
            "\"grid\": %u, \"mode\": %d, \"nchunks\": %u, \"job_count\": %llu, \"my_blocks\": %u, \"refill_below\": %d, \"descend_below\": %d, "
            "\"capL\": %u, \"capR\": %u, \"long_min\": %u, \"long_refill\": %u, \"inflight_cap\": %u, \"park_min\": %u, \"endgame_from\": %llu, "
@@ -89,7 +94,8 @@ int main(int argc, char **argv) {
            l.blocks.my_blocks, l.refill_below, l.descend_below, l.capL, l.capR, l.long_min, l.long_refill, l.inflight_cap, l.park_min,
            l.endgame_from, l.stash_wave_f4, l.block_major, l.job_batch, l.batch_until, l.partial_bytes, l.stash_bytes, l.drain_bytes, t.max_blocks,
            t.tab_flags, ort::kPlanTabMatCap, ort::kPlanTabLightCap, ort::kPlanTabProCap);
-    if (views_given) printf(", \"views\": %d, \"view_count\": %u, \"view_jobs\": %llu", l.views, l.view_count, l.view_jobs);
+    if (adaptive) printf(", \"adaptive\": %d", l.adaptive);
+    if (views_given || adaptive) printf(", \"views\": %d, \"view_count\": %u, \"view_jobs\": %llu", l.views, l.view_count, l.view_jobs);
     printf("}\n");
     return 0;
 }
