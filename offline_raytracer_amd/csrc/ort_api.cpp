@@ -100,15 +100,20 @@ void tile32_jobs(const ort_render_params *p, std::vector<ort_tile_job> *jobs) {
         }
 }
 
-/* out: the caller's memory (host) or a device pointer; device_render takes them apart */
+/* one camera render on the device: out_rgb and the adaptive render's three other planes as the call's form has them */
+int run_render(ort_scene *scene, const ort_render_params *p, const ort::RenderCall &c, void *out_rgb, void *out_spp = nullptr, void *out_m2 = nullptr,
+               void *states = nullptr) {
+    std::string err;
+    const int rc = ort::device_render(scene, p, c, out_rgb, out_spp, out_m2, states, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
+/* out: the caller's memory (host) or a device pointer */
 int render_common(ort_scene *scene, const ort_render_params *p, bool host, void *out, void *stream, ort_stats *stats) {
-    void *d_out = host ? nullptr : out;
-    float *h_out = host ? (float *)out : nullptr;
     int rc = check_params(scene, p);
     if (rc != ORT_OK) return rc;
-    std::string err;
+    std::vector<ort_tile_job> jobs;
     if (p->policy == ORT_POLICY_TILE32 || p->policy == ORT_POLICY_WHOLE) {
-        std::vector<ort_tile_job> jobs;
         if (p->policy == ORT_POLICY_TILE32) {
             tile32_jobs(p, &jobs);
         } else {
@@ -117,11 +122,10 @@ int render_common(ort_scene *scene, const ort_render_params *p, bool host, void 
             jobs.push_back(j);
         }
         if (jobs.empty()) return ORT_OK;
-        rc = ort::device_render(scene, p, jobs.data(), (uint32_t)jobs.size(), d_out, h_out, stream, nullptr, stats, &err);
-    } else {
-        rc = ort::device_render(scene, p, nullptr, 0, d_out, h_out, stream, nullptr, stats, &err);
     }
-    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+    ort::RenderCall c{host, stream, stats}; /* the fields not named stay null / zero: no jobs, the scene's camera, no stopping rule */
+    if (!jobs.empty()) { c.jobs = jobs.data(); c.job_count = (uint32_t)jobs.size(); }
+    return run_render(scene, p, c, out);
 }
 
 template <typename T>
@@ -338,9 +342,9 @@ static int ort_tiled_raytrace_batch_impl(ort_scene *s, float *out_rgb, int32_t w
         if (j.spp == 0) return fail(ORT_ERR_INVALID, "job spp must be >= 1");
     }
     if (job_count == 0) return ORT_OK;
-    std::string err;
-    rc = ort::device_render(s, &p, jobs, job_count, nullptr, out_rgb, nullptr, final_states, stats, &err);
-    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+    ort::RenderCall c{true, nullptr, stats};
+    c.jobs = jobs; c.job_count = job_count; c.job_states = final_states;
+    return run_render(s, &p, c, out_rgb);
 }
 
 static int ort_tiled_raytrace_impl(ort_scene *s, float *out_rgb, int32_t width, int32_t height, int32_t x0, int32_t y0, int32_t x1,
@@ -480,6 +484,17 @@ static bool view_in_box(const ort_camera &c, const float lo[3], const float hi[3
     return true;
 }
 
+/* every view's aperture lies in the scene's box */
+static int check_views_in_box(const ort_scene *s, const ort_view *views, uint32_t view_count) {
+    float lo[3], hi[3];
+    ort::scene_origin_box(*s, lo, hi);
+    for (uint32_t v = 0; v < view_count; ++v)
+        if (!view_in_box(views[v].camera, lo, hi))
+            return fail(ORT_ERR_UNSUPPORTED, "view " + std::to_string(v) + ": the camera's aperture is not finite or leaves the box of the scene's shapes and its own "
+                                             "camera_p (+ 0.25 per side) that the tree was built for; create the scene with a camera_p out there");
+    return ORT_OK;
+}
+
 /* view_count == 0 is OK whatever else is passed; then argument errors, what the call does not do, and the scene's state */
 static int render_views_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool host, void *out,
                                void *stream, ort_stats *stats) {
@@ -493,16 +508,11 @@ static int render_views_common(ort_scene *s, const ort_render_params *p, const o
         return fail(ORT_ERR_UNSUPPORTED, "a batch of views needs a per-pixel seeding policy (PIXEL or CHUNK)");
     if (p->shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, "a batch of views is not sharded: deal views to GPUs, not blocks");
     if (p->flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "a batch of views has no packed framebuffer");
-    float lo[3], hi[3];
-    ort::scene_origin_box(*s, lo, hi);
-    for (uint32_t v = 0; v < view_count; ++v)
-        if (!view_in_box(views[v].camera, lo, hi))
-            return fail(ORT_ERR_UNSUPPORTED, "view " + std::to_string(v) + ": the camera's aperture is not finite or leaves the box of the scene's shapes and its own "
-                                             "camera_p (+ 0.25 per side) that the tree was built for; create the scene with a camera_p out there");
+    if ((rc = check_views_in_box(s, views, view_count)) != ORT_OK) return rc;
     if ((rc = check_resident(s)) != ORT_OK) return rc;
-    std::string err;
-    rc = ort::device_render(s, p, nullptr, 0, host ? nullptr : out, host ? (float *)out : nullptr, stream, nullptr, stats, &err, views, view_count);
-    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+    ort::RenderCall c{host, stream, stats};
+    c.views = views; c.view_count = view_count;
+    return run_render(s, p, c, out);
 }
 
 /* The adaptive camera render, one frame or a batch of views.  view_count == 0 is OK whatever else is passed (the views form); then
@@ -527,21 +537,16 @@ static int render_adaptive_common(ort_scene *s, const ort_render_params *p, cons
     if (q.flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "the adaptive render has no packed framebuffer");
     ort_view own;
     if (batch) {
-        float lo[3], hi[3];
-        ort::scene_origin_box(*s, lo, hi);
-        for (uint32_t v = 0; v < view_count; ++v)
-            if (!view_in_box(views[v].camera, lo, hi))
-                return fail(ORT_ERR_UNSUPPORTED, "view " + std::to_string(v) + ": the camera's aperture is not finite or leaves the box of the scene's shapes and its own "
-                                                 "camera_p (+ 0.25 per side) that the tree was built for; create the scene with a camera_p out there");
+        if ((rc = check_views_in_box(s, views, view_count)) != ORT_OK) return rc;
     } else {
         ort::camera_basis(*s, q.width, q.height, &own.camera);
         own.seed = q.seed;
         views = &own;
     }
     if ((rc = check_resident(s)) != ORT_OK) return rc;
-    std::string err;
-    rc = ort::device_render_adaptive(s, &q, *ad, views, view_count, host, out_rgb, out_spp, out_m2, states, stream, stats, &err);
-    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+    ort::RenderCall c{host, stream, stats};
+    c.views = views; c.view_count = view_count; c.ad = ad;
+    return run_render(s, &q, c, out_rgb, out_spp, out_m2, states);
 }
 
 static int ort_render_views_workspace_bytes_impl(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) {

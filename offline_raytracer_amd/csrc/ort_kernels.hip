@@ -11,20 +11,13 @@
 #include "ort_setup.h"
 
 #ifndef ORT_HOST_SIM /* tools/host_sim.cpp drives the lane code itself and has no device */
-/* the five-waves build of the plain loop (ort_kernels_w5.hip) */
-void ort_launch_w5(int diffuse, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes);
-size_t ort_w5_sizeof_scene_view();
-size_t ort_w5_sizeof_render_hot();
-/* the adaptive radiance queries' kernels (ort_kernels_adaptive.hip) */
-void ort_launch_radiance_adaptive(int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes);
-size_t ort_adaptive_sizeof_scene_view();
-size_t ort_adaptive_sizeof_render_hot();
-size_t ort_adaptive_sizeof_render_view();
-/* the adaptive camera render's kernels (ort_kernels_render_adaptive.hip) */
-void ort_launch_render_adaptive(int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes);
-size_t ort_render_adaptive_sizeof_scene_view();
-size_t ort_render_adaptive_sizeof_render_hot();
-size_t ort_render_adaptive_sizeof_render_view();
+/* the sibling kernel units: a launcher each, and the sizes of the argument structs as the unit compiled them (same_layout) */
+void ort_launch_w5(int diffuse, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes); /* the five-waves build of the plain loop */
+void ort_w5_layout(size_t sizes[3]);
+void ort_launch_radiance_adaptive(int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes); /* ort_kernels_adaptive.hip */
+void ort_adaptive_layout(size_t sizes[3]);
+void ort_launch_render_adaptive(int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes); /* ort_kernels_render_adaptive.hip */
+void ort_render_adaptive_layout(size_t sizes[3]);
 
 namespace ort {
 
@@ -280,7 +273,7 @@ static int launch_wavefront(DeviceScene *d, const SceneView &sv, const RenderVie
 
 /* The path-trace kernel a plan names.  These sixteen variants, the six of a batch of views, the eight of the radiance queries
    (device_radiance), the eight of the adaptive ones (ort_kernels_adaptive.hip), the eight of the adaptive camera render
-   (device_render_adaptive, ort_kernels_render_adaptive.hip) and the two of ort_kernels_w5.hip are all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
+   (ort_kernels_render_adaptive.hip) and the two of ort_kernels_w5.hip are all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
    an error, not a fallback. */
 static int launch_path_tracer(const LaunchPlan &pl, hipStream_t stream, const SceneView &sv, const RenderHot &hot, std::string *err) {
     if (pl.adaptive) { /* pt_adaptive<counters, diffuse, tabs>: the plain loop over a batch of views, every pixel cut by the stopping rule */
@@ -453,72 +446,71 @@ static int read_render_stats(const DeviceScene *d, bool counters, ort_stats *sta
     return ORT_OK;
 }
 
-/* The render call.  What runs, on which grid and with which thresholds is plan_render's decision (ort_plan.h); this is the
-   plumbing around it: settle the previous call, staging, plan, views, buffers, launch, combine, finish. */
-int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *jobs, uint32_t job_count, void *d_out,
-                  float *h_out, void *stream_v, uint32_t *final_states, ort_stats *stats, std::string *err, const ort_view *views,
-                  uint32_t view_count) {
+/* a sibling unit compiles the argument structs in a namespace of its own and takes them as bytes (the RenderView too: its lanes
+   read it behind hot.c): its three sizes against this unit's */
+static bool same_layout(void (*unit_layout)(size_t *)) {
+    size_t s[3];
+    unit_layout(s);
+    return s[0] == sizeof(SceneView) && s[1] == sizeof(RenderHot) && s[2] == sizeof(RenderView);
+}
+
+/* The camera render call, plain or (c.ad) adaptive.  What runs, on which grid and with which thresholds is plan_render's or
+   plan_render_adaptive's decision (ort_plan.h), and what the RenderView says besides pointers is render_view's (ort_setup.h); this
+   is the plumbing around them: settle the previous call, plan, staging, views, buffers, launch, combine, finish */
+int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c, void *out_rgb, void *out_spp, void *out_m2, void *states, std::string *err) {
     DeviceScene *d = scene->dev;
     if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
     ORT_HIP(hipSetDevice(d->device));
-    hipStream_t stream = (hipStream_t)stream_v;
-    const bool packed_out = (p->flags & ORT_RENDER_PACKED) != 0 && !jobs;
-    if (!views) view_count = 1;
-    /* a batch of views: view_count frames, view-major */
-    const size_t image_bytes = packed_out ? (size_t)block_grid_for(p).my_blocks * 768u : (size_t)view_count * (size_t)p->width * (size_t)p->height * 12u;
+    if (c.ad && !same_layout(ort_render_adaptive_layout)) { *err = "internal: the adaptive render kernels were built with other argument layouts"; return ORT_ERR_INTERNAL; }
+    hipStream_t stream = (hipStream_t)c.stream;
+    const uint32_t view_count = c.views ? c.view_count : 1u;
     int rc;
     /* One render at a time per scene: the job counter, the work counters, the partial planes and the stashes belong
        to the scene.  A render that was returned from without waiting is waited for here, and its tripwire checked. */
     if ((rc = settle_inflight(d, err))) return rc;
 
-    float *out = (float *)d_out;
-    if (!out) {
-        if ((rc = d->staging.ensure(image_bytes, err))) return rc;
-        out = d->staging.as<float>();
-        if (h_out) ORT_HIP(hipMemcpyAsync(out, h_out, image_bytes, hipMemcpyHostToDevice, stream));
-    }
-
     SceneView sv = scene_view(scene, d);
-    const bool w5_layout_ok = ort_w5_sizeof_scene_view() == sizeof(SceneView) && ort_w5_sizeof_render_hot() == sizeof(RenderHot);
-    const LaunchPlan pl = plan_render(scene_traits(scene, d), *p, jobs != nullptr, job_count, w5_layout_ok, d->knobs, view_count);
-
+    const SceneTraits traits = scene_traits(scene, d);
+    const LaunchPlan pl = c.ad ? plan_render_adaptive(traits, *p, d->knobs, view_count)
+                               : plan_render(traits, *p, c.jobs != nullptr, c.job_count, same_layout(ort_w5_layout), d->knobs, view_count);
     sv.util = pl.util ? d->ctrl() + 8 : nullptr;
     if (pl.wide) sv.nodes = d->nodes4.as<const float4>();
     /* the camera: the scene's own; a batch of one view is the same call with that view's camera and seed; the lanes of a larger
        batch read theirs from the table (the VIEWS kernels: sv.cam stays the scene's, unread) */
     ort_camera cam;
     camera_basis(*scene, p->width, p->height, &cam);
-    if (views && !pl.views) cam = views[0].camera;
+    if (c.views && !pl.views) cam = c.views[0].camera;
     memcpy(sv.cam, &cam, sizeof(cam));
 
     RenderView rv{};
-    rv.W = p->width; rv.H = p->height;
-    rv.x0 = p->x0; rv.y0 = p->y0; rv.x1 = p->x1; rv.y1 = p->y1;
-    rv.seed = views && !pl.views ? views[0].seed : p->seed; rv.spp = p->spp; rv.chunk = p->chunk; rv.rr = p->rr;
-    rv.out = out;
-    rv.packed_out = packed_out;
+    render_view(*p, pl, c.views, c.ad, &rv);
+    /* the planes as the lanes see them: the caller's device pointers, or the scene's staging buffers holding the caller's words.
+       view_count frames, view-major, or the packed framebuffer; the 4-byte planes stage where the radiance queries' do */
+    const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
+    struct Plane { void *caller; DevBuf *stage; size_t bytes; void *dev; };
+    Plane planes[4] = {{out_rgb, &d->staging, rv.packed_out ? (size_t)rv.my_blocks * 768u : pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u, nullptr},
+                       {out_m2, &d->query_stage[4], pixels * 4u, nullptr}, {states, &d->query_stage[5], pixels * 4u, nullptr}};
+    for (Plane &pn : planes) {
+        pn.dev = pn.caller;
+        if (!c.host || !pn.caller) continue;
+        if ((rc = pn.stage->ensure(pn.bytes, err))) return rc;
+        pn.dev = pn.stage->p;
+        ORT_HIP(hipMemcpyAsync(pn.dev, pn.caller, pn.bytes, hipMemcpyHostToDevice, stream));
+    }
+    rv.out = (float *)planes[0].dev;
+    rv.ad_spp = (uint32_t *)planes[1].dev;
+    rv.ad_m2 = (float *)planes[2].dev;
+    rv.final_states = (uint32_t *)planes[3].dev;
     rv.next_job = d->ctrl();
     rv.counters = d->ctrl() + 1;
-    rv.mode = pl.mode; rv.nchunks = pl.nchunks; rv.job_count = pl.job_count;
-    rv.shard_count = pl.blocks.shard_count; rv.shard_index = pl.blocks.shard_index;
-    rv.blocks_w = pl.blocks.blocks_w; rv.block_x0 = pl.blocks.block_x0; rv.block_y0 = pl.blocks.block_y0;
-    rv.my_blocks = pl.blocks.my_blocks;
-    rv.refill_below = pl.refill_below; rv.descend_below = pl.descend_below;
-    rv.capL = pl.capL; rv.capR = pl.capR;
-    rv.long_min = pl.long_min; rv.long_refill = pl.long_refill; rv.inflight_cap = pl.inflight_cap; rv.park_min = pl.park_min;
-    rv.endgame_from = pl.endgame_from;
-    rv.stash_wave_f4 = pl.stash_wave_f4;
-    rv.block_major = pl.block_major;
-    rv.job_batch = pl.job_batch; rv.batch_until = pl.batch_until;
-
-    if (jobs) {
-        if ((rc = d->jobs.ensure((size_t)job_count * sizeof(ort_tile_job), err))) return rc;
+    if (c.jobs) {
+        if ((rc = d->jobs.ensure((size_t)c.job_count * sizeof(ort_tile_job), err))) return rc;
         /* synchronous: the caller's job list may be gone when this call returns */
         ORT_HIP(hipStreamSynchronize(stream));
-        ORT_HIP(hipMemcpy(d->jobs.p, jobs, (size_t)job_count * sizeof(ort_tile_job), hipMemcpyHostToDevice));
+        ORT_HIP(hipMemcpy(d->jobs.p, c.jobs, (size_t)c.job_count * sizeof(ort_tile_job), hipMemcpyHostToDevice));
         rv.jobs = d->jobs.as<const ort_tile_job>();
-        if (final_states) {
-            if ((rc = d->states.ensure((size_t)job_count * 4u, err))) return rc;
+        if (c.job_states) {
+            if ((rc = d->states.ensure((size_t)c.job_count * 4u, err))) return rc;
             rv.final_states = d->states.as<uint32_t>();
         }
     }
@@ -526,12 +518,10 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
         /* the camera table (pack_view_table).  Both copies of it are the previous call's until that has finished (settled
            above); the caller's array is read here and not again */
         std::vector<float> &tab = d->view_tab_host;
-        pack_view_table(views, view_count, tab);
+        pack_view_table(c.views, view_count, tab);
         if ((rc = d->view_tab.ensure(tab.size() * sizeof(float), err))) return rc;
         ORT_HIP(hipMemcpyAsync(d->view_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, stream));
         rv.views = d->view_tab.as<const float4>();
-        rv.view_jobs = pl.view_jobs;
-        rv.view_count = pl.view_count;
     }
     if (pl.mode == PLAN_JOBS_CHUNK) {
         if ((rc = d->partial.ensure(pl.partial_bytes, err))) return rc;
@@ -542,7 +532,7 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
         rv.stash = d->stash.as<float4>();
     }
     ORT_HIP(hipMemsetAsync(d->ctrl(), 0, 128 * sizeof(unsigned long long), stream));
-    if (pl.drain_bytes && stats) {
+    if (pl.drain_bytes && c.stats) {
         if ((rc = d->drain.ensure(pl.drain_bytes, err))) return rc;
         ORT_HIP(hipMemsetAsync(d->drain.p, 0, pl.drain_bytes, stream));
         rv.drain = d->drain.as<unsigned long long>();
@@ -551,7 +541,7 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
        fields every ray reads by value and a pointer to the rest */
     ORT_HIP(hipMemcpyAsync(d->rv_dev.p, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
     const RenderHot hot = render_hot<RenderHot>(rv, d->rv_dev.p);
-    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
+    if (c.stats) ORT_HIP(hipEventRecord(d->ev0, stream));
     if (pl.wavefront) rc = pl.counters ? launch_wavefront<true>(d, sv, rv, hot, stream, err) : launch_wavefront<false>(d, sv, rv, hot, stream, err);
     else rc = launch_path_tracer(pl, stream, sv, hot, err);
     if (rc) return rc;
@@ -565,105 +555,22 @@ int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *
         } else if (cgrid) hipLaunchKernelGGL(combine_chunks, dim3(cgrid), dim3(256), 0, stream, hot);
         ORT_HIP(hipGetLastError());
     }
-    if (stats) ORT_HIP(hipEventRecord(d->ev1, stream));
+    if (c.stats) ORT_HIP(hipEventRecord(d->ev1, stream));
 
-    if (!d_out && h_out) ORT_HIP(hipMemcpyAsync(h_out, out, image_bytes, hipMemcpyDeviceToHost, stream));
-    if (final_states) ORT_HIP(hipMemcpyAsync(final_states, d->states.p, (size_t)job_count * 4u, hipMemcpyDeviceToHost, stream));
+    if (c.host)
+        for (const Plane &pn : planes)
+            if (pn.caller) ORT_HIP(hipMemcpyAsync(pn.caller, pn.dev, pn.bytes, hipMemcpyDeviceToHost, stream));
+    if (c.job_states) ORT_HIP(hipMemcpyAsync(c.job_states, d->states.p, (size_t)c.job_count * 4u, hipMemcpyDeviceToHost, stream));
     /* every synchronous form of the call checks the tripwire before it returns (the fire-and-forget device form, stats == NULL,
        cannot without a sync: the next call on the scene does; bench.py asks for stats) */
     ORT_HIP(hipEventRecord(d->ev_done, stream));
     d->inflight = true;
-    if (stats || !d_out || final_states)
+    if (c.stats || c.host || c.job_states)
         if ((rc = settle_inflight(d, err, "reference-order fallback queue overflowed"))) return rc;
-    if (stats && d->knobs.debug_fallback && (rc = print_fallback_diag(d, pl, err))) return rc;
-    if (stats && rv.drain && (rc = print_drain_diag(d, pl, err))) return rc;
-    if (stats && (rc = read_render_stats(d, pl.counters, stats, err))) return rc;
-    if (stats && pl.counters && pl.util && (rc = print_util_diag(d, err))) return rc;
-    return ORT_OK;
-}
-
-/* The adaptive camera render (ort_render_adaptive, ort_render_views_adaptive): view_count frames (the single-frame call passes
-   the scene's own camera and params->seed as its one view), every pixel sampled until the stopping rule ad (checked by the
-   caller) says stop.  What runs is plan_render_adaptive's decision; this is device_render's plumbing for it, with four planes
-   where that has one: rgb (12 bytes a pixel) and, each where asked for (null otherwise), the sample counts, the sums of squared
-   sample luminance and the final states (4 bytes a pixel), view-major.  host: the planes are the caller's memory, staged whole
-   both ways so that pixels outside the rect keep what they held, and the call returns when they are back; otherwise device
-   pointers, one launch enqueued on stream, waited for only with stats.  No workspace: PIXEL jobs have no partial planes */
-int device_render_adaptive(Scene *scene, const ort_render_params *p, const ort_adaptive &ad, const ort_view *views, uint32_t view_count, bool host,
-                           void *out_rgb, void *out_spp, void *out_m2, void *states, void *stream_v, ort_stats *stats, std::string *err) {
-    DeviceScene *d = scene->dev;
-    if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
-    ORT_HIP(hipSetDevice(d->device));
-    if (ort_render_adaptive_sizeof_scene_view() != sizeof(SceneView) || ort_render_adaptive_sizeof_render_hot() != sizeof(RenderHot) ||
-        ort_render_adaptive_sizeof_render_view() != sizeof(RenderView)) {
-        *err = "internal: the adaptive render kernels were built with other argument layouts";
-        return ORT_ERR_INTERNAL;
-    }
-    hipStream_t stream = (hipStream_t)stream_v;
-    int rc;
-    if ((rc = settle_inflight(d, err))) return rc;
-    const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
-    /* the planes as the lanes see them: the caller's device pointers, or the scene's staging buffers holding the caller's words */
-    struct Plane { void *caller; DevBuf *stage; size_t bytes; void *dev; };
-    Plane planes[4] = {{out_rgb, &d->staging, pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u, nullptr},
-                       {out_m2, &d->query_stage[4], pixels * 4u, nullptr}, {states, &d->query_stage[5], pixels * 4u, nullptr}};
-    for (Plane &pn : planes) {
-        pn.dev = pn.caller;
-        if (!host || !pn.caller) continue;
-        if ((rc = pn.stage->ensure(pn.bytes, err))) return rc;
-        pn.dev = pn.stage->p;
-        ORT_HIP(hipMemcpyAsync(pn.dev, pn.caller, pn.bytes, hipMemcpyHostToDevice, stream));
-    }
-
-    SceneView sv = scene_view(scene, d);
-    const LaunchPlan pl = plan_render_adaptive(scene_traits(scene, d), *p, d->knobs, view_count);
-    ort_camera cam; /* sv.cam stays the scene's: the VIEWS lanes do not read it */
-    camera_basis(*scene, p->width, p->height, &cam);
-    memcpy(sv.cam, &cam, sizeof(cam));
-
-    RenderView rv{};
-    rv.W = p->width; rv.H = p->height;
-    rv.x0 = p->x0; rv.y0 = p->y0; rv.x1 = p->x1; rv.y1 = p->y1;
-    rv.spp = ad.max_spp; rv.rr = p->rr;
-    rv.ad_min_spp = ad.min_spp; rv.ad_check_every = ad.check_every;
-    rv.ad_tolerance = ad.tolerance; rv.ad_floor = ad.floor;
-    rv.out = (float *)planes[0].dev;
-    rv.ad_spp = (uint32_t *)planes[1].dev;
-    rv.ad_m2 = (float *)planes[2].dev;
-    rv.final_states = (uint32_t *)planes[3].dev;
-    rv.next_job = d->ctrl();
-    rv.counters = d->ctrl() + 1;
-    rv.mode = pl.mode; rv.nchunks = pl.nchunks; rv.job_count = pl.job_count;
-    rv.shard_count = pl.blocks.shard_count; rv.shard_index = pl.blocks.shard_index;
-    rv.blocks_w = pl.blocks.blocks_w; rv.block_x0 = pl.blocks.block_x0; rv.block_y0 = pl.blocks.block_y0;
-    rv.my_blocks = pl.blocks.my_blocks;
-    rv.refill_below = pl.refill_below; rv.descend_below = pl.descend_below;
-    rv.job_batch = pl.job_batch; rv.batch_until = pl.batch_until;
-    {
-        /* the camera table, as device_render uploads it: the caller's array is read here and not again */
-        std::vector<float> &tab = d->view_tab_host;
-        pack_view_table(views, view_count, tab);
-        if ((rc = d->view_tab.ensure(tab.size() * sizeof(float), err))) return rc;
-        ORT_HIP(hipMemcpyAsync(d->view_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-        rv.views = d->view_tab.as<const float4>();
-        rv.view_jobs = pl.view_jobs;
-        rv.view_count = pl.view_count;
-    }
-    ORT_HIP(hipMemsetAsync(d->ctrl(), 0, 128 * sizeof(unsigned long long), stream));
-    ORT_HIP(hipMemcpyAsync(d->rv_dev.p, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
-    const RenderHot hot = render_hot<RenderHot>(rv, d->rv_dev.p);
-    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
-    if ((rc = launch_path_tracer(pl, stream, sv, hot, err))) return rc;
-    ORT_HIP(hipGetLastError());
-    if (stats) ORT_HIP(hipEventRecord(d->ev1, stream));
-    if (host)
-        for (const Plane &pn : planes)
-            if (pn.caller) ORT_HIP(hipMemcpyAsync(pn.caller, pn.dev, pn.bytes, hipMemcpyDeviceToHost, stream));
-    ORT_HIP(hipEventRecord(d->ev_done, stream));
-    d->inflight = true;
-    if (stats || host)
-        if ((rc = settle_inflight(d, err, "reference-order fallback queue overflowed"))) return rc;
-    if (stats && (rc = read_render_stats(d, pl.counters, stats, err))) return rc;
+    if (c.stats && d->knobs.debug_fallback && (rc = print_fallback_diag(d, pl, err))) return rc;
+    if (c.stats && rv.drain && (rc = print_drain_diag(d, pl, err))) return rc;
+    if (c.stats && (rc = read_render_stats(d, pl.counters, c.stats, err))) return rc;
+    if (c.stats && pl.counters && pl.util && (rc = print_util_diag(d, err))) return rc;
     return ORT_OK;
 }
 
@@ -690,15 +597,6 @@ static RaycastIO ray_query_io(Scene *scene, DeviceScene *d, const void *rays) {
     io.rays = (const float2 *)rays;
     ort::ray_query_io(*scene, d->scene_lo, d->scene_hi, &io);
     return io;
-}
-
-/* runtime bools to template arguments: f(std::bool_constant...) with one constant per bool, true first at every level */
-template <typename F>
-static void with_bools(F f) { f(); }
-template <typename F, typename... Rest>
-static void with_bools(F f, bool b, Rest... rest) {
-    if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
-    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 /* One launch of a ray query over count rays.  rv holds what the query's lanes read behind hot.c besides the policy (nothing for
@@ -862,8 +760,7 @@ int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const vo
     DeviceScene *d;
     int rc;
     if ((rc = begin_query(scene, q.stats, &d, err))) return rc;
-    if (ad && (ort_adaptive_sizeof_scene_view() != sizeof(SceneView) || ort_adaptive_sizeof_render_hot() != sizeof(RenderHot) ||
-               ort_adaptive_sizeof_render_view() != sizeof(RenderView))) {
+    if (ad && !same_layout(ort_adaptive_layout)) {
         *err = "internal: the adaptive kernels were built with other argument layouts";
         return ORT_ERR_INTERNAL;
     }

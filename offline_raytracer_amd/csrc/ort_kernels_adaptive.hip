@@ -4,8 +4,8 @@
  * The lane code (ort_lane.h) compiled a third time, at the limits of ort_kernels.hip proper (four waves per SIMD, 24 LDS stack
  * entries), for the eight variants of radiance_lane<..., ADAPT = true> only.  A unit of its own because eight more path-trace
  * kernels are a quarter more compile time: here they compile beside the others (under make -j3 the three units build at once)
- * and the library builds no slower than before them (profiles/r10_adaptive.md).  device_radiance_adaptive (ort_kernels.hip)
- * launches them through ort_launch_radiance_adaptive.
+ * and the library builds no slower than before them (profiles/r10_adaptive.md).  device_radiance (ort_kernels.hip), given
+ * a stopping rule, launches them through ort_launch_radiance_adaptive.
  */
 #define ORT_ADAPTIVE_TU 1
 #include "ort_lane.h"
@@ -18,15 +18,8 @@ void ort_launch_radiance_adaptive(int counters, int diffuse, int tabs, unsigned 
     RenderHot hot;
     memcpy(&sv, sv_bytes, sizeof(sv));
     memcpy(&hot, hot_bytes, sizeof(hot));
-#define ORT_RA(C, D, T)                                                                                                          \
-    if ((counters != 0) == C && (diffuse != 0) == D && (tabs != 0) == T) {                                                       \
-        hipLaunchKernelGGL((radiance_adaptive_rays<C, D, T>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, sv, hot);      \
-        return;                                                                                                                  \
-    }
-    ORT_RA(true, true, true) ORT_RA(true, true, false) ORT_RA(true, false, true) ORT_RA(true, false, false)
-    ORT_RA(false, true, true) ORT_RA(false, true, false) ORT_RA(false, false, true) ORT_RA(false, false, false)
-#undef ORT_RA
+    ort::with_bools([&](auto C, auto D, auto T) {
+        hipLaunchKernelGGL((radiance_adaptive_rays<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, sv, hot);
+    }, counters != 0, diffuse != 0, tabs != 0);
 }
-size_t ort_adaptive_sizeof_scene_view() { return sizeof(ort_ad::SceneView); }
-size_t ort_adaptive_sizeof_render_hot() { return sizeof(ort_ad::RenderHot); }
-size_t ort_adaptive_sizeof_render_view() { return sizeof(ort_ad::RenderView); }
+void ort_adaptive_layout(size_t sizes[3]) { sizes[0] = sizeof(ort_ad::SceneView); sizes[1] = sizeof(ort_ad::RenderHot); sizes[2] = sizeof(ort_ad::RenderView); }

@@ -20,7 +20,8 @@
 #include "ort_lane.h"
 
 /* the five-waves variants of the plain loop, launched by device_render (ort_kernels.hip proper).  The argument structs are
-   the same declarations compiled in this unit's namespace: passed as bytes */
+   the same declarations compiled in this unit's namespace: passed as bytes, and the caller checks the sizes (the RenderView's
+   too: the lanes read it behind hot.c) */
 void ort_launch_w5(int diffuse, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes) {
     ort_w5::SceneView sv;
     ort_w5::RenderHot hot;
@@ -29,5 +30,4 @@ void ort_launch_w5(int diffuse, unsigned int grid, void *stream, const void *sv_
     if (diffuse) hipLaunchKernelGGL((ort_w5::pt_persistent<false, true, true, true>), dim3(grid), dim3(ort_w5::kBlock), 0, (hipStream_t)stream, sv, hot);
     else hipLaunchKernelGGL((ort_w5::pt_persistent<false, false, true, true>), dim3(grid), dim3(ort_w5::kBlock), 0, (hipStream_t)stream, sv, hot);
 }
-size_t ort_w5_sizeof_scene_view() { return sizeof(ort_w5::SceneView); }
-size_t ort_w5_sizeof_render_hot() { return sizeof(ort_w5::RenderHot); }
+void ort_w5_layout(size_t sizes[3]) { sizes[0] = sizeof(ort_w5::SceneView); sizes[1] = sizeof(ort_w5::RenderHot); sizes[2] = sizeof(ort_w5::RenderView); }

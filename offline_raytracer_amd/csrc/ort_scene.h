@@ -211,17 +211,24 @@ uint32_t rgbe_pack(float r, float g, float b);
 int device_count(int *n, std::string *err);
 int device_upload(Scene *scene, int device, std::string *err);
 void device_release(Scene *scene);
-/* views (may be null: the scene's own camera and p->seed): view_count frames, each from views[v].camera with views[v].seed
-   (ort_render_views; PIXEL / CHUNK job spaces, jobs == null) */
-int device_render(Scene *scene, const ort_render_params *p, const ort_tile_job *jobs, uint32_t job_count,
-                  void *d_out, float *h_out, void *stream, uint32_t *final_states, ort_stats *stats, std::string *err,
-                  const ort_view *views = nullptr, uint32_t view_count = 1);
+/* One camera render call.  host: the planes are the caller's memory, staged whole both ways so that pixels outside the rect keep
+   what they held, and the call returns when they are back; otherwise they are device pointers and the call is one launch
+   enqueued on stream (it waits only for stats or job_states).  Every plane is passed once, whichever form it is */
+struct RenderCall {
+    bool host;
+    void *stream;
+    ort_stats *stats;         /* may be null */
+    const ort_tile_job *jobs; /* explicit jobs (the TILE32 / WHOLE policies, ort_tiled_raytrace_batch); null: the PIXEL / CHUNK job space of p */
+    uint32_t job_count;
+    uint32_t *job_states;     /* ... and where their final states go (may be null): always the caller's memory, read back before the call returns */
+    const ort_view *views;    /* view_count frames, each from views[v].camera with views[v].seed; null: the scene's own camera and p->seed */
+    uint32_t view_count;
+    const ort_adaptive *ad;   /* the stopping rule (checked by the caller) that cuts every pixel of views (not null then); null: a plain render */
+};
+/* out_rgb: view_count frames, view-major (or, ORT_RENDER_PACKED, this shard's blocks).  The adaptive render's other planes (each
+   may be null, and is for a plain render): samples taken, sums of squared sample luminance and final states, a word a pixel */
+int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c, void *out_rgb, void *out_spp, void *out_m2, void *states, std::string *err);
 int device_unit_eval(int device, const void *records, uint32_t n, float *out, std::string *err);
-/* the adaptive camera render: view_count >= 1 frames, every pixel cut by the stopping rule ad.  The four planes (out_spp, out_m2
-   and states may each be null) are view-major, and either the caller's memory (host: staged, synchronous) or device pointers
-   (enqueued on stream, waited for only with stats) */
-int device_render_adaptive(Scene *scene, const ort_render_params *p, const ort_adaptive &ad, const ort_view *views, uint32_t view_count, bool host,
-                           void *out_rgb, void *out_spp, void *out_m2, void *states, void *stream, ort_stats *stats, std::string *err);
 /* One ray query call.  host: the arrays are the caller's memory, staged to the device in bounded slices, and the call returns
    when the answers are back; otherwise they are device pointers and the call is one launch enqueued on stream (it waits only
    for stats).  Every array is passed once, whichever form it is */

@@ -1,9 +1,10 @@
 /*
  * ort_setup.h -- what the host works out from a committed scene before a kernel can run, as plain functions of their
  * inputs: the layout and the image of the small LDS tables, the shape table of the ray queries (the inverse of the tree's
- * slot maps), what raycast_needs_exact reads, and the camera table of a batch of views.  No HIP in here: ort_kernels.hip
- * calls these and keeps the uploads and launches; tools/host_sim.cpp calls the same functions to run the lane code on host
- * threads, so the CPU tests exercise the product's own tables (tests/test_query_lanes_host.py).
+ * slot maps), what raycast_needs_exact reads, the camera table of a batch of views, and every field of a call's RenderView that
+ * is not a pointer.  No HIP in here: ort_kernels.hip calls these and keeps the uploads and launches; tools/host_sim.cpp calls the
+ * same functions to run the lane code on host threads, so the CPU tests exercise the product's own tables and launch set-up
+ * (tests/test_query_lanes_host.py), and tools/launch_plan prints the fill of a plan (tests/test_launch_plan.py).
  */
 #ifndef ORT_SETUP_H
 #define ORT_SETUP_H
@@ -13,6 +14,7 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ort_plan.h"
@@ -134,6 +136,47 @@ inline void radiance_adaptive_view(const IO &q, const void *seeds, const ort_ada
     rv->ad_tolerance = ad.tolerance; rv->ad_floor = ad.floor;
     rv->ad_spp = (uint32_t *)out_spp;
     rv->ad_m2 = (float *)out_m2;
+}
+
+/* camera renders: everything in the RenderView (View) that is not a pointer -- what the call says and what its plan says
+   (plan_render, or with a stopping rule ad plan_render_adaptive).  views: the batch's, null for the scene's own camera and
+   p.seed.  A batch of one view of the plain render is the single-frame call with that view's seed (and camera: the caller's to
+   set); the lanes of a larger batch, and of every adaptive render, read both from the camera table.  With ad, spp is max_spp and
+   seed and chunk stay unset: a job's length is the rule's.  A field the plan leaves at zero stays zero */
+template <typename View>
+inline void render_view(const ort_render_params &p, const LaunchPlan &pl, const ort_view *views, const ort_adaptive *ad, View *rv) {
+    rv->W = p.width; rv->H = p.height;
+    rv->x0 = p.x0; rv->y0 = p.y0; rv->x1 = p.x1; rv->y1 = p.y1;
+    rv->rr = p.rr;
+    if (ad) {
+        rv->spp = ad->max_spp;
+        rv->ad_min_spp = ad->min_spp; rv->ad_check_every = ad->check_every;
+        rv->ad_tolerance = ad->tolerance; rv->ad_floor = ad->floor;
+    } else {
+        rv->seed = views && !pl.views ? views[0].seed : p.seed; rv->spp = p.spp; rv->chunk = p.chunk;
+    }
+    rv->packed_out = (p.flags & ORT_RENDER_PACKED) != 0 && pl.mode != PLAN_JOBS_EXPLICIT;
+    rv->mode = pl.mode; rv->nchunks = pl.nchunks; rv->job_count = pl.job_count;
+    rv->shard_count = pl.blocks.shard_count; rv->shard_index = pl.blocks.shard_index;
+    rv->blocks_w = pl.blocks.blocks_w; rv->block_x0 = pl.blocks.block_x0; rv->block_y0 = pl.blocks.block_y0;
+    rv->my_blocks = pl.blocks.my_blocks;
+    if (pl.views) { rv->view_jobs = pl.view_jobs; rv->view_count = pl.view_count; }
+    rv->refill_below = pl.refill_below; rv->descend_below = pl.descend_below;
+    rv->capL = pl.capL; rv->capR = pl.capR;
+    rv->long_min = pl.long_min; rv->long_refill = pl.long_refill; rv->inflight_cap = pl.inflight_cap; rv->park_min = pl.park_min;
+    rv->endgame_from = pl.endgame_from;
+    rv->stash_wave_f4 = pl.stash_wave_f4;
+    rv->block_major = pl.block_major;
+    rv->job_batch = pl.job_batch; rv->batch_until = pl.batch_until;
+}
+
+/* runtime bools to template arguments: f(std::bool_constant...) with one constant per bool, true first at every level */
+template <typename F>
+inline void with_bools(F f) { f(); }
+template <typename F, typename... Rest>
+inline void with_bools(F f, bool b, Rest... rest) {
+    if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 /* the kernels' by-value argument (Hot: RenderHot of ort_lane.h): the few fields of rv every ray reads, and where the lanes find

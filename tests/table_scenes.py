@@ -22,8 +22,8 @@ W, H = 64, 48
 
 
 def launch_plan_tool():
-    src = [os.path.join(ROOT, "tools", "launch_plan.cpp"), os.path.join(ROOT, "offline_raytracer_amd", "csrc", "ort_plan.h"),
-           os.path.join(ROOT, "include", "ort.h")]
+    src = [os.path.join(ROOT, "tools", "launch_plan.cpp"), os.path.join(ROOT, "include", "ort.h")]
+    src += [os.path.join(ROOT, "offline_raytracer_amd", "csrc", h) for h in ("ort_plan.h", "ort_setup.h", "ort_scene.h")]
     if not os.path.exists(TOOL) or any(os.path.getmtime(s) > os.path.getmtime(TOOL) for s in src):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or hipcc

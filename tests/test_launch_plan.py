@@ -22,8 +22,8 @@ KNOBS = ("ORT_DEBUG_FORCE_FALLBACK ORT_DEBUG_UTIL ORT_DEBUG_FALLBACK ORT_DEBUG_D
 
 @pytest.fixture(scope="module")
 def tool():
-    src = [os.path.join(ROOT, "tools", "launch_plan.cpp"), os.path.join(ROOT, "offline_raytracer_amd", "csrc", "ort_plan.h"),
-           os.path.join(ROOT, "include", "ort.h")]
+    src = [os.path.join(ROOT, "tools", "launch_plan.cpp"), os.path.join(ROOT, "include", "ort.h")]
+    src += [os.path.join(ROOT, "offline_raytracer_amd", "csrc", h) for h in ("ort_plan.h", "ort_setup.h", "ort_scene.h")]
     if not os.path.exists(TOOL) or any(os.path.getmtime(s) > os.path.getmtime(TOOL) for s in src):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or (hipcc if os.path.exists(hipcc) else None)
@@ -42,6 +42,19 @@ def plan(tool, env=None, **kw):
     r = subprocess.run([tool] + ["%s=%s" % kv for kv in args.items()], env=e, capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr
     return json.loads(r.stdout)
+
+
+def fill(tool, **kw):
+    """-> (the plan, the fields of the RenderView that are not pointers as the shared fill sets them for it: fill=1)"""
+    args = dict(cu_count=CU, diffuse_only=1, fast_tree_bytes=6 << 20, sah_cost=0.05, fill=1)
+    args.update(kw)
+    e = {k: v for k, v in os.environ.items() if k not in KNOBS}
+    r = subprocess.run([tool] + ["%s=%s" % kv for kv in args.items()], env=e, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    lines = r.stdout.splitlines()
+    fields = dict(line.split(" = ") for line in lines[1:])
+    assert len(fields) == len(lines) - 1 == 39
+    return json.loads(lines[0]), {k: float(v) if k in ("rr", "ad_tolerance", "ad_floor") else int(v) for k, v in fields.items()}
 
 
 def qplan(tool, query, count, env=None, **kw):
@@ -444,3 +457,42 @@ def test_radiance_has_no_other_kernel_to_force(tool):
         base = qplan(tool, "radiance", count, has_wide=1, sah_cost=0.5)
         for env in ({"ORT_EXCHANGE": "1"}, {"ORT_WAVES5": "1"}, {"ORT_WIDE": "1"}, {"ORT_MODE": "wavefront"}, FORCE_ALL):
             assert qplan(tool, "radiance", count, env, has_wide=1, sah_cost=0.5) == base, env
+
+
+# ---- the RenderView a plan is turned into (render_view, csrc/ort_setup.h): what device_render uploads besides pointers -------
+FRAME = dict(width=20, height=13, x0=3, y0=2, x1=17, y1=9, seed=9, rr=0.5)   # 3 x 2 blocks under the rect
+EXCHANGE_FIELDS = ("capL", "capR", "long_min", "long_refill", "inflight_cap", "park_min", "stash_wave_f4")
+
+
+def test_fill_of_the_adaptive_call(tool):
+    """spp is max_spp whatever params->spp says; seed and chunk stay unset (the lanes read the seed from the camera table, and a
+    job's length is the rule's), and so do the exchange fields and endgame_from"""
+    for views in ({}, dict(views=3, view_seed=40)):
+        p, rv = fill(tool, policy="pixel", adaptive=1, spp=5, chunk=5, min_spp=8, max_spp=64, check_every=4, tolerance=0.25, floor=0.5, **FRAME, **views)
+        n = views.get("views", 1)
+        assert (rv["seed"], rv["chunk"], rv["spp"], rv["endgame_from"], rv["block_major"], rv["packed_out"]) == (0, 0, 64, 0, 0, 0)
+        assert [rv[k] for k in EXCHANGE_FIELDS] == [0] * 7
+        assert (rv["ad_min_spp"], rv["ad_check_every"], rv["ad_tolerance"], rv["ad_floor"], rv["rr"]) == (8, 4, 0.25, 0.5, 0.5)
+        assert (rv["mode"], rv["nchunks"], rv["my_blocks"], rv["view_jobs"], rv["view_count"], rv["job_count"]) == (1, 1, 6, 384, n, 384 * n)
+        assert (rv["W"], rv["H"], rv["x0"], rv["y0"], rv["x1"], rv["y1"]) == (20, 13, 3, 2, 17, 9)
+        assert (rv["blocks_w"], rv["block_x0"], rv["block_y0"], rv["shard_index"], rv["shard_count"]) == (3, 0, 0, 0, 1)
+        assert (rv["refill_below"], rv["descend_below"], rv["job_batch"], rv["batch_until"]) == (16, 8, 64, 0)
+        assert (rv["job_batch"], rv["batch_until"], rv["refill_below"]) == (p["job_batch"], p["batch_until"], p["refill_below"])
+
+
+def test_fill_of_a_one_view_batch_is_the_single_frame_call_with_that_views_seed(tool):
+    """view_count and view_jobs stay unset: the launch is the single-frame kernel's"""
+    _, one = fill(tool, policy="chunk", spp=4, chunk=2, views=1, view_seed=77, **FRAME)
+    _, single = fill(tool, policy="chunk", spp=4, chunk=2, **FRAME)
+    assert (one["view_count"], one["view_jobs"], one["seed"], single["seed"]) == (0, 0, 77, 9)
+    assert (one["mode"], one["nchunks"], one["job_count"], one["my_blocks"], one["block_major"], one["spp"], one["chunk"]) == (2, 2, 768, 6, 1, 4, 2)
+    assert dict(one, seed=9) == single
+
+
+def test_fill_of_a_three_view_chunk_batch(tool):
+    """the job space is three times the view's, the seed params->seed (unread: the lanes take theirs from the camera table)"""
+    p, rv = fill(tool, policy="chunk", spp=4, chunk=2, views=3, view_seed=77, **FRAME)
+    assert (rv["view_count"], rv["view_jobs"], rv["job_count"], rv["seed"]) == (3, 768, 2304, 9)
+    assert rv["job_count"] == 3 * rv["view_jobs"] == p["job_count"]
+    assert (rv["mode"], rv["nchunks"], rv["block_major"], rv["endgame_from"]) == (2, 2, 1, 0)
+    assert [rv[k] for k in EXCHANGE_FIELDS] == [0] * 7

@@ -12,7 +12,7 @@
  * (tests/test_host.py holds its image against the oracle; nothing else uses it).
  *
  * The ray-query lanes (raycast_lane, occluded_lane, radiance_lane with and without its adaptive rule), the batch-of-views flavour of pt_lane and its adaptive one run here too, on
- * the tables the product's own host code packs (ort_setup.h): tests/test_query_lanes_host.py holds them against the
+ * the tables the product's own host code packs, and the camera modes on the launch plan and RenderView fill of the product's own render call (ort_plan.h, ort_setup.h): tests/test_query_lanes_host.py holds them against the
  * reference's answers and the oracle, tests/test_host_sanitizers.py runs the same binary built with ASan + UBSan
  * (make host_sim_san).
  *
@@ -23,6 +23,7 @@
  *   or: host_sim --radiance scn base rays.f32 seeds.u32 spp rr out.f32 states.u32
  *   or: host_sim --radiance-adaptive scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
  *   or: host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32   (cams: p, x, y, z axes, 12 floats a view)
+ *       (as on the device, one view is the single-frame lane with that view's camera and seed: the VIEWS lanes run from two views on)
  *   or: host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
  *       (the adaptive camera render of the scene's own camera: pt_lane<..., VIEWS, ADAPT> over a one-view batch; the planes start
  *       at the guard values -7.0f, 0xeeeeeeee, -1.0f, 0xdddddddd, which pixels outside the rect keep)
@@ -340,6 +341,48 @@ static int radiance_adaptive_mode(char **a) { /* scn base rays.f32 seeds.u32 min
            write_bytes(a[13], states.data(), 4 * n) ? 0 : 1;
 }
 
+/* The camera modes set their launch up as device_render does: a plan (plan_render, plan_render_adaptive) and render_view's fill of
+   it, for traits the simulation states itself and knobs that keep its schedule -- one simulated lane per thread: no batches, jobs
+   in chunk-major order, the plain loop -- whatever the environment says; the modes add their pointers */
+static SceneTraits sim_traits(const Sim &S) {
+    SceneTraits t;
+    t.diffuse_only = getenv("SIM_DIFFUSE") != nullptr; /* caller vouches for Ks = Kt = 0 */
+    t.tab_flags = S.tab_flags;
+    t.fast_tree_bytes = S.scene->tree.nodes.size() * sizeof(DevNode) + S.scene->tree.tris.size() * sizeof(DevTri);
+    t.sah_cost = S.scene->tree.sah_cost;
+    t.has_wide = !S.scene->tree.nodes4.empty();
+    t.max_blocks = 1;
+    return t;
+}
+static Knobs sim_knobs() {
+    Knobs kn;
+    kn.refill_below = 12;
+    kn.descend_below = getenv("SIM_DESCEND_BELOW") ? atoi(getenv("SIM_DESCEND_BELOW")) : 8;
+    kn.job_batch = 0; /* draw_job then never reads batch_until (want < need takes need) */
+    kn.exchange = kn.waves5 = kn.wide = kn.lpt = 0;
+    return kn;
+}
+static ort_render_params sim_params(int W, int H, uint32_t spp, uint32_t seed, const std::string &policy, uint32_t chunk) {
+    ort_render_params p{};
+    p.width = W; p.height = H; p.x1 = W; p.y1 = H;
+    p.spp = spp; p.seed = seed; p.chunk = chunk; p.rr = getenv("SIM_RR") ? (float)atof(getenv("SIM_RR")) : 0.8f;
+    p.policy = policy == "pixel" ? ORT_POLICY_PIXEL : policy == "chunk" ? ORT_POLICY_CHUNK : ORT_POLICY_WHOLE;
+    return p;
+}
+/* the plain loop's lanes over the job space of rv: pt_lane<counters, diffuse, tabs, explicit jobs, wide, views>, wide or views or
+   neither.  SIM_DIFFUSE: the caller vouches for Ks = Kt = 0; the wide lanes run in the all-lobes flavour whatever it says.  TABS =
+   false: the small tables are read from their arrays; SIM_TABS: from the packed image */
+static void run_pt_lanes(const Sim &S, const RenderHot &hot, bool wide, bool views) {
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
+        with_bools([&](auto D, auto T) {
+            constexpr bool d = decltype(D)::value, t = decltype(T)::value;
+            if (views) pt_lane<true, d, t, false, false, true>(sv, hot, S.tab, stack, focal, 0, w);
+            else if (!wide) pt_lane<true, d, t>(sv, hot, S.tab, stack, focal, 0, w);
+            else if constexpr (!d) pt_lane<true, false, t, false, true>(sv, hot, S.tab, stack, focal, 0, w);
+        }, getenv("SIM_DIFFUSE") != nullptr && !wide, S.tab != nullptr);
+    });
+}
+
 static int views_mode(char **a) { /* scn base cams.f32 seeds.u32 W H spp policy chunk out.f32 */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
@@ -354,47 +397,28 @@ static int views_mode(char **a) { /* scn base cams.f32 seeds.u32 W H spp policy 
     static_assert(sizeof(ort_camera) == 48, "a camera is twelve floats");
     const int W = atoi(a[4]), H = atoi(a[5]);
     const uint32_t spp = (uint32_t)strtoul(a[6], 0, 10), chunk = (uint32_t)strtoul(a[8], 0, 10);
-    const std::string policy = a[7];
     if (W <= 0 || H <= 0 || W > 65535 || H > 65535) { fprintf(stderr, "bad frame size\n"); return 1; }
+    const std::string policy = a[7];
+    if (policy != "pixel" && policy != "chunk") { fprintf(stderr, "a batch of views renders under the pixel or the chunk policy\n"); return 1; }
+    if (policy == "chunk" && (!chunk || spp % chunk)) { fprintf(stderr, "chunk must divide spp\n"); return 1; }
+    const ort_render_params p = sim_params(W, H, spp, 0, policy, chunk);
+    const LaunchPlan pl = plan_render(sim_traits(S), p, false, 0, false, sim_knobs(), nv);
     std::vector<float> tab_host; /* the camera table, 16-byte aligned for the lanes' float4 reads */
     pack_view_table(views.data(), nv, tab_host);
     std::vector<float4> view_tab(4u * nv);
     memcpy(view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
-    ort_camera cam; /* sv.cam stays the scene's: the VIEWS lanes do not read it */
+    ort_camera cam; /* the scene's (unread by the VIEWS lanes), or as on the device the one view's of a batch of one */
     camera_basis(*S.scene, W, H, &cam);
+    if (!pl.views) cam = views[0].camera;
     memcpy(S.sv.cam, &cam, sizeof(cam));
     RenderView rv{};
-    rv.W = W; rv.H = H; rv.x0 = 0; rv.y0 = 0; rv.x1 = W; rv.y1 = H;
-    rv.spp = spp; rv.chunk = chunk; rv.rr = getenv("SIM_RR") ? (float)atof(getenv("SIM_RR")) : 0.8f;
-    rv.shard_count = 1; rv.shard_index = 0;
-    rv.blocks_w = (uint32_t)((W + 7) / 8);
-    rv.my_blocks = rv.blocks_w * (uint32_t)((H + 7) / 8);
-    std::vector<float> out((size_t)nv * W * H * 3, 0.0f), partial;
-    if (policy == "pixel") { rv.mode = JOBS_PIXEL; rv.nchunks = 1; }
-    else if (policy == "chunk") {
-        if (!chunk || spp % chunk) { fprintf(stderr, "chunk must divide spp\n"); return 1; }
-        rv.mode = JOBS_CHUNK; rv.nchunks = spp / chunk;
-        partial.assign((size_t)nv * rv.nchunks * rv.my_blocks * 64 * 3, 0.0f); rv.partial = partial.data();
-    } else { fprintf(stderr, "a batch of views renders under the pixel or the chunk policy\n"); return 1; }
-    rv.view_jobs = (unsigned long long)rv.my_blocks * 64 * rv.nchunks;
-    rv.view_count = nv;
-    rv.views = view_tab.data();
-    rv.job_count = rv.view_jobs * nv;
-    rv.out = out.data(); rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
-    rv.refill_below = 12;
-    rv.descend_below = getenv("SIM_DESCEND_BELOW") ? atoi(getenv("SIM_DESCEND_BELOW")) : 8;
+    render_view(p, pl, views.data(), nullptr, &rv);
+    std::vector<float> out((size_t)nv * W * H * 3, 0.0f), partial(pl.partial_bytes / sizeof(float), 0.0f);
+    rv.out = out.data(); rv.partial = partial.data(); rv.views = view_tab.data();
+    rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
     const RenderHot hot = render_hot<RenderHot>(rv, &rv);
-    const bool diffuse_only = getenv("SIM_DIFFUSE") != nullptr;
     auto t0 = std::chrono::steady_clock::now();
-    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
-        if (diffuse_only) {
-            if (S.tab) pt_lane<true, true, true, false, false, true>(sv, hot, S.tab, stack, focal, 0, w);
-            else pt_lane<true, true, false, false, false, true>(sv, hot, nullptr, stack, focal, 0, w);
-        } else {
-            if (S.tab) pt_lane<true, false, true, false, false, true>(sv, hot, S.tab, stack, focal, 0, w);
-            else pt_lane<true, false, false, false, false, true>(sv, hot, nullptr, stack, focal, 0, w);
-        }
-    });
+    run_pt_lanes(S, hot, false, pl.views);
     if (rv.mode == JOBS_CHUNK)
         for (uint32_t v = 0; v < nv; ++v)
             for (unsigned long long i = 0; i < (unsigned long long)rv.my_blocks * 64; ++i) combine_pixel(hot, i, v);
@@ -402,7 +426,7 @@ static int views_mode(char **a) { /* scn base cams.f32 seeds.u32 W H spp policy 
     return write_bytes(a[9], out.data(), out.size() * sizeof(float)) ? 0 : 1;
 }
 
-/* the adaptive camera render (ort_render_adaptive): what device_render_adaptive sets up, for one simulated lane per thread */
+/* the adaptive camera render (ort_render_adaptive): what device_render sets up for it, for one simulated lane per thread */
 static int render_adaptive_mode(char **a) { /* scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32 */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
@@ -423,32 +447,19 @@ static int render_adaptive_mode(char **a) { /* scn base W H x0 y0 x1 y1 seed min
     std::vector<uint32_t> spp(n, 0xeeeeeeeeu), states(n, 0xddddddddu);
     ort_render_params p{};
     p.width = W; p.height = H; p.x0 = x0; p.y0 = y0; p.x1 = x1; p.y1 = y1;
-    const BlockGrid g = block_grid_for(&p); /* the blocks under the rect, as plan_render_adaptive counts them */
+    p.policy = ORT_POLICY_PIXEL; p.rr = (float)atof(a[14]);
     RenderView rv{};
-    rv.mode = JOBS_PIXEL; rv.nchunks = 1;
-    rv.W = W; rv.H = H; rv.x0 = x0; rv.y0 = y0; rv.x1 = x1; rv.y1 = y1;
-    rv.spp = ad.max_spp; rv.rr = (float)atof(a[14]);
-    rv.ad_min_spp = ad.min_spp; rv.ad_check_every = ad.check_every; rv.ad_tolerance = ad.tolerance; rv.ad_floor = ad.floor;
+    render_view(p, plan_render_adaptive(sim_traits(S), p, sim_knobs(), 1), &view, &ad, &rv);
     rv.out = out.data(); rv.ad_spp = spp.data(); rv.ad_m2 = m2.data(); rv.final_states = states.data();
-    rv.shard_count = g.shard_count; rv.shard_index = g.shard_index;
-    rv.blocks_w = g.blocks_w; rv.block_x0 = g.block_x0; rv.block_y0 = g.block_y0; rv.my_blocks = g.my_blocks;
-    rv.view_jobs = (unsigned long long)g.my_blocks * 64; rv.view_count = 1; rv.views = view_tab.data();
-    rv.job_count = rv.view_jobs;
+    rv.views = view_tab.data();
     rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
-    rv.refill_below = 12;
-    rv.descend_below = getenv("SIM_DESCEND_BELOW") ? atoi(getenv("SIM_DESCEND_BELOW")) : 8;
     const RenderHot hot = render_hot<RenderHot>(rv, &rv);
-    const bool diffuse_only = getenv("SIM_DIFFUSE") != nullptr; /* caller vouches for Ks = Kt = 0 */
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
         AdaptState A; /* the lane's own, as pt_adaptive's slot of LDS */
-        if (diffuse_only) {
-            if (S.tab) pt_lane<true, true, true, true, false, true, true>(sv, hot, S.tab, stack, focal, 0, w, false, nullptr, &A);
-            else pt_lane<true, true, false, true, false, true, true>(sv, hot, nullptr, stack, focal, 0, w, false, nullptr, &A);
-        } else {
-            if (S.tab) pt_lane<true, false, true, true, false, true, true>(sv, hot, S.tab, stack, focal, 0, w, false, nullptr, &A);
-            else pt_lane<true, false, false, true, false, true, true>(sv, hot, nullptr, stack, focal, 0, w, false, nullptr, &A);
-        }
+        with_bools([&](auto D, auto T) {
+            pt_lane<true, decltype(D)::value, decltype(T)::value, true, false, true, true>(sv, hot, S.tab, stack, focal, 0, w, false, nullptr, &A);
+        }, getenv("SIM_DIFFUSE") != nullptr, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return write_bytes(a[15], out.data(), 12 * n) && write_bytes(a[16], spp.data(), 4 * n) && write_bytes(a[17], m2.data(), 4 * n) &&
@@ -490,27 +501,12 @@ int main(int argc, char **argv) {
     camera_basis(*scene, W, H, &cam);
     memcpy(sv.cam, &cam, sizeof(cam));
 
-    std::vector<float> out((size_t)W * H * 3, 0.0f), partial;
-    RenderView rv{};
-    rv.W = W; rv.H = H; rv.x0 = 0; rv.y0 = 0; rv.x1 = W; rv.y1 = H;
-    rv.seed = seed; rv.spp = spp; rv.chunk = chunk; rv.rr = getenv("SIM_RR") ? (float)atof(getenv("SIM_RR")) : 0.8f;
-    rv.refill_below = 12;
-    rv.descend_below = getenv("SIM_DESCEND_BELOW") ? atoi(getenv("SIM_DESCEND_BELOW")) : 8;
-    rv.out = out.data(); rv.next_job = ctrl; rv.counters = ctrl + 1;
-    rv.shard_count = argc > 11 ? (uint32_t)atoi(argv[11]) : 1; rv.shard_index = argc > 11 ? (uint32_t)atoi(argv[10]) : 0;
-    if (!rv.shard_count || rv.shard_index >= rv.shard_count) { fprintf(stderr, "bad shard\n"); return 1; }
-    rv.block_x0 = rv.block_y0 = 0;
-    rv.blocks_w = (uint32_t)((W + 7) / 8);
-    uint32_t blocks_total = rv.blocks_w * (uint32_t)((H + 7) / 8);
-    rv.my_blocks = (blocks_total - rv.shard_index + rv.shard_count - 1) / rv.shard_count;
+    ort_render_params p = sim_params(W, H, spp, seed, policy, chunk);
+    p.shard_count = argc > 11 ? (uint32_t)atoi(argv[11]) : 1; p.shard_index = argc > 11 ? (uint32_t)atoi(argv[10]) : 0;
+    if (!p.shard_count || p.shard_index >= p.shard_count) { fprintf(stderr, "bad shard\n"); return 1; }
+    if (policy == "chunk" && (!chunk || spp % chunk)) { fprintf(stderr, "chunk must divide spp\n"); return 1; }
     std::vector<ort_tile_job> jobs;
-    std::vector<uint32_t> finals;
-    if (policy == "pixel") { rv.mode = JOBS_PIXEL; rv.nchunks = 1; rv.job_count = (unsigned long long)rv.my_blocks * 64; }
-    else if (policy == "chunk") {
-        if (!chunk || spp % chunk) { fprintf(stderr, "chunk must divide spp\n"); return 1; }
-        rv.mode = JOBS_CHUNK; rv.nchunks = spp / chunk; rv.job_count = (unsigned long long)rv.my_blocks * 64 * rv.nchunks;
-        partial.assign((size_t)rv.nchunks * rv.my_blocks * 64 * 3, 0.0f); rv.partial = partial.data(); /* packed block layout: edge blocks are whole */
-    } else {
+    if (policy != "pixel" && policy != "chunk") {
         uint32_t master = seed;
         auto xs = [&]() { master ^= master << 13; master ^= master >> 17; master ^= master >> 5; return master; };
         if (policy == "whole") jobs.push_back(ort_tile_job{0, 0, W, H, xs(), spp});
@@ -521,15 +517,20 @@ int main(int argc, char **argv) {
                 if (j.x0 < j.x1 && j.y0 < j.y1) jobs.push_back(j);
             }
         }
-        finals.resize(jobs.size());
-        rv.mode = JOBS_EXPLICIT; rv.jobs = jobs.data(); rv.job_count = jobs.size(); rv.final_states = finals.data();
     }
+    const LaunchPlan pl = plan_render(sim_traits(S), p, !jobs.empty(), jobs.size(), false, sim_knobs());
+    RenderView rv{};
+    render_view(p, pl, nullptr, nullptr, &rv);
+    std::vector<float> out((size_t)W * H * 3, 0.0f), partial(pl.partial_bytes / sizeof(float), 0.0f); /* packed block layout: edge blocks are whole */
+    std::vector<uint32_t> finals(jobs.size());
+    rv.out = out.data(); rv.partial = partial.data(); rv.next_job = ctrl; rv.counters = ctrl + 1;
+    if (!jobs.empty()) { rv.jobs = jobs.data(); rv.final_states = finals.data(); }
     std::vector<uint32_t> pix_rng((size_t)W * H, 0);
     const RenderHot hot = render_hot<RenderHot>(rv, &rv);
     if (getenv("SIM_RAY_LOG")) { g_ray_log = fopen(getenv("SIM_RAY_LOG"), "wb"); g_dbg_x = atoi(getenv("SIM_X")); g_dbg_y = atoi(getenv("SIM_Y")); }
     if (getenv("SIM_DUMP_RNG")) { g_pixel_rng = pix_rng.data(); g_W = W; }
     auto t0 = std::chrono::steady_clock::now();
-    const bool wide = getenv("SIM_WIDE") != nullptr, diffuse_only = getenv("SIM_DIFFUSE") != nullptr;
+    const bool wide = getenv("SIM_WIDE") != nullptr;
     if (getenv("SIM_WAVEFRONT")) {
         /* the wavefront schedule with a small slot pool: shade all slots, trace all slots, repeat */
         if (S.tab) { fprintf(stderr, "SIM_TABS: the wavefront kernels read the tables from their arrays\n"); return 1; }
@@ -558,19 +559,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "wide tree: %zu nodes, depth %u\n", t.nodes4.size(), t.max_depth4);
             sv.nodes = (const float4 *)t.nodes4.data();
         }
-        /* TABS = false: the small tables are read from their arrays; SIM_TABS: from the packed image */
-        run_lanes(S, [&](const SceneView &svw, uint32_t *stack, float *focal, uint32_t w) {
-            if (wide) {
-                if (S.tab) pt_lane<true, false, true, false, true>(svw, hot, S.tab, stack, focal, 0, w);
-                else pt_lane<true, false, false, false, true>(svw, hot, nullptr, stack, focal, 0, w);
-            } else if (diffuse_only) { /* caller vouches for Ks = Kt = 0 */
-                if (S.tab) pt_lane<true, true, true>(svw, hot, S.tab, stack, focal, 0, w);
-                else pt_lane<true, true>(svw, hot, nullptr, stack, focal, 0, w);
-            } else {
-                if (S.tab) pt_lane<true, false, true>(svw, hot, S.tab, stack, focal, 0, w);
-                else pt_lane<true>(svw, hot, nullptr, stack, focal, 0, w);
-            }
-        });
+        run_pt_lanes(S, hot, wide, false);
     }
     if (rv.mode == JOBS_CHUNK)
         for (unsigned long long i = 0; i < (unsigned long long)rv.my_blocks * 64; ++i) combine_pixel(hot, i);

@@ -4,8 +4,7 @@ namespace ort {
 int device_count(int *n, std::string *err) { *n = 0; *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_upload(Scene *, int, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 void device_release(Scene *) {}
-int device_render(Scene *, const ort_render_params *, const ort_tile_job *, uint32_t, void *, float *, void *, uint32_t *, ort_stats *, std::string *err, const ort_view *, uint32_t) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
-int device_render_adaptive(Scene *, const ort_render_params *, const ort_adaptive &, const ort_view *, uint32_t, bool, void *, void *, void *, void *, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
+int device_render(Scene *, const ort_render_params *, const RenderCall &, void *, void *, void *, void *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_unit_eval(int, const void *, uint32_t, float *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_raycast(Scene *, const QueryCall &, const void *, void *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_occluded(Scene *, const QueryCall &, const void *, const void *, void *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }

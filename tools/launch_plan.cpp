@@ -6,14 +6,35 @@
    keys: the SceneTraits and ort_render_params fields by name, policy=pixel|chunk, counters=1, explicit_jobs=1 job_count=N,
    w5_layout_ok=0, views=N (the plan of an ort_render_views batch of N views; its fields are appended to the line), adaptive=1
    (plan_render_adaptive: the plan of ort_render_adaptive, or with views=N of ort_render_views_adaptive; "adaptive" and the
-   views fields are appended); max_blocks
+   views fields are appended); fill=1: after the plan, every field of the RenderView that is not a pointer as the shared fill
+   (render_view, csrc/ort_setup.h) sets it for that plan, "name = value" one per line -- seed=, rr= are the call's, view_seed=S
+   gives view v of views=N the seed S + v, min_spp= max_spp= check_every= tolerance= floor= are the stopping rule's; max_blocks
    defaults to what an upload on cu_count units fixes.  tab_flags, where not given, follows from
    materials= (index 0 included), lights=, pro_boxes=, pro_spheres=, pro_cyls= as at upload (table_fit_flags; all 0 by default).  tests/test_launch_plan.py holds the measured
    crossovers and the knobs the GPU tests force kernels with against it. */
 #include <stdio.h>
 
+#include <type_traits>
+#include <vector>
+
 #include "../include/ort.h"
 #include "../offline_raytracer_amd/csrc/ort_plan.h"
+#include "../offline_raytracer_amd/csrc/ort_setup.h"
+
+/* the RenderView (csrc/ort_lane.h, which only a HIP compiler reads) without its pointers: the fields render_view fills.  Kept by
+   hand in step with ort_lane.h: a field render_view assigns and this list lacks does not compile, but one added to RenderView and
+   forgotten in render_view does not show here */
+#define FILL_FIELDS(F) F(mode) F(W) F(H) F(x0) F(y0) F(x1) F(y1) F(seed) F(spp) F(chunk) F(rr) F(packed_out) F(nchunks) F(job_count) F(shard_index) \
+    F(shard_count) F(blocks_w) F(block_x0) F(block_y0) F(my_blocks) F(view_jobs) F(view_count) F(refill_below) F(descend_below) F(capL) F(capR) F(long_min) \
+    F(long_refill) F(inflight_cap) F(park_min) F(endgame_from) F(stash_wave_f4) F(block_major) F(job_batch) F(batch_until) F(ad_min_spp) F(ad_check_every) \
+    F(ad_tolerance) F(ad_floor)
+struct FillView {
+    int mode, W, H, x0, y0, x1, y1, refill_below, descend_below, packed_out;
+    uint32_t seed, spp, chunk, nchunks, shard_index, shard_count, blocks_w, block_x0, block_y0, my_blocks, view_count, capL, capR, long_min, long_refill,
+        inflight_cap, park_min, stash_wave_f4, block_major, job_batch, ad_min_spp, ad_check_every;
+    unsigned long long job_count, view_jobs, endgame_from, batch_until;
+    float rr, ad_tolerance, ad_floor;
+};
 
 int main(int argc, char **argv) {
     const ort::Knobs kn = ort::read_knobs();
@@ -28,7 +49,9 @@ int main(int argc, char **argv) {
     unsigned long materials = 0, lights = 0, pro_boxes = 0, pro_spheres = 0, pro_cyls = 0;
     unsigned long long job_count = 0;
     unsigned long view_count = 1;
-    bool views_given = false, adaptive = false;
+    bool views_given = false, adaptive = false, fill = false;
+    unsigned long view_seed = 0;
+    ort_adaptive ad{};
     const char *query = nullptr;
     unsigned long long count = 0;
     for (int i = 1; i < argc; ++i) {
@@ -67,6 +90,15 @@ int main(int argc, char **argv) {
         else if (is("count")) count = strtoull(v, nullptr, 0);
         else if (is("views")) { view_count = strtoul(v, nullptr, 0); views_given = true; }
         else if (is("adaptive")) adaptive = atoi(v) != 0;
+        else if (is("fill")) fill = atoi(v) != 0;
+        else if (is("seed")) p.seed = (uint32_t)strtoul(v, nullptr, 0);
+        else if (is("rr")) p.rr = strtof(v, nullptr);
+        else if (is("view_seed")) view_seed = strtoul(v, nullptr, 0);
+        else if (is("min_spp")) ad.min_spp = (uint32_t)strtoul(v, nullptr, 0);
+        else if (is("max_spp")) ad.max_spp = (uint32_t)strtoul(v, nullptr, 0);
+        else if (is("check_every")) ad.check_every = (uint32_t)strtoul(v, nullptr, 0);
+        else if (is("tolerance")) ad.tolerance = strtof(v, nullptr);
+        else if (is("floor")) ad.floor = strtof(v, nullptr);
         else { fprintf(stderr, "launch_plan: unknown argument %s\n", argv[i]); return 2; }
     }
     if (!tab_flags_given) t.tab_flags = ort::table_fit_flags(materials, lights, (uint32_t)pro_boxes, (uint32_t)pro_spheres, (uint32_t)pro_cyls);
@@ -97,5 +129,17 @@ int main(int argc, char **argv) {
     if (adaptive) printf(", \"adaptive\": %d", l.adaptive);
     if (views_given || adaptive) printf(", \"views\": %d, \"view_count\": %u, \"view_jobs\": %llu", l.views, l.view_count, l.view_jobs);
     printf("}\n");
+    if (fill) { /* as device_render calls it: a batch's views, the single adaptive frame's one view, or none */
+        std::vector<ort_view> views(views_given || adaptive ? view_count : 0);
+        for (size_t v = 0; v < views.size(); ++v) views[v].seed = (uint32_t)(view_seed + v);
+        FillView rv{};
+        ort::render_view(p, l, views.empty() ? nullptr : views.data(), adaptive ? &ad : nullptr, &rv);
+        auto print = [](const char *name, auto v) {
+            if constexpr (std::is_floating_point<decltype(v)>::value) printf("%s = %.9g\n", name, (double)v);
+            else printf("%s = %lld\n", name, (long long)v);
+        };
+#define FILL_PRINT(f) print(#f, rv.f);
+        FILL_FIELDS(FILL_PRINT)
+    }
     return 0;
 }
