@@ -1,9 +1,12 @@
 /*
  * ort_kernels.hip -- host side of the path-trace kernels: scene upload and the render and ray-query calls as HIP plumbing
  * (device_render turns the LaunchPlan of ort_plan.h, where the launch policy lives, into buffers and launches), and the
- * kernels' four-waves-per-SIMD build (instantiated by launch_path_tracer below; the lane code itself is ort_lane.h).
+ * kernels' four-waves-per-SIMD build (the lane code itself is ort_lane.h).  A plan becomes a launch by its KernelVariant
+ * (plan_variant, ort_plan.h): kLaunchers below pairs every entry of that header's list of built kernels with this unit's kernel,
+ * which that instantiates, or a sibling unit's launcher.  A render and a ray query share the steps around their kernels.
  */
 #include <algorithm>
+#include <memory>
 #include <type_traits>
 
 #include "ort_lane.h"
@@ -38,7 +41,7 @@ static_assert(kPlanBlock == (uint32_t)kBlock && kPlanLdsStack == (uint32_t)kLdsS
         }                                                                                      \
     } while (0)
 
-/* a device allocation that frees itself (on the device that is current then: device_release sets it); move-only */
+/* a device allocation that frees itself (on the device that is current then: ~DeviceScene sets it); move-only */
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
@@ -59,8 +62,16 @@ struct DevBuf {
     template <typename T> T *as() const { return (T *)p; }
 };
 
+/* what an upload creates on its device, and owns: the buffers free themselves, the rest goes here */
 struct DeviceScene {
-    int device = -1;
+    explicit DeviceScene(int device_index) : device(device_index) {}
+    ~DeviceScene() { /* the members' destructors run after this body: on this device */
+        (void)hipSetDevice(device);
+        if (h_active) (void)hipHostFree(h_active);
+        for (hipEvent_t ev : {ev0, ev1, ev_done})
+            if (ev) (void)hipEventDestroy(ev);
+    }
+    const int device;
     Knobs knobs;
     DevBuf nodes, tris, spheres, boxes, cyls, materials;
     DevBuf nodes4; /* the 4-wide form of the tree (uploaded when it exists and its depth fits the traversal stacks) */
@@ -116,14 +127,7 @@ static int upload_vec(const std::vector<T> &v, DevBuf *dst, std::string *err) {
 }
 
 void device_release(Scene *scene) {
-    DeviceScene *d = scene->dev;
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    if (d->h_active) (void)hipHostFree(d->h_active);
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
-    if (d->ev_done) (void)hipEventDestroy(d->ev_done);
-    delete d; /* every DevBuf frees itself */
+    delete scene->dev;
     scene->dev = nullptr;
 }
 
@@ -135,9 +139,9 @@ int device_upload(Scene *scene, int device, std::string *err) {
     if (device < 0 || device >= n) { *err = "device index out of range"; return ORT_ERR_INVALID; }
     device_release(scene);
     ORT_HIP(hipSetDevice(device));
-    DeviceScene *d = new DeviceScene();
-    d->device = device;
-    scene->dev = d;
+    /* the scene becomes resident (check_resident) once everything is there: a failure on the way frees what was built */
+    std::unique_ptr<DeviceScene> owner(new DeviceScene(device));
+    DeviceScene *d = owner.get();
     const Tree &t = scene->tree;
     if ((rc = upload_vec(t.nodes, &d->nodes, err))) return rc;
     /* a traversal of the wide tree stacks at most three entries per level; the smallest stack is resolve_hit's re-traversal */
@@ -208,6 +212,7 @@ int device_upload(Scene *scene, int device, std::string *err) {
         if ((rc = d->cold.ensure(sizeof(SceneCold), err))) return rc;
         ORT_HIP(hipMemcpy(d->cold.p, &cold, sizeof(SceneCold), hipMemcpyHostToDevice));
     }
+    scene->dev = owner.release();
     return ORT_OK;
 }
 
@@ -230,7 +235,7 @@ int device_unit_eval(int device, const void *records, uint32_t n, float *out, st
    hit) until no slot produces a ray any more.  The host only learns "finished" by reading a
    counter, so it launches iterations in batches and checks after each batch. */
 template <bool COUNTERS>
-static int launch_wavefront(DeviceScene *d, const SceneView &sv, const RenderView &rvf, const RenderHot &rv, hipStream_t stream, std::string *err) {
+static int launch_wavefront(DeviceScene *d, const LaunchPlan &, const SceneView &sv, const RenderView &rvf, const RenderHot &rv, hipStream_t stream, std::string *err) {
     const uint32_t kMaxSlots = 1u << 21;
     unsigned long long want = rvf.job_count < kMaxSlots ? rvf.job_count : kMaxSlots;
     uint32_t S = (uint32_t)((want + kBlock - 1) / kBlock) * kBlock;
@@ -271,66 +276,56 @@ static int launch_wavefront(DeviceScene *d, const SceneView &sv, const RenderVie
     return ORT_OK;
 }
 
-/* The path-trace kernel a plan names.  These sixteen variants, the six of a batch of views, the eight of the radiance queries
-   (device_radiance), the eight of the adaptive ones (ort_kernels_adaptive.hip), the eight of the adaptive camera render
-   (ort_kernels_render_adaptive.hip) and the two of ort_kernels_w5.hip are all that is built (each costs its share of minutes of compile time); plan_render produces no other, and one that did would be
-   an error, not a fallback. */
-static int launch_path_tracer(const LaunchPlan &pl, hipStream_t stream, const SceneView &sv, const RenderHot &hot, std::string *err) {
-    if (pl.adaptive) { /* pt_adaptive<counters, diffuse, tabs>: the plain loop over a batch of views, every pixel cut by the stopping rule */
-        if (!pl.views || !pl.implicit || pl.mode != PLAN_JOBS_PIXEL || pl.exchange || pl.five || pl.wide || pl.wavefront) {
-            *err = "internal: no adaptive kernel is built for this launch plan";
-            return ORT_ERR_INTERNAL;
-        }
-        ort_launch_render_adaptive(pl.counters, pl.diffuse, pl.tabs, pl.grid, (void *)stream, &sv, &hot);
-        return ORT_OK;
-    }
-    if (pl.views) { /* the plain loop with the camera table: counters | diffuse, tabs (implicit follows from both) */
-        if (pl.exchange || pl.five || pl.wide || pl.wavefront || pl.implicit != (!pl.counters && pl.tabs) || (pl.counters && pl.diffuse)) {
-            *err = "internal: no views kernel is built for this launch plan";
-            return ORT_ERR_INTERNAL;
-        }
-#define ORT_PTV(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot); return ORT_OK
-        if (pl.counters) {
-            if (pl.tabs) { ORT_PTV(pt_persistent<true, false, true, false, false, true>); }
-            ORT_PTV(pt_persistent<true, false, false, false, false, true>);
-        }
-        if (pl.diffuse) {
-            if (pl.tabs) { ORT_PTV(pt_persistent<false, true, true, true, false, true>); }
-            ORT_PTV(pt_persistent<false, true, false, false, false, true>);
-        }
-        if (pl.tabs) { ORT_PTV(pt_persistent<false, false, true, true, false, true>); }
-        ORT_PTV(pt_persistent<false, false, false, false, false, true>);
-#undef ORT_PTV
-    }
-    if (pl.five) {
-        ort_launch_w5(pl.diffuse ? 1 : 0, pl.grid, (void *)stream, &sv, &hot);
-        return ORT_OK;
-    }
-    enum : unsigned { X = 32, W = 16, C = 8, D = 4, T = 2, I = 1 }; /* exchange, wide, then the template arguments */
-    const unsigned flavour = (pl.counters ? C : 0u) | (pl.diffuse ? D : 0u);
-    const unsigned key = pl.exchange ? X | flavour : (pl.wide ? W : 0u) | flavour | (pl.tabs ? T : 0u) | (pl.implicit ? I : 0u);
-#define ORT_PT(KEY, ...) case KEY: hipLaunchKernelGGL((__VA_ARGS__), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot); return ORT_OK
-    switch (key) {
-        ORT_PT(X | C | D, pt_persistent_x<true, true>); /* diagnostics: probes of the diffuse flavour */
-        ORT_PT(X | D, pt_persistent_x<false, true>);
-        ORT_PT(X, pt_persistent_x<false, false>);
-        ORT_PT(W | C | T, pt_persistent<true, false, true, false, true>);
-        ORT_PT(W | D | T | I, pt_persistent<false, true, true, true, true>);
-        ORT_PT(W | T | I, pt_persistent<false, false, true, true, true>);
-        ORT_PT(C | D | T, pt_persistent<true, true, true>);
-        ORT_PT(C | D, pt_persistent<true, true, false>);
-        ORT_PT(C | T, pt_persistent<true, false, true>);
-        ORT_PT(C, pt_persistent<true, false, false>);
-        ORT_PT(D | T | I, pt_persistent<false, true, true, true>);
-        ORT_PT(D | T, pt_persistent<false, true, true>);
-        ORT_PT(D, pt_persistent<false, true, false>);
-        ORT_PT(T | I, pt_persistent<false, false, true, true>);
-        ORT_PT(T, pt_persistent<false, false, true>);
-        ORT_PT(0u, pt_persistent<false, false, false>);
-    }
-#undef ORT_PT
-    *err = "internal: no kernel is built for this launch plan";
-    return ORT_ERR_INTERNAL;
+/* the sibling units' kernels, as launchers of launch_wavefront's kind */
+static int launch_five_waves(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
+    ort_launch_w5(pl.diffuse ? 1 : 0, pl.grid, (void *)stream, &sv, &hot);
+    return ORT_OK;
+}
+static int launch_adaptive(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
+    ort_launch_render_adaptive(pl.counters, pl.diffuse, pl.tabs, pl.grid, (void *)stream, &sv, &hot);
+    return ORT_OK;
+}
+
+/* What launches each of the built kernels (kBuiltKernels, ort_plan.h), in that list's order: a kernel of this unit, which its
+   entry here instantiates, or the host function that launches what another family is made of */
+struct Launcher {
+    KernelVariant variant;
+    void (*kernel)(SceneView, RenderHot);
+    int (*host)(DeviceScene *, const LaunchPlan &, const SceneView &, const RenderView &, const RenderHot &, hipStream_t, std::string *);
+};
+template <bool C, bool D, bool T, bool I = false, bool W = false>
+constexpr Launcher loop() { return {{KF_LOOP, C, D, T, I, W}, pt_persistent<C, D, T, I, W>, nullptr}; }
+template <bool C, bool D, bool T, bool I = false>
+constexpr Launcher views() { return {{KF_LOOP_VIEWS, C, D, T, I, false}, pt_persistent<C, D, T, I, false, true>, nullptr}; }
+template <bool C, bool D>
+constexpr Launcher exchange() { return {{KF_EXCHANGE, C, D, true, true, false}, pt_persistent_x<C, D>, nullptr}; }
+constexpr Launcher five(bool d) { return {{KF_FIVE, false, d, true, true, false}, nullptr, launch_five_waves}; }
+constexpr Launcher adaptive(bool c, bool d, bool t) { return {{KF_ADAPTIVE, c, d, t, true, false}, nullptr, launch_adaptive}; }
+constexpr Launcher kLaunchers[] = {
+    {{KF_WAVEFRONT, false, false, false, false, false}, nullptr, launch_wavefront<false>},
+    {{KF_WAVEFRONT, true, false, false, false, false}, nullptr, launch_wavefront<true>},
+    loop<false, false, false>(), loop<false, false, true>(), loop<false, false, true, true>(),
+    loop<false, true, false>(), loop<false, true, true>(), loop<false, true, true, true>(),
+    loop<true, false, false>(), loop<true, false, true>(), loop<true, true, false>(), loop<true, true, true>(),
+    loop<false, false, true, true, true>(), loop<false, true, true, true, true>(), loop<true, false, true, false, true>(),
+    views<false, false, false>(), views<false, false, true, true>(), views<false, true, false>(), views<false, true, true, true>(),
+    views<true, false, false>(), views<true, false, true>(),
+    exchange<false, false>(), exchange<false, true>(), exchange<true, true>(),
+    five(false), five(true),
+    adaptive(false, false, false), adaptive(false, false, true), adaptive(false, true, false), adaptive(false, true, true),
+    adaptive(true, false, false), adaptive(true, false, true), adaptive(true, true, false), adaptive(true, true, true),
+};
+constexpr bool launchers_match(size_t i = 0) { return i == kBuiltKernelCount || (kLaunchers[i].variant == kBuiltKernels[i] && launchers_match(i + 1)); }
+static_assert(sizeof(kLaunchers) / sizeof(kLaunchers[0]) == kBuiltKernelCount && launchers_match(),
+              "kLaunchers holds the entries of kBuiltKernels (ort_plan.h), all of them, in its order");
+
+/* the kernel a plan names, launched; a plan that names one nobody built is an error, not a fallback */
+static int launch_path_tracer(DeviceScene *d, const LaunchPlan &pl, const SceneView &sv, const RenderView &rv, const RenderHot &hot, hipStream_t stream, std::string *err) {
+    const size_t i = built_index(plan_variant(pl));
+    if (i == kBuiltKernelCount) { *err = "internal: no kernel is built for this launch plan"; return ORT_ERR_INTERNAL; }
+    if (kLaunchers[i].host) return kLaunchers[i].host(d, pl, sv, rv, hot, stream, err);
+    hipLaunchKernelGGL(kLaunchers[i].kernel, dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot);
+    return ORT_OK;
 }
 
 /* a render or ray query that was returned from without waiting: waited for, and its tripwire checked (one call at a time
@@ -343,6 +338,48 @@ static int settle_inflight(DeviceScene *d, std::string *err, const char *what = 
     unsigned long long ovf = 0;
     ORT_HIP(hipMemcpy(&ovf, d->ctrl() + 7, sizeof(ovf), hipMemcpyDeviceToHost));
     if (ovf) { *err = what; return ORT_ERR_UNSUPPORTED; }
+    return ORT_OK;
+}
+
+/* ---- the steps of every launch on a scene, render or ray query, around its kernels -------------------------------------------- */
+/* it starts from a zeroed ctrl, and its RenderView points into it: the job counter and the work counters */
+static int reset_ctrl(DeviceScene *d, RenderView *rv, hipStream_t stream, std::string *err) {
+    rv->next_job = d->ctrl();
+    rv->counters = d->ctrl() + 1;
+    ORT_HIP(hipMemsetAsync(d->ctrl(), 0, 128 * sizeof(unsigned long long), stream));
+    return ORT_OK;
+}
+/* ... and from its RenderView in HBM (pageable source: the copy is staged before the call returns); the kernels get the few
+   fields every ray reads by value and a pointer to the rest.  timed: the launch's time is asked for */
+static int upload_view(DeviceScene *d, const RenderView &rv, bool timed, hipStream_t stream, RenderHot *hot, std::string *err) {
+    ORT_HIP(hipMemcpyAsync(d->rv_dev.p, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
+    *hot = render_hot<RenderHot>(rv, d->rv_dev.p);
+    if (timed) ORT_HIP(hipEventRecord(d->ev0, stream));
+    return ORT_OK;
+}
+/* after the last kernel: what the launches said, and the end of the time */
+static int end_kernels(DeviceScene *d, bool timed, hipStream_t stream, std::string *err) {
+    ORT_HIP(hipGetLastError());
+    if (timed) ORT_HIP(hipEventRecord(d->ev1, stream));
+    return ORT_OK;
+}
+/* after everything the call enqueues on the scene's buffers: the next call on the scene settles this one (settle_inflight) */
+static int mark_inflight(DeviceScene *d, hipStream_t stream, std::string *err) {
+    ORT_HIP(hipEventRecord(d->ev_done, stream));
+    d->inflight = true;
+    return ORT_OK;
+}
+
+/* a settled, timed launch's time and counters, added to stats (paths: its kernels count paths) */
+static int add_launch_stats(const DeviceScene *d, bool counters, bool paths, ort_stats *stats, std::string *err) {
+    float ms = 0;
+    ORT_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+    unsigned long long c[6];
+    ORT_HIP(hipMemcpy(c, d->ctrl() + 1, sizeof(c), hipMemcpyDeviceToHost));
+    stats->kernel_ms += ms;
+    stats->fallback_rays += c[5]; /* counted by every kernel flavour (straight to memory, rare) */
+    if (counters) { stats->rays += c[1]; stats->node_tests += c[2]; stats->tri_tests += c[3]; stats->analytic_tests += c[4]; }
+    if (counters && paths) stats->paths += c[0];
     return ORT_OK;
 }
 
@@ -434,18 +471,6 @@ static int print_util_diag(const DeviceScene *d, std::string *err) {
     return ORT_OK;
 }
 
-static int read_render_stats(const DeviceScene *d, bool counters, ort_stats *stats, std::string *err) {
-    memset(stats, 0, sizeof(*stats));
-    float ms = 0;
-    ORT_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
-    stats->kernel_ms = ms;
-    unsigned long long c[6];
-    ORT_HIP(hipMemcpy(c, d->ctrl() + 1, sizeof(c), hipMemcpyDeviceToHost));
-    stats->fallback_rays = c[5]; /* counted by every kernel flavour (straight to memory, rare) */
-    if (counters) { stats->paths = c[0]; stats->rays = c[1]; stats->node_tests = c[2]; stats->tri_tests = c[3]; stats->analytic_tests = c[4]; }
-    return ORT_OK;
-}
-
 /* a sibling unit compiles the argument structs in a namespace of its own and takes them as bytes (the RenderView too: its lanes
    read it behind hot.c): its three sizes against this unit's */
 static bool same_layout(void (*unit_layout)(size_t *)) {
@@ -501,8 +526,6 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     rv.ad_spp = (uint32_t *)planes[1].dev;
     rv.ad_m2 = (float *)planes[2].dev;
     rv.final_states = (uint32_t *)planes[3].dev;
-    rv.next_job = d->ctrl();
-    rv.counters = d->ctrl() + 1;
     if (c.jobs) {
         if ((rc = d->jobs.ensure((size_t)c.job_count * sizeof(ort_tile_job), err))) return rc;
         /* synchronous: the caller's job list may be gone when this call returns */
@@ -531,31 +554,24 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
         if ((rc = d->stash.ensure(pl.stash_bytes, err))) return rc;
         rv.stash = d->stash.as<float4>();
     }
-    ORT_HIP(hipMemsetAsync(d->ctrl(), 0, 128 * sizeof(unsigned long long), stream));
+    if ((rc = reset_ctrl(d, &rv, stream, err))) return rc;
     if (pl.drain_bytes && c.stats) {
         if ((rc = d->drain.ensure(pl.drain_bytes, err))) return rc;
         ORT_HIP(hipMemsetAsync(d->drain.p, 0, pl.drain_bytes, stream));
         rv.drain = d->drain.as<unsigned long long>();
     }
-    /* the RenderView goes to HBM (pageable source: the copy is staged before the call returns); the kernels get the few
-       fields every ray reads by value and a pointer to the rest */
-    ORT_HIP(hipMemcpyAsync(d->rv_dev.p, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
-    const RenderHot hot = render_hot<RenderHot>(rv, d->rv_dev.p);
-    if (c.stats) ORT_HIP(hipEventRecord(d->ev0, stream));
-    if (pl.wavefront) rc = pl.counters ? launch_wavefront<true>(d, sv, rv, hot, stream, err) : launch_wavefront<false>(d, sv, rv, hot, stream, err);
-    else rc = launch_path_tracer(pl, stream, sv, hot, err);
-    if (rc) return rc;
-    ORT_HIP(hipGetLastError());
+    RenderHot hot;
+    if ((rc = upload_view(d, rv, c.stats != nullptr, stream, &hot, err)) || (rc = launch_path_tracer(d, pl, sv, rv, hot, stream, err))) return rc;
     if (rv.mode == JOBS_CHUNK) {
+        ORT_HIP(hipGetLastError());
         unsigned long long total = (unsigned long long)rv.my_blocks * 64ull;
         unsigned int cgrid = (unsigned int)((total + 255) / 256);
         if (pl.views) {
             cgrid = (unsigned int)((total * pl.view_count + 255) / 256);
             if (cgrid) hipLaunchKernelGGL(combine_chunks_views, dim3(cgrid), dim3(256), 0, stream, hot);
         } else if (cgrid) hipLaunchKernelGGL(combine_chunks, dim3(cgrid), dim3(256), 0, stream, hot);
-        ORT_HIP(hipGetLastError());
     }
-    if (c.stats) ORT_HIP(hipEventRecord(d->ev1, stream));
+    if ((rc = end_kernels(d, c.stats != nullptr, stream, err))) return rc;
 
     if (c.host)
         for (const Plane &pn : planes)
@@ -563,13 +579,13 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     if (c.job_states) ORT_HIP(hipMemcpyAsync(c.job_states, d->states.p, (size_t)c.job_count * 4u, hipMemcpyDeviceToHost, stream));
     /* every synchronous form of the call checks the tripwire before it returns (the fire-and-forget device form, stats == NULL,
        cannot without a sync: the next call on the scene does; bench.py asks for stats) */
-    ORT_HIP(hipEventRecord(d->ev_done, stream));
-    d->inflight = true;
+    if ((rc = mark_inflight(d, stream, err))) return rc;
     if (c.stats || c.host || c.job_states)
         if ((rc = settle_inflight(d, err, "reference-order fallback queue overflowed"))) return rc;
     if (c.stats && d->knobs.debug_fallback && (rc = print_fallback_diag(d, pl, err))) return rc;
     if (c.stats && rv.drain && (rc = print_drain_diag(d, pl, err))) return rc;
-    if (c.stats && (rc = read_render_stats(d, pl.counters, c.stats, err))) return rc;
+    if (c.stats) memset(c.stats, 0, sizeof(*c.stats));
+    if (c.stats && (rc = add_launch_stats(d, pl.counters, true, c.stats, err))) return rc;
     if (c.stats && pl.counters && pl.util && (rc = print_util_diag(d, err))) return rc;
     return ORT_OK;
 }
@@ -610,31 +626,14 @@ static int launch_query(Scene *scene, DeviceScene *d, RenderView rv, uint64_t co
     const SceneView sv = scene_view(scene, d);
     const QueryPlan pl = radiance ? plan_radiance(scene_traits(scene, d), count, counters, d->knobs) : plan_ray_query(scene_traits(scene, d), count, counters);
     rv.job_count = count; /* the job space: the ray array, drawn in batches */
-    rv.next_job = d->ctrl();
-    rv.counters = d->ctrl() + 1;
     rv.job_batch = pl.job_batch; rv.batch_until = pl.batch_until;
     rv.refill_below = pl.refill_below; rv.descend_below = pl.descend_below;
-    ORT_HIP(hipMemsetAsync(d->ctrl(), 0, 128 * sizeof(unsigned long long), stream));
-    ORT_HIP(hipMemcpyAsync(d->rv_dev.p, &rv, sizeof(RenderView), hipMemcpyHostToDevice, stream));
-    const RenderHot hot = render_hot<RenderHot>(rv, d->rv_dev.p);
-    if (stats) ORT_HIP(hipEventRecord(d->ev0, stream));
+    RenderHot hot;
+    if ((rc = reset_ctrl(d, &rv, stream, err)) || (rc = upload_view(d, rv, stats != nullptr, stream, &hot, err))) return rc;
     issue(sv, hot, pl);
-    /* mark it in flight; with stats, wait for it and add its time and counters */
-    ORT_HIP(hipGetLastError());
-    if (stats) ORT_HIP(hipEventRecord(d->ev1, stream));
-    ORT_HIP(hipEventRecord(d->ev_done, stream));
-    d->inflight = true;
-    if (stats) {
-        if ((rc = settle_inflight(d, err))) return rc;
-        float ms = 0;
-        ORT_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
-        unsigned long long c[6];
-        ORT_HIP(hipMemcpy(c, d->ctrl() + 1, sizeof(c), hipMemcpyDeviceToHost));
-        stats->kernel_ms += ms;
-        stats->fallback_rays += c[5];
-        if (counters) { stats->rays += c[1]; stats->node_tests += c[2]; stats->tri_tests += c[3]; stats->analytic_tests += c[4]; }
-        if (counters && radiance) stats->paths += c[0];
-    }
+    if ((rc = end_kernels(d, stats != nullptr, stream, err)) || (rc = mark_inflight(d, stream, err))) return rc;
+    /* with stats, wait for it and add its time and counters */
+    if (stats && ((rc = settle_inflight(d, err)) || (rc = add_launch_stats(d, counters, radiance, stats, err)))) return rc;
     return ORT_OK;
 }
 
@@ -781,6 +780,5 @@ int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const vo
 }
 
 } // namespace ort
-
 
 #endif /* !ORT_HOST_SIM */

@@ -371,6 +371,65 @@ inline LaunchPlan plan_render_adaptive(const SceneTraits &t, const ort_render_pa
     return pl;
 }
 
+/* ---- the kernels that are built ------------------------------------------------------------------------------------------ */
+/* A render kernel by name: its family and its template arguments.  A bool its family's kernels do not take is stated as what
+   they are compiled with (the ray exchange and the five-waves build: tabs and implicit; wavefront mode: none of the four) */
+enum KernelFamily : int { KF_NONE = 0, KF_WAVEFRONT, KF_LOOP, KF_LOOP_VIEWS, KF_EXCHANGE, KF_FIVE, KF_ADAPTIVE };
+struct KernelVariant {
+    KernelFamily family;
+    bool counters, diffuse, tabs, implicit, wide;
+};
+constexpr bool operator==(const KernelVariant &a, const KernelVariant &b) {
+    return a.family == b.family && a.counters == b.counters && a.diffuse == b.diffuse && a.tabs == b.tabs && a.implicit == b.implicit && a.wide == b.wide;
+}
+
+/* the variant a plan asks for.  A plan that claims two families at once, or the stopping rule outside a PIXEL batch of views,
+   names none */
+inline KernelVariant plan_variant(const LaunchPlan &pl) {
+    if ((int)pl.wavefront + (int)pl.exchange + (int)pl.five + (int)pl.views > 1 || (pl.adaptive && !(pl.views && pl.mode == PLAN_JOBS_PIXEL)))
+        return {KF_NONE, false, false, false, false, false};
+    if (pl.wavefront) return {KF_WAVEFRONT, pl.counters, false, false, false, false};
+    if (pl.exchange) return {KF_EXCHANGE, pl.counters, pl.diffuse, true, true, false};
+    if (pl.five) return {KF_FIVE, false, pl.diffuse, true, true, false};
+    return {pl.adaptive ? KF_ADAPTIVE : pl.views ? KF_LOOP_VIEWS : KF_LOOP, pl.counters, pl.diffuse, pl.tabs, pl.implicit, pl.wide};
+}
+
+/* All that is built, and every one of them costs its share of minutes of compile time: ort_kernels.hip instantiates the first
+   four families (its table of launchers is held against this list at compile time), ort_kernels_w5.hip the fifth,
+   ort_kernels_render_adaptive.hip the sixth.  plan_render and plan_render_adaptive produce no other (tools/launch_plan sweep=1
+   and tests/test_launch_plan.py hold them to it); one that did would be an error, not a fallback.  The ray queries' families are
+   built for every combination of their bools and need no list */
+constexpr KernelVariant kBuiltKernels[] = {
+    /* family, counters, diffuse, tabs, implicit, wide */
+    {KF_WAVEFRONT, false, false, false, false, false}, {KF_WAVEFRONT, true, false, false, false, false},
+    /* the plain loop: implicit job spaces exist with tables and without counters; under counters the wide tree knows one flavour */
+    {KF_LOOP, false, false, false, false, false}, {KF_LOOP, false, false, true, false, false}, {KF_LOOP, false, false, true, true, false},
+    {KF_LOOP, false, true, false, false, false}, {KF_LOOP, false, true, true, false, false}, {KF_LOOP, false, true, true, true, false},
+    {KF_LOOP, true, false, false, false, false}, {KF_LOOP, true, false, true, false, false},
+    {KF_LOOP, true, true, false, false, false}, {KF_LOOP, true, true, true, false, false}, /* diffuse under counters: the ORT_DEBUG_UTIL probes */
+    {KF_LOOP, false, false, true, true, true}, {KF_LOOP, false, true, true, true, true}, {KF_LOOP, true, false, true, false, true},
+    /* ... with the camera table: counters | diffuse, tabs; implicit follows from both */
+    {KF_LOOP_VIEWS, false, false, false, false, false}, {KF_LOOP_VIEWS, false, false, true, true, false},
+    {KF_LOOP_VIEWS, false, true, false, false, false}, {KF_LOOP_VIEWS, false, true, true, true, false},
+    {KF_LOOP_VIEWS, true, false, false, false, false}, {KF_LOOP_VIEWS, true, false, true, false, false},
+    {KF_EXCHANGE, false, false, true, true, false}, {KF_EXCHANGE, false, true, true, true, false},
+    {KF_EXCHANGE, true, true, true, true, false}, /* diagnostics: probes of the diffuse flavour */
+    {KF_FIVE, false, false, true, true, false}, {KF_FIVE, false, true, true, true, false},
+    {KF_ADAPTIVE, false, false, false, true, false}, {KF_ADAPTIVE, false, false, true, true, false},
+    {KF_ADAPTIVE, false, true, false, true, false}, {KF_ADAPTIVE, false, true, true, true, false},
+    {KF_ADAPTIVE, true, false, false, true, false}, {KF_ADAPTIVE, true, false, true, true, false},
+    {KF_ADAPTIVE, true, true, false, true, false}, {KF_ADAPTIVE, true, true, true, true, false},
+};
+constexpr size_t kBuiltKernelCount = sizeof(kBuiltKernels) / sizeof(kBuiltKernels[0]);
+
+/* the place of v in the list, kBuiltKernelCount where nobody built it */
+constexpr size_t built_index(const KernelVariant &v) {
+    size_t i = 0;
+    while (i < kBuiltKernelCount && !(kBuiltKernels[i] == v)) ++i;
+    return i;
+}
+constexpr bool variant_built(const KernelVariant &v) { return built_index(v) < kBuiltKernelCount; }
+
 /* ---- the ray queries: the job space is the caller's ray array -------------------------------------------------------- */
 /* what ort_kernels.hip launches for a query over count rays: <counters, tabs> of raycast_rays / occluded_rays, <counters,
    diffuse, tabs> of radiance_rays, and the RenderView fields that are policy */

@@ -1,8 +1,8 @@
 """Camera render calls of every kind, one after another, on one uploaded scene: the plain render (CHUNK, PIXEL and the
 explicit jobs of WHOLE), a batch of views, the adaptive frame and the adaptive batch, host and device forms, two frame sizes
-and a radiance query in between.  They share one call path (device_render), the scene's staging buffers, its RenderView,
-camera table and job counter on the device, and the settling of a call that did not wait; every step is held bit for bit
-against the oracle, so a call that leaves something behind for the next one shows.
+and ray queries in between.  They share one call path (device_render), the scene's staging buffers, its RenderView,
+camera table and job counter on the device, and with the ray queries the steps around a launch and the settling of a call that
+did not wait; every step is held bit for bit against the oracle, so a call that leaves something behind for the next one shows.
 
 20 x 13 is 3 x 2 blocks of 8 x 8, partial on two edges; the rect cuts blocks on every side.  The oracle's frames and its
 chains of 64 samples per pixel of the rect are computed once per scene."""
@@ -10,9 +10,11 @@ import numpy as np
 import pytest
 
 import radiance_cases as rc
+import raycast_cases
 import render_adaptive_cases as rac
 import test_gpu_views as tv
 from conftest import assert_bits_equal
+from test_gpu_raycast import assert_same_hits
 from test_gpu_render_adaptive import torch_planes
 from views_cases import SEEDS
 
@@ -40,9 +42,15 @@ def world(api, oracle, scene, name):
         small, _ = osc.render(SW, SH, 3, SEED, "pixel", rr=RR)
         osc.set_camera(cams[0])
         whole, _ = osc.render(W, H, 2, SEED, "whole", rr=RR)
+        # 65 rays of all four kinds, one wave and one more, and their closest hits as test_gpu_raycast.py obtains them
+        some, _ = raycast_cases.mixed_rays(lambda r: osc.raycast(r[:, 0:3], r[:, 3:6])[0], name + " sequence", 80)
+        assert len(some) >= 65
+        hit_rays = np.ascontiguousarray(some[np.round(np.linspace(0, len(some) - 1, 65)).astype(int)])
+        hits = osc.raycast(hit_rays[:, 0:3], hit_rays[:, 3:6])
         cases = rc.mixed(name, scene.flatten(W, H), osc, 40, salt=" sequence")
         rad = rc.expected_of(osc, cases, (2,), RR)[2]   # (sets the oracle's camera to each ray's pinhole: nothing after it renders)
-        _worlds[name] = dict(cams=cams, ref=ref, chain=chain, small_chain=small_chain, small=small, whole=whole, cases=cases, rad=rad)
+        _worlds[name] = dict(cams=cams, ref=ref, chain=chain, small_chain=small_chain, small=small, whole=whole, cases=cases, rad=rad,
+                             hit_rays=hit_rays, hits=hits)
     return _worlds[name]
 
 
@@ -124,3 +132,26 @@ def test_calls_of_every_kind_in_sequence(api, oracle, gpu_scene, name):
     rgb, fin, _ = scene.radiance(wd["cases"].rays, wd["cases"].seeds, 2, RR, want_states=True)
     rc.assert_same(rgb, fin, wd["rad"][0], wd["rad"][1], name + " 9: radiance query")
     adaptive_frame(scene, wd, name + " 9: adaptive frame again")
+    # 10. render, closest hits, radiance, render: four device forms without stats back to back on one stream.  No call waits;
+    # each settles the one before it, and all share the scene's ctrl words, RenderView and events
+    cases = wd["cases"]
+    d_first, d_last = (torch.full((H * W * 3,), float(FILL), dtype=torch.float32, device=dev) for _ in range(2))
+    d_hit_rays = torch.from_numpy(wd["hit_rays"]).to(dev)
+    d_hits = torch.full((65 * 24,), 0xAB, dtype=torch.uint8, device=dev)
+    d_rays = torch.from_numpy(np.ascontiguousarray(cases.rays, "<f4")).to(dev)
+    d_seeds = torch.from_numpy(np.ascontiguousarray(cases.seeds, "<u4").view("<i4")).to(dev)
+    d_rgb = torch.full((40 * 3,), float(FILL), dtype=torch.float32, device=dev)
+    d_fin = torch.zeros(40, dtype=torch.int32, device=dev)
+    pixel = scene.params(W, H, 3, SEED, "pixel", rr=RR)
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        assert scene.render_device(d_first.data_ptr(), pixel, stream=stream.cuda_stream) is None
+        assert scene.raycast_device(d_hit_rays.data_ptr(), 65, d_hits.data_ptr(), stream=stream.cuda_stream) is None
+        assert scene.radiance_device(d_rays.data_ptr(), d_seeds.data_ptr(), 40, 2, RR, d_rgb.data_ptr(), d_fin.data_ptr(),
+                                     stream=stream.cuda_stream) is None
+        assert scene.render_device(d_last.data_ptr(), pixel, stream=stream.cuda_stream) is None
+    stream.synchronize()
+    assert_bits_equal(d_first.cpu().numpy().reshape(H, W, 3), want[0], name + " 10: first render")
+    assert_same_hits(d_hits.cpu().numpy().view(api.HIT_DTYPE), *wd["hits"], name + " 10: closest hits")
+    rc.assert_same(d_rgb.cpu().numpy().reshape(40, 3), d_fin.cpu().numpy().view("<u4"), wd["rad"][0], wd["rad"][1], name + " 10: radiance query")
+    assert_bits_equal(d_last.cpu().numpy().reshape(H, W, 3), want[0], name + " 10: render again")

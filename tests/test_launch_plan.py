@@ -496,3 +496,21 @@ def test_fill_of_a_three_view_chunk_batch(tool):
     assert rv["job_count"] == 3 * rv["view_jobs"] == p["job_count"]
     assert (rv["mode"], rv["nchunks"], rv["block_major"], rv["endgame_from"]) == (2, 2, 1, 0)
     assert [rv[k] for k in EXCHANGE_FIELDS] == [0] * 7
+
+
+# ---- every plan names a kernel that is built (plan_variant, kBuiltKernels: csrc/ort_plan.h) ----------------------------------
+def test_every_plan_of_the_sweep_names_a_built_kernel(tool):
+    """tools/launch_plan sweep=1: plan_render and plan_render_adaptive over traits, job spaces, frames and the knobs that choose
+    kernels, each plan's variant looked up in the list ort_kernels.hip's table of launchers is held against at compile time:
+    what would be an ORT_ERR_INTERNAL on the device is found here"""
+    r = subprocess.run([tool, "sweep=1"], env={k: v for k, v in os.environ.items() if k not in KNOBS}, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    s = json.loads(r.stdout)
+    assert s["plans"] > 0 and (s["unbuilt"], s["first"]) == (0, []), s
+    # the variant of a plan, by name: what the forcings of the GPU tests launch
+    assert (plan(tool, variant=1, **SMALL)["variant"], plan(tool, variant=1, **SMALL)["built"]) == ("loop<0, 1, 1, 1, 0>", 1)
+    assert plan(tool, {"ORT_EXCHANGE": "1", "ORT_DEBUG_UTIL": "1"}, counters=1, variant=1, **SMALL)["variant"] == "exchange<1, 1, 1, 1, 0>"
+    assert plan(tool, {"ORT_WAVES5": "1", "ORT_EXCHANGE": "0"}, variant=1, **SMALL)["variant"] == "five<0, 1, 1, 1, 0>"
+    assert plan(tool, views=3, counters=1, variant=1, **SMALL)["variant"] == "loop_views<1, 0, 1, 0, 0>"
+    assert plan(tool, policy="pixel", adaptive=1, variant=1, **SMALL)["variant"] == "adaptive<0, 1, 1, 1, 0>"
+    assert "variant" not in plan(tool, **SMALL)

@@ -11,7 +11,10 @@
    gives view v of views=N the seed S + v, min_spp= max_spp= check_every= tolerance= floor= are the stopping rule's; max_blocks
    defaults to what an upload on cu_count units fixes.  tab_flags, where not given, follows from
    materials= (index 0 included), lights=, pro_boxes=, pro_spheres=, pro_cyls= as at upload (table_fit_flags; all 0 by default).  tests/test_launch_plan.py holds the measured
-   crossovers and the knobs the GPU tests force kernels with against it. */
+   crossovers and the knobs the GPU tests force kernels with against it.
+   variant=1: the kernel the plan names (plan_variant) and whether it is built (kBuiltKernels) are appended to the line.
+   sweep=1, and nothing else: every plan of a grid over traits, calls and knobs (sweep() below) held against the built kernels; one
+   JSON line with the number of plans, how many name no built kernel, and the first of those. */
 #include <stdio.h>
 
 #include <type_traits>
@@ -36,7 +39,60 @@ struct FillView {
     float rr, ad_tolerance, ad_floor;
 };
 
+/* "family<counters, diffuse, tabs, implicit, wide>" */
+static std::string variant_name(const ort::KernelVariant &v) {
+    static const char *family[] = {"none", "wavefront", "loop", "loop_views", "exchange", "five", "adaptive"};
+    char b[64];
+    snprintf(b, sizeof(b), "%s<%d, %d, %d, %d, %d>", family[v.family], v.counters, v.diffuse, v.tabs, v.implicit, v.wide);
+    return b;
+}
+
+/* every plan the policy gives over: both BSDF flavours; all tables, the prologue's alone, none; a tree inside and outside the L2; a
+   cheap and a dear one; with and without the wide form; PIXEL, CHUNK and explicit jobs (the WHOLE policy); counters; one view and
+   three (implicit job spaces); a frame smaller than the grid and a long launch; both answers of the five-waves layout check; and
+   the knobs that choose kernels, unset and forced either way.  plan_render_adaptive for the single PIXEL frames */
+static int sweep() {
+    unsigned long long plans = 0, unbuilt = 0;
+    std::string first;
+    auto hold = [&](const ort::LaunchPlan &l) {
+        ++plans;
+        const ort::KernelVariant v = ort::plan_variant(l);
+        if (ort::variant_built(v)) return;
+        if (unbuilt++ < 5) first += (first.empty() ? "\"" : ", \"") + variant_name(v) + "\"";
+    };
+    const uint32_t tab_flags[] = {ort::kPlanAllTabs, ort::kPlanTabPro, 0u};
+    const int policies[] = {ORT_POLICY_PIXEL, ORT_POLICY_CHUNK, ORT_POLICY_WHOLE};
+    const int tri[] = {-1, 0, 1};
+    ort::Knobs kn;
+    ort::SceneTraits t;
+    t.cu_count = 256;
+    t.max_blocks = ort::upload_max_blocks(t.cu_count, kn);
+    for (int diffuse_only = 0; diffuse_only < 2; ++diffuse_only) for (uint32_t flags : tab_flags) for (size_t mb : {1u, 64u})
+    for (float sah : {0.02f, 0.3f}) for (int has_wide = 0; has_wide < 2; ++has_wide) {
+        t.diffuse_only = diffuse_only != 0; t.tab_flags = flags; t.fast_tree_bytes = mb << 20; t.sah_cost = sah; t.has_wide = has_wide != 0;
+        for (int policy : policies) for (int counters = 0; counters < 2; ++counters) for (int big = 0; big < 2; ++big)
+        for (uint32_t views : {1u, 3u}) for (int w5 = 0; w5 < 2; ++w5) {
+            const bool explicit_jobs = policy == ORT_POLICY_WHOLE;
+            if (explicit_jobs && views > 1u) continue;
+            ort_render_params p{};
+            p.width = big ? 1920 : 45; p.height = big ? 1080 : 35; p.spp = big ? 512u : 8u; p.chunk = big ? 64u : 4u;
+            p.policy = policy; p.rr = 0.8f; p.flags = counters ? ORT_RENDER_COUNTERS : 0;
+            const uint64_t jobs = explicit_jobs ? ort::shard_block_count(&p) : 0; /* a job per 8 x 8 block */
+            for (int exchange : tri) for (int wide : tri) for (int waves5 : tri) for (int wavefront = 0; wavefront < 2; ++wavefront)
+            for (int general = 0; general < 2; ++general) for (int lds_tables : {-1, 0}) for (int util = 0; util < 2; ++util) {
+                kn.exchange = exchange; kn.wide = wide; kn.waves5 = waves5; kn.wavefront = wavefront != 0;
+                kn.general_kernel = general != 0; kn.lds_tables = lds_tables; kn.debug_util = util != 0;
+                hold(ort::plan_render(t, p, explicit_jobs, jobs, w5 != 0, kn, views));
+                if (policy == ORT_POLICY_PIXEL && views == 1u) hold(ort::plan_render_adaptive(t, p, kn, 1));
+            }
+        }
+    }
+    printf("{\"sweep\": 1, \"plans\": %llu, \"unbuilt\": %llu, \"first\": [%s]}\n", plans, unbuilt, first.c_str());
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc == 2 && strcmp(argv[1], "sweep=1") == 0) return sweep();
     const ort::Knobs kn = ort::read_knobs();
     ort::SceneTraits t;
     t.tab_flags = ort::kPlanAllTabs;
@@ -49,7 +105,7 @@ int main(int argc, char **argv) {
     unsigned long materials = 0, lights = 0, pro_boxes = 0, pro_spheres = 0, pro_cyls = 0;
     unsigned long long job_count = 0;
     unsigned long view_count = 1;
-    bool views_given = false, adaptive = false, fill = false;
+    bool views_given = false, adaptive = false, fill = false, variant = false;
     unsigned long view_seed = 0;
     ort_adaptive ad{};
     const char *query = nullptr;
@@ -91,6 +147,7 @@ int main(int argc, char **argv) {
         else if (is("views")) { view_count = strtoul(v, nullptr, 0); views_given = true; }
         else if (is("adaptive")) adaptive = atoi(v) != 0;
         else if (is("fill")) fill = atoi(v) != 0;
+        else if (is("variant")) variant = atoi(v) != 0;
         else if (is("seed")) p.seed = (uint32_t)strtoul(v, nullptr, 0);
         else if (is("rr")) p.rr = strtof(v, nullptr);
         else if (is("view_seed")) view_seed = strtoul(v, nullptr, 0);
@@ -128,6 +185,7 @@ int main(int argc, char **argv) {
            t.tab_flags, ort::kPlanTabMatCap, ort::kPlanTabLightCap, ort::kPlanTabProCap);
     if (adaptive) printf(", \"adaptive\": %d", l.adaptive);
     if (views_given || adaptive) printf(", \"views\": %d, \"view_count\": %u, \"view_jobs\": %llu", l.views, l.view_count, l.view_jobs);
+    if (variant) printf(", \"variant\": \"%s\", \"built\": %d", variant_name(ort::plan_variant(l)).c_str(), ort::variant_built(ort::plan_variant(l)));
     printf("}\n");
     if (fill) { /* as device_render calls it: a batch's views, the single adaptive frame's one view, or none */
         std::vector<ort_view> views(views_given || adaptive ? view_count : 0);

@@ -1,7 +1,8 @@
 """Host time per camera render call: what device_render's plumbing costs where the kernel is next to nothing.  A 64 x 64, 1 spp
 PIXEL render in the device form without stats (ort_render_image_device: the call enqueues and returns; the next call on the scene
-waits for it), and the same frame as an adaptive call that never checks (ort_render_adaptive_device, min_spp = max_spp = 8, four
-planes).  Per leg: --warmup calls, then --reps windows of --calls calls each ending in one device synchronise, timed on the host
+waits for it), the same frame as an adaptive call that never checks (ort_render_adaptive_device, min_spp = max_spp = 8, four
+planes), and a closest-hit query over 4096 rays in the same form (ort_raycast_device: the ray queries go through the same steps
+around their launch).  Per leg: --warmup calls, then --reps windows of --calls calls each ending in one device synchronise, timed on the host
 clock around the window (a call settles the one before it, so the figure holds that call's kernel too); then --calls calls each
 followed by a synchronise, the clock around the call alone ("idle_us": what the host spends in a call that has nothing to wait
 for).  One JSON line: per leg the microseconds per call of every window, their median, s = (max - min) / median, and the
@@ -14,6 +15,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,11 +40,17 @@ def main():
     n = a.size * a.size
     rgb = torch.zeros(3 * n, dtype=torch.float32, device=dev)
     spp, m2, fin = (torch.zeros(n, dtype=t, device=dev) for t in (torch.int32, torch.float32, torch.int32))
+    rng = np.random.default_rng(2024)   # rays from the camera's place in all directions
+    d = rng.normal(size=(4096, 3))
+    rays = torch.from_numpy(np.concatenate([np.tile(scene.camera(a.size, a.size)[0], (4096, 1)), d / np.linalg.norm(d, axis=1, keepdims=True)],
+                                           axis=1).astype("<f4")).to(dev)
+    hits = torch.zeros(4096 * 24, dtype=torch.uint8, device=dev)
     plain = scene.params(a.size, a.size, 1, 2024, "pixel")
     adaptive = scene.params(a.size, a.size, 0, 2024, "pixel")
     legs = {
         "plain": lambda: scene.render_device(rgb.data_ptr(), plain),
         "adaptive": lambda: scene.render_adaptive_device(adaptive, *FIXED, rgb.data_ptr(), spp.data_ptr(), m2.data_ptr(), fin.data_ptr()),
+        "raycast": lambda: scene.raycast_device(rays.data_ptr(), 4096, hits.data_ptr()),
     }
     out = {"lib": api.LIB_PATH, "scene": a.scene, "size": a.size, "calls": a.calls}
     for name, call in legs.items():
