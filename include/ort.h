@@ -429,6 +429,57 @@ int ort_radiance_adaptive_device(ort_scene *scene, const void *d_rays, const voi
                                  void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, uint32_t flags, void *hip_stream,
                                  ort_stats *stats);
 
+/* ---- irradiance queries: cosine-weighted hemisphere gathers at points -------------------------
+ * Light probes, irradiance and lightmap baking from what a baker has: points and normals, not rays.  out_rgb[i] is the
+ * cosine-weighted mean of the radiance that arrives at p_i over the hemisphere about n_i: spp samples, each a direction drawn
+ * about n_i with the reference's own diffuse lobe and then ort_radiance's sample along it.  IRRADIANCE is pi * out_rgb; the
+ * radiosity of a diffuse texel with reflectance kd is kd * out_rgb (component by component).  The mean is returned as it is,
+ * C / (float)n, so that no rounding is added to it.
+ * points is count x {p.xyz, n.xyz} f32, 24 B each, 8-byte aligned: the layout of a ray, staged, sliced and checked as
+ * ort_radiance's rays.  p is used as given: a caller lifts it off its surface first (say p + 1e-3 n), or every sample starts
+ * inside the surface's own intersection threshold.
+ * The per-point domain is ort_radiance's per-ray test applied to (p, n): six finite components and |n|^2 (f32: x*x + y*y + z*z)
+ * within [0.999, 1.001].  A point outside it gets out_rgb[i] = NaN NaN NaN and final_states[i] = seeds[i] (as given, 0
+ * included) -- in the adaptive form also out_spp[i] = 0 and out_m2[i] = 0 --, is not traced, and leaves its neighbours alone.
+ * A point's samples run on ONE xorshift stream that starts at seeds[i] (0 is taken as 1).  Per sample, every operation a
+ * separately rounded f32 operation (no FMA):
+ *        e0  = rng_01(s);  e1 = rng_01(s)               (random.h: two steps of the stream)
+ *        c   = sqrtf(e0)                                 (ray.cpp:1123, the diffuse lobe)
+ *        phi = (2.0f * kPi) * e1                         (sample_brdf's azimuth)
+ *        m   = sample_lobe(n, c, phi)                    (ray.cpp:1065-1091: n normalised inside, cos/sin of the deterministic libm)
+ *        d   = normalize(m)
+ *   then ort_radiance's sample from the ray (p, d) on the same stream s: direction d as it stands, wo = -normalize(d), no aperture
+ *   draw, the sample body of ray.cpp:1247-1426.  This is sample_brdf's diffuse draw without its lobe-choice draw.
+ * The samples' colours are summed in sample order and divided by (float)spp, component by component; final_states[i] (may be
+ * NULL) is the stream's state afterwards.
+ * Two identities.  With s'_k the stream's state after sample k's two direction draws (never 0), sample k's colour and the state
+ * after it are, bit for bit, ort_radiance's for the single ray (p, d_k) with seed s'_k at spp = 1.  With rr = 0 the roulette never
+ * continues: with h the closest hit of (p, d_k), sample k adds the emission of h's material if that is a light and nothing
+ * otherwise, and draws one more rng_01 exactly when h.mat != 0 and the material is not a light.
+ * rr, flags, stats, count == 0, alignment, the order of the errors (before any device work) and independence of count, order and
+ * slicing are ort_radiance's, with points where rays stand.  With ORT_RENDER_COUNTERS, paths = (points inside the domain) * spp.
+ * A primary ray that ort_raycast would send to the exact octree walk takes it here too, per SAMPLE: p outside the scene's box
+ * with quadrics in the tree (every sample of such a point), a +-0 component of d_k with boxes in it.  Such points cost about
+ * 1 000x per sample (irradiance_points).
+ * The adaptive form is ort_radiance_adaptive's rule, unchanged, over these samples: the same C, Q, checks, outputs (out_spp,
+ * out_m2 and final_states may each be NULL), the same validation of ad, the same two identities -- with min_spp == max_spp == n it
+ * gives ort_irradiance's bits at spp = n -- and, with ORT_RENDER_COUNTERS, paths = the sum of out_spp. */
+
+/* host points and seeds in, host colours (and states) out; synchronous, staged as ort_radiance */
+int ort_irradiance(ort_scene *scene, const float *points, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr,
+                   float *out_rgb, uint32_t *final_states /* may be NULL */, uint32_t flags, ort_stats *stats);
+/* DEVICE pointers on the scene's device; enqueued on hip_stream (NULL = the default stream), returns without waiting unless
+   stats != NULL -- as ort_radiance_device */
+int ort_irradiance_device(ort_scene *scene, const void *d_points, const void *d_seeds, uint64_t count, uint32_t spp, float rr,
+                          void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats);
+/* the adaptive form, host and device: as ort_radiance_adaptive and ort_radiance_adaptive_device */
+int ort_irradiance_adaptive(ort_scene *scene, const float *points, const uint32_t *seeds, uint64_t count, const ort_adaptive *ad, float rr,
+                            float *out_rgb, uint32_t *out_spp /* may be NULL */, float *out_m2 /* may be NULL */,
+                            uint32_t *final_states /* may be NULL */, uint32_t flags, ort_stats *stats);
+int ort_irradiance_adaptive_device(ort_scene *scene, const void *d_points, const void *d_seeds, uint64_t count, const ort_adaptive *ad, float rr,
+                                   void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, uint32_t flags, void *hip_stream,
+                                   ort_stats *stats);
+
 /* ---- the adaptive camera render: one frame, or a batch of views ---------------------------------
  * The camera render with a sample count per pixel: "this noise level, at most max_spp samples", and a sample-count map back.
  * A pixel job under ORT_POLICY_PIXEL is all samples of pixel (x, y) on the stream job_seed(seed, y*W + x); the adaptive render is
@@ -531,7 +582,7 @@ int ort_gather_framebuffer_local(ort_comm **comms, int world, const void *const 
  * 11 fresnel/ggx/geometry ray.cpp:825-897 in Ks l_dot_h N H rough w     out F.xyz D G
  * 12 rng       random.h:5-53    in seed(bits) job(bits)      out step(bits) rng_01 rng_between(0,2pi) state(bits) job_seed(bits)
  * 13 IEEE ops                   in a b c                     out a/b sqrt(a) a*b a+b a-b (f32)bits(a) a*b+c
- * Ops 14-19 run the specialised forms the render and raycast kernels call in place of the functions above, composed
+ * Ops 14-20 run the specialised forms the render and raycast kernels call in place of the functions above, composed
  * as those kernels compose them; each must give its generic function's answer (diagnostics for the parity tests):
  * 14 aab forms  (op 3's inputs, 1/d as op 3)                 out hit_aab_finite t n.xyz, hit_aab_t_finite t, hit_aab_t t
  *               (the _finite forms only for finite o and 1/d: all_finite6)
@@ -541,7 +592,10 @@ int ort_gather_framebuffer_local(ort_comm **comms, int world, const void *const 
  * 17 BSDF sample as the all-lobes kernels draw it (op 5's inputs and outputs): sample_brdf_draw, ort_sincosf of phi,
  *               sample_brdf_finish<NORMALIZED = false>, normalize
  * 18 the same as the diffuse kernels draw it (sample_brdf_draw<true>, sample_brdf_finish<false, true>; diffuse materials)
- * 19 sincos     in x                                         out ort_sincosf of x: sin cos */
+ * 19 sincos     in x                                         out ort_sincosf of x: sin cos
+ * 20 hemisphere draw as the irradiance kernels compose it    in seed(bits) n.xyz     out d.xyz wo.xyz rng(bits)
+ *               (two rng_01, sqrt, ort_sincosf of 2 pi e1, sample_lobe_n about normalize(n), normalize; wo = -normalize(d); the
+ *               stream after the two draws; the seed is a stream state as it stands, 0 not taken as 1) */
 int ort_unit_eval_device(int device, const void *records, uint32_t count, float *out);
 
 /* ---- output ------------------------------------------------------------------------

@@ -138,6 +138,7 @@ EXPORTS = [
     "ort_gather_framebuffer_local", "ort_raycast", "ort_raycast_device",
     "ort_occluded", "ort_occluded_device", "ort_radiance", "ort_radiance_device",
     "ort_radiance_adaptive", "ort_radiance_adaptive_device",
+    "ort_irradiance", "ort_irradiance_device", "ort_irradiance_adaptive", "ort_irradiance_adaptive_device",
     "ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes",
     "ort_render_adaptive", "ort_render_adaptive_device", "ort_render_views_adaptive", "ort_render_views_adaptive_device"]
 
@@ -146,7 +147,7 @@ _lib = None
 
 def build_library():
     """Compile the HIP extension in-tree (hipcc --offload-arch=gfx950)."""
-    subprocess.check_call(["make", "-s", "-j4", "-C", CSRC_DIR])   # four kernel units, one job each
+    subprocess.check_call(["make", "-s", "-j5", "-C", CSRC_DIR])   # five kernel units, one job each
 
 
 def _share_hip_runtime_with_torch():
@@ -209,7 +210,9 @@ def lib():
                 ("ort_raycast", [vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
                 ("ort_occluded", [vp, vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
                 ("ort_radiance", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_float, vp, vp, C.c_uint32, stats]),
-                ("ort_radiance_adaptive", [vp, vp, vp, C.c_uint64, C.POINTER(Adaptive), C.c_float, vp, vp, vp, vp, C.c_uint32, stats])):
+                ("ort_radiance_adaptive", [vp, vp, vp, C.c_uint64, C.POINTER(Adaptive), C.c_float, vp, vp, vp, vp, C.c_uint32, stats]),
+                ("ort_irradiance", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_float, vp, vp, C.c_uint32, stats]),
+                ("ort_irradiance_adaptive", [vp, vp, vp, C.c_uint64, C.POINTER(Adaptive), C.c_float, vp, vp, vp, vp, C.c_uint32, stats])):
             getattr(L, name).argtypes = argtypes
             getattr(L, name + "_device").argtypes = argtypes[:-1] + [vp, stats]
         L.ort_camera_from_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.POINTER(Camera)]
@@ -594,13 +597,17 @@ class Scene:
         (|d|^2 within [0.999, 1.001], all components finite; any other ray gives NaN NaN NaN and its seed back); seeds: (N,)
         uint32, e.g. job_seeds(master, N).  Returns (rgb: float32[N, 3], stats dict), with want_states (rgb, states:
         uint32[N], stats dict); synchronous."""
+        return self._radiance(lib().ort_radiance, rays, seeds, spp, rr, want_states, counters)
+
+    def _radiance(self, call, rays, seeds, spp, rr, want_states, counters):
+        """The host form of a radiance or irradiance query: call is the library's function, rays the (N, 6) array."""
         rays = _rays(rays)
         seeds = _seeds(seeds, len(rays))
         out = np.zeros((len(rays), 3), "<f4")
         states = np.zeros(len(rays), "<u4") if want_states else None
         st, stats = _stats()
-        _check(lib().ort_radiance(self.handle, rays.ctypes.data, seeds.ctypes.data, len(rays), int(spp), float(rr), out.ctypes.data,
-                                  states.ctypes.data if want_states else None, _flags(counters), st))
+        _check(call(self.handle, rays.ctypes.data, seeds.ctypes.data, len(rays), int(spp), float(rr), out.ctypes.data,
+                    states.ctypes.data if want_states else None, _flags(counters), st))
         return (out, states, stats()) if want_states else (out, stats())
 
     def radiance_device(self, d_rays, d_seeds, n, spp, rr, d_out, d_states=0, stream=0, counters=False, want_stats=False):
@@ -621,6 +628,11 @@ class Scene:
         by operation).  A ray that saw no light in its first min_spp samples stops black: pick min_spp for the scene.
         Returns (rgb: float32[N, 3], spp: uint32[N] samples taken, m2: float32[N] sum of squared sample luminance, stats
         dict), with want_states (rgb, spp, m2, states, stats); a ray outside the domain gives NaN, 0, 0 and its seed."""
+        return self._radiance_adaptive(lib().ort_radiance_adaptive, rays, seeds, min_spp, max_spp, tolerance, floor, check_every, rr,
+                                       want_states, counters)
+
+    def _radiance_adaptive(self, call, rays, seeds, min_spp, max_spp, tolerance, floor, check_every, rr, want_states, counters):
+        """The host form of an adaptive radiance or irradiance query, as _radiance."""
         rays = _rays(rays)
         seeds = _seeds(seeds, len(rays))
         ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
@@ -629,9 +641,9 @@ class Scene:
         m2 = np.zeros(len(rays), "<f4")
         states = np.zeros(len(rays), "<u4") if want_states else None
         st, stats = _stats()
-        _check(lib().ort_radiance_adaptive(self.handle, rays.ctypes.data, seeds.ctypes.data, len(rays), C.byref(ad), float(rr),
-                                           out.ctypes.data, spp.ctypes.data, m2.ctypes.data,
-                                           states.ctypes.data if want_states else None, _flags(counters), st))
+        _check(call(self.handle, rays.ctypes.data, seeds.ctypes.data, len(rays), C.byref(ad), float(rr),
+                    out.ctypes.data, spp.ctypes.data, m2.ctypes.data,
+                    states.ctypes.data if want_states else None, _flags(counters), st))
         return (out, spp, m2, states, stats()) if want_states else (out, spp, m2, stats())
 
     def radiance_adaptive_device(self, d_rays, d_seeds, n, min_spp, max_spp, tolerance, floor, check_every, rr, d_out, d_spp=0,
@@ -643,6 +655,41 @@ class Scene:
         ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
         _check(lib().ort_radiance_adaptive_device(self.handle, _ptr(d_rays), _ptr(d_seeds), n, C.byref(ad), float(rr), _ptr(d_out),
                                                   _ptr(d_spp), _ptr(d_m2), _ptr(d_states), _flags(counters), _ptr(stream), st))
+        return stats()
+
+    # -- irradiance queries: cosine-weighted hemisphere gathers at points -------------------------
+    def irradiance(self, points, seeds, spp, rr=0.8, want_states=False, counters=False):
+        """The cosine-weighted mean of the radiance arriving at each point over the hemisphere about its normal: spp samples,
+        each a direction drawn about n with the reference's diffuse lobe and then radiance()'s sample along it, on the
+        xorshift stream that starts at seeds[i] (0 is taken as 1).  points: (N, 6) float32 p.xyz n.xyz, n of unit length
+        (|n|^2 within [0.999, 1.001], all components finite; any other point gives NaN NaN NaN and its seed back), p lifted
+        off its surface by the caller (say p + 1e-3 n).  Irradiance is pi * rgb; a diffuse texel's radiosity is kd * rgb.
+        Returns as radiance(); synchronous."""
+        return self._radiance(lib().ort_irradiance, points, seeds, spp, rr, want_states, counters)
+
+    def irradiance_device(self, d_points, d_seeds, n, spp, rr, d_out, d_states=0, stream=0, counters=False, want_stats=False):
+        """Device points (n x 6 float32) and seeds (n uint32) -> device colours (n x 3 float32) and, if d_states, final
+        states: raw pointers on the scene's device, as radiance_device()."""
+        st, stats = _stats(want_stats)
+        _check(lib().ort_irradiance_device(self.handle, _ptr(d_points), _ptr(d_seeds), n, int(spp), float(rr), _ptr(d_out), _ptr(d_states),
+                                           _flags(counters), _ptr(stream), st))
+        return stats()
+
+    def irradiance_adaptive(self, points, seeds, min_spp, max_spp, tolerance, floor=0.05, check_every=4, rr=0.8, want_states=False,
+                            counters=False):
+        """irradiance() with a sample count per point: radiance_adaptive()'s stopping rule, unchanged, over the point's
+        samples.  Returns as radiance_adaptive(); a point outside the domain gives NaN, 0, 0 and its seed."""
+        return self._radiance_adaptive(lib().ort_irradiance_adaptive, points, seeds, min_spp, max_spp, tolerance, floor, check_every,
+                                       rr, want_states, counters)
+
+    def irradiance_adaptive_device(self, d_points, d_seeds, n, min_spp, max_spp, tolerance, floor, check_every, rr, d_out, d_spp=0,
+                                   d_m2=0, d_states=0, stream=0, counters=False, want_stats=False):
+        """Device points and seeds -> device colours and, where a pointer is given, samples taken, sums of squared sample
+        luminance and final states: as radiance_adaptive_device()."""
+        st, stats = _stats(want_stats)
+        ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
+        _check(lib().ort_irradiance_adaptive_device(self.handle, _ptr(d_points), _ptr(d_seeds), n, C.byref(ad), float(rr), _ptr(d_out),
+                                                    _ptr(d_spp), _ptr(d_m2), _ptr(d_states), _flags(counters), _ptr(stream), st))
         return stats()
 
     def triangle_of(self, index):

@@ -21,6 +21,8 @@ void ort_launch_radiance_adaptive(int counters, int diffuse, int tabs, unsigned 
 void ort_adaptive_layout(size_t sizes[3]);
 void ort_launch_render_adaptive(int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes); /* ort_kernels_render_adaptive.hip */
 void ort_render_adaptive_layout(size_t sizes[3]);
+void ort_launch_irradiance(int adaptive, int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes); /* ort_kernels_irradiance.hip */
+void ort_irradiance_layout(size_t sizes[3]);
 
 namespace ort {
 
@@ -753,14 +755,19 @@ int device_occluded(Scene *scene, const QueryCall &q, const void *rays, const vo
 /* radiance: count rays with their seeds -> 3 floats each and, where asked for (states may be null), the final states.  No shape
    table: a colour names no shape.  With ad (checked by the caller) the adaptive query: the stopping rule's parameters where spp
    stands, and, where asked for, every ray's sample count and its sum of squared sample luminance; plan_radiance's plan as it
-   is, the kernels ort_kernels_adaptive.hip's */
+   is, the kernels ort_kernels_adaptive.hip's.  With points the irradiance queries: the array holds (p, n) where a ray's (o, d)
+   stand -- the same bytes, staging and view -- and the kernels, plain or adaptive, are ort_kernels_irradiance.hip's */
 int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const void *seeds, uint32_t spp, float rr, const ort_adaptive *ad, void *out,
-                    void *out_spp, void *out_m2, void *states, std::string *err) {
+                    void *out_spp, void *out_m2, void *states, bool points, std::string *err) {
     DeviceScene *d;
     int rc;
     if ((rc = begin_query(scene, q.stats, &d, err))) return rc;
     if (ad && !same_layout(ort_adaptive_layout)) {
         *err = "internal: the adaptive kernels were built with other argument layouts";
+        return ORT_ERR_INTERNAL;
+    }
+    if (points && !same_layout(ort_irradiance_layout)) {
+        *err = "internal: the irradiance kernels were built with other argument layouts";
         return ORT_ERR_INTERNAL;
     }
     hipStream_t stream = (hipStream_t)q.stream;
@@ -771,6 +778,8 @@ int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const vo
         if (ad) radiance_adaptive_view(ray_query_io(scene, d, p[0]), p[1], *ad, rr, p[2], p[3], p[4], p[5], &rv);
         else radiance_view(ray_query_io(scene, d, p[0]), p[1], spp, rr, p[2], p[5], &rv);
         return launch_query(scene, d, rv, n, true, counters, stream, q.stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
+            if (points) ort_launch_irradiance(ad != nullptr, pl.counters, pl.diffuse, pl.tabs, pl.grid, (void *)stream, &sv, &hot);
+            else
             if (ad) ort_launch_radiance_adaptive(pl.counters, pl.diffuse, pl.tabs, pl.grid, (void *)stream, &sv, &hot);
             else with_bools([&](auto C, auto D, auto T) {
                 hipLaunchKernelGGL((radiance_rays<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot);

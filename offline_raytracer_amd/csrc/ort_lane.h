@@ -11,10 +11,11 @@
  * 2-wide tree of ort_tree.cpp with a per-lane stack whose first entries live in LDS
  * (column-per-lane, conflict-free) and whose tail spills to scratch.
  *
- * Included by four translation units: ort_kernels.hip (the library's kernels at four waves per SIMD, and the host side),
+ * Included by five translation units: ort_kernels.hip (the library's kernels at four waves per SIMD, and the host side),
  * ort_kernels_w5.hip (the plain-loop kernels at FIVE: 96 registers, 20 LDS stack entries, built with machine LICM off),
  * ort_kernels_adaptive.hip (the adaptive radiance queries' kernels, at the first unit's limits: a unit of their own so that they
- * compile beside it) and ort_kernels_render_adaptive.hip (the adaptive camera render's, likewise).  Same lane code, other limits
+ * compile beside it), ort_kernels_render_adaptive.hip (the adaptive camera render's, likewise) and ort_kernels_irradiance.hip (the
+ * irradiance queries', likewise).  Same lane code, other limits
  * (ORT_WAVES_PER_EU, ORT_LDS_STACK, ORT_SPILL_STACK); each unit compiles it in a namespace of its own (ORT_NS), so that two builds
  * of one template are two symbols.  tools/host_sim.cpp compiles it for the host (ORT_HOST_SIM: one simulated lane).
  */
@@ -42,6 +43,8 @@
 #define ORT_NS ort_ad
 #elif defined(ORT_RENDER_ADAPTIVE_TU)
 #define ORT_NS ort_ra
+#elif defined(ORT_IRRADIANCE_TU)
+#define ORT_NS ort_ir
 #else
 #define ORT_NS ort
 #endif
@@ -1019,11 +1022,19 @@ ORT_D bool adaptive_stop(V3 C, float Q, uint32_t n, float tolerance, float lum_f
    luminance and the sample count of the next check; the job writes its sample count and that sum besides the mean, which
    divides by the samples taken -- per ray for a query, per pixel of its view's planes for a render, with the stream's state.
    Everything of it sits under if constexpr (ADAPT): the other kernels compile as without it */
-template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool VIEWS = false, bool RAYS = false, bool ADAPT = false>
+/* HEMI: irradiance queries (ort_irradiance, ort_irradiance_adaptive; with RAYS): the caller's array holds points (p, n) where RAYS
+   reads rays (o, d) -- the same 24 bytes, the same domain test, read again for every sample -- and a sample's primary direction is
+   drawn in the lane, on the job's stream: sample_brdf's diffuse draw without the lobe choice (e0, e1; c = sqrt(e0), ray.cpp:1123;
+   phi = 2 pi e1), sample_lobe about n (ray.cpp:1065-1091) and normalize for d.  phi is the angle of the one converged sin/cos below;
+   from d on the sample is RAYS' for the ray (p, d): direction d as it stands, wo = -normalize(d).  Everything of it sits under
+   if constexpr (HEMI) */
+template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool VIEWS = false, bool RAYS = false, bool ADAPT = false,
+          bool HEMI = false>
 ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, Prof &pr,
                        float *focal_cache = nullptr, int focal_stride = 0, uint32_t spp_u = 0, uint32_t *late_flag = nullptr, bool no_new_job = false,
                        unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
     static_assert(!ADAPT || (IMPLICIT && (RAYS || VIEWS)), "the adaptive rule is built for the radiance queries and for one-pixel jobs of a batch of views");
+    static_assert(!HEMI || RAYS, "the hemisphere draw starts a sample of a radiance query's job");
     /* VIEWS: unused; every lane reads its view's camera where it needs it (load_view_camera) */
     const V3 cam_p = mk(sv.cam[0], sv.cam[1], sv.cam[2]);
     const V3 cam_x = mk(sv.cam[3], sv.cam[4], sv.cam[5]);
@@ -1040,7 +1051,8 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
         BrdfDraw draw;
         Mat m;
         V3 n, focal;
-        V3 ray_o = mk(0, 0, 0), ray_d = mk(0, 0, 0); /* RAYS: the sample's ray as the caller gave it */
+        V3 ray_o = mk(0, 0, 0), ray_d = mk(0, 0, 0); /* RAYS: the sample's ray as the caller gave it (HEMI: the point and its normal) */
+        [[maybe_unused]] float hemi_c = 0.0f;        /* HEMI: the drawn direction's cosine to the normal */
         if (P.ps == PS_HIT) {
             /* a traversal has finished: ray.cpp:817 then :1251-1277 (primary) or :1355-1421 (bounce) */
             bool alive = true;
@@ -1267,6 +1279,11 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 const float2 a = r[0], b = r[1], e = r[2];
                 ray_o = mk(a.x, a.y, b.x);
                 ray_d = mk(b.y, e.x, e.y);
+                if constexpr (HEMI) { /* the diffuse lobe's draw (sample_brdf_draw without the choice); its azimuth is the pass's one angle */
+                    const float e0 = rng_01(P.rng), e1 = rng_01(P.rng);
+                    hemi_c = __builtin_sqrtf(e0); /* ray.cpp:1123 */
+                    angle = 2.0f * kPi * e1;
+                }
             } else {
             if constexpr (VIEWS)
                 focal = focal_cache ? mk(focal_cache[0], focal_cache[focal_stride], focal_cache[2 * focal_stride])
@@ -1300,11 +1317,14 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
             bool is_trans = false;
             V3 raw = unit1;
             if (bounce) raw = sample_brdf_finish<false, true>(n, unit1, P.wo, m, draw, cs, sn, is_trans);
+            if constexpr (HEMI) { if (!bounce) raw = sample_lobe_n(unit1, hemi_c, cs, sn); } /* unit1 = normalize(n), as sample_lobe's */
             const V3 unit2 = normalize(raw);
             if (bounce) {
                 if (is_trans) P.org = add(P.org, scale(2.0f * kEps, P.dir)); /* ray.cpp:1345-1348: dir is still the arriving direction */
                 P.dir = unit2;
             } else {
+                if constexpr (HEMI) { P.dir = unit2; P.wo = neg(normalize(unit2)); } /* d; wo = -normalize(d), as RAYS for the ray (p, d) */
+                else
                 if constexpr (RAYS) { P.dir = ray_d; P.wo = neg(unit1); } /* the direction as given; wo = -normalize(d) */
                 else {
                 P.dir = unit1;
@@ -1328,6 +1348,8 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 if constexpr (VIEWS) ap = view_aperture_point(load_view_camera(rv, P.job_index), aperture, cs, sn);
                 else
                 ap = sub(add(add(cam_p, scale(aperture * cs, cam_x)), scale(aperture * sn, cam_y)), scale(0.1f, cam_z));
+                if constexpr (HEMI) raw = sample_lobe_n(normalize(ray_d), hemi_c, cs, sn);
+                else
                 if constexpr (RAYS) raw = ray_d;
                 else
                 raw = sub(focal, ap);
@@ -1337,8 +1359,8 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 if (is_trans) P.org = add(P.org, scale(2.0f * kEps, P.dir)); /* ray.cpp:1345-1348: dir is still the arriving direction */
                 P.dir = unit;
             } else {
-                if constexpr (RAYS) { P.dir = raw; P.wo = neg(unit); } /* the direction as given; wo = -normalize(d) */
-                else {
+                if constexpr (RAYS && !HEMI) { P.dir = raw; P.wo = neg(unit); } /* the direction as given; wo = -normalize(d) */
+                else { /* HEMI: d = unit, and wo = -normalize(d) as RAYS for the ray (p, d) */
                 P.dir = unit;
                 P.wo = neg(normalize(P.dir)); /* normalised again (sic) */
                 }
@@ -2071,6 +2093,15 @@ ORT_D void unit_eval_op(uint32_t op, const float *a, float *o) {
         o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = tr ? 1.0f : 0.0f; o[4] = om_bits_f32(seed);
     } break;
     case 19: { float sn, cs; ort_sincosf(a[0], &sn, &cs); o[0] = sn; o[1] = cs; } break;
+    case 20: { /* produce_ray's hemisphere draw (HEMI): seed(bits) n.xyz -> d, wo = -normalize(d), the stream after the two draws */
+        uint32_t seed = om_f32_bits(a[0]);
+        const float e0 = rng_01(seed), e1 = rng_01(seed);
+        float sn, cs;
+        ort_sincosf(2.0f * kPi * e1, &sn, &cs);
+        const V3 d = normalize(sample_lobe_n(normalize(in3(1)), __builtin_sqrtf(e0), cs, sn));
+        const V3 wo = neg(normalize(d));
+        o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = wo.x; o[4] = wo.y; o[5] = wo.z; o[6] = om_bits_f32(seed);
+    } break;
     default: break;
     }
 }
@@ -2161,7 +2192,7 @@ pt_persistent_x(SceneView sv, RenderHot rv) {
     }
 }
 
-#if !defined(ORT_W5_TU) && !defined(ORT_ADAPTIVE_TU) && !defined(ORT_RENDER_ADAPTIVE_TU) /* the five-waves unit only needs the path-trace kernels, the adaptive ones their own */
+#if !defined(ORT_W5_TU) && !defined(ORT_ADAPTIVE_TU) && !defined(ORT_RENDER_ADAPTIVE_TU) && !defined(ORT_IRRADIANCE_TU) /* the five-waves unit only needs the path-trace kernels, the adaptive and irradiance ones their own */
 /* wavefront kernels: fixed-size grids, grid-stride over the slots */
 template <bool COUNTERS>
 __global__ void __launch_bounds__(kBlock) wf_shade(SceneView sv, RenderHot rv, WfView wf, int count_active) {
@@ -2219,7 +2250,7 @@ __global__ void combine_chunks_views(RenderHot rv) {
     combine_pixel(rv, idx % per_view, (uint32_t)(idx / per_view));
 }
 
-#endif /* !ORT_W5_TU && !ORT_ADAPTIVE_TU && !ORT_RENDER_ADAPTIVE_TU */
+#endif /* !ORT_W5_TU && !ORT_ADAPTIVE_TU && !ORT_RENDER_ADAPTIVE_TU && !ORT_IRRADIANCE_TU */
 #endif /* !ORT_HOST_SIM */
 
 #ifndef ORT_W5_TU
@@ -2440,7 +2471,9 @@ occluded_rays(SceneView sv, RenderHot rv, OccludedIO io) {
  * box with quadrics in it) and then skip the fast traversal: resolve_hit re-casts them exactly.  Bounce rays start at hits and
  * need no rule, as in the render.  No ray exchange, no five-waves build, no wide tree, no wavefront mode (ort_plan.h). */
 /* ADAPT: the adaptive query (ort_radiance_adaptive): the same loop, the job ending where produce_ray's stopping rule says */
-template <bool COUNTERS, bool DIFFUSE, bool TABS, bool ADAPT = false>
+/* HEMI: the irradiance queries (ort_irradiance, ort_irradiance_adaptive): the same loop over points, every sample's primary
+   direction drawn in the lane (produce_ray's HEMI flag); the drawn direction passes raycast_needs_exact like a caller's */
+template <bool COUNTERS, bool DIFFUSE, bool TABS, bool ADAPT = false, bool HEMI = false>
 ORT_D void radiance_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, const int tid, const uint32_t lane_id,
                          unsigned long long *pool) {
     uint32_t spill[kSpillStack];
@@ -2455,9 +2488,9 @@ ORT_D void radiance_lane(const SceneView &sv, const RenderHot &rv, const float4 
     for (;;) {
         if (!tracing) {
             if (P.ps == PS_HIT) resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
-            if constexpr (ADAPT) tracing = produce_ray<COUNTERS, DIFFUSE, TABS, true, false, true, true>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool, &A);
+            if constexpr (ADAPT) tracing = produce_ray<COUNTERS, DIFFUSE, TABS, true, false, true, true, HEMI>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool, &A);
             else
-            tracing = produce_ray<COUNTERS, DIFFUSE, TABS, true, false, true>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool);
+            tracing = produce_ray<COUNTERS, DIFFUSE, TABS, true, false, true, false, HEMI>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool);
             if (tracing) {
                 begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
                 if (P.primary) {
@@ -2499,6 +2532,26 @@ radiance_adaptive_rays(SceneView sv, RenderHot rv) {
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
     radiance_lane<COUNTERS, DIFFUSE, TABS, true>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+}
+
+/* the irradiance queries' sixteen (ort_kernels_irradiance.hip), as radiance_rays and radiance_adaptive_rays: rv.c->rays holds points */
+template <bool COUNTERS, bool DIFFUSE, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+irradiance_points(SceneView sv, RenderHot rv) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    if (TABS) fill_tab(sv, lds_tab);
+    radiance_lane<COUNTERS, DIFFUSE, TABS, false, true>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+}
+template <bool COUNTERS, bool DIFFUSE, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+irradiance_adaptive_points(SceneView sv, RenderHot rv) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    if (TABS) fill_tab(sv, lds_tab);
+    radiance_lane<COUNTERS, DIFFUSE, TABS, true, true>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 #endif
 

@@ -245,9 +245,10 @@ int device_raycast(Scene *scene, const QueryCall &q, const void *rays, void *hit
 int device_occluded(Scene *scene, const QueryCall &q, const void *rays, const void *tmax, void *out, std::string *err);
 /* radiance: count rays and seeds -> colours and, where asked for (null otherwise), final states.  ad == null: exactly spp samples
    per ray; otherwise the adaptive query (spp unread): the stopping rule's parameters, and two more optional outputs (samples
-   taken, sum of squared sample luminance) */
+   taken, sum of squared sample luminance).  points: the irradiance queries -- the array holds count points (p, n) in the rays'
+   place, and every sample's direction is drawn about n */
 int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const void *seeds, uint32_t spp, float rr, const ort_adaptive *ad, void *out,
-                    void *out_spp, void *out_m2, void *states, std::string *err);
+                    void *out_spp, void *out_m2, void *states, bool points, std::string *err);
 /* ort_comm.cpp */
 struct Comm;
 uint64_t comm_shard_blocks(int32_t w, int32_t h, uint32_t index, uint32_t count);

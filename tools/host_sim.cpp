@@ -22,6 +22,9 @@
  *   or: host_sim --occluded scn base rays.f32 tmax.f32|- out.u8
  *   or: host_sim --radiance scn base rays.f32 seeds.u32 spp rr out.f32 states.u32
  *   or: host_sim --radiance-adaptive scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
+ *   or: host_sim --irradiance scn base points.f32 seeds.u32 spp rr out.f32 states.u32            (points: p, n, 6 floats each)
+ *   or: host_sim --irradiance-adaptive scn base points.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
+ *       (the irradiance queries: the two modes above over points, radiance_lane<..., HEMI>)
  *   or: host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32   (cams: p, x, y, z axes, 12 floats a view)
  *       (as on the device, one view is the single-frame lane with that view's camera and seed: the VIEWS lanes run from two views on)
  *   or: host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
@@ -268,6 +271,8 @@ static int occluded_mode(char **a) { /* scn base rays.f32 tmax.f32|- out.u8 */
     return write_bytes(a[4], out.data(), n) ? 0 : 1;
 }
 
+/* HEMI: the irradiance query's lanes (--irradiance): the rays file holds points */
+template <bool HEMI>
 static int radiance_mode(char **a) { /* scn base rays.f32 seeds.u32 spp rr out.f32 states.u32 */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
@@ -289,11 +294,11 @@ static int radiance_mode(char **a) { /* scn base rays.f32 seeds.u32 spp rr out.f
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
         if (diffuse_only) {
-            if (S.tab) radiance_lane<true, true, true>(sv, hot, S.tab, stack, 0, w, nullptr);
-            else radiance_lane<true, true, false>(sv, hot, nullptr, stack, 0, w, nullptr);
+            if (S.tab) radiance_lane<true, true, true, false, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
+            else radiance_lane<true, true, false, false, HEMI>(sv, hot, nullptr, stack, 0, w, nullptr);
         } else {
-            if (S.tab) radiance_lane<true, false, true>(sv, hot, S.tab, stack, 0, w, nullptr);
-            else radiance_lane<true, false, false>(sv, hot, nullptr, stack, 0, w, nullptr);
+            if (S.tab) radiance_lane<true, false, true, false, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
+            else radiance_lane<true, false, false, false, HEMI>(sv, hot, nullptr, stack, 0, w, nullptr);
         }
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
@@ -306,6 +311,7 @@ static float float_arg(const char *s) {
     if (s[0] == '0' && (s[1] == 'x' || s[1] == 'X')) { const uint32_t b = (uint32_t)strtoul(s, 0, 16); float f; memcpy(&f, &b, 4); return f; }
     return (float)atof(s);
 }
+template <bool HEMI> /* as radiance_mode's */
 static int radiance_adaptive_mode(char **a) { /* scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32 */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
@@ -329,11 +335,11 @@ static int radiance_adaptive_mode(char **a) { /* scn base rays.f32 seeds.u32 min
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
         if (diffuse_only) {
-            if (S.tab) radiance_lane<true, true, true, true>(sv, hot, S.tab, stack, 0, w, nullptr);
-            else radiance_lane<true, true, false, true>(sv, hot, nullptr, stack, 0, w, nullptr);
+            if (S.tab) radiance_lane<true, true, true, true, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
+            else radiance_lane<true, true, false, true, HEMI>(sv, hot, nullptr, stack, 0, w, nullptr);
         } else {
-            if (S.tab) radiance_lane<true, false, true, true>(sv, hot, S.tab, stack, 0, w, nullptr);
-            else radiance_lane<true, false, false, true>(sv, hot, nullptr, stack, 0, w, nullptr);
+            if (S.tab) radiance_lane<true, false, true, true, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
+            else radiance_lane<true, false, false, true, HEMI>(sv, hot, nullptr, stack, 0, w, nullptr);
         }
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
@@ -471,8 +477,10 @@ int main(int argc, char **argv) {
     if (argc == 4 && mode == "--unit") return unit_mode(argv[2], argv[3]);
     if (argc == 6 && mode == "--raycast") return raycast_mode(argv + 2);
     if (argc == 7 && mode == "--occluded") return occluded_mode(argv + 2);
-    if (argc == 10 && mode == "--radiance") return radiance_mode(argv + 2);
-    if (argc == 16 && mode == "--radiance-adaptive") return radiance_adaptive_mode(argv + 2);
+    if (argc == 10 && mode == "--radiance") return radiance_mode<false>(argv + 2);
+    if (argc == 16 && mode == "--radiance-adaptive") return radiance_adaptive_mode<false>(argv + 2);
+    if (argc == 10 && mode == "--irradiance") return radiance_mode<true>(argv + 2);
+    if (argc == 16 && mode == "--irradiance-adaptive") return radiance_adaptive_mode<true>(argv + 2);
     if (argc == 12 && mode == "--views") return views_mode(argv + 2);
     if (argc == 21 && mode == "--render-adaptive") return render_adaptive_mode(argv + 2);
     if (argc < 10 || mode.rfind("--", 0) == 0) {
@@ -482,6 +490,8 @@ int main(int argc, char **argv) {
                         "       host_sim --occluded scn base rays.f32 tmax.f32|- out.u8\n"
                         "       host_sim --radiance scn base rays.f32 seeds.u32 spp rr out.f32 states.u32\n"
                         "       host_sim --radiance-adaptive scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
+                        "       host_sim --irradiance scn base points.f32 seeds.u32 spp rr out.f32 states.u32\n"
+                        "       host_sim --irradiance-adaptive scn base points.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
                         "       host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32\n"
                         "       host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n");
         return 2;
