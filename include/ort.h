@@ -480,6 +480,53 @@ int ort_irradiance_adaptive_device(ort_scene *scene, const void *d_points, const
                                    void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, uint32_t flags, void *hip_stream,
                                    ort_stats *stats);
 
+/* ---- ambient-occlusion queries: hemisphere visibility gathers at points ------------------------
+ * The visibility gather of a baker's texel or probe: ambient occlusion, a bent normal, "how much sky does this point see within
+ * r".  ort_irradiance's points, seeds and direction draw; ort_occluded's answer along every drawn direction.
+ *  - Inputs.  points is ort_irradiance's array: count x {p.xyz, n.xyz} f32, 24 B each, 8-byte aligned.  seeds is count x u32.  The
+ *    per-point domain and the treatment of p are ort_irradiance's: six finite components, |n|^2 (f32: x*x + y*y + z*z) within
+ *    [0.999, 1.001], p used as given (a caller lifts it off its surface first).
+ *  - The radius.  radius is count x f32, 4-byte aligned, in units of the ray parameter; directions are unit vectors, so it is a
+ *    distance.  It is ort_occluded's tmax, with that call's IEEE rules.  radius == NULL means no limit.  A NaN or <= 0 radius
+ *    (-0.0 and -inf included) leaves every sample of that point open.
+ *  - One sample.  A point's samples run on ONE xorshift stream that starts at seeds[i] (0 is taken as 1).  Sample k is
+ *    ort_irradiance's direction draw, every operation a separately rounded f32 operation (no FMA):
+ *        e0  = rng_01(s);  e1 = rng_01(s)
+ *        c   = sqrtf(e0)
+ *        phi = (2.0f * kPi) * e1
+ *        m   = sample_lobe(n, c, phi)
+ *        d_k = normalize(m)
+ *    and then o_k, the byte ort_occluded returns for the ray (p, d_k) with tmax = radius[i]: (h.mat != 0 && h.t < radius[i]) of the
+ *    reference's closest hit h.  Nothing else is drawn: the stream advances exactly two steps per sample, whatever is hit.
+ *  - Outputs.  out_open[i] is the number of samples with o_k == 0: visibility is out_open / spp, ambient occlusion one minus that;
+ *    the count is returned so that no rounding is added.  out_bent (may be NULL) is count x 3 f32: B starts at (+0, +0, +0) and,
+ *    for every open sample in sample order, B = B + d_k component by component, each a separately rounded f32 add; B is returned as
+ *    it stands -- the caller normalises it, and |B| / out_open measures the open cone.  final_states[i] (may be NULL) is the stream
+ *    after 2 * spp steps.
+ *  - Outside the domain.  Such a point gets out_open[i] = ORT_AO_INVALID, out_bent = NaN NaN NaN and final_states[i] = seeds[i] (as
+ *    given, 0 included), is not traced, and leaves its neighbours alone.
+ *  - Identities.  Sample k's bit is ort_occluded's for (p, d_k) at that radius; d_k is unit op 20's direction for the stream's
+ *    state before the sample; final_states does not depend on the scene; results do not depend on count, order, how the batch is
+ *    sliced or how points fall on the GPU's lanes.
+ *  - Flags and statistics as for ort_occluded.  With ORT_RENDER_COUNTERS, rays = (points inside the domain) * spp -- a sample is
+ *    counted before its radius is looked at --, paths = 0; fallback_rays and kernel_ms are always filled.  A sample that
+ *    ort_occluded would send to the exact octree walk takes it here too: every sample of a point outside the scene's box with
+ *    quadrics in the tree, a +-0 component of d_k with boxes in it.
+ *  - Errors.  count == 0 returns ORT_OK without a launch, whatever the other arguments.  Otherwise errors are reported before any
+ *    device work, in this order: ORT_ERR_INVALID (null scene, points, seeds or out_open; misaligned points (8 bytes) or any other
+ *    array (4 bytes); spp == 0), ORT_ERR_STATE (scene not committed), ORT_ERR_NO_DEVICE (not uploaded). */
+#define ORT_AO_INVALID 0xffffffffu
+
+/* host arrays in, host counts (and bent sums, states) out; synchronous, staged as ort_radiance */
+int ort_ambient_occlusion(ort_scene *scene, const float *points, const uint32_t *seeds, const float *radius /* may be NULL */,
+                          uint64_t count, uint32_t spp, uint32_t *out_open, float *out_bent /* may be NULL */,
+                          uint32_t *final_states /* may be NULL */, uint32_t flags, ort_stats *stats);
+/* DEVICE pointers on the scene's device; enqueued on hip_stream (NULL = the default stream), returns without waiting unless
+   stats != NULL -- as ort_occluded_device */
+int ort_ambient_occlusion_device(ort_scene *scene, const void *d_points, const void *d_seeds, const void *d_radius, uint64_t count,
+                                 uint32_t spp, void *d_out_open, void *d_out_bent, void *d_final_states, uint32_t flags,
+                                 void *hip_stream, ort_stats *stats);
+
 /* ---- the adaptive camera render: one frame, or a batch of views ---------------------------------
  * The camera render with a sample count per pixel: "this noise level, at most max_spp samples", and a sample-count map back.
  * A pixel job under ORT_POLICY_PIXEL is all samples of pixel (x, y) on the stream job_seed(seed, y*W + x); the adaptive render is

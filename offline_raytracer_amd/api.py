@@ -23,6 +23,7 @@ RENDER_PACKED = 2
 COMM_ID_BYTES = 128
 HIT_TRIANGLE, HIT_BOX, HIT_CYLINDER, HIT_SPHERE = 0, 2, 3, 4
 NO_PRIM = 0xFFFFFFFF
+AO_INVALID = 0xFFFFFFFF  # ORT_AO_INVALID: ambient_occlusion()'s open count of a point outside the domain
 MAX_VIEWS = 4096  # ORT_MAX_VIEWS
 
 
@@ -136,7 +137,8 @@ EXPORTS = [
     "ort_shard_block_count", "ort_pack_blocks_host", "ort_unpack_blocks_host", "ort_unpack_blocks_device",
     "ort_comm_unique_id", "ort_comm_create", "ort_comm_create_local", "ort_comm_destroy", "ort_gather_framebuffer",
     "ort_gather_framebuffer_local", "ort_raycast", "ort_raycast_device",
-    "ort_occluded", "ort_occluded_device", "ort_radiance", "ort_radiance_device",
+    "ort_occluded", "ort_occluded_device", "ort_ambient_occlusion", "ort_ambient_occlusion_device",
+    "ort_radiance", "ort_radiance_device",
     "ort_radiance_adaptive", "ort_radiance_adaptive_device",
     "ort_irradiance", "ort_irradiance_device", "ort_irradiance_adaptive", "ort_irradiance_adaptive_device",
     "ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes",
@@ -209,6 +211,7 @@ def lib():
                 ("ort_render_views_adaptive", [vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, C.c_uint32, vp, vp, vp, vp, stats]),
                 ("ort_raycast", [vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
                 ("ort_occluded", [vp, vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
+                ("ort_ambient_occlusion", [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint32, stats]),
                 ("ort_radiance", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_float, vp, vp, C.c_uint32, stats]),
                 ("ort_radiance_adaptive", [vp, vp, vp, C.c_uint64, C.POINTER(Adaptive), C.c_float, vp, vp, vp, vp, C.c_uint32, stats]),
                 ("ort_irradiance", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_float, vp, vp, C.c_uint32, stats]),
@@ -690,6 +693,45 @@ class Scene:
         ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
         _check(lib().ort_irradiance_adaptive_device(self.handle, _ptr(d_points), _ptr(d_seeds), n, C.byref(ad), float(rr), _ptr(d_out),
                                                     _ptr(d_spp), _ptr(d_m2), _ptr(d_states), _flags(counters), _ptr(stream), st))
+        return stats()
+
+    # -- ambient-occlusion queries: hemisphere visibility gathers at points ------------------------
+    def ambient_occlusion(self, points, seeds, spp, radius=None, want_bent=False, want_states=False, counters=False):
+        """How much of the hemisphere about its normal each point sees within radius: spp samples, each irradiance()'s
+        direction draw about n on the xorshift stream that starts at seeds[i] (0 is taken as 1) and then occluded()'s answer
+        for the ray (p, d) with tmax = radius[i].  points: (N, 6) float32 p.xyz n.xyz as for irradiance(); radius: None (no
+        limit), a scalar (broadcast) or an (N,) array, a distance; NaN or <= 0 leaves every sample open.  open[i] counts the
+        samples with nothing in the way: visibility is open / spp, ambient occlusion one minus that.  bent[i] is the float32
+        sum of the open samples' directions, in sample order, not normalised.  A point outside the domain gives AO_INVALID,
+        NaN NaN NaN and its seed back.  Returns (open: uint32[N], [bent: float32[N, 3] if want_bent], [states: uint32[N] if
+        want_states], stats dict); synchronous."""
+        points = _rays(points)
+        seeds = _seeds(seeds, len(points))
+        if radius is not None:
+            radius = np.asarray(radius, dtype="<f4")
+            if radius.ndim == 0:
+                radius = np.full(len(points), radius, dtype="<f4")
+            if radius.shape != (len(points),):
+                raise ValueError("radius must be a scalar or an (N,) array with N = %d, got shape %s" % (len(points), radius.shape))
+            radius = np.ascontiguousarray(radius)
+        out = np.zeros(len(points), "<u4")
+        bent = np.zeros((len(points), 3), "<f4") if want_bent else None
+        states = np.zeros(len(points), "<u4") if want_states else None
+        st, stats = _stats()
+        _check(lib().ort_ambient_occlusion(self.handle, points.ctypes.data, seeds.ctypes.data,
+                                           radius.ctypes.data if radius is not None else None, len(points), int(spp), out.ctypes.data,
+                                           bent.ctypes.data if want_bent else None, states.ctypes.data if want_states else None,
+                                           _flags(counters), st))
+        return (out,) + ((bent,) if want_bent else ()) + ((states,) if want_states else ()) + (stats(),)
+
+    def ambient_occlusion_device(self, d_points, d_seeds, d_radius, n, spp, d_open, d_bent=0, d_states=0, stream=0, counters=False,
+                                 want_stats=False):
+        """Device points (n x 6 float32), seeds (n uint32) and radii (n float32, or None: no limit) -> device open counts (n
+        uint32) and, where a pointer is given, bent sums (n x 3 float32) and final states (n uint32): raw pointers on the
+        scene's device.  Enqueued on stream; waits only when want_stats (returns the stats dict)."""
+        st, stats = _stats(want_stats)
+        _check(lib().ort_ambient_occlusion_device(self.handle, _ptr(d_points), _ptr(d_seeds), _ptr(d_radius), n, int(spp), _ptr(d_open),
+                                                  _ptr(d_bent), _ptr(d_states), _flags(counters), _ptr(stream), st))
         return stats()
 
     def triangle_of(self, index):

@@ -431,6 +431,21 @@ static int occluded_common(ort_scene *s, const ort::QueryCall &q, const void *ra
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
+/* ambient-occlusion queries: count == 0 is OK whatever else is passed; then argument errors, then state errors */
+static int ao_common(ort_scene *s, const ort::QueryCall &q, const void *points, const void *seeds, const void *radius, uint32_t spp, void *out_open,
+                     void *out_bent, void *final_states) {
+    if (q.count == 0) return nothing_to_do(q.stats);
+    if (!s) return fail(ORT_ERR_INVALID, "null scene");
+    int rc = check_ptrs({{points, true, 8}, {seeds, true, 4}, {radius, false, 4}, {out_open, true, 4}, {out_bent, false, 4}, {final_states, false, 4}},
+                        "null points, seeds or out_open", "points must be 8-byte aligned", "seeds, radius, out_open, out_bent and final_states must be 4-byte aligned");
+    if (rc != ORT_OK) return rc;
+    if (spp == 0) return fail(ORT_ERR_INVALID, "spp must be >= 1");
+    if ((rc = check_resident(s)) != ORT_OK) return rc;
+    std::string err;
+    rc = ort::device_ambient_occlusion(s, q, points, seeds, radius, spp, out_open, out_bent, final_states, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
 /* the stopping rule's parameters by themselves */
 static int check_adaptive(const ort_adaptive *ad) {
     if (!ad) return fail(ORT_ERR_INVALID, "null ad (the adaptive parameters)");
@@ -651,6 +666,8 @@ int ort_raycast(ort_scene *s, const float *rays, uint64_t count, ort_hit *hits, 
 int ort_raycast_device(ort_scene *s, const void *d_rays, uint64_t count, void *d_hits, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return raycast_common(s, {false, count, flags, hip_stream, stats}, d_rays, d_hits); }); }
 int ort_occluded(ort_scene *s, const float *rays, const float *tmax, uint64_t count, uint8_t *occluded, uint32_t flags, ort_stats *stats) { return guarded([&]() { return occluded_common(s, {true, count, flags, nullptr, stats}, rays, tmax, occluded); }); }
 int ort_occluded_device(ort_scene *s, const void *d_rays, const void *d_tmax, uint64_t count, void *d_occluded, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return occluded_common(s, {false, count, flags, hip_stream, stats}, d_rays, d_tmax, d_occluded); }); }
+int ort_ambient_occlusion(ort_scene *s, const float *points, const uint32_t *seeds, const float *radius, uint64_t count, uint32_t spp, uint32_t *out_open, float *out_bent, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return ao_common(s, {true, count, flags, nullptr, stats}, points, seeds, radius, spp, out_open, out_bent, final_states); }); }
+int ort_ambient_occlusion_device(ort_scene *s, const void *d_points, const void *d_seeds, const void *d_radius, uint64_t count, uint32_t spp, void *d_out_open, void *d_out_bent, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return ao_common(s, {false, count, flags, hip_stream, stats}, d_points, d_seeds, d_radius, spp, d_out_open, d_out_bent, d_final_states); }); }
 int ort_radiance(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr, float *out_rgb, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {true, count, flags, nullptr, stats}, rays, seeds, spp, rr, false, nullptr, out_rgb, nullptr, nullptr, final_states); }); }
 int ort_radiance_device(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {false, count, flags, hip_stream, stats}, d_rays, d_seeds, spp, rr, false, nullptr, d_out_rgb, nullptr, nullptr, d_final_states); }); }
 int ort_radiance_adaptive(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, const ort_adaptive *ad, float rr, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {true, count, flags, nullptr, stats}, rays, seeds, 0, rr, true, ad, out_rgb, out_spp, out_m2, final_states); }); }

@@ -592,7 +592,7 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     return ORT_OK;
 }
 
-/* ---- the ray queries (ort_raycast*, ort_occluded*, ort_radiance*) -------------------------------------------------------- */
+/* ---- the ray queries (ort_raycast*, ort_occluded*, ort_ambient_occlusion*, ort_radiance*) -------------------------------------------------------- */
 /* What is launched, on which grid and with which thresholds is plan_ray_query's and plan_radiance's decision (ort_plan.h); this
    is the plumbing around them: one launch path (launch_query) and one host-form loop (run_sliced) for the three */
 constexpr uint64_t kRaycastSlice = 1ull << 22;  /* rays per launch of the host form of ort_raycast and ort_occluded (2 x 96 MB of staging) */
@@ -747,6 +747,36 @@ int device_occluded(Scene *scene, const QueryCall &q, const void *rays, const vo
         return launch_query(scene, d, RenderView{}, n, false, counters, stream, q.stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
             with_bools([&](auto C, auto T) {
                 hipLaunchKernelGGL((occluded_rays<decltype(C)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot, io);
+            }, pl.counters, pl.tabs);
+        });
+    });
+}
+
+/* ambient occlusion: count points with their seeds and radii (may be null) -> an open count each and, where asked for, the bent
+   sums and the final states.  The six arrays fill the six staging buffers; a point is spp rays, so the host form's slice is the
+   radiance queries'.  plan_ray_query over the points, as it stands: untuned for this job space (a job is spp traversals and
+   draws, not one) -- no constant departs from it, so none needs a measurement of its own */
+int device_ambient_occlusion(Scene *scene, const QueryCall &q, const void *points, const void *seeds, const void *radius, uint32_t spp, void *out_open,
+                             void *out_bent, void *states, std::string *err) {
+    DeviceScene *d;
+    int rc;
+    if ((rc = begin_query(scene, q.stats, &d, err))) return rc;
+    hipStream_t stream = (hipStream_t)q.stream;
+    const bool counters = (q.flags & ORT_RENDER_COUNTERS) != 0;
+    const QueryArray arrays[] = {{points, 24u, false}, {seeds, 4u, false}, {radius, sizeof(float), false}, {out_open, 4u, true}, {out_bent, 12u, true}, {states, 4u, true}};
+    return run_query(d, q, kRadianceSlice, arrays, err, [&](void *const *p, uint64_t n) {
+        AoIO io{};
+        io.q = ray_query_io(scene, d, p[0]);
+        io.seeds = (const uint32_t *)p[1];
+        io.radius = (const float *)p[2];
+        io.open = (uint32_t *)p[3];
+        io.bent = (float *)p[4];
+        io.states = (uint32_t *)p[5];
+        io.spp = spp;
+        io.mats_nonzero = all_mats_nonzero(scene->tree);
+        return launch_query(scene, d, RenderView{}, n, false, counters, stream, q.stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
+            with_bools([&](auto C, auto T) {
+                hipLaunchKernelGGL((ao_points<decltype(C)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot, io);
             }, pl.counters, pl.tabs);
         });
     });

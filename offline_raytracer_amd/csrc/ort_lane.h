@@ -2463,6 +2463,169 @@ occluded_rays(SceneView sv, RenderHot rv, OccludedIO io) {
 }
 #endif
 
+/* ---- ambient-occlusion queries (ort_ambient_occlusion): hemisphere visibility gathers at points --------------------------
+ * A job is a point (p, n) with a seed and a radius; its spp samples run on one xorshift stream.  A sample is unit op 20's
+ * direction draw about n (two rng_01, sqrt, the deterministic sin/cos, sample_lobe_n about normalize(n), normalize) and then
+ * occluded_lane's ray (p, d) at tmax = radius: the bound, the prologue, raycast_needs_exact on (p, d), the early end on the
+ * prologue's winner, the bounded walk, resolve_hit with the bound for a runner-up and the same comparison.  The lane keeps
+ * the point, normalize(n), the stream, the sample count, the open count, the bent sum and the bound across samples, and
+ * writes 4 to 20 bytes per point at the job's end.  A point outside the domain (produce_ray's RAYS test, on n for d) is
+ * answered where it is drawn: ORT_AO_INVALID, NaN, its seed as given.
+ * WHERE A SAMPLE STARTS.  occluded_lane fetches a ray wherever a lane is idle; here that place holds the binary64 sin/cos.  So
+ * the idle lanes first settle what needs no arithmetic -- the finished sample's verdict, the job's end, the next point (a
+ * loop: an invalid point takes another) -- and then meet at ONE draw, produce_ray's structure: one converged ort_sincosf per
+ * pass of the outer loop for every lane that starts a sample, whether the point's first or a later one.
+ * A radius that is NaN or <= 0 (bound 0) traverses nothing -- nothing is hit below 1e-6 -- but still draws, counts a ray and
+ * adds d to the bent sum.  The stream advances exactly two steps per sample, whatever is hit.
+ * WHERE THE JOB'S STATE LIVES.  With all of it in registers the kernels spill 8 to 34 VGPRs where occluded_rays spills none
+ * (profiles/r14_ao.md).  What is touched once per sample and never inside the walk -- the bent sum and normalize(n) -- sits in
+ * six per-lane LDS words instead (job_cache: word k of a lane at job_cache[k * kBlock], conflict-free), as pt_adaptive keeps its
+ * AdaptState: 6 KB per block, which leaves four blocks per CU.
+ * WHAT THE RADIUS SAVES PER POINT.  The bound is the job's, not the ray's, and every direction has unit length: when p lies
+ * farther than the bound from both child boxes of the fast tree's root, no sample of the point can hit anything of the tree
+ * below the bound, and none visits it (T.cur = kTraversalDone after the prologue; resolve_hit sees a walk that found nothing,
+ * with the bound for a runner-up as ever).  One distance test of the root's record per point -- counted as its two box tests --
+ * instead of a root visit per sample.  Not with spheres in the tree: a sphere's tangent branch reports hits outside its box and
+ * nearer than the box's entry (ort_scene.h), so there every sample walks.  The distance is compared with 0.2 % to spare, far
+ * more than the rounding of |d_k| and of a hit's distance. */
+ORT_D bool ao_box_within(float4 lo_xyz_hi_x, float hi_y, float hi_z, V3 p, float bound) {
+    const float dx = fmaxf(fmaxf(lo_xyz_hi_x.x - p.x, p.x - lo_xyz_hi_x.w), 0.0f);
+    const float dy = fmaxf(fmaxf(lo_xyz_hi_x.y - p.y, p.y - hi_y), 0.0f);
+    const float dz = fmaxf(fmaxf(lo_xyz_hi_x.z - p.z, p.z - hi_z), 0.0f);
+    return !(((dx * dx + dy * dy) + dz * dz) * 0.998f > bound * bound); /* NaN or overflow: within */
+}
+constexpr int kAoCacheWords = 6; /* bent.xyz, normalize(n).xyz */
+struct AoIO {
+    RaycastIO q;            /* q.rays: the points (p, n); and what raycast_needs_exact reads.  hits and prim_src are null */
+    const uint32_t *seeds;  /* count stream seeds (0 is taken as 1) */
+    const float *radius;    /* count limits, or null: none */
+    uint32_t *open;         /* count: samples with nothing in the way, or ORT_AO_INVALID */
+    float *bent;            /* count x 3, or null: the sum of the open samples' directions, in sample order */
+    uint32_t *states;       /* count, or null: the stream after 2 * spp steps */
+    uint32_t spp;           /* >= 1 */
+    uint32_t mats_nonzero;  /* no shape of the scene carries material 0 (the early end, as occluded_lane's) */
+};
+
+template <bool COUNTERS, bool TABS>
+ORT_D void ao_lane(const SceneView &sv, const RenderHot &rv, const AoIO &io, const float4 *tab, uint32_t *lds_stack, float *job_cache, const int tid,
+                   const uint32_t lane_id, unsigned long long *pool) {
+    uint32_t spill[kSpillStack];
+    HitState h;
+    Trav T;
+    Counters c;
+    Prof pr;
+    unsigned long long point = 0;
+    V3 org = mk(0, 0, 0), dir = mk(0, 0, 0);
+    float *const bent = job_cache, *const unit_n = job_cache + 3 * kBlock; /* per-lane words, stride kBlock */
+    uint32_t rng = 1u, sample = 0, open = 0; /* sample: the samples of this point started so far */
+    float bound = 0.0f;
+    bool tracing = false, held = false, busy = false, more = true; /* held: as occluded_lane's; busy: this lane owns a point */
+    bool reach = true; /* something of the fast tree may lie within the bound of this point */
+    for (;;) {
+        if (!tracing) {
+            if (held) { /* the finished sample's verdict */
+                h.runner_t = fminf(h.runner_t, bound); /* the bound is a runner-up the walk may not have seen */
+                resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, org, dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+                if (!(h.hit_mat != 0u && h.best_t < bound)) { open++; bent[0] = bent[0] + dir.x; bent[kBlock] = bent[kBlock] + dir.y; bent[2 * kBlock] = bent[2 * kBlock] + dir.z; }
+                held = false;
+            }
+            bool start = false;
+            for (;;) { /* the job's end and the next point */
+                if (busy) {
+                    if (sample < io.spp) { start = true; break; }
+                    io.open[point] = open;
+                    if (io.bent) { float *b = io.bent + 3ull * point; b[0] = bent[0]; b[1] = bent[kBlock]; b[2] = bent[2 * kBlock]; }
+                    if (io.states) io.states[point] = rng;
+                    busy = false;
+                }
+                if (!more) break;
+                const unsigned long long j = pool ? draw_job(rv, pool) : ORT_NEXT_JOB(rv.c->next_job);
+                if (!(j < rv.c->job_count)) { more = false; break; }
+                const float2 *r = io.q.rays + 3ull * j;
+                const float2 a = r[0], b = r[1], e = r[2];
+                const uint32_t seed = io.seeds[j];
+                const V3 p = mk(a.x, a.y, b.x), n = mk(b.y, e.x, e.y);
+                const float l2 = len2(n);
+                if (!(all_finite6(p, n) && l2 >= 0.999f && l2 <= 1.001f)) { /* the per-point domain (include/ort.h) */
+                    io.open[j] = 0xffffffffu;
+                    if (io.bent) { float *o = io.bent + 3ull * j; o[0] = o[1] = o[2] = om_bits_f32(0x7fc00000u); }
+                    if (io.states) io.states[j] = seed;
+                    continue;
+                }
+                const float tm = io.radius ? io.radius[j] : __builtin_inff();
+                bound = (tm > 0.0f) ? fminf(tm, 3.402823466e+38f) : 0.0f;
+                reach = true;
+                if (io.radius && bound > 0.0f && bound < 3.402823466e+38f && !io.q.tree_spheres) {
+                    /* the root's record as traverse reads it: child 0 lo = a.xyz, hi = (a.w, b.x, b.y); child 1 lo = (b.z, b.w, cc.x), hi = cc.yzw */
+                    const float4 *np = TABS ? tab + kTabTreelet : sv.nodes;
+                    const float4 ra = np[0], rb = np[1], rc = np[2], rd = np[3];
+                    const bool in0 = om_f32_bits(rd.x) != EMPTY_CHILD && ao_box_within(ra, rb.x, rb.y, p, bound);
+                    const bool in1 = om_f32_bits(rd.y) != EMPTY_CHILD && ao_box_within(make_float4(rb.z, rb.w, rc.x, rc.y), rc.z, rc.w, p, bound);
+                    reach = in0 || in1;
+                    if (COUNTERS) c.nodes += 2;
+                }
+                point = j;
+                org = p;
+                const V3 un = normalize(n);
+                unit_n[0] = un.x; unit_n[kBlock] = un.y; unit_n[2 * kBlock] = un.z;
+                rng = seed ? seed : 1u; /* as job_seed: a zero xorshift state never leaves zero */
+                bent[0] = bent[kBlock] = bent[2 * kBlock] = 0.0f;
+                sample = 0; open = 0;
+                busy = true;
+            }
+            if (start) { /* the draw, as unit op 20 composes it: one converged sin/cos for the lanes that start a sample */
+                const float e0 = rng_01(rng), e1 = rng_01(rng);
+                float sn, cs;
+                ort_sincosf(2.0f * kPi * e1, &sn, &cs);
+                dir = normalize(sample_lobe_n(mk(unit_n[0], unit_n[kBlock], unit_n[2 * kBlock]), __builtin_sqrtf(e0), cs, sn));
+                sample++;
+                if (COUNTERS) c.rays++;
+                if (!(bound > 0.0f)) { /* nothing is hit below 1e-6 */
+                    open++; bent[0] = bent[0] + dir.x; bent[kBlock] = bent[kBlock] + dir.y; bent[2 * kBlock] = bent[2 * kBlock] + dir.z;
+                } else {
+                    const bool forced = sv.force_fallback_mask != 0xffffffffu && (om_f32_bits(dir.x) & sv.force_fallback_mask) == 0u;
+                    T.cur = 0;
+                    T.sp = 0;
+                    T.inv_d = mk(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z); /* as begin_ray, with the bound for Flt_Max */
+                    reset_hit(h, bound);
+                    prologue_tests<COUNTERS, TABS>(sv, tab, org, dir, T.inv_d, h, c);
+                    bool seen = false; /* the prologue's winner is one the reference is certain to test */
+                    if (ORT_RARE(forced || raycast_needs_exact(io.q, org, dir, T.inv_d))) {
+                        T.cur = kTraversalDone; /* no fast traversal: resolve_hit re-casts it exactly (a phantom that could win) */
+                        h.phantom_t = 0.0f;
+                    } else if (io.mats_nonzero && h.hit_prim != kNoPrim) {
+                        const uint32_t word = sv.prim_info[info_index(sv, h.hit_prim)].chain;
+                        const uint32_t first = word & 0x07ffffffu;
+                        seen = (word >> 28) == 0u;
+                        if (!seen && (word & kChainNested)) seen = in_rect_half_open(sv.chain_boxes[2u * first], sv.chain_boxes[2u * first + 1u], org);
+                    }
+                    if (!seen) {
+                        if (!reach) T.cur = kTraversalDone; /* nothing of the tree below the bound: no walk, resolve_hit as after one */
+                        tracing = held = true;
+                    } /* seen: occluded, nothing to add */
+                }
+            }
+        }
+        /* a lane that neither traces, owns a point nor is entitled to another draw has none and will get none */
+        if (ORT_BALLOT(tracing || busy || more) == 0ull) break;
+        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS, true>(sv, org, dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+    }
+    flush_counters(rv, c, COUNTERS);
+}
+
+#ifndef ORT_HOST_SIM
+template <bool COUNTERS, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+ao_points(SceneView sv, RenderHot rv, AoIO io) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    __shared__ float lds_job[kAoCacheWords * kBlock]; /* the job's state that is touched once per sample (ao_lane) */
+    if (TABS) fill_tab(sv, lds_tab);
+    ao_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, lds_job + threadIdx.x, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+}
+#endif
+
 /* ---- radiance queries (ort_radiance): the path-traced light that arrives along a caller's ray ---------------------------
  * The plain path-trace loop (pt_lane) with the ray array for a job space (produce_ray's RAYS flag): a lane draws a ray index from
  * its wave's batch, runs spp samples of the reference's sample body (ray.cpp:1247-1426) from that ray on one xorshift stream,

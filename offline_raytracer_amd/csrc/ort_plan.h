@@ -465,7 +465,9 @@ inline unsigned int query_grid(const SceneTraits &t, uint64_t count) {
    - descend_below is 8 or 16 by the 16 MB line, as the renders': ORT_DESCEND_BELOW is not read, and neither is
      ORT_CACHE_RESIDENT;
    - tabs is the prologue's table alone (TAB_PRO: these lanes read neither materials nor lights), whatever ORT_LDS_TABLES says;
-   - there is one BSDF-free flavour: diffuse stays false. */
+   - there is one BSDF-free flavour: diffuse stays false.
+   ort_ambient_occlusion (ao_points) launches by this plan too, over count points: a job there is spp draws and bounded walks, not
+   one ray, and nothing of the plan has been tuned for that. */
 inline QueryPlan plan_ray_query(const SceneTraits &t, uint64_t count, bool counters) {
     QueryPlan pl;
     pl.counters = counters;

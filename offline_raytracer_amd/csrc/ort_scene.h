@@ -243,6 +243,10 @@ struct QueryCall {
 int device_raycast(Scene *scene, const QueryCall &q, const void *rays, void *hits, std::string *err);
 /* occlusion: count rays and their limits (tmax may be null: no limit) -> count bytes */
 int device_occluded(Scene *scene, const QueryCall &q, const void *rays, const void *tmax, void *out, std::string *err);
+/* ambient occlusion: count points (p, n), seeds and radii (radius may be null: no limit), spp samples each -> count open counts
+   and, where asked for (null otherwise), bent sums (3 floats a point) and final states */
+int device_ambient_occlusion(Scene *scene, const QueryCall &q, const void *points, const void *seeds, const void *radius, uint32_t spp, void *out_open,
+                             void *out_bent, void *states, std::string *err);
 /* radiance: count rays and seeds -> colours and, where asked for (null otherwise), final states.  ad == null: exactly spp samples
    per ray; otherwise the adaptive query (spp unread): the stopping rule's parameters, and two more optional outputs (samples
    taken, sum of squared sample luminance).  points: the irradiance queries -- the array holds count points (p, n) in the rays'

@@ -11,7 +11,7 @@
  * kernel.  The library never loads, links or runs it: the render call has no CPU fallback
  * (tests/test_host.py holds its image against the oracle; nothing else uses it).
  *
- * The ray-query lanes (raycast_lane, occluded_lane, radiance_lane with and without its adaptive rule), the batch-of-views flavour of pt_lane and its adaptive one run here too, on
+ * The ray-query lanes (raycast_lane, occluded_lane, ao_lane, radiance_lane with and without its adaptive rule), the batch-of-views flavour of pt_lane and its adaptive one run here too, on
  * the tables the product's own host code packs, and the camera modes on the launch plan and RenderView fill of the product's own render call (ort_plan.h, ort_setup.h): tests/test_query_lanes_host.py holds them against the
  * reference's answers and the oracle, tests/test_host_sanitizers.py runs the same binary built with ASan + UBSan
  * (make host_sim_san).
@@ -20,6 +20,7 @@
  *   or: host_sim --unit records.bin out.f32   (ort_unit_eval_device on the host)
  *   or: host_sim --raycast scn base rays.f32 hits.bin                        (ort_hit records)
  *   or: host_sim --occluded scn base rays.f32 tmax.f32|- out.u8
+ *   or: host_sim --ambient-occlusion scn base points.f32 seeds.u32 radius.f32|- spp open.u32 bent.f32|- states.u32|-   (ao_lane)
  *   or: host_sim --radiance scn base rays.f32 seeds.u32 spp rr out.f32 states.u32
  *   or: host_sim --radiance-adaptive scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
  *   or: host_sim --irradiance scn base points.f32 seeds.u32 spp rr out.f32 states.u32            (points: p, n, 6 floats each)
@@ -271,6 +272,46 @@ static int occluded_mode(char **a) { /* scn base rays.f32 tmax.f32|- out.u8 */
     return write_bytes(a[4], out.data(), n) ? 0 : 1;
 }
 
+/* the ambient-occlusion query's lanes (ao_lane); an output given as - is an optional array the caller did not pass */
+static int ao_mode(char **a) { /* scn base points.f32 seeds.u32 radius.f32|- spp open.u32 bent.f32|- states.u32|- */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO)) return rc;
+    size_t n = 0;
+    std::vector<float2> points;
+    std::vector<uint32_t> seeds;
+    if (!read_rays(a[2], points, &n) || !read_array(a[3], seeds, n, "seeds")) return 1;
+    std::vector<float> radius;
+    const bool limits = std::string(a[4]) != "-", want_bent = std::string(a[7]) != "-", want_states = std::string(a[8]) != "-";
+    if (limits && !read_array(a[4], radius, n, "radii")) return 1;
+    const uint32_t spp = (uint32_t)strtoul(a[5], 0, 10);
+    if (spp == 0u) { fprintf(stderr, "spp must be >= 1\n"); return 1; }
+    std::vector<uint32_t> open(n, 0xeeeeeeeeu), states(want_states ? n : 0, 0xddddddddu); /* every word is written: one that is not keeps its filler */
+    std::vector<float> bent(want_bent ? 3 * n : 0, -7.0f);
+    float lo[3], hi[3];
+    scene_origin_box(*S.scene, lo, hi);
+    AoIO io{};
+    ray_query_io(*S.scene, lo, hi, &io.q);
+    io.q.rays = points.data();
+    io.seeds = seeds.data();
+    io.radius = limits ? radius.data() : nullptr;
+    io.open = open.data();
+    io.bent = want_bent ? bent.data() : nullptr;
+    io.states = want_states ? states.data() : nullptr;
+    io.spp = spp;
+    io.mats_nonzero = all_mats_nonzero(S.scene->tree);
+    RenderView rv{};
+    const RenderHot hot = query_hot(S, rv, n);
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
+        std::vector<float> job((kAoCacheWords - 1) * kBlock + 1); /* exactly: a word beyond the lane's six is a write past the block */
+        if (S.tab) ao_lane<true, true>(sv, hot, io, S.tab, stack, job.data(), 0, w, nullptr);
+        else ao_lane<true, false>(sv, hot, io, nullptr, stack, job.data(), 0, w, nullptr);
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return write_bytes(a[6], open.data(), 4 * n) && (!want_bent || write_bytes(a[7], bent.data(), 12 * n)) &&
+           (!want_states || write_bytes(a[8], states.data(), 4 * n)) ? 0 : 1;
+}
+
 /* HEMI: the irradiance query's lanes (--irradiance): the rays file holds points */
 template <bool HEMI>
 static int radiance_mode(char **a) { /* scn base rays.f32 seeds.u32 spp rr out.f32 states.u32 */
@@ -477,6 +518,7 @@ int main(int argc, char **argv) {
     if (argc == 4 && mode == "--unit") return unit_mode(argv[2], argv[3]);
     if (argc == 6 && mode == "--raycast") return raycast_mode(argv + 2);
     if (argc == 7 && mode == "--occluded") return occluded_mode(argv + 2);
+    if (argc == 11 && mode == "--ambient-occlusion") return ao_mode(argv + 2);
     if (argc == 10 && mode == "--radiance") return radiance_mode<false>(argv + 2);
     if (argc == 16 && mode == "--radiance-adaptive") return radiance_adaptive_mode<false>(argv + 2);
     if (argc == 10 && mode == "--irradiance") return radiance_mode<true>(argv + 2);
@@ -488,6 +530,7 @@ int main(int argc, char **argv) {
                         "       host_sim --unit records.bin out.f32\n"
                         "       host_sim --raycast scn base rays.f32 hits.bin\n"
                         "       host_sim --occluded scn base rays.f32 tmax.f32|- out.u8\n"
+                        "       host_sim --ambient-occlusion scn base points.f32 seeds.u32 radius.f32|- spp open.u32 bent.f32|- states.u32|-\n"
                         "       host_sim --radiance scn base rays.f32 seeds.u32 spp rr out.f32 states.u32\n"
                         "       host_sim --radiance-adaptive scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
                         "       host_sim --irradiance scn base points.f32 seeds.u32 spp rr out.f32 states.u32\n"

@@ -13,7 +13,7 @@ for line in sys.stdin:
     m = re.search(r"remark: +(\w[^:]*): (\S+)", line)
     if m and cur: rows[cur][m.group(1).strip()] = m.group(2)
 for k, v in rows.items():
-    if "pt_persistent" not in k and "wf_" not in k and "raycast_rays" not in k and "occluded_rays" not in k and "radiance_rays" not in k and "radiance_adaptive_rays" not in k and "irradiance" not in k and "pt_adaptive" not in k: continue
-    name = k.replace("_ZN3ort", "").replace("EvNS_9SceneViewENS_9RenderHotE", "").replace("NS_9RaycastIOE", "").replace("NS_10OccludedIOE", "")
+    if "pt_persistent" not in k and "wf_" not in k and "raycast_rays" not in k and "occluded_rays" not in k and "ao_points" not in k and "radiance_rays" not in k and "radiance_adaptive_rays" not in k and "irradiance" not in k and "pt_adaptive" not in k: continue
+    name = k.replace("_ZN3ort", "").replace("EvNS_9SceneViewENS_9RenderHotE", "").replace("NS_9RaycastIOE", "").replace("NS_10OccludedIOE", "").replace("NS_4AoIOE", "")
     print(name, " ".join("%s=%s" % (a, b) for a, b in v.items()))
 '
