@@ -256,9 +256,13 @@ enum : int { PS_NEED_JOB = 0, PS_PIXEL = 1, PS_SAMPLE = 2, PS_HIT = 3, PS_DONE =
 #ifndef ORT_SIM_RAY_HOOK
 #define ORT_SIM_RAY_HOOK(x, y, o, d, t, n, m)
 #endif
+#ifndef ORT_SIM_STACK_HOOK /* traverse's stack depth after every visit and pop (fresh: the traversal starts at the root); tools/host_sim.cpp's probe */
+#define ORT_SIM_STACK_HOOK(lds_entries, sp, fresh)
+#endif
 #else
 #define ORT_SIM_PIXEL_HOOK(x, y, rng)
 #define ORT_SIM_RAY_HOOK(x, y, o, d, t, n, m)
+#define ORT_SIM_STACK_HOOK(lds_entries, sp, fresh)
 #define ORT_BALLOT(p) __ballot(p)
 #define ORT_POPC64(m) __popcll(m)
 #define ORT_NEXT_JOB(p) atomicAdd((p), 1ull)
@@ -1419,8 +1423,9 @@ ORT_D void visit_node(float4 a, float4 b, float4 cc, float4 d, V3 org, V3 inv_d,
         cur = kTraversalDone;
     } else {
         sp--;
-        /* two real loads behind a branch (the volatile keeps the compiler from merging them into one
-           flat_load of a selected generic pointer): the LDS side becomes a plain ds_read */
+        /* two loads behind a branch (the volatile is meant to keep the compiler from merging them into one flat_load of a
+           selected generic pointer, so that the LDS side is a plain ds_read: it does in the pt_persistent kernels; raycast_rays
+           and wf_trace read the tail with flat_load all the same, profiles/r15_deep_stack.md) */
         if (sp < LDS_ENTRIES) cur = lds_stack[sp * BLOCK + tid];
         else cur = ((volatile uint32_t *)spill)[sp - LDS_ENTRIES];
     }
@@ -1512,6 +1517,7 @@ ORT_D bool traverse(const SceneView &sv, V3 org, V3 dir, Trav &T, HitState &h, u
     uint32_t cur = T.cur;
     int sp = T.sp;
     const V3 inv_d = T.inv_d;
+    ORT_SIM_STACK_HOOK(LDS_ENTRIES, sp, cur == 0u);
     while (tracing) {
         ORT_UTIL(sv, 2, true);
         ORT_PHASE(pr, sv, 9, true);
@@ -1537,6 +1543,7 @@ ORT_D bool traverse(const SceneView &sv, V3 org, V3 dir, Trav &T, HitState &h, u
             }
             visit_node<COUNTERS, LDS_ENTRIES, BLOCK>(na, nb, nc, nd, org, inv_d, h.best_t, cur, sp, lds_stack, spill, tid, c);
             }
+            ORT_SIM_STACK_HOOK(LDS_ENTRIES, sp, false);
             /* the stragglers of the descend loop would keep the rest of the wave waiting: break out
                and come back for them (their cur / sp carry over) */
             if (ORT_POPC64(ORT_BALLOT(true)) < stragglers) break;
@@ -1556,11 +1563,11 @@ ORT_D bool traverse(const SceneView &sv, V3 org, V3 dir, Trav &T, HitState &h, u
                 tracing = false;
             } else {
                 sp--;
-                /* two real loads behind a branch (the volatile keeps the compiler from merging them into one
-                   flat_load of a selected generic pointer): the LDS side becomes a plain ds_read */
+                /* two loads behind a branch: see visit_node */
                 if (sp < LDS_ENTRIES) cur = lds_stack[sp * BLOCK + tid];
                 else cur = ((volatile uint32_t *)spill)[sp - LDS_ENTRIES];
             }
+            ORT_SIM_STACK_HOOK(LDS_ENTRIES, sp, false);
             ORT_PHASE(pr, sv, 6, true);
         }
         /* finished: the winner's chain word and material are wanted next (resolve_hit), ask for them now */

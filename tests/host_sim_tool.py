@@ -18,7 +18,7 @@ _KNOBS = ("SIM_", "ORT_", "ASAN_OPTIONS", "UBSAN_OPTIONS", "LSAN_OPTIONS")
 
 
 def built(target):
-    """the path of tools/<target> (host_sim or host_sim_san), made when it is missing or older than its sources"""
+    """the path of tools/<target> (host_sim, host_sim_w5 or host_sim_san), made when it is missing or older than its sources"""
     tool = os.path.join(TOOLS, target)
     src = [os.path.join(TOOLS, f) for f in ("host_sim.cpp", "host_sim_stubs.cpp", "Makefile")]
     src += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".cpp"))]
@@ -50,6 +50,13 @@ def counters(r):
     """the work counters of a run's last stderr line -> {"rays": ..., "fallback": ...}"""
     line = [l for l in r.stderr.splitlines() if l.startswith("sim:")][-1]
     return {k: int(v) for k, v in re.findall(r"(\w+) (\d+)(?= |$)", line)}
+
+
+def stack_probe(r):
+    """the stack probe's lines of a run's stderr, one per instantiation of traverse -> [{"lds": its LDS entries, "deepest": the
+    deepest stack, "traversals", "above": traversals that went past the LDS entries, "steps_above", "scratch_pops"}], the
+    instantiation with the most LDS entries (the main traversal) first; the re-traversal of resolve_hit has four fewer"""
+    return [{k: int(v) for k, v in re.findall(r"(\w+) (\d+)", l[len("stack:"):])} for l in r.stderr.splitlines() if l.startswith("stack:")]
 
 
 def raycast_args(d, scene, rays, base=None):

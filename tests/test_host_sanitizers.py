@@ -5,12 +5,14 @@ sanitized.  The other suites compare output bits, which cannot see a read one re
 harmless data, uninitialised padding that is uploaded, or undefined pointer arithmetic.  Every run here is made with both
 binaries and must (1) end with the plain binary's exit status, (2) report nothing (no "runtime error:", no
 "AddressSanitizer" on stderr) and (3) write byte-identical files.  Leak checking is on (ASAN_OPTIONS=detect_leaks=1):
-host_sim destroys what it creates.  The runs are small: at most 20 x 12 pixels, 2 spp, 120 rays, 2 threads."""
+host_sim destroys what it creates.  The runs are small: at most 20 x 12 pixels, 2 spp, 120 rays, 2 threads (1 000 rays on the
+deep scene, whose point is the traversal stack's scratch tail)."""
 import os
 
 import numpy as np
 import pytest
 
+import deep_scenes
 import host_sim_tool as hs
 import radiance_cases
 import ref_io
@@ -142,6 +144,25 @@ def test_render_modes(tools, tmp_path, policy, chunk, env, shard):
             continue
         args, outs = hs.render_args(str(tmp_path), name, 20, 12, 2, 77, policy, chunk, shard=shard)
         assert both(tools, args, outs, env=env, threads=1 if "SIM_WAVEFRONT" in env else 2).returncode == 0
+
+
+def test_the_stack_in_its_scratch_tail(api, oracle, tools, tmp_path_factory, tmp_path):
+    """the deep scene (tests/deep_scenes.py): nearly every ray's traversal stack runs past its LDS part, up to six entries into spill[], and the
+    re-traversal of resolve_hit with it; the wide tree stacks up to three entries a level and gets 44 deep, the wavefront trace
+    keeps 16 entries outside spill[].  An index past either array is what the sanitizer sees and the bit comparisons may not"""
+    w = deep_scenes.world(api, oracle, tmp_path_factory)
+    d = str(tmp_path)
+    rays = w.rays[::4]
+    r = both(tools, *hs.raycast_args(d, w.scn, rays, w.base))
+    assert r.returncode == 0
+    main, again = hs.stack_probe(r)[:2]
+    assert main["deepest"] >= main["lds"] + 4 and again["above"] > 0
+    tm = np.where(np.arange(len(rays)) % 2 == 0, w.t[::4], np.nextafter(w.t[::4], np.float32(np.inf))).astype("<f4")
+    assert both(tools, *hs.occluded_args(d, w.scn, rays, tm, w.base)).returncode == 0
+    for env in ({}, {"SIM_WIDE": "1"}, {"SIM_WAVEFRONT": "100"}, {"SIM_TABS": "1", "SIM_FORCE_FALLBACK": "0xf"}):
+        args, outs = hs.render_args(d, w.scn, 20, 12, 2, 77, "chunk", 1, w.base)
+        r = both(tools, args, outs, env=env, threads=1 if "SIM_WAVEFRONT" in env else 2)
+        assert r.returncode == 0 and hs.stack_probe(r)[0]["scratch_pops"] > 0
 
 
 def test_unit_records(tools, tmp_path):

@@ -31,6 +31,8 @@
  *   or: host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
  *       (the adaptive camera render of the scene's own camera: pt_lane<..., VIEWS, ADAPT> over a one-view batch; the planes start
  *       at the guard values -7.0f, 0xeeeeeeee, -1.0f, 0xdddddddd, which pixels outside the rect keep)
+ * Every mode prints, per instantiation of traverse, how deep the per-lane stack got ("stack: lds 24 deepest ..."; tests/host_sim_tool.py
+ * stack_probe reads it); make host_sim_w5 builds the same tool with the five-waves unit's split of that stack (20 + 44 entries).
  * All files raw little-endian.  SIM_TABS=1: the TABS = true lane code, on a heap copy of the LDS tables' image.
  */
 #define ORT_HOST_SIM 1
@@ -40,11 +42,28 @@
 static uint32_t *g_pixel_rng; static int g_W;
 static int g_dbg_x = -1, g_dbg_y = -1; static FILE *g_ray_log;
 #define ORT_SIM_RAY_HOOK(PX_, PY_, O_, D_, T_, N_, M_) do { if ((PX_) == g_dbg_x && (PY_) == g_dbg_y && g_ray_log) { float r_[11] = {O_.x, O_.y, O_.z, D_.x, D_.y, D_.z, T_, N_.x, N_.y, N_.z, 0}; unsigned m_ = (M_); fwrite(r_, 4, 10, g_ray_log); fwrite(&m_, 4, 1, g_ray_log); } } while (0)
+/* the stack probe: how deep traverse's per-lane stack gets, per instantiation (its LDS_ENTRIES: the main traversal's kLdsStack, the
+   re-traversal's kLdsStack - 4, the wavefront trace's 16 and 12).  Entries from LDS_ENTRIES on are the scratch tail (spill[]).  A
+   thread counts for itself and adds its counts to the totals when it is done (probe_flush); print_counters prints the totals */
+struct StackProbe { int lds; int deepest; int prev; bool above; unsigned long long rays, rays_above, steps_above, scratch_pops; };
+static thread_local StackProbe t_probe[4];
+static inline void stack_probe(int lds, int sp, bool fresh) {
+    StackProbe *s = t_probe;
+    while (s->lds != lds && s->lds != 0 && s != t_probe + 3) ++s;
+    s->lds = lds;
+    if (fresh) { s->rays++; s->above = false; s->prev = 0; }
+    if (sp > lds) { s->steps_above++; if (!s->above) { s->above = true; s->rays_above++; } }
+    if (!fresh && sp == s->prev - 1 && sp >= lds) s->scratch_pops++; /* the entry popped, index sp, was in scratch */
+    if (sp > s->deepest) s->deepest = sp;
+    s->prev = sp;
+}
+#define ORT_SIM_STACK_HOOK(LDS_, SP_, FRESH_) stack_probe((LDS_), (SP_), (FRESH_))
 #define ORT_SIM_PIXEL_HOOK(x, y, rng) do { if (g_pixel_rng) g_pixel_rng[(y) * g_W + (x)] = (rng); } while (0)
 #include "../offline_raytracer_amd/csrc/ort_lane.h"
 
 #include <algorithm>
 #include <chrono>
+#include <mutex>
 #include <thread>
 
 using namespace ort;
@@ -162,6 +181,21 @@ static int sim_open(Sim &S, const char *scn, const char *base, uint32_t need) {
     return 0;
 }
 
+static StackProbe g_probe[4];
+static std::mutex g_probe_lock;
+static void probe_flush() {
+    std::lock_guard<std::mutex> hold(g_probe_lock);
+    for (StackProbe &t : t_probe) {
+        if (!t.lds) continue;
+        StackProbe *g = g_probe;
+        while (g->lds != t.lds && g->lds != 0 && g != g_probe + 3) ++g;
+        g->lds = t.lds;
+        g->deepest = std::max(g->deepest, t.deepest);
+        g->rays += t.rays; g->rays_above += t.rays_above; g->steps_above += t.steps_above; g->scratch_pops += t.scratch_pops;
+        t = StackProbe{};
+    }
+}
+
 /* a pool of workers on one job counter: every worker owns what a GPU lane owns (traversal stack, focal-point cache, its
    queue of the exact fallback), shares what the lanes share (scene, tables, job counter, work counters, outputs) */
 template <typename Fn>
@@ -174,6 +208,7 @@ static void run_lanes(const Sim &S, Fn lane) {
         coldw.bfs_pool = q.data(); coldw.bfs_locks = lock.data(); coldw.bfs_queue_cap = (uint32_t)q.size(); coldw.bfs_queue_count = 1;
         svw.cold = &coldw;
         lane(svw, stack.data(), focal.data(), (uint32_t)w);
+        probe_flush();
     };
     if (S.n_threads <= 1) { worker(0); return; }
     std::vector<std::thread> pool;
@@ -183,6 +218,10 @@ static void run_lanes(const Sim &S, Fn lane) {
 
 static void print_counters(const Sim &S, double sec, const char *tail = "") {
     const unsigned long long *c = S.ctrl;
+    probe_flush();
+    std::sort(g_probe, g_probe + 4, [](const StackProbe &a, const StackProbe &b) { return a.lds > b.lds; });
+    for (const StackProbe &g : g_probe)
+        if (g.lds) fprintf(stderr, "stack: lds %d deepest %d traversals %llu above %llu steps_above %llu scratch_pops %llu\n", g.lds, g.deepest, g.rays, g.rays_above, g.steps_above, g.scratch_pops);
     fprintf(stderr, "sim: %.2fs paths %llu rays %llu node_tests %llu tri_tests %llu analytic %llu fallback %llu overflow %llu%s\n", sec, c[1], c[2], c[3], c[4], c[5], c[6], c[7], tail);
 }
 
