@@ -1105,7 +1105,9 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 /* sample_random_lights (ray.cpp:537-601): result unused, RNG advances */
                 rng_step(P.rng);
                 if (sv.light_count) {
-                    uint32_t li = P.rng % sv.light_count;
+                    /* one light: x % 1 == 0.  The count is wave-uniform, so this is a scalar branch around the per-lane remainder */
+                    uint32_t li = 0u;
+                    if (sv.light_count != 1u) li = P.rng % sv.light_count;
                     uint32_t is_sphere;
                     if (TABS) is_sphere = ((const uint32_t *)tab)[4 * kTabLights + li];
                     else is_sphere = sv.light_is_sphere[li];

@@ -1,9 +1,21 @@
 #!/bin/bash
 # Developer script: registers / spills / scratch of every path-trace and ray-query kernel variant (hipcc -Rpass-analysis=kernel-resource-usage).
-# usage: [UNIT=ort_kernels_irradiance.hip] tools/kernel_resources.sh [extra hipcc flags]      (UNIT: the kernel unit, ort_kernels.hip by default)
-cd "$(dirname "$0")/../offline_raytracer_amd/csrc"
-/opt/rocm/bin/hipcc -std=c++17 -O3 -fPIC -ffp-contract=off -fno-math-errno --offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt \
-  -Rpass-analysis=kernel-resource-usage "$@" -x hip -c "${UNIT:-ort_kernels.hip}" -o /tmp/ort_k.o 2>&1 | python3 -c '
+# The unit is compiled with the flags csrc/Makefile compiles it with (make print-kernel-flags): the table describes the binary that ships.
+# usage: [UNIT=ort_kernels_irradiance.hip] tools/kernel_resources.sh [--dry-run] [extra hipcc flags]      (UNIT: the kernel unit, ort_kernels.hip by default)
+# --dry-run prints the compile command and stops.
+set -o pipefail
+cd "$(dirname "$0")/../offline_raytracer_amd/csrc" || exit 1
+UNIT="${UNIT:-ort_kernels.hip}"
+dry=0
+if [ "$1" = "--dry-run" ]; then dry=1; shift; fi
+HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
+KFLAGS=$(make -s print-kernel-flags UNIT="$UNIT") || exit 1
+OBJ="${TMPDIR:-/tmp}/ort_k.$$.o"
+if [ $dry = 1 ]; then
+  echo "$HIPCC" $KFLAGS -Rpass-analysis=kernel-resource-usage "$@" -x hip -c "$UNIT" -o "$OBJ"
+  exit 0
+fi
+"$HIPCC" $KFLAGS -Rpass-analysis=kernel-resource-usage "$@" -x hip -c "$UNIT" -o "$OBJ" 2>&1 | python3 -c '
 import re, sys
 cur = None
 rows = {}
@@ -17,3 +29,6 @@ for k, v in rows.items():
     name = k.replace("_ZN3ort", "").replace("EvNS_9SceneViewENS_9RenderHotE", "").replace("NS_9RaycastIOE", "").replace("NS_10OccludedIOE", "").replace("NS_4AoIOE", "")
     print(name, " ".join("%s=%s" % (a, b) for a, b in v.items()))
 '
+rc=$?
+rm -f "$OBJ"
+exit $rc

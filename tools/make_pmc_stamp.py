@@ -18,13 +18,17 @@ valu_issue = vals["SQ_INSTS_VALU"] / (1024.0 * cycles / 2.0)  # 1024 SIMDs, one 
 # gfx950: FETCH_SIZE counts 64 B per 128 B request of wide reads (guide, HBM section): doubled; WRITE_SIZE is exact; both in KB
 hbm = 2.0 * vals["FETCH_SIZE"] * 1024.0 + vals["WRITE_SIZE"] * 1024.0
 commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+# the kernel hash covers the sources, not how they are compiled: the stamp names the flags of the four-waves unit as well
+kernel_flags = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "offline_raytracer_amd", "csrc"), "print-kernel-flags", "UNIT=ort_kernels"],
+                              capture_output=True, text=True, check=True).stdout.strip()
 stamp = {
     "kernel_hash": bench.kernel_source_hash(), "git_commit_at_stamp": commit, "workload_key": sys.argv[2],
     "lanes_active": lanes, "valu_issue_frac": valu_issue, "hbm_bytes_per_launch": hbm,
     "l2_hit_rate": vals["TCC_HIT_sum"] / (vals["TCC_HIT_sum"] + vals["TCC_MISS_sum"]),
     "wave_cycles_waiting_on_memory": vals["SQ_WAIT_ANY"] / vals["SQ_WAVE_CYCLES"],
     "wave_cycles_issue_stalled": vals["SQ_WAIT_INST_ANY"] / vals["SQ_WAVE_CYCLES"],
-    "source": sys.argv[3] if len(sys.argv) > 3 else sys.argv[1],
+    "source": "%s (ort_kernels.hip built with: %s)" % (sys.argv[3] if len(sys.argv) > 3 else sys.argv[1], kernel_flags),
+    "kernel_flags": kernel_flags,
     "counters": vals,
 }
 stamp["git_commit"] = commit
