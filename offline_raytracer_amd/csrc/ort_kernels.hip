@@ -9,21 +9,12 @@
 #include <memory>
 #include <type_traits>
 
-#include "ort_lane.h"
+#define ORT_LIBRARY_KERNELS 1 /* this unit also holds the kernels that are no templates: wf_*, unit_eval, combine_chunks* */
+#include "ort_lane.h" /* in namespace ort, at the header's own limits; it declares the sibling units' launchers */
 #include "ort_plan.h"
 #include "ort_setup.h"
 
 #ifndef ORT_HOST_SIM /* tools/host_sim.cpp drives the lane code itself and has no device */
-/* the sibling kernel units: a launcher each, and the sizes of the argument structs as the unit compiled them (same_layout) */
-void ort_launch_w5(int diffuse, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes); /* the five-waves build of the plain loop */
-void ort_w5_layout(size_t sizes[3]);
-void ort_launch_radiance_adaptive(int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes); /* ort_kernels_adaptive.hip */
-void ort_adaptive_layout(size_t sizes[3]);
-void ort_launch_render_adaptive(int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes); /* ort_kernels_render_adaptive.hip */
-void ort_render_adaptive_layout(size_t sizes[3]);
-void ort_launch_irradiance(int adaptive, int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes); /* ort_kernels_irradiance.hip */
-void ort_irradiance_layout(size_t sizes[3]);
-
 namespace ort {
 
 using namespace ortd;
@@ -280,11 +271,11 @@ static int launch_wavefront(DeviceScene *d, const LaunchPlan &, const SceneView 
 
 /* the sibling units' kernels, as launchers of launch_wavefront's kind */
 static int launch_five_waves(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
-    ort_launch_w5(pl.diffuse ? 1 : 0, pl.grid, (void *)stream, &sv, &hot);
+    ort_launch_w5(plan_variant(pl), pl.grid, stream, sv, hot);
     return ORT_OK;
 }
 static int launch_adaptive(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
-    ort_launch_render_adaptive(pl.counters, pl.diffuse, pl.tabs, pl.grid, (void *)stream, &sv, &hot);
+    ort_launch_render_adaptive(plan_variant(pl), pl.grid, stream, sv, hot);
     return ORT_OK;
 }
 
@@ -473,14 +464,6 @@ static int print_util_diag(const DeviceScene *d, std::string *err) {
     return ORT_OK;
 }
 
-/* a sibling unit compiles the argument structs in a namespace of its own and takes them as bytes (the RenderView too: its lanes
-   read it behind hot.c): its three sizes against this unit's */
-static bool same_layout(void (*unit_layout)(size_t *)) {
-    size_t s[3];
-    unit_layout(s);
-    return s[0] == sizeof(SceneView) && s[1] == sizeof(RenderHot) && s[2] == sizeof(RenderView);
-}
-
 /* The camera render call, plain or (c.ad) adaptive.  What runs, on which grid and with which thresholds is plan_render's or
    plan_render_adaptive's decision (ort_plan.h), and what the RenderView says besides pointers is render_view's (ort_setup.h); this
    is the plumbing around them: settle the previous call, plan, staging, views, buffers, launch, combine, finish */
@@ -488,7 +471,6 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     DeviceScene *d = scene->dev;
     if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
     ORT_HIP(hipSetDevice(d->device));
-    if (c.ad && !same_layout(ort_render_adaptive_layout)) { *err = "internal: the adaptive render kernels were built with other argument layouts"; return ORT_ERR_INTERNAL; }
     hipStream_t stream = (hipStream_t)c.stream;
     const uint32_t view_count = c.views ? c.view_count : 1u;
     int rc;
@@ -499,7 +481,7 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     SceneView sv = scene_view(scene, d);
     const SceneTraits traits = scene_traits(scene, d);
     const LaunchPlan pl = c.ad ? plan_render_adaptive(traits, *p, d->knobs, view_count)
-                               : plan_render(traits, *p, c.jobs != nullptr, c.job_count, same_layout(ort_w5_layout), d->knobs, view_count);
+                               : plan_render(traits, *p, c.jobs != nullptr, c.job_count, /* w5_layout_ok */ true, d->knobs, view_count);
     sv.util = pl.util ? d->ctrl() + 8 : nullptr;
     if (pl.wide) sv.nodes = d->nodes4.as<const float4>();
     /* the camera: the scene's own; a batch of one view is the same call with that view's camera and seed; the lanes of a larger
@@ -792,14 +774,6 @@ int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const vo
     DeviceScene *d;
     int rc;
     if ((rc = begin_query(scene, q.stats, &d, err))) return rc;
-    if (ad && !same_layout(ort_adaptive_layout)) {
-        *err = "internal: the adaptive kernels were built with other argument layouts";
-        return ORT_ERR_INTERNAL;
-    }
-    if (points && !same_layout(ort_irradiance_layout)) {
-        *err = "internal: the irradiance kernels were built with other argument layouts";
-        return ORT_ERR_INTERNAL;
-    }
     hipStream_t stream = (hipStream_t)q.stream;
     const bool counters = (q.flags & ORT_RENDER_COUNTERS) != 0;
     const QueryArray arrays[] = {{rays, 24u, false}, {seeds, 4u, false}, {out, 12u, true}, {out_spp, 4u, true}, {out_m2, 4u, true}, {states, 4u, true}};
@@ -808,9 +782,8 @@ int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const vo
         if (ad) radiance_adaptive_view(ray_query_io(scene, d, p[0]), p[1], *ad, rr, p[2], p[3], p[4], p[5], &rv);
         else radiance_view(ray_query_io(scene, d, p[0]), p[1], spp, rr, p[2], p[5], &rv);
         return launch_query(scene, d, rv, n, true, counters, stream, q.stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
-            if (points) ort_launch_irradiance(ad != nullptr, pl.counters, pl.diffuse, pl.tabs, pl.grid, (void *)stream, &sv, &hot);
-            else
-            if (ad) ort_launch_radiance_adaptive(pl.counters, pl.diffuse, pl.tabs, pl.grid, (void *)stream, &sv, &hot);
+            if (points) ort_launch_irradiance(pl, ad != nullptr, stream, sv, hot);
+            else if (ad) ort_launch_radiance_adaptive(pl, stream, sv, hot);
             else with_bools([&](auto C, auto D, auto T) {
                 hipLaunchKernelGGL((radiance_rays<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot);
             }, pl.counters, pl.diffuse, pl.tabs);

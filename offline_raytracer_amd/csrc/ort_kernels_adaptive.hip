@@ -7,19 +7,13 @@
  * and the library builds no slower than before them (profiles/r10_adaptive.md).  device_radiance (ort_kernels.hip), given
  * a stopping rule, launches them through ort_launch_radiance_adaptive.
  */
-#define ORT_ADAPTIVE_TU 1
+#define ORT_NS ort_ad /* the limits: ort_lane.h's defaults */
 #include "ort_lane.h"
 
-/* The argument structs are the same declarations compiled in this unit's namespace: passed as bytes, and the caller checks the
-   sizes (the RenderView's too: the lanes read it behind hot.c) */
-void ort_launch_radiance_adaptive(int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes) {
+/* the caller's own SceneView and RenderHot: the argument structs are ort_lane.h's one definition */
+void ort_launch_radiance_adaptive(const ort::QueryPlan &pl, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot) {
     using namespace ort_ad;
-    SceneView sv;
-    RenderHot hot;
-    memcpy(&sv, sv_bytes, sizeof(sv));
-    memcpy(&hot, hot_bytes, sizeof(hot));
     ort::with_bools([&](auto C, auto D, auto T) {
-        hipLaunchKernelGGL((radiance_adaptive_rays<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, sv, hot);
-    }, counters != 0, diffuse != 0, tabs != 0);
+        hipLaunchKernelGGL((radiance_adaptive_rays<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot);
+    }, pl.counters, pl.diffuse, pl.tabs);
 }
-void ort_adaptive_layout(size_t sizes[3]) { sizes[0] = sizeof(ort_ad::SceneView); sizes[1] = sizeof(ort_ad::RenderHot); sizes[2] = sizeof(ort_ad::RenderView); }

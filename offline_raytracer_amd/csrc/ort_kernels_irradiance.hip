@@ -8,22 +8,17 @@
  * reason: sixteen more path-trace kernels compile here beside the others (under make -j5 the five units build at once).
  * device_radiance (ort_kernels.hip), given points, launches them through ort_launch_irradiance.
  */
-#define ORT_IRRADIANCE_TU 1
+#define ORT_NS ort_ir /* the limits: ort_lane.h's defaults */
 #include "ort_lane.h"
 
-/* The argument structs are the same declarations compiled in this unit's namespace: passed as bytes, and the caller checks the
-   sizes (the RenderView's too: the lanes read it behind hot.c) */
-void ort_launch_irradiance(int adaptive, int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes) {
+/* adaptive: with the stopping rule (irradiance_adaptive_points).  The caller's own SceneView and RenderHot: the argument structs
+   are ort_lane.h's one definition */
+void ort_launch_irradiance(const ort::QueryPlan &pl, bool adaptive, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot) {
     using namespace ort_ir;
-    SceneView sv;
-    RenderHot hot;
-    memcpy(&sv, sv_bytes, sizeof(sv));
-    memcpy(&hot, hot_bytes, sizeof(hot));
     ort::with_bools([&](auto C, auto D, auto T) {
         if (adaptive)
-            hipLaunchKernelGGL((irradiance_adaptive_points<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, sv, hot);
+            hipLaunchKernelGGL((irradiance_adaptive_points<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot);
         else
-            hipLaunchKernelGGL((irradiance_points<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, sv, hot);
-    }, counters != 0, diffuse != 0, tabs != 0);
+            hipLaunchKernelGGL((irradiance_points<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot);
+    }, pl.counters, pl.diffuse, pl.tabs);
 }
-void ort_irradiance_layout(size_t sizes[3]) { sizes[0] = sizeof(ort_ir::SceneView); sizes[1] = sizeof(ort_ir::RenderHot); sizes[2] = sizeof(ort_ir::RenderView); }

@@ -9,19 +9,14 @@
  * profiles/r12_render_adaptive.md).  device_render (ort_kernels.hip), given a stopping rule, launches them through
  * ort_launch_render_adaptive.
  */
-#define ORT_RENDER_ADAPTIVE_TU 1
+#define ORT_NS ort_ra /* the limits: ort_lane.h's defaults */
 #include "ort_lane.h"
 
-/* The argument structs are the same declarations compiled in this unit's namespace: passed as bytes, and the caller checks the
-   sizes (the RenderView's too: the lanes read it behind hot.c) */
-void ort_launch_render_adaptive(int counters, int diffuse, int tabs, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes) {
+/* KF_ADAPTIVE: implicit jobs over a batch of views.  The caller's own SceneView and RenderHot: the argument structs are
+   ort_lane.h's one definition */
+void ort_launch_render_adaptive(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot) {
     using namespace ort_ra;
-    SceneView sv;
-    RenderHot hot;
-    memcpy(&sv, sv_bytes, sizeof(sv));
-    memcpy(&hot, hot_bytes, sizeof(hot));
     ort::with_bools([&](auto C, auto D, auto T) {
-        hipLaunchKernelGGL((pt_adaptive<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, sv, hot);
-    }, counters != 0, diffuse != 0, tabs != 0);
+        hipLaunchKernelGGL((pt_adaptive<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, stream, sv, hot);
+    }, v.counters, v.diffuse, v.tabs);
 }
-void ort_render_adaptive_layout(size_t sizes[3]) { sizes[0] = sizeof(ort_ra::SceneView); sizes[1] = sizeof(ort_ra::RenderHot); sizes[2] = sizeof(ort_ra::RenderView); }

@@ -13,21 +13,15 @@
  * lane), the ray exchange loses 2 %: those stay at four waves, in ort_kernels.hip proper.  device_render chooses; ORT_WAVES5=0 / 1
  * forces.  Same lane code, same results (tests/test_gpu_parity.py::test_five_waves_build_equals_four_waves_build).
  */
-#define ORT_W5_TU 1
+#define ORT_NS ort_w5
 #define ORT_WAVES_PER_EU 5
 #define ORT_LDS_STACK 20
 #define ORT_SPILL_STACK 44
 #include "ort_lane.h"
 
-/* the five-waves variants of the plain loop, launched by device_render (ort_kernels.hip proper).  The argument structs are
-   the same declarations compiled in this unit's namespace: passed as bytes, and the caller checks the sizes (the RenderView's
-   too: the lanes read it behind hot.c) */
-void ort_launch_w5(int diffuse, unsigned int grid, void *stream, const void *sv_bytes, const void *hot_bytes) {
-    ort_w5::SceneView sv;
-    ort_w5::RenderHot hot;
-    memcpy(&sv, sv_bytes, sizeof(sv));
-    memcpy(&hot, hot_bytes, sizeof(hot));
-    if (diffuse) hipLaunchKernelGGL((ort_w5::pt_persistent<false, true, true, true>), dim3(grid), dim3(ort_w5::kBlock), 0, (hipStream_t)stream, sv, hot);
-    else hipLaunchKernelGGL((ort_w5::pt_persistent<false, false, true, true>), dim3(grid), dim3(ort_w5::kBlock), 0, (hipStream_t)stream, sv, hot);
+/* the five-waves variants of the plain loop (KF_FIVE: no counters, tables, implicit jobs), launched by device_render
+   (ort_kernels.hip proper) with its own SceneView and RenderHot: the argument structs are ort_lane.h's one definition */
+void ort_launch_w5(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot) {
+    if (v.diffuse) hipLaunchKernelGGL((ort_w5::pt_persistent<false, true, true, true>), dim3(grid), dim3(ort_w5::kBlock), 0, stream, sv, hot);
+    else hipLaunchKernelGGL((ort_w5::pt_persistent<false, false, true, true>), dim3(grid), dim3(ort_w5::kBlock), 0, stream, sv, hot);
 }
-void ort_w5_layout(size_t sizes[3]) { sizes[0] = sizeof(ort_w5::SceneView); sizes[1] = sizeof(ort_w5::RenderHot); sizes[2] = sizeof(ort_w5::RenderView); }

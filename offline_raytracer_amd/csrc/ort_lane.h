@@ -16,8 +16,11 @@
  * ort_kernels_adaptive.hip (the adaptive radiance queries' kernels, at the first unit's limits: a unit of their own so that they
  * compile beside it), ort_kernels_render_adaptive.hip (the adaptive camera render's, likewise) and ort_kernels_irradiance.hip (the
  * irradiance queries', likewise).  Same lane code, other limits
- * (ORT_WAVES_PER_EU, ORT_LDS_STACK, ORT_SPILL_STACK); each unit compiles it in a namespace of its own (ORT_NS), so that two builds
- * of one template are two symbols.  tools/host_sim.cpp compiles it for the host (ORT_HOST_SIM: one simulated lane).
+ * (ORT_WAVES_PER_EU, ORT_LDS_STACK, ORT_SPILL_STACK); each unit compiles it in a namespace of its own, which it names beside
+ * its limits (ORT_NS; `ort` when it names none), so that two builds of one template are two symbols.  What does not depend on a
+ * limit -- the argument structs and the sibling units' launchers -- is defined once, in namespace ort, ahead of that namespace;
+ * the kernels that are no templates are compiled for the unit that asks (ORT_LIBRARY_KERNELS: ort_kernels.hip).
+ * tools/host_sim.cpp compiles the lane code for the host (ORT_HOST_SIM: one simulated lane).
  */
 #ifndef ORT_LANE_H
 #define ORT_LANE_H
@@ -37,39 +40,10 @@
 #include "ort_scene.h"
 #include "ort_setup.h"
 
-#ifdef ORT_W5_TU
-#define ORT_NS ort_w5
-#elif defined(ORT_ADAPTIVE_TU)
-#define ORT_NS ort_ad
-#elif defined(ORT_RENDER_ADAPTIVE_TU)
-#define ORT_NS ort_ra
-#elif defined(ORT_IRRADIANCE_TU)
-#define ORT_NS ort_ir
-#else
-#define ORT_NS ort
-#endif
-
-namespace ORT_NS {
-
-using namespace ort;
-using namespace ortd;
-
-constexpr int kBlock = 256;      /* 4 waves */
-#ifndef ORT_LDS_STACK
-#define ORT_LDS_STACK 24
-#endif
-constexpr int kLdsStack = ORT_LDS_STACK; /* entries per lane in LDS: 24 * 256 * 4 B = 24 KB per block */
-#ifndef ORT_SPILL_STACK
-#define ORT_SPILL_STACK 40
-#endif
-constexpr int kSpillStack = ORT_SPILL_STACK;  /* scratch tail */
-static_assert(kLdsStack - 4 + kSpillStack >= (int)kTreeDepthBudget, "the re-traversal of resolve_hit must hold a tree of kTreeDepthBudget levels");
-constexpr uint32_t kBfsPoolQueues = 1024;     /* queues of the breadth-first fallback, shared by all lanes */
-constexpr size_t kBfsPoolBytes = 1024u << 20; /* at most; a queue holds one entry per reference-tree node */
-constexpr int kDiagFallback = 106;            /* fallback_counters = ctrl + 6: the diagnostics sit at ctrl[112..114] */
-constexpr uint32_t kBfsLockStride = 32;       /* u32 units: every lock word has a 128-byte line to itself */
-
-/* the layout of the small LDS tables (kTabRoot ... kTabF4, TAB_*): ort_setup.h, with the host code that fills them */
+/* ---- what passes between the host and the kernels: the argument structs, once for all units ------------------------------
+ * None of them depends on a unit's limits, so the host side (ort_kernels.hip) and every unit's kernels share these very types:
+ * a sibling unit's launcher takes the host's SceneView and RenderHot as they are.  (PrimInfo, plain integers: ort_scene.h.) */
+namespace ort {
 
 #ifdef ORT_HOST_SIM
 #define ORT_CONSTANT_AS
@@ -95,9 +69,6 @@ struct SceneCold {
                                               diagnostics at [kDiagFallback]: octree nodes enqueued, rays traversed again, busy queues met */
 };
 
-/* chain: len << 28 | kChainNested | first pair of chain_boxes (ort_scene.h, RefTree); mat: material index */
-struct PrimInfo { uint32_t chain, mat; };
-
 struct SceneView {
     const float4 *tab_src;    /* kTabF4 float4, the image of the LDS tables */
     uint32_t tab_flags;
@@ -121,21 +92,6 @@ struct SceneView {
     unsigned long long *util; /* diagnostics (ORT_DEBUG_UTIL=1, counters build): per-phase wave-iteration and active-lane sums */
     uint32_t force_fallback_mask; /* tests (ORT_DEBUG_FORCE_FALLBACK): also re-cast rays with (bits(dir.x) & mask) == 0; ~0u = off */
 };
-
-/* host: the PrimInfo array of a committed scene, triangles | boxes | cylinders | spheres */
-inline void build_prim_info(const Tree &t, const RefTree &rt, std::vector<PrimInfo> &out, uint32_t &info_box, uint32_t &info_cyl, uint32_t &info_sphere) {
-    info_box = (uint32_t)t.tri_mat.size();
-    info_cyl = info_box + (uint32_t)t.box_mat.size();
-    info_sphere = info_cyl + (uint32_t)t.cyl_mat.size();
-    out.assign((size_t)info_sphere + t.sphere_mat.size(), PrimInfo{0u, 0u});
-    auto fill = [&out](uint32_t base, const std::vector<uint32_t> &chain, const std::vector<uint32_t> &mat) {
-        for (size_t i = 0; i < mat.size(); ++i) out[base + i] = PrimInfo{i < chain.size() ? chain[i] : 0u, mat[i]};
-    };
-    fill(0u, rt.tri_chain, t.tri_mat);
-    fill(info_box, rt.box_chain, t.box_mat);
-    fill(info_cyl, rt.cyl_chain, t.cyl_mat);
-    fill(info_sphere, rt.sphere_chain, t.sphere_mat);
-}
 
 enum : int { JOBS_EXPLICIT = 0, JOBS_PIXEL = 1, JOBS_CHUNK = 2 };
 
@@ -233,9 +189,87 @@ struct WfView {
     unsigned long long *active; /* rays produced by the last counted shade launch */
 };
 
-/* ---- kernel ---------------------------------------------------------------------------- */
+/* a path's state, as the lanes and WfView::flags hold it */
 enum : int { PS_NEED_JOB = 0, PS_PIXEL = 1, PS_SAMPLE = 2, PS_HIT = 3, PS_DONE = 4 };
 
+/* the third argument of the ray queries' kernels (raycast_rays, occluded_rays, ao_points; their lanes are described below) */
+struct RaycastIO {
+    const float2 *rays;        /* count x 3: o.x o.y | o.z d.x | d.y d.z */
+    uint2 *hits;               /* count x 3: t n.x | n.y n.z | mat prim (ort_hit) */
+    const uint32_t *prim_src;  /* info_index order -> kind << 28 | the shape's index in the scene's own arrays */
+    /* The fast tree's quadric boxes hold every hit the reference's intersectors can report for the rays a render casts
+       (ort_tree.cpp): unit directions, origins within the scene's box (shapes and camera).  A caller's ray need not be
+       either.  A sphere's tangent branch (|b^2 - a c| < 1e-5, ray.cpp:174) widens as 1e-5 / |d|^2 when |d| < 1 -- a
+       "hit" far outside the sphere's box -- and the f32 cancellation of both quadrics grows with the origin's distance.
+       A cylinder's quadric degrades once |d|^2 nears the subnormal range (a = dx^2 + dy^2 is 0 below |d| ~ 1e-19).
+       A direction component of +-0 (or NaN, or one whose reciprocal overflows) makes 1/d non-finite: box shapes in the
+       fast tree then part from the reference for rays from exactly a box's face plane (grazing a room's wall).
+       Such rays take the exact walk of the reference octree instead (resolve_hit: a phantom that could win). */
+    uint32_t tree_spheres;     /* the fast tree holds spheres (those of the analytic prologue are tested outright) */
+    uint32_t tree_quadrics;    /* ... spheres or cylinders */
+    uint32_t tree_boxes;       /* ... boxes */
+    float lo[3], hi[3];        /* the scene's box as ort_tree.cpp sized the quadric boxes for */
+};
+
+struct OccludedIO {
+    RaycastIO q;            /* the rays and what raycast_needs_exact reads; hits and prim_src are null */
+    const float *tmax;      /* count limits, or null: none */
+    uint8_t *out;           /* count bytes, each 0 or 1 */
+    uint32_t mats_nonzero;  /* no shape of the scene carries material 0 */
+};
+
+struct AoIO {
+    RaycastIO q;            /* q.rays: the points (p, n); and what raycast_needs_exact reads.  hits and prim_src are null */
+    const uint32_t *seeds;  /* count stream seeds (0 is taken as 1) */
+    const float *radius;    /* count limits, or null: none */
+    uint32_t *open;         /* count: samples with nothing in the way, or ORT_AO_INVALID */
+    float *bent;            /* count x 3, or null: the sum of the open samples' directions, in sample order */
+    uint32_t *states;       /* count, or null: the stream after 2 * spp steps */
+    uint32_t spp;           /* >= 1 */
+    uint32_t mats_nonzero;  /* no shape of the scene carries material 0 (the early end, as occluded_lane's) */
+};
+
+} // namespace ort
+
+#ifndef ORT_HOST_SIM
+/* The sibling units' entry points, declared here alone: each is defined by the unit that holds its kernels and called by
+   ort_kernels.hip.  The flavour comes as named fields: a render kernel's KernelVariant (plan_variant, ort_plan.h), a query's
+   QueryPlan; every other bool of the kernels is fixed by the family. */
+void ort_launch_w5(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);              /* KF_FIVE: ort_kernels_w5.hip */
+void ort_launch_render_adaptive(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot); /* KF_ADAPTIVE: ort_kernels_render_adaptive.hip */
+void ort_launch_radiance_adaptive(const ort::QueryPlan &pl, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);                    /* ort_kernels_adaptive.hip */
+void ort_launch_irradiance(const ort::QueryPlan &pl, bool adaptive, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);            /* ort_kernels_irradiance.hip */
+#endif
+
+/* The lane code and the limits it is built for: a unit that compiles them at limits of its own, or beside ort_kernels.hip's,
+   names its namespace (ORT_NS) where it states them, so that two builds of one template are two symbols */
+#ifndef ORT_NS
+#define ORT_NS ort
+#endif
+
+namespace ORT_NS {
+
+using namespace ort;
+using namespace ortd;
+
+constexpr int kBlock = 256;      /* 4 waves */
+#ifndef ORT_LDS_STACK
+#define ORT_LDS_STACK 24
+#endif
+constexpr int kLdsStack = ORT_LDS_STACK; /* entries per lane in LDS: 24 * 256 * 4 B = 24 KB per block */
+#ifndef ORT_SPILL_STACK
+#define ORT_SPILL_STACK 40
+#endif
+constexpr int kSpillStack = ORT_SPILL_STACK;  /* scratch tail */
+static_assert(kLdsStack - 4 + kSpillStack >= (int)kTreeDepthBudget, "the re-traversal of resolve_hit must hold a tree of kTreeDepthBudget levels");
+constexpr uint32_t kBfsPoolQueues = 1024;     /* queues of the breadth-first fallback, shared by all lanes */
+constexpr size_t kBfsPoolBytes = 1024u << 20; /* at most; a queue holds one entry per reference-tree node */
+constexpr int kDiagFallback = 106;            /* fallback_counters = ctrl + 6: the diagnostics sit at ctrl[112..114] */
+constexpr uint32_t kBfsLockStride = 32;       /* u32 units: every lock word has a 128-byte line to itself */
+
+/* the layout of the small LDS tables (kTabRoot ... kTabF4, TAB_*): ort_setup.h, with the host code that fills them */
+
+/* ---- kernel ---------------------------------------------------------------------------- */
 #ifdef ORT_HOST_SIM /* one simulated lane per host thread: tools/host_sim.cpp (job draws and counters are atomic: its threads share them) */
 #define ORT_BALLOT(p) ((p) ? 1ull : 0ull)
 #define ORT_POPC64(m) __builtin_popcountll(m)
@@ -2201,7 +2235,7 @@ pt_persistent_x(SceneView sv, RenderHot rv) {
     }
 }
 
-#if !defined(ORT_W5_TU) && !defined(ORT_ADAPTIVE_TU) && !defined(ORT_RENDER_ADAPTIVE_TU) && !defined(ORT_IRRADIANCE_TU) /* the five-waves unit only needs the path-trace kernels, the adaptive and irradiance ones their own */
+#ifdef ORT_LIBRARY_KERNELS /* the kernels that are no templates would be compiled by every unit that includes this: ort_kernels.hip alone asks for them */
 /* wavefront kernels: fixed-size grids, grid-stride over the slots */
 template <bool COUNTERS>
 __global__ void __launch_bounds__(kBlock) wf_shade(SceneView sv, RenderHot rv, WfView wf, int count_active) {
@@ -2259,10 +2293,9 @@ __global__ void combine_chunks_views(RenderHot rv) {
     combine_pixel(rv, idx % per_view, (uint32_t)(idx / per_view));
 }
 
-#endif /* !ORT_W5_TU && !ORT_ADAPTIVE_TU && !ORT_RENDER_ADAPTIVE_TU && !ORT_IRRADIANCE_TU */
+#endif /* ORT_LIBRARY_KERNELS */
 #endif /* !ORT_HOST_SIM */
 
-#ifndef ORT_W5_TU
 /* ---- closest-hit ray queries (ort_raycast): raycast_top_most_node, ray.cpp:1165-1176 --------------------------------
  * The path-trace loop without shading: a lane without a ray takes the next ray index from its wave's batch (draw_job:
  * the job space is the ray array, job_count rays), starts it (begin_ray: analytic prologue from the LDS tables),
@@ -2270,24 +2303,6 @@ __global__ void combine_chunks_views(RenderHot rv) {
  * and, once the ray is finished, resolves its hit to the reference's answer (resolve_hit: chains, ties, phantoms, the
  * exact fallback) and writes the record, the normal normalised as raycast_bvh returns it.  A wave's ray indices are contiguous, so its 24-byte loads and stores
  * coalesce; both are done as three 8-byte accesses (the host checks the alignment). */
-struct RaycastIO {
-    const float2 *rays;        /* count x 3: o.x o.y | o.z d.x | d.y d.z */
-    uint2 *hits;               /* count x 3: t n.x | n.y n.z | mat prim (ort_hit) */
-    const uint32_t *prim_src;  /* info_index order -> kind << 28 | the shape's index in the scene's own arrays */
-    /* The fast tree's quadric boxes hold every hit the reference's intersectors can report for the rays a render casts
-       (ort_tree.cpp): unit directions, origins within the scene's box (shapes and camera).  A caller's ray need not be
-       either.  A sphere's tangent branch (|b^2 - a c| < 1e-5, ray.cpp:174) widens as 1e-5 / |d|^2 when |d| < 1 -- a
-       "hit" far outside the sphere's box -- and the f32 cancellation of both quadrics grows with the origin's distance.
-       A cylinder's quadric degrades once |d|^2 nears the subnormal range (a = dx^2 + dy^2 is 0 below |d| ~ 1e-19).
-       A direction component of +-0 (or NaN, or one whose reciprocal overflows) makes 1/d non-finite: box shapes in the
-       fast tree then part from the reference for rays from exactly a box's face plane (grazing a room's wall).
-       Such rays take the exact walk of the reference octree instead (resolve_hit: a phantom that could win). */
-    uint32_t tree_spheres;     /* the fast tree holds spheres (those of the analytic prologue are tested outright) */
-    uint32_t tree_quadrics;    /* ... spheres or cylinders */
-    uint32_t tree_boxes;       /* ... boxes */
-    float lo[3], hi[3];        /* the scene's box as ort_tree.cpp sized the quadric boxes for */
-};
-
 ORT_D bool raycast_needs_exact(const RaycastIO &io, V3 org, V3 dir, V3 inv_d) {
     const bool short_dir = io.tree_quadrics && !(len2(dir) >= (io.tree_spheres ? 0.999f : 1e-30f));
     const bool inv_nonfinite = io.tree_boxes && !(((inv_d.x - inv_d.x) + (inv_d.y - inv_d.y)) + (inv_d.z - inv_d.z) == 0.0f);
@@ -2388,13 +2403,6 @@ raycast_rays(SceneView sv, RenderHot rv, RaycastIO io) {
  * EXACT WALK.  The rays raycast_needs_exact names, and those ORT_DEBUG_FORCE_FALLBACK selects, skip the fast traversal
  * and the early end; resolve_hit re-casts them exactly and their closest hit is compared with tmax.
  * One byte out per ray, a plain byte store: a wave's ray indices are contiguous, 64 adjacent bytes. */
-struct OccludedIO {
-    RaycastIO q;            /* the rays and what raycast_needs_exact reads; hits and prim_src are null */
-    const float *tmax;      /* count limits, or null: none */
-    uint8_t *out;           /* count bytes, each 0 or 1 */
-    uint32_t mats_nonzero;  /* no shape of the scene carries material 0 */
-};
-
 template <bool COUNTERS, bool TABS>
 ORT_D void occluded_lane(const SceneView &sv, const RenderHot &rv, const OccludedIO &io, const float4 *tab, uint32_t *lds_stack, const int tid,
                          const uint32_t lane_id, unsigned long long *pool) {
@@ -2504,16 +2512,6 @@ ORT_D bool ao_box_within(float4 lo_xyz_hi_x, float hi_y, float hi_z, V3 p, float
     return !(((dx * dx + dy * dy) + dz * dz) * 0.998f > bound * bound); /* NaN or overflow: within */
 }
 constexpr int kAoCacheWords = 6; /* bent.xyz, normalize(n).xyz */
-struct AoIO {
-    RaycastIO q;            /* q.rays: the points (p, n); and what raycast_needs_exact reads.  hits and prim_src are null */
-    const uint32_t *seeds;  /* count stream seeds (0 is taken as 1) */
-    const float *radius;    /* count limits, or null: none */
-    uint32_t *open;         /* count: samples with nothing in the way, or ORT_AO_INVALID */
-    float *bent;            /* count x 3, or null: the sum of the open samples' directions, in sample order */
-    uint32_t *states;       /* count, or null: the stream after 2 * spp steps */
-    uint32_t spp;           /* >= 1 */
-    uint32_t mats_nonzero;  /* no shape of the scene carries material 0 (the early end, as occluded_lane's) */
-};
 
 template <bool COUNTERS, bool TABS>
 ORT_D void ao_lane(const SceneView &sv, const RenderHot &rv, const AoIO &io, const float4 *tab, uint32_t *lds_stack, float *job_cache, const int tid,
@@ -2726,8 +2724,6 @@ irradiance_adaptive_points(SceneView sv, RenderHot rv) {
     radiance_lane<COUNTERS, DIFFUSE, TABS, true, true>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 #endif
-
-#endif /* !ORT_W5_TU */
 
 } // namespace ORT_NS
 

@@ -211,7 +211,8 @@ struct LaunchPlan {
 };
 
 /* job_count: the number of explicit jobs (explicit_jobs; ignored otherwise: PIXEL / CHUNK job spaces follow from p).
-   w5_layout_ok: the five-waves unit's argument structs have this unit's layout (ort_launch_w5 takes them as bytes).
+   w5_layout_ok: a planner switch, false = never the five-waves unit (the units share one definition of the argument structs, so
+   device_render passes true; tools/launch_plan and its tests keep the input).
    view_count: the views of an ort_render_views batch (PIXEL / CHUNK job spaces only).  1 is the render call as it always was: a
    batch of one view is that call with the view's camera and seed.  More than one: the job space is [view][block][chunk][pixel]
    -- the view outermost, so the lanes of a wave almost always share a camera and the launch ends on the last view's last blocks --

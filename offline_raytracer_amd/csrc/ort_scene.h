@@ -149,6 +149,10 @@ struct RefTree {
     bool built = false;
 };
 
+/* What shading asks about a ray's winner, one record per primitive (SceneView::prim_info, ort_lane.h; build_prim_info,
+   ort_setup.h).  chain: len << 28 | kChainNested | first pair of chain_boxes (RefTree's *_chain word); mat: material index */
+struct PrimInfo { uint32_t chain, mat; };
+
 struct DeviceScene; /* ort_kernels.hip */
 
 struct Scene {

@@ -1,8 +1,8 @@
 /*
  * ort_setup.h -- what the host works out from a committed scene before a kernel can run, as plain functions of their
- * inputs: the layout and the image of the small LDS tables, the shape table of the ray queries (the inverse of the tree's
- * slot maps), what raycast_needs_exact reads, the camera table of a batch of views, and every field of a call's RenderView that
- * is not a pointer.  No HIP in here: ort_kernels.hip calls these and keeps the uploads and launches; tools/host_sim.cpp calls the
+ * inputs: the layout and the image of the small LDS tables, the PrimInfo array, the shape table of the ray queries (the inverse
+ * of the tree's slot maps), what raycast_needs_exact reads, the camera table of a batch of views, and every field of a call's
+ * RenderView that is not a pointer.  No HIP in here: ort_kernels.hip calls these and keeps the uploads and launches; tools/host_sim.cpp calls the
  * same functions to run the lane code on host threads, so the CPU tests exercise the product's own tables and launch set-up
  * (tests/test_query_lanes_host.py), and tools/launch_plan prints the fill of a plan (tests/test_launch_plan.py).
  */
@@ -78,6 +78,21 @@ inline uint32_t pack_lds_tables(const Tree &t, const std::vector<DevMaterial> &m
     return flags;
 }
 
+/* the PrimInfo array of a committed scene (SceneView::prim_info), triangles | boxes | cylinders | spheres */
+inline void build_prim_info(const Tree &t, const RefTree &rt, std::vector<PrimInfo> &out, uint32_t &info_box, uint32_t &info_cyl, uint32_t &info_sphere) {
+    info_box = (uint32_t)t.tri_mat.size();
+    info_cyl = info_box + (uint32_t)t.box_mat.size();
+    info_sphere = info_cyl + (uint32_t)t.cyl_mat.size();
+    out.assign((size_t)info_sphere + t.sphere_mat.size(), PrimInfo{0u, 0u});
+    auto fill = [&out](uint32_t base, const std::vector<uint32_t> &chain, const std::vector<uint32_t> &mat) {
+        for (size_t i = 0; i < mat.size(); ++i) out[base + i] = PrimInfo{i < chain.size() ? chain[i] : 0u, mat[i]};
+    };
+    fill(0u, rt.tri_chain, t.tri_mat);
+    fill(info_box, rt.box_chain, t.box_mat);
+    fill(info_cyl, rt.cyl_chain, t.cyl_mat);
+    fill(info_sphere, rt.sphere_chain, t.sphere_mat);
+}
+
 /* ray queries: the inverse of the tree's slot maps, in PrimInfo order (triangles | boxes | cylinders | spheres; info_* are
    build_prim_info's): slot -> kind << 28 | the shape's index in the scene's own arrays.  False when the maps are no bijection
    onto the shape arrays */
@@ -100,7 +115,7 @@ inline bool invert_prim_slots(const Tree &t, uint32_t info_box, uint32_t info_cy
     return bijective;
 }
 
-/* what raycast_needs_exact reads (IO: RaycastIO of ort_lane.h): which kinds of shape the fast tree holds, and the scene's box
+/* what raycast_needs_exact reads (IO: ort::RaycastIO, ort_lane.h): which kinds of shape the fast tree holds, and the scene's box
    (scene_origin_box) */
 template <typename IO>
 inline void ray_query_io(const Scene &scene, const float lo[3], const float hi[3], IO *io) {
@@ -111,7 +126,8 @@ inline void ray_query_io(const Scene &scene, const float lo[3], const float hi[3
     memcpy(io->hi, hi, 3 * sizeof(float));
 }
 
-/* radiance queries: what radiance_lane reads behind hot.c besides the launch policy (View: RenderView of ort_lane.h) -- the
+/* radiance queries: what radiance_lane reads behind hot.c besides the launch policy (View: ort::RenderView, ort_lane.h -- the one
+   definition every kernel unit shares -- or tools/launch_plan's pointer-free FillView) -- the
    job space is one PIXEL-style job per ray; q is the query's ray_query_io with its rays set.  All pointers are the lanes' */
 template <typename View, typename IO>
 inline void radiance_view(const IO &q, const void *seeds, uint32_t spp, float rr, void *out, void *final_states, View *rv) {
@@ -179,7 +195,7 @@ inline void with_bools(F f, bool b, Rest... rest) {
     else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
-/* the kernels' by-value argument (Hot: RenderHot of ort_lane.h): the few fields of rv every ray reads, and where the lanes find
+/* the kernels' by-value argument (Hot: ort::RenderHot, ort_lane.h): the few fields of rv every ray reads, and where the lanes find
    the rest -- rv itself on the host, its copy in HBM on the device */
 template <typename Hot, typename View>
 inline Hot render_hot(const View &rv, const void *where) {

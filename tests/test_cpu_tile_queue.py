@@ -9,19 +9,13 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import DATA, GOLDEN, ROOT, assert_bits_equal
-
-TOOL = os.path.join(ROOT, "tools", "host_sim")
+import host_sim_tool
+from conftest import DATA, GOLDEN, assert_bits_equal
 
 
 @pytest.fixture(scope="module")
 def host_sim():
-    src = [os.path.join(ROOT, "tools", "host_sim.cpp"), os.path.join(ROOT, "offline_raytracer_amd", "csrc", "ort_lane.h")]
-    if not os.path.exists(TOOL) or any(os.path.getmtime(s) > os.path.getmtime(TOOL) for s in src):
-        if not os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")):
-            pytest.skip("tools/host_sim is not built and there is no hipcc to build it with")
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tools")], stderr=subprocess.DEVNULL)
-    return TOOL
+    return host_sim_tool.built("host_sim")
 
 
 def _run(tool, scene, w, h, spp, seed, policy, chunk, out, threads, extra=None, base=None):

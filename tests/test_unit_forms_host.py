@@ -11,22 +11,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_sim_tool
 import ref_io
 import unit_cases as U
-from conftest import GOLDEN, ROOT
-
-TOOL = os.path.join(ROOT, "tools", "host_sim")
-CSRC = os.path.join(ROOT, "offline_raytracer_amd", "csrc")
+from conftest import GOLDEN
 
 
 @pytest.fixture(scope="module")
 def host_sim():
-    src = [os.path.join(ROOT, "tools", "host_sim.cpp")] + [os.path.join(CSRC, f) for f in ("ort_lane.h", "ort_device.h", "ort_detmath.h")]
-    if not os.path.exists(TOOL) or any(os.path.getmtime(s) > os.path.getmtime(TOOL) for s in src):
-        if not os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")):
-            pytest.skip("tools/host_sim is not built and there is no hipcc to build it with")
-        subprocess.check_call(["make", "-s", "-B", "-C", os.path.join(ROOT, "tools")], stderr=subprocess.DEVNULL)
-    return TOOL
+    return host_sim_tool.built("host_sim")
 
 
 @pytest.fixture(scope="module")

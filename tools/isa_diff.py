@@ -1,17 +1,33 @@
 """Developer script: compare the machine code of the kernels of two device-assembly files, kernel by kernel.
 
-Make the two files from two trees (same flags as the Makefile, device side only), e.g. for the four-waves unit:
-  hipcc -std=c++17 -O3 -fPIC -ffp-contract=off -fno-math-errno --offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt \
+Make the two files from two trees, device side only, each unit with the flags the Makefile compiles it with
+(make -s -C offline_raytracer_amd/csrc print-kernel-flags UNIT=ort_kernels_w5), e.g. for the four-waves unit:
+  hipcc -std=c++17 -O3 -fPIC -ffp-contract=off -fno-math-errno --offload-arch=gfx950 -Wall -Wno-unused-function \
+        -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize \
         --cuda-device-only -S -x hip offline_raytracer_amd/csrc/ort_kernels.hip -o before.s
 (the five-waves unit ort_kernels_w5.hip with -mllvm -disable-machine-licm as well).  Then
   python3 tools/isa_diff.py before.s after.s [name filter regex]
-prints, per kernel symbol present in both, whether its instructions are identical.  Local labels are renumbered by
-their order inside the function (a kernel added before another shifts the function numbers in .LBB<f>_<n>);
-comments and assembler directives are ignored.  Exit status 1 if any common kernel differs."""
+prints, per kernel present in both, whether its instructions are identical.  Kernels are paired by their mangled name up
+to the end of the template arguments: the argument types that follow name the namespace the argument structs are
+defined in, which is no part of what a kernel is.  Local labels are renumbered by their order inside the function (a
+kernel added before another shifts the function numbers in .LBB<f>_<n>); comments and assembler directives are ignored.
+Exit status 1 if any common kernel differs."""
 import re
 import sys
 
-DEFAULT = r"pt_persistent|wf_|combine_chunks|unit_eval"
+DEFAULT = r"pt_persistent|pt_adaptive|wf_|combine_chunks|unit_eval|raycast_rays|occluded_rays|ao_points|radiance_|irradiance_"  # every kernel family
+
+
+def kernel_key(sym):
+    """_ZN<namespace><name>[I<bools>E]E<argument types> -> the name without the argument types (sym itself where it is no such name)"""
+    if not sym.startswith("_ZN"):
+        return sym
+    i = 3
+    while i < len(sym) and sym[i].isdigit():
+        m = re.match(r"\d+", sym[i:])
+        i += len(m.group(0)) + int(m.group(0))
+    m = re.match(r"(I(Lb[01]E)+E)?E", sym[i:])
+    return sym[:i + len(m.group(0))] if m and i <= len(sym) else sym
 
 
 def functions(path):
@@ -24,7 +40,8 @@ def functions(path):
         if cur is None:
             continue
         if line.startswith(".Lfunc_end"):
-            out[cur] = body
+            assert kernel_key(cur) not in out, "two functions of %s share the name %s" % (path, kernel_key(cur))
+            out[kernel_key(cur)] = body
             cur = None
             continue
         s = line.split(";")[0].strip()

@@ -24,10 +24,19 @@ for line in sys.stdin:
     if m: cur = m.group(1); rows[cur] = {}; continue
     m = re.search(r"remark: +(\w[^:]*): (\S+)", line)
     if m and cur: rows[cur][m.group(1).strip()] = m.group(2)
+def pretty(k):
+    # _ZN <len>namespace <len>name [I Lb0E Lb1E ... E] E <argument types> -> name<0,1,...>, with the namespace in front where a sibling unit named one
+    if not k.startswith("_ZN"): return k
+    parts, i = [], 3
+    while k[i].isdigit():
+        n = re.match(r"\d+", k[i:]).group(0)
+        parts.append(k[i + len(n):i + len(n) + int(n)])
+        i += len(n) + int(n)
+    bools = re.match(r"I((?:Lb[01]E)+)E", k[i:])
+    return "::".join(p for p in parts if p != "ort") + ("<" + ",".join(re.findall(r"Lb([01])E", bools.group(1))) + ">" if bools else "")
 for k, v in rows.items():
     if "pt_persistent" not in k and "wf_" not in k and "raycast_rays" not in k and "occluded_rays" not in k and "ao_points" not in k and "radiance_rays" not in k and "radiance_adaptive_rays" not in k and "irradiance" not in k and "pt_adaptive" not in k: continue
-    name = k.replace("_ZN3ort", "").replace("EvNS_9SceneViewENS_9RenderHotE", "").replace("NS_9RaycastIOE", "").replace("NS_10OccludedIOE", "").replace("NS_4AoIOE", "")
-    print(name, " ".join("%s=%s" % (a, b) for a, b in v.items()))
+    print(pretty(k), " ".join("%s=%s" % (a, b) for a, b in v.items()))
 '
 rc=$?
 rm -f "$OBJ"

@@ -24,8 +24,9 @@
 #include "../offline_raytracer_amd/csrc/ort_plan.h"
 #include "../offline_raytracer_amd/csrc/ort_setup.h"
 
-/* the RenderView (csrc/ort_lane.h, which only a HIP compiler reads) without its pointers: the fields render_view fills.  Kept by
-   hand in step with ort_lane.h: a field render_view assigns and this list lacks does not compile, but one added to RenderView and
+/* ort::RenderView (csrc/ort_lane.h, which only a HIP compiler reads: the one definition all kernel units and the host side share)
+   without its pointers: the fields render_view fills.  This stand-in is why the set-up functions of ort_setup.h are templates.  Kept
+   by hand in step with ort_lane.h: a field render_view assigns and this list lacks does not compile, but one added to RenderView and
    forgotten in render_view does not show here */
 #define FILL_FIELDS(F) F(mode) F(W) F(H) F(x0) F(y0) F(x1) F(y1) F(seed) F(spp) F(chunk) F(rr) F(packed_out) F(nchunks) F(job_count) F(shard_index) \
     F(shard_count) F(blocks_w) F(block_x0) F(block_y0) F(my_blocks) F(view_jobs) F(view_count) F(refill_below) F(descend_below) F(capL) F(capR) F(long_min) \
