@@ -583,6 +583,71 @@ int ort_render_views_adaptive_device(ort_scene *scene, const ort_render_params *
                                      uint32_t view_count, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states,
                                      void *hip_stream, ort_stats *stats);
 
+/* ---- first-hit feature renders: albedo, normal, depth, coverage and id planes of the camera -----
+ * The noise-free guide planes a denoiser wants next to the colour: what the camera's own samples see FIRST.  A pass of its own on
+ * the pixel's own stream, a raycast per sample instead of a path; through the aperture the planes have the distribution of the
+ * render's samples.
+ * Planes.  Each holds width*height entries per frame with row 0 at the bottom, view_count frames view-major:
+ *    albedo        3 f32 per pixel   mean over spp of the first hit's albedo           (may be NULL)
+ *    normal        3 f32 per pixel   mean over spp of the first hit's unit normal      (may be NULL)
+ *    depth         f32               mean over spp of the first hit's distance         (may be NULL)
+ *    hits          u32               samples that hit a surface; coverage = hits/spp   (may be NULL)
+ *    ids           2 u32: mat, prim  of sample 0                                       (may be NULL)
+ *    final_states  u32               the stream's state after the last sample          (may be NULL)
+ * Pixels outside the rect are left untouched in every plane.
+ * The job.  A job is pixel (x, y) of a frame; its stream starts at job_seed(seed, y*W + x), the ORT_POLICY_PIXEL stream of that
+ * pixel (views[v].seed in the views form).  Sample k = 0 .. spp-1, every operation a separately rounded f32 operation (no FMA):
+ *  - rad = random_between(s, 0, 2 pi): TWO steps of the stream (random.h:47-53);
+ *  - ap, the aperture point of ray.cpp:1233-1234, and d = normalize(focal - ap) of ray.cpp:1237 with focal of ray.cpp:1198 and
+ *    :1215-1221 for that pixel and camera: the render's own expressions in the render's own order;
+ *  - h, the closest hit of the ray (ap, d), exactly the record ort_raycast returns for it: t, the normalised n, mat, prim.  Whatever
+ *    ray comes out gets that query's answer, exact-walk rays included.
+ * Nothing else is drawn: the stream advances exactly 2*spp steps whatever is hit, so final_states does not depend on the scene.
+ * Sums.  A, N and D start at +0.  For every sample with h.mat != 0, in sample order: hits++, A += albedo(h.mat), N += h.n,
+ * D += h.t, each component a separately rounded f32 add.  albedo(m) is materials[m].emit if is_light, else materials[m].diffuse,
+ * as it stands: a mirror or glass surface has its (often zero) diffuse colour.
+ * Outputs.  albedo = A / (float)spp, normal = N / (float)spp, depth = D / (float)spp, component by component (ray.cpp:1428's
+ * division).  hits is the count; a caller who wants the mean over hits divides by coverage.  normal is not re-normalised.  ids =
+ * {h.mat, h.prim} of sample 0; a miss gives 0, ORT_NO_PRIM; ids do not average.  d is a unit vector, so depth is a distance from
+ * the aperture point.
+ * Parameters.  params->policy must be ORT_POLICY_PIXEL; any other policy is ORT_ERR_UNSUPPORTED.  params->spp is within
+ * [1, 1 << 24], so that (float)spp is exact.  params->chunk and params->rr are ignored.  shard_count > 1 and ORT_RENDER_PACKED
+ * return ORT_ERR_UNSUPPORTED.
+ * The views form follows ort_render_views: params->seed is ignored; the per-view seed and camera, the rule where a camera may
+ * stand, ORT_MAX_VIEWS and view_count == 0 (ORT_OK without a launch, whatever the other arguments) are as there.  The single-frame
+ * call is the one-view batch of the scene's own camera (ort_scene_get_camera) and params->seed.
+ * Four identities.  (1) At spp = 1, depth, normal and ids are ort_raycast's t, n, mat, prim for the pixel's first camera ray.
+ * (2) That ray is the first primary ray of the ORT_POLICY_PIXEL render: with rr = 0 and spp = 1, ort_render_image's pixel is emit
+ * of ids.mat if that material is a light, and 0 otherwise.  (3) Frame v of a batch is, in every plane, the single-frame call's
+ * frame for that camera and seed.  (4) Which planes are asked for changes no bit of the others.
+ * Errors are reported before any device work, in ort_render_views_adaptive's order with the planes where ad stands:
+ * ORT_ERR_INVALID (null planes struct, all of the five feature planes NULL, null views, view cap exceeded, null scene or params,
+ * empty or bad params exactly as ort_render_image judges them; then spp above 1 << 24, a plane not 4-byte aligned),
+ * ORT_ERR_UNSUPPORTED (policy, shard, packed, camera outside the box), ORT_ERR_STATE (scene not committed), ORT_ERR_NO_DEVICE (not
+ * uploaded).
+ * The device forms take DEVICE pointers on the scene's device, enqueue on hip_stream (NULL = the default stream) and wait only
+ * when stats != NULL; views and the planes struct are HOST memory in both forms, read before the call returns.  stats follow the
+ * ray queries: with ORT_RENDER_COUNTERS, rays = frames x rect pixels x spp and paths = 0; fallback_rays and kernel_ms are always
+ * filled. */
+typedef struct {
+    float    *albedo;        /* 3 f32 per pixel   may be NULL */
+    float    *normal;        /* 3 f32 per pixel   may be NULL */
+    float    *depth;         /* f32               may be NULL */
+    uint32_t *hits;          /* u32               may be NULL */
+    uint32_t *ids;           /* 2 u32: mat, prim  may be NULL */
+    uint32_t *final_states;  /* u32               may be NULL */
+} ort_feature_planes;        /* HOST pointers in the host forms, DEVICE pointers in the _device forms */
+
+/* host planes in, host planes out (device staging is internal); synchronous */
+int ort_render_features(ort_scene *scene, const ort_render_params *params, const ort_feature_planes *planes, ort_stats *stats);
+int ort_render_features_device(ort_scene *scene, const ort_render_params *params, const ort_feature_planes *planes, void *hip_stream,
+                               ort_stats *stats);
+/* view_count frames per plane, view-major */
+int ort_render_views_features(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
+                              const ort_feature_planes *planes, ort_stats *stats);
+int ort_render_views_features_device(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
+                                     const ort_feature_planes *planes, void *hip_stream, ort_stats *stats);
+
 /* ---- multi-GPU: block sharding and the one collective -------------------------------------
  * Replaces main()'s shared-memory tile pool (macos_main.mm:565-671: eight pthreads, one queue, one framebuffer)
  * across the GPUs of a node: scene replicated, 8x8 blocks dealt round-robin, every rank renders its blocks into a

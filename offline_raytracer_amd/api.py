@@ -117,6 +117,15 @@ VIEW_DTYPE = np.dtype([("camera", "<f4", (4, 3)), ("seed", "<u4")])
 assert VIEW_DTYPE.itemsize == C.sizeof(View) == 52
 
 
+class FeaturePlanes(C.Structure):
+    """ort_feature_planes: where a first-hit feature render writes (ort_render_features); a null pointer is a plane not asked for."""
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("hits", C.c_void_p), ("ids", C.c_void_p),
+                ("final_states", C.c_void_p)]
+
+
+FEATURE_PLANES = ("albedo", "normal", "depth", "hits", "ids", "states")   # render_features()'s want=
+
+
 class Hit(C.Structure):
     """ort_hit: the closest hit of one ray (raycast_top_most_node's hit_t, hit_normal, hit_mat_index) and its shape."""
     _fields_ = [("t", C.c_float), ("n", V3), ("mat", C.c_uint32), ("prim", C.c_uint32)]
@@ -142,7 +151,8 @@ EXPORTS = [
     "ort_radiance_adaptive", "ort_radiance_adaptive_device",
     "ort_irradiance", "ort_irradiance_device", "ort_irradiance_adaptive", "ort_irradiance_adaptive_device",
     "ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes",
-    "ort_render_adaptive", "ort_render_adaptive_device", "ort_render_views_adaptive", "ort_render_views_adaptive_device"]
+    "ort_render_adaptive", "ort_render_adaptive_device", "ort_render_views_adaptive", "ort_render_views_adaptive_device",
+    "ort_render_features", "ort_render_features_device", "ort_render_views_features", "ort_render_views_features_device"]
 
 _lib = None
 
@@ -209,6 +219,8 @@ def lib():
                 ("ort_render_views", [vp, C.POINTER(RenderParams), vp, C.c_uint32, vp, stats]),
                 ("ort_render_adaptive", [vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp, vp, stats]),
                 ("ort_render_views_adaptive", [vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, C.c_uint32, vp, vp, vp, vp, stats]),
+                ("ort_render_features", [vp, C.POINTER(RenderParams), C.POINTER(FeaturePlanes), stats]),
+                ("ort_render_views_features", [vp, C.POINTER(RenderParams), vp, C.c_uint32, C.POINTER(FeaturePlanes), stats]),
                 ("ort_raycast", [vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
                 ("ort_occluded", [vp, vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
                 ("ort_ambient_occlusion", [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint32, stats]),
@@ -546,6 +558,82 @@ class Scene:
         st, stats = _stats(want_stats)
         _check(lib().ort_render_views_adaptive_device(self.handle, C.byref(params), C.byref(ad), views.ctypes.data, len(views),
                                                       _ptr(d_out), _ptr(d_spp), _ptr(d_m2), _ptr(d_states), _ptr(stream), st))
+        return stats()
+
+    # -- first-hit feature renders: albedo, normal, depth, coverage and id planes ---------------
+    @staticmethod
+    def _feature_planes(shape, want, out):
+        """the host planes of a feature render, by name: zeros, or the caller's (out: a dict by the names of want, checked)"""
+        specs = {"albedo": (shape + (3,), "<f4"), "normal": (shape + (3,), "<f4"), "depth": (shape, "<f4"), "hits": (shape, "<u4"),
+                 "ids": (shape + (2,), "<u4"), "states": (shape, "<u4")}
+        want = tuple(want)
+        if not want or len(set(want)) != len(want) or not set(want) <= set(FEATURE_PLANES):
+            raise ValueError("want must name planes of %s, each once, got %r" % (FEATURE_PLANES, want))
+        if out is None:
+            return {k: np.zeros(*specs[k]) for k in want}
+        if set(out) != set(want):
+            raise ValueError("out must hold exactly the planes of want %r, got %r" % (want, tuple(out)))
+        for k in want:
+            a, (sh, dt) = out[k], specs[k]
+            if not isinstance(a, np.ndarray) or a.shape != sh or a.dtype != np.dtype(dt) or not a.flags.c_contiguous:
+                raise ValueError("out[%r] must be a C-contiguous array of shape %s dtype %s" % (k, sh, dt))
+        return dict(out)
+
+    @staticmethod
+    def _feature_struct(ptrs):
+        """name -> pointer (ints, ctypes pointers, None) -> FeaturePlanes"""
+        unknown = set(ptrs) - set(FEATURE_PLANES)
+        if unknown:
+            raise ValueError("unknown feature planes %r: the planes are %s" % (sorted(unknown), FEATURE_PLANES))
+        fp = FeaturePlanes()
+        for k in FEATURE_PLANES:
+            v = _ptr(ptrs.get(k))
+            setattr(fp, "final_states" if k == "states" else k, v.value if isinstance(v, C.c_void_p) else v)
+        return fp
+
+    def render_features(self, width, height, spp, seed, rect=None, want=("albedo", "normal", "depth", "hits", "ids"), counters=False,
+                        out=None):
+        """What the camera's own samples see first, per pixel: the means over spp camera samples (the PIXEL render's aperture
+        draw on the pixel's own stream, then raycast()'s closest hit) of the first hit's albedo (emit of a light, diffuse
+        otherwise), unit normal and distance, the number of samples that hit a surface (coverage = hits / spp), sample 0's
+        (mat, prim) and, with "states" in want, the stream's final state.  Returns (planes, stats dict), planes a dict by
+        the names of want: albedo, normal (H, W, 3) float32, depth (H, W) float32, hits, states (H, W) uint32, ids (H, W, 2)
+        uint32.  Pixels outside rect keep what out's planes held.  Which planes are asked for changes no bit of the others."""
+        planes = self._feature_planes((height, width), want, out)
+        p = self.params(width, height, spp, seed, "pixel", 0, rect, 0.0, counters)
+        fp = self._feature_struct({k: a.ctypes.data for k, a in planes.items()})
+        st, stats = _stats()
+        _check(lib().ort_render_features(self.handle, C.byref(p), C.byref(fp), st))
+        return planes, stats()
+
+    def render_features_device(self, params, stream=None, want_stats=False, **d_planes):
+        """The same into device planes: albedo=, normal=, depth=, hits=, ids=, states= raw device pointers (e.g. torch tensors'
+        data_ptr()), those not given are not written.  params: Scene.params(..., policy="pixel"); its chunk and rr are ignored.
+        Enqueued on stream; waits only when want_stats (returns the stats dict)."""
+        fp = self._feature_struct(d_planes)
+        st, stats = _stats(want_stats)
+        _check(lib().ort_render_features_device(self.handle, C.byref(params), C.byref(fp), _ptr(stream), st))
+        return stats()
+
+    def render_views_features(self, cameras, seeds, width, height, spp, rect=None, want=("albedo", "normal", "depth", "hits", "ids"),
+                              counters=False, out=None):
+        """render_features for a batch of views in one launch (cameras, seeds as render_views): frame v is what render_features
+        gives with seed seeds[v] if the scene's camera were cameras[v].  Every plane has a leading axis of V frames."""
+        views = _views(cameras, seeds)
+        planes = self._feature_planes((len(views), height, width), want, out)
+        p = self.params(width, height, spp, 0, "pixel", 0, rect, 0.0, counters)
+        fp = self._feature_struct({k: a.ctypes.data for k, a in planes.items()})
+        st, stats = _stats()
+        _check(lib().ort_render_views_features(self.handle, C.byref(p), views.ctypes.data, len(views), C.byref(fp), st))
+        return planes, stats()
+
+    def render_views_features_device(self, params, cameras, seeds, stream=None, want_stats=False, **d_planes):
+        """The same into device planes of V frames each, view-major.  Enqueued on stream; waits only when want_stats (returns
+        the stats dict).  params.seed is ignored."""
+        views = _views(cameras, seeds)
+        fp = self._feature_struct(d_planes)
+        st, stats = _stats(want_stats)
+        _check(lib().ort_render_views_features_device(self.handle, C.byref(params), views.ctypes.data, len(views), C.byref(fp), _ptr(stream), st))
         return stats()
 
     # -- closest-hit ray queries -----------------------------------------------------------

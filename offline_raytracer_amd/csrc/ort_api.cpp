@@ -565,6 +565,46 @@ static int render_adaptive_common(ort_scene *s, const ort_render_params *p, cons
     return run_render(s, &q, c, out_rgb, out_spp, out_m2, states);
 }
 
+/* First-hit feature renders, one frame or a batch of views: render_adaptive_common's order with the planes where ad stands.
+   view_count == 0 is OK whatever else is passed (the views form); then nulls (the planes struct, all five feature planes, views) and
+   the view cap, the params as the render call judges them (chunk and rr are not the caller's to set here), spp above 1 << 24 and the
+   planes' alignment, what the call does not do (any policy but PIXEL, shards, a packed framebuffer, a camera outside the box), the
+   scene's state.  !batch: the single-frame form (views unread), the one-view batch of the scene's own camera and params->seed */
+static int render_features_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool batch, bool host,
+                                  const ort_feature_planes *planes, void *stream, ort_stats *stats) {
+    if (batch && view_count == 0) return nothing_to_do(stats);
+    if (!planes) return fail(ORT_ERR_INVALID, "null planes");
+    if (!planes->albedo && !planes->normal && !planes->depth && !planes->hits && !planes->ids)
+        return fail(ORT_ERR_INVALID, "no feature plane is asked for: albedo, normal, depth, hits and ids are all null");
+    if (batch && !views) return fail(ORT_ERR_INVALID, "null views");
+    if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
+    if (!s || !p) return fail(ORT_ERR_INVALID, "null scene or params");
+    ort_render_params q = *p;
+    q.chunk = q.spp;
+    q.rr = 0.0f;
+    int rc = check_param_values(s, &q);
+    if (rc != ORT_OK) return rc;
+    if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp must be <= 1 << 24: a sample count must be exact in float");
+    rc = check_ptrs({{planes->albedo, false, 4}, {planes->normal, false, 4}, {planes->depth, false, 4}, {planes->hits, false, 4}, {planes->ids, false, 4},
+                     {planes->final_states, false, 4}}, "", "", "albedo, normal, depth, hits, ids and final_states must be 4-byte aligned");
+    if (rc != ORT_OK) return rc;
+    if (q.policy != ORT_POLICY_PIXEL) return fail(ORT_ERR_UNSUPPORTED, "the feature render cuts one-pixel jobs: it needs the PIXEL policy");
+    if (q.shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, "the feature render is not sharded");
+    if (q.flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "the feature render has no packed planes");
+    ort_view own;
+    if (batch) {
+        if ((rc = check_views_in_box(s, views, view_count)) != ORT_OK) return rc;
+    } else {
+        ort::camera_basis(*s, q.width, q.height, &own.camera);
+        own.seed = q.seed;
+        views = &own;
+    }
+    if ((rc = check_resident(s)) != ORT_OK) return rc;
+    std::string err;
+    rc = ort::device_render_features(s, &q, views, view_count, {host, 0, q.flags, stream, stats}, *planes, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
 static int ort_render_views_workspace_bytes_impl(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) {
     if (!p || !bytes) return fail(ORT_ERR_INVALID, "null argument");
     *bytes = ort::render_views_workspace_bytes(p, view_count);
@@ -684,6 +724,10 @@ int ort_render_adaptive(ort_scene *s, const ort_render_params *p, const ort_adap
 int ort_render_adaptive_device(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, nullptr, 1, false, false, d_out_rgb, d_out_spp, d_out_m2, d_final_states, hip_stream, stats); }); }
 int ort_render_views_adaptive(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, const ort_view *views, uint32_t view_count, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, views, view_count, true, true, out_rgb, out_spp, out_m2, final_states, nullptr, stats); }); }
 int ort_render_views_adaptive_device(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, const ort_view *views, uint32_t view_count, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, views, view_count, true, false, d_out_rgb, d_out_spp, d_out_m2, d_final_states, hip_stream, stats); }); }
+int ort_render_features(ort_scene *s, const ort_render_params *p, const ort_feature_planes *planes, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, nullptr, 1, false, true, planes, nullptr, stats); }); }
+int ort_render_features_device(ort_scene *s, const ort_render_params *p, const ort_feature_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, nullptr, 1, false, false, planes, hip_stream, stats); }); }
+int ort_render_views_features(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_feature_planes *planes, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, views, view_count, true, true, planes, nullptr, stats); }); }
+int ort_render_views_features_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_feature_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, views, view_count, true, false, planes, hip_stream, stats); }); }
 int ort_render_views_workspace_bytes(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) { return guarded([&]() { return ort_render_views_workspace_bytes_impl(p, view_count, bytes); }); }
 int ort_shard_block_count(int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, uint64_t *blocks) { return guarded([&]() { return ort_shard_block_count_impl(width, height, shard_index, shard_count, blocks); }); }
 int ort_pack_blocks_host(const float *full_rgb, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, float *packed) { return guarded([&]() { return ort_pack_blocks_host_impl(full_rgb, width, height, shard_index, shard_count, packed); }); }

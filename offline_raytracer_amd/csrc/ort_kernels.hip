@@ -602,13 +602,14 @@ static RaycastIO ray_query_io(Scene *scene, DeviceScene *d, const void *rays) {
 /* One launch of a ray query over count rays.  rv holds what the query's lanes read behind hot.c besides the policy (nothing for
    raycast_rays and occluded_rays, radiance_view for radiance_rays); issue(sv, hot, plan) enqueues the kernel the plan names.
    stats (may be NULL): synchronous, the launch's time and counters added (radiance: the primary rays traced as paths) */
-template <typename Issue>
-static int launch_query(Scene *scene, DeviceScene *d, RenderView rv, uint64_t count, bool radiance, bool counters, hipStream_t stream, ort_stats *stats,
-                        std::string *err, Issue issue) {
+template <typename Plan, typename Issue>
+static int launch_planned(Scene *scene, DeviceScene *d, RenderView rv, uint64_t count, Plan plan, bool radiance, hipStream_t stream, ort_stats *stats,
+                          std::string *err, Issue issue) {
     int rc;
     if ((rc = settle_inflight(d, err))) return rc;
     const SceneView sv = scene_view(scene, d);
-    const QueryPlan pl = radiance ? plan_radiance(scene_traits(scene, d), count, counters, d->knobs) : plan_ray_query(scene_traits(scene, d), count, counters);
+    const QueryPlan pl = plan(scene_traits(scene, d), d->knobs); /* after scene_view: under ORT_KNOBS_LIVE it reads the knobs again */
+    const bool counters = pl.counters;
     rv.job_count = count; /* the job space: the ray array, drawn in batches */
     rv.job_batch = pl.job_batch; rv.batch_until = pl.batch_until;
     rv.refill_below = pl.refill_below; rv.descend_below = pl.descend_below;
@@ -619,6 +620,14 @@ static int launch_query(Scene *scene, DeviceScene *d, RenderView rv, uint64_t co
     /* with stats, wait for it and add its time and counters */
     if (stats && ((rc = settle_inflight(d, err)) || (rc = add_launch_stats(d, counters, radiance, stats, err)))) return rc;
     return ORT_OK;
+}
+/* ... by the plan of the ray queries (plan_ray_query) or the radiance queries (plan_radiance) over count rays.  launch_planned
+   takes the plan as a function of the traits and the knobs, to call once the knobs are this call's */
+template <typename Issue>
+static int launch_query(Scene *scene, DeviceScene *d, const RenderView &rv, uint64_t count, bool radiance, bool counters, hipStream_t stream, ort_stats *stats,
+                        std::string *err, Issue issue) {
+    return launch_planned(scene, d, rv, count, [&](const SceneTraits &t, const Knobs &kn) { return radiance ? plan_radiance(t, count, counters, kn) : plan_ray_query(t, count, counters); },
+                          radiance, stream, stats, err, issue);
 }
 
 /* One array of the host form of a query: `bytes` per ray between the caller's memory and a staging buffer of the scene, towards
@@ -762,6 +771,56 @@ int device_ambient_occlusion(Scene *scene, const QueryCall &q, const void *point
             }, pl.counters, pl.tabs);
         });
     });
+}
+
+/* first-hit feature renders: view_count frames of p's rect -> the planes asked for.  The planes are frames, not arrays over the
+   jobs, so the host form stages them as device_render stages its own -- whole, both ways, plane i through the scene's i-th query
+   staging buffer -- and the launch is one; the camera table is device_render's too (pack_view_table, the scene's view_tab).  The
+   launch goes through the queries' one path by plan_features (ort_plan.h) */
+int device_render_features(Scene *scene, const ort_render_params *p, const ort_view *views, uint32_t view_count, const QueryCall &q,
+                           const ort_feature_planes &planes, std::string *err) {
+    DeviceScene *d;
+    int rc;
+    if ((rc = begin_query(scene, q.stats, &d, err)) || (rc = ensure_prim_src(scene, d, err))) return rc;
+    hipStream_t stream = (hipStream_t)q.stream;
+    /* the staging buffers and both copies of the camera table are the previous call's until that has finished */
+    if ((rc = settle_inflight(d, err))) return rc;
+    const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
+    struct Plane { void *caller; size_t bytes; void *dev; };
+    Plane pn[6] = {{planes.albedo, pixels * 12u, nullptr}, {planes.normal, pixels * 12u, nullptr}, {planes.depth, pixels * 4u, nullptr},
+                   {planes.hits, pixels * 4u, nullptr}, {planes.ids, pixels * 8u, nullptr}, {planes.final_states, pixels * 4u, nullptr}};
+    static_assert(sizeof(pn) / sizeof(pn[0]) <= sizeof(d->query_stage) / sizeof(d->query_stage[0]), "one staging buffer per plane");
+    for (size_t i = 0; i < 6; ++i) {
+        pn[i].dev = pn[i].caller;
+        if (!q.host || !pn[i].caller) continue;
+        if ((rc = d->query_stage[i].ensure(pn[i].bytes, err))) return rc;
+        pn[i].dev = d->query_stage[i].p;
+        ORT_HIP(hipMemcpyAsync(pn[i].dev, pn[i].caller, pn[i].bytes, hipMemcpyHostToDevice, stream));
+    }
+    std::vector<float> &tab = d->view_tab_host; /* the caller's array is read here and not again */
+    pack_view_table(views, view_count, tab);
+    if ((rc = d->view_tab.ensure(tab.size() * sizeof(float), err))) return rc;
+    ORT_HIP(hipMemcpyAsync(d->view_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    RenderView rv{};
+    features_view(*p, view_count, &rv);
+    rv.views = d->view_tab.as<const float4>();
+    FeatureIO io{};
+    io.q = ray_query_io(scene, d, nullptr);
+    io.q.prim_src = d->prim_src.as<const uint32_t>();
+    io.albedo = (float *)pn[0].dev; io.normal = (float *)pn[1].dev; io.depth = (float *)pn[2].dev;
+    io.hits = (uint32_t *)pn[3].dev; io.ids = (uint32_t *)pn[4].dev; io.states = (uint32_t *)pn[5].dev;
+    const bool counters = (q.flags & ORT_RENDER_COUNTERS) != 0;
+    auto planner = [&](const SceneTraits &t, const Knobs &kn) { return plan_features(t, *p, view_count, counters, kn); };
+    rc = launch_planned(scene, d, rv, rv.job_count, planner, false, stream, q.stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &plan) {
+        with_bools([&](auto C, auto T) {
+            hipLaunchKernelGGL((feature_pixels<decltype(C)::value, decltype(T)::value>), dim3(plan.grid), dim3(kBlock), 0, stream, sv, hot, io);
+        }, plan.counters, plan.tabs);
+    });
+    if (rc || !q.host) return rc;
+    for (const Plane &x : pn)
+        if (x.caller) ORT_HIP(hipMemcpyAsync(x.caller, x.dev, x.bytes, hipMemcpyDeviceToHost, stream));
+    ORT_HIP(hipStreamSynchronize(stream));
+    return settle_inflight(d, err);
 }
 
 /* radiance: count rays with their seeds -> 3 floats each and, where asked for (states may be null), the final states.  No shape

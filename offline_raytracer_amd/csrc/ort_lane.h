@@ -229,6 +229,18 @@ struct AoIO {
     uint32_t mats_nonzero;  /* no shape of the scene carries material 0 (the early end, as occluded_lane's) */
 };
 
+/* the third argument of feature_pixels: the planes of ort_render_features, view_count frames of W * H entries each, view-major.
+   The job space, the rect, spp and the camera table are the RenderView's (features_view, ort_setup.h) */
+struct FeatureIO {
+    RaycastIO q;            /* q.prim_src, and what raycast_needs_exact reads.  rays and hits are null */
+    float *albedo;          /* 3 per pixel, or null */
+    float *normal;          /* 3 per pixel, or null */
+    float *depth;           /* 1 per pixel, or null */
+    uint32_t *hits;         /* 1 per pixel, or null: samples that hit a surface */
+    uint32_t *ids;          /* 2 per pixel, or null: mat, prim of sample 0 */
+    uint32_t *states;       /* 1 per pixel, or null: the stream after 2 * spp steps */
+};
+
 } // namespace ort
 
 #ifndef ORT_HOST_SIM
@@ -2630,6 +2642,130 @@ ao_points(SceneView sv, RenderHot rv, AoIO io) {
     __shared__ float lds_job[kAoCacheWords * kBlock]; /* the job's state that is touched once per sample (ao_lane) */
     if (TABS) fill_tab(sv, lds_tab);
     ao_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, lds_job + threadIdx.x, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+}
+#endif
+
+/* ---- first-hit feature renders (ort_render_features): albedo, normal, depth, coverage and id planes of the camera ---------
+ * A job is pixel (x, y) of a frame of the batch; its spp samples run on the PIXEL policy's stream of that pixel, job_seed(the
+ * view's seed, y * W + x).  A sample is the render's own camera sample (produce_ray: rng_between for the aperture angle -- two
+ * steps of the stream --, the deterministic sin/cos, view_aperture_point, normalize(focal - ap)) and then raycast_lane's ray
+ * (ap, d): begin_ray, raycast_needs_exact, the walk with refill_below, resolve_hit, normalize(n), prim_src.  A sample that hits
+ * a surface (mat != 0) counts and adds the material's albedo (emit of a light, diffuse otherwise), n and t to the job's sums,
+ * each component a separately rounded add in sample order; the job ends with the sums divided by (float)spp.  Sample 0 also
+ * names the pixel's ids.  Nothing else is drawn: the stream advances 2 * spp steps whatever is hit.
+ * THE JOB SPACE is [view][8x8 block of the rect][pixel in block], as the PIXEL render's implicit one (produce_ray): a wave's
+ * jobs are one block -- coherent primary rays, and plane stores that coalesce.  A pixel of an edge block outside the rect is
+ * a job that ends where it is drawn.
+ * WHERE A SAMPLE STARTS is ao_lane's answer: the idle lanes first settle the finished sample's sums, the job's end and the
+ * next pixel, and then meet at ONE converged ort_sincosf per pass of the outer loop.
+ * WHERE THE JOB'S STATE LIVES.  The seven sums are touched once per sample and never inside the walk: seven per-lane LDS words
+ * (job_cache: word k of a lane at job_cache[k * kBlock]), as ao_lane keeps its six.  The hit count, the stream, the pixel and
+ * the view stay in registers.  The view's camera is read from the table at every sample's start (load_view_camera) and the
+ * focal point recomputed there -- the render's expressions in the render's order, so the same bits -- instead of either being
+ * held through the walk.  The ids go straight to memory at sample 0 (profiles/r18_features.md). */
+constexpr int kFeatureCacheWords = 7; /* albedo.xyz, normal.xyz, depth */
+
+template <bool COUNTERS, bool TABS>
+ORT_D void feature_lane(const SceneView &sv, const RenderHot &rv, const FeatureIO &io, const float4 *tab, uint32_t *lds_stack, float *job_cache, const int tid,
+                        const uint32_t lane_id, unsigned long long *pool) {
+    uint32_t spill[kSpillStack];
+    PathState P; /* org, dir; rng; pxy; job_index: the view; sample: the samples of this pixel started so far */
+    HitState h;
+    Trav T;
+    Counters c;
+    Prof pr;
+    const uint32_t spp = rv.c->spp;
+    uint32_t hits = 0;
+    bool tracing = false, held = false, busy = false, more = true; /* held: as raycast_lane's; busy: this lane owns a pixel */
+    for (;;) {
+        if (!tracing) {
+            if (held) { /* the finished sample: raycast_lane's record, into the sums */
+                resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+                if (P.sample == 1u && io.ids) {
+                    const uint32_t src = h.hit_prim != kNoPrim ? io.q.prim_src[info_index(sv, h.hit_prim)] : kNoPrim;
+                    const size_t at = ((size_t)P.job_index * (size_t)rv.H + (P.pxy >> 16)) * (size_t)rv.W + (P.pxy & 0xffffu);
+                    io.ids[2u * at] = h.hit_mat;
+                    io.ids[2u * at + 1u] = src;
+                }
+                if (h.hit_mat != 0u) {
+                    Mat m;
+                    if (TABS) m = load_mat(tab + kTabMats, h.hit_mat);
+                    else m = load_mat(sv.materials, h.hit_mat);
+                    const V3 a = m.is_light ? m.emit : m.kd;
+                    const V3 n = normalize(h.hit_n); /* ray.cpp:817, as raycast_lane returns it */
+                    hits++;
+                    job_cache[0] = job_cache[0] + a.x; job_cache[kBlock] = job_cache[kBlock] + a.y; job_cache[2 * kBlock] = job_cache[2 * kBlock] + a.z;
+                    job_cache[3 * kBlock] = job_cache[3 * kBlock] + n.x; job_cache[4 * kBlock] = job_cache[4 * kBlock] + n.y; job_cache[5 * kBlock] = job_cache[5 * kBlock] + n.z;
+                    job_cache[6 * kBlock] = job_cache[6 * kBlock] + h.best_t;
+                }
+                held = false;
+            }
+            bool start = false;
+            for (;;) { /* the job's end and the next pixel */
+                if (busy) {
+                    if (P.sample < spp) { start = true; break; }
+                    const size_t at = ((size_t)P.job_index * (size_t)rv.H + (P.pxy >> 16)) * (size_t)rv.W + (P.pxy & 0xffffu);
+                    const float fs = (float)spp; /* ray.cpp:1428's division, component by component */
+                    if (io.albedo) { float *o = io.albedo + 3u * at; o[0] = job_cache[0] / fs; o[1] = job_cache[kBlock] / fs; o[2] = job_cache[2 * kBlock] / fs; }
+                    if (io.normal) { float *o = io.normal + 3u * at; o[0] = job_cache[3 * kBlock] / fs; o[1] = job_cache[4 * kBlock] / fs; o[2] = job_cache[5 * kBlock] / fs; }
+                    if (io.depth) io.depth[at] = job_cache[6 * kBlock] / fs;
+                    if (io.hits) io.hits[at] = hits;
+                    if (io.states) io.states[at] = P.rng;
+                    busy = false;
+                }
+                if (!more) break;
+                const unsigned long long j = pool ? draw_job(rv, pool) : ORT_NEXT_JOB(rv.c->next_job);
+                if (!(j < rv.c->job_count)) { more = false; break; }
+                const uint32_t view = (uint32_t)(j / rv.c->view_jobs), within = (uint32_t)(j % rv.c->view_jobs);
+                const uint32_t lb = within >> 6, pin = within & 63u;
+                const int x = (int)((rv.c->block_x0 + lb % rv.c->blocks_w) * 8u + (pin & 7u));
+                const int y = (int)((rv.c->block_y0 + lb / rv.c->blocks_w) * 8u + (pin >> 3));
+                if (x < rv.c->x0 || x >= rv.c->x1 || y < rv.c->y0 || y >= rv.c->y1) continue;
+                P.job_index = view;
+                P.pxy = (uint32_t)x | ((uint32_t)y << 16);
+                P.rng = job_seed(om_f32_bits(rv.c->views[4u * (size_t)view].w), (uint32_t)(y * rv.W + x));
+                P.sample = 0;
+                hits = 0;
+                for (int k = 0; k < kFeatureCacheWords; ++k) job_cache[k * kBlock] = 0.0f;
+                busy = true;
+            }
+            if (start) { /* the camera sample, as produce_ray composes it: one converged sin/cos for the lanes that start a sample */
+                const ViewCamera cam = load_view_camera(rv, P.job_index);
+                const V3 focal = view_focal_point(rv, P.pxy, cam);
+                const float angle = rng_between(P.rng, 0.0f, 2 * kPi); /* ray.cpp:1232 */
+                float sn, cs;
+                ort_sincosf(angle, &sn, &cs);
+                P.org = view_aperture_point(cam, 0.1f, cs, sn); /* ray.cpp:1199, :1233-1234 */
+                P.dir = normalize(sub(focal, P.org));           /* ray.cpp:1237 */
+                P.sample++;
+                begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
+                if (ORT_RARE(raycast_needs_exact(io.q, P.org, P.dir, T.inv_d))) {
+                    T.cur = kTraversalDone; /* no fast traversal: resolve_hit re-casts it exactly (a phantom that could win) */
+                    h.phantom_t = 0.0f;
+                }
+                if (COUNTERS) c.rays++;
+                tracing = held = true;
+            }
+        }
+        /* a lane that neither traces, owns a pixel nor is entitled to another draw has none and will get none */
+        if (ORT_BALLOT(tracing || busy || more) == 0ull) break;
+        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS, true>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+    }
+    flush_counters(rv, c, COUNTERS);
+}
+
+/* TABS: the prologue shapes AND the materials fit their LDS slots (TAB_PRO, TAB_MATS: plan_features, ort_plan.h); otherwise both
+   are read from HBM */
+#ifndef ORT_HOST_SIM
+template <bool COUNTERS, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+feature_pixels(SceneView sv, RenderHot rv, FeatureIO io) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    __shared__ float lds_job[kFeatureCacheWords * kBlock]; /* the job's sums (feature_lane) */
+    if (TABS) fill_tab(sv, lds_tab);
+    feature_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, lds_job + threadIdx.x, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 #endif
 

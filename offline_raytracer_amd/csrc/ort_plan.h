@@ -482,6 +482,25 @@ inline QueryPlan plan_ray_query(const SceneTraits &t, uint64_t count, bool count
     return pl;
 }
 
+/* The launch of a first-hit feature render (ort_render_features and its views forms; the feature_pixels kernels): the job space
+   is [view][8x8 block under the rect][pixel in block], a job is spp camera samples of one pixel, each one ray of ort_raycast.
+   plan_ray_query over those jobs (the grid, the refill and descend thresholds: the walk is that query's), with two differences:
+   - these lanes read the materials too, so tabs asks for both the prologue's table and the materials' (TAB_PRO and TAB_MATS); a
+     scene past either cap reads both from HBM;
+   - a job is a PIXEL job of the render, spp samples long and one of an 8x8 block's 64, not one ray of a long array: the batches
+     are the render's (plan_job_batches: a block at a time, ORT_JOB_BATCH and ORT_BATCH_TAIL read).  plan_ray_query's 1024 indices
+     per draw hand a full HD frame -- eight jobs per lane -- to the first quarter of the waves, sixteen jobs a lane, before its
+     tail rule starts: measured at 1920 x 1080 x 16 spp, 3.5 / 10.8 / 11.0 ms against 1.4 / 4.0 / 2.8 ms on the analytic scene, the
+     bunny room and the dwarf room (profiles/r18_features.md). */
+inline unsigned long long feature_view_jobs(const ort_render_params &p) { return (unsigned long long)block_grid_for(&p).my_blocks * 64ull; }
+inline QueryPlan plan_features(const SceneTraits &t, const ort_render_params &p, uint32_t view_count, bool counters, const Knobs &kn) {
+    const unsigned long long count = feature_view_jobs(p) * view_count;
+    QueryPlan pl = plan_ray_query(t, count, counters);
+    pl.tabs = (t.tab_flags & (kPlanTabPro | kPlanTabMats)) == (kPlanTabPro | kPlanTabMats);
+    plan_job_batches(count, (unsigned long long)pl.grid * kPlanBlock, kn, &pl.job_batch, &pl.batch_until);
+    return pl;
+}
+
 /* The launch of a radiance query over count rays (ort_radiance; the radiance_rays kernels): always the plain persistent loop at
    four waves.  The ray exchange, the five-waves unit, the wide tree and wavefront mode are not built with a ray job space and
    their knobs are not looked at; ORT_DEBUG_UTIL has no probes here.  diffuse, tabs, the refill and descend thresholds and the

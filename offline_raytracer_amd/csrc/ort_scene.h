@@ -257,6 +257,12 @@ int device_ambient_occlusion(Scene *scene, const QueryCall &q, const void *point
    place, and every sample's direction is drawn about n */
 int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const void *seeds, uint32_t spp, float rr, const ort_adaptive *ad, void *out,
                     void *out_spp, void *out_m2, void *states, bool points, std::string *err);
+/* first-hit feature renders: view_count frames of p's rect (checked by the caller: PIXEL, no shards, not packed), view v from
+   views[v].camera on views[v].seed, p->spp camera samples a pixel -> the planes asked for (null otherwise), view-major.  q.count is
+   unread.  The host form stages every plane whole both ways, as device_render does, so that pixels outside the rect keep what they
+   held */
+int device_render_features(Scene *scene, const ort_render_params *p, const ort_view *views, uint32_t view_count, const QueryCall &q,
+                           const ort_feature_planes &planes, std::string *err);
 /* ort_comm.cpp */
 struct Comm;
 uint64_t comm_shard_blocks(int32_t w, int32_t h, uint32_t index, uint32_t count);

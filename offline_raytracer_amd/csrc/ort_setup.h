@@ -186,6 +186,22 @@ inline void render_view(const ort_render_params &p, const LaunchPlan &pl, const 
     rv->job_batch = pl.job_batch; rv->batch_until = pl.batch_until;
 }
 
+/* first-hit feature renders: what feature_lane reads behind hot.c besides the launch policy and the camera table's pointer -- the
+   frame, the rect, the 8x8 blocks under it, spp, and the job space [view][block][pixel in block] (plan_features, ort_plan.h) */
+template <typename View>
+inline void features_view(const ort_render_params &p, uint32_t view_count, View *rv) {
+    const BlockGrid g = block_grid_for(&p);
+    rv->mode = PLAN_JOBS_PIXEL;
+    rv->W = p.width; rv->H = p.height;
+    rv->x0 = p.x0; rv->y0 = p.y0; rv->x1 = p.x1; rv->y1 = p.y1;
+    rv->spp = p.spp;
+    rv->shard_count = g.shard_count; rv->shard_index = g.shard_index;
+    rv->blocks_w = g.blocks_w; rv->block_x0 = g.block_x0; rv->block_y0 = g.block_y0;
+    rv->my_blocks = g.my_blocks;
+    rv->view_jobs = feature_view_jobs(p); rv->view_count = view_count;
+    rv->job_count = rv->view_jobs * view_count;
+}
+
 /* runtime bools to template arguments: f(std::bool_constant...) with one constant per bool, true first at every level */
 template <typename F>
 inline void with_bools(F f) { f(); }

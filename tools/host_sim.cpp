@@ -31,6 +31,9 @@
  *   or: host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
  *       (the adaptive camera render of the scene's own camera: pt_lane<..., VIEWS, ADAPT> over a one-view batch; the planes start
  *       at the guard values -7.0f, 0xeeeeeeee, -1.0f, 0xdddddddd, which pixels outside the rect keep)
+ *   or: host_sim --features scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|-
+ *       (the first-hit feature render, feature_lane: a batch of views, or with cams - the scene's own camera on the seed given; a
+ *       plane given as - is not passed; the planes start at -7.0f, 0xeeeeeeee and, the states, 0xdddddddd)
  * Every mode prints, per instantiation of traverse, how deep the per-lane stack got ("stack: lds 24 deepest ..."; tests/host_sim_tool.py
  * stack_probe reads it); make host_sim_w5 builds the same tool with the five-waves unit's split of that stack (20 + 44 entries).
  * All files raw little-endian.  SIM_TABS=1: the TABS = true lane code, on a heap copy of the LDS tables' image.
@@ -552,8 +555,71 @@ static int render_adaptive_mode(char **a) { /* scn base W H x0 y0 x1 y1 seed min
            write_bytes(a[18], states.data(), 4 * n) ? 0 : 1;
 }
 
+/* the first-hit feature render (ort_render_features and its views form): what device_render_features sets up for it, for one
+   simulated lane per thread.  cams - : the single-frame form, the scene's own camera on the seed given where the seeds file stands.
+   A plane given as - is one the caller did not pass; every word of a plane starts as a filler that a pixel outside the rect keeps */
+static int features_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|- */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_MATS)) return rc;
+    const int W = atoi(a[4]), H = atoi(a[5]), x0 = atoi(a[6]), y0 = atoi(a[7]), x1 = atoi(a[8]), y1 = atoi(a[9]);
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || x0 < 0 || y0 < 0 || x1 > W || y1 > H || x0 >= x1 || y0 >= y1) { fprintf(stderr, "bad frame size or rect\n"); return 1; }
+    const uint32_t spp = (uint32_t)strtoul(a[10], 0, 10);
+    if (spp == 0u || spp > (1u << 24)) { fprintf(stderr, "spp must be within [1, 1 << 24]\n"); return 1; }
+    std::vector<ort_view> views;
+    if (std::string(a[2]) == "-") {
+        views.resize(1);
+        camera_basis(*S.scene, W, H, &views[0].camera);
+        views[0].seed = (uint32_t)strtoul(a[3], 0, 10);
+    } else {
+        std::vector<unsigned char> cb;
+        if (!read_bytes(a[2], cb)) return 1;
+        if (cb.empty() || cb.size() % 48u) { fprintf(stderr, "%s: not a whole, positive number of 48-byte cameras\n", a[2]); return 1; }
+        std::vector<uint32_t> seeds;
+        if (!read_array(a[3], seeds, cb.size() / 48u, "seeds")) return 1;
+        views.resize(seeds.size());
+        for (size_t v = 0; v < views.size(); ++v) { memcpy(&views[v].camera, &cb[48u * v], 48); views[v].seed = seeds[v]; }
+    }
+    const uint32_t nv = (uint32_t)views.size();
+    std::vector<float> tab_host; /* the camera table, 16-byte aligned for the lanes' float4 reads */
+    pack_view_table(views.data(), nv, tab_host);
+    std::vector<float4> view_tab(4u * nv);
+    memcpy(view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
+    std::vector<uint32_t> src;
+    if (!invert_prim_slots(S.scene->tree, S.sv.info_box, S.sv.info_cyl, S.sv.info_sphere, src)) { fprintf(stderr, "the tree's slot maps are not a bijection onto its shape arrays\n"); return 1; }
+    bool want[6];
+    for (int k = 0; k < 6; ++k) want[k] = std::string(a[11 + k]) != "-";
+    const size_t n = (size_t)nv * W * H; /* exactly: a write past a plane's end is a write past the block */
+    std::vector<float> albedo(want[0] ? 3 * n : 0, -7.0f), normal(want[1] ? 3 * n : 0, -7.0f), depth(want[2] ? n : 0, -7.0f);
+    std::vector<uint32_t> hits(want[3] ? n : 0, 0xeeeeeeeeu), ids(want[4] ? 2 * n : 0, 0xeeeeeeeeu), states(want[5] ? n : 0, 0xddddddddu);
+    ort_render_params p{};
+    p.width = W; p.height = H; p.x0 = x0; p.y0 = y0; p.x1 = x1; p.y1 = y1;
+    p.policy = ORT_POLICY_PIXEL; p.spp = spp;
+    float lo[3], hi[3];
+    scene_origin_box(*S.scene, lo, hi);
+    FeatureIO io{};
+    ray_query_io(*S.scene, lo, hi, &io.q);
+    io.q.prim_src = src.data();
+    io.albedo = want[0] ? albedo.data() : nullptr; io.normal = want[1] ? normal.data() : nullptr; io.depth = want[2] ? depth.data() : nullptr;
+    io.hits = want[3] ? hits.data() : nullptr; io.ids = want[4] ? ids.data() : nullptr; io.states = want[5] ? states.data() : nullptr;
+    RenderView rv{};
+    features_view(p, nv, &rv);
+    rv.views = view_tab.data();
+    const RenderHot hot = query_hot(S, rv, (size_t)rv.job_count);
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
+        std::vector<float> job((kFeatureCacheWords - 1) * kBlock + 1); /* exactly: a word beyond the lane's seven is a write past the block */
+        if (S.tab) feature_lane<true, true>(sv, hot, io, S.tab, stack, job.data(), 0, w, nullptr);
+        else feature_lane<true, false>(sv, hot, io, nullptr, stack, job.data(), 0, w, nullptr);
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return (!want[0] || write_bytes(a[11], albedo.data(), 12 * n)) && (!want[1] || write_bytes(a[12], normal.data(), 12 * n)) &&
+           (!want[2] || write_bytes(a[13], depth.data(), 4 * n)) && (!want[3] || write_bytes(a[14], hits.data(), 4 * n)) &&
+           (!want[4] || write_bytes(a[15], ids.data(), 8 * n)) && (!want[5] || write_bytes(a[16], states.data(), 4 * n)) ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
+    if (argc == 19 && mode == "--features") return features_mode(argv + 2);
     if (argc == 4 && mode == "--unit") return unit_mode(argv[2], argv[3]);
     if (argc == 6 && mode == "--raycast") return raycast_mode(argv + 2);
     if (argc == 7 && mode == "--occluded") return occluded_mode(argv + 2);
@@ -575,7 +641,8 @@ int main(int argc, char **argv) {
                         "       host_sim --irradiance scn base points.f32 seeds.u32 spp rr out.f32 states.u32\n"
                         "       host_sim --irradiance-adaptive scn base points.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
                         "       host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32\n"
-                        "       host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n");
+                        "       host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
+                        "       host_sim --features scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|-\n");
         return 2;
     }
     int W = atoi(argv[3]), H = atoi(argv[4]);
