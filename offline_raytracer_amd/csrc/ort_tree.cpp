@@ -103,7 +103,7 @@ struct Builder {
     std::vector<TriRef> tri_refs;
     Tree *tree;
     static constexpr int kBins = 16;
-    uint32_t kMaxLeafTri = 4;   /* tuning knobs (env ORT_LEAF_TRI / ORT_LEAF_OTHER); results do not depend on them */
+    uint32_t kMaxLeafTri = 4;   /* tuning knobs (env ORT_LEAF_TRI / ORT_LEAF_OTHER); results do not depend on them: tests/test_tree_shapes_host.py, tests/test_gpu_tree_shapes.py */
     uint32_t kMaxLeafOther = 2;
     static constexpr uint32_t kDepthBudget = kTreeDepthBudget; /* ort_scene.h: the kernels' smallest traversal stack */
 
@@ -571,7 +571,8 @@ int build_tree(Scene *scene, std::string *err) {
             (void)b.emit_leaf(i, i + 1);
             (b.prims[i].kind == PRIM_BOX ? tree->pro_boxes : b.prims[i].kind == PRIM_SPHERE ? tree->pro_spheres : tree->pro_cyls)++;
         }
-        tree->leaf_count = 0;
+        tree->leaf_count = 0; /* the prologue's shapes went through emit_leaf for their records alone: they are no leaves */
+        tree->max_leaf_prims = 0;
         const uint32_t n_all = (uint32_t)b.prims.size();
         uint32_t root;
         if (n_pro == n_all) { /* nothing left for the tree */

@@ -9,7 +9,7 @@ What is committed is data only: inputs and the reference's outputs.
   ref_det   = reference + deterministic libm (oracle/det_math.h)  -> bit-exact anchor
   ref_glibc = reference + glibc libm, "as shipped" on this box     -> distance report
 
-usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges | --only-tables]
+usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges | --only-tables | --only-cluster]
 """
 import json
 import os
@@ -247,6 +247,44 @@ def golden_tablescenes(manifest):
         manifest["tablescenes"][variant] = dg
 
 
+def golden_clusterscene(manifest):
+    """the cluster scene (tools/make_clusterscene.py: full leaves, duplicates, coplanar faces -- where a misreading of the
+    reference's visiting order that oracle and lane code share would sit): the reference's loader counts, its CHUNK and PIXEL
+    renders at the host tests' frame -> renders_cluster.npz, and its closest hits for the 2 000 rays of tests/tree_shapes.py
+    (the reference's own first cast placing the surface starts) -> raycast_cluster.npz.  The .scn is regenerated by the tests."""
+    import hashlib
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import make_clusterscene
+    import tree_shapes
+    d = tempfile.mkdtemp(prefix="cluster_", dir=TMP) + "/"
+    scn, layout = make_clusterscene.write_scene(d)
+    dump = os.path.join(d, "cluster.dump")
+    info = run(REF_DET, "scene-dump", scn, d, 64, 48, dump)
+    dg = ref_io.scene_digest(ref_io.read_scene_dump(dump))
+    dg["octree"] = info
+    dg["scn_sha256"] = hashlib.sha256(open(scn, "rb").read()).hexdigest()
+    dg["renders"] = []
+    arrays = {}
+    W, H, spp, _ = tree_shapes.RENDER
+    for policy, chunk in tree_shapes.GOLDEN_RENDERS:
+        out = os.path.join(d, "r.f32")
+        js = run(REF_DET, "render", scn, d, W, H, spp, tree_shapes.SEED, policy, out, chunk)
+        key = "%s_%dx%d_%dspp_c%d_s%d" % (policy, W, H, spp, chunk, tree_shapes.SEED)
+        arrays[key] = np.fromfile(out, "<f4").reshape(H, W, 3)
+        dg["renders"].append(dict(key=key, policy=policy, width=W, height=H, spp=spp, chunk=chunk, seed=tree_shapes.SEED,
+                                  shapes_tested=js["shapes_tested"], final_rng=js["final_rng"]))
+    np.savez_compressed(os.path.join(HERE, "renders_cluster.npz"), **arrays)
+
+    def cast(rays):
+        np.ascontiguousarray(rays, "<f4").tofile(os.path.join(d, "rays.bin"))
+        run(REF_DET, "raycast", scn, d, os.path.join(d, "rays.bin"), os.path.join(d, "hits.bin"))
+        return np.fromfile(os.path.join(d, "hits.bin"), dtype=np.dtype([("t", "<f4"), ("n", "<f4", 3), ("mat", "<u4")]))
+    rays = tree_shapes.ray_set("cluster", layout, lambda r: cast(r)["t"])
+    hits = cast(rays)
+    np.savez_compressed(os.path.join(HERE, "raycast_cluster.npz"), rays=rays, t=hits["t"], n=hits["n"], mat=hits["mat"])
+    manifest["clusterscene"] = dg
+
+
 def golden_showcase():
     """a crop of an image the reference itself wrote (showcase/1.hdr): header, file size, 32x64 RGBE pixels"""
     raw = open("/root/reference/showcase/1.hdr", "rb").read()
@@ -302,6 +340,11 @@ def main():
     if "--only-tables" in sys.argv:  # add / refresh the table-cap scenes' fixtures without touching the others
         manifest = json.load(open(os.path.join(HERE, "manifest.json")))
         golden_tablescenes(manifest)
+        json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
+        return
+    if "--only-cluster" in sys.argv:  # add / refresh the cluster scene's fixtures without touching the others
+        manifest = json.load(open(os.path.join(HERE, "manifest.json")))
+        golden_clusterscene(manifest)
         json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
         return
     if "--only-c5" in sys.argv:  # add / refresh the C5 fixtures without touching the others
@@ -420,6 +463,7 @@ def main():
 
     golden_c5(manifest)
     golden_tablescenes(manifest)
+    golden_clusterscene(manifest)
     golden_showcase()
     golden_unit_edges()
     golden_raycast_edges()

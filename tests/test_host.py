@@ -170,7 +170,7 @@ def test_reference_compatible_octree_counts(manifest, load_scene, name):
     assert ti["ref_nonempty_leaves"] == want["octree_leaves"]
 
 
-def test_fast_tree_shape(load_scene):
+def test_fast_tree_shape(load_scene, tmp_path):
     ti = load_scene("c3_bunny_room").tree_info()
     assert ti["prologue_prims"] == 8  # six room slabs, the table, the light: tested outright, not in the tree
     assert load_scene("testscene").tree_info()["prologue_prims"] == 12  # its nine boxes and three largest spheres; the rest stays in the tree
@@ -178,6 +178,28 @@ def test_fast_tree_shape(load_scene):
     assert ti["max_leaf_prims"] <= 16
     assert ti["max_depth"] <= 60  # kTreeDepthBudget (ort_scene.h): the kernels' smallest stack, 20 LDS + 40 scratch entries
     assert ti["node_bytes"] == ti["node_count"] * 64
+    # the same through tools/host_sim --tree-check, which walks the tree itself, and under the builder's leaf knobs
+    import tree_shapes
+    scn, base = os.path.join(DATA, "c3_bunny_room.scn"), DATA + "/"
+    line, r = tree_shapes.tree_check(scn, base, "default")
+    assert line is not None, r.stderr
+    assert (line["nodes"], line["leaves"], line["depth"], line["prologue"]) == (ti["node_count"], ti["leaf_count"], ti["max_depth"], 8)
+    assert max(line["max_leaf"].values()) == line["max_leaf"]["triangle"] == ti["max_leaf_prims"] == 4   # ORT_LEAF_TRI's default
+    one, _ = tree_shapes.tree_check(scn, base, "leaf1")
+    assert one["max_leaf"]["triangle"] == 1 and one["leaves"] == one["nodes"] + 1 > line["leaves"]
+    assert one["leaves"] == load_scene("c3_bunny_room").info().triangle_count   # one triangle a leaf (the analytic shapes are all in the prologue)
+    many, _ = tree_shapes.tree_check(scn, base, "leaf16")
+    assert 4 <= many["max_leaf"]["triangle"] <= 16 and many["leaves"] <= line["leaves"]
+    # the special roots: a scene without a shape and one that is all prologue have an empty tree, a lone shape outside the
+    # prologue hangs under node 0 as its single leaf
+    brdf = "brdf 0.5 0.5 0.5 0.0 0.0 0.0 10\n"
+    for text, env, want in ((brdf, {}, (1, 0, 0)), (brdf + "sphere 0.0 0.0 0.0 1.0\n", {}, (1, 0, 1)),
+                            (brdf + "sphere 0.0 0.0 0.0 1.0\n", {"ORT_ANALYTIC_PROLOGUE": "0"}, (1, 1, 0))):
+        p = tmp_path / "tiny.scn"
+        p.write_text(text)
+        line, r = tree_shapes.tree_check(str(p), str(tmp_path) + "/", "default", extra_env=env)
+        assert line is not None, r.stderr
+        assert (line["nodes"], line["leaves"], line["prologue"]) == want and line["depth"] == 0
 
 
 def test_empty_and_tiny_scenes_commit(api):

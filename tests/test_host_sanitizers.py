@@ -165,6 +165,22 @@ def test_the_stack_in_its_scratch_tail(api, oracle, tools, tmp_path_factory, tmp
         assert r.returncode == 0 and hs.stack_probe(r)[0]["scratch_pops"] > 0
 
 
+def test_tree_check_on_full_leaves(tools, tmp_path):
+    """--tree-check on the cluster scene (tools/make_clusterscene.py) committed under ORT_LEAF_TRI=16 ORT_LEAF_OTHER=16: the
+    builder writing 16-primitive leaves of every kind, and the check's own walks of both trees, under the sanitizers; then one
+    frame and the scene's aimed rays through those leaves"""
+    import tree_shapes
+    scn, layout = tree_shapes.make_clusterscene.write_scene(str(tmp_path))
+    base, env = str(tmp_path) + "/", tree_shapes.VARIANTS["leaf16"]
+    r = both(tools, ["--tree-check", scn, base], [], env=env)
+    assert r.returncode == 0 and "max_leaf triangle 16 sphere 16 box 16 cylinder 16" in r.stdout, r.stdout + r.stderr
+    rays = tree_shapes.aimed_rays(layout, np.random.default_rng(3))[::7]
+    assert both(tools, *hs.raycast_args(str(tmp_path), scn, rays, base), env=env).returncode == 0
+    for extra in ({}, {"SIM_WIDE": "1"}, {"SIM_TABS": "1"}):
+        args, outs = hs.render_args(str(tmp_path), scn, 20, 12, 2, 77, "chunk", 1, base)
+        assert both(tools, args, outs, env=dict(env, **extra)).returncode == 0
+
+
 def test_unit_records(tools, tmp_path):
     z = np.load(os.path.join(GOLDEN, "unit_edges.npz"))
     recs = z["records"].view(ref_io.UNIT_REC_DTYPE).reshape(-1)

@@ -34,6 +34,10 @@
  *   or: host_sim --features scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|-
  *       (the first-hit feature render, feature_lane: a batch of views, or with cams - the scene's own camera on the seed given; a
  *       plane given as - is not passed; the planes start at -7.0f, 0xeeeeeeee and, the states, 0xdddddddd)
+ *   or: host_sim --tree-check scn base
+ *       (no lane runs: the fast tree, binary and 4-wide, as build_tree made it under the environment's ORT_LEAF_TRI, ORT_LEAF_OTHER,
+ *       ORT_TREE_SPLIT_KINDS and ORT_ANALYTIC_PROLOGUE, checked for everything the lanes take for granted -- see TreeCheck; one line
+ *       on stdout when it is sound, the first violation on stderr and status 1 when it is not)
  * Every mode prints, per instantiation of traverse, how deep the per-lane stack got ("stack: lds 24 deepest ..."; tests/host_sim_tool.py
  * stack_probe reads it); make host_sim_w5 builds the same tool with the five-waves unit's split of that stack (20 + 44 entries).
  * All files raw little-endian.  SIM_TABS=1: the TABS = true lane code, on a heap copy of the LDS tables' image.
@@ -63,6 +67,9 @@ static inline void stack_probe(int lds, int sp, bool fresh) {
 #define ORT_SIM_STACK_HOOK(LDS_, SP_, FRESH_) stack_probe((LDS_), (SP_), (FRESH_))
 #define ORT_SIM_PIXEL_HOOK(x, y, rng) do { if (g_pixel_rng) g_pixel_rng[(y) * g_W + (x)] = (rng); } while (0)
 #include "../offline_raytracer_amd/csrc/ort_lane.h"
+
+#include <float.h>
+#include <stdarg.h>
 
 #include <algorithm>
 #include <chrono>
@@ -617,8 +624,258 @@ static int features_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x
            (!want[4] || write_bytes(a[15], ids.data(), 8 * n)) && (!want[5] || write_bytes(a[16], states.data(), 4 * n)) ? 0 : 1;
 }
 
+/* --tree-check scn base: the scene committed under the environment's knobs (ORT_LEAF_TRI, ORT_LEAF_OTHER, ORT_TREE_SPLIT_KINDS,
+   ORT_ANALYTIC_PROLOGUE), and everything the lanes take for granted about what build_tree hands them, verified from the finished
+   arrays alone: nothing of the builder's own bookkeeping is trusted but the scene's source shapes.  The first violation is
+   printed and ends the run with status 1; a sound tree prints one line (tests/test_tree_shapes_host.py reads it). */
+struct TreeCheck {
+    const Scene &sc;
+    const Tree &t;
+    std::vector<uint32_t> covered[5];      /* per kind code: how many leaves (or the prologue) hold each slot */
+    std::vector<double> tight[5];          /* per kind code: 6 doubles a slot, the box of the shape itself */
+    std::vector<uint32_t> leaves2, leaves4; /* the leaf words the two walks reach */
+    uint32_t max_leaf[5] = {0, 0, 0, 0, 0}, leaf_count = 0, depth = 0, depth4 = 0, root_kinds[2] = {0, 0};
+    std::vector<uint8_t> seen2, seen4;
+    std::string err;
+    struct Sub { double lo[3], hi[3]; bool sphere; uint32_t kinds; };
+
+    explicit TreeCheck(const Scene &s) : sc(s), t(s.tree) {}
+    bool fail(const char *fmt, ...) {
+        if (!err.empty()) return false;
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof(buf), fmt, ap);
+        va_end(ap);
+        err = buf;
+        return false;
+    }
+    size_t kind_size(uint32_t k) const { return k == PRIM_TRI ? t.tris.size() : k == PRIM_SPHERE ? t.spheres.size() : k == PRIM_BOX ? t.boxes.size() : t.cyls.size(); }
+    static const char *kind_name(uint32_t k) { return k == PRIM_TRI ? "triangle" : k == PRIM_SPHERE ? "sphere" : k == PRIM_BOX ? "box" : k == PRIM_CYL ? "cylinder" : "?"; }
+    void set_tight(uint32_t k, uint32_t slot, const double lo[3], const double hi[3]) {
+        for (int c = 0; c < 3; ++c) { tight[k][6 * (size_t)slot + c] = lo[c]; tight[k][6 * (size_t)slot + 3 + c] = hi[c]; }
+    }
+    /* the slot tables against the source shapes: a bijection source -> slot, the record at the slot is that shape's, bit for bit */
+    bool slots() {
+        for (uint32_t k : {(uint32_t)PRIM_TRI, (uint32_t)PRIM_BOX, (uint32_t)PRIM_CYL, (uint32_t)PRIM_SPHERE}) {
+            covered[k].assign(kind_size(k), 0u);
+            tight[k].assign(6 * kind_size(k), 0.0);
+        }
+        std::vector<uint8_t> taken;
+        auto claim = [&](uint32_t k, const std::vector<uint32_t> &slot, size_t i) {
+            if (slot[i] >= kind_size(k)) return fail("%s %zu: slot %u outside the %zu records of its kind", kind_name(k), i, slot[i], kind_size(k));
+            if (taken[slot[i]]) return fail("%s %zu: slot %u is taken twice", kind_name(k), i, slot[i]);
+            taken[slot[i]] = 1;
+            return true;
+        };
+        size_t n_tri = 0;
+        for (const HostMesh &m : sc.meshes) n_tri += m.indices.size() / 3;
+        if (t.tri_slot.size() != n_tri || t.tris.size() != n_tri || t.tri_mat.size() != n_tri) return fail("%zu triangles, %zu slots, %zu records", n_tri, t.tri_slot.size(), t.tris.size());
+        taken.assign(n_tri, 0);
+        size_t g = 0;
+        for (const HostMesh &m : sc.meshes)
+            for (size_t k = 0; k + 2 < m.indices.size(); k += 3, ++g) {
+                if (!claim(PRIM_TRI, t.tri_slot, g)) return false;
+                const DevTri &d = t.tris[t.tri_slot[g]];
+                const float *v[3] = {&m.vertices[3 * (size_t)m.indices[k]], &m.vertices[3 * (size_t)m.indices[k + 1]], &m.vertices[3 * (size_t)m.indices[k + 2]]};
+                if (memcmp(d.v0, v[0], 12) != 0 || t.tri_mat[t.tri_slot[g]] != m.mat) return fail("triangle %zu: the record at slot %u is another triangle's", g, t.tri_slot[g]);
+                double lo[3], hi[3];
+                for (int c = 0; c < 3; ++c) { lo[c] = std::min({v[0][c], v[1][c], v[2][c]}); hi[c] = std::max({v[0][c], v[1][c], v[2][c]}); }
+                set_tight(PRIM_TRI, t.tri_slot[g], lo, hi);
+            }
+        if (t.sphere_slot.size() != sc.spheres.size() || t.spheres.size() != sc.spheres.size() || t.sphere_mat.size() != sc.spheres.size()) return fail("sphere counts disagree");
+        taken.assign(sc.spheres.size(), 0);
+        for (size_t i = 0; i < sc.spheres.size(); ++i) {
+            if (!claim(PRIM_SPHERE, t.sphere_slot, i)) return false;
+            const ort_sphere &s = sc.spheres[i];
+            const DevSphere &d = t.spheres[t.sphere_slot[i]];
+            const float want[4] = {s.center.x, s.center.y, s.center.z, s.r};
+            if (memcmp(&d, want, 16) != 0 || t.sphere_mat[t.sphere_slot[i]] != s.mat) return fail("sphere %zu: the record at slot %u is another sphere's", i, t.sphere_slot[i]);
+            double lo[3], hi[3];
+            for (int c = 0; c < 3; ++c) { lo[c] = (double)want[c] - fabs((double)s.r); hi[c] = (double)want[c] + fabs((double)s.r); }
+            set_tight(PRIM_SPHERE, t.sphere_slot[i], lo, hi);
+        }
+        if (t.box_slot.size() != sc.boxes.size() || t.boxes.size() != sc.boxes.size() || t.box_mat.size() != sc.boxes.size()) return fail("box counts disagree");
+        taken.assign(sc.boxes.size(), 0);
+        for (size_t i = 0; i < sc.boxes.size(); ++i) {
+            if (!claim(PRIM_BOX, t.box_slot, i)) return false;
+            const ort_box &b = sc.boxes[i];
+            const DevBox &d = t.boxes[t.box_slot[i]];
+            const float mn[3] = {b.min.x, b.min.y, b.min.z}, mx[3] = {b.max.x, b.max.y, b.max.z};
+            if (memcmp(d.lo, mn, 12) != 0 || memcmp(d.hi, mx, 12) != 0 || t.box_mat[t.box_slot[i]] != b.mat) return fail("box %zu: the record at slot %u is another box's", i, t.box_slot[i]);
+            double lo[3], hi[3];
+            for (int c = 0; c < 3; ++c) { lo[c] = std::min(mn[c], mx[c]); hi[c] = std::max(mn[c], mx[c]); }
+            set_tight(PRIM_BOX, t.box_slot[i], lo, hi);
+        }
+        if (t.cyl_slot.size() != sc.cylinders.size() || t.cyls.size() != sc.cylinders.size() || t.cyl_mat.size() != sc.cylinders.size()) return fail("cylinder counts disagree");
+        taken.assign(sc.cylinders.size(), 0);
+        for (size_t i = 0; i < sc.cylinders.size(); ++i) {
+            if (!claim(PRIM_CYL, t.cyl_slot, i)) return false;
+            const ort_cylinder &c = sc.cylinders[i];
+            const DevCyl &d = t.cyls[t.cyl_slot[i]];
+            float rot[9], len;
+            cylinder_frame_for(c, rot, &len);
+            const float base[3] = {c.base.x, c.base.y, c.base.z};
+            if (memcmp(d.base, base, 12) != 0 || memcmp(&d.r, &c.r, 4) != 0 || memcmp(d.rot, rot, 36) != 0 || memcmp(&d.len, &len, 4) != 0 || t.cyl_mat[t.cyl_slot[i]] != c.mat)
+                return fail("cylinder %zu: the record at slot %u is another cylinder's", i, t.cyl_slot[i]);
+            /* the segment the intersector tests, base .. base + len * a, and a disc of radius r about each end */
+            double lo[3], hi[3];
+            for (int k = 0; k < 3; ++k) {
+                const double a = rot[6 + k], p0 = base[k], p1 = (double)base[k] + (double)len * a, e = fabs((double)c.r) * sqrt(std::max(0.0, 1.0 - a * a));
+                lo[k] = std::min(p0, p1) - e; hi[k] = std::max(p0, p1) + e;
+            }
+            set_tight(PRIM_CYL, t.cyl_slot[i], lo, hi);
+        }
+        /* the prologue's shapes are the first of their kind's array */
+        if (t.pro_boxes > t.boxes.size() || t.pro_spheres > t.spheres.size() || t.pro_cyls > t.cyls.size()) return fail("the prologue is longer than a shape array");
+        if (t.analytic_prologue != (t.pro_boxes + t.pro_spheres + t.pro_cyls > 0)) return fail("analytic_prologue disagrees with the prologue's counts");
+        for (uint32_t i = 0; i < t.pro_boxes; ++i) covered[PRIM_BOX][i]++;
+        for (uint32_t i = 0; i < t.pro_spheres; ++i) covered[PRIM_SPHERE][i]++;
+        for (uint32_t i = 0; i < t.pro_cyls; ++i) covered[PRIM_CYL][i]++;
+        return true;
+    }
+    /* a child word and its box -> what lies below it; wide: the word is the 4-wide tree's */
+    bool below(uint32_t word, const float lo[3], const float hi[3], uint32_t level, bool wide, Sub *out, const char *where, uint32_t at) {
+        for (int c = 0; c < 3; ++c) { out->lo[c] = DBL_MAX; out->hi[c] = -DBL_MAX; }
+        out->sphere = false;
+        out->kinds = 0;
+        if (word & LEAF_BIT) {
+            const uint32_t kind = (word >> 28) & 7u, count = ((word >> 24) & 15u) + 1u, first = word & 0x00ffffffu;
+            if (kind != PRIM_TRI && kind != PRIM_BOX && kind != PRIM_CYL && kind != PRIM_SPHERE) return fail("%s node %u: leaf word %08x has kind %u", where, at, word, kind);
+            if (count < 1u || count > MAX_LEAF_PRIMS) return fail("%s node %u: leaf word %08x holds %u primitives", where, at, word, count);
+            if ((size_t)first + count > kind_size(kind)) return fail("%s node %u: leaf %08x runs to %u of %zu %ss", where, at, word, first + count, kind_size(kind), kind_name(kind));
+            for (uint32_t i = first; i < first + count; ++i) {
+                if (!wide) covered[kind][i]++;
+                for (int c = 0; c < 3; ++c) { out->lo[c] = std::min(out->lo[c], tight[kind][6 * (size_t)i + c]); out->hi[c] = std::max(out->hi[c], tight[kind][6 * (size_t)i + 3 + c]); }
+            }
+            out->sphere = kind == PRIM_SPHERE;
+            out->kinds = 1u << kind;
+            (wide ? leaves4 : leaves2).push_back(word);
+            if (!wide) { leaf_count++; max_leaf[kind] = std::max(max_leaf[kind], count); depth = std::max(depth, level); }
+        } else {
+            const uint32_t i = word & NODE_INDEX_MASK;
+            std::vector<uint8_t> &seen = wide ? seen4 : seen2;
+            if (i >= seen.size()) return fail("%s node %u: child index %u of %zu nodes", where, at, i, seen.size());
+            if (seen[i]) return fail("%s node %u is reached twice", where, i);
+            seen[i] = 1;
+            if (!wide) depth = std::max(depth, level);
+            else depth4 = std::max(depth4, level + 1u);
+            const uint32_t n = wide ? 4u : 2u;
+            for (uint32_t k = 0; k < n; ++k) {
+                uint32_t cw;
+                float clo[3], chi[3];
+                if (wide) {
+                    const DevNode4 &w = t.nodes4[i];
+                    cw = w.child[k];
+                    clo[0] = w.lox[k]; clo[1] = w.loy[k]; clo[2] = w.loz[k]; chi[0] = w.hix[k]; chi[1] = w.hiy[k]; chi[2] = w.hiz[k];
+                } else {
+                    const DevNode &b = t.nodes[i];
+                    cw = k ? b.child1 : b.child0;
+                    memcpy(clo, k ? b.lo1 : b.lo0, 12); memcpy(chi, k ? b.hi1 : b.hi0, 12);
+                }
+                if (cw == EMPTY_CHILD) {
+                    if (!(clo[0] > chi[0] && clo[1] > chi[1] && clo[2] > chi[2])) return fail("%s node %u: the box of empty child %u is not inverted", where, i, k);
+                    continue;
+                }
+                Sub s;
+                if (!below(cw, clo, chi, level + 1u, wide, &s, where, i)) return false;
+                for (int c = 0; c < 3; ++c) { out->lo[c] = std::min(out->lo[c], s.lo[c]); out->hi[c] = std::max(out->hi[c], s.hi[c]); }
+                out->sphere |= s.sphere;
+                out->kinds |= s.kinds;
+                if (!wide && i == 0 && level == 0) root_kinds[k] = s.kinds;
+            }
+            if (out->kinds == 0 && !(i == 0 && level == 0)) return fail("%s node %u has nothing below it", where, i);
+            if (((word & SPHERE_BELOW_BIT) != 0) != out->sphere && !(i == 0 && level == 0))
+                return fail("%s node %u: child word %08x, SPHERE_BELOW_BIT %s but %s below it", where, at, word, (word & SPHERE_BELOW_BIT) ? "set" : "clear", out->sphere ? "a sphere leaf" : "no sphere leaf");
+        }
+        if (!(word == 0u && level == 0))
+            for (int c = 0; c < 3; ++c)
+                if (out->kinds && !((double)lo[c] <= out->lo[c] && (double)hi[c] >= out->hi[c]))
+                    return fail("%s node %u: the box of child %08x, [%.9g, %.9g] on axis %d, does not contain what is below it, [%.17g, %.17g]", where, at, word, lo[c], hi[c], c, out->lo[c], out->hi[c]);
+        return true;
+    }
+    /* interior nodes in breadth-first order, children in slot order */
+    std::vector<uint32_t> breadth_first(bool wide) const {
+        std::vector<uint32_t> order(1, 0u);
+        for (size_t h = 0; h < order.size(); ++h)
+            for (uint32_t k = 0; k < (wide ? 4u : 2u); ++k) {
+                const uint32_t cw = wide ? t.nodes4[order[h]].child[k] : (k ? t.nodes[order[h]].child1 : t.nodes[order[h]].child0);
+                if (!(cw & LEAF_BIT)) order.push_back(cw & NODE_INDEX_MASK);
+            }
+        return order;
+    }
+    bool run() {
+        if (!slots()) return false;
+        if (t.nodes.empty()) return fail("no node 0");
+        seen2.assign(t.nodes.size(), 0);
+        seen4.assign(t.nodes4.size(), 0);
+        const float none[3] = {0, 0, 0};
+        Sub all;
+        if (!below(0u, none, none, 0u, false, &all, "binary", 0u)) return false; /* node 0: no child word points at it, no box holds it */
+        for (size_t i = 0; i < seen2.size(); ++i)
+            if (!seen2[i]) return fail("binary node %zu is not reached from node 0", i);
+        for (uint32_t k : {(uint32_t)PRIM_TRI, (uint32_t)PRIM_BOX, (uint32_t)PRIM_CYL, (uint32_t)PRIM_SPHERE})
+            for (size_t i = 0; i < covered[k].size(); ++i)
+                if (covered[k][i] != 1u) return fail("%s slot %zu is in %u leaves (the prologue counted as one)", kind_name(k), i, covered[k][i]);
+        /* the special roots */
+        const DevNode &root = t.nodes[0];
+        const bool single = root.child1 == EMPTY_CHILD && root.child0 != EMPTY_CHILD;
+        if (root.child0 == EMPTY_CHILD && (root.child1 != EMPTY_CHILD || t.nodes.size() != 1 || leaf_count != 0)) return fail("an empty root with something under it");
+        if (single && (!(root.child0 & LEAF_BIT) || t.nodes.size() != 1)) return fail("a root with one child that is not a single leaf");
+        if (single) depth = 0; /* the builder counts the leaf where it made it, before it wrapped it in node 0 */
+        const char *split_env = getenv("ORT_TREE_SPLIT_KINDS");
+        const uint32_t analytic = (1u << PRIM_BOX) | (1u << PRIM_CYL) | (1u << PRIM_SPHERE), tri = 1u << PRIM_TRI;
+        if ((!split_env || atoi(split_env) != 0) && (all.kinds & tri) && (all.kinds & analytic)) /* analytic shapes left, triangles right */
+            if ((root_kinds[0] & tri) || (root_kinds[1] & analytic)) return fail("the kind-split root has kinds %x left and %x right", root_kinds[0], root_kinds[1]);
+        ort_tree_info ti;
+        if (ort_scene_get_tree_info(&static_cast<const ort_scene &>(sc), &ti) != ORT_OK) return fail("ort_scene_get_tree_info: %s", ort_last_error());
+        const uint32_t biggest = std::max({max_leaf[PRIM_TRI], max_leaf[PRIM_BOX], max_leaf[PRIM_CYL], max_leaf[PRIM_SPHERE]});
+        if (depth > kTreeDepthBudget) return fail("depth %u is past the budget of %u", depth, kTreeDepthBudget);
+        if (ti.node_count != t.nodes.size() || ti.leaf_count != leaf_count || ti.max_leaf_prims != biggest || ti.max_depth != depth)
+            return fail("tree info says %u nodes, %u leaves, max leaf %u, depth %u; the walk finds %zu, %u, %u, %u", ti.node_count, ti.leaf_count, ti.max_leaf_prims, ti.max_depth,
+                        t.nodes.size(), leaf_count, biggest, depth);
+        /* the top of the tree has the lowest indices, breadth-first */
+        const std::vector<uint32_t> bfs = breadth_first(false);
+        for (uint32_t k = 0; k < std::min<size_t>(kTreeletNodes, bfs.size()); ++k)
+            if (bfs[k] != k) return fail("binary node %u is number %u in breadth-first order: [0, %u) is not the top of the tree", bfs[k], k, kTreeletNodes);
+        /* the 4-wide tree (a scene that is all prologue has none: nothing would walk it) */
+        if (t.nodes4.empty() && (leaf_count != 0 || ti.wide_node_count != 0 || ti.wide_max_depth != 0)) return fail("no wide tree");
+        Sub all4;
+        if (!t.nodes4.empty() && !below(0u, none, none, 0u, true, &all4, "wide", 0u)) return false;
+        for (size_t i = 0; i < seen4.size(); ++i)
+            if (!seen4[i]) return fail("wide node %zu is not reached from node 0", i);
+        const std::vector<uint32_t> bfs4 = t.nodes4.empty() ? std::vector<uint32_t>() : breadth_first(true);
+        for (uint32_t k = 0; k < bfs4.size(); ++k)
+            if (bfs4[k] != k) return fail("wide node %u is number %u in breadth-first order", bfs4[k], k);
+        if (ti.wide_node_count != t.nodes4.size() || ti.wide_max_depth != depth4) return fail("tree info says %u wide nodes, depth %u; the walk finds %zu, %u", ti.wide_node_count, ti.wide_max_depth, t.nodes4.size(), depth4);
+        std::sort(leaves2.begin(), leaves2.end());
+        std::sort(leaves4.begin(), leaves4.end());
+        if (leaves2 != leaves4) return fail("the binary tree reaches %zu leaf words, the wide tree %zu, or other ones", leaves2.size(), leaves4.size());
+        printf("tree-check ok: nodes %zu leaves %u depth %u wide_nodes %zu wide_depth %u prologue %u max_leaf triangle %u sphere %u box %u cylinder %u\n", t.nodes.size(), leaf_count, depth,
+               t.nodes4.size(), depth4, t.pro_boxes + t.pro_spheres + t.pro_cyls, max_leaf[PRIM_TRI], max_leaf[PRIM_SPHERE], max_leaf[PRIM_BOX], max_leaf[PRIM_CYL]);
+        return true;
+    }
+};
+
+static int tree_check_mode(char **a) { /* scn base */
+    ort_scene *scene = nullptr;
+    if (ort_scene_load_scn(a[0], a[1], &scene) != ORT_OK || ort_scene_commit(scene) != ORT_OK) {
+        fprintf(stderr, "scene: %s\n", ort_last_error());
+        if (scene) ort_scene_destroy(scene);
+        return 1;
+    }
+    int rc = 0;
+    {
+        TreeCheck tc(*scene);
+        if (!tc.run()) { fprintf(stderr, "tree-check: %s\n", tc.err.c_str()); rc = 1; }
+    }
+    ort_scene_destroy(scene);
+    return rc;
+}
+
 int main(int argc, char **argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
+    if (argc == 4 && mode == "--tree-check") return tree_check_mode(argv + 2);
     if (argc == 19 && mode == "--features") return features_mode(argv + 2);
     if (argc == 4 && mode == "--unit") return unit_mode(argv[2], argv[3]);
     if (argc == 6 && mode == "--raycast") return raycast_mode(argv + 2);
@@ -633,6 +890,7 @@ int main(int argc, char **argv) {
     if (argc < 10 || mode.rfind("--", 0) == 0) {
         fprintf(stderr, "usage: host_sim scn base W H spp seed policy chunk out.f32 [shard_index shard_count]\n"
                         "       host_sim --unit records.bin out.f32\n"
+                        "       host_sim --tree-check scn base\n"
                         "       host_sim --raycast scn base rays.f32 hits.bin\n"
                         "       host_sim --occluded scn base rays.f32 tmax.f32|- out.u8\n"
                         "       host_sim --ambient-occlusion scn base points.f32 seeds.u32 radius.f32|- spp open.u32 bent.f32|- states.u32|-\n"
