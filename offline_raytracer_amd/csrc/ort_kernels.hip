@@ -362,6 +362,33 @@ static int mark_inflight(DeviceScene *d, hipStream_t stream, std::string *err) {
     d->inflight = true;
     return ORT_OK;
 }
+/* A frame-sized plane of a render call as the lanes see it (dev): the caller's device pointer, or in the host form one of the
+   scene's staging buffers holding the caller's words -- staged whole, both ways.  A plane that is not asked for stays null */
+struct Plane { void *caller; DevBuf *stage; size_t bytes; void *dev; };
+static int stage_planes_in(Plane *planes, size_t n, bool host, hipStream_t stream, std::string *err) {
+    for (Plane *pn = planes; pn != planes + n; ++pn) {
+        pn->dev = pn->caller;
+        if (!host || !pn->caller) continue;
+        if (int rc = pn->stage->ensure(pn->bytes, err)) return rc;
+        pn->dev = pn->stage->p;
+        ORT_HIP(hipMemcpyAsync(pn->dev, pn->caller, pn->bytes, hipMemcpyHostToDevice, stream));
+    }
+    return ORT_OK;
+}
+static int stage_planes_out(const Plane *planes, size_t n, bool host, hipStream_t stream, std::string *err) {
+    for (const Plane *pn = planes; host && pn != planes + n; ++pn)
+        if (pn->caller) ORT_HIP(hipMemcpyAsync(pn->caller, pn->dev, pn->bytes, hipMemcpyDeviceToHost, stream));
+    return ORT_OK;
+}
+/* the camera table of a batch of views, packed and on its way to d->view_tab.  Both copies of it are the previous call's until
+   that has finished (the caller has settled it); the caller's array is read here and not again */
+static int upload_view_table(DeviceScene *d, const ort_view *views, uint32_t n, hipStream_t stream, std::string *err) {
+    std::vector<float> &tab = d->view_tab_host;
+    pack_view_table(views, n, tab);
+    if (int rc = d->view_tab.ensure(tab.size() * sizeof(float), err)) return rc;
+    ORT_HIP(hipMemcpyAsync(d->view_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    return ORT_OK;
+}
 
 /* a settled, timed launch's time and counters, added to stats (paths: its kernels count paths) */
 static int add_launch_stats(const DeviceScene *d, bool counters, bool paths, ort_stats *stats, std::string *err) {
@@ -496,16 +523,9 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     /* the planes as the lanes see them: the caller's device pointers, or the scene's staging buffers holding the caller's words.
        view_count frames, view-major, or the packed framebuffer; the 4-byte planes stage where the radiance queries' do */
     const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
-    struct Plane { void *caller; DevBuf *stage; size_t bytes; void *dev; };
     Plane planes[4] = {{out_rgb, &d->staging, rv.packed_out ? (size_t)rv.my_blocks * 768u : pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u, nullptr},
                        {out_m2, &d->query_stage[4], pixels * 4u, nullptr}, {states, &d->query_stage[5], pixels * 4u, nullptr}};
-    for (Plane &pn : planes) {
-        pn.dev = pn.caller;
-        if (!c.host || !pn.caller) continue;
-        if ((rc = pn.stage->ensure(pn.bytes, err))) return rc;
-        pn.dev = pn.stage->p;
-        ORT_HIP(hipMemcpyAsync(pn.dev, pn.caller, pn.bytes, hipMemcpyHostToDevice, stream));
-    }
+    if ((rc = stage_planes_in(planes, 4, c.host, stream, err))) return rc;
     rv.out = (float *)planes[0].dev;
     rv.ad_spp = (uint32_t *)planes[1].dev;
     rv.ad_m2 = (float *)planes[2].dev;
@@ -521,13 +541,8 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
             rv.final_states = d->states.as<uint32_t>();
         }
     }
-    if (pl.views) {
-        /* the camera table (pack_view_table).  Both copies of it are the previous call's until that has finished (settled
-           above); the caller's array is read here and not again */
-        std::vector<float> &tab = d->view_tab_host;
-        pack_view_table(c.views, view_count, tab);
-        if ((rc = d->view_tab.ensure(tab.size() * sizeof(float), err))) return rc;
-        ORT_HIP(hipMemcpyAsync(d->view_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (pl.views) { /* the camera table; the previous call was settled above */
+        if ((rc = upload_view_table(d, c.views, view_count, stream, err))) return rc;
         rv.views = d->view_tab.as<const float4>();
     }
     if (pl.mode == PLAN_JOBS_CHUNK) {
@@ -557,9 +572,7 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     }
     if ((rc = end_kernels(d, c.stats != nullptr, stream, err))) return rc;
 
-    if (c.host)
-        for (const Plane &pn : planes)
-            if (pn.caller) ORT_HIP(hipMemcpyAsync(pn.caller, pn.dev, pn.bytes, hipMemcpyDeviceToHost, stream));
+    if ((rc = stage_planes_out(planes, 4, c.host, stream, err))) return rc;
     if (c.job_states) ORT_HIP(hipMemcpyAsync(c.job_states, d->states.p, (size_t)c.job_count * 4u, hipMemcpyDeviceToHost, stream));
     /* every synchronous form of the call checks the tripwire before it returns (the fire-and-forget device form, stats == NULL,
        cannot without a sync: the next call on the scene does; bench.py asks for stats) */
@@ -774,8 +787,8 @@ int device_ambient_occlusion(Scene *scene, const QueryCall &q, const void *point
 }
 
 /* first-hit feature renders: view_count frames of p's rect -> the planes asked for.  The planes are frames, not arrays over the
-   jobs, so the host form stages them as device_render stages its own -- whole, both ways, plane i through the scene's i-th query
-   staging buffer -- and the launch is one; the camera table is device_render's too (pack_view_table, the scene's view_tab).  The
+   jobs, so the host form stages them as device_render stages its own (stage_planes_in / _out) -- plane i through the scene's i-th
+   query staging buffer -- and the launch is one; the camera table is device_render's too (upload_view_table).  The
    launch goes through the queries' one path by plan_features (ort_plan.h) */
 int device_render_features(Scene *scene, const ort_render_params *p, const ort_view *views, uint32_t view_count, const QueryCall &q,
                            const ort_feature_planes &planes, std::string *err) {
@@ -786,21 +799,11 @@ int device_render_features(Scene *scene, const ort_render_params *p, const ort_v
     /* the staging buffers and both copies of the camera table are the previous call's until that has finished */
     if ((rc = settle_inflight(d, err))) return rc;
     const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
-    struct Plane { void *caller; size_t bytes; void *dev; };
-    Plane pn[6] = {{planes.albedo, pixels * 12u, nullptr}, {planes.normal, pixels * 12u, nullptr}, {planes.depth, pixels * 4u, nullptr},
-                   {planes.hits, pixels * 4u, nullptr}, {planes.ids, pixels * 8u, nullptr}, {planes.final_states, pixels * 4u, nullptr}};
+    DevBuf *const st = d->query_stage;
+    Plane pn[6] = {{planes.albedo, st, pixels * 12u, nullptr}, {planes.normal, st + 1, pixels * 12u, nullptr}, {planes.depth, st + 2, pixels * 4u, nullptr},
+                   {planes.hits, st + 3, pixels * 4u, nullptr}, {planes.ids, st + 4, pixels * 8u, nullptr}, {planes.final_states, st + 5, pixels * 4u, nullptr}};
     static_assert(sizeof(pn) / sizeof(pn[0]) <= sizeof(d->query_stage) / sizeof(d->query_stage[0]), "one staging buffer per plane");
-    for (size_t i = 0; i < 6; ++i) {
-        pn[i].dev = pn[i].caller;
-        if (!q.host || !pn[i].caller) continue;
-        if ((rc = d->query_stage[i].ensure(pn[i].bytes, err))) return rc;
-        pn[i].dev = d->query_stage[i].p;
-        ORT_HIP(hipMemcpyAsync(pn[i].dev, pn[i].caller, pn[i].bytes, hipMemcpyHostToDevice, stream));
-    }
-    std::vector<float> &tab = d->view_tab_host; /* the caller's array is read here and not again */
-    pack_view_table(views, view_count, tab);
-    if ((rc = d->view_tab.ensure(tab.size() * sizeof(float), err))) return rc;
-    ORT_HIP(hipMemcpyAsync(d->view_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    if ((rc = stage_planes_in(pn, 6, q.host, stream, err)) || (rc = upload_view_table(d, views, view_count, stream, err))) return rc;
     RenderView rv{};
     features_view(*p, view_count, &rv);
     rv.views = d->view_tab.as<const float4>();
@@ -816,9 +819,7 @@ int device_render_features(Scene *scene, const ort_render_params *p, const ort_v
             hipLaunchKernelGGL((feature_pixels<decltype(C)::value, decltype(T)::value>), dim3(plan.grid), dim3(kBlock), 0, stream, sv, hot, io);
         }, plan.counters, plan.tabs);
     });
-    if (rc || !q.host) return rc;
-    for (const Plane &x : pn)
-        if (x.caller) ORT_HIP(hipMemcpyAsync(x.caller, x.dev, x.bytes, hipMemcpyDeviceToHost, stream));
+    if (rc || (rc = stage_planes_out(pn, 6, q.host, stream, err)) || !q.host) return rc;
     ORT_HIP(hipStreamSynchronize(stream));
     return settle_inflight(d, err);
 }

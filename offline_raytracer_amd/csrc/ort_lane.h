@@ -1005,8 +1005,9 @@ ORT_D V3 view_aperture_point(const ViewCamera &cam, float aperture, float cs, fl
    wave trace like paths and end their jobs together -- plain loop on the headline frame 4 728 -> 5 204 Mpaths/s,
    analytic scene 3 567 -> 3 886 (profiles/r03_tuning.md).  Near the end of the job space (batch_until) a wave asks
    for exactly what it needs, so that no wave sits on indices that idle lanes elsewhere could take.  Which lane runs
-   which job cannot change a bit of the image (seeds belong to jobs). */
+   which job cannot change a bit of the image (seeds belong to jobs).  No pool (wave_job_pool): one atomic per lane and draw. */
 ORT_D unsigned long long draw_job(const RenderHot &rv, unsigned long long *pool) {
+    if (!pool) return ORT_NEXT_JOB(rv.c->next_job);
     const unsigned long long mask = __ballot(true);
     const uint32_t n = (uint32_t)__popcll(mask);
     const uint32_t rank = (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -1039,6 +1040,33 @@ ORT_D unsigned long long *wave_job_pool(const RenderHot &rv, unsigned long long 
 /* one simulated lane draws one index at a time (tools/host_sim.cpp passes no pool) */
 ORT_D unsigned long long draw_job(const RenderHot &rv, unsigned long long *) { return ORT_NEXT_JOB(rv.c->next_job); }
 #endif
+
+/* entry j of a caller's array of 24-byte rays (o, d) or points (p, n), as three 8-byte loads (the host checks the alignment) */
+struct Ray6 { V3 o, d; };
+ORT_D Ray6 load_ray(const float2 *rays, unsigned long long j) {
+    const float2 *r = rays + 3ull * j;
+    const float2 a = r[0], b = r[1], e = r[2];
+    return Ray6{mk(a.x, a.y, b.x), mk(b.y, e.x, e.y)};
+}
+/* the per-ray / per-point domain (include/ort.h): six finite components, |d|^2 within [0.999, 1.001]: what a primary direction
+   is in the reference (for a point, n stands for d) */
+ORT_D bool in_query_domain(V3 o, V3 d) {
+    const float l2 = len2(d);
+    return all_finite6(o, d) && l2 >= 0.999f && l2 <= 1.001f;
+}
+/* pixel (x, y) of a view's frame: its word index in a view-major plane, view_count frames of W * H each */
+ORT_D size_t plane_index(const RenderHot &rv, uint32_t view, uint32_t x, uint32_t y) { return ((size_t)view * (size_t)rv.H + (size_t)y) * (size_t)rv.W + (size_t)x; }
+/* 8x8 block blk of the rect's block grid and pixel-in-block pin -> (x, y); outside: a pixel of an edge block that the rect does not hold */
+struct BlockPixel { int x, y; bool outside; };
+ORT_D BlockPixel block_pixel(const RenderHot &rv, uint32_t blk, uint32_t pin) {
+    const int x = (int)((rv.c->block_x0 + blk % rv.c->blocks_w) * 8u + (pin & 7u));
+    const int y = (int)((rv.c->block_y0 + blk / rv.c->blocks_w) * 8u + (pin >> 3));
+    return BlockPixel{x, y, x < rv.c->x0 || x >= rv.c->x1 || y < rv.c->y0 || y >= rv.c->y1};
+}
+/* tests (ORT_DEBUG_FORCE_FALLBACK): this ray is re-cast exactly whatever the fast traversal found */
+ORT_D bool forced_fallback(const SceneView &sv, V3 dir) {
+    return sv.force_fallback_mask != 0xffffffffu && (om_f32_bits(dir.x) & sv.force_fallback_mask) == 0u;
+}
 
 /* adaptive radiance queries: the luminance of a colour, and the stopping rule after n samples with colour sum C and sum of
    squared sample luminance Q, operation by operation as include/ort.h defines them (every operation rounded on its own: the
@@ -1204,7 +1232,7 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 else p = pixel_ptr(rv, P.jyp >> 16, px, py);
                 p[0] = o.x; p[1] = o.y; p[2] = o.z;
                 if constexpr (ADAPT) { /* JOBS_PIXEL: the pixel's words of its view's planes, view_count frames of W * H each */
-                    const size_t at = ((size_t)P.job_index * (size_t)rv.H + (size_t)py) * (size_t)rv.W + (size_t)px;
+                    const size_t at = plane_index(rv, P.job_index, px, py);
                     if (rv.c->ad_spp) rv.c->ad_spp[at] = P.sample;
                     if (rv.c->ad_m2) rv.c->ad_m2[at] = A->q;
                     if (rv.c->final_states) rv.c->final_states[at] = P.rng;
@@ -1226,23 +1254,16 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
             }
             if (P.ps == PS_NEED_JOB) {
                 if (no_new_job) return false; /* ray exchange, end of the launch: this lane takes a parked path first (pt_lane_x) */
-                unsigned long long j;
-#ifndef ORT_HOST_SIM
-                if (pool) j = draw_job(rv, pool);
-                else
-#endif
-                j = ORT_NEXT_JOB(rv.c->next_job);
+                unsigned long long j = draw_job(rv, pool);
                 if (j >= rv.c->job_count) { P.ps = PS_DONE; break; }
                 if (IMPLICIT && late_flag && j >= rv.c->endgame_from) *late_flag = 1u; /* ray exchange: the launch is near its end (pt_lane_x) */
                 if constexpr (RAYS) {
-                    /* the per-ray domain (include/ort.h): six finite components, |d|^2 within [0.999, 1.001]: what a primary
-                       direction is in the reference.  A ray outside it is answered here, NaN and its seed, without a traversal */
-                    const float2 *r = rv.c->rays + 3ull * j;
+                    /* a ray outside the per-ray domain (in_query_domain) is answered here, NaN and its seed, without a traversal */
+                    const float2 *r = rv.c->rays + 3ull * j; /* load_ray's twin, kept in this form: through the helper the radiance kernels' code moves */
                     const float2 a = r[0], b = r[1], e = r[2];
                     const uint32_t seed = rv.c->seeds[j];
                     const V3 d = mk(b.y, e.x, e.y);
-                    const float l2 = len2(d);
-                    if (!(all_finite6(mk(a.x, a.y, b.x), d) && l2 >= 0.999f && l2 <= 1.001f)) {
+                    if (!in_query_domain(mk(a.x, a.y, b.x), d)) {
                         float *p = rv.c->out + 3u * (size_t)j;
                         p[0] = p[1] = p[2] = om_bits_f32(0x7fc00000u);
                         if (rv.c->final_states) rv.c->final_states[j] = seed;
@@ -1290,6 +1311,7 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                         pin = rem & 63u;
                     }
                     uint32_t blk = rv.c->shard_index + lb * rv.c->shard_count;
+                    /* block_pixel's twin, kept in this form: the render kernels' code moves with the helper's */
                     int x = (int)((rv.c->block_x0 + blk % rv.c->blocks_w) * 8u + (pin & 7u));
                     int y = (int)((rv.c->block_y0 + blk / rv.c->blocks_w) * 8u + (pin >> 3));
                     if (x < rv.c->x0 || x >= rv.c->x1 || y < rv.c->y0 || y >= rv.c->y1) continue;
@@ -1327,10 +1349,9 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
             /* ray.cpp:1215-1221: point on the focal plane through the pixel centre: a function of the pixel alone,
                read back from the per-lane cache or (wavefront mode) recomputed -- same expressions, same bits */
             if constexpr (RAYS) { /* the caller's ray; no aperture, so no angle is drawn */
-                const float2 *r = rv.c->rays + 3ull * (((unsigned long long)P.pxy << 32) | P.job_index);
-                const float2 a = r[0], b = r[1], e = r[2];
-                ray_o = mk(a.x, a.y, b.x);
-                ray_d = mk(b.y, e.x, e.y);
+                const Ray6 r = load_ray(rv.c->rays, ((unsigned long long)P.pxy << 32) | P.job_index);
+                ray_o = r.o;
+                ray_d = r.d;
                 if constexpr (HEMI) { /* the diffuse lobe's draw (sample_brdf_draw without the choice); its azimuth is the pass's one angle */
                     const float e0 = rng_01(P.rng), e1 = rng_01(P.rng);
                     hemi_c = __builtin_sqrtf(e0); /* ray.cpp:1123 */
@@ -1656,7 +1677,7 @@ ORT_D void resolve_hit(const SceneView &sv, const float4 *tab, V3 org, V3 dir, V
         word = pi.chain; mat = pi.mat;
     }
     bool stale = false; /* the winner has changed since */
-    bool recast = sv.force_fallback_mask != 0xffffffffu && (om_f32_bits(dir.x) & sv.force_fallback_mask) == 0u;
+    bool recast = forced_fallback(sv, dir);
     if (!ORT_RARE(recast)) {
         if (ORT_RARE(h.phantom_t <= h.best_t)) {
             recast = true;
@@ -2322,6 +2343,15 @@ ORT_D bool raycast_needs_exact(const RaycastIO &io, V3 org, V3 dir, V3 inv_d) {
                                           org.z >= io.lo[2] && org.z <= io.hi[2]);
     return short_dir || far || inv_nonfinite;
 }
+/* no fast traversal for a ray that has just been started: resolve_hit re-casts it exactly (a phantom that could win) */
+ORT_D void skip_fast_walk(Trav &T, HitState &h) {
+    T.cur = kTraversalDone;
+    h.phantom_t = 0.0f;
+}
+ORT_D float ray_bound(float tm) { return (tm > 0.0f) ? fminf(tm, 3.402823466e+38f) : 0.0f; } /* THE BOUND (at occluded_lane, which keeps a twin of this line); 0 for NaN or <= 0 */
+/* three of a lane's LDS words (job_cache: word k at job_cache[k * kBlock]) as a V3: read, and accumulated by separately rounded adds */
+ORT_D V3 cache_v3(const float *w) { return mk(w[0], w[kBlock], w[2 * kBlock]); }
+ORT_D void cache_add_v3(float *w, V3 v) { w[0] = w[0] + v.x; w[kBlock] = w[kBlock] + v.y; w[2 * kBlock] = w[2 * kBlock] + v.z; }
 
 template <bool COUNTERS, bool TABS>
 ORT_D void raycast_lane(const SceneView &sv, const RenderHot &rv, const RaycastIO &io, const float4 *tab, uint32_t *lds_stack, const int tid,
@@ -2347,18 +2377,14 @@ ORT_D void raycast_lane(const SceneView &sv, const RenderHot &rv, const RaycastI
                 held = false;
             }
             if (more) {
-                const unsigned long long j = pool ? draw_job(rv, pool) : ORT_NEXT_JOB(rv.c->next_job);
+                const unsigned long long j = draw_job(rv, pool);
                 if (j < rv.c->job_count) {
-                    const float2 *r = io.rays + 3ull * j;
-                    const float2 a = r[0], b = r[1], e = r[2];
-                    P.org = mk(a.x, a.y, b.x);
-                    P.dir = mk(b.y, e.x, e.y);
+                    const Ray6 r = load_ray(io.rays, j);
+                    P.org = r.o;
+                    P.dir = r.d;
                     ray = j;
                     begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
-                    if (ORT_RARE(raycast_needs_exact(io, P.org, P.dir, T.inv_d))) {
-                        T.cur = kTraversalDone; /* no fast traversal: resolve_hit re-casts it exactly (a phantom that could win) */
-                        h.phantom_t = 0.0f;
-                    }
+                    if (ORT_RARE(raycast_needs_exact(io, P.org, P.dir, T.inv_d))) skip_fast_walk(T, h);
                     if (COUNTERS) c.rays++;
                     tracing = held = true;
                 } else {
@@ -2436,15 +2462,15 @@ ORT_D void occluded_lane(const SceneView &sv, const RenderHot &rv, const Occlude
                 held = false;
             }
             if (more) {
-                const unsigned long long j = pool ? draw_job(rv, pool) : ORT_NEXT_JOB(rv.c->next_job);
+                const unsigned long long j = draw_job(rv, pool);
                 if (j < rv.c->job_count) {
-                    const float2 *r = io.q.rays + 3ull * j;
-                    const float2 a = r[0], b = r[1], e = r[2];
+                    const Ray6 r = load_ray(io.q.rays, j);
                     const float tm = io.tmax ? io.tmax[j] : __builtin_inff();
-                    P.org = mk(a.x, a.y, b.x);
-                    P.dir = mk(b.y, e.x, e.y);
+                    P.org = r.o;
+                    P.dir = r.d;
                     ray = j;
                     if (COUNTERS) c.rays++;
+                    /* forced_fallback's and ray_bound's twins, kept in this form: through either helper occluded_rays' code moves */
                     const bool forced = sv.force_fallback_mask != 0xffffffffu && (om_f32_bits(P.dir.x) & sv.force_fallback_mask) == 0u;
                     bound = (tm > 0.0f) ? fminf(tm, 3.402823466e+38f) : 0.0f;
                     if (!(tm > 0.0f) && !forced) {
@@ -2457,8 +2483,7 @@ ORT_D void occluded_lane(const SceneView &sv, const RenderHot &rv, const Occlude
                         prologue_tests<COUNTERS, TABS>(sv, tab, P.org, P.dir, T.inv_d, h, c);
                         bool seen = false; /* the prologue's winner is one the reference is certain to test */
                         if (ORT_RARE(forced || raycast_needs_exact(io.q, P.org, P.dir, T.inv_d))) {
-                            T.cur = kTraversalDone; /* no fast traversal: resolve_hit re-casts it exactly (a phantom that could win) */
-                            h.phantom_t = 0.0f;
+                            skip_fast_walk(T, h);
                         } else if (io.mats_nonzero && h.hit_prim != kNoPrim) {
                             const uint32_t word = sv.prim_info[info_index(sv, h.hit_prim)].chain;
                             const uint32_t first = word & 0x07ffffffu;
@@ -2545,7 +2570,7 @@ ORT_D void ao_lane(const SceneView &sv, const RenderHot &rv, const AoIO &io, con
             if (held) { /* the finished sample's verdict */
                 h.runner_t = fminf(h.runner_t, bound); /* the bound is a runner-up the walk may not have seen */
                 resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, org, dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
-                if (!(h.hit_mat != 0u && h.best_t < bound)) { open++; bent[0] = bent[0] + dir.x; bent[kBlock] = bent[kBlock] + dir.y; bent[2 * kBlock] = bent[2 * kBlock] + dir.z; }
+                if (!(h.hit_mat != 0u && h.best_t < bound)) { open++; cache_add_v3(bent, dir); }
                 held = false;
             }
             bool start = false;
@@ -2553,26 +2578,25 @@ ORT_D void ao_lane(const SceneView &sv, const RenderHot &rv, const AoIO &io, con
                 if (busy) {
                     if (sample < io.spp) { start = true; break; }
                     io.open[point] = open;
-                    if (io.bent) { float *b = io.bent + 3ull * point; b[0] = bent[0]; b[1] = bent[kBlock]; b[2] = bent[2 * kBlock]; }
+                    if (io.bent) { float *b = io.bent + 3ull * point; const V3 s = cache_v3(bent); b[0] = s.x; b[1] = s.y; b[2] = s.z; }
                     if (io.states) io.states[point] = rng;
                     busy = false;
                 }
                 if (!more) break;
-                const unsigned long long j = pool ? draw_job(rv, pool) : ORT_NEXT_JOB(rv.c->next_job);
+                const unsigned long long j = draw_job(rv, pool);
                 if (!(j < rv.c->job_count)) { more = false; break; }
-                const float2 *r = io.q.rays + 3ull * j;
+                const float2 *r = io.q.rays + 3ull * j; /* load_ray's twin, kept in this form: through the helper ao_points' code moves */
                 const float2 a = r[0], b = r[1], e = r[2];
                 const uint32_t seed = io.seeds[j];
                 const V3 p = mk(a.x, a.y, b.x), n = mk(b.y, e.x, e.y);
-                const float l2 = len2(n);
-                if (!(all_finite6(p, n) && l2 >= 0.999f && l2 <= 1.001f)) { /* the per-point domain (include/ort.h) */
+                if (!in_query_domain(p, n)) { /* the per-point domain (include/ort.h) */
                     io.open[j] = 0xffffffffu;
                     if (io.bent) { float *o = io.bent + 3ull * j; o[0] = o[1] = o[2] = om_bits_f32(0x7fc00000u); }
                     if (io.states) io.states[j] = seed;
                     continue;
                 }
                 const float tm = io.radius ? io.radius[j] : __builtin_inff();
-                bound = (tm > 0.0f) ? fminf(tm, 3.402823466e+38f) : 0.0f;
+                bound = ray_bound(tm);
                 reach = true;
                 if (io.radius && bound > 0.0f && bound < 3.402823466e+38f && !io.q.tree_spheres) {
                     /* the root's record as traverse reads it: child 0 lo = a.xyz, hi = (a.w, b.x, b.y); child 1 lo = (b.z, b.w, cc.x), hi = cc.yzw */
@@ -2596,13 +2620,13 @@ ORT_D void ao_lane(const SceneView &sv, const RenderHot &rv, const AoIO &io, con
                 const float e0 = rng_01(rng), e1 = rng_01(rng);
                 float sn, cs;
                 ort_sincosf(2.0f * kPi * e1, &sn, &cs);
-                dir = normalize(sample_lobe_n(mk(unit_n[0], unit_n[kBlock], unit_n[2 * kBlock]), __builtin_sqrtf(e0), cs, sn));
+                dir = normalize(sample_lobe_n(cache_v3(unit_n), __builtin_sqrtf(e0), cs, sn));
                 sample++;
                 if (COUNTERS) c.rays++;
                 if (!(bound > 0.0f)) { /* nothing is hit below 1e-6 */
-                    open++; bent[0] = bent[0] + dir.x; bent[kBlock] = bent[kBlock] + dir.y; bent[2 * kBlock] = bent[2 * kBlock] + dir.z;
+                    open++; cache_add_v3(bent, dir);
                 } else {
-                    const bool forced = sv.force_fallback_mask != 0xffffffffu && (om_f32_bits(dir.x) & sv.force_fallback_mask) == 0u;
+                    const bool forced = forced_fallback(sv, dir);
                     T.cur = 0;
                     T.sp = 0;
                     T.inv_d = mk(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z); /* as begin_ray, with the bound for Flt_Max */
@@ -2610,8 +2634,7 @@ ORT_D void ao_lane(const SceneView &sv, const RenderHot &rv, const AoIO &io, con
                     prologue_tests<COUNTERS, TABS>(sv, tab, org, dir, T.inv_d, h, c);
                     bool seen = false; /* the prologue's winner is one the reference is certain to test */
                     if (ORT_RARE(forced || raycast_needs_exact(io.q, org, dir, T.inv_d))) {
-                        T.cur = kTraversalDone; /* no fast traversal: resolve_hit re-casts it exactly (a phantom that could win) */
-                        h.phantom_t = 0.0f;
+                        skip_fast_walk(T, h);
                     } else if (io.mats_nonzero && h.hit_prim != kNoPrim) {
                         const uint32_t word = sv.prim_info[info_index(sv, h.hit_prim)].chain;
                         const uint32_t first = word & 0x07ffffffu;
@@ -2653,7 +2676,7 @@ ao_points(SceneView sv, RenderHot rv, AoIO io) {
  * a surface (mat != 0) counts and adds the material's albedo (emit of a light, diffuse otherwise), n and t to the job's sums,
  * each component a separately rounded add in sample order; the job ends with the sums divided by (float)spp.  Sample 0 also
  * names the pixel's ids.  Nothing else is drawn: the stream advances 2 * spp steps whatever is hit.
- * THE JOB SPACE is [view][8x8 block of the rect][pixel in block], as the PIXEL render's implicit one (produce_ray): a wave's
+ * THE JOB SPACE is [view][8x8 block of the rect][pixel in block], as the PIXEL render's implicit one (produce_ray; block_pixel decodes it here): a wave's
  * jobs are one block -- coherent primary rays, and plane stores that coalesce.  A pixel of an edge block outside the rect is
  * a job that ends where it is drawn.
  * WHERE A SAMPLE STARTS is ao_lane's answer: the idle lanes first settle the finished sample's sums, the job's end and the
@@ -2683,7 +2706,7 @@ ORT_D void feature_lane(const SceneView &sv, const RenderHot &rv, const FeatureI
                 resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
                 if (P.sample == 1u && io.ids) {
                     const uint32_t src = h.hit_prim != kNoPrim ? io.q.prim_src[info_index(sv, h.hit_prim)] : kNoPrim;
-                    const size_t at = ((size_t)P.job_index * (size_t)rv.H + (P.pxy >> 16)) * (size_t)rv.W + (P.pxy & 0xffffu);
+                    const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
                     io.ids[2u * at] = h.hit_mat;
                     io.ids[2u * at + 1u] = src;
                 }
@@ -2694,8 +2717,8 @@ ORT_D void feature_lane(const SceneView &sv, const RenderHot &rv, const FeatureI
                     const V3 a = m.is_light ? m.emit : m.kd;
                     const V3 n = normalize(h.hit_n); /* ray.cpp:817, as raycast_lane returns it */
                     hits++;
-                    job_cache[0] = job_cache[0] + a.x; job_cache[kBlock] = job_cache[kBlock] + a.y; job_cache[2 * kBlock] = job_cache[2 * kBlock] + a.z;
-                    job_cache[3 * kBlock] = job_cache[3 * kBlock] + n.x; job_cache[4 * kBlock] = job_cache[4 * kBlock] + n.y; job_cache[5 * kBlock] = job_cache[5 * kBlock] + n.z;
+                    cache_add_v3(job_cache, a);
+                    cache_add_v3(job_cache + 3 * kBlock, n);
                     job_cache[6 * kBlock] = job_cache[6 * kBlock] + h.best_t;
                 }
                 held = false;
@@ -2704,23 +2727,22 @@ ORT_D void feature_lane(const SceneView &sv, const RenderHot &rv, const FeatureI
             for (;;) { /* the job's end and the next pixel */
                 if (busy) {
                     if (P.sample < spp) { start = true; break; }
-                    const size_t at = ((size_t)P.job_index * (size_t)rv.H + (P.pxy >> 16)) * (size_t)rv.W + (P.pxy & 0xffffu);
+                    const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
                     const float fs = (float)spp; /* ray.cpp:1428's division, component by component */
-                    if (io.albedo) { float *o = io.albedo + 3u * at; o[0] = job_cache[0] / fs; o[1] = job_cache[kBlock] / fs; o[2] = job_cache[2 * kBlock] / fs; }
-                    if (io.normal) { float *o = io.normal + 3u * at; o[0] = job_cache[3 * kBlock] / fs; o[1] = job_cache[4 * kBlock] / fs; o[2] = job_cache[5 * kBlock] / fs; }
+                    if (io.albedo) { float *o = io.albedo + 3u * at; const V3 s = cache_v3(job_cache); o[0] = s.x / fs; o[1] = s.y / fs; o[2] = s.z / fs; }
+                    if (io.normal) { float *o = io.normal + 3u * at; const V3 s = cache_v3(job_cache + 3 * kBlock); o[0] = s.x / fs; o[1] = s.y / fs; o[2] = s.z / fs; }
                     if (io.depth) io.depth[at] = job_cache[6 * kBlock] / fs;
                     if (io.hits) io.hits[at] = hits;
                     if (io.states) io.states[at] = P.rng;
                     busy = false;
                 }
                 if (!more) break;
-                const unsigned long long j = pool ? draw_job(rv, pool) : ORT_NEXT_JOB(rv.c->next_job);
+                const unsigned long long j = draw_job(rv, pool);
                 if (!(j < rv.c->job_count)) { more = false; break; }
                 const uint32_t view = (uint32_t)(j / rv.c->view_jobs), within = (uint32_t)(j % rv.c->view_jobs);
-                const uint32_t lb = within >> 6, pin = within & 63u;
-                const int x = (int)((rv.c->block_x0 + lb % rv.c->blocks_w) * 8u + (pin & 7u));
-                const int y = (int)((rv.c->block_y0 + lb / rv.c->blocks_w) * 8u + (pin >> 3));
-                if (x < rv.c->x0 || x >= rv.c->x1 || y < rv.c->y0 || y >= rv.c->y1) continue;
+                const BlockPixel bp = block_pixel(rv, within >> 6, within & 63u);
+                if (bp.outside) continue;
+                const int x = bp.x, y = bp.y;
                 P.job_index = view;
                 P.pxy = (uint32_t)x | ((uint32_t)y << 16);
                 P.rng = job_seed(om_f32_bits(rv.c->views[4u * (size_t)view].w), (uint32_t)(y * rv.W + x));
@@ -2739,10 +2761,7 @@ ORT_D void feature_lane(const SceneView &sv, const RenderHot &rv, const FeatureI
                 P.dir = normalize(sub(focal, P.org));           /* ray.cpp:1237 */
                 P.sample++;
                 begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
-                if (ORT_RARE(raycast_needs_exact(io.q, P.org, P.dir, T.inv_d))) {
-                    T.cur = kTraversalDone; /* no fast traversal: resolve_hit re-casts it exactly (a phantom that could win) */
-                    h.phantom_t = 0.0f;
-                }
+                if (ORT_RARE(raycast_needs_exact(io.q, P.org, P.dir, T.inv_d))) skip_fast_walk(T, h);
                 if (COUNTERS) c.rays++;
                 tracing = held = true;
             }
@@ -2799,14 +2818,11 @@ ORT_D void radiance_lane(const SceneView &sv, const RenderHot &rv, const float4 
             tracing = produce_ray<COUNTERS, DIFFUSE, TABS, true, false, true, false, HEMI>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool);
             if (tracing) {
                 begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
-                if (P.primary) {
+                if (P.primary) { /* the facts raycast_needs_exact asks for, from the launch's copy (kept in this form: in a helper the radiance kernels' code moves) */
                     RaycastIO q{};
                     q.tree_spheres = rv.c->ray_tree_spheres; q.tree_quadrics = rv.c->ray_tree_quadrics; q.tree_boxes = rv.c->ray_tree_boxes;
                     for (int k = 0; k < 3; ++k) { q.lo[k] = rv.c->ray_lo[k]; q.hi[k] = rv.c->ray_hi[k]; }
-                    if (ORT_RARE(raycast_needs_exact(q, P.org, P.dir, T.inv_d))) {
-                        T.cur = kTraversalDone; /* no fast traversal: resolve_hit re-casts it exactly (a phantom that could win) */
-                        h.phantom_t = 0.0f;
-                    }
+                    if (ORT_RARE(raycast_needs_exact(q, P.org, P.dir, T.inv_d))) skip_fast_walk(T, h);
                 }
                 if (COUNTERS) c.rays++;
             }

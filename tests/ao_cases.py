@@ -125,6 +125,31 @@ def classes(w, radius, spp=SAMPLES):
     return ((occ > 0) & (occ < spp)).mean(), (occ == 0).mean(), (occ == spp).mean()
 
 
+LADDER_POINTS = 64
+LADDER_SEED = 20   # of the draw below: with it 64 of testscene's 64 first samples hit a surface (the test asserts at least 48)
+
+
+def radius_ladder(oracle, osc, flat, n=LADDER_POINTS):
+    """The strict < of a sample's verdict, at one sample per point: n surface points (irradiance_cases.on_surfaces) with arbitrary
+    seeds; t = the oracle's distance along sample 0's direction; each point whose sample hits a surface three times, at radius
+    prev(t), t and next(t), the neighbouring floats: open counts 1, 1, 0.  Points whose sample hits nothing are left out.
+    -> (points (3m, 6), seeds (3m,), radii (3m,), open uint32 (3m,), how many of the n points were left out)"""
+    rng = np.random.default_rng(LADDER_SEED)
+    lo, hi = rc.origin_box(flat)
+    pts = ic.on_surfaces(rng, osc, lo, hi, n)
+    seeds = rng.integers(1, 1 << 32, size=n, dtype=np.uint64).astype("<u4")
+    assert ic.in_domain(pts).all()
+    d0, _, _ = ic.directions(oracle, pts[:, 3:6], seeds)
+    t, _, mat = osc.raycast(pts[:, 0:3], d0)
+    hit = np.flatnonzero(np.asarray(mat) != 0)
+    t = np.asarray(t, "<f4")[hit]
+    assert np.isfinite(t).all() and (t > 0).all()
+    radii = np.stack([np.nextafter(t, F(0)), t, np.nextafter(t, F(np.inf))], axis=1).astype("<f4")
+    assert (radii[:, 0] < t).all() and (t < radii[:, 2]).all() and np.isfinite(radii).all()
+    return (np.repeat(pts[hit], 3, axis=0).astype("<f4"), np.repeat(seeds[hit], 3), radii.reshape(-1),
+            np.tile(np.array([1, 1, 0], "<u4"), len(hit)), n - len(hit))
+
+
 def assert_same(got, want, what):
     """(open, bent, states) against (open, bent, states): all bits, NaN by position; a None on either side is not compared"""
     for g, w_, label in zip(got, want, ("open", "bent", "final states")):

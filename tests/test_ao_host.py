@@ -257,6 +257,22 @@ def test_far_points_fall_back(host_sim, world, tmp_path):
     assert hs.counters(got[3])["fallback"] < 8 * len(near)
 
 
+def test_radius_ladder(host_sim, oracle, load_scene, tmp_path):
+    """ao_cases.radius_ladder on testscene, one sample per point: at a radius one float below the sample's own hit distance and at
+    that distance the sample is open, one float above it is occluded -- by the bounded walk, with the LDS table, and with every
+    sample re-cast exactly (SIM_FORCE_FALLBACK=0: there the closest hit is found at t itself and the comparison alone decides)"""
+    flat = load_scene("testscene").flatten(1, 1)
+    points, seeds, radii, want, left_out = ao.radius_ladder(oracle, oracle.OracleScene(flat), flat)
+    print("radius ladder: %d of %d points left out (their sample hits nothing), %d rungs" % (left_out, ao.LADDER_POINTS, len(points)))
+    assert 4 * left_out <= ao.LADDER_POINTS and 0 < len(points) <= 3 * ao.LADDER_POINTS
+    for env in ({}, {"SIM_TABS": "1"}, {"SIM_FORCE_FALLBACK": "0"}):
+        got = ao.host_sim(host_sim, tmp_path, "testscene", points, seeds, radii, 1, want_bent=False, want_states=False, env=env, threads=8)
+        bad = np.flatnonzero(got[0] != want)
+        assert len(bad) == 0, "%r: %d open counts differ, first at point %d rung %s: %d" % (env, len(bad), bad[0] // 3, ("prev(t)", "t", "next(t)")[bad[0] % 3], got[0][bad[0]])
+        if "SIM_FORCE_FALLBACK" in env:
+            assert hs.counters(got[3])["fallback"] >= len(points)
+
+
 # ---- 4. under the sanitizers ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["testscene", "c2_analytic"])
 def test_host_sim_under_sanitizers(world, tmp_path, name):

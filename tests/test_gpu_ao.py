@@ -120,6 +120,22 @@ def test_a_sample_is_an_occlusion_query(world):
     assert 0 < occ.mean() < 1
 
 
+def test_radius_ladder(oracle, gpu_scene):
+    """ao_cases.radius_ladder's arrays (tests/test_ao_host.py runs them through the lane code on the host), one launch at one sample
+    per point: open one float below the sample's own hit distance and at it, occluded one float above.  What this pins on the device
+    is the bound: a bounded walk that accepted a hit at or beyond its bound, or cut one below it, fails here.  It does not pin the
+    verdict's strict <: the bounded walk never accepts a hit at t == bound, so with <= these samples are still open; only a sample
+    that takes the exact walk shows it, and that is the host test's run under SIM_FORCE_FALLBACK=0 (the device reads its knob at
+    upload, and this is one launch at the defaults)"""
+    scene = gpu_scene("testscene")
+    flat = scene.flatten(1, 1)
+    points, seeds, radii, want, left_out = ao.radius_ladder(oracle, oracle.OracleScene(flat), flat)
+    assert 4 * left_out <= ao.LADDER_POINTS and 0 < len(points) <= 192
+    out, _ = scene.ambient_occlusion(points, seeds, 1, radius=radii)
+    bad = np.flatnonzero(out != want)
+    assert len(bad) == 0, "%d open counts differ, first at point %d rung %s: %d" % (len(bad), bad[0] // 3, ("prev(t)", "t", "next(t)")[bad[0] % 3], out[bad[0]])
+
+
 # ---- 4. counts and guard words ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("count", [1, 63, 65, 513])
 def test_counts_and_guard_words(api, world, count):

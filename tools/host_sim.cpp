@@ -266,6 +266,16 @@ static RenderHot query_hot(Sim &S, RenderView &rv, size_t count) {
     return render_hot<RenderHot>(rv, &rv);
 }
 
+/* what the ray queries' lanes ask of the scene (ray_query_io, ort_setup.h), and the caller's rays or points */
+static RaycastIO sim_query_io(const Sim &S, const float2 *rays = nullptr) {
+    float lo[3], hi[3];
+    scene_origin_box(*S.scene, lo, hi);
+    RaycastIO q{};
+    ray_query_io(*S.scene, lo, hi, &q);
+    q.rays = rays;
+    return q;
+}
+
 static int raycast_mode(char **a) { /* scn base rays.f32 hits.bin */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO)) return rc;
@@ -275,17 +285,13 @@ static int raycast_mode(char **a) { /* scn base rays.f32 hits.bin */
     std::vector<uint2> hits(3 * n);
     std::vector<uint32_t> src;
     if (!invert_prim_slots(S.scene->tree, S.sv.info_box, S.sv.info_cyl, S.sv.info_sphere, src)) { fprintf(stderr, "the tree's slot maps are not a bijection onto its shape arrays\n"); return 1; }
-    float lo[3], hi[3];
-    scene_origin_box(*S.scene, lo, hi);
-    RaycastIO io{};
-    ray_query_io(*S.scene, lo, hi, &io);
-    io.rays = rays.data(); io.hits = hits.data(); io.prim_src = src.data();
+    RaycastIO io = sim_query_io(S, rays.data());
+    io.hits = hits.data(); io.prim_src = src.data();
     RenderView rv{};
     const RenderHot hot = query_hot(S, rv, n);
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
-        if (S.tab) raycast_lane<true, true>(sv, hot, io, S.tab, stack, 0, w, nullptr);
-        else raycast_lane<true, false>(sv, hot, io, nullptr, stack, 0, w, nullptr);
+        with_bools([&](auto T) { raycast_lane<true, decltype(T)::value>(sv, hot, io, S.tab, stack, 0, w, nullptr); }, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     static_assert(sizeof(ort_hit) == 3 * sizeof(uint2), "ort_hit is three 8-byte words");
@@ -302,11 +308,8 @@ static int occluded_mode(char **a) { /* scn base rays.f32 tmax.f32|- out.u8 */
     const bool limits = std::string(a[3]) != "-";
     if (limits && !read_array(a[3], tmax, n, "limits")) return 1;
     std::vector<uint8_t> out(n, (uint8_t)0xee); /* every byte is written: one that is not stays neither 0 nor 1 */
-    float lo[3], hi[3];
-    scene_origin_box(*S.scene, lo, hi);
     OccludedIO io{};
-    ray_query_io(*S.scene, lo, hi, &io.q);
-    io.q.rays = rays.data();
+    io.q = sim_query_io(S, rays.data());
     io.tmax = limits ? tmax.data() : nullptr;
     io.out = out.data();
     io.mats_nonzero = all_mats_nonzero(S.scene->tree);
@@ -314,8 +317,7 @@ static int occluded_mode(char **a) { /* scn base rays.f32 tmax.f32|- out.u8 */
     const RenderHot hot = query_hot(S, rv, n);
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
-        if (S.tab) occluded_lane<true, true>(sv, hot, io, S.tab, stack, 0, w, nullptr);
-        else occluded_lane<true, false>(sv, hot, io, nullptr, stack, 0, w, nullptr);
+        with_bools([&](auto T) { occluded_lane<true, decltype(T)::value>(sv, hot, io, S.tab, stack, 0, w, nullptr); }, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return write_bytes(a[4], out.data(), n) ? 0 : 1;
@@ -336,11 +338,8 @@ static int ao_mode(char **a) { /* scn base points.f32 seeds.u32 radius.f32|- spp
     if (spp == 0u) { fprintf(stderr, "spp must be >= 1\n"); return 1; }
     std::vector<uint32_t> open(n, 0xeeeeeeeeu), states(want_states ? n : 0, 0xddddddddu); /* every word is written: one that is not keeps its filler */
     std::vector<float> bent(want_bent ? 3 * n : 0, -7.0f);
-    float lo[3], hi[3];
-    scene_origin_box(*S.scene, lo, hi);
     AoIO io{};
-    ray_query_io(*S.scene, lo, hi, &io.q);
-    io.q.rays = points.data();
+    io.q = sim_query_io(S, points.data());
     io.seeds = seeds.data();
     io.radius = limits ? radius.data() : nullptr;
     io.open = open.data();
@@ -353,8 +352,7 @@ static int ao_mode(char **a) { /* scn base points.f32 seeds.u32 radius.f32|- spp
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
         std::vector<float> job((kAoCacheWords - 1) * kBlock + 1); /* exactly: a word beyond the lane's six is a write past the block */
-        if (S.tab) ao_lane<true, true>(sv, hot, io, S.tab, stack, job.data(), 0, w, nullptr);
-        else ao_lane<true, false>(sv, hot, io, nullptr, stack, job.data(), 0, w, nullptr);
+        with_bools([&](auto T) { ao_lane<true, decltype(T)::value>(sv, hot, io, S.tab, stack, job.data(), 0, w, nullptr); }, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return write_bytes(a[6], open.data(), 4 * n) && (!want_bent || write_bytes(a[7], bent.data(), 12 * n)) &&
@@ -372,24 +370,16 @@ static int radiance_mode(char **a) { /* scn base rays.f32 seeds.u32 spp rr out.f
     if (!read_rays(a[2], rays, &n) || !read_array(a[3], seeds, n, "seeds")) return 1;
     std::vector<float> out(3 * n, 0.0f);
     std::vector<uint32_t> states(n, 0u);
-    float lo[3], hi[3];
-    scene_origin_box(*S.scene, lo, hi);
-    RaycastIO q{};
-    ray_query_io(*S.scene, lo, hi, &q);
-    q.rays = rays.data();
+    const RaycastIO q = sim_query_io(S, rays.data());
     RenderView rv{};
     radiance_view(q, seeds.data(), (uint32_t)strtoul(a[4], 0, 10), (float)atof(a[5]), out.data(), states.data(), &rv);
     const RenderHot hot = query_hot(S, rv, n);
     const bool diffuse_only = getenv("SIM_DIFFUSE") != nullptr; /* caller vouches for Ks = Kt = 0 */
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
-        if (diffuse_only) {
-            if (S.tab) radiance_lane<true, true, true, false, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
-            else radiance_lane<true, true, false, false, HEMI>(sv, hot, nullptr, stack, 0, w, nullptr);
-        } else {
-            if (S.tab) radiance_lane<true, false, true, false, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
-            else radiance_lane<true, false, false, false, HEMI>(sv, hot, nullptr, stack, 0, w, nullptr);
-        }
+        with_bools([&](auto D, auto T) {
+            radiance_lane<true, decltype(D)::value, decltype(T)::value, false, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
+        }, diffuse_only, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return write_bytes(a[6], out.data(), 12 * n) && write_bytes(a[7], states.data(), 4 * n) ? 0 : 1;
@@ -413,24 +403,16 @@ static int radiance_adaptive_mode(char **a) { /* scn base rays.f32 seeds.u32 min
     if (ad.min_spp < 2u || ad.max_spp < ad.min_spp || ad.max_spp > (1u << 24) || ad.check_every == 0u) { fprintf(stderr, "bad adaptive parameters\n"); return 1; }
     std::vector<float> out(3 * n, 0.0f), m2(n, -1.0f);
     std::vector<uint32_t> spp(n, 0xeeeeeeeeu), states(n, 0u); /* every word is written: one that is not keeps its filler */
-    float lo[3], hi[3];
-    scene_origin_box(*S.scene, lo, hi);
-    RaycastIO q{};
-    ray_query_io(*S.scene, lo, hi, &q);
-    q.rays = rays.data();
+    const RaycastIO q = sim_query_io(S, rays.data());
     RenderView rv{};
     radiance_adaptive_view(q, seeds.data(), ad, (float)atof(a[9]), out.data(), spp.data(), m2.data(), states.data(), &rv);
     const RenderHot hot = query_hot(S, rv, n);
     const bool diffuse_only = getenv("SIM_DIFFUSE") != nullptr; /* caller vouches for Ks = Kt = 0 */
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
-        if (diffuse_only) {
-            if (S.tab) radiance_lane<true, true, true, true, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
-            else radiance_lane<true, true, false, true, HEMI>(sv, hot, nullptr, stack, 0, w, nullptr);
-        } else {
-            if (S.tab) radiance_lane<true, false, true, true, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
-            else radiance_lane<true, false, false, true, HEMI>(sv, hot, nullptr, stack, 0, w, nullptr);
-        }
+        with_bools([&](auto D, auto T) {
+            radiance_lane<true, decltype(D)::value, decltype(T)::value, true, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
+        }, diffuse_only, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return write_bytes(a[10], out.data(), 12 * n) && write_bytes(a[11], spp.data(), 4 * n) && write_bytes(a[12], m2.data(), 4 * n) &&
@@ -601,10 +583,8 @@ static int features_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x
     ort_render_params p{};
     p.width = W; p.height = H; p.x0 = x0; p.y0 = y0; p.x1 = x1; p.y1 = y1;
     p.policy = ORT_POLICY_PIXEL; p.spp = spp;
-    float lo[3], hi[3];
-    scene_origin_box(*S.scene, lo, hi);
     FeatureIO io{};
-    ray_query_io(*S.scene, lo, hi, &io.q);
+    io.q = sim_query_io(S);
     io.q.prim_src = src.data();
     io.albedo = want[0] ? albedo.data() : nullptr; io.normal = want[1] ? normal.data() : nullptr; io.depth = want[2] ? depth.data() : nullptr;
     io.hits = want[3] ? hits.data() : nullptr; io.ids = want[4] ? ids.data() : nullptr; io.states = want[5] ? states.data() : nullptr;
@@ -615,8 +595,7 @@ static int features_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
         std::vector<float> job((kFeatureCacheWords - 1) * kBlock + 1); /* exactly: a word beyond the lane's seven is a write past the block */
-        if (S.tab) feature_lane<true, true>(sv, hot, io, S.tab, stack, job.data(), 0, w, nullptr);
-        else feature_lane<true, false>(sv, hot, io, nullptr, stack, job.data(), 0, w, nullptr);
+        with_bools([&](auto T) { feature_lane<true, decltype(T)::value>(sv, hot, io, S.tab, stack, job.data(), 0, w, nullptr); }, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return (!want[0] || write_bytes(a[11], albedo.data(), 12 * n)) && (!want[1] || write_bytes(a[12], normal.data(), 12 * n)) &&
