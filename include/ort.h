@@ -583,6 +583,69 @@ int ort_render_views_adaptive_device(ort_scene *scene, const ort_render_params *
                                      uint32_t view_count, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states,
                                      void *hip_stream, ort_stats *stats);
 
+/* ---- light-group renders: one frame per group of lights, in one pass ------------------------------
+ * The frame split by which light the energy came from, so that a compositor can re-tint, dim or switch off a light after the
+ * render: G frames, and if asked for the unsplit frame, for about the price of one render instead of G renders of G scenes.
+ * Job.  The job is the ORT_POLICY_PIXEL job of pixel (x, y): all spp camera samples on the stream job_seed(seed, y*W + x)
+ * (views[v].seed in the views form).  The samples are ort_render_image's samples, unchanged, the aperture draw included.
+ * Sums, every operation a separately rounded f32 operation:
+ *  - C is the render's sum.  C_g, for g in [0, G), starts at (+0, +0, +0).
+ *  - Whenever a sample adds a vector e to C -- a light was hit: at the primary hit unguarded (ray.cpp:1254-1259), at a bounce only
+ *    if e is finite (ray.cpp:1358-1371) -- let m be the material that was hit and g = group_of_material[m].  If g < G then
+ *    C_g = C_g + e, component by component: the same e under the same conditions.
+ *  - Entries of materials that are not lights are never read and may hold any byte.  A light whose entry is ORT_NO_LIGHT_GROUP
+ *    is in no group.
+ * Outputs, each plane with row 0 at the bottom:
+ *    out_groups    view_count x G frames of width*height*3 f32; frame (v, g) starts at ((v*G + g) * height*width*3) floats
+ *                  and holds C_g / (float)spp
+ *    out_rgb       view_count frames, view-major: C / (float)spp                        (may be NULL)
+ *    final_states  width*height u32 per view: the stream's state after the job          (may be NULL)
+ * Pixels outside the rect are left untouched in every plane.
+ * Five identities.  (1) out_rgb and final_states are ort_render_image's ORT_POLICY_PIXEL frame and its jobs' final states, bit for
+ * bit.  (2) Frame g is, bit for bit, ort_render_image's ORT_POLICY_PIXEL frame of the scene whose light materials outside group g
+ * have emit = +0 (is_light untouched): that scene has the same geometry and tree, so every path takes the same turns and draws the
+ * same numbers, and its dark lights add +-0, or a NaN that the bounce guard drops, to a sum that started at +0 -- which never
+ * changes it.  (3) Frame g depends only on which materials are in group g: moving other lights between groups, another G, or NULL
+ * for out_rgb or final_states changes no bit of it.  (4) Frame (v, .) of a batch is the single-frame call's for that camera and
+ * seed; the single-frame call is the one-view batch of the scene's own camera (ort_scene_get_camera) and params->seed.  (5) The
+ * frames of a partition of the lights add up to out_rgb only up to rounding, not bit for bit (f32 addition is not associative):
+ * that is why the call offers out_rgb from the same pass.
+ * Parameters.  params->policy must be ORT_POLICY_PIXEL; any other policy is ORT_ERR_UNSUPPORTED.  params->spp is within
+ * [1, 1 << 24], so that (float)spp is exact.  shard_count > 1 and ORT_RENDER_PACKED return ORT_ERR_UNSUPPORTED.  params->chunk is
+ * ignored; rr is judged as the render call judges it (rr >= 0).  The views form follows ort_render_views: params->seed is ignored;
+ * the per-view seed and camera, the rule where a camera may stand, ORT_MAX_VIEWS and view_count == 0 (ORT_OK without a launch,
+ * whatever the other arguments) are as there.
+ * Errors are reported before any device work, in ort_render_views_adaptive's order with the groups where ad stands:
+ * ORT_ERR_INVALID (null out_groups or views, view cap exceeded, null scene or params, empty or bad params exactly as
+ * ort_render_image judges them; then spp above 1 << 24; then groups == NULL, a null table, material_count not the scene's,
+ * group_count 0 or above ORT_MAX_LIGHT_GROUPS, a LIGHT material's entry that is neither < group_count nor ORT_NO_LIGHT_GROUP, a
+ * plane not 4-byte aligned), ORT_ERR_UNSUPPORTED (policy, shard, packed, camera outside the box), ORT_ERR_STATE (scene not
+ * committed), ORT_ERR_NO_DEVICE (not uploaded).
+ * The device forms take DEVICE pointers for the planes on the scene's device, enqueue on hip_stream (NULL = the default stream)
+ * and wait only when stats != NULL; views, the groups struct and its table are HOST memory in every form, copied before the call
+ * returns.  stats as for the render call; with ORT_RENDER_COUNTERS, paths = view_count x rect pixels x spp.  No workspace is
+ * needed: the group sums of a pixel live in its words of out_groups while its job runs. */
+#define ORT_MAX_LIGHT_GROUPS 8u
+#define ORT_NO_LIGHT_GROUP   0xffu
+typedef struct {
+    const uint8_t *group_of_material; /* HOST array in every form, copied before the call returns; material_count entries */
+    uint32_t material_count;          /* must equal the scene's material_count (index 0 included) */
+    uint32_t group_count;             /* G, 1 .. ORT_MAX_LIGHT_GROUPS */
+} ort_light_groups;
+
+/* host planes in, host planes out (device staging is internal); synchronous */
+int ort_render_light_groups(ort_scene *scene, const ort_render_params *params, const ort_light_groups *groups, float *out_groups,
+                            float *out_rgb /* may be NULL */, uint32_t *final_states /* may be NULL */, ort_stats *stats);
+int ort_render_light_groups_device(ort_scene *scene, const ort_render_params *params, const ort_light_groups *groups,
+                                   void *d_out_groups, void *d_out_rgb, void *d_final_states, void *hip_stream, ort_stats *stats);
+/* view_count x G group frames, view_count frames per other plane, view-major */
+int ort_render_views_light_groups(ort_scene *scene, const ort_render_params *params, const ort_light_groups *groups,
+                                  const ort_view *views, uint32_t view_count, float *out_groups, float *out_rgb /* may be NULL */,
+                                  uint32_t *final_states /* may be NULL */, ort_stats *stats);
+int ort_render_views_light_groups_device(ort_scene *scene, const ort_render_params *params, const ort_light_groups *groups,
+                                         const ort_view *views, uint32_t view_count, void *d_out_groups, void *d_out_rgb,
+                                         void *d_final_states, void *hip_stream, ort_stats *stats);
+
 /* ---- first-hit feature renders: albedo, normal, depth, coverage and id planes of the camera -----
  * The noise-free guide planes a denoiser wants next to the colour: what the camera's own samples see FIRST.  A pass of its own on
  * the pixel's own stream, a raycast per sample instead of a path; through the aperture the planes have the distribution of the

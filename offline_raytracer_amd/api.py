@@ -25,6 +25,8 @@ HIT_TRIANGLE, HIT_BOX, HIT_CYLINDER, HIT_SPHERE = 0, 2, 3, 4
 NO_PRIM = 0xFFFFFFFF
 AO_INVALID = 0xFFFFFFFF  # ORT_AO_INVALID: ambient_occlusion()'s open count of a point outside the domain
 MAX_VIEWS = 4096  # ORT_MAX_VIEWS
+MAX_LIGHT_GROUPS = 8     # ORT_MAX_LIGHT_GROUPS
+NO_LIGHT_GROUP = 0xFF    # ORT_NO_LIGHT_GROUP: a light that is in no group
 
 
 class OrtError(RuntimeError):
@@ -123,6 +125,10 @@ class FeaturePlanes(C.Structure):
                 ("final_states", C.c_void_p)]
 
 
+class LightGroups(C.Structure):
+    _fields_ = [("group_of_material", C.c_void_p), ("material_count", C.c_uint32), ("group_count", C.c_uint32)]
+
+
 FEATURE_PLANES = ("albedo", "normal", "depth", "hits", "ids", "states")   # render_features()'s want=
 
 
@@ -152,7 +158,9 @@ EXPORTS = [
     "ort_irradiance", "ort_irradiance_device", "ort_irradiance_adaptive", "ort_irradiance_adaptive_device",
     "ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes",
     "ort_render_adaptive", "ort_render_adaptive_device", "ort_render_views_adaptive", "ort_render_views_adaptive_device",
-    "ort_render_features", "ort_render_features_device", "ort_render_views_features", "ort_render_views_features_device"]
+    "ort_render_features", "ort_render_features_device", "ort_render_views_features", "ort_render_views_features_device",
+    "ort_render_light_groups", "ort_render_light_groups_device", "ort_render_views_light_groups",
+    "ort_render_views_light_groups_device"]
 
 _lib = None
 
@@ -219,6 +227,8 @@ def lib():
                 ("ort_render_views", [vp, C.POINTER(RenderParams), vp, C.c_uint32, vp, stats]),
                 ("ort_render_adaptive", [vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp, vp, stats]),
                 ("ort_render_views_adaptive", [vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, C.c_uint32, vp, vp, vp, vp, stats]),
+                ("ort_render_light_groups", [vp, C.POINTER(RenderParams), C.POINTER(LightGroups), vp, vp, vp, stats]),
+                ("ort_render_views_light_groups", [vp, C.POINTER(RenderParams), C.POINTER(LightGroups), vp, C.c_uint32, vp, vp, vp, stats]),
                 ("ort_render_features", [vp, C.POINTER(RenderParams), C.POINTER(FeaturePlanes), stats]),
                 ("ort_render_views_features", [vp, C.POINTER(RenderParams), vp, C.c_uint32, C.POINTER(FeaturePlanes), stats]),
                 ("ort_raycast", [vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
@@ -558,6 +568,99 @@ class Scene:
         st, stats = _stats(want_stats)
         _check(lib().ort_render_views_adaptive_device(self.handle, C.byref(params), C.byref(ad), views.ctypes.data, len(views),
                                                       _ptr(d_out), _ptr(d_spp), _ptr(d_m2), _ptr(d_states), _ptr(stream), st))
+        return stats()
+
+    # -- light-group renders: one frame per group of lights, in one pass --------------------------
+    def light_materials(self):
+        """the indices of the materials that are lights, ascending"""
+        return [int(m) for m in np.nonzero(self._get("materials", MATERIAL_DTYPE, self.info().material_count)["is_light"])[0]]
+
+    def _light_groups(self, groups, group_count):
+        """groups -> (the ort_light_groups struct, the table that it points into, G).  groups: a byte per material of the scene,
+        or a dict {material index: group} with every other material NO_LIGHT_GROUP.  group_count: G, by default one more
+        than the largest group named."""
+        n = self.info().material_count
+        if isinstance(groups, dict):
+            table = np.full(n, NO_LIGHT_GROUP, np.uint8)
+            for m, g in groups.items():
+                if not 0 <= int(m) < n:
+                    raise ValueError("groups: material %d is not one of the scene's %d" % (m, n))
+                table[int(m)] = g
+        else:
+            table = np.ascontiguousarray(groups, dtype=np.uint8)
+            if table.shape != (n,):
+                raise ValueError("groups must hold a byte per material: shape (%d,), got %s" % (n, table.shape))
+        if group_count is None:
+            named = table[table != NO_LIGHT_GROUP] if isinstance(groups, dict) else table[self.light_materials()]
+            named = named[named != NO_LIGHT_GROUP]
+            group_count = int(named.max()) + 1 if len(named) else 1
+        return LightGroups(table.ctypes.data, n, group_count), table, int(group_count)
+
+    @staticmethod
+    def _group_planes(shape, G, want_rgb, want_states, out):
+        """the host planes of a light-group render: zeros, or the caller's (out: (groups[, rgb][, states]), checked)"""
+        lead, hw = shape[:-2], shape[-2:]
+        specs = [(lead + (G,) + hw + (3,), "<f4")] + ([(shape + (3,), "<f4")] if want_rgb else []) + ([(shape, "<u4")] if want_states else [])
+        if out is None:
+            return [np.zeros(sh, dt) for sh, dt in specs]
+        if len(out) != len(specs):
+            raise ValueError("out must hold %d planes (groups%s%s), got %d" % (len(specs), ", rgb" if want_rgb else "", ", states" if want_states else "", len(out)))
+        for a, (sh, dt) in zip(out, specs):
+            if not isinstance(a, np.ndarray) or a.shape != sh or a.dtype != np.dtype(dt) or not a.flags.c_contiguous:
+                raise ValueError("out: every plane must be a C-contiguous array, expected shape %s dtype %s" % (sh, dt))
+        return list(out)
+
+    def render_light_groups(self, width, height, spp, seed, groups, want_rgb=True, want_states=False, group_count=None, rect=None,
+                            rr=0.8, counters=False, out=None):
+        """render(policy="pixel") split by which light the energy came from, in one pass: frame g holds what the lights of
+        group g contribute and is, bit for bit, the render of the scene with every other light's emission set to zero
+        (include/ort.h gives the contract).  groups: a length-material_count sequence of group indices (a light's entry below
+        G or NO_LIGHT_GROUP; other materials' entries are not read), or a dict {material index: group}, e.g. {m: i for i, m
+        in enumerate(scene.light_materials())}.  Returns (frames (G, H, W, 3) float32[, rgb (H, W, 3) float32 the unsplit
+        frame][, states (H, W) uint32], stats dict).  Pixels outside rect keep what out's planes held."""
+        lg, table, G = self._light_groups(groups, group_count)
+        planes = self._group_planes((height, width), G, want_rgb, want_states, out)
+        p = self.params(width, height, spp, seed, "pixel", 0, rect, rr, counters)
+        st, stats = _stats()
+        _check(lib().ort_render_light_groups(self.handle, C.byref(p), C.byref(lg), planes[0].ctypes.data,
+                                             planes[1].ctypes.data if want_rgb else None,
+                                             planes[-1].ctypes.data if want_states else None, st))
+        return tuple(planes) + (stats(),)
+
+    def render_light_groups_device(self, params, groups, d_groups, d_rgb=0, d_states=0, group_count=None, stream=None, want_stats=False):
+        """The same into device planes (raw device pointers, e.g. torch tensors' data_ptr(): (G, H, W, 3) float32 and, where a
+        pointer is given, (H, W, 3) float32 / (H, W) uint32).  params: Scene.params(..., policy="pixel").  Enqueued on stream;
+        waits only when want_stats (returns the stats dict)."""
+        lg, table, _ = self._light_groups(groups, group_count)
+        st, stats = _stats(want_stats)
+        _check(lib().ort_render_light_groups_device(self.handle, C.byref(params), C.byref(lg), _ptr(d_groups), _ptr(d_rgb), _ptr(d_states),
+                                                    _ptr(stream), st))
+        return stats()
+
+    def render_views_light_groups(self, cameras, seeds, width, height, spp, groups, want_rgb=True, want_states=False, group_count=None,
+                                  rect=None, rr=0.8, counters=False, out=None):
+        """render_light_groups for a batch of views in one launch (cameras, seeds as render_views): frames (v, .) are what
+        render_light_groups gives with seed seeds[v] if the scene's camera were cameras[v].  Returns (frames (V, G, H, W, 3)[,
+        rgb (V, H, W, 3)][, states (V, H, W)], stats dict)."""
+        views = _views(cameras, seeds)
+        lg, table, G = self._light_groups(groups, group_count)
+        planes = self._group_planes((len(views), height, width), G, want_rgb, want_states, out)
+        p = self.params(width, height, spp, 0, "pixel", 0, rect, rr, counters)
+        st, stats = _stats()
+        _check(lib().ort_render_views_light_groups(self.handle, C.byref(p), C.byref(lg), views.ctypes.data, len(views), planes[0].ctypes.data,
+                                                   planes[1].ctypes.data if want_rgb else None,
+                                                   planes[-1].ctypes.data if want_states else None, st))
+        return tuple(planes) + (stats(),)
+
+    def render_views_light_groups_device(self, params, cameras, seeds, groups, d_groups, d_rgb=0, d_states=0, group_count=None,
+                                         stream=None, want_stats=False):
+        """The same into device planes, view-major: (V, G, H, W, 3), (V, H, W, 3), (V, H, W).  Enqueued on stream; waits only
+        when want_stats (returns the stats dict).  params.seed is ignored."""
+        views = _views(cameras, seeds)
+        lg, table, _ = self._light_groups(groups, group_count)
+        st, stats = _stats(want_stats)
+        _check(lib().ort_render_views_light_groups_device(self.handle, C.byref(params), C.byref(lg), views.ctypes.data, len(views),
+                                                          _ptr(d_groups), _ptr(d_rgb), _ptr(d_states), _ptr(stream), st))
         return stats()
 
     # -- first-hit feature renders: albedo, normal, depth, coverage and id planes ---------------

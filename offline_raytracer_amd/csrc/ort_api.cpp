@@ -565,6 +565,51 @@ static int render_adaptive_common(ort_scene *s, const ort_render_params *p, cons
     return run_render(s, &q, c, out_rgb, out_spp, out_m2, states);
 }
 
+/* Light-group renders, one frame or a batch of views: render_adaptive_common's order with the groups where ad stands.
+   view_count == 0 is OK whatever else is passed (the views form); then nulls (out_groups, views) and the view cap, the params as the
+   render call judges them (chunk is not the caller's to set here), spp above 1 << 24, the groups (null struct or table, another
+   material count than the scene's, a group count outside [1, ORT_MAX_LIGHT_GROUPS], a light's entry that names no group and is not
+   ORT_NO_LIGHT_GROUP; other materials' entries are not read) and the planes' alignment, what the call does not do (any policy but
+   PIXEL, shards, a packed framebuffer, a camera outside the box), the scene's state.  !batch: the single-frame form (views unread),
+   the one-view batch of the scene's own camera and params->seed */
+static int render_groups_common(ort_scene *s, const ort_render_params *p, const ort_light_groups *groups, const ort_view *views, uint32_t view_count,
+                                bool batch, bool host, void *out_groups, void *out_rgb, void *states, void *stream, ort_stats *stats) {
+    if (batch && view_count == 0) return nothing_to_do(stats);
+    if (batch && (!views || !out_groups)) return fail(ORT_ERR_INVALID, "null views or group frames");
+    if (!batch && !out_groups) return fail(ORT_ERR_INVALID, host ? "null group frames" : "null device group frames");
+    if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
+    if (!s || !p) return fail(ORT_ERR_INVALID, "null scene or params");
+    ort_render_params q = *p;
+    q.chunk = q.spp;
+    int rc = check_param_values(s, &q);
+    if (rc != ORT_OK) return rc;
+    if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp must be <= 1 << 24: a sample count must be exact in float");
+    if (!groups) return fail(ORT_ERR_INVALID, "null groups (the light-group table)");
+    if (!groups->group_of_material) return fail(ORT_ERR_INVALID, "null group_of_material");
+    if (groups->material_count != s->materials.size()) return fail(ORT_ERR_INVALID, "groups->material_count is not the scene's material count");
+    if (groups->group_count == 0 || groups->group_count > ORT_MAX_LIGHT_GROUPS) return fail(ORT_ERR_INVALID, "group_count must be within [1, ORT_MAX_LIGHT_GROUPS]");
+    for (size_t m = 0; m < s->materials.size(); ++m)
+        if (s->materials[m].is_light && groups->group_of_material[m] >= groups->group_count && groups->group_of_material[m] != ORT_NO_LIGHT_GROUP)
+            return fail(ORT_ERR_INVALID, "light material " + std::to_string(m) + ": its group is neither below group_count nor ORT_NO_LIGHT_GROUP");
+    rc = check_ptrs({{out_groups, true, 4}, {out_rgb, false, 4}, {states, false, 4}}, "", "", "out_groups, out_rgb and final_states must be 4-byte aligned");
+    if (rc != ORT_OK) return rc;
+    if (q.policy != ORT_POLICY_PIXEL) return fail(ORT_ERR_UNSUPPORTED, "the light-group render splits one-pixel jobs: it needs the PIXEL policy");
+    if (q.shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, "the light-group render is not sharded");
+    if (q.flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "the light-group render has no packed framebuffer");
+    ort_view own;
+    if (batch) {
+        if ((rc = check_views_in_box(s, views, view_count)) != ORT_OK) return rc;
+    } else {
+        ort::camera_basis(*s, q.width, q.height, &own.camera);
+        own.seed = q.seed;
+        views = &own;
+    }
+    if ((rc = check_resident(s)) != ORT_OK) return rc;
+    ort::RenderCall c{host, stream, stats};
+    c.views = views; c.view_count = view_count; c.groups = groups; c.out_groups = out_groups;
+    return run_render(s, &q, c, out_rgb, nullptr, nullptr, states);
+}
+
 /* First-hit feature renders, one frame or a batch of views: render_adaptive_common's order with the planes where ad stands.
    view_count == 0 is OK whatever else is passed (the views form); then nulls (the planes struct, all five feature planes, views) and
    the view cap, the params as the render call judges them (chunk and rr are not the caller's to set here), spp above 1 << 24 and the
@@ -723,6 +768,10 @@ int ort_render_views_device(ort_scene *s, const ort_render_params *p, const ort_
 int ort_render_adaptive(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, nullptr, 1, false, true, out_rgb, out_spp, out_m2, final_states, nullptr, stats); }); }
 int ort_render_adaptive_device(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, nullptr, 1, false, false, d_out_rgb, d_out_spp, d_out_m2, d_final_states, hip_stream, stats); }); }
 int ort_render_views_adaptive(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, const ort_view *views, uint32_t view_count, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, views, view_count, true, true, out_rgb, out_spp, out_m2, final_states, nullptr, stats); }); }
+int ort_render_light_groups(ort_scene *s, const ort_render_params *p, const ort_light_groups *groups, float *out_groups, float *out_rgb, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_groups_common(s, p, groups, nullptr, 1, false, true, out_groups, out_rgb, final_states, nullptr, stats); }); }
+int ort_render_light_groups_device(ort_scene *s, const ort_render_params *p, const ort_light_groups *groups, void *d_out_groups, void *d_out_rgb, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_groups_common(s, p, groups, nullptr, 1, false, false, d_out_groups, d_out_rgb, d_final_states, hip_stream, stats); }); }
+int ort_render_views_light_groups(ort_scene *s, const ort_render_params *p, const ort_light_groups *groups, const ort_view *views, uint32_t view_count, float *out_groups, float *out_rgb, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_groups_common(s, p, groups, views, view_count, true, true, out_groups, out_rgb, final_states, nullptr, stats); }); }
+int ort_render_views_light_groups_device(ort_scene *s, const ort_render_params *p, const ort_light_groups *groups, const ort_view *views, uint32_t view_count, void *d_out_groups, void *d_out_rgb, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_groups_common(s, p, groups, views, view_count, true, false, d_out_groups, d_out_rgb, d_final_states, hip_stream, stats); }); }
 int ort_render_views_adaptive_device(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, const ort_view *views, uint32_t view_count, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, views, view_count, true, false, d_out_rgb, d_out_spp, d_out_m2, d_final_states, hip_stream, stats); }); }
 int ort_render_features(ort_scene *s, const ort_render_params *p, const ort_feature_planes *planes, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, nullptr, 1, false, true, planes, nullptr, stats); }); }
 int ort_render_features_device(ort_scene *s, const ort_render_params *p, const ort_feature_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, nullptr, 1, false, false, planes, hip_stream, stats); }); }

@@ -76,6 +76,8 @@ struct DeviceScene {
     DevBuf rv_dev; /* the RenderView of the render in flight (RenderHot::c) */
     DevBuf view_tab; /* ... and, for a batch of views, its camera table (RenderView::views) */
     std::vector<float> view_tab_host; /* the source of that upload: the scene's, so that it outlives a call that does not wait */
+    DevBuf group_tab; /* ... and, for a light-group render, its group table (RenderView::group_of_material), uploaded per call */
+    std::vector<uint8_t> group_tab_host; /* likewise its source */
     uint32_t tab_flags = 0;
     uint32_t light_count = 0;
     bool diffuse_only = false; /* no surface material can enter the specular / transmission blocks */
@@ -278,6 +280,10 @@ static int launch_adaptive(DeviceScene *, const LaunchPlan &pl, const SceneView 
     ort_launch_render_adaptive(plan_variant(pl), pl.grid, stream, sv, hot);
     return ORT_OK;
 }
+static int launch_groups(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
+    ort_launch_render_groups(plan_variant(pl), pl.grid, stream, sv, hot);
+    return ORT_OK;
+}
 
 /* What launches each of the built kernels (kBuiltKernels, ort_plan.h), in that list's order: a kernel of this unit, which its
    entry here instantiates, or the host function that launches what another family is made of */
@@ -294,6 +300,7 @@ template <bool C, bool D>
 constexpr Launcher exchange() { return {{KF_EXCHANGE, C, D, true, true, false}, pt_persistent_x<C, D>, nullptr}; }
 constexpr Launcher five(bool d) { return {{KF_FIVE, false, d, true, true, false}, nullptr, launch_five_waves}; }
 constexpr Launcher adaptive(bool c, bool d, bool t) { return {{KF_ADAPTIVE, c, d, t, true, false}, nullptr, launch_adaptive}; }
+constexpr Launcher groups(bool c, bool d, bool t) { return {{KF_GROUPS, c, d, t, true, false}, nullptr, launch_groups}; }
 constexpr Launcher kLaunchers[] = {
     {{KF_WAVEFRONT, false, false, false, false, false}, nullptr, launch_wavefront<false>},
     {{KF_WAVEFRONT, true, false, false, false, false}, nullptr, launch_wavefront<true>},
@@ -307,6 +314,8 @@ constexpr Launcher kLaunchers[] = {
     five(false), five(true),
     adaptive(false, false, false), adaptive(false, false, true), adaptive(false, true, false), adaptive(false, true, true),
     adaptive(true, false, false), adaptive(true, false, true), adaptive(true, true, false), adaptive(true, true, true),
+    groups(false, false, false), groups(false, false, true), groups(false, true, false), groups(false, true, true),
+    groups(true, false, false), groups(true, false, true), groups(true, true, false), groups(true, true, true),
 };
 constexpr bool launchers_match(size_t i = 0) { return i == kBuiltKernelCount || (kLaunchers[i].variant == kBuiltKernels[i] && launchers_match(i + 1)); }
 static_assert(sizeof(kLaunchers) / sizeof(kLaunchers[0]) == kBuiltKernelCount && launchers_match(),
@@ -491,8 +500,8 @@ static int print_util_diag(const DeviceScene *d, std::string *err) {
     return ORT_OK;
 }
 
-/* The camera render call, plain or (c.ad) adaptive.  What runs, on which grid and with which thresholds is plan_render's or
-   plan_render_adaptive's decision (ort_plan.h), and what the RenderView says besides pointers is render_view's (ort_setup.h); this
+/* The camera render call, plain, (c.ad) adaptive or (c.groups) split by light group.  What runs, on which grid and with which
+   thresholds is plan_render's, plan_render_adaptive's or plan_render_groups' decision (ort_plan.h), and what the RenderView says besides pointers is render_view's (ort_setup.h); this
    is the plumbing around them: settle the previous call, plan, staging, views, buffers, launch, combine, finish */
 int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c, void *out_rgb, void *out_spp, void *out_m2, void *states, std::string *err) {
     DeviceScene *d = scene->dev;
@@ -507,7 +516,8 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
 
     SceneView sv = scene_view(scene, d);
     const SceneTraits traits = scene_traits(scene, d);
-    const LaunchPlan pl = c.ad ? plan_render_adaptive(traits, *p, d->knobs, view_count)
+    const LaunchPlan pl = c.groups ? plan_render_groups(traits, *p, d->knobs, view_count)
+                          : c.ad ? plan_render_adaptive(traits, *p, d->knobs, view_count)
                                : plan_render(traits, *p, c.jobs != nullptr, c.job_count, /* w5_layout_ok */ true, d->knobs, view_count);
     sv.util = pl.util ? d->ctrl() + 8 : nullptr;
     if (pl.wide) sv.nodes = d->nodes4.as<const float4>();
@@ -523,13 +533,22 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     /* the planes as the lanes see them: the caller's device pointers, or the scene's staging buffers holding the caller's words.
        view_count frames, view-major, or the packed framebuffer; the 4-byte planes stage where the radiance queries' do */
     const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
-    Plane planes[4] = {{out_rgb, &d->staging, rv.packed_out ? (size_t)rv.my_blocks * 768u : pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u, nullptr},
-                       {out_m2, &d->query_stage[4], pixels * 4u, nullptr}, {states, &d->query_stage[5], pixels * 4u, nullptr}};
-    if ((rc = stage_planes_in(planes, 4, c.host, stream, err))) return rc;
+    Plane planes[5] = {{out_rgb, &d->staging, rv.packed_out ? (size_t)rv.my_blocks * 768u : pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u, nullptr},
+                       {out_m2, &d->query_stage[4], pixels * 4u, nullptr}, {states, &d->query_stage[5], pixels * 4u, nullptr},
+                       {c.out_groups, &d->query_stage[0], pixels * 12u * (c.groups ? c.groups->group_count : 0u), nullptr}};
+    if ((rc = stage_planes_in(planes, 5, c.host, stream, err))) return rc;
     rv.out = (float *)planes[0].dev;
     rv.ad_spp = (uint32_t *)planes[1].dev;
     rv.ad_m2 = (float *)planes[2].dev;
     rv.final_states = (uint32_t *)planes[3].dev;
+    if (c.groups) { /* the group table, the scene's copy of it on its way to the device; the previous call was settled above */
+        d->group_tab_host.assign(c.groups->group_of_material, c.groups->group_of_material + c.groups->material_count);
+        if ((rc = d->group_tab.ensure(d->group_tab_host.size(), err))) return rc;
+        ORT_HIP(hipMemcpyAsync(d->group_tab.p, d->group_tab_host.data(), d->group_tab_host.size(), hipMemcpyHostToDevice, stream));
+        rv.group_of_material = d->group_tab.as<const uint8_t>();
+        rv.group_count = c.groups->group_count;
+        rv.group_out = (float *)planes[4].dev;
+    }
     if (c.jobs) {
         if ((rc = d->jobs.ensure((size_t)c.job_count * sizeof(ort_tile_job), err))) return rc;
         /* synchronous: the caller's job list may be gone when this call returns */
@@ -572,7 +591,7 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     }
     if ((rc = end_kernels(d, c.stats != nullptr, stream, err))) return rc;
 
-    if ((rc = stage_planes_out(planes, 4, c.host, stream, err))) return rc;
+    if ((rc = stage_planes_out(planes, 5, c.host, stream, err))) return rc;
     if (c.job_states) ORT_HIP(hipMemcpyAsync(c.job_states, d->states.p, (size_t)c.job_count * 4u, hipMemcpyDeviceToHost, stream));
     /* every synchronous form of the call checks the tripwire before it returns (the fire-and-forget device form, stats == NULL,
        cannot without a sync: the next call on the scene does; bench.py asks for stats) */

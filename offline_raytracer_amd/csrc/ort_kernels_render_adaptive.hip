@@ -1,13 +1,15 @@
 /*
- * ort_kernels_render_adaptive.hip -- the kernels of the adaptive camera render (ort_render_adaptive, ort_render_views_adaptive):
- * pt_adaptive.
+ * ort_kernels_render_adaptive.hip -- the kernels of the camera renders that run one-pixel jobs over a batch of views with something
+ * added to the plain loop: the adaptive render (ort_render_adaptive, ort_render_views_adaptive: pt_adaptive) and the light-group
+ * render (ort_render_light_groups, ort_render_views_light_groups: pt_groups).
  *
  * The lane code (ort_lane.h) compiled a fourth time, at the limits of ort_kernels.hip proper (four waves per SIMD, 24 LDS stack
- * entries), for the eight variants of pt_lane<..., VIEWS = true, ADAPT = true> only.  A unit of its own for the reason
- * ort_kernels_adaptive.hip is one: eight more path-trace kernels are compile time that ort_kernels.hip, the unit that sets the
- * build's wall time, should not carry; here they compile beside the others (under make -j4 the four units build at once;
- * profiles/r12_render_adaptive.md).  device_render (ort_kernels.hip), given a stopping rule, launches them through
- * ort_launch_render_adaptive.
+ * entries), for the eight variants of pt_lane<..., VIEWS = true, ADAPT = true> and the eight of pt_lane<..., VIEWS = true,
+ * GROUPS = true> only.  A unit of its own for the reason ort_kernels_adaptive.hip is one: more path-trace kernels are compile
+ * time that ort_kernels.hip, the unit that sets the build's wall time, should not carry; here they compile beside the others
+ * (profiles/r12_render_adaptive.md, profiles/r21_light_groups.md).  The light-group kernels share this unit, sixteen kernels as
+ * the irradiance unit holds, instead of adding a sixth.  device_render (ort_kernels.hip), given a stopping rule or a group table,
+ * launches them through ort_launch_render_adaptive or ort_launch_render_groups.
  */
 #define ORT_NS ort_ra /* the limits: ort_lane.h's defaults */
 #include "ort_lane.h"
@@ -18,5 +20,13 @@ void ort_launch_render_adaptive(const ort::KernelVariant &v, unsigned int grid, 
     using namespace ort_ra;
     ort::with_bools([&](auto C, auto D, auto T) {
         hipLaunchKernelGGL((pt_adaptive<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, stream, sv, hot);
+    }, v.counters, v.diffuse, v.tabs);
+}
+
+/* KF_GROUPS: likewise */
+void ort_launch_render_groups(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot) {
+    using namespace ort_ra;
+    ort::with_bools([&](auto C, auto D, auto T) {
+        hipLaunchKernelGGL((pt_groups<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, stream, sv, hot);
     }, v.counters, v.diffuse, v.tabs);
 }

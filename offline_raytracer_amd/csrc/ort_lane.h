@@ -14,7 +14,7 @@
  * Included by five translation units: ort_kernels.hip (the library's kernels at four waves per SIMD, and the host side),
  * ort_kernels_w5.hip (the plain-loop kernels at FIVE: 96 registers, 20 LDS stack entries, built with machine LICM off),
  * ort_kernels_adaptive.hip (the adaptive radiance queries' kernels, at the first unit's limits: a unit of their own so that they
- * compile beside it), ort_kernels_render_adaptive.hip (the adaptive camera render's, likewise) and ort_kernels_irradiance.hip (the
+ * compile beside it), ort_kernels_render_adaptive.hip (the adaptive camera render's and the light-group render's, likewise) and ort_kernels_irradiance.hip (the
  * irradiance queries', likewise).  Same lane code, other limits
  * (ORT_WAVES_PER_EU, ORT_LDS_STACK, ORT_SPILL_STACK); each unit compiles it in a namespace of its own, which it names beside
  * its limits (ORT_NS; `ort` when it names none), so that two builds of one template are two symbols.  What does not depend on a
@@ -147,6 +147,13 @@ struct RenderView {
     float ad_tolerance, ad_floor;
     uint32_t *ad_spp;
     float *ad_m2;
+    /* light-group renders (ort_render_light_groups; the pt_groups kernels): group_of_material holds a byte per material of the
+       scene, read only for a light that was hit; group_out holds view_count x group_count frames of W * H * 3 floats, frame
+       (v, g) at (v * group_count + g) * W * H * 3, and its words ARE the pixel's group sums while its job runs.  out and
+       final_states (a plane of view_count * W * H words, as the adaptive render's) may each be null */
+    const uint8_t *group_of_material;
+    uint32_t group_count;
+    float *group_out;
 };
 
 /* ---- the order in which a CHUNK render issues its jobs ----------------------------------------------------------
@@ -249,6 +256,7 @@ struct FeatureIO {
    QueryPlan; every other bool of the kernels is fixed by the family. */
 void ort_launch_w5(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);              /* KF_FIVE: ort_kernels_w5.hip */
 void ort_launch_render_adaptive(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot); /* KF_ADAPTIVE: ort_kernels_render_adaptive.hip */
+void ort_launch_render_groups(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);   /* KF_GROUPS: ort_kernels_render_adaptive.hip */
 void ort_launch_radiance_adaptive(const ort::QueryPlan &pl, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);                    /* ort_kernels_adaptive.hip */
 void ort_launch_irradiance(const ort::QueryPlan &pl, bool adaptive, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);            /* ort_kernels_irradiance.hip */
 #endif
@@ -1056,6 +1064,10 @@ ORT_D bool in_query_domain(V3 o, V3 d) {
 }
 /* pixel (x, y) of a view's frame: its word index in a view-major plane, view_count frames of W * H each */
 ORT_D size_t plane_index(const RenderHot &rv, uint32_t view, uint32_t x, uint32_t y) { return ((size_t)view * (size_t)rv.H + (size_t)y) * (size_t)rv.W + (size_t)x; }
+/* light-group renders: pixel pxy's three words of frame (view, g) of rv.c->group_out */
+ORT_D float *group_pixel_ptr(const RenderHot &rv, uint32_t view, uint32_t g, uint32_t pxy) {
+    return rv.c->group_out + 3u * plane_index(rv, view * rv.c->group_count + g, pxy & 0xffffu, pxy >> 16);
+}
 /* 8x8 block blk of the rect's block grid and pixel-in-block pin -> (x, y); outside: a pixel of an edge block that the rect does not hold */
 struct BlockPixel { int x, y; bool outside; };
 ORT_D BlockPixel block_pixel(const RenderHot &rv, uint32_t blk, uint32_t pin) {
@@ -1106,13 +1118,20 @@ ORT_D bool adaptive_stop(V3 C, float Q, uint32_t n, float tolerance, float lum_f
    phi = 2 pi e1), sample_lobe about n (ray.cpp:1065-1091) and normalize for d.  phi is the angle of the one converged sin/cos below;
    from d on the sample is RAYS' for the ray (p, d): direction d as it stands, wo = -normalize(d).  Everything of it sits under
    if constexpr (HEMI) */
+/* GROUPS: light-group renders (ort_render_light_groups; with VIEWS, one-pixel jobs in JOBS_PIXEL mode): whenever a sample adds an
+   emission e to the pixel's sum, the same e is added to the sum of the hit light's group (rv.c->group_of_material, a byte per
+   material in HBM, read here alone; a group at or above group_count is no group).  The G sums are the pixel's own words of the G
+   output frames: the job belongs to this lane from start to end, so it zeroes them at the pixel's start, loads, adds and stores one
+   triple per emission and divides them in place at the job's end -- no registers, no LDS, no atomics.  The render's own frame and
+   the final states are optional planes.  Everything of it sits under if constexpr (GROUPS) */
 template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool VIEWS = false, bool RAYS = false, bool ADAPT = false,
-          bool HEMI = false>
+          bool HEMI = false, bool GROUPS = false>
 ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, Prof &pr,
                        float *focal_cache = nullptr, int focal_stride = 0, uint32_t spp_u = 0, uint32_t *late_flag = nullptr, bool no_new_job = false,
                        unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
     static_assert(!ADAPT || (IMPLICIT && (RAYS || VIEWS)), "the adaptive rule is built for the radiance queries and for one-pixel jobs of a batch of views");
     static_assert(!HEMI || RAYS, "the hemisphere draw starts a sample of a radiance query's job");
+    static_assert(!GROUPS || (IMPLICIT && VIEWS && !RAYS && !ADAPT), "the group sums are built for plain one-pixel jobs of a batch of views");
     /* VIEWS: unused; every lane reads its view's camera where it needs it (load_view_camera) */
     const V3 cam_p = mk(sv.cam[0], sv.cam[1], sv.cam[2]);
     const V3 cam_x = mk(sv.cam[3], sv.cam[4], sv.cam[5]);
@@ -1150,6 +1169,13 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 if (P.primary || (!isnan3(e) && !isinf3(e))) {
                     P.color = add(P.color, e);
                     if constexpr (ADAPT) { const float y = adaptive_luminance(e); A->q = A->q + y * y; }
+                    if constexpr (GROUPS) {
+                        const uint32_t g = rv.c->group_of_material[hit_mat];
+                        if (g < rv.c->group_count) {
+                            float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
+                            q[0] = q[0] + e.x; q[1] = q[1] + e.y; q[2] = q[2] + e.z;
+                        }
+                    }
                 }
                 alive = false;
             } else {
@@ -1227,10 +1253,20 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                     P.ps = PS_NEED_JOB;
                 } else {
                 uint32_t px = P.pxy & 0xffffu, py = P.pxy >> 16;
+                if constexpr (GROUPS) { /* JOBS_PIXEL: the G sums become means where they stand; the frame and the states if asked for */
+                    const float fs = (float)job_spp;
+                    for (uint32_t g = 0; g < rv.c->group_count; ++g) {
+                        float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
+                        q[0] = q[0] / fs; q[1] = q[1] / fs; q[2] = q[2] / fs;
+                    }
+                    if (rv.c->out) { float *p = view_pixel_ptr(rv, P.job_index, 0u, px, py); p[0] = o.x; p[1] = o.y; p[2] = o.z; }
+                    if (rv.c->final_states) rv.c->final_states[plane_index(rv, P.job_index, px, py)] = P.rng;
+                } else {
                 float *p;
                 if constexpr (VIEWS) p = view_pixel_ptr(rv, P.job_index, P.jyp >> 16, px, py);
                 else p = pixel_ptr(rv, P.jyp >> 16, px, py);
                 p[0] = o.x; p[1] = o.y; p[2] = o.z;
+                }
                 if constexpr (ADAPT) { /* JOBS_PIXEL: the pixel's words of its view's planes, view_count frames of W * H each */
                     const size_t at = plane_index(rv, P.job_index, px, py);
                     if (rv.c->ad_spp) rv.c->ad_spp[at] = P.sample;
@@ -1338,6 +1374,12 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 P.sample = 0;
                 P.ps = PS_SAMPLE;
                 if constexpr (ADAPT) { A->q = 0.0f; A->next = rv.c->ad_min_spp; }
+                if constexpr (GROUPS) {
+                    for (uint32_t g = 0; g < rv.c->group_count; ++g) {
+                        float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
+                        q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
+                    }
+                }
                 if (focal_cache) { /* the pixel's focal point, once per pixel (persistent kernel: three floats of LDS per lane) */
                     V3 f;
                     if constexpr (VIEWS) f = view_focal_point(rv, P.pxy, load_view_camera(rv, P.job_index));
@@ -1740,7 +1782,9 @@ ORT_D void flush_counters(const RenderHot &rv, const Counters &c, bool all) {
 /* persistent mode: one lane runs jobs until the job space is empty */
 /* ADAPT: the adaptive camera render (pt_adaptive): the same loop, a pixel ending where produce_ray's stopping rule says; A is the
    lane's AdaptState, wherever the caller keeps it */
-template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool WIDE = false, bool VIEWS = false, bool ADAPT = false>
+/* GROUPS: the light-group render (pt_groups): the same loop, produce_ray keeping the group sums in the output frames */
+template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool WIDE = false, bool VIEWS = false, bool ADAPT = false,
+          bool GROUPS = false>
 ORT_D void pt_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, float *lds_focal, const int tid,
                    const uint32_t lane_id, bool prof_on = false, unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
     uint32_t spill[kSpillStack];
@@ -1763,6 +1807,8 @@ ORT_D void pt_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, 
             if (P.ps == PS_HIT) resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true, WIDE>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
             ORT_PHASE(pr, sv, 0, P.ps == PS_HIT);
             if constexpr (ADAPT) tracing = produce_ray<COUNTERS, DIFFUSE, TABS, IMPLICIT, VIEWS, false, true>(sv, rv, tab, P, h, c, pr, lds_focal + tid, kBlock, spp_u, nullptr, false, pool, A);
+            else
+            if constexpr (GROUPS) tracing = produce_ray<COUNTERS, DIFFUSE, TABS, IMPLICIT, VIEWS, false, false, false, true>(sv, rv, tab, P, h, c, pr, lds_focal + tid, kBlock, spp_u, nullptr, false, pool);
             else
             tracing = produce_ray<COUNTERS, DIFFUSE, TABS, IMPLICIT, VIEWS>(sv, rv, tab, P, h, c, pr, lds_focal + tid, kBlock, spp_u, nullptr, false, pool);
             if (tracing) {
@@ -2242,6 +2288,22 @@ pt_adaptive(SceneView sv, RenderHot rv) {
     if (TABS) fill_tab(sv, lds_tab);
     pt_lane<COUNTERS, DIFFUSE, TABS, true, false, true, true>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
                                                               wave_job_pool(rv, lds_pool), A);
+}
+
+/* The light-group render (ort_render_light_groups, ort_render_views_light_groups): the plain loop over the implicit one-pixel jobs
+   of a batch of views (JOBS_PIXEL; the single frame is the one-view batch of the scene's own camera), every emission added to its
+   light's group as well (produce_ray's GROUPS flag).  Built beside pt_adaptive, in ort_kernels_render_adaptive.hip alone.  The
+   group sums live in the output frames, so the kernel holds what pt_persistent holds and nothing more.  No probes, no drain times */
+template <bool COUNTERS, bool DIFFUSE, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+pt_groups(SceneView sv, RenderHot rv) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ float lds_focal[3 * kBlock]; /* focal[component][lane] */
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as pt_persistent */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    if (TABS) fill_tab(sv, lds_tab);
+    pt_lane<COUNTERS, DIFFUSE, TABS, true, false, true, false, true>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
+                                                                     wave_job_pool(rv, lds_pool));
 }
 
 /* the same with the ray exchange (pt_lane_x): implicit job spaces only, LDS tables required */
