@@ -2,7 +2,7 @@
  * ort_kernels_adaptive.hip -- the kernels of the adaptive radiance queries (ort_radiance_adaptive): radiance_adaptive_rays.
  *
  * The lane code (ort_lane.h) compiled a third time, at the limits of ort_kernels.hip proper (four waves per SIMD, 24 LDS stack
- * entries), for the eight variants of radiance_lane<..., ADAPT = true> only.  A unit of its own because eight more path-trace
+ * entries), for the eight variants of radiance_lane with LF_ADAPT only.  A unit of its own because eight more path-trace
  * kernels are a quarter more compile time: here they compile beside the others (under make -j3 the three units build at once)
  * and the library builds no slower than before them (profiles/r10_adaptive.md).  device_radiance (ort_kernels.hip), given
  * a stopping rule, launches them through ort_launch_radiance_adaptive.

@@ -3,8 +3,8 @@
  * irradiance_points and irradiance_adaptive_points.
  *
  * The lane code (ort_lane.h) compiled a fifth time, at the limits of ort_kernels.hip proper (four waves per SIMD, 24 LDS stack
- * entries), for the sixteen variants of radiance_lane<..., HEMI = true> only: the radiance queries' loop over points, every
- * sample's primary direction drawn in the lane (produce_ray's HEMI flag).  A unit of its own for ort_kernels_adaptive.hip's
+ * entries), for the sixteen variants of radiance_lane with LF_HEMI only: the radiance queries' loop over points, every
+ * sample's primary direction drawn in the lane (produce_ray's HEMI).  A unit of its own for ort_kernels_adaptive.hip's
  * reason: sixteen more path-trace kernels compile here beside the others (under make -j5 the five units build at once).
  * device_radiance (ort_kernels.hip), given points, launches them through ort_launch_irradiance.
  */

@@ -4,8 +4,8 @@
  * render (ort_render_light_groups, ort_render_views_light_groups: pt_groups).
  *
  * The lane code (ort_lane.h) compiled a fourth time, at the limits of ort_kernels.hip proper (four waves per SIMD, 24 LDS stack
- * entries), for the eight variants of pt_lane<..., VIEWS = true, ADAPT = true> and the eight of pt_lane<..., VIEWS = true,
- * GROUPS = true> only.  A unit of its own for the reason ort_kernels_adaptive.hip is one: more path-trace kernels are compile
+ * entries), for the eight variants of pt_lane with LF_IMPLICIT | LF_VIEWS | LF_ADAPT and the eight with LF_IMPLICIT | LF_VIEWS |
+ * LF_GROUPS only.  A unit of its own for the reason ort_kernels_adaptive.hip is one: more path-trace kernels are compile
  * time that ort_kernels.hip, the unit that sets the build's wall time, should not carry; here they compile beside the others
  * (profiles/r12_render_adaptive.md, profiles/r21_light_groups.md).  The light-group kernels share this unit, sixteen kernels as
  * the irradiance unit holds, instead of adding a sixth.  device_render (ort_kernels.hip), given a stopping rule or a group table,

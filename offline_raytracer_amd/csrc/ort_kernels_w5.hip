@@ -19,7 +19,8 @@
 #define ORT_SPILL_STACK 44
 #include "ort_lane.h"
 
-/* the five-waves variants of the plain loop (KF_FIVE: no counters, tables, implicit jobs), launched by device_render
+/* the five-waves variants of the plain loop (KF_FIVE: no counters, tables, implicit jobs -- pt_lane with LF_TABS | LF_IMPLICIT,
+   and LF_DIFFUSE or not), launched by device_render
    (ort_kernels.hip proper) with its own SceneView and RenderHot: the argument structs are ort_lane.h's one definition */
 void ort_launch_w5(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot) {
     if (v.diffuse) hipLaunchKernelGGL((ort_w5::pt_persistent<false, true, true, true>), dim3(grid), dim3(ort_w5::kBlock), 0, stream, sv, hot);

@@ -384,6 +384,90 @@ extern unsigned long long g_cs[4][16];
 constexpr uint32_t kNoPrim = 0xffffffffu;
 constexpr uint32_t kTraversalDone = 0xffffffffu; /* == EMPTY_CHILD: a leaf word no tree contains */
 
+/* ---- the compile-time flavours of the lane code, by name -----------------------------------------------------------------
+ * Every lane function below is a template over ONE flag word F (and, where it owns a stack, the ints LDS_ENTRIES and BLOCK): a
+ * set of the names defined here, read back into constexpr bools of the same names at the function's top.  A caller derives its
+ * callee's word from its own by name (F | LF_RAYS, F & ~LF_WIDE, walk_of(F)); a __global__ wrapper builds its lane's from its
+ * bools with lf_if.  A word holds only names its function reads (LF_OF_*): two kernels that need the same walk then share one
+ * instantiation of it, as they always have -- and which instantiations are shared moves the compiler's code (a word that carried
+ * its caller's other names along changed the treelet's address arithmetic in every TABS kernel).  flavour_ok states the legal
+ * sets once, and every function asserts it.  A new flavour is one name here, its place in the LF_OF_* of the functions that
+ * read it, one line in flavour_ok, and the callers that turn it on. */
+constexpr uint32_t LF_COUNTERS = 1u << 0; /* the diagnostics build: paths, rays and tests are counted (Counters), the probes are live */
+constexpr uint32_t LF_DIFFUSE = 1u << 1;  /* every surface material of the scene has Ks = Kt = 0 (see at pt_persistent) */
+constexpr uint32_t LF_TABS = 1u << 2;     /* the small read-only tables are in LDS (fill_tab): prologue shapes, materials, lights, treelet */
+/* IMPLICIT: the caller vouches for an implicit job space (PIXEL / CHUNK policies: every job is one pixel, spp_u
+   samples): the job's rect, its sample count and its index then need no registers of their own */
+constexpr uint32_t LF_IMPLICIT = 1u << 3;
+constexpr uint32_t LF_WIDE = 1u << 4;     /* the fast tree is the 4-wide one (DevNode4; visit_node4): the plain loop of a single frame only */
+/* VIEWS: a batch of views (ort_render_views): the job index names the view first, and the view's camera and seed come from
+   the table behind rv.c->views instead of sv.cam and rv.c->seed -- the same expressions on the same operands, so the same bits */
+constexpr uint32_t LF_VIEWS = 1u << 5;
+/* RAYS: radiance queries (ort_radiance; with IMPLICIT): the job space is the caller's ray array (rv.c->rays), a job is ONE ray with
+   spp_u samples on the stream that starts at rv.c->seeds[j].  Every sample starts at the ray's origin in the ray's direction,
+   with wo = -normalize(d) (ray.cpp:1240-1246 for a camera without an aperture), and no aperture angle is drawn; the job ends
+   with 12 bytes at out + 3 j and its stream's state.  The ray is read again for every sample (24 bytes from L2 per path of
+   hundreds of node tests) instead of held in six registers through the traversal loop; P.job_index | P.pxy << 32 is the ray index */
+constexpr uint32_t LF_RAYS = 1u << 6;
+/* ADAPT: adaptive radiance queries (ort_radiance_adaptive; with RAYS) and the adaptive camera render (ort_render_adaptive,
+   ort_render_views_adaptive; with VIEWS, one-pixel jobs in JOBS_PIXEL mode): spp_u is max_spp, and the job also ends at the first
+   check of the stopping rule (adaptive_stop) that says so.  A (the lane's AdaptState) holds the sum of squared sample
+   luminance and the sample count of the next check; the job writes its sample count and that sum besides the mean, which
+   divides by the samples taken -- per ray for a query, per pixel of its view's planes for a render, with the stream's state.
+   Everything of it sits under if constexpr (ADAPT): the other kernels compile as without it */
+constexpr uint32_t LF_ADAPT = 1u << 7;
+/* HEMI: irradiance queries (ort_irradiance, ort_irradiance_adaptive; with RAYS): the caller's array holds points (p, n) where RAYS
+   reads rays (o, d) -- the same 24 bytes, the same domain test, read again for every sample -- and a sample's primary direction is
+   drawn in the lane, on the job's stream: sample_brdf's diffuse draw without the lobe choice (e0, e1; c = sqrt(e0), ray.cpp:1123;
+   phi = 2 pi e1), sample_lobe about n (ray.cpp:1065-1091) and normalize for d.  phi is the angle of the one converged sin/cos below;
+   from d on the sample is RAYS' for the ray (p, d): direction d as it stands, wo = -normalize(d).  Everything of it sits under
+   if constexpr (HEMI) */
+constexpr uint32_t LF_HEMI = 1u << 8;
+/* GROUPS: light-group renders (ort_render_light_groups; with VIEWS, one-pixel jobs in JOBS_PIXEL mode): whenever a sample adds an
+   emission e to the pixel's sum, the same e is added to the sum of the hit light's group (rv.c->group_of_material, a byte per
+   material in HBM, read here alone; a group at or above group_count is no group).  The G sums are the pixel's own words of the G
+   output frames: the job belongs to this lane from start to end, so it zeroes them at the pixel's start, loads, adds and stores one
+   triple per emission and divides them in place at the job's end -- no registers, no LDS, no atomics.  The render's own frame and
+   the final states are optional planes.  Everything of it sits under if constexpr (GROUPS) */
+constexpr uint32_t LF_GROUPS = 1u << 9;
+/* the walk's own options */
+constexpr uint32_t LF_TREELET = 1u << 10;     /* traverse: the top of the binary tree is read from the LDS tables (with TABS, never WIDE) */
+constexpr uint32_t LF_ANNOUNCE = 1u << 11;    /* traverse asks for a finished ray's PrimInfo (announce_winner); resolve_hit then finds it ANNOUNCED */
+constexpr uint32_t LF_EXACT_ORDER = 1u << 12; /* test_prim: the exact walk's records, in the reference's order: no exclusion, phantoms, ties or runner-up */
+constexpr uint32_t LF_FINITE_RAY = 1u << 13;  /* test_prim: origin and 1/d are finite, a box takes hit_aab_finite */
+constexpr uint32_t LF_FROM_TAB = 1u << 14;    /* test_prim: the shape's record comes from the LDS tables (rec) */
+constexpr uint32_t LF_HAS_EXCL = 1u << 15;    /* prologue_tests: the re-traversals of resolve_hit ignore one shape (excl); a ray's first traversal ignores none */
+
+constexpr uint32_t lf_if(bool on, uint32_t names) { return on ? names : 0u; }
+
+/* the names each function reads */
+constexpr uint32_t LF_OF_TEST_PRIM = LF_COUNTERS | LF_EXACT_ORDER | LF_FINITE_RAY | LF_FROM_TAB;
+constexpr uint32_t LF_OF_PROLOGUE = LF_COUNTERS | LF_TABS | LF_HAS_EXCL;
+constexpr uint32_t LF_OF_BEGIN_RAY = LF_COUNTERS | LF_TABS;
+constexpr uint32_t LF_OF_TRAVERSE = LF_COUNTERS | LF_TREELET | LF_ANNOUNCE | LF_WIDE;
+constexpr uint32_t LF_OF_RESOLVE_HIT = LF_COUNTERS | LF_TABS | LF_ANNOUNCE | LF_WIDE;
+constexpr uint32_t LF_OF_PRODUCE_RAY = LF_COUNTERS | LF_DIFFUSE | LF_TABS | LF_IMPLICIT | LF_VIEWS | LF_RAYS | LF_ADAPT | LF_HEMI | LF_GROUPS;
+constexpr uint32_t LF_OF_LANE = LF_OF_PRODUCE_RAY | LF_WIDE; /* pt_lane ... radiance_lane: a job's flavour */
+/* ... and, from a lane's flavour f, the words of the three steps of its loop: begin_ray (and a prologue in its place); traverse,
+   where finished rays announce their winners and the top of the binary tree comes from the LDS tables if there are any; and the
+   resolve_hit that follows such a walk */
+constexpr uint32_t begin_of(uint32_t f) { return f & LF_OF_BEGIN_RAY; }
+constexpr uint32_t walk_of(uint32_t f) { return (f & (LF_COUNTERS | LF_WIDE)) | LF_ANNOUNCE | lf_if((f & LF_TABS) && !(f & LF_WIDE), LF_TREELET); }
+constexpr uint32_t resolve_of(uint32_t f) { return (f & (LF_COUNTERS | LF_TABS | LF_WIDE)) | LF_ANNOUNCE; }
+
+/* the sets that are built: f holds none but the names its function reads, and what each flavour needs beside it or cannot stand beside */
+constexpr bool flavour_ok(uint32_t f, uint32_t reads) {
+    const bool IMPLICIT = f & LF_IMPLICIT, WIDE = f & LF_WIDE, VIEWS = f & LF_VIEWS, RAYS = f & LF_RAYS, ADAPT = f & LF_ADAPT;
+    const bool HEMI = f & LF_HEMI, GROUPS = f & LF_GROUPS, TREELET = f & LF_TREELET, EXACT_ORDER = f & LF_EXACT_ORDER;
+    return (f & ~reads) == 0u
+        && (!RAYS || (IMPLICIT && !VIEWS))                        /* a caller's ray array is an implicit job space of its own */
+        && (!ADAPT || (IMPLICIT && (RAYS || VIEWS)))              /* the adaptive rule is built for the radiance queries and for one-pixel jobs of a batch of views */
+        && (!HEMI || RAYS)                                        /* the hemisphere draw starts a sample of a radiance query's job */
+        && (!GROUPS || (IMPLICIT && VIEWS && !RAYS && !ADAPT))    /* the group sums are built for plain one-pixel jobs of a batch of views */
+        && (!WIDE || !(VIEWS || RAYS || ADAPT || HEMI || GROUPS || TREELET)) /* the 4-wide tree serves the single frame's plain loop, and has no treelet */
+        && (!EXACT_ORDER || !(f & (LF_FINITE_RAY | LF_FROM_TAB))); /* the exact walk reads HBM */
+}
+
 ORT_D uint32_t prim_order(const SceneView &sv, uint32_t kind, uint32_t slot) {
     return (kind == PRIM_TRI) ? sv.cold->tri_order[slot] : (kind == PRIM_SPHERE) ? sv.cold->sphere_order[slot]
          : (kind == PRIM_BOX) ? sv.cold->box_order[slot] : sv.cold->cyl_order[slot];
@@ -391,10 +475,12 @@ ORT_D uint32_t prim_order(const SceneView &sv, uint32_t kind, uint32_t slot) {
 
 /* one primitive against the ray, exactly as raycast_bvh does per record (ray.cpp:647-716):
    accept when hit_t >= 1e-6 and strictly closer than the best so far */
-template <bool COUNTERS, bool EXACT_ORDER, bool FINITE_RAY = false, bool FROM_TAB = false>
+template <uint32_t F>
 ORT_D void test_prim(const SceneView &sv, uint32_t kind, uint32_t slot, V3 org, V3 dir, V3 inv_d, float &best_t, V3 &hit_n,
                      uint32_t &hit_prim, float &phantom_t, float &runner_t, unsigned long long &c_tris, unsigned long long &c_analytic,
                      uint32_t excl = 0xffffffffu, const float4 *rec = nullptr /* FROM_TAB: the shape's record in the LDS tables */) {
+    static_assert(flavour_ok(F, LF_OF_TEST_PRIM), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS, EXACT_ORDER = F & LF_EXACT_ORDER, FINITE_RAY = F & LF_FINITE_RAY, FROM_TAB = F & LF_FROM_TAB;
     float t;
     V3 n = mk(0, 0, 0);
     bool tangent = false;
@@ -646,7 +732,7 @@ ORT_D bool ref_raycast_bfs(const SceneView &sv, V3 org, V3 dir, V3 inv_d, uint32
         uint32_t rec_first = om_f32_bits(b.w), rec_count = om_f32_bits(c.x);
         for (uint32_t r = 0; r < rec_count; ++r) {
             uint32_t rec = sv.cold->ref_recs[rec_first + r];
-            test_prim<COUNTERS, true>(sv, rec >> 28, rec & 0x00ffffffu, org, dir, inv_d, best_t, hit_n, hit_prim, unused, unused, c_tris, c_analytic);
+            test_prim<lf_if(COUNTERS, LF_COUNTERS) | LF_EXACT_ORDER>(sv, rec >> 28, rec & 0x00ffffffu, org, dir, inv_d, best_t, hit_n, hit_prim, unused, unused, c_tris, c_analytic);
         }
         if (first_child >= 0) {
             for (uint32_t k = 0; k < 8u; ++k) {
@@ -752,9 +838,11 @@ ORT_D void reset_hit(HitState &h, float best_t) {
 
 /* the analytic prologue (ort_tree.cpp): the lanes that start a ray now all test the same shape at the same
    time -- uniform addresses, no divergence -- and enter the tree with best_t already set */
-/* HAS_EXCL: the re-traversals of resolve_hit ignore one shape (excl); a ray's first traversal ignores none */
-template <bool COUNTERS, bool TABS, bool HAS_EXCL = false>
+template <uint32_t F>
 ORT_D void prologue_tests(const SceneView &sv, const float4 *tab, V3 org, V3 dir, V3 inv_d, HitState &h, Counters &c, uint32_t excl = kNoPrim) {
+    static_assert(flavour_ok(F, LF_OF_PROLOGUE), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS, TABS = F & LF_TABS, HAS_EXCL = F & LF_HAS_EXCL;
+    constexpr uint32_t SHAPE = (F & LF_COUNTERS) | lf_if(TABS, LF_FROM_TAB); /* test_prim's flavour for a prologue shape */
     /* TABS: the shapes' records come from the LDS tables */
     const float4 *pb = nullptr, *ps = nullptr, *pc = nullptr; /* formed under TABS only: tab is null without them */
     if (TABS) { pb = tab + kTabPro; ps = pb + 2u * sv.pro_boxes; pc = ps + sv.pro_spheres; }
@@ -765,7 +853,7 @@ ORT_D void prologue_tests(const SceneView &sv, const float4 *tab, V3 org, V3 dir
 #endif
     if (!ORT_PROLOGUE_DEFER && ORT_BALLOT(!all_finite6(org, inv_d)) == 0ull) {
         for (uint32_t i = 0; i < sv.pro_boxes; ++i)
-            test_prim<COUNTERS, false, true, TABS>(sv, PRIM_BOX, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? pb + 2u * i : nullptr);
+            test_prim<SHAPE | LF_FINITE_RAY>(sv, PRIM_BOX, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? pb + 2u * i : nullptr);
     } else
     if (ORT_BALLOT(!all_finite6(org, inv_d)) == 0ull) {
         /* distances only while the boxes compete (test_prim's rule: accept 1e-6 <= t < best, equal distances by reference
@@ -793,12 +881,12 @@ ORT_D void prologue_tests(const SceneView &sv, const float4 *tab, V3 org, V3 dir
         }
     } else {
         for (uint32_t i = 0; i < sv.pro_boxes; ++i)
-            test_prim<COUNTERS, false, false, TABS>(sv, PRIM_BOX, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? pb + 2u * i : nullptr);
+            test_prim<SHAPE>(sv, PRIM_BOX, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? pb + 2u * i : nullptr);
     }
     for (uint32_t i = 0; i < sv.pro_spheres; ++i)
-        test_prim<COUNTERS, false, false, TABS>(sv, PRIM_SPHERE, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? ps + i : nullptr);
+        test_prim<SHAPE>(sv, PRIM_SPHERE, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? ps + i : nullptr);
     for (uint32_t i = 0; i < sv.pro_cyls; ++i)
-        test_prim<COUNTERS, false, false, TABS>(sv, PRIM_CYL, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? pc + 4u * i : nullptr);
+        test_prim<SHAPE>(sv, PRIM_CYL, i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl, TABS ? pc + 4u * i : nullptr);
 }
 
 #ifndef ORT_HOST_SIM
@@ -856,7 +944,7 @@ ORT_D bool ref_raycast_bfs_wave(const SceneView &sv, const int leader, V3 org_l,
             uint32_t prim = kNoPrim;
             if (r0 + rank < rec_count) {
                 const uint32_t rec = sv.cold->ref_recs[rec_first + r0 + rank];
-                test_prim<COUNTERS, true>(sv, rec >> 28, rec & 0x00ffffffu, org, dir, inv_d, t, n, prim, unused, unused, c_tris, c_analytic);
+                test_prim<lf_if(COUNTERS, LF_COUNTERS) | LF_EXACT_ORDER>(sv, rec >> 28, rec & 0x00ffffffu, org, dir, inv_d, t, n, prim, unused, unused, c_tris, c_analytic);
             }
             /* the lanes that would take their record: the smallest distance wins, the lowest lane (= earliest record) among equals */
             unsigned long long takers = __ballot(prim != kNoPrim);
@@ -1097,41 +1185,13 @@ ORT_D bool adaptive_stop(V3 C, float Q, uint32_t n, float tolerance, float lum_f
     return vm <= thr * thr;
 }
 
-/* IMPLICIT: the caller vouches for an implicit job space (PIXEL / CHUNK policies: every job is one pixel, spp_u
-   samples): the job's rect, its sample count and its index then need no registers of their own */
-/* VIEWS: a batch of views (ort_render_views): the job index names the view first, and the view's camera and seed come from
-   the table behind rv.c->views instead of sv.cam and rv.c->seed -- the same expressions on the same operands, so the same bits */
-/* RAYS: radiance queries (ort_radiance; with IMPLICIT): the job space is the caller's ray array (rv.c->rays), a job is ONE ray with
-   spp_u samples on the stream that starts at rv.c->seeds[j].  Every sample starts at the ray's origin in the ray's direction,
-   with wo = -normalize(d) (ray.cpp:1240-1246 for a camera without an aperture), and no aperture angle is drawn; the job ends
-   with 12 bytes at out + 3 j and its stream's state.  The ray is read again for every sample (24 bytes from L2 per path of
-   hundreds of node tests) instead of held in six registers through the traversal loop; P.job_index | P.pxy << 32 is the ray index */
-/* ADAPT: adaptive radiance queries (ort_radiance_adaptive; with RAYS) and the adaptive camera render (ort_render_adaptive,
-   ort_render_views_adaptive; with VIEWS, one-pixel jobs in JOBS_PIXEL mode): spp_u is max_spp, and the job also ends at the first
-   check of the stopping rule (adaptive_stop) that says so.  A (the lane's AdaptState) holds the sum of squared sample
-   luminance and the sample count of the next check; the job writes its sample count and that sum besides the mean, which
-   divides by the samples taken -- per ray for a query, per pixel of its view's planes for a render, with the stream's state.
-   Everything of it sits under if constexpr (ADAPT): the other kernels compile as without it */
-/* HEMI: irradiance queries (ort_irradiance, ort_irradiance_adaptive; with RAYS): the caller's array holds points (p, n) where RAYS
-   reads rays (o, d) -- the same 24 bytes, the same domain test, read again for every sample -- and a sample's primary direction is
-   drawn in the lane, on the job's stream: sample_brdf's diffuse draw without the lobe choice (e0, e1; c = sqrt(e0), ray.cpp:1123;
-   phi = 2 pi e1), sample_lobe about n (ray.cpp:1065-1091) and normalize for d.  phi is the angle of the one converged sin/cos below;
-   from d on the sample is RAYS' for the ray (p, d): direction d as it stands, wo = -normalize(d).  Everything of it sits under
-   if constexpr (HEMI) */
-/* GROUPS: light-group renders (ort_render_light_groups; with VIEWS, one-pixel jobs in JOBS_PIXEL mode): whenever a sample adds an
-   emission e to the pixel's sum, the same e is added to the sum of the hit light's group (rv.c->group_of_material, a byte per
-   material in HBM, read here alone; a group at or above group_count is no group).  The G sums are the pixel's own words of the G
-   output frames: the job belongs to this lane from start to end, so it zeroes them at the pixel's start, loads, adds and stores one
-   triple per emission and divides them in place at the job's end -- no registers, no LDS, no atomics.  The render's own frame and
-   the final states are optional planes.  Everything of it sits under if constexpr (GROUPS) */
-template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool VIEWS = false, bool RAYS = false, bool ADAPT = false,
-          bool HEMI = false, bool GROUPS = false>
+template <uint32_t F> /* IMPLICIT ... GROUPS: at their names, LF_IMPLICIT ... LF_GROUPS */
 ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, Prof &pr,
                        float *focal_cache = nullptr, int focal_stride = 0, uint32_t spp_u = 0, uint32_t *late_flag = nullptr, bool no_new_job = false,
                        unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
-    static_assert(!ADAPT || (IMPLICIT && (RAYS || VIEWS)), "the adaptive rule is built for the radiance queries and for one-pixel jobs of a batch of views");
-    static_assert(!HEMI || RAYS, "the hemisphere draw starts a sample of a radiance query's job");
-    static_assert(!GROUPS || (IMPLICIT && VIEWS && !RAYS && !ADAPT), "the group sums are built for plain one-pixel jobs of a batch of views");
+    static_assert(flavour_ok(F, LF_OF_PRODUCE_RAY), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS, DIFFUSE = F & LF_DIFFUSE, TABS = F & LF_TABS, IMPLICIT = F & LF_IMPLICIT, VIEWS = F & LF_VIEWS;
+    constexpr bool RAYS = F & LF_RAYS, ADAPT = F & LF_ADAPT, HEMI = F & LF_HEMI, GROUPS = F & LF_GROUPS;
     /* VIEWS: unused; every lane reads its view's camera where it needs it (load_view_camera) */
     const V3 cam_p = mk(sv.cam[0], sv.cam[1], sv.cam[2]);
     const V3 cam_x = mk(sv.cam[3], sv.cam[4], sv.cam[5]);
@@ -1602,14 +1662,16 @@ ORT_D void visit_node4(float4 lx, float4 ly, float4 lz, float4 hx, float4 hy, fl
 /* raycast_top_most_node (ray.cpp:1165-1176): start at the root.  The lanes that start a ray now are converged: they
    test the analytic prologue together and visit the root node together, its record read from the LDS tables, before
    they join the traversal loop (whose other lanes are at arbitrary depths) */
-template <bool COUNTERS, bool TABS, int LDS_ENTRIES, int BLOCK>
+template <uint32_t F, int LDS_ENTRIES, int BLOCK>
 ORT_D void begin_ray(const SceneView &sv, const float4 *tab, const PathState &P, Trav &T, HitState &h, Counters &c, Prof &pr,
                      uint32_t *lds_stack, uint32_t *spill, int tid) {
+    static_assert(flavour_ok(F, LF_OF_BEGIN_RAY), "see flavour_ok");
+    [[maybe_unused]] constexpr bool COUNTERS = F & LF_COUNTERS; /* the probes' */
     T.cur = 0;
     T.sp = 0;
     T.inv_d = mk(1.0f / P.dir.x, 1.0f / P.dir.y, 1.0f / P.dir.z); /* ray.cpp:210, once per ray */
     reset_hit(h, 3.402823466e+38f); /* Flt_Max, ray.cpp:627 */
-    prologue_tests<COUNTERS, TABS>(sv, tab, P.org, P.dir, T.inv_d, h, c);
+    prologue_tests<F>(sv, tab, P.org, P.dir, T.inv_d, h, c);
     ORT_PHASE(pr, sv, 4, true);
 }
 
@@ -1621,9 +1683,11 @@ ORT_D void begin_ray(const SceneView &sv, const float4 *tab, const PathState &P,
  * conservative; fminf/fmaxf drop the NaN of 0 * inf, i.e. that axis is ignored.
  * Returns when this lane's ray is finished, or -- refill_below > 0 -- as soon as fewer than
  * refill_below lanes of the wave are still traversing (the caller resumes later: all state is in T/h). */
-template <bool COUNTERS, int LDS_ENTRIES, int BLOCK, bool TREELET = false, bool ANNOUNCE = false, bool WIDE = false>
+template <uint32_t F, int LDS_ENTRIES, int BLOCK>
 ORT_D bool traverse(const SceneView &sv, V3 org, V3 dir, Trav &T, HitState &h, uint32_t *lds_stack, uint32_t *spill, int tid,
                     int refill_below, int descend_below, Counters &c, Prof &pr, uint32_t excl = kNoPrim, const float4 *tab = nullptr) {
+    static_assert(flavour_ok(F, LF_OF_TRAVERSE), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS, TREELET = F & LF_TREELET, ANNOUNCE = F & LF_ANNOUNCE, WIDE = F & LF_WIDE;
     bool tracing = true;
     uint32_t cur = T.cur;
     int sp = T.sp;
@@ -1668,7 +1732,7 @@ ORT_D bool traverse(const SceneView &sv, V3 org, V3 dir, Trav &T, HitState &h, u
             ORT_UTIL(sv, 1, true);
             uint32_t kind = (cur >> 28) & 7u, count = ((cur >> 24) & 15u) + 1u, first = cur & 0x00ffffffu;
             for (uint32_t i = 0; i < count; ++i)
-                test_prim<COUNTERS, false>(sv, kind, first + i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl);
+                test_prim<F & LF_COUNTERS>(sv, kind, first + i, org, dir, inv_d, h.best_t, h.hit_n, h.hit_prim, h.phantom_t, h.runner_t, c.tris, c.analytic, excl);
             if (sp == 0) {
                 cur = kTraversalDone;
                 tracing = false;
@@ -1706,9 +1770,11 @@ ORT_D bool traverse(const SceneView &sv, V3 org, V3 dir, Trav &T, HitState &h, u
    The extra traversals run here, to completion, for the lanes that need them (1e-5 of the rays of the
    reference's scenes, 1e-2 with slanted cylinders) while the rest of the wave waits: the shape to ignore is
    a local of this rare branch, not a register carried through every ray's traversal. */
-template <bool COUNTERS, bool TABS, int LDS_ENTRIES, int BLOCK, bool ANNOUNCED = false, bool WIDE = false>
+template <uint32_t F, int LDS_ENTRIES, int BLOCK>
 ORT_D void resolve_hit(const SceneView &sv, const float4 *tab, V3 org, V3 dir, V3 inv_d, uint32_t lane_id, HitState &h, Counters &c, Prof &pr,
                        uint32_t *lds_stack, uint32_t *spill, int tid) {
+    static_assert(flavour_ok(F, LF_OF_RESOLVE_HIT), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS, ANNOUNCED = F & LF_ANNOUNCE;
     /* the winner's chain word and material index: announced by the traversal (in the lane's stack entries 0 and 1),
        or fetched here */
     uint32_t word = 0, mat = 0;
@@ -1742,8 +1808,8 @@ ORT_D void resolve_hit(const SceneView &sv, const float4 *tab, V3 org, V3 dir, V
                 t2.cur = 0; t2.sp = 0; t2.inv_d = inv_d;
                 /* CH_UNKNOWN: only hits at or before the leaf box's entry matter (the hit tests' "<" must accept t == gap) */
                 reset_hit(h, verdict == CH_REJECT ? 3.402823466e+38f : om_bits_f32(om_f32_bits(gap) + 1u));
-                prologue_tests<COUNTERS, TABS, true>(sv, tab, org, dir, inv_d, h, c, w_prim);
-                (void)traverse<COUNTERS, LDS_ENTRIES - 4, BLOCK, false, false, WIDE>(sv, org, dir, t2, h, lds_stack, spill, tid, 0, 0, c, pr, w_prim);
+                prologue_tests<(F & LF_OF_PROLOGUE) | LF_HAS_EXCL>(sv, tab, org, dir, inv_d, h, c, w_prim);
+                (void)traverse<F & LF_OF_TRAVERSE & ~LF_ANNOUNCE, LDS_ENTRIES - 4, BLOCK>(sv, org, dir, t2, h, lds_stack, spill, tid, 0, 0, c, pr, w_prim);
                 if (verdict == CH_UNKNOWN) {
                     if (h.hit_prim != kNoPrim || h.phantom_t <= gap) {
                         recast = true; /* something is there: order decides */
@@ -1783,10 +1849,11 @@ ORT_D void flush_counters(const RenderHot &rv, const Counters &c, bool all) {
 /* ADAPT: the adaptive camera render (pt_adaptive): the same loop, a pixel ending where produce_ray's stopping rule says; A is the
    lane's AdaptState, wherever the caller keeps it */
 /* GROUPS: the light-group render (pt_groups): the same loop, produce_ray keeping the group sums in the output frames */
-template <bool COUNTERS, bool DIFFUSE = false, bool TABS = false, bool IMPLICIT = false, bool WIDE = false, bool VIEWS = false, bool ADAPT = false,
-          bool GROUPS = false>
+template <uint32_t F>
 ORT_D void pt_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, float *lds_focal, const int tid,
                    const uint32_t lane_id, bool prof_on = false, unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
+    static_assert(flavour_ok(F, LF_OF_LANE), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS, IMPLICIT = F & LF_IMPLICIT;
     uint32_t spill[kSpillStack];
     const uint32_t spp_u = IMPLICIT ? ((rv.mode == JOBS_PIXEL) ? rv.c->spp : rv.c->chunk) : 0u; /* samples per (one-pixel) job */
     Prof pr;
@@ -1804,20 +1871,16 @@ ORT_D void pt_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, 
             ORT_UTIL(sv, 3, true);
             ORT_UTIL(sv, 4, P.ps == PS_HIT);
             ORT_PHASE(pr, sv, 7, true);
-            if (P.ps == PS_HIT) resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true, WIDE>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+            if (P.ps == PS_HIT) resolve_hit<resolve_of(F), kLdsStack, kBlock>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
             ORT_PHASE(pr, sv, 0, P.ps == PS_HIT);
-            if constexpr (ADAPT) tracing = produce_ray<COUNTERS, DIFFUSE, TABS, IMPLICIT, VIEWS, false, true>(sv, rv, tab, P, h, c, pr, lds_focal + tid, kBlock, spp_u, nullptr, false, pool, A);
-            else
-            if constexpr (GROUPS) tracing = produce_ray<COUNTERS, DIFFUSE, TABS, IMPLICIT, VIEWS, false, false, false, true>(sv, rv, tab, P, h, c, pr, lds_focal + tid, kBlock, spp_u, nullptr, false, pool);
-            else
-            tracing = produce_ray<COUNTERS, DIFFUSE, TABS, IMPLICIT, VIEWS>(sv, rv, tab, P, h, c, pr, lds_focal + tid, kBlock, spp_u, nullptr, false, pool);
+            tracing = produce_ray<F & ~LF_WIDE>(sv, rv, tab, P, h, c, pr, lds_focal + tid, kBlock, spp_u, nullptr, false, pool, A);
             if (tracing) {
-                begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
+                begin_ray<begin_of(F), kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
                 if (COUNTERS) c.rays++;
             }
         }
         if (ORT_BALLOT(P.ps != PS_DONE) == 0ull) break;
-        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS && !WIDE, true, WIDE>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+        if (tracing) tracing = traverse<walk_of(F), kLdsStack, kBlock>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
     }
     flush_counters(rv, c, COUNTERS);
 }
@@ -1885,9 +1948,11 @@ ORT_D void stash_load(const Stash &st, uint32_t slot, const RenderHot &rv, PathS
     lds_info[0] = om_f32_bits(j.z); lds_info[kBlock] = om_f32_bits(j.w);
 }
 
-template <bool COUNTERS, bool DIFFUSE, bool TABS>
+template <uint32_t F>
 ORT_D void pt_lane_x(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, float *lds_focal, const int tid,
                      const uint32_t lane_id, bool prof_on, unsigned long long *pool) {
+    static_assert(flavour_ok(F, LF_OF_LANE), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS;
     uint32_t spill[kSpillStack];
     Prof pr;
     pr.on = prof_on;
@@ -2012,14 +2077,14 @@ ORT_D void pt_lane_x(const SceneView &sv, const RenderHot &rv, const float4 *tab
             ORT_UTIL(sv, 3, true);
             ORT_UTIL(sv, 4, P.ps == PS_HIT);
             ORT_PHASE(pr, sv, 7, true);
-            if (P.ps == PS_HIT) resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+            if (P.ps == PS_HIT) resolve_hit<resolve_of(F), kLdsStack, kBlock>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
             ORT_PHASE(pr, sv, 0, P.ps == PS_HIT);
             /* near the end of the launch a lane whose job ends draws no new one while the wave still holds parked paths: the
                next exchange step hands it one of those (endgame branch above), so that the stashes are empty when the job
                space is */
-            tracing = produce_ray<COUNTERS, DIFFUSE, TABS, true>(sv, rv, tab, P, h, c, pr, focal_cache, kBlock, spp_u, late_flag, early_end && ltop + rtop > 0u, pool);
+            tracing = produce_ray<F | LF_IMPLICIT>(sv, rv, tab, P, h, c, pr, focal_cache, kBlock, spp_u, late_flag, early_end && ltop + rtop > 0u, pool);
             if (tracing) {
-                begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
+                begin_ray<begin_of(F), kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
                 if (COUNTERS) c.rays++;
             }
         }
@@ -2027,7 +2092,7 @@ ORT_D void pt_lane_x(const SceneView &sv, const RenderHot &rv, const float4 *tab
         /* in a traversal phase come back for more parked rays when half the lanes have finished; otherwise (and once
            L is empty) when only stragglers are left, which then park */
         const int below = (long_phase && ltop > 0u) ? (int)rv.c->long_refill : rv.refill_below;
-        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS, true>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, below, rv.descend_below, c, pr, kNoPrim, tab);
+        if (tracing) tracing = traverse<walk_of(F), kLdsStack, kBlock>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, below, rv.descend_below, c, pr, kNoPrim, tab);
     }
     flush_counters(rv, c, COUNTERS);
 }
@@ -2040,8 +2105,9 @@ constexpr int kWfSpill = 48;
 static_assert(kWfLdsStack - 4 + kWfSpill >= (int)kTreeDepthBudget, "wavefront trace stack must hold a tree of kTreeDepthBudget levels");
 
 /* one slot: resume its path, produce the next ray, store everything back; returns true if a ray was produced */
-template <bool COUNTERS>
+template <uint32_t F>
 ORT_D bool wf_shade_slot(const SceneView &sv, const RenderHot &rv, const float4 *tab, const WfView &wf, uint32_t i, Counters &c) {
+    constexpr bool COUNTERS = F & LF_COUNTERS;
     uint32_t fl = wf.flags[i];
     PathState P;
     P.ps = (int)(fl & 7u);
@@ -2062,7 +2128,7 @@ ORT_D bool wf_shade_slot(const SceneView &sv, const RenderHot &rv, const float4 
         h.hit_mat = (P.ps == PS_HIT && h.hit_prim != kNoPrim) ? sv.prim_info[info_index(sv, h.hit_prim)].mat : 0u;
     }
     Prof pr;
-    bool tracing = produce_ray<COUNTERS>(sv, rv, tab, P, h, c, pr);
+    bool tracing = produce_ray<F>(sv, rv, tab, P, h, c, pr);
     if (tracing) {
         wf.od0[i] = make_float4(P.org.x, P.org.y, P.org.z, P.dir.x);
         wf.od1[i] = make_float2(P.dir.y, P.dir.z);
@@ -2077,7 +2143,7 @@ ORT_D bool wf_shade_slot(const SceneView &sv, const RenderHot &rv, const float4 
 }
 
 /* one slot: closest hit of its ray, resolved to the reference's answer */
-template <bool COUNTERS>
+template <uint32_t F>
 ORT_D void wf_trace_slot(const SceneView &sv, const float4 *tab, const WfView &wf, uint32_t i, uint32_t lane_id, uint32_t *lds_stack,
                          uint32_t *spill, int tid, Counters &c) {
     if (!(wf.flags[i] & WF_HAS_RAY)) return;
@@ -2088,9 +2154,9 @@ ORT_D void wf_trace_slot(const SceneView &sv, const float4 *tab, const WfView &w
     HitState h;
     Trav T;
     Prof pr;
-    begin_ray<COUNTERS, false, kWfLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
-    traverse<COUNTERS, kWfLdsStack, kBlock>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, 0, 0, c, pr);
-    resolve_hit<COUNTERS, false, kWfLdsStack, kBlock>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+    begin_ray<F, kWfLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
+    traverse<F, kWfLdsStack, kBlock>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, 0, 0, c, pr);
+    resolve_hit<F, kWfLdsStack, kBlock>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
     wf.hit0[i] = make_float4(h.best_t, h.hit_n.x, h.hit_n.y, h.hit_n.z);
     wf.hitp[i] = h.hit_prim;
 }
@@ -2256,7 +2322,7 @@ pt_persistent(SceneView sv, RenderHot rv) {
         if (threadIdx.x < 4) g_lds_prof[96 + threadIdx.x] = __builtin_amdgcn_s_memtime();
         __syncthreads();
     }
-    pt_lane<COUNTERS, DIFFUSE, TABS, IMPLICIT, WIDE, VIEWS>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, prof,
+    pt_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | lf_if(IMPLICIT, LF_IMPLICIT) | lf_if(WIDE, LF_WIDE) | lf_if(VIEWS, LF_VIEWS)>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, prof,
                                                     wave_job_pool(rv, lds_pool));
     if ((threadIdx.x & 63u) == 0u && rv.c->drain) rv.c->drain[blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime();
     if (prof) {
@@ -2286,7 +2352,7 @@ pt_adaptive(SceneView sv, RenderHot rv) {
     AdaptState *const A = reinterpret_cast<AdaptState *>(lds_adapt) + threadIdx.x;
 #endif
     if (TABS) fill_tab(sv, lds_tab);
-    pt_lane<COUNTERS, DIFFUSE, TABS, true, false, true, true>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
+    pt_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_ADAPT>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
                                                               wave_job_pool(rv, lds_pool), A);
 }
 
@@ -2302,7 +2368,7 @@ pt_groups(SceneView sv, RenderHot rv) {
     __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as pt_persistent */
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
-    pt_lane<COUNTERS, DIFFUSE, TABS, true, false, true, false, true>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
+    pt_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_GROUPS>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
                                                                      wave_job_pool(rv, lds_pool));
 }
 
@@ -2321,7 +2387,7 @@ pt_persistent_x(SceneView sv, RenderHot rv) {
         if (threadIdx.x < 4) g_lds_prof[96 + threadIdx.x] = __builtin_amdgcn_s_memtime();
         __syncthreads();
     }
-    pt_lane_x<COUNTERS, DIFFUSE, true>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, prof,
+    pt_lane_x<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | LF_TABS>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, prof,
                                        wave_job_pool(rv, lds_pool));
     if ((threadIdx.x & 63u) == 0u && rv.c->drain) rv.c->drain[blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime();
     if (prof) {
@@ -2339,7 +2405,7 @@ __global__ void __launch_bounds__(kBlock) wf_shade(SceneView sv, RenderHot rv, W
     unsigned long long produced = 0;
     const uint32_t stride = gridDim.x * (uint32_t)kBlock;
     for (uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x; i < wf.slots; i += stride)
-        if (wf_shade_slot<COUNTERS>(sv, rv, lds_tab, wf, i, c)) produced++;
+        if (wf_shade_slot<lf_if(COUNTERS, LF_COUNTERS)>(sv, rv, lds_tab, wf, i, c)) produced++;
     if (count_active && produced) atomicAdd(wf.active, produced);
     flush_counters(rv, c, COUNTERS);
 }
@@ -2353,7 +2419,7 @@ __global__ void __launch_bounds__(kBlock) wf_trace(SceneView sv, RenderHot rv, W
     const uint32_t stride = gridDim.x * (uint32_t)kBlock;
     const uint32_t lane_id = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
     for (uint32_t i = lane_id; i < wf.slots; i += stride)
-        wf_trace_slot<COUNTERS>(sv, lds_tab, wf, i, lane_id, lds_stack, spill, (int)threadIdx.x, c);
+        wf_trace_slot<lf_if(COUNTERS, LF_COUNTERS)>(sv, lds_tab, wf, i, lane_id, lds_stack, spill, (int)threadIdx.x, c);
     flush_counters(rv, c, COUNTERS);
 }
 
@@ -2415,9 +2481,11 @@ ORT_D float ray_bound(float tm) { return (tm > 0.0f) ? fminf(tm, 3.402823466e+38
 ORT_D V3 cache_v3(const float *w) { return mk(w[0], w[kBlock], w[2 * kBlock]); }
 ORT_D void cache_add_v3(float *w, V3 v) { w[0] = w[0] + v.x; w[kBlock] = w[kBlock] + v.y; w[2 * kBlock] = w[2 * kBlock] + v.z; }
 
-template <bool COUNTERS, bool TABS>
+template <uint32_t F>
 ORT_D void raycast_lane(const SceneView &sv, const RenderHot &rv, const RaycastIO &io, const float4 *tab, uint32_t *lds_stack, const int tid,
                         const uint32_t lane_id, unsigned long long *pool) {
+    static_assert(flavour_ok(F, LF_OF_LANE), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS;
     uint32_t spill[kSpillStack];
     PathState P;
     HitState h;
@@ -2429,7 +2497,7 @@ ORT_D void raycast_lane(const SceneView &sv, const RenderHot &rv, const RaycastI
     for (;;) {
         if (!tracing) {
             if (held) {
-                resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+                resolve_hit<resolve_of(F), kLdsStack, kBlock>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
                 const uint32_t src = h.hit_prim != kNoPrim ? io.prim_src[info_index(sv, h.hit_prim)] : kNoPrim;
                 const V3 n = normalize(h.hit_n); /* ray.cpp:817: the normal leaves raycast_bvh normalised (a miss's stays 0) */
                 uint2 *o = io.hits + 3ull * ray;
@@ -2445,7 +2513,7 @@ ORT_D void raycast_lane(const SceneView &sv, const RenderHot &rv, const RaycastI
                     P.org = r.o;
                     P.dir = r.d;
                     ray = j;
-                    begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
+                    begin_ray<begin_of(F), kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
                     if (ORT_RARE(raycast_needs_exact(io, P.org, P.dir, T.inv_d))) skip_fast_walk(T, h);
                     if (COUNTERS) c.rays++;
                     tracing = held = true;
@@ -2456,7 +2524,7 @@ ORT_D void raycast_lane(const SceneView &sv, const RenderHot &rv, const RaycastI
         }
         /* a lane that is not tracing now has no ray and will get none */
         if (ORT_BALLOT(tracing) == 0ull) break;
-        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS, true>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+        if (tracing) tracing = traverse<walk_of(F), kLdsStack, kBlock>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
     }
     flush_counters(rv, c, COUNTERS);
 }
@@ -2471,7 +2539,7 @@ raycast_rays(SceneView sv, RenderHot rv, RaycastIO io) {
     __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* per wave: the unissued part of its last batch of ray indices (draw_job) */
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
-    raycast_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+    raycast_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(TABS, LF_TABS)>(sv, rv, io, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 #endif
 
@@ -2503,9 +2571,11 @@ raycast_rays(SceneView sv, RenderHot rv, RaycastIO io) {
  * EXACT WALK.  The rays raycast_needs_exact names, and those ORT_DEBUG_FORCE_FALLBACK selects, skip the fast traversal
  * and the early end; resolve_hit re-casts them exactly and their closest hit is compared with tmax.
  * One byte out per ray, a plain byte store: a wave's ray indices are contiguous, 64 adjacent bytes. */
-template <bool COUNTERS, bool TABS>
+template <uint32_t F>
 ORT_D void occluded_lane(const SceneView &sv, const RenderHot &rv, const OccludedIO &io, const float4 *tab, uint32_t *lds_stack, const int tid,
                          const uint32_t lane_id, unsigned long long *pool) {
+    static_assert(flavour_ok(F, LF_OF_LANE), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS;
     uint32_t spill[kSpillStack];
     PathState P;
     HitState h;
@@ -2519,7 +2589,7 @@ ORT_D void occluded_lane(const SceneView &sv, const RenderHot &rv, const Occlude
         if (!tracing) {
             if (held) {
                 h.runner_t = fminf(h.runner_t, bound); /* the bound is a runner-up the walk may not have seen */
-                resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+                resolve_hit<resolve_of(F), kLdsStack, kBlock>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
                 io.out[ray] = (h.hit_mat != 0u && h.best_t < bound) ? (uint8_t)1 : (uint8_t)0;
                 held = false;
             }
@@ -2542,7 +2612,7 @@ ORT_D void occluded_lane(const SceneView &sv, const RenderHot &rv, const Occlude
                         T.sp = 0;
                         T.inv_d = mk(1.0f / P.dir.x, 1.0f / P.dir.y, 1.0f / P.dir.z); /* as begin_ray, with the bound for Flt_Max */
                         reset_hit(h, bound);
-                        prologue_tests<COUNTERS, TABS>(sv, tab, P.org, P.dir, T.inv_d, h, c);
+                        prologue_tests<begin_of(F)>(sv, tab, P.org, P.dir, T.inv_d, h, c);
                         bool seen = false; /* the prologue's winner is one the reference is certain to test */
                         if (ORT_RARE(forced || raycast_needs_exact(io.q, P.org, P.dir, T.inv_d))) {
                             skip_fast_walk(T, h);
@@ -2562,7 +2632,7 @@ ORT_D void occluded_lane(const SceneView &sv, const RenderHot &rv, const Occlude
         }
         /* a lane that is neither tracing nor entitled to another draw has no ray and will get none */
         if (ORT_BALLOT(tracing || more) == 0ull) break;
-        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS, true>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+        if (tracing) tracing = traverse<walk_of(F), kLdsStack, kBlock>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
     }
     flush_counters(rv, c, COUNTERS);
 }
@@ -2575,7 +2645,7 @@ occluded_rays(SceneView sv, RenderHot rv, OccludedIO io) {
     __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
-    occluded_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+    occluded_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(TABS, LF_TABS)>(sv, rv, io, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 #endif
 
@@ -2612,9 +2682,11 @@ ORT_D bool ao_box_within(float4 lo_xyz_hi_x, float hi_y, float hi_z, V3 p, float
 }
 constexpr int kAoCacheWords = 6; /* bent.xyz, normalize(n).xyz */
 
-template <bool COUNTERS, bool TABS>
+template <uint32_t F>
 ORT_D void ao_lane(const SceneView &sv, const RenderHot &rv, const AoIO &io, const float4 *tab, uint32_t *lds_stack, float *job_cache, const int tid,
                    const uint32_t lane_id, unsigned long long *pool) {
+    static_assert(flavour_ok(F, LF_OF_LANE), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS, TABS = F & LF_TABS;
     uint32_t spill[kSpillStack];
     HitState h;
     Trav T;
@@ -2631,7 +2703,7 @@ ORT_D void ao_lane(const SceneView &sv, const RenderHot &rv, const AoIO &io, con
         if (!tracing) {
             if (held) { /* the finished sample's verdict */
                 h.runner_t = fminf(h.runner_t, bound); /* the bound is a runner-up the walk may not have seen */
-                resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, org, dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+                resolve_hit<resolve_of(F), kLdsStack, kBlock>(sv, tab, org, dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
                 if (!(h.hit_mat != 0u && h.best_t < bound)) { open++; cache_add_v3(bent, dir); }
                 held = false;
             }
@@ -2693,7 +2765,7 @@ ORT_D void ao_lane(const SceneView &sv, const RenderHot &rv, const AoIO &io, con
                     T.sp = 0;
                     T.inv_d = mk(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z); /* as begin_ray, with the bound for Flt_Max */
                     reset_hit(h, bound);
-                    prologue_tests<COUNTERS, TABS>(sv, tab, org, dir, T.inv_d, h, c);
+                    prologue_tests<begin_of(F)>(sv, tab, org, dir, T.inv_d, h, c);
                     bool seen = false; /* the prologue's winner is one the reference is certain to test */
                     if (ORT_RARE(forced || raycast_needs_exact(io.q, org, dir, T.inv_d))) {
                         skip_fast_walk(T, h);
@@ -2712,7 +2784,7 @@ ORT_D void ao_lane(const SceneView &sv, const RenderHot &rv, const AoIO &io, con
         }
         /* a lane that neither traces, owns a point nor is entitled to another draw has none and will get none */
         if (ORT_BALLOT(tracing || busy || more) == 0ull) break;
-        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS, true>(sv, org, dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+        if (tracing) tracing = traverse<walk_of(F), kLdsStack, kBlock>(sv, org, dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
     }
     flush_counters(rv, c, COUNTERS);
 }
@@ -2726,7 +2798,7 @@ ao_points(SceneView sv, RenderHot rv, AoIO io) {
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     __shared__ float lds_job[kAoCacheWords * kBlock]; /* the job's state that is touched once per sample (ao_lane) */
     if (TABS) fill_tab(sv, lds_tab);
-    ao_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, lds_job + threadIdx.x, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+    ao_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(TABS, LF_TABS)>(sv, rv, io, lds_tab, lds_stack, lds_job + threadIdx.x, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 #endif
 
@@ -2750,9 +2822,11 @@ ao_points(SceneView sv, RenderHot rv, AoIO io) {
  * held through the walk.  The ids go straight to memory at sample 0 (profiles/r18_features.md). */
 constexpr int kFeatureCacheWords = 7; /* albedo.xyz, normal.xyz, depth */
 
-template <bool COUNTERS, bool TABS>
+template <uint32_t F>
 ORT_D void feature_lane(const SceneView &sv, const RenderHot &rv, const FeatureIO &io, const float4 *tab, uint32_t *lds_stack, float *job_cache, const int tid,
                         const uint32_t lane_id, unsigned long long *pool) {
+    static_assert(flavour_ok(F, LF_OF_LANE), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS, TABS = F & LF_TABS;
     uint32_t spill[kSpillStack];
     PathState P; /* org, dir; rng; pxy; job_index: the view; sample: the samples of this pixel started so far */
     HitState h;
@@ -2765,7 +2839,7 @@ ORT_D void feature_lane(const SceneView &sv, const RenderHot &rv, const FeatureI
     for (;;) {
         if (!tracing) {
             if (held) { /* the finished sample: raycast_lane's record, into the sums */
-                resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+                resolve_hit<resolve_of(F), kLdsStack, kBlock>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
                 if (P.sample == 1u && io.ids) {
                     const uint32_t src = h.hit_prim != kNoPrim ? io.q.prim_src[info_index(sv, h.hit_prim)] : kNoPrim;
                     const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
@@ -2822,7 +2896,7 @@ ORT_D void feature_lane(const SceneView &sv, const RenderHot &rv, const FeatureI
                 P.org = view_aperture_point(cam, 0.1f, cs, sn); /* ray.cpp:1199, :1233-1234 */
                 P.dir = normalize(sub(focal, P.org));           /* ray.cpp:1237 */
                 P.sample++;
-                begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
+                begin_ray<begin_of(F), kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
                 if (ORT_RARE(raycast_needs_exact(io.q, P.org, P.dir, T.inv_d))) skip_fast_walk(T, h);
                 if (COUNTERS) c.rays++;
                 tracing = held = true;
@@ -2830,7 +2904,7 @@ ORT_D void feature_lane(const SceneView &sv, const RenderHot &rv, const FeatureI
         }
         /* a lane that neither traces, owns a pixel nor is entitled to another draw has none and will get none */
         if (ORT_BALLOT(tracing || busy || more) == 0ull) break;
-        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS, true>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+        if (tracing) tracing = traverse<walk_of(F), kLdsStack, kBlock>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
     }
     flush_counters(rv, c, COUNTERS);
 }
@@ -2846,7 +2920,7 @@ feature_pixels(SceneView sv, RenderHot rv, FeatureIO io) {
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     __shared__ float lds_job[kFeatureCacheWords * kBlock]; /* the job's sums (feature_lane) */
     if (TABS) fill_tab(sv, lds_tab);
-    feature_lane<COUNTERS, TABS>(sv, rv, io, lds_tab, lds_stack, lds_job + threadIdx.x, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+    feature_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(TABS, LF_TABS)>(sv, rv, io, lds_tab, lds_stack, lds_job + threadIdx.x, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 #endif
 
@@ -2860,26 +2934,27 @@ feature_pixels(SceneView sv, RenderHot rv, FeatureIO io) {
 /* ADAPT: the adaptive query (ort_radiance_adaptive): the same loop, the job ending where produce_ray's stopping rule says */
 /* HEMI: the irradiance queries (ort_irradiance, ort_irradiance_adaptive): the same loop over points, every sample's primary
    direction drawn in the lane (produce_ray's HEMI flag); the drawn direction passes raycast_needs_exact like a caller's */
-template <bool COUNTERS, bool DIFFUSE, bool TABS, bool ADAPT = false, bool HEMI = false>
+template <uint32_t F>
 ORT_D void radiance_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, const int tid, const uint32_t lane_id,
                          unsigned long long *pool) {
+    constexpr uint32_t JOB = F | LF_IMPLICIT | LF_RAYS; /* the caller names what varies: COUNTERS, DIFFUSE, TABS, ADAPT, HEMI */
+    static_assert(flavour_ok(JOB, LF_OF_LANE), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS;
     uint32_t spill[kSpillStack];
     const uint32_t spp_u = rv.c->spp;
     Prof pr;
     PathState P;
-    [[maybe_unused]] AdaptState A; /* ADAPT only */
+    AdaptState A; /* ADAPT only */
     HitState h;
     Trav T;
     Counters c;
     bool tracing = false;
     for (;;) {
         if (!tracing) {
-            if (P.ps == PS_HIT) resolve_hit<COUNTERS, TABS, kLdsStack, kBlock, true>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
-            if constexpr (ADAPT) tracing = produce_ray<COUNTERS, DIFFUSE, TABS, true, false, true, true, HEMI>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool, &A);
-            else
-            tracing = produce_ray<COUNTERS, DIFFUSE, TABS, true, false, true, false, HEMI>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool);
+            if (P.ps == PS_HIT) resolve_hit<resolve_of(F), kLdsStack, kBlock>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+            tracing = produce_ray<JOB>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool, &A);
             if (tracing) {
-                begin_ray<COUNTERS, TABS, kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
+                begin_ray<begin_of(F), kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
                 if (P.primary) { /* the facts raycast_needs_exact asks for, from the launch's copy (kept in this form: in a helper the radiance kernels' code moves) */
                     RaycastIO q{};
                     q.tree_spheres = rv.c->ray_tree_spheres; q.tree_quadrics = rv.c->ray_tree_quadrics; q.tree_boxes = rv.c->ray_tree_boxes;
@@ -2890,7 +2965,7 @@ ORT_D void radiance_lane(const SceneView &sv, const RenderHot &rv, const float4 
             }
         }
         if (ORT_BALLOT(P.ps != PS_DONE) == 0ull) break;
-        if (tracing) tracing = traverse<COUNTERS, kLdsStack, kBlock, TABS, true>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+        if (tracing) tracing = traverse<walk_of(F), kLdsStack, kBlock>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
     }
     flush_counters(rv, c, COUNTERS);
 }
@@ -2904,7 +2979,7 @@ radiance_rays(SceneView sv, RenderHot rv) {
     __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
-    radiance_lane<COUNTERS, DIFFUSE, TABS>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+    radiance_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS)>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 
 /* the adaptive query's eight, as radiance_rays */
@@ -2915,7 +2990,7 @@ radiance_adaptive_rays(SceneView sv, RenderHot rv) {
     __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
-    radiance_lane<COUNTERS, DIFFUSE, TABS, true>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+    radiance_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_ADAPT>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 
 /* the irradiance queries' sixteen (ort_kernels_irradiance.hip), as radiance_rays and radiance_adaptive_rays: rv.c->rays holds points */
@@ -2926,7 +3001,7 @@ irradiance_points(SceneView sv, RenderHot rv) {
     __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
-    radiance_lane<COUNTERS, DIFFUSE, TABS, false, true>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+    radiance_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_HEMI>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 template <bool COUNTERS, bool DIFFUSE, bool TABS>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
@@ -2935,7 +3010,7 @@ irradiance_adaptive_points(SceneView sv, RenderHot rv) {
     __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
-    radiance_lane<COUNTERS, DIFFUSE, TABS, true, true>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+    radiance_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_ADAPT | LF_HEMI>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 #endif
 

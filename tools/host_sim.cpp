@@ -25,17 +25,17 @@
  *   or: host_sim --radiance-adaptive scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
  *   or: host_sim --irradiance scn base points.f32 seeds.u32 spp rr out.f32 states.u32            (points: p, n, 6 floats each)
  *   or: host_sim --irradiance-adaptive scn base points.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
- *       (the irradiance queries: the two modes above over points, radiance_lane<..., HEMI>)
+ *       (the irradiance queries: the two modes above over points, radiance_lane with LF_HEMI)
  *   or: host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32   (cams: p, x, y, z axes, 12 floats a view)
  *       (as on the device, one view is the single-frame lane with that view's camera and seed: the VIEWS lanes run from two views on)
  *   or: host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
- *       (the adaptive camera render of the scene's own camera: pt_lane<..., VIEWS, ADAPT> over a one-view batch; the planes start
+ *       (the adaptive camera render of the scene's own camera: pt_lane with LF_IMPLICIT | LF_VIEWS | LF_ADAPT over a one-view batch; the planes start
  *       at the guard values -7.0f, 0xeeeeeeee, -1.0f, 0xdddddddd, which pixels outside the rect keep)
  *   or: host_sim --features scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|-
  *       (the first-hit feature render, feature_lane: a batch of views, or with cams - the scene's own camera on the seed given; a
  *       plane given as - is not passed; the planes start at -7.0f, 0xeeeeeeee and, the states, 0xdddddddd)
  *   or: host_sim --light-groups scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr groups.u8 G groups.f32 rgb.f32|- states.u32|-
- *       (the light-group render, pt_lane<..., VIEWS, GROUPS>: a batch of views, or with cams - the scene's own camera on the seed
+ *       (the light-group render, pt_lane with LF_IMPLICIT | LF_VIEWS | LF_GROUPS: a batch of views, or with cams - the scene's own camera on the seed
  *       given; groups.u8 holds a byte per material of the scene, G is the group count; the planes start at -7.0f and, the states,
  *       0xdddddddd; rgb and states given as - are not passed)
  *   or: host_sim --tree-check scn base
@@ -44,7 +44,7 @@
  *       on stdout when it is sound, the first violation on stderr and status 1 when it is not)
  * Every mode prints, per instantiation of traverse, how deep the per-lane stack got ("stack: lds 24 deepest ..."; tests/host_sim_tool.py
  * stack_probe reads it); make host_sim_w5 builds the same tool with the five-waves unit's split of that stack (20 + 44 entries).
- * All files raw little-endian.  SIM_TABS=1: the TABS = true lane code, on a heap copy of the LDS tables' image.
+ * All files raw little-endian.  SIM_TABS=1: the LF_TABS lane code, on a heap copy of the LDS tables' image.
  */
 #define ORT_HOST_SIM 1
 #include <stdint.h>
@@ -295,7 +295,7 @@ static int raycast_mode(char **a) { /* scn base rays.f32 hits.bin */
     const RenderHot hot = query_hot(S, rv, n);
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
-        with_bools([&](auto T) { raycast_lane<true, decltype(T)::value>(sv, hot, io, S.tab, stack, 0, w, nullptr); }, S.tab != nullptr);
+        with_bools([&](auto T) { raycast_lane<LF_COUNTERS | lf_if(decltype(T)::value, LF_TABS)>(sv, hot, io, S.tab, stack, 0, w, nullptr); }, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     static_assert(sizeof(ort_hit) == 3 * sizeof(uint2), "ort_hit is three 8-byte words");
@@ -321,7 +321,7 @@ static int occluded_mode(char **a) { /* scn base rays.f32 tmax.f32|- out.u8 */
     const RenderHot hot = query_hot(S, rv, n);
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
-        with_bools([&](auto T) { occluded_lane<true, decltype(T)::value>(sv, hot, io, S.tab, stack, 0, w, nullptr); }, S.tab != nullptr);
+        with_bools([&](auto T) { occluded_lane<LF_COUNTERS | lf_if(decltype(T)::value, LF_TABS)>(sv, hot, io, S.tab, stack, 0, w, nullptr); }, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return write_bytes(a[4], out.data(), n) ? 0 : 1;
@@ -356,7 +356,7 @@ static int ao_mode(char **a) { /* scn base points.f32 seeds.u32 radius.f32|- spp
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
         std::vector<float> job((kAoCacheWords - 1) * kBlock + 1); /* exactly: a word beyond the lane's six is a write past the block */
-        with_bools([&](auto T) { ao_lane<true, decltype(T)::value>(sv, hot, io, S.tab, stack, job.data(), 0, w, nullptr); }, S.tab != nullptr);
+        with_bools([&](auto T) { ao_lane<LF_COUNTERS | lf_if(decltype(T)::value, LF_TABS)>(sv, hot, io, S.tab, stack, job.data(), 0, w, nullptr); }, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return write_bytes(a[6], open.data(), 4 * n) && (!want_bent || write_bytes(a[7], bent.data(), 12 * n)) &&
@@ -382,14 +382,14 @@ static int radiance_mode(char **a) { /* scn base rays.f32 seeds.u32 spp rr out.f
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
         with_bools([&](auto D, auto T) {
-            radiance_lane<true, decltype(D)::value, decltype(T)::value, false, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
+            radiance_lane<LF_COUNTERS | lf_if(decltype(D)::value, LF_DIFFUSE) | lf_if(decltype(T)::value, LF_TABS) | lf_if(HEMI, LF_HEMI)>(sv, hot, S.tab, stack, 0, w, nullptr);
         }, diffuse_only, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return write_bytes(a[6], out.data(), 12 * n) && write_bytes(a[7], states.data(), 4 * n) ? 0 : 1;
 }
 
-/* the adaptive query: radiance_lane<..., ADAPT>; tolerance and floor are read as float bits when written 0x........ (a test can
+/* the adaptive query: radiance_lane with LF_ADAPT; tolerance and floor are read as float bits when written 0x........ (a test can
    pass any float exactly), as decimals otherwise */
 static float float_arg(const char *s) {
     if (s[0] == '0' && (s[1] == 'x' || s[1] == 'X')) { const uint32_t b = (uint32_t)strtoul(s, 0, 16); float f; memcpy(&f, &b, 4); return f; }
@@ -415,7 +415,7 @@ static int radiance_adaptive_mode(char **a) { /* scn base rays.f32 seeds.u32 min
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
         with_bools([&](auto D, auto T) {
-            radiance_lane<true, decltype(D)::value, decltype(T)::value, true, HEMI>(sv, hot, S.tab, stack, 0, w, nullptr);
+            radiance_lane<LF_COUNTERS | lf_if(decltype(D)::value, LF_DIFFUSE) | lf_if(decltype(T)::value, LF_TABS) | LF_ADAPT | lf_if(HEMI, LF_HEMI)>(sv, hot, S.tab, stack, 0, w, nullptr);
         }, diffuse_only, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
@@ -451,16 +451,16 @@ static ort_render_params sim_params(int W, int H, uint32_t spp, uint32_t seed, c
     p.policy = policy == "pixel" ? ORT_POLICY_PIXEL : policy == "chunk" ? ORT_POLICY_CHUNK : ORT_POLICY_WHOLE;
     return p;
 }
-/* the plain loop's lanes over the job space of rv: pt_lane<counters, diffuse, tabs, explicit jobs, wide, views>, wide or views or
+/* the plain loop's lanes over the job space of rv: pt_lane with explicit jobs (no LF_IMPLICIT), and LF_WIDE or LF_VIEWS or
    neither.  SIM_DIFFUSE: the caller vouches for Ks = Kt = 0; the wide lanes run in the all-lobes flavour whatever it says.  TABS =
    false: the small tables are read from their arrays; SIM_TABS: from the packed image */
 static void run_pt_lanes(const Sim &S, const RenderHot &hot, bool wide, bool views) {
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
         with_bools([&](auto D, auto T) {
-            constexpr bool d = decltype(D)::value, t = decltype(T)::value;
-            if (views) pt_lane<true, d, t, false, false, true>(sv, hot, S.tab, stack, focal, 0, w);
-            else if (!wide) pt_lane<true, d, t>(sv, hot, S.tab, stack, focal, 0, w);
-            else if constexpr (!d) pt_lane<true, false, t, false, true>(sv, hot, S.tab, stack, focal, 0, w);
+            constexpr uint32_t F = LF_COUNTERS | lf_if(decltype(D)::value, LF_DIFFUSE) | lf_if(decltype(T)::value, LF_TABS);
+            if (views) pt_lane<F | LF_VIEWS>(sv, hot, S.tab, stack, focal, 0, w);
+            else if (!wide) pt_lane<F>(sv, hot, S.tab, stack, focal, 0, w);
+            else if constexpr (!(F & LF_DIFFUSE)) pt_lane<F | LF_WIDE>(sv, hot, S.tab, stack, focal, 0, w);
         }, getenv("SIM_DIFFUSE") != nullptr && !wide, S.tab != nullptr);
     });
 }
@@ -540,7 +540,7 @@ static int render_adaptive_mode(char **a) { /* scn base W H x0 y0 x1 y1 seed min
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
         AdaptState A; /* the lane's own, as pt_adaptive's slot of LDS */
         with_bools([&](auto D, auto T) {
-            pt_lane<true, decltype(D)::value, decltype(T)::value, true, false, true, true>(sv, hot, S.tab, stack, focal, 0, w, false, nullptr, &A);
+            pt_lane<LF_COUNTERS | lf_if(decltype(D)::value, LF_DIFFUSE) | lf_if(decltype(T)::value, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_ADAPT>(sv, hot, S.tab, stack, focal, 0, w, false, nullptr, &A);
         }, getenv("SIM_DIFFUSE") != nullptr, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
@@ -600,7 +600,7 @@ static int light_groups_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
         with_bools([&](auto D, auto T) {
-            pt_lane<true, decltype(D)::value, decltype(T)::value, true, false, true, false, true>(sv, hot, S.tab, stack, focal, 0, w);
+            pt_lane<LF_COUNTERS | lf_if(decltype(D)::value, LF_DIFFUSE) | lf_if(decltype(T)::value, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_GROUPS>(sv, hot, S.tab, stack, focal, 0, w);
         }, getenv("SIM_DIFFUSE") != nullptr, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
@@ -659,7 +659,7 @@ static int features_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
         std::vector<float> job((kFeatureCacheWords - 1) * kBlock + 1); /* exactly: a word beyond the lane's seven is a write past the block */
-        with_bools([&](auto T) { feature_lane<true, decltype(T)::value>(sv, hot, io, S.tab, stack, job.data(), 0, w, nullptr); }, S.tab != nullptr);
+        with_bools([&](auto T) { feature_lane<LF_COUNTERS | lf_if(decltype(T)::value, LF_TABS)>(sv, hot, io, S.tab, stack, job.data(), 0, w, nullptr); }, S.tab != nullptr);
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return (!want[0] || write_bytes(a[11], albedo.data(), 12 * n)) && (!want[1] || write_bytes(a[12], normal.data(), 12 * n)) &&
@@ -1010,9 +1010,9 @@ int main(int argc, char **argv) {
         Counters c;
         for (;;) {
             unsigned long long produced = 0;
-            for (uint32_t i = 0; i < slots; ++i) produced += wf_shade_slot<true>(sv, hot, nullptr, wf, i, c) ? 1 : 0;
+            for (uint32_t i = 0; i < slots; ++i) produced += wf_shade_slot<LF_COUNTERS>(sv, hot, nullptr, wf, i, c) ? 1 : 0;
             if (!produced) break;
-            for (uint32_t i = 0; i < slots; ++i) wf_trace_slot<true>(sv, nullptr, wf, i, 0, wlds.data(), wspill.data(), 0, c);
+            for (uint32_t i = 0; i < slots; ++i) wf_trace_slot<LF_COUNTERS>(sv, nullptr, wf, i, 0, wlds.data(), wspill.data(), 0, c);
         }
         flush_counters(hot, c, true);
     } else {
