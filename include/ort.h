@@ -646,6 +646,59 @@ int ort_render_views_light_groups_device(ort_scene *scene, const ort_render_para
                                          const ort_view *views, uint32_t view_count, void *d_out_groups, void *d_out_rgb,
                                          void *d_final_states, void *hip_stream, ort_stats *stats);
 
+/* ---- sample-map renders: the caller's sample count per pixel -------------------------------------
+ * The camera render with a job length of the caller's choosing for every pixel: the second pass of a two-pass scheme (a pilot
+ * frame, a map built from its out_m2 and guide planes, the samples spent where the map says), a foveated frame, or -- a map that
+ * is zero outside a pixel set -- the sparse camera render of just that set, aperture draw included.
+ * The map.  sample_map holds view_count frames of width*height u32, view-major, row 0 at the bottom: the layout of
+ * ort_render_adaptive's out_spp, which can be fed back as it stands.  HOST memory in the host forms, a DEVICE pointer on the
+ * scene's device in the _device forms (a map built on the GPU never visits the host).  It must be 4-byte aligned and must not
+ * overlap an output plane (not checked).  It is read, never written.
+ * Job.  The job is the ORT_POLICY_PIXEL job of pixel (x, y): camera samples, the aperture draw included, on the stream
+ * job_seed(seed, y*W + x) (views[v].seed in the views form), cut after n = min(sample_map[i], params->spp) samples.  params->spp
+ * is the cap and lies within [1, 1 << 24], so that (float)n is exact.  The map's values are never judged: a value above the cap
+ * is clamped, 0xffffffff included, identically in all four forms (the device forms cannot see the values before the launch).
+ * n == 0: the pixel is not rendered -- its stream is never started and its words in every output plane stay untouched, exactly as
+ * the pixels outside the rect.  An all-zero map returns ORT_OK after a launch that writes nothing.
+ * Outputs for n >= 1, each plane view_count frames, view-major, row 0 at the bottom:
+ *    out_rgb       C / (float)n, component by component, C the render's sum of the n samples
+ *    out_m2        Q, the sum of squared sample luminance, accumulated operation by operation as ort_radiance_adaptive
+ *                  defines it                                                             (may be NULL)
+ *    final_states  the stream's state after sample n                                      (may be NULL)
+ * Which optional planes are asked for changes no bit of the others.
+ * Four identities, all bit for bit.  (1) A constant map n, or any map at or above a cap n, gives ort_render_image's
+ * ORT_POLICY_PIXEL frame at spp = n, and ort_render_adaptive's planes at min_spp == max_spp == n.  (2) The planes of pixel i
+ * depend only on n_i, the seed and the camera, not on the rest of the map.  (3) ort_render_adaptive's out_spp as the map, the same
+ * seed and a cap >= max_spp give that call's out_rgb, out_m2 and final_states.  (4) Frame v of a batch is the single-frame call's
+ * for that camera, seed and map frame; the single-frame call is the one-view batch of the scene's own camera
+ * (ort_scene_get_camera) and params->seed.
+ * Not offered: resuming a pixel's stream or sums from an earlier call.  Passes taken with DIFFERENT seeds are independent
+ * estimates and combine weighted by their counts: rgb = (n1 * rgb1 + n2 * rgb2) / (n1 + n2) where n1 + n2 > 0.
+ * Parameters.  params->policy must be ORT_POLICY_PIXEL; any other policy is ORT_ERR_UNSUPPORTED.  shard_count > 1 and
+ * ORT_RENDER_PACKED return ORT_ERR_UNSUPPORTED.  params->chunk is ignored; rr is judged as the render call judges it (rr >= 0).
+ * The views form follows ort_render_views: params->seed is ignored; the per-view seed and camera, the rule where a camera may
+ * stand, ORT_MAX_VIEWS and view_count == 0 (ORT_OK without a launch, whatever the other arguments) are as there.
+ * Errors are reported before any device work, in ort_render_light_groups' order with the map where the groups stand:
+ * ORT_ERR_INVALID (null out_rgb or views, view cap exceeded, null scene or params, empty or bad params exactly as
+ * ort_render_image judges them; then spp above 1 << 24; then a null sample_map, a map or plane not 4-byte aligned),
+ * ORT_ERR_UNSUPPORTED (policy, shard, packed, camera outside the box), ORT_ERR_STATE (scene not committed), ORT_ERR_NO_DEVICE
+ * (not uploaded).
+ * The device forms take DEVICE pointers for the map and the planes, enqueue on hip_stream (NULL = the default stream) and wait
+ * only when stats != NULL; views is HOST memory in every form, copied before the call returns.  stats as for the render call; with
+ * ORT_RENDER_COUNTERS, paths = the sum of n over the rect of every frame.  No workspace is needed. */
+/* host map and planes (device staging is internal); synchronous */
+int ort_render_sample_map(ort_scene *scene, const ort_render_params *params, const uint32_t *sample_map, float *out_rgb,
+                          float *out_m2 /* may be NULL */, uint32_t *final_states /* may be NULL */, ort_stats *stats);
+int ort_render_sample_map_device(ort_scene *scene, const ort_render_params *params, const void *d_sample_map, void *d_out_rgb,
+                                 void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats);
+/* view_count frames of the map and of every plane, view-major */
+int ort_render_views_sample_map(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
+                                const uint32_t *sample_map, float *out_rgb, float *out_m2 /* may be NULL */,
+                                uint32_t *final_states /* may be NULL */, ort_stats *stats);
+int ort_render_views_sample_map_device(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
+                                       const void *d_sample_map, void *d_out_rgb, void *d_out_m2, void *d_final_states,
+                                       void *hip_stream, ort_stats *stats);
+
 /* ---- first-hit feature renders: albedo, normal, depth, coverage and id planes of the camera -----
  * The noise-free guide planes a denoiser wants next to the colour: what the camera's own samples see FIRST.  A pass of its own on
  * the pixel's own stream, a raycast per sample instead of a path; through the aperture the planes have the distribution of the

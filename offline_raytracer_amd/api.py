@@ -160,7 +160,8 @@ EXPORTS = [
     "ort_render_adaptive", "ort_render_adaptive_device", "ort_render_views_adaptive", "ort_render_views_adaptive_device",
     "ort_render_features", "ort_render_features_device", "ort_render_views_features", "ort_render_views_features_device",
     "ort_render_light_groups", "ort_render_light_groups_device", "ort_render_views_light_groups",
-    "ort_render_views_light_groups_device"]
+    "ort_render_views_light_groups_device",
+    "ort_render_sample_map", "ort_render_sample_map_device", "ort_render_views_sample_map", "ort_render_views_sample_map_device"]
 
 _lib = None
 
@@ -229,6 +230,8 @@ def lib():
                 ("ort_render_views_adaptive", [vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, C.c_uint32, vp, vp, vp, vp, stats]),
                 ("ort_render_light_groups", [vp, C.POINTER(RenderParams), C.POINTER(LightGroups), vp, vp, vp, stats]),
                 ("ort_render_views_light_groups", [vp, C.POINTER(RenderParams), C.POINTER(LightGroups), vp, C.c_uint32, vp, vp, vp, stats]),
+                ("ort_render_sample_map", [vp, C.POINTER(RenderParams), vp, vp, vp, vp, stats]),
+                ("ort_render_views_sample_map", [vp, C.POINTER(RenderParams), vp, C.c_uint32, vp, vp, vp, vp, stats]),
                 ("ort_render_features", [vp, C.POINTER(RenderParams), C.POINTER(FeaturePlanes), stats]),
                 ("ort_render_views_features", [vp, C.POINTER(RenderParams), vp, C.c_uint32, C.POINTER(FeaturePlanes), stats]),
                 ("ort_raycast", [vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
@@ -661,6 +664,81 @@ class Scene:
         st, stats = _stats(want_stats)
         _check(lib().ort_render_views_light_groups_device(self.handle, C.byref(params), C.byref(lg), views.ctypes.data, len(views),
                                                           _ptr(d_groups), _ptr(d_rgb), _ptr(d_states), _ptr(stream), st))
+        return stats()
+
+    # -- sample-map renders: the caller's sample count per pixel ----------------------------------
+    @staticmethod
+    def _sample_map(sample_map, shape):
+        """the caller's map -> a C-contiguous uint32 array of that shape (integers, taken modulo 2^32: 0xffffffff stays itself)"""
+        m = np.asarray(sample_map)
+        if m.shape != shape:
+            raise ValueError("sample_map must have shape %s, got %s" % (shape, m.shape))
+        if m.dtype != np.dtype("<u4"):
+            m = (m.astype(np.int64) & 0xFFFFFFFF).astype("<u4")
+        return np.ascontiguousarray(m)
+
+    @staticmethod
+    def _map_planes(shape, want_m2, want_states, out):
+        """the host planes of a sample-map render: zeros, or the caller's (out: (rgb[, m2][, states]), checked)"""
+        specs = [(shape + (3,), "<f4")] + ([(shape, "<f4")] if want_m2 else []) + ([(shape, "<u4")] if want_states else [])
+        if out is None:
+            return [np.zeros(sh, dt) for sh, dt in specs]
+        if len(out) != len(specs):
+            raise ValueError("out must hold %d planes (rgb%s%s), got %d" % (len(specs), ", m2" if want_m2 else "", ", states" if want_states else "", len(out)))
+        for a, (sh, dt) in zip(out, specs):
+            if not isinstance(a, np.ndarray) or a.shape != sh or a.dtype != np.dtype(dt) or not a.flags.c_contiguous:
+                raise ValueError("out: every plane must be a C-contiguous array, expected shape %s dtype %s" % (sh, dt))
+        return list(out)
+
+    def render_sample_map(self, width, height, sample_map, cap, seed, want_m2=True, want_states=False, rect=None, rr=0.8, counters=False,
+                          out=None):
+        """render(policy="pixel") with the caller's sample count per pixel: pixel (x, y) gets min(sample_map[y, x], cap)
+        samples of its own stream, and a pixel whose count is 0 is not rendered -- its words of every plane keep what out
+        held, as the pixels outside rect do (include/ort.h gives the contract).  sample_map: (H, W) integers, row 0 at the
+        bottom -- render_adaptive's spp plane can be passed as it stands.  Returns (rgb (H, W, 3) float32[, m2 (H, W) float32
+        sum of squared sample luminance][, states (H, W) uint32], stats dict).  Passes taken with different seeds combine
+        weighted by their counts: (n1 * rgb1 + n2 * rgb2) / (n1 + n2)."""
+        smap = self._sample_map(sample_map, (height, width))
+        planes = self._map_planes((height, width), want_m2, want_states, out)
+        p = self.params(width, height, cap, seed, "pixel", 0, rect, rr, counters)
+        st, stats = _stats()
+        _check(lib().ort_render_sample_map(self.handle, C.byref(p), smap.ctypes.data, planes[0].ctypes.data,
+                                           planes[1].ctypes.data if want_m2 else None,
+                                           planes[-1].ctypes.data if want_states else None, st))
+        return tuple(planes) + (stats(),)
+
+    def render_sample_map_device(self, params, d_map, d_rgb, d_m2=0, d_states=0, stream=None, want_stats=False):
+        """The same with the map and the planes on the device (raw device pointers, e.g. torch tensors' data_ptr(): the map
+        (H, W) uint32 -- or int32 holding the same words --, (H, W, 3) float32 and, where a pointer is given, (H, W) float32 /
+        uint32).  params: Scene.params(..., policy="pixel"), its spp the cap.  Enqueued on stream; waits only when
+        want_stats (returns the stats dict)."""
+        st, stats = _stats(want_stats)
+        _check(lib().ort_render_sample_map_device(self.handle, C.byref(params), _ptr(d_map), _ptr(d_rgb), _ptr(d_m2), _ptr(d_states),
+                                                  _ptr(stream), st))
+        return stats()
+
+    def render_views_sample_map(self, cameras, seeds, width, height, sample_map, cap, want_m2=True, want_states=False, rect=None,
+                                rr=0.8, counters=False, out=None):
+        """render_sample_map for a batch of views in one launch (cameras, seeds as render_views; sample_map (V, H, W), a map
+        per view): frame v is what render_sample_map gives with seed seeds[v] and sample_map[v] if the scene's camera were
+        cameras[v].  Returns (rgb (V, H, W, 3)[, m2 (V, H, W)][, states (V, H, W)], stats dict)."""
+        views = _views(cameras, seeds)
+        smap = self._sample_map(sample_map, (len(views), height, width))
+        planes = self._map_planes((len(views), height, width), want_m2, want_states, out)
+        p = self.params(width, height, cap, 0, "pixel", 0, rect, rr, counters)
+        st, stats = _stats()
+        _check(lib().ort_render_views_sample_map(self.handle, C.byref(p), views.ctypes.data, len(views), smap.ctypes.data,
+                                                 planes[0].ctypes.data, planes[1].ctypes.data if want_m2 else None,
+                                                 planes[-1].ctypes.data if want_states else None, st))
+        return tuple(planes) + (stats(),)
+
+    def render_views_sample_map_device(self, params, cameras, seeds, d_map, d_rgb, d_m2=0, d_states=0, stream=None, want_stats=False):
+        """The same with the maps and the planes on the device, V frames each, view-major.  Enqueued on stream; waits only
+        when want_stats (returns the stats dict).  params.seed is ignored."""
+        views = _views(cameras, seeds)
+        st, stats = _stats(want_stats)
+        _check(lib().ort_render_views_sample_map_device(self.handle, C.byref(params), views.ctypes.data, len(views), _ptr(d_map),
+                                                        _ptr(d_rgb), _ptr(d_m2), _ptr(d_states), _ptr(stream), st))
         return stats()
 
     # -- first-hit feature renders: albedo, normal, depth, coverage and id planes ---------------

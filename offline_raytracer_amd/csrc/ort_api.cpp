@@ -610,6 +610,45 @@ static int render_groups_common(ort_scene *s, const ort_render_params *p, const 
     return run_render(s, &q, c, out_rgb, nullptr, nullptr, states);
 }
 
+/* Sample-map renders, one frame or a batch of views: render_groups_common's order with the map where the groups stand.
+   view_count == 0 is OK whatever else is passed (the views form); then nulls (out_rgb, views) and the view cap, the params as the
+   render call judges them (chunk is not the caller's to set here), spp -- the cap -- above 1 << 24, the map (null) and the map's
+   and the planes' alignment, what the call does not do (any policy but PIXEL, shards, a packed framebuffer, a camera outside the
+   box), the scene's state.  The map's VALUES are never judged, in any form: the device forms cannot see them before the launch,
+   so the lanes cut every one at the cap.  !batch: the single-frame form (views unread), the one-view batch of the scene's own
+   camera and params->seed */
+static int render_sample_map_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool batch, bool host,
+                                    const void *sample_map, void *out_rgb, void *out_m2, void *states, void *stream, ort_stats *stats) {
+    if (batch && view_count == 0) return nothing_to_do(stats);
+    if (batch && (!views || !out_rgb)) return fail(ORT_ERR_INVALID, "null views or framebuffer");
+    if (!batch && !out_rgb) return fail(ORT_ERR_INVALID, host ? "null framebuffer" : "null device framebuffer");
+    if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
+    if (!s || !p) return fail(ORT_ERR_INVALID, "null scene or params");
+    ort_render_params q = *p;
+    q.chunk = q.spp;
+    int rc = check_param_values(s, &q);
+    if (rc != ORT_OK) return rc;
+    if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp (the cap on a pixel's samples) must be <= 1 << 24: a sample count must be exact in float");
+    if (!sample_map) return fail(ORT_ERR_INVALID, host ? "null sample_map" : "null device sample_map");
+    rc = check_ptrs({{sample_map, true, 4}, {out_rgb, true, 4}, {out_m2, false, 4}, {states, false, 4}}, "", "", "sample_map, out_rgb, out_m2 and final_states must be 4-byte aligned");
+    if (rc != ORT_OK) return rc;
+    if (q.policy != ORT_POLICY_PIXEL) return fail(ORT_ERR_UNSUPPORTED, "the sample-map render cuts one-pixel jobs: it needs the PIXEL policy");
+    if (q.shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, "the sample-map render is not sharded");
+    if (q.flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "the sample-map render has no packed framebuffer");
+    ort_view own;
+    if (batch) {
+        if ((rc = check_views_in_box(s, views, view_count)) != ORT_OK) return rc;
+    } else {
+        ort::camera_basis(*s, q.width, q.height, &own.camera);
+        own.seed = q.seed;
+        views = &own;
+    }
+    if ((rc = check_resident(s)) != ORT_OK) return rc;
+    ort::RenderCall c{host, stream, stats};
+    c.views = views; c.view_count = view_count; c.sample_map = sample_map;
+    return run_render(s, &q, c, out_rgb, nullptr, out_m2, states);
+}
+
 /* First-hit feature renders, one frame or a batch of views: render_adaptive_common's order with the planes where ad stands.
    view_count == 0 is OK whatever else is passed (the views form); then nulls (the planes struct, all five feature planes, views) and
    the view cap, the params as the render call judges them (chunk and rr are not the caller's to set here), spp above 1 << 24 and the
@@ -773,6 +812,10 @@ int ort_render_light_groups_device(ort_scene *s, const ort_render_params *p, con
 int ort_render_views_light_groups(ort_scene *s, const ort_render_params *p, const ort_light_groups *groups, const ort_view *views, uint32_t view_count, float *out_groups, float *out_rgb, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_groups_common(s, p, groups, views, view_count, true, true, out_groups, out_rgb, final_states, nullptr, stats); }); }
 int ort_render_views_light_groups_device(ort_scene *s, const ort_render_params *p, const ort_light_groups *groups, const ort_view *views, uint32_t view_count, void *d_out_groups, void *d_out_rgb, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_groups_common(s, p, groups, views, view_count, true, false, d_out_groups, d_out_rgb, d_final_states, hip_stream, stats); }); }
 int ort_render_views_adaptive_device(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, const ort_view *views, uint32_t view_count, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, views, view_count, true, false, d_out_rgb, d_out_spp, d_out_m2, d_final_states, hip_stream, stats); }); }
+int ort_render_sample_map(ort_scene *s, const ort_render_params *p, const uint32_t *sample_map, float *out_rgb, float *out_m2, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_sample_map_common(s, p, nullptr, 1, false, true, sample_map, out_rgb, out_m2, final_states, nullptr, stats); }); }
+int ort_render_sample_map_device(ort_scene *s, const ort_render_params *p, const void *d_sample_map, void *d_out_rgb, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_sample_map_common(s, p, nullptr, 1, false, false, d_sample_map, d_out_rgb, d_out_m2, d_final_states, hip_stream, stats); }); }
+int ort_render_views_sample_map(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const uint32_t *sample_map, float *out_rgb, float *out_m2, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_sample_map_common(s, p, views, view_count, true, true, sample_map, out_rgb, out_m2, final_states, nullptr, stats); }); }
+int ort_render_views_sample_map_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const void *d_sample_map, void *d_out_rgb, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_sample_map_common(s, p, views, view_count, true, false, d_sample_map, d_out_rgb, d_out_m2, d_final_states, hip_stream, stats); }); }
 int ort_render_features(ort_scene *s, const ort_render_params *p, const ort_feature_planes *planes, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, nullptr, 1, false, true, planes, nullptr, stats); }); }
 int ort_render_features_device(ort_scene *s, const ort_render_params *p, const ort_feature_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, nullptr, 1, false, false, planes, hip_stream, stats); }); }
 int ort_render_views_features(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_feature_planes *planes, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, views, view_count, true, true, planes, nullptr, stats); }); }

@@ -284,6 +284,10 @@ static int launch_groups(DeviceScene *, const LaunchPlan &pl, const SceneView &s
     ort_launch_render_groups(plan_variant(pl), pl.grid, stream, sv, hot);
     return ORT_OK;
 }
+static int launch_sample_map(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
+    ort_launch_render_sample_map(plan_variant(pl), pl.grid, stream, sv, hot);
+    return ORT_OK;
+}
 
 /* What launches each of the built kernels (kBuiltKernels, ort_plan.h), in that list's order: a kernel of this unit, which its
    entry here instantiates, or the host function that launches what another family is made of */
@@ -301,6 +305,7 @@ constexpr Launcher exchange() { return {{KF_EXCHANGE, C, D, true, true, false}, 
 constexpr Launcher five(bool d) { return {{KF_FIVE, false, d, true, true, false}, nullptr, launch_five_waves}; }
 constexpr Launcher adaptive(bool c, bool d, bool t) { return {{KF_ADAPTIVE, c, d, t, true, false}, nullptr, launch_adaptive}; }
 constexpr Launcher groups(bool c, bool d, bool t) { return {{KF_GROUPS, c, d, t, true, false}, nullptr, launch_groups}; }
+constexpr Launcher sample_map(bool c, bool d, bool t) { return {{KF_SAMPLE_MAP, c, d, t, true, false}, nullptr, launch_sample_map}; }
 constexpr Launcher kLaunchers[] = {
     {{KF_WAVEFRONT, false, false, false, false, false}, nullptr, launch_wavefront<false>},
     {{KF_WAVEFRONT, true, false, false, false, false}, nullptr, launch_wavefront<true>},
@@ -316,6 +321,8 @@ constexpr Launcher kLaunchers[] = {
     adaptive(true, false, false), adaptive(true, false, true), adaptive(true, true, false), adaptive(true, true, true),
     groups(false, false, false), groups(false, false, true), groups(false, true, false), groups(false, true, true),
     groups(true, false, false), groups(true, false, true), groups(true, true, false), groups(true, true, true),
+    sample_map(false, false, false), sample_map(false, false, true), sample_map(false, true, false), sample_map(false, true, true),
+    sample_map(true, false, false), sample_map(true, false, true), sample_map(true, true, false), sample_map(true, true, true),
 };
 constexpr bool launchers_match(size_t i = 0) { return i == kBuiltKernelCount || (kLaunchers[i].variant == kBuiltKernels[i] && launchers_match(i + 1)); }
 static_assert(sizeof(kLaunchers) / sizeof(kLaunchers[0]) == kBuiltKernelCount && launchers_match(),
@@ -500,8 +507,9 @@ static int print_util_diag(const DeviceScene *d, std::string *err) {
     return ORT_OK;
 }
 
-/* The camera render call, plain, (c.ad) adaptive or (c.groups) split by light group.  What runs, on which grid and with which
-   thresholds is plan_render's, plan_render_adaptive's or plan_render_groups' decision (ort_plan.h), and what the RenderView says besides pointers is render_view's (ort_setup.h); this
+/* The camera render call, plain, (c.ad) adaptive, (c.groups) split by light group or (c.sample_map) cut by the caller's map.  What
+   runs, on which grid and with which thresholds is plan_render's, plan_render_adaptive's, plan_render_groups' or
+   plan_render_sample_map's decision (ort_plan.h), and what the RenderView says besides pointers is render_view's (ort_setup.h); this
    is the plumbing around them: settle the previous call, plan, staging, views, buffers, launch, combine, finish */
 int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c, void *out_rgb, void *out_spp, void *out_m2, void *states, std::string *err) {
     DeviceScene *d = scene->dev;
@@ -516,7 +524,8 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
 
     SceneView sv = scene_view(scene, d);
     const SceneTraits traits = scene_traits(scene, d);
-    const LaunchPlan pl = c.groups ? plan_render_groups(traits, *p, d->knobs, view_count)
+    const LaunchPlan pl = c.sample_map ? plan_render_sample_map(traits, *p, d->knobs, view_count)
+                          : c.groups ? plan_render_groups(traits, *p, d->knobs, view_count)
                           : c.ad ? plan_render_adaptive(traits, *p, d->knobs, view_count)
                                : plan_render(traits, *p, c.jobs != nullptr, c.job_count, /* w5_layout_ok */ true, d->knobs, view_count);
     sv.util = pl.util ? d->ctrl() + 8 : nullptr;
@@ -533,14 +542,17 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     /* the planes as the lanes see them: the caller's device pointers, or the scene's staging buffers holding the caller's words.
        view_count frames, view-major, or the packed framebuffer; the 4-byte planes stage where the radiance queries' do */
     const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
-    Plane planes[5] = {{out_rgb, &d->staging, rv.packed_out ? (size_t)rv.my_blocks * 768u : pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u, nullptr},
+    Plane planes[6] = {{out_rgb, &d->staging, rv.packed_out ? (size_t)rv.my_blocks * 768u : pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u, nullptr},
                        {out_m2, &d->query_stage[4], pixels * 4u, nullptr}, {states, &d->query_stage[5], pixels * 4u, nullptr},
-                       {c.out_groups, &d->query_stage[0], pixels * 12u * (c.groups ? c.groups->group_count : 0u), nullptr}};
-    if ((rc = stage_planes_in(planes, 5, c.host, stream, err))) return rc;
+                       {c.out_groups, &d->query_stage[0], pixels * 12u * (c.groups ? c.groups->group_count : 0u), nullptr},
+                       /* the one plane that is read and not written: staged in with the others, never out */
+                       {const_cast<void *>(c.sample_map), &d->query_stage[1], pixels * 4u, nullptr}};
+    if ((rc = stage_planes_in(planes, 6, c.host, stream, err))) return rc;
     rv.out = (float *)planes[0].dev;
     rv.ad_spp = (uint32_t *)planes[1].dev;
     rv.ad_m2 = (float *)planes[2].dev;
     rv.final_states = (uint32_t *)planes[3].dev;
+    rv.sample_map = (const uint32_t *)planes[5].dev;
     if (c.groups) { /* the group table, the scene's copy of it on its way to the device; the previous call was settled above */
         d->group_tab_host.assign(c.groups->group_of_material, c.groups->group_of_material + c.groups->material_count);
         if ((rc = d->group_tab.ensure(d->group_tab_host.size(), err))) return rc;

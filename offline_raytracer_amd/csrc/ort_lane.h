@@ -14,7 +14,7 @@
  * Included by five translation units: ort_kernels.hip (the library's kernels at four waves per SIMD, and the host side),
  * ort_kernels_w5.hip (the plain-loop kernels at FIVE: 96 registers, 20 LDS stack entries, built with machine LICM off),
  * ort_kernels_adaptive.hip (the adaptive radiance queries' kernels, at the first unit's limits: a unit of their own so that they
- * compile beside it), ort_kernels_render_adaptive.hip (the adaptive camera render's and the light-group render's, likewise) and ort_kernels_irradiance.hip (the
+ * compile beside it), ort_kernels_render_adaptive.hip (the adaptive camera render's, the light-group render's and the sample-map render's, likewise) and ort_kernels_irradiance.hip (the
  * irradiance queries', likewise).  Same lane code, other limits
  * (ORT_WAVES_PER_EU, ORT_LDS_STACK, ORT_SPILL_STACK); each unit compiles it in a namespace of its own, which it names beside
  * its limits (ORT_NS; `ort` when it names none), so that two builds of one template are two symbols.  What does not depend on a
@@ -154,6 +154,10 @@ struct RenderView {
     const uint8_t *group_of_material;
     uint32_t group_count;
     float *group_out;
+    /* sample-map renders (ort_render_sample_map; the pt_sample_map kernels): a plane of view_count * W * H words, a pixel's word
+       where its colour is in out: the caller's sample count for that pixel, read once where its job is drawn and cut at spp
+       above, the cap.  ad_m2 and final_states (each may be null) are planes as the adaptive render's */
+    const uint32_t *sample_map;
 };
 
 /* ---- the order in which a CHUNK render issues its jobs ----------------------------------------------------------
@@ -257,6 +261,7 @@ struct FeatureIO {
 void ort_launch_w5(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);              /* KF_FIVE: ort_kernels_w5.hip */
 void ort_launch_render_adaptive(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot); /* KF_ADAPTIVE: ort_kernels_render_adaptive.hip */
 void ort_launch_render_groups(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);   /* KF_GROUPS: ort_kernels_render_adaptive.hip */
+void ort_launch_render_sample_map(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot); /* KF_SAMPLE_MAP: ort_kernels_render_adaptive.hip */
 void ort_launch_radiance_adaptive(const ort::QueryPlan &pl, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);                    /* ort_kernels_adaptive.hip */
 void ort_launch_irradiance(const ort::QueryPlan &pl, bool adaptive, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);            /* ort_kernels_irradiance.hip */
 #endif
@@ -430,6 +435,13 @@ constexpr uint32_t LF_HEMI = 1u << 8;
    triple per emission and divides them in place at the job's end -- no registers, no LDS, no atomics.  The render's own frame and
    the final states are optional planes.  Everything of it sits under if constexpr (GROUPS) */
 constexpr uint32_t LF_GROUPS = 1u << 9;
+/* SPPMAP: sample-map renders (ort_render_sample_map; with VIEWS, one-pixel jobs in JOBS_PIXEL mode): the job of pixel i is
+   n = min(rv.c->sample_map[i], spp_u) samples long, spp_u being the cap; the lane that draws the job reads the word once, and a
+   job of no samples is dropped right there, as a pixel outside the rect is: nothing written, the stream never started, the next job
+   drawn in the same pass.  A (the lane's AdaptState) holds n in `next` and the sum of squared sample luminance in q; the job
+   writes the mean over n and, where asked for, that sum and the stream's state.  Everything of it sits under
+   if constexpr (SPPMAP) */
+constexpr uint32_t LF_SPPMAP = 1u << 16;
 /* the walk's own options */
 constexpr uint32_t LF_TREELET = 1u << 10;     /* traverse: the top of the binary tree is read from the LDS tables (with TABS, never WIDE) */
 constexpr uint32_t LF_ANNOUNCE = 1u << 11;    /* traverse asks for a finished ray's PrimInfo (announce_winner); resolve_hit then finds it ANNOUNCED */
@@ -446,7 +458,7 @@ constexpr uint32_t LF_OF_PROLOGUE = LF_COUNTERS | LF_TABS | LF_HAS_EXCL;
 constexpr uint32_t LF_OF_BEGIN_RAY = LF_COUNTERS | LF_TABS;
 constexpr uint32_t LF_OF_TRAVERSE = LF_COUNTERS | LF_TREELET | LF_ANNOUNCE | LF_WIDE;
 constexpr uint32_t LF_OF_RESOLVE_HIT = LF_COUNTERS | LF_TABS | LF_ANNOUNCE | LF_WIDE;
-constexpr uint32_t LF_OF_PRODUCE_RAY = LF_COUNTERS | LF_DIFFUSE | LF_TABS | LF_IMPLICIT | LF_VIEWS | LF_RAYS | LF_ADAPT | LF_HEMI | LF_GROUPS;
+constexpr uint32_t LF_OF_PRODUCE_RAY = LF_COUNTERS | LF_DIFFUSE | LF_TABS | LF_IMPLICIT | LF_VIEWS | LF_RAYS | LF_ADAPT | LF_HEMI | LF_GROUPS | LF_SPPMAP;
 constexpr uint32_t LF_OF_LANE = LF_OF_PRODUCE_RAY | LF_WIDE; /* pt_lane ... radiance_lane: a job's flavour */
 /* ... and, from a lane's flavour f, the words of the three steps of its loop: begin_ray (and a prologue in its place); traverse,
    where finished rays announce their winners and the top of the binary tree comes from the LDS tables if there are any; and the
@@ -459,12 +471,14 @@ constexpr uint32_t resolve_of(uint32_t f) { return (f & (LF_COUNTERS | LF_TABS |
 constexpr bool flavour_ok(uint32_t f, uint32_t reads) {
     const bool IMPLICIT = f & LF_IMPLICIT, WIDE = f & LF_WIDE, VIEWS = f & LF_VIEWS, RAYS = f & LF_RAYS, ADAPT = f & LF_ADAPT;
     const bool HEMI = f & LF_HEMI, GROUPS = f & LF_GROUPS, TREELET = f & LF_TREELET, EXACT_ORDER = f & LF_EXACT_ORDER;
+    const bool SPPMAP = f & LF_SPPMAP;
     return (f & ~reads) == 0u
         && (!RAYS || (IMPLICIT && !VIEWS))                        /* a caller's ray array is an implicit job space of its own */
         && (!ADAPT || (IMPLICIT && (RAYS || VIEWS)))              /* the adaptive rule is built for the radiance queries and for one-pixel jobs of a batch of views */
         && (!HEMI || RAYS)                                        /* the hemisphere draw starts a sample of a radiance query's job */
         && (!GROUPS || (IMPLICIT && VIEWS && !RAYS && !ADAPT))    /* the group sums are built for plain one-pixel jobs of a batch of views */
-        && (!WIDE || !(VIEWS || RAYS || ADAPT || HEMI || GROUPS || TREELET)) /* the 4-wide tree serves the single frame's plain loop, and has no treelet */
+        && (!SPPMAP || (IMPLICIT && VIEWS && !RAYS && !ADAPT && !GROUPS)) /* the sample map cuts plain one-pixel jobs of a batch of views */
+        && (!WIDE || !(VIEWS || RAYS || ADAPT || HEMI || GROUPS || SPPMAP || TREELET)) /* the 4-wide tree serves the single frame's plain loop, and has no treelet */
         && (!EXACT_ORDER || !(f & (LF_FINITE_RAY | LF_FROM_TAB))); /* the exact walk reads HBM */
 }
 
@@ -1185,13 +1199,13 @@ ORT_D bool adaptive_stop(V3 C, float Q, uint32_t n, float tolerance, float lum_f
     return vm <= thr * thr;
 }
 
-template <uint32_t F> /* IMPLICIT ... GROUPS: at their names, LF_IMPLICIT ... LF_GROUPS */
+template <uint32_t F> /* IMPLICIT ... SPPMAP: at their names, LF_IMPLICIT ... LF_SPPMAP */
 ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, Prof &pr,
                        float *focal_cache = nullptr, int focal_stride = 0, uint32_t spp_u = 0, uint32_t *late_flag = nullptr, bool no_new_job = false,
                        unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
     static_assert(flavour_ok(F, LF_OF_PRODUCE_RAY), "see flavour_ok");
     constexpr bool COUNTERS = F & LF_COUNTERS, DIFFUSE = F & LF_DIFFUSE, TABS = F & LF_TABS, IMPLICIT = F & LF_IMPLICIT, VIEWS = F & LF_VIEWS;
-    constexpr bool RAYS = F & LF_RAYS, ADAPT = F & LF_ADAPT, HEMI = F & LF_HEMI, GROUPS = F & LF_GROUPS;
+    constexpr bool RAYS = F & LF_RAYS, ADAPT = F & LF_ADAPT, HEMI = F & LF_HEMI, GROUPS = F & LF_GROUPS, SPPMAP = F & LF_SPPMAP;
     /* VIEWS: unused; every lane reads its view's camera where it needs it (load_view_camera) */
     const V3 cam_p = mk(sv.cam[0], sv.cam[1], sv.cam[2]);
     const V3 cam_x = mk(sv.cam[3], sv.cam[4], sv.cam[5]);
@@ -1228,7 +1242,7 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 V3 e = P.primary ? m.emit : had(P.weight, m.emit);
                 if (P.primary || (!isnan3(e) && !isinf3(e))) {
                     P.color = add(P.color, e);
-                    if constexpr (ADAPT) { const float y = adaptive_luminance(e); A->q = A->q + y * y; }
+                    if constexpr (ADAPT || SPPMAP) { const float y = adaptive_luminance(e); A->q = A->q + y * y; }
                     if constexpr (GROUPS) {
                         const uint32_t g = rv.c->group_of_material[hit_mat];
                         if (g < rv.c->group_count) {
@@ -1295,7 +1309,9 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
             /* a lane arrives here after its sample ended (PS_SAMPLE), or with nothing yet (PS_NEED_JOB).
                Pixel write-back, next pixel / next job and the new camera ray all happen in this same
                pass, so the rest of the wave does not wait through a second trip round the loop. */
-            const uint32_t job_spp = IMPLICIT ? spp_u : P.spp;
+            uint32_t job_spp_of_lane = IMPLICIT ? spp_u : P.spp;
+            if constexpr (SPPMAP) job_spp_of_lane = A->next; /* the n of the job in hand; with none in hand (P.ps is not PS_SAMPLE) whatever the word holds decides nothing */
+            const uint32_t job_spp = job_spp_of_lane;
             bool job_ends = P.ps == PS_SAMPLE && P.sample == job_spp;
             if constexpr (ADAPT) job_ends = P.ps == PS_SAMPLE && (P.sample == job_spp || A->next == 0u); /* ... or the rule said stop */
             if (job_ends) {
@@ -1330,6 +1346,11 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 if constexpr (ADAPT) { /* JOBS_PIXEL: the pixel's words of its view's planes, view_count frames of W * H each */
                     const size_t at = plane_index(rv, P.job_index, px, py);
                     if (rv.c->ad_spp) rv.c->ad_spp[at] = P.sample;
+                    if (rv.c->ad_m2) rv.c->ad_m2[at] = A->q;
+                    if (rv.c->final_states) rv.c->final_states[at] = P.rng;
+                }
+                if constexpr (SPPMAP) { /* likewise, without the sample count: the caller holds it */
+                    const size_t at = plane_index(rv, P.job_index, px, py);
                     if (rv.c->ad_m2) rv.c->ad_m2[at] = A->q;
                     if (rv.c->final_states) rv.c->final_states[at] = P.rng;
                 }
@@ -1411,6 +1432,12 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                     int x = (int)((rv.c->block_x0 + blk % rv.c->blocks_w) * 8u + (pin & 7u));
                     int y = (int)((rv.c->block_y0 + blk / rv.c->blocks_w) * 8u + (pin >> 3));
                     if (x < rv.c->x0 || x >= rv.c->x1 || y < rv.c->y0 || y >= rv.c->y1) continue;
+                    if constexpr (SPPMAP) { /* the job's length, one word of the caller's map, cut at the cap; no samples: no job */
+                        const uint32_t asked = rv.c->sample_map[plane_index(rv, P.job_index, (uint32_t)x, (uint32_t)y)];
+                        const uint32_t n = asked < spp_u ? asked : spp_u;
+                        if (n == 0u) continue;
+                        A->next = n;
+                    }
                     uint32_t pix = (uint32_t)(y * rv.W + x);
                     if (!IMPLICIT) P.jxx = (uint32_t)x | ((uint32_t)(x + 1) << 16);
                     P.pxy = (uint32_t)x | ((uint32_t)y << 16);
@@ -1434,6 +1461,7 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 P.sample = 0;
                 P.ps = PS_SAMPLE;
                 if constexpr (ADAPT) { A->q = 0.0f; A->next = rv.c->ad_min_spp; }
+                if constexpr (SPPMAP) A->q = 0.0f;
                 if constexpr (GROUPS) {
                     for (uint32_t g = 0; g < rv.c->group_count; ++g) {
                         float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
@@ -1447,6 +1475,9 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                     focal_cache[0] = f.x; focal_cache[focal_stride] = f.y; focal_cache[2 * focal_stride] = f.z;
                 }
             }
+            if constexpr (SPPMAP) {
+                /* a job in hand has n >= 1 samples and P.sample < n here: nothing to skip */
+            } else
             if (P.sample == job_spp) continue; /* spp == 0: the reference's sample loop runs zero times */
             /* ray.cpp:1215-1221: point on the focal plane through the pixel centre: a function of the pixel alone,
                read back from the per-lane cache or (wavefront mode) recomputed -- same expressions, same bits */
@@ -1849,6 +1880,8 @@ ORT_D void flush_counters(const RenderHot &rv, const Counters &c, bool all) {
 /* ADAPT: the adaptive camera render (pt_adaptive): the same loop, a pixel ending where produce_ray's stopping rule says; A is the
    lane's AdaptState, wherever the caller keeps it */
 /* GROUPS: the light-group render (pt_groups): the same loop, produce_ray keeping the group sums in the output frames */
+/* SPPMAP: the sample-map render (pt_sample_map): the same loop, produce_ray cutting every job at its word of the caller's map; A
+   as for ADAPT */
 template <uint32_t F>
 ORT_D void pt_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, float *lds_focal, const int tid,
                    const uint32_t lane_id, bool prof_on = false, unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
@@ -2370,6 +2403,26 @@ pt_groups(SceneView sv, RenderHot rv) {
     if (TABS) fill_tab(sv, lds_tab);
     pt_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_GROUPS>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
                                                                      wave_job_pool(rv, lds_pool));
+}
+
+/* The sample-map render (ort_render_sample_map, ort_render_views_sample_map): the plain loop over the implicit one-pixel jobs of a
+   batch of views (JOBS_PIXEL; the single frame is the one-view batch of the scene's own camera), every job as long as the caller's
+   map says (produce_ray's SPPMAP flag).  Built beside pt_adaptive, in ort_kernels_render_adaptive.hip alone.  The job's length and
+   its sum of squared sample luminance are the two LDS words per lane that pt_adaptive keeps its AdaptState in, for that
+   kernel's reason: touched once per sample, not worth two registers through the traversal loop.  No probes, no drain times */
+template <bool COUNTERS, bool DIFFUSE, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+pt_sample_map(SceneView sv, RenderHot rv) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ float lds_focal[3 * kBlock]; /* focal[component][lane] */
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as pt_persistent */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    static_assert(sizeof(AdaptState) == sizeof(uint2), "a lane's AdaptState is two words of LDS");
+    __shared__ uint2 lds_adapt[kBlock]; /* raw words: produce_ray sets n where it draws a job and Q at the pixel's start; before a lane's first job n is read and not used */
+    AdaptState *const A = reinterpret_cast<AdaptState *>(lds_adapt) + threadIdx.x;
+    if (TABS) fill_tab(sv, lds_tab);
+    pt_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_SPPMAP>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
+                                                                     wave_job_pool(rv, lds_pool), A);
 }
 
 /* the same with the ray exchange (pt_lane_x): implicit job spaces only, LDS tables required */

@@ -3,7 +3,7 @@
  * ort_kernels.hip launches, with which grid and which thresholds, decided from a few facts about the uploaded scene
  * (SceneTraits), the render parameters or the ray count, and the developer knobs: plan_render for ort_render_image and
  * ort_render_views, plan_render_adaptive for ort_render_adaptive and ort_render_views_adaptive, plan_render_groups for ort_render_light_groups and
- * ort_render_views_light_groups, plan_ray_query for ort_raycast and ort_occluded, plan_radiance for ort_radiance.  Host-only and free of HIP,
+ * ort_render_views_light_groups, plan_render_sample_map for ort_render_sample_map and ort_render_views_sample_map, plan_ray_query for ort_raycast and ort_occluded, plan_radiance for ort_radiance.  Host-only and free of HIP,
  * so that tools/launch_plan.cpp and tests/test_launch_plan.py can hold the measured crossovers without a device.
  * ort_kernels.hip turns a LaunchPlan or a QueryPlan into launches and decides nothing.
  */
@@ -191,6 +191,7 @@ struct LaunchPlan {
     bool views = false;
     bool adaptive = false; /* the adaptive camera render (plan_render_adaptive): the pt_adaptive kernels <counters, diffuse, tabs> */
     bool groups = false;   /* the light-group render (plan_render_groups): the pt_groups kernels <counters, diffuse, tabs> */
+    bool sample_map = false; /* the sample-map render (plan_render_sample_map): the pt_sample_map kernels <counters, diffuse, tabs> */
     uint32_t view_count = 1;
     unsigned long long view_jobs = 0; /* jobs of one view (job_count / view_count) */
     unsigned int grid = 1;
@@ -385,10 +386,22 @@ inline LaunchPlan plan_render_groups(const SceneTraits &t, const ort_render_para
     return pl;
 }
 
+/* The launch of the sample-map render (ort_render_sample_map, ort_render_views_sample_map; the pt_sample_map kernels) over
+   view_count >= 1 frames: plan_render_adaptive's launch in every field, with the caller's map where the stopping rule stands.  The
+   job space holds every pixel under the rect, whatever its word of the map says: the plan cannot read a map that may live on the
+   device, and a job of no samples ends where it is drawn.  p.spp is the cap on a job's length (render_view's to say); p.chunk is
+   not read */
+inline LaunchPlan plan_render_sample_map(const SceneTraits &t, const ort_render_params &p, const Knobs &kn, uint32_t view_count = 1) {
+    LaunchPlan pl = plan_render_adaptive(t, p, kn, view_count);
+    pl.adaptive = false;
+    pl.sample_map = true;
+    return pl;
+}
+
 /* ---- the kernels that are built ------------------------------------------------------------------------------------------ */
 /* A render kernel by name: its family and its template arguments.  A bool its family's kernels do not take is stated as what
    they are compiled with (the ray exchange and the five-waves build: tabs and implicit; wavefront mode: none of the four) */
-enum KernelFamily : int { KF_NONE = 0, KF_WAVEFRONT, KF_LOOP, KF_LOOP_VIEWS, KF_EXCHANGE, KF_FIVE, KF_ADAPTIVE, KF_GROUPS };
+enum KernelFamily : int { KF_NONE = 0, KF_WAVEFRONT, KF_LOOP, KF_LOOP_VIEWS, KF_EXCHANGE, KF_FIVE, KF_ADAPTIVE, KF_GROUPS, KF_SAMPLE_MAP };
 struct KernelVariant {
     KernelFamily family;
     bool counters, diffuse, tabs, implicit, wide;
@@ -397,21 +410,22 @@ constexpr bool operator==(const KernelVariant &a, const KernelVariant &b) {
     return a.family == b.family && a.counters == b.counters && a.diffuse == b.diffuse && a.tabs == b.tabs && a.implicit == b.implicit && a.wide == b.wide;
 }
 
-/* the variant a plan asks for.  A plan that claims two families at once, or the stopping rule or the group sums outside a PIXEL
-   batch of views, names none */
+/* the variant a plan asks for.  A plan that claims two families at once, or the stopping rule, the group sums or the sample map
+   outside a PIXEL batch of views, names none */
 inline KernelVariant plan_variant(const LaunchPlan &pl) {
-    if ((int)pl.wavefront + (int)pl.exchange + (int)pl.five + (int)pl.views > 1 || (pl.adaptive && pl.groups) ||
-        ((pl.adaptive || pl.groups) && !(pl.views && pl.mode == PLAN_JOBS_PIXEL)))
+    if ((int)pl.wavefront + (int)pl.exchange + (int)pl.five + (int)pl.views > 1 || (int)pl.adaptive + (int)pl.groups + (int)pl.sample_map > 1 ||
+        ((pl.adaptive || pl.groups || pl.sample_map) && !(pl.views && pl.mode == PLAN_JOBS_PIXEL)))
         return {KF_NONE, false, false, false, false, false};
     if (pl.wavefront) return {KF_WAVEFRONT, pl.counters, false, false, false, false};
     if (pl.exchange) return {KF_EXCHANGE, pl.counters, pl.diffuse, true, true, false};
     if (pl.five) return {KF_FIVE, false, pl.diffuse, true, true, false};
-    return {pl.adaptive ? KF_ADAPTIVE : pl.groups ? KF_GROUPS : pl.views ? KF_LOOP_VIEWS : KF_LOOP, pl.counters, pl.diffuse, pl.tabs, pl.implicit, pl.wide};
+    return {pl.adaptive ? KF_ADAPTIVE : pl.groups ? KF_GROUPS : pl.sample_map ? KF_SAMPLE_MAP : pl.views ? KF_LOOP_VIEWS : KF_LOOP, pl.counters, pl.diffuse, pl.tabs, pl.implicit, pl.wide};
 }
 
 /* All that is built, and every one of them costs its share of minutes of compile time: ort_kernels.hip instantiates the first
    four families (its table of launchers is held against this list at compile time), ort_kernels_w5.hip the fifth,
-   ort_kernels_render_adaptive.hip the sixth and the seventh.  plan_render, plan_render_adaptive and plan_render_groups produce no other (tools/launch_plan sweep=1
+   ort_kernels_render_adaptive.hip the sixth, the seventh and the eighth.  plan_render, plan_render_adaptive, plan_render_groups and
+   plan_render_sample_map produce no other (tools/launch_plan sweep=1
    and tests/test_launch_plan.py hold them to it); one that did would be an error, not a fallback.  The ray queries' families are
    built for every combination of their bools and need no list */
 constexpr KernelVariant kBuiltKernels[] = {
@@ -438,6 +452,10 @@ constexpr KernelVariant kBuiltKernels[] = {
     {KF_GROUPS, false, true, false, true, false}, {KF_GROUPS, false, true, true, true, false},
     {KF_GROUPS, true, false, false, true, false}, {KF_GROUPS, true, false, true, true, false},
     {KF_GROUPS, true, true, false, true, false}, {KF_GROUPS, true, true, true, true, false},
+    {KF_SAMPLE_MAP, false, false, false, true, false}, {KF_SAMPLE_MAP, false, false, true, true, false},
+    {KF_SAMPLE_MAP, false, true, false, true, false}, {KF_SAMPLE_MAP, false, true, true, true, false},
+    {KF_SAMPLE_MAP, true, false, false, true, false}, {KF_SAMPLE_MAP, true, false, true, true, false},
+    {KF_SAMPLE_MAP, true, true, false, true, false}, {KF_SAMPLE_MAP, true, true, true, true, false},
 };
 constexpr size_t kBuiltKernelCount = sizeof(kBuiltKernels) / sizeof(kBuiltKernels[0]);
 
