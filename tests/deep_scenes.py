@@ -223,3 +223,53 @@ def assert_conditions(w):
     for tool, (probe, counters) in probes(w, "graze").items():   # the grazing set: a quarter of it re-traversed, in scratch
         assert probe[1]["traversals"] >= len(w.graze) // 4 and probe[1]["above"] >= len(w.graze) // 4, (tool, probe)
         assert counters["fallback"] * 20 <= counters["rays"], (tool, counters)
+
+
+# ---- the light-group and sample-map renders: the host's frame, 4 spp ---------------------------------------------------------------
+LIGHT_GROUPS = (8, 5)   # G, and the group the scene's one light material is in: seven frames stay +0
+MAP_CAP = 4
+
+
+def light_material(w):
+    lights = np.nonzero(w.flat.materials["is_light"])[0]
+    assert len(lights) == 1
+    return int(lights[0])
+
+
+def group_table(w, filler=0x5A):
+    """a byte per material: the light's group, a filler the call must not read for every other material"""
+    t = np.full(len(w.flat.materials), filler, np.uint8)
+    t[light_material(w)] = LIGHT_GROUPS[1]
+    return t
+
+
+def pixel_chains(w):
+    """render_adaptive_cases.chains of the host's whole frame, four samples a pixel, from the scene's own camera"""
+    import render_adaptive_cases as rac
+    width, height, spp, _ = RENDER
+
+    def make():
+        w.osc.set_camera(w.scene.camera(width, height))
+        return rac.chains(w.osc, width, height, SEED, rac.RR, spp=spp)
+    return cached(w, "pixel chains", make)
+
+
+def light_groups_expected(w):
+    """-> (frames (8, h, w, 3), rgb (h, w, 3), states (h, w)): the light's frame and out_rgb are the oracle's PIXEL render of the
+    scene, the states its one-pixel jobs', every other frame +0"""
+    width, height, spp, _ = RENDER
+    img, _ = oracle_render(w, width, height, spp, "pixel", 0)
+    states = np.zeros((height, width), "<u4")
+    for (x, y), (_, st) in pixel_chains(w).items():
+        states[y, x] = st[spp - 1]
+    frames = np.zeros((LIGHT_GROUPS[0], height, width, 3), "<f4")
+    frames[LIGHT_GROUPS[1]] = img
+    return frames, img, states
+
+
+def sample_map_expected(w):
+    """sample_map_cases.mixed_map() at cap 4 -> (the map, (rgb, m2, states)): the oracle's chains cut at the map's counts"""
+    import sample_map_cases as sm
+    assert (sm.W, sm.H) == RENDER[:2]
+    smap = sm.mixed_map()
+    return smap, sm.expected_from(pixel_chains(w), smap, MAP_CAP)

@@ -118,9 +118,28 @@ def _scale(s, v):
     return (np.asarray(s, "<f4").reshape(-1, 1) * np.asarray(v, "<f4").reshape(1, 3)).astype("<f4")
 
 
-def camera_rays(oracle, cam, w, h, seed, spp, rect=None):
+def oracle_streams(oracle, seed, pix):
+    """the pixels' stream seeds, one oracle_job_seed call each"""
+    return np.array([job_seed(seed, int(i)) for i in pix], "<u4")
+
+
+def oracle_draw(oracle, state):
+    """the aperture angle's draw, one oracle_rng_table call a stream -> (the states after it, the angles)"""
+    after, rad = np.zeros(len(state), "<u4"), np.zeros(len(state), "<f4")
+    for i in range(len(state)):
+        # n = 2: {state, value} x 2 of rng_01, then two chained random_between(0, 2 pi): the state after two steps sits
+        # in the second rng_01 entry, the first random_between value behind the four words
+        b = oracle.rng_table(int(state[i]), 2)
+        after[i] = struct.unpack_from("<I", b, 8)[0]
+        rad[i] = struct.unpack_from("<f", b, 16)[0]
+    return after, rad
+
+
+def camera_rays(oracle, cam, w, h, seed, spp, rect=None, streams=oracle_streams, draw=oracle_draw):
     """cam (4, 3): p, x_axis, y_axis, z_axis.  -> (ap (n, spp, 3), d (n, spp, 3), states after each sample (n, spp), xs, ys) for the
-    n pixels of rect in row-major order: every sample's primary ray as oracle_tiled_raytrace composes it, operation by operation"""
+    n pixels of rect in row-major order: every sample's primary ray as oracle_tiled_raytrace composes it, operation by operation.
+    streams, draw: the two steps that cost an oracle call a pixel, for a caller with a whole large frame to get through (and
+    its own duty to pin what it passes against these)"""
     cam = np.asarray(cam, "<f4").reshape(4, 3)
     p, X, Y, Z = cam
     x0, y0, x1, y1 = rect if rect else (0, 0, w, h)
@@ -133,18 +152,12 @@ def camera_rays(oracle, cam, w, h, seed, spp, rect=None):
         py = ((F(2.0) * ys.astype("<f4")).astype("<f4") / F(h)).astype("<f4") - F(1.0)
         to_pixel = _normalize(oracle, ((_scale(px, X) + _scale(py, Y)).astype("<f4") - Z[None, :]).astype("<f4"))
         focal = (p[None, :] + (F(fl) * to_pixel).astype("<f4")).astype("<f4")
-        state = np.array([job_seed(seed, int(y) * w + int(x)) for x, y in zip(xs, ys)], "<u4")
+        state = streams(oracle, seed, ys.astype(np.int64) * w + xs)
         ap = np.zeros((n, spp, 3), "<f4")
         d = np.zeros((n, spp, 3), "<f4")
         after = np.zeros((n, spp), "<u4")
         for k in range(spp):
-            rad = np.zeros(n, "<f4")
-            for i in range(n):
-                # n = 2: {state, value} x 2 of rng_01, then two chained random_between(0, 2 pi): the state after two steps sits
-                # in the second rng_01 entry, the first random_between value behind the four words
-                b = oracle.rng_table(int(state[i]), 2)
-                state[i] = struct.unpack_from("<I", b, 8)[0]
-                rad[i] = struct.unpack_from("<f", b, 16)[0]
+            state, rad = draw(oracle, state)
             sc = oracle.unit_batch(ref_io.make_unit_records(9, rad.reshape(-1, 1)))
             sn, cs = sc[:, 0].astype("<f4"), sc[:, 1].astype("<f4")
             a = (p[None, :] + _scale((F(0.1) * cs).astype("<f4"), X)).astype("<f4")

@@ -77,6 +77,30 @@ class _Flat:
     pass
 
 
+def dark_twin(oracle, flat, keep, csg=True):
+    """the OracleScene of flat whose light materials outside keep have emit = +0 (is_light stays); keep = None: flat's own"""
+    t = _Flat()
+    t.__dict__.update(flat.__dict__)
+    if keep is not None:
+        mats = flat.materials.copy()
+        for m in np.nonzero(flat.materials["is_light"])[0]:
+            if int(m) not in keep:
+                mats["emit"][m] = F(0.0)
+        assert (mats["is_light"] == flat.materials["is_light"]).all()
+        t.materials = mats
+    return oracle.OracleScene(t, with_reference_csg=csg)
+
+
+class SceneRef:
+    """what tools/host_sim loads of a scene that is no Case: host_light_groups' and host_sample_map's c"""
+
+    def __init__(self, scn, base):
+        self.scn, self.base = scn, base
+
+    def hs_args(self):
+        return [self.scn, self.base]
+
+
 class Case:
     """One scene: the product's committed scene, its flattened arrays, its light materials, and the oracle's frames of it and of
     its dark twins, each computed once and handed out read-only"""
@@ -102,7 +126,7 @@ class Case:
         self.flat = self.scene.flatten(W, H)
         self.lights = [int(m) for m in np.nonzero(self.flat.materials["is_light"])[0]]
         self.cam = np.asarray(self.flat.camera, "<f4").reshape(4, 3)
-        self._twins, self._frames = {}, {}
+        self._twins, self._frames, self._cams = {}, {}, {}
 
     def hs_args(self):
         return [self.scn, self.base]
@@ -127,52 +151,53 @@ class Case:
         """the OracleScene whose light materials outside keep have emit = +0; keep = None: the scene itself"""
         key = None if keep is None else frozenset(keep)
         if key not in self._twins:
-            t = _Flat()
-            t.__dict__.update(self.flat.__dict__)
-            if key is not None:
-                mats = self.flat.materials.copy()
-                for m in self.lights:
-                    if m not in key:
-                        mats["emit"][m] = F(0.0)
-                assert (mats["is_light"] == self.flat.materials["is_light"]).all()
-                t.materials = mats
-            self._twins[key] = self.oracle.OracleScene(t, with_reference_csg=self.csg)
+            self._twins[key] = dark_twin(self.oracle, self.flat, key, self.csg)
         return self._twins[key]
 
-    def frame(self, keep, spp, seed=SEED, cam=None, rect=None):
-        """the PIXEL render (H, W, 3) of twin(keep) from cam (the scene's own by default); pixels outside rect are +0"""
-        cam = self.cam if cam is None else np.asarray(cam, "<f4").reshape(4, 3)
-        key = (None if keep is None else frozenset(keep), spp, seed, cam.tobytes(), rect)
+    def camera(self, size=None):
+        """the scene's own camera for a frame of size (w, h): the module's 24 x 16 by default"""
+        size = tuple(size) if size else (W, H)
+        if size not in self._cams:
+            self._cams[size] = self.cam if size == (W, H) else np.asarray(self.scene.flatten(*size).camera, "<f4").reshape(4, 3)
+        return self._cams[size]
+
+    def frame(self, keep, spp, seed=SEED, cam=None, rect=None, size=None):
+        """the PIXEL render (h, w, 3) of twin(keep) from cam (the scene's own by default); pixels outside rect are +0.  size:
+        (w, h), the module's 24 x 16 by default"""
+        w, h = size if size else (W, H)
+        cam = self.camera(size) if cam is None else np.asarray(cam, "<f4").reshape(4, 3)
+        key = (None if keep is None else frozenset(keep), spp, seed, cam.tobytes(), rect, (w, h))
         if key not in self._frames:
             osc = self.twin(keep)
             osc.set_camera(cam)
-            img, _ = osc.render(W, H, spp, seed, "pixel", rect=rect, rr=RR, threads=8)
+            img, _ = osc.render(w, h, spp, seed, "pixel", rect=rect, rr=RR, threads=8)
             img.setflags(write=False)
             self._frames[key] = img
         return self._frames[key]
 
-    def states(self, spp, seed=SEED, cam=None, rect=None):
-        """the final states (H, W) of the scene's own one-pixel jobs, which are its PIXEL render's pixels; outside rect 0"""
-        cam = self.cam if cam is None else np.asarray(cam, "<f4").reshape(4, 3)
-        key = ("states", spp, seed, cam.tobytes(), rect)
+    def states(self, spp, seed=SEED, cam=None, rect=None, size=None):
+        """the final states (h, w) of the scene's own one-pixel jobs, which are its PIXEL render's pixels; outside rect 0"""
+        w, h = size if size else (W, H)
+        cam = self.camera(size) if cam is None else np.asarray(cam, "<f4").reshape(4, 3)
+        key = ("states", spp, seed, cam.tobytes(), rect, (w, h))
         if key not in self._frames:
-            img = self.frame(None, spp, seed, cam, rect)
+            img = self.frame(None, spp, seed, cam, rect, size)
             osc = self.twin(None)
             osc.set_camera(cam)
-            x0, y0, x1, y1 = rect if rect else (0, 0, W, H)
-            st = np.zeros((H, W), "<u4")
-            one = np.zeros((H, W, 3), "<f4")
+            x0, y0, x1, y1 = rect if rect else (0, 0, w, h)
+            st = np.zeros((h, w), "<u4")
+            one = np.zeros((h, w, 3), "<f4")
             for y in range(y0, y1):
                 for x in range(x0, x1):
-                    _, st[y, x] = osc.tiled_raytrace(one, x, y, x + 1, y + 1, self.oracle.job_seed(seed, y * W + x), spp, RR)
+                    _, st[y, x] = osc.tiled_raytrace(one, x, y, x + 1, y + 1, self.oracle.job_seed(seed, y * w + x), spp, RR)
             assert (one.view("<u4") == img.view("<u4")).all()   # the PIXEL render is these jobs
             st.setflags(write=False)
             self._frames[key] = st
         return self._frames[key]
 
-    def expected(self, groups, G, spp, seed=SEED, cam=None, rect=None):
-        """{material: group}, G -> the (G, H, W, 3) frames the call must give inside rect: frame g is the twin's that keeps group g"""
-        return np.stack([self.frame([m for m, k in groups.items() if k == g], spp, seed, cam, rect) for g in range(G)])
+    def expected(self, groups, G, spp, seed=SEED, cam=None, rect=None, size=None):
+        """{material: group}, G -> the (G, h, w, 3) frames the call must give inside rect: frame g is the twin's that keeps group g"""
+        return np.stack([self.frame([m for m, k in groups.items() if k == g], spp, seed, cam, rect, size) for g in range(G)])
 
 
 _cases = {}
@@ -187,18 +212,21 @@ def case(api, oracle, name, tmp_path_factory):
 BATCH_SEEDS = (SEED, 7, 99)
 
 
-def batch_cameras(api, c):
+def batch_cameras(api, c, size=None):
     """three views for a batch of the rooms: the scene's own camera, one a step nearer the table and turned a little, and the
-    scene's own again (on another seed: BATCH_SEEDS)"""
+    scene's own again (on another seed: BATCH_SEEDS); for frames of size (w, h), the module's 24 x 16 by default"""
+    w, h = size if size else (W, H)
+    own = c.camera(size)
     q = np.array([0.416981, 0.279589, 0.480987, 0.718247]) + np.array([0.02, -0.015, 0.01, 0.0])
-    other = api.camera_from_pose(c.cam[0] * F(0.9), q / np.linalg.norm(q), 0.2, W, H)
-    return np.stack([c.cam, other, c.cam])
+    other = api.camera_from_pose(own[0] * F(0.9), q / np.linalg.norm(q), 0.2, w, h)
+    return np.stack([own, other, own])
 
 
 # ---- outside the rect ------------------------------------------------------------------------------------------------------
-def inside(rect):
-    m = np.zeros((H, W), bool)
-    x0, y0, x1, y1 = rect if rect else (0, 0, W, H)
+def inside(rect, size=None):
+    w, h = size if size else (W, H)
+    m = np.zeros((h, w), bool)
+    x0, y0, x1, y1 = rect if rect else (0, 0, w, h)
     m[y0:y1, x0:x1] = True
     return m
 

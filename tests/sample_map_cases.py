@@ -31,30 +31,33 @@ BATCH_SEEDS = lg.BATCH_SEEDS
 assert (lg.W, lg.H, lg.RR) == (W, H, RR)
 
 
-def base_map(shift=0):
-    """every value of VALUES, laid out so that horizontal and vertical neighbours differ: the index steps by 1 along x and by
-    3 along y, modulo 8"""
-    y, x = np.mgrid[0:H, 0:W]
-    return np.array(VALUES, "<u4")[(x + 3 * y + shift) % len(VALUES)]
+def base_map(shift=0, size=None, values=VALUES):
+    """every value of `values`, laid out so that horizontal and vertical neighbours differ: the index steps by 1 along x and by
+    3 along y, modulo their number (8 for VALUES); size: (w, h), the module's 24 x 16 by default"""
+    w, h = size if size else (W, H)
+    y, x = np.mgrid[0:h, 0:w]
+    return np.array(values, "<u4")[(x + 3 * y + shift) % len(values)]
 
 
-def border(rect):
+def border(rect, size=None):
     """the pixels of rect's outermost ring"""
+    w, h = size if size else (W, H)
     x0, y0, x1, y1 = rect
-    m = np.zeros((H, W), bool)
+    m = np.zeros((h, w), bool)
     m[y0:y1, x0:x1] = True
     m[y0 + 1:y1 - 1, x0 + 1:x1 - 1] = False
     return m
 
 
-def mixed_map(shift=0):
-    """base_map with one whole 8 x 8 block of zeros, one row of zeros, and a zero on every other pixel of RECT's border"""
-    m = base_map(shift)
-    bx, by = ZERO_BLOCK
+def mixed_map(shift=0, size=None, values=VALUES, rect=RECT, zero_block=ZERO_BLOCK, zero_row=ZERO_ROW):
+    """base_map with one whole 8 x 8 block of zeros, one row of zeros, and a zero on every other pixel of rect's border"""
+    w, h = size if size else (W, H)
+    m = base_map(shift, size, values)
+    bx, by = zero_block
     m[by:by + 8, bx:bx + 8] = 0
-    m[ZERO_ROW, :] = 0
-    y, x = np.mgrid[0:H, 0:W]
-    m[border(RECT) & ((x + y) % 2 == 0)] = 0
+    m[zero_row, :] = 0
+    y, x = np.mgrid[0:h, 0:w]
+    m[border(rect, size) & ((x + y) % 2 == 0)] = 0
     return m
 
 
@@ -63,39 +66,50 @@ def counts(smap, cap=CAP):
     return np.minimum(np.asarray(smap, "<u4"), np.uint32(cap)).astype("<u4")
 
 
-def inside(rect):
-    return lg.inside(rect)
+def inside(rect, size=None):
+    return lg.inside(rect, size)
 
 
 _chains = {}
 
 
-def chains(c, seed=SEED, cam=None):
-    """{(x, y): (colours float32[CAP, 3], states)} of case c's whole frame from cam (the scene's own by default), once"""
-    cam = c.cam if cam is None else np.asarray(cam, "<f4").reshape(4, 3)
-    key = (c.name, seed, cam.tobytes())
+def chains(c, seed=SEED, cam=None, size=None, window=None, cap=CAP):
+    """{(x, y): (colours float32[cap, 3], states)} of case c's frame from cam (the scene's own by default), once; size: (w, h),
+    the module's 24 x 16 by default; window: the pixels that get a chain, the whole frame by default"""
+    w, h = size if size else (W, H)
+    cam = c.camera(size) if cam is None else np.asarray(cam, "<f4").reshape(4, 3)
+    key = (c.name, seed, cam.tobytes(), (w, h), window, cap)
     if key not in _chains:
         osc = c.twin(None)
         osc.set_camera(cam)
-        _chains[key] = rac.chains(osc, W, H, seed, RR, None, CAP)
+        _chains[key] = rac.chains(osc, w, h, seed, RR, window, cap)
     return _chains[key]
 
 
-def expected(c, smap, cap=CAP, seed=SEED, cam=None, rect=None):
-    """-> (rgb (H, W, 3) float32, m2 (H, W) float32, states (H, W) uint32): the oracle's planes where n >= 1 inside rect, the
-    guards elsewhere"""
+def expected_from(chain, smap, cap=CAP, rect=None, size=None):
+    """{(x, y): (colours, states)} of the pixels the oracle answers for, each at least min(cap, its count) samples long -> (rgb
+    (h, w, 3) float32, m2 (h, w) float32, states (h, w) uint32): the chain cut at n = min(map, cap) where n >= 1 inside rect,
+    the guards elsewhere"""
+    w, h = size if size else (W, H)
     n = counts(smap, cap)
-    rgb = np.full((H, W, 3), GUARD_RGB, "<f4")
-    m2 = np.full((H, W), GUARD_M2, "<f4")
-    fin = np.full((H, W), GUARD_STATE, "<u4")
-    m = inside(rect)
-    for (x, y), (cols, states) in chains(c, seed, cam).items():
+    rgb = np.full((h, w, 3), GUARD_RGB, "<f4")
+    m2 = np.full((h, w), GUARD_M2, "<f4")
+    fin = np.full((h, w), GUARD_STATE, "<u4")
+    m = inside(rect, size)
+    for (x, y), (cols, states) in chain.items():
         k = int(n[y, x])
         if k == 0 or not m[y, x]:
             continue
         rgb[y, x], took, m2[y, x], fin[y, x] = ac.cut(cols, states, Adaptive(k, k, 1, 0, 0))
         assert took == k
     return rgb, m2, fin
+
+
+def expected(c, smap, cap=CAP, seed=SEED, cam=None, rect=None, size=None, window=None, chain=CAP):
+    """-> (rgb (h, w, 3) float32, m2 (h, w) float32, states (h, w) uint32): the oracle's planes where n >= 1 inside rect, the
+    guards elsewhere; with a window, the oracle's planes inside it alone (a large frame is held against it window by window);
+    chain: the samples a pixel's chain holds, at least min(cap, the map's largest count)"""
+    return expected_from(chains(c, seed, cam, size, window, chain), smap, cap, rect, size)
 
 
 def assert_planes(got, want, what):
@@ -111,15 +125,16 @@ def assert_planes(got, want, what):
             raise AssertionError("%s: %d of %d %s differ bitwise; first at %s: %r vs %r" % (what, int(ne.sum()), ne.size, name, at, g[at], w_[at]))
 
 
-def guards(V=None, want_m2=True, want_states=True):
+def guards(V=None, want_m2=True, want_states=True, size=None):
     """the host planes of a call, every word a guard value"""
+    w, h = size if size else (W, H)
     lead = () if V is None else (V,)
-    return ([np.full(lead + (H, W, 3), GUARD_RGB, "<f4")] + ([np.full(lead + (H, W), GUARD_M2, "<f4")] if want_m2 else []) +
-            ([np.full(lead + (H, W), GUARD_STATE, "<u4")] if want_states else []))
+    return ([np.full(lead + (h, w, 3), GUARD_RGB, "<f4")] + ([np.full(lead + (h, w), GUARD_M2, "<f4")] if want_m2 else []) +
+            ([np.full(lead + (h, w), GUARD_STATE, "<u4")] if want_states else []))
 
 
-def batch_cameras(api, c):
-    return lg.batch_cameras(api, c)
+def batch_cameras(api, c, size=None):
+    return lg.batch_cameras(api, c, size)
 
 
 # ---- tools/host_sim --sample-map --------------------------------------------------------------------------------------------

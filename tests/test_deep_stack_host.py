@@ -171,3 +171,31 @@ def test_the_culling_slack_bounds_how_early_a_triangle_hit_may_be(api, oracle, w
     assert (early[missed] > 1.9e-4).all(), "a hit no earlier than the slack allows was missed: %r" % (np.sort(early[missed])[:5],)
     print("bounded walk: %d of %d hits missed, all among the %d rays whose hit precedes its plane by more than 1.9e-4" %
           (missed.sum(), len(missed), (early > 1.9e-4).sum()))
+
+
+# the light-group and sample-map lanes (pt_groups, pt_sample_map): a unit of their own on the device
+@pytest.mark.parametrize("env", ENVS, ids=ids)
+@pytest.mark.parametrize("tool", ds.TOOLS)
+def test_light_groups(w, tmp_path, tool, env):
+    """the scene's one light material in group 5 of 8: frame 5, out_rgb and the states are the oracle's PIXEL render, the other
+    seven frames +0 in every word"""
+    import light_groups_cases as lg
+    width, height, spp, _ = ds.RENDER
+    assert (lg.W, lg.H) == (width, height)
+    frames, rgb, states = lg.host_light_groups(hs.built(tool), tmp_path, lg.SceneRef(w.scn, w.base), ds.group_table(w), ds.LIGHT_GROUPS[0], spp,
+                                               seed=ds.SEED, env=env, threads=8)
+    want = ds.light_groups_expected(w)
+    assert (want[1] != 0).any()
+    for got, w_, label in zip((frames[0], rgb[0], states[0]), want, ("group frames", "out_rgb", "final states")):
+        lg.assert_plane(got, w_, None, lg.GUARD_F, "%s %r: %s" % (tool, env, label))
+
+
+@pytest.mark.parametrize("env", ENVS, ids=ids)
+@pytest.mark.parametrize("tool", ds.TOOLS)
+def test_sample_map(w, tmp_path, tool, env):
+    import light_groups_cases as lg
+    import sample_map_cases as sm
+    smap, want = ds.sample_map_expected(w)
+    got, _ = sm.host_sample_map(hs.built(tool), tmp_path, lg.SceneRef(w.scn, w.base), smap, ds.MAP_CAP, seed=ds.SEED, env=env, threads=8)
+    sm.assert_planes(tuple(p[0] for p in got), want, "%s %r" % (tool, env))
+    assert (sm.counts(smap, ds.MAP_CAP) == ds.MAP_CAP).any() and (want[0] != sm.GUARD_RGB).any()

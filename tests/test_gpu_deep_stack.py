@@ -183,3 +183,34 @@ def test_render_adaptive(w, knobs, variant):
                                                    rr=rac.RR, want_states=True)
     rac.assert_same((rgb, spp, m2, fin), want, variant)
     assert len(np.unique(spp)) > 1
+
+
+@pytest.mark.parametrize("variant", ["default", "tables_in_hbm", "general", "some_exact"])
+def test_light_groups(w, knobs, variant):
+    """pt_groups, built beside pt_adaptive: the scene's one light material in group 5 of 8, on guard-filled planes: frame 5,
+    out_rgb and the states are the oracle's PIXEL render, the other seven frames +0 in every word"""
+    import light_groups_cases as lg
+    width, height, spp, _ = ds.RENDER
+    G = ds.LIGHT_GROUPS[0]
+    want = ds.light_groups_expected(w)
+    knobs(VARIANTS.get(variant, {}))
+    for counters in (False, True):
+        out = [np.full((G, height, width, 3), lg.GUARD_F, "<f4"), np.full((height, width, 3), lg.GUARD_F, "<f4"), np.full((height, width), lg.GUARD_STATE, "<u4")]
+        frames, rgb, states, st = w.scene.render_light_groups(width, height, spp, ds.SEED, ds.group_table(w), True, True, group_count=G, rr=lg.RR,
+                                                              counters=counters, out=out)
+        for got, w_, label in zip((frames, rgb, states), want, ("group frames", "out_rgb", "final states")):
+            lg.assert_plane(got, w_, None, lg.GUARD_F, "%s counters=%s: %s" % (variant, counters, label))
+        assert st["paths"] == (width * height * spp if counters else 0)
+
+
+@pytest.mark.parametrize("variant", ["default", "tables_in_hbm", "general", "some_exact"])
+def test_sample_map(w, knobs, variant):
+    """pt_sample_map: the mixed map at cap 4 against the oracle's chains, the guards where a pixel has no samples"""
+    import sample_map_cases as sm
+    width, height = ds.RENDER[:2]
+    smap, want = ds.sample_map_expected(w)
+    knobs(VARIANTS.get(variant, {}))
+    for counters in (False, True):
+        out = w.scene.render_sample_map(width, height, smap, ds.MAP_CAP, ds.SEED, True, True, rr=sm.RR, counters=counters, out=sm.guards())
+        sm.assert_planes(out[:3], want, "%s counters=%s" % (variant, counters))
+        assert out[3]["paths"] == (int(sm.counts(smap, ds.MAP_CAP).sum()) if counters else 0)

@@ -155,3 +155,153 @@ def test_calls_of_every_kind_in_sequence(api, oracle, gpu_scene, name):
     assert_same_hits(d_hits.cpu().numpy().view(api.HIT_DTYPE), *wd["hits"], name + " 10: closest hits")
     rc.assert_same(d_rgb.cpu().numpy().reshape(40, 3), d_fin.cpu().numpy().view("<u4"), wd["rad"][0], wd["rad"][1], name + " 10: radiance query")
     assert_bits_equal(d_last.cpu().numpy().reshape(H, W, 3), want[0], name + " 10: render again")
+
+
+# ---- the light-group and sample-map calls among the others ---------------------------------------------------------------------------
+# device_render stages the group frames through the ray queries' ray buffer (query_stage[0]) and the sample map through their
+# output buffer (query_stage[1], read-only, never staged out), and keeps the group table on the host side of the scene: a call
+# that leaves something of its own there, or finds something of another's, shows in the next step
+GUARD_F, GUARD_M2, GUARD_STATE = np.float32(-7.0), np.float32(-1.0), 0xDDDDDDDD
+GROUP_SPP, MAP_CAP = 4, 16
+
+
+def masked(got, want, guard, what, rect=RECT):
+    """got (..., H, W[, 3]) equals want bit for bit inside the rect and holds guard outside it"""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.shape == want.shape, "%s: shape %s vs %s" % (what, got.shape, want.shape)
+    m = np.zeros((H, W), bool)
+    m[rect[1]:rect[3], rect[0]:rect[2]] = True
+    m = m if got.shape[-1] != 3 else m[..., None]
+    ne = (got.view("<u4") != want.view("<u4")) & m
+    assert not ne.any(), "%s: %d words inside the rect differ; first at %r" % (what, int(ne.sum()), tuple(np.argwhere(ne)[0]))
+    g = np.array(guard, got.dtype).reshape(1).view("<u4")[0]
+    out = (got.view("<u4") != g) & ~m
+    assert not out.any(), "%s: %d words outside the rect were written; first at %r" % (what, int(out.sum()), tuple(np.argwhere(out)[0]))
+
+
+def group_world(api, oracle, scene, name, wd):
+    """the oracle's part of the light-group and sample-map steps, once per scene: its PIXEL renders of the dark twins (rect, 4
+    spp, the scene's own camera and seed), the maps and the planes the chains give for them, the feature planes"""
+    import feature_cases as fc
+    import light_groups_cases as lg
+    import sample_map_cases as sm
+    if "groups" in wd:
+        return wd["groups"]
+    g = {}
+    flat = scene.flatten(W, H)
+    g["lights"] = [int(m) for m in np.nonzero(flat.materials["is_light"])[0]]
+    twins = {}
+
+    def frame(keep):
+        """the rect of the PIXEL render of the twin that keeps the lights of `keep`, +0 elsewhere; keep None: the scene itself"""
+        key = None if keep is None else frozenset(keep)
+        if key not in twins:
+            osc = lg.dark_twin(oracle, flat, key)
+            osc.set_camera(wd["cams"][0])
+            twins[key] = osc.render(W, H, GROUP_SPP, SEED, "pixel", rect=RECT, rr=RR, threads=8)[0]
+        return twins[key]
+
+    def frames(groups, G):
+        return np.stack([frame([m for m, k in groups.items() if k == i]) for i in range(G)])
+    g["frame"], g["frames"] = frame, frames
+    g["table"] = lambda groups: np.array([groups.get(m, lg.NO_GROUP if m in g["lights"] else 0x5A) for m in range(len(flat.materials))], np.uint8)
+    states = np.zeros((H, W), "<u4")
+    for (x, y), (_, st) in wd["chain"][0].items():
+        states[y, x] = st[GROUP_SPP - 1]
+    g["states"] = states
+    g["maps"] = np.stack([sm.mixed_map(s, (W, H), rect=RECT, zero_row=5) for s in (0, 3, 6)])
+    assert all((sm.counts(m, MAP_CAP)[RECT[1]:RECT[3], RECT[0]:RECT[2]] == k).any() for m in g["maps"] for k in (0, 1, MAP_CAP))
+    g["map_planes"] = [sm.expected_from(wd["chain"][v], g["maps"][v], MAP_CAP, RECT, (W, H)) for v in range(3)]
+    osc = oracle.OracleScene(flat)
+    g["features"] = fc.expected(fc.frame(oracle, osc, flat, wd["cams"][0], W, H, SEED, 2, RECT), 2, fc.GUARDS)
+    wd["groups"] = g
+    return g
+
+
+def map_guards(V=None):
+    lead = () if V is None else (V,)
+    return [np.full(lead + (H, W, 3), GUARD_F, "<f4"), np.full(lead + (H, W), GUARD_M2, "<f4"), np.full(lead + (H, W), GUARD_STATE, "<u4")]
+
+
+@pytest.mark.parametrize("name", ["glass_room", "c3_bunny_room"])
+def test_light_groups_and_sample_maps_in_sequence(api, oracle, gpu_scene, name):
+    import torch
+    import feature_cases as fc
+    import sample_map_cases as sm
+    scene = gpu_scene(name)
+    wd = world(api, oracle, scene, name)
+    g = group_world(api, oracle, scene, name, wd)
+    cams, lights = wd["cams"], g["lights"]
+    inside = inside_rect()
+
+    def raycast(what):
+        hits, _ = scene.raycast(wd["hit_rays"])
+        assert_same_hits(hits, *wd["hits"], what)
+
+    def light_groups(groups, G, what):
+        out = [np.full((G, H, W, 3), GUARD_F, "<f4"), np.full((H, W, 3), GUARD_F, "<f4"), np.full((H, W), GUARD_STATE, "<u4")]
+        frames, rgb, states, _ = scene.render_light_groups(W, H, GROUP_SPP, SEED, g["table"](groups), True, True, group_count=G, rect=RECT, rr=RR, out=out)
+        masked(frames, g["frames"](groups, G), GUARD_F, what + ": group frames")
+        masked(rgb, g["frame"](None), GUARD_F, what + ": out_rgb")
+        masked(states, g["states"], GUARD_STATE, what + ": final states")
+        return frames
+
+    # 1. a host raycast of 65 rays: it fills the ray queries' two staging buffers
+    raycast(name + " 1: closest hits")
+    # 2. light groups, G = 1, host form, guard-filled planes: the group frames are staged where the rays were
+    light_groups({m: 0 for m in lights}, 1, name + " 2: light groups, G = 1")
+    # 3. G = 8 with empty groups: eight frames grow that buffer
+    eight = {m: (6, 2)[i % 2] for i, m in enumerate(lights)}
+    frames = light_groups(eight, 8, name + " 3: light groups, G = 8")
+    assert not frames[[0, 1, 3, 4, 5, 7]][:, inside].view("<u4").any() and frames[6][inside].any()
+    # 4. a sample map in host form: the map is staged where the hits were
+    maps = g["maps"].copy()
+    got = scene.render_sample_map(W, H, maps[0], MAP_CAP, SEED, True, True, rect=RECT, rr=RR, out=map_guards())
+    assert (maps == g["maps"]).all(), name + " 4: the host map was written"
+    sm.assert_planes(got[:3], g["map_planes"][0], name + " 4: sample map")
+    # 5. the raycast again
+    raycast(name + " 5: closest hits again")
+    # 6. a three-view sample-map batch, a map per view
+    got = scene.render_views_sample_map(cams, SEEDS, W, H, maps, MAP_CAP, True, True, rect=RECT, rr=RR, out=map_guards(3))
+    assert (maps == g["maps"]).all(), name + " 6: the host maps were written"
+    for v in range(3):
+        sm.assert_planes(tuple(p[v] for p in got[:3]), g["map_planes"][v], "%s 6: sample-map batch, view %d" % (name, v))
+    # 7. a features render
+    planes, _ = scene.render_features(W, H, 2, SEED, rect=RECT, want=fc.PLANES, out=fc.guard_planes((H, W)))
+    fc.assert_same(planes, g["features"], name + " 7: features")
+    # 8. the plain CHUNK render
+    plain_chunk(scene, wd, name + " 8: plain chunk render")
+    # 9. four device forms with stats == NULL back to back on one stream, no wait between them, each settling the one before:
+    # light groups with table A, with table B (the lights' groups permuted: the table is the call's own), a sample map, a render
+    G = len(lights) + 1
+    table_a = {m: i for i, m in enumerate(lights)}
+    table_b = {m: (i + 1) % G for i, m in enumerate(lights)}
+    dev = torch.device("cuda", 0)
+    n = H * W
+    full = lambda k, fill, dt: torch.full((k,), fill, dtype=dt, device=dev)
+    a, b = ([full(3 * n * G, float(GUARD_F), torch.float32), full(3 * n, float(GUARD_F), torch.float32), full(n, GUARD_STATE - (1 << 32), torch.int32)] for _ in range(2))
+    m = [full(3 * n, float(GUARD_F), torch.float32), full(n, float(GUARD_M2), torch.float32), full(n, GUARD_STATE - (1 << 32), torch.int32)]
+    d_map = torch.from_numpy(np.ascontiguousarray(maps[1]).view("<i4").reshape(-1)).to(dev)
+    d_img = full(3 * n, float(FILL), torch.float32)
+    p = scene.params(W, H, GROUP_SPP, SEED, "pixel", 0, RECT, RR)
+    stream = torch.cuda.Stream(dev)
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        assert scene.render_light_groups_device(p, g["table"](table_a), *[x.data_ptr() for x in a], group_count=G, stream=stream.cuda_stream) is None
+        assert scene.render_light_groups_device(p, g["table"](table_b), *[x.data_ptr() for x in b], group_count=G, stream=stream.cuda_stream) is None
+        assert scene.render_sample_map_device(scene.params(W, H, MAP_CAP, SEED, "pixel", 0, RECT, RR), d_map.data_ptr(), *[x.data_ptr() for x in m],
+                                              stream=stream.cuda_stream) is None
+        assert scene.render_device(d_img.data_ptr(), scene.params(W, H, 3, SEED, "pixel", rr=RR), stream=stream.cuda_stream) is None
+    stream.synchronize()
+    for t, table, label in ((a, table_a, "table A"), (b, table_b, "table B")):
+        h = [x.cpu().numpy() for x in t]
+        masked(h[0].reshape(G, H, W, 3), g["frames"](table, G), GUARD_F, "%s 9: light groups with %s: group frames" % (name, label))
+        masked(h[1].reshape(H, W, 3), g["frame"](None), GUARD_F, "%s 9: light groups with %s: out_rgb" % (name, label))
+        masked(h[2].view("<u4").reshape(H, W), g["states"], GUARD_STATE, "%s 9: light groups with %s: final states" % (name, label))
+    assert (d_map.cpu().numpy().view("<u4").reshape(H, W) == g["maps"][1]).all(), name + " 9: the map tensor was written"
+    h = [x.cpu().numpy() for x in m]
+    sm.assert_planes((h[0].reshape(H, W, 3), h[1].reshape(H, W), h[2].view("<u4").reshape(H, W)),
+                     sm.expected_from(wd["chain"][0], g["maps"][1], MAP_CAP, RECT, (W, H)), name + " 9: sample map, device form")
+    assert_bits_equal(d_img.cpu().numpy().reshape(H, W, 3), wd["ref"]("pixel", 3, 0)[0][0], name + " 9: plain render, device form")
+    # 10. the adaptive frame
+    adaptive_frame(scene, wd, name + " 10: adaptive frame")

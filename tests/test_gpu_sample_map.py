@@ -203,3 +203,41 @@ def test_device_form_of_a_batch(api, case):
     assert st is None
     for v in range(3):
         sm.assert_planes(tuple(x[v] for x in got), sm.expected(c, maps[v], seed=seeds[v], cam=cams[v], rect=sm.RECT), "device form, view %d" % v)
+
+
+# ---- 9. every kernel of the family; job batches; the exact walk ----------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["room_diffuse", "c2_analytic", lg.TABLE_SCENE])
+def test_every_kernel_of_the_family(case, monkeypatch, name):
+    """pt_sample_map<counters, diffuse, tabs>: the diffuse room takes the diffuse flavour, ORT_KERNEL=general its all-lobes one (the
+    analytic scene's own); ORT_LDS_TABLES=0 reads the tables from HBM, as the table scene always does -- with it, ORT_KERNEL=general
+    launches the all-lobes flavour with tabs = false, with and without counters, which nothing else does.  One answer; with
+    counters, paths = the sum of min(map, cap) over the rect"""
+    c = case(name)
+    m = sm.mixed_map()
+    want = sm.expected(c, m, rect=sm.RECT)
+    asked = int(sm.counts(m)[sm.inside(sm.RECT)].sum())
+    for env in ({}, {"ORT_LDS_TABLES": "0"}, {"ORT_KERNEL": "general"}, {"ORT_KERNEL": "general", "ORT_LDS_TABLES": "0"}):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        for counters in (False, True):
+            got, st = run(c, m, rect=sm.RECT, counters=counters)
+            sm.assert_planes(got, want, "%s %s counters=%s" % (name, env, counters))
+            assert st["paths"] == (asked if counters else 0)
+        for k in env:
+            monkeypatch.delenv(k)
+
+
+def test_independent_of_batches_and_walk(case, monkeypatch):
+    c = case("room_all_lobes")
+    m = sm.mixed_map()
+    want = sm.expected(c, m, rect=sm.RECT)
+    for batch in ("0", "7", "128"):
+        monkeypatch.setenv("ORT_JOB_BATCH", batch)
+        got, _ = run(c, m, rect=sm.RECT)
+        sm.assert_planes(got, want, "ORT_JOB_BATCH=" + batch)
+    monkeypatch.delenv("ORT_JOB_BATCH")
+    monkeypatch.setenv("ORT_DEBUG_FORCE_FALLBACK", "0")
+    got, st = run(c, m, rect=sm.RECT, counters=True)
+    monkeypatch.delenv("ORT_DEBUG_FORCE_FALLBACK")
+    sm.assert_planes(got, want, "every ray re-cast exactly")
+    assert st["fallback_rays"] == st["rays"] > 0

@@ -11,9 +11,11 @@ import pytest
 import ao_cases
 import adaptive_cases
 import feature_cases
+import light_groups_cases as lg
 import occluded_cases
 import radiance_cases
 import render_adaptive_cases as rac
+import sample_map_cases as sm
 import tree_shapes as ts
 from conftest import assert_bits_equal
 from test_gpu_raycast import assert_same_hits
@@ -164,7 +166,9 @@ def test_ray_queries(handle, knobs, name, variant, tables):
 @pytest.mark.parametrize("tables", ["lds", "hbm"])
 @pairs
 def test_camera_queries(handle, knobs, name, variant, tables):
-    """ort_render_features, ort_render_views and ort_render_adaptive on the small frames, with the tables in LDS and in HBM"""
+    """ort_render_features, ort_render_views, ort_render_adaptive, ort_render_light_groups (one group per light material, against
+    the dark twins of the world's flattened scene) and ort_render_sample_map (the mixed map) on the small frames, with the tables
+    in LDS and in HBM"""
     w, scene = handle(name, variant)
     knobs({} if tables == "lds" else {"ORT_LDS_TABLES": "0"})
     what = "%s %s tables in %s" % (name, variant, tables)
@@ -184,3 +188,13 @@ def test_camera_queries(handle, knobs, name, variant, tables):
                                                want_states=True)
     rac.assert_same((rgb, n, m2, fin), ts.render_adaptive_expected(w), what + " adaptive render")
     same_as_first(name, variant, "render adaptive", rgb, n, m2, fin)
+    groups, G = ts.light_groups_of(w)
+    out = [np.full((G, height, width, 3), lg.GUARD_F, "<f4"), np.full((height, width, 3), lg.GUARD_F, "<f4"), np.full((height, width), lg.GUARD_STATE, "<u4")]
+    frames, rgb, states, _ = scene.render_light_groups(width, height, spp, ts.SEED, ts.group_table(w), True, True, group_count=G, rr=lg.RR, out=out)
+    for got, want, label in zip((frames, rgb, states), ts.light_groups_expected(w), ("group frames", "out_rgb", "final states")):
+        lg.assert_plane(got, want, None, lg.GUARD_F, "%s light groups: %s" % (what, label))
+    same_as_first(name, variant, "light groups", frames, rgb, states)
+    smap, want = ts.sample_map_expected(w)
+    got = scene.render_sample_map(width, height, smap, ts.MAP_CAP, ts.SEED, True, True, rr=sm.RR, out=sm.guards())[:3]
+    sm.assert_planes(got, want, what + " sample map")
+    same_as_first(name, variant, "sample map", *got)

@@ -24,8 +24,10 @@ import deep_scenes
 import feature_cases
 import host_sim_tool as hs
 import irradiance_cases
+import light_groups_cases as lg
 import occluded_cases
 import radiance_cases
+import sample_map_cases as sm
 import table_scenes
 import tree_shapes as ts
 from conftest import DATA, assert_bits_equal
@@ -246,3 +248,23 @@ def test_views(world, tmp_path, name, variant, policy):
     for v, (cam, seed) in enumerate(zip(cams, ts.VIEW_SEEDS)):
         ref, _ = ts.oracle_render(w, width, height, spp, policy, chunk, cam=cam, seed=seed)
         assert_bits_equal(frames[v], ref, "%s %s %s view %d" % (name, variant, policy, v))
+
+
+@pytest.mark.parametrize("env", [{}, TABS], ids=ids)
+@pairs
+def test_light_groups_and_sample_map(world, tmp_path, name, variant, env):
+    """the lanes of pt_groups and pt_sample_map at VIEWS' frame: one group per light material against the dark twins of the
+    world's flattened scene, and the mixed map at cap 4 against the oracle's chains"""
+    w = world(name)
+    width, height, spp, _ = ts.VIEWS
+    assert (lg.W, lg.H) == (width, height)
+    ref = lg.SceneRef(w.scn, w.base)
+    _, G = ts.light_groups_of(w)
+    frames, rgb, states = lg.host_light_groups(hs.built("host_sim"), tmp_path, ref, ts.group_table(w), G, spp, seed=ts.SEED, env=_env(variant, env), threads=8)
+    want = ts.light_groups_expected(w)
+    assert (want[0] != 0).any()
+    for got, w_, label in zip((frames[0], rgb[0], states[0]), want, ("group frames", "out_rgb", "final states")):
+        lg.assert_plane(got, w_, None, lg.GUARD_F, "%s %s %r light groups: %s" % (name, variant, env, label))
+    smap, want = ts.sample_map_expected(w)
+    got, _ = sm.host_sample_map(hs.built("host_sim"), tmp_path, ref, smap, ts.MAP_CAP, seed=ts.SEED, env=_env(variant, env), threads=8)
+    sm.assert_planes(tuple(p[0] for p in got), want, "%s %s %r sample map" % (name, variant, env))

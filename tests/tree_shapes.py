@@ -13,9 +13,11 @@ import ao_cases
 import feature_cases
 import host_sim_tool as hs
 import irradiance_cases
+import light_groups_cases as lg
 import radiance_cases
 import raycast_cases
 import render_adaptive_cases as rac
+import sample_map_cases as sm
 import views_cases
 from adaptive_cases import Adaptive
 from conftest import DATA, GOLDEN, ROOT
@@ -358,9 +360,57 @@ def view_cams(w):
     return cached(w, "view cams", make)
 
 
-def render_adaptive_expected(w):
+def pixel_chains(w):
+    """render_adaptive_cases.chains of the whole VIEWS frame from the scene's own camera, four samples a pixel"""
     def make():
         width, height = VIEWS[:2]
         w.osc.set_camera(w.scene.camera(width, height))
-        return rac.expected_from(rac.chains(w.osc, width, height, SEED, rac.RR, spp=RENDER_AD.max_spp), width, height, RENDER_AD)
-    return cached(w, "render adaptive", make)
+        return rac.chains(w.osc, width, height, SEED, rac.RR, spp=RENDER_AD.max_spp)
+    return cached(w, "pixel chains", make)
+
+
+def render_adaptive_expected(w):
+    return cached(w, "render adaptive", lambda: rac.expected_from(pixel_chains(w), VIEWS[0], VIEWS[1], RENDER_AD))
+
+
+MAP_CAP = 4   # the chains' length
+
+
+def light_groups_of(w):
+    """-> ({light material: group}, G): one group per light material, in material order; past eight they share the last"""
+    lights = [int(m) for m in np.nonzero(w.flat.materials["is_light"])[0]]
+    groups = {m: min(g, lg.MAX_GROUPS - 1) for g, m in enumerate(lights)}
+    return groups, max(groups.values()) + 1
+
+
+def group_table(w, filler=0x5A):
+    t = np.full(len(w.flat.materials), filler, np.uint8)
+    for m, g in light_groups_of(w)[0].items():
+        t[m] = g
+    return t
+
+
+def light_groups_expected(w):
+    """-> (frames (G, h, w, 3), rgb (h, w, 3), states (h, w)) at VIEWS' frame and spp: frame g is the oracle's PIXEL render of the
+    dark twin that keeps group g (light_groups_cases.dark_twin of w.flat), rgb its render of the scene, the states its chains'"""
+    def make():
+        width, height, spp, _ = VIEWS
+        groups, G = light_groups_of(w)
+        cam = w.scene.camera(width, height)
+        frames = []
+        for g in range(G):
+            twin = lg.dark_twin(w.oracle, w.flat, [m for m, k in groups.items() if k == g])
+            twin.set_camera(cam)
+            frames.append(twin.render(width, height, spp, SEED, "pixel", rr=lg.RR, threads=8)[0])
+        rgb, _ = oracle_render(w, width, height, spp, "pixel", 0)
+        states = np.zeros((height, width), "<u4")
+        for (x, y), (_, st) in pixel_chains(w).items():
+            states[y, x] = st[spp - 1]
+        return np.stack(frames), rgb, states
+    return cached(w, "light groups", make)
+
+
+def sample_map_expected(w):
+    """sample_map_cases.mixed_map() at cap 4 -> (the map, (rgb, m2, states)) from the oracle's chains"""
+    assert (sm.W, sm.H) == VIEWS[:2]
+    return cached(w, "sample map", lambda: (sm.mixed_map(), sm.expected_from(pixel_chains(w), sm.mixed_map(), MAP_CAP)))
