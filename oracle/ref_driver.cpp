@@ -21,8 +21,9 @@
  * Commands (all binary I/O is little-endian, formats documented in
  * tests/golden/README.md and mirrored by tests/ref_io.py):
  *   scene-dump <scn> <base_dir> <W> <H> <out.bin>
- *   render <scn> <base_dir> <W> <H> <spp> <seed> <policy> <out.f32> [chunk] [x0 y0 x1 y1]
- *          policy = tile32 | whole | pixel | chunk | sample
+ *   render <scn> <base_dir> <W> <H> <spp> <seed> <policy> <out.f32> [chunk] [x0 y0 x1 y1] [states.u32]
+ *          policy = tile32 | whole | pixel | chunk | sample; states.u32 (pixel only): every pixel's final series state
+ *   chain <scn> <base_dir> <W> <H> <n> <seed> <x0> <y0> <x1> <y1> <colours.f32> <states.u32>
  *   unit <in.bin> <out.bin>        per-function input/output tables
  *   rng <seed> <n> <out.bin>
  *   raycast <scn> <base_dir> <rays.bin> <out.bin>
@@ -385,6 +386,7 @@ now_sec(void)
  *            (sum over k of call results, in k order) / (spp/chunk).
  *   sample : chunk with chunk = 1.
  * Optional rect restricts which pixels are rendered (others are left 0).
+ * pixel can also write a W x H plane of u32: the state of each pixel's series after its call (0 outside the rect).
  */
 static int
 cmd_render(int argc, char **argv)
@@ -398,11 +400,15 @@ cmd_render(int argc, char **argv)
     u32 chunk = (argc > 10) ? (u32)strtoul(argv[10], 0, 10) : 1;
     i32 x0 = 0, y0 = 0, x1 = W, y1 = H;
     if (argc > 14) { x0 = atoi(argv[11]); y0 = atoi(argv[12]); x1 = atoi(argv[13]); y1 = atoi(argv[14]); }
+    const char *states_path = (argc > 15) ? argv[15] : 0;
+    if (states_path && strcmp(policy, "pixel")) { fprintf(stderr, "a states plane is written for policy pixel only\n"); return 2; }
+    if (x0 < 0 || y0 < 0 || x1 > W || y1 > H) { fprintf(stderr, "rect outside the image\n"); return 2; }
     assemble_scene(argv[2], argv[3], W, H);
     RefScene *s = g_scene;
     const f32 rr = 0.8f; /* macos_main.mm:656 */
 
     v3 *out = (v3 *)calloc((size_t)W * H, sizeof(v3));
+    u32 *states = (u32 *)calloc((size_t)W * H, sizeof(u32));
     u64 tested = 0;
     u32 final_state = 0;
     double t0 = now_sec();
@@ -436,6 +442,7 @@ cmd_render(int argc, char **argv)
                 RandomSeries series = start_random_series(job_seed(seed, (u32)(y * W + x)));
                 tested += tiled_raytrace_bvh(&s->world, &s->camera, s->root, out, W, H, x, y, x + 1, y + 1, &series, spp, rr);
                 final_state = series.next_random;
+                states[y * W + x] = final_state;
             }
     } else if (!strcmp(policy, "chunk") || !strcmp(policy, "sample")) {
         if (!strcmp(policy, "sample")) chunk = 1;
@@ -465,10 +472,51 @@ cmd_render(int argc, char **argv)
     FILE *f = fopen(out_path, "wb");
     fwrite(out, sizeof(v3), (size_t)W * H, f);
     fclose(f);
+    if (states_path) {
+        f = fopen(states_path, "wb");
+        fwrite(states, sizeof(u32), (size_t)W * H, f);
+        fclose(f);
+    }
     double paths = (double)(x1 - x0) * (double)(y1 - y0) * (double)spp;
     printf("{\"width\": %d, \"height\": %d, \"spp\": %u, \"seed\": %u, \"policy\": \"%s\", \"chunk\": %u, "
            "\"shapes_tested\": %llu, \"final_rng\": %u, \"seconds\": %.6f, \"paths\": %.0f, \"mpaths_per_s\": %.6f}\n",
            W, H, spp, seed, policy, chunk, (unsigned long long)tested, final_state, dt, paths, paths / dt * 1e-6);
+    return 0;
+}
+
+/*
+ * chain: for every pixel of the rect, in row-major order, n successive calls of tiled_raytrace_bvh over that one pixel at
+ * spp = 1 on ONE series started at job_seed(seed, y*W + x): each call continues where the one before left the series.
+ * colours.f32 = per pixel n x {r g b}, the pixel as each call left it; states.u32 = per pixel n x the state after each call.
+ */
+static int
+cmd_chain(int argc, char **argv)
+{
+    if (argc < 14) return 1;
+    i32 W = atoi(argv[4]), H = atoi(argv[5]);
+    u32 n = (u32)strtoul(argv[6], 0, 10);
+    u32 seed = (u32)strtoul(argv[7], 0, 10);
+    i32 x0 = atoi(argv[8]), y0 = atoi(argv[9]), x1 = atoi(argv[10]), y1 = atoi(argv[11]);
+    if (x0 < 0 || y0 < 0 || x1 > W || y1 > H) { fprintf(stderr, "rect outside the image\n"); return 2; }
+    assemble_scene(argv[2], argv[3], W, H);
+    RefScene *s = g_scene;
+    const f32 rr = 0.8f; /* macos_main.mm:656 */
+    v3 *out = (v3 *)calloc((size_t)W * H, sizeof(v3));
+    FILE *fc = fopen(argv[12], "wb"), *fs = fopen(argv[13], "wb");
+    u64 tested = 0;
+    for (i32 y = y0; y < y1; ++y)
+        for (i32 x = x0; x < x1; ++x) {
+            RandomSeries series = start_random_series(job_seed(seed, (u32)(y * W + x)));
+            for (u32 k = 0; k < n; ++k) {
+                tested += tiled_raytrace_bvh(&s->world, &s->camera, s->root, out, W, H, x, y, x + 1, y + 1, &series, 1, rr);
+                put_v3(fc, out[y * W + x]);
+                put_u32(fs, series.next_random);
+            }
+        }
+    fclose(fc);
+    fclose(fs);
+    printf("{\"width\": %d, \"height\": %d, \"samples\": %u, \"seed\": %u, \"shapes_tested\": %llu}\n", W, H, n, seed,
+           (unsigned long long)tested);
     return 0;
 }
 
@@ -605,11 +653,12 @@ int
 main(int argc, char **argv)
 {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s scene-dump|render|unit|rng|raycast ...\n", argv[0]);
+        fprintf(stderr, "usage: %s scene-dump|render|chain|unit|rng|raycast ...\n", argv[0]);
         return 1;
     }
     if (!strcmp(argv[1], "scene-dump")) return cmd_scene_dump(argc, argv);
     if (!strcmp(argv[1], "render")) return cmd_render(argc, argv);
+    if (!strcmp(argv[1], "chain")) return cmd_chain(argc, argv);
     if (!strcmp(argv[1], "unit")) return cmd_unit(argc, argv);
     if (!strcmp(argv[1], "rng")) return cmd_rng(argc, argv);
     if (!strcmp(argv[1], "raycast")) return cmd_raycast(argc, argv);

@@ -48,14 +48,8 @@ def world(api, oracle, tmp_path_factory):
     w.scene = api.Scene.from_arrays(**args).commit()
     w.flat = w.scene.flatten(GPU_RENDER[0], GPU_RENDER[1])
     w.osc = oracle.OracleScene(w.flat, with_reference_csg=True)
-    rng = np.random.default_rng(5)
-    slope = rng.uniform(-1, 1, (N_RAYS, 2)) * [1 / 3, 1 / 4]     # the 4:3 frame of the scene's camera
-    w.rays = np.zeros((N_RAYS, 6), "<f4")
-    w.rays[:, 1:3] = rng.uniform(-2, 2, (N_RAYS, 2))
-    w.rays[:, 3], w.rays[:, 4:6] = 1, slope
-    w.rays[:, 3:6] /= np.linalg.norm(w.rays[:, 3:6].astype(np.float64), axis=1, keepdims=True)   # the queries take unit directions
+    w.rays, w.graze, rng = ray_sets(w.layout)
     w.t, w.n, w.mat = w.osc.raycast(w.rays[:, 0:3], w.rays[:, 3:6])
-    w.graze = grazing_rays(w.layout, rng, N_RAYS)
     w.graze_hits = w.osc.raycast(w.graze[:, 0:3], w.graze[:, 3:6])
     # pinholes for the radiance queries: in front of the inner stack, looking down the same cone
     p = np.concatenate([rng.uniform(1, 8, (N_RADIANCE, 1)), rng.uniform(0.5, 3, (N_RADIANCE, 2)) * rng.choice([-1, 1], (N_RADIANCE, 2))], axis=1)
@@ -74,7 +68,27 @@ def world(api, oracle, tmp_path_factory):
     w.oracle = oracle
     # the same scene under a camera that looks at the silhouette of the third cylinder (the one nearly along x) near its end,
     # where most rays that reach it draw a verdict other than CH_ADMIT: its frame's rays are re-traversed by resolve_hit
-    b, a, r = [np.asarray(v, np.float64) for v in w.layout["cylinders"][2]]
+    w.graze_scn = write_graze_scene(w.scn, w.layout, w.dir)
+    w.graze_scene = api.Scene.load_scn(w.graze_scn)   # for its camera, as the loader reads it
+    w.cache = {}
+    _world["w"] = w
+    return w
+
+
+def ray_sets(layout):
+    """-> (the cone rays, the grazing rays, the generator as they leave it): what world() casts, from the layout alone"""
+    rng = np.random.default_rng(5)
+    slope = rng.uniform(-1, 1, (N_RAYS, 2)) * [1 / 3, 1 / 4]     # the 4:3 frame of the scene's camera
+    rays = np.zeros((N_RAYS, 6), "<f4")
+    rays[:, 1:3] = rng.uniform(-2, 2, (N_RAYS, 2))
+    rays[:, 3], rays[:, 4:6] = 1, slope
+    rays[:, 3:6] /= np.linalg.norm(rays[:, 3:6].astype(np.float64), axis=1, keepdims=True)   # the queries take unit directions
+    return rays, grazing_rays(layout, rng, N_RAYS), rng
+
+
+def write_graze_scene(scn, layout, directory):
+    """the .scn next to scn with the grazing camera in place of the scene's own -> its path (the PLY files are shared)"""
+    b, a, r = [np.asarray(v, np.float64) for v in layout["cylinders"][2]]
     c = b + 0.1 * a
     side = np.cross(a, c)
     d = c + 0.9 * float(r) * side / np.linalg.norm(side)
@@ -82,16 +96,13 @@ def world(api, oracle, tmp_path_factory):
     x = np.cross([0.0, 0.0, 1.0], z)
     x /= np.linalg.norm(x)
     qw, qx, qy, qz = make_tablescene._quat_wxyz(np.stack([x, np.cross(z, x), z], axis=1))
-    text = open(w.scn).read().splitlines()
+    text = open(scn).read().splitlines()
     cam = [i for i, l in enumerate(text) if l.startswith("camera ")]
     assert len(cam) == 1
     text[cam[0]] = "camera 0. 0. 0. b %g q %.9f %.9f %.9f %.9f" % (GRAZE_B, qw, qx, qy, qz)
-    w.graze_scn = os.path.join(w.dir, "deepscene_graze.scn")
-    open(w.graze_scn, "w").write("\n".join(text) + "\n")
-    w.graze_scene = api.Scene.load_scn(w.graze_scn)   # for its camera, as the loader reads it
-    w.cache = {}
-    _world["w"] = w
-    return w
+    path = os.path.join(directory, "deepscene_graze.scn")
+    open(path, "w").write("\n".join(text) + "\n")
+    return path
 
 
 def grazing_rays(layout, rng, n):

@@ -9,7 +9,7 @@ What is committed is data only: inputs and the reference's outputs.
   ref_det   = reference + deterministic libm (oracle/det_math.h)  -> bit-exact anchor
   ref_glibc = reference + glibc libm, "as shipped" on this box     -> distance report
 
-usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges | --only-tables | --only-cluster]
+usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges | --only-tables | --only-cluster | --only-generated]
 """
 import json
 import os
@@ -285,6 +285,115 @@ def golden_clusterscene(manifest):
     manifest["clusterscene"] = dg
 
 
+def _npz(name, arrays):
+    """np.savez_compressed with the members in sorted order and a fixed date: the same arrays give the same bytes"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(os.path.join(HERE, name), "w", zipfile.ZIP_DEFLATED) as z:
+        for k in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[k]), allow_pickle=False)
+            z.writestr(zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(), zipfile.ZIP_DEFLATED)
+
+
+def _scene_entry(scn, base, w, h, d):
+    """the reference loader's counts, array digests and octree statistics of a scene file, and the file's SHA-256"""
+    import hashlib
+    dump = os.path.join(d, "scene.dump")
+    info = run(REF_DET, "scene-dump", scn, base, w, h, dump)
+    dg = ref_io.scene_digest(ref_io.read_scene_dump(dump))
+    dg["octree"] = info
+    dg["scn_sha256"] = hashlib.sha256(open(scn, "rb").read()).hexdigest()
+    return dg
+
+
+def _ref_pixel(scn, base, w, h, spp, seed, d, policy="pixel", chunk=0, states=True):
+    """-> (frame, states plane or None, {shapes_tested, final_rng}) of the reference's render"""
+    out, sp = os.path.join(d, "r.f32"), os.path.join(d, "r.u32")
+    args = [REF_DET, "render", scn, base, w, h, spp, seed, policy, out, max(chunk, 1)]
+    if states:
+        assert policy == "pixel"
+        args += [0, 0, w, h, sp]
+    js = run(*args)
+    return (np.fromfile(out, "<f4").reshape(h, w, 3), np.fromfile(sp, "<u4").reshape(h, w) if states else None,
+            dict(shapes_tested=js["shapes_tested"], final_rng=js["final_rng"]))
+
+
+def golden_generated(manifest):
+    """the generated scenes that the suite otherwise holds against the oracle alone (tests/reference_goldens.py): the deep scene
+    (tools/make_deepscene.py), the light-pick rooms, the rooms of the light-group and feature renders with their dark and white
+    twins written as files, and the per-pixel chains of one-sample calls.  The scene files are regenerated by the tests."""
+    import hashlib
+    import deep_scenes
+    import light_groups_cases as lg
+    import reference_goldens as rg
+    import render_adaptive_cases as rac
+    import test_gpu_light_pick as pick
+    G = manifest["generated"] = {}
+    d = tempfile.mkdtemp(prefix="generated_", dir=TMP) + "/"
+
+    # the deep scene
+    scn, graze_scn, layout = rg.deep_files(d)
+    w, h = deep_scenes.GPU_RENDER[:2]
+    deep = G["deepscene"] = _scene_entry(scn, d, w, h, d)
+    deep["graze"] = _scene_entry(graze_scn, d, w, h, d)
+    deep["ply_sha256"] = {k: hashlib.sha256(open(os.path.join(d, k + ".ply"), "rb").read()).hexdigest() for k in ("inner", "outer")}
+    deep["renders"] = {}
+    arrays = {}
+    for cam, policy, w, h, spp, chunk, key in rg.deep_renders():
+        arrays[key], _, deep["renders"][key] = _ref_pixel(scn if cam == "cone" else graze_scn, d, w, h, spp, deep_scenes.SEED, d, policy, chunk, states=False)
+    _npz("renders_deepscene.npz", arrays)
+    rays, graze, _ = deep_scenes.ray_sets(layout)
+    arrays = {}
+    deep["rays_sha256"] = {}
+    for name, rr in (("cone", rays), ("graze", graze)):
+        np.ascontiguousarray(rr, "<f4").tofile(os.path.join(d, "rays.bin"))
+        run(REF_DET, "raycast", scn, d, os.path.join(d, "rays.bin"), os.path.join(d, "hits.bin"))
+        hits = np.fromfile(os.path.join(d, "hits.bin"), dtype=np.dtype([("t", "<f4"), ("n", "<f4", 3), ("mat", "<u4")]))
+        arrays.update({name + "__t": hits["t"], name + "__n": hits["n"], name + "__mat": hits["mat"]})
+        deep["rays_sha256"][name] = hashlib.sha256(np.ascontiguousarray(rr, "<f4").tobytes()).hexdigest()
+    _npz("raycast_deepscene.npz", arrays)
+
+    # the light-pick rooms
+    G["light_pick"] = {}
+    arrays = {}
+    for flavour, lights, key, text in rg.pick_rooms():
+        scn = rg.write_text(d, "pick_" + key, text)
+        e = G["light_pick"][key] = _scene_entry(scn, d, pick.W, pick.H, d)
+        arrays[key + "__pixel"], arrays[key + "__states"], e["render"] = _ref_pixel(scn, d, pick.W, pick.H, pick.SPP, pick.SEED, d)
+    _npz("renders_light_pick.npz", arrays)
+
+    # the rooms, their dark twins and their white twin, as files
+    G["rooms"] = {}
+    arrays = {}
+    for name in lg.ROOMS:
+        G["rooms"][name] = {}
+        for variant, text in rg.room_variants(name):
+            scn = rg.write_text(d, "%s_%s" % (name, variant), text)
+            e = G["rooms"][name][variant] = _scene_entry(scn, d, lg.W, lg.H, d)
+            e["renders"] = {}
+            for spp in lg.SPPS:
+                key = "%s__%s__%dspp" % (name, variant, spp)
+                img, states, e["renders"][key] = _ref_pixel(scn, d, lg.W, lg.H, spp, lg.SEED, d)
+                arrays[key] = img
+                if not variant.startswith("dark"):
+                    arrays[key + "__states"] = states
+    _npz("renders_rooms.npz", arrays)
+
+    # the chains of one-sample calls
+    G["chains"] = {}
+    arrays = {}
+    for name in rg.CHAIN_SCENES:
+        scn, base = rg.chain_scene(d, name)
+        cols, states = os.path.join(d, "chain.f32"), os.path.join(d, "chain.u32")
+        js = run(REF_DET, "chain", scn, base, rac.W, rac.H, rg.CHAIN_SAMPLES, rac.SEED, 0, 0, rac.W, rac.H, cols, states)
+        arrays[name + "__colours"] = np.fromfile(cols, "<f4").reshape(rac.H, rac.W, rg.CHAIN_SAMPLES, 3)
+        arrays[name + "__states"] = np.fromfile(states, "<u4").reshape(rac.H, rac.W, rg.CHAIN_SAMPLES)
+        G["chains"][name] = dict(scn_sha256=hashlib.sha256(open(scn, "rb").read()).hexdigest(), samples=rg.CHAIN_SAMPLES, seed=rac.SEED,
+                                 width=rac.W, height=rac.H, shapes_tested=js["shapes_tested"])
+    _npz("chains_rooms.npz", arrays)
+
+
 def golden_showcase():
     """a crop of an image the reference itself wrote (showcase/1.hdr): header, file size, 32x64 RGBE pixels"""
     raw = open("/root/reference/showcase/1.hdr", "rb").read()
@@ -345,6 +454,11 @@ def main():
     if "--only-cluster" in sys.argv:  # add / refresh the cluster scene's fixtures without touching the others
         manifest = json.load(open(os.path.join(HERE, "manifest.json")))
         golden_clusterscene(manifest)
+        json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
+        return
+    if "--only-generated" in sys.argv:  # add / refresh the generated scenes' fixtures without touching the others
+        manifest = json.load(open(os.path.join(HERE, "manifest.json")))
+        golden_generated(manifest)
         json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
         return
     if "--only-c5" in sys.argv:  # add / refresh the C5 fixtures without touching the others
@@ -464,6 +578,7 @@ def main():
     golden_c5(manifest)
     golden_tablescenes(manifest)
     golden_clusterscene(manifest)
+    golden_generated(manifest)
     golden_showcase()
     golden_unit_edges()
     golden_raycast_edges()

@@ -293,3 +293,193 @@ def test_oracle_on_the_scenes_at_and_past_the_table_caps(api, oracle, manifest, 
     assert_bits_equal(t, r["t"], "t")
     assert_bits_equal(n, r["n"], "normal")
     assert (mat == r["mat"]).all() and (r["mat"] >= 7).sum() >= 40  # the fixture sees the grid's materials, not the walls alone
+
+
+# ---- the generated scenes that the other tests hold against the oracle alone (make_golden.py --only-generated) ---------------------
+DIGEST_KEYS = ("counts", "camera_bits", "ambient_bits", "materials_sha256", "spheres_sha256", "boxes_sha256", "cylinders_sha256", "lights", "meshes", "sha256")
+
+
+def _loaded(api, scn, meta, w, h):
+    """the file has the manifest's hash and the product's loader gives the reference loader's arrays -> (scene, flat)"""
+    import reference_goldens as rg
+    assert rg.sha256(scn) == meta["scn_sha256"], scn
+    scene = api.Scene.load_scn(scn).commit()
+    flat = scene.flatten(w, h)
+    dg = ref_io.scene_digest(flat)
+    for k in DIGEST_KEYS:
+        assert dg[k] == meta[k], (scn, k)
+    return scene, flat
+
+
+def _same_tree(osc, meta):
+    st = osc.tree_stats()
+    assert (st["nodes"], st["nonempty_leaves"], st["record_bytes"]) == (meta["octree"]["octree_nodes"], meta["octree"]["octree_leaves"], meta["octree"]["record_bytes"])
+
+
+def _pixel_planes_match(oracle, osc, w, h, spp, seed, frame, states, meta, what):
+    """the oracle's PIXEL render, its counters and (states given) every pixel's final series state against the reference's"""
+    import reference_goldens as rg
+    if states is None:
+        img, st = osc.render(w, h, spp, seed, "pixel", threads=1)
+    else:
+        img, st, got = rg.oracle_pixel_planes(oracle, osc, w, h, spp, seed)
+        rg.assert_words_equal(got, states, what + ": final states")
+    assert_bits_equal(img, frame, what)
+    assert (st["shapes_tested"], st["final_rng"]) == (meta["shapes_tested"], meta["final_rng"]), what
+
+
+@pytest.fixture(scope="module")
+def deep(api, manifest, tmp_path_factory):
+    """the deep scene's files, regenerated: (scn, graze_scn, layout, the manifest's entry, {which: the committed scene of the file})"""
+    import deep_scenes
+    import reference_goldens as rg
+    d = tmp_path_factory.mktemp("golden_deepscene")
+    scn, graze_scn, layout = rg.deep_files(d)
+    meta = manifest["generated"]["deepscene"]
+    for k in ("inner", "outer"):
+        assert rg.sha256(os.path.join(str(d), k + ".ply")) == meta["ply_sha256"][k]
+    w, h = deep_scenes.GPU_RENDER[:2]
+    scenes = {"cone": _loaded(api, scn, meta, w, h)[0], "graze": _loaded(api, graze_scn, meta["graze"], w, h)[0]}
+    return scn, graze_scn, layout, meta, scenes
+
+
+def test_deep_scene_is_the_references(api, oracle, deep):
+    """coordinates out to 1.2e18: the loader's arrays, the arrays the deep-stack tests build without a file (make_deepscene.arrays,
+    what deep_scenes.world commits) and the oracle's octree are the reference's"""
+    import deep_scenes
+    from deep_scenes import make_deepscene
+    scn, graze_scn, layout, meta, scenes = deep
+    w, h = deep_scenes.GPU_RENDER[:2]
+    args, _ = make_deepscene.arrays()
+    flat = api.Scene.from_arrays(**args).commit().flatten(w, h)
+    dg = ref_io.scene_digest(flat)
+    for k in DIGEST_KEYS:
+        assert dg[k] == meta[k], k
+    _same_tree(oracle.OracleScene(flat, with_reference_csg=True), meta)
+    assert meta["octree"] == dict(meta["graze"]["octree"])   # the grazing scene differs by its camera alone
+    assert meta["camera_bits"] != meta["graze"]["camera_bits"]
+
+
+def test_deep_scene_renders_match_reference(oracle, deep):
+    """the reference's own frames of the deep scene in four seeding policies, and of the grazing camera's scene: image bits,
+    shapes-tested counter, final RNG state"""
+    import deep_scenes
+    import reference_goldens as rg
+    _, _, _, meta, scenes = deep
+    z = rg.load("renders_deepscene.npz")
+    assert sorted(z.files) == sorted(k for *_, k in rg.deep_renders()) == sorted(meta["renders"])
+    for cam, policy, w, h, spp, chunk, key in rg.deep_renders():
+        osc = oracle.OracleScene(scenes[cam].flatten(w, h), with_reference_csg=True)
+        img, st = osc.render(w, h, spp, deep_scenes.SEED, policy, chunk=max(chunk, 1), threads=1)
+        assert_bits_equal(img, z[key], key)
+        assert st["shapes_tested"] == meta["renders"][key]["shapes_tested"], key
+        if policy != "tile32":
+            assert st["final_rng"] == meta["renders"][key]["final_rng"], key
+        assert (z[key] != 0).any()
+
+
+def test_deep_scene_raycasts_match_reference(oracle, deep):
+    """the 4 000 cone rays and the 4 000 grazing rays of deep_scenes.world: the rays regenerate bit for bit, and the oracle's t,
+    normal and material are the reference's"""
+    import deep_scenes
+    import reference_goldens as rg
+    _, _, layout, meta, scenes = deep
+    z = rg.load("raycast_deepscene.npz")
+    rays, graze, _ = deep_scenes.ray_sets(layout)
+    osc = oracle.OracleScene(scenes["cone"].flatten(64, 64), with_reference_csg=True)
+    import hashlib
+    for name, rr in (("cone", rays), ("graze", graze)):
+        assert hashlib.sha256(np.ascontiguousarray(rr, "<f4").tobytes()).hexdigest() == meta["rays_sha256"][name], name
+        t, n, mat = osc.raycast(rr[:, 0:3], rr[:, 3:6])
+        assert_bits_equal(t, z[name + "__t"], name + " t")
+        assert_bits_equal(n, z[name + "__n"], name + " normals")
+        assert (mat == z[name + "__mat"]).all(), name
+        assert (z[name + "__mat"] != 0).all()   # the room is closed
+
+
+def test_light_pick_rooms_match_reference(api, oracle, manifest, tmp_path_factory):
+    """the rooms of 1, 1, 2 and 3 lights of tests/test_gpu_light_pick.py in both flavours: the oracle's PIXEL image and every
+    pixel's final RandomSeries state -- what that test holds the device against -- are the reference's"""
+    import reference_goldens as rg
+    import test_gpu_light_pick as pick
+    d = tmp_path_factory.mktemp("golden_light_pick")
+    z = rg.load("renders_light_pick.npz")
+    rooms = rg.pick_rooms()
+    assert len(rooms) == 8 and len(z.files) == 16
+    for flavour, lights, key, text in rooms:
+        meta = manifest["generated"]["light_pick"][key]
+        scene, flat = _loaded(api, rg.write_text(d, "pick_" + key, text), meta, pick.W, pick.H)
+        assert flat.lights["type"].tolist() == pick.LIGHTS[lights][1]
+        osc = oracle.OracleScene(flat)
+        _same_tree(osc, meta)
+        _pixel_planes_match(oracle, osc, pick.W, pick.H, pick.SPP, pick.SEED, z[key + "__pixel"], z[key + "__states"], meta["render"], key)
+
+
+@pytest.mark.parametrize("name", ["room_all_lobes", "room_diffuse"])
+def test_rooms_and_their_twins_match_reference(api, oracle, manifest, tmp_path_factory, name):
+    """the rooms of the light-group and feature renders, their three dark twins and their white twin.  Both ways: the oracle on
+    the twin written as a file (every other `light` line 0 0 0; every `brdf` and `light` line `light 1 1 1`) and the oracle on
+    the patched material arrays that light_groups_cases.dark_twin and feature_cases.twin(white=True) build give the reference's
+    frames of the files, so the construction the other tests use is the reference's"""
+    import feature_cases as fc
+    import light_groups_cases as lg
+    import reference_goldens as rg
+    d = tmp_path_factory.mktemp("golden_" + name)
+    z = rg.load("renders_rooms.npz")
+    metas = manifest["generated"]["rooms"][name]
+    flats = {}
+    for variant, text in rg.room_variants(name):
+        meta = metas[variant]
+        _, flats[variant] = _loaded(api, rg.write_text(d, "%s_%s" % (name, variant), text), meta, lg.W, lg.H)
+        osc = oracle.OracleScene(flats[variant])
+        _same_tree(osc, meta)
+        for spp in lg.SPPS:
+            key = "%s__%s__%dspp" % (name, variant, spp)
+            states = None if variant.startswith("dark") else z[key + "__states"]
+            _pixel_planes_match(oracle, osc, lg.W, lg.H, spp, lg.SEED, z[key], states, meta["renders"][key], key + ", the file")
+    own = flats["own"]
+    lights = [int(m) for m in np.nonzero(own.materials["is_light"])[0]]
+    assert len(lights) == 3
+    for g, m in enumerate(lights):
+        emit = flats["dark%d" % g].materials["emit"].view("<u4")
+        assert (flats["dark%d" % g].materials["is_light"] == own.materials["is_light"]).all()
+        assert emit[m].any() and not emit[[k for k in lights if k != m]].any()   # all-zero bits: +0, the value dark_twin writes
+        twin = lg.dark_twin(oracle, own, frozenset([m]))
+        for spp in lg.SPPS:
+            key = "%s__dark%d__%dspp" % (name, g, spp)
+            img, _ = twin.render(lg.W, lg.H, spp, lg.SEED, "pixel", rr=lg.RR, threads=1)
+            assert_bits_equal(img, z[key], key + ", the patched arrays")
+            assert (z[key] != 0).any() and (z[key].view("<u4") != z["%s__own__%dspp" % (name, spp)].view("<u4")).any()
+    white = fc.twin(oracle, own, white=True)
+    for spp in lg.SPPS:
+        key = "%s__white__%dspp" % (name, spp)
+        img, states = fc.twin_planes(white, own.camera, lg.W, lg.H, lg.SEED, spp)
+        assert_bits_equal(img, z[key], key + ", the patched arrays")
+        rg.assert_words_equal(states, z[key + "__states"], key + ", the patched arrays: final states")
+
+
+@pytest.mark.parametrize("name", ["room_all_lobes", "glass_room"])
+def test_pixel_chains_match_reference(api, oracle, manifest, tmp_path_factory, name):
+    """render_adaptive_cases.chains -- one sample per call, the series threaded through, what the adaptive and sample-map
+    expectations are cut from -- against the reference called the same way (ref_driver's chain): every call's colour and the
+    state after it, 64 calls a pixel"""
+    import reference_goldens as rg
+    import render_adaptive_cases as rac
+    scn, _ = rg.chain_scene(tmp_path_factory.mktemp("golden_chain_" + name), name)
+    meta = manifest["generated"]["chains"][name]
+    assert rg.sha256(scn) == meta["scn_sha256"]
+    assert (meta["samples"], meta["seed"], meta["width"], meta["height"]) == (rg.CHAIN_SAMPLES, rac.SEED, rac.W, rac.H) and rg.CHAIN_SAMPLES == rac.MAX_SPP
+    want = rg.chains_from(rg.load("chains_rooms.npz"), name)
+    scene = api.Scene.load_scn(scn).commit()
+    osc = oracle.OracleScene(scene.flatten(rac.W, rac.H))
+    got = rac.chains(osc, rac.W, rac.H, rac.SEED, rac.RR)
+    assert sorted(got) == sorted(want)
+    tested, img = 0, np.zeros((rac.H, rac.W, 3), "<f4")
+    for (x, y), (_, states) in got.items():   # the same calls once more, for the counter the chains do not keep
+        for s in [oracle.job_seed(rac.SEED, y * rac.W + x)] + states[:-1].tolist():
+            tested += osc.tiled_raytrace(img, x, y, x + 1, y + 1, int(s), 1, rac.RR)[0]
+    assert tested == meta["shapes_tested"]
+    cols = np.stack([got[k][0] for k in sorted(got)])
+    assert_bits_equal(cols, np.stack([want[k][0] for k in sorted(got)]), name + " colours")
+    rg.assert_words_equal(np.stack([got[k][1] for k in sorted(got)]), np.stack([want[k][1] for k in sorted(got)]), name + " states")
+    assert (cols != 0).any(axis=(1, 2)).mean() > 0.5   # most pixels see light within 64 samples
