@@ -338,6 +338,28 @@ def _views(cameras, seeds):
     return views
 
 
+def _lead(views):
+    """the leading axes of a render's planes: none for one frame (views None), (V,) for a batch"""
+    return () if views is None else (len(views),)
+
+
+def _is_plane(a, shape, dtype):
+    return isinstance(a, np.ndarray) and a.shape == shape and a.dtype == np.dtype(dtype) and a.flags.c_contiguous
+
+
+def _host_planes(specs, out, what):
+    """The host planes of a render, as a list: zeros by specs [(shape, dtype), ...], or the caller's out checked against them.
+    what: the planes' names, for the message about their number"""
+    if out is None:
+        return [np.zeros(sh, dt) for sh, dt in specs]
+    if len(out) != len(specs):
+        raise ValueError("out must hold %d planes (%s), got %d" % (len(specs), what, len(out)))
+    for a, (sh, dt) in zip(out, specs):
+        if not _is_plane(a, sh, dt):
+            raise ValueError("out: every plane must be a C-contiguous array, expected shape %s dtype %s" % (sh, dt))
+    return list(out)
+
+
 class Scene:
     """Owning wrapper of an ort_scene handle."""
 
@@ -507,19 +529,27 @@ class Scene:
         _check(lib().ort_render_views_device(self.handle, C.byref(params), views.ctypes.data, len(views), _ptr(d_out_ptr), _ptr(stream), st))
         return stats()
 
+    # -- the camera renders that cut one-pixel jobs: four kinds, each one frame or a batch of views, host or device form ----
+    def _pixel_jobs(self, kind, views, device, params, head, tail, stream=None, want_stats=True):
+        """One of a kind's four entry points: ort_render_[views_]<kind>[_device](scene, params, *head[, views, count], *tail[,
+        stream], stats).  views: None for the single-frame form, or the ort_view array (_views).  -> the stats dict, or None"""
+        name = "ort_render_%s%s%s" % ("" if views is None else "views_", kind, "_device" if device else "")
+        args = list(head) + ([] if views is None else [views.ctypes.data, len(views)]) + list(tail) + ([_ptr(stream)] if device else [])
+        st, stats = _stats(want_stats)
+        _check(getattr(lib(), name)(self.handle, C.byref(params), *args, st))
+        return stats()
+
     # -- the adaptive camera render: one frame, or a batch of views ----------------------------
-    @staticmethod
-    def _planes(shape, out, want_states):
-        """the four host planes of an adaptive render: zeros, or the caller's (out: (rgb, spp, m2[, states]), checked)"""
+    def _adaptive_host(self, views, width, height, ad, seed, rect, rr, want_states, counters, out):
+        shape = _lead(views) + (height, width)
         specs = [(shape + (3,), "<f4"), (shape, "<u4"), (shape, "<f4")] + ([(shape, "<u4")] if want_states else [])
-        if out is None:
-            return [np.zeros(sh, dt) for sh, dt in specs]
-        if len(out) != len(specs):
-            raise ValueError("out must hold %d planes (rgb, spp, m2%s), got %d" % (len(specs), ", states" if want_states else "", len(out)))
-        for a, (sh, dt) in zip(out, specs):
-            if not isinstance(a, np.ndarray) or a.shape != sh or a.dtype != np.dtype(dt) or not a.flags.c_contiguous:
-                raise ValueError("out: every plane must be a C-contiguous array, expected shape %s dtype %s" % (sh, dt))
-        return list(out)
+        planes = _host_planes(specs, out, "rgb, spp, m2" + (", states" if want_states else ""))
+        p = self.params(width, height, 1, seed, "pixel", 0, rect, rr, counters)
+        tail = [a.ctypes.data for a in planes] + ([] if want_states else [None])
+        return tuple(planes) + (self._pixel_jobs("adaptive", views, False, p, [C.byref(ad)], tail),)
+
+    def _adaptive_device(self, views, params, ad, d_planes, stream, want_stats):
+        return self._pixel_jobs("adaptive", views, True, params, [C.byref(ad)], [_ptr(d) for d in d_planes], stream, want_stats)
 
     def render_adaptive(self, width, height, min_spp, max_spp, tolerance, floor=0.05, check_every=4, seed=0, rect=None, rr=0.8,
                         want_states=False, counters=False, out=None):
@@ -529,12 +559,7 @@ class Scene:
         (H, W, 3) float32, spp (H, W) uint32 samples taken, m2 (H, W) float32 sum of squared sample luminance, stats dict),
         with want_states (rgb, spp, m2, states (H, W) uint32, stats).  Pixels outside rect keep what out's planes held."""
         ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
-        planes = self._planes((height, width), out, want_states)
-        p = self.params(width, height, 1, seed, "pixel", 0, rect, rr, counters)
-        st, stats = _stats()
-        _check(lib().ort_render_adaptive(self.handle, C.byref(p), C.byref(ad), planes[0].ctypes.data, planes[1].ctypes.data,
-                                         planes[2].ctypes.data, planes[3].ctypes.data if want_states else None, st))
-        return tuple(planes) + (stats(),)
+        return self._adaptive_host(None, width, height, ad, seed, rect, rr, want_states, counters, out)
 
     def render_adaptive_device(self, params, min_spp, max_spp, tolerance, floor, check_every, d_out, d_spp=0, d_m2=0, d_states=0,
                                stream=None, want_stats=False):
@@ -542,10 +567,7 @@ class Scene:
         pointer is given, (H, W) uint32 / float32 / uint32).  params: Scene.params(..., policy="pixel"); its spp is ignored.
         Enqueued on stream; waits only when want_stats (returns the stats dict)."""
         ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
-        st, stats = _stats(want_stats)
-        _check(lib().ort_render_adaptive_device(self.handle, C.byref(params), C.byref(ad), _ptr(d_out), _ptr(d_spp), _ptr(d_m2),
-                                                _ptr(d_states), _ptr(stream), st))
-        return stats()
+        return self._adaptive_device(None, params, ad, (d_out, d_spp, d_m2, d_states), stream, want_stats)
 
     def render_views_adaptive(self, cameras, seeds, width, height, min_spp, max_spp, tolerance, floor=0.05, check_every=4, rect=None,
                               rr=0.8, want_states=False, counters=False, out=None):
@@ -554,13 +576,7 @@ class Scene:
         W), m2 (V, H, W)[, states (V, H, W)], stats dict)."""
         views = _views(cameras, seeds)
         ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
-        planes = self._planes((len(views), height, width), out, want_states)
-        p = self.params(width, height, 1, 0, "pixel", 0, rect, rr, counters)
-        st, stats = _stats()
-        _check(lib().ort_render_views_adaptive(self.handle, C.byref(p), C.byref(ad), views.ctypes.data, len(views), planes[0].ctypes.data,
-                                               planes[1].ctypes.data, planes[2].ctypes.data,
-                                               planes[3].ctypes.data if want_states else None, st))
-        return tuple(planes) + (stats(),)
+        return self._adaptive_host(views, width, height, ad, 0, rect, rr, want_states, counters, out)
 
     def render_views_adaptive_device(self, params, cameras, seeds, min_spp, max_spp, tolerance, floor, check_every, d_out, d_spp=0,
                                      d_m2=0, d_states=0, stream=None, want_stats=False):
@@ -568,10 +584,7 @@ class Scene:
         the stats dict).  params.seed and params.spp are ignored."""
         views = _views(cameras, seeds)
         ad = _adaptive(min_spp, max_spp, check_every, tolerance, floor)
-        st, stats = _stats(want_stats)
-        _check(lib().ort_render_views_adaptive_device(self.handle, C.byref(params), C.byref(ad), views.ctypes.data, len(views),
-                                                      _ptr(d_out), _ptr(d_spp), _ptr(d_m2), _ptr(d_states), _ptr(stream), st))
-        return stats()
+        return self._adaptive_device(views, params, ad, (d_out, d_spp, d_m2, d_states), stream, want_stats)
 
     # -- light-group renders: one frame per group of lights, in one pass --------------------------
     def light_materials(self):
@@ -599,19 +612,18 @@ class Scene:
             group_count = int(named.max()) + 1 if len(named) else 1
         return LightGroups(table.ctypes.data, n, group_count), table, int(group_count)
 
-    @staticmethod
-    def _group_planes(shape, G, want_rgb, want_states, out):
-        """the host planes of a light-group render: zeros, or the caller's (out: (groups[, rgb][, states]), checked)"""
-        lead, hw = shape[:-2], shape[-2:]
-        specs = [(lead + (G,) + hw + (3,), "<f4")] + ([(shape + (3,), "<f4")] if want_rgb else []) + ([(shape, "<u4")] if want_states else [])
-        if out is None:
-            return [np.zeros(sh, dt) for sh, dt in specs]
-        if len(out) != len(specs):
-            raise ValueError("out must hold %d planes (groups%s%s), got %d" % (len(specs), ", rgb" if want_rgb else "", ", states" if want_states else "", len(out)))
-        for a, (sh, dt) in zip(out, specs):
-            if not isinstance(a, np.ndarray) or a.shape != sh or a.dtype != np.dtype(dt) or not a.flags.c_contiguous:
-                raise ValueError("out: every plane must be a C-contiguous array, expected shape %s dtype %s" % (sh, dt))
-        return list(out)
+    def _light_groups_host(self, views, width, height, spp, seed, groups, want_rgb, want_states, group_count, rect, rr, counters, out):
+        lg, table, G = self._light_groups(groups, group_count)
+        lead, hw = _lead(views), (height, width)
+        specs = [(lead + (G,) + hw + (3,), "<f4")] + ([(lead + hw + (3,), "<f4")] if want_rgb else []) + ([(lead + hw, "<u4")] if want_states else [])
+        planes = _host_planes(specs, out, "groups" + (", rgb" if want_rgb else "") + (", states" if want_states else ""))
+        p = self.params(width, height, spp, seed, "pixel", 0, rect, rr, counters)
+        tail = [planes[0].ctypes.data, planes[1].ctypes.data if want_rgb else None, planes[-1].ctypes.data if want_states else None]
+        return tuple(planes) + (self._pixel_jobs("light_groups", views, False, p, [C.byref(lg)], tail),)
+
+    def _light_groups_device(self, views, params, groups, d_planes, group_count, stream, want_stats):
+        lg, table, _ = self._light_groups(groups, group_count)
+        return self._pixel_jobs("light_groups", views, True, params, [C.byref(lg)], [_ptr(d) for d in d_planes], stream, want_stats)
 
     def render_light_groups(self, width, height, spp, seed, groups, want_rgb=True, want_states=False, group_count=None, rect=None,
                             rr=0.8, counters=False, out=None):
@@ -621,24 +633,13 @@ class Scene:
         G or NO_LIGHT_GROUP; other materials' entries are not read), or a dict {material index: group}, e.g. {m: i for i, m
         in enumerate(scene.light_materials())}.  Returns (frames (G, H, W, 3) float32[, rgb (H, W, 3) float32 the unsplit
         frame][, states (H, W) uint32], stats dict).  Pixels outside rect keep what out's planes held."""
-        lg, table, G = self._light_groups(groups, group_count)
-        planes = self._group_planes((height, width), G, want_rgb, want_states, out)
-        p = self.params(width, height, spp, seed, "pixel", 0, rect, rr, counters)
-        st, stats = _stats()
-        _check(lib().ort_render_light_groups(self.handle, C.byref(p), C.byref(lg), planes[0].ctypes.data,
-                                             planes[1].ctypes.data if want_rgb else None,
-                                             planes[-1].ctypes.data if want_states else None, st))
-        return tuple(planes) + (stats(),)
+        return self._light_groups_host(None, width, height, spp, seed, groups, want_rgb, want_states, group_count, rect, rr, counters, out)
 
     def render_light_groups_device(self, params, groups, d_groups, d_rgb=0, d_states=0, group_count=None, stream=None, want_stats=False):
         """The same into device planes (raw device pointers, e.g. torch tensors' data_ptr(): (G, H, W, 3) float32 and, where a
         pointer is given, (H, W, 3) float32 / (H, W) uint32).  params: Scene.params(..., policy="pixel").  Enqueued on stream;
         waits only when want_stats (returns the stats dict)."""
-        lg, table, _ = self._light_groups(groups, group_count)
-        st, stats = _stats(want_stats)
-        _check(lib().ort_render_light_groups_device(self.handle, C.byref(params), C.byref(lg), _ptr(d_groups), _ptr(d_rgb), _ptr(d_states),
-                                                    _ptr(stream), st))
-        return stats()
+        return self._light_groups_device(None, params, groups, (d_groups, d_rgb, d_states), group_count, stream, want_stats)
 
     def render_views_light_groups(self, cameras, seeds, width, height, spp, groups, want_rgb=True, want_states=False, group_count=None,
                                   rect=None, rr=0.8, counters=False, out=None):
@@ -646,25 +647,14 @@ class Scene:
         render_light_groups gives with seed seeds[v] if the scene's camera were cameras[v].  Returns (frames (V, G, H, W, 3)[,
         rgb (V, H, W, 3)][, states (V, H, W)], stats dict)."""
         views = _views(cameras, seeds)
-        lg, table, G = self._light_groups(groups, group_count)
-        planes = self._group_planes((len(views), height, width), G, want_rgb, want_states, out)
-        p = self.params(width, height, spp, 0, "pixel", 0, rect, rr, counters)
-        st, stats = _stats()
-        _check(lib().ort_render_views_light_groups(self.handle, C.byref(p), C.byref(lg), views.ctypes.data, len(views), planes[0].ctypes.data,
-                                                   planes[1].ctypes.data if want_rgb else None,
-                                                   planes[-1].ctypes.data if want_states else None, st))
-        return tuple(planes) + (stats(),)
+        return self._light_groups_host(views, width, height, spp, 0, groups, want_rgb, want_states, group_count, rect, rr, counters, out)
 
     def render_views_light_groups_device(self, params, cameras, seeds, groups, d_groups, d_rgb=0, d_states=0, group_count=None,
                                          stream=None, want_stats=False):
         """The same into device planes, view-major: (V, G, H, W, 3), (V, H, W, 3), (V, H, W).  Enqueued on stream; waits only
         when want_stats (returns the stats dict).  params.seed is ignored."""
         views = _views(cameras, seeds)
-        lg, table, _ = self._light_groups(groups, group_count)
-        st, stats = _stats(want_stats)
-        _check(lib().ort_render_views_light_groups_device(self.handle, C.byref(params), C.byref(lg), views.ctypes.data, len(views),
-                                                          _ptr(d_groups), _ptr(d_rgb), _ptr(d_states), _ptr(stream), st))
-        return stats()
+        return self._light_groups_device(views, params, groups, (d_groups, d_rgb, d_states), group_count, stream, want_stats)
 
     # -- sample-map renders: the caller's sample count per pixel ----------------------------------
     @staticmethod
@@ -677,18 +667,17 @@ class Scene:
             m = (m.astype(np.int64) & 0xFFFFFFFF).astype("<u4")
         return np.ascontiguousarray(m)
 
-    @staticmethod
-    def _map_planes(shape, want_m2, want_states, out):
-        """the host planes of a sample-map render: zeros, or the caller's (out: (rgb[, m2][, states]), checked)"""
+    def _sample_map_host(self, views, width, height, sample_map, cap, seed, want_m2, want_states, rect, rr, counters, out):
+        shape = _lead(views) + (height, width)
+        smap = self._sample_map(sample_map, shape)
         specs = [(shape + (3,), "<f4")] + ([(shape, "<f4")] if want_m2 else []) + ([(shape, "<u4")] if want_states else [])
-        if out is None:
-            return [np.zeros(sh, dt) for sh, dt in specs]
-        if len(out) != len(specs):
-            raise ValueError("out must hold %d planes (rgb%s%s), got %d" % (len(specs), ", m2" if want_m2 else "", ", states" if want_states else "", len(out)))
-        for a, (sh, dt) in zip(out, specs):
-            if not isinstance(a, np.ndarray) or a.shape != sh or a.dtype != np.dtype(dt) or not a.flags.c_contiguous:
-                raise ValueError("out: every plane must be a C-contiguous array, expected shape %s dtype %s" % (sh, dt))
-        return list(out)
+        planes = _host_planes(specs, out, "rgb" + (", m2" if want_m2 else "") + (", states" if want_states else ""))
+        p = self.params(width, height, cap, seed, "pixel", 0, rect, rr, counters)
+        tail = [smap.ctypes.data, planes[0].ctypes.data, planes[1].ctypes.data if want_m2 else None, planes[-1].ctypes.data if want_states else None]
+        return tuple(planes) + (self._pixel_jobs("sample_map", views, False, p, [], tail),)
+
+    def _sample_map_device(self, views, params, d_planes, stream, want_stats):
+        return self._pixel_jobs("sample_map", views, True, params, [], [_ptr(d) for d in d_planes], stream, want_stats)
 
     def render_sample_map(self, width, height, sample_map, cap, seed, want_m2=True, want_states=False, rect=None, rr=0.8, counters=False,
                           out=None):
@@ -698,24 +687,14 @@ class Scene:
         bottom -- render_adaptive's spp plane can be passed as it stands.  Returns (rgb (H, W, 3) float32[, m2 (H, W) float32
         sum of squared sample luminance][, states (H, W) uint32], stats dict).  Passes taken with different seeds combine
         weighted by their counts: (n1 * rgb1 + n2 * rgb2) / (n1 + n2)."""
-        smap = self._sample_map(sample_map, (height, width))
-        planes = self._map_planes((height, width), want_m2, want_states, out)
-        p = self.params(width, height, cap, seed, "pixel", 0, rect, rr, counters)
-        st, stats = _stats()
-        _check(lib().ort_render_sample_map(self.handle, C.byref(p), smap.ctypes.data, planes[0].ctypes.data,
-                                           planes[1].ctypes.data if want_m2 else None,
-                                           planes[-1].ctypes.data if want_states else None, st))
-        return tuple(planes) + (stats(),)
+        return self._sample_map_host(None, width, height, sample_map, cap, seed, want_m2, want_states, rect, rr, counters, out)
 
     def render_sample_map_device(self, params, d_map, d_rgb, d_m2=0, d_states=0, stream=None, want_stats=False):
         """The same with the map and the planes on the device (raw device pointers, e.g. torch tensors' data_ptr(): the map
         (H, W) uint32 -- or int32 holding the same words --, (H, W, 3) float32 and, where a pointer is given, (H, W) float32 /
         uint32).  params: Scene.params(..., policy="pixel"), its spp the cap.  Enqueued on stream; waits only when
         want_stats (returns the stats dict)."""
-        st, stats = _stats(want_stats)
-        _check(lib().ort_render_sample_map_device(self.handle, C.byref(params), _ptr(d_map), _ptr(d_rgb), _ptr(d_m2), _ptr(d_states),
-                                                  _ptr(stream), st))
-        return stats()
+        return self._sample_map_device(None, params, (d_map, d_rgb, d_m2, d_states), stream, want_stats)
 
     def render_views_sample_map(self, cameras, seeds, width, height, sample_map, cap, want_m2=True, want_states=False, rect=None,
                                 rr=0.8, counters=False, out=None):
@@ -723,23 +702,13 @@ class Scene:
         per view): frame v is what render_sample_map gives with seed seeds[v] and sample_map[v] if the scene's camera were
         cameras[v].  Returns (rgb (V, H, W, 3)[, m2 (V, H, W)][, states (V, H, W)], stats dict)."""
         views = _views(cameras, seeds)
-        smap = self._sample_map(sample_map, (len(views), height, width))
-        planes = self._map_planes((len(views), height, width), want_m2, want_states, out)
-        p = self.params(width, height, cap, 0, "pixel", 0, rect, rr, counters)
-        st, stats = _stats()
-        _check(lib().ort_render_views_sample_map(self.handle, C.byref(p), views.ctypes.data, len(views), smap.ctypes.data,
-                                                 planes[0].ctypes.data, planes[1].ctypes.data if want_m2 else None,
-                                                 planes[-1].ctypes.data if want_states else None, st))
-        return tuple(planes) + (stats(),)
+        return self._sample_map_host(views, width, height, sample_map, cap, 0, want_m2, want_states, rect, rr, counters, out)
 
     def render_views_sample_map_device(self, params, cameras, seeds, d_map, d_rgb, d_m2=0, d_states=0, stream=None, want_stats=False):
         """The same with the maps and the planes on the device, V frames each, view-major.  Enqueued on stream; waits only
         when want_stats (returns the stats dict).  params.seed is ignored."""
         views = _views(cameras, seeds)
-        st, stats = _stats(want_stats)
-        _check(lib().ort_render_views_sample_map_device(self.handle, C.byref(params), views.ctypes.data, len(views), _ptr(d_map),
-                                                        _ptr(d_rgb), _ptr(d_m2), _ptr(d_states), _ptr(stream), st))
-        return stats()
+        return self._sample_map_device(views, params, (d_map, d_rgb, d_m2, d_states), stream, want_stats)
 
     # -- first-hit feature renders: albedo, normal, depth, coverage and id planes ---------------
     @staticmethod
@@ -755,9 +724,8 @@ class Scene:
         if set(out) != set(want):
             raise ValueError("out must hold exactly the planes of want %r, got %r" % (want, tuple(out)))
         for k in want:
-            a, (sh, dt) = out[k], specs[k]
-            if not isinstance(a, np.ndarray) or a.shape != sh or a.dtype != np.dtype(dt) or not a.flags.c_contiguous:
-                raise ValueError("out[%r] must be a C-contiguous array of shape %s dtype %s" % (k, sh, dt))
+            if not _is_plane(out[k], *specs[k]):
+                raise ValueError("out[%r] must be a C-contiguous array of shape %s dtype %s" % ((k,) + specs[k]))
         return dict(out)
 
     @staticmethod
@@ -772,6 +740,16 @@ class Scene:
             setattr(fp, "final_states" if k == "states" else k, v.value if isinstance(v, C.c_void_p) else v)
         return fp
 
+    def _features_host(self, views, width, height, spp, seed, rect, want, counters, out):
+        planes = self._feature_planes(_lead(views) + (height, width), want, out)
+        p = self.params(width, height, spp, seed, "pixel", 0, rect, 0.0, counters)
+        fp = self._feature_struct({k: a.ctypes.data for k, a in planes.items()})
+        return planes, self._pixel_jobs("features", views, False, p, [], [C.byref(fp)])
+
+    def _features_device(self, views, params, d_planes, stream, want_stats):
+        fp = self._feature_struct(d_planes)
+        return self._pixel_jobs("features", views, True, params, [], [C.byref(fp)], stream, want_stats)
+
     def render_features(self, width, height, spp, seed, rect=None, want=("albedo", "normal", "depth", "hits", "ids"), counters=False,
                         out=None):
         """What the camera's own samples see first, per pixel: the means over spp camera samples (the PIXEL render's aperture
@@ -780,42 +758,26 @@ class Scene:
         (mat, prim) and, with "states" in want, the stream's final state.  Returns (planes, stats dict), planes a dict by
         the names of want: albedo, normal (H, W, 3) float32, depth (H, W) float32, hits, states (H, W) uint32, ids (H, W, 2)
         uint32.  Pixels outside rect keep what out's planes held.  Which planes are asked for changes no bit of the others."""
-        planes = self._feature_planes((height, width), want, out)
-        p = self.params(width, height, spp, seed, "pixel", 0, rect, 0.0, counters)
-        fp = self._feature_struct({k: a.ctypes.data for k, a in planes.items()})
-        st, stats = _stats()
-        _check(lib().ort_render_features(self.handle, C.byref(p), C.byref(fp), st))
-        return planes, stats()
+        return self._features_host(None, width, height, spp, seed, rect, want, counters, out)
 
     def render_features_device(self, params, stream=None, want_stats=False, **d_planes):
         """The same into device planes: albedo=, normal=, depth=, hits=, ids=, states= raw device pointers (e.g. torch tensors'
         data_ptr()), those not given are not written.  params: Scene.params(..., policy="pixel"); its chunk and rr are ignored.
         Enqueued on stream; waits only when want_stats (returns the stats dict)."""
-        fp = self._feature_struct(d_planes)
-        st, stats = _stats(want_stats)
-        _check(lib().ort_render_features_device(self.handle, C.byref(params), C.byref(fp), _ptr(stream), st))
-        return stats()
+        return self._features_device(None, params, d_planes, stream, want_stats)
 
     def render_views_features(self, cameras, seeds, width, height, spp, rect=None, want=("albedo", "normal", "depth", "hits", "ids"),
                               counters=False, out=None):
         """render_features for a batch of views in one launch (cameras, seeds as render_views): frame v is what render_features
         gives with seed seeds[v] if the scene's camera were cameras[v].  Every plane has a leading axis of V frames."""
         views = _views(cameras, seeds)
-        planes = self._feature_planes((len(views), height, width), want, out)
-        p = self.params(width, height, spp, 0, "pixel", 0, rect, 0.0, counters)
-        fp = self._feature_struct({k: a.ctypes.data for k, a in planes.items()})
-        st, stats = _stats()
-        _check(lib().ort_render_views_features(self.handle, C.byref(p), views.ctypes.data, len(views), C.byref(fp), st))
-        return planes, stats()
+        return self._features_host(views, width, height, spp, 0, rect, want, counters, out)
 
     def render_views_features_device(self, params, cameras, seeds, stream=None, want_stats=False, **d_planes):
         """The same into device planes of V frames each, view-major.  Enqueued on stream; waits only when want_stats (returns
         the stats dict).  params.seed is ignored."""
         views = _views(cameras, seeds)
-        fp = self._feature_struct(d_planes)
-        st, stats = _stats(want_stats)
-        _check(lib().ort_render_views_features_device(self.handle, C.byref(params), views.ctypes.data, len(views), C.byref(fp), _ptr(stream), st))
-        return stats()
+        return self._features_device(views, params, d_planes, stream, want_stats)
 
     # -- closest-hit ray queries -----------------------------------------------------------
     def raycast(self, rays, counters=False):

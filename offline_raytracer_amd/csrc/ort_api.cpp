@@ -511,182 +511,173 @@ static int check_views_in_box(const ort_scene *s, const ort_view *views, uint32_
     return ORT_OK;
 }
 
-/* view_count == 0 is OK whatever else is passed; then argument errors, what the call does not do, and the scene's state */
+static int check_view_cap(uint32_t view_count) {
+    static_assert(sizeof(ort_view) == 52, "ort_view is a camera and a seed");
+    if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
+    return ORT_OK;
+}
+
+/* no call that takes views renders a shard of a frame or into a packed framebuffer; each says so in its own words */
+static int refuse_shards_and_packed(const ort_render_params &p, const char *sharded, const char *packed) {
+    if (p.shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, sharded);
+    if (p.flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, packed);
+    return ORT_OK;
+}
+
+/* view_count == 0 is OK whatever else is passed; then argument errors, what the call does not do, and the scene's state.  Always a
+   batch, so there is no own-view form here; unlike the pixel-job renders below it allows CHUNK */
 static int render_views_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool host, void *out,
                                void *stream, ort_stats *stats) {
     if (view_count == 0) return nothing_to_do(stats);
     if (!views || !out) return fail(ORT_ERR_INVALID, "null views or framebuffer");
-    static_assert(sizeof(ort_view) == 52, "ort_view is a camera and a seed");
-    if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
-    int rc = check_param_values(s, p);
-    if (rc != ORT_OK) return rc;
+    int rc = check_view_cap(view_count);
+    if (rc != ORT_OK || (rc = check_param_values(s, p)) != ORT_OK) return rc;
     if (p->policy != ORT_POLICY_PIXEL && p->policy != ORT_POLICY_CHUNK)
         return fail(ORT_ERR_UNSUPPORTED, "a batch of views needs a per-pixel seeding policy (PIXEL or CHUNK)");
-    if (p->shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, "a batch of views is not sharded: deal views to GPUs, not blocks");
-    if (p->flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "a batch of views has no packed framebuffer");
-    if ((rc = check_views_in_box(s, views, view_count)) != ORT_OK) return rc;
-    if ((rc = check_resident(s)) != ORT_OK) return rc;
+    rc = refuse_shards_and_packed(*p, "a batch of views is not sharded: deal views to GPUs, not blocks", "a batch of views has no packed framebuffer");
+    if (rc != ORT_OK || (rc = check_views_in_box(s, views, view_count)) != ORT_OK || (rc = check_resident(s)) != ORT_OK) return rc;
     ort::RenderCall c{host, stream, stats};
     c.views = views; c.view_count = view_count;
     return run_render(s, p, c, out);
 }
 
-/* The adaptive camera render, one frame or a batch of views.  view_count == 0 is OK whatever else is passed (the views form); then
-   render_views_common's order with the stopping rule's checks directly after the params': nulls and the view cap, the params with
-   ad->max_spp where spp stands (spp and chunk are not the caller's to set here), ad as ort_radiance_adaptive judges it, what the
-   call does not do (any policy but PIXEL, shards, a packed framebuffer, a camera outside the box), the scene's state.  !batch:
-   the single-frame form (views unread), the one-view batch of the scene's own camera and params->seed */
+/* The camera renders that cut one-pixel jobs -- adaptive, light groups, sample map, first-hit features -- each one frame or a batch
+   of views, host or device form.  A kind is the words of its three refusals and four steps of its own; the order of the checks,
+   which is every one of these calls' contract (include/ort.h), is this function:
+     1. view_count == 0 is OK whatever else is passed (the views form);
+     2. the kind's null arguments (nulls), the view cap, a null scene or params;
+     3. the params as the render call judges them, after the kind has overwritten what is not the caller's to set here (adjust;
+        chunk never is: one job per pixel);
+     4. the kind's own argument checks (checks);
+     5. what the call does not do: any policy but PIXEL, shards, packed planes, a camera outside the scene's box;
+     6. the scene's state; then the launch (launch), with the params as adjusted and a RenderCall that holds the form and the views.
+   !batch is the single-frame form: views is not read, and the call renders the one-view batch of the scene's own camera and
+   params->seed. */
+struct PixelJobKind {
+    const char *not_pixel, *sharded, *packed;
+};
+
+extern "C++" { /* a template, in the middle of the C entry points */
+template <typename Nulls, typename Adjust, typename Checks, typename Launch>
+static int render_pixel_jobs(const PixelJobKind &kind, ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool batch,
+                             bool host, void *stream, ort_stats *stats, Nulls nulls, Adjust adjust, Checks checks, Launch launch) {
+    if (batch && view_count == 0) return nothing_to_do(stats);
+    int rc = nulls();
+    if (rc != ORT_OK || (rc = check_view_cap(view_count)) != ORT_OK) return rc;
+    if (!s || !p) return fail(ORT_ERR_INVALID, "null scene or params");
+    ort_render_params q = *p;
+    adjust(&q);
+    q.chunk = q.spp;
+    if ((rc = check_param_values(s, &q)) != ORT_OK || (rc = checks(q)) != ORT_OK) return rc;
+    if (q.policy != ORT_POLICY_PIXEL) return fail(ORT_ERR_UNSUPPORTED, kind.not_pixel);
+    if ((rc = refuse_shards_and_packed(q, kind.sharded, kind.packed)) != ORT_OK) return rc;
+    ort_view own;
+    if (batch) {
+        if ((rc = check_views_in_box(s, views, view_count)) != ORT_OK) return rc;
+    } else {
+        ort::camera_basis(*s, q.width, q.height, &own.camera);
+        own.seed = q.seed;
+        views = &own;
+    }
+    if ((rc = check_resident(s)) != ORT_OK) return rc;
+    ort::RenderCall c{host, stream, stats};
+    c.views = views; c.view_count = view_count;
+    return launch(q, c);
+}
+} // extern "C++"
+
+/* the nulls of a kind whose first plane is required: the views or the plane (the views form), the plane by the form's name */
+static int check_first_plane(bool batch, bool host, const ort_view *views, const void *plane, const char *in_batch, const char *in_host, const char *in_device) {
+    if (!plane || (batch && !views)) return fail(ORT_ERR_INVALID, batch ? in_batch : host ? in_host : in_device);
+    return ORT_OK;
+}
+
+/* The adaptive camera render: spp is not the caller's to set either -- the params are judged with ad->max_spp where it stands --
+   and its own check is ad, as ort_radiance_adaptive judges it */
 static int render_adaptive_common(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, const ort_view *views, uint32_t view_count, bool batch,
                                   bool host, void *out_rgb, void *out_spp, void *out_m2, void *states, void *stream, ort_stats *stats) {
-    if (batch && view_count == 0) return nothing_to_do(stats);
-    if (batch && (!views || !out_rgb)) return fail(ORT_ERR_INVALID, "null views or framebuffer");
-    if (!batch && !out_rgb) return fail(ORT_ERR_INVALID, host ? "null framebuffer" : "null device framebuffer");
-    if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
-    if (!s || !p) return fail(ORT_ERR_INVALID, "null scene or params");
-    ort_render_params q = *p;
-    q.spp = ad && ad->max_spp ? ad->max_spp : 1u; /* a null ad or a max_spp of 0 is check_adaptive's to name */
-    q.chunk = q.spp;
-    int rc = check_param_values(s, &q);
-    if (rc != ORT_OK || (rc = check_adaptive(ad)) != ORT_OK) return rc;
-    if (q.policy != ORT_POLICY_PIXEL) return fail(ORT_ERR_UNSUPPORTED, "the adaptive render cuts one-pixel jobs: it needs the PIXEL policy");
-    if (q.shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, "the adaptive render is not sharded");
-    if (q.flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "the adaptive render has no packed framebuffer");
-    ort_view own;
-    if (batch) {
-        if ((rc = check_views_in_box(s, views, view_count)) != ORT_OK) return rc;
-    } else {
-        ort::camera_basis(*s, q.width, q.height, &own.camera);
-        own.seed = q.seed;
-        views = &own;
-    }
-    if ((rc = check_resident(s)) != ORT_OK) return rc;
-    ort::RenderCall c{host, stream, stats};
-    c.views = views; c.view_count = view_count; c.ad = ad;
-    return run_render(s, &q, c, out_rgb, out_spp, out_m2, states);
+    static const PixelJobKind kind = {"the adaptive render cuts one-pixel jobs: it needs the PIXEL policy", "the adaptive render is not sharded",
+                                      "the adaptive render has no packed framebuffer"};
+    return render_pixel_jobs(
+        kind, s, p, views, view_count, batch, host, stream, stats,
+        [&] { return check_first_plane(batch, host, views, out_rgb, "null views or framebuffer", "null framebuffer", "null device framebuffer"); },
+        [&](ort_render_params *q) { q->spp = ad && ad->max_spp ? ad->max_spp : 1u; }, /* a null ad or a max_spp of 0 is check_adaptive's to name */
+        [&](const ort_render_params &) { return check_adaptive(ad); },
+        [&](const ort_render_params &q, ort::RenderCall c) { c.ad = ad; return run_render(s, &q, c, out_rgb, out_spp, out_m2, states); });
 }
 
-/* Light-group renders, one frame or a batch of views: render_adaptive_common's order with the groups where ad stands.
-   view_count == 0 is OK whatever else is passed (the views form); then nulls (out_groups, views) and the view cap, the params as the
-   render call judges them (chunk is not the caller's to set here), spp above 1 << 24, the groups (null struct or table, another
-   material count than the scene's, a group count outside [1, ORT_MAX_LIGHT_GROUPS], a light's entry that names no group and is not
-   ORT_NO_LIGHT_GROUP; other materials' entries are not read) and the planes' alignment, what the call does not do (any policy but
-   PIXEL, shards, a packed framebuffer, a camera outside the box), the scene's state.  !batch: the single-frame form (views unread),
-   the one-view batch of the scene's own camera and params->seed */
+/* Light-group renders.  Own checks: spp above 1 << 24, the groups (a null struct or table, another material count than the scene's,
+   a group count outside [1, ORT_MAX_LIGHT_GROUPS], a light's entry that names no group and is not ORT_NO_LIGHT_GROUP; other
+   materials' entries are not read), the planes' alignment */
 static int render_groups_common(ort_scene *s, const ort_render_params *p, const ort_light_groups *groups, const ort_view *views, uint32_t view_count,
                                 bool batch, bool host, void *out_groups, void *out_rgb, void *states, void *stream, ort_stats *stats) {
-    if (batch && view_count == 0) return nothing_to_do(stats);
-    if (batch && (!views || !out_groups)) return fail(ORT_ERR_INVALID, "null views or group frames");
-    if (!batch && !out_groups) return fail(ORT_ERR_INVALID, host ? "null group frames" : "null device group frames");
-    if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
-    if (!s || !p) return fail(ORT_ERR_INVALID, "null scene or params");
-    ort_render_params q = *p;
-    q.chunk = q.spp;
-    int rc = check_param_values(s, &q);
-    if (rc != ORT_OK) return rc;
-    if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp must be <= 1 << 24: a sample count must be exact in float");
-    if (!groups) return fail(ORT_ERR_INVALID, "null groups (the light-group table)");
-    if (!groups->group_of_material) return fail(ORT_ERR_INVALID, "null group_of_material");
-    if (groups->material_count != s->materials.size()) return fail(ORT_ERR_INVALID, "groups->material_count is not the scene's material count");
-    if (groups->group_count == 0 || groups->group_count > ORT_MAX_LIGHT_GROUPS) return fail(ORT_ERR_INVALID, "group_count must be within [1, ORT_MAX_LIGHT_GROUPS]");
-    for (size_t m = 0; m < s->materials.size(); ++m)
-        if (s->materials[m].is_light && groups->group_of_material[m] >= groups->group_count && groups->group_of_material[m] != ORT_NO_LIGHT_GROUP)
-            return fail(ORT_ERR_INVALID, "light material " + std::to_string(m) + ": its group is neither below group_count nor ORT_NO_LIGHT_GROUP");
-    rc = check_ptrs({{out_groups, true, 4}, {out_rgb, false, 4}, {states, false, 4}}, "", "", "out_groups, out_rgb and final_states must be 4-byte aligned");
-    if (rc != ORT_OK) return rc;
-    if (q.policy != ORT_POLICY_PIXEL) return fail(ORT_ERR_UNSUPPORTED, "the light-group render splits one-pixel jobs: it needs the PIXEL policy");
-    if (q.shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, "the light-group render is not sharded");
-    if (q.flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "the light-group render has no packed framebuffer");
-    ort_view own;
-    if (batch) {
-        if ((rc = check_views_in_box(s, views, view_count)) != ORT_OK) return rc;
-    } else {
-        ort::camera_basis(*s, q.width, q.height, &own.camera);
-        own.seed = q.seed;
-        views = &own;
-    }
-    if ((rc = check_resident(s)) != ORT_OK) return rc;
-    ort::RenderCall c{host, stream, stats};
-    c.views = views; c.view_count = view_count; c.groups = groups; c.out_groups = out_groups;
-    return run_render(s, &q, c, out_rgb, nullptr, nullptr, states);
+    static const PixelJobKind kind = {"the light-group render splits one-pixel jobs: it needs the PIXEL policy", "the light-group render is not sharded",
+                                      "the light-group render has no packed framebuffer"};
+    return render_pixel_jobs(
+        kind, s, p, views, view_count, batch, host, stream, stats,
+        [&] { return check_first_plane(batch, host, views, out_groups, "null views or group frames", "null group frames", "null device group frames"); },
+        [](ort_render_params *) {},
+        [&](const ort_render_params &q) {
+            if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp must be <= 1 << 24: a sample count must be exact in float");
+            if (!groups) return fail(ORT_ERR_INVALID, "null groups (the light-group table)");
+            if (!groups->group_of_material) return fail(ORT_ERR_INVALID, "null group_of_material");
+            if (groups->material_count != s->materials.size()) return fail(ORT_ERR_INVALID, "groups->material_count is not the scene's material count");
+            if (groups->group_count == 0 || groups->group_count > ORT_MAX_LIGHT_GROUPS) return fail(ORT_ERR_INVALID, "group_count must be within [1, ORT_MAX_LIGHT_GROUPS]");
+            for (size_t m = 0; m < s->materials.size(); ++m)
+                if (s->materials[m].is_light && groups->group_of_material[m] >= groups->group_count && groups->group_of_material[m] != ORT_NO_LIGHT_GROUP)
+                    return fail(ORT_ERR_INVALID, "light material " + std::to_string(m) + ": its group is neither below group_count nor ORT_NO_LIGHT_GROUP");
+            return check_ptrs({{out_groups, true, 4}, {out_rgb, false, 4}, {states, false, 4}}, "", "", "out_groups, out_rgb and final_states must be 4-byte aligned");
+        },
+        [&](const ort_render_params &q, ort::RenderCall c) {
+            c.groups = groups; c.out_groups = out_groups;
+            return run_render(s, &q, c, out_rgb, nullptr, nullptr, states);
+        });
 }
 
-/* Sample-map renders, one frame or a batch of views: render_groups_common's order with the map where the groups stand.
-   view_count == 0 is OK whatever else is passed (the views form); then nulls (out_rgb, views) and the view cap, the params as the
-   render call judges them (chunk is not the caller's to set here), spp -- the cap -- above 1 << 24, the map (null) and the map's
-   and the planes' alignment, what the call does not do (any policy but PIXEL, shards, a packed framebuffer, a camera outside the
-   box), the scene's state.  The map's VALUES are never judged, in any form: the device forms cannot see them before the launch,
-   so the lanes cut every one at the cap.  !batch: the single-frame form (views unread), the one-view batch of the scene's own
-   camera and params->seed */
+/* Sample-map renders.  Own checks: spp -- the cap -- above 1 << 24, a null map, the map's and the planes' alignment.  The map's
+   VALUES are never judged, in any form: the device forms cannot see them before the launch, so the lanes cut every one at the cap */
 static int render_sample_map_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool batch, bool host,
                                     const void *sample_map, void *out_rgb, void *out_m2, void *states, void *stream, ort_stats *stats) {
-    if (batch && view_count == 0) return nothing_to_do(stats);
-    if (batch && (!views || !out_rgb)) return fail(ORT_ERR_INVALID, "null views or framebuffer");
-    if (!batch && !out_rgb) return fail(ORT_ERR_INVALID, host ? "null framebuffer" : "null device framebuffer");
-    if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
-    if (!s || !p) return fail(ORT_ERR_INVALID, "null scene or params");
-    ort_render_params q = *p;
-    q.chunk = q.spp;
-    int rc = check_param_values(s, &q);
-    if (rc != ORT_OK) return rc;
-    if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp (the cap on a pixel's samples) must be <= 1 << 24: a sample count must be exact in float");
-    if (!sample_map) return fail(ORT_ERR_INVALID, host ? "null sample_map" : "null device sample_map");
-    rc = check_ptrs({{sample_map, true, 4}, {out_rgb, true, 4}, {out_m2, false, 4}, {states, false, 4}}, "", "", "sample_map, out_rgb, out_m2 and final_states must be 4-byte aligned");
-    if (rc != ORT_OK) return rc;
-    if (q.policy != ORT_POLICY_PIXEL) return fail(ORT_ERR_UNSUPPORTED, "the sample-map render cuts one-pixel jobs: it needs the PIXEL policy");
-    if (q.shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, "the sample-map render is not sharded");
-    if (q.flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "the sample-map render has no packed framebuffer");
-    ort_view own;
-    if (batch) {
-        if ((rc = check_views_in_box(s, views, view_count)) != ORT_OK) return rc;
-    } else {
-        ort::camera_basis(*s, q.width, q.height, &own.camera);
-        own.seed = q.seed;
-        views = &own;
-    }
-    if ((rc = check_resident(s)) != ORT_OK) return rc;
-    ort::RenderCall c{host, stream, stats};
-    c.views = views; c.view_count = view_count; c.sample_map = sample_map;
-    return run_render(s, &q, c, out_rgb, nullptr, out_m2, states);
+    static const PixelJobKind kind = {"the sample-map render cuts one-pixel jobs: it needs the PIXEL policy", "the sample-map render is not sharded",
+                                      "the sample-map render has no packed framebuffer"};
+    return render_pixel_jobs(
+        kind, s, p, views, view_count, batch, host, stream, stats,
+        [&] { return check_first_plane(batch, host, views, out_rgb, "null views or framebuffer", "null framebuffer", "null device framebuffer"); },
+        [](ort_render_params *) {},
+        [&](const ort_render_params &q) {
+            if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp (the cap on a pixel's samples) must be <= 1 << 24: a sample count must be exact in float");
+            if (!sample_map) return fail(ORT_ERR_INVALID, host ? "null sample_map" : "null device sample_map");
+            return check_ptrs({{sample_map, true, 4}, {out_rgb, true, 4}, {out_m2, false, 4}, {states, false, 4}}, "", "",
+                              "sample_map, out_rgb, out_m2 and final_states must be 4-byte aligned");
+        },
+        [&](const ort_render_params &q, ort::RenderCall c) { c.sample_map = sample_map; return run_render(s, &q, c, out_rgb, nullptr, out_m2, states); });
 }
 
-/* First-hit feature renders, one frame or a batch of views: render_adaptive_common's order with the planes where ad stands.
-   view_count == 0 is OK whatever else is passed (the views form); then nulls (the planes struct, all five feature planes, views) and
-   the view cap, the params as the render call judges them (chunk and rr are not the caller's to set here), spp above 1 << 24 and the
-   planes' alignment, what the call does not do (any policy but PIXEL, shards, a packed framebuffer, a camera outside the box), the
-   scene's state.  !batch: the single-frame form (views unread), the one-view batch of the scene's own camera and params->seed */
+/* First-hit feature renders.  Nulls: the planes struct, all five feature planes, the views.  rr is not the caller's to set either.  Own
+   checks: spp above 1 << 24, the planes' alignment.  The launch is device_render_features, not run_render */
 static int render_features_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool batch, bool host,
                                   const ort_feature_planes *planes, void *stream, ort_stats *stats) {
-    if (batch && view_count == 0) return nothing_to_do(stats);
-    if (!planes) return fail(ORT_ERR_INVALID, "null planes");
-    if (!planes->albedo && !planes->normal && !planes->depth && !planes->hits && !planes->ids)
-        return fail(ORT_ERR_INVALID, "no feature plane is asked for: albedo, normal, depth, hits and ids are all null");
-    if (batch && !views) return fail(ORT_ERR_INVALID, "null views");
-    if (view_count > ORT_MAX_VIEWS) return fail(ORT_ERR_INVALID, "more than ORT_MAX_VIEWS (4096) views in one call");
-    if (!s || !p) return fail(ORT_ERR_INVALID, "null scene or params");
-    ort_render_params q = *p;
-    q.chunk = q.spp;
-    q.rr = 0.0f;
-    int rc = check_param_values(s, &q);
-    if (rc != ORT_OK) return rc;
-    if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp must be <= 1 << 24: a sample count must be exact in float");
-    rc = check_ptrs({{planes->albedo, false, 4}, {planes->normal, false, 4}, {planes->depth, false, 4}, {planes->hits, false, 4}, {planes->ids, false, 4},
-                     {planes->final_states, false, 4}}, "", "", "albedo, normal, depth, hits, ids and final_states must be 4-byte aligned");
-    if (rc != ORT_OK) return rc;
-    if (q.policy != ORT_POLICY_PIXEL) return fail(ORT_ERR_UNSUPPORTED, "the feature render cuts one-pixel jobs: it needs the PIXEL policy");
-    if (q.shard_count > 1) return fail(ORT_ERR_UNSUPPORTED, "the feature render is not sharded");
-    if (q.flags & ORT_RENDER_PACKED) return fail(ORT_ERR_UNSUPPORTED, "the feature render has no packed planes");
-    ort_view own;
-    if (batch) {
-        if ((rc = check_views_in_box(s, views, view_count)) != ORT_OK) return rc;
-    } else {
-        ort::camera_basis(*s, q.width, q.height, &own.camera);
-        own.seed = q.seed;
-        views = &own;
-    }
-    if ((rc = check_resident(s)) != ORT_OK) return rc;
-    std::string err;
-    rc = ort::device_render_features(s, &q, views, view_count, {host, 0, q.flags, stream, stats}, *planes, &err);
-    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+    static const PixelJobKind kind = {"the feature render cuts one-pixel jobs: it needs the PIXEL policy", "the feature render is not sharded",
+                                      "the feature render has no packed planes"};
+    return render_pixel_jobs(
+        kind, s, p, views, view_count, batch, host, stream, stats,
+        [&] {
+            if (!planes) return fail(ORT_ERR_INVALID, "null planes");
+            if (!planes->albedo && !planes->normal && !planes->depth && !planes->hits && !planes->ids)
+                return fail(ORT_ERR_INVALID, "no feature plane is asked for: albedo, normal, depth, hits and ids are all null");
+            return batch && !views ? fail(ORT_ERR_INVALID, "null views") : ORT_OK;
+        },
+        [](ort_render_params *q) { q->rr = 0.0f; },
+        [&](const ort_render_params &q) {
+            if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp must be <= 1 << 24: a sample count must be exact in float");
+            return check_ptrs({{planes->albedo, false, 4}, {planes->normal, false, 4}, {planes->depth, false, 4}, {planes->hits, false, 4}, {planes->ids, false, 4},
+                               {planes->final_states, false, 4}}, "", "", "albedo, normal, depth, hits, ids and final_states must be 4-byte aligned");
+        },
+        [&](const ort_render_params &q, const ort::RenderCall &c) {
+            std::string err;
+            const int rc = ort::device_render_features(s, &q, c.views, c.view_count, {host, 0, q.flags, stream, stats}, *planes, &err);
+            return rc == ORT_OK ? ORT_OK : fail(rc, err);
+        });
 }
 
 static int ort_render_views_workspace_bytes_impl(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) {

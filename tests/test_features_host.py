@@ -13,7 +13,7 @@ import pytest
 import feature_cases as fc
 import host_sim_tool as hs
 from conftest import DATA, ROOT
-from host_cases import aligned as _aligned, scene as _scene
+from host_cases import aligned as _aligned, params as _params, scene as _scene
 
 NAMES = {"ort_render_features", "ort_render_features_device", "ort_render_views_features", "ort_render_views_features_device"}
 SCENES = ["c2_analytic", "c3_bunny_room", "open"]
@@ -99,13 +99,6 @@ def test_entry_points_have_c_linkage(api):
         assert word in section, word
     order = [section.rindex(k) for k in ("ORT_ERR_INVALID (", "ORT_ERR_UNSUPPORTED (policy", "ORT_ERR_STATE (", "ORT_ERR_NO_DEVICE (")]
     assert order == sorted(order)
-
-
-def _params(api, **kw):
-    p = api.Scene.params(kw.pop("width", 8), kw.pop("height", 8), kw.pop("spp", 4), 1, kw.pop("policy", "pixel"), kw.pop("chunk", 0),
-                         kw.pop("rect", None), kw.pop("rr", 0.8), shard=kw.pop("shard", (0, 1)), packed=kw.pop("packed", False))
-    assert not kw
-    return p
 
 
 def _caller(api, views_form, device_form):

@@ -16,7 +16,7 @@ import render_adaptive_cases as rac
 import table_scenes
 from adaptive_cases import Adaptive
 from conftest import DATA, ROOT
-from host_cases import aligned as _aligned, scene as _scene
+from host_cases import adaptive_params as _params, aligned as _aligned, scene as _scene
 
 NAMES = {"ort_render_adaptive", "ort_render_adaptive_device", "ort_render_views_adaptive", "ort_render_views_adaptive_device"}
 _worlds = {}
@@ -97,13 +97,6 @@ def test_entry_points_have_c_linkage(api):
 
 
 GOOD = tuple(rac.FRAME)   # any valid set: the errors do not depend on it
-
-
-def _params(api, **kw):
-    p = api.Scene.params(kw.pop("width", 8), kw.pop("height", 8), kw.pop("spp", 0), 1, kw.pop("policy", "pixel"), kw.pop("chunk", 0),
-                         kw.pop("rect", None), kw.pop("rr", 0.8), shard=kw.pop("shard", (0, 1)), packed=kw.pop("packed", False))
-    assert not kw
-    return p
 
 
 def _caller(api, views_form, device_form):
