@@ -44,7 +44,19 @@ int ort_abi_version(void);
 /* ---- plain data mirrors of the reference structs ---------------------------------- */
 typedef struct { float x, y, z; } ort_v3;
 
-/* ray.h:30-40 */
+/* ray.h:30-40.  The coefficients are used as given: any IEEE-754 value is allowed in diffuse, specular, transmission, ior and
+ * emit -- negative, above 1, denormal, +-inf, NaN (a .scn file can say them too: its lexer reads 1.0e+39 as +inf and 0.0e+39 as
+ * NaN) -- and no call clamps, rejects or repairs one.  What a call returns is then the reference's own result on the same
+ * numbers, in every bit, a NaN output where the reference has one (sign and payload are not promised).  What makes that hold:
+ *   - a bounce adds a light's emission to a sample only when none of its components is NaN or inf (ray.cpp's guard); a primary
+ *     hit on a light adds it as it stands, so a non-finite emit shows in the pixels that see the light directly and nowhere else;
+ *   - a primary hit scales the path's weight by diffuse only if |diffuse|^2 > 0: false for a NaN and for a square that underflows;
+ *   - the lobe weights |Kd|, |Ks|, |Kt| over their sum are NaN when the sum is 0, inf or NaN: every "choice < weight" is then
+ *     false and the sample takes the specular draw and then refracts, whichever kernel flavour runs; a scene is "diffuse only"
+ *     when no material passes |Ks|^2 > 0, |Kt|^2 > 0 or a specular or transmission weight > 0, the comparisons that guard the
+ *     specular and transmission blocks themselves;
+ *   - the stopping rule of the adaptive calls keeps sampling when its variance is NaN (a sum of squared luminance that overflowed).
+ * The roulette probability rr of every call must lie in (0, 1): at rr >= 1 or NaN a path in a closed scene has no bound. */
 typedef struct {
     ort_v3 diffuse;
     float specular[4]; /* .w ("alpha") is parsed but unused by the path */

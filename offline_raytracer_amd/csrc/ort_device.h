@@ -306,8 +306,10 @@ ORT_D V3 sample_lobe(V3 N, float c, float phi) { return sample_lobe_n(normalize(
 /* sample_brdf (ray.cpp:1100-1161) in two halves around the evaluation of cos/sin(phi):
    draw: the three RNG draws, the lobe's cos(theta) and the azimuth phi = 2 pi e1 */
 struct BrdfDraw { float c, phi, choice; };
-/* DIFFUSE_SCENE: every material has pd_c = 1, so the other lobes are drawn only when the choice is exactly 1.0 -- a hint
-   for the register allocator (block frequencies), not a change of the code's meaning */
+/* DIFFUSE_SCENE: a material with finite weights has pd_c = 1, so the other lobes are drawn only when the choice is exactly
+   1.0; one whose weights are NaN (Kd NaN, inf or all zero: make_dev_material's a / s) fails choice < pd_c on every draw and
+   takes the other lobes' draw every time, as it does in the all-lobes flavour and in the reference.  The flag is a hint for
+   the register allocator (block frequencies), not a change of the code's meaning */
 template <bool DIFFUSE_SCENE = false>
 ORT_D BrdfDraw sample_brdf_draw(uint32_t &rng, float rough, const Mat &mt) {
     float e0 = rng_01(rng), e1 = rng_01(rng);

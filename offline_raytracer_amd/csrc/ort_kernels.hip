@@ -153,14 +153,7 @@ int device_upload(Scene *scene, int device, std::string *err) {
     }
     const std::vector<DevMaterial> mats = dev_materials(*scene);
     if ((rc = upload_vec(mats, &d->materials, err))) return rc;
-    d->diffuse_only = true; /* the four guards of eval_scattering / pdf_brdf, for every material a path can scatter on */
-    for (size_t i = 1; i < mats.size(); ++i) {
-        const DevMaterial &dm = mats[i];
-        if (dm.is_light) continue;
-        const float ks2 = dm.specular[0] * dm.specular[0] + dm.specular[1] * dm.specular[1] + dm.specular[2] * dm.specular[2];
-        const float kt2 = dm.transmission[0] * dm.transmission[0] + dm.transmission[1] * dm.transmission[1] + dm.transmission[2] * dm.transmission[2];
-        if (ks2 > 0.0f || kt2 > 0.0f || dm.ps_c > 0.0f || dm.pt_c > 0.0f) d->diffuse_only = false;
-    }
+    d->diffuse_only = materials_diffuse_only(mats);
     const std::vector<uint32_t> lis = light_sphere_flags(*scene);
     d->light_count = (uint32_t)lis.size();
     if ((rc = upload_vec(lis, &d->light_is_sphere, err))) return rc;

@@ -48,6 +48,20 @@ inline std::vector<DevMaterial> dev_materials(const Scene &scene) {
     for (size_t i = 0; i < mats.size(); ++i) mats[i] = make_dev_material(scene.materials[i]);
     return mats;
 }
+/* whether no surface material can enter the specular / transmission blocks: the four guards of eval_scattering / pdf_brdf, for
+   every material a path can scatter on.  This picks the DIFFUSE kernel flavour.  Every comparison with a NaN is false, so a scene
+   whose materials are NaN, inf-diffuse or all-zero (pd_c = ps_c = pt_c = NaN) counts as diffuse-only: the blocks' own guards are
+   the same comparisons, and skip them for such a material too (tests/hostile_materials.py) */
+inline bool materials_diffuse_only(const std::vector<DevMaterial> &mats) {
+    for (size_t i = 1; i < mats.size(); ++i) {
+        const DevMaterial &dm = mats[i];
+        if (dm.is_light) continue;
+        const float ks2 = dm.specular[0] * dm.specular[0] + dm.specular[1] * dm.specular[1] + dm.specular[2] * dm.specular[2];
+        const float kt2 = dm.transmission[0] * dm.transmission[0] + dm.transmission[1] * dm.transmission[1] + dm.transmission[2] * dm.transmission[2];
+        if (ks2 > 0.0f || kt2 > 0.0f || dm.ps_c > 0.0f || dm.pt_c > 0.0f) return false;
+    }
+    return true;
+}
 inline std::vector<uint32_t> light_sphere_flags(const Scene &scene) {
     std::vector<uint32_t> lis(scene.lights.size());
     for (size_t i = 0; i < lis.size(); ++i) lis[i] = (scene.lights[i].type == 1u) ? 1u : 0u;

@@ -9,7 +9,7 @@ What is committed is data only: inputs and the reference's outputs.
   ref_det   = reference + deterministic libm (oracle/det_math.h)  -> bit-exact anchor
   ref_glibc = reference + glibc libm, "as shipped" on this box     -> distance report
 
-usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges | --only-tables | --only-cluster | --only-generated]
+usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges | --only-tables | --only-cluster | --only-generated | --only-hostile]
 """
 import json
 import os
@@ -329,7 +329,7 @@ def golden_generated(manifest):
     import reference_goldens as rg
     import render_adaptive_cases as rac
     import test_gpu_light_pick as pick
-    G = manifest["generated"] = {}
+    G = manifest["generated"] = {k: v for k, v in manifest.get("generated", {}).items() if k == "hostile"}   # --only-hostile's part stays
     d = tempfile.mkdtemp(prefix="generated_", dir=TMP) + "/"
 
     # the deep scene
@@ -392,6 +392,48 @@ def golden_generated(manifest):
         G["chains"][name] = dict(scn_sha256=hashlib.sha256(open(scn, "rb").read()).hexdigest(), samples=rg.CHAIN_SAMPLES, seed=rac.SEED,
                                  width=rac.W, height=rac.H, shapes_tested=js["shapes_tested"])
     _npz("chains_rooms.npz", arrays)
+
+
+def golden_hostile(manifest):
+    """the scenes of tests/hostile_materials.py -- NaN, inf, negative, huge and vanishing coefficients, written as the literals
+    the reference's own lexer turns into them: its frames in four seeding policies and the PIXEL final states, the 96 x 64 frame,
+    the diffuse twin, the three dark twins, the 64-sample chains of every pixel, and the loader's material arrays (the digests go
+    into the manifest as for every scene; the materials themselves into the npz, since a NaN has to be compared as a NaN).  The
+    scene files are regenerated by the tests."""
+    import hashlib
+    import hostile_materials as hm
+    G = manifest.setdefault("generated", {})
+    Hs = G["hostile"] = {"scenes": {}, "renders": {}, "chains": {}}
+    d = tempfile.mkdtemp(prefix="hostile_", dir=TMP) + "/"
+    files = {}
+    arrays = {}
+    for stem, text in hm.variants():
+        scn, base = hm.write(d, stem, text)
+        files[stem] = scn
+        dump = os.path.join(d, stem + ".dump")
+        info = run(REF_DET, "scene-dump", scn, base, hm.W, hm.H, dump)
+        sd = ref_io.read_scene_dump(dump)
+        dg = ref_io.scene_digest(sd)
+        dg["octree"] = info
+        dg["scn_sha256"] = hashlib.sha256(open(scn, "rb").read()).hexdigest()
+        Hs["scenes"][stem] = dg
+        if stem in hm.SCENES:
+            arrays[stem + "__materials"] = np.frombuffer(sd.materials.tobytes(), "<u4").reshape(len(sd.materials), -1)
+    for scene, policy, chunk, (w, h), states in hm.RENDERS:
+        key = hm.key(scene, policy, chunk, (w, h))
+        arrays[key], st, Hs["renders"][key] = _ref_pixel(files[scene], d, w, h, hm.SPP, hm.SEED, d, policy, chunk, states=states)
+        if states:
+            arrays[key + "__states"] = st
+    _npz("renders_hostile.npz", arrays)
+    arrays = {}
+    for name in hm.SCENES:
+        cols, states = os.path.join(d, "chain.f32"), os.path.join(d, "chain.u32")
+        js = run(REF_DET, "chain", files[name], d, hm.W, hm.H, hm.CHAIN_SAMPLES, hm.SEED, 0, 0, hm.W, hm.H, cols, states)
+        arrays[name + "__colours"] = np.fromfile(cols, "<f4").reshape(hm.H, hm.W, hm.CHAIN_SAMPLES, 3)
+        arrays[name + "__states"] = np.fromfile(states, "<u4").reshape(hm.H, hm.W, hm.CHAIN_SAMPLES)
+        Hs["chains"][name] = dict(scn_sha256=Hs["scenes"][name]["scn_sha256"], samples=hm.CHAIN_SAMPLES, seed=hm.SEED, width=hm.W, height=hm.H,
+                                  shapes_tested=js["shapes_tested"])
+    _npz("chains_hostile.npz", arrays)
 
 
 def golden_showcase():
@@ -459,6 +501,11 @@ def main():
     if "--only-generated" in sys.argv:  # add / refresh the generated scenes' fixtures without touching the others
         manifest = json.load(open(os.path.join(HERE, "manifest.json")))
         golden_generated(manifest)
+        json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
+        return
+    if "--only-hostile" in sys.argv:  # add / refresh the hostile-material scenes' fixtures without touching the others
+        manifest = json.load(open(os.path.join(HERE, "manifest.json")))
+        golden_hostile(manifest)
         json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
         return
     if "--only-c5" in sys.argv:  # add / refresh the C5 fixtures without touching the others
@@ -579,6 +626,7 @@ def main():
     golden_tablescenes(manifest)
     golden_clusterscene(manifest)
     golden_generated(manifest)
+    golden_hostile(manifest)
     golden_showcase()
     golden_unit_edges()
     golden_raycast_edges()

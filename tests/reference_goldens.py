@@ -74,17 +74,22 @@ def room_text(name):
     return lg.ROOM + lg.SPHERES[name[len("room_"):]] + lg.THREE_LIGHTS
 
 
-def dark_twin_text(name, keep):
-    """the room with every `light` line but the keep-th (in file order, which is the light materials' order) reading light 0 0 0"""
+def dark_text(text, keep, lights=3):
+    """a scene's text with every `light` line but the keep-th (in file order, which is the light materials' order) reading light 0 0 0"""
     out, k = [], 0
-    for line in room_text(name).splitlines():
+    for line in text.splitlines():
         if line.startswith("light "):
             if k != keep:
                 line = "light 0 0 0"
             k += 1
         out.append(line)
-    assert k == 3
+    assert k == lights
     return "\n".join(out) + "\n"
+
+
+def dark_twin_text(name, keep):
+    """the room with every `light` line but the keep-th reading light 0 0 0"""
+    return dark_text(room_text(name), keep)
 
 
 def white_twin_text(name):

@@ -166,6 +166,7 @@ static int sim_open(Sim &S, const char *scn, const char *base, uint32_t need) {
     ort_scene_get_tree_info(S.scene, &ti);
     fprintf(stderr, "tree: %u nodes, %u leaves, max leaf %u, depth %u, sah %.2f\n", ti.node_count, ti.leaf_count, ti.max_leaf_prims, ti.max_depth, ti.sah_cost);
     S.mats = dev_materials(*S.scene);
+    fprintf(stderr, "materials: %zu, diffuse_only %d\n", S.mats.size(), (int)materials_diffuse_only(S.mats)); /* the flavour an upload picks */
     S.lis = light_sphere_flags(*S.scene);
     SceneView &sv = S.sv;
     sv.nodes = (const float4 *)t.nodes.data(); sv.tris = (const float4 *)t.tris.data();
