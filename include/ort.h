@@ -299,6 +299,10 @@ int ort_render_views_workspace_bytes(const ort_render_params *params, uint32_t v
  * Replaces raycast_top_most_node (reference code/ray.cpp:1165-1176): the closest hit of each of the caller's rays,
  * bit for bit the reference's hit_t, hit_normal and hit_mat_index (ties in the reference's test order, phantom
  * sphere hits and visibility chains included).  A miss is t = FLT_MAX, n = 0, mat = 0, prim = ORT_NO_PRIM.
+ * A shape may itself carry material 0, the "no hit" material: in a .scn file every sphere, box, cylinder or mesh written
+ * before the first `brdf` or `light` line does (parser.cpp:1260-1440), and ort_scene_create accepts mat = 0 on any shape.
+ * Such a shape is geometry like any other and wins closest-hit contests: a hit on it returns the shape's t, n and prim
+ * with mat = 0 -- never ORT_NO_PRIM with a finite t.  What a caller of the hit makes of mat = 0 is said per query below.
  * Rays: count x {o.xyz, d.xyz} f32, 24 B each; d need not be of unit length (the reference does not normalise it),
  * zero components are allowed.  Every IEEE-754 ray gets the reference's answer, NaN, infinite, zero, subnormal and
  * overflowing components included: every non-NaN output bit for bit, a NaN output NaN in the same field and component
@@ -333,9 +337,12 @@ int ort_raycast_device(ort_scene *scene, const void *d_rays, uint64_t count, voi
  * Rays as for ort_raycast (24 B each, d not normalised, any IEEE-754 bits); tmax[i] is in units of the ray parameter,
  * the same t as ort_hit.t.  The comparison is the IEEE one: a NaN tmax or a NaN h.t gives 0; tmax <= 0, -0.0 and
  * -inf give 0; a miss (t = FLT_MAX, mat = 0) gives 0 for every tmax, +inf included; tmax == h.t gives 0 (strict),
- * the next float above h.t gives 1.  tmax == NULL means no limit: the answers of tmax[i] = +inf.  The output is one
- * byte per ray, exactly 0 or 1 (the layout of a bool tensor).  occluded[i] answers rays[i]; results do not depend on
- * count, order or how the batch is sliced.  There is no tmin: the intersectors' own threshold (1e-6) stands.
+ * the next float above h.t gives 1.  A closest hit on a shape that carries material 0 (see ort_raycast) gives byte 0
+ * for every tmax too, tmax == NULL included, even where a solid surface lies behind it below tmax: only the closest
+ * hit is asked.  A solid shape in front of such a shape is the ordinary comparison.  tmax == NULL means no limit: the
+ * answers of tmax[i] = +inf.  The output is one byte per ray, exactly 0 or 1 (the layout of a bool tensor).
+ * occluded[i] answers rays[i]; results do not depend on count, order or how the batch is sliced.  There is no tmin:
+ * the intersectors' own threshold (1e-6) stands.
  * The traversal never looks beyond tmax, writes one byte instead of 24 and needs no shape table; the rays that
  * ort_raycast sends to the exact octree walk take it here too (occluded_rays).
  * flags and stats as for ort_raycast.  rays must be 8-byte aligned, a non-NULL tmax 4-byte aligned.  count == 0 returns
@@ -510,6 +517,8 @@ int ort_irradiance_adaptive_device(ort_scene *scene, const void *d_points, const
  *        d_k = normalize(m)
  *    and then o_k, the byte ort_occluded returns for the ray (p, d_k) with tmax = radius[i]: (h.mat != 0 && h.t < radius[i]) of the
  *    reference's closest hit h.  Nothing else is drawn: the stream advances exactly two steps per sample, whatever is hit.
+ *    A sample whose closest hit is on a shape that carries material 0 (see ort_raycast) is therefore an open sample, at every
+ *    radius, and its direction enters the bent sum.
  *  - Outputs.  out_open[i] is the number of samples with o_k == 0: visibility is out_open / spp, ambient occlusion one minus that;
  *    the count is returned so that no rounding is added.  out_bent (may be NULL) is count x 3 f32: B starts at (+0, +0, +0) and,
  *    for every open sample in sample order, B = B + d_k component by component, each a separately rounded f32 add; B is returned as
@@ -736,8 +745,9 @@ int ort_render_views_sample_map_device(ort_scene *scene, const ort_render_params
  * as it stands: a mirror or glass surface has its (often zero) diffuse colour.
  * Outputs.  albedo = A / (float)spp, normal = N / (float)spp, depth = D / (float)spp, component by component (ray.cpp:1428's
  * division).  hits is the count; a caller who wants the mean over hits divides by coverage.  normal is not re-normalised.  ids =
- * {h.mat, h.prim} of sample 0; a miss gives 0, ORT_NO_PRIM; ids do not average.  d is a unit vector, so depth is a distance from
- * the aperture point.
+ * {h.mat, h.prim} of sample 0; a miss gives 0, ORT_NO_PRIM; ids do not average.  A sample whose closest hit is on a shape that
+ * carries material 0 (see ort_raycast) does not count in hits and adds nothing to A, N or D; as sample 0 it gives ids = {0, the
+ * shape's prim}.  d is a unit vector, so depth is a distance from the aperture point.
  * Parameters.  params->policy must be ORT_POLICY_PIXEL; any other policy is ORT_ERR_UNSUPPORTED.  params->spp is within
  * [1, 1 << 24], so that (float)spp is exact.  params->chunk and params->rr are ignored.  shard_count > 1 and ORT_RENDER_PACKED
  * return ORT_ERR_UNSUPPORTED.

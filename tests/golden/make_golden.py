@@ -9,7 +9,7 @@ What is committed is data only: inputs and the reference's outputs.
   ref_det   = reference + deterministic libm (oracle/det_math.h)  -> bit-exact anchor
   ref_glibc = reference + glibc libm, "as shipped" on this box     -> distance report
 
-usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges | --only-tables | --only-cluster | --only-generated | --only-hostile]
+usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges | --only-tables | --only-cluster | --only-generated | --only-hostile | --only-void]
 """
 import json
 import os
@@ -329,7 +329,7 @@ def golden_generated(manifest):
     import reference_goldens as rg
     import render_adaptive_cases as rac
     import test_gpu_light_pick as pick
-    G = manifest["generated"] = {k: v for k, v in manifest.get("generated", {}).items() if k == "hostile"}   # --only-hostile's part stays
+    G = manifest["generated"] = {k: v for k, v in manifest.get("generated", {}).items() if k in ("hostile", "void")}   # --only-hostile's and --only-void's parts stay
     d = tempfile.mkdtemp(prefix="generated_", dir=TMP) + "/"
 
     # the deep scene
@@ -436,6 +436,76 @@ def golden_hostile(manifest):
     _npz("chains_hostile.npz", arrays)
 
 
+def golden_void(manifest):
+    """the scenes of tests/void_material.py -- shapes written before the first `brdf` line, which carry material 0: the
+    reference's closest hits (t, n, mat) on void_seen for void_material.ray_sets' rays (raycast_void.npz), its frames in four
+    seeding policies, the PIXEL final states, the 96 x 64 frames, the three dark twins and the 64-sample chains of void_hidden
+    (renders_void.npz, chains_void.npz), and the loader's counts, digests and light list of every text.  void_seen and all_void
+    are NOT rendered: a primary hit on a void shape dereferences a null material in the reference, as a primary miss does.
+    _no_primary_void refuses, with the oracle, every scene whose camera could meet one."""
+    import hashlib
+    import feature_cases as fc
+    import oracle_lib
+    import void_material as vm
+    G = manifest.setdefault("generated", {})
+    V = G["void"] = {"scenes": {}, "renders": {}, "chains": {}, "raycast": {}}
+    d = tempfile.mkdtemp(prefix="void_", dir=TMP) + "/"
+    files, dumps = {}, {}
+    for stem in vm.STEMS:
+        scn, base = vm.write(d, stem)
+        files[stem] = scn
+        dump = os.path.join(d, stem + ".dump")
+        info = run(REF_DET, "scene-dump", scn, base, vm.W, vm.H, dump)
+        dumps[stem] = ref_io.read_scene_dump(dump)
+        dg = ref_io.scene_digest(dumps[stem])
+        dg["octree"] = info
+        dg["scn_sha256"] = hashlib.sha256(open(scn, "rb").read()).hexdigest()
+        V["scenes"][stem] = dg
+
+    def _no_primary_void(stem, w, h, spp):
+        """no camera sample of the scene's PIXEL streams at w x h, nor of a frame four times as fine, has a closest hit that
+        carries material 0 or misses"""
+        dump = os.path.join(d, "cam.dump")
+        for ww, hh, n in ((w, h, spp), (4 * w, 4 * h, 2)):
+            run(REF_DET, "scene-dump", files[stem], d, ww, hh, dump)
+            flat = ref_io.read_scene_dump(dump)
+            f = fc.frame(oracle_lib, oracle_lib.OracleScene(flat), flat, flat.camera, ww, hh, vm.SEED, n)
+            assert (f.mat != 0).all(), "%s at %d x %d: %d camera samples meet material 0 or miss; the reference cannot render it" % (stem, ww, hh, int((f.mat == 0).sum()))
+
+    # closest hits on void_seen
+    def cast(rays):
+        np.ascontiguousarray(rays, "<f4").tofile(os.path.join(d, "rays.bin"))
+        run(REF_DET, "raycast", files["void_seen"], d, os.path.join(d, "rays.bin"), os.path.join(d, "hits.bin"))
+        return np.fromfile(os.path.join(d, "hits.bin"), dtype=np.dtype([("t", "<f4"), ("n", "<f4", 3), ("mat", "<u4")]))
+    rays, kind = vm.ray_sets(dumps["void_seen"], lambda r: (lambda h: (h["t"], h["mat"]))(cast(r)))
+    hits = cast(rays)
+    _npz("raycast_void.npz", dict(t=hits["t"], n=hits["n"], mat=hits["mat"], kind=kind))
+    V["raycast"] = dict(scene="void_seen", rays_sha256=vm.rays_sha256(rays), count=int(len(rays)))
+
+    # frames and chains of void_hidden
+    arrays = {}
+    for scene, policy, chunk, (w, h), states in vm.RENDERS:
+        assert scene in vm.RENDERED
+        _no_primary_void(scene, w, h, vm.CHAIN_SAMPLES if (w, h) == (vm.W, vm.H) else vm.SPP)
+        key = vm.key(scene, policy, chunk, (w, h))
+        arrays[key], st, V["renders"][key] = _ref_pixel(files[scene], d, w, h, vm.SPP, vm.SEED, d, policy, chunk, states=states)
+        if states:
+            arrays[key + "__states"] = st
+    _npz("renders_void.npz", arrays)
+    arrays = {}
+    name = "void_hidden"
+    _no_primary_void(name, vm.W, vm.H, vm.CHAIN_SAMPLES)
+    cols, states = os.path.join(d, "chain.f32"), os.path.join(d, "chain.u32")
+    js = run(REF_DET, "chain", files[name], d, vm.W, vm.H, vm.CHAIN_SAMPLES, vm.SEED, 0, 0, vm.W, vm.H, cols, states)
+    arrays[name + "__colours"] = np.fromfile(cols, "<f4").reshape(vm.H, vm.W, vm.CHAIN_SAMPLES, 3)
+    arrays[name + "__states"] = np.fromfile(states, "<u4").reshape(vm.H, vm.W, vm.CHAIN_SAMPLES)
+    V["chains"][name] = dict(scn_sha256=V["scenes"][name]["scn_sha256"], samples=vm.CHAIN_SAMPLES, seed=vm.SEED, width=vm.W, height=vm.H,
+                             shapes_tested=js["shapes_tested"])
+    _npz("chains_void.npz", arrays)
+    for f in vm.FILES:
+        V.setdefault("files", {})[f] = hashlib.sha256(open(os.path.join(HERE, f), "rb").read()).hexdigest()
+
+
 def golden_showcase():
     """a crop of an image the reference itself wrote (showcase/1.hdr): header, file size, 32x64 RGBE pixels"""
     raw = open("/root/reference/showcase/1.hdr", "rb").read()
@@ -506,6 +576,11 @@ def main():
     if "--only-hostile" in sys.argv:  # add / refresh the hostile-material scenes' fixtures without touching the others
         manifest = json.load(open(os.path.join(HERE, "manifest.json")))
         golden_hostile(manifest)
+        json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
+        return
+    if "--only-void" in sys.argv:  # add / refresh the void-material scenes' fixtures without touching the others
+        manifest = json.load(open(os.path.join(HERE, "manifest.json")))
+        golden_void(manifest)
         json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
         return
     if "--only-c5" in sys.argv:  # add / refresh the C5 fixtures without touching the others
@@ -627,6 +702,7 @@ def main():
     golden_clusterscene(manifest)
     golden_generated(manifest)
     golden_hostile(manifest)
+    golden_void(manifest)
     golden_showcase()
     golden_unit_edges()
     golden_raycast_edges()

@@ -160,9 +160,11 @@ class Case:
     """what light_groups_cases.host_light_groups, sample_map_cases.host_sample_map and sample_map_cases.chains take of a case:
     the scene file of `name` written into directory, its committed scene, flattened arrays and oracle scene"""
 
+    write_scene = staticmethod(write)   # (directory, name) -> (scn, base); tests/void_material.py writes its own scenes
+
     def __init__(self, api, oracle, name, directory):
         self.name, self.oracle, self.csg = name, oracle, True
-        self.scn, self.base = write(directory, name)
+        self.scn, self.base = self.write_scene(directory, name)
         self.scene = api.Scene.load_scn(self.scn).commit()
         self.flat = self.scene.flatten(W, H)
         self.lights = [int(m) for m in np.nonzero(self.flat.materials["is_light"])[0]]

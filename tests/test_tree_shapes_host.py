@@ -168,6 +168,8 @@ def test_raycast(world, tmp_path, name, variant, env):
     assert_bits_equal(hits["t"], t, what + " t")
     assert_bits_equal(hits["n"], n, what + " normals")
     assert (hits["mat"] == mat).all(), "%s: %d materials differ" % (what, (hits["mat"] != mat).sum())
+    # holds because no shape of these scenes carries material 0; tests/test_void_material_host.py has the scenes where a hit with
+    # mat == 0 names a shape
     assert ((hits["prim"] == hs.NO_PRIM) == (mat == 0)).all()
     c = hs.counters(r)
     assert c["rays"] == len(rays)

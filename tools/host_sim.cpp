@@ -167,6 +167,7 @@ static int sim_open(Sim &S, const char *scn, const char *base, uint32_t need) {
     fprintf(stderr, "tree: %u nodes, %u leaves, max leaf %u, depth %u, sah %.2f\n", ti.node_count, ti.leaf_count, ti.max_leaf_prims, ti.max_depth, ti.sah_cost);
     S.mats = dev_materials(*S.scene);
     fprintf(stderr, "materials: %zu, diffuse_only %d\n", S.mats.size(), (int)materials_diffuse_only(S.mats)); /* the flavour an upload picks */
+    fprintf(stderr, "shapes: mats_nonzero %u\n", all_mats_nonzero(t)); /* whether the occlusion lanes may take their early end */
     S.lis = light_sphere_flags(*S.scene);
     SceneView &sv = S.sv;
     sv.nodes = (const float4 *)t.nodes.data(); sv.tris = (const float4 *)t.tris.data();
