@@ -165,7 +165,20 @@ int ort_scene_get_camera(const ort_scene *scene, int32_t width, int32_t height, 
  * Replaces the octree construction of main() (macos_main.mm:418-545 driving
  * ray.cpp:1799-2045).  Closest-hit results do not depend on the tree (SURVEY 8a note),
  * so this builds the GPU layout directly: a flat SoA tree with 16-byte-aligned node
- * records and triangle slabs. */
+ * records and triangle slabs.
+ * What a shape may be.  Sizes need not be positive: a sphere or cylinder of negative or zero radius, a box with max < min or
+ * max == min on any axis, a cylinder whose axis is (0, 0, 0), a mesh whose triangles have no area are all accepted, and every
+ * call gives for them what the reference gives, bit for bit (a box is bounded by the min and max of its corners, a quadric by
+ * |r|; where the reference's own octree, built from r * (1, 1, 1) or from 0/0, finds such a shape and where it does not is
+ * reproduced by the tree kept for that purpose).
+ * What is refused.  Every shape gets a bounding box, grown for spheres and cylinders by a slack that scales with the diagonal
+ * of the box of ALL shapes and camera_p.  A scene in which any shape's box, after the slack, has a non-finite component or one
+ * beyond 1e30 in magnitude is refused: ORT_ERR_INVALID, ort_last_error() "scene contains a non-finite or oversized primitive".
+ * One huge shape is enough: with a sphere of radius 1e20 in the scene the slack of every other quadric overflows.  A NaN or
+ * infinite centre, corner, radius, axis or vertex is refused for the same reason; 1e12 is accepted.  The reference renders
+ * such scenes; this library does not.  A refused scene stays a valid, uncommitted handle: it still answers ort_scene_get_info and the
+ * ort_scene_get_* calls, ort_scene_get_tree_info returns ORT_ERR_STATE, the next commit refuses it again in the same way, and
+ * it is destroyed as any other. */
 int ort_scene_commit(ort_scene *scene);
 int ort_scene_get_tree_info(const ort_scene *scene, ort_tree_info *out);
 

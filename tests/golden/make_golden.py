@@ -9,7 +9,7 @@ What is committed is data only: inputs and the reference's outputs.
   ref_det   = reference + deterministic libm (oracle/det_math.h)  -> bit-exact anchor
   ref_glibc = reference + glibc libm, "as shipped" on this box     -> distance report
 
-usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges | --only-tables | --only-cluster | --only-generated | --only-hostile | --only-void]
+usage: python tests/golden/make_golden.py [--only-c5 | --only-showcase | --only-unit-edges | --only-raycast-edges | --only-tables | --only-cluster | --only-generated | --only-hostile | --only-void | --only-shapes]
 """
 import json
 import os
@@ -329,7 +329,7 @@ def golden_generated(manifest):
     import reference_goldens as rg
     import render_adaptive_cases as rac
     import test_gpu_light_pick as pick
-    G = manifest["generated"] = {k: v for k, v in manifest.get("generated", {}).items() if k in ("hostile", "void")}   # --only-hostile's and --only-void's parts stay
+    G = manifest["generated"] = {k: v for k, v in manifest.get("generated", {}).items() if k in ("hostile", "void", "shapes")}   # --only-hostile's, --only-void's and --only-shapes' parts stay
     d = tempfile.mkdtemp(prefix="generated_", dir=TMP) + "/"
 
     # the deep scene
@@ -506,6 +506,74 @@ def golden_void(manifest):
         V.setdefault("files", {})[f] = hashlib.sha256(open(os.path.join(HERE, f), "rb").read()).hexdigest()
 
 
+REF_TIME_LIMIT = 600   # seconds a reference run on a hostile-shape scene may take
+
+
+def golden_shapes(manifest):
+    """the scenes of tests/hostile_shapes.py -- zero, negative and inverted sizes, zero axes, vanishing and huge scales, lights
+    made of such shapes: the reference's scene-dump of every text, its closest hits (t, n, mat) on shapes_seen and on shapes_leaves
+    for hostile_shapes.ray_sets' rays (raycast_shapes.npz), its frames in four seeding policies with the PIXEL final states at
+    24 x 16, the PIXEL and CHUNK frames at 96 x 64, the frames of the scenes without their hostile shapes and of the dark twins
+    (renders_shapes.npz) and the 64-sample chains (chains_shapes.npz).  Every reference run must end with status 0 within
+    REF_TIME_LIMIT: a line that makes it crash or hang does not belong in hostile_shapes.py (its docstring names those)."""
+    import hashlib
+    import hostile_shapes as hsh
+    global run
+    plain_run = run
+
+    def run(binary, *args):   # noqa: F811  (the helpers above call the module's run)
+        out = subprocess.run([binary] + [str(a) for a in args], stdout=subprocess.PIPE, timeout=REF_TIME_LIMIT)
+        assert out.returncode == 0, "the reference ended with status %d on %s" % (out.returncode, " ".join(str(a) for a in args[:2]))
+        text = out.stdout.decode().strip()
+        return json.loads(text.splitlines()[-1]) if text.startswith("{") or "\n{" in text else text
+    try:
+        G = manifest.setdefault("generated", {})
+        S = G["shapes"] = {"scenes": {}, "renders": {}, "chains": {}, "raycast": {}}
+        d = tempfile.mkdtemp(prefix="shapes_", dir=TMP) + "/"
+        files, dumps = {}, {}
+        for stem in hsh.STEMS:
+            scn, base = hsh.write(d, stem)
+            files[stem] = scn
+            dump = os.path.join(d, stem + ".dump")
+            info = run(REF_DET, "scene-dump", scn, base, hsh.W, hsh.H, dump)
+            dumps[stem] = ref_io.read_scene_dump(dump)
+            dg = ref_io.scene_digest(dumps[stem])
+            dg["octree"] = info
+            dg["scn_sha256"] = hashlib.sha256(open(scn, "rb").read()).hexdigest()
+            S["scenes"][stem] = dg
+
+        def cast(rays, scene="shapes_seen"):
+            np.ascontiguousarray(rays, "<f4").tofile(os.path.join(d, "rays.bin"))
+            run(REF_DET, "raycast", files[scene], d, os.path.join(d, "rays.bin"), os.path.join(d, "hits.bin"))
+            return np.fromfile(os.path.join(d, "hits.bin"), dtype=np.dtype([("t", "<f4"), ("n", "<f4", 3), ("mat", "<u4")]))
+        rays, kind = hsh.ray_sets(dumps["shapes_seen"], lambda r: cast(r)["t"])
+        hits, leaves = cast(rays), cast(rays, "shapes_leaves")   # the same rays where every hostile shape lies in a tree leaf
+        _npz("raycast_shapes.npz", dict(t=hits["t"], n=hits["n"], mat=hits["mat"], kind=kind, leaves__t=leaves["t"], leaves__n=leaves["n"], leaves__mat=leaves["mat"]))
+        S["raycast"] = dict(scenes=["shapes_seen", "shapes_leaves"], rays_sha256=hsh.rays_sha256(rays), count=int(len(rays)))
+
+        arrays = {}
+        for scene, policy, chunk, (w, h), states in hsh.RENDERS:
+            key = hsh.key(scene, policy, chunk, (w, h))
+            arrays[key], st, S["renders"][key] = _ref_pixel(files[scene], d, w, h, hsh.SPP, hsh.SEED, d, policy, chunk, states=states)
+            if states:
+                arrays[key + "__states"] = st
+        _npz("renders_shapes.npz", arrays)
+        arrays = {}
+        for name in hsh.CHAINS:
+            cols, states = os.path.join(d, "chain.f32"), os.path.join(d, "chain.u32")
+            js = run(REF_DET, "chain", files[name], d, hsh.W, hsh.H, hsh.CHAIN_SAMPLES, hsh.SEED, 0, 0, hsh.W, hsh.H, cols, states)
+            arrays[name + "__colours"] = np.fromfile(cols, "<f4").reshape(hsh.H, hsh.W, hsh.CHAIN_SAMPLES, 3)
+            arrays[name + "__states"] = np.fromfile(states, "<u4").reshape(hsh.H, hsh.W, hsh.CHAIN_SAMPLES)
+            S["chains"][name] = dict(scn_sha256=S["scenes"][name]["scn_sha256"], samples=hsh.CHAIN_SAMPLES, seed=hsh.SEED, width=hsh.W, height=hsh.H,
+                                     shapes_tested=js["shapes_tested"])
+        _npz("chains_shapes.npz", arrays)
+        for f in hsh.FILES:
+            assert os.path.getsize(os.path.join(HERE, f)) < (1 << 20), f
+            S.setdefault("files", {})[f] = hashlib.sha256(open(os.path.join(HERE, f), "rb").read()).hexdigest()
+    finally:
+        run = plain_run
+
+
 def golden_showcase():
     """a crop of an image the reference itself wrote (showcase/1.hdr): header, file size, 32x64 RGBE pixels"""
     raw = open("/root/reference/showcase/1.hdr", "rb").read()
@@ -581,6 +649,11 @@ def main():
     if "--only-void" in sys.argv:  # add / refresh the void-material scenes' fixtures without touching the others
         manifest = json.load(open(os.path.join(HERE, "manifest.json")))
         golden_void(manifest)
+        json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
+        return
+    if "--only-shapes" in sys.argv:  # add / refresh the hostile-shape scenes' fixtures without touching the others
+        manifest = json.load(open(os.path.join(HERE, "manifest.json")))
+        golden_shapes(manifest)
         json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
         return
     if "--only-c5" in sys.argv:  # add / refresh the C5 fixtures without touching the others
@@ -703,6 +776,7 @@ def main():
     golden_generated(manifest)
     golden_hostile(manifest)
     golden_void(manifest)
+    golden_shapes(manifest)
     golden_showcase()
     golden_unit_edges()
     golden_raycast_edges()

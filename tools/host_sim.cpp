@@ -959,6 +959,14 @@ struct TreeCheck {
         if (leaves2 != leaves4) return fail("the binary tree reaches %zu leaf words, the wide tree %zu, or other ones", leaves2.size(), leaves4.size());
         printf("tree-check ok: nodes %zu leaves %u depth %u wide_nodes %zu wide_depth %u prologue %u max_leaf triangle %u sphere %u box %u cylinder %u\n", t.nodes.size(), leaf_count, depth,
                t.nodes4.size(), depth4, t.pro_boxes + t.pro_spheres + t.pro_cyls, max_leaf[PRIM_TRI], max_leaf[PRIM_SPHERE], max_leaf[PRIM_BOX], max_leaf[PRIM_CYL]);
+        /* which source shapes the prologue holds (stderr: the line above is all of stdout); every other shape is in exactly one leaf */
+        fprintf(stderr, "prologue: box");
+        for (size_t i = 0; i < sc.boxes.size(); ++i) if (t.box_slot[i] < t.pro_boxes) fprintf(stderr, " %zu", i);
+        fprintf(stderr, " sphere");
+        for (size_t i = 0; i < sc.spheres.size(); ++i) if (t.sphere_slot[i] < t.pro_spheres) fprintf(stderr, " %zu", i);
+        fprintf(stderr, " cylinder");
+        for (size_t i = 0; i < sc.cylinders.size(); ++i) if (t.cyl_slot[i] < t.pro_cyls) fprintf(stderr, " %zu", i);
+        fprintf(stderr, "\n");
         return true;
     }
 };
