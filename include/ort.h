@@ -706,7 +706,8 @@ int ort_render_views_light_groups_device(ort_scene *scene, const ort_render_para
  * seed and a cap >= max_spp give that call's out_rgb, out_m2 and final_states.  (4) Frame v of a batch is the single-frame call's
  * for that camera, seed and map frame; the single-frame call is the one-view batch of the scene's own camera
  * (ort_scene_get_camera) and params->seed.
- * Not offered: resuming a pixel's stream or sums from an earlier call.  Passes taken with DIFFERENT seeds are independent
+ * This call starts every pixel's stream anew; a pixel's stream and sums are resumed from an earlier call through
+ * ort_render_accumulate (below), which takes the same map.  Passes taken with DIFFERENT seeds are independent
  * estimates and combine weighted by their counts: rgb = (n1 * rgb1 + n2 * rgb2) / (n1 + n2) where n1 + n2 > 0.
  * Parameters.  params->policy must be ORT_POLICY_PIXEL; any other policy is ORT_ERR_UNSUPPORTED.  shard_count > 1 and
  * ORT_RENDER_PACKED return ORT_ERR_UNSUPPORTED.  params->chunk is ignored; rr is judged as the render call judges it (rr >= 0).
@@ -732,6 +733,84 @@ int ort_render_views_sample_map(ort_scene *scene, const ort_render_params *param
 int ort_render_views_sample_map_device(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
                                        const void *d_sample_map, void *d_out_rgb, void *d_out_m2, void *d_final_states,
                                        void *hip_stream, ort_stats *stats);
+
+/* ---- accumulating renders: a frame's samples continued across calls ------------------------------
+ * The sample-map render on planes that carry a pixel's state from call to call: render 64 samples, look, continue to 1024; render
+ * until a time budget runs out; checkpoint the planes and pick the frame up after a restart; refine the pixels of a pilot pass
+ * instead of blending an independent estimate.  After any split of a pixel's samples over calls the planes hold the bits of the
+ * single call.
+ * The planes (ort_accum_planes) belong to the caller and are read AND written; each holds view_count frames of width*height
+ * entries, view-major, row 0 at the bottom -- the layout of ort_render_adaptive's planes:
+ *    sum_rgb   3 f32 per pixel   C, the UNDIVIDED colour sum.  (out_rgb * n is not C: the division rounds once, which is why
+ *                                a mean cannot serve as state)
+ *    m2        f32               Q, the sum of squared sample luminance, as ort_radiance_adaptive defines it   (may be NULL)
+ *    count     u32               n, the samples this pixel has had so far
+ *    states    u32               the stream's state after sample n
+ * HOST pointers in the host forms, DEVICE pointers on the scene's device in the _device forms; the struct itself is host memory in
+ * every form and is read before the call returns.  Every given plane and the map must be 4-byte aligned.  Planes and the map must
+ * not overlap one another (not checked).  A caller starts a frame by setting count to zero and nothing else.
+ * sample_map (may be NULL) is ort_render_sample_map's map, read and never written; out_rgb (may be NULL) is a frame of
+ * view_count * width * height * 3 f32, written and never read.
+ * Contract for pixel i inside the rect, operation by operation:
+ *    n0    = count[i]
+ *    asked = sample_map ? sample_map[i] : params->spp
+ *    add   = min(asked, params->spp, (1 << 24) - min(n0, 1 << 24))
+ * params->spp is the cap on what ONE call adds and lies within [1, 1 << 24]; the total never passes 1 << 24, so (float)n stays
+ * exact.  Neither the map's nor the planes' values are ever judged, identically in all four forms.
+ * add == 0: no word of any plane is read (count[i] and the map word apart) or written for this pixel and its stream is not touched
+ * -- exactly the sample-map render's empty job and the pixels outside the rect.
+ * n0 == 0, a fresh pixel: the stream starts at job_seed(seed, y*W + x) (views[v].seed in the views form), C = (+0, +0, +0),
+ * Q = +0; sum_rgb[i], m2[i] and states[i] are NOT read, whatever they hold.
+ * n0 > 0, a continued pixel: the stream starts at states[i], WITH 0 TAKEN AS 1 (a zero xorshift state never leaves zero, the
+ * roulette would then never end a path in a closed room: the rule is the contract's, not the caller's duty); C = sum_rgb[i] and,
+ * if m2 is given, Q = m2[i] (Q = +0 otherwise) -- used as they stand, NaN and infinities included, as a hostile material is.  A
+ * sample that reaches no light adds the colour +0, so a stored -0 is +0 afterwards: the sums start as stored + (+0).
+ * Then add camera samples run, the aperture draw included: ort_render_image's ORT_POLICY_PIXEL samples, unchanged, each adding
+ * at most one vector to C component by component and its squared luminance to Q.  Written afterwards:
+ *    sum_rgb[i] = C;  m2[i] = Q if m2 is given;  count[i] = n0 + add;  states[i] = the stream's state;
+ *    out_rgb[i] = C / (float)(n0 + add), component by component, if out_rgb is given.
+ * out_rgb is written only for pixels that took samples in THIS call; every other pixel keeps what it held.
+ * Five identities, all bit for bit.  (1) From count == 0 one call gives in out_rgb, m2 and states what ort_render_sample_map
+ * gives for the same map and cap, and count equals that call's n; with a constant add = n that is ort_render_image's
+ * ORT_POLICY_PIXEL frame at spp = n and ort_render_adaptive's planes at min_spp == max_spp == n.  (2) Split invariance: for any
+ * split of a pixel's samples over any number of calls -- other maps, caps and rects per call, other pixels doing anything -- the
+ * four planes after the last call depend only on the pixel's total n, the seed and the camera, so sum_rgb / (float)count is the
+ * single call's pixel.  (3) From the caller's own planes the call is add chained spp = 1 renders from that state: C receives each
+ * one's colour in order, starting from the given C.  (4) Whether m2 or out_rgb is NULL changes no bit of the other planes.
+ * (5) Frame v of a batch is the single-frame call's for that camera and seed; the single-frame call is the one-view batch of the
+ * scene's own camera (ort_scene_get_camera) and params->seed.
+ * Parameters.  params->policy must be ORT_POLICY_PIXEL; any other policy, shard_count > 1 and ORT_RENDER_PACKED return
+ * ORT_ERR_UNSUPPORTED.  params->chunk is ignored; rr is judged as the render call judges it.  The views form follows
+ * ort_render_views: params->seed is ignored, and view_count == 0 is ORT_OK without a launch, whatever the other arguments.
+ * Errors are reported before any device work, in ort_render_sample_map's order with acc where the map stands: ORT_ERR_INVALID
+ * (null views, view cap exceeded, null scene or params, empty or bad params exactly as ort_render_image judges them; then spp
+ * above 1 << 24; then a null acc, acc->sum_rgb, acc->count or acc->states; then a given plane or map not 4-byte aligned),
+ * ORT_ERR_UNSUPPORTED (policy, shard, packed, camera outside the box), ORT_ERR_STATE (scene not committed), ORT_ERR_NO_DEVICE
+ * (not uploaded).
+ * The device forms enqueue on hip_stream (NULL = the default stream) and wait for the launch only when stats != NULL.  Successive
+ * calls on one stream therefore chain passes on planes that never leave the device: no plane visits the host between them, and
+ * the order of the stream is the order of the passes.  (As every call on a scene, a call first waits until the scene's previous
+ * launch has finished: a scene runs one launch at a time.)  views is HOST memory in every form, copied before the call returns.
+ * stats as for the render call; with ORT_RENDER_COUNTERS, paths = the sum of add over the rect of every frame.  No workspace is
+ * needed. */
+typedef struct {
+    float    *sum_rgb;  /* 3 f32 per pixel: C, the undivided colour sum        in and out */
+    float    *m2;       /* f32: Q, the sum of squared sample luminance         in and out, may be NULL */
+    uint32_t *count;    /* u32: n, the samples this pixel has had so far       in and out */
+    uint32_t *states;   /* u32: the stream's state after sample n              in and out */
+} ort_accum_planes;     /* HOST pointers in the host forms, DEVICE pointers in the _device forms; the struct itself is host memory */
+/* host planes, map and frame (device staging is internal); synchronous */
+int ort_render_accumulate(ort_scene *scene, const ort_render_params *params, const ort_accum_planes *acc,
+                          const uint32_t *sample_map /* may be NULL */, float *out_rgb /* may be NULL */, ort_stats *stats);
+int ort_render_accumulate_device(ort_scene *scene, const ort_render_params *params, const ort_accum_planes *acc,
+                                 const void *d_sample_map, void *d_out_rgb, void *hip_stream, ort_stats *stats);
+/* view_count frames of every plane, of the map and of out_rgb, view-major */
+int ort_render_views_accumulate(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
+                                const ort_accum_planes *acc, const uint32_t *sample_map /* may be NULL */,
+                                float *out_rgb /* may be NULL */, ort_stats *stats);
+int ort_render_views_accumulate_device(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
+                                       const ort_accum_planes *acc, const void *d_sample_map, void *d_out_rgb, void *hip_stream,
+                                       ort_stats *stats);
 
 /* ---- first-hit feature renders: albedo, normal, depth, coverage and id planes of the camera -----
  * The noise-free guide planes a denoiser wants next to the colour: what the camera's own samples see FIRST.  A pass of its own on

@@ -129,6 +129,11 @@ class LightGroups(C.Structure):
     _fields_ = [("group_of_material", C.c_void_p), ("material_count", C.c_uint32), ("group_count", C.c_uint32)]
 
 
+class AccumPlanes(C.Structure):
+    """ort_accum_planes: the caller's planes of an accumulating render (ort_render_accumulate), read and written; m2 may be null."""
+    _fields_ = [("sum_rgb", C.c_void_p), ("m2", C.c_void_p), ("count", C.c_void_p), ("states", C.c_void_p)]
+
+
 FEATURE_PLANES = ("albedo", "normal", "depth", "hits", "ids", "states")   # render_features()'s want=
 
 
@@ -161,7 +166,8 @@ EXPORTS = [
     "ort_render_features", "ort_render_features_device", "ort_render_views_features", "ort_render_views_features_device",
     "ort_render_light_groups", "ort_render_light_groups_device", "ort_render_views_light_groups",
     "ort_render_views_light_groups_device",
-    "ort_render_sample_map", "ort_render_sample_map_device", "ort_render_views_sample_map", "ort_render_views_sample_map_device"]
+    "ort_render_sample_map", "ort_render_sample_map_device", "ort_render_views_sample_map", "ort_render_views_sample_map_device",
+    "ort_render_accumulate", "ort_render_accumulate_device", "ort_render_views_accumulate", "ort_render_views_accumulate_device"]
 
 _lib = None
 
@@ -232,6 +238,8 @@ def lib():
                 ("ort_render_views_light_groups", [vp, C.POINTER(RenderParams), C.POINTER(LightGroups), vp, C.c_uint32, vp, vp, vp, stats]),
                 ("ort_render_sample_map", [vp, C.POINTER(RenderParams), vp, vp, vp, vp, stats]),
                 ("ort_render_views_sample_map", [vp, C.POINTER(RenderParams), vp, C.c_uint32, vp, vp, vp, vp, stats]),
+                ("ort_render_accumulate", [vp, C.POINTER(RenderParams), C.POINTER(AccumPlanes), vp, vp, stats]),
+                ("ort_render_views_accumulate", [vp, C.POINTER(RenderParams), vp, C.c_uint32, C.POINTER(AccumPlanes), vp, vp, stats]),
                 ("ort_render_features", [vp, C.POINTER(RenderParams), C.POINTER(FeaturePlanes), stats]),
                 ("ort_render_views_features", [vp, C.POINTER(RenderParams), vp, C.c_uint32, C.POINTER(FeaturePlanes), stats]),
                 ("ort_raycast", [vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
@@ -710,6 +718,57 @@ class Scene:
         views = _views(cameras, seeds)
         return self._sample_map_device(views, params, (d_map, d_rgb, d_m2, d_states), stream, want_stats)
 
+    # -- accumulating renders: a frame's samples continued across calls ---------------------------
+    def _accumulate_host(self, views, acc, add, seed, cap, rect, rr, counters, use_m2, out):
+        if not isinstance(acc, Accumulator) or acc.views != (None if views is None else len(views)):
+            raise ValueError("acc must be an Accumulator of %s" % ("one frame (views=None)" if views is None else "%d views" % len(views)))
+        shape = _lead(views) + (acc.height, acc.width)
+        if np.ndim(add) == 0:   # the same count for every pixel: no map, the cap is the count
+            smap, cap = None, int(add) if cap is None else cap
+        else:
+            smap = self._sample_map(add, shape)
+            cap = min(max(int(smap.max()) if smap.size else 1, 1), 1 << 24) if cap is None else cap
+        if out is not None and not _is_plane(out, shape + (3,), "<f4"):
+            raise ValueError("out must be a C-contiguous float32 array of shape %s" % (shape + (3,),))
+        p = self.params(acc.width, acc.height, cap, seed, "pixel", 0, rect, rr, counters)
+        planes = acc._struct(use_m2)
+        tail = [C.byref(planes), None if smap is None else smap.ctypes.data, None if out is None else out.ctypes.data]
+        return self._pixel_jobs("accumulate", views, False, p, [], tail)
+
+    def _accumulate_device(self, views, params, d_sum, d_count, d_states, d_m2, d_map, d_rgb, stream, want_stats):
+        planes = AccumPlanes(d_sum or None, d_m2 or None, d_count or None, d_states or None)
+        return self._pixel_jobs("accumulate", views, True, params, [], [C.byref(planes), _ptr(d_map), _ptr(d_rgb)], stream, want_stats)
+
+    def render_accumulate(self, acc, add, seed, cap=None, rect=None, rr=0.8, counters=False, use_m2=True, out=None):
+        """Continue the frame that acc (an Accumulator) holds: every pixel of rect takes up to `add` more samples of ITS OWN
+        stream, from where its last call left it, and acc's planes -- the undivided colour sums, the sums of squared sample
+        luminance, the sample counts, the streams' states -- are updated in place.  After any split into calls the planes hold
+        the bits of the single call, so acc.rgb() is render(policy="pixel")'s frame at the total count (include/ort.h gives the
+        contract).  add: an integer, the same for every pixel, or an (H, W) map of integers as render_sample_map takes it, cut
+        at cap (by default the map's largest value); a pixel never passes 1 << 24 samples.  A fresh Accumulator starts the
+        frame.  use_m2=False leaves acc.m2 out of the call; out: an (H, W, 3) float32 array that receives sum / count of the
+        pixels that took samples in this call (the others keep what it held).  Returns the stats dict."""
+        return self._accumulate_host(None, acc, add, seed, cap, rect, rr, counters, use_m2, out)
+
+    def render_accumulate_device(self, params, d_sum, d_count, d_states, d_m2=0, d_map=0, d_rgb=0, stream=None, want_stats=False):
+        """The same on the device's own planes (raw device pointers, e.g. torch tensors' data_ptr(): (H, W, 3) float32 sums,
+        (H, W) uint32 counts -- or int32 holding the same words -- and states, and where a pointer is given (H, W) float32 m2, the
+        (H, W) map and the (H, W, 3) frame).  params: Scene.params(..., policy="pixel"), its spp the cap on what this call adds.
+        Enqueued on stream; waits only when want_stats (returns the stats dict), so successive calls on one stream chain
+        passes on planes that never visit the host."""
+        return self._accumulate_device(None, params, d_sum, d_count, d_states, d_m2, d_map, d_rgb, stream, want_stats)
+
+    def render_views_accumulate(self, cameras, seeds, acc, add, cap=None, rect=None, rr=0.8, counters=False, use_m2=True, out=None):
+        """render_accumulate for a batch of views in one launch (cameras, seeds as render_views; acc an Accumulator of V views,
+        add an integer or a (V, H, W) map, out (V, H, W, 3)): frame v is what render_accumulate gives with seed seeds[v] if the
+        scene's camera were cameras[v].  Returns the stats dict."""
+        return self._accumulate_host(_views(cameras, seeds), acc, add, 0, cap, rect, rr, counters, use_m2, out)
+
+    def render_views_accumulate_device(self, params, cameras, seeds, d_sum, d_count, d_states, d_m2=0, d_map=0, d_rgb=0, stream=None,
+                                       want_stats=False):
+        """The same with every plane on the device, V frames each, view-major.  params.seed is ignored."""
+        return self._accumulate_device(_views(cameras, seeds), params, d_sum, d_count, d_states, d_m2, d_map, d_rgb, stream, want_stats)
+
     # -- first-hit feature renders: albedo, normal, depth, coverage and id planes ---------------
     @staticmethod
     def _feature_planes(shape, want, out):
@@ -1001,6 +1060,56 @@ class Scene:
         _check(lib().ort_tiled_raytrace_batch(self.handle, out.ctypes.data, width, height, jobs.ctypes.data, len(jobs),
                                               rr, finals.ctypes.data, st))
         return finals, stats()
+
+
+class Accumulator:
+    """The host planes of an accumulating render (Scene.render_accumulate): sum_rgb (H, W, 3) float32, the undivided colour
+    sums; m2 (H, W) float32, the sums of squared sample luminance; count (H, W) uint32, the samples each pixel has had; states
+    (H, W) uint32, the streams' states.  views=V: V frames of each, (V, H, W[, 3]).  A fresh one has count == 0 everywhere,
+    which is all the call reads of a pixel that has had no sample.  save / load: the checkpoint of a frame."""
+
+    def __init__(self, width, height, views=None):
+        self.width, self.height, self.views = int(width), int(height), None if views is None else int(views)
+        shape = (() if views is None else (self.views,)) + (self.height, self.width)
+        self.sum_rgb = np.zeros(shape + (3,), "<f4")
+        self.m2 = np.zeros(shape, "<f4")
+        self.count = np.zeros(shape, "<u4")
+        self.states = np.zeros(shape, "<u4")
+
+    def _struct(self, use_m2=True):
+        shape = self.count.shape
+        for a, sh, dt in ((self.sum_rgb, shape + (3,), "<f4"), (self.m2, shape, "<f4"), (self.count, shape, "<u4"), (self.states, shape, "<u4")):
+            if not _is_plane(a, sh, dt):
+                raise ValueError("Accumulator: every plane must be a C-contiguous array, expected shape %s dtype %s" % (sh, dt))
+        return AccumPlanes(self.sum_rgb.ctypes.data, self.m2.ctypes.data if use_m2 else None, self.count.ctypes.data, self.states.ctypes.data)
+
+    def rgb(self, fill=0.0):
+        """sum_rgb / count in float32, component by component -- the call's own out_rgb; fill where count == 0"""
+        out = np.full(self.sum_rgb.shape, fill, "<f4")
+        had = self.count != 0
+        with np.errstate(all="ignore"):
+            out[had] = self.sum_rgb[had] / self.count[had].astype("<f4")[:, None]
+        return out
+
+    def save(self, path):
+        """the frame as it stands, into one .npz file (np.savez): Accumulator.load(path) continues it"""
+        with open(path, "wb") as f:
+            np.savez(f, sum_rgb=self.sum_rgb, m2=self.m2, count=self.count, states=self.states)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            count = z["count"]
+            if count.ndim not in (2, 3) or count.dtype != np.dtype("<u4"):
+                raise ValueError("%s: count must be (H, W) or (V, H, W) uint32, got %s %s" % (path, count.shape, count.dtype))
+            acc = cls(count.shape[-1], count.shape[-2], None if count.ndim == 2 else count.shape[0])
+            for name in ("sum_rgb", "m2", "count", "states"):
+                a = z[name]
+                have = getattr(acc, name)
+                if a.shape != have.shape or a.dtype != have.dtype:
+                    raise ValueError("%s: %s must be %s %s, got %s %s" % (path, name, have.shape, have.dtype, a.shape, a.dtype))
+                have[...] = a
+        return acc
 
 
 def _adaptive(min_spp, max_spp, check_every, tolerance, floor):

@@ -653,6 +653,31 @@ static int render_sample_map_common(ort_scene *s, const ort_render_params *p, co
         [&](const ort_render_params &q, ort::RenderCall c) { c.sample_map = sample_map; return run_render(s, &q, c, out_rgb, nullptr, out_m2, states); });
 }
 
+/* Accumulating renders: render_sample_map_common's order with acc where the map stands.  Nulls: the views (the views form); no plane
+   is required before the params are judged, out_rgb being optional.  Own checks: spp -- the cap on what one call adds -- above
+   1 << 24, a null acc or a null sum_rgb, count or states plane in it, the alignment of every plane and of the map.  Neither the map's
+   values nor the planes' are ever judged: the lanes cut every count and take every sum and state as it stands */
+static int render_accumulate_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool batch, bool host,
+                                    const ort_accum_planes *acc, const void *sample_map, void *out_rgb, void *stream, ort_stats *stats) {
+    static const PixelJobKind kind = {"the accumulating render continues one-pixel jobs: it needs the PIXEL policy", "the accumulating render is not sharded",
+                                      "the accumulating render has no packed framebuffer"};
+    return render_pixel_jobs(
+        kind, s, p, views, view_count, batch, host, stream, stats,
+        [&] { return batch && !views ? fail(ORT_ERR_INVALID, "null views") : ORT_OK; },
+        [](ort_render_params *) {},
+        [&](const ort_render_params &q) {
+            if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp (the cap on the samples a call adds to a pixel) must be <= 1 << 24: a sample count must be exact in float");
+            if (!acc) return fail(ORT_ERR_INVALID, "null acc (the accumulation planes)");
+            if (!acc->sum_rgb || !acc->count || !acc->states) return fail(ORT_ERR_INVALID, host ? "null sum_rgb, count or states plane" : "null device sum_rgb, count or states plane");
+            return check_ptrs({{acc->sum_rgb, true, 4}, {acc->m2, false, 4}, {acc->count, true, 4}, {acc->states, true, 4}, {sample_map, false, 4}, {out_rgb, false, 4}}, "", "",
+                              "sum_rgb, m2, count, states, sample_map and out_rgb must be 4-byte aligned");
+        },
+        [&](const ort_render_params &q, ort::RenderCall c) {
+            c.sample_map = sample_map; c.acc_sum = acc->sum_rgb;
+            return run_render(s, &q, c, out_rgb, acc->count, acc->m2, acc->states);
+        });
+}
+
 /* First-hit feature renders.  Nulls: the planes struct, all five feature planes, the views.  rr is not the caller's to set either.  Own
    checks: spp above 1 << 24, the planes' alignment.  The launch is device_render_features, not run_render */
 static int render_features_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool batch, bool host,
@@ -807,6 +832,10 @@ int ort_render_sample_map(ort_scene *s, const ort_render_params *p, const uint32
 int ort_render_sample_map_device(ort_scene *s, const ort_render_params *p, const void *d_sample_map, void *d_out_rgb, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_sample_map_common(s, p, nullptr, 1, false, false, d_sample_map, d_out_rgb, d_out_m2, d_final_states, hip_stream, stats); }); }
 int ort_render_views_sample_map(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const uint32_t *sample_map, float *out_rgb, float *out_m2, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_sample_map_common(s, p, views, view_count, true, true, sample_map, out_rgb, out_m2, final_states, nullptr, stats); }); }
 int ort_render_views_sample_map_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const void *d_sample_map, void *d_out_rgb, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_sample_map_common(s, p, views, view_count, true, false, d_sample_map, d_out_rgb, d_out_m2, d_final_states, hip_stream, stats); }); }
+int ort_render_accumulate(ort_scene *s, const ort_render_params *p, const ort_accum_planes *acc, const uint32_t *sample_map, float *out_rgb, ort_stats *stats) { return guarded([&]() { return render_accumulate_common(s, p, nullptr, 1, false, true, acc, sample_map, out_rgb, nullptr, stats); }); }
+int ort_render_accumulate_device(ort_scene *s, const ort_render_params *p, const ort_accum_planes *acc, const void *d_sample_map, void *d_out_rgb, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_accumulate_common(s, p, nullptr, 1, false, false, acc, d_sample_map, d_out_rgb, hip_stream, stats); }); }
+int ort_render_views_accumulate(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_accum_planes *acc, const uint32_t *sample_map, float *out_rgb, ort_stats *stats) { return guarded([&]() { return render_accumulate_common(s, p, views, view_count, true, true, acc, sample_map, out_rgb, nullptr, stats); }); }
+int ort_render_views_accumulate_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_accum_planes *acc, const void *d_sample_map, void *d_out_rgb, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_accumulate_common(s, p, views, view_count, true, false, acc, d_sample_map, d_out_rgb, hip_stream, stats); }); }
 int ort_render_features(ort_scene *s, const ort_render_params *p, const ort_feature_planes *planes, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, nullptr, 1, false, true, planes, nullptr, stats); }); }
 int ort_render_features_device(ort_scene *s, const ort_render_params *p, const ort_feature_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, nullptr, 1, false, false, planes, hip_stream, stats); }); }
 int ort_render_views_features(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_feature_planes *planes, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, views, view_count, true, true, planes, nullptr, stats); }); }

@@ -281,6 +281,10 @@ static int launch_sample_map(DeviceScene *, const LaunchPlan &pl, const SceneVie
     ort_launch_render_sample_map(plan_variant(pl), pl.grid, stream, sv, hot);
     return ORT_OK;
 }
+static int launch_accumulate(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
+    ort_launch_render_accumulate(plan_variant(pl), pl.grid, stream, sv, hot);
+    return ORT_OK;
+}
 
 /* What launches each of the built kernels (kBuiltKernels, ort_plan.h), in that list's order: a kernel of this unit, which its
    entry here instantiates, or the host function that launches what another family is made of */
@@ -299,6 +303,7 @@ constexpr Launcher five(bool d) { return {{KF_FIVE, false, d, true, true, false}
 constexpr Launcher adaptive(bool c, bool d, bool t) { return {{KF_ADAPTIVE, c, d, t, true, false}, nullptr, launch_adaptive}; }
 constexpr Launcher groups(bool c, bool d, bool t) { return {{KF_GROUPS, c, d, t, true, false}, nullptr, launch_groups}; }
 constexpr Launcher sample_map(bool c, bool d, bool t) { return {{KF_SAMPLE_MAP, c, d, t, true, false}, nullptr, launch_sample_map}; }
+constexpr Launcher accumulate(bool c, bool d, bool t) { return {{KF_ACCUM, c, d, t, true, false}, nullptr, launch_accumulate}; }
 constexpr Launcher kLaunchers[] = {
     {{KF_WAVEFRONT, false, false, false, false, false}, nullptr, launch_wavefront<false>},
     {{KF_WAVEFRONT, true, false, false, false, false}, nullptr, launch_wavefront<true>},
@@ -316,6 +321,8 @@ constexpr Launcher kLaunchers[] = {
     groups(true, false, false), groups(true, false, true), groups(true, true, false), groups(true, true, true),
     sample_map(false, false, false), sample_map(false, false, true), sample_map(false, true, false), sample_map(false, true, true),
     sample_map(true, false, false), sample_map(true, false, true), sample_map(true, true, false), sample_map(true, true, true),
+    accumulate(false, false, false), accumulate(false, false, true), accumulate(false, true, false), accumulate(false, true, true),
+    accumulate(true, false, false), accumulate(true, false, true), accumulate(true, true, false), accumulate(true, true, true),
 };
 constexpr bool launchers_match(size_t i = 0) { return i == kBuiltKernelCount || (kLaunchers[i].variant == kBuiltKernels[i] && launchers_match(i + 1)); }
 static_assert(sizeof(kLaunchers) / sizeof(kLaunchers[0]) == kBuiltKernelCount && launchers_match(),
@@ -500,9 +507,10 @@ static int print_util_diag(const DeviceScene *d, std::string *err) {
     return ORT_OK;
 }
 
-/* The camera render call, plain, (c.ad) adaptive, (c.groups) split by light group or (c.sample_map) cut by the caller's map.  What
-   runs, on which grid and with which thresholds is plan_render's, plan_render_adaptive's, plan_render_groups' or
-   plan_render_sample_map's decision (ort_plan.h), and what the RenderView says besides pointers is render_view's (ort_setup.h); this
+/* The camera render call, plain, (c.ad) adaptive, (c.groups) split by light group, (c.sample_map) cut by the caller's map or
+   (c.acc_sum) continued from the caller's planes.  What
+   runs, on which grid and with which thresholds is plan_render's, plan_render_adaptive's, plan_render_groups',
+   plan_render_sample_map's or plan_render_accumulate's decision (ort_plan.h), and what the RenderView says besides pointers is render_view's (ort_setup.h); this
    is the plumbing around them: settle the previous call, plan, staging, views, buffers, launch, combine, finish */
 int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c, void *out_rgb, void *out_spp, void *out_m2, void *states, std::string *err) {
     DeviceScene *d = scene->dev;
@@ -517,7 +525,8 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
 
     SceneView sv = scene_view(scene, d);
     const SceneTraits traits = scene_traits(scene, d);
-    const LaunchPlan pl = c.sample_map ? plan_render_sample_map(traits, *p, d->knobs, view_count)
+    const LaunchPlan pl = c.acc_sum ? plan_render_accumulate(traits, *p, d->knobs, view_count)
+                          : c.sample_map ? plan_render_sample_map(traits, *p, d->knobs, view_count)
                           : c.groups ? plan_render_groups(traits, *p, d->knobs, view_count)
                           : c.ad ? plan_render_adaptive(traits, *p, d->knobs, view_count)
                                : plan_render(traits, *p, c.jobs != nullptr, c.job_count, /* w5_layout_ok */ true, d->knobs, view_count);
@@ -535,17 +544,20 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     /* the planes as the lanes see them: the caller's device pointers, or the scene's staging buffers holding the caller's words.
        view_count frames, view-major, or the packed framebuffer; the 4-byte planes stage where the radiance queries' do */
     const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
-    Plane planes[6] = {{out_rgb, &d->staging, rv.packed_out ? (size_t)rv.my_blocks * 768u : pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u, nullptr},
+    Plane planes[7] = {{out_rgb, &d->staging, rv.packed_out ? (size_t)rv.my_blocks * 768u : pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u, nullptr},
                        {out_m2, &d->query_stage[4], pixels * 4u, nullptr}, {states, &d->query_stage[5], pixels * 4u, nullptr},
                        {c.out_groups, &d->query_stage[0], pixels * 12u * (c.groups ? c.groups->group_count : 0u), nullptr},
                        /* the one plane that is read and not written: staged in with the others, never out */
-                       {const_cast<void *>(c.sample_map), &d->query_stage[1], pixels * 4u, nullptr}};
-    if ((rc = stage_planes_in(planes, 6, c.host, stream, err))) return rc;
+                       {const_cast<void *>(c.sample_map), &d->query_stage[1], pixels * 4u, nullptr},
+                       /* the accumulating render's colour sums, staged both ways as its count (out_spp), m2 and states are */
+                       {c.acc_sum, &d->query_stage[2], pixels * 12u, nullptr}};
+    if ((rc = stage_planes_in(planes, 7, c.host, stream, err))) return rc;
     rv.out = (float *)planes[0].dev;
     rv.ad_spp = (uint32_t *)planes[1].dev;
     rv.ad_m2 = (float *)planes[2].dev;
     rv.final_states = (uint32_t *)planes[3].dev;
     rv.sample_map = (const uint32_t *)planes[5].dev;
+    rv.acc_sum = (float *)planes[6].dev;
     if (c.groups) { /* the group table, the scene's copy of it on its way to the device; the previous call was settled above */
         d->group_tab_host.assign(c.groups->group_of_material, c.groups->group_of_material + c.groups->material_count);
         if ((rc = d->group_tab.ensure(d->group_tab_host.size(), err))) return rc;
@@ -596,7 +608,7 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     }
     if ((rc = end_kernels(d, c.stats != nullptr, stream, err))) return rc;
 
-    if ((rc = stage_planes_out(planes, 5, c.host, stream, err))) return rc;
+    if ((rc = stage_planes_out(planes, 5, c.host, stream, err)) || (rc = stage_planes_out(planes + 6, 1, c.host, stream, err))) return rc;
     if (c.job_states) ORT_HIP(hipMemcpyAsync(c.job_states, d->states.p, (size_t)c.job_count * 4u, hipMemcpyDeviceToHost, stream));
     /* every synchronous form of the call checks the tripwire before it returns (the fire-and-forget device form, stats == NULL,
        cannot without a sync: the next call on the scene does; bench.py asks for stats) */

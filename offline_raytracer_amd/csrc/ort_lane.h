@@ -158,6 +158,11 @@ struct RenderView {
        where its colour is in out: the caller's sample count for that pixel, read once where its job is drawn and cut at spp
        above, the cap.  ad_m2 and final_states (each may be null) are planes as the adaptive render's */
     const uint32_t *sample_map;
+    /* accumulating renders (ort_render_accumulate; the pt_accumulate kernels): the sample-map render's fields, sample_map null
+       where every pixel is asked for the cap, and four planes of the caller's that are read AND written: acc_sum, three floats a
+       pixel, the undivided colour sum; ad_spp, the samples a pixel has had; ad_m2 (may be null) and final_states as above.  out
+       (may be null) is written alone */
+    float *acc_sum;
 };
 
 /* ---- the order in which a CHUNK render issues its jobs ----------------------------------------------------------
@@ -262,6 +267,7 @@ void ort_launch_w5(const ort::KernelVariant &v, unsigned int grid, hipStream_t s
 void ort_launch_render_adaptive(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot); /* KF_ADAPTIVE: ort_kernels_render_adaptive.hip */
 void ort_launch_render_groups(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);   /* KF_GROUPS: ort_kernels_render_adaptive.hip */
 void ort_launch_render_sample_map(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot); /* KF_SAMPLE_MAP: ort_kernels_render_adaptive.hip */
+void ort_launch_render_accumulate(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot); /* KF_ACCUM: ort_kernels_render_adaptive.hip */
 void ort_launch_radiance_adaptive(const ort::QueryPlan &pl, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);                    /* ort_kernels_adaptive.hip */
 void ort_launch_irradiance(const ort::QueryPlan &pl, bool adaptive, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);            /* ort_kernels_irradiance.hip */
 #endif
@@ -442,6 +448,17 @@ constexpr uint32_t LF_GROUPS = 1u << 9;
    writes the mean over n and, where asked for, that sum and the stream's state.  Everything of it sits under
    if constexpr (SPPMAP) */
 constexpr uint32_t LF_SPPMAP = 1u << 16;
+/* ACCUM: accumulating renders (ort_render_accumulate; with SPPMAP, whose job draw and job end it extends): a pixel's samples
+   continue across calls.  The caller's planes hold, per pixel, the UNDIVIDED colour sum C (rv.c->acc_sum), the sum of squared
+   sample luminance Q (ad_m2, may be null), the samples taken so far n0 (ad_spp) and the stream's state after sample n0
+   (final_states).  The lane that draws the job reads n0 beside the map word (a null map: the cap stands in for it) and forms
+   add = min(asked, spp_u, (1 << 24) - min(n0, 1 << 24)); add == 0 is SPPMAP's empty job.  n0 == 0: the job_seed start, C = Q = +0,
+   nothing else of the planes read.  n0 > 0: the stream starts at the stored state (0 taken as 1: a zero xorshift state never
+   leaves zero), C and Q at the stored sums + (+0), which is what the first added colour makes of them.  The job's end stores
+   C, Q, n0 + add, the state and, where asked for (out), C / (float)(n0 + add); n0 is read again there, so it is not live
+   through the traversal loop.  A pixel's words are one lane's for the length of its job: no atomics.  Everything of it sits
+   under if constexpr (ACCUM) */
+constexpr uint32_t LF_ACCUM = 1u << 17;
 /* the walk's own options */
 constexpr uint32_t LF_TREELET = 1u << 10;     /* traverse: the top of the binary tree is read from the LDS tables (with TABS, never WIDE) */
 constexpr uint32_t LF_ANNOUNCE = 1u << 11;    /* traverse asks for a finished ray's PrimInfo (announce_winner); resolve_hit then finds it ANNOUNCED */
@@ -458,7 +475,7 @@ constexpr uint32_t LF_OF_PROLOGUE = LF_COUNTERS | LF_TABS | LF_HAS_EXCL;
 constexpr uint32_t LF_OF_BEGIN_RAY = LF_COUNTERS | LF_TABS;
 constexpr uint32_t LF_OF_TRAVERSE = LF_COUNTERS | LF_TREELET | LF_ANNOUNCE | LF_WIDE;
 constexpr uint32_t LF_OF_RESOLVE_HIT = LF_COUNTERS | LF_TABS | LF_ANNOUNCE | LF_WIDE;
-constexpr uint32_t LF_OF_PRODUCE_RAY = LF_COUNTERS | LF_DIFFUSE | LF_TABS | LF_IMPLICIT | LF_VIEWS | LF_RAYS | LF_ADAPT | LF_HEMI | LF_GROUPS | LF_SPPMAP;
+constexpr uint32_t LF_OF_PRODUCE_RAY = LF_COUNTERS | LF_DIFFUSE | LF_TABS | LF_IMPLICIT | LF_VIEWS | LF_RAYS | LF_ADAPT | LF_HEMI | LF_GROUPS | LF_SPPMAP | LF_ACCUM;
 constexpr uint32_t LF_OF_LANE = LF_OF_PRODUCE_RAY | LF_WIDE; /* pt_lane ... radiance_lane: a job's flavour */
 /* ... and, from a lane's flavour f, the words of the three steps of its loop: begin_ray (and a prologue in its place); traverse,
    where finished rays announce their winners and the top of the binary tree comes from the LDS tables if there are any; and the
@@ -471,13 +488,14 @@ constexpr uint32_t resolve_of(uint32_t f) { return (f & (LF_COUNTERS | LF_TABS |
 constexpr bool flavour_ok(uint32_t f, uint32_t reads) {
     const bool IMPLICIT = f & LF_IMPLICIT, WIDE = f & LF_WIDE, VIEWS = f & LF_VIEWS, RAYS = f & LF_RAYS, ADAPT = f & LF_ADAPT;
     const bool HEMI = f & LF_HEMI, GROUPS = f & LF_GROUPS, TREELET = f & LF_TREELET, EXACT_ORDER = f & LF_EXACT_ORDER;
-    const bool SPPMAP = f & LF_SPPMAP;
+    const bool SPPMAP = f & LF_SPPMAP, ACCUM = f & LF_ACCUM;
     return (f & ~reads) == 0u
         && (!RAYS || (IMPLICIT && !VIEWS))                        /* a caller's ray array is an implicit job space of its own */
         && (!ADAPT || (IMPLICIT && (RAYS || VIEWS)))              /* the adaptive rule is built for the radiance queries and for one-pixel jobs of a batch of views */
         && (!HEMI || RAYS)                                        /* the hemisphere draw starts a sample of a radiance query's job */
         && (!GROUPS || (IMPLICIT && VIEWS && !RAYS && !ADAPT))    /* the group sums are built for plain one-pixel jobs of a batch of views */
         && (!SPPMAP || (IMPLICIT && VIEWS && !RAYS && !ADAPT && !GROUPS)) /* the sample map cuts plain one-pixel jobs of a batch of views */
+        && (!ACCUM || SPPMAP)                                     /* accumulation continues the sample map's jobs */
         && (!WIDE || !(VIEWS || RAYS || ADAPT || HEMI || GROUPS || SPPMAP || TREELET)) /* the 4-wide tree serves the single frame's plain loop, and has no treelet */
         && (!EXACT_ORDER || !(f & (LF_FINITE_RAY | LF_FROM_TAB))); /* the exact walk reads HBM */
 }
@@ -1199,13 +1217,14 @@ ORT_D bool adaptive_stop(V3 C, float Q, uint32_t n, float tolerance, float lum_f
     return vm <= thr * thr;
 }
 
-template <uint32_t F> /* IMPLICIT ... SPPMAP: at their names, LF_IMPLICIT ... LF_SPPMAP */
+template <uint32_t F> /* IMPLICIT ... ACCUM: at their names, LF_IMPLICIT ... LF_ACCUM */
 ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, Prof &pr,
                        float *focal_cache = nullptr, int focal_stride = 0, uint32_t spp_u = 0, uint32_t *late_flag = nullptr, bool no_new_job = false,
                        unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
     static_assert(flavour_ok(F, LF_OF_PRODUCE_RAY), "see flavour_ok");
     constexpr bool COUNTERS = F & LF_COUNTERS, DIFFUSE = F & LF_DIFFUSE, TABS = F & LF_TABS, IMPLICIT = F & LF_IMPLICIT, VIEWS = F & LF_VIEWS;
     constexpr bool RAYS = F & LF_RAYS, ADAPT = F & LF_ADAPT, HEMI = F & LF_HEMI, GROUPS = F & LF_GROUPS, SPPMAP = F & LF_SPPMAP;
+    constexpr bool ACCUM = F & LF_ACCUM;
     /* VIEWS: unused; every lane reads its view's camera where it needs it (load_view_camera) */
     const V3 cam_p = mk(sv.cam[0], sv.cam[1], sv.cam[2]);
     const V3 cam_x = mk(sv.cam[3], sv.cam[4], sv.cam[5]);
@@ -1316,7 +1335,17 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
             if constexpr (ADAPT) job_ends = P.ps == PS_SAMPLE && (P.sample == job_spp || A->next == 0u); /* ... or the rule said stop */
             if (job_ends) {
                 /* ray.cpp:1428 */
-                V3 o = divs(P.color, (float)(ADAPT ? P.sample : job_spp));
+                V3 o;
+                if constexpr (ACCUM) { /* the pixel's words, sums first; the mean over all its samples, this call's and the earlier ones' */
+                    const uint32_t px = P.pxy & 0xffffu, py = P.pxy >> 16;
+                    const size_t at = plane_index(rv, P.job_index, px, py);
+                    const uint32_t total = rv.c->ad_spp[at] + job_spp; /* n0 + add <= 1 << 24: exact in float */
+                    float *q = rv.c->acc_sum + 3u * at;
+                    q[0] = P.color.x; q[1] = P.color.y; q[2] = P.color.z;
+                    rv.c->ad_spp[at] = total;
+                    o = divs(P.color, (float)total);
+                } else
+                o = divs(P.color, (float)(ADAPT ? P.sample : job_spp));
                 if constexpr (RAYS) {
                     const size_t ray = ((size_t)P.pxy << 32) | P.job_index;
                     float *p = rv.c->out + 3u * ray;
@@ -1337,6 +1366,8 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                     }
                     if (rv.c->out) { float *p = view_pixel_ptr(rv, P.job_index, 0u, px, py); p[0] = o.x; p[1] = o.y; p[2] = o.z; }
                     if (rv.c->final_states) rv.c->final_states[plane_index(rv, P.job_index, px, py)] = P.rng;
+                } else if constexpr (ACCUM) { /* the frame is an optional plane here */
+                    if (rv.c->out) { float *p = view_pixel_ptr(rv, P.job_index, 0u, px, py); p[0] = o.x; p[1] = o.y; p[2] = o.z; }
                 } else {
                 float *p;
                 if constexpr (VIEWS) p = view_pixel_ptr(rv, P.job_index, P.jyp >> 16, px, py);
@@ -1352,7 +1383,7 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 if constexpr (SPPMAP) { /* likewise, without the sample count: the caller holds it */
                     const size_t at = plane_index(rv, P.job_index, px, py);
                     if (rv.c->ad_m2) rv.c->ad_m2[at] = A->q;
-                    if (rv.c->final_states) rv.c->final_states[at] = P.rng;
+                    if (ACCUM || rv.c->final_states) rv.c->final_states[at] = P.rng; /* ACCUM: the state is a required plane */
                 }
                 if (IMPLICIT) {
                     P.ps = PS_NEED_JOB; /* a one-pixel job ends with its pixel */
@@ -1369,6 +1400,7 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 }
                 }
             }
+            [[maybe_unused]] uint32_t acc_n0 = 0u; /* ACCUM: the samples the pixel drawn in this pass has had; a pixel starts in the pass that draws its job */
             if (P.ps == PS_NEED_JOB) {
                 if (no_new_job) return false; /* ray exchange, end of the launch: this lane takes a parked path first (pt_lane_x) */
                 unsigned long long j = draw_job(rv, pool);
@@ -1433,8 +1465,16 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                     int y = (int)((rv.c->block_y0 + blk / rv.c->blocks_w) * 8u + (pin >> 3));
                     if (x < rv.c->x0 || x >= rv.c->x1 || y < rv.c->y0 || y >= rv.c->y1) continue;
                     if constexpr (SPPMAP) { /* the job's length, one word of the caller's map, cut at the cap; no samples: no job */
-                        const uint32_t asked = rv.c->sample_map[plane_index(rv, P.job_index, (uint32_t)x, (uint32_t)y)];
-                        const uint32_t n = asked < spp_u ? asked : spp_u;
+                        const size_t at = plane_index(rv, P.job_index, (uint32_t)x, (uint32_t)y);
+                        uint32_t asked;
+                        if constexpr (ACCUM) asked = rv.c->sample_map ? rv.c->sample_map[at] : spp_u;
+                        else asked = rv.c->sample_map[at];
+                        uint32_t n = asked < spp_u ? asked : spp_u;
+                        if constexpr (ACCUM) { /* ... and at what keeps the pixel's total within 1 << 24 */
+                            acc_n0 = rv.c->ad_spp[at];
+                            const uint32_t room = (1u << 24) - (acc_n0 < (1u << 24) ? acc_n0 : (1u << 24));
+                            n = n < room ? n : room;
+                        }
                         if (n == 0u) continue;
                         A->next = n;
                     }
@@ -1462,6 +1502,18 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
                 P.ps = PS_SAMPLE;
                 if constexpr (ADAPT) { A->q = 0.0f; A->next = rv.c->ad_min_spp; }
                 if constexpr (SPPMAP) A->q = 0.0f;
+                if constexpr (ACCUM) {
+                    if (acc_n0) { /* a continued pixel: its stream and its sums as the planes hold them, judged no more than a material is */
+                        const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
+                        const uint32_t state = rv.c->final_states[at];
+                        P.rng = state ? state : 1u; /* as job_seed: a zero xorshift state never leaves zero */
+                        /* + (+0): the call is chained one-sample renders whose colours are added to C, and a colour is never -0,
+                           so a -0 the caller stored is +0 after the first of them whatever it holds; every other value stands */
+                        const float *q = rv.c->acc_sum + 3u * at;
+                        P.color = mk(q[0] + 0.0f, q[1] + 0.0f, q[2] + 0.0f);
+                        if (rv.c->ad_m2) A->q = rv.c->ad_m2[at] + 0.0f;
+                    }
+                }
                 if constexpr (GROUPS) {
                     for (uint32_t g = 0; g < rv.c->group_count; ++g) {
                         float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
@@ -1882,6 +1934,7 @@ ORT_D void flush_counters(const RenderHot &rv, const Counters &c, bool all) {
 /* GROUPS: the light-group render (pt_groups): the same loop, produce_ray keeping the group sums in the output frames */
 /* SPPMAP: the sample-map render (pt_sample_map): the same loop, produce_ray cutting every job at its word of the caller's map; A
    as for ADAPT */
+/* ACCUM: the accumulating render (pt_accumulate): SPPMAP's loop, produce_ray starting a pixel from the caller's planes */
 template <uint32_t F>
 ORT_D void pt_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, float *lds_focal, const int tid,
                    const uint32_t lane_id, bool prof_on = false, unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
@@ -2422,6 +2475,24 @@ pt_sample_map(SceneView sv, RenderHot rv) {
     AdaptState *const A = reinterpret_cast<AdaptState *>(lds_adapt) + threadIdx.x;
     if (TABS) fill_tab(sv, lds_tab);
     pt_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_SPPMAP>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
+                                                                     wave_job_pool(rv, lds_pool), A);
+}
+
+/* The accumulating render (ort_render_accumulate, ort_render_views_accumulate): pt_sample_map's loop and its LDS, word for word,
+   with produce_ray's ACCUM flag on top of SPPMAP: a job starts from the pixel's words of the caller's planes and ends by storing
+   them.  The map may be null.  Built beside pt_sample_map, in ort_kernels_render_adaptive.hip alone */
+template <bool COUNTERS, bool DIFFUSE, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+pt_accumulate(SceneView sv, RenderHot rv) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ float lds_focal[3 * kBlock]; /* focal[component][lane] */
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as pt_persistent */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    static_assert(sizeof(AdaptState) == sizeof(uint2), "a lane's AdaptState is two words of LDS");
+    __shared__ uint2 lds_adapt[kBlock]; /* as pt_sample_map: add where a job is drawn, Q at the pixel's start */
+    AdaptState *const A = reinterpret_cast<AdaptState *>(lds_adapt) + threadIdx.x;
+    if (TABS) fill_tab(sv, lds_tab);
+    pt_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_SPPMAP | LF_ACCUM>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
                                                                      wave_job_pool(rv, lds_pool), A);
 }
 

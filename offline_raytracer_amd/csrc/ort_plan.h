@@ -3,7 +3,7 @@
  * ort_kernels.hip launches, with which grid and which thresholds, decided from a few facts about the uploaded scene
  * (SceneTraits), the render parameters or the ray count, and the developer knobs: plan_render for ort_render_image and
  * ort_render_views, plan_render_adaptive for ort_render_adaptive and ort_render_views_adaptive, plan_render_groups for ort_render_light_groups and
- * ort_render_views_light_groups, plan_render_sample_map for ort_render_sample_map and ort_render_views_sample_map, plan_ray_query for ort_raycast and ort_occluded, plan_radiance for ort_radiance.  Host-only and free of HIP,
+ * ort_render_views_light_groups, plan_render_sample_map for ort_render_sample_map and ort_render_views_sample_map, plan_render_accumulate for ort_render_accumulate and ort_render_views_accumulate, plan_ray_query for ort_raycast and ort_occluded, plan_radiance for ort_radiance.  Host-only and free of HIP,
  * so that tools/launch_plan.cpp and tests/test_launch_plan.py can hold the measured crossovers without a device.
  * ort_kernels.hip turns a LaunchPlan or a QueryPlan into launches and decides nothing.
  */
@@ -192,6 +192,7 @@ struct LaunchPlan {
     bool adaptive = false; /* the adaptive camera render (plan_render_adaptive): the pt_adaptive kernels <counters, diffuse, tabs> */
     bool groups = false;   /* the light-group render (plan_render_groups): the pt_groups kernels <counters, diffuse, tabs> */
     bool sample_map = false; /* the sample-map render (plan_render_sample_map): the pt_sample_map kernels <counters, diffuse, tabs> */
+    bool accumulate = false; /* the accumulating render (plan_render_accumulate): the pt_accumulate kernels <counters, diffuse, tabs> */
     uint32_t view_count = 1;
     unsigned long long view_jobs = 0; /* jobs of one view (job_count / view_count) */
     unsigned int grid = 1;
@@ -398,10 +399,20 @@ inline LaunchPlan plan_render_sample_map(const SceneTraits &t, const ort_render_
     return pl;
 }
 
+/* The launch of the accumulating render (ort_render_accumulate, ort_render_views_accumulate; the pt_accumulate kernels):
+   plan_render_sample_map's launch in every field, for kernels that start a pixel from the caller's planes.  Neither the map nor the
+   planes' counts can be read here, so the job space again holds every pixel under the rect */
+inline LaunchPlan plan_render_accumulate(const SceneTraits &t, const ort_render_params &p, const Knobs &kn, uint32_t view_count = 1) {
+    LaunchPlan pl = plan_render_sample_map(t, p, kn, view_count);
+    pl.sample_map = false;
+    pl.accumulate = true;
+    return pl;
+}
+
 /* ---- the kernels that are built ------------------------------------------------------------------------------------------ */
 /* A render kernel by name: its family and its template arguments.  A bool its family's kernels do not take is stated as what
    they are compiled with (the ray exchange and the five-waves build: tabs and implicit; wavefront mode: none of the four) */
-enum KernelFamily : int { KF_NONE = 0, KF_WAVEFRONT, KF_LOOP, KF_LOOP_VIEWS, KF_EXCHANGE, KF_FIVE, KF_ADAPTIVE, KF_GROUPS, KF_SAMPLE_MAP };
+enum KernelFamily : int { KF_NONE = 0, KF_WAVEFRONT, KF_LOOP, KF_LOOP_VIEWS, KF_EXCHANGE, KF_FIVE, KF_ADAPTIVE, KF_GROUPS, KF_SAMPLE_MAP, KF_ACCUM };
 struct KernelVariant {
     KernelFamily family;
     bool counters, diffuse, tabs, implicit, wide;
@@ -410,22 +421,22 @@ constexpr bool operator==(const KernelVariant &a, const KernelVariant &b) {
     return a.family == b.family && a.counters == b.counters && a.diffuse == b.diffuse && a.tabs == b.tabs && a.implicit == b.implicit && a.wide == b.wide;
 }
 
-/* the variant a plan asks for.  A plan that claims two families at once, or the stopping rule, the group sums or the sample map
-   outside a PIXEL batch of views, names none */
+/* the variant a plan asks for.  A plan that claims two families at once, or the stopping rule, the group sums, the sample map or
+   the accumulation outside a PIXEL batch of views, names none */
 inline KernelVariant plan_variant(const LaunchPlan &pl) {
-    if ((int)pl.wavefront + (int)pl.exchange + (int)pl.five + (int)pl.views > 1 || (int)pl.adaptive + (int)pl.groups + (int)pl.sample_map > 1 ||
-        ((pl.adaptive || pl.groups || pl.sample_map) && !(pl.views && pl.mode == PLAN_JOBS_PIXEL)))
+    if ((int)pl.wavefront + (int)pl.exchange + (int)pl.five + (int)pl.views > 1 || (int)pl.adaptive + (int)pl.groups + (int)pl.sample_map + (int)pl.accumulate > 1 ||
+        ((pl.adaptive || pl.groups || pl.sample_map || pl.accumulate) && !(pl.views && pl.mode == PLAN_JOBS_PIXEL)))
         return {KF_NONE, false, false, false, false, false};
     if (pl.wavefront) return {KF_WAVEFRONT, pl.counters, false, false, false, false};
     if (pl.exchange) return {KF_EXCHANGE, pl.counters, pl.diffuse, true, true, false};
     if (pl.five) return {KF_FIVE, false, pl.diffuse, true, true, false};
-    return {pl.adaptive ? KF_ADAPTIVE : pl.groups ? KF_GROUPS : pl.sample_map ? KF_SAMPLE_MAP : pl.views ? KF_LOOP_VIEWS : KF_LOOP, pl.counters, pl.diffuse, pl.tabs, pl.implicit, pl.wide};
+    return {pl.adaptive ? KF_ADAPTIVE : pl.groups ? KF_GROUPS : pl.sample_map ? KF_SAMPLE_MAP : pl.accumulate ? KF_ACCUM : pl.views ? KF_LOOP_VIEWS : KF_LOOP, pl.counters, pl.diffuse, pl.tabs, pl.implicit, pl.wide};
 }
 
 /* All that is built, and every one of them costs its share of minutes of compile time: ort_kernels.hip instantiates the first
    four families (its table of launchers is held against this list at compile time), ort_kernels_w5.hip the fifth,
-   ort_kernels_render_adaptive.hip the sixth, the seventh and the eighth.  plan_render, plan_render_adaptive, plan_render_groups and
-   plan_render_sample_map produce no other (tools/launch_plan sweep=1
+   ort_kernels_render_adaptive.hip the sixth to the ninth.  plan_render, plan_render_adaptive, plan_render_groups,
+   plan_render_sample_map and plan_render_accumulate produce no other (tools/launch_plan sweep=1
    and tests/test_launch_plan.py hold them to it); one that did would be an error, not a fallback.  The ray queries' families are
    built for every combination of their bools and need no list */
 constexpr KernelVariant kBuiltKernels[] = {
@@ -456,6 +467,10 @@ constexpr KernelVariant kBuiltKernels[] = {
     {KF_SAMPLE_MAP, false, true, false, true, false}, {KF_SAMPLE_MAP, false, true, true, true, false},
     {KF_SAMPLE_MAP, true, false, false, true, false}, {KF_SAMPLE_MAP, true, false, true, true, false},
     {KF_SAMPLE_MAP, true, true, false, true, false}, {KF_SAMPLE_MAP, true, true, true, true, false},
+    {KF_ACCUM, false, false, false, true, false}, {KF_ACCUM, false, false, true, true, false},
+    {KF_ACCUM, false, true, false, true, false}, {KF_ACCUM, false, true, true, true, false},
+    {KF_ACCUM, true, false, false, true, false}, {KF_ACCUM, true, false, true, true, false},
+    {KF_ACCUM, true, true, false, true, false}, {KF_ACCUM, true, true, true, true, false},
 };
 constexpr size_t kBuiltKernelCount = sizeof(kBuiltKernels) / sizeof(kBuiltKernels[0]);
 

@@ -11,7 +11,7 @@
  * kernel.  The library never loads, links or runs it: the render call has no CPU fallback
  * (tests/test_host.py holds its image against the oracle; nothing else uses it).
  *
- * The ray-query lanes (raycast_lane, occluded_lane, ao_lane, radiance_lane with and without its adaptive rule), the batch-of-views flavour of pt_lane, its adaptive one, its light-group one and its sample-map one run here too, on
+ * The ray-query lanes (raycast_lane, occluded_lane, ao_lane, radiance_lane with and without its adaptive rule), the batch-of-views flavour of pt_lane, its adaptive one, its light-group one, its sample-map one and its accumulating one run here too, on
  * the tables the product's own host code packs, and the camera modes on the launch plan and RenderView fill of the product's own render call (ort_plan.h, ort_setup.h): tests/test_query_lanes_host.py holds them against the
  * reference's answers and the oracle, tests/test_host_sanitizers.py runs the same binary built with ASan + UBSan
  * (make host_sim_san).
@@ -42,6 +42,10 @@
  *       (the sample-map render, pt_lane<..., VIEWS, SPPMAP>: a batch of views, or with cams - the scene's own camera on the seed
  *       given; map.u32 holds views x W x H sample counts, cap is the most a pixel gets; the planes start at -7.0f, the sums at
  *       -1.0f and the states at 0xdddddddd; m2 and states given as - are not passed)
+ *   or: host_sim --accumulate scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32|- sum.f32 m2.f32|- count.u32 states.u32 rgb.f32|-
+ *       (the accumulating render, pt_lane<..., VIEWS, SPPMAP, ACCUM>: as --sample-map, the map given as - is not passed; every
+ *       plane file holds views x W x H entries, is READ before the lanes run and WRITTEN after them, so that runs chain; m2 and rgb
+ *       given as - are not passed)
  *   or: host_sim --tree-check scn base
  *       (no lane runs: the fast tree, binary and 4-wide, as build_tree made it under the environment's ORT_LEAF_TRI, ORT_LEAF_OTHER,
  *       ORT_TREE_SPLIT_KINDS and ORT_ANALYTIC_PROLOGUE, checked for everything the lanes take for granted -- see TreeCheck; one line
@@ -671,6 +675,68 @@ static int sample_map_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H
            (!want_states || write_bytes(a[15], states.data(), 4 * n)) ? 0 : 1;
 }
 
+/* the accumulating render (ort_render_accumulate and its views form): what device_render sets up for it, for one simulated lane
+   per thread.  The planes are the files' words, in and out */
+static int accumulate_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32|- sum.f32 m2.f32|- count.u32 states.u32 rgb.f32|- */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
+    const int W = atoi(a[4]), H = atoi(a[5]), x0 = atoi(a[6]), y0 = atoi(a[7]), x1 = atoi(a[8]), y1 = atoi(a[9]);
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || x0 < 0 || y0 < 0 || x1 > W || y1 > H || x0 >= x1 || y0 >= y1) { fprintf(stderr, "bad frame size or rect\n"); return 1; }
+    const uint32_t cap = (uint32_t)strtoul(a[10], 0, 10);
+    if (cap == 0u || cap > (1u << 24)) { fprintf(stderr, "cap must be within [1, 1 << 24]\n"); return 1; }
+    std::vector<ort_view> views;
+    if (std::string(a[2]) == "-") {
+        views.resize(1);
+        camera_basis(*S.scene, W, H, &views[0].camera);
+        views[0].seed = (uint32_t)strtoul(a[3], 0, 10);
+    } else {
+        std::vector<unsigned char> cb;
+        if (!read_bytes(a[2], cb)) return 1;
+        if (cb.empty() || cb.size() % 48u) { fprintf(stderr, "%s: not a whole, positive number of 48-byte cameras\n", a[2]); return 1; }
+        std::vector<uint32_t> seeds;
+        if (!read_array(a[3], seeds, cb.size() / 48u, "seeds")) return 1;
+        views.resize(seeds.size());
+        for (size_t v = 0; v < views.size(); ++v) { memcpy(&views[v].camera, &cb[48u * v], 48); views[v].seed = seeds[v]; }
+    }
+    const uint32_t nv = (uint32_t)views.size();
+    memcpy(S.sv.cam, &views[0].camera, sizeof(views[0].camera)); /* unread by the VIEWS lanes */
+    std::vector<float> tab_host; /* the camera table, 16-byte aligned for the lanes' float4 reads */
+    pack_view_table(views.data(), nv, tab_host);
+    std::vector<float4> view_tab(4u * nv);
+    memcpy(view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
+    const size_t n = (size_t)nv * W * H; /* exactly: a read or write past a plane's end is one past the block */
+    const bool want_map = std::string(a[12]) != "-", want_m2 = std::string(a[14]) != "-", want_rgb = std::string(a[17]) != "-";
+    std::vector<uint32_t> map, count, states;
+    std::vector<float> sum, m2, rgb;
+    if (want_map && !read_array(a[12], map, n, "map words (views x W x H)")) return 1;
+    if (!read_array(a[13], sum, 3 * n, "sum floats (views x W x H x 3)")) return 1;
+    if (want_m2 && !read_array(a[14], m2, n, "m2 floats (views x W x H)")) return 1;
+    if (!read_array(a[15], count, n, "count words (views x W x H)")) return 1;
+    if (!read_array(a[16], states, n, "state words (views x W x H)")) return 1;
+    if (want_rgb && !read_array(a[17], rgb, 3 * n, "rgb floats (views x W x H x 3)")) return 1;
+    ort_render_params p{};
+    p.width = W; p.height = H; p.x0 = x0; p.y0 = y0; p.x1 = x1; p.y1 = y1;
+    p.policy = ORT_POLICY_PIXEL; p.spp = cap; p.rr = (float)atof(a[11]);
+    RenderView rv{};
+    render_view(p, plan_render_accumulate(sim_traits(S), p, sim_knobs(), nv), views.data(), nullptr, &rv);
+    rv.out = want_rgb ? rgb.data() : nullptr; rv.ad_m2 = want_m2 ? m2.data() : nullptr;
+    rv.sample_map = want_map ? map.data() : nullptr;
+    rv.acc_sum = sum.data(); rv.ad_spp = count.data(); rv.final_states = states.data();
+    rv.views = view_tab.data();
+    rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
+    const RenderHot hot = render_hot<RenderHot>(rv, &rv);
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
+        AdaptState A; /* the lane's own, as pt_accumulate's slot of LDS */
+        with_bools([&](auto D, auto T) {
+            pt_lane<LF_COUNTERS | lf_if(decltype(D)::value, LF_DIFFUSE) | lf_if(decltype(T)::value, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_SPPMAP | LF_ACCUM>(sv, hot, S.tab, stack, focal, 0, w, false, nullptr, &A);
+        }, getenv("SIM_DIFFUSE") != nullptr, S.tab != nullptr);
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return write_bytes(a[13], sum.data(), 12 * n) && (!want_m2 || write_bytes(a[14], m2.data(), 4 * n)) && write_bytes(a[15], count.data(), 4 * n) &&
+           write_bytes(a[16], states.data(), 4 * n) && (!want_rgb || write_bytes(a[17], rgb.data(), 12 * n)) ? 0 : 1;
+}
+
 /* the first-hit feature render (ort_render_features and its views form): what device_render_features sets up for it, for one
    simulated lane per thread.  cams - : the single-frame form, the scene's own camera on the seed given where the seeds file stands.
    A plane given as - is one the caller did not pass; every word of a plane starts as a filler that a pixel outside the rect keeps */
@@ -1003,6 +1069,7 @@ int main(int argc, char **argv) {
     if (argc == 21 && mode == "--render-adaptive") return render_adaptive_mode(argv + 2);
     if (argc == 19 && mode == "--light-groups") return light_groups_mode(argv + 2);
     if (argc == 18 && mode == "--sample-map") return sample_map_mode(argv + 2);
+    if (argc == 20 && mode == "--accumulate") return accumulate_mode(argv + 2);
     if (argc < 10 || mode.rfind("--", 0) == 0) {
         fprintf(stderr, "usage: host_sim scn base W H spp seed policy chunk out.f32 [shard_index shard_count]\n"
                         "       host_sim --unit records.bin out.f32\n"
@@ -1018,7 +1085,8 @@ int main(int argc, char **argv) {
                         "       host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
                         "       host_sim --features scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|-\n"
                         "       host_sim --light-groups scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr groups.u8 G groups.f32 rgb.f32|- states.u32|-\n"
-                        "       host_sim --sample-map scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32 rgb.f32 m2.f32|- states.u32|-\n");
+                        "       host_sim --sample-map scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32 rgb.f32 m2.f32|- states.u32|-\n"
+                        "       host_sim --accumulate scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32|- sum.f32 m2.f32|- count.u32 states.u32 rgb.f32|-\n");
         return 2;
     }
     int W = atoi(argv[3]), H = atoi(argv[4]);

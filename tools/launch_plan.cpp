@@ -10,7 +10,8 @@
    (plan_render_adaptive: the plan of ort_render_adaptive, or with views=N of ort_render_views_adaptive; "adaptive" and the
    views fields are appended), groups=1 (plan_render_groups: the plan of ort_render_light_groups, or with views=N of
    ort_render_views_light_groups; "groups" and the views fields are appended), sample_map=1 (plan_render_sample_map: the plan
-   of ort_render_sample_map, or with views=N of ort_render_views_sample_map; "sample_map" and the views fields are appended); fill=1: after the plan, every field of the RenderView that is not a pointer as the shared fill
+   of ort_render_sample_map, or with views=N of ort_render_views_sample_map; "sample_map" and the views fields are appended), accumulate=1 (plan_render_accumulate: the plan of ort_render_accumulate, or
+   with views=N of ort_render_views_accumulate; "accumulate" and the views fields are appended); fill=1: after the plan, every field of the RenderView that is not a pointer as the shared fill
    (render_view, csrc/ort_setup.h) sets it for that plan, "name = value" one per line -- seed=, rr= are the call's, view_seed=S
    gives view v of views=N the seed S + v, min_spp= max_spp= check_every= tolerance= floor= are the stopping rule's; max_blocks
    defaults to what an upload on cu_count units fixes.  tab_flags, where not given, follows from
@@ -46,7 +47,7 @@ struct FillView {
 
 /* "family<counters, diffuse, tabs, implicit, wide>" */
 static std::string variant_name(const ort::KernelVariant &v) {
-    static const char *family[] = {"none", "wavefront", "loop", "loop_views", "exchange", "five", "adaptive", "groups", "sample_map"};
+    static const char *family[] = {"none", "wavefront", "loop", "loop_views", "exchange", "five", "adaptive", "groups", "sample_map", "accumulate"};
     char b[64];
     snprintf(b, sizeof(b), "%s<%d, %d, %d, %d, %d>", family[v.family], v.counters, v.diffuse, v.tabs, v.implicit, v.wide);
     return b;
@@ -55,7 +56,7 @@ static std::string variant_name(const ort::KernelVariant &v) {
 /* every plan the policy gives over: both BSDF flavours; all tables, the prologue's alone, none; a tree inside and outside the L2; a
    cheap and a dear one; with and without the wide form; PIXEL, CHUNK and explicit jobs (the WHOLE policy); counters; one view and
    three (implicit job spaces); a frame smaller than the grid and a long launch; both answers of the five-waves layout check; and
-   the knobs that choose kernels, unset and forced either way.  plan_render_adaptive, plan_render_groups and plan_render_sample_map for the single PIXEL frames */
+   the knobs that choose kernels, unset and forced either way.  plan_render_adaptive, plan_render_groups, plan_render_sample_map and plan_render_accumulate for the single PIXEL frames */
 static int sweep() {
     unsigned long long plans = 0, unbuilt = 0;
     std::string first;
@@ -88,7 +89,7 @@ static int sweep() {
                 kn.exchange = exchange; kn.wide = wide; kn.waves5 = waves5; kn.wavefront = wavefront != 0;
                 kn.general_kernel = general != 0; kn.lds_tables = lds_tables; kn.debug_util = util != 0;
                 hold(ort::plan_render(t, p, explicit_jobs, jobs, w5 != 0, kn, views));
-                if (policy == ORT_POLICY_PIXEL && views == 1u) { hold(ort::plan_render_adaptive(t, p, kn, 1)); hold(ort::plan_render_groups(t, p, kn, 1)); hold(ort::plan_render_sample_map(t, p, kn, 1)); }
+                if (policy == ORT_POLICY_PIXEL && views == 1u) { hold(ort::plan_render_adaptive(t, p, kn, 1)); hold(ort::plan_render_groups(t, p, kn, 1)); hold(ort::plan_render_sample_map(t, p, kn, 1)); hold(ort::plan_render_accumulate(t, p, kn, 1)); }
             }
         }
     }
@@ -110,7 +111,7 @@ int main(int argc, char **argv) {
     unsigned long materials = 0, lights = 0, pro_boxes = 0, pro_spheres = 0, pro_cyls = 0;
     unsigned long long job_count = 0;
     unsigned long view_count = 1;
-    bool views_given = false, adaptive = false, groups = false, sample_map = false, fill = false, variant = false;
+    bool views_given = false, adaptive = false, groups = false, sample_map = false, accumulate = false, fill = false, variant = false;
     unsigned long view_seed = 0;
     ort_adaptive ad{};
     const char *query = nullptr;
@@ -153,6 +154,7 @@ int main(int argc, char **argv) {
         else if (is("adaptive")) adaptive = atoi(v) != 0;
         else if (is("groups")) groups = atoi(v) != 0;
         else if (is("sample_map")) sample_map = atoi(v) != 0;
+        else if (is("accumulate")) accumulate = atoi(v) != 0;
         else if (is("fill")) fill = atoi(v) != 0;
         else if (is("variant")) variant = atoi(v) != 0;
         else if (is("seed")) p.seed = (uint32_t)strtoul(v, nullptr, 0);
@@ -199,8 +201,8 @@ int main(int argc, char **argv) {
     }
     if (!explicit_jobs && p.policy == ORT_POLICY_CHUNK && p.chunk == 0) { fprintf(stderr, "launch_plan: chunk=0\n"); return 2; }
     if (views_given && (view_count < 1 || view_count > ORT_MAX_VIEWS || explicit_jobs)) { fprintf(stderr, "launch_plan: views=1..%u, implicit job spaces only\n", ORT_MAX_VIEWS); return 2; }
-    if ((adaptive || groups || sample_map) && (explicit_jobs || p.policy != ORT_POLICY_PIXEL || p.shard_count > 1 || (int)adaptive + (int)groups + (int)sample_map > 1)) { fprintf(stderr, "launch_plan: adaptive=1, groups=1 or sample_map=1 (one of them) needs policy=pixel, implicit jobs and no shards\n"); return 2; }
-    const ort::LaunchPlan l = sample_map ? ort::plan_render_sample_map(t, p, kn, (uint32_t)view_count) : groups ? ort::plan_render_groups(t, p, kn, (uint32_t)view_count) : adaptive ? ort::plan_render_adaptive(t, p, kn, (uint32_t)view_count)
+    if ((adaptive || groups || sample_map || accumulate) && (explicit_jobs || p.policy != ORT_POLICY_PIXEL || p.shard_count > 1 || (int)adaptive + (int)groups + (int)sample_map + (int)accumulate > 1)) { fprintf(stderr, "launch_plan: adaptive=1, groups=1, sample_map=1 or accumulate=1 (one of them) needs policy=pixel, implicit jobs and no shards\n"); return 2; }
+    const ort::LaunchPlan l = accumulate ? ort::plan_render_accumulate(t, p, kn, (uint32_t)view_count) : sample_map ? ort::plan_render_sample_map(t, p, kn, (uint32_t)view_count) : groups ? ort::plan_render_groups(t, p, kn, (uint32_t)view_count) : adaptive ? ort::plan_render_adaptive(t, p, kn, (uint32_t)view_count)
                                        : ort::plan_render(t, p, explicit_jobs, job_count, w5_layout_ok, kn, (uint32_t)view_count);
     printf("{\"wavefront\": %d, \"exchange\": %d, \"five\": %d, \"wide\": %d, \"counters\": %d, \"diffuse\": %d, \"tabs\": %d, \"implicit\": %d, \"util\": %d, "
            "\"grid\": %u, \"mode\": %d, \"nchunks\": %u, \"job_count\": %llu, \"my_blocks\": %u, \"refill_below\": %d, \"descend_below\": %d, "
@@ -214,11 +216,12 @@ int main(int argc, char **argv) {
     if (adaptive) printf(", \"adaptive\": %d", l.adaptive);
     if (groups) printf(", \"groups\": %d", l.groups);
     if (sample_map) printf(", \"sample_map\": %d", l.sample_map);
-    if (views_given || adaptive || groups || sample_map) printf(", \"views\": %d, \"view_count\": %u, \"view_jobs\": %llu", l.views, l.view_count, l.view_jobs);
+    if (accumulate) printf(", \"accumulate\": %d", l.accumulate);
+    if (views_given || adaptive || groups || sample_map || accumulate) printf(", \"views\": %d, \"view_count\": %u, \"view_jobs\": %llu", l.views, l.view_count, l.view_jobs);
     if (variant) printf(", \"variant\": \"%s\", \"built\": %d", variant_name(ort::plan_variant(l)).c_str(), ort::variant_built(ort::plan_variant(l)));
     printf("}\n");
     if (fill) { /* as device_render calls it: a batch's views, the single adaptive frame's one view, or none */
-        std::vector<ort_view> views(views_given || adaptive || groups || sample_map ? view_count : 0);
+        std::vector<ort_view> views(views_given || adaptive || groups || sample_map || accumulate ? view_count : 0);
         for (size_t v = 0; v < views.size(); ++v) views[v].seed = (uint32_t)(view_seed + v);
         FillView rv{};
         ort::render_view(p, l, views.empty() ? nullptr : views.data(), adaptive ? &ad : nullptr, &rv);
