@@ -878,6 +878,75 @@ int ort_render_views_features(ort_scene *scene, const ort_render_params *params,
 int ort_render_views_features_device(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
                                      const ort_feature_planes *planes, void *hip_stream, ort_stats *stats);
 
+/* ---- denoising: a variance-guided, edge-avoiding a-trous filter over rendered frames -----------
+ * What uses the planes above: the mean colour with its sample count n and its sum of squared sample luminance Q (ort_render_adaptive,
+ * ort_render_sample_map, ort_render_accumulate) and the guide planes of ort_render_features.  `iterations` passes of 5 x 5 taps at
+ * stride 1, 2, 4, ... over the albedo-demodulated colour; a tap's weight falls with the angle between the normals, with the depth
+ * difference and with the luminance difference measured in standard deviations of the pixel's own noise.  The calls take no scene
+ * handle -- a frame loaded from a checkpoint can be denoised -- and `device` is used as ort_unit_eval_device uses it.
+ * Planes.  All six are required; each holds frame_count frames of width*height entries, view-major, row 0 at the bottom; out_rgb is
+ * 3 f32 per pixel likewise.  No tap ever crosses from one frame into another: frame f of a batch is the single-frame call's result
+ * for that frame's planes.  out_rgb may be in->rgb itself (in place); any other overlap is the caller's error and is not checked.
+ * Every operation below is a separately rounded f32 operation (no FMA), and no weight uses a transcendental function, so the
+ * result is defined bit for bit.  lum(c) = (0.2126f*c.x + 0.7152f*c.y) + 0.0722f*c.z.  fall(x): r = 1.0f / (1.0f + x); r = r*r;
+ * r = r*r.
+ * Prologue, per pixel.  n = count, fn = (float)n; a_k = albedo_k > 1e-3f ? albedo_k : 1e-3f; c_k = rgb_k / a_k; Y = lum(rgb);
+ * v = m2 / fn - Y*Y; if (v < 0) v = 0; vm = n > 1 ? v / (fn - 1.0f) : Y*Y; la = lum(a); var = vm / (la*la).
+ * The pixel is USABLE iff n >= 1 and all of rgb, m2, albedo, normal, depth, c and var are finite.  Usability is decided here and
+ * never judged again.  An unusable pixel is never a tap, and its output is out_rgb = rgb, the input's bits: a pixel with
+ * count == 0 (what a sample map left out), a NaN pixel, a pixel whose variance overflows.
+ * Iteration j = 0 .. iterations-1, stride s = 1 << j, for each usable pixel p; inputs are the c and var planes of the previous
+ * iteration (two planes, used in turn):
+ *  - variance prefilter.  G = GW = 0; for dy = -1..1 (outer), dx = -1..1 (inner), q = p + (dx, dy): skip q outside the frame or
+ *    unusable; w3 = k3[|dx|] * k3[|dy|] with k3 = {0.5, 0.25}; G = G + w3*var_q; GW = GW + w3.  Then g = G / GW.
+ *  - l_p = lum(c_p); den = (sigma_l*sigma_l)*g + 1e-10f.
+ *  - taps.  S = (0, 0, 0), V = 0, W = 0; for dy = -2..2 (outer), dx = -2..2 (inner), q = p + s*(dx, dy): skip q outside the frame
+ *    or unusable; h = k[|dx|] * k[|dy|] with k = {0.375, 0.25, 0.0625}.  The centre tap has w = h.  Any other tap:
+ *       d  = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z
+ *       wn = d > 0 ? d : 0, then wn = wn*wn, normal_squarings times
+ *       dz = z_p - z_q;  zm = max(|z_p|, |z_q|)
+ *       xz = (dz*dz) / (((zm*zm) * (float)(s*s*(dx*dx + dy*dy))) * (sigma_z*sigma_z))
+ *       dl = l_p - lum(c_q);  xl = (dl*dl) / den
+ *       w  = ((h*wn) * fall(xz)) * fall(xl);  if w is not finite, w = 0
+ *    then, for every tap: S_k = S_k + w*c_q,k;  V = V + (w*w)*var_q;  W = W + w.
+ *  - result.  c'_p = S / W component by component, var'_p = V / (W*W).  Unusable pixels keep their entries.
+ * After the last iteration out_rgb_k = c'_k * a_k.
+ * Consequences.  A pixel with a zero normal (a miss) has wn = 0 with every neighbour and keeps its own value up to (rgb/a)*a.
+ * Mirrors and glass are not followed by the feature planes: what is seen in them is filtered by the guides of the surface itself.
+ * Values that become non-finite during the iterations propagate by IEEE rules; a NaN output matches the contract by position, not
+ * by sign or payload, as elsewhere in this library.  Results do not depend on frame_count, on the tile shape, or on how pixels
+ * fall on the GPU's lanes.
+ * frame_count == 0 returns ORT_OK without a launch, whatever the other arguments.  Otherwise errors are reported before any device
+ * work, in this order: ORT_ERR_INVALID (a null params struct, planes struct, plane or out_rgb; then a plane or out_rgb not 4-byte
+ * aligned; then width or height < 1 or frame_count*width*height >= 2^31; then iterations outside [1, 8]; then normal_squarings > 8;
+ * then sigma_l or sigma_z NaN, infinite or <= 0; then, in the device form, a workspace that is null, not 16-byte aligned or shorter
+ * than ort_denoise_workspace_bytes), then ORT_ERR_NO_DEVICE (no such device).
+ * The host form stages the planes, allocates and frees its own workspace and is synchronous.  The device form takes DEVICE pointers
+ * on `device` (the two structs are host memory, read before the call returns), enqueues on hip_stream (NULL = the default stream)
+ * and waits only when stats != NULL; it never allocates: the caller passes a workspace of ort_denoise_workspace_bytes = 48 bytes per
+ * pixel and frame (two planes of (c, var), one of (normal, depth)), 16-byte aligned, whose contents are lost.  stats (may be NULL)
+ * gets kernel_ms, the HIP-event time of the pack and the passes; every other field is 0. */
+typedef struct {
+    uint32_t iterations;        /* 1 .. 8 passes, strides 1 .. 1 << (iterations-1) */
+    uint32_t normal_squarings;  /* 0 .. 8: the normal weight is max(0, n_p . n_q) ^ (2 ^ normal_squarings) */
+    float sigma_l;              /* luminance tolerance, in standard deviations */
+    float sigma_z;              /* relative depth tolerance per pixel of tap distance */
+} ort_denoise_params;
+typedef struct {            /* HOST pointers in the host form, DEVICE pointers in the device form; the struct is host memory */
+    const float    *rgb;    /* 3 f32 / pixel: the MEAN colour (out_rgb of any render call, or sum / count) */
+    const float    *m2;     /* f32: Q, the sum of squared sample luminance */
+    const uint32_t *count;  /* u32: n, the samples the pixel has had */
+    const float    *albedo; /* 3 f32 / pixel   ort_render_features' planes */
+    const float    *normal; /* 3 f32 / pixel */
+    const float    *depth;  /* f32 */
+} ort_denoise_planes;
+int ort_denoise_workspace_bytes(int32_t width, int32_t height, uint32_t frame_count, uint64_t *bytes);
+int ort_denoise(int device, const ort_denoise_params *p, const ort_denoise_planes *in, int32_t width, int32_t height,
+                uint32_t frame_count, float *out_rgb, ort_stats *stats);
+int ort_denoise_device(int device, const ort_denoise_params *p, const ort_denoise_planes *in, int32_t width, int32_t height,
+                       uint32_t frame_count, void *d_out_rgb, void *d_workspace, uint64_t workspace_bytes, void *hip_stream,
+                       ort_stats *stats);
+
 /* ---- multi-GPU: block sharding and the one collective -------------------------------------
  * Replaces main()'s shared-memory tile pool (macos_main.mm:565-671: eight pthreads, one queue, one framebuffer)
  * across the GPUs of a node: scene replicated, 8x8 blocks dealt round-robin, every rank renders its blocks into a

@@ -129,6 +129,21 @@ class LightGroups(C.Structure):
     _fields_ = [("group_of_material", C.c_void_p), ("material_count", C.c_uint32), ("group_count", C.c_uint32)]
 
 
+class DenoiseParams(C.Structure):
+    """ort_denoise_params"""
+    _fields_ = [("iterations", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_l", C.c_float), ("sigma_z", C.c_float)]
+
+
+class DenoisePlanes(C.Structure):
+    """ort_denoise_planes: the six planes a denoise call reads, all required"""
+    _fields_ = [("rgb", C.c_void_p), ("m2", C.c_void_p), ("count", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p),
+                ("depth", C.c_void_p)]
+
+
+# denoise()'s defaults: the best of the grid of profiles/r25_denoise.md (RMSE against 16 384 spp, summed over two scenes at 64 and 256 spp)
+DENOISE_DEFAULTS = dict(iterations=4, normal_squarings=7, sigma_l=8.0, sigma_z=0.02)
+
+
 class AccumPlanes(C.Structure):
     """ort_accum_planes: the caller's planes of an accumulating render (ort_render_accumulate), read and written; m2 may be null."""
     _fields_ = [("sum_rgb", C.c_void_p), ("m2", C.c_void_p), ("count", C.c_void_p), ("states", C.c_void_p)]
@@ -167,7 +182,8 @@ EXPORTS = [
     "ort_render_light_groups", "ort_render_light_groups_device", "ort_render_views_light_groups",
     "ort_render_views_light_groups_device",
     "ort_render_sample_map", "ort_render_sample_map_device", "ort_render_views_sample_map", "ort_render_views_sample_map_device",
-    "ort_render_accumulate", "ort_render_accumulate_device", "ort_render_views_accumulate", "ort_render_views_accumulate_device"]
+    "ort_render_accumulate", "ort_render_accumulate_device", "ort_render_views_accumulate", "ort_render_views_accumulate_device",
+    "ort_denoise_workspace_bytes", "ort_denoise", "ort_denoise_device"]
 
 _lib = None
 
@@ -260,6 +276,10 @@ def lib():
         L.ort_pack_blocks_host.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.ort_unpack_blocks_host.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.ort_unpack_blocks_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.ort_denoise_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.ort_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoisePlanes), C.c_int32, C.c_int32, C.c_uint32, vp, stats]
+        L.ort_denoise_device.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoisePlanes), C.c_int32, C.c_int32, C.c_uint32, vp, vp,
+                                         C.c_uint64, vp, stats]
         L.ort_comm_unique_id.argtypes = [C.c_void_p]
         L.ort_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.ort_comm_create_local.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]
@@ -1091,6 +1111,11 @@ class Accumulator:
             out[had] = self.sum_rgb[had] / self.count[had].astype("<f4")[:, None]
         return out
 
+    def denoise(self, planes, **kw):
+        """the frame as it stands, denoised (denoise()): its own rgb(), m2 and count with the albedo, normal and depth planes of a
+        Scene.render_features dict of the same shape -> (out, stats)"""
+        return denoise(self.rgb(), self.m2, self.count, planes["albedo"], planes["normal"], planes["depth"], **kw)
+
     def save(self, path):
         """the frame as it stands, into one .npz file (np.savez): Accumulator.load(path) continues it"""
         with open(path, "wb") as f:
@@ -1174,6 +1199,63 @@ def views_workspace_bytes(params, view_count):
     n = C.c_uint64(0)
     _check(lib().ort_render_views_workspace_bytes(C.byref(params), view_count, C.byref(n)))
     return n.value
+
+
+# ---- denoising (ort_denoise.h) --------------------------------------------------------------------
+def _denoise_params(iterations, normal_squarings, sigma_l, sigma_z):
+    for name, v in (("iterations", iterations), ("normal_squarings", normal_squarings)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("%s must fit an unsigned 32-bit word, got %r" % (name, v))
+    return DenoiseParams(int(iterations), int(normal_squarings), float(sigma_l), float(sigma_z))
+
+
+def denoise_workspace_bytes(width, height, frame_count=1):
+    n = C.c_uint64(0)
+    _check(lib().ort_denoise_workspace_bytes(int(width), int(height), int(frame_count), C.byref(n)))
+    return n.value
+
+
+def denoise(rgb, m2, count, albedo, normal, depth, iterations=DENOISE_DEFAULTS["iterations"], sigma_l=DENOISE_DEFAULTS["sigma_l"],
+            sigma_z=DENOISE_DEFAULTS["sigma_z"], normal_squarings=DENOISE_DEFAULTS["normal_squarings"], device=0, out=None):
+    """ort_denoise: the mean colour rgb (H, W, 3) with its sums of squared sample luminance m2 (H, W) and sample counts count
+    (H, W) uint32 -- what render_adaptive, render_sample_map or an Accumulator give -- and render_features' albedo, normal and
+    depth planes -> (out (H, W, 3) float32, stats).  A leading V on every array is a batch of V frames, each denoised on its
+    own.  out may be rgb itself (in place)."""
+    count = np.ascontiguousarray(count, dtype="<u4")
+    if count.ndim not in (2, 3):
+        raise ValueError("count must be (H, W) or (V, H, W), got shape %s" % (count.shape,))
+    shape = count.shape
+    planes = []
+    for name, a, sh in (("rgb", rgb, shape + (3,)), ("m2", m2, shape), ("albedo", albedo, shape + (3,)), ("normal", normal, shape + (3,)),
+                        ("depth", depth, shape)):
+        a = np.ascontiguousarray(a, dtype="<f4")
+        if a.shape != sh:
+            raise ValueError("%s must have shape %s, got %s" % (name, sh, a.shape))
+        planes.append(a)
+    if out is None:
+        out = np.empty(shape + (3,), "<f4")
+    elif not _is_plane(out, shape + (3,), "<f4"):
+        raise ValueError("out must be a C-contiguous float32 array of shape %s" % (shape + (3,),))
+    frames = 1 if count.ndim == 2 else shape[0]
+    p = _denoise_params(iterations, normal_squarings, sigma_l, sigma_z)
+    pl = DenoisePlanes(planes[0].ctypes.data, planes[1].ctypes.data, count.ctypes.data, planes[2].ctypes.data, planes[3].ctypes.data,
+                       planes[4].ctypes.data)
+    st, stats = _stats()
+    _check(lib().ort_denoise(int(device), C.byref(p), C.byref(pl), shape[-1], shape[-2], frames, out.ctypes.data, st))
+    return out, stats()
+
+
+def denoise_device(d_rgb, d_m2, d_count, d_albedo, d_normal, d_depth, width, height, d_out, d_workspace, workspace_bytes, frame_count=1,
+                   iterations=DENOISE_DEFAULTS["iterations"], sigma_l=DENOISE_DEFAULTS["sigma_l"], sigma_z=DENOISE_DEFAULTS["sigma_z"],
+                   normal_squarings=DENOISE_DEFAULTS["normal_squarings"], device=0, stream=None, want_stats=False):
+    """ort_denoise_device: raw device pointers (torch data_ptr()) of the six planes, of out (may be d_rgb) and of a workspace of
+    denoise_workspace_bytes; enqueued on stream, waits only for stats -> stats or None"""
+    p = _denoise_params(iterations, normal_squarings, sigma_l, sigma_z)
+    pl = DenoisePlanes(*[p_ if p_ else None for p_ in (d_rgb, d_m2, d_count, d_albedo, d_normal, d_depth)])
+    st, stats = _stats(want_stats)
+    _check(lib().ort_denoise_device(int(device), C.byref(p), C.byref(pl), int(width), int(height), int(frame_count), _ptr(d_out),
+                                    _ptr(d_workspace), int(workspace_bytes), _ptr(stream), st))
+    return stats()
 
 
 # ---- multi-GPU: block sharding and the one collective (ort_comm.cpp) -----------------------------

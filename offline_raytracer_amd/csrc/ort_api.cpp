@@ -746,6 +746,38 @@ static int ort_unpack_blocks_device_impl(const void *d_packed, int32_t width, in
     rc = ort::unpack_blocks_device(d_packed, width, height, shard_index, shard_count, d_full_rgb, hip_stream, &err);
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
+
+/* ---- the denoiser (ort_denoise.h, device_denoise): no scene, the order of the checks is the call's contract (include/ort.h) ---- */
+static int ort_denoise_workspace_bytes_impl(int32_t width, int32_t height, uint32_t frame_count, uint64_t *bytes) {
+    if (!bytes) return fail(ORT_ERR_INVALID, "null argument");
+    *bytes = 0;
+    if (frame_count == 0) return ORT_OK;
+    if (width < 1 || height < 1 || (uint64_t)frame_count * (uint64_t)width * (uint64_t)height >= (1ull << 31)) return fail(ORT_ERR_INVALID, "bad frame size");
+    *bytes = 48ull * ((uint64_t)frame_count * (uint64_t)width * (uint64_t)height);
+    return ORT_OK;
+}
+static int denoise_common(int device, bool host, const ort_denoise_params *p, const ort_denoise_planes *in, int32_t width, int32_t height, uint32_t frame_count,
+                          void *out_rgb, void *workspace, uint64_t workspace_bytes, void *hip_stream, ort_stats *stats) {
+    if (frame_count == 0) return ORT_OK;
+    if (!p || !in) return fail(ORT_ERR_INVALID, "null params or planes struct");
+    const void *ptrs[] = {in->rgb, in->m2, in->count, in->albedo, in->normal, in->depth, out_rgb};
+    for (const void *q : ptrs)
+        if (!q) return fail(ORT_ERR_INVALID, "null plane (all six planes and out_rgb are required)");
+    for (const void *q : ptrs)
+        if ((uintptr_t)q & 3u) return fail(ORT_ERR_INVALID, "plane not 4-byte aligned");
+    if (width < 1 || height < 1 || (uint64_t)frame_count * (uint64_t)width * (uint64_t)height >= (1ull << 31)) return fail(ORT_ERR_INVALID, "bad frame size");
+    if (p->iterations < 1 || p->iterations > 8) return fail(ORT_ERR_INVALID, "iterations must be within [1, 8]");
+    if (p->normal_squarings > 8) return fail(ORT_ERR_INVALID, "normal_squarings must be at most 8");
+    for (float sigma : {p->sigma_l, p->sigma_z})
+        if (!(sigma > 0.0f) || !(sigma <= FLT_MAX)) return fail(ORT_ERR_INVALID, "sigma_l and sigma_z must be finite and > 0");
+    if (!host) {
+        const uint64_t need = 48ull * ((uint64_t)frame_count * (uint64_t)width * (uint64_t)height);
+        if (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < need) return fail(ORT_ERR_INVALID, "null, misaligned or short workspace (ort_denoise_workspace_bytes)");
+    }
+    std::string err;
+    int rc = ort::device_denoise(device, host, *p, *in, width, height, frame_count, out_rgb, workspace, hip_stream, stats, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
 static int ort_comm_unique_id_impl(void *id) {
     if (!id) return fail(ORT_ERR_INVALID, "null argument");
     std::string err;
@@ -845,6 +877,9 @@ int ort_shard_block_count(int32_t width, int32_t height, uint32_t shard_index, u
 int ort_pack_blocks_host(const float *full_rgb, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, float *packed) { return guarded([&]() { return ort_pack_blocks_host_impl(full_rgb, width, height, shard_index, shard_count, packed); }); }
 int ort_unpack_blocks_host(const float *packed, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, float *full_rgb) { return guarded([&]() { return ort_unpack_blocks_host_impl(packed, width, height, shard_index, shard_count, full_rgb); }); }
 int ort_unpack_blocks_device(const void *d_packed, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, void *d_full_rgb, void *hip_stream) { return guarded([&]() { return ort_unpack_blocks_device_impl(d_packed, width, height, shard_index, shard_count, d_full_rgb, hip_stream); }); }
+int ort_denoise_workspace_bytes(int32_t width, int32_t height, uint32_t frame_count, uint64_t *bytes) { return guarded([&]() { return ort_denoise_workspace_bytes_impl(width, height, frame_count, bytes); }); }
+int ort_denoise(int device, const ort_denoise_params *p, const ort_denoise_planes *in, int32_t width, int32_t height, uint32_t frame_count, float *out_rgb, ort_stats *stats) { return guarded([&]() { return denoise_common(device, true, p, in, width, height, frame_count, out_rgb, nullptr, 0, nullptr, stats); }); }
+int ort_denoise_device(int device, const ort_denoise_params *p, const ort_denoise_planes *in, int32_t width, int32_t height, uint32_t frame_count, void *d_out_rgb, void *d_workspace, uint64_t workspace_bytes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return denoise_common(device, false, p, in, width, height, frame_count, d_out_rgb, d_workspace, workspace_bytes, hip_stream, stats); }); }
 int ort_comm_unique_id(void *id) { return guarded([&]() { return ort_comm_unique_id_impl(id); }); }
 int ort_comm_create(const void *id, int rank, int world, int device, ort_comm **out) { return guarded([&]() { return ort_comm_create_impl(id, rank, world, device, out); }); }
 int ort_comm_create_local(int world, const int *devices, ort_comm **out) { return guarded([&]() { return ort_comm_create_local_impl(world, devices, out); }); }

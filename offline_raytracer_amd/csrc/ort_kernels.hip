@@ -4,6 +4,7 @@
  * kernels' four-waves-per-SIMD build (the lane code itself is ort_lane.h).  A plan becomes a launch by its KernelVariant
  * (plan_variant, ort_plan.h): kLaunchers below pairs every entry of that header's list of built kernels with this unit's kernel,
  * which that instantiates, or a sibling unit's launcher.  A render and a ray query share the steps around their kernels.
+ * The denoiser's kernels (ort_denoise.h) are launched from here too (device_denoise): they need no scene and no plan.
  */
 #include <algorithm>
 #include <memory>
@@ -13,6 +14,7 @@
 #include "ort_lane.h" /* in namespace ort, at the header's own limits; it declares the sibling units' launchers */
 #include "ort_plan.h"
 #include "ort_setup.h"
+#include "ort_denoise.h" /* the denoiser's pixel functions and kernels (namespace ortdn); device_denoise below launches them */
 
 #ifndef ORT_HOST_SIM /* tools/host_sim.cpp drives the lane code itself and has no device */
 namespace ort {
@@ -885,6 +887,74 @@ int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const vo
             }, pl.counters, pl.diffuse, pl.tabs);
         });
     });
+}
+
+/* ---- the denoiser (ort_denoise.h): a pack, then `iterations` a-trous passes that ping-pong between the workspace's two CV planes.
+   No scene: the call names its device.  host: the caller's planes are staged whole, the passes run in place on the staged colour
+   and the workspace is this call's own; otherwise every pointer is the device's, nothing is allocated and the passes are enqueued
+   on stream (the call waits only for stats).  The arguments are checked by the caller (ort_api.cpp: denoise_common). */
+int device_denoise(int device, bool host, const ort_denoise_params &p, const ort_denoise_planes &in, int32_t w, int32_t h, uint32_t frames, void *out_rgb,
+                   void *workspace, void *stream_, ort_stats *stats, std::string *err) {
+    int count = 0;
+    int rc = device_count(&count, err);
+    if (rc != ORT_OK) return rc;
+    if (device < 0 || device >= count) { *err = "no such HIP device"; return ORT_ERR_NO_DEVICE; }
+    ORT_HIP(hipSetDevice(device));
+    hipStream_t stream = host ? nullptr : (hipStream_t)stream_;
+    const size_t n = (size_t)frames * (size_t)w * (size_t)h;
+    DevBuf d_rgb, d_m2, d_count, d_albedo, d_normal, d_depth, d_ws;
+    const void *rgb = in.rgb, *m2 = in.m2, *cnt = in.count, *albedo = in.albedo, *normal = in.normal, *depth = in.depth;
+    if (host) {
+        struct { DevBuf *buf; const void **src; size_t bytes; } stage[] = {{&d_rgb, &rgb, 12 * n},       {&d_m2, &m2, 4 * n},         {&d_count, &cnt, 4 * n},
+                                                                           {&d_albedo, &albedo, 12 * n}, {&d_normal, &normal, 12 * n}, {&d_depth, &depth, 4 * n}};
+        for (auto &s : stage) {
+            if ((rc = s.buf->ensure(s.bytes, err))) return rc;
+            ORT_HIP(hipMemcpy(s.buf->p, *s.src, s.bytes, hipMemcpyHostToDevice));
+            *s.src = s.buf->p;
+        }
+        if ((rc = d_ws.ensure(ortdn::kWorkspaceBytesPerPixel * n, err))) return rc;
+        workspace = d_ws.p;
+    }
+    float *d_out = host ? d_rgb.as<float>() : (float *)out_rgb;
+    ortdn::F4 *cv[2] = {(ortdn::F4 *)workspace, (ortdn::F4 *)workspace + n};
+    ortdn::F4 *gd = (ortdn::F4 *)workspace + 2 * n;
+    const ortdn::Params prm{p.iterations, p.normal_squarings, p.sigma_l * p.sigma_l, p.sigma_z * p.sigma_z};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct EventGuard { hipEvent_t &a, &b; ~EventGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } guard{ev0, ev1};
+    if (stats) {
+        ORT_HIP(hipEventCreate(&ev0));
+        ORT_HIP(hipEventCreate(&ev1));
+        ORT_HIP(hipEventRecord(ev0, stream));
+    }
+    constexpr uint64_t kMaxGrid = 1u << 20; /* workgroups of one launch; the kernels stride over what is beyond */
+    const uint64_t pack_groups = (n + 255u) / 256u;
+    hipLaunchKernelGGL(ortdn::denoise_pack, dim3((uint32_t)std::min(pack_groups, kMaxGrid)), dim3(256), 0, stream, (const float *)rgb, (const float *)m2,
+                       (const uint32_t *)cnt, (const float *)albedo, (const float *)normal, (const float *)depth, cv[0], gd, (uint32_t)n);
+    ORT_HIP(hipGetLastError());
+    const uint32_t tiles_x = ((uint32_t)w + ortdn::kTileW - 1u) / ortdn::kTileW, tiles_y = ((uint32_t)h + ortdn::kTileH - 1u) / ortdn::kTileH;
+    const uint64_t tiles = (uint64_t)tiles_x * tiles_y * frames;
+    const dim3 grid((uint32_t)std::min(tiles, kMaxGrid));
+    for (uint32_t j = 0; j < p.iterations; ++j) {
+        const int s = 1 << j;
+        const ortdn::F4 *src = cv[j & 1u];
+        if (j + 1u == p.iterations)
+            hipLaunchKernelGGL(ortdn::denoise_atrous<true>, grid, dim3(256), 0, stream, src, gd, (ortdn::F4 *)nullptr, (const float *)rgb, (const float *)albedo, d_out, w, h,
+                               tiles_x, tiles_y, tiles, s, prm);
+        else
+            hipLaunchKernelGGL(ortdn::denoise_atrous<false>, grid, dim3(256), 0, stream, src, gd, cv[(j & 1u) ^ 1u], (const float *)nullptr, (const float *)nullptr,
+                               (float *)nullptr, w, h, tiles_x, tiles_y, tiles, s, prm);
+        ORT_HIP(hipGetLastError());
+    }
+    if (stats) {
+        ORT_HIP(hipEventRecord(ev1, stream));
+        ORT_HIP(hipEventSynchronize(ev1));
+        float ms = 0.0f;
+        ORT_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+        *stats = ort_stats{};
+        stats->kernel_ms = ms;
+    }
+    if (host) ORT_HIP(hipMemcpy(out_rgb, d_out, 12 * n, hipMemcpyDeviceToHost));
+    return ORT_OK;
 }
 
 } // namespace ort
