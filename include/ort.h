@@ -947,6 +947,83 @@ int ort_denoise_device(int device, const ort_denoise_params *p, const ort_denois
                        uint32_t frame_count, void *d_out_rgb, void *d_workspace, uint64_t workspace_bytes, void *hip_stream,
                        ort_stats *stats);
 
+/* ---- planning the next pass: where a frame's next samples go (csrc/ort_sampleplan.h) -----------
+ * The step between two passes of ort_render_accumulate: from a frame's colour, its sum of squared sample luminance Q and its
+ * sample counts n, a sample map -- the layout ort_render_sample_map and ort_render_accumulate read -- that asks, for every pixel,
+ * for the samples that bring the worst error of its neighbourhood down to a tolerance at the variance measured so far; and per
+ * frame 32 bytes of totals, which are all a caller needs to read to decide whether to go on.  The calls take no scene handle -- a
+ * checkpoint can be planned -- and `device` is used as ort_unit_eval_device uses it.
+ * Planes.  rgb, m2 and count hold frame_count frames of width*height entries, view-major, row 0 at the bottom; sample_map is one
+ * u32 per pixel likewise and totals is frame_count entries.  No window crosses from one frame into another and a budget is per
+ * frame: frame f of a batch is the single-frame call's result for that frame's planes.  Every pixel of every frame of the map is
+ * written.  The map may not overlap a plane (not checked).
+ * Every f32 operation below is rounded on its own (no FMA, correctly rounded divides); nothing uses a transcendental function, and
+ * the allocation uses the SQUARED relative error, so no square root is taken.  Everything that is summed is an integer.  The result
+ * is defined bit for bit.  lum(c) = (0.2126f*c.x + 0.7152f*c.y) + 0.0722f*c.z.  tol2 = tolerance*tolerance, taken once.
+ * Per pixel, its error e (the terms of the adaptive calls' stopping rule):
+ *    n = count; fn = (float)n; m = rgb_is_sum ? lum(rgb) / fn : lum(rgb);
+ *    v = m2 / fn - m*m; if (v < 0) v = 0; vm = v / (fn - 1.0f);
+ *    a = |m|; b = a > floor ? a : floor; e = vm / (b*b).
+ *    The pixel is UNKNOWN if n < 2.  It is INVALID if it is not unknown and either n > 1<<24 or e is not finite.  Unknown and
+ *    invalid pixels have e = +0.  A valid e that is not > 0 is +0 (a -0 never reaches a comparison of bits).  The pixel is
+ *    UNCONVERGED if it is valid and e > tol2.  This is decided once; the later steps read e alone.
+ * Window.  d = the maximum of e over the (2*radius+1)^2 pixels around the pixel that lie inside its own frame: a maximum of
+ * non-negative finite floats, independent of order.
+ * What the pixel wants.  room = min(cap, (1<<24) - min(n, 1<<24)).
+ *    unknown pixel:       want = min(pilot, room)
+ *    otherwise, d > tol2: need = fn * (d / tol2) - fn;
+ *                         k = need >= 16777216.0f ? 1<<24 : (need > 0 ? (uint32_t)need : 0);  if (k < min_add) k = min_add;
+ *                         want = min(k, room)
+ *    otherwise:           want = 0
+ *    An invalid pixel wants nothing of its own error but is planned from its neighbours' like any other: a NaN pixel cannot eat
+ *    a budget for ever.
+ * Per frame.  wanted = the sum of want, in 64 bits.  If budget == 0 or wanted <= budget, add = want; otherwise
+ * add = (uint32_t)((uint64_t)want * budget / wanted), an integer division.  sample_map = add.  planned = the sum of add.
+ * worst = the maximum e.  unconverged, unknown and invalid count pixels.
+ * Consequences.  planned <= budget wherever a budget is given.  A scaled frame has planned > budget - (its pixels with want > 0).
+ * A scaled plan can be all zero while pixels are unconverged: the budget is exhausted.  planned == 0 and unconverged == 0 together
+ * mean converged (with pilot > 0 an unknown pixel with room keeps planned above 0).  add <= want <= room <= cap: the pass that
+ * follows, with params->spp = cap, takes exactly the map.  Results do not depend on frame_count, on the tile shape, or on which
+ * lane or workgroup added what.
+ * frame_count == 0 returns ORT_OK without a launch, whatever the other arguments.  Otherwise errors are reported before any device
+ * work, in this order: ORT_ERR_INVALID (a null params struct, planes struct, plane, sample_map or totals; then a plane or the map
+ * not 4-byte aligned or totals not 8-byte aligned; then width or height < 1 or frame_count*width*height >= 2^31; then, in the
+ * struct's order: tolerance NaN, infinite, <= 0 or with tolerance*tolerance (f32) == 0; floor NaN, infinite or <= 0; radius > 3;
+ * min_add == 0; cap outside [1, 1<<24]; rgb_is_sum > 1; reserved != 0; budget > 1<<39; then, in the device form, a workspace that is
+ * null, not 4-byte aligned or shorter than ort_plan_samples_workspace_bytes), then ORT_ERR_NO_DEVICE (no such device).
+ * The host form stages the planes, allocates and frees its own workspace and is synchronous.  The device form takes DEVICE pointers
+ * on `device` (the two structs are host memory, read before the call returns), zeroes d_totals on hip_stream itself, enqueues there
+ * (NULL = the default stream) and waits only when stats != NULL; it never allocates: the caller passes a workspace of
+ * ort_plan_samples_workspace_bytes = 4 bytes per pixel and frame (the e plane), whose contents are lost.  stats (may be NULL) gets
+ * kernel_ms, the HIP-event time of the three kernels; every other field is 0. */
+typedef struct {
+    float    tolerance;   /* target relative standard error of a pixel's mean luminance; finite, > 0, and tolerance*tolerance (f32) > 0 */
+    float    floor;       /* stands in for |mean luminance| in the dark, as ort_adaptive's floor; finite, > 0 */
+    uint32_t radius;      /* 0..3: a pixel plans for the worst error within (2r+1) x (2r+1) */
+    uint32_t pilot;       /* samples asked for a pixel that has had fewer than 2 (no estimate yet); may be 0 */
+    uint32_t min_add;     /* >= 1: the least an unconverged pixel asks for */
+    uint32_t cap;         /* 1 .. 1<<24: the most any pixel gets in one pass (params->spp of the pass that follows) */
+    uint32_t rgb_is_sum;  /* 0: rgb is the MEAN colour; 1: rgb is ort_accum_planes.sum_rgb, the undivided sum */
+    uint32_t reserved;    /* must be 0 */
+    uint64_t budget;      /* 0: no budget; else 1 .. 1<<39: the most samples one FRAME gets in this pass */
+} ort_plan_params;
+typedef struct {            /* HOST pointers in the host form, DEVICE pointers in the device form; the struct is host memory */
+    const float    *rgb;    /* 3 f32 / pixel: the mean colour, or with rgb_is_sum the undivided sum */
+    const float    *m2;     /* f32: Q, the sum of squared sample luminance */
+    const uint32_t *count;  /* u32: n, the samples the pixel has had */
+} ort_plan_planes;
+typedef struct {
+    uint64_t wanted, planned;                 /* the sums of want and of add over the frame */
+    uint32_t unconverged, unknown, invalid;   /* pixels */
+    float    worst;                           /* the largest e of the frame: a squared relative standard error */
+} ort_plan_totals; /* 32 bytes */
+int ort_plan_samples_workspace_bytes(int32_t width, int32_t height, uint32_t frame_count, uint64_t *bytes);
+int ort_plan_samples(int device, const ort_plan_params *p, const ort_plan_planes *in, int32_t width, int32_t height,
+                     uint32_t frame_count, uint32_t *sample_map, ort_plan_totals *totals, ort_stats *stats);
+int ort_plan_samples_device(int device, const ort_plan_params *p, const ort_plan_planes *in, int32_t width, int32_t height,
+                            uint32_t frame_count, void *d_sample_map, void *d_totals, void *d_workspace, uint64_t workspace_bytes,
+                            void *hip_stream, ort_stats *stats);
+
 /* ---- multi-GPU: block sharding and the one collective -------------------------------------
  * Replaces main()'s shared-memory tile pool (macos_main.mm:565-671: eight pthreads, one queue, one framebuffer)
  * across the GPUs of a node: scene replicated, 8x8 blocks dealt round-robin, every rank renders its blocks into a

@@ -144,6 +144,32 @@ class DenoisePlanes(C.Structure):
 DENOISE_DEFAULTS = dict(iterations=4, normal_squarings=7, sigma_l=8.0, sigma_z=0.02)
 
 
+class PlanParams(C.Structure):
+    """ort_plan_params"""
+    _fields_ = [("tolerance", C.c_float), ("floor", C.c_float), ("radius", C.c_uint32), ("pilot", C.c_uint32), ("min_add", C.c_uint32),
+                ("cap", C.c_uint32), ("rgb_is_sum", C.c_uint32), ("reserved", C.c_uint32), ("budget", C.c_uint64)]
+
+
+class PlanPlanes(C.Structure):
+    """ort_plan_planes: the three planes a plan reads, all required"""
+    _fields_ = [("rgb", C.c_void_p), ("m2", C.c_void_p), ("count", C.c_void_p)]
+
+
+class PlanTotals(C.Structure):
+    """ort_plan_totals: 32 bytes per frame"""
+    _fields_ = [("wanted", C.c_uint64), ("planned", C.c_uint64), ("unconverged", C.c_uint32), ("unknown", C.c_uint32), ("invalid", C.c_uint32),
+                ("worst", C.c_float)]
+
+    def as_dict(self):
+        return dict(wanted=int(self.wanted), planned=int(self.planned), unconverged=int(self.unconverged), unknown=int(self.unknown),
+                    invalid=int(self.invalid), worst=np.float32(self.worst))
+
+
+PLAN_TOTALS_DTYPE = np.dtype([("wanted", "<u8"), ("planned", "<u8"), ("unconverged", "<u4"), ("unknown", "<u4"), ("invalid", "<u4"), ("worst", "<f4")])
+# plan_samples()'s defaults: the floor of the adaptive calls, a 3 x 3 window as the measured two-pass scheme (profiles/r23_sample_map.md)
+PLAN_DEFAULTS = dict(floor=0.05, radius=1, pilot=16, min_add=1, cap=1024)
+
+
 class AccumPlanes(C.Structure):
     """ort_accum_planes: the caller's planes of an accumulating render (ort_render_accumulate), read and written; m2 may be null."""
     _fields_ = [("sum_rgb", C.c_void_p), ("m2", C.c_void_p), ("count", C.c_void_p), ("states", C.c_void_p)]
@@ -183,7 +209,8 @@ EXPORTS = [
     "ort_render_views_light_groups_device",
     "ort_render_sample_map", "ort_render_sample_map_device", "ort_render_views_sample_map", "ort_render_views_sample_map_device",
     "ort_render_accumulate", "ort_render_accumulate_device", "ort_render_views_accumulate", "ort_render_views_accumulate_device",
-    "ort_denoise_workspace_bytes", "ort_denoise", "ort_denoise_device"]
+    "ort_denoise_workspace_bytes", "ort_denoise", "ort_denoise_device",
+    "ort_plan_samples_workspace_bytes", "ort_plan_samples", "ort_plan_samples_device"]
 
 _lib = None
 
@@ -280,6 +307,10 @@ def lib():
         L.ort_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoisePlanes), C.c_int32, C.c_int32, C.c_uint32, vp, stats]
         L.ort_denoise_device.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoisePlanes), C.c_int32, C.c_int32, C.c_uint32, vp, vp,
                                          C.c_uint64, vp, stats]
+        L.ort_plan_samples_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.ort_plan_samples.argtypes = [C.c_int, C.POINTER(PlanParams), C.POINTER(PlanPlanes), C.c_int32, C.c_int32, C.c_uint32, vp, vp, stats]
+        L.ort_plan_samples_device.argtypes = [C.c_int, C.POINTER(PlanParams), C.POINTER(PlanPlanes), C.c_int32, C.c_int32, C.c_uint32, vp, vp, vp,
+                                              C.c_uint64, vp, stats]
         L.ort_comm_unique_id.argtypes = [C.c_void_p]
         L.ort_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.ort_comm_create_local.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]
@@ -789,6 +820,84 @@ class Scene:
         """The same with every plane on the device, V frames each, view-major.  params.seed is ignored."""
         return self._accumulate_device(_views(cameras, seeds), params, d_sum, d_count, d_states, d_m2, d_map, d_rgb, stream, want_stats)
 
+    # -- the converge loop: plan on the device, accumulate the plan, until nothing is planned --------
+    @staticmethod
+    def _pass_budget(budget, spent, passes_left):
+        """the per-frame budget of the next pass under a total of `budget` a frame: what is left, shared among the passes left;
+        None without a total, 0 when nothing is left to share (the loop ends: 0 would mean "no budget" to the planner)"""
+        return None if budget is None else max(int(budget) - spent, 0) // passes_left
+
+    def render_converge(self, acc, tolerance, seed, passes=8, budget=None, pilot=PLAN_DEFAULTS["pilot"], cap=PLAN_DEFAULTS["cap"], keep_maps=False,
+                        cameras=None, rr=0.8, **plan_kw):
+        """Sample the frame acc (an Accumulator) holds until it has converged: up to `passes` times, plan the next pass from acc's
+        own planes (Accumulator.plan: tolerance, pilot, cap and plan_kw -- floor, radius, min_add) and, unless every frame's plan
+        is empty (planned == 0), render_accumulate exactly that map with cap as the pass's cap.  From a fresh Accumulator the first
+        plan is the pilot.  budget: the most samples a FRAME gets over the whole loop; pass k plans with (what is left) //
+        (passes left) as its budget, and the loop ends when that is 0.  cameras: (V, 4, 3) for an Accumulator of V views, seed then
+        being the V seeds (render_views_accumulate); a frame's spending is counted as the largest of the batch.  Returns the list
+        of every plan's totals -- one entry per plan made, each the dict (or, for views, the list of dicts) of plan_samples with
+        "budget" added, the last one being the plan that ended the loop unless the passes ran out -- and, with keep_maps,
+        (totals, maps)."""
+        history, maps, spent = [], [], 0
+        for k in range(int(passes)):
+            b = self._pass_budget(budget, spent, int(passes) - k)
+            if b == 0:
+                break
+            smap, totals = acc.plan(tolerance, pilot=pilot, cap=cap, budget=b, **plan_kw)
+            per_frame = totals if isinstance(totals, list) else [totals]
+            for t in per_frame:
+                t["budget"] = b
+            history.append(totals)
+            if all(t["planned"] == 0 for t in per_frame):
+                break
+            if keep_maps:
+                maps.append(smap)
+            if cameras is None:
+                self.render_accumulate(acc, smap, seed, cap=cap, rr=rr)
+            else:
+                self.render_views_accumulate(cameras, seed, acc, smap, cap=cap, rr=rr)
+            spent += max(t["planned"] for t in per_frame)
+        return (history, maps) if keep_maps else history
+
+    def render_converge_device(self, width, height, d_sum, d_m2, d_count, d_states, d_map, d_totals, d_workspace, tolerance, seed, passes=8,
+                               budget=None, pilot=PLAN_DEFAULTS["pilot"], cap=PLAN_DEFAULTS["cap"], cameras=None, rr=0.8, stream=None, device=0,
+                               **plan_kw):
+        """render_converge on the device's own planes, none of which visits the host: d_sum, d_m2, d_count, d_states (the planes of
+        render_accumulate_device), the caller's map d_map (uint32 or int32, a word per pixel), d_totals (32 bytes per frame, e.g. 4
+        int64 per frame) and d_workspace (plan_workspace_bytes) are torch tensors on the scene's device.  Plan and pass are
+        enqueued on stream (a raw stream, as the other device forms take; None: the default stream); between them the host reads
+        d_totals, 32 bytes per frame, and nothing else.  Returns the list of every plan's totals, as render_converge."""
+        import torch
+        frames = 1 if cameras is None else len(cameras)
+        ws_bytes = d_workspace.numel() * d_workspace.element_size()
+        if d_totals.numel() * d_totals.element_size() < 32 * frames:
+            raise ValueError("d_totals must hold 32 bytes per frame")
+        history, spent = [], 0
+        ext = torch.cuda.ExternalStream(stream, device=d_totals.device) if stream else torch.cuda.current_stream(d_totals.device)
+        for k in range(int(passes)):
+            b = self._pass_budget(budget, spent, int(passes) - k)
+            if b == 0:
+                break
+            plan_samples_device(d_sum.data_ptr(), d_m2.data_ptr(), d_count.data_ptr(), width, height, d_map.data_ptr(), d_totals.data_ptr(),
+                                d_workspace.data_ptr(), ws_bytes, tolerance, frame_count=frames, pilot=pilot, cap=cap, rgb_is_sum=True, budget=b,
+                                device=device, stream=stream, **plan_kw)
+            with torch.cuda.stream(ext):
+                raw = d_totals.reshape(-1).view(torch.uint8)[:32 * frames].cpu()   # the one read: ordered behind the plan on its stream
+            per_frame = _totals_dicts(np.frombuffer(raw.numpy().tobytes(), PLAN_TOTALS_DTYPE))
+            for t in per_frame:
+                t["budget"] = b
+            history.append(per_frame if cameras is not None else per_frame[0])
+            if all(t["planned"] == 0 for t in per_frame):
+                break
+            params = self.params(width, height, cap, 0 if cameras is not None else seed, "pixel", 0, None, rr)
+            if cameras is None:
+                self.render_accumulate_device(params, d_sum.data_ptr(), d_count.data_ptr(), d_states.data_ptr(), d_m2.data_ptr(), d_map.data_ptr(), stream=stream)
+            else:
+                self.render_views_accumulate_device(params, cameras, seed, d_sum.data_ptr(), d_count.data_ptr(), d_states.data_ptr(), d_m2.data_ptr(),
+                                                    d_map.data_ptr(), stream=stream)
+            spent += max(t["planned"] for t in per_frame)
+        return history
+
     # -- first-hit feature renders: albedo, normal, depth, coverage and id planes ---------------
     @staticmethod
     def _feature_planes(shape, want, out):
@@ -1116,6 +1225,11 @@ class Accumulator:
         Scene.render_features dict of the same shape -> (out, stats)"""
         return denoise(self.rgb(), self.m2, self.count, planes["albedo"], planes["normal"], planes["depth"], **kw)
 
+    def plan(self, tolerance, **kw):
+        """where the frame's next samples should go (plan_samples()): its own sum_rgb (rgb_is_sum=True), m2 and count -> (map,
+        totals); the map is what render_accumulate takes as add, with cap=cap"""
+        return plan_samples(self.sum_rgb, self.m2, self.count, tolerance, rgb_is_sum=True, **kw)
+
     def save(self, path):
         """the frame as it stands, into one .npz file (np.savez): Accumulator.load(path) continues it"""
         with open(path, "wb") as f:
@@ -1255,6 +1369,78 @@ def denoise_device(d_rgb, d_m2, d_count, d_albedo, d_normal, d_depth, width, hei
     st, stats = _stats(want_stats)
     _check(lib().ort_denoise_device(int(device), C.byref(p), C.byref(pl), int(width), int(height), int(frame_count), _ptr(d_out),
                                     _ptr(d_workspace), int(workspace_bytes), _ptr(stream), st))
+    return stats()
+
+
+# ---- planning the next pass's sample map (ort_sampleplan.h) -----------------------------------------
+def _plan_params(tolerance, floor, radius, pilot, min_add, cap, rgb_is_sum, budget):
+    for name, v in (("radius", radius), ("pilot", pilot), ("min_add", min_add), ("cap", cap)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("%s must fit an unsigned 32-bit word, got %r" % (name, v))
+    budget = 0 if budget is None else int(budget)
+    if not 0 <= budget <= 0xFFFFFFFFFFFFFFFF:
+        raise ValueError("budget must fit an unsigned 64-bit word, got %r" % (budget,))
+    return PlanParams(float(tolerance), float(floor), int(radius), int(pilot), int(min_add), int(cap), 1 if rgb_is_sum else 0, 0, budget)
+
+
+def _totals_dicts(records):
+    """PLAN_TOTALS_DTYPE records -> a list of dicts"""
+    return [dict(wanted=int(r["wanted"]), planned=int(r["planned"]), unconverged=int(r["unconverged"]), unknown=int(r["unknown"]),
+                 invalid=int(r["invalid"]), worst=np.float32(r["worst"])) for r in records]
+
+
+def plan_workspace_bytes(width, height, frames=1):
+    n = C.c_uint64(0)
+    _check(lib().ort_plan_samples_workspace_bytes(int(width), int(height), int(frames), C.byref(n)))
+    return n.value
+
+
+def plan_samples(rgb, m2, count, tolerance, floor=PLAN_DEFAULTS["floor"], radius=PLAN_DEFAULTS["radius"], pilot=PLAN_DEFAULTS["pilot"],
+                 min_add=PLAN_DEFAULTS["min_add"], cap=PLAN_DEFAULTS["cap"], rgb_is_sum=False, budget=None, device=0, out=None, want_stats=False):
+    """ort_plan_samples: the colour rgb (H, W, 3) -- the mean, or with rgb_is_sum the undivided sum --, the sums of squared sample
+    luminance m2 (H, W) and the sample counts count (H, W) uint32 -> (map (H, W) uint32, totals dict): for every pixel the samples
+    that bring the worst squared relative standard error within its (2 radius + 1)^2 window down to tolerance^2 at the variance
+    measured so far, at least min_add and at most cap; pilot for a pixel that has had fewer than 2 samples; scaled down by integer
+    division where the frame's sum passes budget (include/ort.h gives the rule operation by operation).  The map is what
+    render_sample_map and render_accumulate take, with cap as their cap.  totals: wanted, planned, unconverged, unknown, invalid,
+    worst.  A leading V on every array is a batch of V frames, each planned on its own with its own budget: totals is a list.
+    want_stats: (map, totals, stats)."""
+    count = np.ascontiguousarray(count, dtype="<u4")
+    if count.ndim not in (2, 3):
+        raise ValueError("count must be (H, W) or (V, H, W), got shape %s" % (count.shape,))
+    shape = count.shape
+    planes = []
+    for name, a, sh in (("rgb", rgb, shape + (3,)), ("m2", m2, shape)):
+        a = np.ascontiguousarray(a, dtype="<f4")
+        if a.shape != sh:
+            raise ValueError("%s must have shape %s, got %s" % (name, sh, a.shape))
+        planes.append(a)
+    if out is None:
+        out = np.empty(shape, "<u4")
+    elif not _is_plane(out, shape, "<u4"):
+        raise ValueError("out must be a C-contiguous uint32 array of shape %s" % (shape,))
+    frames = 1 if count.ndim == 2 else shape[0]
+    p = _plan_params(tolerance, floor, radius, pilot, min_add, cap, rgb_is_sum, budget)
+    pl = PlanPlanes(planes[0].ctypes.data, planes[1].ctypes.data, count.ctypes.data)
+    totals = np.zeros(frames, PLAN_TOTALS_DTYPE)
+    st, stats = _stats()
+    _check(lib().ort_plan_samples(int(device), C.byref(p), C.byref(pl), shape[-1], shape[-2], frames, out.ctypes.data, totals.ctypes.data, st))
+    t = _totals_dicts(totals)
+    t = t[0] if count.ndim == 2 else t
+    return (out, t, stats()) if want_stats else (out, t)
+
+
+def plan_samples_device(d_rgb, d_m2, d_count, width, height, d_map, d_totals, d_workspace, workspace_bytes, tolerance, frame_count=1,
+                        floor=PLAN_DEFAULTS["floor"], radius=PLAN_DEFAULTS["radius"], pilot=PLAN_DEFAULTS["pilot"], min_add=PLAN_DEFAULTS["min_add"],
+                        cap=PLAN_DEFAULTS["cap"], rgb_is_sum=False, budget=None, device=0, stream=None, want_stats=False):
+    """ort_plan_samples_device: raw device pointers (torch data_ptr()) of the three planes, of the map, of frame_count entries of
+    totals (32 bytes each, PLAN_TOTALS_DTYPE; 8-byte aligned) and of a workspace of plan_workspace_bytes; the totals are zeroed
+    and the kernels enqueued on stream, waits only for stats -> stats or None"""
+    p = _plan_params(tolerance, floor, radius, pilot, min_add, cap, rgb_is_sum, budget)
+    pl = PlanPlanes(*[p_ if p_ else None for p_ in (d_rgb, d_m2, d_count)])
+    st, stats = _stats(want_stats)
+    _check(lib().ort_plan_samples_device(int(device), C.byref(p), C.byref(pl), int(width), int(height), int(frame_count), _ptr(d_map),
+                                         _ptr(d_totals), _ptr(d_workspace), int(workspace_bytes), _ptr(stream), st))
     return stats()
 
 

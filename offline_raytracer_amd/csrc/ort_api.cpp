@@ -778,6 +778,43 @@ static int denoise_common(int device, bool host, const ort_denoise_params *p, co
     int rc = ort::device_denoise(device, host, *p, *in, width, height, frame_count, out_rgb, workspace, hip_stream, stats, &err);
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
+/* ---- the sample planner (ort_sampleplan.h, device_plan_samples): no scene, the order of the checks is the call's contract (include/ort.h) ---- */
+static int ort_plan_samples_workspace_bytes_impl(int32_t width, int32_t height, uint32_t frame_count, uint64_t *bytes) {
+    if (!bytes) return fail(ORT_ERR_INVALID, "null argument");
+    *bytes = 0;
+    if (frame_count == 0) return ORT_OK;
+    if (width < 1 || height < 1 || (uint64_t)frame_count * (uint64_t)width * (uint64_t)height >= (1ull << 31)) return fail(ORT_ERR_INVALID, "bad frame size");
+    *bytes = 4ull * ((uint64_t)frame_count * (uint64_t)width * (uint64_t)height);
+    return ORT_OK;
+}
+static int plan_common(int device, bool host, const ort_plan_params *p, const ort_plan_planes *in, int32_t width, int32_t height, uint32_t frame_count,
+                       void *sample_map, void *totals, void *workspace, uint64_t workspace_bytes, void *hip_stream, ort_stats *stats) {
+    if (frame_count == 0) return ORT_OK;
+    if (!p || !in) return fail(ORT_ERR_INVALID, "null params or planes struct");
+    const void *ptrs[] = {in->rgb, in->m2, in->count, sample_map};
+    for (const void *q : ptrs)
+        if (!q) return fail(ORT_ERR_INVALID, "null plane (rgb, m2, count and sample_map are required)");
+    if (!totals) return fail(ORT_ERR_INVALID, "null totals");
+    for (const void *q : ptrs)
+        if ((uintptr_t)q & 3u) return fail(ORT_ERR_INVALID, "plane or sample_map not 4-byte aligned");
+    if ((uintptr_t)totals & 7u) return fail(ORT_ERR_INVALID, "totals not 8-byte aligned");
+    if (width < 1 || height < 1 || (uint64_t)frame_count * (uint64_t)width * (uint64_t)height >= (1ull << 31)) return fail(ORT_ERR_INVALID, "bad frame size");
+    if (!(p->tolerance > 0.0f) || !(p->tolerance <= FLT_MAX) || !(p->tolerance * p->tolerance > 0.0f)) return fail(ORT_ERR_INVALID, "tolerance must be finite and > 0, and so must its square");
+    if (!(p->floor > 0.0f) || !(p->floor <= FLT_MAX)) return fail(ORT_ERR_INVALID, "floor must be finite and > 0");
+    if (p->radius > 3) return fail(ORT_ERR_INVALID, "radius must be at most 3");
+    if (p->min_add < 1) return fail(ORT_ERR_INVALID, "min_add must be at least 1");
+    if (p->cap < 1 || p->cap > (1u << 24)) return fail(ORT_ERR_INVALID, "cap must be within [1, 1 << 24]");
+    if (p->rgb_is_sum > 1) return fail(ORT_ERR_INVALID, "rgb_is_sum must be 0 or 1");
+    if (p->reserved != 0) return fail(ORT_ERR_INVALID, "reserved must be 0");
+    if (p->budget > (1ull << 39)) return fail(ORT_ERR_INVALID, "budget must be at most 1 << 39");
+    if (!host) {
+        const uint64_t need = 4ull * ((uint64_t)frame_count * (uint64_t)width * (uint64_t)height);
+        if (!workspace || ((uintptr_t)workspace & 3u) || workspace_bytes < need) return fail(ORT_ERR_INVALID, "null, misaligned or short workspace (ort_plan_samples_workspace_bytes)");
+    }
+    std::string err;
+    int rc = ort::device_plan_samples(device, host, *p, *in, width, height, frame_count, sample_map, totals, workspace, hip_stream, stats, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
 static int ort_comm_unique_id_impl(void *id) {
     if (!id) return fail(ORT_ERR_INVALID, "null argument");
     std::string err;
@@ -880,6 +917,9 @@ int ort_unpack_blocks_device(const void *d_packed, int32_t width, int32_t height
 int ort_denoise_workspace_bytes(int32_t width, int32_t height, uint32_t frame_count, uint64_t *bytes) { return guarded([&]() { return ort_denoise_workspace_bytes_impl(width, height, frame_count, bytes); }); }
 int ort_denoise(int device, const ort_denoise_params *p, const ort_denoise_planes *in, int32_t width, int32_t height, uint32_t frame_count, float *out_rgb, ort_stats *stats) { return guarded([&]() { return denoise_common(device, true, p, in, width, height, frame_count, out_rgb, nullptr, 0, nullptr, stats); }); }
 int ort_denoise_device(int device, const ort_denoise_params *p, const ort_denoise_planes *in, int32_t width, int32_t height, uint32_t frame_count, void *d_out_rgb, void *d_workspace, uint64_t workspace_bytes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return denoise_common(device, false, p, in, width, height, frame_count, d_out_rgb, d_workspace, workspace_bytes, hip_stream, stats); }); }
+int ort_plan_samples_workspace_bytes(int32_t width, int32_t height, uint32_t frame_count, uint64_t *bytes) { return guarded([&]() { return ort_plan_samples_workspace_bytes_impl(width, height, frame_count, bytes); }); }
+int ort_plan_samples(int device, const ort_plan_params *p, const ort_plan_planes *in, int32_t width, int32_t height, uint32_t frame_count, uint32_t *sample_map, ort_plan_totals *totals, ort_stats *stats) { return guarded([&]() { return plan_common(device, true, p, in, width, height, frame_count, sample_map, totals, nullptr, 0, nullptr, stats); }); }
+int ort_plan_samples_device(int device, const ort_plan_params *p, const ort_plan_planes *in, int32_t width, int32_t height, uint32_t frame_count, void *d_sample_map, void *d_totals, void *d_workspace, uint64_t workspace_bytes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return plan_common(device, false, p, in, width, height, frame_count, d_sample_map, d_totals, d_workspace, workspace_bytes, hip_stream, stats); }); }
 int ort_comm_unique_id(void *id) { return guarded([&]() { return ort_comm_unique_id_impl(id); }); }
 int ort_comm_create(const void *id, int rank, int world, int device, ort_comm **out) { return guarded([&]() { return ort_comm_create_impl(id, rank, world, device, out); }); }
 int ort_comm_create_local(int world, const int *devices, ort_comm **out) { return guarded([&]() { return ort_comm_create_local_impl(world, devices, out); }); }

@@ -5,6 +5,7 @@
  * (plan_variant, ort_plan.h): kLaunchers below pairs every entry of that header's list of built kernels with this unit's kernel,
  * which that instantiates, or a sibling unit's launcher.  A render and a ray query share the steps around their kernels.
  * The denoiser's kernels (ort_denoise.h) are launched from here too (device_denoise): they need no scene and no plan.
+ * So are the sample planner's (ort_sampleplan.h, device_plan_samples).
  */
 #include <algorithm>
 #include <memory>
@@ -15,6 +16,7 @@
 #include "ort_plan.h"
 #include "ort_setup.h"
 #include "ort_denoise.h" /* the denoiser's pixel functions and kernels (namespace ortdn); device_denoise below launches them */
+#include "ort_sampleplan.h" /* the sample planner's (namespace ortsp); device_plan_samples below launches them */
 
 #ifndef ORT_HOST_SIM /* tools/host_sim.cpp drives the lane code itself and has no device */
 namespace ort {
@@ -954,6 +956,84 @@ int device_denoise(int device, bool host, const ort_denoise_params &p, const ort
         stats->kernel_ms = ms;
     }
     if (host) ORT_HIP(hipMemcpy(out_rgb, d_out, 12 * n, hipMemcpyDeviceToHost));
+    return ORT_OK;
+}
+
+/* ---- the sample planner (ort_sampleplan.h): error, want, scale, one after the other on one stream; the device decides whether a
+   frame is scaled, so nothing comes back to the host between them.  No scene: the call names its device.  host: the caller's
+   planes are staged whole, the map, the totals and the workspace are this call's own and are copied back; otherwise every pointer
+   is the device's, nothing is allocated and the kernels are enqueued on stream behind the zeroing of the totals (the call waits
+   only for stats).  The arguments are checked by the caller (ort_api.cpp: plan_common). */
+int device_plan_samples(int device, bool host, const ort_plan_params &p, const ort_plan_planes &in, int32_t w, int32_t h, uint32_t frames, void *sample_map,
+                        void *totals, void *workspace, void *stream_, ort_stats *stats, std::string *err) {
+    static_assert(sizeof(ort_plan_totals) == sizeof(ortsp::Totals) && offsetof(ort_plan_totals, worst) == offsetof(ortsp::Totals, worst_bits) &&
+                      offsetof(ort_plan_totals, unconverged) == offsetof(ortsp::Totals, unconverged), "ortsp::Totals is ort_plan_totals");
+    int count = 0;
+    int rc = device_count(&count, err);
+    if (rc != ORT_OK) return rc;
+    if (device < 0 || device >= count) { *err = "no such HIP device"; return ORT_ERR_NO_DEVICE; }
+    ORT_HIP(hipSetDevice(device));
+    hipStream_t stream = host ? nullptr : (hipStream_t)stream_;
+    const size_t n = (size_t)frames * (size_t)w * (size_t)h;
+    const size_t totals_bytes = sizeof(ortsp::Totals) * (size_t)frames;
+    DevBuf d_rgb, d_m2, d_count, d_map, d_totals, d_ws;
+    const void *rgb = in.rgb, *m2 = in.m2, *cnt = in.count;
+    void *d_sample_map = sample_map, *d_tot = totals;
+    if (host) {
+        struct { DevBuf *buf; const void **src; size_t bytes; } stage[] = {{&d_rgb, &rgb, 12 * n}, {&d_m2, &m2, 4 * n}, {&d_count, &cnt, 4 * n}};
+        for (auto &s : stage) {
+            if ((rc = s.buf->ensure(s.bytes, err))) return rc;
+            ORT_HIP(hipMemcpy(s.buf->p, *s.src, s.bytes, hipMemcpyHostToDevice));
+            *s.src = s.buf->p;
+        }
+        if ((rc = d_map.ensure(4 * n, err)) || (rc = d_totals.ensure(totals_bytes, err)) || (rc = d_ws.ensure(ortsp::kWorkspaceBytesPerPixel * n, err))) return rc;
+        d_sample_map = d_map.p;
+        d_tot = d_totals.p;
+        workspace = d_ws.p;
+    }
+    const ortsp::Params prm{p.tolerance * p.tolerance, p.floor, p.radius, p.pilot, p.min_add, p.cap, p.rgb_is_sum, p.budget};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct EventGuard { hipEvent_t &a, &b; ~EventGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } guard{ev0, ev1};
+    if (stats) {
+        ORT_HIP(hipEventCreate(&ev0));
+        ORT_HIP(hipEventCreate(&ev1));
+        ORT_HIP(hipEventRecord(ev0, stream));
+    }
+    ORT_HIP(hipMemsetAsync(d_tot, 0, totals_bytes, stream));
+    /* a workgroup issues its atomics once per frame it touched, and they all meet on the frame's 32 bytes: the grid is the measured
+       balance between that queue (about 10 ns a workgroup and total) and the lanes the window's loads want in flight -- at 1080p
+       256 .. 4096 workgroups give 0.147, 0.099, 0.087, 0.107, 0.168 ms at radius 1 (profiles/r26_sample_plan.md).  The tiles beyond
+       the grid are reached by stride */
+    constexpr uint64_t kMaxGrid = 1024;
+    const uint32_t tiles_x = ((uint32_t)w + ortsp::kTileW - 1u) / ortsp::kTileW, tiles_y = ((uint32_t)h + ortsp::kTileH - 1u) / ortsp::kTileH;
+    const uint64_t tiles = (uint64_t)tiles_x * tiles_y * frames;
+    const dim3 grid((uint32_t)std::min(tiles, kMaxGrid));
+    float *e_plane = (float *)workspace;
+    ortsp::Totals *tot = (ortsp::Totals *)d_tot;
+    hipLaunchKernelGGL(ortsp::sampleplan_error, grid, dim3(256), 0, stream, (const float *)rgb, (const float *)m2, (const uint32_t *)cnt, e_plane, tot, w, h, tiles_x,
+                       tiles_y, tiles, prm);
+    ORT_HIP(hipGetLastError());
+    /* the window from an LDS tile with halo wherever there is a window; ORT_PLAN_TILE=0 / 1 (a developer knob, read at every call)
+       forces the direct loads / the tile at every radius.  The map is the same either way */
+    const char *knob = getenv("ORT_PLAN_TILE");
+    const bool tile = knob && (knob[0] == '0' || knob[0] == '1') ? knob[0] == '1' : p.radius >= 1;
+    hipLaunchKernelGGL(tile ? ortsp::sampleplan_want<true> : ortsp::sampleplan_want<false>, grid, dim3(256), 0, stream, (const float *)e_plane, (const uint32_t *)cnt,
+                       (uint32_t *)d_sample_map, tot, w, h, tiles_x, tiles_y, tiles, prm);
+    ORT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ortsp::sampleplan_scale, grid, dim3(256), 0, stream, (uint32_t *)d_sample_map, tot, w, h, tiles_x, tiles_y, tiles, prm);
+    ORT_HIP(hipGetLastError());
+    if (stats) {
+        ORT_HIP(hipEventRecord(ev1, stream));
+        ORT_HIP(hipEventSynchronize(ev1));
+        float ms = 0.0f;
+        ORT_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+        *stats = ort_stats{};
+        stats->kernel_ms = ms;
+    }
+    if (host) {
+        ORT_HIP(hipMemcpy(sample_map, d_sample_map, 4 * n, hipMemcpyDeviceToHost));
+        ORT_HIP(hipMemcpy(totals, d_tot, totals_bytes, hipMemcpyDeviceToHost));
+    }
     return ORT_OK;
 }
 

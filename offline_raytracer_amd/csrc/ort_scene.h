@@ -272,6 +272,11 @@ int device_render_features(Scene *scene, const ort_render_params *p, const ort_v
    the caller's and the passes are enqueued on stream.  The arguments are checked by the caller */
 int device_denoise(int device, bool host, const ort_denoise_params &p, const ort_denoise_planes &in, int32_t w, int32_t h, uint32_t frames, void *out_rgb,
                    void *workspace, void *stream, ort_stats *stats, std::string *err);
+/* the sample planner (include/ort.h: ort_plan_samples), on `device` and without a scene.  host: the planes, the map and the totals
+   are the caller's memory, staged whole, and the workspace is the call's own (workspace unread); otherwise all are device pointers,
+   the workspace is the caller's and the kernels are enqueued on stream.  The arguments are checked by the caller */
+int device_plan_samples(int device, bool host, const ort_plan_params &p, const ort_plan_planes &in, int32_t w, int32_t h, uint32_t frames, void *sample_map,
+                        void *totals, void *workspace, void *stream, ort_stats *stats, std::string *err);
 /* ort_comm.cpp */
 struct Comm;
 uint64_t comm_shard_blocks(int32_t w, int32_t h, uint32_t index, uint32_t count);
