@@ -603,7 +603,7 @@ static int render_adaptive_common(ort_scene *s, const ort_render_params *p, cons
         [&] { return check_first_plane(batch, host, views, out_rgb, "null views or framebuffer", "null framebuffer", "null device framebuffer"); },
         [&](ort_render_params *q) { q->spp = ad && ad->max_spp ? ad->max_spp : 1u; }, /* a null ad or a max_spp of 0 is check_adaptive's to name */
         [&](const ort_render_params &) { return check_adaptive(ad); },
-        [&](const ort_render_params &q, ort::RenderCall c) { c.ad = ad; return run_render(s, &q, c, out_rgb, out_spp, out_m2, states); });
+        [&](const ort_render_params &q, ort::RenderCall c) { c.kind = ort::RK_ADAPTIVE; c.ad = ad; return run_render(s, &q, c, out_rgb, out_spp, out_m2, states); });
 }
 
 /* Light-group renders.  Own checks: spp above 1 << 24, the groups (a null struct or table, another material count than the scene's,
@@ -629,7 +629,7 @@ static int render_groups_common(ort_scene *s, const ort_render_params *p, const 
             return check_ptrs({{out_groups, true, 4}, {out_rgb, false, 4}, {states, false, 4}}, "", "", "out_groups, out_rgb and final_states must be 4-byte aligned");
         },
         [&](const ort_render_params &q, ort::RenderCall c) {
-            c.groups = groups; c.out_groups = out_groups;
+            c.kind = ort::RK_GROUPS; c.groups = groups; c.out_groups = out_groups;
             return run_render(s, &q, c, out_rgb, nullptr, nullptr, states);
         });
 }
@@ -650,7 +650,7 @@ static int render_sample_map_common(ort_scene *s, const ort_render_params *p, co
             return check_ptrs({{sample_map, true, 4}, {out_rgb, true, 4}, {out_m2, false, 4}, {states, false, 4}}, "", "",
                               "sample_map, out_rgb, out_m2 and final_states must be 4-byte aligned");
         },
-        [&](const ort_render_params &q, ort::RenderCall c) { c.sample_map = sample_map; return run_render(s, &q, c, out_rgb, nullptr, out_m2, states); });
+        [&](const ort_render_params &q, ort::RenderCall c) { c.kind = ort::RK_SAMPLE_MAP; c.sample_map = sample_map; return run_render(s, &q, c, out_rgb, nullptr, out_m2, states); });
 }
 
 /* Accumulating renders: render_sample_map_common's order with acc where the map stands.  Nulls: the views (the views form); no plane
@@ -673,7 +673,7 @@ static int render_accumulate_common(ort_scene *s, const ort_render_params *p, co
                               "sum_rgb, m2, count, states, sample_map and out_rgb must be 4-byte aligned");
         },
         [&](const ort_render_params &q, ort::RenderCall c) {
-            c.sample_map = sample_map; c.acc_sum = acc->sum_rgb;
+            c.kind = ort::RK_ACCUMULATE; c.sample_map = sample_map; c.acc_sum = acc->sum_rgb;
             return run_render(s, &q, c, out_rgb, acc->count, acc->m2, acc->states);
         });
 }

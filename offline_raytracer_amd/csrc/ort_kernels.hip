@@ -2,8 +2,9 @@
  * ort_kernels.hip -- host side of the path-trace kernels: scene upload and the render and ray-query calls as HIP plumbing
  * (device_render turns the LaunchPlan of ort_plan.h, where the launch policy lives, into buffers and launches), and the
  * kernels' four-waves-per-SIMD build (the lane code itself is ort_lane.h).  A plan becomes a launch by its KernelVariant
- * (plan_variant, ort_plan.h): kLaunchers below pairs every entry of that header's list of built kernels with this unit's kernel,
- * which that instantiates, or a sibling unit's launcher.  A render and a ray query share the steps around their kernels.
+ * (plan_variant, ort_plan.h): a variant of a pixel-job kind's family, built in full, goes to the sibling unit's one entry point
+ * (ort_launch_pixel_jobs); for the others kLaunchers below pairs every entry of that header's list of built kernels with this
+ * unit's kernel, which that instantiates, or a sibling unit's launcher.  A render and a ray query share the steps around their kernels.
  * The denoiser's kernels (ort_denoise.h) are launched from here too (device_denoise): they need no scene and no plan.
  * So are the sample planner's (ort_sampleplan.h, device_plan_samples).
  */
@@ -268,29 +269,13 @@ static int launch_wavefront(DeviceScene *d, const LaunchPlan &, const SceneView 
     return ORT_OK;
 }
 
-/* the sibling units' kernels, as launchers of launch_wavefront's kind */
+/* the five-waves unit's kernels, as a launcher of launch_wavefront's kind */
 static int launch_five_waves(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
     ort_launch_w5(plan_variant(pl), pl.grid, stream, sv, hot);
     return ORT_OK;
 }
-static int launch_adaptive(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
-    ort_launch_render_adaptive(plan_variant(pl), pl.grid, stream, sv, hot);
-    return ORT_OK;
-}
-static int launch_groups(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
-    ort_launch_render_groups(plan_variant(pl), pl.grid, stream, sv, hot);
-    return ORT_OK;
-}
-static int launch_sample_map(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
-    ort_launch_render_sample_map(plan_variant(pl), pl.grid, stream, sv, hot);
-    return ORT_OK;
-}
-static int launch_accumulate(DeviceScene *, const LaunchPlan &pl, const SceneView &sv, const RenderView &, const RenderHot &hot, hipStream_t stream, std::string *) {
-    ort_launch_render_accumulate(plan_variant(pl), pl.grid, stream, sv, hot);
-    return ORT_OK;
-}
 
-/* What launches each of the built kernels (kBuiltKernels, ort_plan.h), in that list's order: a kernel of this unit, which its
+/* What launches each of the listed kernels (kBuiltKernels, ort_plan.h), in that list's order: a kernel of this unit, which its
    entry here instantiates, or the host function that launches what another family is made of */
 struct Launcher {
     KernelVariant variant;
@@ -304,10 +289,6 @@ constexpr Launcher views() { return {{KF_LOOP_VIEWS, C, D, T, I, false}, pt_pers
 template <bool C, bool D>
 constexpr Launcher exchange() { return {{KF_EXCHANGE, C, D, true, true, false}, pt_persistent_x<C, D>, nullptr}; }
 constexpr Launcher five(bool d) { return {{KF_FIVE, false, d, true, true, false}, nullptr, launch_five_waves}; }
-constexpr Launcher adaptive(bool c, bool d, bool t) { return {{KF_ADAPTIVE, c, d, t, true, false}, nullptr, launch_adaptive}; }
-constexpr Launcher groups(bool c, bool d, bool t) { return {{KF_GROUPS, c, d, t, true, false}, nullptr, launch_groups}; }
-constexpr Launcher sample_map(bool c, bool d, bool t) { return {{KF_SAMPLE_MAP, c, d, t, true, false}, nullptr, launch_sample_map}; }
-constexpr Launcher accumulate(bool c, bool d, bool t) { return {{KF_ACCUM, c, d, t, true, false}, nullptr, launch_accumulate}; }
 constexpr Launcher kLaunchers[] = {
     {{KF_WAVEFRONT, false, false, false, false, false}, nullptr, launch_wavefront<false>},
     {{KF_WAVEFRONT, true, false, false, false, false}, nullptr, launch_wavefront<true>},
@@ -319,23 +300,18 @@ constexpr Launcher kLaunchers[] = {
     views<true, false, false>(), views<true, false, true>(),
     exchange<false, false>(), exchange<false, true>(), exchange<true, true>(),
     five(false), five(true),
-    adaptive(false, false, false), adaptive(false, false, true), adaptive(false, true, false), adaptive(false, true, true),
-    adaptive(true, false, false), adaptive(true, false, true), adaptive(true, true, false), adaptive(true, true, true),
-    groups(false, false, false), groups(false, false, true), groups(false, true, false), groups(false, true, true),
-    groups(true, false, false), groups(true, false, true), groups(true, true, false), groups(true, true, true),
-    sample_map(false, false, false), sample_map(false, false, true), sample_map(false, true, false), sample_map(false, true, true),
-    sample_map(true, false, false), sample_map(true, false, true), sample_map(true, true, false), sample_map(true, true, true),
-    accumulate(false, false, false), accumulate(false, false, true), accumulate(false, true, false), accumulate(false, true, true),
-    accumulate(true, false, false), accumulate(true, false, true), accumulate(true, true, false), accumulate(true, true, true),
 };
 constexpr bool launchers_match(size_t i = 0) { return i == kBuiltKernelCount || (kLaunchers[i].variant == kBuiltKernels[i] && launchers_match(i + 1)); }
 static_assert(sizeof(kLaunchers) / sizeof(kLaunchers[0]) == kBuiltKernelCount && launchers_match(),
               "kLaunchers holds the entries of kBuiltKernels (ort_plan.h), all of them, in its order");
 
-/* the kernel a plan names, launched; a plan that names one nobody built is an error, not a fallback */
+/* the kernel a plan names, launched: a pixel-job kind's by the sibling unit that builds those families in full, any other by its
+   place in the list; a plan that names one nobody built is an error, not a fallback */
 static int launch_path_tracer(DeviceScene *d, const LaunchPlan &pl, const SceneView &sv, const RenderView &rv, const RenderHot &hot, hipStream_t stream, std::string *err) {
-    const size_t i = built_index(plan_variant(pl));
-    if (i == kBuiltKernelCount) { *err = "internal: no kernel is built for this launch plan"; return ORT_ERR_INTERNAL; }
+    const KernelVariant v = plan_variant(pl);
+    if (!variant_built(v)) { *err = "internal: no kernel is built for this launch plan"; return ORT_ERR_INTERNAL; }
+    if (pixel_job_family(v.family)) { ort_launch_pixel_jobs(v, pl.grid, stream, sv, hot); return ORT_OK; }
+    const size_t i = built_index(v);
     if (kLaunchers[i].host) return kLaunchers[i].host(d, pl, sv, rv, hot, stream, err);
     hipLaunchKernelGGL(kLaunchers[i].kernel, dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot);
     return ORT_OK;
@@ -511,11 +487,10 @@ static int print_util_diag(const DeviceScene *d, std::string *err) {
     return ORT_OK;
 }
 
-/* The camera render call, plain, (c.ad) adaptive, (c.groups) split by light group, (c.sample_map) cut by the caller's map or
-   (c.acc_sum) continued from the caller's planes.  What
-   runs, on which grid and with which thresholds is plan_render's, plan_render_adaptive's, plan_render_groups',
-   plan_render_sample_map's or plan_render_accumulate's decision (ort_plan.h), and what the RenderView says besides pointers is render_view's (ort_setup.h); this
-   is the plumbing around them: settle the previous call, plan, staging, views, buffers, launch, combine, finish */
+/* The camera render call, of the kind the caller states (c.kind): plain, adaptive (c.ad), split by light group (c.groups), cut
+   by the caller's map (c.sample_map) or continued from the caller's planes (c.acc_sum, with or without a map).  What runs, on
+   which grid and with which thresholds is plan_render's or, for a pixel-job kind, plan_pixel_jobs' decision (ort_plan.h), and
+   what the RenderView says besides pointers is render_view's (ort_setup.h); this is the plumbing around them: settle the previous call, plan, staging, views, buffers, launch, combine, finish */
 int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c, void *out_rgb, void *out_spp, void *out_m2, void *states, std::string *err) {
     DeviceScene *d = scene->dev;
     if (!d) { *err = "scene is not uploaded to a device (ort_scene_upload)"; return ORT_ERR_NO_DEVICE; }
@@ -529,11 +504,8 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
 
     SceneView sv = scene_view(scene, d);
     const SceneTraits traits = scene_traits(scene, d);
-    const LaunchPlan pl = c.acc_sum ? plan_render_accumulate(traits, *p, d->knobs, view_count)
-                          : c.sample_map ? plan_render_sample_map(traits, *p, d->knobs, view_count)
-                          : c.groups ? plan_render_groups(traits, *p, d->knobs, view_count)
-                          : c.ad ? plan_render_adaptive(traits, *p, d->knobs, view_count)
-                               : plan_render(traits, *p, c.jobs != nullptr, c.job_count, /* w5_layout_ok */ true, d->knobs, view_count);
+    const LaunchPlan pl = c.kind != RK_PLAIN ? plan_pixel_jobs(c.kind, traits, *p, d->knobs, view_count)
+                                             : plan_render(traits, *p, c.jobs != nullptr, c.job_count, /* w5_layout_ok */ true, d->knobs, view_count);
     sv.util = pl.util ? d->ctrl() + 8 : nullptr;
     if (pl.wide) sv.nodes = d->nodes4.as<const float4>();
     /* the camera: the scene's own; a batch of one view is the same call with that view's camera and seed; the lanes of a larger

@@ -13,42 +13,25 @@
  * the irradiance unit holds, instead of adding a sixth.  The sample-map kernels make it twenty-four: measured, the unit then
  * compiles in about half the time ort_kernels.hip takes beside it, so the build's wall time is still that unit's
  * (profiles/r23_sample_map.md).  The eight pt_accumulate kernels (LF_SPPMAP | LF_ACCUM) make it thirty-two: the unit then
- * takes three quarters of ort_kernels.hip's time (profiles/r24_accumulate.md), launched through ort_launch_render_accumulate.
- * device_render (ort_kernels.hip), given a stopping rule, a group table or a sample map, launches
- * them through ort_launch_render_adaptive, ort_launch_render_groups or ort_launch_render_sample_map.
+ * takes three quarters of ort_kernels.hip's time (profiles/r24_accumulate.md).
+ * All four families are built in full, every <counters, diffuse, tabs>, so that nothing lists them (variant_built, ort_plan.h):
+ * device_render (ort_kernels.hip), for a render of a kind that is not plain, launches them through the one entry point below.
  */
 #define ORT_NS ort_ra /* the limits: ort_lane.h's defaults */
 #include "ort_lane.h"
 
-/* KF_ADAPTIVE: implicit jobs over a batch of views.  The caller's own SceneView and RenderHot: the argument structs are
-   ort_lane.h's one definition */
-void ort_launch_render_adaptive(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot) {
+/* A variant of a pixel-job kind's family (KF_ADAPTIVE to KF_ACCUM): implicit jobs over a batch of views.  The caller's own
+   SceneView and RenderHot: the argument structs are ort_lane.h's one definition.  A new kind is one more case */
+void ort_launch_pixel_jobs(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot) {
     using namespace ort_ra;
     ort::with_bools([&](auto C, auto D, auto T) {
-        hipLaunchKernelGGL((pt_adaptive<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, stream, sv, hot);
-    }, v.counters, v.diffuse, v.tabs);
-}
-
-/* KF_GROUPS: likewise */
-void ort_launch_render_groups(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot) {
-    using namespace ort_ra;
-    ort::with_bools([&](auto C, auto D, auto T) {
-        hipLaunchKernelGGL((pt_groups<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, stream, sv, hot);
-    }, v.counters, v.diffuse, v.tabs);
-}
-
-/* KF_SAMPLE_MAP: likewise */
-void ort_launch_render_sample_map(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot) {
-    using namespace ort_ra;
-    ort::with_bools([&](auto C, auto D, auto T) {
-        hipLaunchKernelGGL((pt_sample_map<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, stream, sv, hot);
-    }, v.counters, v.diffuse, v.tabs);
-}
-
-/* KF_ACCUM: likewise */
-void ort_launch_render_accumulate(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot) {
-    using namespace ort_ra;
-    ort::with_bools([&](auto C, auto D, auto T) {
-        hipLaunchKernelGGL((pt_accumulate<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(grid), dim3(kBlock), 0, stream, sv, hot);
+        constexpr bool c = decltype(C)::value, d = decltype(D)::value, t = decltype(T)::value;
+        switch (v.family) {
+        case ort::KF_ADAPTIVE: hipLaunchKernelGGL((pt_adaptive<c, d, t>), dim3(grid), dim3(kBlock), 0, stream, sv, hot); break;
+        case ort::KF_GROUPS: hipLaunchKernelGGL((pt_groups<c, d, t>), dim3(grid), dim3(kBlock), 0, stream, sv, hot); break;
+        case ort::KF_SAMPLE_MAP: hipLaunchKernelGGL((pt_sample_map<c, d, t>), dim3(grid), dim3(kBlock), 0, stream, sv, hot); break;
+        case ort::KF_ACCUM: hipLaunchKernelGGL((pt_accumulate<c, d, t>), dim3(grid), dim3(kBlock), 0, stream, sv, hot); break;
+        default: break; /* launch_path_tracer sends no other family here */
+        }
     }, v.counters, v.diffuse, v.tabs);
 }

@@ -264,10 +264,7 @@ struct FeatureIO {
    ort_kernels.hip.  The flavour comes as named fields: a render kernel's KernelVariant (plan_variant, ort_plan.h), a query's
    QueryPlan; every other bool of the kernels is fixed by the family. */
 void ort_launch_w5(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);              /* KF_FIVE: ort_kernels_w5.hip */
-void ort_launch_render_adaptive(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot); /* KF_ADAPTIVE: ort_kernels_render_adaptive.hip */
-void ort_launch_render_groups(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);   /* KF_GROUPS: ort_kernels_render_adaptive.hip */
-void ort_launch_render_sample_map(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot); /* KF_SAMPLE_MAP: ort_kernels_render_adaptive.hip */
-void ort_launch_render_accumulate(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot); /* KF_ACCUM: ort_kernels_render_adaptive.hip */
+void ort_launch_pixel_jobs(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);      /* KF_ADAPTIVE to KF_ACCUM: ort_kernels_render_adaptive.hip */
 void ort_launch_radiance_adaptive(const ort::QueryPlan &pl, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);                    /* ort_kernels_adaptive.hip */
 void ort_launch_irradiance(const ort::QueryPlan &pl, bool adaptive, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);            /* ort_kernels_irradiance.hip */
 #endif

@@ -2,8 +2,9 @@
  * ort_plan.h -- the launch policy of the render call, of a batch of views and of the three ray queries, as arithmetic: what
  * ort_kernels.hip launches, with which grid and which thresholds, decided from a few facts about the uploaded scene
  * (SceneTraits), the render parameters or the ray count, and the developer knobs: plan_render for ort_render_image and
- * ort_render_views, plan_render_adaptive for ort_render_adaptive and ort_render_views_adaptive, plan_render_groups for ort_render_light_groups and
- * ort_render_views_light_groups, plan_render_sample_map for ort_render_sample_map and ort_render_views_sample_map, plan_render_accumulate for ort_render_accumulate and ort_render_views_accumulate, plan_ray_query for ort_raycast and ort_occluded, plan_radiance for ort_radiance.  Host-only and free of HIP,
+ * ort_render_views; plan_pixel_jobs, given the RenderKind, for the renders that cut one-pixel jobs over a batch of views
+ * (ort_render_adaptive, ort_render_light_groups, ort_render_sample_map, ort_render_accumulate and the views form of each);
+ * plan_ray_query for ort_raycast and ort_occluded, plan_radiance for ort_radiance.  Host-only and free of HIP,
  * so that tools/launch_plan.cpp and tests/test_launch_plan.py can hold the measured crossovers without a device.
  * ort_kernels.hip turns a LaunchPlan or a QueryPlan into launches and decides nothing.
  */
@@ -179,6 +180,11 @@ inline void plan_job_batches(unsigned long long job_count, unsigned long long la
     *batch_until = job_count > tail ? job_count - tail : 0ull;
 }
 
+/* What a camera render is: the plain one (plan_render), or one of the kinds that cut one-pixel jobs over a batch of views
+   (plan_pixel_jobs), each with a kernel family of its own (kind_family).  The caller of device_render states it (RenderCall::kind),
+   the plan carries it, and plan_variant turns it into the family: nobody infers it */
+enum RenderKind : int { RK_PLAIN = 0, RK_ADAPTIVE, RK_GROUPS, RK_SAMPLE_MAP, RK_ACCUMULATE };
+
 /* everything device_render decides before it touches the device */
 struct LaunchPlan {
     /* the kernel: wavefront <counters> | five waves <diffuse> | exchange <counters, diffuse> | plain loop <counters, diffuse, tabs,
@@ -189,10 +195,7 @@ struct LaunchPlan {
     /* a batch of views (ort_render_views, view_count > 1): the plain loop's VIEWS kernels, whose lanes read their camera from a
        per-view table; the job space is view_count times the single view's, the view outermost */
     bool views = false;
-    bool adaptive = false; /* the adaptive camera render (plan_render_adaptive): the pt_adaptive kernels <counters, diffuse, tabs> */
-    bool groups = false;   /* the light-group render (plan_render_groups): the pt_groups kernels <counters, diffuse, tabs> */
-    bool sample_map = false; /* the sample-map render (plan_render_sample_map): the pt_sample_map kernels <counters, diffuse, tabs> */
-    bool accumulate = false; /* the accumulating render (plan_render_accumulate): the pt_accumulate kernels <counters, diffuse, tabs> */
+    RenderKind kind = RK_PLAIN; /* other than plain (plan_pixel_jobs): that kind's kernels <counters, diffuse, tabs> */
     uint32_t view_count = 1;
     unsigned long long view_jobs = 0; /* jobs of one view (job_count / view_count) */
     unsigned int grid = 1;
@@ -346,15 +349,26 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
     return pl;
 }
 
-/* The launch of the adaptive camera render (ort_render_adaptive, ort_render_views_adaptive; the pt_adaptive kernels) over
-   view_count >= 1 frames: always the plain persistent loop at four waves, over the implicit one-pixel jobs of the PIXEL policy,
-   with the camera read from the view table -- the single frame is the one-view batch of the scene's own camera.  The job space is
-   plan_render's for a batch of views, [view][block][pixel], and so are the grid, the refill and descend thresholds and the batch
-   rules; p.spp and p.chunk are not read (a job's length is the stopping rule's to decide, at most max_spp).  The ray exchange,
-   the five-waves unit, the wide tree and wavefront mode are not built with the rule and their knobs are not looked at;
-   ORT_DEBUG_UTIL and ORT_DEBUG_DRAIN have no probes here.  Both BSDF flavours exist with counters, as for the radiance queries;
-   every variant is IMPLICIT.  No partial planes, no stashes: no workspace. */
-inline LaunchPlan plan_render_adaptive(const SceneTraits &t, const ort_render_params &p, const Knobs &kn, uint32_t view_count = 1) {
+/* The launch of a camera render that cuts one-pixel jobs over view_count >= 1 frames, of the kind given (not RK_PLAIN): always
+   the plain persistent loop at four waves, over the implicit one-pixel jobs of the PIXEL policy, with the camera read from the
+   view table -- the single frame is the one-view batch of the scene's own camera.  The job space is plan_render's for a batch of
+   views, [view][block][pixel], and so are the grid, the refill and descend thresholds and the batch rules; p.chunk is not read.
+   The ray exchange, the five-waves unit, the wide tree and wavefront mode are not built for these kinds and their knobs are not
+   looked at; ORT_DEBUG_UTIL and ORT_DEBUG_DRAIN have no probes here.  Both BSDF flavours exist with counters, as for the radiance
+   queries; every variant is IMPLICIT.  No partial planes, no stashes: no workspace.  The kinds have every field but `kind` in
+   common (tests/test_launch_plan.py and the kinds' *_host.py tests hold them to it); what a job is differs:
+   - RK_ADAPTIVE (ort_render_adaptive, ort_render_views_adaptive; the pt_adaptive kernels): p.spp is not read either -- a job's
+     length is the stopping rule's to decide, at most max_spp;
+   - RK_GROUPS (ort_render_light_groups, ort_render_views_light_groups; pt_groups): the group sums where the stopping rule
+     stands.  A job is p.spp samples long (render_view's to say);
+   - RK_SAMPLE_MAP (ort_render_sample_map, ort_render_views_sample_map; pt_sample_map): the caller's map where the stopping rule
+     stands.  The job space holds every pixel under the rect, whatever its word of the map says: the plan cannot read a map that
+     may live on the device, and a job of no samples ends where it is drawn.  p.spp is the cap on a job's length (render_view's to
+     say);
+   - RK_ACCUMULATE (ort_render_accumulate, ort_render_views_accumulate; pt_accumulate): the sample-map render's launch, for
+     kernels that start a pixel from the caller's planes.  Neither the map nor the planes' counts can be read here, so the job
+     space again holds every pixel under the rect */
+inline LaunchPlan plan_pixel_jobs(RenderKind kind, const SceneTraits &t, const ort_render_params &p, const Knobs &kn, uint32_t view_count = 1) {
     LaunchPlan pl;
     plan_loop_exits(tree_is_cache_resident(t.fast_tree_bytes, kn.cache_resident), kn, &pl.refill_below, &pl.descend_below);
     pl.blocks = block_grid_for(&p); /* the caller has refused shards: the blocks under the rect */
@@ -364,7 +378,7 @@ inline LaunchPlan plan_render_adaptive(const SceneTraits &t, const ort_render_pa
     pl.views = true;
     pl.view_count = view_count;
     pl.job_count = pl.view_jobs * view_count;
-    pl.adaptive = true;
+    pl.kind = kind;
     pl.counters = (p.flags & ORT_RENDER_COUNTERS) != 0;
     pl.diffuse = t.diffuse_only && !kn.general_kernel;
     pl.tabs = (t.tab_flags & kPlanAllTabs) == kPlanAllTabs && kn.lds_tables != 0;
@@ -373,39 +387,6 @@ inline LaunchPlan plan_render_adaptive(const SceneTraits &t, const ort_render_pa
     pl.grid = (unsigned int)(blocks < t.max_blocks ? blocks : t.max_blocks);
     if (pl.grid == 0) pl.grid = 1;
     plan_job_batches(pl.job_count, (unsigned long long)pl.grid * kPlanBlock, kn, &pl.job_batch, &pl.batch_until);
-    return pl;
-}
-
-/* The launch of the light-group render (ort_render_light_groups, ort_render_views_light_groups; the pt_groups kernels) over
-   view_count >= 1 frames: plan_render_adaptive's launch in every field -- views, JOBS_PIXEL, implicit, the plain loop at four waves,
-   both BSDF flavours with counters, no workspace -- with the group sums where the stopping rule stands.  A job is p.spp samples
-   long (render_view's to say); p.chunk is not read */
-inline LaunchPlan plan_render_groups(const SceneTraits &t, const ort_render_params &p, const Knobs &kn, uint32_t view_count = 1) {
-    LaunchPlan pl = plan_render_adaptive(t, p, kn, view_count);
-    pl.adaptive = false;
-    pl.groups = true;
-    return pl;
-}
-
-/* The launch of the sample-map render (ort_render_sample_map, ort_render_views_sample_map; the pt_sample_map kernels) over
-   view_count >= 1 frames: plan_render_adaptive's launch in every field, with the caller's map where the stopping rule stands.  The
-   job space holds every pixel under the rect, whatever its word of the map says: the plan cannot read a map that may live on the
-   device, and a job of no samples ends where it is drawn.  p.spp is the cap on a job's length (render_view's to say); p.chunk is
-   not read */
-inline LaunchPlan plan_render_sample_map(const SceneTraits &t, const ort_render_params &p, const Knobs &kn, uint32_t view_count = 1) {
-    LaunchPlan pl = plan_render_adaptive(t, p, kn, view_count);
-    pl.adaptive = false;
-    pl.sample_map = true;
-    return pl;
-}
-
-/* The launch of the accumulating render (ort_render_accumulate, ort_render_views_accumulate; the pt_accumulate kernels):
-   plan_render_sample_map's launch in every field, for kernels that start a pixel from the caller's planes.  Neither the map nor the
-   planes' counts can be read here, so the job space again holds every pixel under the rect */
-inline LaunchPlan plan_render_accumulate(const SceneTraits &t, const ort_render_params &p, const Knobs &kn, uint32_t view_count = 1) {
-    LaunchPlan pl = plan_render_sample_map(t, p, kn, view_count);
-    pl.sample_map = false;
-    pl.accumulate = true;
     return pl;
 }
 
@@ -420,25 +401,29 @@ struct KernelVariant {
 constexpr bool operator==(const KernelVariant &a, const KernelVariant &b) {
     return a.family == b.family && a.counters == b.counters && a.diffuse == b.diffuse && a.tabs == b.tabs && a.implicit == b.implicit && a.wide == b.wide;
 }
+/* the pixel-job kinds' families stand in the kinds' order, KF_ADAPTIVE to KF_ACCUM */
+constexpr KernelFamily kind_family(RenderKind k) { return (KernelFamily)((int)KF_ADAPTIVE + ((int)k - (int)RK_ADAPTIVE)); }
+constexpr bool pixel_job_family(KernelFamily f) { return f >= KF_ADAPTIVE && f <= KF_ACCUM; }
+static_assert(kind_family(RK_GROUPS) == KF_GROUPS && kind_family(RK_SAMPLE_MAP) == KF_SAMPLE_MAP && kind_family(RK_ACCUMULATE) == KF_ACCUM,
+              "a pixel-job kind and its kernel family are added at the same place of their enums");
 
-/* the variant a plan asks for.  A plan that claims two families at once, or the stopping rule, the group sums, the sample map or
-   the accumulation outside a PIXEL batch of views, names none */
+/* the variant a plan asks for.  A plan that claims two families at once, or a pixel-job kind outside a PIXEL batch of views,
+   names none */
 inline KernelVariant plan_variant(const LaunchPlan &pl) {
-    if ((int)pl.wavefront + (int)pl.exchange + (int)pl.five + (int)pl.views > 1 || (int)pl.adaptive + (int)pl.groups + (int)pl.sample_map + (int)pl.accumulate > 1 ||
-        ((pl.adaptive || pl.groups || pl.sample_map || pl.accumulate) && !(pl.views && pl.mode == PLAN_JOBS_PIXEL)))
+    if ((int)pl.wavefront + (int)pl.exchange + (int)pl.five + (int)pl.views > 1 || (pl.kind != RK_PLAIN && !(pl.views && pl.mode == PLAN_JOBS_PIXEL)))
         return {KF_NONE, false, false, false, false, false};
     if (pl.wavefront) return {KF_WAVEFRONT, pl.counters, false, false, false, false};
     if (pl.exchange) return {KF_EXCHANGE, pl.counters, pl.diffuse, true, true, false};
     if (pl.five) return {KF_FIVE, false, pl.diffuse, true, true, false};
-    return {pl.adaptive ? KF_ADAPTIVE : pl.groups ? KF_GROUPS : pl.sample_map ? KF_SAMPLE_MAP : pl.accumulate ? KF_ACCUM : pl.views ? KF_LOOP_VIEWS : KF_LOOP, pl.counters, pl.diffuse, pl.tabs, pl.implicit, pl.wide};
+    return {pl.kind != RK_PLAIN ? kind_family(pl.kind) : pl.views ? KF_LOOP_VIEWS : KF_LOOP, pl.counters, pl.diffuse, pl.tabs, pl.implicit, pl.wide};
 }
 
-/* All that is built, and every one of them costs its share of minutes of compile time: ort_kernels.hip instantiates the first
-   four families (its table of launchers is held against this list at compile time), ort_kernels_w5.hip the fifth,
-   ort_kernels_render_adaptive.hip the sixth to the ninth.  plan_render, plan_render_adaptive, plan_render_groups,
-   plan_render_sample_map and plan_render_accumulate produce no other (tools/launch_plan sweep=1
-   and tests/test_launch_plan.py hold them to it); one that did would be an error, not a fallback.  The ray queries' families are
-   built for every combination of their bools and need no list */
+/* All that is built of the families that are built in part, and every one of them costs its share of minutes of compile time:
+   ort_kernels.hip instantiates the first four families (its table of launchers is held against this list at compile time),
+   ort_kernels_w5.hip the fifth.  The pixel-job kinds' families (ort_kernels_render_adaptive.hip) are built in full -- every
+   <counters, diffuse, tabs>, implicit, not wide -- and, like the ray queries' families, need no list: variant_built states the
+   rule.  plan_render and plan_pixel_jobs produce nothing that is not built (tools/launch_plan sweep=1 and
+   tests/test_launch_plan.py hold them to it); a plan that did would be an error, not a fallback */
 constexpr KernelVariant kBuiltKernels[] = {
     /* family, counters, diffuse, tabs, implicit, wide */
     {KF_WAVEFRONT, false, false, false, false, false}, {KF_WAVEFRONT, true, false, false, false, false},
@@ -455,32 +440,16 @@ constexpr KernelVariant kBuiltKernels[] = {
     {KF_EXCHANGE, false, false, true, true, false}, {KF_EXCHANGE, false, true, true, true, false},
     {KF_EXCHANGE, true, true, true, true, false}, /* diagnostics: probes of the diffuse flavour */
     {KF_FIVE, false, false, true, true, false}, {KF_FIVE, false, true, true, true, false},
-    {KF_ADAPTIVE, false, false, false, true, false}, {KF_ADAPTIVE, false, false, true, true, false},
-    {KF_ADAPTIVE, false, true, false, true, false}, {KF_ADAPTIVE, false, true, true, true, false},
-    {KF_ADAPTIVE, true, false, false, true, false}, {KF_ADAPTIVE, true, false, true, true, false},
-    {KF_ADAPTIVE, true, true, false, true, false}, {KF_ADAPTIVE, true, true, true, true, false},
-    {KF_GROUPS, false, false, false, true, false}, {KF_GROUPS, false, false, true, true, false},
-    {KF_GROUPS, false, true, false, true, false}, {KF_GROUPS, false, true, true, true, false},
-    {KF_GROUPS, true, false, false, true, false}, {KF_GROUPS, true, false, true, true, false},
-    {KF_GROUPS, true, true, false, true, false}, {KF_GROUPS, true, true, true, true, false},
-    {KF_SAMPLE_MAP, false, false, false, true, false}, {KF_SAMPLE_MAP, false, false, true, true, false},
-    {KF_SAMPLE_MAP, false, true, false, true, false}, {KF_SAMPLE_MAP, false, true, true, true, false},
-    {KF_SAMPLE_MAP, true, false, false, true, false}, {KF_SAMPLE_MAP, true, false, true, true, false},
-    {KF_SAMPLE_MAP, true, true, false, true, false}, {KF_SAMPLE_MAP, true, true, true, true, false},
-    {KF_ACCUM, false, false, false, true, false}, {KF_ACCUM, false, false, true, true, false},
-    {KF_ACCUM, false, true, false, true, false}, {KF_ACCUM, false, true, true, true, false},
-    {KF_ACCUM, true, false, false, true, false}, {KF_ACCUM, true, false, true, true, false},
-    {KF_ACCUM, true, true, false, true, false}, {KF_ACCUM, true, true, true, true, false},
 };
 constexpr size_t kBuiltKernelCount = sizeof(kBuiltKernels) / sizeof(kBuiltKernels[0]);
 
-/* the place of v in the list, kBuiltKernelCount where nobody built it */
+/* the place of v in the list, kBuiltKernelCount where it is not listed */
 constexpr size_t built_index(const KernelVariant &v) {
     size_t i = 0;
     while (i < kBuiltKernelCount && !(kBuiltKernels[i] == v)) ++i;
     return i;
 }
-constexpr bool variant_built(const KernelVariant &v) { return built_index(v) < kBuiltKernelCount; }
+constexpr bool variant_built(const KernelVariant &v) { return pixel_job_family(v.family) ? v.implicit && !v.wide : built_index(v) < kBuiltKernelCount; }
 
 /* ---- the ray queries: the job space is the caller's ray array -------------------------------------------------------- */
 /* what ort_kernels.hip launches for a query over count rays: <counters, tabs> of raycast_rays / occluded_rays, <counters,

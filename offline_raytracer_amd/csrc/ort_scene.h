@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ort.h"
+#include "ort_plan.h" /* RenderKind */
 
 namespace ort {
 
@@ -227,7 +228,8 @@ struct RenderCall {
     uint32_t *job_states;     /* ... and where their final states go (may be null): always the caller's memory, read back before the call returns */
     const ort_view *views;    /* view_count frames, each from views[v].camera with views[v].seed; null: the scene's own camera and p->seed */
     uint32_t view_count;
-    const ort_adaptive *ad;   /* the stopping rule (checked by the caller) that cuts every pixel of views (not null then); null: a plain render */
+    RenderKind kind;          /* what the render is (ort_plan.h); the fields below are the arguments of the kinds that are not plain, each null where the kind does not take it */
+    const ort_adaptive *ad;   /* RK_ADAPTIVE: the stopping rule (checked by the caller) that cuts every pixel of views (not null then) */
     const ort_light_groups *groups; /* the light-group render's table (checked by the caller; views not null then, ad null); null: no group frames */
     void *out_groups;         /* ... and its view_count x group_count frames, as the call's form has them; out_rgb and states may then be null */
     const void *sample_map;   /* the sample-map render's map, view_count planes of a word a pixel, as the call's form has them (checked by the caller; views not null then, ad and groups null); null: every job is p->spp long */

@@ -169,7 +169,7 @@ inline void radiance_adaptive_view(const IO &q, const void *seeds, const ort_ada
 }
 
 /* camera renders: everything in the RenderView (View) that is not a pointer -- what the call says and what its plan says
-   (plan_render, or with a stopping rule ad plan_render_adaptive).  views: the batch's, null for the scene's own camera and
+   (plan_render, or plan_pixel_jobs: with a stopping rule ad, RK_ADAPTIVE's).  views: the batch's, null for the scene's own camera and
    p.seed.  A batch of one view of the plain render is the single-frame call with that view's seed (and camera: the caller's to
    set); the lanes of a larger batch, and of every adaptive render, read both from the camera table.  With ad, spp is max_spp and
    seed and chunk stay unset: a job's length is the rule's.  A field the plan leaves at zero stays zero */

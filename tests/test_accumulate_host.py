@@ -120,7 +120,7 @@ def test_host_sim_under_sanitizers(api, case, tmp_path):
 
 # ---- 3. the launch plan ---------------------------------------------------------------------------------------------------------
 def test_launch_plan_names_the_accumulate_kernels():
-    """plan_render_accumulate: plan_render_sample_map's launch in every other field, whatever the knobs say; its variant is
+    """plan_pixel_jobs, RK_ACCUMULATE: the sample-map render's launch in every other field, whatever the knobs say; its variant is
     accumulate<...> and is built"""
     r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tools"), "launch_plan"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr

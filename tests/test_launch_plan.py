@@ -500,7 +500,7 @@ def test_fill_of_a_three_view_chunk_batch(tool):
 
 # ---- every plan names a kernel that is built (plan_variant, kBuiltKernels: csrc/ort_plan.h) ----------------------------------
 def test_every_plan_of_the_sweep_names_a_built_kernel(tool):
-    """tools/launch_plan sweep=1: plan_render and plan_render_adaptive over traits, job spaces, frames and the knobs that choose
+    """tools/launch_plan sweep=1: plan_render and plan_pixel_jobs over traits, job spaces, frames and the knobs that choose
     kernels, each plan's variant looked up in the list ort_kernels.hip's table of launchers is held against at compile time:
     what would be an ORT_ERR_INTERNAL on the device is found here"""
     r = subprocess.run([tool, "sweep=1"], env={k: v for k, v in os.environ.items() if k not in KNOBS}, capture_output=True, text=True, timeout=60)

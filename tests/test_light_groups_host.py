@@ -300,7 +300,7 @@ def test_python_shapes(api):
 
 # ---- 4. the launch plan -----------------------------------------------------------------------------------------------------------
 def test_launch_plan_names_the_groups_kernels():
-    """plan_render_groups: the plain loop over implicit one-pixel jobs of a batch of views, both BSDF flavours with counters,
+    """plan_pixel_jobs, RK_GROUPS: the plain loop over implicit one-pixel jobs of a batch of views, both BSDF flavours with counters,
     whatever the knobs say; its variant is groups<...> and is built; the plans of the other calls name what they named"""
     r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tools"), "launch_plan"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -320,7 +320,7 @@ def test_launch_plan_names_the_groups_kernels():
             assert pl["variant"] == "groups<%d, 1, 1, 1, 0>" % counters and pl["built"] == 1
             assert pl["job_count"] == pl["view_jobs"] == 240 * 135 * 64 and pl["grid"] == pl["max_blocks"] == 1024
             assert pl["partial_bytes"] == pl["stash_bytes"] == pl["drain_bytes"] == 0
-            same = plan(env, adaptive=1, counters=counters, has_wide=1, **frame)   # plan_render_adaptive's launch in every other field
+            same = plan(env, adaptive=1, counters=counters, has_wide=1, **frame)   # the adaptive render's launch in every other field
             assert {k: v for k, v in pl.items() if k not in ("groups", "variant", "built")} == {k: v for k, v in same.items() if k != "adaptive"}
     pl = plan({"ORT_KERNEL": "general", "ORT_LDS_TABLES": "0"}, groups=1, variant=1, views=3, x0=5, y0=9, **{**frame, "x1": 20, "y1": 17, "width": 27, "height": 19})
     assert pl["variant"] == "groups<0, 0, 0, 1, 0>" and pl["built"] == 1 and pl["view_count"] == 3

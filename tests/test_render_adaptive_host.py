@@ -235,7 +235,7 @@ def test_python_shapes(api):
 
 # ---- 4. the launch plan -----------------------------------------------------------------------------------------------------------
 def test_launch_plan_prints_the_adaptive_plan():
-    """plan_render_adaptive: always the plain loop over implicit one-pixel jobs of a batch of views, both BSDF flavours with
+    """plan_pixel_jobs, RK_ADAPTIVE: always the plain loop over implicit one-pixel jobs of a batch of views, both BSDF flavours with
     counters, the job space the blocks under the rect times the views; no exchange, no five waves, no wide tree, no wavefront,
     whatever the knobs say"""
     r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tools"), "launch_plan"], capture_output=True, text=True)

@@ -145,7 +145,7 @@ def test_host_sim_under_sanitizers(case, tmp_path):
 
 # ---- 3. the launch plan -----------------------------------------------------------------------------------------------------------
 def test_launch_plan_names_the_sample_map_kernels():
-    """plan_render_sample_map: plan_render_adaptive's launch in every other field, whatever the knobs say; its variant is
+    """plan_pixel_jobs, RK_SAMPLE_MAP: the adaptive render's launch in every other field, whatever the knobs say; its variant is
     sample_map<...> and is built; the fill of the call: spp is the cap, the job space every pixel under the rect"""
     r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tools"), "launch_plan"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr

@@ -433,7 +433,7 @@ static int radiance_adaptive_mode(char **a) { /* scn base rays.f32 seeds.u32 min
            write_bytes(a[13], states.data(), 4 * n) ? 0 : 1;
 }
 
-/* The camera modes set their launch up as device_render does: a plan (plan_render, plan_render_adaptive) and render_view's fill of
+/* The camera modes set their launch up as device_render does: a plan (plan_render, plan_pixel_jobs) and render_view's fill of
    it, for traits the simulation states itself and knobs that keep its schedule -- one simulated lane per thread: no batches, jobs
    in chunk-major order, the plain loop -- whatever the environment says; the modes add their pointers */
 static SceneTraits sim_traits(const Sim &S) {
@@ -461,6 +461,55 @@ static ort_render_params sim_params(int W, int H, uint32_t spp, uint32_t seed, c
     p.policy = policy == "pixel" ? ORT_POLICY_PIXEL : policy == "chunk" ? ORT_POLICY_CHUNK : ORT_POLICY_WHOLE;
     return p;
 }
+/* What the camera modes open with: the views and their packed table, and for the modes that take a rect the PIXEL params of it */
+struct SimCameras {
+    std::vector<ort_view> views;
+    uint32_t nv = 0;
+    std::vector<float4> view_tab; /* the camera table, 16-byte aligned for the lanes' float4 reads */
+    ort_render_params p{};        /* the frame and the rect under the PIXEL policy; spp, rr and the rest are the mode's to set */
+    size_t n = 0;                 /* the words of a one-word plane, nv * W * H exactly: an access past a plane's end is one past the block */
+};
+/* the views of cams.f32 and seeds.u32, and their table */
+static bool read_cameras(const char *cams, const char *seeds_path, SimCameras *c) {
+    static_assert(sizeof(ort_camera) == 48, "a camera is twelve floats");
+    if (cams) {
+        std::vector<unsigned char> cb;
+        if (!read_bytes(cams, cb)) return false;
+        if (cb.empty() || cb.size() % 48u) { fprintf(stderr, "%s: not a whole, positive number of 48-byte cameras\n", cams); return false; }
+        std::vector<uint32_t> seeds;
+        if (!read_array(seeds_path, seeds, cb.size() / 48u, "seeds")) return false;
+        c->views.resize(seeds.size());
+        for (size_t v = 0; v < c->views.size(); ++v) { memcpy(&c->views[v].camera, &cb[48u * v], 48); c->views[v].seed = seeds[v]; }
+    }
+    c->nv = (uint32_t)c->views.size();
+    std::vector<float> tab_host;
+    pack_view_table(c->views.data(), c->nv, tab_host);
+    c->view_tab.resize(4u * c->nv);
+    memcpy(c->view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
+    return true;
+}
+/* ... of a mode with a rect: frame = W H x0 y0 x1 y1; cams "-" is the single-frame form, the scene's own camera on the seed given
+   where the seeds file stands.  S.sv.cam becomes the first view's, unread by the VIEWS lanes */
+static bool sim_cameras(Sim &S, const char *cams, const char *seeds, char **frame, SimCameras *c) {
+    ort_render_params &p = c->p;
+    p.width = atoi(frame[0]); p.height = atoi(frame[1]); p.x0 = atoi(frame[2]); p.y0 = atoi(frame[3]); p.x1 = atoi(frame[4]); p.y1 = atoi(frame[5]);
+    p.policy = ORT_POLICY_PIXEL;
+    if (p.width <= 0 || p.height <= 0 || p.width > 65535 || p.height > 65535 || p.x0 < 0 || p.y0 < 0 || p.x1 > p.width || p.y1 > p.height || p.x0 >= p.x1 || p.y0 >= p.y1) {
+        fprintf(stderr, "bad frame size or rect\n");
+        return false;
+    }
+    const bool own = std::string(cams) == "-";
+    if (own) {
+        c->views.resize(1);
+        camera_basis(*S.scene, p.width, p.height, &c->views[0].camera);
+        c->views[0].seed = (uint32_t)strtoul(seeds, 0, 10);
+    }
+    if (!read_cameras(own ? nullptr : cams, seeds, c)) return false;
+    c->n = (size_t)c->nv * p.width * p.height;
+    memcpy(S.sv.cam, &c->views[0].camera, sizeof(ort_camera));
+    return true;
+}
+
 /* the plain loop's lanes over the job space of rv: pt_lane with explicit jobs (no LF_IMPLICIT), and LF_WIDE or LF_VIEWS or
    neither.  SIM_DIFFUSE: the caller vouches for Ks = Kt = 0; the wide lanes run in the all-lobes flavour whatever it says.  TABS =
    false: the small tables are read from their arrays; SIM_TABS: from the packed image */
@@ -478,15 +527,10 @@ static void run_pt_lanes(const Sim &S, const RenderHot &hot, bool wide, bool vie
 static int views_mode(char **a) { /* scn base cams.f32 seeds.u32 W H spp policy chunk out.f32 */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
-    std::vector<unsigned char> cb;
-    if (!read_bytes(a[2], cb)) return 1;
-    if (cb.empty() || cb.size() % 48u) { fprintf(stderr, "%s: not a whole, positive number of 48-byte cameras\n", a[2]); return 1; }
-    const uint32_t nv = (uint32_t)(cb.size() / 48u);
-    std::vector<uint32_t> seeds;
-    if (!read_array(a[3], seeds, nv, "seeds")) return 1;
-    std::vector<ort_view> views(nv);
-    for (uint32_t v = 0; v < nv; ++v) { memcpy(&views[v].camera, &cb[48u * v], 48); views[v].seed = seeds[v]; }
-    static_assert(sizeof(ort_camera) == 48, "a camera is twelve floats");
+    SimCameras c; /* no rect, and the policy is the caller's: the views and their table alone */
+    if (!read_cameras(a[2], a[3], &c)) return 1;
+    const std::vector<ort_view> &views = c.views;
+    const uint32_t nv = c.nv;
     const int W = atoi(a[4]), H = atoi(a[5]);
     const uint32_t spp = (uint32_t)strtoul(a[6], 0, 10), chunk = (uint32_t)strtoul(a[8], 0, 10);
     if (W <= 0 || H <= 0 || W > 65535 || H > 65535) { fprintf(stderr, "bad frame size\n"); return 1; }
@@ -495,10 +539,6 @@ static int views_mode(char **a) { /* scn base cams.f32 seeds.u32 W H spp policy 
     if (policy == "chunk" && (!chunk || spp % chunk)) { fprintf(stderr, "chunk must divide spp\n"); return 1; }
     const ort_render_params p = sim_params(W, H, spp, 0, policy, chunk);
     const LaunchPlan pl = plan_render(sim_traits(S), p, false, 0, false, sim_knobs(), nv);
-    std::vector<float> tab_host; /* the camera table, 16-byte aligned for the lanes' float4 reads */
-    pack_view_table(views.data(), nv, tab_host);
-    std::vector<float4> view_tab(4u * nv);
-    memcpy(view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
     ort_camera cam; /* the scene's (unread by the VIEWS lanes), or as on the device the one view's of a batch of one */
     camera_basis(*S.scene, W, H, &cam);
     if (!pl.views) cam = views[0].camera;
@@ -506,7 +546,7 @@ static int views_mode(char **a) { /* scn base cams.f32 seeds.u32 W H spp policy 
     RenderView rv{};
     render_view(p, pl, views.data(), nullptr, &rv);
     std::vector<float> out((size_t)nv * W * H * 3, 0.0f), partial(pl.partial_bytes / sizeof(float), 0.0f);
-    rv.out = out.data(); rv.partial = partial.data(); rv.views = view_tab.data();
+    rv.out = out.data(); rv.partial = partial.data(); rv.views = c.view_tab.data();
     rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
     const RenderHot hot = render_hot<RenderHot>(rv, &rv);
     auto t0 = std::chrono::steady_clock::now();
@@ -522,28 +562,19 @@ static int views_mode(char **a) { /* scn base cams.f32 seeds.u32 W H spp policy 
 static int render_adaptive_mode(char **a) { /* scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32 */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
-    const int W = atoi(a[2]), H = atoi(a[3]), x0 = atoi(a[4]), y0 = atoi(a[5]), x1 = atoi(a[6]), y1 = atoi(a[7]);
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || x0 < 0 || y0 < 0 || x1 > W || y1 > H || x0 >= x1 || y0 >= y1) { fprintf(stderr, "bad frame size or rect\n"); return 1; }
+    SimCameras c; /* no cameras on this command line: the single-frame form */
+    if (!sim_cameras(S, "-", a[8], a + 2, &c)) return 1;
     ort_adaptive ad{(uint32_t)strtoul(a[9], 0, 10), (uint32_t)strtoul(a[10], 0, 10), (uint32_t)strtoul(a[11], 0, 10), float_arg(a[12]), float_arg(a[13])};
     if (ad.min_spp < 2u || ad.max_spp < ad.min_spp || ad.max_spp > (1u << 24) || ad.check_every == 0u) { fprintf(stderr, "bad adaptive parameters\n"); return 1; }
-    ort_view view;
-    camera_basis(*S.scene, W, H, &view.camera);
-    view.seed = (uint32_t)strtoul(a[8], 0, 10);
-    memcpy(S.sv.cam, &view.camera, sizeof(view.camera)); /* unread by the VIEWS lanes */
-    std::vector<float> tab_host;
-    pack_view_table(&view, 1, tab_host);
-    std::vector<float4> view_tab(4u);
-    memcpy(view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
-    const size_t n = (size_t)W * H; /* exactly: a write past a plane's end is a write past the block */
+    const size_t n = c.n;
     std::vector<float> out(3 * n, -7.0f), m2(n, -1.0f);
     std::vector<uint32_t> spp(n, 0xeeeeeeeeu), states(n, 0xddddddddu);
-    ort_render_params p{};
-    p.width = W; p.height = H; p.x0 = x0; p.y0 = y0; p.x1 = x1; p.y1 = y1;
-    p.policy = ORT_POLICY_PIXEL; p.rr = (float)atof(a[14]);
+    ort_render_params &p = c.p;
+    p.rr = (float)atof(a[14]);
     RenderView rv{};
-    render_view(p, plan_render_adaptive(sim_traits(S), p, sim_knobs(), 1), &view, &ad, &rv);
+    render_view(p, plan_pixel_jobs(RK_ADAPTIVE, sim_traits(S), p, sim_knobs(), 1), c.views.data(), &ad, &rv);
     rv.out = out.data(); rv.ad_spp = spp.data(); rv.ad_m2 = m2.data(); rv.final_states = states.data();
-    rv.views = view_tab.data();
+    rv.views = c.view_tab.data();
     rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
     const RenderHot hot = render_hot<RenderHot>(rv, &rv);
     auto t0 = std::chrono::steady_clock::now();
@@ -563,8 +594,8 @@ static int render_adaptive_mode(char **a) { /* scn base W H x0 y0 x1 y1 seed min
 static int light_groups_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr groups.u8 G groups.f32 rgb.f32|- states.u32|- */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
-    const int W = atoi(a[4]), H = atoi(a[5]), x0 = atoi(a[6]), y0 = atoi(a[7]), x1 = atoi(a[8]), y1 = atoi(a[9]);
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || x0 < 0 || y0 < 0 || x1 > W || y1 > H || x0 >= x1 || y0 >= y1) { fprintf(stderr, "bad frame size or rect\n"); return 1; }
+    SimCameras c;
+    if (!sim_cameras(S, a[2], a[3], a + 4, &c)) return 1;
     const uint32_t spp = (uint32_t)strtoul(a[10], 0, 10), G = (uint32_t)strtoul(a[13], 0, 10);
     if (spp == 0u || spp > (1u << 24)) { fprintf(stderr, "spp must be within [1, 1 << 24]\n"); return 1; }
     if (G == 0u || G > ORT_MAX_LIGHT_GROUPS) { fprintf(stderr, "G must be within [1, ORT_MAX_LIGHT_GROUPS]\n"); return 1; }
@@ -573,38 +604,17 @@ static int light_groups_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W
     if (table.size() != S.scene->materials.size()) { fprintf(stderr, "%s: %zu bytes, the scene has %zu materials\n", a[12], table.size(), S.scene->materials.size()); return 1; }
     for (size_t m = 0; m < table.size(); ++m)
         if (S.scene->materials[m].is_light && table[m] >= G && table[m] != ORT_NO_LIGHT_GROUP) { fprintf(stderr, "light material %zu names no group\n", m); return 1; }
-    std::vector<ort_view> views;
-    if (std::string(a[2]) == "-") {
-        views.resize(1);
-        camera_basis(*S.scene, W, H, &views[0].camera);
-        views[0].seed = (uint32_t)strtoul(a[3], 0, 10);
-    } else {
-        std::vector<unsigned char> cb;
-        if (!read_bytes(a[2], cb)) return 1;
-        if (cb.empty() || cb.size() % 48u) { fprintf(stderr, "%s: not a whole, positive number of 48-byte cameras\n", a[2]); return 1; }
-        std::vector<uint32_t> seeds;
-        if (!read_array(a[3], seeds, cb.size() / 48u, "seeds")) return 1;
-        views.resize(seeds.size());
-        for (size_t v = 0; v < views.size(); ++v) { memcpy(&views[v].camera, &cb[48u * v], 48); views[v].seed = seeds[v]; }
-    }
-    const uint32_t nv = (uint32_t)views.size();
-    memcpy(S.sv.cam, &views[0].camera, sizeof(views[0].camera)); /* unread by the VIEWS lanes */
-    std::vector<float> tab_host; /* the camera table, 16-byte aligned for the lanes' float4 reads */
-    pack_view_table(views.data(), nv, tab_host);
-    std::vector<float4> view_tab(4u * nv);
-    memcpy(view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
     const bool want_rgb = std::string(a[15]) != "-", want_states = std::string(a[16]) != "-";
-    const size_t n = (size_t)nv * W * H; /* exactly: a write past a plane's end is a write past the block */
+    const size_t n = c.n;
     std::vector<float> groups(3 * n * G, -7.0f), rgb(want_rgb ? 3 * n : 0, -7.0f);
     std::vector<uint32_t> states(want_states ? n : 0, 0xddddddddu);
-    ort_render_params p{};
-    p.width = W; p.height = H; p.x0 = x0; p.y0 = y0; p.x1 = x1; p.y1 = y1;
-    p.policy = ORT_POLICY_PIXEL; p.spp = spp; p.rr = (float)atof(a[11]);
+    ort_render_params &p = c.p;
+    p.spp = spp; p.rr = (float)atof(a[11]);
     RenderView rv{};
-    render_view(p, plan_render_groups(sim_traits(S), p, sim_knobs(), nv), views.data(), nullptr, &rv);
+    render_view(p, plan_pixel_jobs(RK_GROUPS, sim_traits(S), p, sim_knobs(), c.nv), c.views.data(), nullptr, &rv);
     rv.out = want_rgb ? rgb.data() : nullptr; rv.final_states = want_states ? states.data() : nullptr;
     rv.group_of_material = table.data(); rv.group_count = G; rv.group_out = groups.data();
-    rv.views = view_tab.data();
+    rv.views = c.view_tab.data();
     rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
     const RenderHot hot = render_hot<RenderHot>(rv, &rv);
     auto t0 = std::chrono::steady_clock::now();
@@ -623,44 +633,23 @@ static int light_groups_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W
 static int sample_map_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32 rgb.f32 m2.f32|- states.u32|- */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
-    const int W = atoi(a[4]), H = atoi(a[5]), x0 = atoi(a[6]), y0 = atoi(a[7]), x1 = atoi(a[8]), y1 = atoi(a[9]);
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || x0 < 0 || y0 < 0 || x1 > W || y1 > H || x0 >= x1 || y0 >= y1) { fprintf(stderr, "bad frame size or rect\n"); return 1; }
+    SimCameras c;
+    if (!sim_cameras(S, a[2], a[3], a + 4, &c)) return 1;
     const uint32_t cap = (uint32_t)strtoul(a[10], 0, 10);
     if (cap == 0u || cap > (1u << 24)) { fprintf(stderr, "cap must be within [1, 1 << 24]\n"); return 1; }
-    std::vector<ort_view> views;
-    if (std::string(a[2]) == "-") {
-        views.resize(1);
-        camera_basis(*S.scene, W, H, &views[0].camera);
-        views[0].seed = (uint32_t)strtoul(a[3], 0, 10);
-    } else {
-        std::vector<unsigned char> cb;
-        if (!read_bytes(a[2], cb)) return 1;
-        if (cb.empty() || cb.size() % 48u) { fprintf(stderr, "%s: not a whole, positive number of 48-byte cameras\n", a[2]); return 1; }
-        std::vector<uint32_t> seeds;
-        if (!read_array(a[3], seeds, cb.size() / 48u, "seeds")) return 1;
-        views.resize(seeds.size());
-        for (size_t v = 0; v < views.size(); ++v) { memcpy(&views[v].camera, &cb[48u * v], 48); views[v].seed = seeds[v]; }
-    }
-    const uint32_t nv = (uint32_t)views.size();
-    memcpy(S.sv.cam, &views[0].camera, sizeof(views[0].camera)); /* unread by the VIEWS lanes */
-    std::vector<float> tab_host; /* the camera table, 16-byte aligned for the lanes' float4 reads */
-    pack_view_table(views.data(), nv, tab_host);
-    std::vector<float4> view_tab(4u * nv);
-    memcpy(view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
-    const size_t n = (size_t)nv * W * H; /* exactly: a read or write past a plane's end is one past the block */
+    const size_t n = c.n;
     std::vector<uint32_t> map;
     if (!read_array(a[12], map, n, "map words (views x W x H)")) return 1;
     const bool want_m2 = std::string(a[14]) != "-", want_states = std::string(a[15]) != "-";
     std::vector<float> rgb(3 * n, -7.0f), m2(want_m2 ? n : 0, -1.0f);
     std::vector<uint32_t> states(want_states ? n : 0, 0xddddddddu);
-    ort_render_params p{};
-    p.width = W; p.height = H; p.x0 = x0; p.y0 = y0; p.x1 = x1; p.y1 = y1;
-    p.policy = ORT_POLICY_PIXEL; p.spp = cap; p.rr = (float)atof(a[11]);
+    ort_render_params &p = c.p;
+    p.spp = cap; p.rr = (float)atof(a[11]);
     RenderView rv{};
-    render_view(p, plan_render_sample_map(sim_traits(S), p, sim_knobs(), nv), views.data(), nullptr, &rv);
+    render_view(p, plan_pixel_jobs(RK_SAMPLE_MAP, sim_traits(S), p, sim_knobs(), c.nv), c.views.data(), nullptr, &rv);
     rv.out = rgb.data(); rv.ad_m2 = want_m2 ? m2.data() : nullptr; rv.final_states = want_states ? states.data() : nullptr;
     rv.sample_map = map.data();
-    rv.views = view_tab.data();
+    rv.views = c.view_tab.data();
     rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
     const RenderHot hot = render_hot<RenderHot>(rv, &rv);
     auto t0 = std::chrono::steady_clock::now();
@@ -680,31 +669,11 @@ static int sample_map_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H
 static int accumulate_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32|- sum.f32 m2.f32|- count.u32 states.u32 rgb.f32|- */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
-    const int W = atoi(a[4]), H = atoi(a[5]), x0 = atoi(a[6]), y0 = atoi(a[7]), x1 = atoi(a[8]), y1 = atoi(a[9]);
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || x0 < 0 || y0 < 0 || x1 > W || y1 > H || x0 >= x1 || y0 >= y1) { fprintf(stderr, "bad frame size or rect\n"); return 1; }
+    SimCameras c;
+    if (!sim_cameras(S, a[2], a[3], a + 4, &c)) return 1;
     const uint32_t cap = (uint32_t)strtoul(a[10], 0, 10);
     if (cap == 0u || cap > (1u << 24)) { fprintf(stderr, "cap must be within [1, 1 << 24]\n"); return 1; }
-    std::vector<ort_view> views;
-    if (std::string(a[2]) == "-") {
-        views.resize(1);
-        camera_basis(*S.scene, W, H, &views[0].camera);
-        views[0].seed = (uint32_t)strtoul(a[3], 0, 10);
-    } else {
-        std::vector<unsigned char> cb;
-        if (!read_bytes(a[2], cb)) return 1;
-        if (cb.empty() || cb.size() % 48u) { fprintf(stderr, "%s: not a whole, positive number of 48-byte cameras\n", a[2]); return 1; }
-        std::vector<uint32_t> seeds;
-        if (!read_array(a[3], seeds, cb.size() / 48u, "seeds")) return 1;
-        views.resize(seeds.size());
-        for (size_t v = 0; v < views.size(); ++v) { memcpy(&views[v].camera, &cb[48u * v], 48); views[v].seed = seeds[v]; }
-    }
-    const uint32_t nv = (uint32_t)views.size();
-    memcpy(S.sv.cam, &views[0].camera, sizeof(views[0].camera)); /* unread by the VIEWS lanes */
-    std::vector<float> tab_host; /* the camera table, 16-byte aligned for the lanes' float4 reads */
-    pack_view_table(views.data(), nv, tab_host);
-    std::vector<float4> view_tab(4u * nv);
-    memcpy(view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
-    const size_t n = (size_t)nv * W * H; /* exactly: a read or write past a plane's end is one past the block */
+    const size_t n = c.n;
     const bool want_map = std::string(a[12]) != "-", want_m2 = std::string(a[14]) != "-", want_rgb = std::string(a[17]) != "-";
     std::vector<uint32_t> map, count, states;
     std::vector<float> sum, m2, rgb;
@@ -714,15 +683,14 @@ static int accumulate_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H
     if (!read_array(a[15], count, n, "count words (views x W x H)")) return 1;
     if (!read_array(a[16], states, n, "state words (views x W x H)")) return 1;
     if (want_rgb && !read_array(a[17], rgb, 3 * n, "rgb floats (views x W x H x 3)")) return 1;
-    ort_render_params p{};
-    p.width = W; p.height = H; p.x0 = x0; p.y0 = y0; p.x1 = x1; p.y1 = y1;
-    p.policy = ORT_POLICY_PIXEL; p.spp = cap; p.rr = (float)atof(a[11]);
+    ort_render_params &p = c.p;
+    p.spp = cap; p.rr = (float)atof(a[11]);
     RenderView rv{};
-    render_view(p, plan_render_accumulate(sim_traits(S), p, sim_knobs(), nv), views.data(), nullptr, &rv);
+    render_view(p, plan_pixel_jobs(RK_ACCUMULATE, sim_traits(S), p, sim_knobs(), c.nv), c.views.data(), nullptr, &rv);
     rv.out = want_rgb ? rgb.data() : nullptr; rv.ad_m2 = want_m2 ? m2.data() : nullptr;
     rv.sample_map = want_map ? map.data() : nullptr;
     rv.acc_sum = sum.data(); rv.ad_spp = count.data(); rv.final_states = states.data();
-    rv.views = view_tab.data();
+    rv.views = c.view_tab.data();
     rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
     const RenderHot hot = render_hot<RenderHot>(rv, &rv);
     auto t0 = std::chrono::steady_clock::now();
@@ -743,47 +711,27 @@ static int accumulate_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H
 static int features_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|- */
     Sim S;
     if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_MATS)) return rc;
-    const int W = atoi(a[4]), H = atoi(a[5]), x0 = atoi(a[6]), y0 = atoi(a[7]), x1 = atoi(a[8]), y1 = atoi(a[9]);
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || x0 < 0 || y0 < 0 || x1 > W || y1 > H || x0 >= x1 || y0 >= y1) { fprintf(stderr, "bad frame size or rect\n"); return 1; }
+    SimCameras c;
+    if (!sim_cameras(S, a[2], a[3], a + 4, &c)) return 1;
     const uint32_t spp = (uint32_t)strtoul(a[10], 0, 10);
     if (spp == 0u || spp > (1u << 24)) { fprintf(stderr, "spp must be within [1, 1 << 24]\n"); return 1; }
-    std::vector<ort_view> views;
-    if (std::string(a[2]) == "-") {
-        views.resize(1);
-        camera_basis(*S.scene, W, H, &views[0].camera);
-        views[0].seed = (uint32_t)strtoul(a[3], 0, 10);
-    } else {
-        std::vector<unsigned char> cb;
-        if (!read_bytes(a[2], cb)) return 1;
-        if (cb.empty() || cb.size() % 48u) { fprintf(stderr, "%s: not a whole, positive number of 48-byte cameras\n", a[2]); return 1; }
-        std::vector<uint32_t> seeds;
-        if (!read_array(a[3], seeds, cb.size() / 48u, "seeds")) return 1;
-        views.resize(seeds.size());
-        for (size_t v = 0; v < views.size(); ++v) { memcpy(&views[v].camera, &cb[48u * v], 48); views[v].seed = seeds[v]; }
-    }
-    const uint32_t nv = (uint32_t)views.size();
-    std::vector<float> tab_host; /* the camera table, 16-byte aligned for the lanes' float4 reads */
-    pack_view_table(views.data(), nv, tab_host);
-    std::vector<float4> view_tab(4u * nv);
-    memcpy(view_tab.data(), tab_host.data(), tab_host.size() * sizeof(float));
     std::vector<uint32_t> src;
     if (!invert_prim_slots(S.scene->tree, S.sv.info_box, S.sv.info_cyl, S.sv.info_sphere, src)) { fprintf(stderr, "the tree's slot maps are not a bijection onto its shape arrays\n"); return 1; }
     bool want[6];
     for (int k = 0; k < 6; ++k) want[k] = std::string(a[11 + k]) != "-";
-    const size_t n = (size_t)nv * W * H; /* exactly: a write past a plane's end is a write past the block */
+    const size_t n = c.n;
     std::vector<float> albedo(want[0] ? 3 * n : 0, -7.0f), normal(want[1] ? 3 * n : 0, -7.0f), depth(want[2] ? n : 0, -7.0f);
     std::vector<uint32_t> hits(want[3] ? n : 0, 0xeeeeeeeeu), ids(want[4] ? 2 * n : 0, 0xeeeeeeeeu), states(want[5] ? n : 0, 0xddddddddu);
-    ort_render_params p{};
-    p.width = W; p.height = H; p.x0 = x0; p.y0 = y0; p.x1 = x1; p.y1 = y1;
-    p.policy = ORT_POLICY_PIXEL; p.spp = spp;
+    ort_render_params &p = c.p;
+    p.spp = spp;
     FeatureIO io{};
     io.q = sim_query_io(S);
     io.q.prim_src = src.data();
     io.albedo = want[0] ? albedo.data() : nullptr; io.normal = want[1] ? normal.data() : nullptr; io.depth = want[2] ? depth.data() : nullptr;
     io.hits = want[3] ? hits.data() : nullptr; io.ids = want[4] ? ids.data() : nullptr; io.states = want[5] ? states.data() : nullptr;
     RenderView rv{};
-    features_view(p, nv, &rv);
-    rv.views = view_tab.data();
+    features_view(p, c.nv, &rv);
+    rv.views = c.view_tab.data();
     const RenderHot hot = query_hot(S, rv, (size_t)rv.job_count);
     auto t0 = std::chrono::steady_clock::now();
     run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {

@@ -6,18 +6,16 @@
    the QueryPlan of ort_render_features, or with views=N of ort_render_views_features (plan_features), its job count and, with
    fill=1, features_view's fill of the RenderView.  Otherwise
    keys: the SceneTraits and ort_render_params fields by name, policy=pixel|chunk, counters=1, explicit_jobs=1 job_count=N,
-   w5_layout_ok=0, views=N (the plan of an ort_render_views batch of N views; its fields are appended to the line), adaptive=1
-   (plan_render_adaptive: the plan of ort_render_adaptive, or with views=N of ort_render_views_adaptive; "adaptive" and the
-   views fields are appended), groups=1 (plan_render_groups: the plan of ort_render_light_groups, or with views=N of
-   ort_render_views_light_groups; "groups" and the views fields are appended), sample_map=1 (plan_render_sample_map: the plan
-   of ort_render_sample_map, or with views=N of ort_render_views_sample_map; "sample_map" and the views fields are appended), accumulate=1 (plan_render_accumulate: the plan of ort_render_accumulate, or
-   with views=N of ort_render_views_accumulate; "accumulate" and the views fields are appended); fill=1: after the plan, every field of the RenderView that is not a pointer as the shared fill
+   w5_layout_ok=0, views=N (the plan of an ort_render_views batch of N views; its fields are appended to the line), one of
+   adaptive=1, groups=1, sample_map=1, accumulate=1 (plan_pixel_jobs for that kind: the plan of ort_render_adaptive,
+   ort_render_light_groups, ort_render_sample_map or ort_render_accumulate, or with views=N of its views form; the key and the
+   views fields are appended); fill=1: after the plan, every field of the RenderView that is not a pointer as the shared fill
    (render_view, csrc/ort_setup.h) sets it for that plan, "name = value" one per line -- seed=, rr= are the call's, view_seed=S
    gives view v of views=N the seed S + v, min_spp= max_spp= check_every= tolerance= floor= are the stopping rule's; max_blocks
    defaults to what an upload on cu_count units fixes.  tab_flags, where not given, follows from
    materials= (index 0 included), lights=, pro_boxes=, pro_spheres=, pro_cyls= as at upload (table_fit_flags; all 0 by default).  tests/test_launch_plan.py holds the measured
    crossovers and the knobs the GPU tests force kernels with against it.
-   variant=1: the kernel the plan names (plan_variant) and whether it is built (kBuiltKernels) are appended to the line.
+   variant=1: the kernel the plan names (plan_variant) and whether it is built (variant_built) are appended to the line.
    sweep=1, and nothing else: every plan of a grid over traits, calls and knobs (sweep() below) held against the built kernels; one
    JSON line with the number of plans, how many name no built kernel, and the first of those. */
 #include <stdio.h>
@@ -45,18 +43,24 @@ struct FillView {
     float rr, ad_tolerance, ad_floor;
 };
 
+/* the pixel-job kinds, in the order of their enum, by their key on the command line, which is also their field of the output and
+   the name of their kernel family */
+struct PixelJobKey { const char *key; ort::RenderKind kind; };
+static const PixelJobKey kPixelJobKeys[] = {{"adaptive", ort::RK_ADAPTIVE}, {"groups", ort::RK_GROUPS}, {"sample_map", ort::RK_SAMPLE_MAP}, {"accumulate", ort::RK_ACCUMULATE}};
+
 /* "family<counters, diffuse, tabs, implicit, wide>" */
 static std::string variant_name(const ort::KernelVariant &v) {
-    static const char *family[] = {"none", "wavefront", "loop", "loop_views", "exchange", "five", "adaptive", "groups", "sample_map", "accumulate"};
+    static const char *family[] = {"none", "wavefront", "loop", "loop_views", "exchange", "five"};
     char b[64];
-    snprintf(b, sizeof(b), "%s<%d, %d, %d, %d, %d>", family[v.family], v.counters, v.diffuse, v.tabs, v.implicit, v.wide);
+    snprintf(b, sizeof(b), "%s<%d, %d, %d, %d, %d>", ort::pixel_job_family(v.family) ? kPixelJobKeys[v.family - ort::KF_ADAPTIVE].key : family[v.family], v.counters,
+             v.diffuse, v.tabs, v.implicit, v.wide);
     return b;
 }
 
 /* every plan the policy gives over: both BSDF flavours; all tables, the prologue's alone, none; a tree inside and outside the L2; a
    cheap and a dear one; with and without the wide form; PIXEL, CHUNK and explicit jobs (the WHOLE policy); counters; one view and
    three (implicit job spaces); a frame smaller than the grid and a long launch; both answers of the five-waves layout check; and
-   the knobs that choose kernels, unset and forced either way.  plan_render_adaptive, plan_render_groups, plan_render_sample_map and plan_render_accumulate for the single PIXEL frames */
+   the knobs that choose kernels, unset and forced either way.  plan_pixel_jobs, every kind, for the single PIXEL frames */
 static int sweep() {
     unsigned long long plans = 0, unbuilt = 0;
     std::string first;
@@ -89,7 +93,8 @@ static int sweep() {
                 kn.exchange = exchange; kn.wide = wide; kn.waves5 = waves5; kn.wavefront = wavefront != 0;
                 kn.general_kernel = general != 0; kn.lds_tables = lds_tables; kn.debug_util = util != 0;
                 hold(ort::plan_render(t, p, explicit_jobs, jobs, w5 != 0, kn, views));
-                if (policy == ORT_POLICY_PIXEL && views == 1u) { hold(ort::plan_render_adaptive(t, p, kn, 1)); hold(ort::plan_render_groups(t, p, kn, 1)); hold(ort::plan_render_sample_map(t, p, kn, 1)); hold(ort::plan_render_accumulate(t, p, kn, 1)); }
+                if (policy == ORT_POLICY_PIXEL && views == 1u)
+                    for (const PixelJobKey &k : kPixelJobKeys) hold(ort::plan_pixel_jobs(k.kind, t, p, kn, 1));
             }
         }
     }
@@ -111,7 +116,8 @@ int main(int argc, char **argv) {
     unsigned long materials = 0, lights = 0, pro_boxes = 0, pro_spheres = 0, pro_cyls = 0;
     unsigned long long job_count = 0;
     unsigned long view_count = 1;
-    bool views_given = false, adaptive = false, groups = false, sample_map = false, accumulate = false, fill = false, variant = false;
+    bool views_given = false, fill = false, variant = false;
+    unsigned asked = 0; /* bit k: kPixelJobKeys[k] was given as 1; at most one may be, and that one is the call's kind (key, below) */
     unsigned long view_seed = 0;
     ort_adaptive ad{};
     const char *query = nullptr;
@@ -121,6 +127,11 @@ int main(int argc, char **argv) {
         const size_t n = eq ? (size_t)(eq - argv[i]) : 0;
         const char *v = eq ? eq + 1 : "";
         auto is = [&](const char *key) { return strlen(key) == n && strncmp(argv[i], key, n) == 0; };
+        auto kind_bit = [&]() { /* of a pixel-job kind's key, 0 for any other argument */
+            unsigned bit = 1u;
+            for (const PixelJobKey &k : kPixelJobKeys) { if (is(k.key)) return bit; bit <<= 1; }
+            return 0u;
+        };
         if (is("diffuse_only")) t.diffuse_only = atoi(v) != 0;
         else if (is("tab_flags")) { t.tab_flags = (uint32_t)strtoul(v, nullptr, 0); tab_flags_given = true; }
         else if (is("materials")) materials = strtoul(v, nullptr, 0);
@@ -151,10 +162,7 @@ int main(int argc, char **argv) {
         else if (is("query")) query = v;
         else if (is("count")) count = strtoull(v, nullptr, 0);
         else if (is("views")) { view_count = strtoul(v, nullptr, 0); views_given = true; }
-        else if (is("adaptive")) adaptive = atoi(v) != 0;
-        else if (is("groups")) groups = atoi(v) != 0;
-        else if (is("sample_map")) sample_map = atoi(v) != 0;
-        else if (is("accumulate")) accumulate = atoi(v) != 0;
+        else if (const unsigned bit = kind_bit()) asked = atoi(v) ? asked | bit : asked & ~bit;
         else if (is("fill")) fill = atoi(v) != 0;
         else if (is("variant")) variant = atoi(v) != 0;
         else if (is("seed")) p.seed = (uint32_t)strtoul(v, nullptr, 0);
@@ -201,9 +209,12 @@ int main(int argc, char **argv) {
     }
     if (!explicit_jobs && p.policy == ORT_POLICY_CHUNK && p.chunk == 0) { fprintf(stderr, "launch_plan: chunk=0\n"); return 2; }
     if (views_given && (view_count < 1 || view_count > ORT_MAX_VIEWS || explicit_jobs)) { fprintf(stderr, "launch_plan: views=1..%u, implicit job spaces only\n", ORT_MAX_VIEWS); return 2; }
-    if ((adaptive || groups || sample_map || accumulate) && (explicit_jobs || p.policy != ORT_POLICY_PIXEL || p.shard_count > 1 || (int)adaptive + (int)groups + (int)sample_map + (int)accumulate > 1)) { fprintf(stderr, "launch_plan: adaptive=1, groups=1, sample_map=1 or accumulate=1 (one of them) needs policy=pixel, implicit jobs and no shards\n"); return 2; }
-    const ort::LaunchPlan l = accumulate ? ort::plan_render_accumulate(t, p, kn, (uint32_t)view_count) : sample_map ? ort::plan_render_sample_map(t, p, kn, (uint32_t)view_count) : groups ? ort::plan_render_groups(t, p, kn, (uint32_t)view_count) : adaptive ? ort::plan_render_adaptive(t, p, kn, (uint32_t)view_count)
-                                       : ort::plan_render(t, p, explicit_jobs, job_count, w5_layout_ok, kn, (uint32_t)view_count);
+    if (asked && (explicit_jobs || p.policy != ORT_POLICY_PIXEL || p.shard_count > 1 || (asked & (asked - 1u)))) { fprintf(stderr, "launch_plan: adaptive=1, groups=1, sample_map=1 or accumulate=1 (one of them) needs policy=pixel, implicit jobs and no shards\n"); return 2; }
+    const PixelJobKey *key = nullptr; /* null: the plain render */
+    for (const PixelJobKey &k : kPixelJobKeys)
+        if (asked == 1u << (&k - kPixelJobKeys)) key = &k;
+    const ort::LaunchPlan l = key ? ort::plan_pixel_jobs(key->kind, t, p, kn, (uint32_t)view_count)
+                                  : ort::plan_render(t, p, explicit_jobs, job_count, w5_layout_ok, kn, (uint32_t)view_count);
     printf("{\"wavefront\": %d, \"exchange\": %d, \"five\": %d, \"wide\": %d, \"counters\": %d, \"diffuse\": %d, \"tabs\": %d, \"implicit\": %d, \"util\": %d, "
            "\"grid\": %u, \"mode\": %d, \"nchunks\": %u, \"job_count\": %llu, \"my_blocks\": %u, \"refill_below\": %d, \"descend_below\": %d, "
            "\"capL\": %u, \"capR\": %u, \"long_min\": %u, \"long_refill\": %u, \"inflight_cap\": %u, \"park_min\": %u, \"endgame_from\": %llu, "
@@ -213,18 +224,15 @@ int main(int argc, char **argv) {
            l.blocks.my_blocks, l.refill_below, l.descend_below, l.capL, l.capR, l.long_min, l.long_refill, l.inflight_cap, l.park_min,
            l.endgame_from, l.stash_wave_f4, l.block_major, l.job_batch, l.batch_until, l.partial_bytes, l.stash_bytes, l.drain_bytes, t.max_blocks,
            t.tab_flags, ort::kPlanTabMatCap, ort::kPlanTabLightCap, ort::kPlanTabProCap);
-    if (adaptive) printf(", \"adaptive\": %d", l.adaptive);
-    if (groups) printf(", \"groups\": %d", l.groups);
-    if (sample_map) printf(", \"sample_map\": %d", l.sample_map);
-    if (accumulate) printf(", \"accumulate\": %d", l.accumulate);
-    if (views_given || adaptive || groups || sample_map || accumulate) printf(", \"views\": %d, \"view_count\": %u, \"view_jobs\": %llu", l.views, l.view_count, l.view_jobs);
+    if (key) printf(", \"%s\": %d", key->key, l.kind == key->kind);
+    if (views_given || key) printf(", \"views\": %d, \"view_count\": %u, \"view_jobs\": %llu", l.views, l.view_count, l.view_jobs);
     if (variant) printf(", \"variant\": \"%s\", \"built\": %d", variant_name(ort::plan_variant(l)).c_str(), ort::variant_built(ort::plan_variant(l)));
     printf("}\n");
     if (fill) { /* as device_render calls it: a batch's views, the single adaptive frame's one view, or none */
-        std::vector<ort_view> views(views_given || adaptive || groups || sample_map || accumulate ? view_count : 0);
+        std::vector<ort_view> views(views_given || key ? view_count : 0);
         for (size_t v = 0; v < views.size(); ++v) views[v].seed = (uint32_t)(view_seed + v);
         FillView rv{};
-        ort::render_view(p, l, views.empty() ? nullptr : views.data(), adaptive ? &ad : nullptr, &rv);
+        ort::render_view(p, l, views.empty() ? nullptr : views.data(), key && key->kind == ort::RK_ADAPTIVE ? &ad : nullptr, &rv);
         auto print = [](const char *name, auto v) {
             if constexpr (std::is_floating_point<decltype(v)>::value) printf("%s = %.9g\n", name, (double)v);
             else printf("%s = %lld\n", name, (long long)v);
