@@ -878,6 +878,85 @@ int ort_render_views_features(ort_scene *scene, const ort_render_params *params,
 int ort_render_views_features_device(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
                                      const ort_feature_planes *planes, void *hip_stream, ort_stats *stats);
 
+/* ---- feature renders that follow mirrors and glass: the planes of the first non-specular vertex -----
+ * ort_render_features stops at the first hit: what is seen in a mirror or through glass gets the guides of the mirror or the glass
+ * itself.  These calls follow the path the renderer itself would take through specular-only surfaces and record albedo, normal,
+ * distance and ids where the path first meets a light or a surface with a diffuse part.  The contract is the reference's sample
+ * body (ray.cpp:1247-1426) cut at that vertex.
+ * Planes.  Each holds width*height entries per frame with row 0 at the bottom, view_count frames view-major:
+ *    albedo        3 f32 per pixel   mean over spp of the recorded vertex's albedo                                  (may be NULL)
+ *    normal        3 f32 per pixel   mean over spp of the recorded vertex's unit normal, as it stands: not mirrored
+ *                                    back into the first surface's frame, not re-normalised                         (may be NULL)
+ *    depth         f32               mean over spp of the path length from the aperture point to the recorded vertex (may be NULL)
+ *    hits          u32               samples that recorded a vertex                                                 (may be NULL)
+ *    ids           2 u32: mat, prim  of sample 0's last vertex                                                      (may be NULL)
+ *    bounces       u32               sum over the recorded samples of the bounces followed                          (may be NULL)
+ *    final_states  u32               the stream's state after the last sample                                       (may be NULL)
+ * At least one of the first six must be given.  Pixels outside the rect are left untouched in every plane.
+ * The job.  A job is pixel (x, y) of a frame; its stream s starts at job_seed(seed, y*W + x), the ORT_POLICY_PIXEL stream of that
+ * pixel (views[v].seed in the views form).  Sample k = 0 .. spp-1, every operation a separately rounded f32 operation (no FMA):
+ *  1. The camera sample: exactly ort_render_features' sample -- rad (two steps of the stream), ap, d = normalize(focal - ap).
+ *     Then o = ap, dir = d, wo = -normalize(d) (ray.cpp:1241, sic), L = +0, b = 0.
+ *  2. The vertex: h, the closest hit of the ray (o, dir), the record ort_raycast returns for it: t, the normalised n, mat, prim.  A
+ *     primary ray that ort_raycast would send to the exact walk takes it here too; bounce rays start at hits and are traced as
+ *     the render traces its bounce rays.
+ *      - h.mat == 0 (a miss, or a shape that carries material 0): the sample ends without a record; as sample 0 it gives
+ *        ids = {0, h.prim}, h.prim being ORT_NO_PRIM for a miss.
+ *      - Otherwise L = L + h.t.  With m = materials[h.mat], the vertex is TERMINAL iff m.is_light, or |m.diffuse|^2 > 0 -- the f32
+ *        x*x + y*y + z*z of ray.cpp:1267, the render's own test, so false for a NaN --, or b == max_bounces.
+ *      - Terminal: hits++, A += albedo(m) (emit of a light, diffuse otherwise, as it stands), N += h.n, D += L, B += b, each
+ *        component a separately rounded f32 add; as sample 0 it gives ids = {h.mat, h.prim}.  The sample ends.
+ *  3. The bounce: otherwise exactly what the render does at a live non-light vertex:
+ *      - o = o + (h.t - 1e-4f) * dir (ray.cpp:1262 / :1411);
+ *      - the roulette: u = rng_01(s); if !(u < rr) the sample ends without a record, and as sample 0 it gives ids = {0, ORT_NO_PRIM};
+ *      - sample_random_lights' burn (ray.cpp:537-601): one step, the light of index state % light_count, and four more steps if that
+ *        light is a sphere; with no lights the one step;
+ *      - wi = sample_brdf(s, h.n, wo, 0.01, Kd, Ks, Kt, ior, &is_trans): three draws, ray.cpp:1100-1161;
+ *      - if is_trans, o = o + (2.0f * 1e-4f) * dir, dir still being the arriving direction (ray.cpp:1345-1348);
+ *      - then dir = wi, wo = -wi, b++, and back to step 2.
+ * No pdf, BSDF value or path weight is evaluated, and none of them advances the stream.
+ * Outputs.  albedo = A / (float)spp, normal = N / (float)spp, depth = D / (float)spp, component by component (ray.cpp:1428's
+ * division); hits; bounces = B; final_states; ids as given above.  A mean over the RECORDED samples is the plane times spp / hits.
+ * Parameters.  params->policy must be ORT_POLICY_PIXEL.  params->spp is within [1, 1 << 24].  params->chunk is ignored.  params->rr
+ * is used, and is judged as the render call judges it.  max_bounces is within [0, ORT_MAX_FOLLOW_BOUNCES]; the cap bounds every path,
+ * so any rr the render call accepts is safe here.  shard_count > 1 and ORT_RENDER_PACKED return ORT_ERR_UNSUPPORTED.  The views form,
+ * the rule where a camera may stand, ORT_MAX_VIEWS and view_count == 0 are as in ort_render_views_features; the single-frame call is
+ * the one-view batch of the scene's own camera and params->seed.
+ * Six identities, all bit for bit.  (1) max_bounces == 0 gives ort_render_features' six planes for any scene and rr; bounces is all
+ * zero.  (2) A scene in which every non-light material has |Kd|^2 > 0 gives those planes for every max_bounces and rr.  (3) Take the
+ * diffuse twin of the scene: every non-light material with |Kd|^2 > 0 made a light, everything else untouched.  While no sample
+ * reaches the cap, final_states equals the final states of the twin's ort_render_image ORT_POLICY_PIXEL jobs at the same seed, spp
+ * and rr.  (4) Frame v of a batch is, in every plane, the single-frame call's frame for that camera and seed.  (5) Which planes are
+ * asked for changes no bit of the others.  (6) The recorded vertex of sample 0 at spp 1 is ort_raycast's record for the last ray of
+ * the chain.
+ * Errors are reported before any device work, in ort_render_views_features' order: ORT_ERR_INVALID (null planes struct, all of the
+ * first six planes NULL, null views, view cap exceeded, null scene or params, empty or bad params exactly as ort_render_image judges
+ * them, rr included; then spp above 1 << 24, max_bounces above ORT_MAX_FOLLOW_BOUNCES, a plane not 4-byte aligned),
+ * ORT_ERR_UNSUPPORTED (policy, shard, packed, camera outside the box), ORT_ERR_STATE (scene not committed), ORT_ERR_NO_DEVICE (not
+ * uploaded).
+ * The device forms are as ort_render_features_device's.  stats follow the ray queries: with ORT_RENDER_COUNTERS, rays is every ray
+ * cast (camera rays plus bounce rays) and paths = 0; fallback_rays and kernel_ms are always filled. */
+#define ORT_MAX_FOLLOW_BOUNCES 64u
+typedef struct {
+    float    *albedo;        /* 3 f32 per pixel   may be NULL */
+    float    *normal;        /* 3 f32 per pixel   may be NULL */
+    float    *depth;         /* f32               may be NULL */
+    uint32_t *hits;          /* u32               may be NULL */
+    uint32_t *ids;           /* 2 u32: mat, prim  may be NULL */
+    uint32_t *bounces;       /* u32               may be NULL */
+    uint32_t *final_states;  /* u32               may be NULL */
+} ort_follow_planes;         /* HOST pointers in the host forms, DEVICE pointers in the _device forms; the struct itself is host memory */
+
+/* host planes in, host planes out (device staging is internal); synchronous */
+int ort_render_follow(ort_scene *scene, const ort_render_params *params, uint32_t max_bounces, const ort_follow_planes *planes, ort_stats *stats);
+int ort_render_follow_device(ort_scene *scene, const ort_render_params *params, uint32_t max_bounces, const ort_follow_planes *planes,
+                             void *hip_stream, ort_stats *stats);
+/* view_count frames per plane, view-major */
+int ort_render_views_follow(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
+                            uint32_t max_bounces, const ort_follow_planes *planes, ort_stats *stats);
+int ort_render_views_follow_device(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
+                                   uint32_t max_bounces, const ort_follow_planes *planes, void *hip_stream, ort_stats *stats);
+
 /* ---- denoising: a variance-guided, edge-avoiding a-trous filter over rendered frames -----------
  * What uses the planes above: the mean colour with its sample count n and its sum of squared sample luminance Q (ort_render_adaptive,
  * ort_render_sample_map, ort_render_accumulate) and the guide planes of ort_render_features.  `iterations` passes of 5 x 5 taps at
@@ -912,7 +991,8 @@ int ort_render_views_features_device(ort_scene *scene, const ort_render_params *
  *  - result.  c'_p = S / W component by component, var'_p = V / (W*W).  Unusable pixels keep their entries.
  * After the last iteration out_rgb_k = c'_k * a_k.
  * Consequences.  A pixel with a zero normal (a miss) has wn = 0 with every neighbour and keeps its own value up to (rgb/a)*a.
- * Mirrors and glass are not followed by the feature planes: what is seen in them is filtered by the guides of the surface itself.
+ * Mirrors and glass are not followed by the feature planes: what is seen in them is filtered by the guides of the surface itself;
+ * ort_render_follow's planes follow them.
  * Values that become non-finite during the iterations propagate by IEEE rules; a NaN output matches the contract by position, not
  * by sign or payload, as elsewhere in this library.  Results do not depend on frame_count, on the tile shape, or on how pixels
  * fall on the GPU's lanes.

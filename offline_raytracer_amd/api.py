@@ -125,6 +125,16 @@ class FeaturePlanes(C.Structure):
                 ("final_states", C.c_void_p)]
 
 
+class FollowPlanes(C.Structure):
+    """ort_follow_planes: where a feature render that follows mirrors and glass writes (ort_render_follow); a null pointer is a
+    plane not asked for."""
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("hits", C.c_void_p), ("ids", C.c_void_p),
+                ("bounces", C.c_void_p), ("final_states", C.c_void_p)]
+
+
+assert C.sizeof(FollowPlanes) == 56
+
+
 class LightGroups(C.Structure):
     _fields_ = [("group_of_material", C.c_void_p), ("material_count", C.c_uint32), ("group_count", C.c_uint32)]
 
@@ -176,6 +186,8 @@ class AccumPlanes(C.Structure):
 
 
 FEATURE_PLANES = ("albedo", "normal", "depth", "hits", "ids", "states")   # render_features()'s want=
+FOLLOW_PLANES = ("albedo", "normal", "depth", "hits", "ids", "bounces", "states")   # render_follow()'s want=
+MAX_FOLLOW_BOUNCES = 64   # ORT_MAX_FOLLOW_BOUNCES
 
 
 class Hit(C.Structure):
@@ -205,6 +217,7 @@ EXPORTS = [
     "ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes",
     "ort_render_adaptive", "ort_render_adaptive_device", "ort_render_views_adaptive", "ort_render_views_adaptive_device",
     "ort_render_features", "ort_render_features_device", "ort_render_views_features", "ort_render_views_features_device",
+    "ort_render_follow", "ort_render_follow_device", "ort_render_views_follow", "ort_render_views_follow_device",
     "ort_render_light_groups", "ort_render_light_groups_device", "ort_render_views_light_groups",
     "ort_render_views_light_groups_device",
     "ort_render_sample_map", "ort_render_sample_map_device", "ort_render_views_sample_map", "ort_render_views_sample_map_device",
@@ -285,6 +298,8 @@ def lib():
                 ("ort_render_views_accumulate", [vp, C.POINTER(RenderParams), vp, C.c_uint32, C.POINTER(AccumPlanes), vp, vp, stats]),
                 ("ort_render_features", [vp, C.POINTER(RenderParams), C.POINTER(FeaturePlanes), stats]),
                 ("ort_render_views_features", [vp, C.POINTER(RenderParams), vp, C.c_uint32, C.POINTER(FeaturePlanes), stats]),
+                ("ort_render_follow", [vp, C.POINTER(RenderParams), C.c_uint32, C.POINTER(FollowPlanes), stats]),
+                ("ort_render_views_follow", [vp, C.POINTER(RenderParams), vp, C.c_uint32, C.c_uint32, C.POINTER(FollowPlanes), stats]),
                 ("ort_raycast", [vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
                 ("ort_occluded", [vp, vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
                 ("ort_ambient_occlusion", [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint32, stats]),
@@ -967,6 +982,76 @@ class Scene:
         views = _views(cameras, seeds)
         return self._features_device(views, params, d_planes, stream, want_stats)
 
+    # -- feature renders that follow mirrors and glass: the planes of the first non-specular vertex ---
+    @staticmethod
+    def _follow_planes(shape, want, out):
+        """the host planes of a follow render, by name: zeros, or the caller's (out: a dict by the names of want, checked)"""
+        specs = {"albedo": (shape + (3,), "<f4"), "normal": (shape + (3,), "<f4"), "depth": (shape, "<f4"), "hits": (shape, "<u4"),
+                 "ids": (shape + (2,), "<u4"), "bounces": (shape, "<u4"), "states": (shape, "<u4")}
+        want = tuple(want)
+        if not want or len(set(want)) != len(want) or not set(want) <= set(FOLLOW_PLANES):
+            raise ValueError("want must name planes of %s, each once, got %r" % (FOLLOW_PLANES, want))
+        if out is None:
+            return {k: np.zeros(*specs[k]) for k in want}
+        if set(out) != set(want):
+            raise ValueError("out must hold exactly the planes of want %r, got %r" % (want, tuple(out)))
+        for k in want:
+            if not _is_plane(out[k], *specs[k]):
+                raise ValueError("out[%r] must be a C-contiguous array of shape %s dtype %s" % ((k,) + specs[k]))
+        return dict(out)
+
+    @staticmethod
+    def _follow_struct(ptrs):
+        """name -> pointer (ints, ctypes pointers, None) -> FollowPlanes"""
+        unknown = set(ptrs) - set(FOLLOW_PLANES)
+        if unknown:
+            raise ValueError("unknown follow planes %r: the planes are %s" % (sorted(unknown), FOLLOW_PLANES))
+        fp = FollowPlanes()
+        for k in FOLLOW_PLANES:
+            v = _ptr(ptrs.get(k))
+            setattr(fp, "final_states" if k == "states" else k, v.value if isinstance(v, C.c_void_p) else v)
+        return fp
+
+    def _follow_host(self, views, width, height, spp, seed, max_bounces, rr, rect, want, counters, out):
+        planes = self._follow_planes(_lead(views) + (height, width), want, out)
+        p = self.params(width, height, spp, seed, "pixel", 0, rect, rr, counters)
+        fp = self._follow_struct({k: a.ctypes.data for k, a in planes.items()})
+        return planes, self._pixel_jobs("follow", views, False, p, [], [C.c_uint32(max_bounces), C.byref(fp)])
+
+    def _follow_device(self, views, params, max_bounces, d_planes, stream, want_stats):
+        fp = self._follow_struct(d_planes)
+        return self._pixel_jobs("follow", views, True, params, [], [C.c_uint32(max_bounces), C.byref(fp)], stream, want_stats)
+
+    def render_follow(self, width, height, spp, seed, max_bounces=8, rr=0.8, want=("albedo", "normal", "depth", "hits", "ids", "bounces"),
+                      rect=None, counters=False, out=None):
+        """render_features with mirrors and glass followed: every camera sample goes on through surfaces that are neither a light
+        nor have a diffuse part, as the render's own path does (roulette rr, the render's draws, at most max_bounces bounces,
+        max_bounces <= MAX_FOLLOW_BOUNCES), and what is recorded is the vertex where it ends: albedo, unit normal (as it stands),
+        the path's length from the aperture point, the samples that recorded a vertex (hits), sample 0's (mat, prim), the sum of
+        the recorded samples' bounces and, with "states" in want, the stream's final state.  The sums are divided by spp: over_hits
+        gives the mean over the recorded samples.  Returns (planes, stats dict) as render_features; bounces is (H, W) uint32.
+        max_bounces = 0 is render_features, bit for bit."""
+        return self._follow_host(None, width, height, spp, seed, max_bounces, rr, rect, want, counters, out)
+
+    def render_follow_device(self, params, max_bounces=8, stream=None, want_stats=False, **d_planes):
+        """The same into device planes: albedo=, normal=, depth=, hits=, ids=, bounces=, states= raw device pointers, those not given
+        are not written.  params: Scene.params(..., policy="pixel"); its chunk is ignored, its rr is the roulette's.  Enqueued on
+        stream; waits only when want_stats (returns the stats dict)."""
+        return self._follow_device(None, params, max_bounces, d_planes, stream, want_stats)
+
+    def render_views_follow(self, cameras, seeds, width, height, spp, max_bounces=8, rr=0.8,
+                            want=("albedo", "normal", "depth", "hits", "ids", "bounces"), rect=None, counters=False, out=None):
+        """render_follow for a batch of views in one launch (cameras, seeds as render_views): frame v is what render_follow gives
+        with seed seeds[v] if the scene's camera were cameras[v].  Every plane has a leading axis of V frames."""
+        views = _views(cameras, seeds)
+        return self._follow_host(views, width, height, spp, 0, max_bounces, rr, rect, want, counters, out)
+
+    def render_views_follow_device(self, params, cameras, seeds, max_bounces=8, stream=None, want_stats=False, **d_planes):
+        """The same into device planes of V frames each, view-major.  Enqueued on stream; waits only when want_stats (returns
+        the stats dict).  params.seed is ignored."""
+        views = _views(cameras, seeds)
+        return self._follow_device(views, params, max_bounces, d_planes, stream, want_stats)
+
     # -- closest-hit ray queries -----------------------------------------------------------
     def raycast(self, rays, counters=False):
         """Closest hit of each ray (raycast_top_most_node, ray.cpp:1165).  rays: (N, 6) float32 o.xyz d.xyz (d need
@@ -1321,6 +1406,15 @@ def _denoise_params(iterations, normal_squarings, sigma_l, sigma_z):
         if not 0 <= int(v) <= 0xFFFFFFFF:
             raise ValueError("%s must fit an unsigned 32-bit word, got %r" % (name, v))
     return DenoiseParams(int(iterations), int(normal_squarings), float(sigma_l), float(sigma_z))
+
+
+def over_hits(plane, hits, spp):
+    """a plane of render_follow or render_features (a sum divided by spp) as the mean over the samples that recorded a vertex:
+    plane * spp / hits in float32, and 0 where hits is 0.  plane (..., H, W) or (..., H, W, 3), hits (..., H, W)"""
+    plane, hits = np.asarray(plane, "<f4"), np.asarray(hits)
+    h = hits.reshape(hits.shape + (1,) * (plane.ndim - hits.ndim)).astype("<f4")
+    with np.errstate(all="ignore"):
+        return np.where(h > 0, plane * np.float32(spp) / h, np.float32(0)).astype("<f4")
 
 
 def denoise_workspace_bytes(width, height, frame_count=1):

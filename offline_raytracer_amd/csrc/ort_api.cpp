@@ -705,6 +705,36 @@ static int render_features_common(ort_scene *s, const ort_render_params *p, cons
         });
 }
 
+/* Feature renders that follow mirrors and glass: render_features_common's order.  Nulls: the planes struct, all of the first six
+   planes, the views.  rr IS the caller's here, judged with the params.  Own checks: spp above 1 << 24, max_bounces above
+   ORT_MAX_FOLLOW_BOUNCES, the planes' alignment.  The launch is device_render_follow */
+static int render_follow_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool batch, bool host,
+                                uint32_t max_bounces, const ort_follow_planes *planes, void *stream, ort_stats *stats) {
+    static const PixelJobKind kind = {"the follow render cuts one-pixel jobs: it needs the PIXEL policy", "the follow render is not sharded",
+                                      "the follow render has no packed planes"};
+    return render_pixel_jobs(
+        kind, s, p, views, view_count, batch, host, stream, stats,
+        [&] {
+            if (!planes) return fail(ORT_ERR_INVALID, "null planes");
+            if (!planes->albedo && !planes->normal && !planes->depth && !planes->hits && !planes->ids && !planes->bounces)
+                return fail(ORT_ERR_INVALID, "no plane is asked for: albedo, normal, depth, hits, ids and bounces are all null");
+            return batch && !views ? fail(ORT_ERR_INVALID, "null views") : ORT_OK;
+        },
+        [](ort_render_params *) {},
+        [&](const ort_render_params &q) {
+            if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp must be <= 1 << 24: a sample count must be exact in float");
+            if (max_bounces > ORT_MAX_FOLLOW_BOUNCES) return fail(ORT_ERR_INVALID, "max_bounces must be <= ORT_MAX_FOLLOW_BOUNCES");
+            return check_ptrs({{planes->albedo, false, 4}, {planes->normal, false, 4}, {planes->depth, false, 4}, {planes->hits, false, 4}, {planes->ids, false, 4},
+                               {planes->bounces, false, 4}, {planes->final_states, false, 4}}, "", "",
+                              "albedo, normal, depth, hits, ids, bounces and final_states must be 4-byte aligned");
+        },
+        [&](const ort_render_params &q, const ort::RenderCall &c) {
+            std::string err;
+            const int rc = ort::device_render_follow(s, &q, c.views, c.view_count, max_bounces, {host, 0, q.flags, stream, stats}, *planes, &err);
+            return rc == ORT_OK ? ORT_OK : fail(rc, err);
+        });
+}
+
 static int ort_render_views_workspace_bytes_impl(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) {
     if (!p || !bytes) return fail(ORT_ERR_INVALID, "null argument");
     *bytes = ort::render_views_workspace_bytes(p, view_count);
@@ -909,6 +939,10 @@ int ort_render_features(ort_scene *s, const ort_render_params *p, const ort_feat
 int ort_render_features_device(ort_scene *s, const ort_render_params *p, const ort_feature_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, nullptr, 1, false, false, planes, hip_stream, stats); }); }
 int ort_render_views_features(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_feature_planes *planes, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, views, view_count, true, true, planes, nullptr, stats); }); }
 int ort_render_views_features_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_feature_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_features_common(s, p, views, view_count, true, false, planes, hip_stream, stats); }); }
+int ort_render_follow(ort_scene *s, const ort_render_params *p, uint32_t max_bounces, const ort_follow_planes *planes, ort_stats *stats) { return guarded([&]() { return render_follow_common(s, p, nullptr, 1, false, true, max_bounces, planes, nullptr, stats); }); }
+int ort_render_follow_device(ort_scene *s, const ort_render_params *p, uint32_t max_bounces, const ort_follow_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_follow_common(s, p, nullptr, 1, false, false, max_bounces, planes, hip_stream, stats); }); }
+int ort_render_views_follow(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, uint32_t max_bounces, const ort_follow_planes *planes, ort_stats *stats) { return guarded([&]() { return render_follow_common(s, p, views, view_count, true, true, max_bounces, planes, nullptr, stats); }); }
+int ort_render_views_follow_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, uint32_t max_bounces, const ort_follow_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_follow_common(s, p, views, view_count, true, false, max_bounces, planes, hip_stream, stats); }); }
 int ort_render_views_workspace_bytes(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) { return guarded([&]() { return ort_render_views_workspace_bytes_impl(p, view_count, bytes); }); }
 int ort_shard_block_count(int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, uint64_t *blocks) { return guarded([&]() { return ort_shard_block_count_impl(width, height, shard_index, shard_count, blocks); }); }
 int ort_pack_blocks_host(const float *full_rgb, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, float *packed) { return guarded([&]() { return ort_pack_blocks_host_impl(full_rgb, width, height, shard_index, shard_count, packed); }); }

@@ -836,6 +836,45 @@ int device_render_features(Scene *scene, const ort_render_params *p, const ort_v
     return settle_inflight(d, err);
 }
 
+/* feature renders that follow mirrors and glass: device_render_features with the seven planes of ort_render_follow -- the seventh
+   stages through the render's frame buffer (d->staging), which no query uses --, follow_view's rr, the cap in the kernels' third
+   argument and plan_follow's plan */
+int device_render_follow(Scene *scene, const ort_render_params *p, const ort_view *views, uint32_t view_count, uint32_t max_bounces, const QueryCall &q,
+                         const ort_follow_planes &planes, std::string *err) {
+    DeviceScene *d;
+    int rc;
+    if ((rc = begin_query(scene, q.stats, &d, err)) || (rc = ensure_prim_src(scene, d, err))) return rc;
+    hipStream_t stream = (hipStream_t)q.stream;
+    /* the staging buffers and both copies of the camera table are the previous call's until that has finished */
+    if ((rc = settle_inflight(d, err))) return rc;
+    const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
+    DevBuf *const st = d->query_stage;
+    Plane pn[7] = {{planes.albedo, st, pixels * 12u, nullptr}, {planes.normal, st + 1, pixels * 12u, nullptr}, {planes.depth, st + 2, pixels * 4u, nullptr},
+                   {planes.hits, st + 3, pixels * 4u, nullptr}, {planes.ids, st + 4, pixels * 8u, nullptr}, {planes.final_states, st + 5, pixels * 4u, nullptr},
+                   {planes.bounces, &d->staging, pixels * 4u, nullptr}};
+    static_assert(sizeof(pn) / sizeof(pn[0]) <= sizeof(d->query_stage) / sizeof(d->query_stage[0]) + 1, "one staging buffer per plane");
+    if ((rc = stage_planes_in(pn, 7, q.host, stream, err)) || (rc = upload_view_table(d, views, view_count, stream, err))) return rc;
+    RenderView rv{};
+    follow_view(*p, view_count, &rv);
+    rv.views = d->view_tab.as<const float4>();
+    FollowIO io{};
+    io.q = ray_query_io(scene, d, nullptr);
+    io.q.prim_src = d->prim_src.as<const uint32_t>();
+    io.albedo = (float *)pn[0].dev; io.normal = (float *)pn[1].dev; io.depth = (float *)pn[2].dev;
+    io.hits = (uint32_t *)pn[3].dev; io.ids = (uint32_t *)pn[4].dev; io.states = (uint32_t *)pn[5].dev; io.bounces = (uint32_t *)pn[6].dev;
+    io.max_bounces = max_bounces;
+    const bool counters = (q.flags & ORT_RENDER_COUNTERS) != 0;
+    auto planner = [&](const SceneTraits &t, const Knobs &kn) { return plan_follow(t, *p, view_count, counters, kn); };
+    rc = launch_planned(scene, d, rv, rv.job_count, planner, false, stream, q.stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &plan) {
+        with_bools([&](auto C, auto T) {
+            hipLaunchKernelGGL((follow_pixels<decltype(C)::value, decltype(T)::value>), dim3(plan.grid), dim3(kBlock), 0, stream, sv, hot, io);
+        }, plan.counters, plan.tabs);
+    });
+    if (rc || (rc = stage_planes_out(pn, 7, q.host, stream, err)) || !q.host) return rc;
+    ORT_HIP(hipStreamSynchronize(stream));
+    return settle_inflight(d, err);
+}
+
 /* radiance: count rays with their seeds -> 3 floats each and, where asked for (states may be null), the final states.  No shape
    table: a colour names no shape.  With ad (checked by the caller) the adaptive query: the stopping rule's parameters where spp
    stands, and, where asked for, every ray's sample count and its sum of squared sample luminance; plan_radiance's plan as it

@@ -257,6 +257,20 @@ struct FeatureIO {
     uint32_t *states;       /* 1 per pixel, or null: the stream after 2 * spp steps */
 };
 
+/* the third argument of follow_pixels: the planes of ort_render_follow, laid out as FeatureIO's.  rr is the RenderView's
+   (follow_view, ort_setup.h) */
+struct FollowIO {
+    RaycastIO q;            /* q.prim_src, and what raycast_needs_exact reads.  rays and hits are null */
+    float *albedo;          /* 3 per pixel, or null */
+    float *normal;          /* 3 per pixel, or null */
+    float *depth;           /* 1 per pixel, or null: the path's length from the aperture point to the recorded vertex */
+    uint32_t *hits;         /* 1 per pixel, or null: samples that recorded a vertex */
+    uint32_t *ids;          /* 2 per pixel, or null: mat, prim of sample 0's last vertex */
+    uint32_t *bounces;      /* 1 per pixel, or null: the bounces followed, summed over the recorded samples */
+    uint32_t *states;       /* 1 per pixel, or null: the stream after the last sample */
+    uint32_t max_bounces;   /* <= ORT_MAX_FOLLOW_BOUNCES: a vertex reached after this many bounces is recorded whatever it is */
+};
+
 } // namespace ort
 
 #ifndef ORT_HOST_SIM
@@ -3042,6 +3056,184 @@ feature_pixels(SceneView sv, RenderHot rv, FeatureIO io) {
     __shared__ float lds_job[kFeatureCacheWords * kBlock]; /* the job's sums (feature_lane) */
     if (TABS) fill_tab(sv, lds_tab);
     feature_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(TABS, LF_TABS)>(sv, rv, io, lds_tab, lds_stack, lds_job + threadIdx.x, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+}
+#endif
+
+/* ---- feature renders that follow mirrors and glass (ort_render_follow): the planes of the first non-specular vertex ----------
+ * feature_lane's job, job space and camera sample; but a sample whose vertex is neither a light nor has a diffuse part goes on
+ * as the render's own path does at a live non-light vertex (produce_ray: ray.cpp:1262, the roulette, sample_random_lights'
+ * burn, sample_brdf's three draws, the 2 eps step through a refracting surface) until it meets a vertex that is one of the two,
+ * or has bounced max_bounces times: THAT vertex is recorded.  No pdf, BSDF value or weight is evaluated; none advances the stream.
+ * A separate lane, not a flavour of feature_lane: the first-hit kernels' code stays as it is (profiles/r28_isa_diff.txt).
+ * WHERE A SAMPLE STARTS AND WHERE IT BOUNCES.  The idle lanes settle the finished vertex; those that bounce hold draw.phi, the
+ * others end the sample (and perhaps the job, and draw the next pixel) and hold the aperture angle: both meet at ONE converged
+ * ort_sincosf per pass of the outer loop, as pt_lane's two kinds of lanes do, and at one normalize behind it (ray.cpp:1158 / :1237).
+ * WHERE THE JOB'S STATE LIVES.  feature_lane's seven sums and the path's length so far (L) are touched once per vertex and never
+ * inside the walk: eight per-lane LDS words.  A ninth, for the sum of the recorded samples' bounces (B), is 544 bytes more than
+ * the counters build with tables has at four blocks a CU (profiles/r28_follow.md), so B is a register, and the bounces of the path
+ * in hand (b <= 64) share one with the hit count (<= 1 << 24): hb = hits | b << 25.  wo is not held: it is -dir at a bounce vertex
+ * and -normalize(dir) at the primary one (ray.cpp:1241, sic).  The material is loaded once after resolve_hit, for the terminal
+ * test and the draw alike. */
+constexpr int kFollowCacheWords = 8; /* albedo.xyz, normal.xyz, depth; L */
+constexpr uint32_t kFollowHitsMask = (1u << 25) - 1u, kFollowBounce = 1u << 25; /* hb: the hit count below, b above */
+
+template <uint32_t F>
+ORT_D void follow_lane(const SceneView &sv, const RenderHot &rv, const FollowIO &io, const float4 *tab, uint32_t *lds_stack, float *job_cache, const int tid,
+                       const uint32_t lane_id, unsigned long long *pool) {
+    static_assert(flavour_ok(F, LF_OF_LANE), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS, TABS = F & LF_TABS;
+    uint32_t spill[kSpillStack];
+    PathState P; /* org, dir; rng; pxy; job_index: the view; sample: the samples of this pixel started so far */
+    HitState h;
+    Trav T;
+    Counters c;
+    Prof pr;
+    const uint32_t spp = rv.c->spp;
+    uint32_t hb = 0, B = 0;
+    bool tracing = false, held = false, busy = false, more = true; /* as feature_lane's */
+    for (;;) {
+        if (!tracing) {
+            bool bounce = false;
+            float angle = 0.0f;
+            BrdfDraw draw;
+            Mat m;
+            V3 n = mk(0, 0, 0);
+            if (held) { /* the finished vertex: raycast_lane's record */
+                resolve_hit<resolve_of(F), kLdsStack, kBlock>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+                uint32_t id_mat = h.hit_mat;
+                bool died = false;
+                if (h.hit_mat != 0u) {
+                    if (TABS) m = load_mat(tab + kTabMats, h.hit_mat);
+                    else m = load_mat(sv.materials, h.hit_mat);
+                    n = normalize(h.hit_n); /* ray.cpp:817, as raycast_lane returns it */
+                    const float L = job_cache[7 * kBlock] + h.best_t;
+                    job_cache[7 * kBlock] = L;
+                    if (m.is_light || len2(m.kd) > 0.0f || (hb >> 25) == io.max_bounces) { /* ray.cpp:1254, :1267; the cap */
+                        const V3 a = m.is_light ? m.emit : m.kd;
+                        hb++;
+                        cache_add_v3(job_cache, a);
+                        cache_add_v3(job_cache + 3 * kBlock, n);
+                        job_cache[6 * kBlock] = job_cache[6 * kBlock] + L;
+                        B += hb >> 25;
+                    } else {
+                        P.org = add(P.org, scale(h.best_t - kEps, P.dir)); /* ray.cpp:1262,1411 */
+                        bounce = rng_01(P.rng) < rv.rr;                    /* ray.cpp:1280 */
+                        if (bounce) {
+                            /* sample_random_lights (ray.cpp:537-601): result unused, RNG advances; as produce_ray's */
+                            rng_step(P.rng);
+                            if (sv.light_count) {
+                                uint32_t li = 0u;
+                                if (sv.light_count != 1u) li = P.rng % sv.light_count;
+                                uint32_t is_sphere;
+                                if (TABS) is_sphere = ((const uint32_t *)tab)[4 * kTabLights + li];
+                                else is_sphere = sv.light_is_sphere[li];
+                                if (is_sphere) { rng_step(P.rng); rng_step(P.rng); rng_step(P.rng); rng_step(P.rng); }
+                            }
+                            draw = sample_brdf_draw<false>(P.rng, kRoughness, m);
+                            angle = draw.phi;
+                        } else {
+                            died = true;
+                            id_mat = 0u;
+                        }
+                    }
+                }
+                if (!bounce && P.sample == 1u && io.ids) { /* sample 0's last vertex; a path the roulette ended has none */
+                    const uint32_t src = !died && h.hit_prim != kNoPrim ? io.q.prim_src[info_index(sv, h.hit_prim)] : kNoPrim;
+                    const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
+                    io.ids[2u * at] = id_mat;
+                    io.ids[2u * at + 1u] = src;
+                }
+                held = false;
+            }
+            bool start = false;
+            if (!bounce) for (;;) { /* the job's end and the next pixel */
+                if (busy) {
+                    if (P.sample < spp) { start = true; break; }
+                    const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
+                    const float fs = (float)spp; /* ray.cpp:1428's division, component by component */
+                    if (io.albedo) { float *o = io.albedo + 3u * at; const V3 s = cache_v3(job_cache); o[0] = s.x / fs; o[1] = s.y / fs; o[2] = s.z / fs; }
+                    if (io.normal) { float *o = io.normal + 3u * at; const V3 s = cache_v3(job_cache + 3 * kBlock); o[0] = s.x / fs; o[1] = s.y / fs; o[2] = s.z / fs; }
+                    if (io.depth) io.depth[at] = job_cache[6 * kBlock] / fs;
+                    if (io.hits) io.hits[at] = hb & kFollowHitsMask;
+                    if (io.bounces) io.bounces[at] = B;
+                    if (io.states) io.states[at] = P.rng;
+                    busy = false;
+                }
+                if (!more) break;
+                const unsigned long long j = draw_job(rv, pool);
+                if (!(j < rv.c->job_count)) { more = false; break; }
+                const uint32_t view = (uint32_t)(j / rv.c->view_jobs), within = (uint32_t)(j % rv.c->view_jobs);
+                const BlockPixel bp = block_pixel(rv, within >> 6, within & 63u);
+                if (bp.outside) continue;
+                const int x = bp.x, y = bp.y;
+                P.job_index = view;
+                P.pxy = (uint32_t)x | ((uint32_t)y << 16);
+                P.rng = job_seed(om_f32_bits(rv.c->views[4u * (size_t)view].w), (uint32_t)(y * rv.W + x));
+                P.sample = 0;
+                hb = 0;
+                B = 0;
+                for (int k = 0; k < kFollowCacheWords; ++k) job_cache[k * kBlock] = 0.0f;
+                busy = true;
+            }
+            if (start || bounce) {
+                /* the lanes that start a camera sample (as produce_ray composes it) and the lanes that bounce: one converged
+                   sin/cos of the aperture angle / the lobe's azimuth, and one converged normalize of what comes out */
+                ViewCamera cam;
+                V3 focal = mk(0, 0, 0);
+                if (start) {
+                    cam = load_view_camera(rv, P.job_index);
+                    focal = view_focal_point(rv, P.pxy, cam);
+                    angle = rng_between(P.rng, 0.0f, 2 * kPi); /* ray.cpp:1232 */
+                }
+                float sn, cs;
+                ort_sincosf(angle, &sn, &cs);
+                V3 raw, ap = mk(0, 0, 0);
+                bool is_trans = false;
+                if (bounce) {
+                    const V3 wo = (hb >> 25) == 0u ? neg(normalize(P.dir)) : neg(P.dir); /* ray.cpp:1241 (sic) / :1408 */
+                    raw = sample_brdf_finish<false>(n, normalize(n), wo, m, draw, cs, sn, is_trans);
+                } else {
+                    ap = view_aperture_point(cam, 0.1f, cs, sn); /* ray.cpp:1199, :1233-1234 */
+                    raw = sub(focal, ap);                        /* ray.cpp:1237 */
+                }
+                const V3 unit = normalize(raw);
+                if (bounce) {
+                    if (is_trans) P.org = add(P.org, scale(2.0f * kEps, P.dir)); /* ray.cpp:1345-1348: dir is still the arriving direction */
+                    P.dir = unit;
+                    hb += kFollowBounce;
+                } else {
+                    P.org = ap;
+                    P.dir = unit;
+                    P.sample++;
+                    hb &= kFollowHitsMask;
+                    job_cache[7 * kBlock] = 0.0f;
+                }
+                begin_ray<begin_of(F), kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
+                /* a primary ray is ort_raycast's; a bounce ray starts at a hit and needs no rule, as in the render */
+                if (!bounce && ORT_RARE(raycast_needs_exact(io.q, P.org, P.dir, T.inv_d))) skip_fast_walk(T, h);
+                if (COUNTERS) c.rays++;
+                tracing = held = true;
+            }
+        }
+        /* a lane that neither traces, owns a pixel nor is entitled to another draw has none and will get none */
+        if (ORT_BALLOT(tracing || busy || more) == 0ull) break;
+        if (tracing) tracing = traverse<walk_of(F), kLdsStack, kBlock>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+    }
+    flush_counters(rv, c, COUNTERS);
+}
+
+/* TABS: the prologue shapes, the materials AND the lights fit their LDS slots (plan_follow, ort_plan.h); otherwise all three are
+   read from HBM */
+#ifndef ORT_HOST_SIM
+template <bool COUNTERS, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+follow_pixels(SceneView sv, RenderHot rv, FollowIO io) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    __shared__ float lds_job[kFollowCacheWords * kBlock]; /* the job's sums and L (follow_lane) */
+    if (TABS) fill_tab(sv, lds_tab);
+    follow_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(TABS, LF_TABS)>(sv, rv, io, lds_tab, lds_stack, lds_job + threadIdx.x, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 #endif
 

@@ -521,6 +521,16 @@ inline QueryPlan plan_features(const SceneTraits &t, const ort_render_params &p,
     return pl;
 }
 
+/* The launch of a feature render that follows mirrors and glass (ort_render_follow and its views forms; the follow_pixels
+   kernels): plan_features' rules over the same job space, with one difference: these lanes read the lights' table too
+   (sample_random_lights' burn at every bounce), so tabs asks for all three small tables (TAB_PRO, TAB_MATS and TAB_LIGHTS); a scene
+   past any of the three caps reads all of them from HBM.  Nothing of the plan has been tuned for paths longer than one ray. */
+inline QueryPlan plan_follow(const SceneTraits &t, const ort_render_params &p, uint32_t view_count, bool counters, const Knobs &kn) {
+    QueryPlan pl = plan_features(t, p, view_count, counters, kn);
+    pl.tabs = (t.tab_flags & kPlanAllTabs) == kPlanAllTabs;
+    return pl;
+}
+
 /* The launch of a radiance query over count rays (ort_radiance; the radiance_rays kernels): always the plain persistent loop at
    four waves.  The ray exchange, the five-waves unit, the wide tree and wavefront mode are not built with a ray job space and
    their knobs are not looked at; ORT_DEBUG_UTIL has no probes here.  diffuse, tabs, the refill and descend thresholds and the

@@ -269,6 +269,10 @@ int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const vo
    held */
 int device_render_features(Scene *scene, const ort_render_params *p, const ort_view *views, uint32_t view_count, const QueryCall &q,
                            const ort_feature_planes &planes, std::string *err);
+/* feature renders that follow mirrors and glass: device_render_features' frames, forms and staging with the seven planes of
+   ort_render_follow; p->rr is the roulette's, max_bounces (checked by the caller) the cap on every path */
+int device_render_follow(Scene *scene, const ort_render_params *p, const ort_view *views, uint32_t view_count, uint32_t max_bounces, const QueryCall &q,
+                         const ort_follow_planes &planes, std::string *err);
 /* the denoiser (include/ort.h: ort_denoise), on `device` and without a scene.  host: every plane and out_rgb are the caller's
    memory, staged whole, and the workspace is the call's own (workspace unread); otherwise all are device pointers, the workspace is
    the caller's and the passes are enqueued on stream.  The arguments are checked by the caller */

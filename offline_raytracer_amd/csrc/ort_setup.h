@@ -216,6 +216,13 @@ inline void features_view(const ort_render_params &p, uint32_t view_count, View 
     rv->job_count = rv->view_jobs * view_count;
 }
 
+/* feature renders that follow mirrors and glass (follow_lane): features_view, and the roulette's rr, which these lanes read */
+template <typename View>
+inline void follow_view(const ort_render_params &p, uint32_t view_count, View *rv) {
+    features_view(p, view_count, rv);
+    rv->rr = p.rr;
+}
+
 /* runtime bools to template arguments: f(std::bool_constant...) with one constant per bool, true first at every level */
 template <typename F>
 inline void with_bools(F f) { f(); }

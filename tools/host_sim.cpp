@@ -32,6 +32,8 @@
  *       (the adaptive camera render of the scene's own camera: pt_lane with LF_IMPLICIT | LF_VIEWS | LF_ADAPT over a one-view batch; the planes start
  *       at the guard values -7.0f, 0xeeeeeeee, -1.0f, 0xdddddddd, which pixels outside the rect keep)
  *   or: host_sim --features scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|-
+ *   or: host_sim --follow scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr max_bounces albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- bounces.u32|- states.u32|-
+ *       (the feature render that follows mirrors and glass, follow_lane: --features' arguments with rr, the cap and the bounces plane)
  *       (the first-hit feature render, feature_lane: a batch of views, or with cams - the scene's own camera on the seed given; a
  *       plane given as - is not passed; the planes start at -7.0f, 0xeeeeeeee and, the states, 0xdddddddd)
  *   or: host_sim --light-groups scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr groups.u8 G groups.f32 rgb.f32|- states.u32|-
@@ -744,6 +746,50 @@ static int features_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x
            (!want[4] || write_bytes(a[15], ids.data(), 8 * n)) && (!want[5] || write_bytes(a[16], states.data(), 4 * n)) ? 0 : 1;
 }
 
+/* the feature render that follows mirrors and glass (ort_render_follow and its views form): what device_render_follow sets up for
+   it, for one simulated lane per thread; features_mode's arguments with rr and the cap behind spp and the bounces plane before
+   the states */
+static int follow_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr max_bounces albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- bounces.u32|- states.u32|- */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
+    SimCameras c;
+    if (!sim_cameras(S, a[2], a[3], a + 4, &c)) return 1;
+    const uint32_t spp = (uint32_t)strtoul(a[10], 0, 10), cap = (uint32_t)strtoul(a[12], 0, 10);
+    if (spp == 0u || spp > (1u << 24)) { fprintf(stderr, "spp must be within [1, 1 << 24]\n"); return 1; }
+    if (cap > ORT_MAX_FOLLOW_BOUNCES) { fprintf(stderr, "max_bounces must be within [0, %u]\n", ORT_MAX_FOLLOW_BOUNCES); return 1; }
+    std::vector<uint32_t> src;
+    if (!invert_prim_slots(S.scene->tree, S.sv.info_box, S.sv.info_cyl, S.sv.info_sphere, src)) { fprintf(stderr, "the tree's slot maps are not a bijection onto its shape arrays\n"); return 1; }
+    bool want[7];
+    for (int k = 0; k < 7; ++k) want[k] = std::string(a[13 + k]) != "-";
+    const size_t n = c.n;
+    std::vector<float> albedo(want[0] ? 3 * n : 0, -7.0f), normal(want[1] ? 3 * n : 0, -7.0f), depth(want[2] ? n : 0, -7.0f);
+    std::vector<uint32_t> hits(want[3] ? n : 0, 0xeeeeeeeeu), ids(want[4] ? 2 * n : 0, 0xeeeeeeeeu), bounces(want[5] ? n : 0, 0xeeeeeeeeu),
+        states(want[6] ? n : 0, 0xddddddddu);
+    ort_render_params &p = c.p;
+    p.spp = spp; p.rr = (float)atof(a[11]);
+    FollowIO io{};
+    io.q = sim_query_io(S);
+    io.q.prim_src = src.data();
+    io.albedo = want[0] ? albedo.data() : nullptr; io.normal = want[1] ? normal.data() : nullptr; io.depth = want[2] ? depth.data() : nullptr;
+    io.hits = want[3] ? hits.data() : nullptr; io.ids = want[4] ? ids.data() : nullptr; io.bounces = want[5] ? bounces.data() : nullptr;
+    io.states = want[6] ? states.data() : nullptr;
+    io.max_bounces = cap;
+    RenderView rv{};
+    follow_view(p, c.nv, &rv);
+    rv.views = c.view_tab.data();
+    const RenderHot hot = query_hot(S, rv, (size_t)rv.job_count);
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
+        std::vector<float> job((kFollowCacheWords - 1) * kBlock + 1); /* exactly: a word beyond the lane's eight is a write past the block */
+        with_bools([&](auto T) { follow_lane<LF_COUNTERS | lf_if(decltype(T)::value, LF_TABS)>(sv, hot, io, S.tab, stack, job.data(), 0, w, nullptr); }, S.tab != nullptr);
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return (!want[0] || write_bytes(a[13], albedo.data(), 12 * n)) && (!want[1] || write_bytes(a[14], normal.data(), 12 * n)) &&
+           (!want[2] || write_bytes(a[15], depth.data(), 4 * n)) && (!want[3] || write_bytes(a[16], hits.data(), 4 * n)) &&
+           (!want[4] || write_bytes(a[17], ids.data(), 8 * n)) && (!want[5] || write_bytes(a[18], bounces.data(), 4 * n)) &&
+           (!want[6] || write_bytes(a[19], states.data(), 4 * n)) ? 0 : 1;
+}
+
 /* --tree-check scn base: the scene committed under the environment's knobs (ORT_LEAF_TRI, ORT_LEAF_OTHER, ORT_TREE_SPLIT_KINDS,
    ORT_ANALYTIC_PROLOGUE), and everything the lanes take for granted about what build_tree hands them, verified from the finished
    arrays alone: nothing of the builder's own bookkeeping is trusted but the scene's source shapes.  The first violation is
@@ -1005,6 +1051,7 @@ int main(int argc, char **argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
     if (argc == 4 && mode == "--tree-check") return tree_check_mode(argv + 2);
     if (argc == 19 && mode == "--features") return features_mode(argv + 2);
+    if (argc == 22 && mode == "--follow") return follow_mode(argv + 2);
     if (argc == 4 && mode == "--unit") return unit_mode(argv[2], argv[3]);
     if (argc == 6 && mode == "--raycast") return raycast_mode(argv + 2);
     if (argc == 7 && mode == "--occluded") return occluded_mode(argv + 2);
@@ -1032,6 +1079,7 @@ int main(int argc, char **argv) {
                         "       host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32\n"
                         "       host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
                         "       host_sim --features scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|-\n"
+                        "       host_sim --follow scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr max_bounces albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- bounces.u32|- states.u32|-\n"
                         "       host_sim --light-groups scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr groups.u8 G groups.f32 rgb.f32|- states.u32|-\n"
                         "       host_sim --sample-map scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32 rgb.f32 m2.f32|- states.u32|-\n"
                         "       host_sim --accumulate scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32|- sum.f32 m2.f32|- count.u32 states.u32 rgb.f32|-\n");
