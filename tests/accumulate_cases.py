@@ -16,6 +16,7 @@ import numpy as np
 import adaptive_cases as ac
 import host_sim_tool as hs
 import sample_map_cases as sm
+from hostile_materials import same_words
 
 F = np.float32
 W, H, CAP, SEED, RR, RECT = sm.W, sm.H, sm.CAP, sm.SEED, sm.RR, sm.RECT
@@ -49,16 +50,23 @@ class Planes:
         return p
 
 
-def assert_planes(got, want, what, skip=()):
-    """every word of the five planes; skip: names of planes the call was not given (the caller holds those against their guards)"""
+def assert_planes(got, want, what, skip=(), nan=False):
+    """every word of the five planes; skip: names of planes the call was not given (the caller holds those against their guards).
+    nan: the chains hold NaN (hostile materials), so the float planes go through hostile_materials.same_words -- equal bits, or a
+    NaN in both -> the NaN words expected in sum_rgb, m2 and out_rgb (0 without nan)"""
+    nans = 0
     for g, w_, name in zip(got.all(), want.all(), NAMES):
         if name in skip:
             continue
         assert g.shape == w_.shape and g.dtype == w_.dtype, "%s: %s %s vs %s" % (what, name, g.shape, w_.shape)
+        if nan:
+            nans += same_words(g, w_, "%s: %s" % (what, name))
+            continue
         ne = np.ascontiguousarray(g).view("<u4") != np.ascontiguousarray(w_).view("<u4")
         if ne.any():
             at = tuple(np.argwhere(ne)[0])
             raise AssertionError("%s: %d of %d words of %s differ; first at %s: %r vs %r" % (what, int(ne.sum()), ne.size, name, at, g[at], w_[at]))
+    return nans
 
 
 # ---- the reference ---------------------------------------------------------------------------------------------------------
@@ -175,6 +183,72 @@ def library_call(api, c, size=None, counters=True):
     return call
 
 
+# ---- the library, device forms: planes in device memory with guard words around them ---------------------------------------------
+PAD, PAD_WORD = 16, 0xABABABAB
+
+
+class DevicePlanes:
+    """the five planes of a Planes as torch tensors on device 0, PAD guard words before and after each; ptr: the planes' device
+    addresses in Planes.all()'s order.  Made inside the caller's stream context, so the uploads are ordered with its launches"""
+
+    def __init__(self, planes):
+        import torch
+        self.shape_of = planes
+        self.t = []
+        for a in planes.all():
+            words = np.ascontiguousarray(a).view("<u4").reshape(-1)
+            whole = np.concatenate([np.full(PAD, PAD_WORD, "<u4"), words, np.full(PAD, PAD_WORD, "<u4")]).view("<i4")
+            self.t.append(torch.from_numpy(whole).to(torch.device("cuda", 0)))
+        self.ptr = [x.data_ptr() + 4 * PAD for x in self.t]
+
+    def download(self):
+        """-> Planes; asserts that no guard word around a plane was written.  The caller has synchronised"""
+        got = self.shape_of.copy()
+        for x, g in zip(self.t, got.all()):
+            words = x.cpu().numpy().view("<u4")
+            assert (words[:PAD] == PAD_WORD).all() and (words[-PAD:] == PAD_WORD).all(), "a guard word around a plane was written"
+            g[...] = words[PAD:-PAD].view(g.dtype).reshape(g.shape)
+        return got
+
+
+def stream_split(c, split, seed=SEED, size=None):
+    """the passes of `split` -- no map, the whole frame, from count == 0 -- through ort_render_accumulate_device (every second pass
+    through ort_render_views_accumulate_device as a batch of one view, the scene's own camera) on a non-default stream, stats ==
+    NULL, no synchronisation between the passes and one at the end -> Planes.  A continued pass reads the sums, m2, counts and
+    states the pass before it wrote, in stream order"""
+    import torch
+    w, h = size if size else (W, H)
+    stream = torch.cuda.Stream(torch.device("cuda", 0))
+    with torch.cuda.stream(stream):
+        d = DevicePlanes(Planes(size=size))
+        for k, n in enumerate(split):
+            p = c.scene.params(w, h, n, seed, "pixel", 0, None, RR)
+            args = dict(d_m2=d.ptr[1], d_map=0, d_rgb=d.ptr[4], stream=stream.cuda_stream)
+            if k % 2:
+                st = c.scene.render_views_accumulate_device(p, np.asarray(c.camera(size), "<f4")[None], [seed], d.ptr[0], d.ptr[2], d.ptr[3], **args)
+            else:
+                st = c.scene.render_accumulate_device(p, d.ptr[0], d.ptr[2], d.ptr[3], **args)
+            assert st is None
+    torch.cuda.synchronize()
+    return d.download()
+
+
+def views_split(call, c, cams, seeds, split, what, nan=False, single=None):
+    """the passes of `split` through the views form on a batch: frame v against the oracle's chains from that camera and seed,
+    folded by model(); single: the planes of the single-frame form after the same passes, which a frame from the scene's own
+    camera on SEED must equal (frame 0 of the matrices' batches)"""
+    got, want = Planes(len(cams)), Planes(len(cams))
+    for n in split:
+        call(got, None, n, cams=cams, seeds=seeds)
+        for v in range(len(cams)):
+            model(want, v, sm.chains(c, int(seeds[v]), cams[v], cap=sum(split)), None, n, None)
+    assert_planes(got, want, what + ": against the oracle, view by view", nan=nan)
+    if single is not None:
+        for g, s_, name in zip(got.all(), single.all(), NAMES):
+            assert (np.ascontiguousarray(g[0]).view("<u4") == np.ascontiguousarray(s_[0]).view("<u4")).all(), "%s: view 0 against the single-frame form, %s" % (what, name)
+    return got
+
+
 # ---- the scenarios -----------------------------------------------------------------------------------------------------------
 def identity_1(call, c, sample_map_planes, what):
     """one call from count == 0 with the mixed map at cap 16 on the rect: the sample-map render's planes (sample_map_planes: its
@@ -211,11 +285,12 @@ def per_pixel_calls():
     return ((sm.mixed_map(0), CAP, RECT), (sm.mixed_map(3), 7, None), (None, 3, SMALL_RECT))
 
 
-def identity_2_per_pixel(call, c, what):
+def identity_2_per_pixel(call, c, what, chain=None, nan=False):
     """three calls -- the mixed map on the rect, the shifted mixed map at cap 7 on the whole frame, a constant 3 through a smaller
     rect -- against the chains cut at the cumulative counts.  A pixel no call sampled holds its guards; one that some but not
-    all calls sampled holds the earlier call's out_rgb"""
-    chain = sm.chains(c, cap=CAP + 7 + 3)
+    all calls sampled holds the earlier call's out_rgb.  chain: the oracle's of c by default; nan: as assert_planes
+    -> the planes after the third call"""
+    chain = sm.chains(c, cap=CAP + 7 + 3) if chain is None else chain
     got, want = Planes(), Planes()
     took = []
     for k, (m, cap, rect) in enumerate(per_pixel_calls()):
@@ -223,24 +298,30 @@ def identity_2_per_pixel(call, c, what):
         paths = call(got, m, cap, rect)
         assert paths in (None, model(want, 0, chain, m, cap, rect))
         took.append(want.count[0] != before)
-        assert_planes(got, want, "%s: after call %d" % (what, k))
+        assert_planes(got, want, "%s: after call %d" % (what, k), nan=nan)
     never = ~(took[0] | took[1] | took[2])
     earlier = took[0] & ~took[1] & ~took[2]
     assert never.any() and earlier.any() and (took[0] & took[1] & took[2]).any()
     assert (got.count[0][never] == 0).all() and (got.states[0][never] == GUARD_STATE).all() and (got.rgb[0][never] == GUARD_RGB).all()
     first = Planes()
     model(first, 0, chain, *per_pixel_calls()[0])
-    assert (got.rgb[0][earlier].view("<u4") == first.rgb[0][earlier].view("<u4")).all()
+    if nan:
+        same_words(got.rgb[0][earlier], first.rgb[0][earlier], what + ": the earlier call's out_rgb")
+    else:
+        assert (got.rgb[0][earlier].view("<u4") == first.rgb[0][earlier].view("<u4")).all()
+    return got
 
 
-def reference_split(call, chain, what):
-    """64 samples as 1 + 3 + 12 + 48 over the whole frame against the fold of the REFERENCE's chains (chains_rooms.npz)"""
+def reference_split(call, chain, what, split=REF_SPLIT, nan=False):
+    """64 samples as 1 + 3 + 12 + 48 (or as `split`) over the whole frame against the fold of the REFERENCE's chains
+    (chains_rooms.npz; chains_hostile.npz with nan, as assert_planes takes it) -> the expected planes after the last pass"""
     got, want = Planes(), Planes()
-    for k in REF_SPLIT:
+    for k in split:
         call(got, None, k)
         model(want, 0, chain, None, k, None)
-        assert_planes(got, want, "%s: after the pass of %d" % (what, k))
-    assert (got.count == 64).all()
+        assert_planes(got, want, "%s: after the pass of %d" % (what, k), nan=nan)
+    assert (got.count == sum(split)).all()
+    return want
 
 
 HOSTILE = (   # (x, y): count, state, sum, m2 -- pixels of RECT

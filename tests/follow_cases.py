@@ -19,6 +19,7 @@ import numpy as np
 import feature_cases as fc
 import host_sim_tool as hs
 import ref_io
+from hostile_materials import same_words
 
 F = np.float32
 W, H, SPPS, RECT, SEED, NO_PRIM = fc.W, fc.H, fc.SPPS, fc.RECT, fc.SEED, fc.NO_PRIM
@@ -29,6 +30,7 @@ SHAPES = dict(fc.SHAPES, bounces=())
 DTYPES = dict(fc.DTYPES, bounces="<u4")
 VIEW_SEEDS = [7, 0xDEADBEEF, 99]   # the batch: the scene's own camera on two more seeds, then pose 1 of views_cases.MOVES
 EPS, ROUGH = F(0.0001), F(0.01)    # ray.cpp:1196, :1194
+FLT_MAX = np.finfo("<f4").max     # the t of a cast that hit nothing
 SCENES = ["glass_room", "c2_analytic", "c3_bunny_room", "open"]
 SPECULAR_SCENES = ["glass_room", "c2_analytic"]
 
@@ -101,7 +103,10 @@ def _sample_brdf(oracle, state, n, wo, mats, mat):
 
 class Chain:
     """one frame's reference at one (spp, rr, cap): the sums A, N, D (n, ...), hits, B, ids_mat, died0 (sample 0 ended at the
-    roulette), last (n, 6): sample 0's last ray, states (n,), xs, ys, and the counts the conditions are stated on"""
+    roulette), void0 (sample 0 ended on a void shape: material 0 WITH a hit, which the oracle's t tells from a miss; void0_bounces:
+    the b it did so at), last (n, 6): sample 0's last ray, states (n,), xs, ys, and the counts the conditions are stated on --
+    among them void_ends (samples that end on a void shape), void_bounce_ends (those with b >= 1), followed_by_mat (per material,
+    the samples followed through it at b == 0) and nonfinite_dirs (bounce rays whose direction has a non-finite component)"""
 
 
 def chain(oracle, osc, flat, cam, w, h, seed, spp, rr, cap, rect=None):
@@ -120,7 +125,8 @@ def chain(oracle, osc, flat, cam, w, h, seed, spp, rr, cap, rect=None):
     state = fc.oracle_streams(oracle, seed, c.ys.astype(np.int64) * w + c.xs)
     c.A, c.N, c.D = np.zeros((n, 3), "<f4"), np.zeros((n, 3), "<f4"), np.zeros(n, "<f4")
     c.hits, c.B, c.ids_mat = np.zeros(n, "<u4"), np.zeros(n, "<u4"), np.zeros(n, "<u4")
-    c.died0, c.last = np.zeros(n, bool), np.zeros((n, 6), "<f4")
+    c.died0, c.void0, c.void0_bounces, c.last = np.zeros(n, bool), np.zeros(n, bool), np.zeros(n, np.int64), np.zeros((n, 6), "<f4")
+    c.void_ends, c.void_bounce_ends, c.nonfinite_dirs, c.followed_by_mat = 0, 0, 0, np.zeros(len(mats), np.int64)
     c.samples, c.rays, c.followed, c.deaths, c.refractions, c.max_b, c.at_cap, c.capped_specular = n * spp, 0, 0, 0, 0, 0, 0, 0
     with np.errstate(all="ignore"):
         for k in range(spp):
@@ -134,9 +140,14 @@ def chain(oracle, osc, flat, cam, w, h, seed, spp, rr, cap, rect=None):
                 c.rays += len(act)
                 c.max_b = max(c.max_b, int(b[act].max()))
                 t, nrm, mat = osc.raycast(o[act], dr[act])
+                void = (mat == 0) & (np.ascontiguousarray(t, "<f4").view("<u4") != FLT_MAX.view("<u4"))   # a void shape, not a miss
+                c.void_ends += int(void.sum())
+                c.void_bounce_ends += int((void & (b[act] >= 1)).sum())
                 if k == 0:
                     c.last[act] = np.concatenate([o[act], dr[act]], axis=1)
                     c.ids_mat[act] = mat
+                    c.void0[act] = void
+                    c.void0_bounces[act] = np.where(void, b[act], 0)
                 hit = mat != 0
                 a, t, nrm, mat = act[hit], t[hit], nrm[hit], mat[hit]
                 L[a] = (L[a] + t).astype("<f4")
@@ -152,6 +163,7 @@ def chain(oracle, osc, flat, cam, w, h, seed, spp, rr, cap, rect=None):
                 c.hits[ta] += 1
                 ba, tb, nb, mb = a[~term], t[~term], nrm[~term], mat[~term]
                 c.followed += int((b[ba] == 0).sum())
+                c.followed_by_mat += np.bincount(mb[b[ba] == 0], minlength=len(mats))
                 o[ba] = (o[ba] + ((tb - EPS).astype("<f4")[:, None] * dr[ba]).astype("<f4")).astype("<f4")   # ray.cpp:1262 / :1411
                 alive = np.zeros(len(ba), bool)
                 for i, p in enumerate(ba):
@@ -170,6 +182,7 @@ def chain(oracle, osc, flat, cam, w, h, seed, spp, rr, cap, rect=None):
                 if len(sa):
                     wi, tr, state[sa] = _sample_brdf(oracle, state[sa], nb[alive], wo[sa], mats, mb[alive])
                     c.refractions += int(tr.sum())
+                    c.nonfinite_dirs += int((~np.isfinite(wi)).any(axis=1).sum())
                     o[sa[tr]] = (o[sa[tr]] + ((F(2.0) * EPS) * dr[sa[tr]]).astype("<f4")).astype("<f4")   # ray.cpp:1345-1348
                     dr[sa], wo[sa] = wi, (-wi).astype("<f4")
                     b[sa] += 1
@@ -182,7 +195,8 @@ def chain(oracle, osc, flat, cam, w, h, seed, spp, rr, cap, rect=None):
 def expected(c, guards=None):
     """{plane: array} of chain c: the sums divided by float32(spp), hits, bounces, sample 0's material (ids[..., 1], the shape,
     is not the oracle's to say: NO_PRIM here, compared through ort_raycast on c.last), the final states.  Pixels outside the
-    rect hold the guards (zeros without)"""
+    rect hold the guards (zeros without).  Beside the planes, "void0" (h, w) bool: sample 0 ended on a void shape, whose ids are
+    {0, that shape} -- what assert_same needs to tell such a pixel from a miss"""
     out = {k: np.full((c.h, c.w) + SHAPES[k], guards[k] if guards else 0, DTYPES[k]) for k in PLANES}
     with np.errstate(all="ignore"):
         out["albedo"][c.ys, c.xs] = (c.A / F(c.spp)).astype("<f4")
@@ -193,27 +207,56 @@ def expected(c, guards=None):
     out["ids"][c.ys, c.xs, 0] = c.ids_mat
     out["ids"][c.ys, c.xs, 1] = NO_PRIM
     out["states"][c.ys, c.xs] = c.states
+    out["void0"] = np.zeros((c.h, c.w), bool)
+    out["void0"][c.ys, c.xs] = c.void0
     return out
 
 
-def assert_same(got, want, what):
+NAN_PLANES = ("albedo", "normal", "depth")
+
+
+def assert_same(got, want, what, nan=False):
     """every plane of got that want has, all bits; ids as feature_cases.assert_same: the material everywhere, the shape NO_PRIM
-    exactly where the material is 0 and nothing was hit (a shape that carries material 0 aside: no scene here has one)"""
+    exactly where the material is 0 and nothing was hit.  Where sample 0 ended on a void shape (want["void0"]) the material is 0
+    and the shape is NOT NO_PRIM: it is the void shape's, which assert_prims compares through the closest-hit query.
+    nan: albedo, normal and depth may hold NaN sums; they go through hostile_materials.same_words (equal bits, or NaN in both)
+    -> the number of NaN words expected in those planes (0 without nan)"""
+    got = {k: v for k, v in got.items() if v is not None}
+    nans = 0
+    if nan:
+        for k in NAN_PLANES:
+            if k in got:
+                nans += same_words(got[k], want[k], "%s %s" % (what, k))
+        got = {k: v for k, v in got.items() if k not in NAN_PLANES}
+    void = want.get("void0")
+    if "ids" in got and void is not None and void.any():
+        ids = np.ascontiguousarray(got["ids"])
+        assert ids.shape == want["ids"].shape and ids.dtype == want["ids"].dtype, "%s ids: %s %s" % (what, ids.shape, ids.dtype)
+        bad = void & ((ids[..., 0] != 0) | (ids[..., 1] == NO_PRIM))
+        assert not bad.any(), "%s ids: %d void ends of sample 0 are not {0, a shape}; first at %s: %r" % (what, bad.sum(), tuple(np.argwhere(bad)[0]), ids[tuple(np.argwhere(bad)[0])])
+        ids = ids.copy()
+        ids[void, 1] = NO_PRIM   # held above; every other pixel goes through the shared rule
+        got = dict(got, ids=ids)
     fc.assert_same({k: v for k, v in got.items() if k != "bounces"}, want, what)
     if got.get("bounces") is not None:
         ne = np.ascontiguousarray(got["bounces"]) != want["bounces"]
         assert got["bounces"].dtype == np.dtype("<u4") and not ne.any(), "%s bounces: %d words differ, first at %s" % (what, ne.sum(), tuple(np.argwhere(ne)[0]) if ne.any() else ())
+    return nans
 
 
 def assert_prims(got_ids, chains, prims, what):
     """got_ids (V, h, w, 2) against the shapes a raycast of the chains' last rays names (prims, concatenated in the chains' order):
-    a sample 0 the roulette ended has NO_PRIM, every other one the record's shape"""
+    a sample 0 the roulette ended has NO_PRIM, every other one the record's shape -- the void shape's where it ended on one
+    (material 0 with a shape), NO_PRIM where the last ray missed everything"""
     at = 0
     for v, c in enumerate(chains):
-        p = prims[at:at + len(c.xs)]
+        p = np.asarray(prims[at:at + len(c.xs)], "<u4")
         at += len(c.xs)
+        assert (p[c.void0] != NO_PRIM).all(), "%s view %d: the closest-hit query names no shape for a void end" % (what, v)
+        assert (got_ids[v][c.ys, c.xs, 0][c.void0] == 0).all(), "%s view %d: ids.mat of a void end" % (what, v)
         want = np.where(c.died0, NO_PRIM, p).astype("<u4")
-        assert (got_ids[v][c.ys, c.xs, 1] == want).all(), "%s view %d: ids.prim" % (what, v)
+        ne = got_ids[v][c.ys, c.xs, 1] != want
+        assert not ne.any(), "%s view %d: ids.prim, %d differ (%d of them void ends)" % (what, v, ne.sum(), (ne & c.void0).sum())
 
 
 # ---- the conditions the inputs are held to ---------------------------------------------------------------------------------------
@@ -272,6 +315,25 @@ def world(api, oracle, load_scene, tmp_path_factory, name):
     return w
 
 
+class CaseWorld:
+    """what world() gives, of a case of hostile_materials, void_material or hostile_shapes: scene, scn + base, size, flat, osc (the
+    case's oracle scene), own (the case's camera: the single frame, on SEED), fcams and fseeds (the batch), oracle, cache"""
+
+
+def case_world(c, cams, seeds, size=(W, H)):
+    """the world of case c with the batch (cams (V, 4, 3), seeds); kept on the case, so chains are computed once a session"""
+    key = (np.ascontiguousarray(cams, "<f4").tobytes(), tuple(int(s) for s in seeds), tuple(size))
+    worlds = c.__dict__.setdefault("_follow_worlds", {})
+    if key not in worlds:
+        w = CaseWorld()
+        w.name, w.scene, w.size, w.flat, w.oracle, w.cache = c.name, c.scene, tuple(size), c.flat, c.oracle, {}
+        w.scn, w.base = getattr(c, "scn", None), getattr(c, "base", None)
+        w.osc, w.own = c.twin(None), np.asarray(c.cam, "<f4").reshape(4, 3)
+        w.fcams, w.fseeds = np.ascontiguousarray(cams, "<f4"), [int(s) for s in seeds]
+        worlds[key] = w
+    return worlds[key]
+
+
 def chains(w, spp, rr, cap, rect=None):
     """[the single frame (the scene's own camera, SEED), the batch's three] at (spp, rr, cap), cached on the world"""
     key = ("chains", spp, float(rr), cap, rect)
@@ -282,11 +344,43 @@ def chains(w, spp, rr, cap, rect=None):
 
 
 def expected_set(w, spp, rr, cap, rect=None, guards=None):
-    """-> (the single frame's planes, the batch's planes stacked (3, h, w, ...), the four chains)"""
+    """-> (the single frame's planes, the batch's planes stacked (V, h, w, ...), the 1 + V chains)"""
     ch = chains(w, spp, rr, cap, rect)
     one = expected(ch[0], guards)
     per = [expected(c, guards) for c in ch[1:]]
-    return one, {k: np.stack([p[k] for p in per]) for k in PLANES}, ch
+    return one, {k: np.stack([p[k] for p in per]) for k in PLANES + ("void0",)}, ch
+
+
+def pin_on_twin(oracle, w, spp, rr, csg=True):
+    """reference 1 pins reference 2 on world w: while nothing reaches the cap, the chains' final states are, on every pixel of the
+    single frame and of the batch, the states of the oracle's own PIXEL jobs on the diffuse twin.  The reference itself cannot
+    render a followed plane; this is what ties the helper to it on the scene at hand"""
+    key = ("pinned", spp, float(rr))
+    if key in w.cache:
+        return
+    tw = twin(oracle, w.flat, csg)
+    for v, c in enumerate(chains(w, spp, rr, 64)):
+        assert c.at_cap == 0, (w.name, v, c.at_cap)
+        ne = twin_states(tw, c.cam, c.w, c.h, c.seed, spp, rr) != expected(c)["states"]
+        assert not ne.any(), "%s frame %d spp %d rr %g: %d states differ from the diffuse twin's, first at %s" % (w.name, v, spp, rr, ne.sum(), tuple(np.argwhere(ne)[0]))
+    w.cache[key] = True
+
+
+def assert_renders(render, raycast, w, spp, settings, what, nan=False):
+    """the single frame and the batch of world w at every (rr, cap) of settings against reference 2, all planes, and ids[..., 1]
+    against the closest-hit query on the chains' last rays.  render(batch, rr, cap) -> {plane: (V, h, w, ...)} (the single frame
+    as a batch of one), raycast(rays (n, 6)) -> prims (n,): the implementation under test, on host threads or on the device
+    -> the NaN words expected in albedo, normal and depth over all of it"""
+    nans = 0
+    for rr, cap in settings:
+        one, batch, ch = expected_set(w, spp, rr, cap)
+        got, gotb = render(False, rr, cap), render(True, rr, cap)
+        nans += assert_same({k: v[0] for k, v in got.items()}, one, "%s single rr %g cap %d" % (what, rr, cap), nan)
+        nans += assert_same(gotb, batch, "%s batch rr %g cap %d" % (what, rr, cap), nan)
+        if "ids" in got:
+            prims = raycast(np.ascontiguousarray(np.concatenate([c.last for c in ch]), "<f4"))
+            assert_prims(np.concatenate([got["ids"], gotb["ids"]]), ch, prims, "%s rr %g cap %d" % (what, rr, cap))
+    return nans
 
 
 def guard_planes(shape, want=PLANES):

@@ -239,6 +239,82 @@ def view_cameras(api, c):
     return np.stack([c.cam, lg.batch_cameras(api, c)[1], UP_CAM])
 
 
+# ---- the renders that follow mirrors and glass (follow_cases.py) ---------------------------------------------------------------------
+# a view for them: from the middle of the room along -y, wide enough that the left edge of the frame is the wall at x = -3 (nan)
+# and the right edge the wall at x = 15 (zero), the two materials with no lobe at all that a sample is followed through.  UP_CAM
+# follows nothing (it faces neg and inf, which are recorded): it stays, as the view whose albedo sums are infinite and negative
+WALL_CAM = np.array([[6.0, 10.0, 3.0], [1.5, 0.0, 0.0], [0.0, 0.0, -0.6], [0.0, 1.0, 0.0]], "<f4")
+FOLLOW_SETTINGS = ((0.5, 64), (0.8, 2))   # (rr, cap): nothing reaches the cap; the cap records specular-only surfaces
+SPECULAR_ONLY = ("nan", "zero", "tiny")   # in both scenes; `hostile` adds the Kd = 0 spheres
+SPECULAR_SPHERES = ("ior0", "iorhalf", "ktinf")
+
+
+def follow_world(c):
+    """follow_cases' world of a case: the single frame from the scene's own camera on SEED; the batch is that camera, WALL_CAM and
+    UP_CAM on VIEW_SEEDS"""
+    import follow_cases as fw
+    return fw.case_world(c, np.stack([c.cam, WALL_CAM, UP_CAM]), VIEW_SEEDS)
+
+
+def follow_conditions(c):
+    """what the follow frames of a case must exercise, from the oracle's side (follow_cases.chain), printed and asserted: on the
+    scene's own camera at rr 0.5, cap 64 at least a tenth of the samples are followed, through each of nan, zero (WALL_CAM's frame:
+    the own camera has that wall behind it) and tiny and, on `hostile`, through at least two of the three Kd = 0 spheres; at least
+    50 roulette deaths and 50 refractions (hostile_diffuse, which has no transmission: 50 draws that sample_brdf answers with its
+    transmission flag all the same); nothing at the cap.  At rr 0.8, cap 2 at least 5 samples are recorded at the cap on a
+    specular-only surface and the own frame's albedo plane expects a NaN word -- the nan wall's Kd, recorded -- on `hostile`,
+    whose spheres send paths that deep.  UP_CAM's frame holds infinite albedo sums.  -> the bounce rays with a non-finite direction, over all
+    frames and both settings"""
+    import follow_cases as fw
+    w = follow_world(c)
+    open_, capped = fw.chains(w, FEATURE_SPP, *FOLLOW_SETTINGS[0]), fw.chains(w, FEATURE_SPP, *FOLLOW_SETTINGS[1])
+    o, k = open_[0], capped[0]
+    by = lambda ch, n: int(ch.followed_by_mat[INDEX[n]])
+    nan_words = int(np.isnan(fw.expected(k)["albedo"]).sum())   # the scene's own frame, the albedo plane alone
+    nonfinite = sum(ch.nonfinite_dirs for ch in open_ + capped)
+    print("%s rr 0.5 cap 64: followed %.3f of the samples (%s; WALL_CAM %.3f: %s), %d roulette deaths, %d refractions, deepest b %d, %d at the cap; "
+          "rr 0.8 cap 2: %d recorded at the cap on a specular-only surface, %d NaN words expected in albedo; %d bounce rays with a non-finite direction"
+          % (c.name, o.followed / o.samples, {n: by(o, n) for n in SPECULAR_ONLY + SPECULAR_SPHERES}, open_[2].followed / open_[2].samples,
+             {n: by(open_[2], n) for n in SPECULAR_ONLY}, o.deaths, o.refractions, o.max_b, o.at_cap, k.capped_specular, nan_words, nonfinite))
+    assert o.followed >= 0.10 * o.samples and o.deaths >= 50 and o.refractions >= 50
+    assert all(ch.at_cap == 0 for ch in open_)
+    assert by(o, "nan") > 0 and by(o, "tiny") > 0 and by(open_[2], "zero") > 0 and by(open_[2], "nan") > 0
+    assert open_[3].followed == 0 and np.isinf(fw.expected(open_[3])["albedo"]).any()
+    if c.name == "hostile":
+        assert sum(by(o, n) > 0 for n in SPECULAR_SPHERES) >= 2
+        assert k.capped_specular >= 5 and nan_words >= 1
+    return nonfinite
+
+
+# ---- the accumulating renders (accumulate_cases.py) -----------------------------------------------------------------------------------
+# 64 samples, the whole of a reference chain: accumulate_cases.REF_SPLIT, and a split with a boundary on either side of sample 27
+# (index 26), where pixel (14, 11) of `hostile` overflows its Q: one pass ends just before it, a pass of one sample takes it
+OVERFLOW_SPLIT = (26, 1, 37)
+
+
+def accumulate_splits():
+    import accumulate_cases as acs
+    return (acs.REF_SPLIT, OVERFLOW_SPLIT)
+
+
+def accumulate_expected(chain, name):
+    """the folds of the reference's chains under both splits, by accumulate_cases.model alone, and what they must hold: infinite m2
+    words at the end (6 pixels of `hostile`, 8 of hostile_diffuse), and on `hostile` under OVERFLOW_SPLIT none after the first
+    pass and one after the pass of one sample -- the continued job reloads a finite Q and leaves an infinite one, and the next
+    reloads that.  The reference's chains hold no NaN word (its bounce guard drops every non-finite emission), so neither do the
+    sums: the NaN-aware compare is there for the device's sake, not because a NaN is expected"""
+    import accumulate_cases as acs
+    for split in accumulate_splits():
+        want, infs = acs.Planes(), []
+        for k in split:
+            acs.model(want, 0, chain, None, k, None)
+            infs.append(int(np.isinf(want.m2).sum()))
+        print("%s %r: infinite m2 words after each pass %r, NaN words %d" % (name, split, infs, sum(int(np.isnan(a).sum()) for a in (want.sum, want.m2, want.rgb))))
+        assert infs[-1] >= 3 and np.isfinite(want.sum).all()
+        if name == "hostile" and split == OVERFLOW_SPLIT:
+            assert infs[:2] == [0, 1]
+
+
 def ray_cases(c):
     """radiance_cases.mixed on the scene -- 64 rays, 8 of them outside the domain -- and 16 pinholes inside the room that look at
     the sphere under the light (`big`, Kd 1e30; part B: the inf light), whose bounces carry the huge, negative and non-finite terms"""

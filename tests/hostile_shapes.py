@@ -99,8 +99,18 @@ def _brdf(i, lobes=False):
     return "brdf %.6f %.6f %.6f %.6f %.6f %.6f 10 0.000000 0.000000 0.000000 1.0" % (kd + ks)
 
 
-def hostile_block(lobes=True):
-    return "".join("%s\n%s\n" % (_brdf(i, lobes), line) for i, (_, _, line) in enumerate(HOSTILE))
+# for the follow renders: the hostile shapes that rays do meet (HIT), turned into mirrors and glass -- Kd = 0, so a sample is
+# followed THROUGH them and its bounce ray starts on a sphere of radius -0.5, an inverted or flat box, a cylinder of radius -0.25
+# or 0, a mesh scaled by -0.6 or turned by a zero quaternion.  Every shape keeps a `brdf` line of its own: MAT stands
+MIRROR = "brdf 0.000000 0.000000 0.000000 1.000000 1.000000 1.000000 20 0.000000 0.000000 0.000000 1.0"
+GLASS = "brdf 0.000000 0.000000 0.000000 0.000000 0.000000 0.000000 10 1.000000 1.000000 1.000000 1.4"
+FOLLOW_SPECULAR = {"sphere_neg": GLASS, "box_inv1": MIRROR, "box_inv3": GLASS, "box_flat": MIRROR, "cyl_neg": MIRROR, "cyl_zero": GLASS,
+                   "mesh_neg": MIRROR, "mesh_q0": GLASS}
+assert set(FOLLOW_SPECULAR) == set(HIT)
+
+
+def hostile_block(lobes=True, specular=False):
+    return "".join("%s\n%s\n" % (FOLLOW_SPECULAR[n] if specular and n in FOLLOW_SPECULAR else _brdf(i, lobes), line) for i, (n, _, line) in enumerate(HOSTILE))
 
 
 # ---- shapes_lights ---------------------------------------------------------------------------------------------------------------
@@ -159,26 +169,31 @@ SCENES = ("shapes_seen", "shapes_lights") + FAR_SCENES + ("shapes_leaves",)
 NO_NONFINITE = ("shapes_seen", "shapes_leaves") + FAR_SCENES   # no reference frame of these holds a non-finite word
 
 
-def text(name, plain=False):
-    """the text of a scene of SCENES; plain: without its hostile shapes"""
+def text(name, plain=False, specular=False):
+    """the text of a scene of SCENES; plain: without its hostile shapes; specular (shapes_seen, shapes_leaves): FOLLOW_SPECULAR's
+    shapes as mirrors and glass"""
     if name == "shapes_seen":
-        return HEAD + ROOM + ("" if plain else hostile_block()) + lg.THREE_LIGHTS
+        return HEAD + ROOM + ("" if plain else hostile_block(specular=specular)) + lg.THREE_LIGHTS
     if name == "shapes_lights":
         return HEAD + ROOM + lg.SPHERES["diffuse"] + ("" if plain else HOSTILE_LIGHTS) + PLAIN_LIGHT
     if name in FAR_SCENES:
         far = "" if plain else _brdf(5) + "\n" + FAR[name[len("shapes_far_"):]] + "\n"
         return HEAD + ROOM + lg.SPHERES["all_lobes"] + far + lg.THREE_LIGHTS
     if name == "shapes_leaves":
-        return HEAD + ROOM + ("" if plain else hostile_block(lobes=False)) + _leaves_fill() + lg.THREE_LIGHTS
+        return HEAD + ROOM + ("" if plain else hostile_block(lobes=False, specular=specular)) + _leaves_fill() + lg.THREE_LIGHTS
     raise KeyError(name)
 
 
 DARK = tuple("%s_dark%d" % (n, g) for n in N_LIGHTS for g in range(N_LIGHTS[n]))
 PLAIN = tuple(n + "_plain" for n in SCENES)
 STEMS = SCENES + PLAIN + DARK
+# written at test time for the follow renders alone; the reference has no frame of them (every follow reference is the oracle's)
+SPECULAR = ("shapes_seen_specular", "shapes_leaves_specular")
 
 
 def scene_text(stem):
+    if stem in SPECULAR:
+        return text(stem[:-len("_specular")], specular=True)
     if stem in SCENES:
         return text(stem)
     if stem in PLAIN:
@@ -393,6 +408,50 @@ def view_cameras(api, c):
     s = c.flat.spheres[c.flat.spheres["r"] == np.float32(-0.5)]
     cam[0] = s[0]["center"] if len(s) else cam[0] * np.float32(0.8)
     return np.stack([c.cam, lg.batch_cameras(api, c)[1], cam])
+
+
+# ---- the renders that follow mirrors and glass (follow_cases.py) ---------------------------------------------------------------------
+# shapes_seen and shapes_leaves, the scenes of the feature tests, give every hostile shape a material with a diffuse part: no sample
+# is followed there (the oracle's count is 0 from every view), so the follow render must BE the first-hit render on them
+# (identity 2 of include/ort.h).  Their SPECULAR twins, written at test time, make the hostile shapes that rays meet mirrors and
+# glass: there the bounce rays START ON hostile shapes -- in the prologue (shapes_seen_specular) and in leaves
+# (shapes_leaves_specular).  The far scenes keep the room's glass and mirror spheres next to one shape of size 1e6 to 1e12
+FOLLOW_SCENES = ("shapes_seen", "shapes_leaves") + SPECULAR + FAR_SCENES
+FOLLOWING = SPECULAR + FAR_SCENES
+FOLLOW_SETTINGS = hm.FOLLOW_SETTINGS
+
+
+def follow_world(api, c):
+    """follow_cases' world of a case: the single frame from the scene's own camera on SEED, the batch view_cameras on VIEW_SEEDS"""
+    import follow_cases as fw
+    return fw.case_world(c, view_cameras(api, c), VIEW_SEEDS)
+
+
+def follow_conditions(api, c):
+    """printed and asserted from the oracle's side (follow_cases.chain; the scene's own frame at rr 0.5, cap 64).  A scene without
+    a specular-only material follows nothing from any view (-> False: the caller asserts identity 2).  Otherwise at least 5 % of
+    the samples are followed, some path bounces twice, at least 10 die at the roulette and none reaches the cap (-> True); on the
+    SPECULAR twins samples are followed through a hostile sphere, a hostile box, a hostile cylinder and a hostile mesh, and at
+    rr 0.8, cap 2 at least 5 samples are recorded at the cap on a specular-only surface"""
+    import follow_cases as fw
+    w = follow_world(api, c)
+    ch = fw.chains(w, FEATURE_SPP, *FOLLOW_SETTINGS[0])
+    spec = fw.specular_only(c.flat)
+    through = {n: int(ch[0].followed_by_mat[MAT[n]]) for n in NAMES if MAT[n] < len(ch[0].followed_by_mat) and ch[0].followed_by_mat[MAT[n]]}
+    print("%s: specular-only materials %s; followed share per frame %s, deaths %s, deepest b %s; the own frame's samples followed through hostile shapes: %s"
+          % (c.name, np.flatnonzero(spec).tolist(), ["%.3f" % (k.followed / k.samples) for k in ch], [k.deaths for k in ch], [k.max_b for k in ch],
+             through if c.name in SPECULAR else "-"))
+    assert all(k.at_cap == 0 for k in ch)
+    if not spec.any():
+        assert all(k.followed == 0 and k.rays == k.samples for k in ch)
+        return False
+    assert ch[0].followed >= 0.05 * ch[0].samples and ch[0].deaths >= 10 and ch[0].max_b >= 2
+    if c.name in SPECULAR:
+        assert sorted(np.flatnonzero(spec).tolist()) == sorted(MAT[n] for n in FOLLOW_SPECULAR)
+        for kind in KINDS_OF_SHAPE:
+            assert any(KIND[n] == kind for n in through), (kind, through)
+        assert fw.chains(w, FEATURE_SPP, *FOLLOW_SETTINGS[1])[0].capped_specular >= 5
+    return True
 
 
 # what the CPU and the GPU tests share, computed once and left unchanged: void_material's helpers, which key on the case's name

@@ -13,7 +13,9 @@ unless said otherwise."""
 import numpy as np
 import pytest
 
+import accumulate_cases as acs
 import adaptive_cases as ac
+import follow_cases as fw
 import hostile_materials as hm
 import irradiance_cases as ic
 import light_groups_cases as lg
@@ -21,6 +23,7 @@ import radiance_cases as rc
 import reference_goldens as rg
 import render_adaptive_cases as rac
 import sample_map_cases as sm
+from test_follow_gpu import device_call as follow_device, host_call as follow_host
 from test_gpu_adaptive import torch_run as adaptive_radiance_device
 from test_gpu_features import device_call as features_device
 from test_gpu_irradiance import torch_irradiance
@@ -233,6 +236,85 @@ def test_render_features(api, case, knobs, name):
         hm.assert_features({k: a[v] for k, a in dev.items()}, want[v], "%s features, view %d, the device form" % (name, v))
     dev, _ = features_device(api, w, hm.FEATURE_SPP, False)
     hm.assert_features({k: a[0] for k, a in dev.items()}, want[0], name + " features, the device form")
+
+
+# ---- the accumulating renders, on the reference's chains ------------------------------------------------------------------------------
+ACCUMULATE_KNOBS = ("default", "hbm_tables", "general", "fallback", "counters")
+
+
+@pytest.mark.parametrize("name,which", [(n, k) for n in hm.SCENES for k in ACCUMULATE_KNOBS if n in KNOB_SETS[k][2]])
+def test_render_accumulate(api, case, knobs, chain_file, name, which):
+    """ort_render_accumulate: 64 samples as 1 + 3 + 12 + 48 and as 26 + 1 + 37 -- a pass ends just before, and a pass of one sample
+    takes, the sample at which a pixel of `hostile` overflows its Q -- against the fold of the REFERENCE's chains with no oracle
+    in between, every plane after every pass.  A continued job reloads sum, m2, count and state from memory: huge, negative and
+    infinite words here.  Under the default plan also accumulate_cases.identity_2_per_pixel against the oracle's chains"""
+    env, counters, _ = KNOB_SETS[which]
+    c = case(name)
+    chain = hm.chains_from(chain_file, name)
+    hm.accumulate_expected(chain, name)
+    knobs(env)
+    call = acs.library_call(api, c, counters=counters)
+    for split in hm.accumulate_splits():
+        acs.reference_split(call, chain, "%s accumulate %r, %s" % (name, split, which), split, nan=True)
+    if which == "default":
+        acs.identity_2_per_pixel(call, c, name + " accumulate, per-pixel calls", chain=hm.chains_of(c), nan=True)
+
+
+@pytest.mark.parametrize("name", hm.SCENES)
+def test_render_accumulate_device_forms_and_views(api, case, knobs, chain_file, name):
+    """the 26 + 1 + 37 split through the _device forms on a non-default stream, guard words around every plane and no
+    synchronisation between the passes, against the fold of the reference's chains; and ort_render_views_accumulate on the
+    file's three views in passes of 1 + 3 against the oracle's chains from each camera, frame 0 the single-frame form's"""
+    knobs({})
+    c = case(name)
+    chain = hm.chains_from(chain_file, name)
+    want = acs.Planes()
+    for k in hm.OVERFLOW_SPLIT:
+        acs.model(want, 0, chain, None, k, None)
+    acs.assert_planes(acs.stream_split(c, hm.OVERFLOW_SPLIT), want, name + " accumulate, the device forms on a stream", nan=True)
+    call = acs.library_call(api, c)
+    single = acs.Planes()
+    for n in (1, 3):
+        call(single, None, n)
+    acs.views_split(call, c, hm.view_cameras(api, c), hm.VIEW_SEEDS, (1, 3), name + " accumulate, views", nan=True, single=single)
+
+
+FOLLOW_KNOBS = ("default", "hbm_tables", "general", "fallback", "counters")
+
+
+@pytest.mark.parametrize("name,which", [(n, k) for n in hm.SCENES for k in FOLLOW_KNOBS if n in KNOB_SETS[k][2]])
+def test_render_follow(api, case, knobs, name, which):
+    """ort_render_follow and ort_render_views_follow against follow_cases' chain, which tests/test_hostile_materials_host.py pins
+    against the oracle's diffuse twin on these very frames: the single frame and a batch of three views (the scene's own camera,
+    WALL_CAM at the nan and the zero wall, UP_CAM at neg and inf) at (spp 5, rr 0.5, cap 64) and (rr 0.8, cap 2), all seven planes,
+    ids' shapes through ort_raycast of the chains' last rays.  The terminal test meets NaN, 1e-30, all-zero, inf and negative Kd;
+    the followed ones draw sample_brdf without a lobe, their records come from LDS (default) or from HBM (hbm_tables), the burn
+    reads the lights' table in LDS, and `fallback` hands the bounce rays to the exact walk.  Under the default plan the device
+    forms too, on a non-default stream over guard words.  No bounce ray of these frames has a non-finite direction (the oracle's
+    count is 0): the NaN words are the nan wall's Kd recorded at the cap"""
+    env, counters, _ = KNOB_SETS[which]
+    c = case(name)
+    assert hm.follow_conditions(c) == 0
+    w = hm.follow_world(c)
+    knobs(env)
+    cast = lambda rays: c.scene.raycast(rays)[0]["prim"]
+    rays = {}
+
+    def host(batch, rr, cap):
+        got, st = follow_host(w, hm.FEATURE_SPP, batch, rr=rr, cap=cap, counters=counters)
+        rays[(batch, rr, cap)] = st["rays"]
+        return got
+    nans = fw.assert_renders(host, cast, w, hm.FEATURE_SPP, hm.FOLLOW_SETTINGS, "%s follow, %s" % (name, which), nan=True)
+    assert (nans > 0) == (name == "hostile")
+    if counters:
+        for rr, cap in hm.FOLLOW_SETTINGS:
+            ch = fw.chains(w, hm.FEATURE_SPP, rr, cap)
+            assert rays[(False, rr, cap)] == ch[0].rays and rays[(True, rr, cap)] == sum(k.rays for k in ch[1:])
+    if which == "fallback":
+        assert follow_host(w, hm.FEATURE_SPP, True, counters=True)[1]["fallback_rays"] > 0
+    if which == "default":
+        device = lambda batch, rr, cap: follow_device(api, w, hm.FEATURE_SPP, batch, rr=rr, cap=cap)[0]
+        fw.assert_renders(device, cast, w, hm.FEATURE_SPP, hm.FOLLOW_SETTINGS, "%s follow, the device forms" % name, nan=True)
 
 
 # ---- the ray and point queries -----------------------------------------------------------------------------------------------------------

@@ -12,9 +12,11 @@ hostile_materials.same_words compares: bit for bit, NaN matching NaN; no pixel, 
 import numpy as np
 import pytest
 
+import accumulate_cases as acs
 import adaptive_cases as ac
 import ao_cases as ao
 import feature_cases as fc
+import follow_cases as fw
 import hostile_materials as hm
 import hostile_shapes as hsh
 import irradiance_cases as ic
@@ -25,6 +27,7 @@ import reference_goldens as rg
 import render_adaptive_cases as rac
 import sample_map_cases as sm
 from raycast_cases import assert_same_answers
+from test_follow_gpu import device_call as follow_device, host_call as follow_host
 from test_gpu_adaptive import torch_run as adaptive_radiance_device
 from test_gpu_ao import torch_form as ao_device
 from test_gpu_features import device_call as features_device
@@ -77,8 +80,9 @@ def case(api, oracle, manifest, tmp_path_factory, monkeypatch):
             c = hsh.case(api, oracle, name, tmp_path_factory, commit)
             for k in hsh.PROLOGUE_WIDE:
                 monkeypatch.delenv(k, raising=False)
-            assert rg.sha256(c.scn) == manifest["generated"]["shapes"]["scenes"][name]["scn_sha256"], name
-            if name == "shapes_seen":   # 11 boxes and 2 spheres; every box and sphere and one cylinder
+            if name not in hsh.SPECULAR:   # those are written for the follow renders alone: the reference has no fixture of them
+                assert rg.sha256(c.scn) == manifest["generated"]["shapes"]["scenes"][name]["scn_sha256"], name
+            if name in ("shapes_seen", "shapes_seen_specular"):   # 11 boxes and 2 spheres; every box and sphere and one cylinder
                 assert c.scene.tree_info()["prologue_prims"] == (17 if commit else 13)
         uploaded(api, c.scene)
         return c
@@ -400,6 +404,75 @@ def test_render_features(api, oracle, case, knobs, name, which):
     assert fc.SEED == hsh.SEED
     dev, _ = features_device(api, w, hsh.FEATURE_SPP, False)
     hsh.assert_features({k: a[0] for k, a in dev.items()}, wants[0][0], wants[0][1], prims[0], name + " features, the device form")
+
+
+@pytest.mark.parametrize("which", ["default", "hbm_tables", "fallback", "counters"])
+@pytest.mark.parametrize("name", hsh.FOLLOW_SCENES + ("shapes_seen@prologue24", "shapes_seen_specular@prologue24") + hsh.ARRAYS)
+def test_render_follow(api, case, knobs, name, which):
+    """ort_render_follow and ort_render_views_follow against follow_cases' chain, which tests/test_hostile_shapes_host.py pins
+    against the oracle's diffuse twin on these frames: the single frame and the batch of hostile_shapes.view_cameras at (spp 5,
+    rr 0.5, cap 64) and (rr 0.8, cap 2), all seven planes, ids' shapes through ort_raycast of the chains' last rays; the device
+    forms under the default plan.  shapes_seen, shapes_leaves and the scene of arrays have no specular-only material: there the
+    six planes are ort_render_views_features' and bounces is zero (identity 2).  Their SPECULAR twins make the hostile shapes
+    that rays meet mirrors and glass, so the bounce rays start ON hostile shapes: 45 % of the own frame's samples are followed
+    where the hostile sphere and boxes sit in the prologue (shapes_seen_specular; committed with a wider prologue, a hostile
+    cylinder sits there too), 27 % where every hostile shape sits in a leaf (shapes_leaves_specular), paths 7 and 9 bounces deep
+    (tests/test_hostile_shapes_host.py asserts the placement).  The far scenes follow 12 %"""
+    env, counters = VARIANTS[which]
+    name, _, commit = name.partition("@")
+    c = case(name, "@" + commit if commit else "")
+    follows = hsh.follow_conditions(api, c)
+    assert follows == (name in hsh.FOLLOWING)
+    w = hsh.follow_world(api, c)
+    knobs(env)
+    cast = lambda rays: c.scene.raycast(rays)[0]["prim"]
+    last = {}
+
+    def host(batch, rr, cap):
+        last[batch], last["stats"] = follow_host(w, hsh.FEATURE_SPP, batch, rr=rr, cap=cap, counters=counters)
+        return last[batch]
+    fw.assert_renders(host, cast, w, hsh.FEATURE_SPP, hsh.FOLLOW_SETTINGS, "%s follow, %s" % (name, which))
+    if counters:
+        assert last["stats"]["rays"] == sum(k.rays for k in fw.chains(w, hsh.FEATURE_SPP, *hsh.FOLLOW_SETTINGS[-1])[1:])
+    if not follows:
+        first, _ = c.scene.render_views_features(w.fcams, w.fseeds, W, H, hsh.FEATURE_SPP, want=fc.PLANES)
+        for k in fc.PLANES:
+            same(last[True][k], first[k], "%s, %s: %s against ort_render_views_features" % (name, which, k))
+        assert not last[True]["bounces"].any()
+    if which == "default":
+        device = lambda batch, rr, cap: follow_device(api, w, hsh.FEATURE_SPP, batch, rr=rr, cap=cap)[0]
+        fw.assert_renders(device, cast, w, hsh.FEATURE_SPP, hsh.FOLLOW_SETTINGS, "%s follow, the device forms" % name)
+
+
+# ---- the accumulating renders -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", PLANS + ["counters"])
+@pytest.mark.parametrize("name", hsh.CHAINS + hsh.ARRAYS)
+def test_render_accumulate(api, case, knobs, chain_file, name, which):
+    """ort_render_accumulate: 64 samples as 1 + 3 + 12 + 48 against the fold of the REFERENCE's chains (the oracle's for the scene
+    of arrays), every plane after every pass: a continued job reloads its sums and its state and walks on among the hostile shapes"""
+    knobs(VARIANTS[which][0])
+    c = case(name)
+    chain = hsh.chains_from(chain_file, name) if name in hsh.CHAINS else hsh.chains_of(c)
+    acs.reference_split(acs.library_call(api, c, counters=VARIANTS[which][1]), chain, "%s accumulate, %s" % (name, which), nan=name not in hsh.NO_NONFINITE)
+
+
+@pytest.mark.parametrize("name", hsh.CHAINS)
+def test_render_accumulate_device_forms_and_views(api, case, knobs, chain_file, name):
+    """the 1 + 3 + 12 + 48 split through the _device forms on a non-default stream, guard words around every plane and no
+    synchronisation between the passes, against the fold of the reference's chains; ort_render_views_accumulate on
+    hostile_shapes.view_cameras in passes of 1 + 3 against the oracle's chains from each camera, frame 0 the single-frame form's"""
+    knobs({})
+    c = case(name)
+    chain, nan = hsh.chains_from(chain_file, name), name not in hsh.NO_NONFINITE
+    want = acs.Planes()
+    for k in acs.REF_SPLIT:
+        acs.model(want, 0, chain, None, k, None)
+    acs.assert_planes(acs.stream_split(c, acs.REF_SPLIT), want, name + " accumulate, the device forms on a stream", nan=nan)
+    call = acs.library_call(api, c)
+    single = acs.Planes()
+    for n in (1, 3):
+        call(single, None, n)
+    acs.views_split(call, c, hsh.view_cameras(api, c), hsh.VIEW_SEEDS, (1, 3), name + " accumulate, views", nan=nan, single=single)
 
 
 @pytest.mark.parametrize("which", PLANS)

@@ -8,9 +8,11 @@ cluster scene against the reference's own pixels and hits (tests/golden/*_cluste
 import numpy as np
 import pytest
 
+import accumulate_cases as acs
 import ao_cases
 import adaptive_cases
 import feature_cases
+import follow_cases as fw
 import light_groups_cases as lg
 import occluded_cases
 import radiance_cases
@@ -165,10 +167,11 @@ def test_ray_queries(handle, knobs, name, variant, tables):
 
 @pytest.mark.parametrize("tables", ["lds", "hbm"])
 @pairs
-def test_camera_queries(handle, knobs, name, variant, tables):
-    """ort_render_features, ort_render_views, ort_render_adaptive, ort_render_light_groups (one group per light material, against
-    the dark twins of the world's flattened scene) and ort_render_sample_map (the mixed map) on the small frames, with the tables
-    in LDS and in HBM"""
+def test_camera_queries(api, handle, knobs, name, variant, tables):
+    """ort_render_features, ort_render_follow (against follow_cases' chain; under no_prologue the counters build's node tests
+    exceed the default tree's for the same rays), ort_render_views, ort_render_adaptive, ort_render_light_groups (one group per
+    light material, against the dark twins of the world's flattened scene), ort_render_sample_map (the mixed map) and
+    ort_render_accumulate (that map in two passes) on the small frames, with the tables in LDS and in HBM"""
     w, scene = handle(name, variant)
     knobs({} if tables == "lds" else {"ORT_LDS_TABLES": "0"})
     what = "%s %s tables in %s" % (name, variant, tables)
@@ -176,6 +179,21 @@ def test_camera_queries(handle, knobs, name, variant, tables):
     planes, _ = scene.render_features(width, height, spp, ts.SEED, want=feature_cases.PLANES)
     feature_cases.assert_same(planes, ts.features_expected(w), what + " features")
     same_as_first(name, variant, "features", *[planes[k] for k in ("albedo", "normal", "depth", "hits", "states")])
+    # follow: the bounce rays start on a surface, so they are the fast walk's own and walk the variant's tree (glass_room's
+    # default tree is one leaf: there they walk one only under the variants without, or with a small, prologue)
+    ts.assert_follow_conditions(w)
+    c = ts.follow_chain(w)
+    followed, st = scene.render_follow(width, height, spp, ts.SEED, ts.FOLLOW[1], ts.FOLLOW[0], want=fw.PLANES, counters=True)
+    fw.assert_same(followed, ts.follow_expected(w), what + " follow")
+    fw.assert_prims(followed["ids"][None], [c], scene.raycast(c.last)[0]["prim"], what + " follow")
+    assert st["rays"] == c.rays and st["paths"] == 0
+    same_as_first(name, variant, "follow", *[followed[k] for k in fw.PLANES if k != "ids"])
+    plain, _ = scene.render_follow(width, height, spp, ts.SEED, ts.FOLLOW[1], ts.FOLLOW[0], want=fw.PLANES)
+    for k in fw.PLANES:
+        assert np.ascontiguousarray(plain[k]).tobytes() == np.ascontiguousarray(followed[k]).tobytes(), "%s follow: %s with and without counters" % (what, k)
+    if variant == "no_prologue":
+        _, default = handle(name, "default")[1].render_follow(width, height, spp, ts.SEED, ts.FOLLOW[1], ts.FOLLOW[0], want=("hits",), counters=True)
+        assert default["rays"] == st["rays"] and st["node_tests"] > default["node_tests"], (st["node_tests"], default["node_tests"])
     width, height, spp, chunk = ts.VIEWS
     cams = ts.view_cams(w)
     for policy, ch in (("chunk", chunk), ("pixel", 0)):
@@ -198,3 +216,23 @@ def test_camera_queries(handle, knobs, name, variant, tables):
     got = scene.render_sample_map(width, height, smap, ts.MAP_CAP, ts.SEED, True, True, rr=sm.RR, out=sm.guards())[:3]
     sm.assert_planes(got, want, what + " sample map")
     same_as_first(name, variant, "sample map", *got)
+    acc = ts.accumulate_passes(w, acs.library_call(api, ts.AccumulateCase(w, scene), counters=False), what)   # two passes, caps 1 and 3, against the chains folded
+    same_as_first(name, variant, "accumulate", acc.sum, acc.m2, acc.count, acc.states)
+
+
+@pairs
+def test_accumulate_device_forms_and_views(api, handle, knobs, name, variant):
+    """passes of 1 + 3 samples through the _device forms on a non-default stream, guard words around every plane and no
+    synchronisation between them, against the oracle's chains folded; and ort_render_views_accumulate on the two views of
+    tree_shapes.view_cams in the same passes against the oracle's chains from each camera"""
+    w, scene = handle(name, variant)
+    knobs({})
+    c = ts.AccumulateCase(w, scene)
+    what = "%s %s accumulate" % (name, variant)
+    want = acs.Planes()
+    for n in ts.ACCUMULATE_CAPS:
+        acs.model(want, 0, ts.pixel_chains(w), None, n, None)
+    got = acs.stream_split(c, ts.ACCUMULATE_CAPS, seed=ts.SEED)
+    acs.assert_planes(got, want, what + ", the device forms on a stream")
+    views = acs.views_split(acs.library_call(api, c), c, ts.view_cams(w), ts.VIEW_SEEDS, ts.ACCUMULATE_CAPS, what + ", views")
+    same_as_first(name, variant, "accumulate on a stream and views", got.sum, got.m2, got.count, got.states, views.sum, views.m2, views.count, views.states)

@@ -12,9 +12,11 @@ pixel, ray or point is skipped.  Frames are 24 x 16 at 16 spp unless said otherw
 import numpy as np
 import pytest
 
+import accumulate_cases as acs
 import adaptive_cases as ac
 import ao_cases as ao
 import feature_cases as fc
+import follow_cases as fw
 import hostile_materials as hm
 import irradiance_cases as ic
 import light_groups_cases as lg
@@ -25,6 +27,7 @@ import render_adaptive_cases as rac
 import sample_map_cases as sm
 import void_material as vm
 from raycast_cases import FLT_MAX, assert_same_answers
+from test_follow_gpu import device_call as follow_device, host_call as follow_host
 from test_gpu_adaptive import torch_run as adaptive_radiance_device
 from test_gpu_ao import torch_form as ao_device
 from test_gpu_features import device_call as features_device
@@ -498,6 +501,81 @@ def test_render_features(api, oracle, case, knobs, name):
     assert fc.SEED == vm.SEED
     dev, _ = features_device(api, w, vm.FEATURE_SPP, False)
     vm.assert_features({k: a[0] for k, a in dev.items()}, wants[0][0], wants[0][1], prims[0], name + " features, the device form")
+
+
+@pytest.mark.parametrize("which", ["default", "hbm_tables", "fallback", "counters"])
+@pytest.mark.parametrize("name", vm.SCENES + ("all_void",))
+def test_render_follow(api, case, knobs, name, which):
+    """ort_render_follow and ort_render_views_follow against follow_cases' chain, which tests/test_void_material_host.py pins
+    against the oracle's diffuse twin on these very frames: the single frame and a batch of four views (one inside a void sphere,
+    GLASS_CAM looking at void shapes through the glass sphere) at (spp 5, rr 0.5, cap 64) and (rr 0.8, cap 2), all seven planes.
+    A camera ray or a bounce ray that ends on a void shape records nothing; as sample 0 it leaves ids {0, that shape} -- the shape
+    ort_raycast names for the chain's last ray -- and NO_PRIM stays for a miss and for a sample 0 the roulette ended.  Under the
+    default plan the device forms too.  all_void: every plane +0, hits 0, and the final states are ort_render_views_features'"""
+    env, counters = VARIANTS[which]
+    c = case(name)
+    vm.follow_conditions(api, c)
+    w = vm.follow_world(api, c)
+    knobs(env)
+    cast = lambda rays: c.scene.raycast(rays)[0]["prim"]
+    last = {}
+
+    def host(batch, rr, cap):
+        last[batch], last["stats"] = follow_host(w, vm.FEATURE_SPP, batch, rr=rr, cap=cap, counters=counters)
+        return last[batch]
+    assert fw.assert_renders(host, cast, w, vm.FEATURE_SPP, vm.FOLLOW_SETTINGS, "%s follow, %s" % (name, which)) == 0
+    if counters:
+        assert last["stats"]["rays"] == sum(k.rays for k in fw.chains(w, vm.FEATURE_SPP, *vm.FOLLOW_SETTINGS[-1])[1:])
+    if which == "fallback" and name != "all_void":
+        assert follow_host(w, vm.FEATURE_SPP, True, counters=True)[1]["fallback_rays"] > 0
+    if which == "default":
+        device = lambda batch, rr, cap: follow_device(api, w, vm.FEATURE_SPP, batch, rr=rr, cap=cap)[0]
+        fw.assert_renders(device, cast, w, vm.FEATURE_SPP, vm.FOLLOW_SETTINGS, "%s follow, the device forms" % name)
+    if name == "all_void":
+        got = last[True]
+        for k in ("albedo", "normal", "depth", "hits", "bounces"):
+            assert not np.ascontiguousarray(got[k]).view("<u4").any(), k
+        assert not got["ids"][..., 0].any() and (got["ids"][..., 1] != fc.NO_PRIM).any()
+        first, _ = c.scene.render_views_features(w.fcams, w.fseeds, W, H, vm.FEATURE_SPP, want=("hits", "states"))
+        rg.assert_words_equal(got["states"], first["states"], "all_void: the final states are the first-hit render's")
+
+
+# ---- the accumulating renders -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", ["default", "hbm_tables", "fallback", "counters"])
+def test_render_accumulate(api, case, knobs, chain_file, which):
+    """ort_render_accumulate.  void_hidden: 64 samples as 1 + 3 + 12 + 48 against the fold of the REFERENCE's chains
+    (chains_void.npz: paths that meet void shapes at bounces).  void_seen: accumulate_cases.identity_2_per_pixel against the
+    oracle's chains, and a pixel whose every camera sample ends on a void shape keeps sum, m2 and out_rgb at +0 while its count
+    and state advance"""
+    env, counters = VARIANTS[which]
+    knobs(env)
+    c = case("void_hidden")
+    acs.reference_split(acs.library_call(api, c, counters=counters), vm.chains_from(chain_file, "void_hidden"), "void_hidden accumulate, " + which)
+    c = case("void_seen")
+    call = acs.library_call(api, c, counters=counters)
+    acs.identity_2_per_pixel(call, c, "void_seen accumulate, " + which, chain=vm.chains_of(c))
+    assert vm.accumulate_primary_void_pixels(call, c, "void_seen accumulate, " + which) >= 50
+
+
+def test_render_accumulate_device_forms_and_views(api, case, knobs, chain_file):
+    """void_hidden's 1 + 3 + 12 + 48 through the _device forms on a non-default stream, guard words around every plane and no
+    synchronisation between the passes, against the fold of the reference's chains; ort_render_views_accumulate on void_seen's
+    three views -- one inside a void sphere, whose frame stays +0 with its counts advanced -- in passes of 1 + 3 against the
+    oracle's chains from each camera, frame 0 the single-frame form's"""
+    knobs({})
+    c = case("void_hidden")
+    chain = vm.chains_from(chain_file, "void_hidden")
+    want = acs.Planes()
+    for k in acs.REF_SPLIT:
+        acs.model(want, 0, chain, None, k, None)
+    acs.assert_planes(acs.stream_split(c, acs.REF_SPLIT), want, "void_hidden accumulate, the device forms on a stream")
+    c = case("void_seen")
+    call = acs.library_call(api, c)
+    single = acs.Planes()
+    for n in (1, 3):
+        call(single, None, n)
+    got = acs.views_split(call, c, vm.view_cameras(api, c), vm.VIEW_SEEDS, (1, 3), "void_seen accumulate, views", single=single)
+    assert not got.sum[2].view("<u4").any() and not got.m2[2].view("<u4").any() and (got.count[2] == 4).all()   # inside the void sphere
 
 
 # ---- the ray and point queries ---------------------------------------------------------------------------------------------------------------

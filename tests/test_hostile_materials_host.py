@@ -11,8 +11,10 @@ import re
 import numpy as np
 import pytest
 
+import accumulate_cases as acs
 import adaptive_cases as ac
 import feature_cases as fc
+import follow_cases as fw
 import host_sim_tool as hs
 import hostile_materials as hm
 import irradiance_cases as ic
@@ -312,6 +314,58 @@ def test_lanes_features_and_queries(api, tool, case, tmp_path, name):
         rc.assert_same(rgb, fin, w_rgb, w_fin, "%s irradiance %r" % (name, e))
         got, r = ic.host_sim_adaptive(t, tmp_path, c.scn, pts.points, pts.seeds, ic.EVERY, hm.RR, c.base, env=env(e), threads=2)
         ac.assert_same(got, ic.expected_adaptive(chain, pts, ic.EVERY), "%s adaptive irradiance %r" % (name, e))
+
+
+@pytest.mark.parametrize("which", ["host_sim", "host_sim_w5"])
+@pytest.mark.parametrize("name", hm.SCENES)
+def test_lanes_follow(oracle, case, tmp_path, name, which):
+    """--follow, the single frame and a batch of three views (the scene's own camera, hostile_materials.WALL_CAM at the nan and the
+    zero wall, UP_CAM at neg and inf), from the arrays, from the tables image and with the exact walk forced, at (spp 5, rr 0.5,
+    cap 64) and (rr 0.8, cap 2), against follow_cases' chain.  follow_lane's terminal test `is_light || |Kd|^2 > 0 || b == cap`
+    meets every hostile Kd here: NaN (false: followed), 1e-30 (its square underflows: followed), the all-zero material (followed),
+    inf and -0.5 (recorded; an infinite and a negative albedo sum), and the three followed ones draw sample_brdf with no lobe.
+    At cap 64 the chain's final states are first pinned against the diffuse twin's PIXEL states from the oracle on every frame.
+    hostile_materials.follow_conditions states what the frames exercise.  No view of either scene gives a bounce ray with a
+    non-finite direction -- the oracle's count over the four frames and both settings is 0: sample_brdf without a lobe still
+    returns a finite direction -- so the NaN words the planes hold are the recorded Kd of the nan wall at the cap"""
+    t = hs.built(which)
+    c = case(name)
+    w = hm.follow_world(c)
+    fw.pin_on_twin(oracle, w, hm.FEATURE_SPP, hm.FOLLOW_SETTINGS[0][0], c.csg)
+    assert hm.follow_conditions(c) == 0
+    cast = lambda rays: hs.raycast(hs.built("host_sim"), tmp_path, c.scn, rays, base=c.base, threads=2)[0]["prim"]
+    for e in ({}, {"SIM_TABS": "1"}, {"SIM_FORCE_FALLBACK": "0xf"}):
+        def render(batch, rr, cap):
+            kw = dict(cams=w.fcams, seeds=w.fseeds) if batch else dict(seed=hm.SEED)
+            got, r = fw.host_sim(t, tmp_path, c.scn, hm.W, hm.H, None, hm.FEATURE_SPP, rr, cap, base=c.base, env=e, threads=2, **kw)
+            _clean(r)
+            return got
+        nans = fw.assert_renders(render, cast, w, hm.FEATURE_SPP, hm.FOLLOW_SETTINGS, "%s follow %r" % (name, e), nan=True)
+        assert (nans > 0) == (name == "hostile")
+
+
+@pytest.mark.parametrize("which", ["host_sim", "host_sim_w5"])
+@pytest.mark.parametrize("name", hm.SCENES)
+def test_lanes_accumulate(api, case, chain_file, tmp_path, name, which):
+    """--accumulate: 64 samples as 1 + 3 + 12 + 48 and as 26 + 1 + 37 -- a pass ends just before, and a pass of one sample takes,
+    the sample at which a pixel of `hostile` overflows its Q -- against the fold of the REFERENCE's chains (chains_hostile.npz, no
+    oracle in between); accumulate_cases.identity_2_per_pixel (maps, caps and rects that differ between the calls) against the
+    oracle's chains, which test_oracle_chains_match_reference holds against the reference's; a batch of three views in two
+    passes against the oracle's chains from each camera.  A continued job reloads sum, m2, count and state from the planes:
+    here those words are huge, negative and infinite"""
+    c = case(name)
+    chain = hm.chains_from(chain_file, name)
+    hm.accumulate_expected(chain, name)
+    cams = hm.view_cameras(api, c)
+    for e in _diffuse_sets(name) + [{"SIM_TABS": "1"}]:
+        call = acs.host_call(hs.built(which), tmp_path, c, env=e, threads=2)
+        for split in hm.accumulate_splits():
+            acs.reference_split(call, chain, "%s accumulate %r %r" % (name, split, e), split, nan=True)
+        acs.identity_2_per_pixel(call, c, "%s accumulate, per-pixel calls %r" % (name, e), chain=hm.chains_of(c), nan=True)
+    single = acs.Planes()
+    for n in (1, 3):
+        call(single, None, n)
+    acs.views_split(call, c, cams, hm.VIEW_SEEDS, (1, 3), name + " accumulate, views", nan=True, single=single)
 
 
 # ---- part B on the CPU: the oracle alone meets the floors ----------------------------------------------------------------------------

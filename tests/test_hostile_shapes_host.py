@@ -9,9 +9,11 @@ Everything is compared with hostile_materials.same_words: bit for bit, NaN match
 import numpy as np
 import pytest
 
+import accumulate_cases as acs
 import adaptive_cases as ac
 import ao_cases as ao
 import feature_cases as fc
+import follow_cases as fw
 import host_sim_tool as hs
 import hostile_materials as hm
 import hostile_shapes as hsh
@@ -48,7 +50,8 @@ def hits_file():
 def case(api, oracle, manifest, tmp_path_factory):
     def get(name):
         c = hsh.case(api, oracle, name, tmp_path_factory)
-        assert rg.sha256(c.scn) == manifest["generated"]["shapes"]["scenes"][name]["scn_sha256"], name
+        if name not in hsh.SPECULAR:   # those are written for the follow renders alone: the reference has no fixture of them
+            assert rg.sha256(c.scn) == manifest["generated"]["shapes"]["scenes"][name]["scn_sha256"], name
         return c
     return get
 
@@ -357,6 +360,63 @@ def test_lanes_features(api, oracle, tool, case, tmp_path, name):
     prims = hs.raycast(hs.built("host_sim"), tmp_path, c.scn, f.rays[:, 0], c.base, threads=2)[0]["prim"]
     got, _ = fc.host_sim(tool, tmp_path, c.scn, W, H, None, hsh.FEATURE_SPP, seed=hsh.SEED, base=c.base, threads=2)
     hsh.assert_features({k: v[0] for k, v in got.items()}, want, f, prims, name + " features")
+
+
+@pytest.mark.parametrize("name", hsh.FOLLOW_SCENES)
+def test_lanes_follow(api, oracle, tool, case, tmp_path, name):
+    """--follow, the single frame and the batch of hostile_shapes.view_cameras, from the arrays, from the tables image and with
+    the exact walk forced, at (spp 5, rr 0.5, cap 64) and (rr 0.8, cap 2), against follow_cases' chain, whose final states are
+    first pinned against the diffuse twin's PIXEL states from the oracle.  shapes_seen and shapes_leaves have no specular-only
+    material -- printed: nothing is followed from any view -- so there the six planes are --features' and bounces is zero, for
+    both settings (identity 2).  Their SPECULAR twins make the hostile shapes that rays meet mirrors and glass, so bounce rays
+    start ON a sphere of radius -0.5, inverted and flat boxes, cylinders of radius -0.25 and 0 and meshes scaled by -0.6 or
+    turned by a zero quaternion: 45 % of the own frame's samples are followed where those spheres and boxes sit in the prologue
+    (shapes_seen_specular; tools/host_sim --tree-check says so here), 27 % where every hostile shape sits in a leaf
+    (shapes_leaves_specular), paths 7 and 9 bounces deep.  The far scenes keep the room's glass and mirror: 12 %"""
+    c = case(name)
+    w = hsh.follow_world(api, c)
+    fw.pin_on_twin(oracle, w, hsh.FEATURE_SPP, hsh.FOLLOW_SETTINGS[0][0], c.csg)
+    follows = hsh.follow_conditions(api, c)
+    assert follows == (name in hsh.FOLLOWING)
+    if name in hsh.SPECULAR:   # where the commit puts the shapes the samples are followed through
+        where = hsh.in_prologue(c)
+        followed = fw.chains(w, hsh.FEATURE_SPP, *hsh.FOLLOW_SETTINGS[0])[0].followed_by_mat
+        inside = [n for n in hsh.FOLLOW_SPECULAR if where[n] and followed[hsh.MAT[n]]]
+        print("%s: followed through prologue shapes %s" % (name, inside))
+        if name == "shapes_seen_specular":
+            assert {"sphere_neg", "box_inv1", "box_inv3", "box_flat"} <= set(inside) and not where["cyl_neg"] and followed[hsh.MAT["cyl_neg"]]
+        else:
+            assert not any(where.values())
+    cast = lambda rays: hs.raycast(hs.built("host_sim"), tmp_path, c.scn, rays, c.base, threads=2)[0]["prim"]
+    for e in RENDER_SETS:
+        last = {}
+
+        def render(batch, rr, cap):
+            kw = dict(cams=w.fcams, seeds=w.fseeds) if batch else dict(seed=hsh.SEED)
+            last[batch] = fw.host_sim(tool, tmp_path, c.scn, W, H, None, hsh.FEATURE_SPP, rr, cap, base=c.base, env=e, threads=2, **kw)[0]
+            if not follows:
+                first, _ = fc.host_sim(tool, tmp_path, c.scn, W, H, None, hsh.FEATURE_SPP, base=c.base, env=e, threads=2, **kw)
+                for k in fc.PLANES:
+                    same(last[batch][k], first[k], "%s %r rr %g cap %d: %s against --features" % (name, e, rr, cap, k))
+                assert not last[batch]["bounces"].any()
+            return last[batch]
+        fw.assert_renders(render, cast, w, hsh.FEATURE_SPP, hsh.FOLLOW_SETTINGS, "%s follow %r" % (name, e))
+
+
+@pytest.mark.parametrize("name", hsh.CHAINS)
+def test_lanes_accumulate(api, tool, case, chain_file, tmp_path, name):
+    """--accumulate: 64 samples as 1 + 3 + 12 + 48 against the fold of the REFERENCE's chains (chains_shapes.npz), from the arrays
+    and from the tables image: a continued job reloads its sums and its state and walks on among the hostile shapes (and, in
+    shapes_lights, towards the hostile lights); a batch of hostile_shapes.view_cameras in passes of 1 + 3 against the oracle's
+    chains from each camera"""
+    c = case(name)
+    for e in RENDER_SETS[:2]:
+        call = acs.host_call(tool, tmp_path, c, env=e, threads=2)
+        acs.reference_split(call, hsh.chains_from(chain_file, name), "%s accumulate %r" % (name, e), nan=name not in hsh.NO_NONFINITE)
+    single = acs.Planes()
+    for n in (1, 3):
+        call(single, None, n)
+    acs.views_split(call, c, hsh.view_cameras(api, c), hsh.VIEW_SEEDS, (1, 3), name + " accumulate, views", nan=name not in hsh.NO_NONFINITE, single=single)
 
 
 def _one(c, d):

@@ -19,9 +19,11 @@ import os
 import numpy as np
 import pytest
 
+import accumulate_cases as acs
 import ao_cases
 import deep_scenes
 import feature_cases
+import follow_cases as fw
 import host_sim_tool as hs
 import irradiance_cases
 import light_groups_cases as lg
@@ -239,6 +241,39 @@ def test_features(world, tmp_path, name, variant):
     feature_cases.assert_same({k: v[0] for k, v in got.items()}, ts.features_expected(w), "%s %s" % (name, variant))
 
 
+def _follow(w, tmp_path, variant, env=None):
+    width, height, spp = ts.FEATURES
+    got, r = fw.host_sim(hs.built("host_sim"), tmp_path, w.scn, width, height, None, spp, ts.FOLLOW[0], ts.FOLLOW[1], seed=ts.SEED, base=w.base,
+                         env=_env(variant, env), threads=8)
+    return {k: v[0] for k, v in got.items()}, hs.counters(r)
+
+
+@pytest.mark.parametrize("env", [{}, TABS], ids=ids)
+@pairs
+def test_follow(world, tmp_path, name, variant, env):
+    """--follow at FEATURES' frame, rr 0.5, cap 64, against follow_cases' chain from the oracle, which knows no variant: all seven
+    planes, the ids' shapes through --raycast of the chain's last rays under the same variant, and every plane but ids byte for
+    byte what the first variant of the scene gave.  The followed bounce rays start on a surface, so they are the fast walk's own:
+    on glass_room, whose default tree is one leaf, they walk a tree only under no_prologue, mixed_root and small_prologue --
+    asserted through the node tests per ray, which under no_prologue exceed the default tree's on every scene"""
+    w = world(name)
+    ts.assert_follow_conditions(w)
+    c = ts.follow_chain(w)
+    got, counted = _follow(w, tmp_path, variant, env)
+    what = "%s %s %r follow" % (name, variant, env)
+    fw.assert_same(got, ts.follow_expected(w), what)
+    assert counted["rays"] == c.rays and counted["paths"] == 0
+    prims = hs.raycast(hs.built("host_sim"), tmp_path, w.scn, c.last, base=w.base, env=_env(variant), threads=8)[0]["prim"]
+    fw.assert_prims(got["ids"][None], [c], prims, what)
+    as_bytes = lambda p: [np.ascontiguousarray(p[k]).tobytes() for k in fw.PLANES if k != "ids"]
+    first = ts.cached(w, ("follow on the host, the default tree", ids(env)), lambda: as_bytes(_follow(w, tmp_path, "default", env)[0]))
+    assert as_bytes(got) == first, "%s: a plane differs from the one under the default tree" % what
+    if variant == "no_prologue":
+        _, default = _follow(w, tmp_path, "default", env)
+        print("%s: node tests per ray %.2f under no_prologue, %.2f under the default tree" % (name, counted["node_tests"] / counted["rays"], default["node_tests"] / default["rays"]))
+        assert default["rays"] == counted["rays"] and counted["node_tests"] > default["node_tests"]
+
+
 @pytest.mark.parametrize("policy", ["chunk", "pixel"])
 @pairs
 def test_views(world, tmp_path, name, variant, policy):
@@ -256,7 +291,8 @@ def test_views(world, tmp_path, name, variant, policy):
 @pairs
 def test_light_groups_and_sample_map(world, tmp_path, name, variant, env):
     """the lanes of pt_groups and pt_sample_map at VIEWS' frame: one group per light material against the dark twins of the
-    world's flattened scene, and the mixed map at cap 4 against the oracle's chains"""
+    world's flattened scene, and the mixed map at cap 4 against the oracle's chains; the lanes of pt_accumulate under the same
+    map in two passes (caps 1 and 3) against those chains folded, every plane byte for byte the default tree's"""
     w = world(name)
     width, height, spp, _ = ts.VIEWS
     assert (lg.W, lg.H) == (width, height)
@@ -270,3 +306,8 @@ def test_light_groups_and_sample_map(world, tmp_path, name, variant, env):
     smap, want = ts.sample_map_expected(w)
     got, _ = sm.host_sample_map(hs.built("host_sim"), tmp_path, ref, smap, ts.MAP_CAP, seed=ts.SEED, env=_env(variant, env), threads=8)
     sm.assert_planes(tuple(p[0] for p in got), want, "%s %s %r sample map" % (name, variant, env))
+    # the lanes of pt_accumulate: a continued job reloads its sums and state and walks the variant's tree from there
+    passes = lambda v: [np.ascontiguousarray(a).tobytes() for a in
+                        ts.accumulate_passes(w, acs.host_call(hs.built("host_sim"), tmp_path, ref, env=_env(v, env), threads=8), "%s %s %r" % (name, v, env)).all()]
+    first = ts.cached(w, ("accumulate on the host, the default tree", ids(env)), lambda: passes("default"))
+    assert passes(variant) == first, "%s %s %r accumulate: a plane differs from the one under the default tree" % (name, variant, env)

@@ -11,9 +11,11 @@ import re
 import numpy as np
 import pytest
 
+import accumulate_cases as acs
 import adaptive_cases as ac
 import ao_cases as ao
 import feature_cases as fc
+import follow_cases as fw
 import host_sim_tool as hs
 import hostile_materials as hm
 import irradiance_cases as ic
@@ -440,6 +442,57 @@ def test_lanes_features(api, oracle, tool, case, tmp_path, name):
     else:
         partial = (want["hits"] > 0) & (want["hits"] < vm.FEATURE_SPP)
         assert partial.any()
+
+
+@pytest.mark.parametrize("name", vm.SCENES + ("all_void",))
+def test_lanes_follow(api, oracle, tool, case, tmp_path, name):
+    """--follow, the single frame and a batch of four views (void_material.view_cameras, one of them inside a void sphere, and
+    GLASS_CAM, which looks at void shapes through the glass sphere), from the arrays, from the tables image and with the exact
+    walk forced, at (spp 5, rr 0.5, cap 64) and (rr 0.8, cap 2), against follow_cases' chain.  A sample that ends on a void shape
+    -- a camera ray or a bounce ray -- records nothing; as sample 0 it leaves ids {0, that shape}, the shape --raycast names for
+    the chain's last ray, and not NO_PRIM, which stays for a miss and for a sample 0 the roulette ended.  At cap 64 the chain's
+    final states are first pinned against the diffuse twin's PIXEL states from the oracle (void_hidden, void_seen: every pixel
+    of every frame).  all_void: every plane +0, hits 0, ids {0, a shape} or {0, NO_PRIM}, and the final states are --features'
+    at the same spp: nothing can be followed"""
+    c = case(name)
+    w = vm.follow_world(api, c)
+    fw.pin_on_twin(oracle, w, vm.FEATURE_SPP, vm.FOLLOW_SETTINGS[0][0], c.csg)
+    vm.follow_conditions(api, c)
+    cast = lambda rays: hs.raycast(hs.built("host_sim"), tmp_path, c.scn, rays, c.base, threads=2)[0]["prim"]
+    for e in RENDER_SETS:
+        last = {}
+
+        def render(batch, rr, cap):
+            kw = dict(cams=w.fcams, seeds=w.fseeds) if batch else dict(seed=vm.SEED)
+            last[batch] = fw.host_sim(tool, tmp_path, c.scn, W, H, None, vm.FEATURE_SPP, rr, cap, base=c.base, env=e, threads=2, **kw)[0]
+            return last[batch]
+        assert fw.assert_renders(render, cast, w, vm.FEATURE_SPP, vm.FOLLOW_SETTINGS, "%s follow %r" % (name, e)) == 0
+        if name == "all_void":
+            first, _ = fc.host_sim(tool, tmp_path, c.scn, W, H, None, vm.FEATURE_SPP, cams=w.fcams, seeds=w.fseeds, base=c.base, env=e, threads=2)
+            got = last[True]
+            for k in ("albedo", "normal", "depth", "hits", "bounces"):
+                assert not np.ascontiguousarray(got[k]).view("<u4").any(), k
+            assert not got["ids"][..., 0].any() and (got["ids"][..., 1] != fc.NO_PRIM).any()
+            rg.assert_words_equal(got["states"], first["states"], "all_void: the final states are the first-hit render's")
+
+
+def test_lanes_accumulate(api, tool, case, chain_file, tmp_path):
+    """--accumulate.  void_hidden: 64 samples as 1 + 3 + 12 + 48 against the fold of the REFERENCE's chains (chains_void.npz: paths
+    that meet void shapes at bounces).  void_seen: accumulate_cases.identity_2_per_pixel against the oracle's chains; a pixel
+    whose every camera sample ends on a void shape keeps sum, m2 and out_rgb at +0 while its count and state advance; and a
+    batch of void_material.view_cameras -- one inside a void sphere -- in passes of 1 + 3 against the oracle's chains"""
+    for e in RENDER_SETS[:2]:
+        c = case("void_hidden")
+        acs.reference_split(acs.host_call(tool, tmp_path, c, env=e, threads=2), vm.chains_from(chain_file, "void_hidden"), "void_hidden accumulate %r" % (e,))
+        c = case("void_seen")
+        call = acs.host_call(tool, tmp_path, c, env=e, threads=2)
+        acs.identity_2_per_pixel(call, c, "void_seen accumulate %r" % (e,), chain=vm.chains_of(c))
+        assert vm.accumulate_primary_void_pixels(call, c, "void_seen accumulate %r" % (e,)) >= 50
+    single = acs.Planes()
+    for n in (1, 3):
+        call(single, None, n)
+    got = acs.views_split(call, c, vm.view_cameras(api, c), vm.VIEW_SEEDS, (1, 3), "void_seen accumulate, views", single=single)
+    assert not got.sum[2].view("<u4").any() and not got.m2[2].view("<u4").any() and (got.count[2] == 4).all()   # inside the void sphere
 
 
 def test_lanes_radiance_and_irradiance(api, tool, case, tmp_path):

@@ -352,6 +352,34 @@ def features_expected(w):
     return cached(w, "features", make)
 
 
+FOLLOW = (0.5, 64)                    # rr, cap of the follow render at FEATURES' frame: nothing reaches the cap
+FOLLOWING_SCENES = ("glass_room", "c2_analytic")
+
+
+def follow_chain(w):
+    """follow_cases.chain of FEATURES' frame from the scene's own camera: the follow render's reference, which knows no variant"""
+    import follow_cases
+    def make():
+        width, height, spp = FEATURES
+        return follow_cases.chain(w.oracle, w.osc, w.flat, w.scene.camera(width, height), width, height, SEED, spp, FOLLOW[0], FOLLOW[1])
+    return cached(w, "follow chain", make)
+
+
+def follow_expected(w):
+    import follow_cases
+    return cached(w, "follow", lambda: follow_cases.expected(follow_chain(w)))
+
+
+def assert_follow_conditions(w):
+    """on the scenes with mirrors and glass at least a tenth of the samples are followed and some path bounces twice: the bounce
+    rays, which start on a surface and so are the fast walk's own, are there to walk whatever tree the variant builds"""
+    c = follow_chain(w)
+    print("%s follow: followed %.3f of the samples, deepest b %d, %d rays for %d samples" % (w.name, c.followed / c.samples, c.max_b, c.rays, c.samples))
+    assert c.at_cap == 0
+    if w.name in FOLLOWING_SCENES:
+        assert c.followed >= 0.10 * c.samples and c.max_b >= 2
+
+
 def view_cams(w):
     """two cameras: the scene's own pose moved towards the middle of the scene and yawed (views_cases.MOVES 1 and 2)"""
     def make():
@@ -414,3 +442,36 @@ def sample_map_expected(w):
     """sample_map_cases.mixed_map() at cap 4 -> (the map, (rgb, m2, states)) from the oracle's chains"""
     assert (sm.W, sm.H) == VIEWS[:2]
     return cached(w, "sample map", lambda: (sm.mixed_map(), sm.expected_from(pixel_chains(w), sm.mixed_map(), MAP_CAP)))
+
+
+class AccumulateCase:
+    """what accumulate_cases' calls and sample_map_cases.chains take of a case, of a world and one of its scene handles"""
+
+    def __init__(self, w, scene):
+        self.name, self.scene, self.osc = "tree shapes " + w.name, scene, w.osc
+
+    def twin(self, keep):
+        assert keep is None
+        return self.osc
+
+    def camera(self, size=None):
+        return self.scene.camera(*(size if size else VIEWS[:2]))
+
+
+ACCUMULATE_CAPS = (1, 3)   # two passes under the mixed map: MAP_CAP = 4 is the chains' length
+
+
+def accumulate_passes(w, call, what):
+    """two accumulating passes under sample_map_cases.mixed_map(), caps 1 and 3, through `call` (accumulate_cases.host_call's or
+    library_call's, at SEED) against pixel_chains folded by accumulate_cases.model, every plane after each pass -> the planes"""
+    import accumulate_cases as acs
+    assert sum(ACCUMULATE_CAPS) == MAP_CAP and (acs.W, acs.H) == VIEWS[:2]
+    smap = sm.mixed_map()
+    got, want = acs.Planes(), acs.Planes()
+    for cap in ACCUMULATE_CAPS:
+        paths = call(got, smap, cap, seed=SEED)
+        asked = acs.model(want, 0, pixel_chains(w), smap, cap, None)
+        assert paths in (None, asked) and asked > 0
+        acs.assert_planes(got, want, "%s accumulate: after the pass at cap %d" % (what, cap))
+    assert len(np.unique(got.count)) >= 4
+    return got

@@ -466,6 +466,71 @@ def view_cameras(api, c):
     return np.stack([c.cam, lg.batch_cameras(api, c)[1], inside_camera(api, c)])
 
 
+# ---- the renders that follow mirrors and glass (follow_cases.py) ---------------------------------------------------------------------
+# a view for them on void_seen: close to the room's glass sphere (0, 0, 0.9), which fills most of the frame, from the side
+# opposite the void sphere over the table and the void box -- the refracted rays leave the glass towards them, so followed samples
+# END on void shapes at b >= 1, which no view of view_cameras gives (the oracle's count there is 0).  p, x_axis, y_axis, z_axis
+# as hostile_materials.UP_CAM is written
+GLASS_CAM = np.array([[-0.634, -1.023, 1.074], [0.499, -0.309, 0.0], [-0.029, -0.048, -0.387], [-0.522, -0.841, 0.143]], "<f4")
+FOLLOW_SETTINGS = hm.FOLLOW_SETTINGS
+FOLLOW_SEEDS = VIEW_SEEDS + (0xDEADBEEF,)
+
+
+def follow_world(api, c):
+    """follow_cases' world of a case: the single frame from the scene's own camera on SEED; the batch is view_cameras (the third
+    stands inside a void sphere: every sample ends on it at b == 0) and GLASS_CAM"""
+    import follow_cases as fw
+    return fw.case_world(c, np.concatenate([view_cameras(api, c), GLASS_CAM[None]]), FOLLOW_SEEDS)
+
+
+def follow_conditions(api, c):
+    """what the follow frames of a case must exercise, from the oracle's side (follow_cases.chain), printed and asserted.
+    void_seen: the scene's own camera ends at least 50 samples on void shapes, GLASS_CAM at least 5 of them at b >= 1 -- a bounce
+    ray that ends on a void shape records nothing and, as sample 0, leaves ids {0, that shape}.  void_hidden: no camera sample
+    sees a void shape from the scene's own camera, and a few followed ones end on one (non-zero, below 1 % of the samples).
+    all_void: every sample of every frame ends on a void shape at b == 0 or misses"""
+    import follow_cases as fw
+    w = follow_world(api, c)
+    per = {s: fw.chains(w, FEATURE_SPP, *s) for s in FOLLOW_SETTINGS}
+    for (rr, cap), ch in per.items():
+        print("%s rr %g cap %d: per frame (own, own, pose 1, inside, GLASS_CAM) followed %s, void ends %s, of them at b >= 1 %s, sample 0's %s"
+              % (c.name, rr, cap, [k.followed for k in ch], [k.void_ends for k in ch], [k.void_bounce_ends for k in ch], [int(k.void0.sum()) for k in ch]))
+    own, glass = per[FOLLOW_SETTINGS[0]][0], per[FOLLOW_SETTINGS[0]][4]
+    if c.name == "void_seen":
+        assert own.void_ends >= 50 and int(own.void0.sum()) >= 50
+        assert glass.void_bounce_ends >= 5 and int((glass.void0_bounces >= 1).sum()) >= 5
+        assert glass.followed >= 0.10 * glass.samples
+    elif c.name == "void_hidden":
+        for s in FOLLOW_SETTINGS:
+            k = per[s][0]
+            assert 0 < k.void_ends == k.void_bounce_ends < 0.01 * k.samples
+        assert own.followed >= 0.10 * own.samples
+    else:
+        assert all(k.followed == 0 and k.rays == k.samples and not k.hits.any() for ch in per.values() for k in ch)
+    assert all((k.void0.all() and k.void_ends == k.samples) for k in (per[s][3] for s in FOLLOW_SETTINGS))   # inside the void sphere
+
+
+def accumulate_primary_void_pixels(call, c, what, passes=(2, 3)):
+    """accumulating passes over the whole frame of void_seen: a pixel whose every camera sample ends on a void shape has sum +0,
+    m2 +0, out_rgb +0, count = the samples asked for, and its state advanced by the camera draws alone -- the state
+    feature_cases.camera_rays leaves after that many samples.  `call`: accumulate_cases.host_call's or library_call's.  Such
+    pixels exist (asserted: at least 50 of 384) -> their number"""
+    import accumulate_cases as acs
+    n = sum(passes)
+    f = first_hits(c, (W, H), spp=n)
+    void = ((f.mat == 0) & (f.t.view("<u4") != raycast_cases.FLT_MAX.view("<u4"))).all(axis=1)
+    assert void.sum() >= 50, void.sum()
+    got = acs.Planes()
+    for k in passes:
+        call(got, None, k)
+    ys, xs = f.ys[void], f.xs[void]
+    for a, name in ((got.sum, "sum_rgb"), (got.m2, "m2"), (got.rgb, "out_rgb")):
+        assert not np.ascontiguousarray(a[0][ys, xs]).view("<u4").any(), "%s: %s of a pixel whose samples all end on a void shape" % (what, name)
+    assert (got.count[0] == n).all() and (got.states[0][ys, xs] == f.after[void, n - 1]).all(), what
+    assert (got.states[0][ys, xs] != f.after[void, passes[0] - 1]).all()
+    return int(void.sum())
+
+
 def advance(oracle, seed, steps):
     """the stream's state `steps` draws after seed (0 is taken as 1): radiance_cases.step, the oracle's xorshift restated there"""
     import radiance_cases as rc
