@@ -957,6 +957,86 @@ int ort_render_views_follow(ort_scene *scene, const ort_render_params *params, c
 int ort_render_views_follow_device(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count,
                                    uint32_t max_bounces, const ort_follow_planes *planes, void *hip_stream, ort_stats *stats);
 
+/* ---- ID-matte renders: per-pixel coverage per material, object or shape, for compositing -----
+ * ort_render_features' ids are those of sample 0 and do not average: through the aperture a pixel at a silhouette, or any pixel off
+ * the focal plane, sees several shapes.  These calls count, per pixel, how many of the camera's samples saw which id: an
+ * anti-aliased matte per material, object or shape is counts / spp (ort_matte_mask below).
+ * Planes.  width*height entries per frame with row 0 at the bottom, view_count frames view-major; K = m->slots:
+ *    ids           K u32 per pixel   [frame][pixel][slot]: the ids kept, ORT_MATTE_EMPTY in an unused slot      (REQUIRED)
+ *    counts        K u32 per pixel   [frame][pixel][slot]: the samples that saw ids' id, 0 in an unused slot     (REQUIRED)
+ *    other         u32               recorded samples that found no slot                                        (may be NULL)
+ *    hits          u32               recorded samples                                                           (may be NULL)
+ *    final_states  u32               the stream's state after the last sample                                   (may be NULL)
+ * Pixels outside the rect are left untouched in every plane.
+ * The job.  The job, its stream, the camera sample and the closest hit h are ort_render_features', word for word.  The stream
+ * advances 2*spp steps whatever is hit.
+ * The id of a sample.  h.mat == 0 (a miss, or a shape that carries material 0) records nothing: this is the rule by which such a
+ * sample "does not count in hits".  Otherwise the sample is recorded with the id
+ *    ORT_MATTE_BY_MATERIAL  h.mat;
+ *    ORT_MATTE_BY_PRIM      h.prim as ort_raycast returns it;
+ *    ORT_MATTE_BY_OBJECT    h.prim for a box, cylinder or sphere; for a triangle ORT_HIT_MESH << 28 | mesh index, the index being the
+ *                           position in the scene's mesh order, as ort_scene_get_mesh takes it.
+ * The slots.  K slots start empty, with used = 0 and other = 0.  For every recorded sample, in sample order, with id x: if a used
+ * slot holds x, its count goes up by one; else if used < K, slot `used` becomes (x, 1) and used++; else other++.  At the job's end
+ * the used slots are ordered by count descending, with ties broken by ascending id (unsigned compare), and written to
+ * ids[at*K + j] and counts[at*K + j], at being the pixel's index in its plane; unused slots get (ORT_MATTE_EMPTY, 0).  hits is the
+ * number of recorded samples.
+ * Lossy slots.  While other == 0 the slots are the pixel's exact histogram.  Where other > 0 the kept ids are the first K to
+ * appear, not the K largest.  A lane cannot know the largest without holding them all.  The caller sees which pixels are affected
+ * and renders again with a larger K.
+ * Six identities, all bit for bit.  (1) sum(counts) + other == hits, and hits and final_states are ort_render_features' planes.
+ * (2) At spp == 1, ids[at*K] is ort_render_features' ids.mat (BY_MATERIAL) or ids.prim (BY_PRIM) where it hit, and ORT_MATTE_EMPTY
+ * where it did not.  (3) Where other == 0 under both modes, the BY_OBJECT counts folded through "object -> its material" are the
+ * BY_MATERIAL counts.  (4) Frame v of a batch is the single-frame call's frame.  (5) other, hits and final_states being asked for
+ * or not changes no bit elsewhere.  (6) Pixels outside the rect are untouched in every plane.
+ * Parameters, the error order, stats and the device-form rules are ort_render_views_features'.  Added to its ORT_ERR_INVALID
+ * list, after "a plane not 4-byte aligned" and in this order: m NULL; by above 2; slots 0 or above ORT_MAX_MATTE_SLOTS; ids or
+ * counts NULL.  (A NULL planes struct stands where ort_render_views_features has it; no "all planes NULL" error exists here.)
+ * During a call the words of ids and counts inside the rect are working memory: their contents before the call are not read. */
+#define ORT_MATTE_BY_MATERIAL 0u
+#define ORT_MATTE_BY_OBJECT 1u
+#define ORT_MATTE_BY_PRIM 2u
+#define ORT_MAX_MATTE_SLOTS 8u
+#define ORT_MATTE_EMPTY 0xffffffffu
+#define ORT_HIT_MESH 1   /* kind of an object id that names a mesh; ort_raycast never returns it */
+typedef struct {
+    uint32_t by;     /* ORT_MATTE_BY_MATERIAL, ORT_MATTE_BY_OBJECT or ORT_MATTE_BY_PRIM */
+    uint32_t slots;  /* K, within [1, ORT_MAX_MATTE_SLOTS] */
+} ort_matte;
+typedef struct {
+    uint32_t *ids;           /* K u32 per pixel   required */
+    uint32_t *counts;        /* K u32 per pixel   required */
+    uint32_t *other;         /* u32               may be NULL */
+    uint32_t *hits;          /* u32               may be NULL */
+    uint32_t *final_states;  /* u32               may be NULL */
+} ort_matte_planes;          /* HOST pointers in the host forms, DEVICE pointers in the _device forms; the struct itself is host memory */
+
+/* host planes in, host planes out (device staging is internal); synchronous */
+int ort_render_matte(ort_scene *scene, const ort_render_params *params, const ort_matte *m, const ort_matte_planes *planes, ort_stats *stats);
+int ort_render_matte_device(ort_scene *scene, const ort_render_params *params, const ort_matte *m, const ort_matte_planes *planes, void *hip_stream,
+                            ort_stats *stats);
+/* view_count frames per plane, view-major */
+int ort_render_views_matte(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count, const ort_matte *m,
+                           const ort_matte_planes *planes, ort_stats *stats);
+int ort_render_views_matte_device(ort_scene *scene, const ort_render_params *params, const ort_view *views, uint32_t view_count, const ort_matte *m,
+                                  const ort_matte_planes *planes, void *hip_stream, ort_stats *stats);
+
+/* ---- a mask from matte slots: the coverage of a selection of ids -----
+ * out_mask[p] = (float)(the sum of counts[p][j] over the slots j whose ids[p][j] is in select) / (float)spp: a u32 sum that wraps
+ * as u32 sums do, one conversion and one f32 division.  ids and counts hold `slots` words per pixel as ort_render_matte writes them
+ * ([frame][pixel][slot]), out_mask one f32 per pixel; a duplicate in select counts once; slots that hold ORT_MATTE_EMPTY are never
+ * selected.  No scene and no allocation: the call names its device, as ort_denoise does, and the device form enqueues one kernel on
+ * hip_stream and does not wait.  select is HOST memory in both forms, copied before the call returns.
+ * frame_count == 0 is ORT_OK without a launch.  ORT_ERR_INVALID, in this order: a null ids, counts, select or out_mask; one of ids,
+ * counts, out_mask not 4-byte aligned; slots 0 or above ORT_MAX_MATTE_SLOTS; width or height < 1 or
+ * frame_count*width*height*slots >= 1 << 31; spp outside [1, 1 << 24]; select_count outside [1, ORT_MAX_MATTE_SELECT]; ORT_MATTE_EMPTY in select.
+ * ORT_ERR_NO_DEVICE: no such device. */
+#define ORT_MAX_MATTE_SELECT 256u
+int ort_matte_mask(int device, const uint32_t *ids, const uint32_t *counts, uint32_t slots, uint32_t spp, const uint32_t *select,
+                   uint32_t select_count, int32_t width, int32_t height, uint32_t frame_count, float *out_mask);
+int ort_matte_mask_device(int device, const void *d_ids, const void *d_counts, uint32_t slots, uint32_t spp, const uint32_t *select,
+                          uint32_t select_count, int32_t width, int32_t height, uint32_t frame_count, void *d_out_mask, void *hip_stream);
+
 /* ---- denoising: a variance-guided, edge-avoiding a-trous filter over rendered frames -----------
  * What uses the planes above: the mean colour with its sample count n and its sum of squared sample luminance Q (ort_render_adaptive,
  * ort_render_sample_map, ort_render_accumulate) and the guide planes of ort_render_features.  `iterations` passes of 5 x 5 taps at

@@ -135,6 +135,20 @@ class FollowPlanes(C.Structure):
 assert C.sizeof(FollowPlanes) == 56
 
 
+class Matte(C.Structure):
+    """ort_matte: what an ID-matte render names a hit by (MATTE_BY) and the slots per pixel"""
+    _fields_ = [("by", C.c_uint32), ("slots", C.c_uint32)]
+
+
+class MattePlanes(C.Structure):
+    """ort_matte_planes: where an ID-matte render writes (ort_render_matte); ids and counts are required, a null pointer among the
+    others is a plane not asked for."""
+    _fields_ = [("ids", C.c_void_p), ("counts", C.c_void_p), ("other", C.c_void_p), ("hits", C.c_void_p), ("final_states", C.c_void_p)]
+
+
+assert C.sizeof(MattePlanes) == 40 and C.sizeof(Matte) == 8
+
+
 class LightGroups(C.Structure):
     _fields_ = [("group_of_material", C.c_void_p), ("material_count", C.c_uint32), ("group_count", C.c_uint32)]
 
@@ -188,6 +202,12 @@ class AccumPlanes(C.Structure):
 FEATURE_PLANES = ("albedo", "normal", "depth", "hits", "ids", "states")   # render_features()'s want=
 FOLLOW_PLANES = ("albedo", "normal", "depth", "hits", "ids", "bounces", "states")   # render_follow()'s want=
 MAX_FOLLOW_BOUNCES = 64   # ORT_MAX_FOLLOW_BOUNCES
+MATTE_PLANES = ("ids", "counts", "other", "hits", "states")   # render_matte()'s planes; want= names the last three
+MATTE_BY = {"material": 0, "object": 1, "prim": 2}   # ORT_MATTE_BY_*
+MATTE_EMPTY = 0xFFFFFFFF   # ORT_MATTE_EMPTY
+HIT_MESH = 1               # ORT_HIT_MESH: the kind of an object id that names a mesh
+MAX_MATTE_SLOTS = 8        # ORT_MAX_MATTE_SLOTS
+MAX_MATTE_SELECT = 256     # ORT_MAX_MATTE_SELECT
 
 
 class Hit(C.Structure):
@@ -218,6 +238,8 @@ EXPORTS = [
     "ort_render_adaptive", "ort_render_adaptive_device", "ort_render_views_adaptive", "ort_render_views_adaptive_device",
     "ort_render_features", "ort_render_features_device", "ort_render_views_features", "ort_render_views_features_device",
     "ort_render_follow", "ort_render_follow_device", "ort_render_views_follow", "ort_render_views_follow_device",
+    "ort_render_matte", "ort_render_matte_device", "ort_render_views_matte", "ort_render_views_matte_device",
+    "ort_matte_mask", "ort_matte_mask_device",
     "ort_render_light_groups", "ort_render_light_groups_device", "ort_render_views_light_groups",
     "ort_render_views_light_groups_device",
     "ort_render_sample_map", "ort_render_sample_map_device", "ort_render_views_sample_map", "ort_render_views_sample_map_device",
@@ -300,6 +322,8 @@ def lib():
                 ("ort_render_views_features", [vp, C.POINTER(RenderParams), vp, C.c_uint32, C.POINTER(FeaturePlanes), stats]),
                 ("ort_render_follow", [vp, C.POINTER(RenderParams), C.c_uint32, C.POINTER(FollowPlanes), stats]),
                 ("ort_render_views_follow", [vp, C.POINTER(RenderParams), vp, C.c_uint32, C.c_uint32, C.POINTER(FollowPlanes), stats]),
+                ("ort_render_matte", [vp, C.POINTER(RenderParams), C.POINTER(Matte), C.POINTER(MattePlanes), stats]),
+                ("ort_render_views_matte", [vp, C.POINTER(RenderParams), vp, C.c_uint32, C.POINTER(Matte), C.POINTER(MattePlanes), stats]),
                 ("ort_raycast", [vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
                 ("ort_occluded", [vp, vp, vp, C.c_uint64, vp, C.c_uint32, stats]),
                 ("ort_ambient_occlusion", [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint32, stats]),
@@ -322,7 +346,9 @@ def lib():
         L.ort_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoisePlanes), C.c_int32, C.c_int32, C.c_uint32, vp, stats]
         L.ort_denoise_device.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoisePlanes), C.c_int32, C.c_int32, C.c_uint32, vp, vp,
                                          C.c_uint64, vp, stats]
-        L.ort_plan_samples_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.ort_matte_mask.argtypes = [C.c_int, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, vp]
+        L.ort_matte_mask_device.argtypes = [C.c_int, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, vp, vp]
+        L.ort_plan_samples_workspace_bytes.argtypes =[C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
         L.ort_plan_samples.argtypes = [C.c_int, C.POINTER(PlanParams), C.POINTER(PlanPlanes), C.c_int32, C.c_int32, C.c_uint32, vp, vp, stats]
         L.ort_plan_samples_device.argtypes = [C.c_int, C.POINTER(PlanParams), C.POINTER(PlanPlanes), C.c_int32, C.c_int32, C.c_uint32, vp, vp, vp,
                                               C.c_uint64, vp, stats]
@@ -1052,6 +1078,104 @@ class Scene:
         views = _views(cameras, seeds)
         return self._follow_device(views, params, max_bounces, d_planes, stream, want_stats)
 
+    # -- ID-matte renders: per-pixel coverage per material, object or shape -------------------------
+    def object_ids(self):
+        """every object id an ID-matte render by="object" can give, with the material the object carries -> (ids (N,) uint32,
+        mats (N,) uint32): HIT_MESH << 28 | i for mesh i, then kind << 28 | i for the boxes (2), cylinders (3) and spheres (4) in
+        the scene's own order.  What selections for matte_mask are built from."""
+        si = self.info()
+        ids, mats = [], []
+        for i in range(si.mesh_count):
+            m = Mesh()
+            _check(lib().ort_scene_get_mesh(self.handle, i, C.byref(m)))
+            ids.append(HIT_MESH << 28 | i)
+            mats.append(m.mat)
+        for kind, name, dtype, n in ((2, "boxes", BOX_DTYPE, si.box_count), (3, "cylinders", CYLINDER_DTYPE, si.cylinder_count),
+                                     (4, "spheres", SPHERE_DTYPE, si.sphere_count)):
+            shapes = self._get(name, dtype, n)
+            ids += [kind << 28 | i for i in range(n)]
+            mats += [int(m) for m in shapes["mat"]]
+        return np.array(ids, "<u4"), np.array(mats, "<u4")
+
+    @staticmethod
+    def _matte(by, slots):
+        if by not in MATTE_BY:
+            raise ValueError("by must be one of %s, got %r" % (tuple(MATTE_BY), by))
+        if not 0 <= int(slots) <= 0xFFFFFFFF:
+            raise ValueError("slots must fit an unsigned 32-bit word, got %r" % (slots,))
+        return Matte(MATTE_BY[by], int(slots))
+
+    @staticmethod
+    def _matte_planes(shape, slots, want, out):
+        """the host planes of a matte render, by name: ids and counts always, those of want besides; zeros, or the caller's (out: a
+        dict by exactly those names, checked)"""
+        k = max(1, min(int(slots), MAX_MATTE_SLOTS))   # a bad slots is the library's to name
+        specs = {"ids": (shape + (k,), "<u4"), "counts": (shape + (k,), "<u4"), "other": (shape, "<u4"), "hits": (shape, "<u4"), "states": (shape, "<u4")}
+        want = tuple(want)
+        if len(set(want)) != len(want) or not set(want) <= set(MATTE_PLANES[2:]):
+            raise ValueError("want must name planes of %s, each once, got %r" % (MATTE_PLANES[2:], want))
+        names = MATTE_PLANES[:2] + want
+        if out is None:
+            return {n: np.zeros(*specs[n]) for n in names}
+        if set(out) != set(names):
+            raise ValueError("out must hold exactly the planes %r, got %r" % (names, tuple(out)))
+        for n in names:
+            if not _is_plane(out[n], *specs[n]):
+                raise ValueError("out[%r] must be a C-contiguous array of shape %s dtype %s" % ((n,) + specs[n]))
+        return dict(out)
+
+    @staticmethod
+    def _matte_struct(ptrs):
+        """name -> pointer (ints, ctypes pointers, None) -> MattePlanes"""
+        unknown = set(ptrs) - set(MATTE_PLANES)
+        if unknown:
+            raise ValueError("unknown matte planes %r: the planes are %s" % (sorted(unknown), MATTE_PLANES))
+        mp = MattePlanes()
+        for k in MATTE_PLANES:
+            v = _ptr(ptrs.get(k))
+            setattr(mp, "final_states" if k == "states" else k, v.value if isinstance(v, C.c_void_p) else v)
+        return mp
+
+    def _matte_host(self, views, width, height, spp, seed, by, slots, rect, want, counters, out):
+        m = self._matte(by, slots)
+        planes = self._matte_planes(_lead(views) + (height, width), slots, want, out)
+        p = self.params(width, height, spp, seed, "pixel", 0, rect, 0.8, counters)
+        mp = self._matte_struct({k: a.ctypes.data for k, a in planes.items()})
+        return planes, self._pixel_jobs("matte", views, False, p, [], [C.byref(m), C.byref(mp)])
+
+    def _matte_device(self, views, params, by, slots, d_planes, stream, want_stats):
+        m = self._matte(by, slots)
+        mp = self._matte_struct(d_planes)
+        return self._pixel_jobs("matte", views, True, params, [], [C.byref(m), C.byref(mp)], stream, want_stats)
+
+    def render_matte(self, width, height, spp, seed, by="object", slots=8, rect=None, want=("other", "hits"), counters=False, out=None):
+        """ID mattes: per pixel, how many of the camera's spp samples (render_features' samples, bit for bit) saw which id --
+        by="material" the hit's material, by="prim" its shape as raycast names it, by="object" the shape, or for a triangle
+        HIT_MESH << 28 | its mesh (object_ids lists them).  Returns ({"ids": (H, W, slots) uint32, "counts": (H, W, slots) uint32,
+        and those of want: "other", "hits", "states" (H, W) uint32}, stats dict).  A pixel's slots are ordered by count
+        descending, then id ascending; unused slots hold (MATTE_EMPTY, 0).  While other is 0 the slots are the pixel's exact
+        histogram; where other > 0 the kept ids are the first `slots` to appear, not the largest: render again with more slots.
+        matte_mask turns a selection of ids into a coverage mask.  Pixels outside rect keep what out's planes held."""
+        return self._matte_host(None, width, height, spp, seed, by, slots, rect, want, counters, out)
+
+    def render_matte_device(self, params, by="object", slots=8, stream=None, want_stats=False, **d_planes):
+        """The same into device planes: ids=, counts= (both required, slots words a pixel), other=, hits=, states= raw device
+        pointers.  params: Scene.params(..., policy="pixel"); its chunk and rr are ignored.  Enqueued on stream; waits only when
+        want_stats (returns the stats dict)."""
+        return self._matte_device(None, params, by, slots, d_planes, stream, want_stats)
+
+    def render_views_matte(self, cameras, seeds, width, height, spp, by="object", slots=8, rect=None, want=("other", "hits"), counters=False,
+                           out=None):
+        """render_matte for a batch of views in one launch (cameras, seeds as render_views): frame v is what render_matte gives
+        with seed seeds[v] if the scene's camera were cameras[v].  Every plane has a leading axis of V frames."""
+        views = _views(cameras, seeds)
+        return self._matte_host(views, width, height, spp, 0, by, slots, rect, want, counters, out)
+
+    def render_views_matte_device(self, params, cameras, seeds, by="object", slots=8, stream=None, want_stats=False, **d_planes):
+        """The same into device planes of V frames each, view-major.  params.seed is ignored."""
+        views = _views(cameras, seeds)
+        return self._matte_device(views, params, by, slots, d_planes, stream, want_stats)
+
     # -- closest-hit ray queries -----------------------------------------------------------
     def raycast(self, rays, counters=False):
         """Closest hit of each ray (raycast_top_most_node, ray.cpp:1165).  rays: (N, 6) float32 o.xyz d.xyz (d need
@@ -1415,6 +1539,37 @@ def over_hits(plane, hits, spp):
     h = hits.reshape(hits.shape + (1,) * (plane.ndim - hits.ndim)).astype("<f4")
     with np.errstate(all="ignore"):
         return np.where(h > 0, plane * np.float32(spp) / h, np.float32(0)).astype("<f4")
+
+
+def _select(select):
+    select = np.ascontiguousarray(np.asarray(select).astype(np.int64).reshape(-1) & 0xFFFFFFFF, dtype="<u4")
+    return select, (select.ctypes.data if len(select) else None)
+
+
+def matte_mask(ids, counts, spp, select, device=0, out=None):
+    """ort_matte_mask: the slots of render_matte -- ids and counts (H, W, K) uint32, or with a leading V -- and a selection of ids
+    (1 .. MAX_MATTE_SELECT of them; a duplicate counts once) -> out (H, W) float32: the selected slots' counts, summed, over
+    float32(spp)."""
+    ids, counts = np.ascontiguousarray(ids, dtype="<u4"), np.ascontiguousarray(counts, dtype="<u4")
+    if ids.ndim not in (3, 4) or ids.shape != counts.shape:
+        raise ValueError("ids and counts must both be (H, W, K) or (V, H, W, K), got shapes %s and %s" % (ids.shape, counts.shape))
+    shape = ids.shape[:-1]
+    if out is None:
+        out = np.empty(shape, "<f4")
+    elif not _is_plane(out, shape, "<f4"):
+        raise ValueError("out must be a C-contiguous float32 array of shape %s" % (shape,))
+    select, sp = _select(select)
+    _check(lib().ort_matte_mask(int(device), ids.ctypes.data, counts.ctypes.data, ids.shape[-1], int(spp), sp, len(select), shape[-1], shape[-2],
+                                1 if ids.ndim == 3 else shape[0], out.ctypes.data))
+    return out
+
+
+def matte_mask_device(d_ids, d_counts, slots, spp, select, width, height, d_out, frame_count=1, device=0, stream=None):
+    """ort_matte_mask_device: raw device pointers (torch data_ptr()) of ids and counts (slots words a pixel) and of out (a float a
+    pixel); select is host memory, read before the call returns.  One kernel enqueued on stream; no wait, no allocation."""
+    select, sp = _select(select)
+    _check(lib().ort_matte_mask_device(int(device), _ptr(d_ids), _ptr(d_counts), int(slots), int(spp), sp, len(select), int(width), int(height),
+                                       int(frame_count), _ptr(d_out), _ptr(stream)))
 
 
 def denoise_workspace_bytes(width, height, frame_count=1):

@@ -735,6 +735,56 @@ static int render_follow_common(ort_scene *s, const ort_render_params *p, const 
         });
 }
 
+/* ID-matte renders: render_features_common's order.  Nulls: the planes struct, the views; no plane is required before the params
+   are judged.  rr is not the caller's to set, as there.  Own checks: spp above 1 << 24, the planes' alignment, then m, by, slots and
+   the two required planes, in that order.  The launch is device_render_matte */
+static int render_matte_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool batch, bool host,
+                               const ort_matte *m, const ort_matte_planes *planes, void *stream, ort_stats *stats) {
+    static const PixelJobKind kind = {"the matte render cuts one-pixel jobs: it needs the PIXEL policy", "the matte render is not sharded",
+                                      "the matte render has no packed planes"};
+    return render_pixel_jobs(
+        kind, s, p, views, view_count, batch, host, stream, stats,
+        [&] {
+            if (!planes) return fail(ORT_ERR_INVALID, "null planes");
+            return batch && !views ? fail(ORT_ERR_INVALID, "null views") : ORT_OK;
+        },
+        [](ort_render_params *q) { q->rr = 0.0f; },
+        [&](const ort_render_params &q) {
+            if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp must be <= 1 << 24: a sample count must be exact in float");
+            if (int rc = check_ptrs({{planes->ids, false, 4}, {planes->counts, false, 4}, {planes->other, false, 4}, {planes->hits, false, 4},
+                                     {planes->final_states, false, 4}}, "", "", "ids, counts, other, hits and final_states must be 4-byte aligned"))
+                return rc;
+            if (!m) return fail(ORT_ERR_INVALID, "null m (the matte's mode and slots)");
+            if (m->by > ORT_MATTE_BY_PRIM) return fail(ORT_ERR_INVALID, "by must be ORT_MATTE_BY_MATERIAL, ORT_MATTE_BY_OBJECT or ORT_MATTE_BY_PRIM");
+            if (m->slots == 0 || m->slots > ORT_MAX_MATTE_SLOTS) return fail(ORT_ERR_INVALID, "slots must be within [1, ORT_MAX_MATTE_SLOTS]");
+            if (!planes->ids || !planes->counts) return fail(ORT_ERR_INVALID, host ? "null ids or counts plane" : "null device ids or counts plane");
+            return (int)ORT_OK;
+        },
+        [&](const ort_render_params &q, const ort::RenderCall &c) {
+            std::string err;
+            const int rc = ort::device_render_matte(s, &q, c.views, c.view_count, *m, {host, 0, q.flags, stream, stats}, *planes, &err);
+            return rc == ORT_OK ? ORT_OK : fail(rc, err);
+        });
+}
+
+/* ---- a mask from matte slots (ort_mattemask.h, device_matte_mask): no scene, the order of the checks is the call's contract (include/ort.h) ---- */
+static int matte_mask_common(int device, bool host, const void *ids, const void *counts, uint32_t slots, uint32_t spp, const uint32_t *select, uint32_t select_count,
+                             int32_t width, int32_t height, uint32_t frame_count, void *out_mask, void *hip_stream) {
+    if (frame_count == 0) return ORT_OK;
+    if (!ids || !counts || !select || !out_mask) return fail(ORT_ERR_INVALID, "null ids, counts, select or out_mask");
+    for (const void *q : {ids, counts, (const void *)out_mask})
+        if ((uintptr_t)q & 3u) return fail(ORT_ERR_INVALID, "ids, counts or out_mask not 4-byte aligned");
+    if (slots == 0 || slots > ORT_MAX_MATTE_SLOTS) return fail(ORT_ERR_INVALID, "slots must be within [1, ORT_MAX_MATTE_SLOTS]");
+    if (width < 1 || height < 1 || (uint64_t)frame_count * (uint64_t)width * (uint64_t)height * slots >= (1ull << 31)) return fail(ORT_ERR_INVALID, "bad frame size");
+    if (spp < 1 || spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp must be within [1, 1 << 24]");
+    if (select_count < 1 || select_count > ORT_MAX_MATTE_SELECT) return fail(ORT_ERR_INVALID, "select_count must be within [1, ORT_MAX_MATTE_SELECT]");
+    for (uint32_t i = 0; i < select_count; ++i)
+        if (select[i] == ORT_MATTE_EMPTY) return fail(ORT_ERR_INVALID, "ORT_MATTE_EMPTY in select");
+    std::string err;
+    int rc = ort::device_matte_mask(device, host, ids, counts, slots, spp, select, select_count, width, height, frame_count, out_mask, hip_stream, &err);
+    return rc == ORT_OK ? ORT_OK : fail(rc, err);
+}
+
 static int ort_render_views_workspace_bytes_impl(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) {
     if (!p || !bytes) return fail(ORT_ERR_INVALID, "null argument");
     *bytes = ort::render_views_workspace_bytes(p, view_count);
@@ -943,6 +993,12 @@ int ort_render_follow(ort_scene *s, const ort_render_params *p, uint32_t max_bou
 int ort_render_follow_device(ort_scene *s, const ort_render_params *p, uint32_t max_bounces, const ort_follow_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_follow_common(s, p, nullptr, 1, false, false, max_bounces, planes, hip_stream, stats); }); }
 int ort_render_views_follow(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, uint32_t max_bounces, const ort_follow_planes *planes, ort_stats *stats) { return guarded([&]() { return render_follow_common(s, p, views, view_count, true, true, max_bounces, planes, nullptr, stats); }); }
 int ort_render_views_follow_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, uint32_t max_bounces, const ort_follow_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_follow_common(s, p, views, view_count, true, false, max_bounces, planes, hip_stream, stats); }); }
+int ort_render_matte(ort_scene *s, const ort_render_params *p, const ort_matte *m, const ort_matte_planes *planes, ort_stats *stats) { return guarded([&]() { return render_matte_common(s, p, nullptr, 1, false, true, m, planes, nullptr, stats); }); }
+int ort_render_matte_device(ort_scene *s, const ort_render_params *p, const ort_matte *m, const ort_matte_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_matte_common(s, p, nullptr, 1, false, false, m, planes, hip_stream, stats); }); }
+int ort_render_views_matte(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_matte *m, const ort_matte_planes *planes, ort_stats *stats) { return guarded([&]() { return render_matte_common(s, p, views, view_count, true, true, m, planes, nullptr, stats); }); }
+int ort_render_views_matte_device(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_matte *m, const ort_matte_planes *planes, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_matte_common(s, p, views, view_count, true, false, m, planes, hip_stream, stats); }); }
+int ort_matte_mask(int device, const uint32_t *ids, const uint32_t *counts, uint32_t slots, uint32_t spp, const uint32_t *select, uint32_t select_count, int32_t width, int32_t height, uint32_t frame_count, float *out_mask) { return guarded([&]() { return matte_mask_common(device, true, ids, counts, slots, spp, select, select_count, width, height, frame_count, out_mask, nullptr); }); }
+int ort_matte_mask_device(int device, const void *d_ids, const void *d_counts, uint32_t slots, uint32_t spp, const uint32_t *select, uint32_t select_count, int32_t width, int32_t height, uint32_t frame_count, void *d_out_mask, void *hip_stream) { return guarded([&]() { return matte_mask_common(device, false, d_ids, d_counts, slots, spp, select, select_count, width, height, frame_count, d_out_mask, hip_stream); }); }
 int ort_render_views_workspace_bytes(const ort_render_params *p, uint32_t view_count, uint64_t *bytes) { return guarded([&]() { return ort_render_views_workspace_bytes_impl(p, view_count, bytes); }); }
 int ort_shard_block_count(int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, uint64_t *blocks) { return guarded([&]() { return ort_shard_block_count_impl(width, height, shard_index, shard_count, blocks); }); }
 int ort_pack_blocks_host(const float *full_rgb, int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count, float *packed) { return guarded([&]() { return ort_pack_blocks_host_impl(full_rgb, width, height, shard_index, shard_count, packed); }); }

@@ -6,7 +6,7 @@
  * (ort_launch_pixel_jobs); for the others kLaunchers below pairs every entry of that header's list of built kernels with this
  * unit's kernel, which that instantiates, or a sibling unit's launcher.  A render and a ray query share the steps around their kernels.
  * The denoiser's kernels (ort_denoise.h) are launched from here too (device_denoise): they need no scene and no plan.
- * So are the sample planner's (ort_sampleplan.h, device_plan_samples).
+ * So are the sample planner's (ort_sampleplan.h, device_plan_samples) and the matte mask's (ort_mattemask.h, device_matte_mask).
  */
 #include <algorithm>
 #include <memory>
@@ -18,6 +18,7 @@
 #include "ort_setup.h"
 #include "ort_denoise.h" /* the denoiser's pixel functions and kernels (namespace ortdn); device_denoise below launches them */
 #include "ort_sampleplan.h" /* the sample planner's (namespace ortsp); device_plan_samples below launches them */
+#include "ort_mattemask.h" /* the matte mask's (namespace ortmm); device_matte_mask below launches it */
 
 #ifndef ORT_HOST_SIM /* tools/host_sim.cpp drives the lane code itself and has no device */
 namespace ort {
@@ -104,6 +105,7 @@ struct DeviceScene {
     unsigned long long *h_active = nullptr; /* pinned */
     /* ray queries (device_raycast): the shape table, built at the first query on this upload, and the host path's staging */
     DevBuf prim_src;
+    DevBuf obj_src; /* ID-matte renders BY_OBJECT (device_render_matte): prim_src with a triangle's word naming its mesh, built at the first such render */
     float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0}; /* shapes and camera (raycast_needs_exact) */
     bool scene_box_known = false;
     DevBuf query_stage[6]; /* the i-th array of the host form in flight (run_query); six: the adaptive radiance query's */
@@ -616,6 +618,16 @@ static int ensure_prim_src(Scene *scene, DeviceScene *d, std::string *err) {
     return upload_vec(src, &d->prim_src, err);
 }
 
+/* the same table with a triangle's word naming its mesh (object_ids_from_prim_src, ort_setup.h): the ids of ORT_MATTE_BY_OBJECT.
+   Built from the scene's mesh triangle counts and uploaded at the first matte render that asks for it */
+static int ensure_obj_src(Scene *scene, DeviceScene *d, std::string *err) {
+    if (d->obj_src.p) return ORT_OK;
+    std::vector<uint32_t> src, obj;
+    const bool ok = invert_prim_slots(scene->tree, d->info_box, d->info_cyl, d->info_sphere, src) && object_ids_from_prim_src(*scene, src, obj);
+    if (!ok) { *err = "internal: the tree's slot maps are not a bijection onto its shape arrays, or a triangle lies beyond the scene's meshes"; return ORT_ERR_INTERNAL; }
+    return upload_vec(obj, &d->obj_src, err);
+}
+
 /* what raycast_needs_exact reads, and the rays (a device pointer) */
 static RaycastIO ray_query_io(Scene *scene, DeviceScene *d, const void *rays) {
     RaycastIO io{};
@@ -875,6 +887,46 @@ int device_render_follow(Scene *scene, const ort_render_params *p, const ort_vie
     return settle_inflight(d, err);
 }
 
+/* ID-matte renders: device_render_features with the five planes of ort_render_matte -- ids and counts hold m.slots words a pixel
+   --, the table the mode names a hit by (the shape table, the object table, none) and plan_matte's plan.  The host form stages
+   ids and counts whole both ways like every other plane, so that pixels outside the rect keep what they held */
+int device_render_matte(Scene *scene, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_matte &m, const QueryCall &q,
+                        const ort_matte_planes &planes, std::string *err) {
+    DeviceScene *d;
+    int rc;
+    if ((rc = begin_query(scene, q.stats, &d, err))) return rc;
+    if (m.by == ORT_MATTE_BY_PRIM && (rc = ensure_prim_src(scene, d, err))) return rc;
+    if (m.by == ORT_MATTE_BY_OBJECT && (rc = ensure_obj_src(scene, d, err))) return rc;
+    hipStream_t stream = (hipStream_t)q.stream;
+    /* the staging buffers and both copies of the camera table are the previous call's until that has finished */
+    if ((rc = settle_inflight(d, err))) return rc;
+    const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
+    DevBuf *const st = d->query_stage;
+    Plane pn[5] = {{planes.ids, st, pixels * 4u * m.slots, nullptr}, {planes.counts, st + 1, pixels * 4u * m.slots, nullptr}, {planes.other, st + 2, pixels * 4u, nullptr},
+                   {planes.hits, st + 3, pixels * 4u, nullptr}, {planes.final_states, st + 4, pixels * 4u, nullptr}};
+    static_assert(sizeof(pn) / sizeof(pn[0]) <= sizeof(d->query_stage) / sizeof(d->query_stage[0]), "one staging buffer per plane");
+    if ((rc = stage_planes_in(pn, 5, q.host, stream, err)) || (rc = upload_view_table(d, views, view_count, stream, err))) return rc;
+    RenderView rv{};
+    matte_view(*p, view_count, &rv);
+    rv.views = d->view_tab.as<const float4>();
+    MatteIO io{};
+    io.q = ray_query_io(scene, d, nullptr);
+    io.q.prim_src = m.by == ORT_MATTE_BY_PRIM ? d->prim_src.as<const uint32_t>() : m.by == ORT_MATTE_BY_OBJECT ? d->obj_src.as<const uint32_t>() : nullptr;
+    io.ids = (uint32_t *)pn[0].dev; io.counts = (uint32_t *)pn[1].dev; io.other = (uint32_t *)pn[2].dev;
+    io.hits = (uint32_t *)pn[3].dev; io.states = (uint32_t *)pn[4].dev;
+    io.by = m.by; io.slots = m.slots;
+    const bool counters = (q.flags & ORT_RENDER_COUNTERS) != 0;
+    auto planner = [&](const SceneTraits &t, const Knobs &kn) { return plan_matte(t, *p, view_count, counters, kn); };
+    rc = launch_planned(scene, d, rv, rv.job_count, planner, false, stream, q.stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &plan) {
+        with_bools([&](auto C, auto T) {
+            hipLaunchKernelGGL((matte_pixels<decltype(C)::value, decltype(T)::value>), dim3(plan.grid), dim3(kBlock), 0, stream, sv, hot, io);
+        }, plan.counters, plan.tabs);
+    });
+    if (rc || (rc = stage_planes_out(pn, 5, q.host, stream, err)) || !q.host) return rc;
+    ORT_HIP(hipStreamSynchronize(stream));
+    return settle_inflight(d, err);
+}
+
 /* radiance: count rays with their seeds -> 3 floats each and, where asked for (states may be null), the final states.  No shape
    table: a colour names no shape.  With ad (checked by the caller) the adaptive query: the stopping rule's parameters where spp
    stands, and, where asked for, every ray's sample count and its sum of squared sample luminance; plan_radiance's plan as it
@@ -1045,6 +1097,38 @@ int device_plan_samples(int device, bool host, const ort_plan_params &p, const o
         ORT_HIP(hipMemcpy(sample_map, d_sample_map, 4 * n, hipMemcpyDeviceToHost));
         ORT_HIP(hipMemcpy(totals, d_tot, totals_bytes, hipMemcpyDeviceToHost));
     }
+    return ORT_OK;
+}
+
+/* ---- a mask from matte slots (ort_mattemask.h): one kernel, one lane a pixel by grid stride.  No scene: the call names its device.
+   The selection is sorted and freed of duplicates here and travels in the launch's arguments, so the device form allocates
+   nothing and has read the caller's select when it returns; it does not wait.  host: ids, counts and the mask are staged whole
+   through buffers of this call's own.  The arguments are checked by the caller (ort_api.cpp: matte_mask_common). */
+int device_matte_mask(int device, bool host, const void *ids, const void *counts, uint32_t slots, uint32_t spp, const uint32_t *select, uint32_t select_count,
+                      int32_t w, int32_t h, uint32_t frames, void *out_mask, void *stream_, std::string *err) {
+    int count = 0;
+    int rc = device_count(&count, err);
+    if (rc != ORT_OK) return rc;
+    if (device < 0 || device >= count) { *err = "no such HIP device"; return ORT_ERR_NO_DEVICE; }
+    ORT_HIP(hipSetDevice(device));
+    hipStream_t stream = host ? nullptr : (hipStream_t)stream_;
+    const size_t n = (size_t)frames * (size_t)w * (size_t)h;
+    DevBuf d_ids, d_counts, d_mask;
+    if (host) {
+        if ((rc = d_ids.ensure(4 * n * slots, err)) || (rc = d_counts.ensure(4 * n * slots, err)) || (rc = d_mask.ensure(4 * n, err))) return rc;
+        ORT_HIP(hipMemcpy(d_ids.p, ids, 4 * n * slots, hipMemcpyHostToDevice));
+        ORT_HIP(hipMemcpy(d_counts.p, counts, 4 * n * slots, hipMemcpyHostToDevice));
+        ids = d_ids.p; counts = d_counts.p;
+    }
+    float *d_out = host ? d_mask.as<float>() : (float *)out_mask;
+    ortmm::Select sel;
+    ortmm::prepare_select(select, select_count, &sel);
+    constexpr uint64_t kMaxGrid = 1u << 16; /* workgroups of one launch; the kernel strides over what is beyond */
+    const uint64_t groups = (n + 255u) / 256u;
+    hipLaunchKernelGGL(ortmm::matte_mask, dim3((uint32_t)std::min(groups, kMaxGrid)), dim3(256), 0, stream, (const uint32_t *)ids, (const uint32_t *)counts, d_out, slots,
+                       (float)spp, (uint32_t)n, sel);
+    ORT_HIP(hipGetLastError());
+    if (host) ORT_HIP(hipMemcpy(out_mask, d_out, 4 * n, hipMemcpyDeviceToHost));
     return ORT_OK;
 }
 

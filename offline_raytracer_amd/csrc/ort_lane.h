@@ -271,6 +271,20 @@ struct FollowIO {
     uint32_t max_bounces;   /* <= ORT_MAX_FOLLOW_BOUNCES: a vertex reached after this many bounces is recorded whatever it is */
 };
 
+/* the third argument of matte_pixels: the planes of ort_render_matte, view_count frames view-major; ids and counts hold `slots`
+   words per pixel and are the lanes' working memory for the length of a job (matte_lane) */
+struct MatteIO {
+    RaycastIO q;            /* what raycast_needs_exact reads; q.prim_src is the table the mode names a hit by: the shape table
+                               (ORT_MATTE_BY_PRIM), the object table (ORT_MATTE_BY_OBJECT), null (ORT_MATTE_BY_MATERIAL).  rays and hits are null */
+    uint32_t *ids;          /* slots per pixel */
+    uint32_t *counts;       /* slots per pixel */
+    uint32_t *other;        /* 1 per pixel, or null: recorded samples that found no slot */
+    uint32_t *hits;         /* 1 per pixel, or null: recorded samples */
+    uint32_t *states;       /* 1 per pixel, or null: the stream after 2 * spp steps */
+    uint32_t by;            /* ORT_MATTE_BY_* */
+    uint32_t slots;         /* K, within [1, ORT_MAX_MATTE_SLOTS] */
+};
+
 } // namespace ort
 
 #ifndef ORT_HOST_SIM
@@ -3234,6 +3248,136 @@ follow_pixels(SceneView sv, RenderHot rv, FollowIO io) {
     __shared__ float lds_job[kFollowCacheWords * kBlock]; /* the job's sums and L (follow_lane) */
     if (TABS) fill_tab(sv, lds_tab);
     follow_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(TABS, LF_TABS)>(sv, rv, io, lds_tab, lds_stack, lds_job + threadIdx.x, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+}
+#endif
+
+/* ---- ID-matte renders (ort_render_matte): per-pixel coverage per material, object or shape ----------------------------------
+ * feature_lane's job, job space, camera sample and closest hit, word for word; what a sample leaves is not a sum but an id (the
+ * hit's material, its shape as ort_raycast names it, or its object: io.q.prim_src is the table the mode reads, null BY_MATERIAL),
+ * binned into the pixel's K slots by include/ort.h's rule.  A separate lane, not a flavour of feature_lane: every existing
+ * kernel's code stays as it is (profiles/r29_isa_diff.txt).
+ * WHERE THE SLOTS LIVE.  Sixteen words a lane do not fit in LDS beside the stack and the tables (feature_pixels' largest variant
+ * holds 39 456 of the 40 960 bytes that four blocks a CU allow), and sixteen dynamically indexed registers are scratch.  So the
+ * slots live where they end up: in the pixel's own K words of io.ids and io.counts, which belong to this lane alone for the length
+ * of the job (as pt_groups keeps its G sums in the pixel's own output words).  The current run (id, length) is held in registers,
+ * and only a sample whose id differs from the run's merges the run into the slots: slot assignment depends on the order of first
+ * appearance alone, so merging runs in order gives the slots of the per-sample rule, and a pixel that sees one id touches memory
+ * once, at its job's end.  used, other and the hit count are registers; no LDS word is the job's.  Plain vector loads and
+ * stores, no atomics: a pixel has one owner, and a lane reads back only what it wrote itself. */
+ORT_D void matte_merge(uint32_t *ids, uint32_t *counts, uint32_t slots, uint32_t &used, uint32_t &other, uint32_t id, uint32_t len) {
+    for (uint32_t j = 0; j < used; ++j)
+        if (ids[j] == id) { counts[j] = counts[j] + len; return; }
+    if (used < slots) { ids[used] = id; counts[used] = len; used++; }
+    else other += len;
+}
+
+/* the job's end: the used slots by count descending, ties by ascending id (a selection sort in place over at most
+   ORT_MAX_MATTE_SLOTS entries), and (ORT_MATTE_EMPTY, 0) in the others */
+ORT_D void matte_finish(uint32_t *ids, uint32_t *counts, uint32_t slots, uint32_t used) {
+    for (uint32_t j = 0; j + 1u < used; ++j) {
+        uint32_t best = j, bi = ids[j], bc = counts[j];
+        const uint32_t ji = bi, jc = bc;
+        for (uint32_t k = j + 1u; k < used; ++k) {
+            const uint32_t ki = ids[k], kc = counts[k];
+            if (kc > bc || (kc == bc && ki < bi)) { best = k; bi = ki; bc = kc; }
+        }
+        if (best != j) { ids[best] = ji; counts[best] = jc; ids[j] = bi; counts[j] = bc; }
+    }
+    for (uint32_t j = used; j < slots; ++j) { ids[j] = 0xffffffffu; counts[j] = 0u; }
+}
+
+template <uint32_t F>
+ORT_D void matte_lane(const SceneView &sv, const RenderHot &rv, const MatteIO &io, const float4 *tab, uint32_t *lds_stack, const int tid, const uint32_t lane_id,
+                      unsigned long long *pool) {
+    static_assert(flavour_ok(F, LF_OF_LANE), "see flavour_ok");
+    constexpr bool COUNTERS = F & LF_COUNTERS;
+    uint32_t spill[kSpillStack];
+    PathState P; /* org, dir; rng; pxy; job_index: the view; sample: the samples of this pixel started so far */
+    HitState h;
+    Trav T;
+    Counters c;
+    Prof pr;
+    const uint32_t spp = rv.c->spp, slots = io.slots;
+    uint32_t hits = 0, used = 0, other = 0, run_id = 0, run_len = 0; /* run_len == 0: no run yet */
+    bool tracing = false, held = false, busy = false, more = true;   /* as feature_lane's */
+    for (;;) {
+        if (!tracing) {
+            if (held) { /* the finished sample: raycast_lane's record, into the run or the slots */
+                resolve_hit<resolve_of(F), kLdsStack, kBlock>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
+                if (h.hit_mat != 0u) {
+                    const uint32_t x = io.by == 0u ? h.hit_mat : io.q.prim_src[info_index(sv, h.hit_prim)];
+                    hits++;
+                    if (run_len != 0u && x == run_id) run_len++;
+                    else {
+                        if (run_len != 0u) {
+                            const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16) * slots;
+                            matte_merge(io.ids + at, io.counts + at, slots, used, other, run_id, run_len);
+                        }
+                        run_id = x;
+                        run_len = 1u;
+                    }
+                }
+                held = false;
+            }
+            bool start = false;
+            for (;;) { /* the job's end and the next pixel */
+                if (busy) {
+                    if (P.sample < spp) { start = true; break; }
+                    const size_t px = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16), at = px * slots;
+                    if (run_len != 0u) matte_merge(io.ids + at, io.counts + at, slots, used, other, run_id, run_len);
+                    matte_finish(io.ids + at, io.counts + at, slots, used);
+                    if (io.other) io.other[px] = other;
+                    if (io.hits) io.hits[px] = hits;
+                    if (io.states) io.states[px] = P.rng;
+                    busy = false;
+                }
+                if (!more) break;
+                const unsigned long long j = draw_job(rv, pool);
+                if (!(j < rv.c->job_count)) { more = false; break; }
+                const uint32_t view = (uint32_t)(j / rv.c->view_jobs), within = (uint32_t)(j % rv.c->view_jobs);
+                const BlockPixel bp = block_pixel(rv, within >> 6, within & 63u);
+                if (bp.outside) continue;
+                const int x = bp.x, y = bp.y;
+                P.job_index = view;
+                P.pxy = (uint32_t)x | ((uint32_t)y << 16);
+                P.rng = job_seed(om_f32_bits(rv.c->views[4u * (size_t)view].w), (uint32_t)(y * rv.W + x));
+                P.sample = 0;
+                hits = used = other = run_len = 0u;
+                busy = true;
+            }
+            if (start) { /* the camera sample, as produce_ray composes it: one converged sin/cos for the lanes that start a sample */
+                const ViewCamera cam = load_view_camera(rv, P.job_index);
+                const V3 focal = view_focal_point(rv, P.pxy, cam);
+                const float angle = rng_between(P.rng, 0.0f, 2 * kPi); /* ray.cpp:1232 */
+                float sn, cs;
+                ort_sincosf(angle, &sn, &cs);
+                P.org = view_aperture_point(cam, 0.1f, cs, sn); /* ray.cpp:1199, :1233-1234 */
+                P.dir = normalize(sub(focal, P.org));           /* ray.cpp:1237 */
+                P.sample++;
+                begin_ray<begin_of(F), kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
+                if (ORT_RARE(raycast_needs_exact(io.q, P.org, P.dir, T.inv_d))) skip_fast_walk(T, h);
+                if (COUNTERS) c.rays++;
+                tracing = held = true;
+            }
+        }
+        /* a lane that neither traces, owns a pixel nor is entitled to another draw has none and will get none */
+        if (ORT_BALLOT(tracing || busy || more) == 0ull) break;
+        if (tracing) tracing = traverse<walk_of(F), kLdsStack, kBlock>(sv, P.org, P.dir, T, h, lds_stack, spill, tid, rv.refill_below, rv.descend_below, c, pr, kNoPrim, tab);
+    }
+    flush_counters(rv, c, COUNTERS);
+}
+
+/* TABS: the prologue shapes fit their LDS slot and so do the materials (plan_matte is plan_features: TAB_PRO and TAB_MATS), though
+   these lanes read no material; otherwise the shapes are read from HBM */
+#ifndef ORT_HOST_SIM
+template <bool COUNTERS, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+matte_pixels(SceneView sv, RenderHot rv, MatteIO io) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    if (TABS) fill_tab(sv, lds_tab);
+    matte_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(TABS, LF_TABS)>(sv, rv, io, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
 }
 #endif
 

@@ -531,6 +531,13 @@ inline QueryPlan plan_follow(const SceneTraits &t, const ort_render_params &p, u
     return pl;
 }
 
+/* The launch of an ID-matte render (ort_render_matte and its views forms; the matte_pixels kernels): plan_features, every rule
+   unchanged -- the job space, the walk and the batches are that render's.  tabs stays plan_features' condition although these lanes
+   read no material: one condition for both first-hit kinds, so that their plans are the same line for line. */
+inline QueryPlan plan_matte(const SceneTraits &t, const ort_render_params &p, uint32_t view_count, bool counters, const Knobs &kn) {
+    return plan_features(t, p, view_count, counters, kn);
+}
+
 /* The launch of a radiance query over count rays (ort_radiance; the radiance_rays kernels): always the plain persistent loop at
    four waves.  The ray exchange, the five-waves unit, the wide tree and wavefront mode are not built with a ray job space and
    their knobs are not looked at; ORT_DEBUG_UTIL has no probes here.  diffuse, tabs, the refill and descend thresholds and the

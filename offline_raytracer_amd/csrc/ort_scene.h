@@ -273,6 +273,15 @@ int device_render_features(Scene *scene, const ort_render_params *p, const ort_v
    ort_render_follow; p->rr is the roulette's, max_bounces (checked by the caller) the cap on every path */
 int device_render_follow(Scene *scene, const ort_render_params *p, const ort_view *views, uint32_t view_count, uint32_t max_bounces, const QueryCall &q,
                          const ort_follow_planes &planes, std::string *err);
+/* ID-matte renders: device_render_features' frames, forms and staging with the five planes of ort_render_matte; m (checked by the
+   caller) names the mode and the slots per pixel */
+int device_render_matte(Scene *scene, const ort_render_params *p, const ort_view *views, uint32_t view_count, const ort_matte &m, const QueryCall &q,
+                        const ort_matte_planes &planes, std::string *err);
+/* a mask from matte slots (include/ort.h: ort_matte_mask), on `device` and without a scene.  host: ids, counts and out_mask are the
+   caller's memory, staged whole; otherwise they are device pointers, nothing is allocated and the kernel is enqueued on stream
+   without a wait.  select is host memory in both forms and travels in the launch.  The arguments are checked by the caller */
+int device_matte_mask(int device, bool host, const void *ids, const void *counts, uint32_t slots, uint32_t spp, const uint32_t *select, uint32_t select_count,
+                      int32_t w, int32_t h, uint32_t frames, void *out_mask, void *stream, std::string *err);
 /* the denoiser (include/ort.h: ort_denoise), on `device` and without a scene.  host: every plane and out_rgb are the caller's
    memory, staged whole, and the workspace is the call's own (workspace unread); otherwise all are device pointers, the workspace is
    the caller's and the passes are enqueued on stream.  The arguments are checked by the caller */

@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -221,6 +222,35 @@ template <typename View>
 inline void follow_view(const ort_render_params &p, uint32_t view_count, View *rv) {
     features_view(p, view_count, rv);
     rv->rr = p.rr;
+}
+
+/* ID-matte renders (matte_lane): features_view as it stands; by and slots travel in the kernels' third argument */
+template <typename View>
+inline void matte_view(const ort_render_params &p, uint32_t view_count, View *rv) {
+    features_view(p, view_count, rv);
+}
+
+/* ID-matte renders BY_OBJECT: invert_prim_slots' table with a triangle's word replaced by ORT_HIT_MESH << 28 | its mesh's index.
+   A triangle's index in the scene's own arrays is mesh-major, so tri_counts (the triangles of every mesh, in the scene's mesh
+   order) names its mesh.  False when a triangle lies beyond the meshes or a mesh index does not fit below bit 28 */
+inline bool object_ids_from_prim_src(const std::vector<uint32_t> &src, const std::vector<uint32_t> &tri_counts, std::vector<uint32_t> &obj) {
+    std::vector<uint64_t> end(tri_counts.size()); /* end[m]: the first triangle id past mesh m */
+    uint64_t sum = 0;
+    for (size_t m = 0; m < tri_counts.size(); ++m) end[m] = sum += tri_counts[m];
+    obj = src;
+    for (uint32_t &w : obj) {
+        if ((w >> 28) != PRIM_TRI) continue;
+        const size_t m = (size_t)(std::upper_bound(end.begin(), end.end(), (uint64_t)(w & 0x0fffffffu)) - end.begin());
+        if (m >= end.size() || m >= 0x10000000u) return false;
+        w = (1u /* ORT_HIT_MESH */ << 28) | (uint32_t)m;
+    }
+    return true;
+}
+/* ... for a scene: tri_counts from its meshes, as ort_scene_get_mesh orders them */
+inline bool object_ids_from_prim_src(const Scene &scene, const std::vector<uint32_t> &src, std::vector<uint32_t> &obj) {
+    std::vector<uint32_t> tri_counts;
+    for (const HostMesh &m : scene.meshes) tri_counts.push_back((uint32_t)(m.indices.size() / 3));
+    return object_ids_from_prim_src(src, tri_counts, obj);
 }
 
 /* runtime bools to template arguments: f(std::bool_constant...) with one constant per bool, true first at every level */

@@ -34,6 +34,9 @@
  *   or: host_sim --features scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|-
  *   or: host_sim --follow scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr max_bounces albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- bounces.u32|- states.u32|-
  *       (the feature render that follows mirrors and glass, follow_lane: --features' arguments with rr, the cap and the bounces plane)
+ *   or: host_sim --matte scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp by slots ids.u32 counts.u32 other.u32|- hits.u32|- states.u32|-
+ *       (the ID-matte render, matte_lane: --features' arguments with by -- 0 material, 1 object, 2 prim -- and slots, and the five planes
+ *       of ort_render_matte; the planes start at 0xeeeeeeee and, the states, 0xdddddddd)
  *       (the first-hit feature render, feature_lane: a batch of views, or with cams - the scene's own camera on the seed given; a
  *       plane given as - is not passed; the planes start at -7.0f, 0xeeeeeeee and, the states, 0xdddddddd)
  *   or: host_sim --light-groups scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr groups.u8 G groups.f32 rgb.f32|- states.u32|-
@@ -746,6 +749,49 @@ static int features_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x
            (!want[4] || write_bytes(a[15], ids.data(), 8 * n)) && (!want[5] || write_bytes(a[16], states.data(), 4 * n)) ? 0 : 1;
 }
 
+/* the ID-matte render (ort_render_matte and its views form): what device_render_matte sets up for it, for one simulated lane per
+   thread; features_mode's arguments with by (0 material, 1 object, 2 prim) and slots behind spp, and the five planes of the call.
+   ids and counts are always written; every word of a plane starts as 0xeeeeeeee (the states: 0xdddddddd) */
+static int matte_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp by slots ids.u32 counts.u32 other.u32|- hits.u32|- states.u32|- */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_MATS)) return rc;
+    SimCameras c;
+    if (!sim_cameras(S, a[2], a[3], a + 4, &c)) return 1;
+    const uint32_t spp = (uint32_t)strtoul(a[10], 0, 10), by = (uint32_t)strtoul(a[11], 0, 10), slots = (uint32_t)strtoul(a[12], 0, 10);
+    if (spp == 0u || spp > (1u << 24)) { fprintf(stderr, "spp must be within [1, 1 << 24]\n"); return 1; }
+    if (by > ORT_MATTE_BY_PRIM) { fprintf(stderr, "by must be 0 (material), 1 (object) or 2 (prim)\n"); return 1; }
+    if (slots == 0u || slots > ORT_MAX_MATTE_SLOTS) { fprintf(stderr, "slots must be within [1, %u]\n", ORT_MAX_MATTE_SLOTS); return 1; }
+    if (std::string(a[13]) == "-" || std::string(a[14]) == "-") { fprintf(stderr, "ids and counts are required\n"); return 1; }
+    std::vector<uint32_t> src, table;
+    if (!invert_prim_slots(S.scene->tree, S.sv.info_box, S.sv.info_cyl, S.sv.info_sphere, src)) { fprintf(stderr, "the tree's slot maps are not a bijection onto its shape arrays\n"); return 1; }
+    if (by == ORT_MATTE_BY_OBJECT && !object_ids_from_prim_src(*S.scene, src, table)) { fprintf(stderr, "a triangle lies beyond the scene's meshes\n"); return 1; }
+    if (by == ORT_MATTE_BY_PRIM) table = src;
+    bool want[3];
+    for (int k = 0; k < 3; ++k) want[k] = std::string(a[15 + k]) != "-";
+    const size_t n = c.n;
+    std::vector<uint32_t> ids(n * slots, 0xeeeeeeeeu), counts(n * slots, 0xeeeeeeeeu), other(want[0] ? n : 0, 0xeeeeeeeeu), hits(want[1] ? n : 0, 0xeeeeeeeeu),
+        states(want[2] ? n : 0, 0xddddddddu);
+    ort_render_params &p = c.p;
+    p.spp = spp;
+    MatteIO io{};
+    io.q = sim_query_io(S);
+    io.q.prim_src = by == ORT_MATTE_BY_MATERIAL ? nullptr : table.data();
+    io.ids = ids.data(); io.counts = counts.data();
+    io.other = want[0] ? other.data() : nullptr; io.hits = want[1] ? hits.data() : nullptr; io.states = want[2] ? states.data() : nullptr;
+    io.by = by; io.slots = slots;
+    RenderView rv{};
+    matte_view(p, c.nv, &rv);
+    rv.views = c.view_tab.data();
+    const RenderHot hot = query_hot(S, rv, (size_t)rv.job_count);
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *, uint32_t w) {
+        with_bools([&](auto T) { matte_lane<LF_COUNTERS | lf_if(decltype(T)::value, LF_TABS)>(sv, hot, io, S.tab, stack, 0, w, nullptr); }, S.tab != nullptr);
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return write_bytes(a[13], ids.data(), 4 * n * slots) && write_bytes(a[14], counts.data(), 4 * n * slots) && (!want[0] || write_bytes(a[15], other.data(), 4 * n)) &&
+           (!want[1] || write_bytes(a[16], hits.data(), 4 * n)) && (!want[2] || write_bytes(a[17], states.data(), 4 * n)) ? 0 : 1;
+}
+
 /* the feature render that follows mirrors and glass (ort_render_follow and its views form): what device_render_follow sets up for
    it, for one simulated lane per thread; features_mode's arguments with rr and the cap behind spp and the bounces plane before
    the states */
@@ -1052,6 +1098,7 @@ int main(int argc, char **argv) {
     if (argc == 4 && mode == "--tree-check") return tree_check_mode(argv + 2);
     if (argc == 19 && mode == "--features") return features_mode(argv + 2);
     if (argc == 22 && mode == "--follow") return follow_mode(argv + 2);
+    if (argc == 20 && mode == "--matte") return matte_mode(argv + 2);
     if (argc == 4 && mode == "--unit") return unit_mode(argv[2], argv[3]);
     if (argc == 6 && mode == "--raycast") return raycast_mode(argv + 2);
     if (argc == 7 && mode == "--occluded") return occluded_mode(argv + 2);
@@ -1080,6 +1127,7 @@ int main(int argc, char **argv) {
                         "       host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
                         "       host_sim --features scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|-\n"
                         "       host_sim --follow scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr max_bounces albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- bounces.u32|- states.u32|-\n"
+                        "       host_sim --matte scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp by slots ids.u32 counts.u32 other.u32|- hits.u32|- states.u32|-\n"
                         "       host_sim --light-groups scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr groups.u8 G groups.f32 rgb.f32|- states.u32|-\n"
                         "       host_sim --sample-map scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32 rgb.f32 m2.f32|- states.u32|-\n"
                         "       host_sim --accumulate scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32|- sum.f32 m2.f32|- count.u32 states.u32 rgb.f32|-\n");

@@ -11,6 +11,8 @@ int device_occluded(Scene *, const QueryCall &, const void *, const void *, void
 int device_ambient_occlusion(Scene *, const QueryCall &, const void *, const void *, const void *, uint32_t, void *, void *, void *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_render_features(Scene *, const ort_render_params *, const ort_view *, uint32_t, const QueryCall &, const ort_feature_planes &, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_render_follow(Scene *, const ort_render_params *, const ort_view *, uint32_t, uint32_t, const QueryCall &, const ort_follow_planes &, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
+int device_render_matte(Scene *, const ort_render_params *, const ort_view *, uint32_t, const ort_matte &, const QueryCall &, const ort_matte_planes &, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
+int device_matte_mask(int, bool, const void *, const void *, uint32_t, uint32_t, const uint32_t *, uint32_t, int32_t, int32_t, uint32_t, void *, void *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_denoise(int, bool, const ort_denoise_params &, const ort_denoise_planes &, int32_t, int32_t, uint32_t, void *, void *, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_plan_samples(int, bool, const ort_plan_params &, const ort_plan_planes &, int32_t, int32_t, uint32_t, void *, void *, void *, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_radiance(Scene *, const QueryCall &, const void *, const void *, uint32_t, float, const ort_adaptive *, void *, void *, void *, void *, bool, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }

@@ -5,7 +5,7 @@
    plan_radiance) instead of a render's LaunchPlan.  query=features width= height= x1= y1= [x0= y0= views=N spp= counters=1 fill=1]:
    the QueryPlan of ort_render_features, or with views=N of ort_render_views_features (plan_features), its job count and, with
    fill=1, features_view's fill of the RenderView.  query=follow with the same arguments and rr=: ort_render_follow's (plan_follow,
-   follow_view).  Otherwise
+   follow_view); query=matte with features' arguments: ort_render_matte's (plan_matte, matte_view).  Otherwise
    keys: the SceneTraits and ort_render_params fields by name, policy=pixel|chunk, counters=1, explicit_jobs=1 job_count=N,
    w5_layout_ok=0, views=N (the plan of an ort_render_views batch of N views; its fields are appended to the line), one of
    adaptive=1, groups=1, sample_map=1, accumulate=1 (plan_pixel_jobs for that kind: the plan of ort_render_adaptive,
@@ -181,10 +181,13 @@ int main(int argc, char **argv) {
     if (query) {
         const bool radiance = strcmp(query, "radiance") == 0, counters = (p.flags & ORT_RENDER_COUNTERS) != 0;
         const bool follow = strcmp(query, "follow") == 0; /* plan_follow and follow_view where features has plan_features and features_view */
-        if (follow || strcmp(query, "features") == 0) { /* plan_features over [view][block under the rect][pixel in block]; fill=1: features_view's fill */
+        const bool matte = strcmp(query, "matte") == 0;   /* plan_matte and matte_view */
+        if (follow || matte || strcmp(query, "features") == 0) { /* plan_features over [view][block under the rect][pixel in block]; fill=1: features_view's fill */
             if (p.width <= 0 || p.height <= 0 || p.x0 < 0 || p.y0 < 0 || p.x1 > p.width || p.y1 > p.height || p.x0 >= p.x1 || p.y0 >= p.y1 || view_count < 1 ||
-                view_count > ORT_MAX_VIEWS || p.shard_count > 1) { fprintf(stderr, "launch_plan: query=features|follow width= height= x1= y1= [x0= y0= views=1..%u spp= rr=], no shards\n", ORT_MAX_VIEWS); return 2; }
-            const ort::QueryPlan q = follow ? ort::plan_follow(t, p, (uint32_t)view_count, counters, kn) : ort::plan_features(t, p, (uint32_t)view_count, counters, kn);
+                view_count > ORT_MAX_VIEWS || p.shard_count > 1) { fprintf(stderr, "launch_plan: query=features|follow|matte width= height= x1= y1= [x0= y0= views=1..%u spp= rr=], no shards\n", ORT_MAX_VIEWS); return 2; }
+            const ort::QueryPlan q = follow  ? ort::plan_follow(t, p, (uint32_t)view_count, counters, kn)
+                                     : matte ? ort::plan_matte(t, p, (uint32_t)view_count, counters, kn)
+                                             : ort::plan_features(t, p, (uint32_t)view_count, counters, kn);
             printf("{\"query\": \"%s\", \"count\": %llu, \"view_jobs\": %llu, \"view_count\": %lu, \"counters\": %d, \"diffuse\": %d, \"tabs\": %d, \"grid\": %u, "
                    "\"refill_below\": %d, \"descend_below\": %d, \"job_batch\": %u, \"batch_until\": %llu, \"max_blocks\": %u, \"tab_flags\": %u}\n",
                    query, ort::feature_view_jobs(p) * view_count, ort::feature_view_jobs(p), view_count, q.counters, q.diffuse, q.tabs, q.grid, q.refill_below, q.descend_below,
@@ -192,6 +195,7 @@ int main(int argc, char **argv) {
             if (fill) {
                 FillView rv{};
                 if (follow) ort::follow_view(p, (uint32_t)view_count, &rv);
+                else if (matte) ort::matte_view(p, (uint32_t)view_count, &rv);
                 else ort::features_view(p, (uint32_t)view_count, &rv);
                 rv.job_batch = q.job_batch; rv.batch_until = q.batch_until; rv.refill_below = q.refill_below; rv.descend_below = q.descend_below; /* as launch_planned sets them */
                 auto print = [](const char *name, auto v) {
