@@ -961,7 +961,7 @@ ORT_D void prologue_tests(const SceneView &sv, const float4 *tab, V3 org, V3 dir
  * scene the walks took 10 % of the launch (one lane walking, 63 waiting) before this. */
 ORT_D float wave_bcast(float v, int lane) { return om_bits_f32((uint32_t)__builtin_amdgcn_readlane((int)om_f32_bits(v), lane)); }
 ORT_D uint32_t wave_bcast(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
-ORT_D uint32_t rank_in(unsigned long long mask) { /* set bits of mask below this lane */
+ORT_D uint32_t lane_rank(unsigned long long mask) { /* set bits of mask below this lane */
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
@@ -975,7 +975,7 @@ ORT_D bool ref_raycast_bfs_wave(const SceneView &sv, const int leader, V3 org_l,
     V3 inv_d = mk(wave_bcast(inv_l.x, leader), wave_bcast(inv_l.y, leader), wave_bcast(inv_l.z, leader));
     asm volatile("" : "+v"(org.x), "+v"(org.y), "+v"(org.z), "+v"(dir.x), "+v"(dir.y), "+v"(dir.z), "+v"(inv_d.x), "+v"(inv_d.y), "+v"(inv_d.z));
     const unsigned long long active = __ballot(true);
-    const uint32_t n_active = (uint32_t)__popcll(active), rank = rank_in(active);
+    const uint32_t n_active = (uint32_t)__popcll(active), rank = lane_rank(active);
     const bool is_leader = ORT_LANE() == leader;
     /* wave-uniform state of the walk */
     float best_t = 3.402823466e+38f;
@@ -1146,9 +1146,6 @@ ORT_D V3 view_aperture_point(const ViewCamera &cam, float aperture, float cs, fl
     return sub(add(add(cam.p, scale(aperture * cs, cam.x)), scale(aperture * sn, cam.y)), scale(0.1f, cam.z));
 }
 
-/* Advance the lane's path state machine until it has produced the next ray (returns true; the ray
-   is P.org / P.dir) or has run out of work (returns false).  On entry with P.ps == PS_HIT, h holds
-   the resolved closest hit of the ray produced by the previous call. */
 #ifndef ORT_HOST_SIM
 /* Job indices for the lanes of this wave that need one now (the active lanes).  The wave draws them from next_job in
    batches -- one returned device-scope atomic, a few microseconds that the whole wave waits for, per job_batch jobs
@@ -1163,7 +1160,7 @@ ORT_D unsigned long long draw_job(const RenderHot &rv, unsigned long long *pool)
     if (!pool) return ORT_NEXT_JOB(rv.c->next_job);
     const unsigned long long mask = __ballot(true);
     const uint32_t n = (uint32_t)__popcll(mask);
-    const uint32_t rank = (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    const uint32_t rank = lane_rank(mask);
     const unsigned long long next = ((volatile unsigned long long *)pool)[0], end = ((volatile unsigned long long *)pool)[1];
     const uint32_t avail = (uint32_t)(end - next);
     unsigned long long j = next + rank;
@@ -1242,340 +1239,529 @@ ORT_D bool adaptive_stop(V3 C, float Q, uint32_t n, float tolerance, float lum_f
     return vm <= thr * thr;
 }
 
+/* ---- produce_ray's steps ---------------------------------------------------------------------------------------------
+ * One pass of the lane state machine, cut where its concerns meet: shade the hit that arrived (shade_arrival), end a job
+ * (end_job), draw the next one (take_job), start a pixel (begin_pixel), draw what a new sample starts from (primary_sample) and
+ * compose the next ray (compose_ray_diffuse, compose_ray_all_lobes).  Every step is a template over produce_ray's flag word and
+ * reads back only the bits it uses; produce_ray (below them) keeps the loop and the control flow. */
+
+/* the frame's one camera (sv.cam) in the form of a view's, and its focal length.  VIEWS: unused; every lane reads its view's
+   camera where it needs it (load_view_camera) */
+struct SceneCamera { ViewCamera v; float focal_length; };
+ORT_D SceneCamera scene_camera(const SceneView &sv) {
+    SceneCamera cam;
+    cam.v.p = mk(sv.cam[0], sv.cam[1], sv.cam[2]);
+    cam.v.x = mk(sv.cam[3], sv.cam[4], sv.cam[5]);
+    cam.v.y = mk(sv.cam[6], sv.cam[7], sv.cam[8]);
+    cam.v.z = mk(sv.cam[9], sv.cam[10], sv.cam[11]);
+    cam.focal_length = len(sub(cam.v.p, mk(0, 0, 0.2f))); /* ray.cpp:1198 */
+    return cam;
+}
+constexpr float kAperture = 0.1f; /* ray.cpp:1199 */
+
+/* what one pass hands from step to step */
+struct RayPass {
+    bool bounce = false;
+    float angle = 0.0f; /* the pass's one angle: the lobe's azimuth (bounce), the aperture angle or HEMI's azimuth (a new sample) */
+    BrdfDraw draw;
+    Mat m;
+    V3 n, focal;
+    V3 ray_o = {0, 0, 0}, ray_d = {0, 0, 0}; /* RAYS: the sample's ray as the caller gave it (HEMI: the point and its normal) */
+    float hemi_c = 0.0f;                     /* HEMI: the drawn direction's cosine to the normal */
+};
+
+/* what a lane that asked for a job got */
+enum JobTake { JOB_TAKEN, JOB_SKIPPED /* nothing to run in it: ask again */, JOB_NONE_LEFT, JOB_PARKED /* ray exchange: a parked path comes first */ };
+
+/* PS_HIT, a traversal has finished: ray.cpp:817 then :1251-1277 (primary) or :1355-1421 (bounce).  Returns whether the path
+   bounces: then s.n, s.m, s.draw and s.angle are the bounce's.  Otherwise the sample has ended: P.sample counts it and (ADAPT) the
+   stopping rule has been asked where a check is due */
+template <uint32_t F>
+ORT_D bool shade_arrival(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, uint32_t spp_u,
+                         AdaptState *A, RayPass &s) {
+    constexpr bool COUNTERS = F & LF_COUNTERS, DIFFUSE = F & LF_DIFFUSE, TABS = F & LF_TABS;
+    constexpr bool ADAPT = F & LF_ADAPT, GROUPS = F & LF_GROUPS, SPPMAP = F & LF_SPPMAP;
+    bool alive = true;
+    const uint32_t hit_mat = h.hit_mat; /* resolve_hit: 0 = nothing hit */
+    s.n = normalize(h.hit_n);
+    ORT_SIM_RAY_HOOK((int)(P.pxy & 0xffffu), (int)(P.pxy >> 16), P.org, P.dir, h.best_t, s.n, hit_mat);
+    if (COUNTERS && P.primary) c.paths++;
+    if (hit_mat) {
+        if (TABS) s.m = load_mat(tab + kTabMats, hit_mat);
+        else s.m = load_mat(sv.materials, hit_mat);
+    }
+    if (!hit_mat) {
+        alive = false; /* bounce miss: ray.cpp:1418-1421; primary miss: undefined in the reference, defined: terminate */
+    } else if (s.m.is_light) {
+        /* ray.cpp:1254-1259 (primary: unweighted, unchecked) / :1358-1371 (bounce: dropped if not finite) */
+        V3 e = P.primary ? s.m.emit : had(P.weight, s.m.emit);
+        if (P.primary || (!isnan3(e) && !isinf3(e))) {
+            P.color = add(P.color, e);
+            if constexpr (ADAPT || SPPMAP) { const float y = adaptive_luminance(e); A->q = A->q + y * y; }
+            if constexpr (GROUPS) {
+                const uint32_t g = rv.c->group_of_material[hit_mat];
+                if (g < rv.c->group_count) {
+                    float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
+                    q[0] = q[0] + e.x; q[1] = q[1] + e.y; q[2] = q[2] + e.z;
+                }
+            }
+        }
+        alive = false;
+    } else {
+        if (P.primary) {
+            if (len2(s.m.kd) > 0.0f) P.weight = had(P.weight, s.m.kd); /* ray.cpp:1267-1270 */
+        } else {
+            /* ray.cpp:1374-1405: pdf and BSDF with the NEW surface's normal and material, the OLD wo (sic) */
+            if (DIFFUSE) {
+                float p = pdf_brdf<true>(s.n, P.dir, P.wo, kRoughness, s.m) * rv.rr;
+                if (p > 0.000001f) {
+                    V3 f = eval_scattering<true>(s.n, P.dir, P.wo, s.m, kRoughness, h.best_t);
+                    P.weight = had(divs(f, p), P.weight);
+                }
+            } else { /* all lobes: the two calls fused, their common terms evaluated once (ort_device.h) */
+                V3 f = mk(0, 0, 0);
+                const float p = pdf_eval_scattering(s.n, P.dir, P.wo, s.m, kRoughness, h.best_t, rv.rr, f);
+                if (p > 0.000001f) P.weight = had(divs(f, p), P.weight);
+            }
+            P.wo = neg(P.dir);
+        }
+        P.org = add(P.org, scale(h.best_t - kEps, P.dir)); /* ray.cpp:1262,1411 */
+    }
+    P.primary = false;
+    /* ray.cpp:1280: the roulette draw happens only while the path is alive */
+    const bool bounce = alive && rng_01(P.rng) < rv.rr;
+    if (bounce) {
+        /* sample_random_lights (ray.cpp:537-601): result unused, RNG advances */
+        rng_step(P.rng);
+        if (sv.light_count) {
+            /* one light: x % 1 == 0.  The count is wave-uniform, so this is a scalar branch around the per-lane remainder */
+            uint32_t li = 0u;
+            if (sv.light_count != 1u) li = P.rng % sv.light_count;
+            uint32_t is_sphere;
+            if (TABS) is_sphere = ((const uint32_t *)tab)[4 * kTabLights + li];
+            else is_sphere = sv.light_is_sphere[li];
+            if (is_sphere) { rng_step(P.rng); rng_step(P.rng); rng_step(P.rng); rng_step(P.rng); }
+        }
+        ORT_UTIL(sv, 6, true);
+        s.draw = sample_brdf_draw<DIFFUSE>(P.rng, kRoughness, s.m);
+        s.angle = s.draw.phi;
+    } else {
+        P.sample++;
+        P.ps = PS_SAMPLE;
+        if constexpr (ADAPT) {
+            /* a check runs after sample n when n >= min_spp, n < max_spp and (n - min_spp) % check_every == 0: A->next
+               counts up to it, so nothing is divided per sample */
+            if (P.sample == A->next && P.sample < spp_u) {
+                const uint32_t after = A->next + rv.c->ad_check_every;
+                A->next = after < A->next ? 0xffffffffu : after; /* beyond 2^32: never again */
+                if (adaptive_stop(P.color, A->q, P.sample, rv.c->ad_tolerance, rv.c->ad_floor)) A->next = 0u;
+            }
+        }
+    }
+    return bounce;
+}
+
+/* the samples of the job in hand, and whether the sample that just ended was its last */
+template <uint32_t F>
+ORT_D uint32_t job_length(const PathState &P, uint32_t spp_u, const AdaptState *A) {
+    if constexpr (F & LF_SPPMAP) return A->next; /* the n of the job in hand; with none in hand (P.ps is not PS_SAMPLE) whatever the word holds decides nothing */
+    else return (F & LF_IMPLICIT) ? spp_u : P.spp;
+}
+template <uint32_t F>
+ORT_D bool job_over(const PathState &P, uint32_t job_spp, const AdaptState *A) {
+    if constexpr (F & LF_ADAPT) return P.ps == PS_SAMPLE && (P.sample == job_spp || A->next == 0u); /* ... or the rule said stop */
+    else return P.ps == PS_SAMPLE && P.sample == job_spp;
+}
+
+/* end_job's write-backs.  First what the job leaves (ray.cpp:1428), the mean of its samples.  ACCUM: the pixel's words, sums
+   first; the mean over all its samples, this call's and the earlier ones' */
+template <uint32_t F>
+ORT_D V3 job_mean(const RenderHot &rv, const PathState &P, uint32_t job_spp) {
+    if constexpr (F & LF_ACCUM) {
+        const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
+        const uint32_t total = rv.c->ad_spp[at] + job_spp; /* n0 + add <= 1 << 24: exact in float */
+        float *q = rv.c->acc_sum + 3u * at;
+        q[0] = P.color.x; q[1] = P.color.y; q[2] = P.color.z;
+        rv.c->ad_spp[at] = total;
+        return divs(P.color, (float)total);
+    } else {
+        return divs(P.color, (float)((F & LF_ADAPT) ? P.sample : job_spp));
+    }
+}
+/* RAYS: the ray's record */
+template <uint32_t F>
+ORT_D void write_ray_record(const RenderHot &rv, const PathState &P, const AdaptState *A, V3 o) {
+    const size_t ray = ((size_t)P.pxy << 32) | P.job_index;
+    float *p = rv.c->out + 3u * ray;
+    p[0] = o.x; p[1] = o.y; p[2] = o.z;
+    if (rv.c->final_states) rv.c->final_states[ray] = P.rng;
+    if constexpr (F & LF_ADAPT) {
+        if (rv.c->ad_spp) rv.c->ad_spp[ray] = P.sample;
+        if (rv.c->ad_m2) rv.c->ad_m2[ray] = A->q;
+    }
+}
+/* the pixel kinds: the pixel's colour where its kind keeps it */
+template <uint32_t F>
+ORT_D void write_pixel(const RenderHot &rv, const PathState &P, uint32_t job_spp, V3 o) {
+    const uint32_t px = P.pxy & 0xffffu, py = P.pxy >> 16;
+    if constexpr (F & LF_GROUPS) { /* JOBS_PIXEL: the G sums become means where they stand; the frame and the states if asked for */
+        const float fs = (float)job_spp;
+        for (uint32_t g = 0; g < rv.c->group_count; ++g) {
+            float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
+            q[0] = q[0] / fs; q[1] = q[1] / fs; q[2] = q[2] / fs;
+        }
+        if (rv.c->out) { float *p = view_pixel_ptr(rv, P.job_index, 0u, px, py); p[0] = o.x; p[1] = o.y; p[2] = o.z; }
+        if (rv.c->final_states) rv.c->final_states[plane_index(rv, P.job_index, px, py)] = P.rng;
+    } else if constexpr (F & LF_ACCUM) { /* the frame is an optional plane here */
+        if (rv.c->out) { float *p = view_pixel_ptr(rv, P.job_index, 0u, px, py); p[0] = o.x; p[1] = o.y; p[2] = o.z; }
+    } else {
+        float *p;
+        if constexpr (F & LF_VIEWS) p = view_pixel_ptr(rv, P.job_index, P.jyp >> 16, px, py);
+        else p = pixel_ptr(rv, P.jyp >> 16, px, py);
+        p[0] = o.x; p[1] = o.y; p[2] = o.z;
+    }
+}
+/* ADAPT, SPPMAP: the pixel's words of its view's planes, view_count frames of W * H each (JOBS_PIXEL) */
+template <uint32_t F>
+ORT_D void write_pixel_planes(const RenderHot &rv, const PathState &P, const AdaptState *A) {
+    if constexpr (F & LF_ADAPT) {
+        const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
+        if (rv.c->ad_spp) rv.c->ad_spp[at] = P.sample;
+        if (rv.c->ad_m2) rv.c->ad_m2[at] = A->q;
+        if (rv.c->final_states) rv.c->final_states[at] = P.rng;
+    }
+    if constexpr (F & LF_SPPMAP) { /* likewise, without the sample count: the caller holds it */
+        const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
+        if (rv.c->ad_m2) rv.c->ad_m2[at] = A->q;
+        if ((F & LF_ACCUM) || rv.c->final_states) rv.c->final_states[at] = P.rng; /* ACCUM: the state is a required plane */
+    }
+}
+/* a tile job: on to the rect's next pixel, or the job has ended with its last */
+ORT_D void next_tile_pixel(const RenderHot &rv, PathState &P) {
+    uint32_t px = P.pxy & 0xffffu, py = P.pxy >> 16;
+    px++;
+    if (px == (P.jxx >> 16)) { px = P.jxx & 0xffffu; py++; }
+    P.pxy = px | (py << 16);
+    if (py == (P.jyp & 0xffffu)) {
+        if (rv.mode == JOBS_EXPLICIT && rv.c->final_states) rv.c->final_states[P.job_index] = P.rng;
+        P.ps = PS_NEED_JOB;
+    } else {
+        P.ps = PS_PIXEL;
+    }
+}
+
+/* PS_SAMPLE with the job's last sample behind it: what the job computed goes where its kind keeps it, and the lane asks for a
+   new job or (a tile job) goes on to its next pixel */
+template <uint32_t F>
+ORT_D void end_job(const RenderHot &rv, PathState &P, uint32_t job_spp, const AdaptState *A) {
+    const V3 o = job_mean<F>(rv, P, job_spp);
+    if constexpr (F & LF_RAYS) {
+        write_ray_record<F>(rv, P, A, o);
+        P.ps = PS_NEED_JOB;
+    } else {
+        write_pixel<F>(rv, P, job_spp, o);
+        write_pixel_planes<F>(rv, P, A);
+        if (F & LF_IMPLICIT) P.ps = PS_NEED_JOB; /* a one-pixel job ends with its pixel */
+        else next_tile_pixel(rv, P);
+    }
+}
+
+/* take_job's decodes, one per job space; false: the job holds nothing to run.
+   RAYS: job j is entry j of the caller's rays.  A ray outside the per-ray domain (in_query_domain) is answered here, NaN and its
+   seed, without a traversal */
+template <uint32_t F>
+ORT_D bool decode_ray_job(const RenderHot &rv, PathState &P, unsigned long long j) {
+    const Ray6 r = load_ray(rv.c->rays, j);
+    const uint32_t seed = rv.c->seeds[j];
+    if (!in_query_domain(r.o, r.d)) {
+        float *p = rv.c->out + 3u * (size_t)j;
+        p[0] = p[1] = p[2] = om_bits_f32(0x7fc00000u);
+        if (rv.c->final_states) rv.c->final_states[j] = seed;
+        if constexpr (F & LF_ADAPT) {
+            if (rv.c->ad_spp) rv.c->ad_spp[j] = 0u;
+            if (rv.c->ad_m2) rv.c->ad_m2[j] = 0.0f;
+        }
+        return false;
+    }
+    P.job_index = (uint32_t)j;
+    P.pxy = (uint32_t)(j >> 32);
+    P.rng = seed ? seed : 1u; /* as job_seed: a zero xorshift state never leaves zero */
+    return true;
+}
+/* JOBS_EXPLICIT: job j is the caller's tile j */
+ORT_D bool decode_tile_job(const RenderHot &rv, PathState &P, unsigned long long j) {
+    ort_tile_job jb = rv.c->jobs[j];
+    P.job_index = (uint32_t)j;
+    P.jxx = (uint32_t)jb.x0 | ((uint32_t)jb.x1 << 16);
+    P.jyp = (uint32_t)jb.y1;
+    P.pxy = (uint32_t)jb.x0 | ((uint32_t)jb.y0 << 16);
+    P.rng = jb.rng_state; P.spp = jb.spp;
+    if (jb.x1 <= jb.x0 || jb.y1 <= jb.y0) { /* empty rect: the reference loops zero times */
+        if (rv.c->final_states) rv.c->final_states[P.job_index] = P.rng;
+        return false;
+    }
+    return true;
+}
+/* the implicit job space: [chunk k][my 8x8 block b][pixel-in-block p], one pixel a job.  VIEWS: [view][the view's job space].
+   SPPMAP, ACCUM: the job's length goes to A->next (no samples: no job), the samples the pixel has had to acc_n0 */
+template <uint32_t F>
+ORT_D bool decode_pixel_job(const RenderHot &rv, PathState &P, unsigned long long j, uint32_t spp_u, AdaptState *A, uint32_t &acc_n0) {
+    constexpr bool IMPLICIT = F & LF_IMPLICIT, VIEWS = F & LF_VIEWS, SPPMAP = F & LF_SPPMAP, ACCUM = F & LF_ACCUM;
+    [[maybe_unused]] uint32_t view_seed = 0u;
+    if constexpr (VIEWS) { /* the view's seed sits in the fourth word of its table entry */
+        P.job_index = (uint32_t)(j / rv.c->view_jobs);
+        j = j % rv.c->view_jobs;
+        view_seed = om_f32_bits(rv.c->views[4u * (size_t)P.job_index].w);
+    }
+    unsigned long long per_chunk = (unsigned long long)rv.c->my_blocks * 64ull;
+    uint32_t k, lb, pin; /* chunk, local block, pixel in block */
+    if (rv.c->block_major) {
+        const uint32_t per_block = rv.c->nchunks * 64u;
+        const uint32_t within = (uint32_t)(j % per_block);
+        lb = (uint32_t)(j / per_block);
+        k = within >> 6;
+        pin = within & 63u;
+    } else {
+        k = (uint32_t)(j / per_chunk);
+        const uint32_t rem = (uint32_t)(j % per_chunk);
+        lb = rem >> 6;
+        pin = rem & 63u;
+    }
+    const BlockPixel bp = block_pixel(rv, rv.c->shard_index + lb * rv.c->shard_count, pin);
+    if (bp.outside) return false;
+    const int x = bp.x, y = bp.y;
+    if constexpr (SPPMAP) { /* the job's length, one word of the caller's map, cut at the cap */
+        const size_t at = plane_index(rv, P.job_index, (uint32_t)x, (uint32_t)y);
+        uint32_t asked;
+        if constexpr (ACCUM) asked = rv.c->sample_map ? rv.c->sample_map[at] : spp_u;
+        else asked = rv.c->sample_map[at];
+        uint32_t n = asked < spp_u ? asked : spp_u;
+        if constexpr (ACCUM) { /* ... and at what keeps the pixel's total within 1 << 24 */
+            acc_n0 = rv.c->ad_spp[at];
+            const uint32_t room = (1u << 24) - (acc_n0 < (1u << 24) ? acc_n0 : (1u << 24));
+            n = n < room ? n : room;
+        }
+        if (n == 0u) return false;
+        A->next = n;
+    }
+    uint32_t pix = (uint32_t)(y * rv.W + x), seed;
+    if constexpr (VIEWS) seed = view_seed;
+    else seed = rv.c->seed;
+    if (!IMPLICIT) P.jxx = (uint32_t)x | ((uint32_t)(x + 1) << 16);
+    P.pxy = (uint32_t)x | ((uint32_t)y << 16);
+    if (rv.mode == JOBS_PIXEL) {
+        P.rng = job_seed(seed, pix);
+        if (!IMPLICIT) P.spp = rv.c->spp;
+        P.jyp = (uint32_t)(y + 1);
+    } else {
+        P.rng = job_seed(seed, k * (uint32_t)(rv.W * rv.H) + pix);
+        if (!IMPLICIT) P.spp = rv.c->chunk;
+        P.jyp = (uint32_t)(y + 1) | (k << 16);
+    }
+    return true;
+}
+
+/* PS_NEED_JOB: draw_job and the decode of what it drew.  JOB_TAKEN leaves the lane at PS_PIXEL, JOB_NONE_LEFT at PS_DONE */
+template <uint32_t F>
+ORT_D JobTake take_job(const RenderHot &rv, PathState &P, uint32_t spp_u, uint32_t *late_flag, bool no_new_job, unsigned long long *pool, AdaptState *A,
+                       uint32_t &acc_n0) {
+    constexpr bool IMPLICIT = F & LF_IMPLICIT;
+    if (no_new_job) return JOB_PARKED; /* ray exchange, end of the launch: this lane takes a parked path first (pt_lane_x) */
+    const unsigned long long j = draw_job(rv, pool);
+    if (j >= rv.c->job_count) { P.ps = PS_DONE; return JOB_NONE_LEFT; }
+    if (IMPLICIT && late_flag && j >= rv.c->endgame_from) *late_flag = 1u; /* ray exchange: the launch is near its end (pt_lane_x) */
+    bool taken;
+    if constexpr (F & LF_RAYS) {
+        taken = decode_ray_job<F>(rv, P, j);
+    } else {
+        if (!IMPLICIT && rv.mode == JOBS_EXPLICIT) taken = decode_tile_job(rv, P, j);
+        else taken = decode_pixel_job<F>(rv, P, j, spp_u, A, acc_n0);
+    }
+    if (!taken) return JOB_SKIPPED;
+    P.ps = PS_PIXEL;
+    return JOB_TAKEN;
+}
+
+/* PS_PIXEL: the pixel's sums and counts at zero (ray.cpp:1211), or (ACCUM, a pixel that has had acc_n0 samples) as the planes hold
+   them; the pixel's focal point into the lane's cache */
+template <uint32_t F>
+ORT_D void begin_pixel(const RenderHot &rv, PathState &P, const SceneCamera &cam, AdaptState *A, uint32_t acc_n0, float *focal_cache, int focal_stride) {
+    ORT_SIM_PIXEL_HOOK((int)(P.pxy & 0xffffu), (int)(P.pxy >> 16), P.rng);
+    P.color = mk(0, 0, 0); /* ray.cpp:1211 */
+    P.sample = 0;
+    P.ps = PS_SAMPLE;
+    if constexpr (F & LF_ADAPT) { A->q = 0.0f; A->next = rv.c->ad_min_spp; }
+    if constexpr (F & LF_SPPMAP) A->q = 0.0f;
+    if constexpr (F & LF_ACCUM) {
+        if (acc_n0) { /* a continued pixel: its stream and its sums as the planes hold them, judged no more than a material is */
+            const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
+            const uint32_t state = rv.c->final_states[at];
+            P.rng = state ? state : 1u; /* as job_seed: a zero xorshift state never leaves zero */
+            /* + (+0): the call is chained one-sample renders whose colours are added to C, and a colour is never -0,
+               so a -0 the caller stored is +0 after the first of them whatever it holds; every other value stands */
+            const float *q = rv.c->acc_sum + 3u * at;
+            P.color = mk(q[0] + 0.0f, q[1] + 0.0f, q[2] + 0.0f);
+            if (rv.c->ad_m2) A->q = rv.c->ad_m2[at] + 0.0f;
+        }
+    }
+    if constexpr (F & LF_GROUPS) {
+        for (uint32_t g = 0; g < rv.c->group_count; ++g) {
+            float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
+            q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
+        }
+    }
+    if (focal_cache) { /* the pixel's focal point, once per pixel (persistent kernel: three floats of LDS per lane) */
+        V3 f;
+        if constexpr (F & LF_VIEWS) f = view_focal_point(rv, P.pxy, load_view_camera(rv, P.job_index));
+        else f = focal_point(rv, P.pxy, cam.v.p, cam.v.x, cam.v.y, cam.v.z, cam.focal_length);
+        focal_cache[0] = f.x; focal_cache[focal_stride] = f.y; focal_cache[2 * focal_stride] = f.z;
+    }
+}
+
+/* what a lane that starts a sample draws before the pass's one sin/cos: the aperture angle (ray.cpp:1232), beside the pixel's
+   focal point; RAYS: the caller's ray, and no angle; HEMI: the direction's cosine and azimuth */
+template <uint32_t F>
+ORT_D void primary_sample(const RenderHot &rv, PathState &P, const SceneCamera &cam, const float *focal_cache, int focal_stride, RayPass &s) {
+    if constexpr (F & LF_RAYS) { /* the caller's ray; no aperture, so no angle is drawn */
+        const Ray6 r = load_ray(rv.c->rays, ((unsigned long long)P.pxy << 32) | P.job_index);
+        s.ray_o = r.o;
+        s.ray_d = r.d;
+        if constexpr (F & LF_HEMI) { /* the diffuse lobe's draw (sample_brdf_draw without the choice); its azimuth is the pass's one angle */
+            const float e0 = rng_01(P.rng), e1 = rng_01(P.rng);
+            s.hemi_c = __builtin_sqrtf(e0); /* ray.cpp:1123 */
+            s.angle = 2.0f * kPi * e1;
+        }
+    } else {
+        /* ray.cpp:1215-1221: point on the focal plane through the pixel centre: a function of the pixel alone,
+           read back from the per-lane cache or (wavefront mode) recomputed -- same expressions, same bits */
+        if constexpr (F & LF_VIEWS) {
+            s.focal = focal_cache ? mk(focal_cache[0], focal_cache[focal_stride], focal_cache[2 * focal_stride])
+                                  : view_focal_point(rv, P.pxy, load_view_camera(rv, P.job_index));
+        } else {
+            s.focal = focal_cache ? mk(focal_cache[0], focal_cache[focal_stride], focal_cache[2 * focal_stride])
+                                  : focal_point(rv, P.pxy, cam.v.p, cam.v.x, cam.v.y, cam.v.z, cam.focal_length);
+        }
+        s.angle = rng_between(P.rng, 0.0f, 2 * kPi); /* ray.cpp:1232 */
+    }
+}
+
+/* where a new sample's ray starts, ray.cpp:1233-1239: the caller's origin (RAYS), or the point of the aperture at the pass's angle */
+template <uint32_t F>
+ORT_D V3 sample_origin(const RenderHot &rv, const PathState &P, const SceneCamera &cam, const RayPass &s, float cs, float sn) {
+    if constexpr (F & LF_RAYS) {
+        return s.ray_o;
+    } else {
+        if constexpr (F & LF_VIEWS) return view_aperture_point(load_view_camera(rv, P.job_index), kAperture, cs, sn);
+        else return view_aperture_point(cam.v, kAperture, cs, sn);
+    }
+}
+/* a new sample's ray is composed: the path starts */
+ORT_D void begin_path(PathState &P, V3 ap) {
+    P.org = ap;
+    P.weight = mk(1, 1, 1);
+    P.primary = true;
+    P.ps = PS_HIT;
+}
+
+/* The next ray, from cos/sin of the pass's angle.  DIFFUSE: the leaner flavour has the registers for the wider merge; the
+   all-lobes one spills on it.  Bounce lanes normalise twice here (the surface normal again, ray.cpp:1069, and the sampled
+   direction, :1158) and so do camera lanes (the ray direction, :1240, and -- sic -- the direction again for wo, :1241): two
+   converged evaluations instead of four divergent ones */
+template <uint32_t F>
+ORT_D void compose_ray_diffuse(const RenderHot &rv, PathState &P, const SceneCamera &cam, const RayPass &s, float cs, float sn) {
+    constexpr bool RAYS = F & LF_RAYS, HEMI = F & LF_HEMI;
+    V3 ap = mk(0, 0, 0);
+    if (!s.bounce) ap = sample_origin<F>(rv, P, cam, s, cs, sn); /* ray.cpp:1233-1239 */
+    const V3 unit1 = normalize(s.bounce ? s.n : (RAYS ? s.ray_d : sub(s.focal, ap)));
+    bool is_trans = false;
+    V3 raw = unit1;
+    if (s.bounce) raw = sample_brdf_finish<false, true>(s.n, unit1, P.wo, s.m, s.draw, cs, sn, is_trans);
+    if constexpr (HEMI) { if (!s.bounce) raw = sample_lobe_n(unit1, s.hemi_c, cs, sn); } /* unit1 = normalize(n), as sample_lobe's */
+    const V3 unit2 = normalize(raw);
+    if (s.bounce) {
+        if (is_trans) P.org = add(P.org, scale(2.0f * kEps, P.dir)); /* ray.cpp:1345-1348: dir is still the arriving direction */
+        P.dir = unit2;
+    } else {
+        if constexpr (HEMI) { /* d; wo = -normalize(d), as RAYS for the ray (p, d) */
+            P.dir = unit2;
+            P.wo = neg(normalize(unit2));
+        } else if constexpr (RAYS) { /* the direction as given; wo = -normalize(d) */
+            P.dir = s.ray_d;
+            P.wo = neg(unit1);
+        } else {
+            P.dir = unit1;
+            P.wo = neg(unit2);
+        }
+        begin_path(P, ap);
+    }
+}
+/* all lobes: both branches end by normalising a direction (ray.cpp:1158 / :1240): one converged evaluation */
+template <uint32_t F>
+ORT_D void compose_ray_all_lobes(const RenderHot &rv, PathState &P, const SceneCamera &cam, const RayPass &s, float cs, float sn) {
+    constexpr bool RAYS = F & LF_RAYS, HEMI = F & LF_HEMI;
+    V3 raw, ap = mk(0, 0, 0);
+    bool is_trans = false;
+    if (s.bounce) {
+        raw = sample_brdf_finish<false>(s.n, normalize(s.n), P.wo, s.m, s.draw, cs, sn, is_trans);
+    } else {
+        /* ray.cpp:1233-1246 */
+        ap = sample_origin<F>(rv, P, cam, s, cs, sn);
+        if constexpr (HEMI) raw = sample_lobe_n(normalize(s.ray_d), s.hemi_c, cs, sn);
+        else if constexpr (RAYS) raw = s.ray_d;
+        else raw = sub(s.focal, ap);
+    }
+    const V3 unit = normalize(raw);
+    if (s.bounce) {
+        if (is_trans) P.org = add(P.org, scale(2.0f * kEps, P.dir)); /* ray.cpp:1345-1348: dir is still the arriving direction */
+        P.dir = unit;
+    } else {
+        if constexpr (RAYS && !HEMI) { /* the direction as given; wo = -normalize(d) */
+            P.dir = raw;
+            P.wo = neg(unit);
+        } else { /* HEMI: d = unit, and wo = -normalize(d) as RAYS for the ray (p, d) */
+            P.dir = unit;
+            P.wo = neg(normalize(P.dir)); /* normalised again (sic) */
+        }
+        begin_path(P, ap);
+    }
+}
+
+/* Advance the lane's path state machine until it has produced the next ray (returns true; the ray
+   is P.org / P.dir) or has run out of work (returns false).  On entry with P.ps == PS_HIT, h holds
+   the resolved closest hit of the ray produced by the previous call. */
 template <uint32_t F> /* IMPLICIT ... ACCUM: at their names, LF_IMPLICIT ... LF_ACCUM */
 ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, Prof &pr,
                        float *focal_cache = nullptr, int focal_stride = 0, uint32_t spp_u = 0, uint32_t *late_flag = nullptr, bool no_new_job = false,
                        unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
     static_assert(flavour_ok(F, LF_OF_PRODUCE_RAY), "see flavour_ok");
-    constexpr bool COUNTERS = F & LF_COUNTERS, DIFFUSE = F & LF_DIFFUSE, TABS = F & LF_TABS, IMPLICIT = F & LF_IMPLICIT, VIEWS = F & LF_VIEWS;
-    constexpr bool RAYS = F & LF_RAYS, ADAPT = F & LF_ADAPT, HEMI = F & LF_HEMI, GROUPS = F & LF_GROUPS, SPPMAP = F & LF_SPPMAP;
-    constexpr bool ACCUM = F & LF_ACCUM;
-    /* VIEWS: unused; every lane reads its view's camera where it needs it (load_view_camera) */
-    const V3 cam_p = mk(sv.cam[0], sv.cam[1], sv.cam[2]);
-    const V3 cam_x = mk(sv.cam[3], sv.cam[4], sv.cam[5]);
-    const V3 cam_y = mk(sv.cam[6], sv.cam[7], sv.cam[8]);
-    const V3 cam_z = mk(sv.cam[9], sv.cam[10], sv.cam[11]);
-    const float focal_length = len(sub(cam_p, mk(0, 0, 0.2f))); /* ray.cpp:1198 */
-    const float aperture = 0.1f;                                /* ray.cpp:1199 */
-
+    constexpr bool COUNTERS = F & LF_COUNTERS, DIFFUSE = F & LF_DIFFUSE, SPPMAP = F & LF_SPPMAP;
+    const SceneCamera cam = scene_camera(sv);
     while (P.ps != PS_DONE) {
         ORT_UTIL(sv, 5, true);
         ORT_PHASE(pr, sv, 8, true);
-        bool bounce = false;
-        float angle = 0.0f;
-        BrdfDraw draw;
-        Mat m;
-        V3 n, focal;
-        V3 ray_o = mk(0, 0, 0), ray_d = mk(0, 0, 0); /* RAYS: the sample's ray as the caller gave it (HEMI: the point and its normal) */
-        [[maybe_unused]] float hemi_c = 0.0f;        /* HEMI: the drawn direction's cosine to the normal */
+        RayPass s;
         if (P.ps == PS_HIT) {
-            /* a traversal has finished: ray.cpp:817 then :1251-1277 (primary) or :1355-1421 (bounce) */
-            bool alive = true;
-            const uint32_t hit_mat = h.hit_mat; /* resolve_hit: 0 = nothing hit */
-            n = normalize(h.hit_n);
-            ORT_SIM_RAY_HOOK((int)(P.pxy & 0xffffu), (int)(P.pxy >> 16), P.org, P.dir, h.best_t, n, hit_mat);
-            if (COUNTERS && P.primary) c.paths++;
-            if (hit_mat) {
-                if (TABS) m = load_mat(tab + kTabMats, hit_mat);
-                else m = load_mat(sv.materials, hit_mat);
-            }
-            if (!hit_mat) {
-                alive = false; /* bounce miss: ray.cpp:1418-1421; primary miss: undefined in the reference, defined: terminate */
-            } else if (m.is_light) {
-                /* ray.cpp:1254-1259 (primary: unweighted, unchecked) / :1358-1371 (bounce: dropped if not finite) */
-                V3 e = P.primary ? m.emit : had(P.weight, m.emit);
-                if (P.primary || (!isnan3(e) && !isinf3(e))) {
-                    P.color = add(P.color, e);
-                    if constexpr (ADAPT || SPPMAP) { const float y = adaptive_luminance(e); A->q = A->q + y * y; }
-                    if constexpr (GROUPS) {
-                        const uint32_t g = rv.c->group_of_material[hit_mat];
-                        if (g < rv.c->group_count) {
-                            float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
-                            q[0] = q[0] + e.x; q[1] = q[1] + e.y; q[2] = q[2] + e.z;
-                        }
-                    }
-                }
-                alive = false;
-            } else {
-                if (P.primary) {
-                    if (len2(m.kd) > 0.0f) P.weight = had(P.weight, m.kd); /* ray.cpp:1267-1270 */
-                } else {
-                    /* ray.cpp:1374-1405: pdf and BSDF with the NEW surface's normal and material, the OLD wo (sic) */
-                    if (DIFFUSE) {
-                        float p = pdf_brdf<true>(n, P.dir, P.wo, kRoughness, m) * rv.rr;
-                        if (p > 0.000001f) {
-                            V3 f = eval_scattering<true>(n, P.dir, P.wo, m, kRoughness, h.best_t);
-                            P.weight = had(divs(f, p), P.weight);
-                        }
-                    } else { /* all lobes: the two calls fused, their common terms evaluated once (ort_device.h) */
-                        V3 f = mk(0, 0, 0);
-                        const float p = pdf_eval_scattering(n, P.dir, P.wo, m, kRoughness, h.best_t, rv.rr, f);
-                        if (p > 0.000001f) P.weight = had(divs(f, p), P.weight);
-                    }
-                    P.wo = neg(P.dir);
-                }
-                P.org = add(P.org, scale(h.best_t - kEps, P.dir)); /* ray.cpp:1262,1411 */
-            }
-            P.primary = false;
-            /* ray.cpp:1280: the roulette draw happens only while the path is alive */
-            bounce = alive && rng_01(P.rng) < rv.rr;
-            if (bounce) {
-                /* sample_random_lights (ray.cpp:537-601): result unused, RNG advances */
-                rng_step(P.rng);
-                if (sv.light_count) {
-                    /* one light: x % 1 == 0.  The count is wave-uniform, so this is a scalar branch around the per-lane remainder */
-                    uint32_t li = 0u;
-                    if (sv.light_count != 1u) li = P.rng % sv.light_count;
-                    uint32_t is_sphere;
-                    if (TABS) is_sphere = ((const uint32_t *)tab)[4 * kTabLights + li];
-                    else is_sphere = sv.light_is_sphere[li];
-                    if (is_sphere) { rng_step(P.rng); rng_step(P.rng); rng_step(P.rng); rng_step(P.rng); }
-                }
-                ORT_UTIL(sv, 6, true);
-                draw = sample_brdf_draw<DIFFUSE>(P.rng, kRoughness, m);
-                angle = draw.phi;
-            } else {
-                P.sample++;
-                P.ps = PS_SAMPLE;
-                if constexpr (ADAPT) {
-                    /* a check runs after sample n when n >= min_spp, n < max_spp and (n - min_spp) % check_every == 0: A->next
-                       counts up to it, so nothing is divided per sample */
-                    if (P.sample == A->next && P.sample < spp_u) {
-                        const uint32_t after = A->next + rv.c->ad_check_every;
-                        A->next = after < A->next ? 0xffffffffu : after; /* beyond 2^32: never again */
-                        if (adaptive_stop(P.color, A->q, P.sample, rv.c->ad_tolerance, rv.c->ad_floor)) A->next = 0u;
-                    }
-                }
-            }
+            s.bounce = shade_arrival<F>(sv, rv, tab, P, h, c, spp_u, A, s);
             ORT_PHASE(pr, sv, 1, true);
         }
-        if (!bounce) {
+        if (!s.bounce) {
             /* a lane arrives here after its sample ended (PS_SAMPLE), or with nothing yet (PS_NEED_JOB).
                Pixel write-back, next pixel / next job and the new camera ray all happen in this same
                pass, so the rest of the wave does not wait through a second trip round the loop. */
-            uint32_t job_spp_of_lane = IMPLICIT ? spp_u : P.spp;
-            if constexpr (SPPMAP) job_spp_of_lane = A->next; /* the n of the job in hand; with none in hand (P.ps is not PS_SAMPLE) whatever the word holds decides nothing */
-            const uint32_t job_spp = job_spp_of_lane;
-            bool job_ends = P.ps == PS_SAMPLE && P.sample == job_spp;
-            if constexpr (ADAPT) job_ends = P.ps == PS_SAMPLE && (P.sample == job_spp || A->next == 0u); /* ... or the rule said stop */
-            if (job_ends) {
-                /* ray.cpp:1428 */
-                V3 o;
-                if constexpr (ACCUM) { /* the pixel's words, sums first; the mean over all its samples, this call's and the earlier ones' */
-                    const uint32_t px = P.pxy & 0xffffu, py = P.pxy >> 16;
-                    const size_t at = plane_index(rv, P.job_index, px, py);
-                    const uint32_t total = rv.c->ad_spp[at] + job_spp; /* n0 + add <= 1 << 24: exact in float */
-                    float *q = rv.c->acc_sum + 3u * at;
-                    q[0] = P.color.x; q[1] = P.color.y; q[2] = P.color.z;
-                    rv.c->ad_spp[at] = total;
-                    o = divs(P.color, (float)total);
-                } else
-                o = divs(P.color, (float)(ADAPT ? P.sample : job_spp));
-                if constexpr (RAYS) {
-                    const size_t ray = ((size_t)P.pxy << 32) | P.job_index;
-                    float *p = rv.c->out + 3u * ray;
-                    p[0] = o.x; p[1] = o.y; p[2] = o.z;
-                    if (rv.c->final_states) rv.c->final_states[ray] = P.rng;
-                    if constexpr (ADAPT) {
-                        if (rv.c->ad_spp) rv.c->ad_spp[ray] = P.sample;
-                        if (rv.c->ad_m2) rv.c->ad_m2[ray] = A->q;
-                    }
-                    P.ps = PS_NEED_JOB;
-                } else {
-                uint32_t px = P.pxy & 0xffffu, py = P.pxy >> 16;
-                if constexpr (GROUPS) { /* JOBS_PIXEL: the G sums become means where they stand; the frame and the states if asked for */
-                    const float fs = (float)job_spp;
-                    for (uint32_t g = 0; g < rv.c->group_count; ++g) {
-                        float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
-                        q[0] = q[0] / fs; q[1] = q[1] / fs; q[2] = q[2] / fs;
-                    }
-                    if (rv.c->out) { float *p = view_pixel_ptr(rv, P.job_index, 0u, px, py); p[0] = o.x; p[1] = o.y; p[2] = o.z; }
-                    if (rv.c->final_states) rv.c->final_states[plane_index(rv, P.job_index, px, py)] = P.rng;
-                } else if constexpr (ACCUM) { /* the frame is an optional plane here */
-                    if (rv.c->out) { float *p = view_pixel_ptr(rv, P.job_index, 0u, px, py); p[0] = o.x; p[1] = o.y; p[2] = o.z; }
-                } else {
-                float *p;
-                if constexpr (VIEWS) p = view_pixel_ptr(rv, P.job_index, P.jyp >> 16, px, py);
-                else p = pixel_ptr(rv, P.jyp >> 16, px, py);
-                p[0] = o.x; p[1] = o.y; p[2] = o.z;
-                }
-                if constexpr (ADAPT) { /* JOBS_PIXEL: the pixel's words of its view's planes, view_count frames of W * H each */
-                    const size_t at = plane_index(rv, P.job_index, px, py);
-                    if (rv.c->ad_spp) rv.c->ad_spp[at] = P.sample;
-                    if (rv.c->ad_m2) rv.c->ad_m2[at] = A->q;
-                    if (rv.c->final_states) rv.c->final_states[at] = P.rng;
-                }
-                if constexpr (SPPMAP) { /* likewise, without the sample count: the caller holds it */
-                    const size_t at = plane_index(rv, P.job_index, px, py);
-                    if (rv.c->ad_m2) rv.c->ad_m2[at] = A->q;
-                    if (ACCUM || rv.c->final_states) rv.c->final_states[at] = P.rng; /* ACCUM: the state is a required plane */
-                }
-                if (IMPLICIT) {
-                    P.ps = PS_NEED_JOB; /* a one-pixel job ends with its pixel */
-                } else {
-                px++;
-                if (px == (P.jxx >> 16)) { px = P.jxx & 0xffffu; py++; }
-                P.pxy = px | (py << 16);
-                if (py == (P.jyp & 0xffffu)) {
-                    if (rv.mode == JOBS_EXPLICIT && rv.c->final_states) rv.c->final_states[P.job_index] = P.rng;
-                    P.ps = PS_NEED_JOB;
-                } else {
-                    P.ps = PS_PIXEL;
-                }
-                }
-                }
-            }
+            const uint32_t job_spp = job_length<F>(P, spp_u, A);
+            if (job_over<F>(P, job_spp, A)) end_job<F>(rv, P, job_spp, A);
             [[maybe_unused]] uint32_t acc_n0 = 0u; /* ACCUM: the samples the pixel drawn in this pass has had; a pixel starts in the pass that draws its job */
             if (P.ps == PS_NEED_JOB) {
-                if (no_new_job) return false; /* ray exchange, end of the launch: this lane takes a parked path first (pt_lane_x) */
-                unsigned long long j = draw_job(rv, pool);
-                if (j >= rv.c->job_count) { P.ps = PS_DONE; break; }
-                if (IMPLICIT && late_flag && j >= rv.c->endgame_from) *late_flag = 1u; /* ray exchange: the launch is near its end (pt_lane_x) */
-                if constexpr (RAYS) {
-                    /* a ray outside the per-ray domain (in_query_domain) is answered here, NaN and its seed, without a traversal */
-                    const float2 *r = rv.c->rays + 3ull * j; /* load_ray's twin, kept in this form: through the helper the radiance kernels' code moves */
-                    const float2 a = r[0], b = r[1], e = r[2];
-                    const uint32_t seed = rv.c->seeds[j];
-                    const V3 d = mk(b.y, e.x, e.y);
-                    if (!in_query_domain(mk(a.x, a.y, b.x), d)) {
-                        float *p = rv.c->out + 3u * (size_t)j;
-                        p[0] = p[1] = p[2] = om_bits_f32(0x7fc00000u);
-                        if (rv.c->final_states) rv.c->final_states[j] = seed;
-                        if constexpr (ADAPT) {
-                            if (rv.c->ad_spp) rv.c->ad_spp[j] = 0u;
-                            if (rv.c->ad_m2) rv.c->ad_m2[j] = 0.0f;
-                        }
-                        continue;
-                    }
-                    P.job_index = (uint32_t)j;
-                    P.pxy = (uint32_t)(j >> 32);
-                    P.rng = seed ? seed : 1u; /* as job_seed: a zero xorshift state never leaves zero */
-                } else
-                if (!IMPLICIT && rv.mode == JOBS_EXPLICIT) {
-                    ort_tile_job jb = rv.c->jobs[j];
-                    P.job_index = (uint32_t)j;
-                    P.jxx = (uint32_t)jb.x0 | ((uint32_t)jb.x1 << 16);
-                    P.jyp = (uint32_t)jb.y1;
-                    P.pxy = (uint32_t)jb.x0 | ((uint32_t)jb.y0 << 16);
-                    P.rng = jb.rng_state; P.spp = jb.spp;
-                    if (jb.x1 <= jb.x0 || jb.y1 <= jb.y0) { /* empty rect: the reference loops zero times */
-                        if (rv.c->final_states) rv.c->final_states[P.job_index] = P.rng;
-                        continue;
-                    }
-                } else {
-                    uint32_t seed;
-                    if constexpr (VIEWS) { /* [view][the view's job space]: the view's seed sits in the fourth word of its table entry */
-                        P.job_index = (uint32_t)(j / rv.c->view_jobs);
-                        j = j % rv.c->view_jobs;
-                        seed = om_f32_bits(rv.c->views[4u * (size_t)P.job_index].w);
-                    }
-                    /* implicit job space: [chunk k][my 8x8 block b][pixel-in-block p] */
-                    unsigned long long per_chunk = (unsigned long long)rv.c->my_blocks * 64ull;
-                    uint32_t k, lb, pin; /* chunk, local block, pixel in block */
-                    if (rv.c->block_major) {
-                        const uint32_t per_block = rv.c->nchunks * 64u;
-                        const uint32_t within = (uint32_t)(j % per_block);
-                        lb = (uint32_t)(j / per_block);
-                        k = within >> 6;
-                        pin = within & 63u;
-                    } else {
-                        k = (uint32_t)(j / per_chunk);
-                        const uint32_t rem = (uint32_t)(j % per_chunk);
-                        lb = rem >> 6;
-                        pin = rem & 63u;
-                    }
-                    uint32_t blk = rv.c->shard_index + lb * rv.c->shard_count;
-                    /* block_pixel's twin, kept in this form: the render kernels' code moves with the helper's */
-                    int x = (int)((rv.c->block_x0 + blk % rv.c->blocks_w) * 8u + (pin & 7u));
-                    int y = (int)((rv.c->block_y0 + blk / rv.c->blocks_w) * 8u + (pin >> 3));
-                    if (x < rv.c->x0 || x >= rv.c->x1 || y < rv.c->y0 || y >= rv.c->y1) continue;
-                    if constexpr (SPPMAP) { /* the job's length, one word of the caller's map, cut at the cap; no samples: no job */
-                        const size_t at = plane_index(rv, P.job_index, (uint32_t)x, (uint32_t)y);
-                        uint32_t asked;
-                        if constexpr (ACCUM) asked = rv.c->sample_map ? rv.c->sample_map[at] : spp_u;
-                        else asked = rv.c->sample_map[at];
-                        uint32_t n = asked < spp_u ? asked : spp_u;
-                        if constexpr (ACCUM) { /* ... and at what keeps the pixel's total within 1 << 24 */
-                            acc_n0 = rv.c->ad_spp[at];
-                            const uint32_t room = (1u << 24) - (acc_n0 < (1u << 24) ? acc_n0 : (1u << 24));
-                            n = n < room ? n : room;
-                        }
-                        if (n == 0u) continue;
-                        A->next = n;
-                    }
-                    uint32_t pix = (uint32_t)(y * rv.W + x);
-                    if (!IMPLICIT) P.jxx = (uint32_t)x | ((uint32_t)(x + 1) << 16);
-                    P.pxy = (uint32_t)x | ((uint32_t)y << 16);
-                    if (rv.mode == JOBS_PIXEL) {
-                        if constexpr (VIEWS) P.rng = job_seed(seed, pix);
-                        else P.rng = job_seed(rv.c->seed, pix);
-                        if (!IMPLICIT) P.spp = rv.c->spp;
-                        P.jyp = (uint32_t)(y + 1);
-                    } else {
-                        if constexpr (VIEWS) P.rng = job_seed(seed, k * (uint32_t)(rv.W * rv.H) + pix);
-                        else P.rng = job_seed(rv.c->seed, k * (uint32_t)(rv.W * rv.H) + pix);
-                        if (!IMPLICIT) P.spp = rv.c->chunk;
-                        P.jyp = (uint32_t)(y + 1) | (k << 16);
-                    }
-                }
-                P.ps = PS_PIXEL;
+                const JobTake t = take_job<F>(rv, P, spp_u, late_flag, no_new_job, pool, A, acc_n0);
+                if (t == JOB_PARKED) return false;
+                if (t == JOB_NONE_LEFT) break;
+                if (t == JOB_SKIPPED) continue;
             }
-            if (P.ps == PS_PIXEL) {
-                ORT_SIM_PIXEL_HOOK((int)(P.pxy & 0xffffu), (int)(P.pxy >> 16), P.rng);
-                P.color = mk(0, 0, 0); /* ray.cpp:1211 */
-                P.sample = 0;
-                P.ps = PS_SAMPLE;
-                if constexpr (ADAPT) { A->q = 0.0f; A->next = rv.c->ad_min_spp; }
-                if constexpr (SPPMAP) A->q = 0.0f;
-                if constexpr (ACCUM) {
-                    if (acc_n0) { /* a continued pixel: its stream and its sums as the planes hold them, judged no more than a material is */
-                        const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
-                        const uint32_t state = rv.c->final_states[at];
-                        P.rng = state ? state : 1u; /* as job_seed: a zero xorshift state never leaves zero */
-                        /* + (+0): the call is chained one-sample renders whose colours are added to C, and a colour is never -0,
-                           so a -0 the caller stored is +0 after the first of them whatever it holds; every other value stands */
-                        const float *q = rv.c->acc_sum + 3u * at;
-                        P.color = mk(q[0] + 0.0f, q[1] + 0.0f, q[2] + 0.0f);
-                        if (rv.c->ad_m2) A->q = rv.c->ad_m2[at] + 0.0f;
-                    }
-                }
-                if constexpr (GROUPS) {
-                    for (uint32_t g = 0; g < rv.c->group_count; ++g) {
-                        float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
-                        q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
-                    }
-                }
-                if (focal_cache) { /* the pixel's focal point, once per pixel (persistent kernel: three floats of LDS per lane) */
-                    V3 f;
-                    if constexpr (VIEWS) f = view_focal_point(rv, P.pxy, load_view_camera(rv, P.job_index));
-                    else f = focal_point(rv, P.pxy, cam_p, cam_x, cam_y, cam_z, focal_length);
-                    focal_cache[0] = f.x; focal_cache[focal_stride] = f.y; focal_cache[2 * focal_stride] = f.z;
-                }
+            if (P.ps == PS_PIXEL) begin_pixel<F>(rv, P, cam, A, acc_n0, focal_cache, focal_stride);
+            if constexpr (!SPPMAP) { /* SPPMAP: a job in hand has n >= 1 samples and P.sample < n here: nothing to skip */
+                if (P.sample == job_spp) continue; /* spp == 0: the reference's sample loop runs zero times */
             }
-            if constexpr (SPPMAP) {
-                /* a job in hand has n >= 1 samples and P.sample < n here: nothing to skip */
-            } else
-            if (P.sample == job_spp) continue; /* spp == 0: the reference's sample loop runs zero times */
-            /* ray.cpp:1215-1221: point on the focal plane through the pixel centre: a function of the pixel alone,
-               read back from the per-lane cache or (wavefront mode) recomputed -- same expressions, same bits */
-            if constexpr (RAYS) { /* the caller's ray; no aperture, so no angle is drawn */
-                const Ray6 r = load_ray(rv.c->rays, ((unsigned long long)P.pxy << 32) | P.job_index);
-                ray_o = r.o;
-                ray_d = r.d;
-                if constexpr (HEMI) { /* the diffuse lobe's draw (sample_brdf_draw without the choice); its azimuth is the pass's one angle */
-                    const float e0 = rng_01(P.rng), e1 = rng_01(P.rng);
-                    hemi_c = __builtin_sqrtf(e0); /* ray.cpp:1123 */
-                    angle = 2.0f * kPi * e1;
-                }
-            } else {
-            if constexpr (VIEWS)
-                focal = focal_cache ? mk(focal_cache[0], focal_cache[focal_stride], focal_cache[2 * focal_stride])
-                                    : view_focal_point(rv, P.pxy, load_view_camera(rv, P.job_index));
-            else
-            focal = focal_cache ? mk(focal_cache[0], focal_cache[focal_stride], focal_cache[2 * focal_stride])
-                                : focal_point(rv, P.pxy, cam_p, cam_x, cam_y, cam_z, focal_length);
-            angle = rng_between(P.rng, 0.0f, 2 * kPi); /* ray.cpp:1232 */
-            }
+            primary_sample<F>(rv, P, cam, focal_cache, focal_stride, s);
             ORT_PHASE(pr, sv, 2, true);
         }
         /* lanes that bounce and lanes that start a new camera sample both need cos/sin of one angle
@@ -1583,76 +1769,9 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
            converged, instead of once in each branch (same operand, same bits) */
         ORT_UTIL(sv, 7, true);
         float cs, sn;
-        ort_sincosf(angle, &sn, &cs);
-        if (DIFFUSE) { /* the leaner flavour has the registers for the wider merge; the all-lobes one spills on it */
-            /* Bounce lanes normalise twice here (the surface normal again, ray.cpp:1069, and the sampled direction,
-               :1158) and so do camera lanes (the ray direction, :1240, and -- sic -- the direction again for wo,
-               :1241): two converged evaluations instead of four divergent ones */
-            V3 ap = mk(0, 0, 0);
-            if (!bounce) { /* ray.cpp:1233-1239 */
-                if constexpr (RAYS) ap = ray_o;
-                else
-                if constexpr (VIEWS) ap = view_aperture_point(load_view_camera(rv, P.job_index), aperture, cs, sn);
-                else
-                ap = sub(add(add(cam_p, scale(aperture * cs, cam_x)), scale(aperture * sn, cam_y)), scale(0.1f, cam_z));
-            }
-            const V3 unit1 = normalize(bounce ? n : (RAYS ? ray_d : sub(focal, ap)));
-            bool is_trans = false;
-            V3 raw = unit1;
-            if (bounce) raw = sample_brdf_finish<false, true>(n, unit1, P.wo, m, draw, cs, sn, is_trans);
-            if constexpr (HEMI) { if (!bounce) raw = sample_lobe_n(unit1, hemi_c, cs, sn); } /* unit1 = normalize(n), as sample_lobe's */
-            const V3 unit2 = normalize(raw);
-            if (bounce) {
-                if (is_trans) P.org = add(P.org, scale(2.0f * kEps, P.dir)); /* ray.cpp:1345-1348: dir is still the arriving direction */
-                P.dir = unit2;
-            } else {
-                if constexpr (HEMI) { P.dir = unit2; P.wo = neg(normalize(unit2)); } /* d; wo = -normalize(d), as RAYS for the ray (p, d) */
-                else
-                if constexpr (RAYS) { P.dir = ray_d; P.wo = neg(unit1); } /* the direction as given; wo = -normalize(d) */
-                else {
-                P.dir = unit1;
-                P.wo = neg(unit2);
-                }
-                P.org = ap;
-                P.weight = mk(1, 1, 1);
-                P.primary = true;
-                P.ps = PS_HIT;
-            }
-        } else {
-            /* both branches end by normalising a direction (ray.cpp:1158 / :1240): one converged evaluation */
-            V3 raw, ap = mk(0, 0, 0);
-            bool is_trans = false;
-            if (bounce) {
-                raw = sample_brdf_finish<false>(n, normalize(n), P.wo, m, draw, cs, sn, is_trans);
-            } else {
-                /* ray.cpp:1233-1246 */
-                if constexpr (RAYS) ap = ray_o;
-                else
-                if constexpr (VIEWS) ap = view_aperture_point(load_view_camera(rv, P.job_index), aperture, cs, sn);
-                else
-                ap = sub(add(add(cam_p, scale(aperture * cs, cam_x)), scale(aperture * sn, cam_y)), scale(0.1f, cam_z));
-                if constexpr (HEMI) raw = sample_lobe_n(normalize(ray_d), hemi_c, cs, sn);
-                else
-                if constexpr (RAYS) raw = ray_d;
-                else
-                raw = sub(focal, ap);
-            }
-            const V3 unit = normalize(raw);
-            if (bounce) {
-                if (is_trans) P.org = add(P.org, scale(2.0f * kEps, P.dir)); /* ray.cpp:1345-1348: dir is still the arriving direction */
-                P.dir = unit;
-            } else {
-                if constexpr (RAYS && !HEMI) { P.dir = raw; P.wo = neg(unit); } /* the direction as given; wo = -normalize(d) */
-                else { /* HEMI: d = unit, and wo = -normalize(d) as RAYS for the ray (p, d) */
-                P.dir = unit;
-                P.wo = neg(normalize(P.dir)); /* normalised again (sic) */
-                }
-                P.org = ap;
-                P.weight = mk(1, 1, 1);
-                P.primary = true;
-                P.ps = PS_HIT;
-            }
-        }
+        ort_sincosf(s.angle, &sn, &cs);
+        if (DIFFUSE) compose_ray_diffuse<F>(rv, P, cam, s, cs, sn);
+        else compose_ray_all_lobes<F>(rv, P, cam, s, cs, sn);
         ORT_PHASE(pr, sv, 3, true);
         return true;
     }
@@ -2013,10 +2132,6 @@ struct Stash {
     uint32_t *stk;  /* [kLdsStack][cap], L only */
     uint32_t cap;
 };
-
-ORT_D uint32_t lane_rank(unsigned long long mask) { /* set bits of mask below this lane */
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 
 constexpr uint32_t kStashVecs = 9u; /* float4 per parked path */
 /* compile-time constants, so that the nine plane offsets of a parked record are literals instead of scalar registers (which were spilled) */
@@ -2971,6 +3086,42 @@ ao_points(SceneView sv, RenderHot rv, AoIO io) {
  * held through the walk.  The ids go straight to memory at sample 0 (profiles/r18_features.md). */
 constexpr int kFeatureCacheWords = 7; /* albedo.xyz, normal.xyz, depth */
 
+/* the pixel lanes' shared steps (feature_lane, follow_lane, matte_lane).
+   A job of the [view][8x8 block of the rect][pixel in block] space is drawn: the lane's view, pixel and stream, no sample started
+   (follow_lane holds the same lines in place, see there) */
+ORT_D JobTake take_pixel_job(const RenderHot &rv, PathState &P, unsigned long long *pool) {
+    const unsigned long long j = draw_job(rv, pool);
+    if (!(j < rv.c->job_count)) return JOB_NONE_LEFT;
+    const uint32_t view = (uint32_t)(j / rv.c->view_jobs), within = (uint32_t)(j % rv.c->view_jobs);
+    const BlockPixel bp = block_pixel(rv, within >> 6, within & 63u);
+    if (bp.outside) return JOB_SKIPPED;
+    const int x = bp.x, y = bp.y;
+    P.job_index = view;
+    P.pxy = (uint32_t)x | ((uint32_t)y << 16);
+    P.rng = job_seed(om_f32_bits(rv.c->views[4u * (size_t)view].w), (uint32_t)(y * rv.W + x));
+    P.sample = 0;
+    return JOB_TAKEN;
+}
+/* the camera sample into P.org / P.dir, as produce_ray's steps compose it (primary_sample, compose_ray_*): one converged sin/cos
+   for the lanes that start a sample */
+ORT_D void view_camera_sample(const RenderHot &rv, PathState &P) {
+    const ViewCamera cam = load_view_camera(rv, P.job_index);
+    const V3 focal = view_focal_point(rv, P.pxy, cam);
+    const float angle = rng_between(P.rng, 0.0f, 2 * kPi); /* ray.cpp:1232 */
+    float sn, cs;
+    ort_sincosf(angle, &sn, &cs);
+    P.org = view_aperture_point(cam, kAperture, cs, sn); /* ray.cpp:1199, :1233-1234 */
+    P.dir = normalize(sub(focal, P.org));                /* ray.cpp:1237 */
+}
+/* the job's end: the means of the albedo, normal and depth sums (job_cache's first seven words) into the planes asked for */
+template <class IO>
+ORT_D void write_feature_means(const IO &io, size_t at, const float *job_cache, uint32_t spp) {
+    const float fs = (float)spp; /* ray.cpp:1428's division, component by component */
+    if (io.albedo) { float *o = io.albedo + 3u * at; const V3 s = cache_v3(job_cache); o[0] = s.x / fs; o[1] = s.y / fs; o[2] = s.z / fs; }
+    if (io.normal) { float *o = io.normal + 3u * at; const V3 s = cache_v3(job_cache + 3 * kBlock); o[0] = s.x / fs; o[1] = s.y / fs; o[2] = s.z / fs; }
+    if (io.depth) io.depth[at] = job_cache[6 * kBlock] / fs;
+}
+
 template <uint32_t F>
 ORT_D void feature_lane(const SceneView &sv, const RenderHot &rv, const FeatureIO &io, const float4 *tab, uint32_t *lds_stack, float *job_cache, const int tid,
                         const uint32_t lane_id, unsigned long long *pool) {
@@ -3013,37 +3164,21 @@ ORT_D void feature_lane(const SceneView &sv, const RenderHot &rv, const FeatureI
                 if (busy) {
                     if (P.sample < spp) { start = true; break; }
                     const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
-                    const float fs = (float)spp; /* ray.cpp:1428's division, component by component */
-                    if (io.albedo) { float *o = io.albedo + 3u * at; const V3 s = cache_v3(job_cache); o[0] = s.x / fs; o[1] = s.y / fs; o[2] = s.z / fs; }
-                    if (io.normal) { float *o = io.normal + 3u * at; const V3 s = cache_v3(job_cache + 3 * kBlock); o[0] = s.x / fs; o[1] = s.y / fs; o[2] = s.z / fs; }
-                    if (io.depth) io.depth[at] = job_cache[6 * kBlock] / fs;
+                    write_feature_means(io, at, job_cache, spp);
                     if (io.hits) io.hits[at] = hits;
                     if (io.states) io.states[at] = P.rng;
                     busy = false;
                 }
                 if (!more) break;
-                const unsigned long long j = draw_job(rv, pool);
-                if (!(j < rv.c->job_count)) { more = false; break; }
-                const uint32_t view = (uint32_t)(j / rv.c->view_jobs), within = (uint32_t)(j % rv.c->view_jobs);
-                const BlockPixel bp = block_pixel(rv, within >> 6, within & 63u);
-                if (bp.outside) continue;
-                const int x = bp.x, y = bp.y;
-                P.job_index = view;
-                P.pxy = (uint32_t)x | ((uint32_t)y << 16);
-                P.rng = job_seed(om_f32_bits(rv.c->views[4u * (size_t)view].w), (uint32_t)(y * rv.W + x));
-                P.sample = 0;
+                const JobTake t = take_pixel_job(rv, P, pool);
+                if (t == JOB_NONE_LEFT) { more = false; break; }
+                if (t == JOB_SKIPPED) continue;
                 hits = 0;
                 for (int k = 0; k < kFeatureCacheWords; ++k) job_cache[k * kBlock] = 0.0f;
                 busy = true;
             }
-            if (start) { /* the camera sample, as produce_ray composes it: one converged sin/cos for the lanes that start a sample */
-                const ViewCamera cam = load_view_camera(rv, P.job_index);
-                const V3 focal = view_focal_point(rv, P.pxy, cam);
-                const float angle = rng_between(P.rng, 0.0f, 2 * kPi); /* ray.cpp:1232 */
-                float sn, cs;
-                ort_sincosf(angle, &sn, &cs);
-                P.org = view_aperture_point(cam, 0.1f, cs, sn); /* ray.cpp:1199, :1233-1234 */
-                P.dir = normalize(sub(focal, P.org));           /* ray.cpp:1237 */
+            if (start) {
+                view_camera_sample(rv, P);
                 P.sample++;
                 begin_ray<begin_of(F), kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
                 if (ORT_RARE(raycast_needs_exact(io.q, P.org, P.dir, T.inv_d))) skip_fast_walk(T, h);
@@ -3164,16 +3299,15 @@ ORT_D void follow_lane(const SceneView &sv, const RenderHot &rv, const FollowIO 
                 if (busy) {
                     if (P.sample < spp) { start = true; break; }
                     const size_t at = plane_index(rv, P.job_index, P.pxy & 0xffffu, P.pxy >> 16);
-                    const float fs = (float)spp; /* ray.cpp:1428's division, component by component */
-                    if (io.albedo) { float *o = io.albedo + 3u * at; const V3 s = cache_v3(job_cache); o[0] = s.x / fs; o[1] = s.y / fs; o[2] = s.z / fs; }
-                    if (io.normal) { float *o = io.normal + 3u * at; const V3 s = cache_v3(job_cache + 3 * kBlock); o[0] = s.x / fs; o[1] = s.y / fs; o[2] = s.z / fs; }
-                    if (io.depth) io.depth[at] = job_cache[6 * kBlock] / fs;
+                    write_feature_means(io, at, job_cache, spp);
                     if (io.hits) io.hits[at] = hb & kFollowHitsMask;
                     if (io.bounces) io.bounces[at] = B;
                     if (io.states) io.states[at] = P.rng;
                     busy = false;
                 }
                 if (!more) break;
+                /* take_pixel_job's lines, in place: through the helper, in each of seven forms tried, these kernels' register
+                   counts change (profiles/r30_lane_steps.md) */
                 const unsigned long long j = draw_job(rv, pool);
                 if (!(j < rv.c->job_count)) { more = false; break; }
                 const uint32_t view = (uint32_t)(j / rv.c->view_jobs), within = (uint32_t)(j % rv.c->view_jobs);
@@ -3207,8 +3341,8 @@ ORT_D void follow_lane(const SceneView &sv, const RenderHot &rv, const FollowIO 
                     const V3 wo = (hb >> 25) == 0u ? neg(normalize(P.dir)) : neg(P.dir); /* ray.cpp:1241 (sic) / :1408 */
                     raw = sample_brdf_finish<false>(n, normalize(n), wo, m, draw, cs, sn, is_trans);
                 } else {
-                    ap = view_aperture_point(cam, 0.1f, cs, sn); /* ray.cpp:1199, :1233-1234 */
-                    raw = sub(focal, ap);                        /* ray.cpp:1237 */
+                    ap = view_aperture_point(cam, kAperture, cs, sn); /* ray.cpp:1199, :1233-1234 */
+                    raw = sub(focal, ap);                             /* ray.cpp:1237 */
                 }
                 const V3 unit = normalize(raw);
                 if (bounce) {
@@ -3332,27 +3466,14 @@ ORT_D void matte_lane(const SceneView &sv, const RenderHot &rv, const MatteIO &i
                     busy = false;
                 }
                 if (!more) break;
-                const unsigned long long j = draw_job(rv, pool);
-                if (!(j < rv.c->job_count)) { more = false; break; }
-                const uint32_t view = (uint32_t)(j / rv.c->view_jobs), within = (uint32_t)(j % rv.c->view_jobs);
-                const BlockPixel bp = block_pixel(rv, within >> 6, within & 63u);
-                if (bp.outside) continue;
-                const int x = bp.x, y = bp.y;
-                P.job_index = view;
-                P.pxy = (uint32_t)x | ((uint32_t)y << 16);
-                P.rng = job_seed(om_f32_bits(rv.c->views[4u * (size_t)view].w), (uint32_t)(y * rv.W + x));
-                P.sample = 0;
+                const JobTake t = take_pixel_job(rv, P, pool);
+                if (t == JOB_NONE_LEFT) { more = false; break; }
+                if (t == JOB_SKIPPED) continue;
                 hits = used = other = run_len = 0u;
                 busy = true;
             }
-            if (start) { /* the camera sample, as produce_ray composes it: one converged sin/cos for the lanes that start a sample */
-                const ViewCamera cam = load_view_camera(rv, P.job_index);
-                const V3 focal = view_focal_point(rv, P.pxy, cam);
-                const float angle = rng_between(P.rng, 0.0f, 2 * kPi); /* ray.cpp:1232 */
-                float sn, cs;
-                ort_sincosf(angle, &sn, &cs);
-                P.org = view_aperture_point(cam, 0.1f, cs, sn); /* ray.cpp:1199, :1233-1234 */
-                P.dir = normalize(sub(focal, P.org));           /* ray.cpp:1237 */
+            if (start) {
+                view_camera_sample(rv, P);
                 P.sample++;
                 begin_ray<begin_of(F), kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
                 if (ORT_RARE(raycast_needs_exact(io.q, P.org, P.dir, T.inv_d))) skip_fast_walk(T, h);
