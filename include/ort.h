@@ -512,6 +512,55 @@ int ort_irradiance_adaptive_device(ort_scene *scene, const void *d_points, const
                                    void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, uint32_t flags, void *hip_stream,
                                    ort_stats *stats);
 
+/* ---- SH light-probe queries: radiance over the sphere as 9 SH coefficients ---------------------
+ * A light probe is not tied to a normal: it stores the radiance that arrives at a point from ALL directions, so that any normal can
+ * be shaded from it later.  out_sh[i] holds, per colour channel, the means over spp uniformly drawn directions of the arriving
+ * radiance times the nine real spherical harmonics of bands 0 to 2.  The mean is returned as it stands, S / (float)spp, so that no
+ * rounding is added: the SH COEFFICIENTS of the radiance field are 4 pi * out_sh (the sphere's measure over the uniform density),
+ * as irradiance is pi * ort_irradiance's mean.
+ *  - Inputs.  points is ort_irradiance's array: count x {p.xyz, n.xyz} f32, 24 B each, 8-byte aligned; the per-point domain test is
+ *    the same and p is used as given.  Here n is only the POLE of the sample pattern (c below is the cosine to it): a caller without
+ *    a preference passes (0, 0, 1).  The SH basis is always in world axes, whatever n is.  seeds is count x u32.
+ *  - One sample.  A point's samples run on ONE xorshift stream that starts at seeds[i] (0 is taken as 1).  Per sample, every
+ *    operation a separately rounded f32 operation (no FMA):
+ *        e0  = rng_01(s);  e1 = rng_01(s)
+ *        c   = 1.0f - 2.0f * e0                          (uniform over the sphere; ort_irradiance has sqrtf(e0) here)
+ *        phi = (2.0f * kPi) * e1
+ *        m   = sample_lobe(n, c, phi);  d = normalize(m)
+ *    then ort_radiance's sample from the ray (p, d) on the same stream: direction d as it stands, wo = -normalize(d), no aperture
+ *    draw.  Whenever that sample adds a vector e to the colour sum C -- the primary hit's emission, or a bounce's emission that
+ *    passed the finite check -- the basis is formed from x, y, z = d (the sample's PRIMARY direction, also at a bounce):
+ *        b0 = 0.282094792f
+ *        b1 = 0.488602512f*y          b2 = 0.488602512f*z          b3 = 0.488602512f*x
+ *        b4 = 1.092548431f*(x*y)      b5 = 1.092548431f*(y*z)      b6 = 0.315391565f*(3.0f*(z*z) - 1.0f)
+ *        b7 = 1.092548431f*(x*z)      b8 = 0.546274215f*(x*x - y*y)
+ *        S[j] = S[j] + b_j * e        component by component, the product rounded and then the sum; S starts at +0
+ *  - Outputs.  out_sh is count x ORT_SH_COEFFS x 3 f32, [point][coefficient][rgb], and holds S[j] / (float)spp.  out_rgb (may be
+ *    NULL) is count x 3 f32, C / (float)spp: the plain mean, which is also out_sh[i][0] / b0 up to rounding.  final_states (may be
+ *    NULL) is the stream's state after the last sample.
+ *  - Outside the domain.  Such a point gets NaN in all 27 words of out_sh[i] and in out_rgb[i], and final_states[i] = seeds[i] (as
+ *    given, 0 included); it is not traced, and its neighbours are unaffected.
+ *  - Two identities, in ort_irradiance's form.  I1: with s'_k the stream's state after sample k's two direction draws, sample k's
+ *    colour and the state after it are, bit for bit, ort_radiance's for the single ray (p, d_k) with seed s'_k at spp = 1; d_k is
+ *    unit op 21's direction for the state before the sample, and b1 ... b8 are unit op 22's.  I2: with rr = 0 the roulette never
+ *    continues: with h the closest hit of (p, d_k), sample k adds the emission of h's material if that is a light and nothing
+ *    otherwise, and draws one more rng_01 exactly when h.mat != 0 and the material is not a light.
+ *  - rr, flags, stats, count == 0, alignment and the order of the errors (before any device work) are ort_irradiance's, with out_sh
+ *    where out_rgb stood as the required output: ORT_ERR_INVALID (null scene, points, seeds or out_sh; misaligned points (8 bytes),
+ *    seeds, out_sh, out_rgb or final_states (4 bytes); spp == 0; rr outside [0, 1) or NaN), ORT_ERR_STATE, ORT_ERR_NO_DEVICE.
+ *    With ORT_RENDER_COUNTERS, paths = (points inside the domain) * spp.  Results do not depend on count, order, how the batch is
+ *    sliced or how points fall on the GPU's lanes.  Primary rays take the exact octree walk where ort_irradiance's do. */
+#define ORT_SH_COEFFS 9u
+
+/* host points and seeds in, host coefficients (and means, states) out; synchronous, staged as ort_radiance */
+int ort_probe_sh(ort_scene *scene, const float *points, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr,
+                 float *out_sh, float *out_rgb /* may be NULL */, uint32_t *final_states /* may be NULL */, uint32_t flags,
+                 ort_stats *stats);
+/* DEVICE pointers on the scene's device; enqueued on hip_stream (NULL = the default stream), returns without waiting unless
+   stats != NULL -- as ort_radiance_device */
+int ort_probe_sh_device(ort_scene *scene, const void *d_points, const void *d_seeds, uint64_t count, uint32_t spp, float rr,
+                        void *d_out_sh, void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats);
+
 /* ---- ambient-occlusion queries: hemisphere visibility gathers at points ------------------------
  * The visibility gather of a baker's texel or probe: ambient occlusion, a bent normal, "how much sky does this point see within
  * r".  ort_irradiance's points, seeds and direction draw; ort_occluded's answer along every drawn direction.
@@ -1243,7 +1292,10 @@ int ort_gather_framebuffer_local(ort_comm **comms, int world, const void *const 
  * 19 sincos     in x                                         out ort_sincosf of x: sin cos
  * 20 hemisphere draw as the irradiance kernels compose it    in seed(bits) n.xyz     out d.xyz wo.xyz rng(bits)
  *               (two rng_01, sqrt, ort_sincosf of 2 pi e1, sample_lobe_n about normalize(n), normalize; wo = -normalize(d); the
- *               stream after the two draws; the seed is a stream state as it stands, 0 not taken as 1) */
+ *               stream after the two draws; the seed is a stream state as it stands, 0 not taken as 1)
+ * 21 sphere draw as the SH light-probe kernels compose it     in seed(bits) n.xyz     out d.xyz wo.xyz rng(bits)
+ *               (op 20 with c = 1 - 2 e0 where that has sqrt(e0))
+ * 22 SH basis   in d.xyz                                     out b1 b2 b3 b4 b5 b6 b7 b8 of ort_probe_sh (b0 is a constant) */
 int ort_unit_eval_device(int device, const void *records, uint32_t count, float *out);
 
 /* ---- output ------------------------------------------------------------------------

@@ -24,6 +24,7 @@ COMM_ID_BYTES = 128
 HIT_TRIANGLE, HIT_BOX, HIT_CYLINDER, HIT_SPHERE = 0, 2, 3, 4
 NO_PRIM = 0xFFFFFFFF
 AO_INVALID = 0xFFFFFFFF  # ORT_AO_INVALID: ambient_occlusion()'s open count of a point outside the domain
+SH_COEFFS = 9            # ORT_SH_COEFFS: probe_sh()'s coefficients per point and colour channel, bands 0 to 2
 MAX_VIEWS = 4096  # ORT_MAX_VIEWS
 MAX_LIGHT_GROUPS = 8     # ORT_MAX_LIGHT_GROUPS
 NO_LIGHT_GROUP = 0xFF    # ORT_NO_LIGHT_GROUP: a light that is in no group
@@ -234,6 +235,7 @@ EXPORTS = [
     "ort_radiance", "ort_radiance_device",
     "ort_radiance_adaptive", "ort_radiance_adaptive_device",
     "ort_irradiance", "ort_irradiance_device", "ort_irradiance_adaptive", "ort_irradiance_adaptive_device",
+    "ort_probe_sh", "ort_probe_sh_device",
     "ort_camera_from_pose", "ort_render_views", "ort_render_views_device", "ort_render_views_workspace_bytes",
     "ort_render_adaptive", "ort_render_adaptive_device", "ort_render_views_adaptive", "ort_render_views_adaptive_device",
     "ort_render_features", "ort_render_features_device", "ort_render_views_features", "ort_render_views_features_device",
@@ -330,7 +332,8 @@ def lib():
                 ("ort_radiance", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_float, vp, vp, C.c_uint32, stats]),
                 ("ort_radiance_adaptive", [vp, vp, vp, C.c_uint64, C.POINTER(Adaptive), C.c_float, vp, vp, vp, vp, C.c_uint32, stats]),
                 ("ort_irradiance", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_float, vp, vp, C.c_uint32, stats]),
-                ("ort_irradiance_adaptive", [vp, vp, vp, C.c_uint64, C.POINTER(Adaptive), C.c_float, vp, vp, vp, vp, C.c_uint32, stats])):
+                ("ort_irradiance_adaptive", [vp, vp, vp, C.c_uint64, C.POINTER(Adaptive), C.c_float, vp, vp, vp, vp, C.c_uint32, stats]),
+                ("ort_probe_sh", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_float, vp, vp, vp, C.c_uint32, stats])):
             getattr(L, name).argtypes = argtypes
             getattr(L, name + "_device").argtypes = argtypes[:-1] + [vp, stats]
         L.ort_camera_from_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.POINTER(Camera)]
@@ -397,6 +400,18 @@ def _rays(rays):
     if rays.ndim != 2 or rays.shape[1] != 6:
         raise ValueError("rays must be an (N, 6) array of o.xyz d.xyz, got shape %s" % (rays.shape,))
     return rays
+
+
+def _probe_points(points):
+    """-> (N, 6) float32 p.xyz n.xyz, C-contiguous: as given, or (N, 3) positions with the pole +z filled in"""
+    points = np.ascontiguousarray(points, dtype="<f4")
+    if points.ndim == 2 and points.shape[1] == 3:
+        pole = np.zeros((len(points), 3), "<f4")
+        pole[:, 2] = 1.0
+        return np.ascontiguousarray(np.concatenate([points, pole], axis=1))
+    if points.ndim != 2 or points.shape[1] != 6:
+        raise ValueError("points must be an (N, 3) array of p.xyz or an (N, 6) array of p.xyz n.xyz, got shape %s" % (points.shape,))
+    return points
 
 
 def _seeds(seeds, n):
@@ -1306,6 +1321,35 @@ class Scene:
                                            _flags(counters), _ptr(stream), st))
         return stats()
 
+    # -- SH light-probe queries: radiance over the sphere as 9 SH coefficients ------------------------
+    def probe_sh(self, points, seeds, spp, rr=0.8, want_rgb=False, want_states=False, counters=False):
+        """The radiance arriving at each point from all directions, projected onto the nine real spherical harmonics of bands
+        0 to 2 (world axes): spp samples, each a direction drawn uniformly over the sphere and then radiance()'s sample along
+        it, on the xorshift stream that starts at seeds[i] (0 is taken as 1).  points: (N, 3) float32 positions, or (N, 6)
+        p.xyz n.xyz as irradiance() takes them -- n is only the pole of the sample pattern, +z where positions alone are
+        given; a point outside irradiance()'s domain gives NaN in all 27 words and its seed back.  Returns (sh: float32[N, 9,
+        3] [point][coefficient][rgb], the MEAN of basis times radiance: the field's SH coefficients are 4 pi * sh, and
+        sh_irradiance() shades a normal from it), then rgb float32[N, 3] (the plain mean) with want_rgb, states uint32[N] with
+        want_states, and the stats dict; synchronous."""
+        points = _probe_points(points)
+        seeds = _seeds(seeds, len(points))
+        sh = np.zeros((len(points), SH_COEFFS, 3), "<f4")
+        rgb = np.zeros((len(points), 3), "<f4") if want_rgb else None
+        states = np.zeros(len(points), "<u4") if want_states else None
+        st, stats = _stats()
+        _check(lib().ort_probe_sh(self.handle, points.ctypes.data, seeds.ctypes.data, len(points), int(spp), float(rr), sh.ctypes.data,
+                                  rgb.ctypes.data if want_rgb else None, states.ctypes.data if want_states else None, _flags(counters), st))
+        return (sh,) + ((rgb,) if want_rgb else ()) + ((states,) if want_states else ()) + (stats(),)
+
+    def probe_sh_device(self, d_points, d_seeds, n, spp, rr, d_sh, d_rgb=0, d_states=0, stream=0, counters=False, want_stats=False):
+        """Device points (n x 6 float32) and seeds (n uint32) -> device coefficients (n x 27 float32) and, where a pointer is
+        given, plain means (n x 3 float32) and final states (n uint32): raw pointers on the scene's device, as
+        radiance_device()."""
+        st, stats = _stats(want_stats)
+        _check(lib().ort_probe_sh_device(self.handle, _ptr(d_points), _ptr(d_seeds), n, int(spp), float(rr), _ptr(d_sh), _ptr(d_rgb),
+                                         _ptr(d_states), _flags(counters), _ptr(stream), st))
+        return stats()
+
     def irradiance_adaptive(self, points, seeds, min_spp, max_spp, tolerance, floor=0.05, check_every=4, rr=0.8, want_states=False,
                             counters=False):
         """irradiance() with a sample count per point: radiance_adaptive()'s stopping rule, unchanged, over the point's
@@ -1466,6 +1510,40 @@ def _adaptive(min_spp, max_spp, check_every, tolerance, floor):
         if not 0 <= int(v) <= 0xFFFFFFFF:
             raise ValueError("%s must fit an unsigned 32-bit word, got %r" % (name, v))
     return Adaptive(int(min_spp), int(max_spp), int(check_every), float(tolerance), float(floor))
+
+
+def sh_basis(d):
+    """The nine real SH basis values of bands 0 to 2 at directions d (..., 3), float32, operation for operation as the
+    probe_sh() kernels form them (include/ort.h): every product and sum rounded to float32 on its own.  -> float32[..., 9]"""
+    d = np.asarray(d, dtype="<f4")
+    if d.shape[-1:] != (3,):
+        raise ValueError("d must be an (..., 3) array of directions, got shape %s" % (d.shape,))
+    F = np.float32
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    with np.errstate(all="ignore"):
+        b = [np.full(x.shape, F(0.282094792), "<f4"),
+             F(0.488602512) * y, F(0.488602512) * z, F(0.488602512) * x,
+             F(1.092548431) * (x * y), F(1.092548431) * (y * z), F(0.315391565) * (F(3.0) * (z * z) - F(1.0)),
+             F(1.092548431) * (x * z), F(0.546274215) * (x * x - y * y)]
+    return np.stack([np.asarray(v, "<f4") for v in b], axis=-1)
+
+
+SH_COSINE_LOBE = (np.pi, 2.0 * np.pi / 3.0, np.pi / 4.0)   # A_l of bands 0, 1, 2: the clamped cosine's zonal coefficients
+
+
+def sh_irradiance(sh, normals):
+    """The cosine-convolved irradiance a renderer evaluates per normal from probe_sh()'s coefficients:
+    4 pi * sum_j A_l(j) * sh[:, j] * Y_j(n), with A = pi, 2 pi / 3, pi / 4 per band, in float64.  sh: (N, 9, 3) or (9, 3);
+    normals: (N, 3) or (3,) unit vectors.  -> float64[N, 3] (or [3])"""
+    sh = np.asarray(sh, dtype=np.float64)
+    n = np.asarray(normals, dtype=np.float64)
+    if sh.shape[-2:] != (SH_COEFFS, 3) or n.shape[-1:] != (3,):
+        raise ValueError("sh must be (..., 9, 3) and normals (..., 3), got shapes %s and %s" % (sh.shape, n.shape))
+    x, y, z = n[..., 0], n[..., 1], n[..., 2]
+    Y = np.stack([np.full(x.shape, 0.282094792), 0.488602512 * y, 0.488602512 * z, 0.488602512 * x, 1.092548431 * (x * y), 1.092548431 * (y * z),
+                  0.315391565 * (3.0 * (z * z) - 1.0), 1.092548431 * (x * z), 0.546274215 * (x * x - y * y)], axis=-1)
+    A = np.array([SH_COSINE_LOBE[0]] + [SH_COSINE_LOBE[1]] * 3 + [SH_COSINE_LOBE[2]] * 5)
+    return 4.0 * np.pi * np.sum((A * Y)[..., :, None] * sh, axis=-2)
 
 
 def decode_prim(prim):

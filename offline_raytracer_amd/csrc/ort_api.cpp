@@ -460,12 +460,16 @@ static int check_adaptive(const ort_adaptive *ad) {
 
 /* radiance queries: count == 0 is OK whatever else is passed; then argument errors, then state errors.  adaptive: the same
    call with the stopping rule's parameters (ad, checked after the pointers) where spp stands, and out_spp and out_m2.  points: the
-   irradiance queries -- the same call with points (p, n) where the rays stand, the same checks in the same order */
+   irradiance queries -- the same call with points (p, n) where the rays stand, the same checks in the same order.  sh: the SH
+   light-probe query (points, not adaptive) -- out_sh is the required output in out_rgb's place, and out_rgb is optional */
 static int radiance_common(ort_scene *s, const ort::QueryCall &q, const void *rays, const void *seeds, uint32_t spp, float rr, bool adaptive,
-                           const ort_adaptive *ad, void *out_rgb, void *out_spp, void *out_m2, void *final_states, bool points = false) {
+                           const ort_adaptive *ad, void *out_rgb, void *out_spp, void *out_m2, void *final_states, bool points = false, bool sh = false,
+                           void *out_sh = nullptr) {
     if (q.count == 0) return nothing_to_do(q.stats);
     if (!s) return fail(ORT_ERR_INVALID, "null scene");
-    int rc = check_ptrs({{rays, true, 8}, {seeds, true, 4}, {out_rgb, true, 4}, {out_spp, false, 4}, {out_m2, false, 4}, {final_states, false, 4}},
+    int rc = sh ? check_ptrs({{rays, true, 8}, {seeds, true, 4}, {out_sh, true, 4}, {out_rgb, false, 4}, {final_states, false, 4}}, "null points, seeds or out_sh",
+                             "points must be 8-byte aligned", "seeds, out_sh, out_rgb and final_states must be 4-byte aligned")
+                : check_ptrs({{rays, true, 8}, {seeds, true, 4}, {out_rgb, true, 4}, {out_spp, false, 4}, {out_m2, false, 4}, {final_states, false, 4}},
                         points ? "null points, seeds or out_rgb" : "null rays, seeds or out_rgb", points ? "points must be 8-byte aligned" : "rays must be 8-byte aligned",
                         adaptive ? "seeds, out_rgb, out_spp, out_m2 and final_states must be 4-byte aligned" : "seeds, out_rgb and final_states must be 4-byte aligned");
     if (rc != ORT_OK) return rc;
@@ -474,7 +478,7 @@ static int radiance_common(ort_scene *s, const ort::QueryCall &q, const void *ra
     if (!(rr >= 0.0f && rr < 1.0f)) return fail(ORT_ERR_INVALID, "rr must be in [0, 1): at 1 a path in a closed room never ends");
     if ((rc = check_resident(s)) != ORT_OK) return rc;
     std::string err;
-    rc = ort::device_radiance(s, q, rays, seeds, spp, rr, adaptive ? ad : nullptr, out_rgb, out_spp, out_m2, final_states, points, &err);
+    rc = ort::device_radiance(s, q, rays, seeds, spp, rr, adaptive ? ad : nullptr, out_rgb, out_spp, out_m2, final_states, points, sh ? out_sh : nullptr, &err);
     return rc == ORT_OK ? ORT_OK : fail(rc, err);
 }
 
@@ -962,6 +966,8 @@ int ort_radiance_device(ort_scene *s, const void *d_rays, const void *d_seeds, u
 int ort_radiance_adaptive(ort_scene *s, const float *rays, const uint32_t *seeds, uint64_t count, const ort_adaptive *ad, float rr, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {true, count, flags, nullptr, stats}, rays, seeds, 0, rr, true, ad, out_rgb, out_spp, out_m2, final_states); }); }
 int ort_irradiance(ort_scene *s, const float *points, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr, float *out_rgb, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {true, count, flags, nullptr, stats}, points, seeds, spp, rr, false, nullptr, out_rgb, nullptr, nullptr, final_states, true); }); }
 int ort_irradiance_device(ort_scene *s, const void *d_points, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {false, count, flags, hip_stream, stats}, d_points, d_seeds, spp, rr, false, nullptr, d_out_rgb, nullptr, nullptr, d_final_states, true); }); }
+int ort_probe_sh(ort_scene *s, const float *points, const uint32_t *seeds, uint64_t count, uint32_t spp, float rr, float *out_sh, float *out_rgb, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {true, count, flags, nullptr, stats}, points, seeds, spp, rr, false, nullptr, out_rgb, nullptr, nullptr, final_states, true, true, out_sh); }); }
+int ort_probe_sh_device(ort_scene *s, const void *d_points, const void *d_seeds, uint64_t count, uint32_t spp, float rr, void *d_out_sh, void *d_out_rgb, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {false, count, flags, hip_stream, stats}, d_points, d_seeds, spp, rr, false, nullptr, d_out_rgb, nullptr, nullptr, d_final_states, true, true, d_out_sh); }); }
 int ort_irradiance_adaptive(ort_scene *s, const float *points, const uint32_t *seeds, uint64_t count, const ort_adaptive *ad, float rr, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, uint32_t flags, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {true, count, flags, nullptr, stats}, points, seeds, 0, rr, true, ad, out_rgb, out_spp, out_m2, final_states, true); }); }
 int ort_irradiance_adaptive_device(ort_scene *s, const void *d_points, const void *d_seeds, uint64_t count, const ort_adaptive *ad, float rr, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {false, count, flags, hip_stream, stats}, d_points, d_seeds, 0, rr, true, ad, d_out_rgb, d_out_spp, d_out_m2, d_final_states, true); }); }
 int ort_radiance_adaptive_device(ort_scene *s, const void *d_rays, const void *d_seeds, uint64_t count, const ort_adaptive *ad, float rr, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, uint32_t flags, void *hip_stream, ort_stats *stats) { return guarded([&]() { return radiance_common(s, {false, count, flags, hip_stream, stats}, d_rays, d_seeds, 0, rr, true, ad, d_out_rgb, d_out_spp, d_out_m2, d_final_states); }); }

@@ -108,7 +108,7 @@ struct DeviceScene {
     DevBuf obj_src; /* ID-matte renders BY_OBJECT (device_render_matte): prim_src with a triangle's word naming its mesh, built at the first such render */
     float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0}; /* shapes and camera (raycast_needs_exact) */
     bool scene_box_known = false;
-    DevBuf query_stage[6]; /* the i-th array of the host form in flight (run_query); six: the adaptive radiance query's */
+    DevBuf query_stage[7]; /* the i-th array of the host form in flight (run_query); seven: the radiance queries' six and the SH light-probe query's sums */
 };
 
 int device_count(int *n, std::string *err) {
@@ -606,6 +606,7 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
    is the plumbing around them: one launch path (launch_query) and one host-form loop (run_sliced) for the three */
 constexpr uint64_t kRaycastSlice = 1ull << 22;  /* rays per launch of the host form of ort_raycast and ort_occluded (2 x 96 MB of staging) */
 constexpr uint64_t kRadianceSlice = 1ull << 20; /* ... of ort_radiance and ort_radiance_adaptive: a ray is spp paths; 44 and 52 MB of staging */
+constexpr uint64_t kProbeShSlice = 1ull << 18;  /* ... of ort_probe_sh: a point is spp paths and 148 bytes; 39 MB of staging */
 /* tests/test_gpu_slice_boundary.py mirrors both: it runs every query over one slice and a ragged remainder */
 
 /* the inverse of the tree's slot maps, in PrimInfo order (triangles | boxes | cylinders | spheres): slot -> kind << 28 |
@@ -931,21 +932,25 @@ int device_render_matte(Scene *scene, const ort_render_params *p, const ort_view
    table: a colour names no shape.  With ad (checked by the caller) the adaptive query: the stopping rule's parameters where spp
    stands, and, where asked for, every ray's sample count and its sum of squared sample luminance; plan_radiance's plan as it
    is, the kernels ort_kernels_adaptive.hip's.  With points the irradiance queries: the array holds (p, n) where a ray's (o, d)
-   stand -- the same bytes, staging and view -- and the kernels, plain or adaptive, are ort_kernels_irradiance.hip's */
+   stand -- the same bytes, staging and view -- and the kernels, plain or adaptive, are ort_kernels_irradiance.hip's.  With out_sh
+   (points then, and no ad) the SH light-probe query: one more array of 27 floats a point, which the view gets as sh_out; out may
+   then be null */
 int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const void *seeds, uint32_t spp, float rr, const ort_adaptive *ad, void *out,
-                    void *out_spp, void *out_m2, void *states, bool points, std::string *err) {
+                    void *out_spp, void *out_m2, void *states, bool points, void *out_sh, std::string *err) {
     DeviceScene *d;
     int rc;
     if ((rc = begin_query(scene, q.stats, &d, err))) return rc;
     hipStream_t stream = (hipStream_t)q.stream;
     const bool counters = (q.flags & ORT_RENDER_COUNTERS) != 0;
-    const QueryArray arrays[] = {{rays, 24u, false}, {seeds, 4u, false}, {out, 12u, true}, {out_spp, 4u, true}, {out_m2, 4u, true}, {states, 4u, true}};
-    return run_query(d, q, kRadianceSlice, arrays, err, [&](void *const *p, uint64_t n) {
+    const QueryArray arrays[] = {{rays, 24u, false}, {seeds, 4u, false}, {out, 12u, true}, {out_spp, 4u, true}, {out_m2, 4u, true}, {states, 4u, true}, {out_sh, 108u, true}};
+    return run_query(d, q, out_sh ? kProbeShSlice : kRadianceSlice, arrays, err, [&](void *const *p, uint64_t n) {
         RenderView rv{};
         if (ad) radiance_adaptive_view(ray_query_io(scene, d, p[0]), p[1], *ad, rr, p[2], p[3], p[4], p[5], &rv);
         else radiance_view(ray_query_io(scene, d, p[0]), p[1], spp, rr, p[2], p[5], &rv);
+        rv.sh_out = (float *)p[6];
         return launch_query(scene, d, rv, n, true, counters, stream, q.stats, err, [&](const SceneView &sv, const RenderHot &hot, const QueryPlan &pl) {
-            if (points) ort_launch_irradiance(pl, ad != nullptr, stream, sv, hot);
+            if (out_sh) ort_launch_probe_sh(pl, stream, sv, hot);
+            else if (points) ort_launch_irradiance(pl, ad != nullptr, stream, sv, hot);
             else if (ad) ort_launch_radiance_adaptive(pl, stream, sv, hot);
             else with_bools([&](auto C, auto D, auto T) {
                 hipLaunchKernelGGL((radiance_rays<decltype(C)::value, decltype(D)::value, decltype(T)::value>), dim3(pl.grid), dim3(kBlock), 0, stream, sv, hot);

@@ -163,6 +163,10 @@ struct RenderView {
        pixel, the undivided colour sum; ad_spp, the samples a pixel has had; ad_m2 (may be null) and final_states as above.  out
        (may be null) is written alone */
     float *acc_sum;
+    /* SH light-probe queries (ort_probe_sh; the probe_sh_points kernels): the irradiance queries' fields, and sh_out, job_count x 27
+       floats, [point][coefficient][rgb]: a point's words ARE its 27 sums while its job runs, as group_out's are a pixel's.  out
+       (may be null here) holds the plain means */
+    float *sh_out;
 };
 
 /* ---- the order in which a CHUNK render issues its jobs ----------------------------------------------------------
@@ -295,6 +299,7 @@ void ort_launch_w5(const ort::KernelVariant &v, unsigned int grid, hipStream_t s
 void ort_launch_pixel_jobs(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);      /* KF_ADAPTIVE to KF_ACCUM: ort_kernels_render_adaptive.hip */
 void ort_launch_radiance_adaptive(const ort::QueryPlan &pl, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);                    /* ort_kernels_adaptive.hip */
 void ort_launch_irradiance(const ort::QueryPlan &pl, bool adaptive, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);            /* ort_kernels_irradiance.hip */
+void ort_launch_probe_sh(const ort::QueryPlan &pl, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);                             /* ort_kernels_irradiance.hip */
 #endif
 
 /* The lane code and the limits it is built for: a unit that compiles them at limits of its own, or beside ort_kernels.hip's,
@@ -484,6 +489,15 @@ constexpr uint32_t LF_SPPMAP = 1u << 16;
    through the traversal loop.  A pixel's words are one lane's for the length of its job: no atomics.  Everything of it sits
    under if constexpr (ACCUM) */
 constexpr uint32_t LF_ACCUM = 1u << 17;
+/* SH: SH light-probe queries (ort_probe_sh; with RAYS and HEMI, never ADAPT): the irradiance query's job with the direction's cosine
+   drawn uniformly, c = 1 - 2 e0 (the whole sphere about the pole n), and, whenever a sample adds an emission e to the point's sum,
+   b_j(d) * e added to the point's nine SH sums, d being the sample's PRIMARY direction and b_j the real SH basis of bands 0 to 2 in
+   world axes (sh_basis_add).  d is not in P.dir once the path has bounced, so the lane keeps it in three words of LDS
+   (produce_ray's focal_cache, unused under RAYS): written where the primary ray is composed, read only when an emission is added
+   -- no registers through the traversal loop, no second sin/cos.  The 27 sums are the point's own words of rv.c->sh_out, as GROUPS
+   keeps its sums: zeroed at the job's start, one load, add and store per word and emission, divided in place at the job's end.
+   rv.c->out is an optional array here.  Everything of it sits under if constexpr (SH) */
+constexpr uint32_t LF_SH = 1u << 18;
 /* the walk's own options */
 constexpr uint32_t LF_TREELET = 1u << 10;     /* traverse: the top of the binary tree is read from the LDS tables (with TABS, never WIDE) */
 constexpr uint32_t LF_ANNOUNCE = 1u << 11;    /* traverse asks for a finished ray's PrimInfo (announce_winner); resolve_hit then finds it ANNOUNCED */
@@ -500,7 +514,7 @@ constexpr uint32_t LF_OF_PROLOGUE = LF_COUNTERS | LF_TABS | LF_HAS_EXCL;
 constexpr uint32_t LF_OF_BEGIN_RAY = LF_COUNTERS | LF_TABS;
 constexpr uint32_t LF_OF_TRAVERSE = LF_COUNTERS | LF_TREELET | LF_ANNOUNCE | LF_WIDE;
 constexpr uint32_t LF_OF_RESOLVE_HIT = LF_COUNTERS | LF_TABS | LF_ANNOUNCE | LF_WIDE;
-constexpr uint32_t LF_OF_PRODUCE_RAY = LF_COUNTERS | LF_DIFFUSE | LF_TABS | LF_IMPLICIT | LF_VIEWS | LF_RAYS | LF_ADAPT | LF_HEMI | LF_GROUPS | LF_SPPMAP | LF_ACCUM;
+constexpr uint32_t LF_OF_PRODUCE_RAY = LF_COUNTERS | LF_DIFFUSE | LF_TABS | LF_IMPLICIT | LF_VIEWS | LF_RAYS | LF_ADAPT | LF_HEMI | LF_GROUPS | LF_SPPMAP | LF_ACCUM | LF_SH;
 constexpr uint32_t LF_OF_LANE = LF_OF_PRODUCE_RAY | LF_WIDE; /* pt_lane ... radiance_lane: a job's flavour */
 /* ... and, from a lane's flavour f, the words of the three steps of its loop: begin_ray (and a prologue in its place); traverse,
    where finished rays announce their winners and the top of the binary tree comes from the LDS tables if there are any; and the
@@ -513,7 +527,7 @@ constexpr uint32_t resolve_of(uint32_t f) { return (f & (LF_COUNTERS | LF_TABS |
 constexpr bool flavour_ok(uint32_t f, uint32_t reads) {
     const bool IMPLICIT = f & LF_IMPLICIT, WIDE = f & LF_WIDE, VIEWS = f & LF_VIEWS, RAYS = f & LF_RAYS, ADAPT = f & LF_ADAPT;
     const bool HEMI = f & LF_HEMI, GROUPS = f & LF_GROUPS, TREELET = f & LF_TREELET, EXACT_ORDER = f & LF_EXACT_ORDER;
-    const bool SPPMAP = f & LF_SPPMAP, ACCUM = f & LF_ACCUM;
+    const bool SPPMAP = f & LF_SPPMAP, ACCUM = f & LF_ACCUM, SH = f & LF_SH;
     return (f & ~reads) == 0u
         && (!RAYS || (IMPLICIT && !VIEWS))                        /* a caller's ray array is an implicit job space of its own */
         && (!ADAPT || (IMPLICIT && (RAYS || VIEWS)))              /* the adaptive rule is built for the radiance queries and for one-pixel jobs of a batch of views */
@@ -521,6 +535,7 @@ constexpr bool flavour_ok(uint32_t f, uint32_t reads) {
         && (!GROUPS || (IMPLICIT && VIEWS && !RAYS && !ADAPT))    /* the group sums are built for plain one-pixel jobs of a batch of views */
         && (!SPPMAP || (IMPLICIT && VIEWS && !RAYS && !ADAPT && !GROUPS)) /* the sample map cuts plain one-pixel jobs of a batch of views */
         && (!ACCUM || SPPMAP)                                     /* accumulation continues the sample map's jobs */
+        && (!SH || (HEMI && !ADAPT))                              /* the SH sums are built for the plain job of points */
         && (!WIDE || !(VIEWS || RAYS || ADAPT || HEMI || GROUPS || SPPMAP || TREELET)) /* the 4-wide tree serves the single frame's plain loop, and has no treelet */
         && (!EXACT_ORDER || !(f & (LF_FINITE_RAY | LF_FROM_TAB))); /* the exact walk reads HBM */
 }
@@ -1273,14 +1288,37 @@ struct RayPass {
 /* what a lane that asked for a job got */
 enum JobTake { JOB_TAKEN, JOB_SKIPPED /* nothing to run in it: ask again */, JOB_NONE_LEFT, JOB_PARKED /* ray exchange: a parked path comes first */ };
 
+/* SH: the real spherical-harmonic basis of bands 0 to 2 at the direction d = (x, y, z), in world axes and in include/ort.h's order
+   and operations (ort_probe_sh), every one a separately rounded f32 operation: b[0] is b1 ... b[7] is b8; b0 is the constant kShB0 */
+constexpr float kShB0 = 0.282094792f;
+struct ShBasis { float b1, b2, b3, b4, b5, b6, b7, b8; };
+ORT_D ShBasis sh_basis(V3 d) {
+    const float x = d.x, y = d.y, z = d.z;
+    ShBasis b;
+    b.b1 = 0.488602512f * y; b.b2 = 0.488602512f * z; b.b3 = 0.488602512f * x;
+    b.b4 = 1.092548431f * (x * y); b.b5 = 1.092548431f * (y * z); b.b6 = 0.315391565f * (3.0f * (z * z) - 1.0f);
+    b.b7 = 1.092548431f * (x * z); b.b8 = 0.546274215f * (x * x - y * y);
+    return b;
+}
+/* ... and S[j] = S[j] + b_j * e for the nine triples at q: the product rounded, then the sum; one load, add and store per word */
+ORT_D void sh_add1(float *q, float b, V3 e) { q[0] = q[0] + b * e.x; q[1] = q[1] + b * e.y; q[2] = q[2] + b * e.z; }
+ORT_D void sh_basis_add(float *q, V3 d, V3 e) {
+    const ShBasis b = sh_basis(d);
+    sh_add1(q, kShB0, e); sh_add1(q + 3, b.b1, e); sh_add1(q + 6, b.b2, e); sh_add1(q + 9, b.b3, e); sh_add1(q + 12, b.b4, e);
+    sh_add1(q + 15, b.b5, e); sh_add1(q + 18, b.b6, e); sh_add1(q + 21, b.b7, e); sh_add1(q + 24, b.b8, e);
+}
+constexpr uint32_t kShWords = 27u; /* ORT_SH_COEFFS x rgb */
+/* the point's 27 words of rv.c->sh_out; the point's index as write_ray_record forms it */
+ORT_D float *sh_point_ptr(const RenderHot &rv, const PathState &P) { return rv.c->sh_out + kShWords * (((size_t)P.pxy << 32) | P.job_index); }
+
 /* PS_HIT, a traversal has finished: ray.cpp:817 then :1251-1277 (primary) or :1355-1421 (bounce).  Returns whether the path
    bounces: then s.n, s.m, s.draw and s.angle are the bounce's.  Otherwise the sample has ended: P.sample counts it and (ADAPT) the
    stopping rule has been asked where a check is due */
 template <uint32_t F>
 ORT_D bool shade_arrival(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, uint32_t spp_u,
-                         AdaptState *A, RayPass &s) {
+                         AdaptState *A, RayPass &s, [[maybe_unused]] const float *dir_cache = nullptr, [[maybe_unused]] int dir_stride = 0) {
     constexpr bool COUNTERS = F & LF_COUNTERS, DIFFUSE = F & LF_DIFFUSE, TABS = F & LF_TABS;
-    constexpr bool ADAPT = F & LF_ADAPT, GROUPS = F & LF_GROUPS, SPPMAP = F & LF_SPPMAP;
+    constexpr bool ADAPT = F & LF_ADAPT, GROUPS = F & LF_GROUPS, SPPMAP = F & LF_SPPMAP, SH = F & LF_SH;
     bool alive = true;
     const uint32_t hit_mat = h.hit_mat; /* resolve_hit: 0 = nothing hit */
     s.n = normalize(h.hit_n);
@@ -1305,6 +1343,8 @@ ORT_D bool shade_arrival(const SceneView &sv, const RenderHot &rv, const float4 
                     q[0] = q[0] + e.x; q[1] = q[1] + e.y; q[2] = q[2] + e.z;
                 }
             }
+            if constexpr (SH) /* the sample's primary direction, from the lane's three words (produce_ray wrote them) */
+                sh_basis_add(sh_point_ptr(rv, P), mk(dir_cache[0], dir_cache[dir_stride], dir_cache[2 * dir_stride]), e);
         }
         alive = false;
     } else {
@@ -1392,8 +1432,15 @@ ORT_D V3 job_mean(const RenderHot &rv, const PathState &P, uint32_t job_spp) {
 template <uint32_t F>
 ORT_D void write_ray_record(const RenderHot &rv, const PathState &P, const AdaptState *A, V3 o) {
     const size_t ray = ((size_t)P.pxy << 32) | P.job_index;
-    float *p = rv.c->out + 3u * ray;
-    p[0] = o.x; p[1] = o.y; p[2] = o.z;
+    if constexpr (F & LF_SH) { /* the 27 sums become means where they stand; the plain mean if asked for */
+        const float fs = (float)rv.c->spp;
+        float *q = sh_point_ptr(rv, P);
+        for (uint32_t k = 0; k < kShWords; ++k) q[k] = q[k] / fs;
+        if (rv.c->out) { float *p = rv.c->out + 3u * ray; p[0] = o.x; p[1] = o.y; p[2] = o.z; }
+    } else {
+        float *p = rv.c->out + 3u * ray;
+        p[0] = o.x; p[1] = o.y; p[2] = o.z;
+    }
     if (rv.c->final_states) rv.c->final_states[ray] = P.rng;
     if constexpr (F & LF_ADAPT) {
         if (rv.c->ad_spp) rv.c->ad_spp[ray] = P.sample;
@@ -1474,8 +1521,14 @@ ORT_D bool decode_ray_job(const RenderHot &rv, PathState &P, unsigned long long 
     const Ray6 r = load_ray(rv.c->rays, j);
     const uint32_t seed = rv.c->seeds[j];
     if (!in_query_domain(r.o, r.d)) {
-        float *p = rv.c->out + 3u * (size_t)j;
-        p[0] = p[1] = p[2] = om_bits_f32(0x7fc00000u);
+        if constexpr (F & LF_SH) { /* all 27 words, and the optional mean */
+            float *q = rv.c->sh_out + kShWords * (size_t)j;
+            for (uint32_t k = 0; k < kShWords; ++k) q[k] = om_bits_f32(0x7fc00000u);
+            if (rv.c->out) { float *p = rv.c->out + 3u * (size_t)j; p[0] = p[1] = p[2] = om_bits_f32(0x7fc00000u); }
+        } else {
+            float *p = rv.c->out + 3u * (size_t)j;
+            p[0] = p[1] = p[2] = om_bits_f32(0x7fc00000u);
+        }
         if (rv.c->final_states) rv.c->final_states[j] = seed;
         if constexpr (F & LF_ADAPT) {
             if (rv.c->ad_spp) rv.c->ad_spp[j] = 0u;
@@ -1610,7 +1663,10 @@ ORT_D void begin_pixel(const RenderHot &rv, PathState &P, const SceneCamera &cam
             q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
         }
     }
-    if (focal_cache) { /* the pixel's focal point, once per pixel (persistent kernel: three floats of LDS per lane) */
+    if constexpr (F & LF_SH) { /* the point's 27 sums start at +0 where they stand; focal_cache is the lane's direction words */
+        float *q = sh_point_ptr(rv, P);
+        for (uint32_t k = 0; k < kShWords; ++k) q[k] = 0.0f;
+    } else if (focal_cache) { /* the pixel's focal point, once per pixel (persistent kernel: three floats of LDS per lane) */
         V3 f;
         if constexpr (F & LF_VIEWS) f = view_focal_point(rv, P.pxy, load_view_camera(rv, P.job_index));
         else f = focal_point(rv, P.pxy, cam.v.p, cam.v.x, cam.v.y, cam.v.z, cam.focal_length);
@@ -1628,7 +1684,8 @@ ORT_D void primary_sample(const RenderHot &rv, PathState &P, const SceneCamera &
         s.ray_d = r.d;
         if constexpr (F & LF_HEMI) { /* the diffuse lobe's draw (sample_brdf_draw without the choice); its azimuth is the pass's one angle */
             const float e0 = rng_01(P.rng), e1 = rng_01(P.rng);
-            s.hemi_c = __builtin_sqrtf(e0); /* ray.cpp:1123 */
+            if constexpr (F & LF_SH) s.hemi_c = 1.0f - 2.0f * e0; /* uniform over the sphere about the pole */
+            else s.hemi_c = __builtin_sqrtf(e0); /* ray.cpp:1123 */
             s.angle = 2.0f * kPi * e1;
         }
     } else {
@@ -1741,7 +1798,8 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
         ORT_PHASE(pr, sv, 8, true);
         RayPass s;
         if (P.ps == PS_HIT) {
-            s.bounce = shade_arrival<F>(sv, rv, tab, P, h, c, spp_u, A, s);
+            if constexpr (F & LF_SH) s.bounce = shade_arrival<F>(sv, rv, tab, P, h, c, spp_u, A, s, focal_cache, focal_stride);
+            else s.bounce = shade_arrival<F>(sv, rv, tab, P, h, c, spp_u, A, s);
             ORT_PHASE(pr, sv, 1, true);
         }
         if (!s.bounce) {
@@ -1772,6 +1830,9 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
         ort_sincosf(s.angle, &sn, &cs);
         if (DIFFUSE) compose_ray_diffuse<F>(rv, P, cam, s, cs, sn);
         else compose_ray_all_lobes<F>(rv, P, cam, s, cs, sn);
+        if constexpr (F & LF_SH) { /* the sample's primary direction d, for the emissions its path adds after it has bounced */
+            if (!s.bounce) { focal_cache[0] = P.dir.x; focal_cache[focal_stride] = P.dir.y; focal_cache[2 * focal_stride] = P.dir.z; }
+        }
         ORT_PHASE(pr, sv, 3, true);
         return true;
     }
@@ -2515,6 +2576,19 @@ ORT_D void unit_eval_op(uint32_t op, const float *a, float *o) {
         const V3 d = normalize(sample_lobe_n(normalize(in3(1)), __builtin_sqrtf(e0), cs, sn));
         const V3 wo = neg(normalize(d));
         o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = wo.x; o[4] = wo.y; o[5] = wo.z; o[6] = om_bits_f32(seed);
+    } break;
+    case 21: { /* produce_ray's sphere draw (SH): op 20 with c = 1 - 2 e0 */
+        uint32_t seed = om_f32_bits(a[0]);
+        const float e0 = rng_01(seed), e1 = rng_01(seed);
+        float sn, cs;
+        ort_sincosf(2.0f * kPi * e1, &sn, &cs);
+        const V3 d = normalize(sample_lobe_n(normalize(in3(1)), 1.0f - 2.0f * e0, cs, sn));
+        const V3 wo = neg(normalize(d));
+        o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = wo.x; o[4] = wo.y; o[5] = wo.z; o[6] = om_bits_f32(seed);
+    } break;
+    case 22: { /* the SH basis (SH): d.xyz -> b1 ... b8 (b0 is a constant) */
+        const ShBasis b = sh_basis(in3(0));
+        o[0] = b.b1; o[1] = b.b2; o[2] = b.b3; o[3] = b.b4; o[4] = b.b5; o[5] = b.b6; o[6] = b.b7; o[7] = b.b8;
     } break;
     default: break;
     }
@@ -3512,10 +3586,12 @@ matte_pixels(SceneView sv, RenderHot rv, MatteIO io) {
 /* ADAPT: the adaptive query (ort_radiance_adaptive): the same loop, the job ending where produce_ray's stopping rule says */
 /* HEMI: the irradiance queries (ort_irradiance, ort_irradiance_adaptive): the same loop over points, every sample's primary
    direction drawn in the lane (produce_ray's HEMI flag); the drawn direction passes raycast_needs_exact like a caller's */
+/* SH: the SH light-probe query (ort_probe_sh): HEMI's loop with the direction drawn over the whole sphere and the nine SH sums
+   beside the colour's (produce_ray's SH flag); dir_cache is where the lane keeps a sample's primary direction */
 template <uint32_t F>
 ORT_D void radiance_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, const int tid, const uint32_t lane_id,
-                         unsigned long long *pool) {
-    constexpr uint32_t JOB = F | LF_IMPLICIT | LF_RAYS; /* the caller names what varies: COUNTERS, DIFFUSE, TABS, ADAPT, HEMI */
+                         unsigned long long *pool, float *dir_cache = nullptr /* SH: the lane's own three words, kBlock apart */) {
+    constexpr uint32_t JOB = F | LF_IMPLICIT | LF_RAYS; /* the caller names what varies: COUNTERS, DIFFUSE, TABS, ADAPT, HEMI, SH */
     static_assert(flavour_ok(JOB, LF_OF_LANE), "see flavour_ok");
     constexpr bool COUNTERS = F & LF_COUNTERS;
     uint32_t spill[kSpillStack];
@@ -3530,7 +3606,8 @@ ORT_D void radiance_lane(const SceneView &sv, const RenderHot &rv, const float4 
     for (;;) {
         if (!tracing) {
             if (P.ps == PS_HIT) resolve_hit<resolve_of(F), kLdsStack, kBlock>(sv, tab, P.org, P.dir, T.inv_d, lane_id, h, c, pr, lds_stack, spill, tid);
-            tracing = produce_ray<JOB>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool, &A);
+            if constexpr (F & LF_SH) tracing = produce_ray<JOB>(sv, rv, tab, P, h, c, pr, dir_cache, kBlock, spp_u, nullptr, false, pool, &A);
+            else tracing = produce_ray<JOB>(sv, rv, tab, P, h, c, pr, nullptr, 0, spp_u, nullptr, false, pool, &A);
             if (tracing) {
                 begin_ray<begin_of(F), kLdsStack, kBlock>(sv, tab, P, T, h, c, pr, lds_stack, spill, tid);
                 if (P.primary) { /* the facts raycast_needs_exact asks for, from the launch's copy (kept in this form: in a helper the radiance kernels' code moves) */
@@ -3589,6 +3666,19 @@ irradiance_adaptive_points(SceneView sv, RenderHot rv) {
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
     radiance_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_ADAPT | LF_HEMI>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool));
+}
+/* the SH light-probe query's eight (ort_kernels_irradiance.hip), as irradiance_points; lds_dir holds every lane's primary direction,
+   dir[component][lane] as the pt_* kernels' lds_focal: 3 KB beside the stack's 24, so four blocks a CU still fit */
+template <bool COUNTERS, bool DIFFUSE, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+probe_sh_points(SceneView sv, RenderHot rv) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ float lds_dir[3 * kBlock];
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as raycast_rays */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    if (TABS) fill_tab(sv, lds_tab);
+    radiance_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_HEMI | LF_SH>(sv, rv, lds_tab, lds_stack, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, wave_job_pool(rv, lds_pool),
+                                                                                                                     lds_dir + threadIdx.x);
 }
 #endif
 

@@ -260,9 +260,10 @@ int device_ambient_occlusion(Scene *scene, const QueryCall &q, const void *point
 /* radiance: count rays and seeds -> colours and, where asked for (null otherwise), final states.  ad == null: exactly spp samples
    per ray; otherwise the adaptive query (spp unread): the stopping rule's parameters, and two more optional outputs (samples
    taken, sum of squared sample luminance).  points: the irradiance queries -- the array holds count points (p, n) in the rays'
-   place, and every sample's direction is drawn about n */
+   place, and every sample's direction is drawn about n.  out_sh (with points, without ad; null otherwise): the SH light-probe
+   query -- the direction is drawn over the whole sphere, out_sh gets 27 floats a point and out may be null */
 int device_radiance(Scene *scene, const QueryCall &q, const void *rays, const void *seeds, uint32_t spp, float rr, const ort_adaptive *ad, void *out,
-                    void *out_spp, void *out_m2, void *states, bool points, std::string *err);
+                    void *out_spp, void *out_m2, void *states, bool points, void *out_sh, std::string *err);
 /* first-hit feature renders: view_count frames of p's rect (checked by the caller: PIXEL, no shards, not packed), view v from
    views[v].camera on views[v].seed, p->spp camera samples a pixel -> the planes asked for (null otherwise), view-major.  q.count is
    unread.  The host form stages every plane whole both ways, as device_render does, so that pixels outside the rect keep what they

@@ -26,6 +26,8 @@
  *   or: host_sim --irradiance scn base points.f32 seeds.u32 spp rr out.f32 states.u32            (points: p, n, 6 floats each)
  *   or: host_sim --irradiance-adaptive scn base points.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
  *       (the irradiance queries: the two modes above over points, radiance_lane with LF_HEMI)
+ *   or: host_sim --probe-sh scn base points.f32 seeds.u32 spp rr sh.f32 out.f32|- states.u32|-      (sh: 27 floats a point)
+ *       (the SH light-probe query: --irradiance with LF_SH and one more output file; out and states given as - are not passed)
  *   or: host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32   (cams: p, x, y, z axes, 12 floats a view)
  *       (as on the device, one view is the single-frame lane with that view's camera and seed: the VIEWS lanes run from two views on)
  *   or: host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32
@@ -402,6 +404,35 @@ static int radiance_mode(char **a) { /* scn base rays.f32 seeds.u32 spp rr out.f
     });
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return write_bytes(a[6], out.data(), 12 * n) && write_bytes(a[7], states.data(), 4 * n) ? 0 : 1;
+}
+
+/* the SH light-probe query's lanes (--probe-sh): radiance_lane with LF_HEMI | LF_SH; the lane's direction words are the worker's
+   focal cache, as the camera lanes use it */
+static int probe_sh_mode(char **a) { /* scn base points.f32 seeds.u32 spp rr sh.f32 out.f32|- states.u32|- */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
+    size_t n = 0;
+    std::vector<float2> points;
+    std::vector<uint32_t> seeds;
+    if (!read_rays(a[2], points, &n) || !read_array(a[3], seeds, n, "seeds")) return 1;
+    const bool want_out = std::string(a[7]) != "-", want_states = std::string(a[8]) != "-";
+    std::vector<float> sh(27 * n, -7.0f), out(want_out ? 3 * n : 0, -7.0f); /* every word is written: one that is not keeps its filler */
+    std::vector<uint32_t> states(want_states ? n : 0, 0xddddddddu);
+    const RaycastIO q = sim_query_io(S, points.data());
+    RenderView rv{};
+    radiance_view(q, seeds.data(), (uint32_t)strtoul(a[4], 0, 10), (float)atof(a[5]), want_out ? out.data() : nullptr, want_states ? states.data() : nullptr, &rv);
+    rv.sh_out = sh.data();
+    const RenderHot hot = query_hot(S, rv, n);
+    const bool diffuse_only = getenv("SIM_DIFFUSE") != nullptr; /* caller vouches for Ks = Kt = 0 */
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
+        with_bools([&](auto D, auto T) {
+            radiance_lane<LF_COUNTERS | lf_if(decltype(D)::value, LF_DIFFUSE) | lf_if(decltype(T)::value, LF_TABS) | LF_HEMI | LF_SH>(sv, hot, S.tab, stack, 0, w, nullptr, focal);
+        }, diffuse_only, S.tab != nullptr);
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return write_bytes(a[6], sh.data(), 108 * n) && (!want_out || write_bytes(a[7], out.data(), 12 * n)) &&
+           (!want_states || write_bytes(a[8], states.data(), 4 * n)) ? 0 : 1;
 }
 
 /* the adaptive query: radiance_lane with LF_ADAPT; tolerance and floor are read as float bits when written 0x........ (a test can
@@ -1107,6 +1138,7 @@ int main(int argc, char **argv) {
     if (argc == 16 && mode == "--radiance-adaptive") return radiance_adaptive_mode<false>(argv + 2);
     if (argc == 10 && mode == "--irradiance") return radiance_mode<true>(argv + 2);
     if (argc == 16 && mode == "--irradiance-adaptive") return radiance_adaptive_mode<true>(argv + 2);
+    if (argc == 11 && mode == "--probe-sh") return probe_sh_mode(argv + 2);
     if (argc == 12 && mode == "--views") return views_mode(argv + 2);
     if (argc == 21 && mode == "--render-adaptive") return render_adaptive_mode(argv + 2);
     if (argc == 19 && mode == "--light-groups") return light_groups_mode(argv + 2);
@@ -1123,6 +1155,7 @@ int main(int argc, char **argv) {
                         "       host_sim --radiance-adaptive scn base rays.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
                         "       host_sim --irradiance scn base points.f32 seeds.u32 spp rr out.f32 states.u32\n"
                         "       host_sim --irradiance-adaptive scn base points.f32 seeds.u32 min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
+                        "       host_sim --probe-sh scn base points.f32 seeds.u32 spp rr sh.f32 out.f32|- states.u32|-\n"
                         "       host_sim --views scn base cams.f32 seeds.u32 W H spp policy chunk out.f32\n"
                         "       host_sim --render-adaptive scn base W H x0 y0 x1 y1 seed min_spp max_spp check_every tolerance floor rr out.f32 spp.u32 m2.f32 states.u32\n"
                         "       host_sim --features scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- states.u32|-\n"

@@ -15,7 +15,7 @@ int device_render_matte(Scene *, const ort_render_params *, const ort_view *, ui
 int device_matte_mask(int, bool, const void *, const void *, uint32_t, uint32_t, const uint32_t *, uint32_t, int32_t, int32_t, uint32_t, void *, void *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_denoise(int, bool, const ort_denoise_params &, const ort_denoise_planes &, int32_t, int32_t, uint32_t, void *, void *, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 int device_plan_samples(int, bool, const ort_plan_params &, const ort_plan_planes &, int32_t, int32_t, uint32_t, void *, void *, void *, void *, ort_stats *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
-int device_radiance(Scene *, const QueryCall &, const void *, const void *, uint32_t, float, const ort_adaptive *, void *, void *, void *, void *, bool, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
+int device_radiance(Scene *, const QueryCall &, const void *, const void *, uint32_t, float, const ort_adaptive *, void *, void *, void *, void *, bool, void *, std::string *err) { *err = "host_sim: no device"; return ORT_ERR_NO_DEVICE; }
 }
 /* the multi-GPU entry points of ort_api.cpp (ort_comm.cpp is HIP code): never called by the harness */
 namespace ort {
