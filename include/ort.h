@@ -729,6 +729,72 @@ int ort_render_views_light_groups_device(ort_scene *scene, const ort_render_para
                                          const ort_view *views, uint32_t view_count, void *d_out_groups, void *d_out_rgb,
                                          void *d_final_states, void *hip_stream, ort_stats *stats);
 
+/* ---- path-depth renders: emission, direct, indirect -- one frame per bounce count, in one pass ----
+ * The frame split by how many bounces the light took: the "emission / direct / indirect" triple of compositors and denoisers,
+ * and with more bins a per-bounce breakdown.  No depth cap exists to render it with, so G renders of G scenes cannot give it.
+ * Job.  The job is the ORT_POLICY_PIXEL job of pixel (x, y): all spp camera samples on the stream job_seed(seed, y*W + x)
+ * (views[v].seed in the views form).  The samples are ort_render_image's samples, unchanged, the aperture draw included.
+ * Depth.  Every ray of a sample has a depth d: 0 for the camera ray, one more with each sample_brdf draw, that is each bounce ray
+ * (ray.cpp:1335-1353).  A re-cast of the same ray on the exact octree walk is not a new depth.
+ * Bins.  G = bin_count bins, 1 <= G <= ORT_MAX_DEPTH_BINS; the bin of a depth is min(d, G - 1).  With G = 3, bin 0
+ * (ORT_DEPTH_EMISSION) is light sources seen directly, bin 1 (ORT_DEPTH_DIRECT) light that took one bounce, bin 2
+ * (ORT_DEPTH_INDIRECT) everything beyond.
+ * Sums, every operation a separately rounded f32 operation:
+ *  - C is the render's sum.  B_g, for g in [0, G), starts at (+0, +0, +0).
+ *  - Whenever a sample adds a vector e to C -- a light was hit: at the primary hit unguarded (ray.cpp:1254-1259), at a bounce only
+ *    if e is finite (ray.cpp:1358-1371) -- on a ray of depth d, then B_bin(d) = B_bin(d) + e, component by component: the same e
+ *    under the same conditions.
+ * Lengths.  N_g, for g in [0, G), starts at 0.  When a sample ends, for any reason -- a light was hit, nothing was hit, a shape of
+ * material 0 was hit, or the roulette said so -- with d the depth of the last ray it cast, N_bin(d) = N_bin(d) + 1.  The N_g of
+ * a pixel add up to spp.
+ * Outputs, each plane with row 0 at the bottom, plane-major as out_groups is:
+ *    out_bins      view_count x G frames of width*height*3 f32; frame (v, g) starts at ((v*G + g) * height*width*3) floats
+ *                  and holds B_g / (float)spp
+ *    out_rgb       view_count frames, view-major: C / (float)spp                        (may be NULL)
+ *    out_lengths   view_count x G planes of width*height u32; plane (v, g) starts at ((v*G + g) * height*width) words
+ *                  and holds N_g                                                        (may be NULL)
+ *    final_states  width*height u32 per view: the stream's state after the job          (may be NULL)
+ * Pixels outside the rect are left untouched in every plane.
+ * Six identities.  (1) out_rgb and final_states are ort_render_image's ORT_POLICY_PIXEL frame and its jobs' final states, bit for
+ * bit.  (2) With G = 1, out_bins is out_rgb bit for bit and out_lengths is spp: the additions are the same, in the same order.
+ * (3) For g < G - 1, frame g and length plane g do not depend on G; nor does any plane depend on which optional planes are NULL.
+ * (4) With rr = 0 no path bounces: every bin but bin 0 is +0 and every length lies in bin 0.  (5) The bins add up to out_rgb only
+ * up to rounding, not bit for bit (f32 addition is not associative): that is why the call offers out_rgb from the same pass.
+ * (6) Frame (v, .) of a batch is the single-frame call's for that camera and seed; the single-frame call is the one-view batch of
+ * the scene's own camera (ort_scene_get_camera) and params->seed.
+ * Parameters.  params->policy must be ORT_POLICY_PIXEL; any other policy is ORT_ERR_UNSUPPORTED.  params->spp is within
+ * [1, 1 << 24], so that (float)spp is exact.  shard_count > 1 and ORT_RENDER_PACKED return ORT_ERR_UNSUPPORTED.  params->chunk is
+ * ignored; rr is judged as the render call judges it (rr >= 0).  The views form follows ort_render_views_light_groups:
+ * params->seed is ignored; the per-view seed and camera, the rule where a camera may stand, ORT_MAX_VIEWS and view_count == 0
+ * (ORT_OK without a launch, whatever the other arguments) are as there.
+ * Errors are reported before any device work, in ort_render_light_groups' order with the bin count where the groups stand:
+ * ORT_ERR_INVALID (null out_bins or views, view cap exceeded, null scene or params, empty or bad params exactly as
+ * ort_render_image judges them; then spp above 1 << 24; then bin_count 0 or above ORT_MAX_DEPTH_BINS; then a plane not 4-byte
+ * aligned), ORT_ERR_UNSUPPORTED (policy, shard, packed, camera outside the box), ORT_ERR_STATE (scene not committed),
+ * ORT_ERR_NO_DEVICE (not uploaded).
+ * The device forms take DEVICE pointers for the planes on the scene's device, enqueue on hip_stream (NULL = the default stream)
+ * and wait only when stats != NULL; views is HOST memory in every form, copied before the call returns.  stats as for the render
+ * call; with ORT_RENDER_COUNTERS, paths = view_count x rect pixels x spp.  No workspace is needed: the bin sums and the length
+ * counts of a pixel live in its words of out_bins and out_lengths while its job runs. */
+#define ORT_MAX_DEPTH_BINS 8u
+#define ORT_DEPTH_EMISSION 0u
+#define ORT_DEPTH_DIRECT   1u
+#define ORT_DEPTH_INDIRECT 2u
+
+/* host planes in, host planes out (device staging is internal); synchronous */
+int ort_render_depths(ort_scene *scene, const ort_render_params *params, uint32_t bin_count, float *out_bins,
+                      float *out_rgb /* may be NULL */, uint32_t *out_lengths /* may be NULL */, uint32_t *final_states /* may be NULL */,
+                      ort_stats *stats);
+int ort_render_depths_device(ort_scene *scene, const ort_render_params *params, uint32_t bin_count, void *d_out_bins, void *d_out_rgb,
+                             void *d_out_lengths, void *d_final_states, void *hip_stream, ort_stats *stats);
+/* view_count x G bin frames and length planes, view_count frames per other plane, view-major */
+int ort_render_views_depths(ort_scene *scene, const ort_render_params *params, uint32_t bin_count, const ort_view *views,
+                            uint32_t view_count, float *out_bins, float *out_rgb /* may be NULL */, uint32_t *out_lengths /* may be NULL */,
+                            uint32_t *final_states /* may be NULL */, ort_stats *stats);
+int ort_render_views_depths_device(ort_scene *scene, const ort_render_params *params, uint32_t bin_count, const ort_view *views,
+                                   uint32_t view_count, void *d_out_bins, void *d_out_rgb, void *d_out_lengths, void *d_final_states,
+                                   void *hip_stream, ort_stats *stats);
+
 /* ---- sample-map renders: the caller's sample count per pixel -------------------------------------
  * The camera render with a job length of the caller's choosing for every pixel: the second pass of a two-pass scheme (a pilot
  * frame, a map built from its out_m2 and guide planes, the samples spent where the map says), a foveated frame, or -- a map that

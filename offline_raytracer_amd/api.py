@@ -28,6 +28,8 @@ SH_COEFFS = 9            # ORT_SH_COEFFS: probe_sh()'s coefficients per point an
 MAX_VIEWS = 4096  # ORT_MAX_VIEWS
 MAX_LIGHT_GROUPS = 8     # ORT_MAX_LIGHT_GROUPS
 NO_LIGHT_GROUP = 0xFF    # ORT_NO_LIGHT_GROUP: a light that is in no group
+MAX_DEPTH_BINS = 8       # ORT_MAX_DEPTH_BINS
+DEPTH_EMISSION, DEPTH_DIRECT, DEPTH_INDIRECT = 0, 1, 2   # ORT_DEPTH_*: the bins of a three-bin path-depth render
 
 
 class OrtError(RuntimeError):
@@ -244,6 +246,7 @@ EXPORTS = [
     "ort_matte_mask", "ort_matte_mask_device",
     "ort_render_light_groups", "ort_render_light_groups_device", "ort_render_views_light_groups",
     "ort_render_views_light_groups_device",
+    "ort_render_depths", "ort_render_depths_device", "ort_render_views_depths", "ort_render_views_depths_device",
     "ort_render_sample_map", "ort_render_sample_map_device", "ort_render_views_sample_map", "ort_render_views_sample_map_device",
     "ort_render_accumulate", "ort_render_accumulate_device", "ort_render_views_accumulate", "ort_render_views_accumulate_device",
     "ort_denoise_workspace_bytes", "ort_denoise", "ort_denoise_device",
@@ -316,6 +319,8 @@ def lib():
                 ("ort_render_views_adaptive", [vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, C.c_uint32, vp, vp, vp, vp, stats]),
                 ("ort_render_light_groups", [vp, C.POINTER(RenderParams), C.POINTER(LightGroups), vp, vp, vp, stats]),
                 ("ort_render_views_light_groups", [vp, C.POINTER(RenderParams), C.POINTER(LightGroups), vp, C.c_uint32, vp, vp, vp, stats]),
+                ("ort_render_depths", [vp, C.POINTER(RenderParams), C.c_uint32, vp, vp, vp, vp, stats]),
+                ("ort_render_views_depths", [vp, C.POINTER(RenderParams), C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, stats]),
                 ("ort_render_sample_map", [vp, C.POINTER(RenderParams), vp, vp, vp, vp, stats]),
                 ("ort_render_views_sample_map", [vp, C.POINTER(RenderParams), vp, C.c_uint32, vp, vp, vp, vp, stats]),
                 ("ort_render_accumulate", [vp, C.POINTER(RenderParams), C.POINTER(AccumPlanes), vp, vp, stats]),
@@ -770,6 +775,56 @@ class Scene:
         when want_stats (returns the stats dict).  params.seed is ignored."""
         views = _views(cameras, seeds)
         return self._light_groups_device(views, params, groups, (d_groups, d_rgb, d_states), group_count, stream, want_stats)
+
+    # -- path-depth renders: emission, direct, indirect -- one frame per bounce count, in one pass ------
+    _DEPTH_PLANES = ("rgb", "lengths", "states")
+
+    def _depths_host(self, views, width, height, spp, seed, bins, rect, rr, want, counters, out):
+        want = tuple(want)
+        if any(w not in self._DEPTH_PLANES for w in want) or len(set(want)) != len(want):
+            raise ValueError("want names planes among %s, each once; got %r" % (self._DEPTH_PLANES, want))
+        G = int(bins)
+        lead, hw = _lead(views), (height, width)
+        Ga = G if 1 <= G <= MAX_DEPTH_BINS else 1   # a bin count the call refuses: planes that are never written
+        shapes = {"bins": (lead + (Ga,) + hw + (3,), "<f4"), "rgb": (lead + hw + (3,), "<f4"), "lengths": (lead + (Ga,) + hw, "<u4"),
+                  "states": (lead + hw, "<u4")}
+        names = ["bins"] + [n for n in self._DEPTH_PLANES if n in want]
+        if out is not None and (not isinstance(out, dict) or set(out) != set(names)):
+            raise ValueError("out must be a dict of the planes %s" % (names,))
+        planes = dict(zip(names, _host_planes([shapes[n] for n in names], None if out is None else [out[n] for n in names], ", ".join(names))))
+        p = self.params(width, height, spp, seed, "pixel", 0, rect, rr, counters)
+        tail = [planes[n].ctypes.data if n in planes else None for n in ("bins",) + self._DEPTH_PLANES]
+        st = self._pixel_jobs("depths", views, False, p, [C.c_uint32(G & 0xFFFFFFFF)], tail)
+        return planes["bins"], {n: planes[n] for n in names[1:]}, st
+
+    def render_depths(self, width, height, spp, seed, bins=3, rr=0.8, want=("rgb",), rect=None, counters=False, out=None):
+        """render(policy="pixel") split by how many bounces the light took, in one pass: with bins=3 frame DEPTH_EMISSION holds the
+        light sources seen directly, DEPTH_DIRECT the light that took one bounce and DEPTH_INDIRECT everything beyond; with more
+        bins (up to MAX_DEPTH_BINS) frame g < bins - 1 holds the light that took exactly g bounces and the last frame the rest
+        (include/ort.h gives the contract).  want: which other planes to return, among "rgb" (the unsplit frame), "lengths"
+        ((bins, H, W) uint32: a pixel's samples counted by the depth of their last ray) and "states" ((H, W) uint32).  Returns
+        (frames (bins, H, W, 3) float32, {name: plane for the planes asked for}, stats dict).  out: a dict of the caller's planes,
+        "bins" and those of want; pixels outside rect keep what they held."""
+        return self._depths_host(None, width, height, spp, seed, bins, rect, rr, want, counters, out)
+
+    def render_depths_device(self, params, bins, d_bins, d_rgb=0, d_lengths=0, d_states=0, stream=None, want_stats=False):
+        """The same into device planes (raw device pointers, e.g. torch tensors' data_ptr(): (bins, H, W, 3) float32 and, where a
+        pointer is given, (H, W, 3) float32 / (bins, H, W) uint32 / (H, W) uint32).  params: Scene.params(..., policy="pixel").
+        Enqueued on stream; waits only when want_stats (returns the stats dict)."""
+        return self._pixel_jobs("depths", None, True, params, [C.c_uint32(int(bins) & 0xFFFFFFFF)], [_ptr(d) for d in (d_bins, d_rgb, d_lengths, d_states)],
+                                stream, want_stats)
+
+    def render_views_depths(self, cameras, seeds, width, height, spp, bins=3, rr=0.8, want=("rgb",), rect=None, counters=False, out=None):
+        """render_depths for a batch of views in one launch (cameras, seeds as render_views): frames (v, .) are what render_depths
+        gives with seed seeds[v] if the scene's camera were cameras[v].  Returns (frames (V, bins, H, W, 3), {"rgb": (V, H, W, 3),
+        "lengths": (V, bins, H, W), "states": (V, H, W)} as asked for, stats dict)."""
+        return self._depths_host(_views(cameras, seeds), width, height, spp, 0, bins, rect, rr, want, counters, out)
+
+    def render_views_depths_device(self, params, cameras, seeds, bins, d_bins, d_rgb=0, d_lengths=0, d_states=0, stream=None, want_stats=False):
+        """The same into device planes, view-major: (V, bins, H, W, 3), (V, H, W, 3), (V, bins, H, W), (V, H, W).  Enqueued on stream;
+        waits only when want_stats (returns the stats dict).  params.seed is ignored."""
+        return self._pixel_jobs("depths", _views(cameras, seeds), True, params, [C.c_uint32(int(bins) & 0xFFFFFFFF)],
+                                [_ptr(d) for d in (d_bins, d_rgb, d_lengths, d_states)], stream, want_stats)
 
     # -- sample-map renders: the caller's sample count per pixel ----------------------------------
     @staticmethod

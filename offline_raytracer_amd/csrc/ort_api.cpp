@@ -638,6 +638,28 @@ static int render_groups_common(ort_scene *s, const ort_render_params *p, const 
         });
 }
 
+/* Path-depth renders: render_groups_common's order with the bin count where the groups stand.  Own checks: spp above 1 << 24, a bin
+   count outside [1, ORT_MAX_DEPTH_BINS], the planes' alignment */
+static int render_depths_common(ort_scene *s, const ort_render_params *p, uint32_t bin_count, const ort_view *views, uint32_t view_count, bool batch, bool host,
+                                void *out_bins, void *out_rgb, void *out_lengths, void *states, void *stream, ort_stats *stats) {
+    static const PixelJobKind kind = {"the path-depth render splits one-pixel jobs: it needs the PIXEL policy", "the path-depth render is not sharded",
+                                      "the path-depth render has no packed framebuffer"};
+    return render_pixel_jobs(
+        kind, s, p, views, view_count, batch, host, stream, stats,
+        [&] { return check_first_plane(batch, host, views, out_bins, "null views or bin frames", "null bin frames", "null device bin frames"); },
+        [](ort_render_params *) {},
+        [&](const ort_render_params &q) {
+            if (q.spp > (1u << 24)) return fail(ORT_ERR_INVALID, "spp must be <= 1 << 24: a sample count must be exact in float");
+            if (bin_count == 0 || bin_count > ORT_MAX_DEPTH_BINS) return fail(ORT_ERR_INVALID, "bin_count must be within [1, ORT_MAX_DEPTH_BINS]");
+            return check_ptrs({{out_bins, true, 4}, {out_rgb, false, 4}, {out_lengths, false, 4}, {states, false, 4}}, "", "",
+                              "out_bins, out_rgb, out_lengths and final_states must be 4-byte aligned");
+        },
+        [&](const ort_render_params &q, ort::RenderCall c) {
+            c.kind = ort::RK_DEPTHS; c.depth_bins = bin_count; c.out_groups = out_bins;
+            return run_render(s, &q, c, out_rgb, out_lengths, nullptr, states);
+        });
+}
+
 /* Sample-map renders.  Own checks: spp -- the cap -- above 1 << 24, a null map, the map's and the planes' alignment.  The map's
    VALUES are never judged, in any form: the device forms cannot see them before the launch, so the lanes cut every one at the cap */
 static int render_sample_map_common(ort_scene *s, const ort_render_params *p, const ort_view *views, uint32_t view_count, bool batch, bool host,
@@ -978,6 +1000,10 @@ int ort_render_views_device(ort_scene *s, const ort_render_params *p, const ort_
 int ort_render_adaptive(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, nullptr, 1, false, true, out_rgb, out_spp, out_m2, final_states, nullptr, stats); }); }
 int ort_render_adaptive_device(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, void *d_out_rgb, void *d_out_spp, void *d_out_m2, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, nullptr, 1, false, false, d_out_rgb, d_out_spp, d_out_m2, d_final_states, hip_stream, stats); }); }
 int ort_render_views_adaptive(ort_scene *s, const ort_render_params *p, const ort_adaptive *ad, const ort_view *views, uint32_t view_count, float *out_rgb, uint32_t *out_spp, float *out_m2, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_adaptive_common(s, p, ad, views, view_count, true, true, out_rgb, out_spp, out_m2, final_states, nullptr, stats); }); }
+int ort_render_depths(ort_scene *s, const ort_render_params *p, uint32_t bin_count, float *out_bins, float *out_rgb, uint32_t *out_lengths, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_depths_common(s, p, bin_count, nullptr, 1, false, true, out_bins, out_rgb, out_lengths, final_states, nullptr, stats); }); }
+int ort_render_depths_device(ort_scene *s, const ort_render_params *p, uint32_t bin_count, void *d_out_bins, void *d_out_rgb, void *d_out_lengths, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_depths_common(s, p, bin_count, nullptr, 1, false, false, d_out_bins, d_out_rgb, d_out_lengths, d_final_states, hip_stream, stats); }); }
+int ort_render_views_depths(ort_scene *s, const ort_render_params *p, uint32_t bin_count, const ort_view *views, uint32_t view_count, float *out_bins, float *out_rgb, uint32_t *out_lengths, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_depths_common(s, p, bin_count, views, view_count, true, true, out_bins, out_rgb, out_lengths, final_states, nullptr, stats); }); }
+int ort_render_views_depths_device(ort_scene *s, const ort_render_params *p, uint32_t bin_count, const ort_view *views, uint32_t view_count, void *d_out_bins, void *d_out_rgb, void *d_out_lengths, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_depths_common(s, p, bin_count, views, view_count, true, false, d_out_bins, d_out_rgb, d_out_lengths, d_final_states, hip_stream, stats); }); }
 int ort_render_light_groups(ort_scene *s, const ort_render_params *p, const ort_light_groups *groups, float *out_groups, float *out_rgb, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_groups_common(s, p, groups, nullptr, 1, false, true, out_groups, out_rgb, final_states, nullptr, stats); }); }
 int ort_render_light_groups_device(ort_scene *s, const ort_render_params *p, const ort_light_groups *groups, void *d_out_groups, void *d_out_rgb, void *d_final_states, void *hip_stream, ort_stats *stats) { return guarded([&]() { return render_groups_common(s, p, groups, nullptr, 1, false, false, d_out_groups, d_out_rgb, d_final_states, hip_stream, stats); }); }
 int ort_render_views_light_groups(ort_scene *s, const ort_render_params *p, const ort_light_groups *groups, const ort_view *views, uint32_t view_count, float *out_groups, float *out_rgb, uint32_t *final_states, ort_stats *stats) { return guarded([&]() { return render_groups_common(s, p, groups, views, view_count, true, true, out_groups, out_rgb, final_states, nullptr, stats); }); }

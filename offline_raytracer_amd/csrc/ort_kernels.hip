@@ -490,7 +490,8 @@ static int print_util_diag(const DeviceScene *d, std::string *err) {
 }
 
 /* The camera render call, of the kind the caller states (c.kind): plain, adaptive (c.ad), split by light group (c.groups), cut
-   by the caller's map (c.sample_map) or continued from the caller's planes (c.acc_sum, with or without a map).  What runs, on
+   by the caller's map (c.sample_map), continued from the caller's planes (c.acc_sum, with or without a map) or split by path
+   depth (c.depth_bins).  What runs, on
    which grid and with which thresholds is plan_render's or, for a pixel-job kind, plan_pixel_jobs' decision (ort_plan.h), and
    what the RenderView says besides pointers is render_view's (ort_setup.h); this is the plumbing around them: settle the previous call, plan, staging, views, buffers, launch, combine, finish */
 int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c, void *out_rgb, void *out_spp, void *out_m2, void *states, std::string *err) {
@@ -522,9 +523,10 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
     /* the planes as the lanes see them: the caller's device pointers, or the scene's staging buffers holding the caller's words.
        view_count frames, view-major, or the packed framebuffer; the 4-byte planes stage where the radiance queries' do */
     const size_t pixels = (size_t)view_count * (size_t)p->width * (size_t)p->height;
-    Plane planes[7] = {{out_rgb, &d->staging, rv.packed_out ? (size_t)rv.my_blocks * 768u : pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u, nullptr},
+    const size_t bins = c.depth_bins ? c.depth_bins : 1u; /* the path-depth render's length planes: a plane per bin where the others have one */
+    Plane planes[7] = {{out_rgb, &d->staging, rv.packed_out ? (size_t)rv.my_blocks * 768u : pixels * 12u, nullptr}, {out_spp, &d->query_stage[3], pixels * 4u * bins, nullptr},
                        {out_m2, &d->query_stage[4], pixels * 4u, nullptr}, {states, &d->query_stage[5], pixels * 4u, nullptr},
-                       {c.out_groups, &d->query_stage[0], pixels * 12u * (c.groups ? c.groups->group_count : 0u), nullptr},
+                       {c.out_groups, &d->query_stage[0], pixels * 12u * (c.groups ? c.groups->group_count : c.depth_bins), nullptr},
                        /* the one plane that is read and not written: staged in with the others, never out */
                        {const_cast<void *>(c.sample_map), &d->query_stage[1], pixels * 4u, nullptr},
                        /* the accumulating render's colour sums, staged both ways as its count (out_spp), m2 and states are */
@@ -543,6 +545,11 @@ int device_render(Scene *scene, const ort_render_params *p, const RenderCall &c,
         rv.group_of_material = d->group_tab.as<const uint8_t>();
         rv.group_count = c.groups->group_count;
         rv.group_out = (float *)planes[4].dev;
+    }
+    if (c.depth_bins) { /* the bin frames where the group frames travel, the length planes where the sample counts do */
+        rv.depth_bins = c.depth_bins;
+        rv.depth_out = (float *)planes[4].dev;
+        rv.depth_len = (uint32_t *)planes[1].dev;
     }
     if (c.jobs) {
         if ((rc = d->jobs.ensure((size_t)c.job_count * sizeof(ort_tile_job), err))) return rc;

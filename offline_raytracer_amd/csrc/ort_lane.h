@@ -167,6 +167,14 @@ struct RenderView {
        floats, [point][coefficient][rgb]: a point's words ARE its 27 sums while its job runs, as group_out's are a pixel's.  out
        (may be null here) holds the plain means */
     float *sh_out;
+    /* path-depth renders (ort_render_depths; the pt_depths kernels): depth_out holds view_count x depth_bins frames of W * H * 3
+       floats, frame (v, g) at (v * depth_bins + g) * W * H * 3, and its words ARE the pixel's bin sums while its job runs, as
+       group_out's are; depth_len (may be null) holds view_count x depth_bins planes of W * H words, plane (v, g) at
+       (v * depth_bins + g) * W * H: the pixel's counts of samples by the depth of their last ray.  out and final_states (a plane
+       of view_count * W * H words) may each be null */
+    uint32_t depth_bins;
+    float *depth_out;
+    uint32_t *depth_len;
 };
 
 /* ---- the order in which a CHUNK render issues its jobs ----------------------------------------------------------
@@ -296,7 +304,7 @@ struct MatteIO {
    ort_kernels.hip.  The flavour comes as named fields: a render kernel's KernelVariant (plan_variant, ort_plan.h), a query's
    QueryPlan; every other bool of the kernels is fixed by the family. */
 void ort_launch_w5(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);              /* KF_FIVE: ort_kernels_w5.hip */
-void ort_launch_pixel_jobs(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);      /* KF_ADAPTIVE to KF_ACCUM: ort_kernels_render_adaptive.hip */
+void ort_launch_pixel_jobs(const ort::KernelVariant &v, unsigned int grid, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);      /* KF_ADAPTIVE to KF_DEPTHS: ort_kernels_render_adaptive.hip */
 void ort_launch_radiance_adaptive(const ort::QueryPlan &pl, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);                    /* ort_kernels_adaptive.hip */
 void ort_launch_irradiance(const ort::QueryPlan &pl, bool adaptive, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);            /* ort_kernels_irradiance.hip */
 void ort_launch_probe_sh(const ort::QueryPlan &pl, hipStream_t stream, const ort::SceneView &sv, const ort::RenderHot &hot);                             /* ort_kernels_irradiance.hip */
@@ -498,6 +506,17 @@ constexpr uint32_t LF_ACCUM = 1u << 17;
    keeps its sums: zeroed at the job's start, one load, add and store per word and emission, divided in place at the job's end.
    rv.c->out is an optional array here.  Everything of it sits under if constexpr (SH) */
 constexpr uint32_t LF_SH = 1u << 18;
+/* DEPTHS: path-depth renders (ort_render_depths; with VIEWS, one-pixel jobs in JOBS_PIXEL mode): every ray of a sample has a depth
+   d, 0 for the camera ray and one more with each sample_brdf draw.  Whenever a sample adds an emission e to the pixel's sum, on a
+   ray of depth d, the same e is added to the sum of bin min(d, depth_bins - 1); when a sample ends, the length count of the bin
+   of its last ray's depth rises by one.  The bin sums are the pixel's own words of the G output frames, kept as GROUPS keeps its
+   sums (zeroed at the pixel's start, one load, add and store per triple and emission, divided in place at the job's end), and the
+   length counts are the pixel's own words of the G length planes where the caller asks for them.  The one new piece of state is
+   d, and it is not a register: it lives in a fourth row of the lane's focal cache (a word of LDS per lane, as pt_persistent_x
+   keeps its late flag), zeroed where a pixel starts and where a sample ends, read where an emission is added or a sample ends,
+   bumped where a bounce is drawn -- once per RAY, hundreds of node tests, while a register would be live through the whole
+   traversal loop of kernels that sit at their 128-register cap.  Everything of it sits under if constexpr (DEPTHS) */
+constexpr uint32_t LF_DEPTHS = 1u << 19;
 /* the walk's own options */
 constexpr uint32_t LF_TREELET = 1u << 10;     /* traverse: the top of the binary tree is read from the LDS tables (with TABS, never WIDE) */
 constexpr uint32_t LF_ANNOUNCE = 1u << 11;    /* traverse asks for a finished ray's PrimInfo (announce_winner); resolve_hit then finds it ANNOUNCED */
@@ -514,7 +533,7 @@ constexpr uint32_t LF_OF_PROLOGUE = LF_COUNTERS | LF_TABS | LF_HAS_EXCL;
 constexpr uint32_t LF_OF_BEGIN_RAY = LF_COUNTERS | LF_TABS;
 constexpr uint32_t LF_OF_TRAVERSE = LF_COUNTERS | LF_TREELET | LF_ANNOUNCE | LF_WIDE;
 constexpr uint32_t LF_OF_RESOLVE_HIT = LF_COUNTERS | LF_TABS | LF_ANNOUNCE | LF_WIDE;
-constexpr uint32_t LF_OF_PRODUCE_RAY = LF_COUNTERS | LF_DIFFUSE | LF_TABS | LF_IMPLICIT | LF_VIEWS | LF_RAYS | LF_ADAPT | LF_HEMI | LF_GROUPS | LF_SPPMAP | LF_ACCUM | LF_SH;
+constexpr uint32_t LF_OF_PRODUCE_RAY = LF_COUNTERS | LF_DIFFUSE | LF_TABS | LF_IMPLICIT | LF_VIEWS | LF_RAYS | LF_ADAPT | LF_HEMI | LF_GROUPS | LF_SPPMAP | LF_ACCUM | LF_SH | LF_DEPTHS;
 constexpr uint32_t LF_OF_LANE = LF_OF_PRODUCE_RAY | LF_WIDE; /* pt_lane ... radiance_lane: a job's flavour */
 /* ... and, from a lane's flavour f, the words of the three steps of its loop: begin_ray (and a prologue in its place); traverse,
    where finished rays announce their winners and the top of the binary tree comes from the LDS tables if there are any; and the
@@ -527,7 +546,7 @@ constexpr uint32_t resolve_of(uint32_t f) { return (f & (LF_COUNTERS | LF_TABS |
 constexpr bool flavour_ok(uint32_t f, uint32_t reads) {
     const bool IMPLICIT = f & LF_IMPLICIT, WIDE = f & LF_WIDE, VIEWS = f & LF_VIEWS, RAYS = f & LF_RAYS, ADAPT = f & LF_ADAPT;
     const bool HEMI = f & LF_HEMI, GROUPS = f & LF_GROUPS, TREELET = f & LF_TREELET, EXACT_ORDER = f & LF_EXACT_ORDER;
-    const bool SPPMAP = f & LF_SPPMAP, ACCUM = f & LF_ACCUM, SH = f & LF_SH;
+    const bool SPPMAP = f & LF_SPPMAP, ACCUM = f & LF_ACCUM, SH = f & LF_SH, DEPTHS = f & LF_DEPTHS;
     return (f & ~reads) == 0u
         && (!RAYS || (IMPLICIT && !VIEWS))                        /* a caller's ray array is an implicit job space of its own */
         && (!ADAPT || (IMPLICIT && (RAYS || VIEWS)))              /* the adaptive rule is built for the radiance queries and for one-pixel jobs of a batch of views */
@@ -536,6 +555,7 @@ constexpr bool flavour_ok(uint32_t f, uint32_t reads) {
         && (!SPPMAP || (IMPLICIT && VIEWS && !RAYS && !ADAPT && !GROUPS)) /* the sample map cuts plain one-pixel jobs of a batch of views */
         && (!ACCUM || SPPMAP)                                     /* accumulation continues the sample map's jobs */
         && (!SH || (HEMI && !ADAPT))                              /* the SH sums are built for the plain job of points */
+        && (!DEPTHS || (IMPLICIT && VIEWS && !RAYS && !ADAPT && !GROUPS && !SPPMAP)) /* the depth bins are built for plain one-pixel jobs of a batch of views */
         && (!WIDE || !(VIEWS || RAYS || ADAPT || HEMI || GROUPS || SPPMAP || TREELET)) /* the 4-wide tree serves the single frame's plain loop, and has no treelet */
         && (!EXACT_ORDER || !(f & (LF_FINITE_RAY | LF_FROM_TAB))); /* the exact walk reads HBM */
 }
@@ -1225,6 +1245,17 @@ ORT_D size_t plane_index(const RenderHot &rv, uint32_t view, uint32_t x, uint32_
 ORT_D float *group_pixel_ptr(const RenderHot &rv, uint32_t view, uint32_t g, uint32_t pxy) {
     return rv.c->group_out + 3u * plane_index(rv, view * rv.c->group_count + g, pxy & 0xffffu, pxy >> 16);
 }
+/* path-depth renders: pixel pxy's three words of frame (view, g) of rv.c->depth_out, its word of plane (view, g) of rv.c->depth_len,
+   and the bin of a depth */
+ORT_D float *depth_pixel_ptr(const RenderHot &rv, uint32_t view, uint32_t g, uint32_t pxy) {
+    return rv.c->depth_out + 3u * plane_index(rv, view * rv.c->depth_bins + g, pxy & 0xffffu, pxy >> 16);
+}
+ORT_D uint32_t *depth_len_ptr(const RenderHot &rv, uint32_t view, uint32_t g, uint32_t pxy) {
+    return rv.c->depth_len + plane_index(rv, view * rv.c->depth_bins + g, pxy & 0xffffu, pxy >> 16);
+}
+ORT_D uint32_t depth_bin(const RenderHot &rv, uint32_t d) { const uint32_t last = rv.c->depth_bins - 1u; return d < last ? d : last; }
+/* ... and the lane's depth word: the fourth row of its focal cache */
+ORT_D uint32_t *depth_word(float *focal_cache, int focal_stride) { return (uint32_t *)(focal_cache + 3 * focal_stride); }
 /* 8x8 block blk of the rect's block grid and pixel-in-block pin -> (x, y); outside: a pixel of an edge block that the rect does not hold */
 struct BlockPixel { int x, y; bool outside; };
 ORT_D BlockPixel block_pixel(const RenderHot &rv, uint32_t blk, uint32_t pin) {
@@ -1316,9 +1347,10 @@ ORT_D float *sh_point_ptr(const RenderHot &rv, const PathState &P) { return rv.c
    stopping rule has been asked where a check is due */
 template <uint32_t F>
 ORT_D bool shade_arrival(const SceneView &sv, const RenderHot &rv, const float4 *tab, PathState &P, const HitState &h, Counters &c, uint32_t spp_u,
-                         AdaptState *A, RayPass &s, [[maybe_unused]] const float *dir_cache = nullptr, [[maybe_unused]] int dir_stride = 0) {
+                         AdaptState *A, RayPass &s, [[maybe_unused]] const float *dir_cache = nullptr, [[maybe_unused]] int dir_stride = 0,
+                         [[maybe_unused]] uint32_t *depth = nullptr /* DEPTHS: the lane's depth word */) {
     constexpr bool COUNTERS = F & LF_COUNTERS, DIFFUSE = F & LF_DIFFUSE, TABS = F & LF_TABS;
-    constexpr bool ADAPT = F & LF_ADAPT, GROUPS = F & LF_GROUPS, SPPMAP = F & LF_SPPMAP, SH = F & LF_SH;
+    constexpr bool ADAPT = F & LF_ADAPT, GROUPS = F & LF_GROUPS, SPPMAP = F & LF_SPPMAP, SH = F & LF_SH, DEPTHS = F & LF_DEPTHS;
     bool alive = true;
     const uint32_t hit_mat = h.hit_mat; /* resolve_hit: 0 = nothing hit */
     s.n = normalize(h.hit_n);
@@ -1342,6 +1374,10 @@ ORT_D bool shade_arrival(const SceneView &sv, const RenderHot &rv, const float4 
                     float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
                     q[0] = q[0] + e.x; q[1] = q[1] + e.y; q[2] = q[2] + e.z;
                 }
+            }
+            if constexpr (DEPTHS) { /* the bin of the arriving ray's depth */
+                float *q = depth_pixel_ptr(rv, P.job_index, depth_bin(rv, *depth), P.pxy);
+                q[0] = q[0] + e.x; q[1] = q[1] + e.y; q[2] = q[2] + e.z;
             }
             if constexpr (SH) /* the sample's primary direction, from the lane's three words (produce_ray wrote them) */
                 sh_basis_add(sh_point_ptr(rv, P), mk(dir_cache[0], dir_cache[dir_stride], dir_cache[2 * dir_stride]), e);
@@ -1385,9 +1421,14 @@ ORT_D bool shade_arrival(const SceneView &sv, const RenderHot &rv, const float4 
         ORT_UTIL(sv, 6, true);
         s.draw = sample_brdf_draw<DIFFUSE>(P.rng, kRoughness, s.m);
         s.angle = s.draw.phi;
+        if constexpr (DEPTHS) *depth = *depth + 1u; /* the bounce ray is one deeper */
     } else {
         P.sample++;
         P.ps = PS_SAMPLE;
+        if constexpr (DEPTHS) { /* the sample's last ray was the one that arrived; the next sample starts at the camera */
+            if (rv.c->depth_len) { uint32_t *n = depth_len_ptr(rv, P.job_index, depth_bin(rv, *depth), P.pxy); *n = *n + 1u; }
+            *depth = 0u;
+        }
         if constexpr (ADAPT) {
             /* a check runs after sample n when n >= min_spp, n < max_spp and (n - min_spp) % check_every == 0: A->next
                counts up to it, so nothing is divided per sample */
@@ -1455,6 +1496,14 @@ ORT_D void write_pixel(const RenderHot &rv, const PathState &P, uint32_t job_spp
         const float fs = (float)job_spp;
         for (uint32_t g = 0; g < rv.c->group_count; ++g) {
             float *q = group_pixel_ptr(rv, P.job_index, g, P.pxy);
+            q[0] = q[0] / fs; q[1] = q[1] / fs; q[2] = q[2] / fs;
+        }
+        if (rv.c->out) { float *p = view_pixel_ptr(rv, P.job_index, 0u, px, py); p[0] = o.x; p[1] = o.y; p[2] = o.z; }
+        if (rv.c->final_states) rv.c->final_states[plane_index(rv, P.job_index, px, py)] = P.rng;
+    } else if constexpr (F & LF_DEPTHS) { /* likewise the G bin sums; the length counts stand as they are */
+        const float fs = (float)job_spp;
+        for (uint32_t g = 0; g < rv.c->depth_bins; ++g) {
+            float *q = depth_pixel_ptr(rv, P.job_index, g, P.pxy);
             q[0] = q[0] / fs; q[1] = q[1] / fs; q[2] = q[2] / fs;
         }
         if (rv.c->out) { float *p = view_pixel_ptr(rv, P.job_index, 0u, px, py); p[0] = o.x; p[1] = o.y; p[2] = o.z; }
@@ -1663,6 +1712,14 @@ ORT_D void begin_pixel(const RenderHot &rv, PathState &P, const SceneCamera &cam
             q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
         }
     }
+    if constexpr (F & LF_DEPTHS) { /* the bin sums and, where asked for, the length counts start at zero where they stand; the first ray is the camera's */
+        for (uint32_t g = 0; g < rv.c->depth_bins; ++g) {
+            float *q = depth_pixel_ptr(rv, P.job_index, g, P.pxy);
+            q[0] = 0.0f; q[1] = 0.0f; q[2] = 0.0f;
+            if (rv.c->depth_len) *depth_len_ptr(rv, P.job_index, g, P.pxy) = 0u;
+        }
+        *depth_word(focal_cache, focal_stride) = 0u;
+    }
     if constexpr (F & LF_SH) { /* the point's 27 sums start at +0 where they stand; focal_cache is the lane's direction words */
         float *q = sh_point_ptr(rv, P);
         for (uint32_t k = 0; k < kShWords; ++k) q[k] = 0.0f;
@@ -1799,6 +1856,7 @@ ORT_D bool produce_ray(const SceneView &sv, const RenderHot &rv, const float4 *t
         RayPass s;
         if (P.ps == PS_HIT) {
             if constexpr (F & LF_SH) s.bounce = shade_arrival<F>(sv, rv, tab, P, h, c, spp_u, A, s, focal_cache, focal_stride);
+            else if constexpr (F & LF_DEPTHS) s.bounce = shade_arrival<F>(sv, rv, tab, P, h, c, spp_u, A, s, nullptr, 0, depth_word(focal_cache, focal_stride));
             else s.bounce = shade_arrival<F>(sv, rv, tab, P, h, c, spp_u, A, s);
             ORT_PHASE(pr, sv, 1, true);
         }
@@ -2140,6 +2198,8 @@ ORT_D void flush_counters(const RenderHot &rv, const Counters &c, bool all) {
 /* SPPMAP: the sample-map render (pt_sample_map): the same loop, produce_ray cutting every job at its word of the caller's map; A
    as for ADAPT */
 /* ACCUM: the accumulating render (pt_accumulate): SPPMAP's loop, produce_ray starting a pixel from the caller's planes */
+/* DEPTHS: the path-depth render (pt_depths): the same loop, produce_ray keeping the bin sums and the length counts in the output
+   planes and the ray's depth in a fourth row of lds_focal, which the caller sizes for it */
 template <uint32_t F>
 ORT_D void pt_lane(const SceneView &sv, const RenderHot &rv, const float4 *tab, uint32_t *lds_stack, float *lds_focal, const int tid,
                    const uint32_t lane_id, bool prof_on = false, unsigned long long *pool = nullptr, AdaptState *A = nullptr) {
@@ -2669,6 +2729,23 @@ pt_groups(SceneView sv, RenderHot rv) {
     __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
     if (TABS) fill_tab(sv, lds_tab);
     pt_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_GROUPS>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
+                                                                     wave_job_pool(rv, lds_pool));
+}
+
+/* The path-depth render (ort_render_depths, ort_render_views_depths): pt_groups' loop with the emission's bin chosen by the depth of
+   the ray it arrived on (produce_ray's DEPTHS flag) instead of by the light that was hit, and a count of the samples by the depth
+   of their last ray.  Built beside pt_groups, in ort_kernels_render_adaptive.hip alone.  The sums and the counts live in the
+   output planes; the depth of the ray in flight is the fourth row of lds_focal, one more word of LDS per lane (1 KB per
+   workgroup).  No probes, no drain times */
+template <bool COUNTERS, bool DIFFUSE, bool TABS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_WAVES_PER_EU, ORT_WAVES_PER_EU)))
+pt_depths(SceneView sv, RenderHot rv) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    __shared__ float lds_focal[4 * kBlock]; /* rows 0-2 focal[component][lane], row 3 the depth of the lane's ray in flight (u32) */
+    __shared__ unsigned long long lds_pool[2 * (kBlock / 64)]; /* as pt_persistent */
+    __shared__ float4 lds_tab[TABS ? kTabF4 : 1];
+    if (TABS) fill_tab(sv, lds_tab);
+    pt_lane<lf_if(COUNTERS, LF_COUNTERS) | lf_if(DIFFUSE, LF_DIFFUSE) | lf_if(TABS, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_DEPTHS>(sv, rv, lds_tab, lds_stack, lds_focal, (int)threadIdx.x, blockIdx.x * (uint32_t)kBlock + threadIdx.x, false,
                                                                      wave_job_pool(rv, lds_pool));
 }
 

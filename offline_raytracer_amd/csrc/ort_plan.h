@@ -183,7 +183,7 @@ inline void plan_job_batches(unsigned long long job_count, unsigned long long la
 /* What a camera render is: the plain one (plan_render), or one of the kinds that cut one-pixel jobs over a batch of views
    (plan_pixel_jobs), each with a kernel family of its own (kind_family).  The caller of device_render states it (RenderCall::kind),
    the plan carries it, and plan_variant turns it into the family: nobody infers it */
-enum RenderKind : int { RK_PLAIN = 0, RK_ADAPTIVE, RK_GROUPS, RK_SAMPLE_MAP, RK_ACCUMULATE };
+enum RenderKind : int { RK_PLAIN = 0, RK_ADAPTIVE, RK_GROUPS, RK_SAMPLE_MAP, RK_ACCUMULATE, RK_DEPTHS };
 
 /* everything device_render decides before it touches the device */
 struct LaunchPlan {
@@ -367,7 +367,9 @@ inline LaunchPlan plan_render(const SceneTraits &t, const ort_render_params &p, 
      say);
    - RK_ACCUMULATE (ort_render_accumulate, ort_render_views_accumulate; pt_accumulate): the sample-map render's launch, for
      kernels that start a pixel from the caller's planes.  Neither the map nor the planes' counts can be read here, so the job
-     space again holds every pixel under the rect */
+     space again holds every pixel under the rect;
+   - RK_DEPTHS (ort_render_depths, ort_render_views_depths; pt_depths): the light-group render's launch, the sums chosen by the
+     depth of the ray an emission arrived on.  A job is p.spp samples long (render_view's to say) */
 inline LaunchPlan plan_pixel_jobs(RenderKind kind, const SceneTraits &t, const ort_render_params &p, const Knobs &kn, uint32_t view_count = 1) {
     LaunchPlan pl;
     plan_loop_exits(tree_is_cache_resident(t.fast_tree_bytes, kn.cache_resident), kn, &pl.refill_below, &pl.descend_below);
@@ -393,7 +395,7 @@ inline LaunchPlan plan_pixel_jobs(RenderKind kind, const SceneTraits &t, const o
 /* ---- the kernels that are built ------------------------------------------------------------------------------------------ */
 /* A render kernel by name: its family and its template arguments.  A bool its family's kernels do not take is stated as what
    they are compiled with (the ray exchange and the five-waves build: tabs and implicit; wavefront mode: none of the four) */
-enum KernelFamily : int { KF_NONE = 0, KF_WAVEFRONT, KF_LOOP, KF_LOOP_VIEWS, KF_EXCHANGE, KF_FIVE, KF_ADAPTIVE, KF_GROUPS, KF_SAMPLE_MAP, KF_ACCUM };
+enum KernelFamily : int { KF_NONE = 0, KF_WAVEFRONT, KF_LOOP, KF_LOOP_VIEWS, KF_EXCHANGE, KF_FIVE, KF_ADAPTIVE, KF_GROUPS, KF_SAMPLE_MAP, KF_ACCUM, KF_DEPTHS };
 struct KernelVariant {
     KernelFamily family;
     bool counters, diffuse, tabs, implicit, wide;
@@ -401,10 +403,10 @@ struct KernelVariant {
 constexpr bool operator==(const KernelVariant &a, const KernelVariant &b) {
     return a.family == b.family && a.counters == b.counters && a.diffuse == b.diffuse && a.tabs == b.tabs && a.implicit == b.implicit && a.wide == b.wide;
 }
-/* the pixel-job kinds' families stand in the kinds' order, KF_ADAPTIVE to KF_ACCUM */
+/* the pixel-job kinds' families stand in the kinds' order, KF_ADAPTIVE to KF_DEPTHS */
 constexpr KernelFamily kind_family(RenderKind k) { return (KernelFamily)((int)KF_ADAPTIVE + ((int)k - (int)RK_ADAPTIVE)); }
-constexpr bool pixel_job_family(KernelFamily f) { return f >= KF_ADAPTIVE && f <= KF_ACCUM; }
-static_assert(kind_family(RK_GROUPS) == KF_GROUPS && kind_family(RK_SAMPLE_MAP) == KF_SAMPLE_MAP && kind_family(RK_ACCUMULATE) == KF_ACCUM,
+constexpr bool pixel_job_family(KernelFamily f) { return f >= KF_ADAPTIVE && f <= KF_DEPTHS; }
+static_assert(kind_family(RK_GROUPS) == KF_GROUPS && kind_family(RK_SAMPLE_MAP) == KF_SAMPLE_MAP && kind_family(RK_ACCUMULATE) == KF_ACCUM && kind_family(RK_DEPTHS) == KF_DEPTHS,
               "a pixel-job kind and its kernel family are added at the same place of their enums");
 
 /* the variant a plan asks for.  A plan that claims two families at once, or a pixel-job kind outside a PIXEL batch of views,

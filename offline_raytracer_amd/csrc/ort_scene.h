@@ -234,6 +234,7 @@ struct RenderCall {
     void *out_groups;         /* ... and its view_count x group_count frames, as the call's form has them; out_rgb and states may then be null */
     const void *sample_map;   /* the sample-map render's map, view_count planes of a word a pixel, as the call's form has them (checked by the caller; views not null then, ad and groups null); null: every job is p->spp long */
     void *acc_sum;            /* the accumulating render's plane of undivided colour sums, as the call's form has it (checked by the caller; views not null then, ad and groups null; sample_map may be null); its count, m2 and states planes travel as out_spp, out_m2 and states, all four read and written; null: no accumulation */
+    uint32_t depth_bins;      /* RK_DEPTHS: the bin count G (checked by the caller; views not null then, ad, groups, sample_map and acc_sum null); its view_count x G bin frames travel as out_groups and its view_count x G length planes (may be null) as out_spp; out_rgb and states may be null; 0: no depth bins */
 };
 /* out_rgb: view_count frames, view-major (or, ORT_RENDER_PACKED, this shard's blocks).  The adaptive render's other planes (each
    may be null, and is for a plain render): samples taken, sums of squared sample luminance and final states, a word a pixel */

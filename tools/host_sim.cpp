@@ -45,6 +45,10 @@
  *       (the light-group render, pt_lane with LF_IMPLICIT | LF_VIEWS | LF_GROUPS: a batch of views, or with cams - the scene's own camera on the seed
  *       given; groups.u8 holds a byte per material of the scene, G is the group count; the planes start at -7.0f and, the states,
  *       0xdddddddd; rgb and states given as - are not passed)
+ *   or: host_sim --depths scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr G bins.f32 rgb.f32|- lengths.u32|- states.u32|-
+ *       (the path-depth render, pt_lane<..., VIEWS, DEPTHS>: a batch of views, or with cams - the scene's own camera on the seed
+ *       given; G is the bin count; the frames start at -7.0f, the lengths at 0xeeeeeeee and the states at 0xdddddddd; rgb, lengths
+ *       and states given as - are not passed)
  *   or: host_sim --sample-map scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32 rgb.f32 m2.f32|- states.u32|-
  *       (the sample-map render, pt_lane<..., VIEWS, SPPMAP>: a batch of views, or with cams - the scene's own camera on the seed
  *       given; map.u32 holds views x W x H sample counts, cap is the most a pixel gets; the planes start at -7.0f, the sums at
@@ -235,7 +239,7 @@ static void run_lanes(const Sim &S, Fn lane) {
         SceneView svw = S.sv;
         SceneCold coldw = S.cold;
         std::vector<uint32_t> q(S.scene->ref.nodes.size() + 8), lock(1, 0u), stack(kLdsStack * kBlock);
-        std::vector<float> focal(3 * kBlock);
+        std::vector<float> focal(4 * kBlock); /* the fourth row: the path-depth render's depth word */
         coldw.bfs_pool = q.data(); coldw.bfs_locks = lock.data(); coldw.bfs_queue_cap = (uint32_t)q.size(); coldw.bfs_queue_count = 1;
         svw.cold = &coldw;
         lane(svw, stack.data(), focal.data(), (uint32_t)w);
@@ -662,6 +666,40 @@ static int light_groups_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W
     print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return write_bytes(a[14], groups.data(), 12 * n * G) && (!want_rgb || write_bytes(a[15], rgb.data(), 12 * n)) &&
            (!want_states || write_bytes(a[16], states.data(), 4 * n)) ? 0 : 1;
+}
+
+/* the path-depth render (ort_render_depths and its views form): what device_render sets up for it, for one simulated lane per
+   thread.  cams - : the single-frame form, the scene's own camera on the seed given where the seeds file stands */
+static int depths_mode(char **a) { /* scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr G bins.f32 rgb.f32|- lengths.u32|- states.u32|- */
+    Sim S;
+    if (int rc = sim_open(S, a[0], a[1], TAB_PRO | TAB_LIGHTS | TAB_MATS)) return rc;
+    SimCameras c;
+    if (!sim_cameras(S, a[2], a[3], a + 4, &c)) return 1;
+    const uint32_t spp = (uint32_t)strtoul(a[10], 0, 10), G = (uint32_t)strtoul(a[12], 0, 10);
+    if (spp == 0u || spp > (1u << 24)) { fprintf(stderr, "spp must be within [1, 1 << 24]\n"); return 1; }
+    if (G == 0u || G > ORT_MAX_DEPTH_BINS) { fprintf(stderr, "G must be within [1, ORT_MAX_DEPTH_BINS]\n"); return 1; }
+    const bool want_rgb = std::string(a[14]) != "-", want_len = std::string(a[15]) != "-", want_states = std::string(a[16]) != "-";
+    const size_t n = c.n;
+    std::vector<float> bins(3 * n * G, -7.0f), rgb(want_rgb ? 3 * n : 0, -7.0f);
+    std::vector<uint32_t> lengths(want_len ? n * G : 0, 0xeeeeeeeeu), states(want_states ? n : 0, 0xddddddddu);
+    ort_render_params &p = c.p;
+    p.spp = spp; p.rr = (float)atof(a[11]);
+    RenderView rv{};
+    render_view(p, plan_pixel_jobs(RK_DEPTHS, sim_traits(S), p, sim_knobs(), c.nv), c.views.data(), nullptr, &rv);
+    rv.out = want_rgb ? rgb.data() : nullptr; rv.final_states = want_states ? states.data() : nullptr;
+    rv.depth_bins = G; rv.depth_out = bins.data(); rv.depth_len = want_len ? lengths.data() : nullptr;
+    rv.views = c.view_tab.data();
+    rv.next_job = S.ctrl; rv.counters = S.ctrl + 1;
+    const RenderHot hot = render_hot<RenderHot>(rv, &rv);
+    auto t0 = std::chrono::steady_clock::now();
+    run_lanes(S, [&](const SceneView &sv, uint32_t *stack, float *focal, uint32_t w) {
+        with_bools([&](auto D, auto T) {
+            pt_lane<LF_COUNTERS | lf_if(decltype(D)::value, LF_DIFFUSE) | lf_if(decltype(T)::value, LF_TABS) | LF_IMPLICIT | LF_VIEWS | LF_DEPTHS>(sv, hot, S.tab, stack, focal, 0, w);
+        }, getenv("SIM_DIFFUSE") != nullptr, S.tab != nullptr);
+    });
+    print_counters(S, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return write_bytes(a[13], bins.data(), 12 * n * G) && (!want_rgb || write_bytes(a[14], rgb.data(), 12 * n)) &&
+           (!want_len || write_bytes(a[15], lengths.data(), 4 * n * G)) && (!want_states || write_bytes(a[16], states.data(), 4 * n)) ? 0 : 1;
 }
 
 /* the sample-map render (ort_render_sample_map and its views form): what device_render sets up for it, for one simulated lane
@@ -1142,6 +1180,7 @@ int main(int argc, char **argv) {
     if (argc == 12 && mode == "--views") return views_mode(argv + 2);
     if (argc == 21 && mode == "--render-adaptive") return render_adaptive_mode(argv + 2);
     if (argc == 19 && mode == "--light-groups") return light_groups_mode(argv + 2);
+    if (argc == 19 && mode == "--depths") return depths_mode(argv + 2);
     if (argc == 18 && mode == "--sample-map") return sample_map_mode(argv + 2);
     if (argc == 20 && mode == "--accumulate") return accumulate_mode(argv + 2);
     if (argc < 10 || mode.rfind("--", 0) == 0) {
@@ -1162,6 +1201,7 @@ int main(int argc, char **argv) {
                         "       host_sim --follow scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr max_bounces albedo.f32|- normal.f32|- depth.f32|- hits.u32|- ids.u32|- bounces.u32|- states.u32|-\n"
                         "       host_sim --matte scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp by slots ids.u32 counts.u32 other.u32|- hits.u32|- states.u32|-\n"
                         "       host_sim --light-groups scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr groups.u8 G groups.f32 rgb.f32|- states.u32|-\n"
+                        "       host_sim --depths scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 spp rr G bins.f32 rgb.f32|- lengths.u32|- states.u32|-\n"
                         "       host_sim --sample-map scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32 rgb.f32 m2.f32|- states.u32|-\n"
                         "       host_sim --accumulate scn base cams.f32|- seeds.u32|seed W H x0 y0 x1 y1 cap rr map.u32|- sum.f32 m2.f32|- count.u32 states.u32 rgb.f32|-\n");
         return 2;

@@ -15,7 +15,7 @@ Exit status 1 if any common kernel differs."""
 import re
 import sys
 
-DEFAULT = r"pt_persistent|pt_adaptive|pt_groups|pt_sample_map|pt_accumulate|wf_|combine_chunks|unit_eval|raycast_rays|occluded_rays|ao_points|feature_pixels|follow_pixels|matte_pixels|radiance_|irradiance_|probe_sh_"  # every kernel family
+DEFAULT = r"pt_persistent|pt_adaptive|pt_groups|pt_sample_map|pt_accumulate|pt_depths|wf_|combine_chunks|unit_eval|raycast_rays|occluded_rays|ao_points|feature_pixels|follow_pixels|matte_pixels|radiance_|irradiance_|probe_sh_"  # every kernel family
 
 
 def kernel_key(sym):

@@ -35,7 +35,7 @@ def pretty(k):
     bools = re.match(r"I((?:Lb[01]E)+)E", k[i:])
     return "::".join(p for p in parts if p != "ort") + ("<" + ",".join(re.findall(r"Lb([01])E", bools.group(1))) + ">" if bools else "")
 for k, v in rows.items():
-    if "pt_persistent" not in k and "wf_" not in k and "raycast_rays" not in k and "occluded_rays" not in k and "ao_points" not in k and "feature_pixels" not in k and "follow_pixels" not in k and "matte_pixels" not in k and "radiance_rays" not in k and "radiance_adaptive_rays" not in k and "irradiance" not in k and "probe_sh" not in k and "pt_adaptive" not in k and "pt_groups" not in k and "pt_sample_map" not in k and "pt_accumulate" not in k: continue
+    if "pt_persistent" not in k and "wf_" not in k and "raycast_rays" not in k and "occluded_rays" not in k and "ao_points" not in k and "feature_pixels" not in k and "follow_pixels" not in k and "matte_pixels" not in k and "radiance_rays" not in k and "radiance_adaptive_rays" not in k and "irradiance" not in k and "probe_sh" not in k and "pt_adaptive" not in k and "pt_groups" not in k and "pt_sample_map" not in k and "pt_accumulate" not in k and "pt_depths" not in k: continue
     print(pretty(k), " ".join("%s=%s" % (a, b) for a, b in v.items()))
 '
 rc=$?

@@ -8,8 +8,8 @@
    follow_view); query=matte with features' arguments: ort_render_matte's (plan_matte, matte_view).  Otherwise
    keys: the SceneTraits and ort_render_params fields by name, policy=pixel|chunk, counters=1, explicit_jobs=1 job_count=N,
    w5_layout_ok=0, views=N (the plan of an ort_render_views batch of N views; its fields are appended to the line), one of
-   adaptive=1, groups=1, sample_map=1, accumulate=1 (plan_pixel_jobs for that kind: the plan of ort_render_adaptive,
-   ort_render_light_groups, ort_render_sample_map or ort_render_accumulate, or with views=N of its views form; the key and the
+   adaptive=1, groups=1, sample_map=1, accumulate=1, depths=1 (plan_pixel_jobs for that kind: the plan of ort_render_adaptive,
+   ort_render_light_groups, ort_render_sample_map, ort_render_accumulate or ort_render_depths, or with views=N of its views form; the key and the
    views fields are appended); fill=1: after the plan, every field of the RenderView that is not a pointer as the shared fill
    (render_view, csrc/ort_setup.h) sets it for that plan, "name = value" one per line -- seed=, rr= are the call's, view_seed=S
    gives view v of views=N the seed S + v, min_spp= max_spp= check_every= tolerance= floor= are the stopping rule's; max_blocks
@@ -47,7 +47,7 @@ struct FillView {
 /* the pixel-job kinds, in the order of their enum, by their key on the command line, which is also their field of the output and
    the name of their kernel family */
 struct PixelJobKey { const char *key; ort::RenderKind kind; };
-static const PixelJobKey kPixelJobKeys[] = {{"adaptive", ort::RK_ADAPTIVE}, {"groups", ort::RK_GROUPS}, {"sample_map", ort::RK_SAMPLE_MAP}, {"accumulate", ort::RK_ACCUMULATE}};
+static const PixelJobKey kPixelJobKeys[] = {{"adaptive", ort::RK_ADAPTIVE}, {"groups", ort::RK_GROUPS}, {"sample_map", ort::RK_SAMPLE_MAP}, {"accumulate", ort::RK_ACCUMULATE}, {"depths", ort::RK_DEPTHS}};
 
 /* "family<counters, diffuse, tabs, implicit, wide>" */
 static std::string variant_name(const ort::KernelVariant &v) {
